@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — ant-steps/s of the AntsRL environment step loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, ages the episode and warms up, times exactly K steps, optionally writes the last timed step's
+outputs (--dump-outputs) and prints the result line.  Everything else it can measure — per-kernel times and the
+roofline figures, the device copy rate, the CPU oracle baseline, the explicit-sweep run, the device reset time, the
+gather's cost and self-check with N > 1 — runs only with --full.
 
 One "step" = RLApi.step + Environment.update (main.py:98 + main.py:131 of the reference) over one
 batch of E environments, through the C-ABI (antsrl_step_update).  Default workload is BASELINE.json
@@ -182,6 +187,33 @@ def reference_cpu_timing(config_name):
         return None
 
 
+#: --dump-outputs: an array of more than this many bytes (as written) is sampled; eight such arrays stay under 64 MB
+DUMP_BYTES_PER_ARRAY = 6 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes `arrays` — (name, device tensor, number of leading axes that index rows: ants or environments) — as
+    out_dir/<name>.npy, float64 tensors as float64 and everything else as float32.  A tensor of more than DUMP_BYTES_PER_ARRAY
+    is written as a sample of its rows: the same rows in every run with the same shape (a seeded generator), their flat
+    indices in out_dir/<name>_rows.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, lead in arrays:
+        wide = t.dtype == torch.float64
+        shape = tuple(t.shape)
+        n_rows = int(np.prod(shape[:lead]))
+        row_bytes = int(np.prod(shape[lead:])) * (8 if wide else 4)
+        if n_rows * row_bytes > DUMP_BYTES_PER_ARRAY:
+            k = max(1, DUMP_BYTES_PER_ARRAY // row_bytes)
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False))
+            idx = np.unravel_index(rows, shape[:lead])
+            t = t[tuple(torch.as_tensor(i, device=t.device) for i in idx)]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64 if wide else torch.float32).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -199,7 +231,16 @@ def main():
                     help="the reference's DIFFUSE_FACTOR (pheromone.py:5-10): 3x3 filter with this weight on the 8 neighbours")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="split the --steps timed steps into this many regions of (nearly) equal length and report the median "
+                         "region (default: 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and roofline figures, the device copy "
+                         "rate, the CPU oracle baseline, the explicit-sweep run, the device reset, the gather's cost and self-check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (observation, agent_state, reward, done, and the "
+                         "in-loop policy's next actions) as DIR/<name>.npy in float32; arrays above %d MiB as a fixed, seeded "
+                         "sample of rows (DIR/<name>_rows.npy: the flat row indices)" % (DUMP_BYTES_PER_ARRAY >> 20))
     ap.add_argument("--act-path", default="auto", choices=["auto", "meta", "kact"],
                     help="AntsCfg.act_path: auto (the library's measured choice), meta (k_move + k_perceive), kact (round 1's "
                          "single kernel) — for A/B runs on one box")
@@ -359,14 +400,16 @@ def main():
         one_step(t)
 
     K = args.steps
-    timing = not args.no_kernel_timing
-    REPEATS = max(1, args.repeats)
+    if K < 1:
+        sys.exit("--steps must be at least 1")
+    timing = args.full and not args.no_kernel_timing
+    REPEATS = max(1, min(K, args.repeats if args.repeats is not None else (5 if args.full else 1)))
+    region_len = [K // REPEATS + (1 if r < K % REPEATS else 0) for r in range(REPEATS)]  # K timed steps in all
     NEV = cm.TIMING_EVENTS
     # per-kernel HIP events on every 10th step only: the event records between two kernels cost
     # ~15 us of stream idle time (rocprof trace) — on every step that would tax `value` by ~5 %, on every 10th by 0.5 %
-    # (100 sampled steps over the default 5 x 200)
     EV_EVERY = 10
-    timed_steps = [(rep, t) for rep in range(REPEATS) for t in range(0, K, EV_EVERY)]  # in EVERY region: the kernel
+    timed_steps = [(rep, t) for rep in range(REPEATS) for t in range(0, region_len[rep], EV_EVERY)]  # in EVERY region: the kernel
     # averages then cover the same launches as the step time (and as a rocprofv3 --stats of the same command)
     evs = HipEvents(NEV * len(timed_steps)) if timing else None
     ev_slot = {rt: i for i, rt in enumerate(timed_steps)}
@@ -402,33 +445,42 @@ def main():
         assert torch.equal(done_all[lo:lo + E].to(torch.uint8), env.done), "rank %d: gathered done rows differ from the local tensor" % rank
         gather_checks += 1
 
-    # REPEATS timed regions of exactly K steps each, every one bracketed by barrier + synchronize on both
-    # sides and reduced with MAX over the ranks; `value` is the MEDIAN region (median of 5),
-    # the spread is reported beside it.
-    region_s, region_local_s = [], []
+    # K timed steps in REPEATS regions of (nearly) equal length, every one bracketed by barrier + synchronize on both
+    # sides and reduced with MAX over the ranks; `value` is the MEDIAN region's time per step (median
+    # of 5, the --full default), the spread is reported beside it.
+    region_s, region_local_s = [], []  # seconds per step of each region
     step_no = args.age + args.warmup
     for rep in range(REPEATS):
         barrier()
         t0 = time.perf_counter()
-        for t in range(K):
+        for t in range(region_len[rep]):
             if timing and t % EV_EVERY == 0:
                 env.set_timing_events([evs.ev[NEV * ev_slot[(rep, t)] + i].value for i in range(NEV)])
             one_step(step_no)
             step_no += 1
         gathered, t_done = barrier()
         el = t_done - t0
-        region_local_s.append(el)  # this rank's own clock, before the MAX over ranks
+        region_local_s.append(el / region_len[rep])  # this rank's own clock, before the MAX over ranks
         if dist is not None:
             tmax = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             el = float(tmax.item())
-        region_s.append(el)
-        check_gather(gathered)
-    elapsed = float(np.median(region_s))
+        region_s.append(el / region_len[rep])
+        if args.full:
+            check_gather(gathered)
+    step_s = float(np.median(region_s))
+    if args.dump_outputs and rank == 0:  # what the last timed step handed its caller (the gathered batch too with N > 1)
+        arrays = [("obs", env.obs, 2)] if want_obs else []
+        arrays += [("agent_state", env.agent_state, 2), ("reward", env.reward, 2), ("done", env.done, 1)]
+        if inloop:
+            arrays += [(n, getattr(env, n), 2) for n in ("next_rotation", "next_pheromone") if getattr(env, n) is not None]
+        if gathered is not None:
+            arrays += [("reward_all", gathered[0], 2), ("done_all", gathered[1], 1)]
+        dump_outputs(args.dump_outputs, arrays)
     # What the gather costs THIS rank per step: a region with it minus a gather-free region of the same rank, once, outside
     # the timed regions (on an 8-GPU node a slow device and a slow collective must be told apart from the line alone).
     gather_overhead_us = None
-    if gather is not None:
+    if gather is not None and args.full:
         KG = max(10, min(K, 50))
         plain = ShardedStepper(env, None, args.gather)
 
@@ -448,7 +500,7 @@ def main():
         if args.gather in ("zero_copy", "inline"):  # (the plain stepper left reward / done on a send slot: harmless, the run is over)
             pass
     pt = getattr(env, "placement_trials", None) if placement else None
-    mine = dict(rank=rank, env_id_base=env_id_base, ms_per_step=float(np.median(region_local_s)) / K * 1e3,
+    mine = dict(rank=rank, env_id_base=env_id_base, ms_per_step=float(np.median(region_local_s)) * 1e3,
                 device=device_identity(torch, local_rank), gather_overhead_us=gather_overhead_us,
                 placement_chosen_ms=(pt["ms_per_step"][pt["chosen"]] if pt else None),
                 placement_default_ms=(pt["ms_per_step"][0] if pt else None))
@@ -511,13 +563,13 @@ def main():
             # (no sweep term with scaled units: that pass does not exist) over the measured step time
             step_bytes = sum(ab[k] for k in kern) * E
             roofline["step_algorithmic_bytes"] = step_bytes
-            roofline["step_achieved"] = round(step_bytes / (elapsed / K) / 1e9, 1)
-            roofline["step_frac"] = round(step_bytes / (elapsed / K) / 1e9 / HBM_PEAK_GBS, 4)
+            roofline["step_achieved"] = round(step_bytes / step_s / 1e9, 1)
+            roofline["step_frac"] = round(step_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4)
             step_traffic = [traffic_rec.get(names[k]) for k in kern]
             if traffic_rec and all(v is not None for v in step_traffic) and not traffic_stale:
                 # (only from counters taken on THIS tree: a stale figure beside a live time would mix two kernels)
                 # real HBM bytes of one whole step (PMC, every kernel of the step) over the measured step time
-                roofline["step_real_traffic_gbs"] = round(sum(step_traffic) / (elapsed / K) / 1e9, 1)
+                roofline["step_real_traffic_gbs"] = round(sum(step_traffic) / step_s / 1e9, 1)
         else:
             roofline = dict(bound="hbm", achieved=None, peak=HBM_PEAK_GBS, unit="GB/s", frac=None, traffic=None)
         if timing and roofline.get("achieved"):
@@ -529,14 +581,14 @@ def main():
             roofline["frac_of_measured_copy"] = round(roofline["achieved"] / copy_gbs, 4)
             roofline["guide_copy_gbs"] = GUIDE_COPY_GBS
             roofline["frac_of_guide_copy"] = round(roofline["achieved"] / GUIDE_COPY_GBS, 4)
-        value = world * E * cfg.n_ants * K / elapsed
+        value = world * E * cfg.n_ants / step_s
         out = {
             "metric": "ant-steps/sec (ants x envs x steps/s), 256^2 grid" if cfg.w == 256 else "ant-steps/sec (ants x envs x steps/s)",
             "value": value, "unit": "ant-steps/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
-            "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": step_s * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64 ant kinematics / f32 grids", "data": "synthetic",
-            "repeats": REPEATS, "ms_per_step_regions": [round(r / K * 1e3, 5) for r in region_s],
-            "ms_per_step_spread": round((max(region_s) - min(region_s)) / K * 1e3, 5),
+            "repeats": REPEATS, "ms_per_step_regions": [round(r * 1e3, 5) for r in region_s],
+            "ms_per_step_spread": round((max(region_s) - min(region_s)) * 1e3, 5),
             "rccl_ranks": (dist.get_world_size() if dist is not None else 1),  # ranks of the process group (one per GPU)
             "collective_backend": (backend if dist is not None else None),   # "nccl" = RCCL; "gloo" = the one-GPU rehearsal
             "gather": ({"mode": args.gather, "algo": args.gather_algo} if dist is not None else None),
@@ -567,10 +619,10 @@ def main():
                        "parallelism": "env-sharded x%d, reward/done all-gather (%s)" % (world, args.gather)},
             "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dict(N=cfg.n_ants, W=cfg.w, H=cfg.h, extra=extra, name=args.config),
                                                cm.make_cfg, synth_init, random_actions)
-    if rank == 0 and out is not None and world == 1 and scaled and not args.no_explicit_sweep and policy is None:
+    if rank == 0 and out is not None and args.full and world == 1 and scaled and not args.no_explicit_sweep and policy is None:
         # The same workload with the per-step sweep kernel forced (SURVEY.md §8(d)'s byte model counts the
         # 2*C*W*H*4 + W*H sweep term, which the scaled units never move): a short run of its own so that the
         # model can be checked like for like.  Outside the timed region.
@@ -602,7 +654,7 @@ def main():
                                      note="same workload with ANTSRL_PHERO_EXPLICIT_SWEEP: the configuration SURVEY.md "
                                           "§8(d)'s 1 865 728 B/env-step model describes")
         env = env_x
-    if rank == 0 and out is not None:
+    if rank == 0 and out is not None and args.full:
         # device-side episode reset (antsrl_generate), outside the timed region: how long a whole-batch
         # "EnvironmentGenerator.generate" takes on the GPU
         torch.cuda.synchronize(dev)

@@ -17,6 +17,6 @@ if [ "$1" = build ]; then
 fi
 shift; A=$1; B=$2; N=${3:-3}; shift 3
 for i in $(seq $N); do for v in $A $B; do
-  ANTSRL_LIB=$V/$v.so python3 $R/bench.py --steps 200 --warmup 20 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
+  ANTSRL_LIB=$V/$v.so python3 $R/bench.py --full --steps 1000 --warmup 20 --no-cpu-baseline "$@" 2>/dev/null | python3 -c "
 import sys, json; d=json.loads(sys.stdin.read()); print('%-8s ms/step=%.4f %s' % ('$v', d['ms_per_step'], d['roofline']['kernel_ms']))" || exit 1
 done; done

@@ -6,12 +6,14 @@
 # the same steady regime.
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
+export PROFILE_OUT=${PROFILE_OUT:-$R/profile_out}  # the raw output of every pass (read by summarize.py; pmc_pass.sh writes there too)
+O=$PROFILE_OUT; mkdir -p $O
 for c in ${CONFIGS:-c3}; do
   cd /tmp
-  rm -rf $R/gpurun_out/prof_$c
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_$c -- \
-      python3 $R/bench.py --config $c --steps 100 --repeats 2 --no-cpu-baseline --no-explicit-sweep > $R/gpurun_out/bench_${c}_rocprof.json 2> $R/gpurun_out/prof_$c.err
-  tail -c 700 $R/gpurun_out/bench_${c}_rocprof.json; echo
+  rm -rf $O/prof_$c
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -- \
+      python3 $R/bench.py --full --config $c --steps 200 --repeats 2 --no-cpu-baseline --no-explicit-sweep > $O/bench_${c}_rocprof.json 2> $O/prof_$c.err
+  tail -c 700 $O/bench_${c}_rocprof.json; echo
   BENCH_ARGS="--config $c" bash $R/profiles/pmc_pass.sh ${c}_fetch FETCH_SIZE | grep "k_perceive\|k_move\|k_update\|k_act\|k_sweep\|k_policy"
   BENCH_ARGS="--config $c" bash $R/profiles/pmc_pass.sh ${c}_write WRITE_SIZE | grep "k_perceive\|k_move\|k_update\|k_act\|k_sweep\|k_policy"
 done

@@ -1,17 +1,19 @@
 #!/bin/bash
 # Usage (on the GPU box, via gpurun):  bash profiles/pmc_pass.sh <tag> <counter> [<counter> ...]
 # One rocprofv3 --pmc pass (counters in their own run, with --kernel-trace only) over a short bench.
-# Prints the per-kernel mean of every counter (last 15 launches) and leaves the csv under gpurun_out/pmc_<tag>.
+# Prints the per-kernel mean of every counter (last 15 launches) and leaves the csv under $PROFILE_OUT/pmc_<tag>
+# (default: profile_out/ in the repository).
 set -e
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
+O=${PROFILE_OUT:-$R/profile_out}; mkdir -p $O
 tag=$1; shift
-rm -rf $R/gpurun_out/pmc_$tag
+rm -rf $O/pmc_$tag
 cd /tmp
-timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $R/gpurun_out/pmc_$tag -- \
-    python3 $R/bench.py --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-kernel-timing --no-explicit-sweep ${BENCH_ARGS} > $R/gpurun_out/pmc_$tag.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$tag -- \
+    python3 $R/bench.py --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --no-kernel-timing --no-explicit-sweep ${BENCH_ARGS} > $O/pmc_$tag.log 2>&1
 # what the counters were taken ON: the kernel sources' hash and the device (bench.py flags stale figures by the hash)
-python3 - $R $R/gpurun_out/pmc_$tag.meta.json <<'PY'
+python3 - $R $O/pmc_$tag.meta.json <<'PY'
 import json, subprocess, sys
 sys.path.insert(0, sys.argv[1])
 from antsrl_amd.build import source_hash
@@ -21,7 +23,7 @@ except Exception:
     uid = None
 json.dump(dict(source_sha16=source_hash(), device=uid), open(sys.argv[2], "w"))
 PY
-python3 - $R/gpurun_out/pmc_$tag <<'PY'
+python3 - $O/pmc_$tag <<'PY'
 import collections, csv, glob, sys
 fs = sorted(glob.glob(sys.argv[1] + "/*/*_counter_collection.csv"))
 agg = collections.defaultdict(list)

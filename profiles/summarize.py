@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condenses the rocprofv3 output of profiles/final_passes.sh (under gpurun_out/) into the tracked files:
+"""Condenses the rocprofv3 output of profiles/final_passes.sh (under $PROFILE_OUT, default profile_out/) into the tracked files:
 
     python profiles/summarize.py r03
 
@@ -17,26 +17,27 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RAW = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out"))
 rnd = sys.argv[1]
 out = os.path.join(ROOT, "profiles", rnd)
 os.makedirs(out, exist_ok=True)
 summary = {}
 for cfg in ("c3", "c2", "c4", "c5"):
-    st = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "prof_%s" % cfg, "*", "*_kernel_stats.csv")), key=os.path.getmtime)
+    st = sorted(glob.glob(os.path.join(RAW, "prof_%s" % cfg, "*", "*_kernel_stats.csv")), key=os.path.getmtime)
     if st:
         rows = list(csv.reader(open(st[-1])))
         keep = [rows[0]] + [r for r in rows[1:] if r[0].lstrip("void ").startswith("k_")]
         csv.writer(open(os.path.join(out, "kernel_stats_%s.csv" % cfg), "w")).writerows(keep)
-    # the same trace restricted to the TIMED regions of the profiled bench run (its last steps x repeats launches of every
+    # the same trace restricted to the TIMED regions of the profiled bench run (its last `steps` launches of every
     # step kernel): rocprofv3's own stats average over the whole process, i.e. also over the 400 ageing steps whose first
     # ~150 are the faster start-of-episode transient — this file is the one to compare with the bench line's kernel_ms
-    tr = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "prof_%s" % cfg, "*", "*_kernel_trace.csv")), key=os.path.getmtime)
-    bl = os.path.join(ROOT, "gpurun_out", "bench_%s_rocprof.json" % cfg)
+    tr = sorted(glob.glob(os.path.join(RAW, "prof_%s" % cfg, "*", "*_kernel_trace.csv")), key=os.path.getmtime)
+    bl = os.path.join(RAW, "bench_%s_rocprof.json" % cfg)
     if tr and os.path.exists(bl):
         try:
             line = [l for l in open(bl) if l.startswith("{")][-1]
             rec = json.loads(line)
-            n_timed = int(rec["steps"]) * int(rec.get("repeats", 1))
+            n_timed = int(rec["steps"])  # (all regions together)
             durs = collections.defaultdict(list)
             for r in csv.DictReader(open(tr[-1])):
                 k = r["Kernel_Name"].replace("void ", "")
@@ -56,7 +57,7 @@ for cfg in ("c3", "c2", "c4", "c5"):
             print("timed stats of %s: %s" % (cfg, e))
     per = {}
     for cname in ("fetch", "write"):
-        fs = sorted(glob.glob(os.path.join(ROOT, "gpurun_out", "pmc_%s_%s" % (cfg, cname), "*", "*_counter_collection.csv")), key=os.path.getmtime)
+        fs = sorted(glob.glob(os.path.join(RAW, "pmc_%s_%s" % (cfg, cname), "*", "*_counter_collection.csv")), key=os.path.getmtime)
         if not fs:
             continue
         agg = collections.defaultdict(list)
@@ -74,7 +75,7 @@ for cfg in ("c3", "c2", "c4", "c5"):
         traffic = {k: int((2 * d["FETCH_SIZE"] + d["WRITE_SIZE"]) * 1024) for k, d in per.items() if "FETCH_SIZE" in d and "WRITE_SIZE" in d}
         metas = []
         for cname in ("fetch", "write"):
-            mp = os.path.join(ROOT, "gpurun_out", "pmc_%s_%s.meta.json" % (cfg, cname))
+            mp = os.path.join(RAW, "pmc_%s_%s.meta.json" % (cfg, cname))
             if os.path.exists(mp):
                 metas.append(json.load(open(mp)))
         if metas and all(m == metas[0] for m in metas):  # (both passes on one tree and one device)

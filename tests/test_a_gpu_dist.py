@@ -87,8 +87,8 @@ def test_bench_py_with_two_ranks_on_one_gpu():
     E, repeats = 96, 2   # (96 envs x 512 ants: the outputs are past vmm.SMALL_BYTES, so the placement tuner really runs)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", ANTSRL_BENCH_BACKEND="gloo", ANTSRL_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--age", "30", "--repeats", str(repeats), "--envs", str(E)]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20",
+           "--warmup", "5", "--age", "30", "--repeats", str(repeats), "--envs", str(E)]
     out = _run(cmd, env)
     assert out.returncode == 0, out.stdout[-6000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
