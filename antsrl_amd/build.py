@@ -16,9 +16,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libantsrl_hip.so")
-#: the same sources with -DANTSRL_PROFILING: A/B selectors, ablation flags and the k_act phase trace exist in this
-#: library only (profiles/*.sh, tests/alt_paths.sh load it through ANTSRL_LIB); the product library has none
-PROF_LIB_PATH = os.path.join(LIB_DIR, "libantsrl_hip_prof.so")
 SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl_sweep.hip", "antsrl_state.hip",
            "antsrl_capi.hip", "antsrl_policy.hip", "antsrl_mem.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
@@ -59,12 +56,13 @@ def is_stale(path: str = LIB_PATH) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(out: str, extra, verbose: bool) -> None:
+def build_hip(force: bool = False, verbose: bool = False) -> str:
     """One hipcc process per source (they are independent translation units), then one link."""
-    os.makedirs(LIB_DIR, exist_ok=True)
-    objdir = os.path.join(os.path.dirname(out), "obj_" + os.path.splitext(os.path.basename(out))[0])  # (object files never travel: .gpurunignore)
+    if not force and not is_stale():
+        return LIB_PATH
+    objdir = os.path.join(LIB_DIR, "obj_libantsrl_hip")
     os.makedirs(objdir, exist_ok=True)
-    flags = [f for f in FLAGS if f != "-shared"] + list(extra)
+    flags = [f for f in FLAGS if f != "-shared"]
     procs = []
     for src in SOURCES:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
@@ -77,38 +75,9 @@ def _compile(out: str, extra, verbose: bool) -> None:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
         objs.append(obj)
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", out])
-
-
-def build_hip(force: bool = False, verbose: bool = False) -> str:
-    if not force and not is_stale():
-        return LIB_PATH
-    _compile(LIB_PATH, [], verbose)
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-o", LIB_PATH])
     return LIB_PATH
 
 
-def build_prof(force: bool = False, verbose: bool = False) -> str:
-    """libantsrl_hip_prof.so: the profiling build (A/B selectors, ablations, phase trace)."""
-    if not force and not is_stale(PROF_LIB_PATH):
-        return PROF_LIB_PATH
-    _compile(PROF_LIB_PATH, ["-DANTSRL_PROFILING"], verbose)
-    return PROF_LIB_PATH
-
-
-def build_variant(name: str, defines, verbose: bool = False) -> str:
-    """lib/variants/<name>.so: the profiling build plus extra -D switches (compile-time ablations and A/B
-    variants for profiles/*.sh; loaded through ANTSRL_LIB)."""
-    out = os.path.join(LIB_DIR, "variants", name + ".so")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    _compile(out, ["-DANTSRL_PROFILING"] + list(defines), verbose)
-    return out
-
-
 if __name__ == "__main__":
-    if "--variant" in sys.argv:  # python -m antsrl_amd.build --variant NAME -DFOO -DBAR=1
-        i = sys.argv.index("--variant")
-        print(build_variant(sys.argv[i + 1], [a for a in sys.argv[i + 2:] if a.startswith("-D")], verbose=True))
-        sys.exit(0)
     print(build_hip(force="--force" in sys.argv, verbose=True))
-    if "--prof" in sys.argv:
-        print(build_prof(force="--force" in sys.argv, verbose=True))

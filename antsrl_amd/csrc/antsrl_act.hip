@@ -60,6 +60,7 @@ __host__ __device__ __forceinline__ ActOff act_offsets(int N, int PP, int words,
     // (it stages a group's rows back to back)
     const size_t rowf = (size_t)PP * K;
     const size_t stride = ((PP <= 64 && rowf <= 368 ? 2 * rowf : rowf) + 3 + 3) / 4 * 4;
+    // (the update-scratch term stays although k_act no longer runs the update: it decides which ActPlan is picked)
     const size_t hash_b = update_scratch_bytes(HT, R, nwaves), stage_b = 4 * (size_t)nwaves * stride;
     o.uni = take(hash_b > stage_b ? hash_b : stage_b);
     o.stride = (uint32_t)stride;
@@ -80,37 +81,6 @@ __host__ __device__ __forceinline__ size_t act_lds_bytes(int N, int PP, int word
 #define LAYOUT_DEFAULT 1       // [Ants, Phero0, Phero1, Anthill, Walls, Food]   (generator order)
 #define LAYOUT_DEFAULT_ROCKS 2 // ... + [CircleObstacles]
 
-// Profiling build only (-DANTSRL_PROFILING, ANTSRL_ABLATE bit ACT_ABL_TRACE): per-workgroup phase timeline of
-// k_act.  Slot k of workgroup e = s_memrealtime (100 MHz) at: 0 entry, 1 after phase 2, 2 after phase 3,
-// 3 exit; slot 4 = HW_ID, slot 5 = XCC_ID, slot 6 after phase 0, slot 7 after phase 1.  Read back with
-// antsrl_debug_read_act_trace (exported by libantsrl_hip_prof.so only).
-#ifdef ANTSRL_PROFILING
-#define ACT_TRACE_SLOTS 8
-#define ACT_TRACE_MAX_WG 8192
-__device__ unsigned long long g_act_trace[ACT_TRACE_SLOTS * ACT_TRACE_MAX_WG];
-
-__device__ __forceinline__ void act_trace(int flags, int e, int tid, int slot)
-{
-    if ((flags & ACT_ABL_TRACE) && tid == 0 && e < ACT_TRACE_MAX_WG) {
-        g_act_trace[e * ACT_TRACE_SLOTS + slot] = wall_clock64();
-        if (slot == 0) {
-            g_act_trace[e * ACT_TRACE_SLOTS + 4] = __builtin_amdgcn_s_getreg(4 | (31 << 11));  // HW_REG_HW_ID
-            g_act_trace[e * ACT_TRACE_SLOTS + 5] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); // HW_REG_XCC_ID
-        }
-    }
-}
-
-extern "C" int antsrl_debug_read_act_trace(unsigned long long *dst, int n_wg)
-{
-    if (!dst || n_wg < 0 || n_wg > ACT_TRACE_MAX_WG) return ANTSRL_E_INVALID;
-    if (hipDeviceSynchronize() != hipSuccess) return ANTSRL_E_DEVICE;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_act_trace), sizeof(unsigned long long) * ACT_TRACE_SLOTS * (size_t)n_wg)
-                   == hipSuccess ? ANTSRL_OK : ANTSRL_E_DEVICE;
-}
-#else
-__device__ __forceinline__ void act_trace(int, int, int, int) {}
-#endif
-
 // FAST selects the software-pipelined perception loop (see phase 3); the two loops live in
 // separate instantiations on purpose: with both in one kernel the optimiser stops scalarising the
 // LDS carve (`ActLds`), its pointers go through scratch and every LDS access degrades to flat_*.
@@ -122,7 +92,7 @@ template <int C, bool STATIC_LDS, int LAYOUT, bool FAST, int TPB, bool OBS16 = f
 __global__ void __launch_bounds__(TPB, 4)
 k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict__ phero_act, const int cur,
       float *__restrict__ obs, float *__restrict__ agent_state, float *__restrict__ reward,
-      uint8_t *__restrict__ done, const int flags, const double *__restrict__ wall_jitter, const int out_buf)
+      uint8_t *__restrict__ done, const int flags)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int e = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
@@ -165,7 +135,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
     const bool explore = p.explore_on != 0;
     const uint8_t primed0 = p.s.reward_primed[e];
 
-    act_trace(flags, e, tid, 0);
     // With one ant per thread (N <= T: the reference's sizes) every independent global load of the ant is
     // issued HERE, ahead of the bitmap staging and the first barrier, and the phases below use the
     // registers: otherwise each phase starts with a dependent round trip to HBM behind a barrier
@@ -232,7 +201,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
             L.hvals[h] = 0u;
         }
     __syncthreads();
-    act_trace(flags, e, tid, 6);
 
     if (do_step) {
         // ---- phase 1a: mandible target (RL_api.py:178-185) + Ants.update_mandibles reads
@@ -283,7 +251,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
         }
         __syncthreads();
     }
-    act_trace(flags, e, tid, 7);
 
     // ---- phase 2: activation, rotate, move (RL_api.py:187-196) and the perception frame
     const double margin = (double)p.r * p.delta * 1.4142135623730951 + 1.5;
@@ -346,7 +313,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
         L.rockmask[i] = rm;
     }
     __syncthreads();
-    act_trace(flags, e, tid, 1);
 
     // ---- phase 3: perception gather, RL_api.py:109-148.  One WAVE per ant, one LANE per perceived
     //      cell (49 of 64 lanes at the reference's 7x7): the cell's offsets, mask bit and output slot
@@ -357,12 +323,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
     const float inv_max = 1.0f / (float)p.max_val;
     const float g_now = (float)p.g_now;                       // scaled mode: v = u * f0^S ...
     const float cut = p.scaled ? (float)p.threshold : 0.0f;   // ... and 0 below the 0.01 cut
-#ifdef ANTSRL_PROFILING
-    const bool abl_gather = flags & ACT_ABL_NO_GATHER, abl_store = flags & ACT_ABL_NO_STORE;
-    const bool abl_explore = flags & ACT_ABL_NO_EXPLORE, abl_items = flags & ACT_ABL_NO_ITEMS;
-#else
-    constexpr bool abl_gather = false, abl_store = false, abl_explore = false, abl_items = false;
-#endif
     const int npass = (PP + 63) >> 6;
     const uint32_t row = (uint32_t)PP * (uint32_t)K;            // floats per ant
     float *stage = L.stage + (size_t)wave * L.stage_stride;
@@ -450,7 +410,7 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
                 const bool real = (i0 + u < i_end) && lane < PP; // clamped duplicates must not count twice
                 const uint32_t cl = c_cell[u];
                 const uint32_t wd = cl >> 5, bit = 1u << (cl & 31);
-                if (real && explore && !abl_explore && !(L.b_old[wd] & bit)) { // reward_custom.py:19,22 (mask ignored)
+                if (real && explore && !(L.b_old[wd] & bit)) { // reward_custom.py:19,22 (mask ignored)
                     atomicAdd(&L.cnt[i], 1u);
                     atomicOr(&g_expl[wd], bit); // marks go straight to HBM: every count uses the LDS copy of the pre-step map
                 }
@@ -571,7 +531,7 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
     // wave works on a single ant at a time (the second slot of the group stays empty).
     const int ustep = npass > 1 ? 1 : ACT_UNROLL;
     if (!FAST)
-    for (int i0 = wave * ustep; i0 < (abl_items ? 0 : N); i0 += nwaves * ustep) {
+    for (int i0 = wave * ustep; i0 < N; i0 += nwaves * ustep) {
         for (int pass = 0; pass < npass; ++pass) {
             const int q = pass * 64 + lane;
             const bool lane_on = q < PP;
@@ -606,7 +566,7 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
                 fd[u] = 0.0f;
 #pragma unroll
                 for (int c = 0; c < C; ++c) pv[u][c] = 0.0f;
-                if (vis[u] && !abl_gather) {
+                if (vis[u]) {
                     if (C == 2) {
                         const float2 t = *reinterpret_cast<const float2 *>(ph + (size_t)cell[u] * PS);
                         pv[u][0] = t.x; pv[u][C - 1] = t.y;
@@ -632,7 +592,7 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
                 if (i >= N || u >= ustep) break; // wave-uniform
                 const uint32_t cl = cell[u];
                 const uint32_t wd = cl >> 5, bit = 1u << (cl & 31);
-                if (valid[u] && explore && !abl_explore && !(L.b_old[wd] & bit)) { // reward_custom.py:19,22
+                if (valid[u] && explore && !(L.b_old[wd] & bit)) { // reward_custom.py:19,22
                     atomicAdd(&L.cnt[i], 1u);                                       // (mask ignored)
                     atomicOr(&g_expl[wd], bit); // marks go straight to HBM: every count uses the LDS copy of the pre-step map
                 }
@@ -693,20 +653,18 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
                 }
                 if (pass == npass - 1) { // the ant's row is complete: copy it out
                     wave_lds_sync();
-                    if (!abl_store) {
-                        float *dst_al = dst - mis; // 16-byte aligned window [mis, mis + row)
-                        const uint32_t n4 = (mis + row + 3) >> 2;
-                        for (uint32_t j = lane; j < n4; j += 64) {
-                            const float4 v = reinterpret_cast<const float4 *>(stage)[j];
-                            const uint32_t lo = 4 * j;
-                            if (lo >= mis && lo + 3 < mis + row) {
-                                store_stream(reinterpret_cast<float4 *>(dst_al) + j, v);
-                            } else {
-                                if (lo + 0 >= mis && lo + 0 < mis + row) store_stream(dst_al + lo + 0, v.x);
-                                if (lo + 1 >= mis && lo + 1 < mis + row) store_stream(dst_al + lo + 1, v.y);
-                                if (lo + 2 >= mis && lo + 2 < mis + row) store_stream(dst_al + lo + 2, v.z);
-                                if (lo + 3 >= mis && lo + 3 < mis + row) store_stream(dst_al + lo + 3, v.w);
-                            }
+                    float *dst_al = dst - mis; // 16-byte aligned window [mis, mis + row)
+                    const uint32_t n4 = (mis + row + 3) >> 2;
+                    for (uint32_t j = lane; j < n4; j += 64) {
+                        const float4 v = reinterpret_cast<const float4 *>(stage)[j];
+                        const uint32_t lo = 4 * j;
+                        if (lo >= mis && lo + 3 < mis + row) {
+                            store_stream(reinterpret_cast<float4 *>(dst_al) + j, v);
+                        } else {
+                            if (lo + 0 >= mis && lo + 0 < mis + row) store_stream(dst_al + lo + 0, v.x);
+                            if (lo + 1 >= mis && lo + 1 < mis + row) store_stream(dst_al + lo + 1, v.y);
+                            if (lo + 2 >= mis && lo + 2 < mis + row) store_stream(dst_al + lo + 2, v.z);
+                            if (lo + 3 >= mis && lo + 3 < mis + row) store_stream(dst_al + lo + 3, v.w);
                         }
                     }
                     wave_lds_sync();
@@ -715,7 +673,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
         }
     }
     __syncthreads();
-    act_trace(flags, e, tid, 2);
 
     // ---- phase 4: agent_state (RL_api.py:160-162), reward.observation hooks, give_reward
     for (int i = tid; i < N; i += T) {
@@ -759,13 +716,6 @@ k_act(const KP p, const int8_t *__restrict__ rotation, const int8_t *__restrict_
         if (p.reward_kind != ANTSRL_REWARD_NONE) p.s.reward_primed[e] = 1;
         if (do_step && done) done[e] = (uint8_t)(p.max_time == p.s.timestep[e]); // RL_api.py:200
     }
-    act_trace(flags, e, tid, 3);
-    if (flags & ACT_FUSED_UPDATE) {
-        // Environment.update of the same step (main.py:131) in the same launch: the staging
-        // region is dead after phase 3 and doubles as the update's scratch.
-        __syncthreads();
-        update_env<C>(p, e, wall_jitter, out_buf, (unsigned char *)L.hkeys);
-    }
 }
 
 // ===================================================================================
@@ -784,7 +734,6 @@ struct ActPlan {
 // throughput either) and one 1024-thread workgroup (0.306-0.315 ms).  So: bitmaps in
 // LDS at 3 then 2 workgroups per CU, only then the global-bitmap plans, then one 1024-thread
 // workgroup, then 512 threads with the whole CU's LDS.
-// ANTSRL_ACT_PLAN=<n> pins candidate n (A/B runs, profiling build only).
 static ActPlan plan_act(const KP &p)
 {
     const size_t cap = 160 * 1024;
@@ -792,7 +741,6 @@ static ActPlan plan_act(const KP &p)
         {512, true, cap / 3},  {512, true, cap / 2},  {512, false, cap / 3}, {512, false, cap / 2},
         {1024, true, cap},     {1024, false, cap},    {512, false, cap},
     };
-    static const int pin = PROF_ENV("ANTSRL_ACT_PLAN") ? atoi(PROF_ENV("ANTSRL_ACT_PLAN")) : -1;
     ActPlan pl{};
     // A batch that leaves half the CUs without a workgroup (E <= CUs / 2) with at least 512 ants per env:
     // one 1024-thread workgroup per env puts twice the waves on the env's perception (c3's envs at
@@ -803,27 +751,24 @@ static ActPlan plan_act(const KP &p)
             n = 256;
         return n;
     }();
-    if (pin < 0 && (long)p.E * 2 <= n_cus && p.N >= 512) {
+    if ((long)p.E * 2 <= n_cus && p.N >= 512) {
         for (bool st : {true, false}) {
             pl.threads = 1024; pl.static_lds = st;
             pl.lds = act_lds_bytes(p.N, p.PP, p.words, p.HT, p.K, 16, st, nullptr, nullptr, p.R);
             if (pl.lds <= cap) return pl;
         }
     }
-    int k = 0;
     for (const auto &c : cand) {
         pl.threads = c.threads;
         pl.static_lds = c.st;
         pl.lds = act_lds_bytes(p.N, p.PP, p.words, p.HT, p.K, c.threads / 64, c.st, nullptr, nullptr, p.R);
-        if (pin >= 0 ? k == pin : pl.lds <= c.limit) return pl;
-        ++k;
+        if (pl.lds <= c.limit) return pl;
     }
-    if (pin < 0) { // nothing fits with the grid's bit maps in LDS: keep them in HBM
-        for (size_t limit : {cap / 2, cap}) {
-            pl.threads = 512; pl.static_lds = false; pl.big = true;
-            pl.lds = act_lds_bytes(p.N, p.PP, p.words, p.HT, p.K, 8, false, nullptr, nullptr, p.R, true);
-            if (pl.lds <= limit) return pl;
-        }
+    // nothing fits with the grid's bit maps in LDS: keep them in HBM
+    for (size_t limit : {cap / 2, cap}) {
+        pl.threads = 512; pl.static_lds = false; pl.big = true;
+        pl.lds = act_lds_bytes(p.N, p.PP, p.words, p.HT, p.K, 8, false, nullptr, nullptr, p.R, true);
+        if (pl.lds <= limit) return pl;
     }
     return pl; // caller checks pl.lds <= cap
 }
@@ -842,7 +787,7 @@ static int act_layout(const KP &p)
 template <int C, bool ST, int LAYOUT, bool FAST, int TPB, bool OBS16 = false, bool ILV = false, bool BIG = false>
 static hipError_t launch_act_t(const KP &p, const ActPlan &pl, const int8_t *rot, const int8_t *ph, int cur,
                                float *obs, float *agent_state, float *reward, uint8_t *done, int flags,
-                               const double *jitter, int out_buf, hipStream_t st)
+                               hipStream_t st)
 {
     // dynamic-LDS opt-in is per kernel function AND per device: set once per size on each device
     static size_t attr_lds[ANTSRL_MAX_DEVICES] = {};
@@ -855,39 +800,37 @@ static hipError_t launch_act_t(const KP &p, const ActPlan &pl, const int8_t *rot
         attr_lds[dev] = pl.lds;
     }
     hipLaunchKernelGGL((k_act<C, ST, LAYOUT, FAST, TPB, OBS16, ILV, BIG>), dim3(p.E), dim3(TPB), pl.lds, st, p, rot, ph, cur, obs,
-                       agent_state, reward, done, flags, jitter, out_buf);
+                       agent_state, reward, done, flags);
     return hipGetLastError();
 }
 
 template <int C, bool ST, int LAYOUT, bool FAST, bool OBS16 = false, bool ILV = false>
 static hipError_t launch_act_k(const KP &p, const ActPlan &pl, const int8_t *rot, const int8_t *ph, int cur,
                                float *obs, float *agent_state, float *reward, uint8_t *done, int flags,
-                               const double *jitter, int out_buf, hipStream_t st)
+                               hipStream_t st)
 {
     if (pl.threads == 1024)
         return launch_act_t<C, ST, LAYOUT, FAST, 1024, OBS16, ILV>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags,
-                                                       jitter, out_buf, st);
-    return launch_act_t<C, ST, LAYOUT, FAST, 512, OBS16, ILV>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, jitter,
-                                                  out_buf, st);
+                                                       st);
+    return launch_act_t<C, ST, LAYOUT, FAST, 512, OBS16, ILV>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, st);
 }
 
 template <int C>
 static hipError_t launch_act_c(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
                                float *agent_state, float *reward, uint8_t *done, int flags,
-                               const double *jitter, int out_buf, hipStream_t st)
+                               hipStream_t st)
 {
     const ActPlan pl = plan_act(p);
     if (pl.lds > 160 * 1024) return hipErrorInvalidValue;
     const int layout = (C == 2) ? act_layout(p) : LAYOUT_GENERIC;
     const uint32_t row = (uint32_t)p.PP * p.K;
     // the pipelined loop: one pass (PP <= 64), row of 8..368 floats (a group of two rows leaves in three
-    // 16-byte stores per lane), observation wanted, no ablation
-    const bool fast = C == 2 && layout != LAYOUT_GENERIC && p.PP <= 64 && row >= 8 && row <= 368 && obs &&
-                      !(flags & 0x700) && !pl.big; // (ACT_ABL_NO_EXPLORE is honoured by the pipelined loop too)
+    // 16-byte stores per lane), observation wanted
+    const bool fast = C == 2 && layout != LAYOUT_GENERIC && p.PP <= 64 && row >= 8 && row <= 368 && obs && !pl.big;
 #define ACT_GO(ST, LY, FA) \
-    return launch_act_k<C, ST, LY, FA>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st)
+    return launch_act_k<C, ST, LY, FA>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, st)
 #define ACT_GOF(ST, LY, O16, IL) \
-    return launch_act_k<C, ST, LY, true, O16, IL>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st)
+    return launch_act_k<C, ST, LY, true, O16, IL>(p, pl, rot, ph, cur, obs, agent_state, reward, done, flags, st)
     // the pipelined loop is specialised on the observation format and on the cell record (DState::phero)
 #define ACT_FAST(ST, LY)                                                                          \
     {                                                                                             \
@@ -898,7 +841,7 @@ static hipError_t launch_act_c(const KP &p, const int8_t *rot, const int8_t *ph,
     if (o16 && (!fast || C != 2 || row < 16)) return hipErrorNotSupported; // bfloat16 observations: pipelined loop only
     if (pl.big) // generic loop, generic channel selection, 512 threads
         return launch_act_t<C, false, LAYOUT_GENERIC, false, 512, false, false, true>(p, pl, rot, ph, cur, obs, agent_state, reward,
-                                                                                      done, flags, jitter, out_buf, st);
+                                                                                      done, flags, st);
     if constexpr (C == 2) {
         if (layout != LAYOUT_GENERIC) {
             if (layout == LAYOUT_DEFAULT) {
@@ -919,13 +862,13 @@ static hipError_t launch_act_c(const KP &p, const int8_t *rot, const int8_t *ph,
 
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
                              float *agent_state, float *reward, uint8_t *done, int flags,
-                             const double *jitter, int out_buf, hipStream_t st)
+                             hipStream_t st)
 {
     switch (p.C) {
-    case 1: return launch_act_c<1>(p, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st);
-    case 2: return launch_act_c<2>(p, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st);
-    case 3: return launch_act_c<3>(p, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st);
-    case 4: return launch_act_c<4>(p, rot, ph, cur, obs, agent_state, reward, done, flags, jitter, out_buf, st);
+    case 1: return launch_act_c<1>(p, rot, ph, cur, obs, agent_state, reward, done, flags, st);
+    case 2: return launch_act_c<2>(p, rot, ph, cur, obs, agent_state, reward, done, flags, st);
+    case 3: return launch_act_c<3>(p, rot, ph, cur, obs, agent_state, reward, done, flags, st);
+    case 4: return launch_act_c<4>(p, rot, ph, cur, obs, agent_state, reward, done, flags, st);
     default: return hipErrorInvalidValue;
     }
 }

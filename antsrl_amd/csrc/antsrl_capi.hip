@@ -15,8 +15,7 @@
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
-                             float *agent_state, float *reward, uint8_t *done, int flags,
-                             const double *jitter, int out_buf, hipStream_t st);
+                             float *agent_state, float *reward, uint8_t *done, int flags, hipStream_t st);
 bool antsrl_act_fits(const KP &p);
 bool antsrl_act_needs_hbm_maps(const KP &p);
 hipError_t antsrl_launch_sweep(const KP &p, int cur, hipStream_t st);
@@ -157,11 +156,10 @@ static bool use_scaled(const AntsCfg *c)
 // Interleaved cell record {p0, p1, food, pad}: with scaled units there is no per-step sweep whose traffic the
 // wider record would inflate, and a perception becomes ONE 16-byte gather per cell instead of an 8-byte
 // and a 4-byte one (profiles/history/obs_write_probe.hip: 48-57 cycles per ant per CU against 70-77 on L2 hits,
-// 180-197 against 275 from HBM).  ANTSRL_NO_INTERLEAVE keeps the separate arrays (A/B).
+// 180-197 against 275 from HBM).  Any other configuration keeps separate pheromone and food arrays.
 static bool use_interleaved(const AntsCfg *c)
 {
-    static const bool off = PROF_ENV("ANTSRL_NO_INTERLEAVE") != nullptr;
-    return !off && use_scaled(c) && c->n_phero == 2;
+    return use_scaled(c) && c->n_phero == 2;
 }
 
 // Carves the workspace; with base == NULL only computes the size.
@@ -269,7 +267,7 @@ static void fill_kp(const AntsCfg *c, KP *p)
         // rounding, and unbiased like the hi + lo split of the full filter.
         const int S = 2 * c->filter_radius + 1;
         p->filter_sep = 0;
-        if (S > 1 && !PROF_ENV("ANTSRL_NO_SEPARABLE")) {
+        if (S > 1) {
             int i0 = 0, j0 = 0;
             double big = 0.0;
             for (int a = 0; a < S; ++a)
@@ -304,10 +302,10 @@ static void fill_kp(const AntsCfg *c, KP *p)
     // 16.2 against 30.1 — profiles/r02/tiny_ab.txt.)
     p->meta = antsrl_meta_supported(*p) && c->act_path != ANTSRL_ACT_SINGLE_KERNEL ? 1 : 0;
     if (p->meta && p->fs == 1) p->fs = 2;
-    // 2 x 4-cell blocks per line for the interleaved records (antsrl_device.h: KP::tiled); ANTSRL_NO_TILED: A/B (profiling build)
-    p->tiled = (p->meta && p->ps == 4 && p->fs == 4 && (c->w & 1) == 0 && (c->h & 3) == 0 && !PROF_ENV("ANTSRL_NO_TILED")) ? 1 : 0;
+    // 2 x 4-cell blocks per line for the interleaved records (antsrl_device.h: KP::tiled)
+    p->tiled = (p->meta && p->ps == 4 && p->fs == 4 && (c->w & 1) == 0 && (c->h & 3) == 0) ? 1 : 0;
     // 4 x 4-cell blocks per line for the 8-byte {food, META} records beside separate pheromone buffers (c4's layout: KP::ftile)
-    p->ftile = (p->meta && p->fs == 2 && (c->w & 3) == 0 && (c->h & 3) == 0 && !PROF_ENV("ANTSRL_NO_TILED")) ? 1 : 0;
+    p->ftile = (p->meta && p->fs == 2 && (c->w & 3) == 0 && (c->h & 3) == 0) ? 1 : 0;
 }
 
 // f0^S for the next observation, f0^(S+1) for the next deposit
@@ -364,18 +362,6 @@ extern "C" int antsrl_create(const AntsCfg *cfg, void *workspace, size_t workspa
 }
 
 extern "C" void antsrl_destroy(AntsHandle *h) { delete h; }
-
-#ifdef ANTSRL_PROFILING
-// Zone probe (profiles/r05/split_workspace_probe.py): the interleaved cell records at a caller-supplied address instead of
-// inside the workspace — call right after antsrl_create, before antsrl_reset / antsrl_generate.  16 * E * W * H bytes.
-extern "C" int antsrl_debug_set_cells_base(AntsHandle *h, void *cells)
-{
-    if (!h || !cells || h->p.ps != 4 || h->p.fs != 4) return ANTSRL_E_INVALID;
-    h->p.s.phero[0] = h->p.s.phero[1] = (float *)cells;
-    h->p.s.food = (float *)cells + 2;
-    return ANTSRL_OK;
-}
-#endif
 
 extern "C" int antsrl_reset(AntsHandle *h, const AntsInit *init, void *stream)
 {
@@ -537,9 +523,7 @@ static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, floa
         // Frames from k_update_move pay where k_perceive is latency-bound — the in-loop policy's launches, whose rows are
         // bfloat16 or stay in LDS: c5 -2.5 %, k_perceive -5 % — and cost 1-2 us of a second sincos where it is bound by its
         // float32 store stream, which hides the prologue anyway (c3 / c2 / c4: +1 %; profiles/r04/frames_ab.txt).
-        // ANTSRL_FRAMES=0 / 1 (profiling library): never / always.
         frames = h->pol.pack != nullptr;
-        if (const char *s = PROF_ENV("ANTSRL_FRAMES")) frames = atoi(s) != 0;
         e = antsrl_launch_update_move(h->p, h->pend_out_buf, h->pend_p.g_dep, h->pend_p.inv_g_dep, rot, ph, done, h->obs_seq, st, frames);
         if (e != hipSuccess) return hip_fail(e, "update + move");
     } else {
@@ -560,8 +544,7 @@ static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, floa
 }
 
 static int do_step(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *obs, float *agent_state,
-                   float *reward, uint8_t *done, hipStream_t st, bool fused_update = false,
-                   const double *jitter = nullptr, bool timed = false)
+                   float *reward, uint8_t *done, hipStream_t st, bool timed = false)
 {
     if (ph && h->p.C != 2) // Ants.activate_pheromone hard-codes two channels, ants.py:89-96
         return fail(ANTSRL_E_INVALID, "pheromone actions need exactly 2 pheromone channels (ants.py:89-96)");
@@ -574,19 +557,15 @@ static int do_step(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *ob
     }
     if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
     if (timed) (void)hipEventRecord(h->ev[2], st);
-    static const int ablate = PROF_ENV("ANTSRL_ABLATE") ? atoi(PROF_ENV("ANTSRL_ABLATE")) & ~15 : 0; // profiling build only
     hipError_t e = antsrl_launch_act(h->p, rot, ph, h->cur, obs, agent_state, reward, done,
-                                     ACT_STEP | (obs ? ACT_HAS_OBS : 0) | (fused_update ? ACT_FUSED_UPDATE : 0) | ablate |
-                                         (obs && h->obs_bf16 ? ACT_OBS_BF16 : 0),
-                                     jitter, h->p.scaled ? 0 : h->cur ^ 1, st);
+                                     ACT_STEP | (obs ? ACT_HAS_OBS : 0) | (obs && h->obs_bf16 ? ACT_OBS_BF16 : 0), st);
     if (e == hipErrorNotSupported) return bf16_unsupported();
     if (e != hipSuccess) return hip_fail(e, "step");
     h->steps_since_update++;
     return ANTSRL_OK;
 }
 
-static int do_update(AntsHandle *h, const double *jitter, hipStream_t st, bool sweep_done,
-                     bool update_fused = false, bool may_defer = false)
+static int do_update(AntsHandle *h, const double *jitter, hipStream_t st, bool sweep_done, bool may_defer)
 {
     hipError_t e;
     int frc = flush_pending(h, st); // (two updates in a row)
@@ -608,17 +587,15 @@ static int do_update(AntsHandle *h, const double *jitter, hipStream_t st, bool s
         e = antsrl_launch_sweep(h->p, h->cur, st);
         if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
     }
-    if (!update_fused) {
-        // Deferred: with the library's own wall jitter (no caller buffer to outlive the call) and nothing that has to
-        // run after the update kernel in this call, the kernel is left for the next step's k_update_move.
-        if (may_defer && !jitter && !h->need_full_collect && antsrl_update_move_supported(h->p)) {
-            h->pend_update = true;
-            h->pend_p = h->p;
-            h->pend_out_buf = h->p.scaled ? 0 : h->cur ^ 1;
-        } else {
-            e = antsrl_launch_update(h->p, jitter, h->p.scaled ? 0 : h->cur ^ 1, st);
-            if (e != hipSuccess) return hip_fail(e, "update");
-        }
+    // Deferred: with the library's own wall jitter (no caller buffer to outlive the call) and nothing that has to
+    // run after the update kernel in this call, the kernel is left for the next step's k_update_move.
+    if (may_defer && !jitter && !h->need_full_collect && antsrl_update_move_supported(h->p)) {
+        h->pend_update = true;
+        h->pend_p = h->p;
+        h->pend_out_buf = h->p.scaled ? 0 : h->cur ^ 1;
+    } else {
+        e = antsrl_launch_update(h->p, jitter, h->p.scaled ? 0 : h->cur ^ 1, st);
+        if (e != hipSuccess) return hip_fail(e, "update");
     }
     if (h->p.scaled) {
         h->sweeps++;
@@ -654,8 +631,7 @@ extern "C" int antsrl_observe(AntsHandle *h, float *obs, float *agent_state, flo
         return meta_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false);
     if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
     hipError_t e = antsrl_launch_act(h->p, nullptr, nullptr, h->cur, obs, agent_state, reward, nullptr,
-                                     obs ? ACT_HAS_OBS | (h->obs_bf16 ? ACT_OBS_BF16 : 0) : 0, nullptr, 0,
-                                     (hipStream_t)stream);
+                                     obs ? ACT_HAS_OBS | (h->obs_bf16 ? ACT_OBS_BF16 : 0) : 0, (hipStream_t)stream);
     if (e == hipErrorNotSupported) return bf16_unsupported();
     if (e != hipSuccess) return hip_fail(e, "observe");
     return ANTSRL_OK;
@@ -666,7 +642,7 @@ extern "C" int antsrl_update(AntsHandle *h, const double *wall_jitter, void *str
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
     if (!h->is_reset) return not_reset(h);
     if (h->phase_next) return mid_update(h);
-    return do_update(h, wall_jitter, (hipStream_t)stream, false, false, true);
+    return do_update(h, wall_jitter, (hipStream_t)stream, false, true);
 }
 
 // Environment.update one reference step at a time (include/antsrl.h).  Bit-identical to antsrl_update: the same device
@@ -763,21 +739,7 @@ extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const i
         if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
     }
     if (timed) (void)hipEventRecord(h->ev[1], st);
-    // Fuse Environment.update into the same launch unless the one-off wall clear of an initial
-    // pheromone grid has to run between this step's observation and this update's deposits.
-    // Measured on MI355X (c3): fusing is within 1 % of two launches either way (0.325 vs 0.328 ms/step with
-    // the loop form of the update; the separate k_update_one has since become the faster kernel) — with
-    // two workgroups per CU the update's latency-bound phases idle half the CU.  Opt-in
-    // (ANTSRL_FUSE_UPDATE=1) for re-evaluation.
-    static const bool want_fuse = PROF_ENV("ANTSRL_FUSE_UPDATE") && atoi(PROF_ENV("ANTSRL_FUSE_UPDATE")) != 0;
-    const bool fuse = want_fuse && !h->p.meta && !(h->p.scaled && h->need_wall_clear);
-    if (fuse && h->p.scaled && h->p.g_dep < 1e-20) { // re-base before the launch (value-preserving)
-        hipError_t e = antsrl_launch_phero_renorm(h->p, st);
-        if (e != hipSuccess) return hip_fail(e, "pheromone renorm");
-        h->sweeps = 0;
-        set_decay(h);
-    }
-    int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, st, fuse, wall_jitter, timed);
+    int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, st, timed);
     if (rc) return rc;
     if (timed) (void)hipEventRecord(h->ev[3], st);
     if (sweep_late) {
@@ -786,7 +748,7 @@ extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const i
     }
     const bool was_done = h->host_timestep == h->cfg.max_time; // RL_api.py:200, same for every env
     const bool regen = was_done && h->has_gen && h->gen.auto_reset;
-    rc = do_update(h, wall_jitter, st, true, fuse, !regen);
+    rc = do_update(h, wall_jitter, st, true, !regen);
     if (timed) (void)hipEventRecord(h->ev[4], st);
     if (rc == ANTSRL_OK && regen) {
         // next episode, like main.py:69-79 does per episode (reference streams: global env g takes seed + g, so the next

@@ -40,48 +40,6 @@
 #define META_STAMP_SHIFT 18
 #define META_NEVER 0x3FFFu
 
-// PROF_ENV("NAME"): A/B and ablation switches exist in the profiling build only (-DANTSRL_PROFILING ->
-// libantsrl_hip_prof.so, see antsrl_amd/build.py); in the product library no environment variable can
-// change what a step computes.
-#ifdef ANTSRL_PROFILING
-#define PROF_ENV(name) getenv(name)
-#else
-#define PROF_ENV(name) ((const char *)nullptr)
-#endif
-// Compile-time ablations (bit masks, results WRONG by design: antsrl_perceive.hip, antsrl_update_one.h) and the wave
-// time-line trace of k_perceive exist in variant builds of the profiling library only — a product build with any of them
-// set does not compile.
-#ifndef PRC_ABL
-#define PRC_ABL 0
-#endif
-#ifndef UM_ABL
-#define UM_ABL 0
-#endif
-#if !defined(ANTSRL_PROFILING) && (PRC_ABL != 0 || UM_ABL != 0 || defined(PRC_TRACE) || defined(UM_TRACE))
-#error "PRC_ABL / UM_ABL / PRC_TRACE / UM_TRACE are profiling switches: build them with -DANTSRL_PROFILING (python -m antsrl_amd.build --variant NAME -D...)"
-#endif
-
-// -DUM_TRACE (variant build; profiles/um_trace.py): the time line of every workgroup of k_update_move's last launch — its
-// thread 0 writes s_memrealtime (10 ns ticks) into g_um_trace[block][slot] at the phase boundaries.
-#ifdef UM_TRACE
-#define UM_TRACE_SLOTS 16
-#define UM_TRACE_MAX_WGS 4096
-static __device__ uint32_t g_um_trace[UM_TRACE_SLOTS * UM_TRACE_MAX_WGS]; // (one copy per translation unit; antsrl_perceive.hip's is the one read back)
-#define UM_STAMP(slot)                                                                                             \
-    do {                                                                                                           \
-        if (threadIdx.x == 0 && blockIdx.x < UM_TRACE_MAX_WGS) g_um_trace[blockIdx.x * UM_TRACE_SLOTS + (slot)] = (uint32_t)wall_clock64(); \
-    } while (0)
-// (the stamp waits until `v` — a value that depends on the loads of interest — is in a register)
-#define UM_STAMP_ON(slot, v)                                                                                       \
-    do {                                                                                                           \
-        asm volatile("" ::"v"(v));                                                                                 \
-        UM_STAMP(slot);                                                                                            \
-    } while (0)
-#else
-#define UM_STAMP(slot) do { } while (0)
-#define UM_STAMP_ON(slot, v) do { } while (0)
-#endif
-
 struct __align__(16) AntFrame { double cx, cy, ct, st; }; // perception centre, cos/sin(theta + pi/2)
 // k_update_move: what the update hands to the move of the same ant in registers — x, y after the update (= the new `prev`)
 // and theta; the food value and META word of the cell the ant stands on (the deposit cell's record IS the record of the
@@ -208,12 +166,5 @@ struct KP {
 // k_act flags
 #define ACT_STEP 1        // run RLApi.step's action phases before observing
 #define ACT_HAS_OBS 2     // obs pointer valid
-#define ACT_FUSED_UPDATE 4 // run Environment.update of the same step at the tail of the launch
 #define ACT_OBS_BF16 8     // `obs` is a bfloat16 tensor (antsrl_set_obs_format): same values, rounded to nearest even
 #define ACT_FRAMES 16      // k_perceive: DState::frames holds this observation's frames (written by the k_update_move in front of it)
-// profiling ablations (env ANTSRL_ABLATE, results are WRONG with any of them set; bench/tests never set it)
-#define ACT_ABL_NO_ITEMS 256   // skip the perception phase
-#define ACT_ABL_NO_GATHER 512  // no pheromone/food gathers
-#define ACT_ABL_NO_STORE 1024  // no observation stores
-#define ACT_ABL_NO_EXPLORE 2048 // no explored-map test/mark
-#define ACT_ABL_TRACE 32768      // (results stay valid) record the per-workgroup phase timeline, see act_trace

@@ -24,12 +24,6 @@
 // ahead, k_perceive ms: c3 0.2274 / 0.2211 / 0.2284, c4 0.518 / 0.484 / 0.480, c5 0.0760 / 0.0749 / 0.0805 —
 // profiles/r03/depth_ab.txt; the other two forms are in profiles/r04/perceive_cleanup.patch).
 
-// Compile-time ablations for profiles/ (results WRONG by design): bit masks, variant builds of the PROFILING library only
-// (`python -m antsrl_amd.build --variant NAME -DPRC_ABL=3`); antsrl_device.h refuses them in a product build.
-//   PRC_ABL  1: no record gathers (every lane reads one L1-resident line)   2: no observation stores   4: no explored marks
-//   UM_ABL   1: no food read   2: no presence stamp   4: no deposit read-modify-write      (k_update_move / k_move)
-constexpr bool abl_gather = (PRC_ABL & 1) != 0, abl_store = (PRC_ABL & 2) != 0, abl_mark = (PRC_ABL & 4) != 0;
-
 #define PLAYOUT_DEFAULT 1       // [Ants, Phero0, Phero1, Anthill, Walls, Food]   (generator order)
 #define PLAYOUT_DEFAULT_ROCKS 2 // ... + [CircleObstacles]
 
@@ -77,8 +71,8 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
             // The record was loaded by the update before its anthill collect ran.  Food on the anthill area is all zero once
             // the collect is done (anthill.py:41-46; the handle only defers an update that needs no full-grid collect), and
             // nothing else in the update writes food: an area cell reads 0, any other cell what the load returned.
-            if (fw->rec) h_q = (UM_ABL & 1) ? 0.0f : ((fw->meta & META_AREA) ? 0.0f : fw->food);
-            else h_q = (UM_ABL & 1) ? 0.0f : food[h_cprev];
+            if (fw->rec) h_q = (fw->meta & META_AREA) ? 0.0f : fw->food;
+            else h_q = food[h_cprev];
         } else {
             h_x = p.s.x[a1]; h_y = p.s.y[a1]; h_th = p.s.theta[a1];
             h_hold = p.s.holding[a1];
@@ -88,7 +82,7 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
                 if (rotation) h_rot = STP_LD(rotation[a1]);
                 if (phero_act) h_pa = STP_LD(phero_act[a1]);
                 h_cprev = frec_xy(p, (int)ppx, (int)ppy); // the food / META RECORD of the previous cell (hash key, food, dirty list)
-                h_q = (UM_ABL & 1) ? 0.0f : food[h_cprev]; // food is first written in phase 1b
+                h_q = food[h_cprev]; // food is first written in phase 1b
             }
         }
     }
@@ -114,7 +108,6 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
     if (!fw) __syncthreads();
     else __builtin_amdgcn_sched_barrier(0); // (no barrier, but nothing of the phases below is hoisted above this point either:
                                             //  the explicit-sweep variant of k_update_move spills three more VGPRs otherwise)
-    if (fw) UM_STAMP(10);
 
     if (do_step) {
         // ---- phase 1a: mandible target (RL_api.py:178-185) + Ants.update_mandibles reads
@@ -158,7 +151,6 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
         }
         if (!fw) __syncthreads();
         else __builtin_amdgcn_sched_barrier(0);
-        if (fw) UM_STAMP(11);
         // ---- phase 1b: ants.py:116 `qte[cell] += dropped - taken`, last ant on a cell wins
         for (int i = tid; i < N; i += T) {
             const uint32_t cprev = cprevs[i];
@@ -172,7 +164,6 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
             STP_ST(p.s.dirty_cell[eN + i], dirty);
             if (fw) break;
         }
-        if (fw) UM_STAMP(12);
     }
 
     // ---- phase 2: activation, rotate, move (RL_api.py:187-196), presence stamp
@@ -213,7 +204,7 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
         const uint32_t cell = frec_xy(p, wrap_index((int)x, W), wrap_index((int)y, H));
         // (a plain store: as an nt store k_update_move gains 1 us and k_perceive, whose gathers then miss the line, loses 4:
         //  profiles/r03/ntstamp_ab.txt)
-        if (!(UM_ABL & 2) || cell == 0xFFFFFFFFu) pres[(size_t)cell * FS2] = (uint16_t)seq;
+        pres[(size_t)cell * FS2] = (uint16_t)seq;
         if (fw && fw->frm_off) {
             // the ant's perception frame, exactly as k_perceive's prologue builds it from the x / y / theta just stored
             // (centre shifted by fwd_delta along the heading, RL_api.py:100-108): that launch then only loads it (ACT_FRAMES)
@@ -228,7 +219,6 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
         }
         if (fw) break;
     }
-    if (fw) UM_STAMP(13);
 }
 
 template <int C>
@@ -257,7 +247,6 @@ k_update_move(const KP p, const int out_buf, const double g_dep, const double in
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int e = env_of_block(blockIdx.x, p.E, seq);
-    UM_STAMP(0);
     UmFwd fw = {};
     { // the move's own per-ant inputs, ahead of the update: their memory round trip rides with the update's loads
         const size_t a = (size_t)e * p.N + (threadIdx.x < (unsigned)p.N ? threadIdx.x : 0);
@@ -268,18 +257,12 @@ k_update_move(const KP p, const int out_buf, const double g_dep, const double in
         fw.has_rot = rotation != nullptr;
         fw.primed = p.s.reward_primed[e]; // (every thread, one address: a branch around a load would carry its own wait)
     }
-    fw.rec = (ILV && C == 2 && !(UM_ABL & 4)) ? 1 : 0; // (interleaved records: the update forwards the cell's food / META words)
+    fw.rec = (ILV && C == 2) ? 1 : 0; // (interleaved records: the update forwards the cell's food / META words)
     // (with_frames: the host's choice per launch — antsrl_capi.hip, meta_observe; 0 = no frame is built, nothing is parked)
     fw.frm_off = with_frames ? (uint32_t)align_up(max(update_one_lds_bytes(p.HT, p.R, (int)(blockDim.x >> 6), p.N), move_lds_bytes(p.HT, p.N)), 16) : 0u;
     update_one_body<C, ILV>(p, e, nullptr, out_buf, smem, g_dep, inv_g_dep, &fw);
     __syncthreads(); // the update's global writes are visible to the whole workgroup; its LDS is dead
-    UM_STAMP(9);
     move_body<C>(p, e, rotation, phero_act, done, 1, seq, smem, &fw);
-#ifdef UM_TRACE
-    __builtin_amdgcn_s_waitcnt(0x0F70); // (the trace build waits for the stores' acknowledgement: slot 14 - slot 13)
-    UM_STAMP(14);
-    if (threadIdx.x == 0 && blockIdx.x < UM_TRACE_MAX_WGS) g_um_trace[blockIdx.x * UM_TRACE_SLOTS + 15] = __builtin_amdgcn_s_getreg(4 | (31 << 11)); // HW_ID
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -403,39 +386,6 @@ __device__ __forceinline__ void policy_tile(const PolArgs &pol, const uint16_t *
     }
 }
 
-// Variant build only (-DPRC_TRACE; profiles/prc_trace.py): the time line of every wave of k_perceive's last launch, in
-// 10 ns ticks (s_memrealtime): 0 entry, 1 past the prologue's barrier, 2 first gathers back (in front of the first group's work),
-// 3..6 behind group 1..4 of the first chunk (stores issued), 7 loop done, 8 every store acknowledged; 9 = HW_ID, 10 = XCC_ID;
-// POLICY: 11 behind the barrier in front of the in-loop net, 12 (wave 0) the net's actions are out.  The
-// stamps are kept in LDS (the launch needs ANTSRL_PRC_LDS_PAD >= 1) and written out by the wave's last instructions.
-#ifdef UM_TRACE
-extern "C" int antsrl_debug_read_um_trace(uint32_t *dst, int n_wgs)
-{
-    if (!dst || n_wgs < 0 || n_wgs > UM_TRACE_MAX_WGS) return ANTSRL_E_INVALID;
-    if (hipDeviceSynchronize() != hipSuccess) return ANTSRL_E_DEVICE;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_um_trace), sizeof(uint32_t) * UM_TRACE_SLOTS * (size_t)n_wgs) == hipSuccess
-               ? ANTSRL_OK : ANTSRL_E_DEVICE;
-}
-#endif
-#ifdef PRC_TRACE
-#define PRC_TRACE_SLOTS 16
-#define PRC_TRACE_MAX_WAVES (1 << 17)
-__device__ uint32_t g_prc_trace[PRC_TRACE_SLOTS * PRC_TRACE_MAX_WAVES];
-#define PRC_STAMP(slot)                                                                       \
-    do {                                                                                      \
-        if (lane == 0) prc_tr[(slot)] = (uint32_t)wall_clock64();                             \
-    } while (0)
-extern "C" int antsrl_debug_read_prc_trace(uint32_t *dst, int n_waves)
-{
-    if (!dst || n_waves < 0 || n_waves > PRC_TRACE_MAX_WAVES) return ANTSRL_E_INVALID;
-    if (hipDeviceSynchronize() != hipSuccess) return ANTSRL_E_DEVICE;
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_prc_trace), sizeof(uint32_t) * PRC_TRACE_SLOTS * (size_t)n_waves) == hipSuccess
-               ? ANTSRL_OK : ANTSRL_E_DEVICE;
-}
-#else
-#define PRC_STAMP(slot) do { } while (0)
-#endif
-
 // HAS_OBS is a template parameter on purpose: with the observation stores behind a run-time branch the
 // compiler cannot count them, every wait on a gather becomes vmcnt(0), i.e. a wait for the previous
 // group's observation stores to be acknowledged by memory — stores and everything else then add up instead
@@ -462,20 +412,9 @@ extern "C" int antsrl_debug_read_prc_trace(uint32_t *dst, int n_waves)
 #define PRC_MIN_WAVES 7
 #endif
 #define PRC_SGPR_ATTR __attribute__((amdgpu_num_sgpr(PRC_SGPR_CAP)))
-#ifdef ANTSRL_PROFILING
-// Placement probe (profiles/r05/env_pitch_probe.py): extra bytes between two environments' blocks of observation rows — the
-// caller's buffer is E * (N * row bytes + pad) then.  A pitch knob for measurements; the product's tensor is dense.
-__device__ uint32_t g_prc_env_pad;
-extern "C" int antsrl_debug_set_obs_env_pad(uint32_t bytes)
-{
-    if (bytes % 16) return ANTSRL_E_INVALID;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_prc_env_pad), &bytes, sizeof(bytes)) == hipSuccess ? ANTSRL_OK : ANTSRL_E_DEVICE;
-}
-#endif
-
 template <int LAYOUT, bool OBS16, bool ILV, bool HAS_OBS, bool POLICY = false, bool PAD = false>
 __global__ void __launch_bounds__(PRC_TPB, PRC_MIN_WAVES) PRC_SGPR_ATTR
-k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_arg, float *__restrict__ agent_state,
+k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs, float *__restrict__ agent_state,
            float *__restrict__ reward, const int flags, const uint32_t seq, const int run, const int nseg, const PolArgs pol,
            const uint32_t pitch_arg)
 {
@@ -488,16 +427,6 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
     constexpr int nwaves = PRC_TPB / 64;
     const int N = p.N, W = p.W, H = p.H, K = p.K, P = p.P, PP = p.PP, R = p.R;
     const size_t G = (size_t)W * H;
-#ifdef PRC_TRACE
-    uint32_t *prc_tr = reinterpret_cast<uint32_t *>(smem + align_up(prc_offsets(run, PP, K, R, nwaves, POLICY, PAD ? pitch_arg : 0u).total, 16) +
-                                                    (POLICY ? 2 * (size_t)prc_policy_img_elems(PP * K) + 4 * 64 : 0)) + wave * PRC_TRACE_SLOTS;
-    if (lane < PRC_TRACE_SLOTS) prc_tr[lane] = 0u;
-    PRC_STAMP(0);
-    if (lane == 0) {
-        prc_tr[9] = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID
-        prc_tr[10] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); // HW_REG_XCC_ID
-    }
-#endif
     // (environment, segment) of this workgroup.  Workgroups are dealt round-robin over the 8 XCDs (b and
     // b + 8 share one): all segments of an environment go to ONE XCD, back to back, so the cell records its
     // ants share are fetched into one L2 (speed only — nothing depends on the placement).
@@ -514,11 +443,6 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
         }
         e = env_of_block(e, p.E, seq); // (odd observations from the other end: antsrl_util.h)
     }
-#ifdef ANTSRL_PROFILING
-    float *__restrict__ obs = HAS_OBS ? reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(obs_arg) + (size_t)e * g_prc_env_pad) : obs_arg;
-#else
-    float *__restrict__ obs = obs_arg;
-#endif
     const PrcOff lo = prc_offsets(run, PP, K, R, nwaves, POLICY, PAD ? pitch_arg : 0u);
     double *rock = (double *)(smem + lo.rock);
     unsigned char *wbase = smem + lo.wave0 + (size_t)wave * lo.per_wave;
@@ -649,7 +573,6 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
             if (R > 0) rmask[lane] = rm;
         }
     }
-    PRC_STAMP(1);
     wave_lds_sync();
     if (n_run <= 0) { // (no barrier below: waves run independently from here on — but for the policy's hand-over)
         if constexpr (POLICY) __syncthreads();
@@ -718,12 +641,12 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
         }                                                                                                \
         _Pragma("unroll") for (int u = 0; u < PRC_UNROLL; ++u)                                           \
         {                                                                                                \
-            const uint32_t gc_ = abl_gather ? (uint32_t)lane : (uint32_t)__shfl((int)GRP.cell[u], src_lane); \
+            const uint32_t gc_ = (uint32_t)__shfl((int)GRP.cell[u], src_lane);                       \
             if (ILV) { /* one {p0, p1, food, META} record per cell: a single 16-byte gather */     \
                 const stream_f4 t = PRC_LOAD4(ph + (size_t)gc_ * 4);                                     \
                 GRP.pv[u][0] = t.x; GRP.pv[u][1] = t.y; GRP.fd[u] = t.z; GRP.mt[u] = __float_as_uint(t.w); \
             } else {                                                                                     \
-                const uint32_t pc_ = abl_gather ? (uint32_t)lane : (uint32_t)__shfl((int)GRP.pc[u], src_lane); \
+                const uint32_t pc_ = (uint32_t)__shfl((int)GRP.pc[u], src_lane);                       \
                 const float2 t = *reinterpret_cast<const float2 *>(ph + (size_t)pc_ * 2);                \
                 const float2 f = *reinterpret_cast<const float2 *>(fm + (size_t)gc_ * 2);                \
                 GRP.pv[u][0] = t.x; GRP.pv[u][1] = t.y; GRP.fd[u] = f.x; GRP.mt[u] = __float_as_uint(f.y); \
@@ -772,7 +695,7 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
             // mark: the stamp half-word of the META word := seq.  A plain 2-byte store, no atomic: every writer of
             // this observation stores the same value, cells explored earlier (stamp < seq) are never written, and
             // a reader that still sees the old stamp counts the cell as unexplored just the same (stamp >= seq).
-            if (unexp && !abl_mark)
+            if (unexp)
                 reinterpret_cast<uint16_t *>(metaw)[(size_t)g.cell[u] * FS * 2 + 1] = (uint16_t)((seq << 2) | ((mt >> 16) & 3u));
             if (has_rows) {
                 float pvs[C];
@@ -852,11 +775,9 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
                 const uint4 w1 = sp[i1], w2 = sp[i2];
                 uint4 w3 = w2;
                 if (!OBS16) w3 = sp[i3]; // (bfloat16: two rows are at most 96 pieces)
-                if (!abl_store) {
-                    store_stream(d + i1, w1);
-                    store_stream(d + i2, w2);
-                    if (!OBS16) store_stream(d + i3, w3);
-                }
+                store_stream(d + i1, w1);
+                store_stream(d + i2, w2);
+                if (!OBS16) store_stream(d + i3, w3);
             } else if (OBS16) {
                 uint16_t *dst16 = reinterpret_cast<uint16_t *>(obs) + ((size_t)e * N + (size_t)PRC_ANT(j0)) * row;
                 const uint32_t mis16 = (uint32_t)(((uintptr_t)dst16 >> 1) & 7);
@@ -867,11 +788,9 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
                 const uint4 w1 = reinterpret_cast<const uint4 *>(st16)[f.g1];
                 const uint4 w2 = reinterpret_cast<const uint4 *>(st16)[f.g2];
                 const uint16_t we = st16[f.fe];
-                if (!abl_store) {
-                    store_stream(reinterpret_cast<uint4 *>(d_al) + f.g1, w1);
-                    store_stream(reinterpret_cast<uint4 *>(d_al) + f.g2, w2);
-                    store_stream(d_al + f.fe, we);
-                }
+                store_stream(reinterpret_cast<uint4 *>(d_al) + f.g1, w1);
+                store_stream(reinterpret_cast<uint4 *>(d_al) + f.g2, w2);
+                store_stream(d_al + f.fe, we);
                 // the next group's 16-byte misalignment
                 carry = (uint32_t)(((uintptr_t)(reinterpret_cast<uint16_t *>(obs) + ((size_t)e * N + (size_t)PRC_ANT(j0 + 2)) * row) >> 1) & 7);
             } else {
@@ -883,12 +802,10 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
                 const float4 v2 = reinterpret_cast<const float4 *>(stage)[f.j2];
                 const float4 v3 = reinterpret_cast<const float4 *>(stage)[f.j3];
                 const float ve = stage[f.fe];
-                if (!abl_store) {
-                    store_stream(reinterpret_cast<float4 *>(dst_al) + f.j1, v1);
-                    store_stream(reinterpret_cast<float4 *>(dst_al) + f.j2, v2);
-                    store_stream(reinterpret_cast<float4 *>(dst_al) + f.j3, v3);
-                    store_stream(dst_al + f.fe, ve);
-                }
+                store_stream(reinterpret_cast<float4 *>(dst_al) + f.j1, v1);
+                store_stream(reinterpret_cast<float4 *>(dst_al) + f.j2, v2);
+                store_stream(reinterpret_cast<float4 *>(dst_al) + f.j3, v3);
+                store_stream(dst_al + f.fe, ve);
                 // the next group's 16-byte misalignment
                 carry = (uint32_t)(((uintptr_t)(reinterpret_cast<float *>(obs) + ((size_t)e * N + (size_t)PRC_ANT(j0 + 2)) * row) >> 2) & 3);
             }
@@ -905,25 +822,19 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
         PRC_FETCH(min(c0, n_run - 1), gA)
         PRC_FETCH(min(c0 + PRC_UNROLL, n_run - 1), gB)
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt / lgkmcnt untouched
-        if (c0 == 0) PRC_STAMP(2);
         PRC_FETCH(min(c0 + 2 * PRC_UNROLL, n_run - 1), gC)
         process(gA, c0);
-        if (c0 == 0) PRC_STAMP(3);
         if (c0 + PRC_UNROLL < n_run) {
             PRC_FETCH(min(c0 + 3 * PRC_UNROLL, n_run - 1), gA)
             process(gB, c0 + PRC_UNROLL);
-            if (c0 == 0) PRC_STAMP(4);
             if (c0 + 2 * PRC_UNROLL < n_run) {
                 process(gC, c0 + 2 * PRC_UNROLL);
-                if (c0 == 0) PRC_STAMP(5);
                 if (c0 + 3 * PRC_UNROLL < n_run) {
                     process(gA, c0 + 3 * PRC_UNROLL);
-                    if (c0 == 0) PRC_STAMP(6);
                 }
             }
         }
     }
-    PRC_STAMP(7);
 #undef PRC_FETCH
 
     // ---- agent_state (RL_api.py:160-162), reward.observation hooks, give_reward: lane j <-> the wave's j-th ant
@@ -968,29 +879,13 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs_
         if ((flags & ACT_STEP) && rw - p.reward_threshold > 0) p.s.reward_state[a] = 255; // ants.py:119-121
     }
 #undef PRC_ANT
-#ifdef PRC_TRACE
-    __builtin_amdgcn_s_waitcnt(0x0F70); // (the trace measures when the wave's stores are acknowledged, too: slot 8 - slot 7)
-    PRC_STAMP(8);
-#endif
     if constexpr (POLICY) {
         __syncthreads(); // every wave's rows and agent_state inputs are in the image
-        PRC_STAMP(11);
         const int t0 = seg * nwaves * run; // first ant of this workgroup's tile
         if (wave == 0) {
             policy_tile(pol, pol_img, (uint32_t)(tile0 - pol_img), pol_as, (int)row, min(nwaves * run, N - t0), eN + (size_t)t0, lane);
-#ifdef PRC_TRACE
-            __builtin_amdgcn_s_waitcnt(0x0F70); // (the actions are out)
-#endif
-            PRC_STAMP(12);
         }
     }
-#ifdef PRC_TRACE
-    wave_lds_sync();
-    {
-        const uint32_t wv = (uint32_t)blockIdx.x * nwaves + (uint32_t)wave;
-        if (wv < PRC_TRACE_MAX_WAVES && lane < PRC_TRACE_SLOTS) g_prc_trace[wv * PRC_TRACE_SLOTS + lane] = prc_tr[lane];
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1046,7 +941,6 @@ static int n_cus()
 // stream; short runs fill the chip (16 waves per CU) several times over so that the tail is short.
 static int pick_run(const KP &p)
 {
-    if (const char *s = PROF_ENV("ANTSRL_PRC_RUN")) return atoi(s);
     const long total = (long)p.E * p.N, slots = (long)n_cus() * 16;
     // c3 (1024 x 512 ants), k_perceive ms early / late in the episode: run 2: 0.313 / 0.308, 4: 0.253 / 0.247,
     // 8: 0.236 / 0.231, 16: 0.237 (late), 32: 0.250 / 0.245, 64: 0.250 (late) — with short runs the segments of one
@@ -1080,16 +974,15 @@ bool antsrl_update_move_supported(const KP &p)
 {
     // (scaled units or an explicit sweep alike: with a sweep the host enqueues k_update_move AHEAD of the step's sweep, whose
     //  input buffer the deferred deposit lands in — antsrl_step_update in antsrl_capi.hip)
-    return p.meta && p.C == 2 && p.N <= 1024 && !PROF_ENV("ANTSRL_NO_DEFER_UPDATE");
+    return p.meta && p.C == 2 && p.N <= 1024;
 }
 
 hipError_t antsrl_launch_update_move(const KP &p, int out_buf, double g_dep, double inv_g_dep, const int8_t *rot,
                                      const int8_t *ph, uint8_t *done, uint32_t seq, hipStream_t st, bool with_frames)
 {
     const int T = (p.N + 63) / 64 * 64;
-    size_t lds = align_up(std::max(update_one_lds_bytes(p.HT, p.R, T / 64, p.N), move_lds_bytes(p.HT, p.N)), 16) +
+    const size_t lds = align_up(std::max(update_one_lds_bytes(p.HT, p.R, T / 64, p.N), move_lds_bytes(p.HT, p.N)), 16) +
                  16 * (size_t)T; // + cos / sin(theta + pi/2) per ant, parked between the update and the move (UmFwd::frm_off)
-    if (const char *s = PROF_ENV("ANTSRL_UM_LDS_PAD")) lds += (size_t)atoi(s) * 1024; // occupancy knob (profiling build)
     static size_t seen[ANTSRL_MAX_DEVICES] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ANTSRL_MAX_DEVICES) return hipErrorInvalidDevice;
@@ -1112,13 +1005,10 @@ static hipError_t launch_perceive_t(const KP &p, const float *cells, float *obs,
                                     int flags, uint32_t seq, hipStream_t st, const PolArgs &pol = PolArgs{}, uint32_t pitch = 0)
 {
     const int run = pick_run(p), nwaves = PRC_TPB / 64;
-    if (run < 1 || run > 64) return hipErrorInvalidValue;
     if (POLICY && run * nwaves > 32) return hipErrorInvalidValue; // one MFMA tile of 32 ants per workgroup
     const int nseg = (p.N + run * nwaves - 1) / (run * nwaves);
     const PrcOff lo = prc_offsets(run, p.PP, p.K, p.R, nwaves, POLICY, PAD ? pitch : 0u);
-    const size_t pad = PROF_ENV("ANTSRL_PRC_LDS_PAD") ? (size_t)atoi(PROF_ENV("ANTSRL_PRC_LDS_PAD")) * 1024 : 0; // occupancy knob
-    size_t lds = lo.total + pad;
-    if (POLICY) lds = align_up(lo.total, 16) + 2 * (size_t)prc_policy_img_elems(p.PP * p.K) + 4 * 64 + pad;
+    const size_t lds = POLICY ? align_up(lo.total, 16) + 2 * (size_t)prc_policy_img_elems(p.PP * p.K) + 4 * 64 : lo.total;
     if (lds > 64 * 1024) return hipErrorInvalidValue; // (never with the shapes antsrl_meta_supported admits)
     hipLaunchKernelGGL((k_perceive<LAYOUT, OBS16, ILV, HAS_OBS, POLICY, PAD>), dim3((unsigned)((size_t)p.E * nseg)), dim3(PRC_TPB), lds, st, p,
                        cells, obs, agent_state, reward, flags, seq, run, nseg, pol, pitch);

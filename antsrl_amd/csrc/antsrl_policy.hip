@@ -49,7 +49,7 @@ k_policy_mlp(const float *__restrict__ obs, const float *__restrict__ agent_stat
              const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
              const float *__restrict__ w3, const float *__restrict__ b3, int8_t *__restrict__ rot_out,
              int8_t *__restrict__ ph_out, float *__restrict__ logits_out, const int M, const int F,
-             const int ksteps, const int newest_first)
+             const int ksteps)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __bf16 *w1s = reinterpret_cast<__bf16 *>(smem); // [32][KP], KP = 16*ksteps + 8 (8 = bank skew)
@@ -107,8 +107,7 @@ k_policy_mlp(const float *__restrict__ obs, const float *__restrict__ agent_stat
     __bf16 *stg = w1s + POL_HIDDEN * KP + (size_t)wib * 32 * POL_SROW; // [32][POL_SROW]
     const int la = lane >> 4, lf = lane & 15;                          // loader role: ant la + 4 i, floats 4 lf .. 4 lf + 3
     const int nchunks = (IN + POL_KC - 1) / POL_KC;
-    for (int t0 = wave; t0 < ntiles; t0 += nwaves) {
-        const int t = newest_first ? ntiles - 1 - t0 : t0; // (A/B switch, see antsrl_launch_policy)
+    for (int t = wave; t < ntiles; t += nwaves) {
         const int ant = min(t * 32 + r, M - 1); // clamped: duplicates are not written back
         const int rows = min(32, M - t * 32);
         const float *tile = obs + (size_t)t * 32 * F;
@@ -301,8 +300,7 @@ k_policy_flat(const float *__restrict__ obs, const float *__restrict__ agent_sta
               const float *__restrict__ b1, const float *__restrict__ w2, const float *__restrict__ b2,
               const float *__restrict__ w3, const float *__restrict__ b3, int8_t *__restrict__ rot_out,
               int8_t *__restrict__ ph_out, float *__restrict__ logits_out, const int M, const int F,
-              const int ksteps /* ceil(F / 16) */, const int tile_elems /* LDS image size per wave, bf16 */,
-              const int newest_first)
+              const int ksteps /* ceil(F / 16) */, const int tile_elems /* LDS image size per wave, bf16 */)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __bf16 *w1s = reinterpret_cast<__bf16 *>(smem); // [32][KP], KP = 16*ksteps + 8 (8 = bank skew)
@@ -344,8 +342,7 @@ k_policy_flat(const float *__restrict__ obs, const float *__restrict__ agent_sta
 
     const int ntiles = (M + 31) / 32;
     const __bf16 *wrow = w1s + r * KP + 8 * h;
-    for (int t0 = wave; t0 < ntiles; t0 += nwaves) {
-        const int t = newest_first ? ntiles - 1 - t0 : t0; // (A/B switch, see antsrl_launch_policy)
+    for (int t = wave; t < ntiles; t += nwaves) {
         const int ant = min(t * 32 + r, M - 1); // clamped: duplicates are not written back
         const int rows = min(32, M - t * 32);
         const uint32_t nelem = (uint32_t)rows * (uint32_t)F;
@@ -490,18 +487,13 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
                                 const float *w2, const float *b2, const float *w3, const float *b3, int8_t *rot,
                                 int8_t *ph, float *logits, int M, int F, hipStream_t st, bool obs_bf16)
 {
-    // tile order (profiling switch): newest rows first was tried for Infinity Cache hits on what k_perceive has just
-    // written and measured no better (c5 0.1301 vs 0.1294 ms/step, profiles/r02/policy_order_ab.txt)
-    const int newest_first = PROF_ENV("ANTSRL_POLICY_NEWEST_FIRST") ? 1 : 0;
-
     if (M < 1 || F < 1) return hipErrorInvalidValue;
     {
         // flat-stream form: W1 (observation columns) + two wave-private tile images (32 F elements + the
         // read-ahead of the last k-step, zero padded) in LDS
-        static const bool off = PROF_ENV("ANTSRL_POLICY_CHUNKED") != nullptr; // A/B: the chunked kernel
         const int ks = (F + 15) / 16, tile_elems = (32 * F + 32 + 7) / 8 * 8;
         const size_t lds = (size_t)POL_HIDDEN * (16 * ks + 8) * 2 + 2 * (size_t)tile_elems * 2;
-        if (!off && ks <= POL_MAX_KSTEPS && lds <= 160 * 1024) {
+        if (ks <= POL_MAX_KSTEPS && lds <= 160 * 1024) {
             const int ntiles = (M + 31) / 32;
             int per_cu = (int)((160 * 1024) / lds);
             per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
@@ -515,13 +507,13 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
                 if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_policy_flat<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL(k_policy_flat<true>, dim3(blocks), dim3(128), lds, st, obs, agent_state, w1, b1, w2, b2, w3,
-                                   b3, rot, ph, logits, M, F, ks, tile_elems, newest_first);
+                                   b3, rot, ph, logits, M, F, ks, tile_elems);
             } else {
                 static size_t attr[ANTSRL_MAX_DEVICES] = {}; // per kernel function and per device
                 if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_policy_flat<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
                 if (e != hipSuccess) return e;
                 hipLaunchKernelGGL(k_policy_flat<false>, dim3(blocks), dim3(128), lds, st, obs, agent_state, w1, b1, w2, b2, w3,
-                                   b3, rot, ph, logits, M, F, ks, tile_elems, newest_first);
+                                   b3, rot, ph, logits, M, F, ks, tile_elems);
             }
             return hipGetLastError();
         }
@@ -545,7 +537,7 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
             attr[dev] = lds;
         }
         hipLaunchKernelGGL(k_policy_mlp<true>, dim3(blocks), dim3(256), lds, st, obs, agent_state, w1, b1, w2, b2, w3, b3,
-                           rot, ph, logits, M, F, ksteps, newest_first);
+                           rot, ph, logits, M, F, ksteps);
     } else {
         static size_t attr[ANTSRL_MAX_DEVICES] = {};
         if (lds > attr[dev]) {
@@ -554,7 +546,7 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
             attr[dev] = lds;
         }
         hipLaunchKernelGGL(k_policy_mlp<false>, dim3(blocks), dim3(256), lds, st, obs, agent_state, w1, b1, w2, b2, w3, b3,
-                           rot, ph, logits, M, F, ksteps, newest_first);
+                           rot, ph, logits, M, F, ksteps);
     }
     return hipGetLastError();
 }

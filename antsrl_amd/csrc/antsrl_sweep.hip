@@ -1,6 +1,5 @@
 // antsrl_sweep.hip — pheromone sweeps: k_sweep0 (radius 0, streaming), k_sweep_march (radius 1..3,
-// register-marching stencil, separable form for rank-1 filters), k_sweep_tiled (float64 cross-check),
-// the wall clear / re-basing passes of the scaled representation, launchers.
+// register-marching stencil, separable form for rank-1 filters), the wall clear / re-basing passes of the scaled representation, launchers.
 #include "antsrl_util.h"
 
 // ===================================================================================
@@ -67,61 +66,6 @@ k_sweep0_scalar(const KP p, const float *__restrict__ in, float *__restrict__ ou
         if (test_bit(p.s.walls_bits + e * p.words, cell)) f = 0.0f;
         if (clip) f = fminf(f, (float)p.max_val);
         out[v] = f;
-    }
-}
-
-// Radius 1..3: LDS-tiled 2-D convolution with zero-fill boundary,
-// scipy.signal.convolve2d(phero, F, 'same', 'fill', 0)  (pheromone.py:44):
-//   out[x,y] = sum_{a,b} F[a,b] * in[x-a+r, y-b+r]   (true convolution: kernel flipped)
-// The wall mask is applied while the tile is staged (walls.py:30 zeroes the INPUT of the
-// convolution, so a wall cell still receives its neighbours' diffusion).
-#define SW_TX 16
-#define SW_TY 64
-template <int C>
-__global__ void __launch_bounds__(256)
-k_sweep_tiled(const KP p, const float *__restrict__ in, float *__restrict__ out)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    float *tile = (float *)smem;
-    const int fr = p.filter_radius, fs = 2 * fr + 1;
-    const int LX = SW_TX + 2 * fr, LY = SW_TY + 2 * fr;
-    const int e = blockIdx.z, x0 = blockIdx.y * SW_TX, y0 = blockIdx.x * SW_TY;
-    const int W = p.W, H = p.H;
-    const size_t G = (size_t)W * H;
-    const float *src = in + (size_t)e * G * C;
-    float *dst = out + (size_t)e * G * C;
-    const uint32_t *walls = p.s.walls_bits + (size_t)e * p.words;
-    for (int t = threadIdx.x; t < LX * LY; t += blockDim.x) {
-        const int lx = t / LY, ly = t - lx * LY;
-        const int gx = x0 + lx - fr, gy = y0 + ly - fr;
-        const bool inside = gx >= 0 && gx < W && gy >= 0 && gy < H;
-        const uint32_t cell = inside ? (uint32_t)(gx * H + gy) : 0u;
-        const bool live = inside && !test_bit(walls, cell);
-#pragma unroll
-        for (int c = 0; c < C; ++c) tile[(size_t)t * C + c] = live ? src[(size_t)cell * C + c] : 0.0f;
-    }
-    __syncthreads();
-    const bool clip = p.has_max_val && p.N > 0;
-    for (int t = threadIdx.x; t < SW_TX * SW_TY; t += blockDim.x) {
-        const int lx = t / SW_TY, ly = t - lx * SW_TY;
-        const int gx = x0 + lx, gy = y0 + ly;
-        if (gx >= W || gy >= H) continue;
-        double acc[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) acc[c] = 0.0;
-        for (int a = 0; a < fs; ++a)
-            for (int b = 0; b < fs; ++b) {
-                const double f = p.filter[a * fs + b];
-                const float *tp = tile + ((size_t)(lx - a + 2 * fr) * LY + (ly - b + 2 * fr)) * C;
-#pragma unroll
-                for (int c = 0; c < C; ++c) acc[c] += f * (double)tp[c];
-            }
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            float f = (acc[c] < p.threshold) ? 0.0f : (float)acc[c];
-            if (clip) f = fminf(f, (float)p.max_val);
-            dst[((size_t)gx * H + gy) * C + c] = f;
-        }
     }
 }
 
@@ -481,46 +425,25 @@ k_sweep_r1x2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
 }
 
 // Radius 2..3, two channels, even H, RANK-1 filter (c4's Gaussian): the separable march with TWO columns per lane
-// (16-byte accesses).  Strips overlap by HL = ceil(R / 2) lanes on either side (the halo), so a wave covers 128 columns
-// and produces 128 - 4 HL of them (R = 3: 120; the one-column form: 58 of 64).  Each input row is convolved across the
-// lanes with v (neighbour columns: the lane's other column, and the adjacent lanes' columns by whole-wave DPP shifts of
-// one and two lanes), the result feeds the S running output rows with u; nothing is kept per block but the accumulators
-// and the prefetched rows.  out[x,y] = sum_a u[a] sum_b v[b] in[x-a+R, y-b+R]   (taps split hi + lo)
-// STACK: a workgroup takes FOUR VERTICALLY STACKED segments of one column strip and its waves march AWAY FROM / TOWARDS
-// the boundaries they share — waves 0 and 1 start at the boundary between segments 0 and 1 and march up (descending x) and
-// down, waves 2 and 3 likewise around the boundary between segments 2 and 3; waves 1 and 2 then END at their common
-// boundary at the same time.  The 2R halo rows two neighbouring segments both need are therefore requested by two waves
-// of ONE workgroup within the same few hundred nanoseconds: one fetch from memory, the second an L1 / L2 hit.  With the flat
-// packing (STACK = false: one wave per (strip, segment) pair in unit order) the second request came from another
-// workgroup — usually on another XCD, i.e. another L2 — much later, and the 32-row segments re-read 2R / 32 = 19 % of the
-// grid from memory (PMC, c4: 3.57 GB fetched for a 2.15 GB grid; profiles/r02/pmc_summary.md).
-// A descending march is the ascending one in mirrored coordinates: the same ring of S running output rows, the row taps u
-// taken in reverse order.  (The order in which an output row's contributions are added differs between the two directions:
-// last-bit differences in float32, inside the 1e-5 bar the grid is held to.)
-// HL: halo lanes per side (>= ceil(R / 2)).  With HL = 4 a wave writes 56 lanes x 16 bytes = 7 WHOLE 128-byte lines per row
-// and every strip starts on a line; with the minimal halo (HL = 2 at R = 3: 120 columns = 960 bytes per row) every
-// strip boundary cuts a line in two, written by two waves — and a partial-line write makes the L2 fetch the line first.
-template <int R, bool STACK, int HL>
+// (16-byte accesses).  Strips overlap by SEP2_HL lanes on either side (the halo), so a wave covers 128 columns and produces
+// 128 - 4 SEP2_HL = 112 of them (the one-column form: 58 of 64).  Each input row is convolved across the lanes with v
+// (neighbour columns: the lane's other column, and the adjacent lanes' columns by whole-wave DPP shifts of one and two
+// lanes), the result feeds the S running output rows with u; nothing is kept per block but the accumulators and the
+// prefetched rows.  out[x,y] = sum_a u[a] sum_b v[b] in[x-a+R, y-b+R]   (taps split hi + lo)
+// SEP2_HL = 4, not the minimal ceil(R / 2): a wave writes 56 lanes x 16 bytes = 7 WHOLE 128-byte lines per row and every
+// strip starts on a line; with the minimal halo (2 at R = 3: 120 columns = 960 bytes per row) every strip boundary cuts a
+// line in two, written by two waves — and a partial-line write makes the L2 fetch the line first.
+// One wave per (column strip, row segment) pair, the pairs of an environment packed densely into its workgroups: no wave is
+// launched only to exit (strips per row rarely divide by 4), so the CUs keep their full wave count.
+#define SEP2_HL 4
+template <int R>
 __global__ void __launch_bounds__(256)
 k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, const int seg_rows, const int nstrips, const int nsegs)
 {
-    static_assert(2 * HL >= R, "halo lanes hold two columns each");
-    constexpr int S = 2 * R + 1, OUTW = 128 - 4 * HL;
+    constexpr int HL = SEP2_HL, S = 2 * R + 1, OUTW = 128 - 4 * HL;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int e = blockIdx.y, W = p.W, H = p.H;
-    int strip, segi;
-    bool desc = false; // march towards smaller x
-    if constexpr (STACK) {
-        strip = blockIdx.x % nstrips;
-        segi = (blockIdx.x / nstrips) * 4 + wave;
-        desc = (wave & 1) == 0;
-    } else {
-        // one wave per (column strip, row segment) pair, the pairs of an environment packed densely into its workgroups:
-        // no wave is launched only to exit (strips per row rarely divide by 4), so the CUs keep their full wave count
-        const int unit = blockIdx.x * 4 + wave;
-        strip = unit % nstrips;
-        segi = unit / nstrips;
-    }
+    const int unit = blockIdx.x * 4 + wave, strip = unit % nstrips, segi = unit / nstrips;
     __shared__ float taps[4 * S]; // u {hi, lo} [S], then v {hi, lo} [S]
     if (threadIdx.x < 2 * S) {
         taps[threadIdx.x] = p.fsep_u[threadIdx.x];
@@ -539,13 +462,12 @@ k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
     const uint32_t *walls = p.s.walls_bits + (size_t)e * p.words;
     const bool clip = p.has_max_val && p.N > 0;
     const float thr = (float)p.threshold, mx = (float)p.max_val;
-    // the filter taps as wave-uniform scalars (SGPRs), hi and lo parts; u in march order
+    // the filter taps as wave-uniform scalars (SGPRs), hi and lo parts
     float uh[S], ul[S], vh[S], vl[S];
 #pragma unroll
     for (int a = 0; a < S; ++a) {
-        const int au = desc ? S - 1 - a : a;
-        uh[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * au])));
-        ul[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * au + 1])));
+        uh[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * a])));
+        ul[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * a + 1])));
         vh[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * S + 2 * a])));
         vl[a] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, taps[2 * S + 2 * a + 1])));
     }
@@ -561,15 +483,15 @@ k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
 #pragma unroll
     for (int j = 0; j < S; ++j) acc[j][0] = acc[j][1] = (v2f)(0.0f);
     const int x_lo = segi * seg_rows, x_hi = min(x_lo + seg_rows, W), nrows = x_hi - x_lo;
-    // march position i <-> grid row x0 + dx * i: positions 0 .. nrows + 2R - 1 cover the segment and its halos
-    const int x0 = desc ? x_hi - 1 + R : x_lo - R, dx = desc ? -1 : 1;
+    // march position i <-> grid row x0 + i: positions 0 .. nrows + 2R - 1 cover the segment and its halos
+    const int x0 = x_lo - R;
     float4 nv[S];
     uint32_t nword[S], ncell[S];
 #define SEP2_LOAD1(I0, s)                                                                            \
     {                                                                                                \
         /* clamped to the grid (masked to zero when used) and to the march's last position: the prefetch of the \
            last turn must not pull in rows nobody needs (it did: 49 rows read per 32-row segment instead of 38) */ \
-        const int xc = min(max(x0 + dx * min((I0) + (s), nrows + 2 * R - 1), 0), W - 1);           \
+        const int xc = min(max(x0 + min((I0) + (s), nrows + 2 * R - 1), 0), W - 1);                \
         ncell[s] = (uint32_t)(xc * H + yc);                                                          \
         nword[s] = walls[ncell[s] >> 5];                                                             \
         nv[s] = *reinterpret_cast<const float4 *>(src + (size_t)ncell[s] * 2);                       \
@@ -580,7 +502,7 @@ k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             // zero fill outside the grid; walls.py:30 zeroes the INPUT of the convolution (arithmetic masks)
-            const int xin = x0 + dx * (i0 + s);
+            const int xin = x0 + (i0 + s);
             const float rowm = (xin >= 0 && xin < W) ? 1.0f : 0.0f;
             const uint32_t sh0 = ncell[s] & 31u; // (even cell index: the pair's two bits sit in one word)
             const float k0 = colmask * rowm * (float)(1u - ((nword[s] >> sh0) & 1u));
@@ -613,18 +535,18 @@ k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
                 h0 = FMA2(vh[R - d], nb0[R + d], h0); h1 = FMA2(vh[R - d], nb1[R + d], h1);
                 h0 = FMA2(vl[R - d], nb0[R + d], h0); h1 = FMA2(vl[R - d], nb1[R + d], h1);
             }
-            // position i + a - R += u[a] h (u in march order): ring slot (s + a - R) mod S
+            // position i + a - R += u[a] h: ring slot (s + a - R) mod S
 #pragma unroll
             for (int a = 0; a < S; ++a) {
                 const int slot = (s + a - R + 2 * S) % S;
                 acc[slot][0] = FMA2(uh[a], h0, acc[slot][0]); acc[slot][1] = FMA2(uh[a], h1, acc[slot][1]);
                 acc[slot][0] = FMA2(ul[a], h0, acc[slot][0]); acc[slot][1] = FMA2(ul[a], h1, acc[slot][1]);
             }
-            { // position i - R just received its last contribution: the segment's row number i - 2R in march order
+            { // position i - R just received its last contribution: the segment's row number i - 2R
                 const int slot = (s - R + 2 * S) % S;
                 const int io = i0 + s - 2 * R;
                 if (io >= 0 && io < nrows && col_out) {
-                    const int x = desc ? x_hi - 1 - io : x_lo + io;
+                    const int x = x_lo + io;
                     float r[4] = {acc[slot][0].x, acc[slot][0].y, acc[slot][1].x, acc[slot][1].y};
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
@@ -660,7 +582,7 @@ static hipError_t launch_sweep_c(const KP &p, int cur, hipStream_t st)
             if (blocks > 256 * 64) blocks = 256 * 64;
             hipLaunchKernelGGL((k_sweep0_scalar<C>), dim3((unsigned)blocks), dim3(256), 0, st, p, in, out, n);
         }
-    } else if (!PROF_ENV("ANTSRL_SWEEP_TILED")) {
+    } else {
         const int fr = p.filter_radius;
         // The march is split along x into segments (each re-reads 2R rows, mostly from L2 / the Infinity Cache) and one
         // wave takes one (column strip, segment) pair; the pairs of an environment fill its workgroups densely.
@@ -668,9 +590,8 @@ static hipError_t launch_sweep_c(const KP &p, int cur, hipStream_t st)
         // per lane: 0.191 ms against 0.205 at 32, 0.219 at 64); radius 3, two columns — 32 (c4: 0.827 ms against 0.854 at
         // 64, 0.900 at 16, 0.907 at 128); radius 3, one column — 64 (0.936 against 1.001 at 32, 1.035 at 128).  Enough
         // waves to keep every SIMD full to the end, short enough streams to keep the chip's write window compact.
-        const bool two_col = C == 2 && (p.H & 1) == 0 && !PROF_ENV("ANTSRL_SWEEP_ONE_COLUMN");
-        int seg_rows = std::min(p.W, fr == 1 ? 16 : (two_col && p.filter_sep) || fr == 2 ? 32 : 64);
-        if (const char *v = PROF_ENV("ANTSRL_SWEEP_SEG")) seg_rows = std::max(1, std::min(p.W, atoi(v)));
+        const bool two_col = C == 2 && (p.H & 1) == 0;
+        const int seg_rows = std::min(p.W, fr == 1 ? 16 : (two_col && p.filter_sep) || fr == 2 ? 32 : 64);
         const int nsegs = (p.W + seg_rows - 1) / seg_rows;
         if constexpr (C == 2) {
             // radius 1 (the reference's 3x3 diffusion), even H: two columns per lane, 16-byte accesses
@@ -681,22 +602,11 @@ static hipError_t launch_sweep_c(const KP &p, int cur, hipStream_t st)
             }
             // radius 2..3 with a rank-1 filter (c4's Gaussian), even H: the separable march, two columns per lane
             if (fr >= 2 && p.filter_sep && two_col) {
-                // 4 halo lanes per side: whole-line stores (see k_sweep_sep2); ANTSRL_SWEEP_MINHALO (profiling) = ceil(R / 2)
-                const bool minhalo = PROF_ENV("ANTSRL_SWEEP_MINHALO") != nullptr;
-                const int hl = minhalo ? (fr + 1) / 2 : 4;
-                const int outw = 128 - 4 * hl;
+                const int outw = 128 - 4 * SEP2_HL;
                 const int strips2 = (p.H + outw - 1) / outw;
-                const bool stack = PROF_ENV("ANTSRL_SWEEP_STACK") != nullptr; // (four stacked segments per workgroup: measured slower)
-                const dim3 grid2(stack ? strips2 * ((nsegs + 3) / 4) : (strips2 * nsegs + 3) / 4, p.E);
-#define SEP2_GO(RR, ST, HLV) hipLaunchKernelGGL((k_sweep_sep2<RR, ST, HLV>), grid2, dim3(256), 0, st, p, in, out, seg_rows, strips2, nsegs)
-                if (fr == 2) {
-                    if (stack) { if (minhalo) SEP2_GO(2, true, 1); else SEP2_GO(2, true, 4); }
-                    else { if (minhalo) SEP2_GO(2, false, 1); else SEP2_GO(2, false, 4); }
-                } else {
-                    if (stack) { if (minhalo) SEP2_GO(3, true, 2); else SEP2_GO(3, true, 4); }
-                    else { if (minhalo) SEP2_GO(3, false, 2); else SEP2_GO(3, false, 4); }
-                }
-#undef SEP2_GO
+                const dim3 grid2((strips2 * nsegs + 3) / 4, p.E);
+                if (fr == 2) hipLaunchKernelGGL((k_sweep_sep2<2>), grid2, dim3(256), 0, st, p, in, out, seg_rows, strips2, nsegs);
+                else hipLaunchKernelGGL((k_sweep_sep2<3>), grid2, dim3(256), 0, st, p, in, out, seg_rows, strips2, nsegs);
                 return hipGetLastError();
             }
         }
@@ -711,11 +621,6 @@ static hipError_t launch_sweep_c(const KP &p, int cur, hipStream_t st)
         else if (fr == 2) MARCH_GO(2, false);
         else MARCH_GO(3, false);
 #undef MARCH_GO
-    } else { // LDS-tiled float64 reference variant (A/B and cross-check: ANTSRL_SWEEP_TILED=1)
-        const int fr = p.filter_radius;
-        const size_t lds = (size_t)(SW_TX + 2 * fr) * (SW_TY + 2 * fr) * C * sizeof(float);
-        dim3 grid((p.H + SW_TY - 1) / SW_TY, (p.W + SW_TX - 1) / SW_TX, p.E);
-        hipLaunchKernelGGL((k_sweep_tiled<C>), grid, dim3(256), lds, st, p, in, out);
     }
     return hipGetLastError();
 }

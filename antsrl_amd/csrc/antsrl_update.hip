@@ -54,8 +54,7 @@ static size_t update_lds_bytes(const KP &p, int threads) { return update_scratch
 // phases: UPD_ALL (one Environment.update) or a subset of its steps (antsrl_update_phase: the per-phase loop kernel runs them)
 hipError_t antsrl_launch_update(const KP &p, const double *jitter, int out_buf, hipStream_t st, int phases)
 {
-    static const bool force_loops = PROF_ENV("ANTSRL_UPDATE_LOOPS") != nullptr; // A/B: the per-phase loop kernel
-    if (p.N <= 1024 && !force_loops && phases == UPD_ALL) { // one ant per thread
+    if (p.N <= 1024 && phases == UPD_ALL) { // one ant per thread
         const int t1 = (p.N + 63) / 64 * 64;
         const size_t l1 = update_one_lds_bytes(p.HT, p.R, t1 / 64, p.N);
         switch (p.C) {

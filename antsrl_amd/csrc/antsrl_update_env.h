@@ -1,5 +1,5 @@
 // antsrl_update_env.h — the update phases of ONE environment as a device function: used by k_update
-// (antsrl_update.hip) and, fused, at the tail of k_act (antsrl_act.hip).
+// (antsrl_update.hip); k_act sizes its LDS union with update_scratch_bytes() (antsrl_act.hip).
 #pragma once
 #include "antsrl_util.h"
 
@@ -28,7 +28,7 @@ __device__ __forceinline__ uint32_t block_excl_scan_flag(bool flag, uint32_t *wa
 }
 
 // The update phases of ONE environment, run by the whole workgroup.  `smem` is
-// update_scratch_bytes() of LDS.  Called by k_update and, fused, at the tail of k_act.
+// update_scratch_bytes() of LDS.  Called by k_update.
 // `phases` (UPD_*): which of the reference's update steps this call runs — Walls.update (step -1), CircleObstacles.update
 // (0), Ants.update (999), Anthill.update (1000); all of them = one Environment.update.  antsrl_update_phase
 // (include/antsrl.h) enqueues them one launch at a time so that HOST EnvObjects of the caller can run between them in

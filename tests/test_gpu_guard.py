@@ -94,8 +94,7 @@ def test_flush_makes_the_workspace_consistent():
     init = synth_init(cfg, seed=4, n_food_discs=5, food_rmin=2, food_rmax=5)
     rot, ph = random_actions(cfg, 3, seed=1)
     a, b = BatchedAntsEnv(cfg), BatchedAntsEnv(cfg)
-    if a.query(cm.Q_DEFERRED_UPDATE) != 1:
-        pytest.skip("updates are not deferred on this path (profiling switch)")
+    assert a.query(cm.Q_DEFERRED_UPDATE) == 1
     for env in (a, b):
         env.reset(init)
         for t in range(3):

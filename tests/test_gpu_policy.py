@@ -81,11 +81,12 @@ def test_policy_on_bfloat16_observations_matches_float32_path():
         assert torch.equal(la, lb) and torch.equal(ra, rb) and torch.equal(pa, pb)
 
 
-@pytest.mark.parametrize("F", [4, 9, 62, 63, 64, 65, 66, 127, 128, 130, 343, 1000])
+@pytest.mark.parametrize("F", [4, 9, 62, 63, 64, 65, 66, 127, 128, 130, 343, 894, 895, 896, 958, 1000, 1022])
 def test_policy_feature_sizes_and_row_counts(F):
     """Chunk boundaries of the streamed rows: feature counts around multiples of 64 (whole chunks, a
     partial last chunk, the two agent_state inputs alone in the last chunk), row counts that are not a
-    multiple of the 32-ant tile, float32 and bfloat16 observations."""
+    multiple of the 32-ant tile, float32 and bfloat16 observations.  F > 848 takes the chunked kernel (k_policy_mlp: the
+    flat kernel's LDS image no longer fits), 894 .. 1022 on and around its chunk boundaries."""
     import torch
     from antsrl_amd import config as cm
     from antsrl_amd.batched import BatchedAntsEnv
@@ -178,8 +179,7 @@ def test_inloop_policy_equals_standalone_kernel(E, N, W, H, R, filt):
     cfg = cm.make_cfg(E, N, W, H, **kw)
     init = synth_init(cfg, seed=5, n_food_discs=6, food_rmin=3, food_rmax=6)
     env = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)
-    if env.query(cm.Q_PERCEIVE_RUN) * 4 > 32:
-        pytest.skip("more than 32 ants per k_perceive workgroup (a profiling-library switch): no in-loop policy")
+    assert env.query(cm.Q_PERCEIVE_RUN) * 4 <= 32, "the in-loop policy needs a 32-ant tile per workgroup"
     plain = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)  # the same run without the in-loop policy
     env.reset(init)
     plain.reset(init)
@@ -275,8 +275,7 @@ def test_act_only_inloop_policy_full_config5_shard():
     b = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)   # in-loop policy, act-only
     c = BatchedAntsEnv(cfg)                             # float32 observations: what the reference's net would read
     assert a.query(cm.Q_CELL_META)
-    if a.query(cm.Q_PERCEIVE_RUN) * 4 > 32:
-        pytest.skip("more than 32 ants per k_perceive workgroup (a profiling-library switch): no in-loop policy")
+    assert a.query(cm.Q_PERCEIVE_RUN) * 4 <= 32, "the in-loop policy needs a 32-ant tile per workgroup"
     pols = []
     for env in (a, b):
         env.reset(init)
