@@ -16,9 +16,14 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_step_update", "antsrl_set_timing_events", "antsrl_set_activation", "antsrl_policy_mlp", "antsrl_read_state", "antsrl_state_bytes",
            "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_mem_alloc", "antsrl_mem_free",
            "antsrl_mem_trim", "antsrl_mem_stats", "antsrl_update_phase",
-           "antsrl_perceptive_field")
+           "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory")
 
 _lib = None
+
+
+class AntsMemNetShape(C.Structure):
+    """include/antsrl.h AntsMemNetShape."""
+    _fields_ = [(n, C.c_int32) for n in ("n_features", "agent_dim", "mem_size", "h1", "h2", "h3", "n_rot", "n_ph")]
 
 
 class AntsrlError(RuntimeError):
@@ -68,6 +73,9 @@ def load() -> C.CDLL:
     lib.antsrl_mem_free.argtypes = [vp]
     lib.antsrl_mem_trim.argtypes = []
     lib.antsrl_mem_stats.argtypes = [C.POINTER(C.c_size_t)] * 4
+    lib.antsrl_memnet_packed_bytes.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(C.c_size_t)]
+    lib.antsrl_memnet_pack.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]
+    lib.antsrl_policy_memory.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -12,6 +12,7 @@
 #include <new>
 
 #include "antsrl_device.h"
+#include "antsrl_memnet.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
@@ -832,6 +833,73 @@ extern "C" int antsrl_policy_mlp(AntsHandle *h, const float *obs, const float *a
     hipError_t e = antsrl_launch_policy(obs, agent_state, w1, b1, w2, b2, w3, b3, rotation, pheromone, logits,
                                         (int)n_ants, n_features, (hipStream_t)stream, h && h->obs_bf16);
     if (e != hipSuccess) return hip_fail(e, "policy_mlp");
+    return ANTSRL_OK;
+}
+
+// ---- memory agent net (antsrl_memnet.hip)
+static int memnet_check(const AntsMemNetShape *s, MemNetDims *d, const char *who)
+{
+    if (!s) return fail(ANTSRL_E_INVALID, "%s: NULL shape", who);
+    if (s->n_features < 1 || s->agent_dim < 1 || s->mem_size < 1 || s->h1 < 1 || s->h2 < 1 || s->h3 < 1 || s->n_rot < 1 ||
+        s->n_ph < 1)
+        return fail(ANTSRL_E_INVALID, "%s: n_features, agent_dim, mem_size, h1, h2, h3, n_rot, n_ph must be >= 1", who);
+    const long long D = (long long)s->n_features + s->agent_dim + s->mem_size;
+    if (D > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: D = n_features + agent_dim + mem_size = %lld > 1024", who, D);
+    if (s->agent_dim > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: agent_dim %d > 32", who, s->agent_dim);
+    if (s->mem_size > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: mem_size %d > 32", who, s->mem_size);
+    if (s->h1 % 32 || s->h2 % 32 || s->h3 % 32 || s->h1 > 256 || s->h2 > 256 || s->h3 > 256)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: h1, h2, h3 (%d, %d, %d) must be multiples of 32 and <= 256", who, s->h1, s->h2,
+                    s->h3);
+    if (s->n_rot > 32 || s->n_ph > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_rot, n_ph (%d, %d) must be <= 32", who, s->n_rot, s->n_ph);
+    *d = MemNetDims{s->n_features, s->agent_dim, s->mem_size, (int)D, s->h1, s->h2, s->h3, s->n_rot, s->n_ph};
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, "memnet_packed_bytes");
+    if (rc != ANTSRL_OK) return rc;
+    if (!bytes) return fail(ANTSRL_E_INVALID, "memnet_packed_bytes: NULL bytes");
+    MemNetLayout L;
+    antsrl_memnet_layout(d, &L);
+    *bytes = L.bytes;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, "memnet_pack");
+    if (rc != ANTSRL_OK) return rc;
+    if (!params || !packed) return fail(ANTSRL_E_INVALID, "memnet_pack: params and packed are required");
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "memnet_pack: packed must be 256-byte aligned");
+    MemNetParams P;
+    for (int i = 0; i < 26; ++i) {
+        if (!params[i]) return fail(ANTSRL_E_INVALID, "memnet_pack: params[%d] is NULL", i);
+        P.p[i] = params[i];
+    }
+    hipError_t e = antsrl_launch_memnet_pack((unsigned char *)packed, P, d, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "memnet_pack");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const void *obs, int obs_format,
+                                    const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
+                                    int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, "policy_memory");
+    if (rc != ANTSRL_OK) return rc;
+    if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
+        return fail(ANTSRL_E_INVALID, "policy_memory: packed, obs, agent_state, mem_in, mem_out, rotation are required");
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "policy_memory: packed must be 256-byte aligned");
+    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
+        return fail(ANTSRL_E_INVALID, "policy_memory: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16");
+    if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "policy_memory: n_ants must be in [1, 2^31)");
+    hipError_t e = antsrl_launch_memnet((const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
+                                        mem_in, (int)n_ants, mem_out, rotation, pheromone, q_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "policy_memory");
     return ANTSRL_OK;
 }
 

@@ -107,3 +107,139 @@ class LinearPolicy:
     def detach(self, env) -> None:
         _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, None, None, None, None, None, None, None, None, None),
                    "set_inloop_policy")
+
+
+#: CollectModelMemory's parameters in its state_dict order (agents/collect_agent_memory.py:39-55): the order
+#: antsrl_memnet_pack takes them in
+MEMNET_LAYERS = ("layer1", "layer2", "layer3", "layer4", "rotation_layer1", "rotation_layer2", "rotation_layer3",
+                 "pheromone_layer1", "pheromone_layer2", "memory_layer1", "memory_layer2", "memory_layer3", "forget_layer")
+
+
+def memnet_shape_from_state_dict(sd) -> dict:
+    """power, mem_size, n_rot, n_ph and n_features of a CollectModelMemory state_dict, from its shapes alone
+    (layer1: h2 x D with h2 = 2^(2+power); memory_layer3: mem_size x h2; D = n_features + 2 + mem_size)."""
+    shp = {k: tuple(torch.as_tensor(v).shape) for k, v in sd.items()}
+    h2, D = shp["layer1.weight"]
+    power = int(round(math.log2(h2))) - 2
+    assert h2 == 2 ** (2 + power), "layer1 width %d is not a power of two" % h2
+    mem = shp["memory_layer3.weight"][0]
+    return dict(power=power, mem_size=mem, n_rot=shp["rotation_layer3.weight"][0], n_ph=shp["pheromone_layer2.weight"][0],
+                n_features=D - 2 - mem)
+
+
+def memnet_param_shapes(n_features: int, power: int, mem_size: int, n_rot: int, n_ph: int) -> dict:
+    """name -> (out, in) of every Linear of CollectModelMemory (collect_agent_memory.py:39-55)."""
+    D, h1, h2, h3 = n_features + 2 + mem_size, 2 ** (1 + power), 2 ** (2 + power), 2 ** (3 + power)
+    return dict(layer1=(h2, D), layer2=(h3, h2), layer3=(h1, h3), layer4=(D, h1), rotation_layer1=(h2, D),
+                rotation_layer2=(h3, h2), rotation_layer3=(n_rot, h3), pheromone_layer1=(h1, D), pheromone_layer2=(n_ph, h1),
+                memory_layer1=(h2, D), memory_layer2=(h2, h2), memory_layer3=(mem_size, h2), forget_layer=(mem_size, h2))
+
+
+class MemoryPolicy:
+    """The reference's recurrent memory agent net `CollectModelMemory` (agents/collect_agent_memory.py:24-78, the net
+    main.py's CollectAgentMemory trains) evaluated on the device by the bf16 MFMA kernel `antsrl_policy_memory`.
+
+    Weights are nn.Linear-initialised (seeded) or loaded with load_state_dict from the reference's own state_dict (its
+    parameter names; power and mem_size are inferred from the shapes, so the shipped checkpoints load as they are).
+    `memory` is the per-ant recurrent state (float32 [M, mem_size] on the device, zeros when first used and after
+    reset_memory()): the reference zeros it once in setup (:111), not per episode."""
+
+    def __init__(self, n_features: int, device, power: int = 5, mem_size: int = 20, n_rot: int = 3, n_ph: int = 3,
+                 seed: int = 0):
+        g = torch.Generator(device="cpu")
+        g.manual_seed(seed)
+        self.n_features = n_features
+        self.device = torch.device(device)
+        sd = {}
+        for name, (out_f, in_f) in memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph).items():
+            b = 1.0 / math.sqrt(in_f)  # nn.Linear's default init
+            sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
+            sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
+        self._lib = _lib.load()
+        self.memory = None
+        self._rot = self._ph = None
+        self._set(sd, power, mem_size, n_rot, n_ph)
+
+    def _set(self, sd, power, mem_size, n_rot, n_ph):
+        self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
+        self.params = {k: torch.as_tensor(v).to(self.device, torch.float32).contiguous() for k, v in sd.items()}
+        self.shape = _lib.AntsMemNetShape(self.n_features, 2, mem_size, 2 ** (1 + power), 2 ** (2 + power),
+                                          2 ** (3 + power), n_rot, n_ph)
+        n = C.c_size_t()
+        _lib.check(self._lib.antsrl_memnet_packed_bytes(C.byref(self.shape), C.byref(n)), "memnet_packed_bytes")
+        if self.memory is not None and self.memory.shape[1] != mem_size:
+            self.memory = None
+        self.packed = None
+        if self.device.type != "cuda":  # weights only (no kernel can run on them)
+            return
+        self.packed = torch.empty((n.value,), dtype=torch.uint8, device=self.device)  # torch blocks are 512-byte aligned
+        ptrs = (C.c_void_p * 26)(*[self.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS for w in ("weight", "bias")])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memnet_pack(C.byref(self.shape), ptrs, C.c_void_p(self.packed.data_ptr()),
+                                                    self._stream()), "memnet_pack")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def state_dict(self) -> dict:
+        return dict(self.params)
+
+    def load_state_dict(self, sd) -> None:
+        """A CollectModelMemory state_dict (the reference's parameter names, e.g. torch.load('good_model.h5') or
+        target_model.state_dict()); power, mem_size and the head sizes come from its shapes, then the weights are
+        repacked."""
+        shp = memnet_shape_from_state_dict(sd)
+        assert shp["n_features"] == self.n_features, "state_dict is for %d features, not %d" % (shp["n_features"], self.n_features)
+        want = memnet_param_shapes(self.n_features, shp["power"], shp["mem_size"], shp["n_rot"], shp["n_ph"])
+        for name, (o, i) in want.items():
+            assert tuple(sd[name + ".weight"].shape) == (o, i) and tuple(sd[name + ".bias"].shape) == (o,), name
+        self._set({k: sd[k] for l in MEMNET_LAYERS for k in (l + ".weight", l + ".bias")}, shp["power"], shp["mem_size"],
+                  shp["n_rot"], shp["n_ph"])
+
+    def reset_memory(self, n_ants: Optional[int] = None) -> None:
+        """Zeros the carried memory (CollectAgentMemory.setup, :111); `n_ants` (re)sizes it."""
+        m = n_ants if n_ants is not None else (self.memory.shape[0] if self.memory is not None else None)
+        self.memory = None if m is None else torch.zeros((m, self.mem_size), dtype=torch.float32, device=self.device)
+
+    def act(self, obs: torch.Tensor, agent_state: torch.Tensor, memory: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, env=None):
+        """CollectAgentMemory.get_action's network branch (:191-200): obs [..., P, P, K] float32 (or bfloat16 from a
+        BatchedAntsEnv(obs_dtype=torch.bfloat16)), agent_state float32 [..., 2] on the device ->
+        (rotation int8 [...], pheromone int8 [...], new_memory float32 [M, mem_size]).
+
+        The old memory is `memory`, or `self.memory` when None (zeros on first use).  The new memory goes to `out` when
+        given (the old one stays intact, as update_replay_memory wants it, :178-185), else in place over the old one.
+        `q` (float32 [M, n_rot + n_ph]) receives both heads' outputs."""
+        assert self.packed is not None, "MemoryPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
+        lead = obs.shape[:-3]
+        m = 1
+        for d in lead:
+            m *= d
+        assert obs.is_contiguous() and agent_state.is_contiguous()
+        assert obs.dtype in (torch.float32, torch.bfloat16) and agent_state.dtype == torch.float32
+        if env is not None:
+            assert env.obs.dtype == obs.dtype, "obs and env.obs differ in dtype"
+        assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
+        if memory is None:
+            if self.memory is None or self.memory.shape[0] != m:
+                assert self.memory is None, "self.memory holds %d ants, not %d: reset_memory(n_ants)" % (self.memory.shape[0], m)
+                self.reset_memory(m)
+            memory = self.memory
+        assert memory.shape == (m, self.mem_size) and memory.dtype == torch.float32 and memory.is_contiguous()
+        dst = memory if out is None else out
+        assert dst.shape == (m, self.mem_size) and dst.dtype == torch.float32 and dst.is_contiguous()
+        if q is not None:
+            assert q.shape == (m, self.n_rot + self.n_ph) and q.dtype == torch.float32 and q.is_contiguous()
+        if self._rot is None or self._rot.numel() != m:
+            self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
+            self._ph = torch.empty((m,), dtype=torch.int8, device=self.device)
+
+        def p(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+
+        fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_policy_memory(C.byref(self.shape), p(self.packed), p(obs), fmt, p(agent_state),
+                                                      p(memory), m, p(dst), p(self._rot), p(self._ph), p(q), self._stream()),
+                       "policy_memory")
+        return self._rot.view(lead), self._ph.view(lead), dst

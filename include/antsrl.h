@@ -455,6 +455,48 @@ int antsrl_set_inloop_policy(AntsHandle *h, int32_t n_features, const float *w1,
                              const float *b2, const float *w3, const float *b3, int8_t *rotation_next,
                              int8_t *pheromone_next, void *stream);
 
+/* Recurrent memory agent net (no kernel counterpart in the reference; replaces the non-epsilon branch of
+ * CollectAgentMemory.get_action, agents/collect_agent_memory.py:189-208, which evaluates CollectModelMemory.forward,
+ * :57-78, on the host).  Per ant, x = cat[obs.view(F), agent_state(agent_dim), old_memory(mem_size)], D = F + agent_dim
+ * + mem_size:
+ *     g = L4(relu(L3(relu(L2(relu(L1(x))))))) + x            layer1 h2 x D, layer2 h3 x h2, layer3 h1 x h3, layer4 D x h1
+ *     q_rot = R3(R2(R1(g)))   q_ph = P2(P1(g))   m = M2(M1(g))    (no activations; widths as in the reference's class)
+ *     new_memory = tanh(M3(m)) * s + old_memory * (1 - s),  s = sigmoid(Fg(m))
+ *     rotation = argmax(q_rot) - n_rot / 2,  pheromone = argmax(q_ph)   (first maximum on ties)
+ * The reference's class has h1 = 2^(1+power), h2 = 2^(2+power), h3 = 2^(3+power) (power 5 in its code, 4 in its shipped
+ * checkpoints) and agent_dim = 2.  Precision: bf16 MFMA operands (weights rounded once, every layer input rounded at the
+ * MFMA), fp32 accumulation, fp32 biases / ReLU / residual (with the fp32 x) / tanh / sigmoid / blend; the carried memory
+ * is read and written as fp32 and never rounded.
+ * Supported: n_features >= 1, 1 <= agent_dim <= 32, 1 <= mem_size <= 32, D <= 1024, h1, h2, h3 multiples of 32 and
+ * <= 256, 1 <= n_rot, n_ph <= 32; ANTSRL_E_UNSUPPORTED for positive values outside that, ANTSRL_E_INVALID for
+ * values < 1 and missing pointers.  Validation happens before any HIP call. */
+typedef struct AntsMemNetShape {
+    int32_t n_features, agent_dim, mem_size, h1, h2, h3, n_rot, n_ph;
+} AntsMemNetShape;
+
+/* Size of the packed weights (host only; no HIP call).  With Dp = D rounded up to 32 and
+ * frag(i, o) = 1024 * (i / 16) * (o / 32) bytes (bf16 MFMA fragments), bias(o) = 4 * o, each block rounded up to 256:
+ *   the sum over the twelve packed layers (in, out) = (Dp, h2) (h2, h3) (h3, h1) (h1, Dp) (Dp, h2) (h2, h3) (h3, 32)
+ *   (Dp, h1) (h1, 32) (Dp, h2) (h2, h2) (h2, 64) of round256(frag(in, out)) + round256(bias(out)).
+ * 567 808 bytes at F = 294, power 5, mem_size 20; 236 032 at power 4, mem_size 10. */
+int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes);
+
+/* Converts the weights once into the kernel's private packed layout (one small kernel on `stream`).  params: host array
+ * of the 26 device pointers of CollectModelMemory.state_dict() in its order (float32, nn.Linear layouts): layer1..4,
+ * rotation_layer1..3, pheromone_layer1..2, memory_layer1..3, forget_layer, each .weight then .bias.  packed: device
+ * buffer of antsrl_memnet_packed_bytes bytes, 256-byte aligned. */
+int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream);
+
+/* The forward pass for n_ants ants (CollectAgentMemory.get_action's target_model call and torch.max, :194-200).
+ * obs: [n_ants][F], float32 (ANTSRL_OBS_F32) or bfloat16 (ANTSRL_OBS_BF16); agent_state float [n_ants][agent_dim];
+ * mem_in float [n_ants][mem_size] (the old memory, the tail of the reference's agent state, :57); mem_out float
+ * [n_ants][mem_size], may equal mem_in (each ant reads its own row before writing it: in place is bit-identical);
+ * rotation int8 [n_ants]; pheromone int8 [n_ants] or NULL; q_out float [n_ants][n_rot + n_ph] (rotation head then
+ * pheromone head) or NULL. */
+int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const void *obs, int obs_format,
+                         const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
+                         int8_t *pheromone, float *q_out, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
