@@ -16,7 +16,9 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_step_update", "antsrl_set_timing_events", "antsrl_set_activation", "antsrl_policy_mlp", "antsrl_read_state", "antsrl_state_bytes",
            "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_mem_alloc", "antsrl_mem_free",
            "antsrl_mem_trim", "antsrl_mem_stats", "antsrl_update_phase",
-           "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory")
+           "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory",
+           "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
+           "antsrl_memtrain_grad", "antsrl_memtrain_apply")
 
 _lib = None
 
@@ -76,6 +78,15 @@ def load() -> C.CDLL:
     lib.antsrl_memnet_packed_bytes.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(C.c_size_t)]
     lib.antsrl_memnet_pack.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]
     lib.antsrl_policy_memory.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    sz = C.POINTER(C.c_size_t)
+    lib.antsrl_memtrain_sizes.argtypes = [C.POINTER(AntsMemNetShape), C.c_int64, sz, sz, sz, sz]
+    lib.antsrl_memtrain_init.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]
+    lib.antsrl_memtrain_unpack.argtypes = [C.POINTER(AntsMemNetShape), vp, C.POINTER(vp), vp]
+    lib.antsrl_memtrain_copy.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, vp]
+    lib.antsrl_memtrain_grad.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64,
+                                         C.c_float, vp, vp, vp, vp]
+    lib.antsrl_memtrain_apply.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, C.c_int64, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

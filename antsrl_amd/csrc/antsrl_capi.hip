@@ -13,6 +13,7 @@
 
 #include "antsrl_device.h"
 #include "antsrl_memnet.h"
+#include "antsrl_memtrain.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
@@ -900,6 +901,156 @@ extern "C" int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed
     hipError_t e = antsrl_launch_memnet((const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
                                         mem_in, (int)n_ants, mem_out, rotation, pheromone, q_out, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "policy_memory");
+    return ANTSRL_OK;
+}
+
+// ---- memory agent training step (antsrl_memtrain.hip)
+#define MT_MAX_B (1 << 24)
+
+static int memtrain_state_check(const void *state, const char *who, const char *name)
+{
+    if (!state) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
+    if ((uintptr_t)state & 255) return fail(ANTSRL_E_INVALID, "%s: %s must be 256-byte aligned", who, name);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_sizes(const AntsMemNetShape *s, int64_t B, size_t *params_floats, size_t *trained_floats,
+                                     size_t *state_bytes, size_t *workspace_bytes)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, "memtrain_sizes");
+    if (rc != ANTSRL_OK) return rc;
+    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_sizes: B must be in [1, 2^24]");
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    MemTrainWork W;
+    antsrl_memtrain_work_layout(d, (int)B, &W);
+    if (params_floats) *params_floats = L.params_floats;
+    if (trained_floats) *trained_floats = L.trained_floats;
+    if (state_bytes) *state_bytes = L.bytes;
+    if (workspace_bytes) *workspace_bytes = W.bytes;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_init(const AntsMemNetShape *s, const float *const *params, void *state, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_init");
+    if (rc != ANTSRL_OK) return rc;
+    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_init: params is required");
+    for (int i = 0; i < 26; ++i)
+        if (!params[i]) return fail(ANTSRL_E_INVALID, "memtrain_init: params[%d] is NULL", i);
+    if ((rc = memtrain_state_check(state, "memtrain_init", "state")) != ANTSRL_OK) return rc;
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char *S = (unsigned char *)state;
+    hipError_t e = hipMemsetAsync(S, 0, L.bytes, st); // m = v = 0, zero padding everywhere (the packs' included)
+    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
+        const int l = i / 2;
+        const size_t n = i % 2 ? (size_t)L.out[l] : (size_t)L.out[l] * L.in[l];
+        const size_t off = L.poff[l] + (i % 2 ? (size_t)L.out[l] * L.in[l] : 0);
+        e = hipMemcpyAsync(S + off * 4, params[i], n * 4, hipMemcpyDeviceToDevice, st);
+    }
+    if (e == hipSuccess) e = antsrl_launch_memtrain_repack(d, S, st);
+    if (e != hipSuccess) return hip_fail(e, "memtrain_init");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_unpack(const AntsMemNetShape *s, const void *state, float *const *params, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_unpack");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_unpack", "state")) != ANTSRL_OK) return rc;
+    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_unpack: params is required");
+    for (int i = 0; i < 26; ++i)
+        if (!params[i]) return fail(ANTSRL_E_INVALID, "memtrain_unpack: params[%d] is NULL", i);
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const unsigned char *S = (const unsigned char *)state;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
+        const int l = i / 2;
+        const size_t n = i % 2 ? (size_t)L.out[l] : (size_t)L.out[l] * L.in[l];
+        const size_t off = L.poff[l] + (i % 2 ? (size_t)L.out[l] * L.in[l] : 0);
+        e = hipMemcpyAsync(params[i], S + off * 4, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    }
+    if (e != hipSuccess) return hip_fail(e, "memtrain_unpack");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_copy(const AntsMemNetShape *s, const void *src_state, void *dst_state, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_copy");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(src_state, "memtrain_copy", "src_state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(dst_state, "memtrain_copy", "dst_state")) != ANTSRL_OK) return rc;
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const unsigned char *S = (const unsigned char *)src_state;
+    unsigned char *T = (unsigned char *)dst_state;
+    if (S == T) return ANTSRL_OK;
+    hipError_t e = hipMemcpyAsync(T, S, L.params_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(T + L.pack_off, S + L.pack_off, L.bytes - L.pack_off, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "memtrain_copy");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_grad(const AntsMemNetShape *s, const void *state, const void *target_state,
+                                    const float *states, const float *agent_states, const int64_t *actions,
+                                    const float *rewards, const float *new_states, const float *new_agent_states,
+                                    const uint8_t *dones, const int64_t *idx, int64_t B, float discount, float *grads,
+                                    float *loss_out, void *workspace, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_grad");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_grad", "state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(target_state, "memtrain_grad", "target_state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(workspace, "memtrain_grad", "workspace")) != ANTSRL_OK) return rc;
+    if (!states || !agent_states || !actions || !rewards || !new_states || !new_agent_states || !dones)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: states, agent_states, actions, rewards, new_states, new_agent_states, "
+                                      "dones are required");
+    if (!grads || !loss_out) return fail(ANTSRL_E_INVALID, "memtrain_grad: grads and loss_out are required");
+    if (((uintptr_t)states | (uintptr_t)agent_states | (uintptr_t)new_states | (uintptr_t)new_agent_states |
+         (uintptr_t)rewards | (uintptr_t)grads | (uintptr_t)loss_out) & 3)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: float arrays must be 4-byte aligned");
+    if (((uintptr_t)actions | (uintptr_t)idx) & 7)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: actions and idx must be 8-byte aligned");
+    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_grad: B must be in [1, 2^24]");
+    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "memtrain_grad: discount is NaN");
+    const MemTrainBatch bt{states, agent_states, rewards, new_states, new_agent_states, actions, idx, dones};
+    hipError_t e = antsrl_launch_memtrain_grad(d, (const unsigned char *)state, (const unsigned char *)target_state, bt,
+                                               (int)B, discount, grads, loss_out, (unsigned char *)workspace,
+                                               (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "memtrain_grad");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *grads, int64_t step, double lr,
+                                     double beta1, double beta2, double eps, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_apply");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_apply", "state")) != ANTSRL_OK) return rc;
+    if (!grads) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads is required");
+    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads must be 4-byte aligned");
+    if (step < 1) return fail(ANTSRL_E_INVALID, "memtrain_apply: step must be >= 1");
+    if (!(lr >= 0.0) || !(lr < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: lr must be finite and >= 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(ANTSRL_E_INVALID, "memtrain_apply: beta1, beta2 must be in [0, 1)");
+    if (!(eps > 0.0) || !(eps < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: eps must be finite and > 0");
+    // torch.optim.Adam (single tensor): the bias corrections in double, then every scalar rounded to float by the op
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1, bc2_sqrt = pow(bc2, 0.5);
+    hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, (float)step_size, (float)bc2_sqrt,
+                                                (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                                                (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "memtrain_apply");
     return ANTSRL_OK;
 }
 

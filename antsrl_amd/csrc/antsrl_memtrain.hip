@@ -1,0 +1,584 @@
+// antsrl_memtrain.hip — one DQN training step of the memory agent net `CollectModelMemory` on the device: what the
+// reference's CollectAgentMemory.train (agents/collect_agent_memory.py:133-176) computes for a minibatch of B
+// transitions, as two stages.
+//
+//   grad   target forward on (new_states, new_agent_states) through the trunk and both Q heads (no memory head);
+//          model forward on (states, agent_states), keeping every layer output; per head
+//          y = r + discount * max(q') * (1 - done) and dL/dq = 2 (q - y) / (B n_head) at the taken action, 0 elsewhere
+//          (the reference's target tensor is the no-grad q with that one entry replaced, so every other entry of
+//          q - target is exactly 0); loss = sum over both heads of (q_a - y)^2 / (B n_head); backward through the heads
+//          into g, then L4, L3, L2, L1 with the ReLU masks; dW = sum_rows dOut^T In, db = sum_rows dOut into one flat
+//          fp32 buffer of the 18 trained tensors (state_dict order).  dx is not needed.
+//   apply  Adam (torch.optim.Adam's single-tensor arithmetic: m.lerp_(g, 1 - beta1), v = v beta2 + (1 - beta2) g g,
+//          p += -step_size m / (sqrt(v) / sqrt(bc2) + eps)) over the flat buffer, writing the fp32 masters, m, v and the
+//          bf16 operand packs the next grad stage reads.  The step size and bias corrections come from the host.
+// The memory head (memory_layer1-3, forget_layer) is not in the loss: the reference leaves its .grad None and Adam skips
+// it, so neither stage touches its masters (they are only ever copied, target := model).
+//
+// Precision contract (what tests/memory_train_ref.py::bf16_train_grads restates):
+//  - MFMA operands are bf16, accumulation fp32 (v_mfma_f32_32x32x16_bf16): the forward layer inputs (x, hidden values,
+//    g, head intermediates) and weights, the backward dOut operands and the saved activations of dW = dOut^T In;
+//  - biases, ReLU and its mask (from the fp32 output: relu(z) > 0 exactly when z > 0), the residual with the fp32 x, the
+//    TD target, dL/dq, the bias gradients (sums of the fp32 dOut), the loss and all of Adam are fp32;
+//  - the masters and Adam's m / v are fp32.  Every buffer between launches is fp32; operands are rounded to bf16 as
+//    they are loaded.
+//
+// Layout.  Every GEMM is one wave per 32 x 32 output tile (no LDS), C = A . B with A read as rows of an fp32 matrix (or
+// the gathered x) and B = W^T read from a bf16 pack with k contiguous: forward C[b][o] = sum_i In[b][i] W[o][i] (pack W),
+// backward data dIn[b][i] = sum_o dOut[b][o] W[o][i] (pack W^T).  The weight gradient dW[o][i] = sum_b dOut[b][o] In[b][i]
+// reduces over rows: each wave owns one tile of dW over a fixed chunk of rows and writes an fp32 partial; k_mt_finalize
+// sums the chunks in ascending order.  No floating-point atomics: the result is bit-identical from run to run.
+//
+// Launches per step: grad = 7 forward (target and model grouped) + 1 TD + 6 backward data + 1 weight gradient + 1
+// finalize = 16, apply = 1.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "antsrl_memtrain.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+
+#define MT_WAVES 4    // waves (independent output tiles) per workgroup
+#define MT_MAXP 4     // problems per grouped GEMM launch
+#define MT_MAXCHUNK 64
+#define MT_TD_BLOCK 256
+
+static inline size_t mt_al(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline int mt_r32(int v) { return (v + 31) / 32 * 32; }
+
+void antsrl_memtrain_state_layout(const MemNetDims &d, MemTrainLayout *L)
+{
+    const int out[MT_NP] = {d.h2, d.h3, d.h1, d.D, d.h2, d.h3, d.n_rot, d.h1, d.n_ph, d.h2, d.h2, d.mem, d.mem};
+    const int in[MT_NP] = {d.D, d.h2, d.h3, d.h1, d.D, d.h2, d.h3, d.D, d.h1, d.D, d.h2, d.h2, d.h2};
+    size_t off = 0, pe = 0;
+    for (int l = 0; l < MT_NP; ++l) {
+        L->out[l] = out[l];
+        L->in[l] = in[l];
+        L->poff[l] = off;
+        off += (size_t)out[l] * in[l] + out[l];
+        if (l == MT_NT - 1) L->trained_floats = off;
+    }
+    L->params_floats = off;
+    for (int l = 0; l < MT_NT; ++l) {
+        L->Np[l] = mt_r32(out[l]);
+        L->Kp[l] = mt_r32(in[l]);
+        L->woff[l] = pe;
+        pe += (size_t)L->Np[l] * L->Kp[l];
+        L->wtoff[l] = pe;
+        pe += (size_t)L->Np[l] * L->Kp[l];
+    }
+    L->pack_elems = pe;
+    L->m_off = mt_al(L->params_floats * 4, 256);
+    L->v_off = mt_al(L->m_off + L->trained_floats * 4, 256);
+    L->pack_off = mt_al(L->v_off + L->trained_floats * 4, 256);
+    L->bytes = mt_al(L->pack_off + pe * 2, 256);
+}
+
+void antsrl_memtrain_work_layout(const MemNetDims &d, int B, MemTrainWork *W)
+{
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const int Bp = mt_r32(B);
+    W->Bp = Bp;
+    // fixed row chunks for the weight gradient: at most MT_MAXCHUNK, each a multiple of 32 rows, at least 256 rows
+    int nch = (Bp + 255) / 256;
+    if (nch > MT_MAXCHUNK) nch = MT_MAXCHUNK;
+    W->chunk = mt_r32((Bp + nch - 1) / nch);
+    W->nchunk = (Bp + W->chunk - 1) / W->chunk;
+    size_t off = 0;
+    auto take = [&](size_t floats) { const size_t o = off; off = mt_al(off + floats, 64); return o; };
+    for (int n = 0; n < 2; ++n)
+        for (int l = 0; l < MT_NT; ++l) W->act[n][l] = take((size_t)Bp * L.Np[l]);
+    size_t *dout[MT_NT] = {&W->dh1, &W->dh2, &W->dh3, &W->dg, &W->dr1, &W->dr2, &W->dqr, &W->dp1, &W->dqp};
+    for (int l = 0; l < MT_NT; ++l) *dout[l] = take((size_t)Bp * L.Np[l]);
+    size_t pc = 0;
+    for (int l = 0; l < MT_NT; ++l) {
+        W->part_layer[l] = pc;
+        pc += (size_t)L.Np[l] * L.Kp[l] + L.Np[l];
+    }
+    W->part_chunk = pc;
+    W->part = take(pc * W->nchunk);
+    W->nloss = (Bp + MT_TD_BLOCK - 1) / MT_TD_BLOCK;
+    W->lossp = take(W->nloss);
+    W->bytes = off * 4;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// operands
+// ------------------------------------------------------------------------------------------------------------------
+struct MtX { // x = cat[obs.view(F), agent_state(A)] of B minibatch rows, read through idx straight from the replay arrays
+    const float *obs, *ag;
+    const int64_t *idx;
+    int B, F, A;
+};
+
+__device__ __forceinline__ float mt_x(const MtX &X, int b, int k)
+{
+    if (b >= X.B || k >= X.F + X.A) return 0.0f;
+    const size_t row = X.idx ? (size_t)X.idx[b] : (size_t)b;
+    return k < X.F ? X.obs[row * X.F + k] : X.ag[row * X.A + (k - X.F)];
+}
+
+__device__ __forceinline__ bf16x8 mt_row8(const float *p) // 8 consecutive fp32 (32-byte aligned) as bf16
+{
+    const float4 u = reinterpret_cast<const float4 *>(p)[0], v = reinterpret_cast<const float4 *>(p)[1];
+    bf16x8 r;
+    r[0] = (__bf16)u.x; r[1] = (__bf16)u.y; r[2] = (__bf16)u.z; r[3] = (__bf16)u.w;
+    r[4] = (__bf16)v.x; r[5] = (__bf16)v.y; r[6] = (__bf16)v.z; r[7] = (__bf16)v.w;
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// grouped GEMM: forward and backward data
+// ------------------------------------------------------------------------------------------------------------------
+struct MtProb {
+    const float *a; int lda;              // A rows [Bp][lda] fp32, or NULL: the gathered x of net `xnet`
+    const __bf16 *w; int ldw; int K;      // B(k, j) = w[j * ldw + k]; K a multiple of 32
+    const float *a2; int lda2;            // optional second segment, summed into the same accumulator (a2 NULL: none)
+    const __bf16 *w2; int ldw2; int K2;
+    const float *bias; int nb;            // fp32 bias of the nb real columns, or NULL
+    const float *mask; int ldm;           // output *= (mask > 0), or NULL
+    float *c; int ldc; int N;             // output [Bp][ldc], N columns (a multiple of 32)
+    int relu, resid, xnet;                // relu; add the fp32 x of net xnet (the residual); which x feeds A
+    int tiles, tile0;
+};
+struct MtGemm {
+    MtProb p[MT_MAXP];
+    MtX x[2]; // 0: target rows (new_states, new_agent_states), 1: model rows (states, agent_states)
+    int np;
+};
+
+__device__ __forceinline__ f32x16 mt_segment(f32x16 acc, const float *a, int lda, const MtX *X, const __bf16 *w, int ldw,
+                                             int K, int arow, int bcol, int h)
+{
+    const __bf16 *wp = w + (size_t)bcol * ldw + 8 * h;
+    if (a) {
+        const float *ap = a + (size_t)arow * lda + 8 * h;
+        for (int k0 = 0; k0 < K; k0 += 16)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mt_row8(ap + k0), *reinterpret_cast<const bf16x8 *>(wp + k0), acc, 0, 0, 0);
+    } else {
+        for (int k0 = 0; k0 < K; k0 += 16) {
+            bf16x8 av;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) av[j] = (__bf16)mt_x(*X, arow, k0 + 8 * h + j);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, *reinterpret_cast<const bf16x8 *>(wp + k0), acc, 0, 0, 0);
+        }
+    }
+    return acc;
+}
+
+__global__ void __launch_bounds__(64 * MT_WAVES) k_mt_gemm(MtGemm G)
+{
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wave = blockIdx.x * MT_WAVES + (threadIdx.x >> 6);
+    int pi = -1;
+#pragma unroll
+    for (int i = 0; i < MT_MAXP; ++i)
+        if (i < G.np && wave >= G.p[i].tile0 && wave < G.p[i].tile0 + G.p[i].tiles) pi = i;
+    if (pi < 0) return;
+    const MtProb &P = G.p[pi];
+    const int t = wave - P.tile0, ntn = P.N / 32;
+    const int m0 = (t / ntn) * 32, n0 = (t % ntn) * 32;
+    f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+    acc = mt_segment(acc, P.a, P.lda, &G.x[P.xnet], P.w, P.ldw, P.K, m0 + r, n0 + r, h);
+    if (P.a2) acc = mt_segment(acc, P.a2, P.lda2, &G.x[P.xnet], P.w2, P.ldw2, P.K2, m0 + r, n0 + r, h);
+    const int j = n0 + r;
+    const float bj = (P.bias && j < P.nb) ? P.bias[j] : 0.0f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const int i = m0 + 8 * (g >> 2) + 4 * h + (g & 3);
+        float v = acc[g] + bj;
+        if (P.resid) v = v + mt_x(G.x[P.xnet], i, j);
+        if (P.relu) v = fmaxf(v, 0.0f);
+        if (P.mask) v = P.mask[(size_t)i * P.ldm + j] > 0.0f ? v : 0.0f;
+        P.c[(size_t)i * P.ldc + j] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// TD targets, dL/dq and the loss partials: one thread per row
+// ------------------------------------------------------------------------------------------------------------------
+struct MtTd {
+    const float *tqr, *tqp, *qr, *qp; // target / model head outputs [Bp][32]
+    float *dqr, *dqp;                 // [Bp][32]
+    const float *rewards;
+    const int64_t *actions, *idx;
+    const uint8_t *dones;
+    float *lossp;
+    int B, n_rot, n_ph;
+    float discount, norm_r, norm_p, inv_r, inv_p; // norm = 2 / (B n_head), inv = 1 / (B n_head)
+};
+
+__device__ __forceinline__ float mt_max(const float *q, int n)
+{
+    float m = q[0];
+    for (int k = 1; k < n; ++k) m = q[k] > m ? q[k] : m;
+    return m;
+}
+
+__global__ void __launch_bounds__(MT_TD_BLOCK) k_mt_td(MtTd T)
+{
+    __shared__ float red[MT_TD_BLOCK];
+    const int b = blockIdx.x * MT_TD_BLOCK + threadIdx.x;
+    const int Bp = (T.B + 31) / 32 * 32;
+    float contrib = 0.0f;
+    if (b < Bp) {
+        float dr = 0.0f, dp = 0.0f;
+        int ar = -1, ap = -1;
+        if (b < T.B) {
+            const size_t row = T.idx ? (size_t)T.idx[b] : (size_t)b;
+            const int64_t a0 = T.actions[2 * row], a1 = T.actions[2 * row + 1];
+            const float rew = T.rewards[row], nd = T.dones[row] ? 0.0f : 1.0f;
+            const size_t o = (size_t)b * 32;
+            if (a0 >= 0 && a0 < T.n_rot) {
+                ar = (int)a0;
+                const float y = rew + (T.discount * mt_max(T.tqr + o, T.n_rot)) * nd;
+                dr = T.qr[o + ar] - y;
+            }
+            if (a1 >= 0 && a1 < T.n_ph) {
+                ap = (int)a1;
+                const float y = rew + (T.discount * mt_max(T.tqp + o, T.n_ph)) * nd;
+                dp = T.qp[o + ap] - y;
+            }
+            contrib = dr * dr * T.inv_r + dp * dp * T.inv_p;
+        }
+        float4 *gr = reinterpret_cast<float4 *>(T.dqr + (size_t)b * 32), *gp = reinterpret_cast<float4 *>(T.dqp + (size_t)b * 32);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            float4 u, v;
+            u.x = 4 * c == ar ? dr * T.norm_r : 0.0f; u.y = 4 * c + 1 == ar ? dr * T.norm_r : 0.0f;
+            u.z = 4 * c + 2 == ar ? dr * T.norm_r : 0.0f; u.w = 4 * c + 3 == ar ? dr * T.norm_r : 0.0f;
+            v.x = 4 * c == ap ? dp * T.norm_p : 0.0f; v.y = 4 * c + 1 == ap ? dp * T.norm_p : 0.0f;
+            v.z = 4 * c + 2 == ap ? dp * T.norm_p : 0.0f; v.w = 4 * c + 3 == ap ? dp * T.norm_p : 0.0f;
+            gr[c] = u;
+            gp[c] = v;
+        }
+    }
+    red[threadIdx.x] = contrib; // fixed-order tree: deterministic
+    __syncthreads();
+    for (int s = MT_TD_BLOCK / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) T.lossp[blockIdx.x] = red[0];
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// weight gradients: one wave per (row chunk, 32 x 32 tile of dW); the in-tile-0 waves also sum db over their chunk
+// ------------------------------------------------------------------------------------------------------------------
+struct MtWg {
+    const float *dy; int lddy;  // dOut [Bp][lddy]
+    const float *x; int ldx;    // In [Bp][ldx], or NULL: the gathered model x
+    int Np, Kp;
+    size_t off;                 // this layer's block in a chunk's partials
+    int tiles, tile0;           // (Np / 32) (Kp / 32) nchunk
+};
+struct MtWgrad {
+    MtWg p[MT_NT];
+    MtX x;
+    float *part;
+    size_t part_chunk;
+    int chunk, Bp, np;
+};
+
+__global__ void __launch_bounds__(64 * MT_WAVES) k_mt_wgrad(MtWgrad G)
+{
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wave = blockIdx.x * MT_WAVES + (threadIdx.x >> 6);
+    int pi = -1;
+    for (int i = 0; i < G.np; ++i)
+        if (wave >= G.p[i].tile0 && wave < G.p[i].tile0 + G.p[i].tiles) pi = i;
+    if (pi < 0) return;
+    const MtWg &P = G.p[pi];
+    const int tpc = (P.Np / 32) * (P.Kp / 32), t = wave - P.tile0;
+    const int c = t / tpc, o0 = ((t % tpc) / (P.Kp / 32)) * 32, i0 = ((t % tpc) % (P.Kp / 32)) * 32;
+    const int b0 = c * G.chunk, b1 = min(b0 + G.chunk, G.Bp);
+    f32x16 acc;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
+    for (int k0 = b0; k0 < b1; k0 += 16) {
+        bf16x8 av, bv;
+        const size_t kb = (size_t)(k0 + 8 * h);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) av[j] = (__bf16)P.dy[(kb + j) * P.lddy + o0 + r];
+        if (P.x) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bv[j] = (__bf16)P.x[(kb + j) * P.ldx + i0 + r];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bv[j] = (__bf16)mt_x(G.x, (int)kb + j, i0 + r);
+        }
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
+    }
+    float *out = G.part + (size_t)c * G.part_chunk + P.off;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) out[(size_t)(o0 + 8 * (g >> 2) + 4 * h + (g & 3)) * P.Kp + i0 + r] = acc[g];
+    if (i0 == 0 && h == 0) { // db over the chunk, fp32, rows in order
+        float s = 0.0f;
+        for (int b = b0; b < b1; ++b) s += P.dy[(size_t)b * P.lddy + o0 + r];
+        out[(size_t)P.Np * P.Kp + o0 + r] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// finalize: sum the chunk partials in ascending order into the flat gradient; the last thread sums the loss partials
+// ------------------------------------------------------------------------------------------------------------------
+struct MtLayers { // the trained layers' place in the flat buffer and in the partials / packs
+    size_t poff[MT_NT], woff[MT_NT], wtoff[MT_NT], part[MT_NT];
+    int out[MT_NT], in[MT_NT], Np[MT_NT], Kp[MT_NT];
+    size_t trained;
+};
+
+__device__ __forceinline__ int mt_layer_of(const MtLayers &T, size_t e)
+{
+    int l = 0;
+#pragma unroll
+    for (int i = 1; i < MT_NT; ++i) l = e >= T.poff[i] ? i : l;
+    return l;
+}
+
+__global__ void __launch_bounds__(256) k_mt_finalize(MtLayers T, const float *part, size_t part_chunk, int nchunk,
+                                                     float *grads, const float *lossp, int nloss, float *loss)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < T.trained) {
+        const int l = mt_layer_of(T, e);
+        const size_t k = e - T.poff[l], nw = (size_t)T.out[l] * T.in[l];
+        const size_t src = T.part[l] + (k < nw ? (k / T.in[l]) * T.Kp[l] + k % T.in[l] : (size_t)T.Np[l] * T.Kp[l] + (k - nw));
+        float s = 0.0f;
+        for (int c = 0; c < nchunk; ++c) s += part[(size_t)c * part_chunk + src];
+        grads[e] = s;
+    } else if (e == T.trained) {
+        float s = 0.0f;
+        for (int i = 0; i < nloss; ++i) s += lossp[i];
+        *loss = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// apply: Adam + repack (update = 0: repack only)
+// ------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_mt_adam(MtLayers T, float *params, float *m, float *v, __bf16 *pack,
+                                                 const float *grads, int update, float step_size, float bc2_sqrt,
+                                                 float w1, float beta2, float w2, float eps)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= T.trained) return;
+    float p = params[e];
+    if (update) {
+        const float g = grads[e];
+        float mm = m[e], vv = v[e];
+        mm = mm + w1 * (g - mm);                        // exp_avg.lerp_(grad, 1 - beta1)
+        vv = vv * beta2 + w2 * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+        const float denom = sqrtf(vv) / bc2_sqrt + eps; // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+        p = p + -step_size * (mm / denom);              // param.addcdiv_(exp_avg, denom, value=-step_size)
+        m[e] = mm;
+        v[e] = vv;
+        params[e] = p;
+    }
+    const int l = mt_layer_of(T, e);
+    const size_t k = e - T.poff[l];
+    if (k < (size_t)T.out[l] * T.in[l]) {
+        const int o = (int)(k / T.in[l]), i = (int)(k % T.in[l]);
+        const __bf16 pb = (__bf16)p;
+        pack[T.woff[l] + (size_t)o * T.Kp[l] + i] = pb;
+        pack[T.wtoff[l] + (size_t)i * T.Np[l] + o] = pb;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// launchers
+// ------------------------------------------------------------------------------------------------------------------
+static MtLayers mt_layers(const MemTrainLayout &L, const MemTrainWork *W)
+{
+    MtLayers T;
+    for (int l = 0; l < MT_NT; ++l) {
+        T.poff[l] = L.poff[l];
+        T.woff[l] = L.woff[l];
+        T.wtoff[l] = L.wtoff[l];
+        T.part[l] = W ? W->part_layer[l] : 0;
+        T.out[l] = L.out[l];
+        T.in[l] = L.in[l];
+        T.Np[l] = L.Np[l];
+        T.Kp[l] = L.Kp[l];
+    }
+    T.trained = L.trained_floats;
+    return T;
+}
+
+hipError_t antsrl_launch_memtrain_apply(const MemNetDims &d, unsigned char *state, const float *grads, float step_size,
+                                        float bc2_sqrt, float w1, float beta2, float w2, float eps, hipStream_t st)
+{
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const MtLayers T = mt_layers(L, nullptr);
+    const unsigned blocks = (unsigned)((L.trained_floats + 255) / 256);
+    hipLaunchKernelGGL(k_mt_adam, dim3(blocks), dim3(256), 0, st, T, reinterpret_cast<float *>(state),
+                       reinterpret_cast<float *>(state + L.m_off), reinterpret_cast<float *>(state + L.v_off),
+                       reinterpret_cast<__bf16 *>(state + L.pack_off), grads, grads ? 1 : 0, step_size, bc2_sqrt, w1, beta2,
+                       w2, eps);
+    return hipGetLastError();
+}
+
+hipError_t antsrl_launch_memtrain_repack(const MemNetDims &d, unsigned char *state, hipStream_t st)
+{
+    return antsrl_launch_memtrain_apply(d, state, nullptr, 0.0f, 1.0f, 0.1f, 0.999f, 0.001f, 1e-8f, st);
+}
+
+struct MtLaunch {
+    MtGemm G;
+    int tiles;
+};
+
+static void mt_add(MtLaunch &Lc, MtProb p, int Bp)
+{
+    p.tiles = (Bp / 32) * (p.N / 32);
+    p.tile0 = Lc.tiles;
+    Lc.tiles += p.tiles;
+    Lc.G.p[Lc.G.np++] = p;
+}
+
+static hipError_t mt_run(MtLaunch &Lc, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_mt_gemm, dim3((Lc.tiles + MT_WAVES - 1) / MT_WAVES), dim3(64 * MT_WAVES), 0, st, Lc.G);
+    return hipGetLastError();
+}
+
+hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char *state, const unsigned char *target,
+                                       const MemTrainBatch &bt, int B, float discount, float *grads, float *loss,
+                                       unsigned char *work, hipStream_t st)
+{
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    MemTrainWork W;
+    antsrl_memtrain_work_layout(d, B, &W);
+    const int Bp = W.Bp, A = d.A + d.mem;
+    float *wk = reinterpret_cast<float *>(work);
+    const unsigned char *net[2] = {target, state};
+    const float *par[2] = {reinterpret_cast<const float *>(target), reinterpret_cast<const float *>(state)};
+    auto Wp = [&](int n, int l) { return reinterpret_cast<const __bf16 *>(net[n] + L.pack_off) + L.woff[l]; };
+    auto WTp = [&](int n, int l) { return reinterpret_cast<const __bf16 *>(net[n] + L.pack_off) + L.wtoff[l]; };
+    auto bias = [&](int n, int l) { return par[n] + L.poff[l] + (size_t)L.out[l] * L.in[l]; };
+    auto act = [&](int n, int l) { return wk + W.act[n][l]; };
+    MtX X[2] = {{bt.new_states, bt.new_agent_states, bt.idx, B, d.F, A}, {bt.states, bt.agent_states, bt.idx, B, d.F, A}};
+    hipError_t e;
+
+    // forward, both nets grouped per layer: (layer, input layer or -1 for x, relu, residual)
+    const int fl[7][2] = {{0, -1}, {1, -1}, {2, -1}, {3, -1}, {4, 7}, {5, 8}, {6, -1}};
+    const int in_of[MT_NT] = {-1, 0, 1, 2, 3, 4, 5, 3, 7};
+    for (int s = 0; s < 7; ++s) {
+        MtLaunch Lc{};
+        Lc.G.x[0] = X[0];
+        Lc.G.x[1] = X[1];
+        for (int q = 0; q < 2; ++q) {
+            const int l = fl[s][q];
+            if (l < 0) continue;
+            for (int n = 0; n < 2; ++n) {
+                MtProb p{};
+                p.a = in_of[l] < 0 ? nullptr : act(n, in_of[l]);
+                p.lda = in_of[l] < 0 ? 0 : L.Np[in_of[l]];
+                p.xnet = n;
+                p.w = Wp(n, l);
+                p.ldw = L.Kp[l];
+                p.K = L.Kp[l];
+                p.bias = bias(n, l);
+                p.nb = L.out[l];
+                p.c = act(n, l);
+                p.ldc = L.Np[l];
+                p.N = L.Np[l];
+                p.relu = l < 3;
+                p.resid = l == 3;
+                mt_add(Lc, p, Bp);
+            }
+        }
+        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+    }
+
+    // TD targets and dL/dq
+    {
+        MtTd T;
+        T.tqr = act(0, 6); T.tqp = act(0, 8); T.qr = act(1, 6); T.qp = act(1, 8);
+        T.dqr = wk + W.dqr; T.dqp = wk + W.dqp;
+        T.rewards = bt.rewards; T.actions = bt.actions; T.idx = bt.idx; T.dones = bt.dones;
+        T.lossp = wk + W.lossp;
+        T.B = B; T.n_rot = d.n_rot; T.n_ph = d.n_ph;
+        T.discount = discount;
+        T.norm_r = (float)(2.0 / ((double)B * d.n_rot));
+        T.norm_p = (float)(2.0 / ((double)B * d.n_ph));
+        T.inv_r = (float)(1.0 / ((double)B * d.n_rot));
+        T.inv_p = (float)(1.0 / ((double)B * d.n_ph));
+        hipLaunchKernelGGL(k_mt_td, dim3(W.nloss), dim3(MT_TD_BLOCK), 0, st, T);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+
+    // backward data (model): dIn = dOut . W (pack W^T), masked by the ReLU of the layer that produced In
+    float *dout[MT_NT] = {wk + W.dh1, wk + W.dh2, wk + W.dh3, wk + W.dg, wk + W.dr1, wk + W.dr2, wk + W.dqr, wk + W.dp1, wk + W.dqp};
+    auto bwd = [&](int l) { // dOut of layer l -> dOut of its input layer
+        MtProb p{};
+        const int il = in_of[l];
+        p.a = dout[l]; p.lda = L.Np[l];
+        p.w = WTp(1, l); p.ldw = L.Np[l]; p.K = L.Np[l];
+        p.c = dout[il]; p.ldc = L.Np[il]; p.N = L.Np[il];
+        p.mask = il < 3 ? act(1, il) : nullptr; p.ldm = L.Np[il];
+        p.xnet = 1;
+        return p;
+    };
+    {
+        MtLaunch Lc{};
+        mt_add(Lc, bwd(6), Bp); // R3 -> dr2
+        mt_add(Lc, bwd(8), Bp); // P2 -> dp1
+        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+    }
+    {
+        MtLaunch Lc{};
+        mt_add(Lc, bwd(5), Bp); // R2 -> dr1
+        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+    }
+    {
+        MtLaunch Lc{};
+        MtProb p = bwd(4); // R1 + P1 -> dg
+        p.a2 = dout[7]; p.lda2 = L.Np[7];
+        p.w2 = WTp(1, 7); p.ldw2 = L.Np[7]; p.K2 = L.Np[7];
+        mt_add(Lc, p, Bp);
+        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+    }
+    for (int l = 3; l >= 1; --l) { // L4 -> dh3, L3 -> dh2, L2 -> dh1
+        MtLaunch Lc{};
+        mt_add(Lc, bwd(l), Bp);
+        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+    }
+
+    // weight gradients: row-chunk partials
+    {
+        MtWgrad G{};
+        G.x = X[1];
+        G.part = wk + W.part;
+        G.part_chunk = W.part_chunk;
+        G.chunk = W.chunk;
+        G.Bp = Bp;
+        int tiles = 0;
+        for (int l = 0; l < MT_NT; ++l) {
+            MtWg &p = G.p[G.np++];
+            p.dy = dout[l]; p.lddy = L.Np[l];
+            p.x = in_of[l] < 0 ? nullptr : act(1, in_of[l]);
+            p.ldx = in_of[l] < 0 ? 0 : L.Np[in_of[l]];
+            p.Np = L.Np[l]; p.Kp = L.Kp[l];
+            p.off = W.part_layer[l];
+            p.tiles = (L.Np[l] / 32) * (L.Kp[l] / 32) * W.nchunk;
+            p.tile0 = tiles;
+            tiles += p.tiles;
+        }
+        hipLaunchKernelGGL(k_mt_wgrad, dim3((tiles + MT_WAVES - 1) / MT_WAVES), dim3(64 * MT_WAVES), 0, st, G);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    {
+        const MtLayers T = mt_layers(L, &W);
+        const unsigned blocks = (unsigned)((L.trained_floats + 1 + 255) / 256);
+        hipLaunchKernelGGL(k_mt_finalize, dim3(blocks), dim3(256), 0, st, T, (const float *)(wk + W.part), W.part_chunk,
+                           W.nchunk, grads, (const float *)(wk + W.lossp), W.nloss, loss);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

@@ -1,0 +1,238 @@
+"""On-device DQN training of the memory agent net: CollectAgentMemory.train (agents/collect_agent_memory.py:133-176) as
+two HIP stages, `antsrl_memtrain_grad` (target and model forwards, TD targets, loss, backward into one flat fp32
+gradient buffer) and `antsrl_memtrain_apply` (Adam, then the bf16 operand repack).  See antsrl_memtrain.hip and
+DESIGN §7.7 for the precision contract.
+
+Each net lives in one device buffer (include/antsrl.h, antsrl_memtrain_sizes): the fp32 masters of the 26 state_dict
+tensors in its order, Adam's m and v for the 18 trained tensors, and the bf16 operand packs.  The memory head
+(memory_layer1-3, forget_layer) gets no gradient in the reference (its .grad stays None, so Adam skips it): it is never
+changed here either, and has no Adam state.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib
+from .policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_shapes, memnet_shape_from_state_dict
+
+#: the 9 layers the loss reaches (the first 18 tensors of the state_dict)
+TRAINED_LAYERS = MEMNET_LAYERS[:9]
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class MemoryTrainer:
+    """CollectAgentMemory's model, target model and optimizer on the device (defaults: the reference class's,
+    discount 0.5, lr 1e-4; main.py passes 0.99 and 1e-5).
+
+    `step(batch_or_replay, idx)` is one training step (grad + apply) and returns the loss as a 0-d device tensor;
+    `train(replay, done)` is CollectAgentMemory.train with the replay on the device.  `policy` is a MemoryPolicy holding
+    the TARGET net (get_action acts with the target net, :194), repacked at every sync_target()."""
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, power: int = 5, mem_size: int = 20, n_rot: int = 3,
+                 n_ph: int = 3, seed: int = 0, state_dict=None):
+        self.device = torch.device(device)
+        assert self.device.type == "cuda", "MemoryTrainer runs on the GPU"
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_features = n_features
+        self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
+        self.update_target_every = int(update_target_every)
+        self.target_update_counter = 0
+        self.syncs = 0
+        self.step_count = 0
+        if state_dict is not None:
+            shp = memnet_shape_from_state_dict(state_dict)
+            assert shp["n_features"] == n_features, "state_dict is for %d features, not %d" % (shp["n_features"], n_features)
+            power, mem_size, n_rot, n_ph = shp["power"], shp["mem_size"], shp["n_rot"], shp["n_ph"]
+        self.policy = MemoryPolicy(n_features, self.device, power=power, mem_size=mem_size, n_rot=n_rot, n_ph=n_ph,
+                                   seed=seed)
+        if state_dict is None:
+            state_dict = {k: v.clone() for k, v in self.policy.state_dict().items()}
+        self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
+        self.shape = self.policy.shape
+        self._lib = _lib.load()
+        pf, tf, sb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), 1, C.byref(pf), C.byref(tf), C.byref(sb), None),
+                   "memtrain_sizes")
+        self.params_floats, self.trained_floats, self.state_bytes = pf.value, tf.value, sb.value
+        self._model = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)  # 512-byte aligned blocks
+        self._target = torch.empty_like(self._model)
+        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
+        self._work = None
+        # the flat layout (include/antsrl.h): state_dict order, dense, weight then bias per layer
+        self._offs = {}
+        off = 0
+        for name, (o, i) in memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph).items():
+            self._offs[name + ".weight"] = (off, (o, i))
+            off += o * i
+            self._offs[name + ".bias"] = (off, (o,))
+            off += o
+        assert off == self.params_floats
+        self.load_state_dict(state_dict, _reset_adam=True)
+
+    # ---- layout views -------------------------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _views(self, buf, region="params"):
+        f = buf.view(torch.float32)
+        if region == "params":
+            base, names = 0, list(self._offs)
+        else:
+            pf = self.params_floats * 4
+            m_off = (pf + 255) // 256 * 256
+            v_off = (m_off + self.trained_floats * 4 + 255) // 256 * 256
+            base = (m_off if region == "m" else v_off) // 4
+            names = [k for k in self._offs if k.split(".")[0] in TRAINED_LAYERS]
+        return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + _numel(self._offs[k][1])].view(self._offs[k][1])
+                for k in names}
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def state_dict(self) -> dict:
+        """The model net's 26 tensors (copies), the reference's names and order."""
+        return {k: v.clone() for k, v in self._views(self._model).items()}
+
+    def target_state_dict(self) -> dict:
+        return {k: v.clone() for k, v in self._views(self._target).items()}
+
+    def load_state_dict(self, sd, _reset_adam: bool = False) -> None:
+        """CollectAgentMemory.load_model (:213-215): sets the model AND the target net (and the acting policy).  Adam's
+        state is kept, as the reference's optimizer keeps it."""
+        for k, (_, shp) in self._offs.items():
+            assert tuple(sd[k].shape) == shp, (k, tuple(sd[k].shape), shp)
+        src = {k: torch.as_tensor(sd[k]).to(self.device, torch.float32).contiguous() for k in self._offs}
+        ptrs = (C.c_void_p * 26)(*[src[k].data_ptr() for k in self._offs])
+        keep = None if _reset_adam else self._model[self._adam_range()].clone()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(self._model), self._stream()),
+                       "memtrain_init")
+            _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(self._target), self._stream()),
+                       "memtrain_init")
+        if keep is not None:
+            self._model[self._adam_range()] = keep
+        self._repack_policy()
+
+    def _adam_range(self):
+        pf = self.params_floats * 4
+        m_off = (pf + 255) // 256 * 256
+        v_off = (m_off + self.trained_floats * 4 + 255) // 256 * 256
+        return slice(m_off, v_off + self.trained_floats * 4)
+
+    def adam_state(self) -> dict:
+        """torch.optim.Adam's state for the 18 trained tensors: step, exp_avg, exp_avg_sq (copies)."""
+        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._model, "m").items()},
+                    exp_avg_sq={k: v.clone() for k, v in self._views(self._model, "v").items()})
+
+    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
+        """The flat gradient (self.grads by default) as views named like the 18 trained state_dict tensors."""
+        g = self.grads if grads is None else grads
+        return {k: g[o: o + _numel(shp)].view(shp) for k, (o, shp) in self._offs.items() if k.split(".")[0] in TRAINED_LAYERS}
+
+    def _repack_policy(self):
+        """policy := target net (a copy into the policy's own tensors, then antsrl_memnet_pack)."""
+        tv = self._views(self._target)
+        for k, dst in self.policy.params.items():
+            dst.copy_(tv[k])
+        ptrs = (C.c_void_p * 26)(*[self.policy.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS
+                                   for w in ("weight", "bias")])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memnet_pack(C.byref(self.shape), ptrs, _p(self.policy.packed), self._stream()),
+                       "memnet_pack")
+
+    def sync_target(self) -> None:
+        """target := model (:170-174), and the acting policy with it.  Adam's state is not copied."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memtrain_copy(C.byref(self.shape), _p(self._model), _p(self._target),
+                                                      self._stream()), "memtrain_copy")
+        self._repack_policy()
+        self.syncs += 1
+
+    # ---- the two stages -----------------------------------------------------------------------------------------
+    def _arrays(self, batch_or_replay):
+        r = batch_or_replay
+        if hasattr(r, "states"):
+            a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones)
+            n = len(r)
+        else:
+            a = tuple(r)
+            n = a[0].shape[0]
+        assert len(a) == 7
+        st, ast, act, rw, nst, nast, dn = a
+        N = st.shape[0]
+        for t, dt in ((st, torch.float32), (ast, torch.float32), (act, torch.int64), (rw, torch.float32),
+                      (nst, torch.float32), (nast, torch.float32), (dn, torch.bool)):
+            assert t.device == self.device and t.dtype == dt and t.is_contiguous() and t.shape[0] == N, (t.shape, t.dtype)
+        assert st[0].numel() == self.n_features and nst[0].numel() == self.n_features
+        assert ast.shape[1:] == (2 + self.mem_size,) and nast.shape[1:] == (2 + self.mem_size,)
+        assert act.shape[1:] == (2,) and rw.dim() == 1 and dn.dim() == 1
+        return a, n
+
+    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stage 1: the loss (0-d device tensor) and the gradients of the 18 trained tensors into self.grads.  Rows are
+        idx (int64 on the device, values in [0, len)) of a DeviceReplayMemory or of a 7-tuple of arrays (states,
+        agent_states, actions, rewards, new_states, new_agent_states, dones), or all rows when idx is None."""
+        a, n = self._arrays(batch_or_replay)
+        if idx is not None:
+            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
+            B = idx.numel()
+        else:
+            B = n
+        assert B >= 1
+        ws = C.c_size_t()
+        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), B, None, None, None, C.byref(ws)), "memtrain_sizes")
+        if self._work is None or self._work.numel() < ws.value:
+            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        st, ast, act, rw, nst, nast, dn = a
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memtrain_grad(C.byref(self.shape), _p(self._model), _p(self._target), _p(st), _p(ast),
+                                                      _p(act), _p(rw), _p(nst), _p(nast), _p(dn), _p(idx), B, self.discount,
+                                                      _p(self.grads), _p(loss), _p(self._work), self._stream()),
+                       "memtrain_grad")
+        return loss
+
+    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
+        """Stage 2: one Adam step over the flat gradient (self.grads by default), then the bf16 repack."""
+        g = self.grads if grads is None else grads
+        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == self.trained_floats and g.is_contiguous()
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_memtrain_apply(C.byref(self.shape), _p(self._model), _p(g), self.step_count, self.lr,
+                                                       self.betas[0], self.betas[1], self.eps, self._stream()),
+                       "memtrain_apply")
+
+    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One training step on the minibatch (grad, then apply): returns the loss as a 0-d device tensor."""
+        loss = self.grad(batch_or_replay, idx)
+        self.apply()
+        return loss
+
+    def train(self, replay, done: bool, minibatch: int = 264, min_replay: int = 1000,
+              generator: Optional[torch.Generator] = None):
+        """CollectAgentMemory.train (:133-176): 0 below min_replay, else a step on `minibatch` rows drawn on the device
+        (with replacement), then the target counter (host side: `done` is a host bool) and the sync."""
+        if len(replay) < min_replay:
+            return 0
+        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
+        loss = self.step(replay, idx)
+        if done:
+            self.target_update_counter += 1
+        if self.target_update_counter >= self.update_target_every:
+            self.sync_target()
+            self.target_update_counter = 0
+        return loss
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n

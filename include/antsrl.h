@@ -497,6 +497,62 @@ int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const voi
                          const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
                          int8_t *pheromone, float *q_out, void *stream);
 
+/* On-device DQN training step of the memory agent net (replaces CollectAgentMemory.train, agents/collect_agent_memory.py:
+ * 133-176: target forward, TD targets, MSE loss, backward, torch.optim.Adam).  Same shape and limits as
+ * antsrl_policy_memory; observations are float32 (what the replay stores).  Two stages, so that a data-parallel caller
+ * can reduce the gradient between them: antsrl_memtrain_grad (loss + flat gradient) and antsrl_memtrain_apply (Adam).
+ * Only the 9 layers the loss reaches are trained (layer1-4, rotation_layer1-3, pheromone_layer1-2: the first 18 tensors
+ * of the state_dict); the memory head is never changed and has no Adam state, as in the reference (its .grad is None).
+ * Precision: bf16 MFMA operands (weights, layer inputs, output gradients), fp32 accumulation, fp32 biases / ReLU masks /
+ * residual / TD target / dL/dq / bias gradients / loss / Adam, fp32 masters and moments.  No floating-point atomics:
+ * bit-identical from run to run.  Every argument is validated before any HIP call; nothing synchronises the host.
+ *
+ * A net's STATE is one device buffer of state_bytes, 256-byte aligned:
+ *   params  at 0: params_floats fp32, the 26 state_dict tensors in order, dense (weight [out][in], then bias [out])
+ *   m       at m_off = round256(4 params_floats): trained_floats fp32 (Adam's exp_avg of the first 18 tensors, same order)
+ *   v       at v_off = round256(m_off + 4 trained_floats): trained_floats fp32 (exp_avg_sq)
+ *   packs   at round256(v_off + 4 trained_floats): bf16, per trained layer W [r32(out)][r32(in)] then W^T, zero padded
+ *   state_bytes = round256(that + 2 x the pack elements), r32 = rounded up to 32.
+ * With D = n_features + agent_dim + mem_size, the 13 layers (out, in) are (h2, D) (h3, h2) (h1, h3) (D, h1) (h2, D)
+ * (h3, h2) (n_rot, h3) (h1, D) (n_ph, h1) | (h2, D) (h2, h2) (mem, h2) (mem, h2); params_floats = sum of out (in + 1)
+ * over all 13, trained_floats over the first 9 (205 442 and 267 690 at F = 294, power 5, mem_size 20).
+ * Workspace for B rows (Bp = r32(B)), in fp32 blocks each rounded up to 64 floats: 3 Bp r32(out) per trained layer
+ * (target and model outputs, model output gradients), nchunk x sum over trained layers of r32(out) (r32(in) + 1)
+ * (row-chunk gradient partials; nchunk = min(64, ceil(Bp / 256)) chunks of r32(ceil(Bp / nchunk)) rows, recounted as
+ * ceil(Bp / chunk)), and ceil(Bp / 256) loss partials.  1 <= B <= 2^24.  Outputs may be NULL. */
+int antsrl_memtrain_sizes(const AntsMemNetShape *s, int64_t B, size_t *params_floats, size_t *trained_floats,
+                          size_t *state_bytes, size_t *workspace_bytes);
+
+/* state := the 26 device tensors params[] (CollectModelMemory.state_dict() order, float32), m = v = 0, packs rebuilt. */
+int antsrl_memtrain_init(const AntsMemNetShape *s, const float *const *params, void *state, void *stream);
+
+/* The 26 masters of `state` into the device tensors params[] (state_dict order). */
+int antsrl_memtrain_unpack(const AntsMemNetShape *s, const void *state, float *const *params, void *stream);
+
+/* target := model (:170-174): masters and packs of src_state into dst_state; Adam's m and v are not copied. */
+int antsrl_memtrain_copy(const AntsMemNetShape *s, const void *src_state, void *dst_state, void *stream);
+
+/* Stage 1 for B rows idx[0..B) (int64, values in [0, N): the caller guarantees it; NULL = rows 0..B-1) of the replay
+ * arrays states float [N][n_features], agent_states float [N][agent_dim + mem_size], actions int64 [N][2] (rotation
+ * index = rotation + n_rot / 2, pheromone index), rewards float [N], new_states, new_agent_states, dones bool [N]:
+ *   y = r + discount * max(q_target(new)) * (1 - done) per head; loss = sum over the heads of mean over B x n_head of
+ *   (q - target)^2 with target = q except y at the taken action.  An action index outside [0, n_head) contributes
+ *   nothing (and is never used as an address).
+ * Writes loss_out (float, on the device) and grads (float [trained_floats], the gradients of the 18 trained tensors in
+ * the params layout).  `state` is the model, `target_state` the target net; workspace: antsrl_memtrain_sizes(B) bytes,
+ * 256-byte aligned.  7 forward launches (both nets grouped per layer) + TD + 6 backward + weight gradient + reduction. */
+int antsrl_memtrain_grad(const AntsMemNetShape *s, const void *state, const void *target_state, const float *states,
+                         const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                         const float *new_agent_states, const uint8_t *dones, const int64_t *idx, int64_t B,
+                         float discount, float *grads, float *loss_out, void *workspace, void *stream);
+
+/* Stage 2: one torch.optim.Adam step (no weight decay, not amsgrad) over grads (float [trained_floats]) for optimizer
+ * step `step` >= 1: m.lerp_(g, 1 - beta1); v = v beta2 + (1 - beta2) g^2; p -= lr / (1 - beta1^step) x
+ * m / (sqrt(v) / sqrt(1 - beta2^step) + eps), the scalars computed in double on the host and rounded to float.  Then
+ * the bf16 packs.  One launch. */
+int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *grads, int64_t step, double lr,
+                          double beta1, double beta2, double eps, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
