@@ -18,7 +18,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_mem_trim", "antsrl_mem_stats", "antsrl_update_phase",
            "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory",
            "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
-           "antsrl_memtrain_grad", "antsrl_memtrain_apply")
+           "antsrl_memtrain_grad", "antsrl_memtrain_apply", "antsrl_memnet_packed_bytes_ex", "antsrl_memnet_pack_ex",
+           "antsrl_policy_memory_ex")
 
 _lib = None
 
@@ -78,6 +79,10 @@ def load() -> C.CDLL:
     lib.antsrl_memnet_packed_bytes.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(C.c_size_t)]
     lib.antsrl_memnet_pack.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]
     lib.antsrl_policy_memory.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
+    lib.antsrl_memnet_packed_bytes_ex.argtypes = [C.POINTER(AntsMemNetShape), i32, C.POINTER(C.c_size_t)]
+    lib.antsrl_memnet_pack_ex.argtypes = [C.POINTER(AntsMemNetShape), i32, C.POINTER(vp), vp, vp]
+    lib.antsrl_policy_memory_ex.argtypes = [C.POINTER(AntsMemNetShape), i32, vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp,
+                                            vp, vp]
     sz = C.POINTER(C.c_size_t)
     lib.antsrl_memtrain_sizes.argtypes = [C.POINTER(AntsMemNetShape), C.c_int64, sz, sz, sz, sz]
     lib.antsrl_memtrain_init.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]

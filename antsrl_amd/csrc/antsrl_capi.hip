@@ -856,52 +856,108 @@ static int memnet_check(const AntsMemNetShape *s, MemNetDims *d, const char *who
     return ANTSRL_OK;
 }
 
-extern "C" int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes)
+// precision: ANTSRL_MEMNET_BF16 (k_memnet) or ANTSRL_MEMNET_FP32 (k_memnet_f32), checked before anything else
+static int memnet_precision(int precision, const char *who)
+{
+    if (precision != ANTSRL_MEMNET_BF16 && precision != ANTSRL_MEMNET_FP32)
+        return fail(ANTSRL_E_INVALID, "%s: precision %d is neither ANTSRL_MEMNET_BF16 (0) nor ANTSRL_MEMNET_FP32 (1)", who,
+                    precision);
+    return ANTSRL_OK;
+}
+
+static int memnet_packed_bytes(const AntsMemNetShape *s, int precision, size_t *bytes, const char *who)
 {
     MemNetDims d;
-    const int rc = memnet_check(s, &d, "memnet_packed_bytes");
+    const int rc = memnet_check(s, &d, who);
     if (rc != ANTSRL_OK) return rc;
-    if (!bytes) return fail(ANTSRL_E_INVALID, "memnet_packed_bytes: NULL bytes");
+    if (!bytes) return fail(ANTSRL_E_INVALID, "%s: NULL bytes", who);
     MemNetLayout L;
-    antsrl_memnet_layout(d, &L);
+    if (precision == ANTSRL_MEMNET_FP32)
+        antsrl_memnet_layout_f32(d, &L);
+    else
+        antsrl_memnet_layout(d, &L);
     *bytes = L.bytes;
     return ANTSRL_OK;
 }
 
-extern "C" int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream)
+static int memnet_pack(const AntsMemNetShape *s, int precision, const float *const *params, void *packed, void *stream,
+                       const char *who)
 {
     MemNetDims d;
-    const int rc = memnet_check(s, &d, "memnet_pack");
+    const int rc = memnet_check(s, &d, who);
     if (rc != ANTSRL_OK) return rc;
-    if (!params || !packed) return fail(ANTSRL_E_INVALID, "memnet_pack: params and packed are required");
-    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "memnet_pack: packed must be 256-byte aligned");
+    if (!params || !packed) return fail(ANTSRL_E_INVALID, "%s: params and packed are required", who);
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
     MemNetParams P;
     for (int i = 0; i < 26; ++i) {
-        if (!params[i]) return fail(ANTSRL_E_INVALID, "memnet_pack: params[%d] is NULL", i);
+        if (!params[i]) return fail(ANTSRL_E_INVALID, "%s: params[%d] is NULL", who, i);
         P.p[i] = params[i];
     }
-    hipError_t e = antsrl_launch_memnet_pack((unsigned char *)packed, P, d, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "memnet_pack");
+    hipError_t e = precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_pack_f32((unsigned char *)packed, P, d, (hipStream_t)stream)
+                                                   : antsrl_launch_memnet_pack((unsigned char *)packed, P, d, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, who);
     return ANTSRL_OK;
+}
+
+static int policy_memory(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
+                         const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
+                         int8_t *pheromone, float *q_out, void *stream, const char *who)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
+        return fail(ANTSRL_E_INVALID, "%s: packed, obs, agent_state, mem_in, mem_out, rotation are required", who);
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
+    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
+        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
+    if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [1, 2^31)", who);
+    hipError_t e = (precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32 : antsrl_launch_memnet)(
+        (const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state, mem_in, (int)n_ants, mem_out,
+        rotation, pheromone, q_out, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, who);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes)
+{
+    return memnet_packed_bytes(s, ANTSRL_MEMNET_BF16, bytes, "memnet_packed_bytes");
+}
+
+extern "C" int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream)
+{
+    return memnet_pack(s, ANTSRL_MEMNET_BF16, params, packed, stream, "memnet_pack");
 }
 
 extern "C" int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const void *obs, int obs_format,
                                     const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
                                     int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
 {
-    MemNetDims d;
-    const int rc = memnet_check(s, &d, "policy_memory");
-    if (rc != ANTSRL_OK) return rc;
-    if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
-        return fail(ANTSRL_E_INVALID, "policy_memory: packed, obs, agent_state, mem_in, mem_out, rotation are required");
-    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "policy_memory: packed must be 256-byte aligned");
-    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "policy_memory: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16");
-    if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "policy_memory: n_ants must be in [1, 2^31)");
-    hipError_t e = antsrl_launch_memnet((const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
-                                        mem_in, (int)n_ants, mem_out, rotation, pheromone, q_out, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "policy_memory");
-    return ANTSRL_OK;
+    return policy_memory(s, ANTSRL_MEMNET_BF16, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out, rotation,
+                         pheromone, q_out, stream, "policy_memory");
+}
+
+extern "C" int antsrl_memnet_packed_bytes_ex(const AntsMemNetShape *s, int precision, size_t *bytes)
+{
+    const int rc = memnet_precision(precision, "memnet_packed_bytes_ex");
+    return rc != ANTSRL_OK ? rc : memnet_packed_bytes(s, precision, bytes, "memnet_packed_bytes_ex");
+}
+
+extern "C" int antsrl_memnet_pack_ex(const AntsMemNetShape *s, int precision, const float *const *params, void *packed,
+                                     void *stream)
+{
+    const int rc = memnet_precision(precision, "memnet_pack_ex");
+    return rc != ANTSRL_OK ? rc : memnet_pack(s, precision, params, packed, stream, "memnet_pack_ex");
+}
+
+extern "C" int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, const void *packed, const void *obs,
+                                       int obs_format, const float *agent_state, const float *mem_in, int64_t n_ants,
+                                       float *mem_out, int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
+{
+    const int rc = memnet_precision(precision, "policy_memory_ex");
+    return rc != ANTSRL_OK ? rc
+                           : policy_memory(s, precision, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out,
+                                           rotation, pheromone, q_out, stream, "policy_memory_ex");
 }
 
 // ---- memory agent training step (antsrl_memtrain.hip)

@@ -14,6 +14,8 @@
 // Each: bf16 A fragments [out tile][k-step][64 lanes][8] (1 KiB per fragment; layers fed from registers in the permuted
 // k order of the accumulator, see antsrl_memnet.hip), then the fp32 bias [32 * out tiles] (zero rows past the width);
 // every block starts on a 256-byte boundary.
+// The fp32 pack (antsrl_memnet_f32.hip) has the same blocks, with fp32 A fragments [out tile][k-group of 8 inputs]
+// [64 lanes][4] (also 1 KiB per fragment; ks counts k-groups there).
 #define MN_NLAYERS 12
 
 struct MemNetDims {
@@ -22,7 +24,7 @@ struct MemNetDims {
 
 struct MemNetLayout {
     int Dp;                       // D rounded up to 32
-    int ks[MN_NLAYERS];           // k-steps of 16 inputs
+    int ks[MN_NLAYERS];           // k-steps of 16 inputs (bf16), k-groups of 8 inputs (fp32)
     int tout[MN_NLAYERS];         // 32-row output tiles
     size_t frag_off[MN_NLAYERS];  // byte offsets into the packed buffer
     size_t bias_off[MN_NLAYERS];
@@ -38,3 +40,9 @@ hipError_t antsrl_launch_memnet_pack(unsigned char *pack, const MemNetParams &P,
 hipError_t antsrl_launch_memnet(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
                                 const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
                                 int8_t *ph, float *q_out, hipStream_t st);
+// fp32 operands (ANTSRL_MEMNET_FP32): same shapes, arguments and outputs
+bool antsrl_memnet_layout_f32(const MemNetDims &d, MemNetLayout *L);
+hipError_t antsrl_launch_memnet_pack_f32(unsigned char *pack, const MemNetParams &P, const MemNetDims &d, hipStream_t st);
+hipError_t antsrl_launch_memnet_f32(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
+                                    const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
+                                    int8_t *ph, float *q_out, hipStream_t st);

@@ -37,10 +37,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "antsrl_memnet.h"
+#include "antsrl_memnet_dev.h"
 #define ANTSRL_MAX_DEVICES 64 // per-device launch bookkeeping (dynamic-LDS opt-in), as in antsrl_util.h
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 #define MN_MAXT 8 // hidden tiles held in registers: widths <= 256
 
@@ -67,21 +67,6 @@ bool antsrl_memnet_layout(const MemNetDims &d, MemNetLayout *L)
     }
     L->bytes = off;
     return true;
-}
-
-// source rows of packed layer i: (tensor index in state_dict order, row) of output row o, or -1 for a zero row
-__device__ __forceinline__ int mn_src(int i, int o, const MemNetDims &d, int *row)
-{
-    // state_dict order: layer1..4 (0..3), rotation_layer1..3 (4..6), pheromone_layer1..2 (7..8),
-    // memory_layer1..3 (9..11), forget_layer (12); packed layer 11 = memory_layer3 (tile 0) + forget_layer (tile 1)
-    const int nrow[MN_NLAYERS] = {d.h2, d.h3, d.h1, d.D, d.h2, d.h3, d.n_rot, d.h1, d.n_ph, d.h2, d.h2, 0};
-    if (i == 11) {
-        const int t = o >> 5, rr = o & 31;
-        *row = rr;
-        return rr < d.mem ? 11 + t : -1;
-    }
-    *row = o;
-    return o < nrow[i] ? i : -1;
 }
 
 __global__ void __launch_bounds__(64)
@@ -119,39 +104,6 @@ k_memnet_pack(unsigned char *__restrict__ pack, MemNetParams P, MemNetDims d, Me
 // ------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------
-struct MemNetIO {
-    const void *obs;
-    const float *agent_state, *mem_in;
-    float *mem_out, *q_out;
-    int8_t *rot, *ph;
-    int M;
-};
-
-// input d of ant `ant` as fp32: observation, agent_state, old memory, zero pad (unconditional clamped loads + selects)
-template <bool OBS16>
-__device__ __forceinline__ float mn_x(const MemNetIO &io, const MemNetDims &d, size_t ant, int k)
-{
-    const int F = d.F, A = d.A;
-    float o;
-    if constexpr (OBS16)
-        o = (float)__builtin_bit_cast(__bf16, reinterpret_cast<const uint16_t *>(io.obs)[ant * F + min(k, F - 1)]);
-    else
-        o = reinterpret_cast<const float *>(io.obs)[ant * F + min(k, F - 1)];
-    const float a = A > 0 ? io.agent_state[ant * A + min(max(k - F, 0), A - 1)] : 0.0f;
-    const float m = io.mem_in[ant * d.mem + min(max(k - F - A, 0), d.mem - 1)];
-    return k < F ? o : (k < F + A ? a : (k < d.D ? m : 0.0f));
-}
-
-// bias of the 16 rows lane (., h) holds in output tile t
-__device__ __forceinline__ void mn_bias(const float *__restrict__ b, int t, int h, float (&bv)[16])
-{
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float4 v = *reinterpret_cast<const float4 *>(b + 32 * t + 8 * q + 4 * h);
-        bv[4 * q] = v.x; bv[4 * q + 1] = v.y; bv[4 * q + 2] = v.z; bv[4 * q + 3] = v.w;
-    }
-}
-
 __device__ __forceinline__ void mn_to_b(const f32x16 &v, bf16x8 &b0, bf16x8 &b1)
 {
 #pragma unroll
@@ -267,38 +219,12 @@ __device__ __forceinline__ void mn_layer_lds(const unsigned char *__restrict__ p
         }
 }
 
-// first maximum of n <= 32 head outputs of ant r, held as rows (g & 3) + 8 (g >> 2) + 4 h by lanes r and r + 32
-__device__ __forceinline__ int mn_argmax(const f32x16 &v, int n, int h)
-{
-    float best = 0.0f;
-    int bi = 1 << 30;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) { // rows ascend with g: a strict > keeps the first maximum
-        const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
-        if (row < n && (bi == (1 << 30) || v[g] > best)) { best = v[g]; bi = row; }
-    }
-    const float ob = __shfl_xor(best, 32);
-    const int oi = __shfl_xor(bi, 32);
-    if (oi != (1 << 30) && (bi == (1 << 30) || ob > best || (ob == best && oi < bi))) bi = oi;
-    return bi;
-}
-
 #ifndef MN_WAVES
 #define MN_WAVES 4 // waves per workgroup (32 ants each) sharing every staged weight chunk
 #endif
 #ifndef MN_WCAP
 #define MN_WCAP 4096 // shared weight buffer, 16-byte units (64 KiB; at least one output tile of any layer)
 #endif
-
-// one observation element as fp32 (the chunk is known to lie inside the observation row)
-template <bool OBS16>
-__device__ __forceinline__ float mn_obs(const MemNetIO &io, const MemNetDims &d, size_t ant, int k)
-{
-    if constexpr (OBS16)
-        return (float)__builtin_bit_cast(__bf16, reinterpret_cast<const uint16_t *>(io.obs)[ant * d.F + k]);
-    else
-        return reinterpret_cast<const float *>(io.obs)[ant * d.F + k];
-}
 
 template <bool OBS16>
 __global__ void __launch_bounds__(64 * MN_WAVES) // one workgroup per CU at D <= 320 (LDS): one wave per SIMD, 512 registers

@@ -113,6 +113,8 @@ class LinearPolicy:
 #: antsrl_memnet_pack takes them in
 MEMNET_LAYERS = ("layer1", "layer2", "layer3", "layer4", "rotation_layer1", "rotation_layer2", "rotation_layer3",
                  "pheromone_layer1", "pheromone_layer2", "memory_layer1", "memory_layer2", "memory_layer3", "forget_layer")
+#: MemoryPolicy precisions -> include/antsrl.h ANTSRL_MEMNET_BF16 / ANTSRL_MEMNET_FP32
+MEMNET_PRECISIONS = {"bf16": 0, "fp32": 1}
 
 
 def memnet_shape_from_state_dict(sd) -> dict:
@@ -137,7 +139,10 @@ def memnet_param_shapes(n_features: int, power: int, mem_size: int, n_rot: int, 
 
 class MemoryPolicy:
     """The reference's recurrent memory agent net `CollectModelMemory` (agents/collect_agent_memory.py:24-78, the net
-    main.py's CollectAgentMemory trains) evaluated on the device by the bf16 MFMA kernel `antsrl_policy_memory`.
+    main.py's CollectAgentMemory trains) evaluated on the device by `antsrl_policy_memory_ex`.
+
+    `precision` picks the kernel: "bf16" (the default: bf16 MFMA operands, fp32 accumulation) or "fp32" (fp32 operands
+    throughout: the reference's own fp32 forward up to summation order, so its actions on near-tied q values too).
 
     Weights are nn.Linear-initialised (seeded) or loaded with load_state_dict from the reference's own state_dict (its
     parameter names; power and mem_size are inferred from the shapes, so the shipped checkpoints load as they are).
@@ -145,7 +150,9 @@ class MemoryPolicy:
     reset_memory()): the reference zeros it once in setup (:111), not per episode."""
 
     def __init__(self, n_features: int, device, power: int = 5, mem_size: int = 20, n_rot: int = 3, n_ph: int = 3,
-                 seed: int = 0):
+                 seed: int = 0, precision: str = "bf16"):
+        assert precision in MEMNET_PRECISIONS, "precision must be one of %s, not %r" % (tuple(MEMNET_PRECISIONS), precision)
+        self.precision = precision
         g = torch.Generator(device="cpu")
         g.manual_seed(seed)
         self.n_features = n_features
@@ -166,7 +173,8 @@ class MemoryPolicy:
         self.shape = _lib.AntsMemNetShape(self.n_features, 2, mem_size, 2 ** (1 + power), 2 ** (2 + power),
                                           2 ** (3 + power), n_rot, n_ph)
         n = C.c_size_t()
-        _lib.check(self._lib.antsrl_memnet_packed_bytes(C.byref(self.shape), C.byref(n)), "memnet_packed_bytes")
+        _lib.check(self._lib.antsrl_memnet_packed_bytes_ex(C.byref(self.shape), self._precision_id(), C.byref(n)),
+                   "memnet_packed_bytes_ex")
         if self.memory is not None and self.memory.shape[1] != mem_size:
             self.memory = None
         self.packed = None
@@ -175,8 +183,11 @@ class MemoryPolicy:
         self.packed = torch.empty((n.value,), dtype=torch.uint8, device=self.device)  # torch blocks are 512-byte aligned
         ptrs = (C.c_void_p * 26)(*[self.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS for w in ("weight", "bias")])
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_memnet_pack(C.byref(self.shape), ptrs, C.c_void_p(self.packed.data_ptr()),
-                                                    self._stream()), "memnet_pack")
+            _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), self._precision_id(), ptrs,
+                                                       C.c_void_p(self.packed.data_ptr()), self._stream()), "memnet_pack_ex")
+
+    def _precision_id(self) -> int:
+        return MEMNET_PRECISIONS[self.precision]
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -187,7 +198,7 @@ class MemoryPolicy:
     def load_state_dict(self, sd) -> None:
         """A CollectModelMemory state_dict (the reference's parameter names, e.g. torch.load('good_model.h5') or
         target_model.state_dict()); power, mem_size and the head sizes come from its shapes, then the weights are
-        repacked."""
+        repacked in the policy's precision."""
         shp = memnet_shape_from_state_dict(sd)
         assert shp["n_features"] == self.n_features, "state_dict is for %d features, not %d" % (shp["n_features"], self.n_features)
         want = memnet_param_shapes(self.n_features, shp["power"], shp["mem_size"], shp["n_rot"], shp["n_ph"])
@@ -239,7 +250,7 @@ class MemoryPolicy:
 
         fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_policy_memory(C.byref(self.shape), p(self.packed), p(obs), fmt, p(agent_state),
-                                                      p(memory), m, p(dst), p(self._rot), p(self._ph), p(q), self._stream()),
-                       "policy_memory")
+            _lib.check(self._lib.antsrl_policy_memory_ex(C.byref(self.shape), self._precision_id(), p(self.packed), p(obs),
+                                                         fmt, p(agent_state), p(memory), m, p(dst), p(self._rot), p(self._ph),
+                                                         p(q), self._stream()), "policy_memory_ex")
         return self._rot.view(lead), self._ph.view(lead), dst

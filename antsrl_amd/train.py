@@ -32,11 +32,12 @@ class MemoryTrainer:
 
     `step(batch_or_replay, idx)` is one training step (grad + apply) and returns the loss as a 0-d device tensor;
     `train(replay, done)` is CollectAgentMemory.train with the replay on the device.  `policy` is a MemoryPolicy holding
-    the TARGET net (get_action acts with the target net, :194), repacked at every sync_target()."""
+    the TARGET net (get_action acts with the target net, :194), repacked at every sync_target() in `policy_precision`
+    ("bf16" or "fp32", MemoryPolicy's precision); the training step itself has bf16 operands either way."""
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, power: int = 5, mem_size: int = 20, n_rot: int = 3,
-                 n_ph: int = 3, seed: int = 0, state_dict=None):
+                 n_ph: int = 3, seed: int = 0, state_dict=None, policy_precision: str = "bf16"):
         self.device = torch.device(device)
         assert self.device.type == "cuda", "MemoryTrainer runs on the GPU"
         if self.device.index is None:
@@ -52,7 +53,7 @@ class MemoryTrainer:
             assert shp["n_features"] == n_features, "state_dict is for %d features, not %d" % (shp["n_features"], n_features)
             power, mem_size, n_rot, n_ph = shp["power"], shp["mem_size"], shp["n_rot"], shp["n_ph"]
         self.policy = MemoryPolicy(n_features, self.device, power=power, mem_size=mem_size, n_rot=n_rot, n_ph=n_ph,
-                                   seed=seed)
+                                   seed=seed, precision=policy_precision)
         if state_dict is None:
             state_dict = {k: v.clone() for k, v in self.policy.state_dict().items()}
         self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
@@ -136,15 +137,15 @@ class MemoryTrainer:
         return {k: g[o: o + _numel(shp)].view(shp) for k, (o, shp) in self._offs.items() if k.split(".")[0] in TRAINED_LAYERS}
 
     def _repack_policy(self):
-        """policy := target net (a copy into the policy's own tensors, then antsrl_memnet_pack)."""
+        """policy := target net (a copy into the policy's own tensors, then antsrl_memnet_pack_ex in its precision)."""
         tv = self._views(self._target)
         for k, dst in self.policy.params.items():
             dst.copy_(tv[k])
         ptrs = (C.c_void_p * 26)(*[self.policy.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS
                                    for w in ("weight", "bias")])
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_memnet_pack(C.byref(self.shape), ptrs, _p(self.policy.packed), self._stream()),
-                       "memnet_pack")
+            _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), self.policy._precision_id(), ptrs,
+                                                       _p(self.policy.packed), self._stream()), "memnet_pack_ex")
 
     def sync_target(self) -> None:
         """target := model (:170-174), and the acting policy with it.  Adam's state is not copied."""

@@ -497,6 +497,29 @@ int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const voi
                          const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
                          int8_t *pheromone, float *q_out, void *stream);
 
+/* Precision of the memory agent net's forward (the _ex entries below; the entries above are ANTSRL_MEMNET_BF16).
+ * ANTSRL_MEMNET_FP32: every MFMA operand is fp32 (weights, x, the hidden values, g, the head intermediates) and nothing
+ * is rounded to bf16; accumulation and the epilogues are fp32 as above (v_mfma_f32_32x32x2_f32: each product is a
+ * k-ordered fmaf chain; two chains per output tile, added once).  bf16 observations are widened exactly.  Results equal
+ * the reference's fp32 forward up to fp32 summation order, and an ant's outputs depend only on its own inputs. */
+#define ANTSRL_MEMNET_BF16 0
+#define ANTSRL_MEMNET_FP32 1
+
+/* antsrl_memnet_packed_bytes for a precision.  ANTSRL_MEMNET_BF16: the same size.  ANTSRL_MEMNET_FP32: the same sum with
+ * frag(i, o) = 1024 * (i / 8) * (o / 32) bytes (fp32 MFMA fragments, 4 bytes per weight):
+ * 1 128 960 bytes at F = 294, power 5, mem_size 20; 467 456 at power 4, mem_size 10.
+ * An unknown precision is ANTSRL_E_INVALID, before any other check. */
+int antsrl_memnet_packed_bytes_ex(const AntsMemNetShape *s, int precision, size_t *bytes);
+
+/* antsrl_memnet_pack into the layout of `precision` (packed: antsrl_memnet_packed_bytes_ex bytes, 256-byte aligned). */
+int antsrl_memnet_pack_ex(const AntsMemNetShape *s, int precision, const float *const *params, void *packed, void *stream);
+
+/* antsrl_policy_memory with weights packed by antsrl_memnet_pack_ex in the same `precision`; every other argument and
+ * rule as there. */
+int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
+                            const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
+                            int8_t *rotation, int8_t *pheromone, float *q_out, void *stream);
+
 /* On-device DQN training step of the memory agent net (replaces CollectAgentMemory.train, agents/collect_agent_memory.py:
  * 133-176: target forward, TD targets, MSE loss, backward, torch.optim.Adam).  Same shape and limits as
  * antsrl_policy_memory; observations are float32 (what the replay stores).  Two stages, so that a data-parallel caller
