@@ -19,7 +19,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory",
            "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
            "antsrl_memtrain_grad", "antsrl_memtrain_apply", "antsrl_memnet_packed_bytes_ex", "antsrl_memnet_pack_ex",
-           "antsrl_policy_memory_ex")
+           "antsrl_policy_memory_ex", "antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post")
 
 _lib = None
 
@@ -27,6 +27,13 @@ _lib = None
 class AntsMemNetShape(C.Structure):
     """include/antsrl.h AntsMemNetShape."""
     _fields_ = [(n, C.c_int32) for n in ("n_features", "agent_dim", "mem_size", "h1", "h2", "h3", "n_rot", "n_ph")]
+
+
+class AntsRecordSpec(C.Structure):
+    """include/antsrl.h AntsRecordSpec."""
+    _fields_ = [(n, C.c_int32) for n in ("n_envs", "n_ants", "env_id_base", "n_features", "agent_dim", "mem_size", "n_rot",
+                                         "obs_format", "obs_pitch", "reserved")] + [
+        (n, C.c_int64) for n in ("K", "head", "max_len")] + [(n, C.c_uint64) for n in ("seed", "step")]
 
 
 class AntsrlError(RuntimeError):
@@ -92,6 +99,10 @@ def load() -> C.CDLL:
                                          C.c_float, vp, vp, vp, vp]
     lib.antsrl_memtrain_apply.argtypes = [C.POINTER(AntsMemNetShape), vp, vp, C.c_int64, C.c_double, C.c_double,
                                           C.c_double, C.c_double, vp]
+    lib.antsrl_agent_select.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp,
+                                        vp, vp]
+    lib.antsrl_replay_record_pre.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 9
+    lib.antsrl_replay_record_post.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 10
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -1,0 +1,194 @@
+"""The memory agent on the device: CollectAgentMemory (agents/collect_agent_memory.py:81-214, the agent main.py:53 runs)
+with its net, its replay memory, its epsilon-greedy step and its training step all resident on the GPU.
+
+`MemoryAgent` has the reference class's surface (setup, initialize, get_action, update_replay_memory, train, save_model,
+load_model, a settable epsilon), so main.py's loop (:92-131) runs on it as it is written, and a fused form of that loop,
+
+    rollout_step(env) = act -> select -> record_pre -> env.step_update -> record_post -> train
+
+in which no observation is ever copied and nothing is read back to the host.  The pieces: `MemoryTrainer` (model, target
+net, Adam; its `policy` is the acting target net, as :194 acts with the target net), `DeviceReplayMemory`, and the three
+entries of antsrl_memagent.hip (antsrl_agent_select, antsrl_replay_record_pre / _post; include/antsrl.h holds their draw
+specification).
+
+What the reference stores as the "before" memory.  get_action overwrites self.previous_memory with the NEW memory
+(:194) before update_replay_memory reads it (:182), so the reference stores the post-action memory in BOTH agent_states
+and new_agent_states: in tests/golden/contract/memory_train_ref.npz the memory columns of rows/agent_states and
+rows/new_agent_states are equal on all 621 rows.  `state_memory="reference"` (the default: parity is this project's bar)
+does the same; `state_memory="carried"` stores the pre-action memory, which is what the code's shape suggests was meant.
+
+Beyond the reference: `record_per_step` (K: how many of a step's n_envs * n_ants transitions are recorded, a stratified
+sample; None = all of them, the reference's behaviour — at c3's 524 288 ants per step a ring of 50 000 rows would be
+overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed`, `precision` (the acting policy's).
+Exploration is drawn once per environment and step (an environment is one reference colony).
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import config as cm
+from .replay import DeviceReplayMemory
+from .train import MemoryTrainer
+
+
+def _backend(api_or_env):
+    """A BatchedAntsEnv, or the one behind an rl_api.RLApi."""
+    b = getattr(api_or_env, "_backend", api_or_env)
+    assert b is not None and hasattr(b, "step_update"), "setup needs a BatchedAntsEnv or an RLApi whose perception is set up"
+    return b
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+class MemoryAgent:
+    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
+                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
+                 precision: str = "bf16", state_memory: str = "reference", mem_size: int = 20, power: int = 5):
+        assert state_memory in ("reference", "carried"), "state_memory must be 'reference' or 'carried', not %r" % (state_memory,)
+        self.name = "collect_agent_memory"
+        self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
+        self.learning_rate = learning_rate
+        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
+        self.update_target_every, self.seed, self.precision, self.state_memory = update_target_every, seed, precision, state_memory
+        self.mem_size, self.power = mem_size, power
+        self.trainer = self.replay_memory = self.generator = None
+        self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
+        self._lib = _lib.load()
+
+    # ---- the reference's surface ----------------------------------------------------------------------------------
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """CollectAgentMemory.setup (:108-127) for every ant of the batch."""
+        env = _backend(api_or_env)
+        cfg = env.cfg
+        self.device = env.device
+        self.n_envs, self.n_ants_per_env, self.env_id_base = cfg.n_envs, cfg.n_ants, cfg.env_id_base
+        self.n_ants = cfg.n_envs * cfg.n_ants
+        self.observation_space = tuple(env.obs.shape[-3:])
+        self.agent_space, self.action_space = [2], [2]
+        self.n_features = int(np.prod(self.observation_space))
+        self.agent_and_mem_space = [2 + self.mem_size]
+        self.trainer = MemoryTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+                                     update_target_every=self.update_target_every, power=self.power, mem_size=self.mem_size,
+                                     n_rot=self.rotations, n_ph=self.pheromones, seed=self.seed,
+                                     policy_precision=self.precision)
+        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_and_mem_space,
+                                                self.action_space, device=self.device)
+        self._mem = [torch.zeros((self.n_ants, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self._cur = 0  # self._mem[self._cur] is previous_memory (:111)
+        self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(self.seed)
+        self.step_counter = 0
+        self._action_step = 0
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    def initialize(self, api_or_env) -> None:
+        """:129-131: every pheromone activation x 10."""
+        env = _backend(api_or_env)
+        c = env.cfg
+        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
+
+    @property
+    def policy(self):
+        return self.trainer.policy
+
+    @property
+    def previous_memory(self) -> torch.Tensor:
+        return self._mem[self._cur]
+
+    def _dev(self, a, dtype):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(device=self.device, dtype=dtype) if (t.device != self.device or t.dtype != dtype) else t
+
+    def get_action(self, obs, agent_state, training: bool, env=None):
+        """:189-206 -> (rotation int8, pheromone int8, memory float32 [M, mem_size]), device tensors.  The target net acts
+        on the whole batch; with `training`, antsrl_agent_select then replaces the actions of the environments that
+        explore this step (probability epsilon each) by uniform ones and gives their ants the old memory back."""
+        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
+        ast = self._dev(agent_state, torch.float32)
+        old, new = self._mem[self._cur], self._mem[1 - self._cur]
+        rot, ph, _ = self.policy.act(obs.contiguous(), ast.contiguous(), memory=old, out=new, env=env)
+        step = self.step_counter
+        if training:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.antsrl_agent_select(self.seed, step, self.env_id_base, self.n_envs, self.n_ants_per_env,
+                                                         float(self.epsilon), self.rotations, self.pheromones, self.mem_size,
+                                                         _p(rot), _p(ph), _p(old), _p(new), _p(self._explored),
+                                                         self._stream()), "agent_select")
+        self._memory_before = old
+        self._cur = 1 - self._cur
+        self._action_step = step
+        self.step_counter += 1
+        return rot, ph, new
+
+    def _state_memory(self) -> torch.Tensor:
+        """The memory that goes into agent_states (see the module docstring)."""
+        return self.previous_memory if self.state_memory == "reference" else self._memory_before
+
+    def _record_kw(self):
+        return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
+                    step=self._action_step, env_id_base=self.env_id_base, n_rot=self.rotations)
+
+    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
+        """:178-187, from arrays the caller kept (`states` must be the observation as it was BEFORE the step: the
+        environment writes every observation into the same buffer).  actions = what get_action returned."""
+        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
+        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
+        rm = self.replay_memory
+        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), self._state_memory(),
+                      self._dev(actions[0], torch.int8).contiguous().view(-1),
+                      None if actions[1] is None else self._dev(actions[1], torch.int8).contiguous().view(-1),
+                      **self._record_kw())
+        if torch.is_tensor(done) or isinstance(done, np.ndarray):
+            done = self._dev(done, torch.uint8).contiguous().view(-1)
+        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(),
+                       self._dev(actions[2], torch.float32).contiguous(), self._dev(rewards, torch.float32).contiguous().view(-1),
+                       done)
+
+    def train(self, done: bool, step: int = 0):
+        """:133-176: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
+        device tensor.  `done` is a host bool (the target counter lives on the host)."""
+        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
+                                  generator=self.generator)
+
+    def save_model(self, file_name: str) -> None:
+        """:208-209: torch.save of the model's 26-tensor state_dict under the reference's names (on the CPU), so the
+        reference loads what this trains."""
+        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
+
+    def load_model(self, file_name: str) -> None:
+        """:211-213: model and target net (and the acting policy) from a state_dict file of the reference's."""
+        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
+
+    # ---- the fused loop -------------------------------------------------------------------------------------------
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
+        observe() or a step): act, select, record_pre, env.step_update, record_post, train.  Returns the loss (0 while the
+        replay memory is below min_replay or when not training, else a 0-d device tensor).  No host synchronisation: `done`
+        for the target counter is the host's own step count against max_time."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        assert obs.is_contiguous(), "MemoryPolicy reads dense observation rows (obs_row_stride=None)"
+        rot, ph, mem = self.get_action(obs, ast, training, env=env)
+        rm = self.replay_memory
+        rm.record_pre(obs, ast, self._state_memory(), rot.view(-1), ph.view(-1), **self._record_kw())
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
+        rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step) if training else 0
+
+    def run(self, env, steps: int, training: bool = True) -> list:
+        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
+        return [self.rollout_step(env, training) for _ in range(steps)]

@@ -18,7 +18,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libantsrl_hip.so")
 SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl_sweep.hip", "antsrl_state.hip",
            "antsrl_capi.hip", "antsrl_policy.hip", "antsrl_mem.hip",
-           "antsrl_memnet.hip", "antsrl_memnet_f32.hip", "antsrl_memtrain.hip"]
+           "antsrl_memnet.hip", "antsrl_memnet_f32.hip", "antsrl_memtrain.hip", "antsrl_memagent.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_memnet.h", "antsrl_memnet_dev.h", "antsrl_memtrain.h")] + [

@@ -92,6 +92,9 @@ static int hip_fail(hipError_t e, const char *what)
     return fail(ANTSRL_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
 }
 
+// for the translation units that hold C-ABI entries of their own (antsrl_memagent.hip)
+__attribute__((visibility("hidden"))) int antsrl_fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
+
 extern "C" int antsrl_abi_version(void) { return ANTSRL_ABI_VERSION; }
 extern "C" size_t antsrl_cfg_size(void) { return sizeof(AntsCfg); }
 extern "C" const char *antsrl_last_error(void) { return g_err; }

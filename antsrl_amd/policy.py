@@ -219,7 +219,11 @@ class MemoryPolicy:
         (rotation int8 [...], pheromone int8 [...], new_memory float32 [M, mem_size]).
 
         The old memory is `memory`, or `self.memory` when None (zeros on first use).  The new memory goes to `out` when
-        given (the old one stays intact, as update_replay_memory wants it, :178-185), else in place over the old one.
+        given (the old one stays intact: the epsilon branch gives it back to exploring colonies, :204, and
+        MemoryAgent(state_memory="carried") records it), else in place over the old one.  What the reference's
+        update_replay_memory stores (:182) is NOT the old memory: get_action has overwritten self.previous_memory with
+        the new one by then (:194), so agent_states and new_agent_states hold the same, post-action memory
+        (antsrl_amd/agent.py).
         `q` (float32 [M, n_rot + n_ph]) receives both heads' outputs."""
         assert self.packed is not None, "MemoryPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
         lead = obs.shape[:-3]

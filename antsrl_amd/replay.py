@@ -14,10 +14,13 @@ Same constructor, `extend`, `random_access`, `__len__`, `__getitem__` as the ref
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
+
+from . import _lib
 
 
 class DeviceReplayMemory:
@@ -36,6 +39,7 @@ class DeviceReplayMemory:
         self.dones = z([], torch.bool)
         self.head = 0   # :36
         self.fill = 0   # :39
+        self._pending = None  # the AntsRecordSpec of a record_pre whose record_post has not come yet
 
     def __len__(self):
         return self.fill
@@ -91,3 +95,77 @@ class DeviceReplayMemory:
                 dst[: n - first] = src[first:]
         self.fill = min(self.max_len, max(self.fill, self.head + n))  # :109
         self.head = (self.head + n) % self.max_len                       # :112
+
+    # ---- one step's transitions recorded around the environment step (antsrl_replay_record_pre / _post) ----------------
+    def record_pre(self, obs, agent_state, memory, rotation, pheromone, n_envs: int, n_ants: int, k: Optional[int] = None,
+                   seed: int = 0, step: int = 0, env_id_base: int = 0, n_rot: int = 3, obs_pitch: int = 0) -> None:
+        """The first half of one step's `extend`, BEFORE the environment step overwrites its observation buffer: states,
+        agent_states (= agent_state ++ memory) and actions (rotation + n_rot // 2, pheromone; pheromone None: 1) of `k`
+        of the n_envs * n_ants transitions (None: all of them, in order) go to the rows `extend` would write next.  Which
+        ants (a stratified sample keyed on seed, env_id_base, step) and the copy itself: include/antsrl.h.  All inputs are
+        device tensors: obs float32 or bfloat16, contiguous [.., P, P, K] — or, with obs_pitch (elements between two
+        ants' rows), the padded buffer of a BatchedAntsEnv(obs_row_stride="line") —, agent_state float32 [M, 2],
+        memory float32 [M, mem], rotation / pheromone int8 [M].  Nothing moves head or fill until record_post."""
+        assert self._pending is None, "record_pre twice without record_post"
+        M = n_envs * n_ants
+        F = int(np.prod(self.observation_space))
+        mem = memory.shape[-1]
+        A = int(np.prod(self.agent_space)) - mem
+        spec = _lib.AntsRecordSpec(n_envs, n_ants, env_id_base, F, A, mem, n_rot, self._obs_format(obs), obs_pitch, 0,
+                                   M if k is None else k, self.head, self.max_len, seed, step)
+        self._check(obs, obs.dtype, M * (obs_pitch or F))
+        self._check(agent_state, torch.float32, M * A)
+        self._check(memory, torch.float32, M * mem)
+        self._check(rotation, torch.int8, M)
+        if pheromone is not None:
+            self._check(pheromone, torch.int8, M)
+        with torch.cuda.device(self.states.device):
+            _lib.check(_lib.load().antsrl_replay_record_pre(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(rotation),
+                                                            _p(pheromone), _p(self.states), _p(self.agent_states),
+                                                            _p(self.actions), self._stream()), "replay_record_pre")
+        self._pending = spec
+
+    def record_post(self, obs, agent_state, memory, reward, done) -> None:
+        """The second half, AFTER the step: rewards, new_states, new_agent_states (= agent_state ++ memory) and dones of the
+        same transitions into the same rows; then head and fill advance exactly as `extend` advances them for k rows.
+        reward float32 [M]; done: the environment's per-environment uint8 / bool [n_envs], or one host bool."""
+        spec = self._pending
+        assert spec is not None, "record_post without record_pre"
+        M = spec.n_envs * spec.n_ants
+        spec.obs_format = self._obs_format(obs)
+        if not torch.is_tensor(done):
+            done = torch.full((spec.n_envs,), 1 if done else 0, dtype=torch.uint8, device=self.states.device)
+        elif done.dtype == torch.bool:
+            done = done.view(torch.uint8)
+        self._check(obs, obs.dtype, M * (spec.obs_pitch or spec.n_features))
+        self._check(agent_state, torch.float32, M * spec.agent_dim)
+        self._check(memory, torch.float32, M * spec.mem_size)
+        self._check(reward, torch.float32, M)
+        self._check(done, torch.uint8, spec.n_envs)
+        with torch.cuda.device(self.states.device):
+            _lib.check(_lib.load().antsrl_replay_record_post(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(reward),
+                                                             _p(done), _p(self.rewards), _p(self.new_states),
+                                                             _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
+                                                             self._stream()), "replay_record_post")
+        self._pending = None
+        n = int(spec.K)
+        if n > self.max_len:  # as extend: only the newest max_len entries survived
+            self.head = (self.head + n - self.max_len) % self.max_len
+            n = self.max_len
+        self.fill = min(self.max_len, max(self.fill, self.head + n))
+        self.head = (self.head + n) % self.max_len
+
+    def _obs_format(self, obs) -> int:
+        assert obs.dtype in (torch.float32, torch.bfloat16), obs.dtype
+        return 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
+
+    def _check(self, t, dtype, numel):
+        assert torch.is_tensor(t) and t.device == self.states.device and t.dtype == dtype and t.is_contiguous() and \
+            t.numel() == numel, (tuple(t.shape), t.dtype, t.device, numel)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.states.device).cuda_stream)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())

@@ -576,6 +576,92 @@ int antsrl_memtrain_grad(const AntsMemNetShape *s, const void *state, const void
 int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *grads, int64_t step, double lr,
                           double beta1, double beta2, double eps, void *stream);
 
+/* The memory agent's loop around the net and the training step (antsrl_memagent.hip; replaces the epsilon branch of
+ * CollectAgentMemory.get_action, agents/collect_agent_memory.py:189-206, and update_replay_memory + ReplayMemory.extend,
+ * :178-187 and agents/replay_memory.py:83-114).  Three entries on plain device pointers: every argument is validated
+ * before any HIP call, nothing synchronises the host, and there are no atomics: results do not depend on scheduling.
+ *
+ * THE DRAW SPECIFICATION.  All randomness of these entries is counter-based, built from the mixer of the wall-jitter
+ * stream (SplitMix64's finaliser; 64-bit unsigned arithmetic, wrapping):
+ *     mix64(z):  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *     draw(seed, tag, env, step, item):
+ *         k = mix64(seed + 0x9E3779B97F4A7C15 * (env + 1))
+ *         k = mix64(k ^ (0xD1B54A32D192ED03 * (step + 1)))
+ *         k = mix64(k + 0x9E3779B97F4A7C15 * (item + 1))        (up to here: the key of the wall-jitter stream)
+ *         k = mix64(k ^ tag)                                     (the stream tag: a fourth round the jitter stream lacks,
+ *                                                                 so equal seeds never replay it, nor one another)
+ *     u01(k)      = (double)(k >> 11) * 2^-53                     uniform in [0, 1), as the wall jitter makes it
+ *     below(k, n) = ((k >> 32) * n) >> 32                         uniform integer in [0, n) by multiply-shift of the
+ *                                                                 HIGH 32 bits; its bias is below n * 2^-32
+ * `env` is always a GLOBAL environment id, env_id_base + e for environment e of the batch at hand, so a shard draws what
+ * the full batch draws for its environments.  `step` is the caller's agent step counter, `seed` the caller's seed.
+ * Streams (tag; env, item):
+ *     ANTSRL_DRAW_EXPLORE    (env_id_base + e, 0):  does environment e explore this step
+ *     ANTSRL_DRAW_ROTATION   (env_id_base + e, a):  the random rotation of ant a of environment e
+ *     ANTSRL_DRAW_PHEROMONE  (env_id_base + e, a):  its random pheromone
+ *     ANTSRL_DRAW_SAMPLE     (env_id_base,     j):  which transition replay entry j of the step records */
+#define ANTSRL_DRAW_EXPLORE 0x45584C4FULL   /* "EXLO" */
+#define ANTSRL_DRAW_ROTATION 0x524F5441ULL  /* "ROTA" */
+#define ANTSRL_DRAW_PHEROMONE 0x50484552ULL /* "PHER" */
+#define ANTSRL_DRAW_SAMPLE 0x53414D50ULL    /* "SAMP" */
+
+/* Epsilon-greedy over n_envs x n_ants ants, in place behind antsrl_policy_memory(_ex) (get_action's else branch, :199-204).
+ * One explore draw per environment and step (an environment is one reference colony; the reference draws once per colony
+ * and step): environment e explores iff u01(draw(seed, ANTSRL_DRAW_EXPLORE, env_id_base + e, step, 0)) < epsilon, so
+ * epsilon 0 never explores and epsilon 1 always does.  For every ant a of an exploring environment
+ *     rotation  = below(draw(.., ANTSRL_DRAW_ROTATION, .., a), n_rot) - n_rot / 2     (np.random.randint(0, n_rot) - n_rot // 2)
+ *     pheromone = below(draw(.., ANTSRL_DRAW_PHEROMONE, .., a), n_ph)
+ *     mem_next[row of a] = mem_old[row of a]                                  ("we keep previous value", :204)
+ * Every other environment's rotation, pheromone and mem_next stay bit for bit what the net wrote.
+ * rotation, pheromone: int8 [n_envs][n_ants]; mem_old, mem_next: float [n_envs][n_ants][mem_size] (mem_old may equal
+ * mem_next: nothing is copied then; a partial overlap is refused); explored: uint8 [n_envs] (1 = explored) or NULL.
+ * 1 <= n_rot, n_ph, mem_size <= 32 (the net's limits), n_envs, n_ants >= 1, n_envs * n_ants < 2^31, env_id_base >= 0 with
+ * env_id_base + n_envs < 2^31, 0 <= epsilon <= 1.  One launch. */
+int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants, double epsilon,
+                        int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation, int8_t *pheromone,
+                        const float *mem_old, float *mem_next, uint8_t *explored, void *stream);
+
+/* One step's transitions into the seven rolling arrays of a replay memory (states float [max_len][n_features],
+ * agent_states float [max_len][agent_dim + mem_size], actions int64 [max_len][2], rewards float [max_len], new_states,
+ * new_agent_states, dones bool [max_len]), in two halves around the environment step, so that the observation the step
+ * overwrites is never copied: antsrl_replay_record_pre before the step (behind antsrl_agent_select),
+ * antsrl_replay_record_post after it, both with the SAME AntsRecordSpec.
+ * Which ants: K of the M = n_envs * n_ants transitions, stratified.  Entry j (0 <= j < K) takes ant
+ *     a_j = lo_j + min(floor(u_j * (hi_j - lo_j)), hi_j - lo_j - 1),  lo_j = floor(j * M / K),  hi_j = floor((j + 1) * M / K)
+ *     u_j = u01(draw(seed, ANTSRL_DRAW_SAMPLE, env_id_base, step, j))       (a double product, rounded once, then floor;
+ *                                                                            the min never binds: u_j <= 1 - 2^-53)
+ * (ant a = e * n_ants + i, the batch's own order).  Both halves compute a_j from the same key, so no index array travels
+ * between them; K == M is the identity, the reference's "every ant, in order".
+ * Where: entry j goes to ring row (head + j) mod max_len; when K > max_len only the last max_len entries are written.
+ * The caller then advances its head by K (mod max_len).
+ *   pre:  states[row] = obs[a], agent_states[row] = agent_state[a] ++ memory[a],
+ *         actions[row] = (rotation[a] + n_rot / 2, pheromone[a]; 1 when pheromone is NULL, replay_memory.py:100-103)
+ *   post: rewards[row] = reward[a], new_states[row] = obs[a], new_agent_states[row] = agent_state[a] ++ memory[a],
+ *         dones[row] = done[a / n_ants] != 0      (the environment's per-environment uint8)
+ * obs: ant a's row of n_features values starts obs_pitch ELEMENTS behind ant a - 1's (0 = dense, n_features), float32
+ * (ANTSRL_OBS_F32) or bfloat16 (ANTSRL_OBS_BF16, widened exactly: the ring is float32); agent_state float [M][agent_dim];
+ * memory float [M][mem_size]; rotation, pheromone int8 [M]; reward float [M]; done uint8 [n_envs].
+ * Limits: n_features >= 1, 1 <= agent_dim, mem_size, n_rot <= 32, n_features + agent_dim + mem_size <= 1024 (the net's),
+ * n_envs, n_ants >= 1, M < 2^31, 1 <= K <= M, max_len >= 1, 0 <= head < max_len, obs_pitch 0 or >= n_features (and
+ * below 2^24).  One launch each: one wave per entry; 16-byte loads and stores wherever a row's addresses allow them,
+ * narrower ones where they do not (decided per row from the addresses themselves). */
+typedef struct AntsRecordSpec {
+    int32_t n_envs, n_ants, env_id_base;
+    int32_t n_features, agent_dim, mem_size, n_rot;
+    int32_t obs_format; /* ANTSRL_OBS_F32 / ANTSRL_OBS_BF16 */
+    int32_t obs_pitch;  /* elements between two ants' rows; 0 = n_features */
+    int32_t reserved;   /* 0 */
+    int64_t K, head, max_len;
+    uint64_t seed, step;
+} AntsRecordSpec;
+
+int antsrl_replay_record_pre(const AntsRecordSpec *r, const void *obs, const float *agent_state, const float *memory,
+                             const int8_t *rotation, const int8_t *pheromone, float *states, float *agent_states,
+                             int64_t *actions, void *stream);
+int antsrl_replay_record_post(const AntsRecordSpec *r, const void *obs, const float *agent_state, const float *memory,
+                              const float *reward, const uint8_t *done, float *rewards, float *new_states,
+                              float *new_agent_states, uint8_t *dones, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""Times the memory agent's loop (antsrl_amd.agent.MemoryAgent) at c3's batch, 1024 envs x 512 ants, F = 294 (7 x 7 x 6),
+power 5, mem 20, on the device:
+
+  record     antsrl_replay_record_pre + _post at K = M (ring of M rows, for this case only) and at K = 4096 (ring of
+             50 000), against the same rows recorded the way the tree offered before — a clone of the observation buffer
+             before the step, then DeviceReplayMemory.extend (at K < M on rows gathered with the restated indices) —
+             in the same process, alternating.  Bytes moved are computed from the shapes; the rate is given as a
+             fraction of what antsrl_bench_copy reaches for the same byte count in this process.
+  select     antsrl_agent_select (epsilon 0.1 and 1.0) next to the memory forward it follows.
+  rollout    one whole MemoryAgent.rollout_step at K = 4096, minibatch 264, and its parts timed one by one.
+
+hipEvents around `--iters` warmed iterations.  Prints one line per case and a JSON summary (--json).
+
+    python profiles/memory_agent_bench.py [--iters 200] [--json out.json]
+    rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/memory_agent_bench.py --probe 40   # launches per step
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from antsrl_amd import _lib  # noqa: E402
+from antsrl_amd import config as cm  # noqa: E402
+from antsrl_amd.agent import MemoryAgent  # noqa: E402
+from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
+from antsrl_amd.replay import DeviceReplayMemory  # noqa: E402
+from antsrl_amd.synth import synth_init  # noqa: E402
+from memory_agent_ref import sample_indices  # noqa: E402
+
+E, N, P, MEM = 1024, 512, (7, 7, 6), 20
+M, F = E * N, 294
+
+
+def timed(fns, iters, warmup=10):
+    """ms per call of each fn in `fns`, alternating them inside one timed loop (one event pair per call)."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for _ in fns]
+    for i in range(iters):
+        for k, fn in enumerate(fns):
+            ev[k][i][0].record()
+            fn()
+            ev[k][i][1].record()
+    torch.cuda.synchronize()
+    return [float(np.median([a.elapsed_time(b) for a, b in row])) for row in ev]
+
+
+def record_bytes(K):
+    """What the two halves must move for K entries: each reads and writes K observation rows, K (2 + mem) agent floats,
+    and the pre half K action pairs (2 int8 read, 2 int64 written), the post half K rewards and done flags."""
+    row = 2 * F * 4 + 2 * (2 + MEM) * 4
+    return K * (row + 2 + 16) + K * (row + 4 + 4 + 1 + 1)
+
+
+def copy_ms(nbytes, iters):
+    nbytes = (nbytes + 15) // 16 * 16
+    a, b = torch.empty(nbytes, dtype=torch.uint8, device="cuda"), torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    lib = _lib.load()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return timed([lambda: _lib.check(lib.antsrl_bench_copy(C.c_void_p(b.data_ptr()), C.c_void_p(a.data_ptr()), nbytes, st))],
+                 iters)[0]
+
+
+def bench_record(K, ring, iters):
+    g = torch.Generator(device="cuda").manual_seed(1)
+    d = dict(device="cuda", generator=g)
+    obs0, obs1 = torch.rand((M, F), **d), torch.rand((M, F), **d)
+    ast0, ast1 = torch.rand((M, 2), **d), torch.rand((M, 2), **d)
+    m0, m1 = torch.rand((M, MEM), **d), torch.rand((M, MEM), **d)
+    rot = torch.randint(-1, 2, (M,), **d).to(torch.int8)
+    ph = torch.randint(0, 3, (M,), **d).to(torch.int8)
+    rew, done = torch.randn((M,), **d), (torch.rand((E,), **d) < 0.1).to(torch.uint8)
+    new, old = DeviceReplayMemory(ring, P, [2 + MEM], [2]), DeviceReplayMemory(ring, P, [2 + MEM], [2])
+    idx = None if K == M else torch.from_numpy(sample_indices(1, 0, 0, M, K)).cuda()
+
+    def fused():
+        new.record_pre(obs0, ast0, m0, rot, ph, n_envs=E, n_ants=N, k=K, seed=1, step=0)
+        new.record_post(obs1, ast1, m1, rew, done)
+
+    def parent():
+        kept, kept_ast = obs0.clone(), torch.cat([ast0, m0], 1)  # before the step: the environment overwrites obs
+        nast = torch.cat([ast1, m1], 1)
+        dn = done.repeat_interleave(N)
+        if idx is None:
+            old.extend(kept, kept_ast, (rot.long() + 1, ph.long()), rew, obs1, nast, dn)
+        else:
+            old.extend(kept[idx], kept_ast[idx], (rot.long()[idx] + 1, ph.long()[idx]), rew[idx], obs1[idx], nast[idx], dn[idx])
+
+    t_new, t_old = timed([fused, parent], iters)
+    for k in ("states", "actions", "rewards", "new_states", "new_agent_states", "dones", "agent_states"):
+        assert torch.equal(getattr(new, k), getattr(old, k)), k  # the same rows, bit for bit
+    by = record_bytes(K)
+    t_copy = copy_ms(by // 2, iters)  # a copy of n bytes moves 2 n
+    return dict(K=K, ring=ring, record_ms=t_new, clone_extend_ms=t_old, speedup=t_old / t_new, bytes=by,
+                gbytes_per_s=by / t_new * 1e-6, copy_ms_same_bytes=t_copy, fraction_of_copy_rate=t_copy / t_new)
+
+
+def c3_env():
+    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0)
+    env = BatchedAntsEnv(cfg)
+    env.reset(synth_init(cfg, seed=3))
+    return env
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--probe", type=int, default=0, help="run this many rollout_steps at K = 4096 and exit (for rocprofv3)")
+    a = ap.parse_args()
+    env = c3_env()
+    ag = MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1)
+    ag.setup(env)
+    ag.initialize(env)
+    env.observe()
+    if a.probe:
+        ag.run(env, a.probe)
+        torch.cuda.synchronize()
+        print("probe: %d rollout steps, %d training steps" % (a.probe, ag.trainer.step_count))
+        return
+    out = dict(device=torch.cuda.get_device_name(0), iters=a.iters, batch=[E, N], n_features=F)
+    out["record"] = [bench_record(M, M, max(20, a.iters // 4)), bench_record(4096, 50000, a.iters)]
+    for r in out["record"]:
+        print("record K = %6d: pre + post %.4f ms | clone + extend %.4f ms (%.1fx) | %.0f MB at %.0f GB/s = %.2f of the "
+              "copy kernel's rate (%.4f ms)" % (r["K"], r["record_ms"], r["clone_extend_ms"], r["speedup"], r["bytes"] * 1e-6,
+                                                r["gbytes_per_s"], r["fraction_of_copy_rate"], r["copy_ms_same_bytes"]), flush=True)
+    # ---- select next to the forward it follows
+    obs, ast = env.obs, env.agent_state
+    old, new = ag._mem
+    pol = ag.policy
+
+    def forward():
+        return pol.act(obs, ast, memory=old, out=new)
+
+    rot, ph, _ = forward()
+    lib, st = _lib.load(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    sel = lambda eps: (lambda: _lib.check(lib.antsrl_agent_select(1, 0, 0, E, N, eps, 3, 3, MEM, p(rot), p(ph), p(old), p(new),  # noqa: E731
+                                                                  None, st)))
+    t_fwd, t_s01, t_s1 = timed([forward, sel(0.1), sel(1.0)], a.iters)
+    out["select"] = dict(forward_ms=t_fwd, select_eps_0p1_ms=t_s01, select_eps_1_ms=t_s1)
+    print("memory forward %.4f ms | select eps 0.1 %.4f ms, eps 1.0 %.4f ms" % (t_fwd, t_s01, t_s1), flush=True)
+    # ---- the whole step and its parts
+    for _ in range(20):  # fill the ring past min_replay: every timed step trains
+        ag.rollout_step(env)
+    rm = ag.replay_memory
+    kw = ag._record_kw()
+    parts = dict(
+        forward=forward,
+        select=sel(0.1),
+        record_pre=lambda: (rm.record_pre(obs, ast, new, rot.view(-1), ph.view(-1), **kw), setattr(rm, "_pending", None)),
+        env_step=lambda: env.step_update(rot, ph),
+        train=lambda: ag.trainer.train(rm, False, minibatch=264, min_replay=1000, generator=ag.generator),
+    )
+    t_parts = dict(zip(parts, timed(list(parts.values()), a.iters)))
+    t_step = timed([lambda: ag.rollout_step(env)], a.iters)[0]
+    out["rollout"] = dict(K=4096, minibatch=264, rollout_step_ms=t_step, parts_ms=t_parts,
+                          parts_sum_ms=sum(t_parts.values()) + t_parts["record_pre"])
+    print("rollout_step %.4f ms | parts %s (record_post ~ record_pre) sum %.4f ms" % (
+        t_step, {k: round(v, 4) for k, v in t_parts.items()}, out["rollout"]["parts_sum_ms"]), flush=True)
+    print(json.dumps(out))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
