@@ -132,6 +132,17 @@ def check(rc: int, what: str = "antsrl") -> None:
         raise AntsrlError("%s failed (%d): %s" % (what, rc, msg))
 
 
+def ptr(t):
+    """A tensor's device address for the ABI (None stays NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """The current torch stream of `device` as the ABI's `void *stream`."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 class HipEvents:
     """Raw hipEvent_t handles (the ABI hook records them on the launch stream)."""
 

@@ -8,8 +8,8 @@ load_model, a settable epsilon), so main.py's loop (:92-131) runs on it as it is
 
 in which no observation is ever copied and nothing is read back to the host.  The pieces: `MemoryTrainer` (model, target
 net, Adam; its `policy` is the acting target net, as :194 acts with the target net), `DeviceReplayMemory`, and the three
-entries of antsrl_memagent.hip (antsrl_agent_select, antsrl_replay_record_pre / _post; include/antsrl.h holds their draw
-specification).
+entries in front of antsrl_memagent.hip's kernels (antsrl_agent_select, antsrl_replay_record_pre / _post;
+include/antsrl.h holds their draw specification).
 
 What the reference stores as the "before" memory.  get_action overwrites self.previous_memory with the NEW memory
 (:194) before update_replay_memory reads it (:182), so the reference stores the post-action memory in BOTH agent_states
@@ -24,13 +24,13 @@ Exploration is drawn once per environment and step (an environment is one refere
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 from . import config as cm
 from .replay import DeviceReplayMemory
 from .train import MemoryTrainer
@@ -41,10 +41,6 @@ def _backend(api_or_env):
     b = getattr(api_or_env, "_backend", api_or_env)
     assert b is not None and hasattr(b, "step_update"), "setup needs a BatchedAntsEnv or an RLApi whose perception is set up"
     return b
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class MemoryAgent:
@@ -123,7 +119,7 @@ class MemoryAgent:
                 _lib.check(self._lib.antsrl_agent_select(self.seed, step, self.env_id_base, self.n_envs, self.n_ants_per_env,
                                                          float(self.epsilon), self.rotations, self.pheromones, self.mem_size,
                                                          _p(rot), _p(ph), _p(old), _p(new), _p(self._explored),
-                                                         self._stream()), "agent_select")
+                                                         _lib.stream(self.device)), "agent_select")
         self._memory_before = old
         self._cur = 1 - self._cur
         self._action_step = step
@@ -170,8 +166,6 @@ class MemoryAgent:
         self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
 
     # ---- the fused loop -------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def rollout_step(self, env, training: bool = True):
         """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after

@@ -1,4 +1,5 @@
-// antsrl_capi.hip — the C-ABI of libantsrl_hip.so (include/antsrl.h).
+// antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), and the library's error
+// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the
@@ -12,8 +13,7 @@
 #include <new>
 
 #include "antsrl_device.h"
-#include "antsrl_memnet.h"
-#include "antsrl_memtrain.h"
+#include "antsrl_fail.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
@@ -78,7 +78,7 @@ struct AntsHandle {
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char *fmt, ...)
+int fail(int code, const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
@@ -87,13 +87,10 @@ static int fail(int code, const char *fmt, ...)
     return code;
 }
 
-static int hip_fail(hipError_t e, const char *what)
+int hip_fail(hipError_t e, const char *what)
 {
     return fail(ANTSRL_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
 }
-
-// for the translation units that hold C-ABI entries of their own (antsrl_memagent.hip)
-__attribute__((visibility("hidden"))) int antsrl_fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
 
 extern "C" int antsrl_abi_version(void) { return ANTSRL_ABI_VERSION; }
 extern "C" size_t antsrl_cfg_size(void) { return sizeof(AntsCfg); }
@@ -485,7 +482,6 @@ extern "C" int antsrl_set_obs_row_stride(AntsHandle *h, int32_t stride_elems)
     return ANTSRL_OK;
 }
 
-static int hip_fail(hipError_t e, const char *what);
 // Enqueues a deferred update on its own (k_update_one), e.g. ahead of a state read.
 static int flush_pending(AntsHandle *h, hipStream_t st)
 {
@@ -837,279 +833,6 @@ extern "C" int antsrl_policy_mlp(AntsHandle *h, const float *obs, const float *a
     hipError_t e = antsrl_launch_policy(obs, agent_state, w1, b1, w2, b2, w3, b3, rotation, pheromone, logits,
                                         (int)n_ants, n_features, (hipStream_t)stream, h && h->obs_bf16);
     if (e != hipSuccess) return hip_fail(e, "policy_mlp");
-    return ANTSRL_OK;
-}
-
-// ---- memory agent net (antsrl_memnet.hip)
-static int memnet_check(const AntsMemNetShape *s, MemNetDims *d, const char *who)
-{
-    if (!s) return fail(ANTSRL_E_INVALID, "%s: NULL shape", who);
-    if (s->n_features < 1 || s->agent_dim < 1 || s->mem_size < 1 || s->h1 < 1 || s->h2 < 1 || s->h3 < 1 || s->n_rot < 1 ||
-        s->n_ph < 1)
-        return fail(ANTSRL_E_INVALID, "%s: n_features, agent_dim, mem_size, h1, h2, h3, n_rot, n_ph must be >= 1", who);
-    const long long D = (long long)s->n_features + s->agent_dim + s->mem_size;
-    if (D > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: D = n_features + agent_dim + mem_size = %lld > 1024", who, D);
-    if (s->agent_dim > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: agent_dim %d > 32", who, s->agent_dim);
-    if (s->mem_size > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: mem_size %d > 32", who, s->mem_size);
-    if (s->h1 % 32 || s->h2 % 32 || s->h3 % 32 || s->h1 > 256 || s->h2 > 256 || s->h3 > 256)
-        return fail(ANTSRL_E_UNSUPPORTED, "%s: h1, h2, h3 (%d, %d, %d) must be multiples of 32 and <= 256", who, s->h1, s->h2,
-                    s->h3);
-    if (s->n_rot > 32 || s->n_ph > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_rot, n_ph (%d, %d) must be <= 32", who, s->n_rot, s->n_ph);
-    *d = MemNetDims{s->n_features, s->agent_dim, s->mem_size, (int)D, s->h1, s->h2, s->h3, s->n_rot, s->n_ph};
-    return ANTSRL_OK;
-}
-
-// precision: ANTSRL_MEMNET_BF16 (k_memnet) or ANTSRL_MEMNET_FP32 (k_memnet_f32), checked before anything else
-static int memnet_precision(int precision, const char *who)
-{
-    if (precision != ANTSRL_MEMNET_BF16 && precision != ANTSRL_MEMNET_FP32)
-        return fail(ANTSRL_E_INVALID, "%s: precision %d is neither ANTSRL_MEMNET_BF16 (0) nor ANTSRL_MEMNET_FP32 (1)", who,
-                    precision);
-    return ANTSRL_OK;
-}
-
-static int memnet_packed_bytes(const AntsMemNetShape *s, int precision, size_t *bytes, const char *who)
-{
-    MemNetDims d;
-    const int rc = memnet_check(s, &d, who);
-    if (rc != ANTSRL_OK) return rc;
-    if (!bytes) return fail(ANTSRL_E_INVALID, "%s: NULL bytes", who);
-    MemNetLayout L;
-    if (precision == ANTSRL_MEMNET_FP32)
-        antsrl_memnet_layout_f32(d, &L);
-    else
-        antsrl_memnet_layout(d, &L);
-    *bytes = L.bytes;
-    return ANTSRL_OK;
-}
-
-static int memnet_pack(const AntsMemNetShape *s, int precision, const float *const *params, void *packed, void *stream,
-                       const char *who)
-{
-    MemNetDims d;
-    const int rc = memnet_check(s, &d, who);
-    if (rc != ANTSRL_OK) return rc;
-    if (!params || !packed) return fail(ANTSRL_E_INVALID, "%s: params and packed are required", who);
-    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
-    MemNetParams P;
-    for (int i = 0; i < 26; ++i) {
-        if (!params[i]) return fail(ANTSRL_E_INVALID, "%s: params[%d] is NULL", who, i);
-        P.p[i] = params[i];
-    }
-    hipError_t e = precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_pack_f32((unsigned char *)packed, P, d, (hipStream_t)stream)
-                                                   : antsrl_launch_memnet_pack((unsigned char *)packed, P, d, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, who);
-    return ANTSRL_OK;
-}
-
-static int policy_memory(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
-                         const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
-                         int8_t *pheromone, float *q_out, void *stream, const char *who)
-{
-    MemNetDims d;
-    const int rc = memnet_check(s, &d, who);
-    if (rc != ANTSRL_OK) return rc;
-    if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
-        return fail(ANTSRL_E_INVALID, "%s: packed, obs, agent_state, mem_in, mem_out, rotation are required", who);
-    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
-    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
-    if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [1, 2^31)", who);
-    hipError_t e = (precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32 : antsrl_launch_memnet)(
-        (const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state, mem_in, (int)n_ants, mem_out,
-        rotation, pheromone, q_out, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, who);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes)
-{
-    return memnet_packed_bytes(s, ANTSRL_MEMNET_BF16, bytes, "memnet_packed_bytes");
-}
-
-extern "C" int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream)
-{
-    return memnet_pack(s, ANTSRL_MEMNET_BF16, params, packed, stream, "memnet_pack");
-}
-
-extern "C" int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const void *obs, int obs_format,
-                                    const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
-                                    int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
-{
-    return policy_memory(s, ANTSRL_MEMNET_BF16, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out, rotation,
-                         pheromone, q_out, stream, "policy_memory");
-}
-
-extern "C" int antsrl_memnet_packed_bytes_ex(const AntsMemNetShape *s, int precision, size_t *bytes)
-{
-    const int rc = memnet_precision(precision, "memnet_packed_bytes_ex");
-    return rc != ANTSRL_OK ? rc : memnet_packed_bytes(s, precision, bytes, "memnet_packed_bytes_ex");
-}
-
-extern "C" int antsrl_memnet_pack_ex(const AntsMemNetShape *s, int precision, const float *const *params, void *packed,
-                                     void *stream)
-{
-    const int rc = memnet_precision(precision, "memnet_pack_ex");
-    return rc != ANTSRL_OK ? rc : memnet_pack(s, precision, params, packed, stream, "memnet_pack_ex");
-}
-
-extern "C" int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, const void *packed, const void *obs,
-                                       int obs_format, const float *agent_state, const float *mem_in, int64_t n_ants,
-                                       float *mem_out, int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
-{
-    const int rc = memnet_precision(precision, "policy_memory_ex");
-    return rc != ANTSRL_OK ? rc
-                           : policy_memory(s, precision, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out,
-                                           rotation, pheromone, q_out, stream, "policy_memory_ex");
-}
-
-// ---- memory agent training step (antsrl_memtrain.hip)
-#define MT_MAX_B (1 << 24)
-
-static int memtrain_state_check(const void *state, const char *who, const char *name)
-{
-    if (!state) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
-    if ((uintptr_t)state & 255) return fail(ANTSRL_E_INVALID, "%s: %s must be 256-byte aligned", who, name);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_sizes(const AntsMemNetShape *s, int64_t B, size_t *params_floats, size_t *trained_floats,
-                                     size_t *state_bytes, size_t *workspace_bytes)
-{
-    MemNetDims d;
-    const int rc = memnet_check(s, &d, "memtrain_sizes");
-    if (rc != ANTSRL_OK) return rc;
-    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_sizes: B must be in [1, 2^24]");
-    MemTrainLayout L;
-    antsrl_memtrain_state_layout(d, &L);
-    MemTrainWork W;
-    antsrl_memtrain_work_layout(d, (int)B, &W);
-    if (params_floats) *params_floats = L.params_floats;
-    if (trained_floats) *trained_floats = L.trained_floats;
-    if (state_bytes) *state_bytes = L.bytes;
-    if (workspace_bytes) *workspace_bytes = W.bytes;
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_init(const AntsMemNetShape *s, const float *const *params, void *state, void *stream)
-{
-    MemNetDims d;
-    int rc = memnet_check(s, &d, "memtrain_init");
-    if (rc != ANTSRL_OK) return rc;
-    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_init: params is required");
-    for (int i = 0; i < 26; ++i)
-        if (!params[i]) return fail(ANTSRL_E_INVALID, "memtrain_init: params[%d] is NULL", i);
-    if ((rc = memtrain_state_check(state, "memtrain_init", "state")) != ANTSRL_OK) return rc;
-    MemTrainLayout L;
-    antsrl_memtrain_state_layout(d, &L);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char *S = (unsigned char *)state;
-    hipError_t e = hipMemsetAsync(S, 0, L.bytes, st); // m = v = 0, zero padding everywhere (the packs' included)
-    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
-        const int l = i / 2;
-        const size_t n = i % 2 ? (size_t)L.out[l] : (size_t)L.out[l] * L.in[l];
-        const size_t off = L.poff[l] + (i % 2 ? (size_t)L.out[l] * L.in[l] : 0);
-        e = hipMemcpyAsync(S + off * 4, params[i], n * 4, hipMemcpyDeviceToDevice, st);
-    }
-    if (e == hipSuccess) e = antsrl_launch_memtrain_repack(d, S, st);
-    if (e != hipSuccess) return hip_fail(e, "memtrain_init");
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_unpack(const AntsMemNetShape *s, const void *state, float *const *params, void *stream)
-{
-    MemNetDims d;
-    int rc = memnet_check(s, &d, "memtrain_unpack");
-    if (rc != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(state, "memtrain_unpack", "state")) != ANTSRL_OK) return rc;
-    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_unpack: params is required");
-    for (int i = 0; i < 26; ++i)
-        if (!params[i]) return fail(ANTSRL_E_INVALID, "memtrain_unpack: params[%d] is NULL", i);
-    MemTrainLayout L;
-    antsrl_memtrain_state_layout(d, &L);
-    const unsigned char *S = (const unsigned char *)state;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
-        const int l = i / 2;
-        const size_t n = i % 2 ? (size_t)L.out[l] : (size_t)L.out[l] * L.in[l];
-        const size_t off = L.poff[l] + (i % 2 ? (size_t)L.out[l] * L.in[l] : 0);
-        e = hipMemcpyAsync(params[i], S + off * 4, n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    }
-    if (e != hipSuccess) return hip_fail(e, "memtrain_unpack");
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_copy(const AntsMemNetShape *s, const void *src_state, void *dst_state, void *stream)
-{
-    MemNetDims d;
-    int rc = memnet_check(s, &d, "memtrain_copy");
-    if (rc != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(src_state, "memtrain_copy", "src_state")) != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(dst_state, "memtrain_copy", "dst_state")) != ANTSRL_OK) return rc;
-    MemTrainLayout L;
-    antsrl_memtrain_state_layout(d, &L);
-    const unsigned char *S = (const unsigned char *)src_state;
-    unsigned char *T = (unsigned char *)dst_state;
-    if (S == T) return ANTSRL_OK;
-    hipError_t e = hipMemcpyAsync(T, S, L.params_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(T + L.pack_off, S + L.pack_off, L.bytes - L.pack_off, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "memtrain_copy");
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_grad(const AntsMemNetShape *s, const void *state, const void *target_state,
-                                    const float *states, const float *agent_states, const int64_t *actions,
-                                    const float *rewards, const float *new_states, const float *new_agent_states,
-                                    const uint8_t *dones, const int64_t *idx, int64_t B, float discount, float *grads,
-                                    float *loss_out, void *workspace, void *stream)
-{
-    MemNetDims d;
-    int rc = memnet_check(s, &d, "memtrain_grad");
-    if (rc != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(state, "memtrain_grad", "state")) != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(target_state, "memtrain_grad", "target_state")) != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(workspace, "memtrain_grad", "workspace")) != ANTSRL_OK) return rc;
-    if (!states || !agent_states || !actions || !rewards || !new_states || !new_agent_states || !dones)
-        return fail(ANTSRL_E_INVALID, "memtrain_grad: states, agent_states, actions, rewards, new_states, new_agent_states, "
-                                      "dones are required");
-    if (!grads || !loss_out) return fail(ANTSRL_E_INVALID, "memtrain_grad: grads and loss_out are required");
-    if (((uintptr_t)states | (uintptr_t)agent_states | (uintptr_t)new_states | (uintptr_t)new_agent_states |
-         (uintptr_t)rewards | (uintptr_t)grads | (uintptr_t)loss_out) & 3)
-        return fail(ANTSRL_E_INVALID, "memtrain_grad: float arrays must be 4-byte aligned");
-    if (((uintptr_t)actions | (uintptr_t)idx) & 7)
-        return fail(ANTSRL_E_INVALID, "memtrain_grad: actions and idx must be 8-byte aligned");
-    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_grad: B must be in [1, 2^24]");
-    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "memtrain_grad: discount is NaN");
-    const MemTrainBatch bt{states, agent_states, rewards, new_states, new_agent_states, actions, idx, dones};
-    hipError_t e = antsrl_launch_memtrain_grad(d, (const unsigned char *)state, (const unsigned char *)target_state, bt,
-                                               (int)B, discount, grads, loss_out, (unsigned char *)workspace,
-                                               (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "memtrain_grad");
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *grads, int64_t step, double lr,
-                                     double beta1, double beta2, double eps, void *stream)
-{
-    MemNetDims d;
-    int rc = memnet_check(s, &d, "memtrain_apply");
-    if (rc != ANTSRL_OK) return rc;
-    if ((rc = memtrain_state_check(state, "memtrain_apply", "state")) != ANTSRL_OK) return rc;
-    if (!grads) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads is required");
-    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads must be 4-byte aligned");
-    if (step < 1) return fail(ANTSRL_E_INVALID, "memtrain_apply: step must be >= 1");
-    if (!(lr >= 0.0) || !(lr < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: lr must be finite and >= 0");
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return fail(ANTSRL_E_INVALID, "memtrain_apply: beta1, beta2 must be in [0, 1)");
-    if (!(eps > 0.0) || !(eps < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: eps must be finite and > 0");
-    // torch.optim.Adam (single tensor): the bias corrections in double, then every scalar rounded to float by the op
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = pow(bc2, 0.5);
-    hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, (float)step_size, (float)bc2_sqrt,
-                                                (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                                                (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "memtrain_apply");
     return ANTSRL_OK;
 }
 

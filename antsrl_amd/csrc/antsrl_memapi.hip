@@ -1,0 +1,456 @@
+// antsrl_memapi.hip — the memory agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h): the net's inference
+// (antsrl_memnet_*, antsrl_policy_memory*), its training step (antsrl_memtrain_*) and the loop around them
+// (antsrl_agent_select, antsrl_replay_record_*).
+//
+// Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip, antsrl_memtrain.hip
+// and antsrl_memagent.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "antsrl_device.h"
+#include "antsrl_fail.h"
+#include "antsrl_memagent.h"
+#include "antsrl_memnet.h"
+#include "antsrl_memtrain.h"
+
+// ---- the shape limits of the net's kernels, shared by the net's, the trainer's and the loop's entries
+static int check_max32(const char *who, const char *name, int32_t v)
+{
+    if (v > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: %s %d > 32", who, name, v);
+    return ANTSRL_OK;
+}
+
+static int check_D(const char *who, int32_t n_features, int32_t agent_dim, int32_t mem_size)
+{
+    const long long D = (long long)n_features + agent_dim + mem_size;
+    if (D > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: D = n_features + agent_dim + mem_size = %lld > 1024", who, D);
+    return ANTSRL_OK;
+}
+
+static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
+
+// the 26 tensors of CollectModelMemory.state_dict(): none NULL
+static int check_params(const char *who, const float *const *params)
+{
+    for (int i = 0; i < 26; ++i)
+        if (!params[i]) return fail(ANTSRL_E_INVALID, "%s: params[%d] is NULL", who, i);
+    return ANTSRL_OK;
+}
+
+// ---- the net (antsrl_memnet.hip, antsrl_memnet_f32.hip)
+static int memnet_check(const AntsMemNetShape *s, MemNetDims *d, const char *who)
+{
+    if (!s) return fail(ANTSRL_E_INVALID, "%s: NULL shape", who);
+    if (s->n_features < 1 || s->agent_dim < 1 || s->mem_size < 1 || s->h1 < 1 || s->h2 < 1 || s->h3 < 1 || s->n_rot < 1 ||
+        s->n_ph < 1)
+        return fail(ANTSRL_E_INVALID, "%s: n_features, agent_dim, mem_size, h1, h2, h3, n_rot, n_ph must be >= 1", who);
+    int rc = check_D(who, s->n_features, s->agent_dim, s->mem_size);
+    if (rc == ANTSRL_OK) rc = check_max32(who, "agent_dim", s->agent_dim);
+    if (rc == ANTSRL_OK) rc = check_max32(who, "mem_size", s->mem_size);
+    if (rc != ANTSRL_OK) return rc;
+    if (s->h1 % 32 || s->h2 % 32 || s->h3 % 32 || s->h1 > 256 || s->h2 > 256 || s->h3 > 256)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: h1, h2, h3 (%d, %d, %d) must be multiples of 32 and <= 256", who, s->h1, s->h2,
+                    s->h3);
+    // (n_rot, n_ph <= 32 has its own, combined text here and check_max32's in the loop's entries: both are tested)
+    if (s->n_rot > 32 || s->n_ph > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_rot, n_ph (%d, %d) must be <= 32", who, s->n_rot, s->n_ph);
+    const int D = s->n_features + s->agent_dim + s->mem_size; // <= 1024 (check_D)
+    *d = MemNetDims{s->n_features, s->agent_dim, s->mem_size, D, s->h1, s->h2, s->h3, s->n_rot, s->n_ph};
+    return ANTSRL_OK;
+}
+
+// precision: ANTSRL_MEMNET_BF16 (k_memnet) or ANTSRL_MEMNET_FP32 (k_memnet_f32), checked before anything else
+static int memnet_precision(int precision, const char *who)
+{
+    if (precision != ANTSRL_MEMNET_BF16 && precision != ANTSRL_MEMNET_FP32)
+        return fail(ANTSRL_E_INVALID, "%s: precision %d is neither ANTSRL_MEMNET_BF16 (0) nor ANTSRL_MEMNET_FP32 (1)", who,
+                    precision);
+    return ANTSRL_OK;
+}
+
+static int memnet_packed_bytes(const AntsMemNetShape *s, int precision, size_t *bytes, const char *who)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    if (!bytes) return fail(ANTSRL_E_INVALID, "%s: NULL bytes", who);
+    MemNetLayout L;
+    if (precision == ANTSRL_MEMNET_FP32)
+        antsrl_memnet_layout_f32(d, &L);
+    else
+        antsrl_memnet_layout(d, &L);
+    *bytes = L.bytes;
+    return ANTSRL_OK;
+}
+
+static int memnet_pack(const AntsMemNetShape *s, int precision, const float *const *params, void *packed, void *stream,
+                       const char *who)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    if (!params || !packed) return fail(ANTSRL_E_INVALID, "%s: params and packed are required", who);
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
+    const int prc = check_params(who, params);
+    if (prc != ANTSRL_OK) return prc;
+    MemNetParams P;
+    for (int i = 0; i < 26; ++i) P.p[i] = params[i];
+    hipError_t e = precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_pack_f32((unsigned char *)packed, P, d, (hipStream_t)stream)
+                                                   : antsrl_launch_memnet_pack((unsigned char *)packed, P, d, (hipStream_t)stream);
+    return enqueued(e, who);
+}
+
+static int policy_memory(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
+                         const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
+                         int8_t *pheromone, float *q_out, void *stream, const char *who)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
+        return fail(ANTSRL_E_INVALID, "%s: packed, obs, agent_state, mem_in, mem_out, rotation are required", who);
+    if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
+    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
+        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
+    if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [1, 2^31)", who);
+    hipError_t e = (precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32 : antsrl_launch_memnet)(
+        (const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state, mem_in, (int)n_ants, mem_out,
+        rotation, pheromone, q_out, (hipStream_t)stream);
+    return enqueued(e, who);
+}
+
+extern "C" int antsrl_memnet_packed_bytes(const AntsMemNetShape *s, size_t *bytes)
+{
+    return memnet_packed_bytes(s, ANTSRL_MEMNET_BF16, bytes, "memnet_packed_bytes");
+}
+
+extern "C" int antsrl_memnet_pack(const AntsMemNetShape *s, const float *const *params, void *packed, void *stream)
+{
+    return memnet_pack(s, ANTSRL_MEMNET_BF16, params, packed, stream, "memnet_pack");
+}
+
+extern "C" int antsrl_policy_memory(const AntsMemNetShape *s, const void *packed, const void *obs, int obs_format,
+                                    const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
+                                    int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
+{
+    return policy_memory(s, ANTSRL_MEMNET_BF16, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out, rotation,
+                         pheromone, q_out, stream, "policy_memory");
+}
+
+extern "C" int antsrl_memnet_packed_bytes_ex(const AntsMemNetShape *s, int precision, size_t *bytes)
+{
+    const int rc = memnet_precision(precision, "memnet_packed_bytes_ex");
+    return rc != ANTSRL_OK ? rc : memnet_packed_bytes(s, precision, bytes, "memnet_packed_bytes_ex");
+}
+
+extern "C" int antsrl_memnet_pack_ex(const AntsMemNetShape *s, int precision, const float *const *params, void *packed,
+                                     void *stream)
+{
+    const int rc = memnet_precision(precision, "memnet_pack_ex");
+    return rc != ANTSRL_OK ? rc : memnet_pack(s, precision, params, packed, stream, "memnet_pack_ex");
+}
+
+extern "C" int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, const void *packed, const void *obs,
+                                       int obs_format, const float *agent_state, const float *mem_in, int64_t n_ants,
+                                       float *mem_out, int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
+{
+    const int rc = memnet_precision(precision, "policy_memory_ex");
+    return rc != ANTSRL_OK ? rc
+                           : policy_memory(s, precision, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out,
+                                           rotation, pheromone, q_out, stream, "policy_memory_ex");
+}
+
+// ---- the training step (antsrl_memtrain.hip)
+#define MT_MAX_B (1 << 24)
+
+// tensor i of the state_dict (weight, bias per layer) in the state's flat fp32 parameter block, in floats
+struct ParamSpan {
+    size_t off, n;
+};
+static ParamSpan param_span(const MemTrainLayout &L, int i)
+{
+    const int l = i / 2;
+    const size_t w = (size_t)L.out[l] * L.in[l];
+    return i % 2 ? ParamSpan{L.poff[l] + w, (size_t)L.out[l]} : ParamSpan{L.poff[l], w};
+}
+
+static int memtrain_state_check(const void *state, const char *who, const char *name)
+{
+    if (!state) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
+    if ((uintptr_t)state & 255) return fail(ANTSRL_E_INVALID, "%s: %s must be 256-byte aligned", who, name);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_sizes(const AntsMemNetShape *s, int64_t B, size_t *params_floats, size_t *trained_floats,
+                                     size_t *state_bytes, size_t *workspace_bytes)
+{
+    MemNetDims d;
+    const int rc = memnet_check(s, &d, "memtrain_sizes");
+    if (rc != ANTSRL_OK) return rc;
+    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_sizes: B must be in [1, 2^24]");
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    MemTrainWork W;
+    antsrl_memtrain_work_layout(d, (int)B, &W);
+    if (params_floats) *params_floats = L.params_floats;
+    if (trained_floats) *trained_floats = L.trained_floats;
+    if (state_bytes) *state_bytes = L.bytes;
+    if (workspace_bytes) *workspace_bytes = W.bytes;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_memtrain_init(const AntsMemNetShape *s, const float *const *params, void *state, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_init");
+    if (rc != ANTSRL_OK) return rc;
+    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_init: params is required");
+    if ((rc = check_params("memtrain_init", params)) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_init", "state")) != ANTSRL_OK) return rc;
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char *S = (unsigned char *)state;
+    hipError_t e = hipMemsetAsync(S, 0, L.bytes, st); // m = v = 0, zero padding everywhere (the packs' included)
+    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
+        const ParamSpan p = param_span(L, i);
+        e = hipMemcpyAsync(S + p.off * 4, params[i], p.n * 4, hipMemcpyDeviceToDevice, st);
+    }
+    if (e == hipSuccess) e = antsrl_launch_memtrain_repack(d, S, st);
+    return enqueued(e, "memtrain_init");
+}
+
+extern "C" int antsrl_memtrain_unpack(const AntsMemNetShape *s, const void *state, float *const *params, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_unpack");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_unpack", "state")) != ANTSRL_OK) return rc;
+    if (!params) return fail(ANTSRL_E_INVALID, "memtrain_unpack: params is required");
+    if ((rc = check_params("memtrain_unpack", params)) != ANTSRL_OK) return rc;
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const unsigned char *S = (const unsigned char *)state;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 26 && e == hipSuccess; ++i) {
+        const ParamSpan p = param_span(L, i);
+        e = hipMemcpyAsync(params[i], S + p.off * 4, p.n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    }
+    return enqueued(e, "memtrain_unpack");
+}
+
+extern "C" int antsrl_memtrain_copy(const AntsMemNetShape *s, const void *src_state, void *dst_state, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_copy");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(src_state, "memtrain_copy", "src_state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(dst_state, "memtrain_copy", "dst_state")) != ANTSRL_OK) return rc;
+    MemTrainLayout L;
+    antsrl_memtrain_state_layout(d, &L);
+    const unsigned char *S = (const unsigned char *)src_state;
+    unsigned char *T = (unsigned char *)dst_state;
+    if (S == T) return ANTSRL_OK;
+    hipError_t e = hipMemcpyAsync(T, S, L.params_floats * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(T + L.pack_off, S + L.pack_off, L.bytes - L.pack_off, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    return enqueued(e, "memtrain_copy");
+}
+
+extern "C" int antsrl_memtrain_grad(const AntsMemNetShape *s, const void *state, const void *target_state,
+                                    const float *states, const float *agent_states, const int64_t *actions,
+                                    const float *rewards, const float *new_states, const float *new_agent_states,
+                                    const uint8_t *dones, const int64_t *idx, int64_t B, float discount, float *grads,
+                                    float *loss_out, void *workspace, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_grad");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_grad", "state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(target_state, "memtrain_grad", "target_state")) != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(workspace, "memtrain_grad", "workspace")) != ANTSRL_OK) return rc;
+    if (!states || !agent_states || !actions || !rewards || !new_states || !new_agent_states || !dones)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: states, agent_states, actions, rewards, new_states, new_agent_states, "
+                                      "dones are required");
+    if (!grads || !loss_out) return fail(ANTSRL_E_INVALID, "memtrain_grad: grads and loss_out are required");
+    if (((uintptr_t)states | (uintptr_t)agent_states | (uintptr_t)new_states | (uintptr_t)new_agent_states |
+         (uintptr_t)rewards | (uintptr_t)grads | (uintptr_t)loss_out) & 3)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: float arrays must be 4-byte aligned");
+    if (((uintptr_t)actions | (uintptr_t)idx) & 7)
+        return fail(ANTSRL_E_INVALID, "memtrain_grad: actions and idx must be 8-byte aligned");
+    if (B < 1 || B > MT_MAX_B) return fail(ANTSRL_E_INVALID, "memtrain_grad: B must be in [1, 2^24]");
+    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "memtrain_grad: discount is NaN");
+    const MemTrainBatch bt{states, agent_states, rewards, new_states, new_agent_states, actions, idx, dones};
+    hipError_t e = antsrl_launch_memtrain_grad(d, (const unsigned char *)state, (const unsigned char *)target_state, bt,
+                                               (int)B, discount, grads, loss_out, (unsigned char *)workspace,
+                                               (hipStream_t)stream);
+    return enqueued(e, "memtrain_grad");
+}
+
+extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *grads, int64_t step, double lr,
+                                     double beta1, double beta2, double eps, void *stream)
+{
+    MemNetDims d;
+    int rc = memnet_check(s, &d, "memtrain_apply");
+    if (rc != ANTSRL_OK) return rc;
+    if ((rc = memtrain_state_check(state, "memtrain_apply", "state")) != ANTSRL_OK) return rc;
+    if (!grads) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads is required");
+    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads must be 4-byte aligned");
+    if (step < 1) return fail(ANTSRL_E_INVALID, "memtrain_apply: step must be >= 1");
+    if (!(lr >= 0.0) || !(lr < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: lr must be finite and >= 0");
+    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+        return fail(ANTSRL_E_INVALID, "memtrain_apply: beta1, beta2 must be in [0, 1)");
+    if (!(eps > 0.0) || !(eps < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: eps must be finite and > 0");
+    // torch.optim.Adam (single tensor): the bias corrections in double, then every scalar rounded to float by the op
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const double step_size = lr / bc1, bc2_sqrt = pow(bc2, 0.5);
+    hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, (float)step_size, (float)bc2_sqrt,
+                                                (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
+                                                (hipStream_t)stream);
+    return enqueued(e, "memtrain_apply");
+}
+
+// ---- the loop (antsrl_memagent.hip)
+static int check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants)
+{
+    if (n_envs < 1 || n_ants < 1) return fail(ANTSRL_E_INVALID, "%s: n_envs and n_ants must be >= 1 (%d, %d)", who, n_envs, n_ants);
+    if ((long long)n_envs * n_ants > 0x7fffffffLL)
+        return fail(ANTSRL_E_INVALID, "%s: n_envs * n_ants = %lld must stay below 2^31", who, (long long)n_envs * n_ants);
+    if (env_id_base < 0 || (long long)env_id_base + n_envs > 0x7fffffffLL)
+        return fail(ANTSRL_E_INVALID, "%s: env_id_base must be >= 0 and env_id_base + n_envs must fit 31 bits", who);
+    return ANTSRL_OK;
+}
+
+static int check_width(const char *who, const char *name, int32_t v)
+{
+    if (v < 1) return fail(ANTSRL_E_INVALID, "%s: %s must be >= 1 (%d)", who, name, v);
+    return check_max32(who, name, v);
+}
+
+#define MISALIGNED(p, n) (((uintptr_t)(p) & ((n) - 1)) != 0)
+
+extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
+                                   double epsilon, int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation,
+                                   int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored, void *stream)
+{
+    const char *who = "agent_select";
+    int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
+    if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
+    if (rc == ANTSRL_OK) rc = check_width(who, "mem_size", mem_size);
+    if (rc != ANTSRL_OK) return rc;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
+    if (!rotation) return fail(ANTSRL_E_INVALID, "%s: rotation is required", who);
+    if (!pheromone) return fail(ANTSRL_E_INVALID, "%s: pheromone is required", who);
+    if (!mem_old) return fail(ANTSRL_E_INVALID, "%s: mem_old is required", who);
+    if (!mem_next) return fail(ANTSRL_E_INVALID, "%s: mem_next is required", who);
+    if (MISALIGNED(mem_old, 4) || MISALIGNED(mem_next, 4)) return fail(ANTSRL_E_INVALID, "%s: mem_old and mem_next must be 4-byte aligned", who);
+    if (mem_old != mem_next) { // the same buffer, or two that do not touch
+        const uintptr_t o = (uintptr_t)mem_old, n = (uintptr_t)mem_next;
+        const uintptr_t bytes = (uintptr_t)n_envs * (uintptr_t)n_ants * (uintptr_t)mem_size * 4;
+        if (o < n + bytes && n < o + bytes) return fail(ANTSRL_E_INVALID, "%s: mem_old and mem_next overlap without being equal", who);
+    }
+    SelArgs a;
+    a.seed = seed; a.step = step; a.epsilon = epsilon;
+    a.rot = rotation; a.ph = pheromone; a.mem_old = mem_old; a.mem_next = mem_next; a.explored = explored;
+    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants; a.n_rot = (uint32_t)n_rot; a.n_ph = (uint32_t)n_ph;
+    a.M = (uint32_t)((long long)n_envs * n_ants);
+    const uint64_t env_floats = (uint64_t)n_ants * (uint64_t)mem_size;
+    const bool vec = env_floats % 4 == 0 && !MISALIGNED(mem_old, 16) && !MISALIGNED(mem_next, 16);
+    const uint64_t env_elems = vec ? env_floats / 4 : env_floats;
+    if (env_elems > 0xffffffffULL) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_ants * mem_size = %llu is too large", who, (unsigned long long)env_floats);
+    a.env_elems = (uint32_t)env_elems;
+    a.mem_elems = env_elems * (uint64_t)n_envs;
+    return enqueued(antsrl_launch_agent_select(a, vec, (hipStream_t)stream), who);
+}
+
+static int check_spec(const char *who, const AntsRecordSpec *r)
+{
+    if (!r) return fail(ANTSRL_E_INVALID, "%s: NULL spec", who);
+    int rc = check_batch(who, r->env_id_base, r->n_envs, r->n_ants);
+    if (rc != ANTSRL_OK) return rc;
+    if (r->n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, r->n_features);
+    if ((rc = check_width(who, "agent_dim", r->agent_dim)) != ANTSRL_OK) return rc;
+    if ((rc = check_width(who, "mem_size", r->mem_size)) != ANTSRL_OK) return rc;
+    if ((rc = check_width(who, "n_rot", r->n_rot)) != ANTSRL_OK) return rc;
+    if ((rc = check_D(who, r->n_features, r->agent_dim, r->mem_size)) != ANTSRL_OK) return rc;
+    if (r->obs_format != ANTSRL_OBS_F32 && r->obs_format != ANTSRL_OBS_BF16)
+        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16 (%d)", who, r->obs_format);
+    if (r->obs_pitch != 0 && (r->obs_pitch < r->n_features || r->obs_pitch >= (1 << 24)))
+        return fail(ANTSRL_E_INVALID, "%s: obs_pitch %d: 0 (dense) or at least the row's %d elements (and below 2^24)", who,
+                    r->obs_pitch, r->n_features);
+    const long long M = (long long)r->n_envs * r->n_ants;
+    if (r->K < 1 || r->K > M) return fail(ANTSRL_E_INVALID, "%s: K must be in [1, n_envs * n_ants = %lld] (%lld)", who, M, (long long)r->K);
+    if (r->max_len < 1) return fail(ANTSRL_E_INVALID, "%s: max_len must be >= 1 (%lld)", who, (long long)r->max_len);
+    if (r->max_len > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: max_len must be <= 2^40", who);
+    if (r->head < 0 || r->head >= r->max_len)
+        return fail(ANTSRL_E_INVALID, "%s: head must be in [0, max_len = %lld) (%lld)", who, (long long)r->max_len, (long long)r->head);
+    return ANTSRL_OK;
+}
+
+static void fill_rec(const AntsRecordSpec *r, RecArgs *a)
+{
+    a->seed = r->seed; a->step = r->step; a->env_base = (uint64_t)r->env_id_base;
+    a->M = (long long)r->n_envs * r->n_ants; a->K = r->K;
+    a->n_write = r->K < r->max_len ? r->K : r->max_len; // only the newest max_len entries can survive
+    a->j0 = r->K - a->n_write;
+    a->row0 = (r->head + a->j0) % r->max_len;
+    a->max_len = r->max_len;
+    a->pitch = r->obs_pitch ? r->obs_pitch : r->n_features;
+    a->n_ants = r->n_ants; a->F = r->n_features; a->A = r->agent_dim; a->mem = r->mem_size; a->half_rot = r->n_rot / 2;
+}
+
+static int launch_rec(const char *who, const AntsRecordSpec *r, const RecArgs &a, bool post, void *stream)
+{
+    return enqueued(antsrl_launch_replay_record(a, r->obs_format == ANTSRL_OBS_BF16, post, (hipStream_t)stream), who);
+}
+
+#define REQUIRE(p, align)                                                                                    \
+    do {                                                                                                     \
+        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                              \
+        if (MISALIGNED(p, align)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
+    } while (0)
+
+extern "C" int antsrl_replay_record_pre(const AntsRecordSpec *r, const void *obs, const float *agent_state,
+                                        const float *memory, const int8_t *rotation, const int8_t *pheromone, float *states,
+                                        float *agent_states, int64_t *actions, void *stream)
+{
+    const char *who = "replay_record_pre";
+    const int rc = check_spec(who, r);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
+    REQUIRE(agent_state, 4);
+    REQUIRE(memory, 4);
+    REQUIRE(rotation, 1);
+    REQUIRE(states, 4);
+    REQUIRE(agent_states, 4);
+    REQUIRE(actions, 8);
+    RecArgs a = {};
+    fill_rec(r, &a);
+    a.obs = obs; a.agent_state = agent_state; a.memory = memory; a.rot = rotation; a.ph = pheromone;
+    a.states = states; a.agent_states = agent_states; a.actions = actions;
+    return launch_rec(who, r, a, false, stream);
+}
+
+extern "C" int antsrl_replay_record_post(const AntsRecordSpec *r, const void *obs, const float *agent_state,
+                                         const float *memory, const float *reward, const uint8_t *done, float *rewards,
+                                         float *new_states, float *new_agent_states, uint8_t *dones, void *stream)
+{
+    const char *who = "replay_record_post";
+    const int rc = check_spec(who, r);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
+    REQUIRE(agent_state, 4);
+    REQUIRE(memory, 4);
+    REQUIRE(reward, 4);
+    REQUIRE(done, 1);
+    REQUIRE(rewards, 4);
+    REQUIRE(new_states, 4);
+    REQUIRE(new_agent_states, 4);
+    REQUIRE(dones, 1);
+    RecArgs a = {};
+    fill_rec(r, &a);
+    a.obs = obs; a.agent_state = agent_state; a.memory = memory; a.reward = reward; a.done = done;
+    a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
+    return launch_rec(who, r, a, true, stream);
+}

@@ -34,40 +34,19 @@
 // at power 5, 236 032 at power 4, F = 294) is read from L2 once: 2.3 GB per c3 batch at power 5 instead of the 9.3 GB
 // of one read per 32 ants.  LDS at D <= 320: 4 x 20.5 KiB of x / g tiles + the 64 KiB chunk = 146 KiB, one workgroup
 // per CU.  DESIGN §7.6 has the measurements.
+//
+// Shared with k_memnet_f32 (antsrl_memnet_dev.h): the packed layout, the input and bias helpers, argmax, the wave-local
+// LDS hand-off and the launcher.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "antsrl_memnet.h"
 #include "antsrl_memnet_dev.h"
-#define ANTSRL_MAX_DEVICES 64 // per-device launch bookkeeping (dynamic-LDS opt-in), as in antsrl_util.h
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 #define MN_MAXT 8 // hidden tiles held in registers: widths <= 256
 
-// ------------------------------------------------------------------------------------------------------------------
-// host + device: the packed layout (private to the library)
-// ------------------------------------------------------------------------------------------------------------------
-static inline size_t mn_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool antsrl_memnet_layout(const MemNetDims &d, MemNetLayout *L)
-{
-    const int Dp = (d.D + 31) / 32 * 32;
-    // in width (padded to 32), out tiles, A order
-    const int in_w[MN_NLAYERS] = {Dp, d.h2, d.h3, d.h1, Dp, d.h2, d.h3, Dp, d.h1, Dp, d.h2, d.h2};
-    const int out_w[MN_NLAYERS] = {d.h2, d.h3, d.h1, Dp, d.h2, d.h3, 32, d.h1, 32, d.h2, d.h2, 64};
-    size_t off = 0;
-    L->Dp = Dp;
-    for (int i = 0; i < MN_NLAYERS; ++i) {
-        L->ks[i] = in_w[i] / 16;
-        L->tout[i] = out_w[i] / 32;
-        L->frag_off[i] = off;
-        off = mn_align(off + (size_t)L->tout[i] * L->ks[i] * 64 * 16);
-        L->bias_off[i] = off;
-        off = mn_align(off + (size_t)L->tout[i] * 32 * 4);
-    }
-    L->bytes = off;
-    return true;
-}
+bool antsrl_memnet_layout(const MemNetDims &d, MemNetLayout *L) { return mn_layout(d, 16, L); } // ks = k-steps of 16 inputs
 
 __global__ void __launch_bounds__(64)
 k_memnet_pack(unsigned char *__restrict__ pack, MemNetParams P, MemNetDims d, MemNetLayout L)
@@ -254,9 +233,7 @@ k_memnet(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNet
 #pragma unroll
         for (int p = 0; p < 16; ++p) xt[(2 * p + h) * stride + k] = (__bf16)xv[p];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync();
     const __bf16 *brow = xt + r * stride + 8 * h;
 
     bf16x8 u[2 * MN_MAXT], v[2 * MN_MAXT];
@@ -264,9 +241,7 @@ k_memnet(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNet
     mn_layer_lds(pk, L, 0, brow, u, true, lane, h, wbuf, wcap); // L1
     mn_layer_reg(pk, L, 1, u, v, true, lane, h, wbuf, wcap);    // L2
     mn_layer_reg(pk, L, 2, v, u, true, lane, h, wbuf, wcap);    // L3
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every lane's L1 reads of x are done before g overwrites it
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync(); // every lane's L1 reads of x are done before g overwrites it
     {
         // L4 + residual, one output tile at a time, into the LDS tile as g (bf16)
         const float *b = reinterpret_cast<const float *>(pk + L.bias_off[3]);
@@ -291,9 +266,7 @@ k_memnet(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNet
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync();
 
     // ---- rotation head: R3(R2(R1(g)))
     {
@@ -381,27 +354,8 @@ hipError_t antsrl_launch_memnet(const unsigned char *pack, const MemNetDims &d, 
     antsrl_memnet_layout(d, &L);
     const MemNetIO io{obs, agent_state, mem_in, mem_out, q_out, rot, ph, M};
     // LDS: one [32][Dp + 8] bf16 tile per wave + the shared weight chunk (>= one output tile of an x / g layer: Dp / 16
-    // fragments).  As many waves as fit in 160 KiB, up to MN_WAVES (D <= 320: 4 waves, 146 KiB; D = 1024: 1 wave).
+    // fragments): D <= 320: 4 waves, 146 KiB; D = 1024: 1 wave
     const int wcap = L.Dp / 16 * 64 > MN_WCAP ? L.Dp / 16 * 64 : MN_WCAP;
-    const size_t tile = (size_t)32 * (L.Dp + 8) * 2;
-    int nw = MN_WAVES;
-    while (nw > 1 && nw * tile + (size_t)wcap * 16 > 160 * 1024) --nw;
-    const size_t lds = nw * tile + (size_t)wcap * 16;
-    const int blocks = (M + 32 * nw - 1) / (32 * nw);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ANTSRL_MAX_DEVICES) return hipErrorInvalidDevice;
-    hipError_t e = hipSuccess;
-    // more than 64 KiB of dynamic LDS is an opt-in per kernel function and per device
-    if (obs_bf16) {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_memnet<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_memnet<true>, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L, wcap);
-    } else {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_memnet<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_memnet<false>, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L, wcap);
-    }
-    return hipGetLastError();
+    return mn_launch<k_memnet<true>, k_memnet<false>>(pack, io, d, L, obs_bf16, MN_WAVES, (size_t)32 * (L.Dp + 8) * 2,
+                                                      (size_t)wcap * 16, st, wcap);
 }

@@ -1,12 +1,40 @@
-// antsrl_memnet_dev.h — device helpers shared by the memory agent net's two forward kernels, k_memnet (bf16 operands,
-// antsrl_memnet.hip) and k_memnet_f32 (fp32 operands, antsrl_memnet_f32.hip): the source rows of a packed layer, the
-// forward's pointers, the fp32 input x, biases and the heads' argmax in the 32x32 accumulator layout.
+// antsrl_memnet_dev.h — what the memory agent net's two forward kernels share: k_memnet (bf16 operands, antsrl_memnet.hip)
+// and k_memnet_f32 (fp32 operands, antsrl_memnet_f32.hip).  The packed layout, the source rows of a packed layer, the
+// forward's pointers, the fp32 input x, biases, the heads' argmax in the 32x32 accumulator layout, the wave-local LDS
+// hand-off and the launcher.  The steps inside the kernels (the pack frame, staging x, L4's residual, the epilogues) stay
+// written out in each .hip file: moved into a shared helper, each of them changes the compiler's schedule of both kernels
+// (sgpr spills 55 -> 70 in k_memnet<false>, 1.7 % on the power-4 forward), and the kernels are to stay as they are.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_lds_optin.h"
 #include "antsrl_memnet.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+// the packed layout (private to the library); k_unit = inputs per `ks` unit: 16 (bf16 k-step) or 8 (fp32 k-group)
+static inline size_t mn_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+static inline bool mn_layout(const MemNetDims &d, int k_unit, MemNetLayout *L)
+{
+    const int Dp = (d.D + 31) / 32 * 32;
+    // in width (padded to 32), out tiles, A order
+    const int in_w[MN_NLAYERS] = {Dp, d.h2, d.h3, d.h1, Dp, d.h2, d.h3, Dp, d.h1, Dp, d.h2, d.h2};
+    const int out_w[MN_NLAYERS] = {d.h2, d.h3, d.h1, Dp, d.h2, d.h3, 32, d.h1, 32, d.h2, d.h2, 64};
+    size_t off = 0;
+    L->Dp = Dp;
+    for (int i = 0; i < MN_NLAYERS; ++i) {
+        L->ks[i] = in_w[i] / k_unit;
+        L->tout[i] = out_w[i] / 32;
+        L->frag_off[i] = off;
+        off = mn_align(off + (size_t)L->tout[i] * L->ks[i] * 64 * 16);
+        L->bias_off[i] = off;
+        off = mn_align(off + (size_t)L->tout[i] * 32 * 4);
+    }
+    L->bytes = off;
+    return true;
+}
 
 // source rows of packed layer i: (tensor index in state_dict order, row) of output row o, or -1 for a zero row
 __device__ __forceinline__ int mn_src(int i, int o, const MemNetDims &d, int *row)
@@ -80,4 +108,32 @@ __device__ __forceinline__ int mn_argmax(const f32x16 &v, int n, int h)
     const int oi = __shfl_xor(bi, 32);
     if (oi != (1 << 30) && (bi == (1 << 30) || ob > best || (ob == best && oi < bi))) bi = oi;
     return bi;
+}
+
+// wave-local LDS hand-off: every lane's accesses to the wave's tile before it are done before any after it
+__device__ __forceinline__ void mn_tile_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// host: the launcher.  K16 / K32 = the forward kernel for bfloat16 / float32 observations; LDS = one `tile` per wave
+// (32 ants) + `shared` bytes per workgroup, as many waves as fit in 160 KiB, up to max_waves; extra = what the kernel
+// takes behind (pack, io, d, L).
+template <auto K16, auto K32, typename... Extra>
+static hipError_t mn_launch(const unsigned char *pack, const MemNetIO &io, const MemNetDims &d, const MemNetLayout &L,
+                            bool obs_bf16, int max_waves, size_t tile, size_t shared, hipStream_t st, Extra... extra)
+{
+    int nw = max_waves;
+    while (nw > 1 && nw * tile + shared > 160 * 1024) --nw;
+    const size_t lds = nw * tile + shared;
+    const int blocks = (io.M + 32 * nw - 1) / (32 * nw);
+    const hipError_t e = obs_bf16 ? antsrl_lds_optin<K16>(lds) : antsrl_lds_optin<K32>(lds);
+    if (e != hipSuccess) return e;
+    if (obs_bf16)
+        hipLaunchKernelGGL(K16, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L, extra...);
+    else
+        hipLaunchKernelGGL(K32, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L, extra...);
+    return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // antsrl_memnet_f32.hip — the memory agent net's forward with fp32 MFMA operands (ANTSRL_MEMNET_FP32): the same net,
 // shapes and outputs as k_memnet (antsrl_memnet.hip), evaluated with v_mfma_f32_32x32x2_f32, so that nothing is rounded
-// to bf16 anywhere.
+// to bf16 anywhere.  What the two kernels share is in antsrl_memnet_dev.h.
 //
 // Precision contract (what tests/memory_policy_ref.py::fp32_forward restates, up to fp32 summation order):
 //  - MFMA operands are fp32 (weights, x, the hidden values, g, the head intermediates), accumulation fp32;
@@ -29,9 +29,6 @@
 #include <stdint.h>
 #include "antsrl_memnet.h"
 #include "antsrl_memnet_dev.h"
-#define ANTSRL_MAX_DEVICES 64 // per-device launch bookkeeping (dynamic-LDS opt-in), as in antsrl_util.h
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define M32_MAXT 8 // hidden tiles held in registers: widths <= 256
 #define M32_PF 4   // k-groups of A fragments in flight (one group = 4 MFMAs = 256 cycles)
@@ -39,29 +36,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define M32_WAVES 4 // waves per workgroup, as many as the LDS tiles allow
 #endif
 
-// ------------------------------------------------------------------------------------------------------------------
-// host + device: the packed layout (private to the library)
-// ------------------------------------------------------------------------------------------------------------------
-static inline size_t m32_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool antsrl_memnet_layout_f32(const MemNetDims &d, MemNetLayout *L)
-{
-    const int Dp = (d.D + 31) / 32 * 32;
-    const int in_w[MN_NLAYERS] = {Dp, d.h2, d.h3, d.h1, Dp, d.h2, d.h3, Dp, d.h1, Dp, d.h2, d.h2};
-    const int out_w[MN_NLAYERS] = {d.h2, d.h3, d.h1, Dp, d.h2, d.h3, 32, d.h1, 32, d.h2, d.h2, 64};
-    size_t off = 0;
-    L->Dp = Dp;
-    for (int i = 0; i < MN_NLAYERS; ++i) {
-        L->ks[i] = in_w[i] / 8; // k-groups of 8 inputs
-        L->tout[i] = out_w[i] / 32;
-        L->frag_off[i] = off;
-        off = m32_align(off + (size_t)L->tout[i] * L->ks[i] * 64 * 16);
-        L->bias_off[i] = off;
-        off = m32_align(off + (size_t)L->tout[i] * 32 * 4);
-    }
-    L->bytes = off;
-    return true;
-}
+bool antsrl_memnet_layout_f32(const MemNetDims &d, MemNetLayout *L) { return mn_layout(d, 8, L); } // ks = k-groups of 8 inputs
 
 __global__ void __launch_bounds__(64)
 k_memnet_pack_f32(unsigned char *__restrict__ pack, MemNetParams P, MemNetDims d, MemNetLayout L)
@@ -230,9 +205,7 @@ k_memnet_f32(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, Me
 #pragma unroll
         for (int p = 0; p < 16; ++p) xt[(2 * p + h) * Dp + m32_swz(2 * p + h, k)] = xv[p];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync();
     float *xrow = xt + r * Dp;
 
     f32x16 u[M32_MAXT], v[M32_MAXT];
@@ -240,9 +213,7 @@ k_memnet_f32(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, Me
     m32_layer_lds(pk, L, 0, xrow, u, true, lane, r, h); // L1
     m32_layer_reg(pk, L, 1, u, v, true, lane, h);       // L2
     m32_layer_reg(pk, L, 2, v, u, true, lane, h);       // L3
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // every lane's L1 reads of x are done before g overwrites it
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync(); // every lane's L1 reads of x are done before g overwrites it
     {
         // L4 + residual, one output tile at a time, into the LDS tile as g (fp32)
         const f32x4 *A = reinterpret_cast<const f32x4 *>(pk + L.frag_off[3]) + lane;
@@ -268,9 +239,7 @@ k_memnet_f32(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, Me
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    mn_tile_sync();
 
     const int nq = d.n_rot + d.n_ph;
     // ---- rotation head: R3(R2(R1(g)))
@@ -343,26 +312,6 @@ hipError_t antsrl_launch_memnet_f32(const unsigned char *pack, const MemNetDims 
     MemNetLayout L;
     antsrl_memnet_layout_f32(d, &L);
     const MemNetIO io{obs, agent_state, mem_in, mem_out, q_out, rot, ph, M};
-    // LDS: one fp32 [32][Dp] tile per wave, as many waves as fit in 160 KiB (D <= 320: 4; D = 1024: 1)
-    const size_t tile = (size_t)32 * L.Dp * 4;
-    int nw = M32_WAVES;
-    while (nw > 1 && nw * tile > 160 * 1024) --nw;
-    const size_t lds = nw * tile;
-    const int blocks = (M + 32 * nw - 1) / (32 * nw);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ANTSRL_MAX_DEVICES) return hipErrorInvalidDevice;
-    hipError_t e = hipSuccess;
-    // more than 64 KiB of dynamic LDS is an opt-in per kernel function and per device
-    if (obs_bf16) {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_memnet_f32<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_memnet_f32<true>, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L);
-    } else {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_memnet_f32<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_memnet_f32<false>, dim3(blocks), dim3(64 * nw), lds, st, pack, io, d, L);
-    }
-    return hipGetLastError();
+    // LDS: one fp32 [32][Dp] tile per wave and nothing shared (D <= 320: 4 waves; D = 1024: 1)
+    return mn_launch<k_memnet_f32<true>, k_memnet_f32<false>>(pack, io, d, L, obs_bf16, M32_WAVES, (size_t)32 * L.Dp * 4, 0, st);
 }

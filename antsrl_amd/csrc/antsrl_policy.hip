@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "antsrl_device.h"
-#define ANTSRL_MAX_DEVICES 64 // per-device launch bookkeeping (dynamic-LDS opt-in), as in antsrl_util.h
+#include "antsrl_lds_optin.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -499,22 +499,15 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
             per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
             int blocks = (ntiles + 1) / 2;
             if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-            hipError_t e = hipSuccess;
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ANTSRL_MAX_DEVICES) return hipErrorInvalidDevice;
-            if (obs_bf16) {
-                static size_t attr[ANTSRL_MAX_DEVICES] = {}; // per kernel function and per device
-                if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_policy_flat<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-                if (e != hipSuccess) return e;
+            // more than 64 KiB of dynamic LDS is an opt-in per kernel function and per device (like k_act)
+            const hipError_t e = obs_bf16 ? antsrl_lds_optin<k_policy_flat<true>>(lds) : antsrl_lds_optin<k_policy_flat<false>>(lds);
+            if (e != hipSuccess) return e;
+            if (obs_bf16)
                 hipLaunchKernelGGL(k_policy_flat<true>, dim3(blocks), dim3(128), lds, st, obs, agent_state, w1, b1, w2, b2, w3,
                                    b3, rot, ph, logits, M, F, ks, tile_elems);
-            } else {
-                static size_t attr[ANTSRL_MAX_DEVICES] = {}; // per kernel function and per device
-                if (lds > attr[dev]) { e = hipFuncSetAttribute((const void *)k_policy_flat<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr[dev] = lds; }
-                if (e != hipSuccess) return e;
+            else
                 hipLaunchKernelGGL(k_policy_flat<false>, dim3(blocks), dim3(128), lds, st, obs, agent_state, w1, b1, w2, b2, w3,
                                    b3, rot, ph, logits, M, F, ks, tile_elems);
-            }
             return hipGetLastError();
         }
     }
@@ -526,27 +519,13 @@ hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, cons
     int per_cu = (int)((160 * 1024) / lds); // resident workgroups per CU by LDS (38-41 KiB each for the reference's sizes)
     per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
     if (blocks > 256 * per_cu) blocks = 256 * per_cu; // tiles are looped: one round of workgroups
-    // more than 64 KiB of dynamic LDS is an opt-in per kernel function and per device (like k_policy_flat, k_act)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= ANTSRL_MAX_DEVICES) return hipErrorInvalidDevice;
-    if (obs_bf16) {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void *)k_policy_mlp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr[dev] = lds;
-        }
+    const hipError_t e = obs_bf16 ? antsrl_lds_optin<k_policy_mlp<true>>(lds) : antsrl_lds_optin<k_policy_mlp<false>>(lds);
+    if (e != hipSuccess) return e;
+    if (obs_bf16)
         hipLaunchKernelGGL(k_policy_mlp<true>, dim3(blocks), dim3(256), lds, st, obs, agent_state, w1, b1, w2, b2, w3, b3,
                            rot, ph, logits, M, F, ksteps);
-    } else {
-        static size_t attr[ANTSRL_MAX_DEVICES] = {};
-        if (lds > attr[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void *)k_policy_mlp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            attr[dev] = lds;
-        }
+    else
         hipLaunchKernelGGL(k_policy_mlp<false>, dim3(blocks), dim3(256), lds, st, obs, agent_state, w1, b1, w2, b2, w3, b3,
                            rot, ph, logits, M, F, ksteps);
-    }
     return hipGetLastError();
 }

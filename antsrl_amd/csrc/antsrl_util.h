@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include "antsrl_device.h"
 #include "antsrl_layout.h"
+#include "antsrl_lds_optin.h" // ANTSRL_MAX_DEVICES, antsrl_lds_optin
 
 #define WAVE 64
 #define PI_D 3.141592653589793
@@ -145,7 +146,6 @@ __device__ __forceinline__ void wave_lds_sync()
 // device re-reads them within the step, and at 0.7 GB per launch a cached write stream evicts the
 // pheromone/food lines the perception gathers reuse and the ant state k_update reads next
 // (measured on c3, same box: k_act 0.340 -> 0.287 ms, k_update 0.051 -> 0.043 ms).
-#define ANTSRL_MAX_DEVICES 64 // per-device launch bookkeeping (dynamic-LDS opt-in)
 typedef float stream_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t stream_u4 __attribute__((ext_vector_type(4)));
 #define ANTSRL_NT_STORE(v, p) __builtin_nontemporal_store(v, p) // (plain stores: k_perceive 0.278 against 0.233 ms)

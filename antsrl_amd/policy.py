@@ -20,6 +20,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 
 class LinearPolicy:
@@ -73,14 +74,11 @@ class LinearPolicy:
             self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
             self._ph = torch.empty((m,), dtype=torch.int8, device=self.device) if self.w3 is not None else None
 
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(self._lib.antsrl_policy_mlp(handle, p(obs), p(agent_state), m, self.n_features, p(self.w1),
-                                                   p(self.b1), p(self.w2), p(self.b2), p(self.w3), p(self.b3),
-                                                   p(self._rot), p(self._ph), p(logits), st), "policy_mlp")
+            st = _lib.stream(self.device)
+            _lib.check(self._lib.antsrl_policy_mlp(handle, _p(obs), _p(agent_state), m, self.n_features, _p(self.w1),
+                                                   _p(self.b1), _p(self.w2), _p(self.b2), _p(self.w3), _p(self.b3),
+                                                   _p(self._rot), _p(self._ph), _p(logits), st), "policy_mlp")
         rot = self._rot.view(lead)
         return rot, (self._ph.view(lead) if self._ph is not None else None)
 
@@ -94,13 +92,10 @@ class LinearPolicy:
         env.next_rotation = torch.zeros((E, N), dtype=torch.int8, device=self.device)
         env.next_pheromone = torch.zeros((E, N), dtype=torch.int8, device=self.device) if self.w3 is not None else None
 
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
         with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, p(self.w1), p(self.b1), p(self.w2), p(self.b2),
-                                                          p(self.w3), p(self.b3), p(env.next_rotation), p(env.next_pheromone), st),
+            st = _lib.stream(self.device)
+            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(self.w1), _p(self.b1), _p(self.w2), _p(self.b2),
+                                                          _p(self.w3), _p(self.b3), _p(env.next_rotation), _p(env.next_pheromone), st),
                        "set_inloop_policy")
         env._loaded = "given an in-loop policy"
 
@@ -113,6 +108,13 @@ class LinearPolicy:
 #: antsrl_memnet_pack takes them in
 MEMNET_LAYERS = ("layer1", "layer2", "layer3", "layer4", "rotation_layer1", "rotation_layer2", "rotation_layer3",
                  "pheromone_layer1", "pheromone_layer2", "memory_layer1", "memory_layer2", "memory_layer3", "forget_layer")
+
+
+def memnet_param_ptrs(sd):
+    """The 26 device tensors of a CollectModelMemory state_dict as the ABI's `params` array."""
+    return (C.c_void_p * 26)(*[sd["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS for w in ("weight", "bias")])
+
+
 #: MemoryPolicy precisions -> include/antsrl.h ANTSRL_MEMNET_BF16 / ANTSRL_MEMNET_FP32
 MEMNET_PRECISIONS = {"bf16": 0, "fp32": 1}
 
@@ -181,16 +183,13 @@ class MemoryPolicy:
         if self.device.type != "cuda":  # weights only (no kernel can run on them)
             return
         self.packed = torch.empty((n.value,), dtype=torch.uint8, device=self.device)  # torch blocks are 512-byte aligned
-        ptrs = (C.c_void_p * 26)(*[self.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS for w in ("weight", "bias")])
+        ptrs = memnet_param_ptrs(self.params)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), self._precision_id(), ptrs,
-                                                       C.c_void_p(self.packed.data_ptr()), self._stream()), "memnet_pack_ex")
+                                                       _p(self.packed), _lib.stream(self.device)), "memnet_pack_ex")
 
     def _precision_id(self) -> int:
         return MEMNET_PRECISIONS[self.precision]
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def state_dict(self) -> dict:
         return dict(self.params)
@@ -249,12 +248,9 @@ class MemoryPolicy:
             self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
             self._ph = torch.empty((m,), dtype=torch.int8, device=self.device)
 
-        def p(t):
-            return None if t is None else C.c_void_p(t.data_ptr())
-
         fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_policy_memory_ex(C.byref(self.shape), self._precision_id(), p(self.packed), p(obs),
-                                                         fmt, p(agent_state), p(memory), m, p(dst), p(self._rot), p(self._ph),
-                                                         p(q), self._stream()), "policy_memory_ex")
+            _lib.check(self._lib.antsrl_policy_memory_ex(C.byref(self.shape), self._precision_id(), _p(self.packed), _p(obs),
+                                                         fmt, _p(agent_state), _p(memory), m, _p(dst), _p(self._rot), _p(self._ph),
+                                                         _p(q), _lib.stream(self.device)), "policy_memory_ex")
         return self._rot.view(lead), self._ph.view(lead), dst

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ptr as _p
 
 
 class DeviceReplayMemory:
@@ -122,7 +123,8 @@ class DeviceReplayMemory:
         with torch.cuda.device(self.states.device):
             _lib.check(_lib.load().antsrl_replay_record_pre(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(rotation),
                                                             _p(pheromone), _p(self.states), _p(self.agent_states),
-                                                            _p(self.actions), self._stream()), "replay_record_pre")
+                                                            _p(self.actions), _lib.stream(self.states.device)),
+                       "replay_record_pre")
         self._pending = spec
 
     def record_post(self, obs, agent_state, memory, reward, done) -> None:
@@ -146,7 +148,7 @@ class DeviceReplayMemory:
             _lib.check(_lib.load().antsrl_replay_record_post(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(reward),
                                                              _p(done), _p(self.rewards), _p(self.new_states),
                                                              _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
-                                                             self._stream()), "replay_record_post")
+                                                             _lib.stream(self.states.device)), "replay_record_post")
         self._pending = None
         n = int(spec.K)
         if n > self.max_len:  # as extend: only the newest max_len entries survived
@@ -162,10 +164,3 @@ class DeviceReplayMemory:
     def _check(self, t, dtype, numel):
         assert torch.is_tensor(t) and t.device == self.states.device and t.dtype == dtype and t.is_contiguous() and \
             t.numel() == numel, (tuple(t.shape), t.dtype, t.device, numel)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.states.device).cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())

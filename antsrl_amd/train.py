@@ -16,14 +16,11 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_shapes, memnet_shape_from_state_dict
+from ._lib import ptr as _p
+from .policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_ptrs, memnet_param_shapes, memnet_shape_from_state_dict
 
 #: the 9 layers the loss reaches (the first 18 tensors of the state_dict)
 TRAINED_LAYERS = MEMNET_LAYERS[:9]
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class MemoryTrainer:
@@ -79,17 +76,17 @@ class MemoryTrainer:
         self.load_state_dict(state_dict, _reset_adam=True)
 
     # ---- layout views -------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+    def _adam_offsets(self):
+        """Byte offsets of Adam's m and v in a state buffer (256-byte aligned blocks behind the parameters)."""
+        m_off = (self.params_floats * 4 + 255) // 256 * 256
+        return m_off, (m_off + self.trained_floats * 4 + 255) // 256 * 256
 
     def _views(self, buf, region="params"):
         f = buf.view(torch.float32)
         if region == "params":
             base, names = 0, list(self._offs)
         else:
-            pf = self.params_floats * 4
-            m_off = (pf + 255) // 256 * 256
-            v_off = (m_off + self.trained_floats * 4 + 255) // 256 * 256
+            m_off, v_off = self._adam_offsets()
             base = (m_off if region == "m" else v_off) // 4
             names = [k for k in self._offs if k.split(".")[0] in TRAINED_LAYERS]
         return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + _numel(self._offs[k][1])].view(self._offs[k][1])
@@ -109,21 +106,18 @@ class MemoryTrainer:
         for k, (_, shp) in self._offs.items():
             assert tuple(sd[k].shape) == shp, (k, tuple(sd[k].shape), shp)
         src = {k: torch.as_tensor(sd[k]).to(self.device, torch.float32).contiguous() for k in self._offs}
-        ptrs = (C.c_void_p * 26)(*[src[k].data_ptr() for k in self._offs])
+        ptrs = memnet_param_ptrs(src)
         keep = None if _reset_adam else self._model[self._adam_range()].clone()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(self._model), self._stream()),
-                       "memtrain_init")
-            _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(self._target), self._stream()),
-                       "memtrain_init")
+            for state in (self._model, self._target):
+                _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(state), _lib.stream(self.device)),
+                           "memtrain_init")
         if keep is not None:
             self._model[self._adam_range()] = keep
         self._repack_policy()
 
     def _adam_range(self):
-        pf = self.params_floats * 4
-        m_off = (pf + 255) // 256 * 256
-        v_off = (m_off + self.trained_floats * 4 + 255) // 256 * 256
+        m_off, v_off = self._adam_offsets()
         return slice(m_off, v_off + self.trained_floats * 4)
 
     def adam_state(self) -> dict:
@@ -141,17 +135,17 @@ class MemoryTrainer:
         tv = self._views(self._target)
         for k, dst in self.policy.params.items():
             dst.copy_(tv[k])
-        ptrs = (C.c_void_p * 26)(*[self.policy.params["%s.%s" % (l, w)].data_ptr() for l in MEMNET_LAYERS
-                                   for w in ("weight", "bias")])
+        ptrs = memnet_param_ptrs(self.policy.params)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), self.policy._precision_id(), ptrs,
-                                                       _p(self.policy.packed), self._stream()), "memnet_pack_ex")
+                                                       _p(self.policy.packed), _lib.stream(self.device)),
+                       "memnet_pack_ex")
 
     def sync_target(self) -> None:
         """target := model (:170-174), and the acting policy with it.  Adam's state is not copied."""
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memtrain_copy(C.byref(self.shape), _p(self._model), _p(self._target),
-                                                      self._stream()), "memtrain_copy")
+                                                      _lib.stream(self.device)), "memtrain_copy")
         self._repack_policy()
         self.syncs += 1
 
@@ -196,7 +190,7 @@ class MemoryTrainer:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memtrain_grad(C.byref(self.shape), _p(self._model), _p(self._target), _p(st), _p(ast),
                                                       _p(act), _p(rw), _p(nst), _p(nast), _p(dn), _p(idx), B, self.discount,
-                                                      _p(self.grads), _p(loss), _p(self._work), self._stream()),
+                                                      _p(self.grads), _p(loss), _p(self._work), _lib.stream(self.device)),
                        "memtrain_grad")
         return loss
 
@@ -207,7 +201,7 @@ class MemoryTrainer:
         self.step_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memtrain_apply(C.byref(self.shape), _p(self._model), _p(g), self.step_count, self.lr,
-                                                       self.betas[0], self.betas[1], self.eps, self._stream()),
+                                                       self.betas[0], self.betas[1], self.eps, _lib.stream(self.device)),
                        "memtrain_apply")
 
     def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
