@@ -19,7 +19,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory",
            "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
            "antsrl_memtrain_grad", "antsrl_memtrain_apply", "antsrl_memnet_packed_bytes_ex", "antsrl_memnet_pack_ex",
-           "antsrl_policy_memory_ex", "antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post")
+           "antsrl_policy_memory_ex", "antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post",
+           "antsrl_policy_memory_tiles", "antsrl_agent_plan")
 
 _lib = None
 
@@ -90,6 +91,8 @@ def load() -> C.CDLL:
     lib.antsrl_memnet_pack_ex.argtypes = [C.POINTER(AntsMemNetShape), i32, C.POINTER(vp), vp, vp]
     lib.antsrl_policy_memory_ex.argtypes = [C.POINTER(AntsMemNetShape), i32, vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp,
                                             vp, vp]
+    lib.antsrl_policy_memory_tiles.argtypes = [C.POINTER(AntsMemNetShape), i32, vp, vp, i32, vp, vp, C.c_int64, vp, vp, vp,
+                                               vp, vp, vp, vp]
     sz = C.POINTER(C.c_size_t)
     lib.antsrl_memtrain_sizes.argtypes = [C.POINTER(AntsMemNetShape), C.c_int64, sz, sz, sz, sz]
     lib.antsrl_memtrain_init.argtypes = [C.POINTER(AntsMemNetShape), C.POINTER(vp), vp, vp]
@@ -101,6 +104,7 @@ def load() -> C.CDLL:
                                           C.c_double, C.c_double, vp]
     lib.antsrl_agent_select.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, i32, i32, i32, vp, vp, vp, vp,
                                         vp, vp]
+    lib.antsrl_agent_plan.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.antsrl_replay_record_pre.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 9
     lib.antsrl_replay_record_post.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 10
     for name in EXPORTS:

@@ -19,7 +19,8 @@ does the same; `state_memory="carried"` stores the pre-action memory, which is w
 
 Beyond the reference: `record_per_step` (K: how many of a step's n_envs * n_ants transitions are recorded, a stratified
 sample; None = all of them, the reference's behaviour — at c3's 524 288 ants per step a ring of 50 000 rows would be
-overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed`, `precision` (the acting policy's).
+overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed`, `precision` (the acting policy's),
+`skip_explored` (off by default: skip the net for tiles whose ants all explore this step; results are unchanged).
 Exploration is drawn once per environment and step (an environment is one reference colony).
 """
 from __future__ import annotations
@@ -47,14 +48,15 @@ class MemoryAgent:
     def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
                  learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
-                 precision: str = "bf16", state_memory: str = "reference", mem_size: int = 20, power: int = 5):
+                 precision: str = "bf16", state_memory: str = "reference", mem_size: int = 20, power: int = 5,
+                 skip_explored: bool = False):
         assert state_memory in ("reference", "carried"), "state_memory must be 'reference' or 'carried', not %r" % (state_memory,)
         self.name = "collect_agent_memory"
         self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
         self.learning_rate = learning_rate
         self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
         self.update_target_every, self.seed, self.precision, self.state_memory = update_target_every, seed, precision, state_memory
-        self.mem_size, self.power = mem_size, power
+        self.mem_size, self.power, self.skip_explored = mem_size, power, skip_explored
         self.trainer = self.replay_memory = self.generator = None
         self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
         self._lib = _lib.load()
@@ -80,6 +82,9 @@ class MemoryAgent:
         self._mem = [torch.zeros((self.n_ants, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
         self._cur = 0  # self._mem[self._cur] is previous_memory (:111)
         self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
+        # skip_explored: antsrl_agent_plan's list of live tiles and its length
+        self._tiles = torch.zeros(((self.n_ants + 31) // 32,), dtype=torch.int32, device=self.device)
+        self._n_live = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(self.seed)
         self.step_counter = 0
@@ -108,12 +113,25 @@ class MemoryAgent:
     def get_action(self, obs, agent_state, training: bool, env=None):
         """:189-206 -> (rotation int8, pheromone int8, memory float32 [M, mem_size]), device tensors.  The target net acts
         on the whole batch; with `training`, antsrl_agent_select then replaces the actions of the environments that
-        explore this step (probability epsilon each) by uniform ones and gives their ants the old memory back."""
+        explore this step (probability epsilon each) by uniform ones and gives their ants the old memory back.  With
+        `skip_explored` (and `training`) antsrl_agent_plan first lists the 32-ant tiles that hold an ant of a
+        non-exploring environment and the net runs on those only (antsrl_policy_memory_tiles): the same results bit for
+        bit, without the forward passes select would throw away."""
         obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
         ast = self._dev(agent_state, torch.float32)
         old, new = self._mem[self._cur], self._mem[1 - self._cur]
-        rot, ph, _ = self.policy.act(obs.contiguous(), ast.contiguous(), memory=old, out=new, env=env)
         step = self.step_counter
+        tiles = None
+        if training and self.skip_explored:
+            # the net only on the tiles select leaves something of: select writes every ant of an exploring environment
+            # (actions and memory), the forward every ant of a listed tile, and a tile is unlisted only when all its
+            # ants explore, so every element of rot, ph and new is still written, with the bits of the full forward
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.antsrl_agent_plan(self.seed, step, self.env_id_base, self.n_envs, self.n_ants_per_env,
+                                                       float(self.epsilon), _p(self._tiles), _p(self._n_live),
+                                                       _lib.stream(self.device)), "agent_plan")
+            tiles = (self._tiles, self._n_live)
+        rot, ph, _ = self.policy.act(obs.contiguous(), ast.contiguous(), memory=old, out=new, env=env, tiles=tiles)
         if training:
             with torch.cuda.device(self.device):
                 _lib.check(self._lib.antsrl_agent_select(self.seed, step, self.env_id_base, self.n_envs, self.n_ants_per_env,

@@ -36,4 +36,6 @@ struct RecArgs {
 
 // vec: the memory copy moves float4 elements (env_elems / mem_elems count those); post: the half behind the environment step
 ANTSRL_INTERNAL hipError_t antsrl_launch_agent_select(const SelArgs &a, bool vec, hipStream_t st);
+// the plan reads seed, step, epsilon, env_base, n_ants and M of `a` (select's own arguments: one env_explores for both)
+ANTSRL_INTERNAL hipError_t antsrl_launch_agent_plan(const SelArgs &a, int32_t *tiles, int32_t *n_live, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_replay_record(const RecArgs &a, bool obs_bf16, bool post, hipStream_t st);

@@ -1,6 +1,6 @@
 // antsrl_memapi.hip — the memory agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h): the net's inference
 // (antsrl_memnet_*, antsrl_policy_memory*), its training step (antsrl_memtrain_*) and the loop around them
-// (antsrl_agent_select, antsrl_replay_record_*).
+// (antsrl_agent_select, antsrl_agent_plan, antsrl_replay_record_*).
 //
 // Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip, antsrl_memtrain.hip
 // and antsrl_memagent.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
@@ -102,17 +102,26 @@ static int memnet_pack(const AntsMemNetShape *s, int precision, const float *con
 
 static int policy_memory(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
                          const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out, int8_t *rotation,
-                         int8_t *pheromone, float *q_out, void *stream, const char *who)
+                         int8_t *pheromone, float *q_out, void *stream, const char *who, bool listed = false,
+                         const int32_t *tiles = nullptr, const int32_t *n_live = nullptr)
 {
     MemNetDims d;
     const int rc = memnet_check(s, &d, who);
     if (rc != ANTSRL_OK) return rc;
     if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
         return fail(ANTSRL_E_INVALID, "%s: packed, obs, agent_state, mem_in, mem_out, rotation are required", who);
+    if (listed && (!tiles || !n_live)) return fail(ANTSRL_E_INVALID, "%s: tiles and n_live are required", who);
+    if (listed && (((uintptr_t)tiles | (uintptr_t)n_live) & 3))
+        return fail(ANTSRL_E_INVALID, "%s: tiles and n_live must be 4-byte aligned", who);
     if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
     if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
         return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
     if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [1, 2^31)", who);
+    if (listed)
+        return enqueued((precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32_tiles : antsrl_launch_memnet_tiles)(
+                            (const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state, mem_in,
+                            (int)n_ants, mem_out, rotation, pheromone, q_out, tiles, n_live, (hipStream_t)stream),
+                        who);
     hipError_t e = (precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32 : antsrl_launch_memnet)(
         (const unsigned char *)packed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state, mem_in, (int)n_ants, mem_out,
         rotation, pheromone, q_out, (hipStream_t)stream);
@@ -158,6 +167,17 @@ extern "C" int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, 
     return rc != ANTSRL_OK ? rc
                            : policy_memory(s, precision, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out,
                                            rotation, pheromone, q_out, stream, "policy_memory_ex");
+}
+
+extern "C" int antsrl_policy_memory_tiles(const AntsMemNetShape *s, int precision, const void *packed, const void *obs,
+                                          int obs_format, const float *agent_state, const float *mem_in, int64_t n_ants,
+                                          float *mem_out, int8_t *rotation, int8_t *pheromone, float *q_out,
+                                          const int32_t *tiles, const int32_t *n_live, void *stream)
+{
+    const int rc = memnet_precision(precision, "policy_memory_tiles");
+    return rc != ANTSRL_OK ? rc
+                           : policy_memory(s, precision, packed, obs, obs_format, agent_state, mem_in, n_ants, mem_out,
+                                           rotation, pheromone, q_out, stream, "policy_memory_tiles", true, tiles, n_live);
 }
 
 // ---- the training step (antsrl_memtrain.hip)
@@ -329,6 +349,12 @@ static int check_width(const char *who, const char *name, int32_t v)
 
 #define MISALIGNED(p, n) (((uintptr_t)(p) & ((n) - 1)) != 0)
 
+#define REQUIRE(p, align)                                                                                    \
+    do {                                                                                                     \
+        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                              \
+        if (MISALIGNED(p, align)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
+    } while (0)
+
 extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
                                    double epsilon, int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation,
                                    int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored, void *stream)
@@ -362,6 +388,22 @@ extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_
     a.env_elems = (uint32_t)env_elems;
     a.mem_elems = env_elems * (uint64_t)n_envs;
     return enqueued(antsrl_launch_agent_select(a, vec, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
+                                 double epsilon, int32_t *tiles, int32_t *n_live, void *stream)
+{
+    const char *who = "agent_plan";
+    const int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    if (rc != ANTSRL_OK) return rc;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
+    REQUIRE(tiles, 4);
+    REQUIRE(n_live, 4);
+    SelArgs a = {};
+    a.seed = seed; a.step = step; a.epsilon = epsilon;
+    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants;
+    a.M = (uint32_t)((long long)n_envs * n_ants);
+    return enqueued(antsrl_launch_agent_plan(a, tiles, n_live, (hipStream_t)stream), who);
 }
 
 static int check_spec(const char *who, const AntsRecordSpec *r)
@@ -404,12 +446,6 @@ static int launch_rec(const char *who, const AntsRecordSpec *r, const RecArgs &a
 {
     return enqueued(antsrl_launch_replay_record(a, r->obs_format == ANTSRL_OBS_BF16, post, (hipStream_t)stream), who);
 }
-
-#define REQUIRE(p, align)                                                                                    \
-    do {                                                                                                     \
-        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                              \
-        if (MISALIGNED(p, align)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
-    } while (0)
 
 extern "C" int antsrl_replay_record_pre(const AntsRecordSpec *r, const void *obs, const float *agent_state,
                                         const float *memory, const int8_t *rotation, const int8_t *pheromone, float *states,

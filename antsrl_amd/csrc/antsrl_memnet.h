@@ -46,3 +46,12 @@ hipError_t antsrl_launch_memnet_pack_f32(unsigned char *pack, const MemNetParams
 hipError_t antsrl_launch_memnet_f32(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
                                     const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
                                     int8_t *ph, float *q_out, hipStream_t st);
+// the same forwards over a device-resident list of 32-ant tiles (tiles[0 .. *n_live), see antsrl_policy_memory_tiles):
+// listed tiles get what the launchers above write for their ants, bit for bit; the other ants are not written
+hipError_t antsrl_launch_memnet_tiles(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
+                                      const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
+                                      int8_t *ph, float *q_out, const int32_t *tiles, const int32_t *n_live, hipStream_t st);
+hipError_t antsrl_launch_memnet_f32_tiles(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
+                                          const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
+                                          int8_t *ph, float *q_out, const int32_t *tiles, const int32_t *n_live,
+                                          hipStream_t st);

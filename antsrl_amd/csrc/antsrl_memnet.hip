@@ -205,18 +205,24 @@ __device__ __forceinline__ void mn_layer_lds(const unsigned char *__restrict__ p
 #define MN_WCAP 4096 // shared weight buffer, 16-byte units (64 KiB; at least one output tile of any layer)
 #endif
 
-template <bool OBS16>
+// List = nothing: the forward over the whole batch, wave w of the grid on ants 32 w .. 32 w + 31 (antsrl_policy_memory).
+// List = (const int32_t *tiles, const int32_t *n_live): the tile-list forward (antsrl_policy_memory_tiles), wave w on tile
+// tiles[w] (mn_list_tile).  Everything behind t0 is the same code, so a listed tile's results are the full forward's bits.
+template <bool OBS16, typename... List>
 __global__ void __launch_bounds__(64 * MN_WAVES) // one workgroup per CU at D <= 320 (LDS): one wave per SIMD, 512 registers
-k_memnet(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNetLayout L, int wcap)
+k_memnet(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNetLayout L, int wcap, List... list)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wib = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int Dp = L.Dp, stride = Dp + 8; // 16-byte aligned rows, 4-bank skew per row
     __bf16 *xt = reinterpret_cast<__bf16 *>(smem) + (size_t)wib * 32 * stride;        // this wave's [32][Dp + 8]: x, then g
     bf16x8 *wbuf = reinterpret_cast<bf16x8 *>(smem + (size_t)nw * 32 * stride * 2);   // shared weight chunk, wcap units
-    const int t0 = (blockIdx.x * nw + wib) * 32;
+    int t0 = (blockIdx.x * nw + wib) * 32;
+    bool on = true; // false: a spare wave of a partly filled tile-list workgroup walks the barriers and writes nothing
+    if constexpr (sizeof...(List) != 0)
+        if (!mn_list_tile(io.M, &t0, &on, list...)) return; // the whole workgroup, before any barrier
     const size_t ant = (size_t)min(t0 + r, io.M - 1); // clamped: duplicates are not written back
-    const bool live = t0 + r < io.M;
+    const bool live = on && t0 + r < io.M;
 
     // ---- stage x (bf16) in the wave's LDS tile: 32-column chunks, lanes 0-31 on ant 2p and lanes 32-63 on ant 2p + 1
     // (128 coalesced bytes of a float32 row per half-wave), the 16 ant pairs' loads in flight together
@@ -358,4 +364,16 @@ hipError_t antsrl_launch_memnet(const unsigned char *pack, const MemNetDims &d, 
     const int wcap = L.Dp / 16 * 64 > MN_WCAP ? L.Dp / 16 * 64 : MN_WCAP;
     return mn_launch<k_memnet<true>, k_memnet<false>>(pack, io, d, L, obs_bf16, MN_WAVES, (size_t)32 * (L.Dp + 8) * 2,
                                                       (size_t)wcap * 16, st, wcap);
+}
+
+hipError_t antsrl_launch_memnet_tiles(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
+                                      const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
+                                      int8_t *ph, float *q_out, const int32_t *tiles, const int32_t *n_live, hipStream_t st)
+{
+    MemNetLayout L;
+    antsrl_memnet_layout(d, &L);
+    const MemNetIO io{obs, agent_state, mem_in, mem_out, q_out, rot, ph, M};
+    const int wcap = L.Dp / 16 * 64 > MN_WCAP ? L.Dp / 16 * 64 : MN_WCAP; // as antsrl_launch_memnet
+    return mn_launch<k_memnet<true, const int32_t *, const int32_t *>, k_memnet<false, const int32_t *, const int32_t *>>(
+        pack, io, d, L, obs_bf16, MN_WAVES, (size_t)32 * (L.Dp + 8) * 2, (size_t)wcap * 16, st, wcap, tiles, n_live);
 }

@@ -1,7 +1,7 @@
 // antsrl_memnet_dev.h — what the memory agent net's two forward kernels share: k_memnet (bf16 operands, antsrl_memnet.hip)
 // and k_memnet_f32 (fp32 operands, antsrl_memnet_f32.hip).  The packed layout, the source rows of a packed layer, the
 // forward's pointers, the fp32 input x, biases, the heads' argmax in the 32x32 accumulator layout, the wave-local LDS
-// hand-off and the launcher.  The steps inside the kernels (the pack frame, staging x, L4's residual, the epilogues) stay
+// hand-off, the tile-list lookup (mn_list_tile) and the launcher.  The steps inside the kernels (the pack frame, staging x, L4's residual, the epilogues) stay
 // written out in each .hip file: moved into a shared helper, each of them changes the compiler's schedule of both kernels
 // (sgpr spills 55 -> 70 in k_memnet<false>, 1.7 % on the power-4 forward), and the kernels are to stay as they are.
 #pragma once
@@ -116,6 +116,27 @@ __device__ __forceinline__ void mn_tile_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The tile-list kernels' place in the batch.  The grid covers all T = ceil(M / 32) tiles, because the host does not know
+// *n_live; wave `slot` = blockIdx.x * waves + wave-in-block takes tile tiles[slot].  false: the workgroup's first slot is
+// at or beyond n_live (clamped to [0, T]) — uniform over the workgroup, so all of it leaves before any barrier.  Else
+// *on says whether this wave has a tile: its slot is below n_live and the entry lies in [0, T).  The entry is compared in
+// a scalar register (wave-uniform) before it is ever multiplied into an address; a wave without a tile runs on tile 0's
+// inputs (valid addresses, M >= 1) and writes nothing.
+__device__ __forceinline__ bool mn_list_tile(int M, int *t0, bool *on, const int32_t *__restrict__ tiles,
+                                             const int32_t *__restrict__ n_live)
+{
+    const int wib = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int T = (M >> 5) + ((M & 31) != 0);
+    const int n = min(max(*n_live, 0), T);
+    const int first = blockIdx.x * nw; // < T: the grid has ceil(T / nw) workgroups
+    if (first >= n) return false;
+    const int slot = first + wib;      // < n <= T inside the branch: within the list's capacity
+    const int t = __builtin_amdgcn_readfirstlane(slot < n ? tiles[slot] : -1);
+    *on = t >= 0 && t < T;
+    *t0 = *on ? t * 32 : 0;
+    return true;
 }
 
 // host: the launcher.  K16 / K32 = the forward kernel for bfloat16 / float32 observations; LDS = one `tile` per wave

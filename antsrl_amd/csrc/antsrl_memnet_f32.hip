@@ -179,17 +179,22 @@ __device__ __forceinline__ f32x16 m32_head(const unsigned char *__restrict__ pk,
     return q;
 }
 
-template <bool OBS16>
+// List = nothing: the whole batch; List = (const int32_t *tiles, const int32_t *n_live): the tile-list forward, as in
+// k_memnet (antsrl_memnet.hip).
+template <bool OBS16, typename... List>
 __global__ void __launch_bounds__(64 * M32_WAVES) // one wave per SIMD at D <= 320 (LDS): up to 512 registers
-k_memnet_f32(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNetLayout L)
+k_memnet_f32(const unsigned char *__restrict__ pk, MemNetIO io, MemNetDims d, MemNetLayout L, List... list)
 {
     extern __shared__ __align__(16) float smem32[];
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wib = threadIdx.x >> 6, nw = blockDim.x >> 6;
     const int Dp = L.Dp;
     float *xt = smem32 + (size_t)wib * 32 * Dp; // this wave's [32][Dp] (swizzled): x, then g
-    const int t0 = (blockIdx.x * nw + wib) * 32;
+    int t0 = (blockIdx.x * nw + wib) * 32;
+    bool on = true; // false: a spare wave of a partly filled tile-list workgroup, which writes nothing
+    if constexpr (sizeof...(List) != 0)
+        if (!mn_list_tile(io.M, &t0, &on, list...)) return;
     const size_t ant = (size_t)min(t0 + r, io.M - 1); // clamped: duplicates are not written back
-    const bool live = t0 + r < io.M;
+    const bool live = on && t0 + r < io.M;
 
     // ---- stage x (fp32) in the wave's LDS tile, as k_memnet does: lanes 0-31 on ant 2p, lanes 32-63 on ant 2p + 1
     for (int c = 0; c < Dp / 32; ++c) {
@@ -314,4 +319,16 @@ hipError_t antsrl_launch_memnet_f32(const unsigned char *pack, const MemNetDims 
     const MemNetIO io{obs, agent_state, mem_in, mem_out, q_out, rot, ph, M};
     // LDS: one fp32 [32][Dp] tile per wave and nothing shared (D <= 320: 4 waves; D = 1024: 1)
     return mn_launch<k_memnet_f32<true>, k_memnet_f32<false>>(pack, io, d, L, obs_bf16, M32_WAVES, (size_t)32 * L.Dp * 4, 0, st);
+}
+
+hipError_t antsrl_launch_memnet_f32_tiles(const unsigned char *pack, const MemNetDims &d, const void *obs, bool obs_bf16,
+                                          const float *agent_state, const float *mem_in, int M, float *mem_out, int8_t *rot,
+                                          int8_t *ph, float *q_out, const int32_t *tiles, const int32_t *n_live,
+                                          hipStream_t st)
+{
+    MemNetLayout L;
+    antsrl_memnet_layout_f32(d, &L);
+    const MemNetIO io{obs, agent_state, mem_in, mem_out, q_out, rot, ph, M};
+    return mn_launch<k_memnet_f32<true, const int32_t *, const int32_t *>, k_memnet_f32<false, const int32_t *, const int32_t *>>(
+        pack, io, d, L, obs_bf16, M32_WAVES, (size_t)32 * L.Dp * 4, 0, st, tiles, n_live);
 }

@@ -212,7 +212,7 @@ class MemoryPolicy:
         self.memory = None if m is None else torch.zeros((m, self.mem_size), dtype=torch.float32, device=self.device)
 
     def act(self, obs: torch.Tensor, agent_state: torch.Tensor, memory: Optional[torch.Tensor] = None,
-            out: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, env=None):
+            out: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, env=None, tiles=None):
         """CollectAgentMemory.get_action's network branch (:191-200): obs [..., P, P, K] float32 (or bfloat16 from a
         BatchedAntsEnv(obs_dtype=torch.bfloat16)), agent_state float32 [..., 2] on the device ->
         (rotation int8 [...], pheromone int8 [...], new_memory float32 [M, mem_size]).
@@ -223,7 +223,12 @@ class MemoryPolicy:
         update_replay_memory stores (:182) is NOT the old memory: get_action has overwritten self.previous_memory with
         the new one by then (:194), so agent_states and new_agent_states hold the same, post-action memory
         (antsrl_amd/agent.py).
-        `q` (float32 [M, n_rot + n_ph]) receives both heads' outputs."""
+        `q` (float32 [M, n_rot + n_ph]) receives both heads' outputs.
+
+        `tiles` = (tiles int32 [ceil(M / 32)], n_live int32 [1]), device tensors (e.g. from antsrl_agent_plan): the net is
+        evaluated by `antsrl_policy_memory_tiles` on the listed 32-ant tiles only, bit for bit as without the list; the
+        other ants' rotation, pheromone, memory and q are NOT written (the returned action tensors are reused buffers:
+        the caller owns every element it did not list).  In place, the listed tiles must be distinct."""
         assert self.packed is not None, "MemoryPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
         lead = obs.shape[:-3]
         m = 1
@@ -250,6 +255,16 @@ class MemoryPolicy:
 
         fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
         with torch.cuda.device(self.device):
+            if tiles is not None:
+                lst, n_live = tiles
+                for t, n in ((lst, (m + 31) // 32), (n_live, 1)):
+                    assert t.dtype == torch.int32 and t.device == obs.device and t.is_contiguous() and t.numel() >= n, \
+                        "tiles = (int32 [ceil(M / 32)], int32 [1]) on the observation's device"
+                _lib.check(self._lib.antsrl_policy_memory_tiles(C.byref(self.shape), self._precision_id(), _p(self.packed),
+                                                                _p(obs), fmt, _p(agent_state), _p(memory), m, _p(dst),
+                                                                _p(self._rot), _p(self._ph), _p(q), _p(lst), _p(n_live),
+                                                                _lib.stream(self.device)), "policy_memory_tiles")
+                return self._rot.view(lead), self._ph.view(lead), dst
             _lib.check(self._lib.antsrl_policy_memory_ex(C.byref(self.shape), self._precision_id(), _p(self.packed), _p(obs),
                                                          fmt, _p(agent_state), _p(memory), m, _p(dst), _p(self._rot), _p(self._ph),
                                                          _p(q), _lib.stream(self.device)), "policy_memory_ex")

@@ -520,6 +520,24 @@ int antsrl_policy_memory_ex(const AntsMemNetShape *s, int precision, const void 
                             const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
                             int8_t *rotation, int8_t *pheromone, float *q_out, void *stream);
 
+/* antsrl_policy_memory_ex over a device-resident list of 32-ant tiles: the forward of part of a batch, decided on the
+ * device (antsrl_agent_plan writes such a list; any other source will do).  With M = n_ants and T = ceil(M / 32), tile t
+ * is ants [32 t, min(32 t + 32, M)).  tiles: int32 [T] on the device, of which entries [0, n) are read,
+ * n = min(max(*n_live, 0), T); n_live: int32 [1] on the device; both required, 4-byte aligned.
+ *   - Every ant of a listed tile gets in mem_out, rotation, pheromone and q_out exactly the bits antsrl_policy_memory_ex
+ *     writes for it (an ant's outputs depend only on its own inputs, in both precisions).
+ *   - Ants of tiles that are not listed are not written at all: their rows keep whatever the buffers held.
+ *   - An entry outside [0, T) is skipped: it is compared before it is used and never becomes an address.
+ *   - Entries need not be sorted.  They must be DISTINCT when mem_in == mem_out: a tile listed twice in place may read
+ *     its own new memory as the old one.  (Out of place a duplicate writes the same bits twice.)
+ * The host does not know n, so the launch covers T tiles: a workgroup whose first slot is at or beyond n leaves at once,
+ * the spare waves of the last, partly filled workgroup walk its barriers and write nothing.  Every other argument, rule
+ * and error code as antsrl_policy_memory_ex.  One launch, no host synchronisation. */
+int antsrl_policy_memory_tiles(const AntsMemNetShape *s, int precision, const void *packed, const void *obs, int obs_format,
+                               const float *agent_state, const float *mem_in, int64_t n_ants, float *mem_out,
+                               int8_t *rotation, int8_t *pheromone, float *q_out, const int32_t *tiles,
+                               const int32_t *n_live, void *stream);
+
 /* On-device DQN training step of the memory agent net (replaces CollectAgentMemory.train, agents/collect_agent_memory.py:
  * 133-176: target forward, TD targets, MSE loss, backward, torch.optim.Adam).  Same shape and limits as
  * antsrl_policy_memory; observations are float32 (what the replay stores).  Two stages, so that a data-parallel caller
@@ -578,7 +596,7 @@ int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *gr
 
 /* The memory agent's loop around the net and the training step (antsrl_memagent.hip; replaces the epsilon branch of
  * CollectAgentMemory.get_action, agents/collect_agent_memory.py:189-206, and update_replay_memory + ReplayMemory.extend,
- * :178-187 and agents/replay_memory.py:83-114).  Three entries on plain device pointers: every argument is validated
+ * :178-187 and agents/replay_memory.py:83-114).  Four entries on plain device pointers: every argument is validated
  * before any HIP call, nothing synchronises the host, and there are no atomics: results do not depend on scheduling.
  *
  * THE DRAW SPECIFICATION.  All randomness of these entries is counter-based, built from the mixer of the wall-jitter
@@ -620,6 +638,21 @@ int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, const float *gr
 int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants, double epsilon,
                         int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation, int8_t *pheromone,
                         const float *mem_old, float *mem_next, uint8_t *explored, void *stream);
+
+/* Which 32-ant tiles of the batch antsrl_agent_select will NOT overwrite entirely: the list antsrl_policy_memory_tiles
+ * needs in front of it, so that the net is not evaluated for ants whose result select throws away.  With
+ * M = n_envs * n_ants ants in the batch's flat order (ant i belongs to environment i / n_ants) and T = ceil(M / 32), tile t
+ * is ants [32 t, min(32 t + 32, M)).  Tile t is LIVE iff at least one of its ants belongs to an environment that does not
+ * explore at (seed, step) — "explores" exactly as in antsrl_agent_select: u01(draw(seed, ANTSRL_DRAW_EXPLORE,
+ * env_id_base + e, step, 0)) < epsilon, the same double comparison.  So a tile that straddles an exploring and a
+ * non-exploring environment (n_ants not a multiple of 32) is live, epsilon 0 lists all T tiles and epsilon 1 none.
+ *   *n_live = the number of live tiles; tiles[0 .. *n_live) = their indices in ascending order;
+ *   tiles[*n_live .. T) are unspecified (they are not written).
+ * tiles: int32 [T], n_live: int32 [1], both on the device, required, 4-byte aligned.  n_envs, n_ants, env_id_base and
+ * epsilon: the rules of antsrl_agent_select.  One launch of one workgroup (a prefix sum over the tiles' flags, no
+ * atomics: the list does not depend on scheduling); no host synchronisation. */
+int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants, double epsilon,
+                      int32_t *tiles, int32_t *n_live, void *stream);
 
 /* One step's transitions into the seven rolling arrays of a replay memory (states float [max_len][n_features],
  * agent_states float [max_len][agent_dim + mem_size], actions int64 [max_len][2], rewards float [max_len], new_states,

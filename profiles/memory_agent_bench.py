@@ -10,9 +10,17 @@ power 5, mem 20, on the device:
   select     antsrl_agent_select (epsilon 0.1 and 1.0) next to the memory forward it follows.
   rollout    one whole MemoryAgent.rollout_step at K = 4096, minibatch 264, and its parts timed one by one.
 
+  --epsilon  the skip_explored sweep instead of the above (epsilon 0, 0.1, 0.5, 0.9, 1 unless values are given): per
+             epsilon and precision the full forward twice (an A/A pair: its spread is what a difference must exceed), the
+             tile-list forward driven by antsrl_agent_plan's list, the plan alone, and rollout_step with the switch off
+             and on (one agent, the switch flipped between alternating iterations).  The yardstick is the full forward
+             and the rollout_step without the switch at the same epsilon.  Default --json:
+             profiles/memory_agent_skip_c3.json.
+
 hipEvents around `--iters` warmed iterations.  Prints one line per case and a JSON summary (--json).
 
     python profiles/memory_agent_bench.py [--iters 200] [--json out.json]
+    python profiles/memory_agent_bench.py --epsilon [--iters 100]
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/memory_agent_bench.py --probe 40   # launches per step
 """
 import argparse
@@ -113,14 +121,60 @@ def c3_env():
     return env
 
 
+def bench_skip(env, ag, epsilons, iters):
+    """The skip_explored sweep (module docstring)."""
+    from antsrl_amd.policy import MemoryPolicy
+    obs, ast = env.obs, env.agent_state
+    old, new = ag._mem
+    lib, st = _lib.load(), C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    T = (M + 31) // 32
+    tiles, n_live = torch.zeros((T,), dtype=torch.int32, device="cuda"), torch.zeros((1,), dtype=torch.int32, device="cuda")
+    pols = dict(bf16=ag.policy, fp32=MemoryPolicy(F, "cuda", power=ag.power, mem_size=MEM, seed=1, precision="fp32"))
+    for _ in range(20):  # fill the ring past min_replay: every timed step trains
+        ag.rollout_step(env)
+    rows = []
+    for eps in epsilons:
+        plan = lambda: _lib.check(lib.antsrl_agent_plan(1, 0, 0, E, N, eps, p(tiles), p(n_live), st))  # noqa: E731
+        plan()
+        live = int(n_live.item())
+        row = dict(epsilon=eps, tiles=T, live_tiles=live, live_fraction=live / T)
+        for name, pol in pols.items():
+            full = lambda: pol.act(obs, ast, memory=old, out=new)  # noqa: E731
+            listed = lambda: pol.act(obs, ast, memory=old, out=new, tiles=(tiles, n_live))  # noqa: E731
+            t_a, t_b, t_tiles, t_plan = timed([full, full, listed, plan], iters)
+            t_full = 0.5 * (t_a + t_b)
+            row[name] = dict(full_forward_ms=[t_a, t_b], aa_spread_ms=abs(t_a - t_b), tile_forward_ms=t_tiles, plan_ms=t_plan,
+                             fraction_times_full_plus_plan_ms=row["live_fraction"] * t_full + t_plan,
+                             plan_plus_tile_forward_ms=t_plan + t_tiles)
+            print("eps %.1f %s: full forward %.4f / %.4f ms (A/A) | tile-list forward %.4f ms + plan %.4f ms | live %d / %d = "
+                  "%.3f -> fraction x full + plan %.4f ms" % (eps, name, t_a, t_b, t_tiles, t_plan, live, T, row["live_fraction"],
+                                                              row[name]["fraction_times_full_plus_plan_ms"]), flush=True)
+        ag.epsilon = eps
+
+        def step(skip):
+            ag.skip_explored = skip
+            ag.rollout_step(env)
+
+        t_off, t_off2, t_on = timed([lambda: step(False), lambda: step(False), lambda: step(True)], iters)
+        row["rollout_step_ms"] = dict(off=[t_off, t_off2], on=t_on)
+        print("eps %.1f rollout_step: off %.4f / %.4f ms (A/A) | on %.4f ms" % (eps, t_off, t_off2, t_on), flush=True)
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--epsilon", type=float, nargs="*", default=None,
+                    help="the skip_explored sweep over these epsilons (none given: 0 0.1 0.5 0.9 1)")
+    ap.add_argument("--skip-explored", action="store_true", help="with --probe: the agent runs with skip_explored=True")
     ap.add_argument("--probe", type=int, default=0, help="run this many rollout_steps at K = 4096 and exit (for rocprofv3)")
     a = ap.parse_args()
     env = c3_env()
-    ag = MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1)
+    ag = MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1,
+                     skip_explored=a.skip_explored)
     ag.setup(env)
     ag.initialize(env)
     env.observe()
@@ -130,6 +184,12 @@ def main():
         print("probe: %d rollout steps, %d training steps" % (a.probe, ag.trainer.step_count))
         return
     out = dict(device=torch.cuda.get_device_name(0), iters=a.iters, batch=[E, N], n_features=F)
+    if a.epsilon is not None:
+        out["skip_explored"] = bench_skip(env, ag, a.epsilon or [0.0, 0.1, 0.5, 0.9, 1.0], a.iters)
+        print(json.dumps(out))
+        with open(a.json or os.path.join(ROOT, "profiles", "memory_agent_skip_c3.json"), "w") as f:
+            json.dump(out, f, indent=1)
+        return
     out["record"] = [bench_record(M, M, max(20, a.iters // 4)), bench_record(4096, 50000, a.iters)]
     for r in out["record"]:
         print("record K = %6d: pre + post %.4f ms | clone + extend %.4f ms (%.1fx) | %.0f MB at %.0f GB/s = %.2f of the "
