@@ -3,4 +3,14 @@ reference's RLApi surface).  See DESIGN.md."""
 from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
-__all__ = ["config", "AntsCfg", "make_cfg"]
+__all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer"]
+
+
+def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
+    if name == "CollectAgent":
+        from .agent import CollectAgent
+        return CollectAgent
+    if name == "LinearTrainer":
+        from .train import LinearTrainer
+        return LinearTrainer
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -20,7 +20,9 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
            "antsrl_memtrain_grad", "antsrl_memtrain_apply", "antsrl_memnet_packed_bytes_ex", "antsrl_memnet_pack_ex",
            "antsrl_policy_memory_ex", "antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post",
-           "antsrl_policy_memory_tiles", "antsrl_agent_plan")
+           "antsrl_policy_memory_tiles", "antsrl_agent_plan", "antsrl_agent_select_actions",
+           "antsrl_replay_record_pre_plain", "antsrl_replay_record_post_plain", "antsrl_lintrain_sizes",
+           "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step")
 
 _lib = None
 
@@ -107,6 +109,14 @@ def load() -> C.CDLL:
     lib.antsrl_agent_plan.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, vp, vp, vp]
     lib.antsrl_replay_record_pre.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 9
     lib.antsrl_replay_record_post.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 10
+    lib.antsrl_agent_select_actions.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp]
+    lib.antsrl_replay_record_pre_plain.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 8
+    lib.antsrl_replay_record_post_plain.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 9
+    lib.antsrl_lintrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
+    lib.antsrl_lintrain_grad.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
+    lib.antsrl_lintrain_apply.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    lib.antsrl_lintrain_step.argtypes = [i32] + [vp] * 13 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
+                                                             C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -34,7 +34,7 @@ from . import _lib
 from ._lib import ptr as _p
 from . import config as cm
 from .replay import DeviceReplayMemory
-from .train import MemoryTrainer
+from .train import LinearTrainer, MemoryTrainer
 
 
 def _backend(api_or_env):
@@ -199,6 +199,197 @@ class MemoryAgent:
         done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
         env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
         rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step) if training else 0
+
+    def run(self, env, steps: int, training: bool = True) -> list:
+        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
+        return [self.rollout_step(env, training) for _ in range(steps)]
+
+
+class CollectAgent:
+    """The linear agent on the device: CollectAgent (agents/collect_agent.py:54-184) with its net (the one config 5
+    runs: LinearPolicy), its replay memory, its epsilon-greedy step and its training step resident on the GPU.
+
+    The reference class's surface (setup, initialize, get_action, update_replay_memory, train, save_model, load_model, a
+    settable epsilon) and MemoryAgent's fused loop,
+
+        rollout_step(env) = act -> select -> record_pre -> env.step_update -> record_post -> train
+
+    with no host synchronisation.  The pieces: `LinearTrainer` (layer2 and layer3 trained, layer1 frozen and shared with
+    the target net, whose only own tensor is layer3; its `policy` is the acting net), `DeviceReplayMemory` with 2-float
+    agent_states rows, and the memory-less entries antsrl_agent_select_actions / antsrl_replay_record_*_plain (the
+    memory agent's kernels, draw specification and stream tags).
+
+    `inloop=True` takes the actions from the observation kernel (LinearPolicy.attach: bfloat16 observations on the
+    cell-meta path) whenever the weights in the handle are the acting weights the observation was produced under, and
+    from the standalone kernel otherwise — the two kernels give the same actions bit for bit, so both settings give the
+    same actions, rings, weights and losses.  A training step changes layer2, so while the agent trains at every step
+    the in-loop actions of the step before are one update old and are not used: in-loop acting pays off for the steps
+    that do not train (below min_replay, training=False).  The handle's weights are refreshed
+    (antsrl_set_inloop_policy) lazily: at the first step that will not train after the acting weights changed."""
+
+    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
+                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
+                 inloop: bool = False):
+        assert rotations == 3 and pheromones == 3, "the linear net's heads are 3 wide (antsrl_policy_mlp)"
+        self.name = "collect_agent"
+        self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
+        self.learning_rate = learning_rate
+        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
+        self.update_target_every, self.seed, self.inloop = update_target_every, seed, inloop
+        self.trainer = self.replay_memory = self.generator = None
+        self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
+        self.inloop_hits = 0   # steps whose actions came from the observation kernel
+        self._lib = _lib.load()
+
+    # ---- the reference's surface ----------------------------------------------------------------------------------
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """CollectAgent.setup (:75-98) for every ant of the batch."""
+        env = _backend(api_or_env)
+        cfg = env.cfg
+        self.device = env.device
+        self.n_envs, self.n_ants_per_env, self.env_id_base = cfg.n_envs, cfg.n_ants, cfg.env_id_base
+        self.n_ants = cfg.n_envs * cfg.n_ants
+        self.observation_space = tuple(env.obs.shape[-3:])
+        self.agent_space, self.action_space = [2], [2]
+        self.n_features = int(np.prod(self.observation_space))
+        self.trainer = LinearTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+                                     update_target_every=self.update_target_every, seed=self.seed)
+        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_space,
+                                                self.action_space, device=self.device)
+        self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
+        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(self.seed)
+        self.step_counter = 0
+        self._action_step = 0
+        self._env = None            # the environment the in-loop policy is attached to
+        self._handle_version = -1   # trainer.version of the weights in its handle
+        self._next_version = -1     # ... of the weights its next_rotation / next_pheromone were produced under
+        if trained_model is not None:
+            self.load_model(trained_model)
+        if self.inloop:
+            self._attach(env)
+
+    def initialize(self, api_or_env) -> None:
+        """:100-102: every pheromone activation x 10."""
+        env = _backend(api_or_env)
+        c = env.cfg
+        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
+
+    @property
+    def policy(self):
+        return self.trainer.policy
+
+    def _dev(self, a, dtype):
+        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+        return t.to(device=self.device, dtype=dtype) if (t.device != self.device or t.dtype != dtype) else t
+
+    # ---- the in-loop policy's weights -----------------------------------------------------------------------------
+    def _attach(self, env) -> None:
+        self.policy.attach(env)  # allocates env.next_rotation / next_pheromone, copies the weights into the handle
+        self._env, self._handle_version, self._next_version = env, self.trainer.version, -1
+
+    def refresh_inloop(self) -> None:
+        """The acting weights into the handle again (antsrl_set_inloop_policy: a 38 KB device copy and the pack)."""
+        env, p = self._env, self.policy
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(p.w1), _p(p.b1), _p(p.w2), _p(p.b2),
+                                                          _p(p.w3), _p(p.b3), _p(env.next_rotation), _p(env.next_pheromone),
+                                                          _lib.stream(self.device)), "set_inloop_policy")
+        self._handle_version = self.trainer.version
+
+    def get_action(self, obs, agent_state, training: bool, env=None):
+        """:161-177 -> (rotation int8, pheromone int8), device tensors.  The target net (the shared layer1, the live
+        layer2, the target layer3) acts on the whole batch; with `training`, antsrl_agent_select_actions then replaces the
+        actions of the environments that explore this step (probability epsilon each, one draw per environment) by
+        uniform ones."""
+        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
+        ast = self._dev(agent_state, torch.float32)
+        step = self.step_counter
+        lead = obs.shape[:-3]
+        attached = self.inloop and env is not None and env is self._env and obs is env.obs
+        if attached and self._next_version == self.trainer.version:
+            self._rot.copy_(env.next_rotation.view(-1))  # what the observation kernel left for this observation
+            self._ph.copy_(env.next_pheromone.view(-1))
+            self.inloop_hits += 1
+        else:
+            # the handle gets the acting weights again only when the observation this step produces can use them: a
+            # step that trains moves layer2 behind that observation, and its in-loop actions are never taken
+            if attached and self._handle_version != self.trainer.version and not self._will_train(training):
+                self.refresh_inloop()
+            rot, ph = self.policy.act(obs.contiguous(), ast.contiguous(), env=env)
+            self._rot.copy_(rot.reshape(-1))
+            self._ph.copy_(ph.reshape(-1))
+        if training:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
+                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
+                                                                 self.pheromones, _p(self._rot), _p(self._ph),
+                                                                 _p(self._explored), _lib.stream(self.device)),
+                           "agent_select_actions")
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), self._ph.view(lead)
+
+    def _will_train(self, training: bool) -> bool:
+        """Whether train() at the end of the step that starts now will take a training step (it runs behind this step's
+        record: the rows of this step count)."""
+        k = self.n_ants if self.record_per_step is None else self.record_per_step
+        return bool(training) and min(self.replay_size, len(self.replay_memory) + k) >= self.min_replay
+
+    def _record_kw(self):
+        return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
+                    step=self._action_step, env_id_base=self.env_id_base, n_rot=self.rotations)
+
+    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
+        """:150-159, from arrays the caller kept (`states`: the observation as it was BEFORE the step).  actions = what
+        get_action returned; rotation + rotations // 2 is what is stored."""
+        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
+        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
+        rm = self.replay_memory
+        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), None,
+                      self._dev(actions[0], torch.int8).contiguous().view(-1),
+                      None if actions[1] is None else self._dev(actions[1], torch.int8).contiguous().view(-1),
+                      **self._record_kw())
+        if torch.is_tensor(done) or isinstance(done, np.ndarray):
+            done = self._dev(done, torch.uint8).contiguous().view(-1)
+        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(), None,
+                       self._dev(rewards, torch.float32).contiguous().view(-1), done)
+
+    def train(self, done: bool, step: int = 0):
+        """:105-148: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
+        device tensor.  `done` is a host bool (the target counter lives on the host)."""
+        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
+                                  generator=self.generator)
+
+    def save_model(self, file_name: str) -> None:
+        """:179-180: torch.save of the model's six-tensor state_dict under CollectModel's names (on the CPU): the
+        reference's CollectAgent.load_model loads it."""
+        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
+
+    def load_model(self, file_name: str) -> None:
+        """:182-184: model and target net from a state_dict file of the reference's."""
+        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
+
+    # ---- the fused loop -------------------------------------------------------------------------------------------
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop on `env` (a BatchedAntsEnv holding a current observation): act, select, record_pre,
+        env.step_update, record_post, train.  Returns the loss (0 while the replay memory is below min_replay or when not
+        training, else a 0-d device tensor).  No host synchronisation."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        assert obs.is_contiguous(), "LinearPolicy reads dense observation rows (obs_row_stride=None)"
+        rot, ph = self.get_action(obs, ast, training, env=env)
+        rm = self.replay_memory
+        rm.record_pre(obs, ast, None, rot.view(-1), ph.view(-1), **self._record_kw())
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
+        if env is self._env:
+            self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
+        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
         return self.train(done, self._action_step) if training else 0
 
     def run(self, env, steps: int, training: bool = True) -> list:

@@ -1,6 +1,7 @@
 // antsrl_memapi.hip — the memory agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h): the net's inference
 // (antsrl_memnet_*, antsrl_policy_memory*), its training step (antsrl_memtrain_*) and the loop around them
-// (antsrl_agent_select, antsrl_agent_plan, antsrl_replay_record_*).
+// (antsrl_agent_select, antsrl_agent_plan, antsrl_replay_record_*), with the loop's memory-less forms for the linear agent
+// (antsrl_agent_select_actions, antsrl_replay_record_*_plain: the same kernels without a memory operand).
 //
 // Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip, antsrl_memtrain.hip
 // and antsrl_memagent.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
@@ -406,14 +407,16 @@ extern "C" int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_ba
     return enqueued(antsrl_launch_agent_plan(a, tiles, n_live, (hipStream_t)stream), who);
 }
 
-static int check_spec(const char *who, const AntsRecordSpec *r)
+// plain: the memory-less entries, whose spec has mem_size == 0 (the entries with a memory go on refusing that)
+static int check_spec(const char *who, const AntsRecordSpec *r, bool plain = false)
 {
     if (!r) return fail(ANTSRL_E_INVALID, "%s: NULL spec", who);
     int rc = check_batch(who, r->env_id_base, r->n_envs, r->n_ants);
     if (rc != ANTSRL_OK) return rc;
     if (r->n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, r->n_features);
     if ((rc = check_width(who, "agent_dim", r->agent_dim)) != ANTSRL_OK) return rc;
-    if ((rc = check_width(who, "mem_size", r->mem_size)) != ANTSRL_OK) return rc;
+    if (plain && r->mem_size != 0) return fail(ANTSRL_E_INVALID, "%s: mem_size must be 0 (%d): this entry records no memory", who, r->mem_size);
+    if (!plain && (rc = check_width(who, "mem_size", r->mem_size)) != ANTSRL_OK) return rc;
     if ((rc = check_width(who, "n_rot", r->n_rot)) != ANTSRL_OK) return rc;
     if ((rc = check_D(who, r->n_features, r->agent_dim, r->mem_size)) != ANTSRL_OK) return rc;
     if (r->obs_format != ANTSRL_OBS_F32 && r->obs_format != ANTSRL_OBS_BF16)
@@ -487,6 +490,71 @@ extern "C" int antsrl_replay_record_post(const AntsRecordSpec *r, const void *ob
     RecArgs a = {};
     fill_rec(r, &a);
     a.obs = obs; a.agent_state = agent_state; a.memory = memory; a.reward = reward; a.done = done;
+    a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
+    return launch_rec(who, r, a, true, stream);
+}
+
+// ---- the loop without a memory (the linear agent: agents/collect_agent.py:150-177).  The kernels are the ones above: the
+// select kernel copies no memory when mem_old == mem_next (both NULL here), the record kernel's small fields are
+// agent_dim + mem_size wide (mem_size 0 here), so neither ever touches a memory pointer.
+extern "C" int antsrl_agent_select_actions(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
+                                           double epsilon, int32_t n_rot, int32_t n_ph, int8_t *rotation, int8_t *pheromone,
+                                           uint8_t *explored, void *stream)
+{
+    const char *who = "agent_select_actions";
+    int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
+    if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
+    if (rc != ANTSRL_OK) return rc;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
+    if (!rotation) return fail(ANTSRL_E_INVALID, "%s: rotation is required", who);
+    if (!pheromone) return fail(ANTSRL_E_INVALID, "%s: pheromone is required", who);
+    SelArgs a = {};
+    a.seed = seed; a.step = step; a.epsilon = epsilon;
+    a.rot = rotation; a.ph = pheromone; a.explored = explored; // mem_old == mem_next == NULL: no memory part
+    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants; a.n_rot = (uint32_t)n_rot; a.n_ph = (uint32_t)n_ph;
+    a.M = (uint32_t)((long long)n_envs * n_ants);
+    return enqueued(antsrl_launch_agent_select(a, false, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_replay_record_pre_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state,
+                                              const int8_t *rotation, const int8_t *pheromone, float *states,
+                                              float *agent_states, int64_t *actions, void *stream)
+{
+    const char *who = "replay_record_pre_plain";
+    const int rc = check_spec(who, r, true);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
+    REQUIRE(agent_state, 4);
+    REQUIRE(rotation, 1);
+    REQUIRE(states, 4);
+    REQUIRE(agent_states, 4);
+    REQUIRE(actions, 8);
+    RecArgs a = {};
+    fill_rec(r, &a);
+    a.obs = obs; a.agent_state = agent_state; a.rot = rotation; a.ph = pheromone;
+    a.states = states; a.agent_states = agent_states; a.actions = actions;
+    return launch_rec(who, r, a, false, stream);
+}
+
+extern "C" int antsrl_replay_record_post_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state,
+                                               const float *reward, const uint8_t *done, float *rewards, float *new_states,
+                                               float *new_agent_states, uint8_t *dones, void *stream)
+{
+    const char *who = "replay_record_post_plain";
+    const int rc = check_spec(who, r, true);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
+    REQUIRE(agent_state, 4);
+    REQUIRE(reward, 4);
+    REQUIRE(done, 1);
+    REQUIRE(rewards, 4);
+    REQUIRE(new_states, 4);
+    REQUIRE(new_agent_states, 4);
+    REQUIRE(dones, 1);
+    RecArgs a = {};
+    fill_rec(r, &a);
+    a.obs = obs; a.agent_state = agent_state; a.reward = reward; a.done = done;
     a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
     return launch_rec(who, r, a, true, stream);
 }

@@ -33,6 +33,7 @@
 // finalize = 16, apply = 1.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_adam.h"
 #include "antsrl_memtrain.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -370,10 +371,7 @@ __global__ void __launch_bounds__(256) k_mt_adam(MtLayers T, float *params, floa
     if (update) {
         const float g = grads[e];
         float mm = m[e], vv = v[e];
-        mm = mm + w1 * (g - mm);                        // exp_avg.lerp_(grad, 1 - beta1)
-        vv = vv * beta2 + w2 * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        const float denom = sqrtf(vv) / bc2_sqrt + eps; // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-        p = p + -step_size * (mm / denom);              // param.addcdiv_(exp_avg, denom, value=-step_size)
+        p = adam_element(p, g, mm, vv, step_size, bc2_sqrt, w1, beta2, w2, eps); // antsrl_adam.h
         m[e] = mm;
         v[e] = vv;
         params[e] = p;

@@ -104,23 +104,32 @@ class DeviceReplayMemory:
         agent_states (= agent_state ++ memory) and actions (rotation + n_rot // 2, pheromone; pheromone None: 1) of `k`
         of the n_envs * n_ants transitions (None: all of them, in order) go to the rows `extend` would write next.  Which
         ants (a stratified sample keyed on seed, env_id_base, step) and the copy itself: include/antsrl.h.  All inputs are
+        `memory` None: the memory-less form (agent_states rows are agent_state alone; antsrl_replay_record_pre_plain).
         device tensors: obs float32 or bfloat16, contiguous [.., P, P, K] — or, with obs_pitch (elements between two
         ants' rows), the padded buffer of a BatchedAntsEnv(obs_row_stride="line") —, agent_state float32 [M, 2],
         memory float32 [M, mem], rotation / pheromone int8 [M].  Nothing moves head or fill until record_post."""
         assert self._pending is None, "record_pre twice without record_post"
         M = n_envs * n_ants
         F = int(np.prod(self.observation_space))
-        mem = memory.shape[-1]
+        mem = 0 if memory is None else memory.shape[-1]
         A = int(np.prod(self.agent_space)) - mem
         spec = _lib.AntsRecordSpec(n_envs, n_ants, env_id_base, F, A, mem, n_rot, self._obs_format(obs), obs_pitch, 0,
                                    M if k is None else k, self.head, self.max_len, seed, step)
         self._check(obs, obs.dtype, M * (obs_pitch or F))
         self._check(agent_state, torch.float32, M * A)
-        self._check(memory, torch.float32, M * mem)
+        if memory is not None:
+            self._check(memory, torch.float32, M * mem)
         self._check(rotation, torch.int8, M)
         if pheromone is not None:
             self._check(pheromone, torch.int8, M)
         with torch.cuda.device(self.states.device):
+            if memory is None:
+                _lib.check(_lib.load().antsrl_replay_record_pre_plain(C.byref(spec), _p(obs), _p(agent_state), _p(rotation),
+                                                                      _p(pheromone), _p(self.states), _p(self.agent_states),
+                                                                      _p(self.actions), _lib.stream(self.states.device)),
+                           "replay_record_pre_plain")
+                self._pending = spec
+                return
             _lib.check(_lib.load().antsrl_replay_record_pre(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(rotation),
                                                             _p(pheromone), _p(self.states), _p(self.agent_states),
                                                             _p(self.actions), _lib.stream(self.states.device)),
@@ -141,14 +150,24 @@ class DeviceReplayMemory:
             done = done.view(torch.uint8)
         self._check(obs, obs.dtype, M * (spec.obs_pitch or spec.n_features))
         self._check(agent_state, torch.float32, M * spec.agent_dim)
-        self._check(memory, torch.float32, M * spec.mem_size)
+        assert (memory is None) == (spec.mem_size == 0), "record_post: a memory exactly when record_pre had one"
+        if memory is not None:
+            self._check(memory, torch.float32, M * spec.mem_size)
         self._check(reward, torch.float32, M)
         self._check(done, torch.uint8, spec.n_envs)
         with torch.cuda.device(self.states.device):
-            _lib.check(_lib.load().antsrl_replay_record_post(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(reward),
-                                                             _p(done), _p(self.rewards), _p(self.new_states),
-                                                             _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
-                                                             _lib.stream(self.states.device)), "replay_record_post")
+            if memory is None:
+                _lib.check(_lib.load().antsrl_replay_record_post_plain(C.byref(spec), _p(obs), _p(agent_state), _p(reward),
+                                                                       _p(done), _p(self.rewards), _p(self.new_states),
+                                                                       _p(self.new_agent_states),
+                                                                       _p(self.dones.view(torch.uint8)),
+                                                                       _lib.stream(self.states.device)),
+                           "replay_record_post_plain")
+            else:
+                _lib.check(_lib.load().antsrl_replay_record_post(C.byref(spec), _p(obs), _p(agent_state), _p(memory),
+                                                                 _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
+                                                                 _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
+                                                                 _lib.stream(self.states.device)), "replay_record_post")
         self._pending = None
         n = int(spec.K)
         if n > self.max_len:  # as extend: only the newest max_len entries survived

@@ -231,3 +231,199 @@ def _numel(shape):
     for s in shape:
         n *= s
     return n
+
+
+#: CollectModel.state_dict()'s names and order (agents/collect_agent.py:24-51 over explore_agent_pytorch.py:24-45)
+LINEAR_NAMES = ("explore_model.layer1.weight", "explore_model.layer1.bias", "explore_model.layer2.weight",
+                "explore_model.layer2.bias", "layer3.weight", "layer3.bias")
+#: the four trained tensors in the flat 198-float block (include/antsrl.h): name -> (offset, shape)
+LINEAR_TRAINED = {"explore_model.layer2.weight": (0, (3, 32)), "explore_model.layer2.bias": (96, (3,)),
+                  "layer3.weight": (99, (3, 32)), "layer3.bias": (195, (3,))}
+
+
+class LinearTrainer:
+    """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
+    reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
+
+    Only layer2 and layer3 are trained (198 floats): the reference freezes layer1, whose .grad stays None.  Model and
+    target net share one ExploreModel, so the target net's rotation head is the live layer2 and only layer3 has a target
+    copy.  `policy` is the acting LinearPolicy (get_action acts with the target net, :166): the shared layer1, the live
+    layer2 and the target layer3 — its head tensors are views of this trainer's buffers, so it needs no copy after a
+    step.  `version` counts the changes of the acting weights (every step moves layer2).
+
+    The surface is MemoryTrainer's: grad / apply / step, train(replay, done), state_dict / load_state_dict under the
+    reference's six names, target_state_dict, sync_target, adam_state, grad_dict."""
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
+        from .policy import LinearPolicy
+        self.device = torch.device(device)
+        assert self.device.type == "cuda", "LinearTrainer runs on the GPU"
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_features = n_features
+        self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
+        self.update_target_every = int(update_target_every)
+        self.target_update_counter = 0
+        self.syncs = 0
+        self.step_count = 0
+        self.version = 0
+        self._lib = _lib.load()
+        p = LinearPolicy(n_features, self.device, seed=seed)
+        self.heads = torch.cat([p.w2.reshape(-1), p.b2, p.w3.reshape(-1), p.b3]).contiguous()
+        self.target_l3 = self.heads[99:198].clone()
+        self._adam = torch.zeros((2, 198), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((198,), dtype=torch.float32, device=self.device)
+        self._work = None
+        p.w2, p.b2 = self.heads[0:96].view(3, 32), self.heads[96:99]              # the live layer2
+        p.w3, p.b3 = self.target_l3[0:96].view(3, 32), self.target_l3[96:99]      # the target layer3
+        self.policy = p
+        self.trained_floats = 198
+        if state_dict is not None:
+            self.load_state_dict(state_dict)
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def _model_views(self) -> dict:
+        d = {"explore_model.layer1.weight": self.policy.w1, "explore_model.layer1.bias": self.policy.b1}
+        for k, (o, shp) in LINEAR_TRAINED.items():
+            d[k] = self.heads[o: o + _numel(shp)].view(shp)
+        return d
+
+    def state_dict(self) -> dict:
+        """The model's six tensors (copies) under CollectModel's names, in its order."""
+        return {k: v.clone() for k, v in self._model_views().items()}
+
+    def target_state_dict(self) -> dict:
+        """The target net's: the shared layer1 and layer2, its own layer3."""
+        d = self.state_dict()
+        d["layer3.weight"], d["layer3.bias"] = self.target_l3[0:96].view(3, 32).clone(), self.target_l3[96:99].clone()
+        return d
+
+    def load_state_dict(self, sd) -> None:
+        """CollectAgent.load_model (:182-184): sets the model AND the target net.  CollectModel's names, or ExploreModel's
+        bare layer1 / layer2 (with layer3).  Adam's state is kept, as the reference's optimizer keeps it."""
+        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v
+              for k, v in sd.items()}
+        for k, dst in self._model_views().items():
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+            dst.copy_(src)
+        self.target_l3.copy_(self.heads[99:198])
+        self.version += 1
+
+    def adam_state(self) -> dict:
+        """torch.optim.Adam's state for the four trained tensors: step, exp_avg, exp_avg_sq (copies)."""
+        def views(row):
+            return {k: self._adam[row, o: o + _numel(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
+        return dict(step=self.step_count, exp_avg=views(0), exp_avg_sq=views(1))
+
+    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
+        """The flat gradient (self.grads by default) as views named like the four trained tensors."""
+        g = self.grads if grads is None else grads
+        return {k: g[o: o + _numel(shp)].view(shp) for k, (o, shp) in LINEAR_TRAINED.items()}
+
+    def sync_target(self) -> None:
+        """target := model (:143-146): layer3 is all the two nets do not share."""
+        self.target_l3.copy_(self.heads[99:198])
+        self.syncs += 1
+        self.version += 1
+
+    # ---- the stages ---------------------------------------------------------------------------------------------
+    def _arrays(self, batch_or_replay):
+        r = batch_or_replay
+        a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones) \
+            if hasattr(r, "states") else tuple(r)
+        n = len(r) if hasattr(r, "states") else a[0].shape[0]
+        assert len(a) == 7
+        st, ast, act, rw, nst, nast, dn = a
+        N = st.shape[0]
+        for t, dt in ((st, torch.float32), (ast, torch.float32), (act, torch.int64), (rw, torch.float32),
+                      (nst, torch.float32), (nast, torch.float32), (dn, torch.bool)):
+            assert t.device == self.device and t.dtype == dt and t.is_contiguous() and t.shape[0] == N, (t.shape, t.dtype)
+        assert st[0].numel() == self.n_features and nst[0].numel() == self.n_features
+        assert ast.shape[1:] == (2,) and nast.shape[1:] == (2,), "agent_states rows are the 2 floats of agent_state"
+        assert act.shape[1:] == (2,) and rw.dim() == 1 and dn.dim() == 1
+        return a, n, N
+
+    def _batch(self, batch_or_replay, idx):
+        a, n, N = self._arrays(batch_or_replay)
+        if idx is not None:
+            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
+            B = idx.numel()
+        else:
+            B = n
+        assert B >= 1
+        ws = C.c_size_t()
+        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, C.byref(ws), None), "lintrain_sizes")
+        if self._work is None or self._work.numel() < ws.value:
+            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
+        return a, N, B
+
+    def launches(self, B: int) -> int:
+        """Kernel launches of one step on B rows: 1 up to 512 rows, else 2 (antsrl_lintrain_sizes)."""
+        n = C.c_int32()
+        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, None, C.byref(n)), "lintrain_sizes")
+        return n.value
+
+    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The loss (0-d device tensor) and the gradients of the four trained tensors into self.grads; nothing is
+        updated.  Rows: as MemoryTrainer.grad."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        p = self.policy
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_lintrain_grad(self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3),
+                                                      _p(st), _p(ast), _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N,
+                                                      _p(idx), B, self.discount, _p(self.grads), _p(loss), _p(self._work),
+                                                      _lib.stream(self.device)), "lintrain_grad")
+        return loss
+
+    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
+        """One Adam step on the 198 trained floats from the flat gradient (self.grads by default)."""
+        g = self.grads if grads is None else grads
+        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == 198 and g.is_contiguous()
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_lintrain_apply(_p(self.heads), _p(self._adam[0]), _p(self._adam[1]), _p(g),
+                                                       self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                       _lib.stream(self.device)), "lintrain_apply")
+        self.version += 1
+
+    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+             keep_grads: bool = True) -> torch.Tensor:
+        """One training step on the minibatch, gradient and Adam in the same launches (antsrl_lintrain_step): returns the
+        loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        p = self.policy
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_lintrain_step(self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3),
+                                                      _p(self._adam[0]), _p(self._adam[1]), _p(st), _p(ast), _p(act), _p(rw),
+                                                      _p(nst), _p(nast), _p(dn), N, _p(idx), B, self.discount,
+                                                      self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                      _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
+                                                      _lib.stream(self.device)), "lintrain_step")
+        self.version += 1
+        return loss
+
+    def train(self, replay, done: bool, minibatch: int = 264, min_replay: int = 1000,
+              generator: Optional[torch.Generator] = None):
+        """CollectAgent.train (:105-148): 0 below min_replay, else a step on `minibatch` rows drawn on the device (with
+        replacement), then the target counter (host side: `done` is a host bool) and the sync."""
+        if len(replay) < min_replay:
+            return 0
+        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
+        return self.train_on(replay, idx, done)
+
+    def train_on(self, batch_or_replay, idx: Optional[torch.Tensor], done: bool):
+        """train() on rows the caller picked: the step, then the target counter and the sync."""
+        loss = self.step(batch_or_replay, idx)
+        if done:
+            self.target_update_counter += 1
+        if self.target_update_counter >= self.update_target_every:
+            self.sync_target()
+            self.target_update_counter = 0
+        return loss

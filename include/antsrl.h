@@ -695,6 +695,76 @@ int antsrl_replay_record_post(const AntsRecordSpec *r, const void *obs, const fl
                               const float *reward, const uint8_t *done, float *rewards, float *new_states,
                               float *new_agent_states, uint8_t *dones, void *stream);
 
+/* The loop without a memory, for the linear agent (CollectAgent, agents/collect_agent.py:150-177; its agent_states rows
+ * are the 2 floats of agent_state).  antsrl_agent_select and AntsRecordSpec go on refusing mem_size == 0; these three
+ * entries launch the SAME kernels without a memory operand, under the same draw specification and the same stream tags:
+ * for equal (seed, step, env_id_base, n_envs, n_ants, epsilon, n_rot, n_ph) antsrl_agent_select_actions writes the
+ * rotation, pheromone and explored bytes antsrl_agent_select writes, and for an AntsRecordSpec that differs in mem_size
+ * alone (0 here) the _plain entries write the states, actions, rewards, new_states and dones rows the entries above
+ * write; agent_states / new_agent_states are float [max_len][agent_dim], row = agent_state[a].  Every other rule (limits,
+ * alignment, validation before any HIP call, one launch each, no atomics, no host synchronisation) is theirs. */
+int antsrl_agent_select_actions(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
+                                double epsilon, int32_t n_rot, int32_t n_ph, int8_t *rotation, int8_t *pheromone,
+                                uint8_t *explored, void *stream);
+int antsrl_replay_record_pre_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state,
+                                   const int8_t *rotation, const int8_t *pheromone, float *states, float *agent_states,
+                                   int64_t *actions, void *stream);
+int antsrl_replay_record_post_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state, const float *reward,
+                                    const uint8_t *done, float *rewards, float *new_states, float *new_agent_states,
+                                    uint8_t *dones, void *stream);
+
+/* The linear agent's training step: CollectAgent.train (agents/collect_agent.py:105-148) for the net antsrl_policy_mlp
+ * evaluates (layer1 [32][F + 2], layer2 [3][32], layer3 [3][32]; F = n_features, n_features + 2 <= 1024).
+ * What is trained: layer2 and layer3, 198 floats.  layer1 is frozen (CollectModel.__init__ clears its requires_grad; its
+ * .grad stays None): it is only read, and has no Adam state.  Model and target net share ONE ExploreModel, so the target
+ * net's rotation head is the live layer2 and only layer3 has a target copy.
+ *   heads      float [198]: w2 [3][32] at 0, b2 [3] at 96, w3 [3][32] at 99, b3 [3] at 195 (the state_dict's order)
+ *   target_l3  float [99]:  w3 [3][32] at 0, b3 [3] at 96
+ *   adam_m, adam_v, grads: float [198], laid out like heads
+ * Per minibatch row b (replay row i = idx[b], or b when idx is NULL; i is clamped to [0, n_rows)), with
+ * x = states[i] ++ agent_states[i] and x' = new_states[i] ++ new_agent_states[i]:
+ *     h  = layer1(x), h' = layer1(x')                     the sequence of antsrl_policy_mlp's flat form (k_policy_flat, the
+ *                                                         form it takes whenever W1 and two 32-row images fit the LDS: every
+ *                                                         F the reference's perception produces; its fallback for wider rows
+ *                                                         feeds agent_state through the MFMA instead): x and w1 rounded to
+ *                                                         bfloat16 (RNE), the F observation inputs accumulated in fp32 by
+ *                                                         v_mfma_f32_32x32x16_bf16 in ascending 16-input steps, then
+ *                                                         acc + (x[F] * w1[.][F] + x[F + 1] * w1[.][F + 1]) + b1 in fp32
+ *     q_rot = layer2(h), q_ph = layer3(h)                 EVERYTHING FROM HERE ON IS fp32 on the fp32 masters (the acting
+ *     q'_rot = layer2(h'), q'_ph = target_l3(h')          kernel rounds h and the head weights to bfloat16 for its second
+ *     y_*  = rewards[i] + discount * max(q'_*) * !dones[i]  MFMA; the training forward does not: q - y feeds the gradient)
+ *     d_rot = q_rot[actions[i][0]] - y_rot,  d_ph = q_ph[actions[i][1]] - y_ph        (action indices clamped to 0..2)
+ *     loss  = sum_b (d_rot^2 + d_ph^2) / (3 B)            = MSE(q_rot, target_rot) + MSE(q_ph, target_ph), whose targets
+ *     dL/dq = 2 d / (3 B) at the taken action, 0 elsewhere  are the no-grad q with the taken entry replaced by y
+ *     grads = dL/dq^T h (weights), sum_b dL/dq (biases)
+ * Sums over rows are taken in a fixed order (32 rows of a tile in row order per wave, a wave's tiles in order, waves in
+ * order, workgroups in order) without atomics: equal inputs give equal bits.  Adam is torch.optim.Adam's single-tensor
+ * arithmetic in fp32 per element (antsrl_memtrain_apply's), its step size and sqrt(1 - beta2^step) computed in double on
+ * the host.  The target sync (target_l3 := heads[99 .. 198) when the caller's `done` counter says so) is one 396-byte
+ * device copy of the caller's.
+ * Launches: one for B <= 512 (one workgroup, whose 4 waves take up to 4 tiles each), else two (antsrl_lintrain_sizes
+ * reports which).  workspace
+ * (256-byte aligned, workspace_bytes) is needed for two launches only.  states / new_states float [n_rows][n_features],
+ * agent_states / new_agent_states float [n_rows][2], actions int64 [n_rows][2], rewards float [n_rows], dones bool
+ * [n_rows], idx int64 [B] or NULL, all on the device; loss: one device float.  1 <= B <= 2^24.
+ *   _grad:  loss and grads; heads is not written.
+ *   _apply: Adam on heads from grads; step >= 1 is Adam's step count.
+ *   _step:  both in the same launches (grads may be NULL). */
+int antsrl_lintrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes, int32_t *launches);
+int antsrl_lintrain_grad(int32_t n_features, const float *w1, const float *b1, const float *heads, const float *target_l3,
+                         const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                         const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                         const int64_t *idx, int64_t B, float discount, float *grads, float *loss, void *workspace,
+                         void *stream);
+int antsrl_lintrain_apply(float *heads, float *adam_m, float *adam_v, const float *grads, int64_t step, double lr,
+                          double beta1, double beta2, double eps, void *stream);
+int antsrl_lintrain_step(int32_t n_features, const float *w1, const float *b1, float *heads, const float *target_l3,
+                         float *adam_m, float *adam_v, const float *states, const float *agent_states,
+                         const int64_t *actions, const float *rewards, const float *new_states,
+                         const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                         float discount, int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
+                         float *loss, void *workspace, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */

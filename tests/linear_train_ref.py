@@ -1,0 +1,186 @@
+"""The linear agent's training step restated twice, for the tests of antsrl_lintrain_step:
+
+  fp32_train_step      the reference's arithmetic: CollectAgent.train (agents/collect_agent.py:105-148) in torch fp32 with
+                       autograd, then torch.optim.Adam's single-tensor update — what linear_train_ref.npz records;
+  contract_train_step  the device contract of include/antsrl.h: layer1 on bfloat16-rounded x and w1 (the products are
+                       exact in fp32; they are summed in float64 here, the MFMA sums them in fp32), everything behind
+                       it in fp32 from the closed form  dL/dq = 2 (q - y) / (3 B) at the taken action.
+
+Both take and update a `state` dict: sd (the six tensors under CollectModel's names), target_w3 / target_b3, m / v (Adam's
+moments of the four trained tensors, by name), step.  `batch` = (states [B, F], agent_states [B, 2], actions [B, 2],
+rewards [B], new_states, new_agent_states, dones [B]), already gathered.  Both return (loss, grads by name)."""
+import numpy as np
+import torch
+
+NAMES = ("explore_model.layer1.weight", "explore_model.layer1.bias", "explore_model.layer2.weight",
+         "explore_model.layer2.bias", "layer3.weight", "layer3.bias")
+TRAINED = NAMES[2:]
+U_BF16 = 2.0 ** -9  # bfloat16's unit roundoff (8 significand bits, round to nearest even)
+
+
+def new_state(sd):
+    sd = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32).clone() for k, v in sd.items()}
+    return dict(sd=sd, target_w3=sd["layer3.weight"].clone(), target_b3=sd["layer3.bias"].clone(),
+                m={k: torch.zeros_like(sd[k]) for k in TRAINED}, v={k: torch.zeros_like(sd[k]) for k in TRAINED}, step=0)
+
+
+def sync_target(state):
+    state["target_w3"], state["target_b3"] = state["sd"]["layer3.weight"].clone(), state["sd"]["layer3.bias"].clone()
+
+
+def _t(batch):
+    st, ast, act, rw, nst, nast, dn = batch
+    f = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
+    B = len(rw)
+    return (f(st).reshape(B, -1), f(ast).reshape(B, 2), torch.as_tensor(np.asarray(act), dtype=torch.int64), f(rw),
+            f(nst).reshape(B, -1), f(nast).reshape(B, 2), torch.as_tensor(np.asarray(dn), dtype=torch.bool))
+
+
+def adam(state, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
+    """torch.optim.Adam, single tensor, fp32 per element; the bias corrections in double."""
+    state["step"] += 1
+    t = state["step"]
+    bc1, bc2 = 1.0 - betas[0] ** t, 1.0 - betas[1] ** t
+    step_size, bc2_sqrt = np.float32(lr / bc1), np.float32(bc2 ** 0.5)
+    for k in TRAINED:
+        g = grads[k].to(torch.float32)
+        m, v = state["m"][k], state["v"][k]
+        m.lerp_(g, float(np.float32(1.0 - betas[0])))
+        v.mul_(float(np.float32(betas[1]))).addcmul_(g, g, value=float(np.float32(1.0 - betas[1])))
+        denom = (v.sqrt() / float(bc2_sqrt)).add_(float(np.float32(eps)))
+        state["sd"][k].addcdiv_(m, denom, value=-float(step_size))
+
+
+def fp32_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
+    st, ast, act, rw, nst, nast, dn = _t(batch)
+    sd = state["sd"]
+    p = {k: sd[k].clone().requires_grad_(k in TRAINED) for k in NAMES}
+
+    def net(x, a, w3, b3):
+        out = torch.cat([x, a], dim=1) @ p[NAMES[0]].T + p[NAMES[1]]
+        return out @ p[NAMES[2]].T + p[NAMES[3]], out @ w3.T + b3
+    rows = torch.arange(len(rw))
+    with torch.no_grad():
+        fr, fp = net(nst, nast, state["target_w3"], state["target_b3"])  # the target net: shared layer1 and layer2
+        tr, tp = net(st, ast, p[NAMES[4]], p[NAMES[5]])
+        tr, tp = tr.clone(), tp.clone()
+        tr[rows, act[:, 0]] = rw + discount * fr.max(dim=1).values * ~dn
+        tp[rows, act[:, 1]] = rw + discount * fp.max(dim=1).values * ~dn
+    qr, qp = net(st, ast, p[NAMES[4]], p[NAMES[5]])
+    loss = torch.nn.functional.mse_loss(qr, tr) + torch.nn.functional.mse_loss(qp, tp)
+    loss.backward()
+    grads = {k: p[k].grad.detach().clone() for k in TRAINED}
+    if update:
+        adam(state, grads, lr, betas, eps)
+    return float(loss.detach()), grads
+
+
+def bf16(x):
+    return torch.as_tensor(x, dtype=torch.float32).to(torch.bfloat16).to(torch.float32)
+
+
+def contract_hidden(sd, x, a):
+    """layer1 as the device computes it: [B, 32] fp32."""
+    w1, b1 = sd[NAMES[0]], sd[NAMES[1]]
+    F = x.shape[1]
+    acc = (bf16(x).double() @ bf16(w1[:, :F]).double().T).to(torch.float32)
+    wa, aa = bf16(w1[:, F:]), bf16(a)
+    return acc + (aa[:, 0:1] * wa[:, 0] + aa[:, 1:2] * wa[:, 1]) + b1
+
+
+def contract_forward(state, batch, discount=0.5):
+    """h, the d = q - y of both heads, and what they are made of (all fp32)."""
+    st, ast, act, rw, nst, nast, dn = _t(batch)
+    sd = state["sd"]
+    h, hn = contract_hidden(sd, st, ast), contract_hidden(sd, nst, nast)
+    lin = lambda v, w, b: (v.double() @ w.double().T).to(torch.float32) + b  # noqa: E731
+    qr, qp = lin(h, sd[NAMES[2]], sd[NAMES[3]]), lin(h, sd[NAMES[4]], sd[NAMES[5]])
+    nr, npq = lin(hn, sd[NAMES[2]], sd[NAMES[3]]), lin(hn, state["target_w3"], state["target_b3"])
+    live = (~dn).to(torch.float32)
+    rows = torch.arange(len(rw))
+    yr = rw + discount * nr.max(dim=1).values * live
+    yp = rw + discount * npq.max(dim=1).values * live
+    return dict(h=h, hn=hn, qr=qr, qp=qp, nr=nr, np=npq, dr=qr[rows, act[:, 0]] - yr, dp=qp[rows, act[:, 1]] - yp, act=act)
+
+
+def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
+    f = contract_forward(state, batch, discount)
+    B = len(f["dr"])
+    h, act = f["h"], f["act"]
+    scale, inv = np.float32(2.0 / (3.0 * B)), np.float32(1.0 / (3.0 * B))
+    dq = torch.zeros((B, 6), dtype=torch.float32)
+    rows = torch.arange(B)
+    dq[rows, act[:, 0]] = f["dr"] * float(scale)
+    dq[rows, 3 + act[:, 1]] = f["dp"] * float(scale)
+    loss = float((f["dr"] * f["dr"] * float(inv) + f["dp"] * f["dp"] * float(inv)).double().sum())
+    gw = (dq.double().T @ h.double()).to(torch.float32)
+    gb = dq.double().sum(dim=0).to(torch.float32)
+    grads = {NAMES[2]: gw[:3].clone(), NAMES[3]: gb[:3].clone(), NAMES[4]: gw[3:].clone(), NAMES[5]: gb[3:].clone()}
+    if update:
+        adam(state, grads, lr, betas, eps)
+    return loss, grads
+
+
+def bf16_bounds(state, batch, discount=0.5):
+    """How far the contract may stand from fp32, from bfloat16's unit roundoff u = 2^-9 alone.  x and w1 are each
+    rounded once, so a product is off by at most (2 u + u^2) |x w|:
+        e_h  = (2 u + u^2) (|x| |w1|^T)                         per hidden value           [B, 32]
+        e_q  = e_h |W|^T per head output, e_y = discount max_o e_q' (max is 1-Lipschitz), e_d = e_q[action] + e_y
+        loss:  sum_b (2 |d| e_d + e_d^2) / (3 B) per head
+        grad:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  (weights; h := 1, e_h := 0 for the biases)
+    with d, h taken from the fp32 forward.  fp32 summation adds a slack of the order 2^-24 * (terms) on top, far below."""
+    st, ast, act, rw, nst, nast, dn = _t(batch)
+    sd = state["sd"]
+    c = 2 * U_BF16 + U_BF16 ** 2
+    w1 = sd[NAMES[0]].double().abs()
+    eh = c * (torch.cat([st, ast], 1).double().abs() @ w1.T)
+    ehn = c * (torch.cat([nst, nast], 1).double().abs() @ w1.T)
+    hfun = lambda x, a: torch.cat([x, a], 1).double() @ sd[NAMES[0]].double().T + sd[NAMES[1]].double()  # noqa: E731
+    h, hn = hfun(st, ast), hfun(nst, nast)
+    rows = torch.arange(len(rw))
+    live = (~dn).double()
+    out = {}
+    for head, (wk, bk, tw, tb, col) in enumerate(((NAMES[2], NAMES[3], sd[NAMES[2]], sd[NAMES[3]], 0),
+                                                  (NAMES[4], NAMES[5], state["target_w3"], state["target_b3"], 1))):
+        W = sd[wk].double()
+        q = h @ W.T + sd[bk].double()
+        qn = hn @ tw.double().T + tb.double()
+        d = q[rows, act[:, col]] - (rw.double() + discount * qn.max(dim=1).values * live)
+        eq = (eh @ W.abs().T)[rows, act[:, col]]
+        ey = discount * (ehn @ tw.double().abs().T).max(dim=1).values * live
+        ed = eq + ey
+        B = len(rw)
+        out[("loss", head)] = float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum())
+        per = (2.0 / (3 * B)) * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh)   # [B, 32]
+        gw = torch.zeros((3, 32), dtype=torch.float64)
+        gb = torch.zeros((3,), dtype=torch.float64)
+        gw.index_add_(0, act[:, col], per)
+        gb.index_add_(0, act[:, col], (2.0 / (3 * B)) * ed)
+        out[wk], out[bk] = gw, gb
+    out["h"] = eh
+    return out
+
+
+def acting_gap_safe(w, x, head, nsig=4.0):
+    """Which rows' fp32 decision of one head (0 rotation, 1 pheromone) the bfloat16 acting kernel must reproduce.
+
+    The acting kernel rounds x and w1 (layer1's operands) and then h and the head's weights (its second MFMA) to bfloat16.
+    Each rounding is a relative error in [-u, u], u = 2^-9, taken as independent and uniform (variance u^2 / 3), so a
+    product of two rounded operands has relative variance 2 u^2 / 3:
+        var h[j]   = (2 u^2 / 3) sum_k (x_k w1[j][k])^2
+        var (q_a - q_b) = sum_j (W_a[j] - W_b[j])^2 var h[j]               (both heads read the same h: its error is shared)
+                        + (2 u^2 / 3) sum_j (h[j]^2 + var h[j]) (W_a[j]^2 + W_b[j]^2)      (the head's own roundings)
+    with a, b the fp32 top two.  A row is safe when the fp32 gap exceeds nsig = 4 standard deviations of that (a sum of
+    some 300 independent terms: a 4-sigma excursion has probability below 1e-4).  fp32 accumulation adds 2^-24-sized
+    terms, far below.  w: the six tensors by name (float64), x: [M, F + 2] float64.  Returns (safe [M] bool, argmax [M])."""
+    u = U_BF16
+    W1 = w[NAMES[0]]
+    h = x @ W1.T + w[NAMES[1]]
+    vh = (2 * u * u / 3) * ((x * x) @ (W1 * W1).T)
+    W, b = w[NAMES[2 + 2 * head]], w[NAMES[3 + 2 * head]]
+    q = h @ W.T + b
+    top = q.topk(2, dim=1)
+    Wa, Wb = W[top.indices[:, 0]], W[top.indices[:, 1]]
+    dW = Wa - Wb
+    vg = (vh * dW * dW).sum(1) + (2 * u * u / 3) * ((h * h + vh) * (Wa * Wa + Wb * Wb)).sum(1)
+    return (top.values[:, 0] - top.values[:, 1]) > nsig * vg.sqrt(), top.indices[:, 0]
