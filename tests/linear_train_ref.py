@@ -6,7 +6,10 @@
                        exact in fp32; they are summed in float64 here, the MFMA sums them in fp32), everything behind
                        it in fp32 from the closed form  dL/dq = 2 (q - y) / (3 B) at the taken action.
 
-Both take and update a `state` dict: sd (the six tensors under CollectModel's names), target_w3 / target_b3, m / v (Adam's
+bf16_bounds bounds contract against fp32 from bfloat16's unit roundoff; fp32_sum_bounds bounds a device against the contract
+from the order of fp32 sums alone (the bound of the shapes beyond F = 294: linear_train_cases.py).
+
+Both restatements take and update a `state` dict: sd (the six tensors under CollectModel's names), target_w3 / target_b3, m / v (Adam's
 moments of the four trained tensors, by name), step.  `batch` = (states [B, F], agent_states [B, 2], actions [B, 2],
 rewards [B], new_states, new_agent_states, dones [B]), already gathered.  Both return (loss, grads by name)."""
 import numpy as np
@@ -121,14 +124,48 @@ def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999),
     return loss, grads
 
 
+def _propagate(head, act, rw, live, discount, h, hn, eh, ehn, own=0.0, elem=0.0, rowsum=0.0, loss_elem=0.0):
+    """One head's share of a forward error bound, carried to the loss and the gradient sums (bf16_bounds and
+    fp32_sum_bounds share it).  head = (W, b, next W, next b, column of act); h, hn the hidden values of the rows and of
+    their successors and eh, ehn what they may be off by (float64, [B, 32]).
+        e_q  = e_h |W|^T + own ((|h| + e_h) |W|^T + |b|)        own: the head's own sum (0: exact)
+        e_y  = discount max_o e_q' (max is 1-Lipschitz);  e_d = e_q[action] + e_y + elem (|q| + |reward| + discount |max q'| + e_q + e_y)
+        loss:  sum_b (2 |d| e_d + e_d^2) / (3 B)  +  (rowsum + loss_elem) sum_b (|d| + e_d)^2 / (3 B)
+        grad:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  +  rowsum sum_b 2 / (3 B) (|d| + e_d) (|h| + e_h)
+    (weights; h := 1, e_h := 0 for the biases).  Returns (loss bound, weight bound [3, 32], bias bound [3])."""
+    W, b, tw, tb, col = head
+    W, b, tw, tb = W.double(), b.double(), tw.double(), tb.double()
+    B = len(rw)
+    rows = torch.arange(B)
+    a = act[:, col]
+    q = (h @ W.T + b)[rows, a]
+    qn = (hn @ tw.T + tb).max(dim=1).values
+    d = q - (rw.double() + discount * qn * live)
+    eq = (eh @ W.abs().T + own * ((h.abs() + eh) @ W.abs().T + b.abs()))[rows, a]
+    ey = discount * (ehn @ tw.abs().T + own * ((hn.abs() + ehn) @ tw.abs().T + tb.abs())).max(dim=1).values * live
+    ed = eq + ey + elem * (q.abs() + rw.double().abs() + discount * qn.abs() * live + eq + ey)
+    loss = float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum() + (rowsum + loss_elem) * ((d.abs() + ed) ** 2 / (3 * B)).sum())
+    per = (2.0 / (3 * B)) * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh
+                             + rowsum * (d.abs() + ed)[:, None] * (h.abs() + eh))   # [B, 32]
+    gw = torch.zeros((3, 32), dtype=torch.float64)
+    gb = torch.zeros((3,), dtype=torch.float64)
+    gw.index_add_(0, a, per)
+    gb.index_add_(0, a, (2.0 / (3 * B)) * (ed + rowsum * (d.abs() + ed)))
+    return loss, gw, gb
+
+
+def _heads(state):
+    sd = state["sd"]
+    return ((sd[NAMES[2]], sd[NAMES[3]], sd[NAMES[2]], sd[NAMES[3]], 0),          # rotation: the target net shares layer2
+            (sd[NAMES[4]], sd[NAMES[5]], state["target_w3"], state["target_b3"], 1))
+
+
 def bf16_bounds(state, batch, discount=0.5):
     """How far the contract may stand from fp32, from bfloat16's unit roundoff u = 2^-9 alone.  x and w1 are each
     rounded once, so a product is off by at most (2 u + u^2) |x w|:
         e_h  = (2 u + u^2) (|x| |w1|^T)                         per hidden value           [B, 32]
-        e_q  = e_h |W|^T per head output, e_y = discount max_o e_q' (max is 1-Lipschitz), e_d = e_q[action] + e_y
-        loss:  sum_b (2 |d| e_d + e_d^2) / (3 B) per head
-        grad:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  (weights; h := 1, e_h := 0 for the biases)
-    with d, h taken from the fp32 forward.  fp32 summation adds a slack of the order 2^-24 * (terms) on top, far below."""
+    carried through the heads, the TD target, the loss and the gradient sums by _propagate, with d, h taken from the
+    fp32 forward.  fp32 summation adds a slack of the order 2^-24 * (terms) on top, far below (fp32_sum_bounds)."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd = state["sd"]
     c = 2 * U_BF16 + U_BF16 ** 2
@@ -137,27 +174,49 @@ def bf16_bounds(state, batch, discount=0.5):
     ehn = c * (torch.cat([nst, nast], 1).double().abs() @ w1.T)
     hfun = lambda x, a: torch.cat([x, a], 1).double() @ sd[NAMES[0]].double().T + sd[NAMES[1]].double()  # noqa: E731
     h, hn = hfun(st, ast), hfun(nst, nast)
-    rows = torch.arange(len(rw))
     live = (~dn).double()
     out = {}
-    for head, (wk, bk, tw, tb, col) in enumerate(((NAMES[2], NAMES[3], sd[NAMES[2]], sd[NAMES[3]], 0),
-                                                  (NAMES[4], NAMES[5], state["target_w3"], state["target_b3"], 1))):
-        W = sd[wk].double()
-        q = h @ W.T + sd[bk].double()
-        qn = hn @ tw.double().T + tb.double()
-        d = q[rows, act[:, col]] - (rw.double() + discount * qn.max(dim=1).values * live)
-        eq = (eh @ W.abs().T)[rows, act[:, col]]
-        ey = discount * (ehn @ tw.double().abs().T).max(dim=1).values * live
-        ed = eq + ey
-        B = len(rw)
-        out[("loss", head)] = float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum())
-        per = (2.0 / (3 * B)) * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh)   # [B, 32]
-        gw = torch.zeros((3, 32), dtype=torch.float64)
-        gb = torch.zeros((3,), dtype=torch.float64)
-        gw.index_add_(0, act[:, col], per)
-        gb.index_add_(0, act[:, col], (2.0 / (3 * B)) * ed)
-        out[wk], out[bk] = gw, gb
+    for i, head in enumerate(_heads(state)):
+        out[("loss", i)], out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = _propagate(head, act, rw, live, discount, h, hn, eh, ehn)
     out["h"] = eh
+    return out
+
+
+U_FP32 = 2.0 ** -24  # fp32's unit roundoff
+
+
+def gamma(n, u=U_FP32):
+    """Higham's gamma_n = n u / (1 - n u): n roundings of relative size u compound to at most this."""
+    return n * u / (1.0 - n * u)
+
+
+def fp32_sum_bounds(state, batch, discount=0.5):
+    """An a-priori bound on |device - contract_train_step| per trained tensor (elementwise, float64) and for the loss
+    (key "loss"), from the order of fp32 sums alone; nothing is read from a device.  Operands are equal on both sides (the
+    bfloat16 roundings are part of the contract, and their products are exact in fp32), so all that differs is where the
+    sums round: contract_train_step sums in float64 and rounds once, a device sums in fp32 in an order of its own.  With
+    u = 2^-24 and gamma(n) = n u / (1 - n u), whatever the order:
+        layer1   e_h = gamma(F + 3) (|bf16 x| |bf16 w1|^T + |b1|)     F + 2 products and the bias: at most F + 3 roundings
+        heads    that error through |W|, and gamma(34) on the head's own sum of 32 products and a bias
+        y, d     a rounding each for discount * max, + reward, q - y, and the restatement's own: 4 u on the operands
+        rows     gamma(B + 2) sum_b |term|: B - 1 additions, the product, the 2 / (3 B) scaling and the restatement's rounding
+        loss     gamma(4) more per term: d * d, * 1 / (3 B), twice, and the sum of the two heads
+    carried to d, the loss and the gradients by _propagate, as bf16_bounds carries 2 u + u^2."""
+    st, ast, act, rw, nst, nast, dn = _t(batch)
+    sd = state["sd"]
+    B, F = st.shape
+    w1, b1 = bf16(sd[NAMES[0]]).double(), sd[NAMES[1]].double()
+
+    def hidden(x, a):
+        xa = bf16(torch.cat([x, a], 1)).double()
+        return xa @ w1.T + b1, gamma(F + 3) * (xa.abs() @ w1.abs().T + b1.abs())
+    (h, eh), (hn, ehn) = hidden(st, ast), hidden(nst, nast)
+    live = (~dn).double()
+    out = {"loss": 0.0}
+    for i, head in enumerate(_heads(state)):
+        loss, out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = _propagate(
+            head, act, rw, live, discount, h, hn, eh, ehn, own=gamma(34), elem=4 * U_FP32, rowsum=gamma(B + 2), loss_elem=gamma(4))
+        out["loss"] += loss
     return out
 
 
