@@ -3,7 +3,7 @@ reference's RLApi surface).  See DESIGN.md."""
 from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
-__all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer"]
+__all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -13,4 +13,10 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "LinearTrainer":
         from .train import LinearTrainer
         return LinearTrainer
+    if name == "ExploreAgent":
+        from .agent import ExploreAgent
+        return ExploreAgent
+    if name == "ExploreTrainer":
+        from .train import ExploreTrainer
+        return ExploreTrainer
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

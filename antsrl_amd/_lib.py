@@ -22,7 +22,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_policy_memory_ex", "antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post",
            "antsrl_policy_memory_tiles", "antsrl_agent_plan", "antsrl_agent_select_actions",
            "antsrl_replay_record_pre_plain", "antsrl_replay_record_post_plain", "antsrl_lintrain_sizes",
-           "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step")
+           "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step", "antsrl_exptrain_sizes",
+           "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step")
 
 _lib = None
 
@@ -116,6 +117,11 @@ def load() -> C.CDLL:
     lib.antsrl_lintrain_grad.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
     lib.antsrl_lintrain_apply.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.antsrl_lintrain_step.argtypes = [i32] + [vp] * 13 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
+                                                             C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.antsrl_exptrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
+    lib.antsrl_exptrain_grad.argtypes = [i32] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
+    lib.antsrl_exptrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    lib.antsrl_exptrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
                                                              C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol

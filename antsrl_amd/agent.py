@@ -34,7 +34,7 @@ from . import _lib
 from ._lib import ptr as _p
 from . import config as cm
 from .replay import DeviceReplayMemory
-from .train import LinearTrainer, MemoryTrainer
+from .train import ExploreTrainer, LinearTrainer, MemoryTrainer
 
 
 def _backend(api_or_env):
@@ -244,8 +244,10 @@ class CollectAgent:
         self._lib = _lib.load()
 
     # ---- the reference's surface ----------------------------------------------------------------------------------
-    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
-        """CollectAgent.setup (:75-98) for every ant of the batch."""
+    def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None) -> None:
+        """CollectAgent.setup (:75-98) for every ant of the batch.  `explore_model`: a four-tensor ExploreModel state_dict
+        file (ExploreAgent.save_model) whose layer1 and layer2 go under the collect heads (:84, the curriculum's second
+        stage: layer1 stays frozen from here on); applied behind `trained_model`, layer3 stays as it is."""
         env = _backend(api_or_env)
         cfg = env.cfg
         self.device = env.device
@@ -270,6 +272,8 @@ class CollectAgent:
         self._next_version = -1     # ... of the weights its next_rotation / next_pheromone were produced under
         if trained_model is not None:
             self.load_model(trained_model)
+        if explore_model is not None:
+            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
         if self.inloop:
             self._attach(env)
 
@@ -387,6 +391,170 @@ class CollectAgent:
         rm.record_pre(obs, ast, None, rot.view(-1), ph.view(-1), **self._record_kw())
         done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
         env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
+        if env is self._env:
+            self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
+        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step) if training else 0
+
+    def run(self, env, steps: int, training: bool = True) -> list:
+        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
+        return [self.rollout_step(env, training) for _ in range(steps)]
+
+
+class ExploreAgent:
+    """The explore agent on the device: ExploreAgentPytorch (agents/explore_agent_pytorch.py:48-165), the first stage of
+    the curriculum whose second stage is CollectAgent (collect_agent.py:81-90 puts this net's layer1 under the collect
+    heads and freezes it).  Rotation only: get_action returns (rotation, None), the environment is stepped without a
+    pheromone action and the replay memory stores (rotation + 1, 1).
+
+    The reference class cannot run as written (its forward concatenates without dim=1, :43, and train / get_action call
+    the two-input model with one argument, :100, :109, :150); what is built here is what it means: ExploreModel with
+    CollectModel.forward's concat (collect_agent.py:47-49) and the DQN step every other agent has, both layers trained
+    and the target net a full copy (`ExploreTrainer`, antsrl_exptrain.hip).
+
+    The surface and the fused loop are CollectAgent's.  `inloop=True` takes the actions from the observation kernel
+    whenever the handle holds the acting weights the observation was produced under.  The acting net is the target net,
+    which changes at a sync or a load only, so the handle is refreshed (antsrl_set_inloop_policy without a pheromone
+    head) at the first step after one of those and every other step is an in-loop hit, training or not."""
+
+    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
+                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 256, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
+                 inloop: bool = False):
+        assert rotations == 3, "the net's rotation head is 3 wide (antsrl_policy_mlp)"
+        self.name = "explore_agent_pytorch"
+        self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
+        self.learning_rate = learning_rate
+        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
+        self.update_target_every, self.seed, self.inloop = update_target_every, seed, inloop
+        self.trainer = self.replay_memory = self.generator = None
+        self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
+        self.inloop_hits = 0   # steps whose actions came from the observation kernel
+        self._lib = _lib.load()
+
+    # ---- the reference's surface ----------------------------------------------------------------------------------
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """ExploreAgentPytorch.setup (:69-85) for every ant of the batch."""
+        env = _backend(api_or_env)
+        cfg = env.cfg
+        self.device = env.device
+        self.n_envs, self.n_ants_per_env, self.env_id_base = cfg.n_envs, cfg.n_ants, cfg.env_id_base
+        self.n_ants = cfg.n_envs * cfg.n_ants
+        self.observation_space = tuple(env.obs.shape[-3:])
+        self.agent_space, self.action_space = [2], [2]
+        self.n_features = int(np.prod(self.observation_space))
+        self.trainer = ExploreTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+                                      update_target_every=self.update_target_every, seed=self.seed)
+        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_space,
+                                                self.action_space, device=self.device)
+        self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
+        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        # antsrl_agent_select_actions draws a pheromone for every exploring ant: it lands here and is never read
+        self._ph_scratch = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(self.seed)
+        self.step_counter = 0
+        self._action_step = 0
+        self._env = None            # the environment the in-loop policy is attached to
+        self._handle_version = -1   # trainer.version of the weights in its handle
+        self._next_version = -1     # ... of the weights its next_rotation was produced under
+        if trained_model is not None:
+            self.load_model(trained_model)
+        if self.inloop:
+            self.policy.attach(env)  # allocates env.next_rotation, copies the weights into the handle
+            self._env, self._handle_version = env, self.trainer.version
+
+    def initialize(self, api_or_env) -> None:
+        """:87-88: every pheromone activation x 10."""
+        env = _backend(api_or_env)
+        c = env.cfg
+        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
+
+    @property
+    def policy(self):
+        return self.trainer.policy
+
+    _dev = CollectAgent._dev
+    _record_kw = CollectAgent._record_kw
+
+    def refresh_inloop(self) -> None:
+        """The acting weights (the target net) into the handle again: after a sync or a load."""
+        env, p = self._env, self.policy
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(p.w1), _p(p.b1), _p(p.w2), _p(p.b2),
+                                                          None, None, _p(env.next_rotation), None,
+                                                          _lib.stream(self.device)), "set_inloop_policy")
+        self._handle_version = self.trainer.version
+
+    def get_action(self, obs, agent_state, training: bool, env=None):
+        """:146-156 -> (rotation int8, None), rotation a device tensor.  The target net acts on the whole batch; with
+        `training`, antsrl_agent_select_actions then replaces the rotations of the environments that explore this step
+        (probability epsilon each, one draw per environment) by uniform ones: the draws of the draw specification."""
+        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
+        ast = self._dev(agent_state, torch.float32)
+        step = self.step_counter
+        lead = obs.shape[:-3]
+        attached = self.inloop and env is not None and env is self._env and obs is env.obs
+        if attached and self._next_version == self.trainer.version:
+            self._rot.copy_(env.next_rotation.view(-1))  # what the observation kernel left for this observation
+            self.inloop_hits += 1
+        else:
+            if attached and self._handle_version != self.trainer.version:
+                self.refresh_inloop()  # the observation this step produces is acted on with these weights
+            rot, _ = self.policy.act(obs.contiguous(), ast.contiguous(), env=env)
+            self._rot.copy_(rot.reshape(-1))
+        if training:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
+                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
+                                                                 3, _p(self._rot), _p(self._ph_scratch),
+                                                                 _p(self._explored), _lib.stream(self.device)),
+                           "agent_select_actions")
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), None
+
+    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
+        """:135-144, from arrays the caller kept (`states`: the observation as it was BEFORE the step).  actions = what
+        get_action returned; (rotation + rotations // 2, 1) is what is stored (replay_memory.py:100-103)."""
+        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
+        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
+        rm = self.replay_memory
+        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), None,
+                      self._dev(actions[0], torch.int8).contiguous().view(-1), None, **self._record_kw())
+        if torch.is_tensor(done) or isinstance(done, np.ndarray):
+            done = self._dev(done, torch.uint8).contiguous().view(-1)
+        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(), None,
+                       self._dev(rewards, torch.float32).contiguous().view(-1), done)
+
+    def train(self, done: bool, step: int = 0):
+        """:90-133: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
+        device tensor.  `done` is a host bool (the target counter lives on the host)."""
+        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
+                                  generator=self.generator)
+
+    def save_model(self, file_name: str) -> None:
+        """:158-159: torch.save of the model's four-tensor state_dict under ExploreModel's names (on the CPU): the
+        reference's ExploreModel loads it, and CollectAgent.setup(explore_model=...) takes it as its frozen layer1."""
+        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
+
+    def load_model(self, file_name: str) -> None:
+        """:162-164: model and target net from a state_dict file."""
+        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
+
+    # ---- the fused loop -------------------------------------------------------------------------------------------
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop on `env` (a BatchedAntsEnv holding a current observation): act, select, record_pre,
+        env.step_update without a pheromone action, record_post, train.  Returns the loss (0 while the replay memory is
+        below min_replay or when not training, else a 0-d device tensor).  No host synchronisation."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        assert obs.is_contiguous(), "LinearPolicy reads dense observation rows (obs_row_stride=None)"
+        rot, _ = self.get_action(obs, ast, training, env=env)
+        rm = self.replay_memory
+        rm.record_pre(obs, ast, None, rot.view(-1), None, **self._record_kw())
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), None)
         if env is self._env:
             self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
         rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)

@@ -1,0 +1,338 @@
+// antsrl_exptrain.hip — the DQN training step of ExploreModel (layer1 [32][F + 2] and layer2 [3][32], both trained; the
+// target net a full copy) as TWO launches.  include/antsrl.h ("The explore agent's training step") holds the contract,
+// antsrl_exptrain.h the layout of a net's block, DESIGN.md §7.12 the reasons.
+//
+// Stage 1 (k_exptrain_fwd), one wave per 32 minibatch rows, four waves per workgroup.  It is k_lintrain's forward
+// (antsrl_lintrain.hip) with two bf16 images of W1 in LDS, the model's for h and the target's for h' (both fit at every
+// supported width: 129 KB of the 160 at F = 1022, so there is no second code path for wide rows): lane (r, h) gathers row
+// idx[r] of states / new_states, rounds it to bf16 and multiplies it with the image by v_mfma_f32_32x32x16_bf16 over the
+// 16-input steps in ascending order from a zero accumulator, then  acc + (as0 * w1[.][F] + as1 * w1[.][F + 1]) + b1  in
+// fp32 on bf16-rounded operands: the acting kernel's sequence.  Behind that everything is fp32 on the fp32 masters: q and
+// q', the TD target, d = q[a] - y, dq = d * 2 / (3 B), and
+//     dh[b][j] = dq[b] * w2[a_b][j]             one fp32 product, stored to the workspace as it is.
+// The wave leaves h (with a column of ones for b2) and dq (with the row's loss term) in its LDS tile, and lane l sums
+// outputs l and l + 64 of the 100 (layer2's 99 gradients, the loss) over the tile's 32 rows in row order from zero; the
+// workgroup adds its four waves' sums in wave order and writes them to its row of the partials.
+// Stage 2 (k_exptrain_l1).  Workgroup s < S = ceil((F + 3) / 8) owns columns 8 s .. 8 s + 7 of the [32][F + 3] product
+//     g[j][k] = sum_b dh[b][j] * xe[b][k],      xe[b] = bf16(states[i_b]) ++ bf16(agent_states[i_b]) ++ 1
+// (columns 0 .. F + 1 are g_w1, column F + 2 is g_b1).  Lane (j, c) = (lane & 31, lane >> 5) of wave w keeps the four
+// columns 8 s + 4 c .. + 3 of hidden unit j and walks rows w, w + 16, w + 32, ... (16 waves) in ascending order, one fmaf per
+// row and column from zero, eight rows' loads in flight: the stage is bound by the latency of its dependent loads (idx[b],
+// then the row), so it wants rows in flight, not arithmetic.  The 16 waves' sums are then added in wave order from wave
+// 0's, (((w0 + w1) + w2) + ...) + w15.  The same workgroup
+// writes the gradient and runs Adam on its own columns, so nothing crosses workgroups.  Workgroup S adds stage 1's
+// partials in workgroup order, writes layer2's gradient and the loss and runs Adam on layer2.
+// No atomics anywhere and every order above is fixed: equal inputs give equal bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "antsrl_adam.h"
+#include "antsrl_exptrain.h"
+#include "antsrl_lds_optin.h"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+struct __attribute__((packed, aligned(4))) EtF4 { float v[4]; }; // 4-byte aligned 16-byte load (rows with F % 4 != 0)
+
+#define ET_HSTRIDE 33 // floats per row of a wave's h tile: 32 hidden values and the 1.0 of b2
+#define ET_DSTRIDE 4  // floats per row of its dq tile: 3 dq, the loss term
+#define ET_SLOT 100   // floats per layer2 in LDS: [3][32] + [3], padded to 16 bytes
+#define ET_TILE (32 * ET_HSTRIDE + 32 * ET_DSTRIDE)
+#define ET_UNROLL 8   // rows per wave in flight in stage 2
+
+__device__ __forceinline__ void et_wave_sync()
+{
+    // LDS hand-off inside one wave: its LDS instructions execute in order, only the compiler must not reorder
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ float et_bf16(const float x) { return (float)(__bf16)x; }
+
+// 8 consecutive inputs k0 .. k0 + 7 of a row as a bf16 fragment; inputs at or beyond F are zero and never read
+__device__ __forceinline__ bf16x8 et_frag(const float *__restrict__ row, const int k0, const int F, const bool whole)
+{
+    bf16x8 b;
+    if (whole) {
+        const EtF4 lo = *reinterpret_cast<const EtF4 *>(row + k0), hi = *reinterpret_cast<const EtF4 *>(row + k0 + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            b[j] = (__bf16)lo.v[j];
+            b[4 + j] = (__bf16)hi.v[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float x = row[min(k0 + j, F - 1)]; // unconditional on a clamped address, then a select
+            b[j] = (__bf16)(k0 + j < F ? x : 0.0f);
+        }
+    }
+    return b;
+}
+
+// layer2's three outputs for this lane's row: the lane's 16 hidden values against its part of the weights, the other
+// half-wave's part added, then the bias.  w: [3][32] + [3] in LDS
+__device__ __forceinline__ void et_head(const float *w, const float (&hv)[16], const int h, float (&q)[3])
+{
+#pragma unroll
+    for (int o = 0; o < 3; ++o) {
+        float p = 0.0f;
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const float4 ww = *reinterpret_cast<const float4 *>(w + o * ET_HIDDEN + 8 * g4 + 4 * h);
+            p += ww.x * hv[4 * g4];
+            p += ww.y * hv[4 * g4 + 1];
+            p += ww.z * hv[4 * g4 + 2];
+            p += ww.w * hv[4 * g4 + 3];
+        }
+        q[o] = (p + __shfl_xor(p, 32)) + w[3 * ET_HIDDEN + o];
+    }
+}
+
+// the replay row of minibatch row b (b < B), never outside the replay arrays
+__device__ __forceinline__ long long et_row(const ExpTrainArgs &a, const int b)
+{
+    const long long ri = a.idx ? a.idx[b] : (long long)b;
+    return ri < 0 ? 0 : (ri >= a.n_rows ? a.n_rows - 1 : ri);
+}
+
+// gradient p of the block is `total`: stored, and Adam on trained float p
+__device__ __forceinline__ void et_epilogue(const ExpTrainArgs &a, const size_t p, const float total)
+{
+    if (a.grads) a.grads[p] = total;
+    if (a.adam) {
+        float mm = a.m[p], vv = a.v[p];
+        a.model[p] = adam_element(a.model[p], total, mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
+        a.m[p] = mm;
+        a.v[p] = vv;
+    }
+}
+
+__global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const int F = a.F, IN = F + 2, ksteps = a.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
+    __bf16 *w1s = reinterpret_cast<__bf16 *>(smem);                  // [2][32][KP]: the model's W1, the target's
+    float *hw = reinterpret_cast<float *>(smem + (size_t)2 * ET_HIDDEN * KP * 2); // 2 slots of ET_SLOT: layer2 of the model, of the target
+    float *l1x = hw + 2 * ET_SLOT;                                   // [2][3][32]: b1 and the bf16-rounded W1 columns F, F + 1
+    float *wpart = l1x + 6 * ET_HIDDEN;                              // [ET_WAVES][ET_PART]
+    float *tiles = wpart + ET_WAVES * ET_PART;                       // per wave: h [32][33], dq [32][4]
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wib = threadIdx.x >> 6;
+    float *ht = tiles + (size_t)wib * ET_TILE, *dqs = ht + 32 * ET_HSTRIDE;
+    const size_t ob1 = (size_t)ET_HIDDEN * IN, ol2 = ob1 + ET_HIDDEN;
+
+    for (int net = 0; net < 2; ++net) {
+        const float *blk = net ? a.target : a.model;
+        for (int row = wib; row < ET_HIDDEN; row += ET_WAVES) // W1's observation columns -> bf16
+            for (int k = lane; k < 16 * ksteps; k += 64) {
+                const float wv = blk[(size_t)row * IN + min(k, F - 1)];
+                w1s[(net * ET_HIDDEN + row) * KP + k] = (__bf16)(k < F ? wv : 0.0f);
+            }
+        for (int i = threadIdx.x; i < ET_L2; i += 64 * ET_WAVES) hw[net * ET_SLOT + i] = blk[ol2 + i];
+        if (threadIdx.x < ET_HIDDEN) {
+            const int hid = threadIdx.x;
+            l1x[(3 * net) * ET_HIDDEN + hid] = blk[ob1 + hid];
+            l1x[(3 * net + 1) * ET_HIDDEN + hid] = et_bf16(blk[(size_t)hid * IN + F]);
+            l1x[(3 * net + 2) * ET_HIDDEN + hid] = et_bf16(blk[(size_t)hid * IN + F + 1]);
+        }
+    }
+    ht[r * ET_HSTRIDE + 32] = 1.0f; // (both half-waves write the same value)
+    __syncthreads();
+
+    float out[2] = {0.0f, 0.0f}; // outputs lane, lane + 64: w2 [o / 32][o % 32], b2, the loss
+    int dcol[2], hcol[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int o = lane + 64 * j;
+        if (o < 96) { dcol[j] = o >> 5; hcol[j] = o & 31; }
+        else if (o < 99) { dcol[j] = o - 96; hcol[j] = 32; }
+        else { dcol[j] = 3; hcol[j] = 32; } // o == 99: the loss (o > 99 is never stored)
+    }
+
+    const int t = blockIdx.x * ET_WAVES + wib; // this wave's tile
+    if (t < a.ntiles) {
+        const __bf16 *wrow = w1s + r * KP + 8 * h, *wrow_t = wrow + ET_HIDDEN * KP;
+        const int nwhole = F / 16; // k-steps whose 16 inputs all lie inside the row
+        const int brow = t * 32 + r;
+        const bool valid = brow < a.B;
+        const long long ri = et_row(a, min(brow, a.B - 1));
+        const float *xs = a.states + (size_t)ri * F, *xn = a.new_states + (size_t)ri * F;
+        f32x16 acc, accn;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[g] = accn[g] = 0.0f;
+        int s = 0;
+#pragma unroll 1
+        for (; s < nwhole; ++s) {
+            const bf16x8 bs = et_frag(xs, 16 * s + 8 * h, F, true), bn = et_frag(xn, 16 * s + 8 * h, F, true);
+            const bf16x8 am = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s), at = *reinterpret_cast<const bf16x8 *>(wrow_t + 16 * s);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bs, acc, 0, 0, 0);
+            accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, bn, accn, 0, 0, 0);
+        }
+#pragma unroll 1
+        for (; s < ksteps; ++s) {
+            const bf16x8 bs = et_frag(xs, 16 * s + 8 * h, F, false), bn = et_frag(xn, 16 * s + 8 * h, F, false);
+            const bf16x8 am = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s), at = *reinterpret_cast<const bf16x8 *>(wrow_t + 16 * s);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bs, acc, 0, 0, 0);
+            accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, bn, accn, 0, 0, 0);
+        }
+        const float as0 = et_bf16(a.agent_states[(size_t)ri * 2]), as1 = et_bf16(a.agent_states[(size_t)ri * 2 + 1]);
+        const float an0 = et_bf16(a.new_agent_states[(size_t)ri * 2]), an1 = et_bf16(a.new_agent_states[(size_t)ri * 2 + 1]);
+        float hv[16], hn[16];
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) { // accumulator register g = 4 g4 + j of half-wave h is hidden value 8 g4 + 4 h + j
+            const int o = 8 * g4 + 4 * h;
+            const float4 bb = *reinterpret_cast<const float4 *>(l1x + o);
+            const float4 c0 = *reinterpret_cast<const float4 *>(l1x + ET_HIDDEN + o);
+            const float4 c1 = *reinterpret_cast<const float4 *>(l1x + 2 * ET_HIDDEN + o);
+            const float4 tb = *reinterpret_cast<const float4 *>(l1x + 3 * ET_HIDDEN + o);
+            const float4 t0 = *reinterpret_cast<const float4 *>(l1x + 4 * ET_HIDDEN + o);
+            const float4 t1 = *reinterpret_cast<const float4 *>(l1x + 5 * ET_HIDDEN + o);
+            const float bm[4] = {bb.x, bb.y, bb.z, bb.w}, m0[4] = {c0.x, c0.y, c0.z, c0.w}, m1[4] = {c1.x, c1.y, c1.z, c1.w};
+            const float bt[4] = {tb.x, tb.y, tb.z, tb.w}, u0[4] = {t0.x, t0.y, t0.z, t0.w}, u1[4] = {t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { // k_policy_flat's expression
+                hv[4 * g4 + j] = acc[4 * g4 + j] + (as0 * m0[j] + as1 * m1[j]) + bm[j];
+                hn[4 * g4 + j] = accn[4 * g4 + j] + (an0 * u0[j] + an1 * u1[j]) + bt[j];
+            }
+        }
+        float q[3], qn[3];
+        __builtin_amdgcn_sched_barrier(0); // (the weight vectors of both heads are not all hoisted in front of the first product)
+        et_head(hw, hv, h, q);             // the model's layer2 on h
+        __builtin_amdgcn_sched_barrier(0);
+        et_head(hw + ET_SLOT, hn, h, qn);  // the target's on h'
+        __builtin_amdgcn_sched_barrier(0);
+        const long long a64 = a.actions[(size_t)ri * 2];
+        const int act = a64 < 0 ? 0 : (a64 > 2 ? 2 : (int)a64);
+        const float live = a.dones[ri] ? 0.0f : 1.0f;
+        const float y = a.rewards[ri] + a.discount * fmaxf(fmaxf(qn[0], qn[1]), qn[2]) * live;
+        const float d = (act == 0 ? q[0] : act == 1 ? q[1] : q[2]) - y;
+        const float gq = valid ? d * a.dq_scale : 0.0f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) ht[r * ET_HSTRIDE + (g & 3) + 8 * (g >> 2) + 4 * h] = hv[g];
+        if (h == 0) {
+#pragma unroll
+            for (int o = 0; o < 3; ++o) dqs[r * ET_DSTRIDE + o] = act == o ? gq : 0.0f;
+            dqs[r * ET_DSTRIDE + 3] = valid ? d * d * a.loss_scale : 0.0f;
+        }
+        if (valid) { // dh = dq * w2[a]: the lane's 16 hidden units, four at a time
+            float *dst = a.dh + (size_t)brow * ET_HIDDEN;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+                const float4 ww = *reinterpret_cast<const float4 *>(hw + act * ET_HIDDEN + 8 * g4 + 4 * h);
+                *reinterpret_cast<float4 *>(dst + 8 * g4 + 4 * h) = make_float4(gq * ww.x, gq * ww.y, gq * ww.z, gq * ww.w);
+            }
+        }
+        et_wave_sync();
+#pragma unroll 4
+        for (int rr = 0; rr < 32; ++rr) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) out[j] += dqs[rr * ET_DSTRIDE + dcol[j]] * ht[rr * ET_HSTRIDE + hcol[j]];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        if (lane + 64 * j < ET_OUT) wpart[wib * ET_PART + lane + 64 * j] = out[j];
+    __syncthreads();
+    if (threadIdx.x < ET_OUT) {
+        float s = 0.0f;
+#pragma unroll
+        for (int w = 0; w < ET_WAVES; ++w) s += wpart[w * ET_PART + threadIdx.x];
+        a.partials[(size_t)blockIdx.x * ET_PART + threadIdx.x] = s;
+    }
+}
+
+// columns k0 .. k0 + 3 of xe[b] = bf16(states[ri]) ++ bf16(agent_states[ri]) ++ 1 (zero beyond)
+__device__ __forceinline__ void et_cols(const ExpTrainArgs &a, const long long ri, const int k0, float (&x)[4])
+{
+    const int F = a.F;
+    if (k0 + 3 < F) {
+        const EtF4 v = *reinterpret_cast<const EtF4 *>(a.states + (size_t)ri * F + k0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = et_bf16(v.v[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + i;
+            if (k < F) x[i] = et_bf16(a.states[(size_t)ri * F + k]);
+            else if (k < F + 2) x[i] = et_bf16(a.agent_states[(size_t)ri * 2 + (k - F)]);
+            else x[i] = k == F + 2 ? 1.0f : 0.0f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * ET_L1_WAVES) k_exptrain_l1(const ExpTrainArgs a, const int nslabs)
+{
+    __shared__ float red[ET_L1_WAVES * ET_HIDDEN * ET_SLAB];
+    const int F = a.F, IN = F + 2;
+    if ((int)blockIdx.x == nslabs) { // layer2 and the loss: stage 1's partials in workgroup order
+        if (threadIdx.x >= ET_OUT) return;
+        float s = 0.0f;
+        for (int b = 0; b < a.blocks; ++b) s += a.partials[(size_t)b * ET_PART + threadIdx.x];
+        if (threadIdx.x == ET_L2) *a.loss = s;
+        else et_epilogue(a, (size_t)ET_HIDDEN * IN + ET_HIDDEN + threadIdx.x, s);
+        return;
+    }
+    const int lane = threadIdx.x & 63, j = lane & 31, c = lane >> 5, wib = threadIdx.x >> 6;
+    const int k0 = blockIdx.x * ET_SLAB + 4 * c;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int b0 = wib; b0 < a.B; b0 += ET_L1_WAVES * ET_UNROLL) {
+        float d[ET_UNROLL], x[ET_UNROLL][4];
+#pragma unroll
+        for (int u = 0; u < ET_UNROLL; ++u) { // the loads of ET_UNROLL rows first: they do not depend on one another
+            const int b = min(b0 + ET_L1_WAVES * u, a.B - 1);
+            d[u] = a.dh[(size_t)b * ET_HIDDEN + j];
+            et_cols(a, et_row(a, b), k0, x[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < ET_UNROLL; ++u)
+            if (b0 + ET_L1_WAVES * u < a.B) { // (uniform in the wave)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = fmaf(d[u], x[u][i], acc[i]);
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[(wib * ET_HIDDEN + j) * ET_SLAB + 4 * c + i] = acc[i];
+    __syncthreads();
+    if (threadIdx.x >= ET_HIDDEN * ET_SLAB) return;
+    const int jj = threadIdx.x >> 3, col = threadIdx.x & 7, k = blockIdx.x * ET_SLAB + col;
+    float s = red[jj * ET_SLAB + col];
+#pragma unroll
+    for (int w = 1; w < ET_L1_WAVES; ++w) s += red[(w * ET_HIDDEN + jj) * ET_SLAB + col];
+    if (k < IN) et_epilogue(a, (size_t)jj * IN + k, s);
+    else if (k == IN) et_epilogue(a, (size_t)ET_HIDDEN * IN + jj, s);
+}
+
+__global__ void __launch_bounds__(256) k_exptrain_apply(const ExpTrainArgs a, const int P)
+{
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    float mm = a.m[p], vv = a.v[p];
+    a.model[p] = adam_element(a.model[p], a.grads[p], mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
+    a.m[p] = mm;
+    a.v[p] = vv;
+}
+
+static size_t et_lds(int ksteps)
+{
+    return (size_t)2 * ET_HIDDEN * (16 * ksteps + 8) * 2 +
+           (2 * ET_SLOT + 6 * ET_HIDDEN + (size_t)ET_WAVES * ET_PART + (size_t)ET_WAVES * ET_TILE) * 4;
+}
+
+hipError_t antsrl_launch_exptrain(const ExpTrainArgs &a, hipStream_t st)
+{
+    const size_t lds = et_lds(a.ksteps); // 61 KB at F = 294, 151 KB at the widest rows: above 64 KiB it is an opt-in per device
+    hipError_t e = antsrl_lds_optin<k_exptrain_fwd>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_exptrain_fwd, dim3(a.blocks), dim3(64 * ET_WAVES), lds, st, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const int nslabs = (a.F + 3 + ET_SLAB - 1) / ET_SLAB;
+    hipLaunchKernelGGL(k_exptrain_l1, dim3(nslabs + 1), dim3(64 * ET_L1_WAVES), 0, st, a, nslabs);
+    return hipGetLastError();
+}
+
+hipError_t antsrl_launch_exptrain_apply(const ExpTrainArgs &a, hipStream_t st)
+{
+    const int P = (int)antsrl_exptrain_floats(a.F);
+    hipLaunchKernelGGL(k_exptrain_apply, dim3((P + 255) / 256), dim3(256), 0, st, a, P);
+    return hipGetLastError();
+}

@@ -1,5 +1,7 @@
 // antsrl_linapi.hip — the linear agent's training step in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The linear
-// agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels.
+// agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels, and
+// behind them the explore agent's ("The explore agent's training step"): antsrl_exptrain_sizes / _grad / _apply / _step
+// in front of antsrl_exptrain.hip's, with the same argument rules.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -8,6 +10,7 @@
 #include <stdint.h>
 
 #include "antsrl_device.h"
+#include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
 #include "antsrl_lintrain.h"
 
@@ -37,7 +40,8 @@ struct LtAdam {
     double lr, beta1, beta2, eps;
 };
 
-static int lt_adam(const char *who, const LtAdam &o, LinTrainArgs *a)
+template <class Args> // LinTrainArgs or ExpTrainArgs
+static int lt_adam(const char *who, const LtAdam &o, Args *a)
 {
     if (o.step < 1) return fail(ANTSRL_E_INVALID, "%s: step must be >= 1", who);
     if (!(o.lr >= 0.0) || !(o.lr < 1e30)) return fail(ANTSRL_E_INVALID, "%s: lr must be finite and >= 0", who);
@@ -161,5 +165,120 @@ extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const f
     if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
     a.m = adam_m; a.v = adam_v;
     const hipError_t e = antsrl_launch_lintrain(a, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+}
+
+// ---- the explore agent's training step (antsrl_exptrain.hip) ------------------------------------------------------------
+
+static int et_B(const char *who, int64_t B)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > ET_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, ET_MAX_B);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
+                                     int32_t *launches)
+{
+    const char *who = "exptrain_sizes";
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = et_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
+    if (workspace_bytes) *workspace_bytes = antsrl_exptrain_dh_offset((int)B) + (size_t)B * ET_HIDDEN * sizeof(float);
+    if (launches) *launches = 2;
+    return ANTSRL_OK;
+}
+
+// the arguments the gradient stage and the fused step share
+static int et_batch(const char *who, int32_t n_features, float *model, const float *target, const float *states,
+                    const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                    const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                    float discount, float *grads, bool grads_required, float *loss, void *workspace, ExpTrainArgs *a)
+{
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = et_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
+    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
+    LT_REQUIRE(model, 4);
+    LT_REQUIRE(target, 4);
+    LT_REQUIRE(states, 4);
+    LT_REQUIRE(agent_states, 4);
+    LT_REQUIRE(actions, 8);
+    LT_REQUIRE(rewards, 4);
+    LT_REQUIRE(new_states, 4);
+    LT_REQUIRE(new_agent_states, 4);
+    LT_REQUIRE(dones, 1);
+    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
+    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
+    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
+    LT_REQUIRE(loss, 4);
+    LT_REQUIRE(workspace, 256);
+    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
+    a->states = states; a->agent_states = agent_states; a->rewards = rewards; a->new_states = new_states;
+    a->new_agent_states = new_agent_states; a->actions = actions; a->idx = idx; a->dones = dones;
+    a->model = model; a->target = target;
+    a->grads = grads; a->loss = loss;
+    a->partials = (float *)workspace;
+    a->dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
+    a->n_rows = n_rows;
+    a->B = (int)B; a->F = n_features; a->ksteps = (n_features + 15) / 16; a->ntiles = ((int)B + 31) / 32;
+    a->blocks = antsrl_exptrain_blocks((int)B);
+    a->discount = discount;
+    a->dq_scale = (float)(2.0 / (3.0 * (double)B));
+    a->loss_scale = (float)(1.0 / (3.0 * (double)B));
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_exptrain_grad(int32_t n_features, const float *model, const float *target, const float *states,
+                                    const float *agent_states, const int64_t *actions, const float *rewards,
+                                    const float *new_states, const float *new_agent_states, const uint8_t *dones,
+                                    int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, float *loss,
+                                    void *workspace, void *stream)
+{
+    const char *who = "exptrain_grad";
+    ExpTrainArgs a = {};
+    const int rc = et_batch(who, n_features, const_cast<float *>(model), target, states, agent_states, actions, rewards,
+                            new_states, new_agent_states, dones, n_rows, idx, B, discount, grads, true, loss, workspace, &a);
+    if (rc != ANTSRL_OK) return rc;
+    const hipError_t e = antsrl_launch_exptrain(a, (hipStream_t)stream); // a.adam == 0: model is only read
+    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+}
+
+extern "C" int antsrl_exptrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
+                                     int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
+{
+    const char *who = "exptrain_apply";
+    int rc = lt_features(who, n_features);
+    if (rc != ANTSRL_OK) return rc;
+    LT_REQUIRE(model, 4);
+    LT_REQUIRE(adam_m, 4);
+    LT_REQUIRE(adam_v, 4);
+    LT_REQUIRE(grads, 4);
+    ExpTrainArgs a = {};
+    if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
+    a.F = n_features; a.model = model; a.m = adam_m; a.v = adam_v; a.grads = const_cast<float *>(grads);
+    const hipError_t e = antsrl_launch_exptrain_apply(a, (hipStream_t)stream);
+    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+}
+
+extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
+                                    const float *states, const float *agent_states, const int64_t *actions,
+                                    const float *rewards, const float *new_states, const float *new_agent_states,
+                                    const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount,
+                                    int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
+                                    float *loss, void *workspace, void *stream)
+{
+    const char *who = "exptrain_step";
+    ExpTrainArgs a = {};
+    int rc = et_batch(who, n_features, model, target, states, agent_states, actions, rewards, new_states, new_agent_states,
+                      dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
+    if (rc != ANTSRL_OK) return rc;
+    LT_REQUIRE(adam_m, 4);
+    LT_REQUIRE(adam_v, 4);
+    if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
+    a.m = adam_m; a.v = adam_v;
+    const hipError_t e = antsrl_launch_exptrain(a, (hipStream_t)stream);
     return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
 }

@@ -241,6 +241,10 @@ LINEAR_TRAINED = {"explore_model.layer2.weight": (0, (3, 32)), "explore_model.la
                   "layer3.weight": (99, (3, 32)), "layer3.bias": (195, (3,))}
 
 
+#: ExploreModel.state_dict()'s names and order (agents/explore_agent_pytorch.py:24-45)
+EXPLORE_NAMES = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias")
+
+
 class LinearTrainer:
     """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
     reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
@@ -309,6 +313,19 @@ class LinearTrainer:
             assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
             dst.copy_(src)
         self.target_l3.copy_(self.heads[99:198])
+        self.version += 1
+
+    def load_explore_state_dict(self, sd) -> None:
+        """The hand-over from stage 1 of the curriculum (the line agents/collect_agent.py:84 has commented out): layer1
+        and layer2 from a four-tensor ExploreModel state_dict (an ExploreAgent's save_model; bare names or behind the
+        `explore_model.` prefix).  layer3, its target copy and Adam's state stay as they are."""
+        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
+        views = self._model_views()
+        for k in EXPLORE_NAMES:
+            dst = views["explore_model." + k]
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+            dst.copy_(src)
         self.version += 1
 
     def adam_state(self) -> dict:
@@ -427,3 +444,163 @@ class LinearTrainer:
             self.sync_target()
             self.target_update_counter = 0
         return loss
+
+
+class ExploreTrainer:
+    """ExploreAgentPytorch's model, target model and optimizer on the device (agents/explore_agent_pytorch.py:48-133 as it
+    was meant: ExploreModel with the concat of CollectModel.forward, collect_agent.py:47-49; defaults: the reference
+    class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_exptrain_step` (antsrl_exptrain.hip).
+
+    Both layers are trained: one flat fp32 block of P = 32 (F + 2) + 32 + 96 + 3 floats per net (include/antsrl.h), the
+    target net a second block.  `policy` is the acting LinearPolicy without a pheromone head (get_action acts with the
+    target net, :150): its w1, b1, w2, b2 are views of the TARGET block, so a training step never changes the actions and
+    a sync needs no copy into the policy.  `version` counts the changes of the acting weights: syncs and loads.
+
+    The surface is LinearTrainer's: grad / apply / step, train(replay, done), train_on, launches, state_dict /
+    load_state_dict under ExploreModel's four names, target_state_dict, sync_target, adam_state, grad_dict."""
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
+        from .policy import LinearPolicy
+        self.device = torch.device(device)
+        assert self.device.type == "cuda", "ExploreTrainer runs on the GPU"
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.n_features = n_features
+        self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
+        self.update_target_every = int(update_target_every)
+        self.target_update_counter = 0
+        self.syncs = 0
+        self.step_count = 0
+        self.version = 0
+        self._lib = _lib.load()
+        IN = n_features + 2
+        self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
+                      "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
+        tf = C.c_size_t()
+        _lib.check(self._lib.antsrl_exptrain_sizes(n_features, 1, C.byref(tf), None, None), "exptrain_sizes")
+        self.trained_floats = tf.value
+        assert self.trained_floats == 32 * IN + 131
+        p = LinearPolicy(n_features, self.device, with_pheromone_head=False, seed=seed)
+        self.model = torch.cat([p.w1.reshape(-1), p.b1, p.w2.reshape(-1), p.b2]).contiguous()
+        self.target = self.model.clone()
+        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
+        self._work = None
+        tv = self._views(self.target)
+        p.w1, p.b1, p.w2, p.b2 = (tv[k] for k in EXPLORE_NAMES)  # the acting net IS the target block
+        self.policy = p
+        if state_dict is not None:
+            self.load_state_dict(state_dict)
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def _views(self, flat) -> dict:
+        return {k: flat[o: o + _numel(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self) -> dict:
+        """The model's four tensors (copies) under ExploreModel's names, in its order."""
+        return {k: v.clone() for k, v in self._views(self.model).items()}
+
+    def target_state_dict(self) -> dict:
+        return {k: v.clone() for k, v in self._views(self.target).items()}
+
+    def load_state_dict(self, sd) -> None:
+        """ExploreAgentPytorch.load_model (:157-159): sets the model AND the target net.  ExploreModel's names, bare or
+        behind CollectModel's `explore_model.` prefix (other entries, such as layer3, are ignored).  Adam's state is
+        kept, as the reference's optimizer keeps it."""
+        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
+        for k, dst in self._views(self.model).items():
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+            dst.copy_(src)
+        self.target.copy_(self.model)
+        self.version += 1
+
+    def adam_state(self) -> dict:
+        """torch.optim.Adam's state for the four tensors: step, exp_avg, exp_avg_sq (copies)."""
+        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
+                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
+
+    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
+        """The flat gradient (self.grads by default) as views named like the four tensors."""
+        return self._views(self.grads if grads is None else grads)
+
+    def sync_target(self) -> None:
+        """target := model (:127-131): one device copy of the block; the acting policy's tensors are views of it."""
+        self.target.copy_(self.model)
+        self.syncs += 1
+        self.version += 1
+
+    # ---- the stages ---------------------------------------------------------------------------------------------
+    _arrays = LinearTrainer._arrays
+
+    def _batch(self, batch_or_replay, idx):
+        a, n, N = self._arrays(batch_or_replay)
+        if idx is not None:
+            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
+            B = idx.numel()
+        else:
+            B = n
+        assert B >= 1
+        ws = C.c_size_t()
+        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, C.byref(ws), None), "exptrain_sizes")
+        if self._work is None or self._work.numel() < ws.value:
+            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
+        return a, N, B
+
+    def launches(self, B: int) -> int:
+        """Kernel launches of one step on B rows: 2 (antsrl_exptrain_sizes)."""
+        n = C.c_int32()
+        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, None, C.byref(n)), "exptrain_sizes")
+        return n.value
+
+    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The loss (0-d device tensor) and the gradients of all P floats into self.grads; nothing is updated.  Rows: as
+        MemoryTrainer.grad."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_exptrain_grad(self.n_features, _p(self.model), _p(self.target), _p(st), _p(ast),
+                                                      _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N, _p(idx), B,
+                                                      self.discount, _p(self.grads), _p(loss), _p(self._work),
+                                                      _lib.stream(self.device)), "exptrain_grad")
+        return loss
+
+    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
+        """One Adam step on all P floats from the flat gradient (self.grads by default)."""
+        g = self.grads if grads is None else grads
+        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == self.trained_floats and g.is_contiguous()
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_exptrain_apply(self.n_features, _p(self.model), _p(self._adam[0]), _p(self._adam[1]),
+                                                       _p(g), self.step_count, self.lr, self.betas[0], self.betas[1],
+                                                       self.eps, _lib.stream(self.device)), "exptrain_apply")
+
+    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+             keep_grads: bool = True) -> torch.Tensor:
+        """One training step on the minibatch, gradient and Adam in the same two launches (antsrl_exptrain_step): returns
+        the loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        if loss is None:
+            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_exptrain_step(self.n_features, _p(self.model), _p(self.target), _p(self._adam[0]),
+                                                      _p(self._adam[1]), _p(st), _p(ast), _p(act), _p(rw), _p(nst),
+                                                      _p(nast), _p(dn), N, _p(idx), B, self.discount, self.step_count,
+                                                      self.lr, self.betas[0], self.betas[1], self.eps,
+                                                      _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
+                                                      _lib.stream(self.device)), "exptrain_step")
+        return loss
+
+    def train(self, replay, done: bool, minibatch: int = 256, min_replay: int = 1000,
+              generator: Optional[torch.Generator] = None):
+        """ExploreAgentPytorch.train (:90-133): 0 below min_replay, else a step on `minibatch` rows drawn on the device
+        (with replacement), then the target counter (host side: `done` is a host bool) and the sync."""
+        if len(replay) < min_replay:
+            return 0
+        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
+        return self.train_on(replay, idx, done)
+
+    train_on = LinearTrainer.train_on

@@ -765,6 +765,58 @@ int antsrl_lintrain_step(int32_t n_features, const float *w1, const float *b1, f
                          float discount, int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
                          float *loss, void *workspace, void *stream);
 
+/* The explore agent's training step: ExploreAgentPytorch.train (agents/explore_agent_pytorch.py:90-133) for ExploreModel
+ * (:24-45; layer1 [32][F + 2], layer2 [3][32]; F = n_features, n_features + 2 <= 1024) — the net whose layer1 the linear
+ * agent above freezes.  The reference class cannot run as written (its forward concatenates without dim=1, :43, and train
+ * and get_action call the two-input model with one argument): this is what it means, CollectModel.forward's concat
+ * (collect_agent.py:47-49) and the DQN step of the other agents.  BOTH layers are trained and the target net is a full
+ * copy.  A net is ONE flat fp32 block of P = 32 (F + 2) + 32 + 96 + 3 floats in the state_dict's order:
+ *   w1 [32][F + 2] at 0,  b1 [32] at 32 (F + 2),  w2 [3][32] at 32 (F + 2) + 32,  b2 [3] at 32 (F + 2) + 128
+ * `model` and `target` are two such blocks; adam_m, adam_v and grads are float [P], laid out the same way.  target is only
+ * read.  Per minibatch row b (replay row i = idx[b], or b when idx is NULL; i is clamped to [0, n_rows); a = actions[i][0]
+ * clamped to 0..2), with x = states[i] ++ agent_states[i] and x' = new_states[i] ++ new_agent_states[i]:
+ *     h  = layer1_model(x), h' = layer1_target(x')       the acting kernel's sequence, as for antsrl_lintrain_* above: x
+ *                                                         and w1 rounded to bfloat16 (RNE), the F observation inputs
+ *                                                         through v_mfma_f32_32x32x16_bf16 in ascending 16-input steps,
+ *                                                         then acc + (x[F] w1[.][F] + x[F + 1] w1[.][F + 1]) + b1 in fp32
+ *     q  = layer2_model(h), q' = layer2_target(h')        everything from here on is fp32 on the fp32 masters
+ *     y  = rewards[i] + discount * max(q') * !dones[i],   d = q[a] - y
+ *     loss  = sum_b d^2 / (3 B)                           MSELoss over [B, 3]: two of three entries are 0
+ *     dq[b] = d * (2 / (3 B)) at a, 0 elsewhere;          g_w2 = dq^T h,  g_b2 = sum_b dq
+ *     dh[b][j]   = dq[b][a] * w2[a][j]                    one fp32 product, never rounded to bfloat16
+ *     g_w1[j][k] = sum_b dh[b][j] * bf16(x[b][k])         all F + 2 columns, agent_state's two included
+ *     g_b1[j]    = sum_b dh[b][j]
+ * Layer1's gradient is taken with the bfloat16-rounded x the forward used, against the fp32 master w1: a straight-through
+ * gradient.  An Adam step at lr 1e-4 is about one bfloat16 ulp of a weight of size 0.05: steps accumulate in the fp32
+ * master and reach the forward pass when the master crosses a rounding boundary.
+ * Order of the sums over rows (no atomics; equal inputs give equal bits):
+ *   g_w2, g_b2, loss: the 32 rows of a tile in row order from zero (product rounded, then added); a workgroup of the
+ *       forward stage adds its four tiles' sums in tile order; the workgroups' sums are added in workgroup order.
+ *   g_w1, g_b1: rows w, w + 16, w + 32, ... in ascending order by one fmaf per row from zero, for w = 0..15; then
+ *       (((s0 + s1) + s2) + ...) + s15.
+ * Adam is antsrl_lintrain_*'s (antsrl_adam.h) on all P floats, its step size and sqrt(1 - beta2^step) computed in double on
+ * the host.  _grad followed by _apply gives the bits of _step.  The target sync is one device copy of the block, the
+ * caller's.
+ * Launches: two (the forward stage, one wave per 32 rows; the layer1 stage, one workgroup per 8 columns of the [32][F + 3]
+ * product, which also runs Adam on its own columns).  workspace (256-byte aligned, workspace_bytes: the forward stage's
+ * partial sums and dh [B][32]) is always needed.  Arrays as for antsrl_lintrain_*.  1 <= B <= 65536 (above:
+ * ANTSRL_E_UNSUPPORTED).  Every argument is checked before anything is launched; no host synchronisation.
+ *   _grad:  loss and grads; model is not written.
+ *   _apply: Adam on model from grads; step >= 1 is Adam's step count.
+ *   _step:  both in the same two launches (grads may be NULL). */
+int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes, int32_t *launches);
+int antsrl_exptrain_grad(int32_t n_features, const float *model, const float *target, const float *states,
+                         const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                         const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                         float discount, float *grads, float *loss, void *workspace, void *stream);
+int antsrl_exptrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads, int64_t step,
+                          double lr, double beta1, double beta2, double eps, void *stream);
+int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
+                         const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                         const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                         const int64_t *idx, int64_t B, float discount, int64_t step, double lr, double beta1, double beta2,
+                         double eps, float *grads, float *loss, void *workspace, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
