@@ -22,6 +22,11 @@ sample; None = all of them, the reference's behaviour — at c3's 524 288 ants p
 overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed`, `precision` (the acting policy's),
 `skip_explored` (off by default: skip the net for tiles whose ants all explore this step; results are unchanged).
 Exploration is drawn once per environment and step (an environment is one reference colony).
+
+`_DeviceAgent` holds what the three agents share (the hyper-parameters, the front of setup, the reference's surface
+around get_action, and the fused loop); `_InLoopAgent` adds what the two memory-less agents share on top of it: their
+acting step and the bookkeeping of the in-loop policy's handle.  An agent writes its trainer, its get_action and what
+it keeps between steps.
 """
 from __future__ import annotations
 
@@ -44,26 +49,27 @@ def _backend(api_or_env):
     return b
 
 
-class MemoryAgent:
-    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
-                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
-                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
-                 precision: str = "bf16", state_memory: str = "reference", mem_size: int = 20, power: int = 5,
-                 skip_explored: bool = False):
-        assert state_memory in ("reference", "carried"), "state_memory must be 'reference' or 'carried', not %r" % (state_memory,)
-        self.name = "collect_agent_memory"
+class _DeviceAgent:
+    """What every device agent is around its get_action: the hyper-parameters, the front of setup, the reference's
+    surface and the fused loop.  A subclass builds its trainer in setup, writes get_action (which returns (rotation,
+    pheromone or None) and, for an agent with a memory, the new memory behind them) and overrides `_state_memory` when it
+    has a memory to store and `_stepped` when it watches the environment's steps."""
+
+    def __init__(self, name: str, epsilon: float, discount: float, rotations: int, pheromones: int, learning_rate: float,
+                 record_per_step: Optional[int], replay_size: int, minibatch: int, min_replay: int,
+                 update_target_every: int, seed: int):
+        self.name = name
         self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
         self.learning_rate = learning_rate
         self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
-        self.update_target_every, self.seed, self.precision, self.state_memory = update_target_every, seed, precision, state_memory
-        self.mem_size, self.power, self.skip_explored = mem_size, power, skip_explored
+        self.update_target_every, self.seed = update_target_every, seed
         self.trainer = self.replay_memory = self.generator = None
         self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
         self._lib = _lib.load()
 
-    # ---- the reference's surface ----------------------------------------------------------------------------------
-    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
-        """CollectAgentMemory.setup (:108-127) for every ant of the batch."""
+    def _setup(self, api_or_env, agent_states_space):
+        """The front of every setup: the batch's sizes, the spaces, the replay memory (its agent_states rows
+        `agent_states_space` wide), the generator and the counters.  Returns the BatchedAntsEnv."""
         env = _backend(api_or_env)
         cfg = env.cfg
         self.device = env.device
@@ -72,28 +78,18 @@ class MemoryAgent:
         self.observation_space = tuple(env.obs.shape[-3:])
         self.agent_space, self.action_space = [2], [2]
         self.n_features = int(np.prod(self.observation_space))
-        self.agent_and_mem_space = [2 + self.mem_size]
-        self.trainer = MemoryTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
-                                     update_target_every=self.update_target_every, power=self.power, mem_size=self.mem_size,
-                                     n_rot=self.rotations, n_ph=self.pheromones, seed=self.seed,
-                                     policy_precision=self.precision)
-        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_and_mem_space,
+        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, agent_states_space,
                                                 self.action_space, device=self.device)
-        self._mem = [torch.zeros((self.n_ants, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
-        self._cur = 0  # self._mem[self._cur] is previous_memory (:111)
         self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
-        # skip_explored: antsrl_agent_plan's list of live tiles and its length
-        self._tiles = torch.zeros(((self.n_ants + 31) // 32,), dtype=torch.int32, device=self.device)
-        self._n_live = torch.zeros((1,), dtype=torch.int32, device=self.device)
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(self.seed)
         self.step_counter = 0
         self._action_step = 0
-        if trained_model is not None:
-            self.load_model(trained_model)
+        return env
 
+    # ---- the reference's surface ----------------------------------------------------------------------------------
     def initialize(self, api_or_env) -> None:
-        """:129-131: every pheromone activation x 10."""
+        """Every pheromone activation x 10."""
         env = _backend(api_or_env)
         c = env.cfg
         env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
@@ -102,13 +98,115 @@ class MemoryAgent:
     def policy(self):
         return self.trainer.policy
 
-    @property
-    def previous_memory(self) -> torch.Tensor:
-        return self._mem[self._cur]
-
     def _dev(self, a, dtype):
         t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
         return t.to(device=self.device, dtype=dtype) if (t.device != self.device or t.dtype != dtype) else t
+
+    def _obs(self, a):
+        """An observation as the kernels take it: a bfloat16 tensor as it is, anything else as float32 on the device."""
+        return a if (torch.is_tensor(a) and a.dtype == torch.bfloat16) else self._dev(a, torch.float32)
+
+    def _state_memory(self):
+        """The memory that goes into agent_states: none."""
+        return None
+
+    def _stepped(self, env) -> None:
+        """`env` has just been stepped with this step's actions."""
+
+    def _record_kw(self):
+        return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
+                    step=self._action_step, env_id_base=self.env_id_base, n_rot=self.rotations)
+
+    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
+        """One step's transitions from arrays the caller kept (`states` must be the observation as it was BEFORE the
+        step: the environment writes every observation into the same buffer).  actions = what get_action returned;
+        rotation + rotations // 2 is what is stored, and 1 for a pheromone that is None (replay_memory.py:100-103)."""
+        rot, ph, mem = (*actions, None)[:3]
+        rm = self.replay_memory
+        rm.record_pre(self._obs(states).contiguous(), self._dev(agent_state, torch.float32).contiguous(), self._state_memory(),
+                      self._dev(rot, torch.int8).contiguous().view(-1),
+                      None if ph is None else self._dev(ph, torch.int8).contiguous().view(-1), **self._record_kw())
+        if torch.is_tensor(done) or isinstance(done, np.ndarray):
+            done = self._dev(done, torch.uint8).contiguous().view(-1)
+        rm.record_post(self._obs(new_states).contiguous(), self._dev(new_agent_states, torch.float32).contiguous(),
+                       None if mem is None else self._dev(mem, torch.float32).contiguous(),
+                       self._dev(rewards, torch.float32).contiguous().view(-1), done)
+
+    def train(self, done: bool, step: int = 0):
+        """0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d device
+        tensor.  `done` is a host bool (the target counter lives on the host)."""
+        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
+                                  generator=self.generator)
+
+    def save_model(self, file_name: str) -> None:
+        """torch.save of the model's state_dict under the reference's names (on the CPU), so the reference loads what
+        this trains."""
+        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
+
+    def load_model(self, file_name: str) -> None:
+        """Model and target net (and the acting policy) from a state_dict file of the reference's."""
+        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
+
+    # ---- the fused loop -------------------------------------------------------------------------------------------
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
+        observe() or a step): act, select, record_pre, env.step_update (without a pheromone action when get_action gives
+        none), record_post, train.  Returns the loss (0 while the replay memory is below min_replay or when not training,
+        else a 0-d device tensor).  No host synchronisation: `done` for the target counter is the host's own step count
+        against max_time."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        assert obs.is_contiguous(), "%s reads dense observation rows (obs_row_stride=None)" % type(self.policy).__name__
+        rot, ph, mem = (*self.get_action(obs, ast, training, env=env), None)[:3]
+        rm = self.replay_memory
+        rm.record_pre(obs, ast, self._state_memory(), rot.view(-1), None if ph is None else ph.view(-1), **self._record_kw())
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        shape = (env.cfg.n_envs, env.cfg.n_ants)
+        env.step_update(rot.view(shape), None if ph is None else ph.view(shape))
+        self._stepped(env)
+        rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step) if training else 0
+
+    def run(self, env, steps: int, training: bool = True) -> list:
+        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
+        return [self.rollout_step(env, training) for _ in range(steps)]
+
+
+class MemoryAgent(_DeviceAgent):
+    """CollectAgentMemory on the device (the module docstring).  Reference lines (collect_agent_memory.py): setup
+    :108-127, initialize :129-131, train :133-176, update_replay_memory :178-187, get_action :189-206, save_model
+    :208-209 (the 26-tensor state_dict), load_model :211-213."""
+
+    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
+                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
+                 precision: str = "bf16", state_memory: str = "reference", mem_size: int = 20, power: int = 5,
+                 skip_explored: bool = False):
+        assert state_memory in ("reference", "carried"), "state_memory must be 'reference' or 'carried', not %r" % (state_memory,)
+        super().__init__("collect_agent_memory", epsilon, discount, rotations, pheromones, learning_rate, record_per_step,
+                         replay_size, minibatch, min_replay, update_target_every, seed)
+        self.precision, self.state_memory = precision, state_memory
+        self.mem_size, self.power, self.skip_explored = mem_size, power, skip_explored
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """CollectAgentMemory.setup (:108-127) for every ant of the batch."""
+        self.agent_and_mem_space = [2 + self.mem_size]
+        self._setup(api_or_env, self.agent_and_mem_space)
+        self.trainer = MemoryTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+                                     update_target_every=self.update_target_every, power=self.power, mem_size=self.mem_size,
+                                     n_rot=self.rotations, n_ph=self.pheromones, seed=self.seed,
+                                     policy_precision=self.precision)
+        self._mem = [torch.zeros((self.n_ants, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self._cur = 0  # self._mem[self._cur] is previous_memory (:111)
+        # skip_explored: antsrl_agent_plan's list of live tiles and its length
+        self._tiles = torch.zeros(((self.n_ants + 31) // 32,), dtype=torch.int32, device=self.device)
+        self._n_live = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    @property
+    def previous_memory(self) -> torch.Tensor:
+        return self._mem[self._cur]
 
     def get_action(self, obs, agent_state, training: bool, env=None):
         """:189-206 -> (rotation int8, pheromone int8, memory float32 [M, mem_size]), device tensors.  The target net acts
@@ -117,7 +215,7 @@ class MemoryAgent:
         `skip_explored` (and `training`) antsrl_agent_plan first lists the 32-ant tiles that hold an ant of a
         non-exploring environment and the net runs on those only (antsrl_policy_memory_tiles): the same results bit for
         bit, without the forward passes select would throw away."""
-        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
+        obs = self._obs(obs)
         ast = self._dev(agent_state, torch.float32)
         old, new = self._mem[self._cur], self._mem[1 - self._cur]
         step = self.step_counter
@@ -148,65 +246,86 @@ class MemoryAgent:
         """The memory that goes into agent_states (see the module docstring)."""
         return self.previous_memory if self.state_memory == "reference" else self._memory_before
 
-    def _record_kw(self):
-        return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
-                    step=self._action_step, env_id_base=self.env_id_base, n_rot=self.rotations)
 
-    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
-        """:178-187, from arrays the caller kept (`states` must be the observation as it was BEFORE the step: the
-        environment writes every observation into the same buffer).  actions = what get_action returned."""
-        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
-        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
-        rm = self.replay_memory
-        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), self._state_memory(),
-                      self._dev(actions[0], torch.int8).contiguous().view(-1),
-                      None if actions[1] is None else self._dev(actions[1], torch.int8).contiguous().view(-1),
-                      **self._record_kw())
-        if torch.is_tensor(done) or isinstance(done, np.ndarray):
-            done = self._dev(done, torch.uint8).contiguous().view(-1)
-        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(),
-                       self._dev(actions[2], torch.float32).contiguous(), self._dev(rewards, torch.float32).contiguous().view(-1),
-                       done)
+class _InLoopAgent(_DeviceAgent):
+    """What the two memory-less agents share on top of _DeviceAgent: the acting step on a LinearPolicy and the in-loop
+    form of it.  `inloop=True` takes the actions from the observation kernel (LinearPolicy.attach: bfloat16 observations
+    on the cell-meta path) whenever the weights in the handle are the acting weights the observation was produced
+    under, and from the standalone kernel otherwise — the two kernels give the same actions bit for bit, so both
+    settings give the same actions, rings, weights and losses.  The handle's weights are refreshed
+    (antsrl_set_inloop_policy) lazily: at the first step after the acting weights changed for which `_refresh_due`."""
 
-    def train(self, done: bool, step: int = 0):
-        """:133-176: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
-        device tensor.  `done` is a host bool (the target counter lives on the host)."""
-        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
-                                  generator=self.generator)
+    def __init__(self, name: str, *hyper, inloop: bool):
+        super().__init__(name, *hyper)
+        self.inloop = inloop
+        self.inloop_hits = 0   # steps whose actions came from the observation kernel
 
-    def save_model(self, file_name: str) -> None:
-        """:208-209: torch.save of the model's 26-tensor state_dict under the reference's names (on the CPU), so the
-        reference loads what this trains."""
-        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
+    def _setup(self, api_or_env, agent_states_space):
+        env = super()._setup(api_or_env, agent_states_space)
+        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        # (without a pheromone head only antsrl_agent_select_actions writes here, the pheromone it draws for every
+        # exploring ant, and nothing reads it)
+        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self._env = None            # the environment the in-loop policy is attached to
+        self._handle_version = -1   # trainer.version of the weights in its handle
+        self._next_version = -1     # ... of the weights its next_rotation / next_pheromone were produced under
+        return env
 
-    def load_model(self, file_name: str) -> None:
-        """:211-213: model and target net (and the acting policy) from a state_dict file of the reference's."""
-        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
+    # ---- the in-loop policy's weights -----------------------------------------------------------------------------
+    def _attach(self, env) -> None:
+        self.policy.attach(env)  # allocates env.next_rotation / next_pheromone, copies the weights into the handle
+        self._env, self._handle_version, self._next_version = env, self.trainer.version, -1
 
-    # ---- the fused loop -------------------------------------------------------------------------------------------
+    def refresh_inloop(self) -> None:
+        """The acting weights into the handle again (antsrl_set_inloop_policy: a 38 KB device copy and the pack; w3, b3
+        and next_pheromone are None for a policy without a pheromone head)."""
+        env, p = self._env, self.policy
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(p.w1), _p(p.b1), _p(p.w2), _p(p.b2),
+                                                          _p(p.w3), _p(p.b3), _p(env.next_rotation), _p(env.next_pheromone),
+                                                          _lib.stream(self.device)), "set_inloop_policy")
+        self._handle_version = self.trainer.version
 
-    def rollout_step(self, env, training: bool = True):
-        """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
-        observe() or a step): act, select, record_pre, env.step_update, record_post, train.  Returns the loss (0 while the
-        replay memory is below min_replay or when not training, else a 0-d device tensor).  No host synchronisation: `done`
-        for the target counter is the host's own step count against max_time."""
-        env = _backend(env)
-        obs, ast = env.obs, env.agent_state
-        assert obs.is_contiguous(), "MemoryPolicy reads dense observation rows (obs_row_stride=None)"
-        rot, ph, mem = self.get_action(obs, ast, training, env=env)
-        rm = self.replay_memory
-        rm.record_pre(obs, ast, self._state_memory(), rot.view(-1), ph.view(-1), **self._record_kw())
-        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
-        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
-        rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
-        return self.train(done, self._action_step) if training else 0
+    def _refresh_due(self, training: bool) -> bool:
+        """Whether a handle with stale weights gets the acting weights at the step that starts now."""
+        raise NotImplementedError
 
-    def run(self, env, steps: int, training: bool = True) -> list:
-        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
-        return [self.rollout_step(env, training) for _ in range(steps)]
+    def _stepped(self, env) -> None:
+        if env is self._env:
+            self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
+
+    def get_action(self, obs, agent_state, training: bool, env=None):
+        """-> (rotation int8, pheromone int8 or None), device tensors: the acting net on the whole batch (in the loop or
+        standalone); with `training`, antsrl_agent_select_actions then replaces the actions of the environments that
+        explore this step (probability epsilon each, one draw per environment) by uniform ones: the draws of the draw
+        specification, a pheromone among 3 whether the net has that head or not."""
+        obs = self._obs(obs)
+        ast = self._dev(agent_state, torch.float32)
+        step = self.step_counter
+        lead = obs.shape[:-3]
+        attached = self.inloop and env is not None and env is self._env and obs is env.obs
+        if attached and self._next_version == self.trainer.version:
+            rot, ph = env.next_rotation, env.next_pheromone  # what the observation kernel left for this observation
+            self.inloop_hits += 1
+        else:
+            if attached and self._handle_version != self.trainer.version and self._refresh_due(training):
+                self.refresh_inloop()
+            rot, ph = self.policy.act(obs.contiguous(), ast.contiguous(), env=env)
+        self._rot.copy_(rot.reshape(-1))
+        if ph is not None:
+            self._ph.copy_(ph.reshape(-1))
+        if training:
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
+                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
+                                                                 3, _p(self._rot), _p(self._ph), _p(self._explored),
+                                                                 _lib.stream(self.device)), "agent_select_actions")
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), (None if ph is None else self._ph.view(lead))
 
 
-class CollectAgent:
+class CollectAgent(_InLoopAgent):
     """The linear agent on the device: CollectAgent (agents/collect_agent.py:54-184) with its net (the one config 5
     runs: LinearPolicy), its replay memory, its epsilon-greedy step and its training step resident on the GPU.
 
@@ -220,56 +339,31 @@ class CollectAgent:
     agent_states rows, and the memory-less entries antsrl_agent_select_actions / antsrl_replay_record_*_plain (the
     memory agent's kernels, draw specification and stream tags).
 
-    `inloop=True` takes the actions from the observation kernel (LinearPolicy.attach: bfloat16 observations on the
-    cell-meta path) whenever the weights in the handle are the acting weights the observation was produced under, and
-    from the standalone kernel otherwise — the two kernels give the same actions bit for bit, so both settings give the
-    same actions, rings, weights and losses.  A training step changes layer2, so while the agent trains at every step
-    the in-loop actions of the step before are one update old and are not used: in-loop acting pays off for the steps
-    that do not train (below min_replay, training=False).  The handle's weights are refreshed
-    (antsrl_set_inloop_policy) lazily: at the first step that will not train after the acting weights changed."""
+    `inloop=True` (_InLoopAgent): a training step changes layer2, so while the agent trains at every step the in-loop
+    actions of the step before are one update old and are not used: in-loop acting pays off for the steps that do not
+    train (below min_replay, training=False), and the handle is refreshed at the first step that will not train after
+    the acting weights changed.
+
+    Reference lines (collect_agent.py): setup :75-98, initialize :100-102, train :105-148, update_replay_memory
+    :150-159, get_action :161-177 (the acting net is the target net: the shared layer1, the live layer2, the target
+    layer3), save_model :179-180 (the six-tensor state_dict under CollectModel's names: the
+    reference's CollectAgent.load_model loads it), load_model :182-184."""
 
     def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
                  learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
                  inloop: bool = False):
         assert rotations == 3 and pheromones == 3, "the linear net's heads are 3 wide (antsrl_policy_mlp)"
-        self.name = "collect_agent"
-        self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
-        self.learning_rate = learning_rate
-        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
-        self.update_target_every, self.seed, self.inloop = update_target_every, seed, inloop
-        self.trainer = self.replay_memory = self.generator = None
-        self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
-        self.inloop_hits = 0   # steps whose actions came from the observation kernel
-        self._lib = _lib.load()
+        super().__init__("collect_agent", epsilon, discount, rotations, pheromones, learning_rate, record_per_step,
+                         replay_size, minibatch, min_replay, update_target_every, seed, inloop=inloop)
 
-    # ---- the reference's surface ----------------------------------------------------------------------------------
     def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None) -> None:
         """CollectAgent.setup (:75-98) for every ant of the batch.  `explore_model`: a four-tensor ExploreModel state_dict
         file (ExploreAgent.save_model) whose layer1 and layer2 go under the collect heads (:84, the curriculum's second
         stage: layer1 stays frozen from here on); applied behind `trained_model`, layer3 stays as it is."""
-        env = _backend(api_or_env)
-        cfg = env.cfg
-        self.device = env.device
-        self.n_envs, self.n_ants_per_env, self.env_id_base = cfg.n_envs, cfg.n_ants, cfg.env_id_base
-        self.n_ants = cfg.n_envs * cfg.n_ants
-        self.observation_space = tuple(env.obs.shape[-3:])
-        self.agent_space, self.action_space = [2], [2]
-        self.n_features = int(np.prod(self.observation_space))
+        env = self._setup(api_or_env, [2])
         self.trainer = LinearTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
                                      update_target_every=self.update_target_every, seed=self.seed)
-        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_space,
-                                                self.action_space, device=self.device)
-        self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
-        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        self.generator = torch.Generator(device=self.device)
-        self.generator.manual_seed(self.seed)
-        self.step_counter = 0
-        self._action_step = 0
-        self._env = None            # the environment the in-loop policy is attached to
-        self._handle_version = -1   # trainer.version of the weights in its handle
-        self._next_version = -1     # ... of the weights its next_rotation / next_pheromone were produced under
         if trained_model is not None:
             self.load_model(trained_model)
         if explore_model is not None:
@@ -277,66 +371,10 @@ class CollectAgent:
         if self.inloop:
             self._attach(env)
 
-    def initialize(self, api_or_env) -> None:
-        """:100-102: every pheromone activation x 10."""
-        env = _backend(api_or_env)
-        c = env.cfg
-        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
-
-    @property
-    def policy(self):
-        return self.trainer.policy
-
-    def _dev(self, a, dtype):
-        t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
-        return t.to(device=self.device, dtype=dtype) if (t.device != self.device or t.dtype != dtype) else t
-
-    # ---- the in-loop policy's weights -----------------------------------------------------------------------------
-    def _attach(self, env) -> None:
-        self.policy.attach(env)  # allocates env.next_rotation / next_pheromone, copies the weights into the handle
-        self._env, self._handle_version, self._next_version = env, self.trainer.version, -1
-
-    def refresh_inloop(self) -> None:
-        """The acting weights into the handle again (antsrl_set_inloop_policy: a 38 KB device copy and the pack)."""
-        env, p = self._env, self.policy
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(p.w1), _p(p.b1), _p(p.w2), _p(p.b2),
-                                                          _p(p.w3), _p(p.b3), _p(env.next_rotation), _p(env.next_pheromone),
-                                                          _lib.stream(self.device)), "set_inloop_policy")
-        self._handle_version = self.trainer.version
-
-    def get_action(self, obs, agent_state, training: bool, env=None):
-        """:161-177 -> (rotation int8, pheromone int8), device tensors.  The target net (the shared layer1, the live
-        layer2, the target layer3) acts on the whole batch; with `training`, antsrl_agent_select_actions then replaces the
-        actions of the environments that explore this step (probability epsilon each, one draw per environment) by
-        uniform ones."""
-        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
-        ast = self._dev(agent_state, torch.float32)
-        step = self.step_counter
-        lead = obs.shape[:-3]
-        attached = self.inloop and env is not None and env is self._env and obs is env.obs
-        if attached and self._next_version == self.trainer.version:
-            self._rot.copy_(env.next_rotation.view(-1))  # what the observation kernel left for this observation
-            self._ph.copy_(env.next_pheromone.view(-1))
-            self.inloop_hits += 1
-        else:
-            # the handle gets the acting weights again only when the observation this step produces can use them: a
-            # step that trains moves layer2 behind that observation, and its in-loop actions are never taken
-            if attached and self._handle_version != self.trainer.version and not self._will_train(training):
-                self.refresh_inloop()
-            rot, ph = self.policy.act(obs.contiguous(), ast.contiguous(), env=env)
-            self._rot.copy_(rot.reshape(-1))
-            self._ph.copy_(ph.reshape(-1))
-        if training:
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
-                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
-                                                                 self.pheromones, _p(self._rot), _p(self._ph),
-                                                                 _p(self._explored), _lib.stream(self.device)),
-                           "agent_select_actions")
-        self._action_step = step
-        self.step_counter += 1
-        return self._rot.view(lead), self._ph.view(lead)
+    def _refresh_due(self, training: bool) -> bool:
+        """Only when the observation this step produces can use the weights: a step that trains moves layer2 behind
+        that observation, and its in-loop actions are never taken."""
+        return not self._will_train(training)
 
     def _will_train(self, training: bool) -> bool:
         """Whether train() at the end of the step that starts now will take a training step (it runs behind this step's
@@ -344,64 +382,8 @@ class CollectAgent:
         k = self.n_ants if self.record_per_step is None else self.record_per_step
         return bool(training) and min(self.replay_size, len(self.replay_memory) + k) >= self.min_replay
 
-    def _record_kw(self):
-        return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
-                    step=self._action_step, env_id_base=self.env_id_base, n_rot=self.rotations)
 
-    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
-        """:150-159, from arrays the caller kept (`states`: the observation as it was BEFORE the step).  actions = what
-        get_action returned; rotation + rotations // 2 is what is stored."""
-        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
-        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
-        rm = self.replay_memory
-        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), None,
-                      self._dev(actions[0], torch.int8).contiguous().view(-1),
-                      None if actions[1] is None else self._dev(actions[1], torch.int8).contiguous().view(-1),
-                      **self._record_kw())
-        if torch.is_tensor(done) or isinstance(done, np.ndarray):
-            done = self._dev(done, torch.uint8).contiguous().view(-1)
-        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(), None,
-                       self._dev(rewards, torch.float32).contiguous().view(-1), done)
-
-    def train(self, done: bool, step: int = 0):
-        """:105-148: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
-        device tensor.  `done` is a host bool (the target counter lives on the host)."""
-        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
-                                  generator=self.generator)
-
-    def save_model(self, file_name: str) -> None:
-        """:179-180: torch.save of the model's six-tensor state_dict under CollectModel's names (on the CPU): the
-        reference's CollectAgent.load_model loads it."""
-        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
-
-    def load_model(self, file_name: str) -> None:
-        """:182-184: model and target net from a state_dict file of the reference's."""
-        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
-
-    # ---- the fused loop -------------------------------------------------------------------------------------------
-    def rollout_step(self, env, training: bool = True):
-        """One step of main.py's loop on `env` (a BatchedAntsEnv holding a current observation): act, select, record_pre,
-        env.step_update, record_post, train.  Returns the loss (0 while the replay memory is below min_replay or when not
-        training, else a 0-d device tensor).  No host synchronisation."""
-        env = _backend(env)
-        obs, ast = env.obs, env.agent_state
-        assert obs.is_contiguous(), "LinearPolicy reads dense observation rows (obs_row_stride=None)"
-        rot, ph = self.get_action(obs, ast, training, env=env)
-        rm = self.replay_memory
-        rm.record_pre(obs, ast, None, rot.view(-1), ph.view(-1), **self._record_kw())
-        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
-        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), ph.view(env.cfg.n_envs, env.cfg.n_ants))
-        if env is self._env:
-            self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
-        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
-        return self.train(done, self._action_step) if training else 0
-
-    def run(self, env, steps: int, training: bool = True) -> list:
-        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
-        return [self.rollout_step(env, training) for _ in range(steps)]
-
-
-class ExploreAgent:
+class ExploreAgent(_InLoopAgent):
     """The explore agent on the device: ExploreAgentPytorch (agents/explore_agent_pytorch.py:48-165), the first stage of
     the curriculum whose second stage is CollectAgent (collect_agent.py:81-90 puts this net's layer1 under the collect
     heads and freezes it).  Rotation only: get_action returns (rotation, None), the environment is stepped without a
@@ -412,154 +394,33 @@ class ExploreAgent:
     CollectModel.forward's concat (collect_agent.py:47-49) and the DQN step every other agent has, both layers trained
     and the target net a full copy (`ExploreTrainer`, antsrl_exptrain.hip).
 
-    The surface and the fused loop are CollectAgent's.  `inloop=True` takes the actions from the observation kernel
-    whenever the handle holds the acting weights the observation was produced under.  The acting net is the target net,
-    which changes at a sync or a load only, so the handle is refreshed (antsrl_set_inloop_policy without a pheromone
-    head) at the first step after one of those and every other step is an in-loop hit, training or not."""
+    The surface and the fused loop are CollectAgent's.  `inloop=True` (_InLoopAgent): the acting net is the target net,
+    which changes at a sync or a load only, so the handle is refreshed (without a pheromone head) at the first step
+    after one of those and every other step is an in-loop hit, training or not.
+
+    Reference lines (explore_agent_pytorch.py): setup :69-85, initialize :87-88, train :90-133, update_replay_memory
+    :135-144, get_action :146-156, save_model :158-159 (the four-tensor state_dict under ExploreModel's names: the
+    reference's ExploreModel loads it, and CollectAgent.setup(explore_model=...) takes it as its frozen layer1),
+    load_model :162-164."""
 
     def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
                  learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 256, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
                  inloop: bool = False):
         assert rotations == 3, "the net's rotation head is 3 wide (antsrl_policy_mlp)"
-        self.name = "explore_agent_pytorch"
-        self.epsilon, self.discount, self.rotations, self.pheromones = epsilon, discount, rotations, pheromones
-        self.learning_rate = learning_rate
-        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
-        self.update_target_every, self.seed, self.inloop = update_target_every, seed, inloop
-        self.trainer = self.replay_memory = self.generator = None
-        self.step_counter = 0  # agent steps so far: the `step` key of the draw specification
-        self.inloop_hits = 0   # steps whose actions came from the observation kernel
-        self._lib = _lib.load()
+        super().__init__("explore_agent_pytorch", epsilon, discount, rotations, pheromones, learning_rate, record_per_step,
+                         replay_size, minibatch, min_replay, update_target_every, seed, inloop=inloop)
 
-    # ---- the reference's surface ----------------------------------------------------------------------------------
     def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
         """ExploreAgentPytorch.setup (:69-85) for every ant of the batch."""
-        env = _backend(api_or_env)
-        cfg = env.cfg
-        self.device = env.device
-        self.n_envs, self.n_ants_per_env, self.env_id_base = cfg.n_envs, cfg.n_ants, cfg.env_id_base
-        self.n_ants = cfg.n_envs * cfg.n_ants
-        self.observation_space = tuple(env.obs.shape[-3:])
-        self.agent_space, self.action_space = [2], [2]
-        self.n_features = int(np.prod(self.observation_space))
+        env = self._setup(api_or_env, [2])
         self.trainer = ExploreTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
                                       update_target_every=self.update_target_every, seed=self.seed)
-        self.replay_memory = DeviceReplayMemory(self.replay_size, self.observation_space, self.agent_space,
-                                                self.action_space, device=self.device)
-        self._explored = torch.zeros((self.n_envs,), dtype=torch.uint8, device=self.device)
-        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        # antsrl_agent_select_actions draws a pheromone for every exploring ant: it lands here and is never read
-        self._ph_scratch = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        self.generator = torch.Generator(device=self.device)
-        self.generator.manual_seed(self.seed)
-        self.step_counter = 0
-        self._action_step = 0
-        self._env = None            # the environment the in-loop policy is attached to
-        self._handle_version = -1   # trainer.version of the weights in its handle
-        self._next_version = -1     # ... of the weights its next_rotation was produced under
         if trained_model is not None:
             self.load_model(trained_model)
         if self.inloop:
-            self.policy.attach(env)  # allocates env.next_rotation, copies the weights into the handle
-            self._env, self._handle_version = env, self.trainer.version
+            self._attach(env)
 
-    def initialize(self, api_or_env) -> None:
-        """:87-88: every pheromone activation x 10."""
-        env = _backend(api_or_env)
-        c = env.cfg
-        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
-
-    @property
-    def policy(self):
-        return self.trainer.policy
-
-    _dev = CollectAgent._dev
-    _record_kw = CollectAgent._record_kw
-
-    def refresh_inloop(self) -> None:
-        """The acting weights (the target net) into the handle again: after a sync or a load."""
-        env, p = self._env, self.policy
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_set_inloop_policy(env._h, self.n_features, _p(p.w1), _p(p.b1), _p(p.w2), _p(p.b2),
-                                                          None, None, _p(env.next_rotation), None,
-                                                          _lib.stream(self.device)), "set_inloop_policy")
-        self._handle_version = self.trainer.version
-
-    def get_action(self, obs, agent_state, training: bool, env=None):
-        """:146-156 -> (rotation int8, None), rotation a device tensor.  The target net acts on the whole batch; with
-        `training`, antsrl_agent_select_actions then replaces the rotations of the environments that explore this step
-        (probability epsilon each, one draw per environment) by uniform ones: the draws of the draw specification."""
-        obs = obs if (torch.is_tensor(obs) and obs.dtype == torch.bfloat16) else self._dev(obs, torch.float32)
-        ast = self._dev(agent_state, torch.float32)
-        step = self.step_counter
-        lead = obs.shape[:-3]
-        attached = self.inloop and env is not None and env is self._env and obs is env.obs
-        if attached and self._next_version == self.trainer.version:
-            self._rot.copy_(env.next_rotation.view(-1))  # what the observation kernel left for this observation
-            self.inloop_hits += 1
-        else:
-            if attached and self._handle_version != self.trainer.version:
-                self.refresh_inloop()  # the observation this step produces is acted on with these weights
-            rot, _ = self.policy.act(obs.contiguous(), ast.contiguous(), env=env)
-            self._rot.copy_(rot.reshape(-1))
-        if training:
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
-                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
-                                                                 3, _p(self._rot), _p(self._ph_scratch),
-                                                                 _p(self._explored), _lib.stream(self.device)),
-                           "agent_select_actions")
-        self._action_step = step
-        self.step_counter += 1
-        return self._rot.view(lead), None
-
-    def update_replay_memory(self, states, agent_state, actions, rewards, new_states, new_agent_states, done) -> None:
-        """:135-144, from arrays the caller kept (`states`: the observation as it was BEFORE the step).  actions = what
-        get_action returned; (rotation + rotations // 2, 1) is what is stored (replay_memory.py:100-103)."""
-        st = states if (torch.is_tensor(states) and states.dtype == torch.bfloat16) else self._dev(states, torch.float32)
-        nst = new_states if (torch.is_tensor(new_states) and new_states.dtype == torch.bfloat16) else self._dev(new_states, torch.float32)
-        rm = self.replay_memory
-        rm.record_pre(st.contiguous(), self._dev(agent_state, torch.float32).contiguous(), None,
-                      self._dev(actions[0], torch.int8).contiguous().view(-1), None, **self._record_kw())
-        if torch.is_tensor(done) or isinstance(done, np.ndarray):
-            done = self._dev(done, torch.uint8).contiguous().view(-1)
-        rm.record_post(nst.contiguous(), self._dev(new_agent_states, torch.float32).contiguous(), None,
-                       self._dev(rewards, torch.float32).contiguous().view(-1), done)
-
-    def train(self, done: bool, step: int = 0):
-        """:90-133: 0 below min_replay, else one step on `minibatch` rows drawn on the device; the loss stays a 0-d
-        device tensor.  `done` is a host bool (the target counter lives on the host)."""
-        return self.trainer.train(self.replay_memory, bool(done), minibatch=self.minibatch, min_replay=self.min_replay,
-                                  generator=self.generator)
-
-    def save_model(self, file_name: str) -> None:
-        """:158-159: torch.save of the model's four-tensor state_dict under ExploreModel's names (on the CPU): the
-        reference's ExploreModel loads it, and CollectAgent.setup(explore_model=...) takes it as its frozen layer1."""
-        torch.save({k: v.cpu() for k, v in self.trainer.state_dict().items()}, file_name)
-
-    def load_model(self, file_name: str) -> None:
-        """:162-164: model and target net from a state_dict file."""
-        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
-
-    # ---- the fused loop -------------------------------------------------------------------------------------------
-    def rollout_step(self, env, training: bool = True):
-        """One step of main.py's loop on `env` (a BatchedAntsEnv holding a current observation): act, select, record_pre,
-        env.step_update without a pheromone action, record_post, train.  Returns the loss (0 while the replay memory is
-        below min_replay or when not training, else a 0-d device tensor).  No host synchronisation."""
-        env = _backend(env)
-        obs, ast = env.obs, env.agent_state
-        assert obs.is_contiguous(), "LinearPolicy reads dense observation rows (obs_row_stride=None)"
-        rot, _ = self.get_action(obs, ast, training, env=env)
-        rm = self.replay_memory
-        rm.record_pre(obs, ast, None, rot.view(-1), None, **self._record_kw())
-        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
-        env.step_update(rot.view(env.cfg.n_envs, env.cfg.n_ants), None)
-        if env is self._env:
-            self._next_version = self._handle_version  # (a stale handle's actions are never equal to trainer.version)
-        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
-        return self.train(done, self._action_step) if training else 0
-
-    def run(self, env, steps: int, training: bool = True) -> list:
-        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
-        return [self.rollout_step(env, training) for _ in range(steps)]
+    def _refresh_due(self, training: bool) -> bool:
+        """Always: the observation this step produces is acted on with these weights."""
+        return True

@@ -1,5 +1,5 @@
 // antsrl_exptrain.h — the on-device DQN training step of ExploreModel (antsrl_exptrain.hip), shared with its C-ABI
-// entries (antsrl_expapi.hip).  The net is agents/explore_agent_pytorch.py:24-45 with the concat of
+// entries (antsrl_linapi.hip).  The net is agents/explore_agent_pytorch.py:24-45 with the concat of
 // agents/collect_agent.py:47-49: layer1 [32][F + 2] and layer2 [3][32], BOTH trained; the target net is a full copy.
 //
 // A net is ONE flat fp32 block of P = 32 (F + 2) + 32 + 96 + 3 floats in the state_dict's order:
@@ -14,9 +14,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_adam.h"
+#include "antsrl_dqn.h"
 #include "antsrl_fail.h"
 
-#define ET_HIDDEN 32
+#define ET_HIDDEN DQN_HIDDEN
 #define ET_L2 99            // floats of layer2: w2 [3][32], b2 [3]
 #define ET_OUT 100          // what the forward stage sums over rows: layer2's 99 gradients and the loss
 #define ET_PART 104         // floats per workgroup in the partials (ET_OUT rounded up to 16 bytes)
@@ -26,21 +28,12 @@
 #define ET_SLAB 8           // columns of layer1 one workgroup of the layer1 stage owns
 
 struct ExpTrainArgs {
-    const float *states, *agent_states, *rewards, *new_states, *new_agent_states;
-    const int64_t *actions, *idx; // actions [N][2]; idx [B] or NULL (rows 0 .. B - 1)
-    const uint8_t *dones;
+    DqnBatch batch;           // grads: P floats; partials: [workgroups of the forward stage][ET_PART]
     float *model;             // P floats: read by the forward, written by Adam
     const float *target;      // P floats, only read
-    float *m, *v;             // Adam's moments, P floats each (adam only)
-    float *grads;             // P floats, or NULL
-    float *loss;              // one float
-    float *partials;          // workspace: [workgroups of the forward stage][ET_PART]
     float *dh;                // workspace: [B][32]
-    long long n_rows;         // rows of the replay arrays: idx is clamped to [0, n_rows)
-    int B, F, ksteps, ntiles, blocks; // blocks: workgroups of the forward stage
-    float discount, dq_scale /* 2 / (3 B) */, loss_scale /* 1 / (3 B) */;
-    int adam;                 // 0: gradients and loss only
-    float step_size, bc2_sqrt, w1m, beta2, w2m, eps;
+    int blocks;               // workgroups of the forward stage
+    AdamArgs adam;            // m, v: P floats each
 };
 
 static inline size_t antsrl_exptrain_floats(int F) { return (size_t)ET_HIDDEN * (F + 2) + ET_HIDDEN + ET_L2; }
@@ -50,5 +43,3 @@ static inline size_t antsrl_exptrain_dh_offset(int B) { return ((size_t)antsrl_e
 
 // the forward stage and the layer1 stage: two launches
 ANTSRL_INTERNAL hipError_t antsrl_launch_exptrain(const ExpTrainArgs &a, hipStream_t st);
-// Adam alone on all P floats from a.grads (a.model, a.m, a.v, a.F and the Adam scalars are read)
-ANTSRL_INTERNAL hipError_t antsrl_launch_exptrain_apply(const ExpTrainArgs &a, hipStream_t st);

@@ -25,13 +25,9 @@
 // No atomics anywhere and every order above is fixed: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_adam.h"
+#include "antsrl_dqn_dev.h"
 #include "antsrl_exptrain.h"
 #include "antsrl_lds_optin.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-struct __attribute__((packed, aligned(4))) EtF4 { float v[4]; }; // 4-byte aligned 16-byte load (rows with F % 4 != 0)
 
 #define ET_HSTRIDE 33 // floats per row of a wave's h tile: 32 hidden values and the 1.0 of b2
 #define ET_DSTRIDE 4  // floats per row of its dq tile: 3 dq, the loss term
@@ -39,78 +35,13 @@ struct __attribute__((packed, aligned(4))) EtF4 { float v[4]; }; // 4-byte align
 #define ET_TILE (32 * ET_HSTRIDE + 32 * ET_DSTRIDE)
 #define ET_UNROLL 8   // rows per wave in flight in stage 2
 
-__device__ __forceinline__ void et_wave_sync()
-{
-    // LDS hand-off inside one wave: its LDS instructions execute in order, only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ float et_bf16(const float x) { return (float)(__bf16)x; }
-
-// 8 consecutive inputs k0 .. k0 + 7 of a row as a bf16 fragment; inputs at or beyond F are zero and never read
-__device__ __forceinline__ bf16x8 et_frag(const float *__restrict__ row, const int k0, const int F, const bool whole)
-{
-    bf16x8 b;
-    if (whole) {
-        const EtF4 lo = *reinterpret_cast<const EtF4 *>(row + k0), hi = *reinterpret_cast<const EtF4 *>(row + k0 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            b[j] = (__bf16)lo.v[j];
-            b[4 + j] = (__bf16)hi.v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = row[min(k0 + j, F - 1)]; // unconditional on a clamped address, then a select
-            b[j] = (__bf16)(k0 + j < F ? x : 0.0f);
-        }
-    }
-    return b;
-}
-
-// layer2's three outputs for this lane's row: the lane's 16 hidden values against its part of the weights, the other
-// half-wave's part added, then the bias.  w: [3][32] + [3] in LDS
-__device__ __forceinline__ void et_head(const float *w, const float (&hv)[16], const int h, float (&q)[3])
-{
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        float p = 0.0f;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 ww = *reinterpret_cast<const float4 *>(w + o * ET_HIDDEN + 8 * g4 + 4 * h);
-            p += ww.x * hv[4 * g4];
-            p += ww.y * hv[4 * g4 + 1];
-            p += ww.z * hv[4 * g4 + 2];
-            p += ww.w * hv[4 * g4 + 3];
-        }
-        q[o] = (p + __shfl_xor(p, 32)) + w[3 * ET_HIDDEN + o];
-    }
-}
-
-// the replay row of minibatch row b (b < B), never outside the replay arrays
-__device__ __forceinline__ long long et_row(const ExpTrainArgs &a, const int b)
-{
-    const long long ri = a.idx ? a.idx[b] : (long long)b;
-    return ri < 0 ? 0 : (ri >= a.n_rows ? a.n_rows - 1 : ri);
-}
-
-// gradient p of the block is `total`: stored, and Adam on trained float p
-__device__ __forceinline__ void et_epilogue(const ExpTrainArgs &a, const size_t p, const float total)
-{
-    if (a.grads) a.grads[p] = total;
-    if (a.adam) {
-        float mm = a.m[p], vv = a.v[p];
-        a.model[p] = adam_element(a.model[p], total, mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
-        a.m[p] = mm;
-        a.v[p] = vv;
-    }
-}
 
 __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int F = a.F, IN = F + 2, ksteps = a.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
+    const DqnBatch &mb = a.batch;
+    const int F = mb.F, IN = F + 2, ksteps = mb.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
     __bf16 *w1s = reinterpret_cast<__bf16 *>(smem);                  // [2][32][KP]: the model's W1, the target's
     float *hw = reinterpret_cast<float *>(smem + (size_t)2 * ET_HIDDEN * KP * 2); // 2 slots of ET_SLOT: layer2 of the model, of the target
     float *l1x = hw + 2 * ET_SLOT;                                   // [2][3][32]: b1 and the bf16-rounded W1 columns F, F + 1
@@ -122,11 +53,7 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
 
     for (int net = 0; net < 2; ++net) {
         const float *blk = net ? a.target : a.model;
-        for (int row = wib; row < ET_HIDDEN; row += ET_WAVES) // W1's observation columns -> bf16
-            for (int k = lane; k < 16 * ksteps; k += 64) {
-                const float wv = blk[(size_t)row * IN + min(k, F - 1)];
-                w1s[(net * ET_HIDDEN + row) * KP + k] = (__bf16)(k < F ? wv : 0.0f);
-            }
+        dqn_stage_w1(blk, w1s + net * ET_HIDDEN * KP, F, ksteps, KP, wib, ET_WAVES, lane);
         for (int i = threadIdx.x; i < ET_L2; i += 64 * ET_WAVES) hw[net * ET_SLOT + i] = blk[ol2 + i];
         if (threadIdx.x < ET_HIDDEN) {
             const int hid = threadIdx.x;
@@ -149,33 +76,33 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
     }
 
     const int t = blockIdx.x * ET_WAVES + wib; // this wave's tile
-    if (t < a.ntiles) {
+    if (t < mb.ntiles) {
         const __bf16 *wrow = w1s + r * KP + 8 * h, *wrow_t = wrow + ET_HIDDEN * KP;
         const int nwhole = F / 16; // k-steps whose 16 inputs all lie inside the row
         const int brow = t * 32 + r;
-        const bool valid = brow < a.B;
-        const long long ri = et_row(a, min(brow, a.B - 1));
-        const float *xs = a.states + (size_t)ri * F, *xn = a.new_states + (size_t)ri * F;
+        const bool valid = brow < mb.B;
+        const long long ri = dqn_row(mb, min(brow, mb.B - 1));
+        const float *xs = mb.states + (size_t)ri * F, *xn = mb.new_states + (size_t)ri * F;
         f32x16 acc, accn;
 #pragma unroll
         for (int g = 0; g < 16; ++g) acc[g] = accn[g] = 0.0f;
         int s = 0;
 #pragma unroll 1
         for (; s < nwhole; ++s) {
-            const bf16x8 bs = et_frag(xs, 16 * s + 8 * h, F, true), bn = et_frag(xn, 16 * s + 8 * h, F, true);
+            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, true), bn = dqn_frag(xn, 16 * s + 8 * h, F, true);
             const bf16x8 am = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s), at = *reinterpret_cast<const bf16x8 *>(wrow_t + 16 * s);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bs, acc, 0, 0, 0);
             accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, bn, accn, 0, 0, 0);
         }
 #pragma unroll 1
         for (; s < ksteps; ++s) {
-            const bf16x8 bs = et_frag(xs, 16 * s + 8 * h, F, false), bn = et_frag(xn, 16 * s + 8 * h, F, false);
+            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, false), bn = dqn_frag(xn, 16 * s + 8 * h, F, false);
             const bf16x8 am = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s), at = *reinterpret_cast<const bf16x8 *>(wrow_t + 16 * s);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bs, acc, 0, 0, 0);
             accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(at, bn, accn, 0, 0, 0);
         }
-        const float as0 = et_bf16(a.agent_states[(size_t)ri * 2]), as1 = et_bf16(a.agent_states[(size_t)ri * 2 + 1]);
-        const float an0 = et_bf16(a.new_agent_states[(size_t)ri * 2]), an1 = et_bf16(a.new_agent_states[(size_t)ri * 2 + 1]);
+        const float as0 = et_bf16(mb.agent_states[(size_t)ri * 2]), as1 = et_bf16(mb.agent_states[(size_t)ri * 2 + 1]);
+        const float an0 = et_bf16(mb.new_agent_states[(size_t)ri * 2]), an1 = et_bf16(mb.new_agent_states[(size_t)ri * 2 + 1]);
         float hv[16], hn[16];
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) { // accumulator register g = 4 g4 + j of half-wave h is hidden value 8 g4 + 4 h + j
@@ -189,29 +116,29 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
             const float bm[4] = {bb.x, bb.y, bb.z, bb.w}, m0[4] = {c0.x, c0.y, c0.z, c0.w}, m1[4] = {c1.x, c1.y, c1.z, c1.w};
             const float bt[4] = {tb.x, tb.y, tb.z, tb.w}, u0[4] = {t0.x, t0.y, t0.z, t0.w}, u1[4] = {t1.x, t1.y, t1.z, t1.w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { // k_policy_flat's expression
-                hv[4 * g4 + j] = acc[4 * g4 + j] + (as0 * m0[j] + as1 * m1[j]) + bm[j];
-                hn[4 * g4 + j] = accn[4 * g4 + j] + (an0 * u0[j] + an1 * u1[j]) + bt[j];
+            for (int j = 0; j < 4; ++j) {
+                hv[4 * g4 + j] = dqn_hidden(acc[4 * g4 + j], as0, m0[j], as1, m1[j], bm[j]);
+                hn[4 * g4 + j] = dqn_hidden(accn[4 * g4 + j], an0, u0[j], an1, u1[j], bt[j]);
             }
         }
         float q[3], qn[3];
         __builtin_amdgcn_sched_barrier(0); // (the weight vectors of both heads are not all hoisted in front of the first product)
-        et_head(hw, hv, h, q);             // the model's layer2 on h
+        dqn_head(hw, hv, h, q);             // the model's layer2 on h
         __builtin_amdgcn_sched_barrier(0);
-        et_head(hw + ET_SLOT, hn, h, qn);  // the target's on h'
+        dqn_head(hw + ET_SLOT, hn, h, qn);  // the target's on h'
         __builtin_amdgcn_sched_barrier(0);
-        const long long a64 = a.actions[(size_t)ri * 2];
+        const long long a64 = mb.actions[(size_t)ri * 2];
         const int act = a64 < 0 ? 0 : (a64 > 2 ? 2 : (int)a64);
-        const float live = a.dones[ri] ? 0.0f : 1.0f;
-        const float y = a.rewards[ri] + a.discount * fmaxf(fmaxf(qn[0], qn[1]), qn[2]) * live;
+        const float live = mb.dones[ri] ? 0.0f : 1.0f;
+        const float y = mb.rewards[ri] + mb.discount * fmaxf(fmaxf(qn[0], qn[1]), qn[2]) * live;
         const float d = (act == 0 ? q[0] : act == 1 ? q[1] : q[2]) - y;
-        const float gq = valid ? d * a.dq_scale : 0.0f;
+        const float gq = valid ? d * mb.dq_scale : 0.0f;
 #pragma unroll
         for (int g = 0; g < 16; ++g) ht[r * ET_HSTRIDE + (g & 3) + 8 * (g >> 2) + 4 * h] = hv[g];
         if (h == 0) {
 #pragma unroll
             for (int o = 0; o < 3; ++o) dqs[r * ET_DSTRIDE + o] = act == o ? gq : 0.0f;
-            dqs[r * ET_DSTRIDE + 3] = valid ? d * d * a.loss_scale : 0.0f;
+            dqs[r * ET_DSTRIDE + 3] = valid ? d * d * mb.loss_scale : 0.0f;
         }
         if (valid) { // dh = dq * w2[a]: the lane's 16 hidden units, four at a time
             float *dst = a.dh + (size_t)brow * ET_HIDDEN;
@@ -221,7 +148,7 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
                 *reinterpret_cast<float4 *>(dst + 8 * g4 + 4 * h) = make_float4(gq * ww.x, gq * ww.y, gq * ww.z, gq * ww.w);
             }
         }
-        et_wave_sync();
+        dqn_wave_sync();
 #pragma unroll 4
         for (int rr = 0; rr < 32; ++rr) {
 #pragma unroll
@@ -236,16 +163,16 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
         float s = 0.0f;
 #pragma unroll
         for (int w = 0; w < ET_WAVES; ++w) s += wpart[w * ET_PART + threadIdx.x];
-        a.partials[(size_t)blockIdx.x * ET_PART + threadIdx.x] = s;
+        mb.partials[(size_t)blockIdx.x * ET_PART + threadIdx.x] = s;
     }
 }
 
 // columns k0 .. k0 + 3 of xe[b] = bf16(states[ri]) ++ bf16(agent_states[ri]) ++ 1 (zero beyond)
-__device__ __forceinline__ void et_cols(const ExpTrainArgs &a, const long long ri, const int k0, float (&x)[4])
+__device__ __forceinline__ void et_cols(const DqnBatch &a, const long long ri, const int k0, float (&x)[4])
 {
     const int F = a.F;
     if (k0 + 3 < F) {
-        const EtF4 v = *reinterpret_cast<const EtF4 *>(a.states + (size_t)ri * F + k0);
+        const DqnF4 v = *reinterpret_cast<const DqnF4 *>(a.states + (size_t)ri * F + k0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = et_bf16(v.v[i]);
     } else {
@@ -262,30 +189,31 @@ __device__ __forceinline__ void et_cols(const ExpTrainArgs &a, const long long r
 __global__ void __launch_bounds__(64 * ET_L1_WAVES) k_exptrain_l1(const ExpTrainArgs a, const int nslabs)
 {
     __shared__ float red[ET_L1_WAVES * ET_HIDDEN * ET_SLAB];
-    const int F = a.F, IN = F + 2;
+    const DqnBatch &mb = a.batch;
+    const int F = mb.F, IN = F + 2;
     if ((int)blockIdx.x == nslabs) { // layer2 and the loss: stage 1's partials in workgroup order
         if (threadIdx.x >= ET_OUT) return;
         float s = 0.0f;
-        for (int b = 0; b < a.blocks; ++b) s += a.partials[(size_t)b * ET_PART + threadIdx.x];
-        if (threadIdx.x == ET_L2) *a.loss = s;
-        else et_epilogue(a, (size_t)ET_HIDDEN * IN + ET_HIDDEN + threadIdx.x, s);
+        for (int b = 0; b < a.blocks; ++b) s += mb.partials[(size_t)b * ET_PART + threadIdx.x];
+        if (threadIdx.x == ET_L2) *mb.loss = s;
+        else dqn_store_adam(a.model, mb.grads, a.adam, (size_t)ET_HIDDEN * IN + ET_HIDDEN + threadIdx.x, s);
         return;
     }
     const int lane = threadIdx.x & 63, j = lane & 31, c = lane >> 5, wib = threadIdx.x >> 6;
     const int k0 = blockIdx.x * ET_SLAB + 4 * c;
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 1
-    for (int b0 = wib; b0 < a.B; b0 += ET_L1_WAVES * ET_UNROLL) {
+    for (int b0 = wib; b0 < mb.B; b0 += ET_L1_WAVES * ET_UNROLL) {
         float d[ET_UNROLL], x[ET_UNROLL][4];
 #pragma unroll
         for (int u = 0; u < ET_UNROLL; ++u) { // the loads of ET_UNROLL rows first: they do not depend on one another
-            const int b = min(b0 + ET_L1_WAVES * u, a.B - 1);
+            const int b = min(b0 + ET_L1_WAVES * u, mb.B - 1);
             d[u] = a.dh[(size_t)b * ET_HIDDEN + j];
-            et_cols(a, et_row(a, b), k0, x[u]);
+            et_cols(mb, dqn_row(mb, b), k0, x[u]);
         }
 #pragma unroll
         for (int u = 0; u < ET_UNROLL; ++u)
-            if (b0 + ET_L1_WAVES * u < a.B) { // (uniform in the wave)
+            if (b0 + ET_L1_WAVES * u < mb.B) { // (uniform in the wave)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[i] = fmaf(d[u], x[u][i], acc[i]);
             }
@@ -298,18 +226,8 @@ __global__ void __launch_bounds__(64 * ET_L1_WAVES) k_exptrain_l1(const ExpTrain
     float s = red[jj * ET_SLAB + col];
 #pragma unroll
     for (int w = 1; w < ET_L1_WAVES; ++w) s += red[(w * ET_HIDDEN + jj) * ET_SLAB + col];
-    if (k < IN) et_epilogue(a, (size_t)jj * IN + k, s);
-    else if (k == IN) et_epilogue(a, (size_t)ET_HIDDEN * IN + jj, s);
-}
-
-__global__ void __launch_bounds__(256) k_exptrain_apply(const ExpTrainArgs a, const int P)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    float mm = a.m[p], vv = a.v[p];
-    a.model[p] = adam_element(a.model[p], a.grads[p], mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
-    a.m[p] = mm;
-    a.v[p] = vv;
+    if (k < IN) dqn_store_adam(a.model, mb.grads, a.adam, (size_t)jj * IN + k, s);
+    else if (k == IN) dqn_store_adam(a.model, mb.grads, a.adam, (size_t)ET_HIDDEN * IN + jj, s);
 }
 
 static size_t et_lds(int ksteps)
@@ -320,19 +238,12 @@ static size_t et_lds(int ksteps)
 
 hipError_t antsrl_launch_exptrain(const ExpTrainArgs &a, hipStream_t st)
 {
-    const size_t lds = et_lds(a.ksteps); // 61 KB at F = 294, 151 KB at the widest rows: above 64 KiB it is an opt-in per device
+    const size_t lds = et_lds(a.batch.ksteps); // 61 KB at F = 294, 151 KB at the widest rows: above 64 KiB it is an opt-in per device
     hipError_t e = antsrl_lds_optin<k_exptrain_fwd>(lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_exptrain_fwd, dim3(a.blocks), dim3(64 * ET_WAVES), lds, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    const int nslabs = (a.F + 3 + ET_SLAB - 1) / ET_SLAB;
+    const int nslabs = (a.batch.F + 3 + ET_SLAB - 1) / ET_SLAB;
     hipLaunchKernelGGL(k_exptrain_l1, dim3(nslabs + 1), dim3(64 * ET_L1_WAVES), 0, st, a, nslabs);
-    return hipGetLastError();
-}
-
-hipError_t antsrl_launch_exptrain_apply(const ExpTrainArgs &a, hipStream_t st)
-{
-    const int P = (int)antsrl_exptrain_floats(a.F);
-    hipLaunchKernelGGL(k_exptrain_apply, dim3((P + 255) / 256), dim3(256), 0, st, a, P);
     return hipGetLastError();
 }

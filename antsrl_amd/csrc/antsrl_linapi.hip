@@ -1,15 +1,18 @@
 // antsrl_linapi.hip — the linear agent's training step in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The linear
 // agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels, and
 // behind them the explore agent's ("The explore agent's training step"): antsrl_exptrain_sizes / _grad / _apply / _step
-// in front of antsrl_exptrain.hip's, with the same argument rules.
+// in front of antsrl_exptrain.hip's, with the same argument rules.  dqn_batch checks and fills what both steps take from
+// the replay arrays (DqnBatch, antsrl_dqn.h), antsrl_adam_args (antsrl_adam.h) Adam's part; an entry checks its own
+// net's pointers, its limit on B and its workspace rule.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 
+#include "antsrl_adam.h"
 #include "antsrl_device.h"
+#include "antsrl_dqn.h"
 #include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
 #include "antsrl_lintrain.h"
@@ -29,36 +32,54 @@ static int lt_B(const char *who, int64_t B)
     return ANTSRL_OK;
 }
 
+static int et_B(const char *who, int64_t B)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > ET_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, ET_MAX_B);
+    return ANTSRL_OK;
+}
+
 #define LT_REQUIRE(p, align)                                                                                             \
     do {                                                                                                                 \
         if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                                          \
         if ((uintptr_t)(p) & ((align) - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
     } while (0)
 
-struct LtAdam {
-    int64_t step;
-    double lr, beta1, beta2, eps;
-};
-
-template <class Args> // LinTrainArgs or ExpTrainArgs
-static int lt_adam(const char *who, const LtAdam &o, Args *a)
+// the minibatch of a gradient stage or a fused step, for n_features and B its entry has checked; workspace (checked by
+// the entry's own rule) becomes the partials
+static int dqn_batch(const char *who, int32_t n_features, const float *states, const float *agent_states,
+                     const int64_t *actions, const float *rewards, const float *new_states, const float *new_agent_states,
+                     const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads,
+                     bool grads_required, float *loss, void *workspace, DqnBatch *q)
 {
-    if (o.step < 1) return fail(ANTSRL_E_INVALID, "%s: step must be >= 1", who);
-    if (!(o.lr >= 0.0) || !(o.lr < 1e30)) return fail(ANTSRL_E_INVALID, "%s: lr must be finite and >= 0", who);
-    if (!(o.beta1 >= 0.0 && o.beta1 < 1.0) || !(o.beta2 >= 0.0 && o.beta2 < 1.0))
-        return fail(ANTSRL_E_INVALID, "%s: beta1, beta2 must be in [0, 1)", who);
-    if (!(o.eps > 0.0) || !(o.eps < 1e30)) return fail(ANTSRL_E_INVALID, "%s: eps must be finite and > 0", who);
-    // torch.optim.Adam (single tensor): the bias corrections in double, then every scalar rounded to float by the op
-    const double bc1 = 1.0 - pow(o.beta1, (double)o.step), bc2 = 1.0 - pow(o.beta2, (double)o.step);
-    a->adam = 1;
-    a->step_size = (float)(o.lr / bc1);
-    a->bc2_sqrt = (float)pow(bc2, 0.5);
-    a->w1m = (float)(1.0 - o.beta1);
-    a->beta2 = (float)o.beta2;
-    a->w2m = (float)(1.0 - o.beta2);
-    a->eps = (float)o.eps;
+    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
+    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
+    LT_REQUIRE(states, 4);
+    LT_REQUIRE(agent_states, 4);
+    LT_REQUIRE(actions, 8);
+    LT_REQUIRE(rewards, 4);
+    LT_REQUIRE(new_states, 4);
+    LT_REQUIRE(new_agent_states, 4);
+    LT_REQUIRE(dones, 1);
+    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
+    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
+    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
+    LT_REQUIRE(loss, 4);
+    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
+    q->states = states; q->agent_states = agent_states; q->rewards = rewards; q->new_states = new_states;
+    q->new_agent_states = new_agent_states; q->actions = actions; q->idx = idx; q->dones = dones;
+    q->grads = grads; q->loss = loss; q->partials = (float *)workspace;
+    q->n_rows = n_rows;
+    q->B = (int)B; q->F = n_features; q->ksteps = (n_features + 15) / 16; q->ntiles = ((int)B + 31) / 32;
+    q->discount = discount;
+    q->dq_scale = (float)(2.0 / (3.0 * (double)B));
+    q->loss_scale = (float)(1.0 / (3.0 * (double)B));
     return ANTSRL_OK;
 }
+
+static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
+
+// ---- the linear agent's training step (antsrl_lintrain.hip) ---------------------------------------------------------------
 
 extern "C" int antsrl_lintrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
                                      int32_t *launches)
@@ -74,44 +95,19 @@ extern "C" int antsrl_lintrain_sizes(int32_t n_features, int64_t B, size_t *trai
     return ANTSRL_OK;
 }
 
-// the arguments the gradient stage and the fused step share
-static int lt_batch(const char *who, int32_t n_features, const float *w1, const float *b1, float *heads,
-                    const float *target_l3, const float *states, const float *agent_states, const int64_t *actions,
-                    const float *rewards, const float *new_states, const float *new_agent_states, const uint8_t *dones,
-                    int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, bool grads_required,
-                    float *loss, void *workspace, LinTrainArgs *a)
+// the net and the workspace of the gradient stage and the fused step
+static int lt_net(const char *who, int32_t n_features, int64_t B, const float *w1, const float *b1, float *heads,
+                  const float *target_l3, void *workspace, LinTrainArgs *a)
 {
     int rc = lt_features(who, n_features);
     if (rc == ANTSRL_OK) rc = lt_B(who, B);
     if (rc != ANTSRL_OK) return rc;
-    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
-    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
     LT_REQUIRE(w1, 4);
     LT_REQUIRE(b1, 4);
     LT_REQUIRE(heads, 4);
     LT_REQUIRE(target_l3, 4);
-    LT_REQUIRE(states, 4);
-    LT_REQUIRE(agent_states, 4);
-    LT_REQUIRE(actions, 8);
-    LT_REQUIRE(rewards, 4);
-    LT_REQUIRE(new_states, 4);
-    LT_REQUIRE(new_agent_states, 4);
-    LT_REQUIRE(dones, 1);
-    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
-    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
-    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
-    LT_REQUIRE(loss, 4);
     if (antsrl_lintrain_blocks((int)B, n_features) > 1) LT_REQUIRE(workspace, 256);
-    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
-    a->states = states; a->agent_states = agent_states; a->rewards = rewards; a->new_states = new_states;
-    a->new_agent_states = new_agent_states; a->actions = actions; a->idx = idx; a->dones = dones;
     a->w1 = w1; a->b1 = b1; a->heads = heads; a->target_l3 = target_l3;
-    a->grads = grads; a->loss = loss; a->partials = (float *)workspace;
-    a->n_rows = n_rows;
-    a->B = (int)B; a->F = n_features; a->ksteps = (n_features + 15) / 16; a->ntiles = ((int)B + 31) / 32;
-    a->discount = discount;
-    a->dq_scale = (float)(2.0 / (3.0 * (double)B));
-    a->loss_scale = (float)(1.0 / (3.0 * (double)B));
     return ANTSRL_OK;
 }
 
@@ -123,12 +119,12 @@ extern "C" int antsrl_lintrain_grad(int32_t n_features, const float *w1, const f
 {
     const char *who = "lintrain_grad";
     LinTrainArgs a = {};
-    const int rc = lt_batch(who, n_features, w1, b1, const_cast<float *>(heads), target_l3, states, agent_states, actions,
-                            rewards, new_states, new_agent_states, dones, n_rows, idx, B, discount, grads, true, loss,
-                            workspace, &a);
+    int rc = lt_net(who, n_features, B, w1, b1, const_cast<float *>(heads), target_l3, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, true, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
-    const hipError_t e = antsrl_launch_lintrain(a, (hipStream_t)stream); // a.adam == 0: heads is only read
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    return enqueued(antsrl_launch_lintrain(a, (hipStream_t)stream), who); // a.adam.on == 0: heads is only read
 }
 
 extern "C" int antsrl_lintrain_apply(float *heads, float *adam_m, float *adam_v, const float *grads, int64_t step, double lr,
@@ -139,12 +135,11 @@ extern "C" int antsrl_lintrain_apply(float *heads, float *adam_m, float *adam_v,
     LT_REQUIRE(adam_m, 4);
     LT_REQUIRE(adam_v, 4);
     LT_REQUIRE(grads, 4);
-    LinTrainArgs a = {};
-    const int rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a);
+    AdamArgs o = {};
+    const int rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o);
     if (rc != ANTSRL_OK) return rc;
-    a.heads = heads; a.m = adam_m; a.v = adam_v; a.grads = const_cast<float *>(grads);
-    const hipError_t e = antsrl_launch_lintrain_apply(a, (hipStream_t)stream);
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    o.m = adam_m; o.v = adam_v;
+    return enqueued(antsrl_launch_adam(heads, o, grads, LT_HEADS, (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const float *b1, float *heads,
@@ -157,25 +152,19 @@ extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const f
 {
     const char *who = "lintrain_step";
     LinTrainArgs a = {};
-    int rc = lt_batch(who, n_features, w1, b1, heads, target_l3, states, agent_states, actions, rewards, new_states,
-                      new_agent_states, dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
+    int rc = lt_net(who, n_features, B, w1, b1, heads, target_l3, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, false, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
     LT_REQUIRE(adam_m, 4);
     LT_REQUIRE(adam_v, 4);
-    if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
-    a.m = adam_m; a.v = adam_v;
-    const hipError_t e = antsrl_launch_lintrain(a, (hipStream_t)stream);
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    return enqueued(antsrl_launch_lintrain(a, (hipStream_t)stream), who);
 }
 
 // ---- the explore agent's training step (antsrl_exptrain.hip) ------------------------------------------------------------
-
-static int et_B(const char *who, int64_t B)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > ET_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, ET_MAX_B);
-    return ANTSRL_OK;
-}
 
 extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
                                      int32_t *launches)
@@ -190,44 +179,19 @@ extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trai
     return ANTSRL_OK;
 }
 
-// the arguments the gradient stage and the fused step share
-static int et_batch(const char *who, int32_t n_features, float *model, const float *target, const float *states,
-                    const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
-                    const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
-                    float discount, float *grads, bool grads_required, float *loss, void *workspace, ExpTrainArgs *a)
+// the nets and the workspace of the gradient stage and the fused step
+static int et_net(const char *who, int32_t n_features, int64_t B, float *model, const float *target, void *workspace,
+                  ExpTrainArgs *a)
 {
     int rc = lt_features(who, n_features);
     if (rc == ANTSRL_OK) rc = et_B(who, B);
     if (rc != ANTSRL_OK) return rc;
-    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
-    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
     LT_REQUIRE(model, 4);
     LT_REQUIRE(target, 4);
-    LT_REQUIRE(states, 4);
-    LT_REQUIRE(agent_states, 4);
-    LT_REQUIRE(actions, 8);
-    LT_REQUIRE(rewards, 4);
-    LT_REQUIRE(new_states, 4);
-    LT_REQUIRE(new_agent_states, 4);
-    LT_REQUIRE(dones, 1);
-    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
-    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
-    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
-    LT_REQUIRE(loss, 4);
     LT_REQUIRE(workspace, 256);
-    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
-    a->states = states; a->agent_states = agent_states; a->rewards = rewards; a->new_states = new_states;
-    a->new_agent_states = new_agent_states; a->actions = actions; a->idx = idx; a->dones = dones;
     a->model = model; a->target = target;
-    a->grads = grads; a->loss = loss;
-    a->partials = (float *)workspace;
     a->dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
-    a->n_rows = n_rows;
-    a->B = (int)B; a->F = n_features; a->ksteps = (n_features + 15) / 16; a->ntiles = ((int)B + 31) / 32;
     a->blocks = antsrl_exptrain_blocks((int)B);
-    a->discount = discount;
-    a->dq_scale = (float)(2.0 / (3.0 * (double)B));
-    a->loss_scale = (float)(1.0 / (3.0 * (double)B));
     return ANTSRL_OK;
 }
 
@@ -239,11 +203,12 @@ extern "C" int antsrl_exptrain_grad(int32_t n_features, const float *model, cons
 {
     const char *who = "exptrain_grad";
     ExpTrainArgs a = {};
-    const int rc = et_batch(who, n_features, const_cast<float *>(model), target, states, agent_states, actions, rewards,
-                            new_states, new_agent_states, dones, n_rows, idx, B, discount, grads, true, loss, workspace, &a);
+    int rc = et_net(who, n_features, B, const_cast<float *>(model), target, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, true, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
-    const hipError_t e = antsrl_launch_exptrain(a, (hipStream_t)stream); // a.adam == 0: model is only read
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
 }
 
 extern "C" int antsrl_exptrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
@@ -256,11 +221,10 @@ extern "C" int antsrl_exptrain_apply(int32_t n_features, float *model, float *ad
     LT_REQUIRE(adam_m, 4);
     LT_REQUIRE(adam_v, 4);
     LT_REQUIRE(grads, 4);
-    ExpTrainArgs a = {};
-    if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
-    a.F = n_features; a.model = model; a.m = adam_m; a.v = adam_v; a.grads = const_cast<float *>(grads);
-    const hipError_t e = antsrl_launch_exptrain_apply(a, (hipStream_t)stream);
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    AdamArgs o = {};
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o)) != ANTSRL_OK) return rc;
+    o.m = adam_m; o.v = adam_v;
+    return enqueued(antsrl_launch_adam(model, o, grads, (int)antsrl_exptrain_floats(n_features), (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
@@ -272,13 +236,14 @@ extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const floa
 {
     const char *who = "exptrain_step";
     ExpTrainArgs a = {};
-    int rc = et_batch(who, n_features, model, target, states, agent_states, actions, rewards, new_states, new_agent_states,
-                      dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
+    int rc = et_net(who, n_features, B, model, target, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, false, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
     LT_REQUIRE(adam_m, 4);
     LT_REQUIRE(adam_v, 4);
-    if ((rc = lt_adam(who, LtAdam{step, lr, beta1, beta2, eps}, &a)) != ANTSRL_OK) return rc;
-    a.m = adam_m; a.v = adam_v;
-    const hipError_t e = antsrl_launch_exptrain(a, (hipStream_t)stream);
-    return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK;
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who);
 }

@@ -8,9 +8,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_adam.h"
+#include "antsrl_dqn.h"
 #include "antsrl_fail.h"
 
-#define LT_HIDDEN 32
+#define LT_HIDDEN DQN_HIDDEN
 #define LT_HEADS 198       // trained floats
 #define LT_L3 99           // floats of one layer3
 #define LT_OUT 199         // the 198 gradients and the loss
@@ -19,26 +21,14 @@
 #define LT_MAX_BLOCKS 1024 // workgroups of 4 waves otherwise (tiles are looped)
 
 struct LinTrainArgs {
-    const float *states, *agent_states, *rewards, *new_states, *new_agent_states;
-    const int64_t *actions, *idx; // actions [N][2]; idx [B] or NULL (rows 0 .. B - 1)
-    const uint8_t *dones;
+    DqnBatch batch;           // grads: LT_HEADS floats; partials: [workgroups][LT_PART] (more than one workgroup only)
     const float *w1, *b1;     // the frozen layer1
     float *heads;             // LT_HEADS floats: read by the forward, written by Adam
     const float *target_l3;   // LT_L3 floats
-    float *m, *v;             // Adam's moments, LT_HEADS floats each (adam only)
-    float *grads;             // LT_HEADS floats, or NULL
-    float *loss;              // one float
-    float *partials;          // [workgroups][LT_PART] (more than one workgroup only)
-    long long n_rows;         // rows of the replay arrays: idx is clamped to [0, n_rows)
-    int B, F, ksteps, ntiles;
-    float discount, dq_scale /* 2 / (3 B) */, loss_scale /* 1 / (3 B) */;
-    int adam;                 // 0: gradients and loss only
-    float step_size, bc2_sqrt, w1m, beta2, w2m, eps;
+    AdamArgs adam;            // m, v: LT_HEADS floats each
 };
 
 // workgroups of the gradient stage for B rows (1: the step is one launch)
 ANTSRL_INTERNAL int antsrl_lintrain_blocks(int B, int F);
 // the gradient stage, and behind it (more than one workgroup) the finish: at most two launches
 ANTSRL_INTERNAL hipError_t antsrl_launch_lintrain(const LinTrainArgs &a, hipStream_t st);
-// Adam alone from a.grads (a.heads, a.m, a.v and the Adam scalars are read)
-ANTSRL_INTERNAL hipError_t antsrl_launch_lintrain_apply(const LinTrainArgs &a, hipStream_t st);

@@ -20,87 +20,30 @@
 // 198 floats.  No atomics anywhere: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_adam.h"
+#include "antsrl_dqn_dev.h"
 #include "antsrl_lds_optin.h"
 #include "antsrl_lintrain.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-struct __attribute__((packed, aligned(4))) LtF4 { float v[4]; }; // 4-byte aligned 16-byte load
 
 #define LT_HSTRIDE 33 // floats per row of a wave's h tile: 32 hidden values and the 1.0 of the biases
 #define LT_DSTRIDE 8  // floats per row of its dq tile: 6 dq, the loss term, pad
 #define LT_SLOT 100   // floats per head in LDS: [3][32] + [3], padded to 16 bytes
 #define LT_HW 304     // the three slots, padded
 
-__device__ __forceinline__ void lt_wave_sync()
-{
-    // LDS hand-off inside one wave: its LDS instructions execute in order, only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// 8 consecutive inputs k0 .. k0 + 7 of a row as a bf16 fragment; inputs at or beyond F are zero and never read
-__device__ __forceinline__ bf16x8 lt_frag(const float *__restrict__ row, const int k0, const int F, const bool whole)
-{
-    bf16x8 b;
-    if (whole) {
-        const LtF4 lo = *reinterpret_cast<const LtF4 *>(row + k0), hi = *reinterpret_cast<const LtF4 *>(row + k0 + 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            b[j] = (__bf16)lo.v[j];
-            b[4 + j] = (__bf16)hi.v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float x = row[min(k0 + j, F - 1)]; // unconditional on a clamped address, then a select
-            b[j] = (__bf16)(k0 + j < F ? x : 0.0f);
-        }
-    }
-    return b;
-}
-
-// the three outputs of one head for this lane's row: the lane's 16 hidden values against its part of the weights, the
-// other half-wave's part added, then the bias.  w: [3][32] + [3] in LDS
-__device__ __forceinline__ void lt_head(const float *w, const float (&hv)[16], const int h, float (&q)[3])
-{
-#pragma unroll
-    for (int o = 0; o < 3; ++o) {
-        float p = 0.0f;
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const float4 ww = *reinterpret_cast<const float4 *>(w + o * LT_HIDDEN + 8 * g4 + 4 * h);
-            p += ww.x * hv[4 * g4];
-            p += ww.y * hv[4 * g4 + 1];
-            p += ww.z * hv[4 * g4 + 2];
-            p += ww.w * hv[4 * g4 + 3];
-        }
-        q[o] = (p + __shfl_xor(p, 32)) + w[3 * LT_HIDDEN + o];
-    }
-}
-
 // what thread t < LT_OUT does with total t of the step: gradient t (and Adam on trained float t), or the loss
 __device__ __forceinline__ void lt_epilogue(const LinTrainArgs &a, const int t, const float total)
 {
-    if (t == LT_HEADS) {
-        *a.loss = total;
-        return;
-    }
-    if (a.grads) a.grads[t] = total;
-    if (a.adam) {
-        float mm = a.m[t], vv = a.v[t];
-        a.heads[t] = adam_element(a.heads[t], total, mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
-        a.m[t] = mm;
-        a.v[t] = vv;
-    }
+    if (t == LT_HEADS)
+        *a.batch.loss = total;
+    else
+        dqn_store_adam(a.heads, a.batch.grads, a.adam, t, total);
 }
 
 template <int NW> // waves per workgroup
 __global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int F = a.F, IN = F + 2, ksteps = a.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
+    const DqnBatch &mb = a.batch;
+    const int F = mb.F, IN = F + 2, ksteps = mb.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
     __bf16 *w1s = reinterpret_cast<__bf16 *>(smem);                                        // [32][KP]
     float *hw = reinterpret_cast<float *>(smem + (size_t)LT_HIDDEN * KP * 2); // 3 slots of LT_SLOT: layer2, layer3, the target's layer3
     float *l1x = hw + LT_HW;                                                  // [3][32]: b1 and the bf16-rounded W1 columns F, F + 1
@@ -109,11 +52,7 @@ __global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wib = threadIdx.x >> 6;
     float *ht = tiles + (size_t)wib * (32 * LT_HSTRIDE + 32 * LT_DSTRIDE), *dqs = ht + 32 * LT_HSTRIDE;
 
-    for (int row = wib; row < LT_HIDDEN; row += NW) // W1's observation columns -> bf16
-        for (int k = lane; k < 16 * ksteps; k += 64) {
-            const float wv = a.w1[(size_t)row * IN + min(k, F - 1)];
-            w1s[row * KP + k] = (__bf16)(k < F ? wv : 0.0f);
-        }
+    dqn_stage_w1(a.w1, w1s, F, ksteps, KP, wib, NW, lane);
     for (int i = threadIdx.x; i < LT_HEADS + LT_L3; i += 64 * NW)
         hw[(i / LT_L3) * LT_SLOT + i % LT_L3] = i < LT_HEADS ? a.heads[i] : a.target_l3[i - LT_HEADS];
     if (threadIdx.x < LT_HIDDEN) {
@@ -140,32 +79,31 @@ __global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
 
     const __bf16 *wrow = w1s + r * KP + 8 * h;
     const int nwhole = F / 16; // k-steps whose 16 inputs all lie inside the row
-    for (int t = blockIdx.x * NW + wib; t < a.ntiles; t += gridDim.x * NW) {
+    for (int t = blockIdx.x * NW + wib; t < mb.ntiles; t += gridDim.x * NW) {
         const int brow = t * 32 + r;
-        const bool valid = brow < a.B;
-        long long ri = a.idx ? a.idx[min(brow, a.B - 1)] : (long long)min(brow, a.B - 1);
-        ri = ri < 0 ? 0 : (ri >= a.n_rows ? a.n_rows - 1 : ri); // never outside the replay arrays
-        const float *xs = a.states + (size_t)ri * F, *xn = a.new_states + (size_t)ri * F;
+        const bool valid = brow < mb.B;
+        const long long ri = dqn_row(mb, min(brow, mb.B - 1));
+        const float *xs = mb.states + (size_t)ri * F, *xn = mb.new_states + (size_t)ri * F;
         f32x16 acc, accn;
 #pragma unroll
         for (int g = 0; g < 16; ++g) acc[g] = accn[g] = 0.0f;
         int s = 0;
 #pragma unroll 1
         for (; s < nwhole; ++s) {
-            const bf16x8 bs = lt_frag(xs, 16 * s + 8 * h, F, true), bn = lt_frag(xn, 16 * s + 8 * h, F, true);
+            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, true), bn = dqn_frag(xn, 16 * s + 8 * h, F, true);
             const bf16x8 af = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bs, acc, 0, 0, 0);
             accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bn, accn, 0, 0, 0);
         }
 #pragma unroll 1
         for (; s < ksteps; ++s) {
-            const bf16x8 bs = lt_frag(xs, 16 * s + 8 * h, F, false), bn = lt_frag(xn, 16 * s + 8 * h, F, false);
+            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, false), bn = dqn_frag(xn, 16 * s + 8 * h, F, false);
             const bf16x8 af = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bs, acc, 0, 0, 0);
             accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bn, accn, 0, 0, 0);
         }
-        const float as0 = (float)(__bf16)a.agent_states[(size_t)ri * 2], as1 = (float)(__bf16)a.agent_states[(size_t)ri * 2 + 1];
-        const float an0 = (float)(__bf16)a.new_agent_states[(size_t)ri * 2], an1 = (float)(__bf16)a.new_agent_states[(size_t)ri * 2 + 1];
+        const float as0 = (float)(__bf16)mb.agent_states[(size_t)ri * 2], as1 = (float)(__bf16)mb.agent_states[(size_t)ri * 2 + 1];
+        const float an0 = (float)(__bf16)mb.new_agent_states[(size_t)ri * 2], an1 = (float)(__bf16)mb.new_agent_states[(size_t)ri * 2 + 1];
         float hv[16], hn[16];
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) { // accumulator register g = 4 g4 + j of half-wave h is hidden value 8 g4 + 4 h + j
@@ -174,41 +112,41 @@ __global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
             const float4 c1 = *reinterpret_cast<const float4 *>(l1x + 2 * LT_HIDDEN + 8 * g4 + 4 * h);
             const float bias1[4] = {bb.x, bb.y, bb.z, bb.w}, was0[4] = {c0.x, c0.y, c0.z, c0.w}, was1[4] = {c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { // k_policy_flat's expression
-                hv[4 * g4 + j] = acc[4 * g4 + j] + (as0 * was0[j] + as1 * was1[j]) + bias1[j];
-                hn[4 * g4 + j] = accn[4 * g4 + j] + (an0 * was0[j] + an1 * was1[j]) + bias1[j];
+            for (int j = 0; j < 4; ++j) {
+                hv[4 * g4 + j] = dqn_hidden(acc[4 * g4 + j], as0, was0[j], as1, was1[j], bias1[j]);
+                hn[4 * g4 + j] = dqn_hidden(accn[4 * g4 + j], an0, was0[j], an1, was1[j], bias1[j]);
             }
         }
         float qr[3], qp[3], nr[3], np[3];
         // (scheduling fences: the 48 weight vectors of the four heads are not all hoisted in front of the first product)
         __builtin_amdgcn_sched_barrier(0);
-        lt_head(hw, hv, h, qr);                  // model: layer2
+        dqn_head(hw, hv, h, qr);                  // model: layer2
         __builtin_amdgcn_sched_barrier(0);
-        lt_head(hw + LT_SLOT, hv, h, qp);        //        layer3
+        dqn_head(hw + LT_SLOT, hv, h, qp);        //        layer3
         __builtin_amdgcn_sched_barrier(0);
-        lt_head(hw, hn, h, nr);                  // target: the shared, live layer2
+        dqn_head(hw, hn, h, nr);                  // target: the shared, live layer2
         __builtin_amdgcn_sched_barrier(0);
-        lt_head(hw + 2 * LT_SLOT, hn, h, np);    //         its own layer3
+        dqn_head(hw + 2 * LT_SLOT, hn, h, np);    //         its own layer3
         __builtin_amdgcn_sched_barrier(0);
-        const long long ar64 = a.actions[(size_t)ri * 2], ap64 = a.actions[(size_t)ri * 2 + 1];
+        const long long ar64 = mb.actions[(size_t)ri * 2], ap64 = mb.actions[(size_t)ri * 2 + 1];
         const int ar = ar64 < 0 ? 0 : (ar64 > 2 ? 2 : (int)ar64), ap = ap64 < 0 ? 0 : (ap64 > 2 ? 2 : (int)ap64);
-        const float rew = a.rewards[ri], live = a.dones[ri] ? 0.0f : 1.0f;
-        const float yr = rew + a.discount * fmaxf(fmaxf(nr[0], nr[1]), nr[2]) * live;
-        const float yp = rew + a.discount * fmaxf(fmaxf(np[0], np[1]), np[2]) * live;
+        const float rew = mb.rewards[ri], live = mb.dones[ri] ? 0.0f : 1.0f;
+        const float yr = rew + mb.discount * fmaxf(fmaxf(nr[0], nr[1]), nr[2]) * live;
+        const float yp = rew + mb.discount * fmaxf(fmaxf(np[0], np[1]), np[2]) * live;
         const float dr = (ar == 0 ? qr[0] : ar == 1 ? qr[1] : qr[2]) - yr, dp = (ap == 0 ? qp[0] : ap == 1 ? qp[1] : qp[2]) - yp;
-        lt_wave_sync(); // the previous tile's sums are done with the tile
+        dqn_wave_sync(); // the previous tile's sums are done with the tile
 #pragma unroll
         for (int g = 0; g < 16; ++g) ht[r * LT_HSTRIDE + (g & 3) + 8 * (g >> 2) + 4 * h] = hv[g];
         if (h == 0) {
-            const float gr = valid ? dr * a.dq_scale : 0.0f, gp = valid ? dp * a.dq_scale : 0.0f;
+            const float gr = valid ? dr * mb.dq_scale : 0.0f, gp = valid ? dp * mb.dq_scale : 0.0f;
 #pragma unroll
             for (int o = 0; o < 3; ++o) {
                 dqs[r * LT_DSTRIDE + o] = ar == o ? gr : 0.0f;
                 dqs[r * LT_DSTRIDE + 3 + o] = ap == o ? gp : 0.0f;
             }
-            dqs[r * LT_DSTRIDE + 6] = valid ? dr * dr * a.loss_scale + dp * dp * a.loss_scale : 0.0f;
+            dqs[r * LT_DSTRIDE + 6] = valid ? dr * dr * mb.loss_scale + dp * dp * mb.loss_scale : 0.0f;
         }
-        lt_wave_sync();
+        dqn_wave_sync();
 #pragma unroll 4
         for (int rr = 0; rr < 32; ++rr) {
 #pragma unroll
@@ -226,7 +164,7 @@ __global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
         if (gridDim.x == 1)
             lt_epilogue(a, threadIdx.x, s); // (every wave has read the heads into LDS long before: behind two barriers)
         else
-            a.partials[(size_t)blockIdx.x * LT_PART + threadIdx.x] = s;
+            mb.partials[(size_t)blockIdx.x * LT_PART + threadIdx.x] = s;
     }
 }
 
@@ -234,18 +172,15 @@ __global__ void __launch_bounds__(256) k_lintrain_finish(const LinTrainArgs a, c
 {
     if (threadIdx.x >= LT_OUT) return;
     float s = 0.0f;
-    for (int b = 0; b < nblocks; ++b) s += a.partials[(size_t)b * LT_PART + threadIdx.x];
+    for (int b = 0; b < nblocks; ++b) s += a.batch.partials[(size_t)b * LT_PART + threadIdx.x];
     lt_epilogue(a, threadIdx.x, s);
 }
 
-__global__ void __launch_bounds__(256) k_lintrain_apply(const LinTrainArgs a)
+// Adam alone on P floats from a flat gradient (antsrl_launch_adam, antsrl_adam.h)
+__global__ void __launch_bounds__(256) k_adam_flat(float *params, const AdamArgs o, const float *grads, const int P)
 {
-    if (threadIdx.x >= LT_HEADS) return;
-    const int t = threadIdx.x;
-    float mm = a.m[t], vv = a.v[t];
-    a.heads[t] = adam_element(a.heads[t], a.grads[t], mm, vv, a.step_size, a.bc2_sqrt, a.w1m, a.beta2, a.w2m, a.eps);
-    a.m[t] = mm;
-    a.v[t] = vv;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p < P) adam_at(params, o, p, grads[p]);
 }
 
 static size_t lt_lds(int ksteps, int nw)
@@ -265,8 +200,8 @@ int antsrl_lintrain_blocks(int B, int F)
 
 hipError_t antsrl_launch_lintrain(const LinTrainArgs &a, hipStream_t st)
 {
-    const int blocks = antsrl_lintrain_blocks(a.B, a.F);
-    const size_t lds = lt_lds(a.ksteps, 4); // up to 91 KB at the widest rows: above 64 KiB it is an opt-in per device
+    const int blocks = antsrl_lintrain_blocks(a.batch.B, a.batch.F);
+    const size_t lds = lt_lds(a.batch.ksteps, 4); // up to 91 KB at the widest rows: above 64 KiB it is an opt-in per device
     hipError_t e = antsrl_lds_optin<k_lintrain<4>>(lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_lintrain<4>, dim3(blocks), dim3(256), lds, st, a);
@@ -275,8 +210,8 @@ hipError_t antsrl_launch_lintrain(const LinTrainArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t antsrl_launch_lintrain_apply(const LinTrainArgs &a, hipStream_t st)
+hipError_t antsrl_launch_adam(float *params, const AdamArgs &o, const float *grads, int P, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_lintrain_apply, dim3(1), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_adam_flat, dim3((P + 255) / 256), dim3(256), 0, st, params, o, grads, P);
     return hipGetLastError();
 }

@@ -6,9 +6,9 @@
 // Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip, antsrl_memtrain.hip
 // and antsrl_memagent.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
-#include <math.h>
 #include <stdint.h>
 
+#include "antsrl_adam.h"
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
 #include "antsrl_memagent.h"
@@ -317,17 +317,10 @@ extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, cons
     if ((rc = memtrain_state_check(state, "memtrain_apply", "state")) != ANTSRL_OK) return rc;
     if (!grads) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads is required");
     if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "memtrain_apply: grads must be 4-byte aligned");
-    if (step < 1) return fail(ANTSRL_E_INVALID, "memtrain_apply: step must be >= 1");
-    if (!(lr >= 0.0) || !(lr < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: lr must be finite and >= 0");
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
-        return fail(ANTSRL_E_INVALID, "memtrain_apply: beta1, beta2 must be in [0, 1)");
-    if (!(eps > 0.0) || !(eps < 1e30)) return fail(ANTSRL_E_INVALID, "memtrain_apply: eps must be finite and > 0");
-    // torch.optim.Adam (single tensor): the bias corrections in double, then every scalar rounded to float by the op
-    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-    const double step_size = lr / bc1, bc2_sqrt = pow(bc2, 0.5);
-    hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, (float)step_size, (float)bc2_sqrt,
-                                                (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps,
-                                                (hipStream_t)stream);
+    AdamArgs o = {};
+    if ((rc = antsrl_adam_args("memtrain_apply", step, lr, beta1, beta2, eps, &o)) != ANTSRL_OK) return rc;
+    hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, o.step_size, o.bc2_sqrt, o.w1m, o.beta2,
+                                                o.w2m, o.eps, (hipStream_t)stream);
     return enqueued(e, "memtrain_apply");
 }
 

@@ -11,6 +11,7 @@ changed here either, and has no Adam state.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -23,39 +24,120 @@ from .policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_ptrs, memnet_param
 TRAINED_LAYERS = MEMNET_LAYERS[:9]
 
 
-class MemoryTrainer:
-    """CollectAgentMemory's model, target model and optimizer on the device (defaults: the reference class's,
-    discount 0.5, lr 1e-4; main.py passes 0.99 and 1e-5).
+class _DqnTrainer:
+    """What the three trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
+    workspace, and train() around step().  A subclass holds its nets, writes grad / apply / step over its own entries,
+    sync_target, and `_sizes(B, workspace_bytes, launches)`, its antsrl_*train_sizes call."""
 
-    `step(batch_or_replay, idx)` is one training step (grad + apply) and returns the loss as a 0-d device tensor;
-    `train(replay, done)` is CollectAgentMemory.train with the replay on the device.  `policy` is a MemoryPolicy holding
-    the TARGET net (get_action acts with the target net, :194), repacked at every sync_target() in `policy_precision`
-    ("bf16" or "fp32", MemoryPolicy's precision); the training step itself has bf16 operands either way."""
+    minibatch = 264  # train()'s default: the reference class's
 
-    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
-                 eps: float = 1e-8, update_target_every: int = 1, power: int = 5, mem_size: int = 20, n_rot: int = 3,
-                 n_ph: int = 3, seed: int = 0, state_dict=None, policy_precision: str = "bf16"):
+    def __init__(self, n_features: int, device, ast_width: int, discount: float, lr: float, betas, eps: float,
+                 update_target_every: int):
         self.device = torch.device(device)
-        assert self.device.type == "cuda", "MemoryTrainer runs on the GPU"
+        assert self.device.type == "cuda", "%s runs on the GPU" % type(self).__name__
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        self.n_features = n_features
+        self.n_features, self._ast_width = n_features, ast_width  # floats of an observation, of an agent_states row
         self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
         self.update_target_every = int(update_target_every)
         self.target_update_counter = 0
         self.syncs = 0
         self.step_count = 0
+        self._work = None
+        self._lib = _lib.load()
+
+    def _arrays(self, batch_or_replay):
+        r = batch_or_replay
+        a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones) \
+            if hasattr(r, "states") else tuple(r)
+        n = len(r) if hasattr(r, "states") else a[0].shape[0]
+        assert len(a) == 7
+        st, ast, act, rw, nst, nast, dn = a
+        N = st.shape[0]
+        for t, dt in ((st, torch.float32), (ast, torch.float32), (act, torch.int64), (rw, torch.float32),
+                      (nst, torch.float32), (nast, torch.float32), (dn, torch.bool)):
+            assert t.device == self.device and t.dtype == dt and t.is_contiguous() and t.shape[0] == N, (t.shape, t.dtype)
+        assert st[0].numel() == self.n_features and nst[0].numel() == self.n_features
+        assert ast.shape[1:] == (self._ast_width,) and nast.shape[1:] == (self._ast_width,), \
+            "agent_states rows are %d floats" % self._ast_width
+        assert act.shape[1:] == (2,) and rw.dim() == 1 and dn.dim() == 1
+        return a, n, N
+
+    def _batch(self, batch_or_replay, idx):
+        """The seven arrays, their rows N and the minibatch's B, with the workspace grown to what B rows need."""
+        a, n, N = self._arrays(batch_or_replay)
+        if idx is not None:
+            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
+            B = idx.numel()
+        else:
+            B = n
+        assert B >= 1
+        ws = C.c_size_t()
+        self._sizes(B, C.byref(ws), None)
+        if self._work is None or self._work.numel() < ws.value:
+            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
+        return a, N, B
+
+    def launches(self, B: int) -> int:
+        """Kernel launches of one step on B rows (antsrl_lintrain_sizes: 1 up to 512 rows, else 2; antsrl_exptrain_sizes:
+        2)."""
+        n = C.c_int32()
+        self._sizes(B, None, C.byref(n))
+        return n.value
+
+    def _loss(self, loss):
+        return torch.empty((), dtype=torch.float32, device=self.device) if loss is None else loss
+
+    def _grads(self, grads):
+        g = self.grads if grads is None else grads
+        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == self.trained_floats and g.is_contiguous()
+        return g
+
+    def train(self, replay, done: bool, minibatch: Optional[int] = None, min_replay: int = 1000,
+              generator: Optional[torch.Generator] = None):
+        """The reference's train: 0 below min_replay, else a step on `minibatch` rows (the class's by default) drawn on
+        the device (with replacement), then the target counter (host side: `done` is a host bool) and the sync."""
+        if len(replay) < min_replay:
+            return 0
+        idx = torch.randint(0, len(replay), (self.minibatch if minibatch is None else minibatch,), device=self.device,
+                            generator=generator)
+        return self.train_on(replay, idx, done)
+
+    def train_on(self, batch_or_replay, idx: Optional[torch.Tensor], done: bool):
+        """train() on rows the caller picked: the step, then the target counter and the sync."""
+        loss = self.step(batch_or_replay, idx)
+        if done:
+            self.target_update_counter += 1
+        if self.target_update_counter >= self.update_target_every:
+            self.sync_target()
+            self.target_update_counter = 0
+        return loss
+
+
+class MemoryTrainer(_DqnTrainer):
+    """CollectAgentMemory's model, target model and optimizer on the device (defaults: the reference class's,
+    discount 0.5, lr 1e-4; main.py passes 0.99 and 1e-5).
+
+    `step(batch_or_replay, idx)` is one training step (grad + apply) and returns the loss as a 0-d device tensor;
+    `train(replay, done)` is CollectAgentMemory.train (:133-176) with the replay on the device.  `policy` is a
+    MemoryPolicy holding the TARGET net (get_action acts with the target net, :194), repacked at every sync_target() in
+    `policy_precision` ("bf16" or "fp32", MemoryPolicy's precision); the training step itself has bf16 operands either
+    way."""
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, power: int = 5, mem_size: int = 20, n_rot: int = 3,
+                 n_ph: int = 3, seed: int = 0, state_dict=None, policy_precision: str = "bf16"):
         if state_dict is not None:
             shp = memnet_shape_from_state_dict(state_dict)
             assert shp["n_features"] == n_features, "state_dict is for %d features, not %d" % (shp["n_features"], n_features)
             power, mem_size, n_rot, n_ph = shp["power"], shp["mem_size"], shp["n_rot"], shp["n_ph"]
+        super().__init__(n_features, device, 2 + mem_size, discount, lr, betas, eps, update_target_every)
         self.policy = MemoryPolicy(n_features, self.device, power=power, mem_size=mem_size, n_rot=n_rot, n_ph=n_ph,
                                    seed=seed, precision=policy_precision)
         if state_dict is None:
             state_dict = {k: v.clone() for k, v in self.policy.state_dict().items()}
         self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
         self.shape = self.policy.shape
-        self._lib = _lib.load()
         pf, tf, sb = C.c_size_t(), C.c_size_t(), C.c_size_t()
         _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), 1, C.byref(pf), C.byref(tf), C.byref(sb), None),
                    "memtrain_sizes")
@@ -63,7 +145,6 @@ class MemoryTrainer:
         self._model = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)  # 512-byte aligned blocks
         self._target = torch.empty_like(self._model)
         self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
-        self._work = None
         # the flat layout (include/antsrl.h): state_dict order, dense, weight then bias per layer
         self._offs = {}
         off = 0
@@ -89,7 +170,7 @@ class MemoryTrainer:
             m_off, v_off = self._adam_offsets()
             base = (m_off if region == "m" else v_off) // 4
             names = [k for k in self._offs if k.split(".")[0] in TRAINED_LAYERS]
-        return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + _numel(self._offs[k][1])].view(self._offs[k][1])
+        return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + math.prod(self._offs[k][1])].view(self._offs[k][1])
                 for k in names}
 
     # ---- weights ------------------------------------------------------------------------------------------------
@@ -128,7 +209,7 @@ class MemoryTrainer:
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the 18 trained state_dict tensors."""
         g = self.grads if grads is None else grads
-        return {k: g[o: o + _numel(shp)].view(shp) for k, (o, shp) in self._offs.items() if k.split(".")[0] in TRAINED_LAYERS}
+        return {k: g[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items() if k.split(".")[0] in TRAINED_LAYERS}
 
     def _repack_policy(self):
         """policy := target net (a copy into the policy's own tensors, then antsrl_memnet_pack_ex in its precision)."""
@@ -150,43 +231,16 @@ class MemoryTrainer:
         self.syncs += 1
 
     # ---- the two stages -----------------------------------------------------------------------------------------
-    def _arrays(self, batch_or_replay):
-        r = batch_or_replay
-        if hasattr(r, "states"):
-            a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones)
-            n = len(r)
-        else:
-            a = tuple(r)
-            n = a[0].shape[0]
-        assert len(a) == 7
-        st, ast, act, rw, nst, nast, dn = a
-        N = st.shape[0]
-        for t, dt in ((st, torch.float32), (ast, torch.float32), (act, torch.int64), (rw, torch.float32),
-                      (nst, torch.float32), (nast, torch.float32), (dn, torch.bool)):
-            assert t.device == self.device and t.dtype == dt and t.is_contiguous() and t.shape[0] == N, (t.shape, t.dtype)
-        assert st[0].numel() == self.n_features and nst[0].numel() == self.n_features
-        assert ast.shape[1:] == (2 + self.mem_size,) and nast.shape[1:] == (2 + self.mem_size,)
-        assert act.shape[1:] == (2,) and rw.dim() == 1 and dn.dim() == 1
-        return a, n
+    def _sizes(self, B, workspace_bytes, launches):
+        assert launches is None, "antsrl_memtrain_sizes reports no launch count"
+        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), B, None, None, None, workspace_bytes), "memtrain_sizes")
 
     def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stage 1: the loss (0-d device tensor) and the gradients of the 18 trained tensors into self.grads.  Rows are
         idx (int64 on the device, values in [0, len)) of a DeviceReplayMemory or of a 7-tuple of arrays (states,
         agent_states, actions, rewards, new_states, new_agent_states, dones), or all rows when idx is None."""
-        a, n = self._arrays(batch_or_replay)
-        if idx is not None:
-            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
-            B = idx.numel()
-        else:
-            B = n
-        assert B >= 1
-        ws = C.c_size_t()
-        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), B, None, None, None, C.byref(ws)), "memtrain_sizes")
-        if self._work is None or self._work.numel() < ws.value:
-            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
-        if loss is None:
-            loss = torch.empty((), dtype=torch.float32, device=self.device)
-        st, ast, act, rw, nst, nast, dn = a
+        (st, ast, act, rw, nst, nast, dn), _, B = self._batch(batch_or_replay, idx)
+        loss = self._loss(loss)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memtrain_grad(C.byref(self.shape), _p(self._model), _p(self._target), _p(st), _p(ast),
                                                       _p(act), _p(rw), _p(nst), _p(nast), _p(dn), _p(idx), B, self.discount,
@@ -196,8 +250,7 @@ class MemoryTrainer:
 
     def apply(self, grads: Optional[torch.Tensor] = None) -> None:
         """Stage 2: one Adam step over the flat gradient (self.grads by default), then the bf16 repack."""
-        g = self.grads if grads is None else grads
-        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == self.trained_floats and g.is_contiguous()
+        g = self._grads(grads)
         self.step_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memtrain_apply(C.byref(self.shape), _p(self._model), _p(g), self.step_count, self.lr,
@@ -209,28 +262,6 @@ class MemoryTrainer:
         loss = self.grad(batch_or_replay, idx)
         self.apply()
         return loss
-
-    def train(self, replay, done: bool, minibatch: int = 264, min_replay: int = 1000,
-              generator: Optional[torch.Generator] = None):
-        """CollectAgentMemory.train (:133-176): 0 below min_replay, else a step on `minibatch` rows drawn on the device
-        (with replacement), then the target counter (host side: `done` is a host bool) and the sync."""
-        if len(replay) < min_replay:
-            return 0
-        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
-        loss = self.step(replay, idx)
-        if done:
-            self.target_update_counter += 1
-        if self.target_update_counter >= self.update_target_every:
-            self.sync_target()
-            self.target_update_counter = 0
-        return loss
-
-
-def _numel(shape):
-    n = 1
-    for s in shape:
-        n *= s
-    return n
 
 
 #: CollectModel.state_dict()'s names and order (agents/collect_agent.py:24-51 over explore_agent_pytorch.py:24-45)
@@ -245,7 +276,7 @@ LINEAR_TRAINED = {"explore_model.layer2.weight": (0, (3, 32)), "explore_model.la
 EXPLORE_NAMES = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias")
 
 
-class LinearTrainer:
+class LinearTrainer(_DqnTrainer):
     """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
     reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
 
@@ -256,29 +287,19 @@ class LinearTrainer:
     step.  `version` counts the changes of the acting weights (every step moves layer2).
 
     The surface is MemoryTrainer's: grad / apply / step, train(replay, done), state_dict / load_state_dict under the
-    reference's six names, target_state_dict, sync_target, adam_state, grad_dict."""
+    reference's six names, target_state_dict, sync_target, adam_state, grad_dict.  train() is CollectAgent.train
+    (:105-148)."""
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
         from .policy import LinearPolicy
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "LinearTrainer runs on the GPU"
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.n_features = n_features
-        self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
-        self.update_target_every = int(update_target_every)
-        self.target_update_counter = 0
-        self.syncs = 0
-        self.step_count = 0
+        super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
         self.version = 0
-        self._lib = _lib.load()
         p = LinearPolicy(n_features, self.device, seed=seed)
         self.heads = torch.cat([p.w2.reshape(-1), p.b2, p.w3.reshape(-1), p.b3]).contiguous()
         self.target_l3 = self.heads[99:198].clone()
         self._adam = torch.zeros((2, 198), dtype=torch.float32, device=self.device)
         self.grads = torch.zeros((198,), dtype=torch.float32, device=self.device)
-        self._work = None
         p.w2, p.b2 = self.heads[0:96].view(3, 32), self.heads[96:99]              # the live layer2
         p.w3, p.b3 = self.target_l3[0:96].view(3, 32), self.target_l3[96:99]      # the target layer3
         self.policy = p
@@ -290,7 +311,7 @@ class LinearTrainer:
     def _model_views(self) -> dict:
         d = {"explore_model.layer1.weight": self.policy.w1, "explore_model.layer1.bias": self.policy.b1}
         for k, (o, shp) in LINEAR_TRAINED.items():
-            d[k] = self.heads[o: o + _numel(shp)].view(shp)
+            d[k] = self.heads[o: o + math.prod(shp)].view(shp)
         return d
 
     def state_dict(self) -> dict:
@@ -331,13 +352,13 @@ class LinearTrainer:
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the four trained tensors: step, exp_avg, exp_avg_sq (copies)."""
         def views(row):
-            return {k: self._adam[row, o: o + _numel(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
+            return {k: self._adam[row, o: o + math.prod(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
         return dict(step=self.step_count, exp_avg=views(0), exp_avg_sq=views(1))
 
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the four trained tensors."""
         g = self.grads if grads is None else grads
-        return {k: g[o: o + _numel(shp)].view(shp) for k, (o, shp) in LINEAR_TRAINED.items()}
+        return {k: g[o: o + math.prod(shp)].view(shp) for k, (o, shp) in LINEAR_TRAINED.items()}
 
     def sync_target(self) -> None:
         """target := model (:143-146): layer3 is all the two nets do not share."""
@@ -346,48 +367,14 @@ class LinearTrainer:
         self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    def _arrays(self, batch_or_replay):
-        r = batch_or_replay
-        a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones) \
-            if hasattr(r, "states") else tuple(r)
-        n = len(r) if hasattr(r, "states") else a[0].shape[0]
-        assert len(a) == 7
-        st, ast, act, rw, nst, nast, dn = a
-        N = st.shape[0]
-        for t, dt in ((st, torch.float32), (ast, torch.float32), (act, torch.int64), (rw, torch.float32),
-                      (nst, torch.float32), (nast, torch.float32), (dn, torch.bool)):
-            assert t.device == self.device and t.dtype == dt and t.is_contiguous() and t.shape[0] == N, (t.shape, t.dtype)
-        assert st[0].numel() == self.n_features and nst[0].numel() == self.n_features
-        assert ast.shape[1:] == (2,) and nast.shape[1:] == (2,), "agent_states rows are the 2 floats of agent_state"
-        assert act.shape[1:] == (2,) and rw.dim() == 1 and dn.dim() == 1
-        return a, n, N
-
-    def _batch(self, batch_or_replay, idx):
-        a, n, N = self._arrays(batch_or_replay)
-        if idx is not None:
-            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
-            B = idx.numel()
-        else:
-            B = n
-        assert B >= 1
-        ws = C.c_size_t()
-        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, C.byref(ws), None), "lintrain_sizes")
-        if self._work is None or self._work.numel() < ws.value:
-            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
-        return a, N, B
-
-    def launches(self, B: int) -> int:
-        """Kernel launches of one step on B rows: 1 up to 512 rows, else 2 (antsrl_lintrain_sizes)."""
-        n = C.c_int32()
-        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, None, C.byref(n)), "lintrain_sizes")
-        return n.value
+    def _sizes(self, B, workspace_bytes, launches):
+        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, workspace_bytes, launches), "lintrain_sizes")
 
     def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The loss (0-d device tensor) and the gradients of the four trained tensors into self.grads; nothing is
         updated.  Rows: as MemoryTrainer.grad."""
         (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        if loss is None:
-            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        loss = self._loss(loss)
         p = self.policy
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_lintrain_grad(self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3),
@@ -398,8 +385,7 @@ class LinearTrainer:
 
     def apply(self, grads: Optional[torch.Tensor] = None) -> None:
         """One Adam step on the 198 trained floats from the flat gradient (self.grads by default)."""
-        g = self.grads if grads is None else grads
-        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == 198 and g.is_contiguous()
+        g = self._grads(grads)
         self.step_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_lintrain_apply(_p(self.heads), _p(self._adam[0]), _p(self._adam[1]), _p(g),
@@ -412,8 +398,7 @@ class LinearTrainer:
         """One training step on the minibatch, gradient and Adam in the same launches (antsrl_lintrain_step): returns the
         loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
         (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        if loss is None:
-            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        loss = self._loss(loss)
         p = self.policy
         self.step_count += 1
         with torch.cuda.device(self.device):
@@ -426,27 +411,8 @@ class LinearTrainer:
         self.version += 1
         return loss
 
-    def train(self, replay, done: bool, minibatch: int = 264, min_replay: int = 1000,
-              generator: Optional[torch.Generator] = None):
-        """CollectAgent.train (:105-148): 0 below min_replay, else a step on `minibatch` rows drawn on the device (with
-        replacement), then the target counter (host side: `done` is a host bool) and the sync."""
-        if len(replay) < min_replay:
-            return 0
-        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
-        return self.train_on(replay, idx, done)
 
-    def train_on(self, batch_or_replay, idx: Optional[torch.Tensor], done: bool):
-        """train() on rows the caller picked: the step, then the target counter and the sync."""
-        loss = self.step(batch_or_replay, idx)
-        if done:
-            self.target_update_counter += 1
-        if self.target_update_counter >= self.update_target_every:
-            self.sync_target()
-            self.target_update_counter = 0
-        return loss
-
-
-class ExploreTrainer:
+class ExploreTrainer(_DqnTrainer):
     """ExploreAgentPytorch's model, target model and optimizer on the device (agents/explore_agent_pytorch.py:48-133 as it
     was meant: ExploreModel with the concat of CollectModel.forward, collect_agent.py:47-49; defaults: the reference
     class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_exptrain_step` (antsrl_exptrain.hip).
@@ -457,23 +423,16 @@ class ExploreTrainer:
     a sync needs no copy into the policy.  `version` counts the changes of the acting weights: syncs and loads.
 
     The surface is LinearTrainer's: grad / apply / step, train(replay, done), train_on, launches, state_dict /
-    load_state_dict under ExploreModel's four names, target_state_dict, sync_target, adam_state, grad_dict."""
+    load_state_dict under ExploreModel's four names, target_state_dict, sync_target, adam_state, grad_dict.  train() is
+    ExploreAgentPytorch.train (:90-133)."""
+
+    minibatch = 256
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
         from .policy import LinearPolicy
-        self.device = torch.device(device)
-        assert self.device.type == "cuda", "ExploreTrainer runs on the GPU"
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.n_features = n_features
-        self.discount, self.lr, self.betas, self.eps = float(discount), float(lr), tuple(float(b) for b in betas), float(eps)
-        self.update_target_every = int(update_target_every)
-        self.target_update_counter = 0
-        self.syncs = 0
-        self.step_count = 0
+        super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
         self.version = 0
-        self._lib = _lib.load()
         IN = n_features + 2
         self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
                       "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
@@ -486,7 +445,6 @@ class ExploreTrainer:
         self.target = self.model.clone()
         self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
         self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
-        self._work = None
         tv = self._views(self.target)
         p.w1, p.b1, p.w2, p.b2 = (tv[k] for k in EXPLORE_NAMES)  # the acting net IS the target block
         self.policy = p
@@ -495,7 +453,7 @@ class ExploreTrainer:
 
     # ---- weights ------------------------------------------------------------------------------------------------
     def _views(self, flat) -> dict:
-        return {k: flat[o: o + _numel(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
 
     def state_dict(self) -> dict:
         """The model's four tensors (copies) under ExploreModel's names, in its order."""
@@ -532,34 +490,14 @@ class ExploreTrainer:
         self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    _arrays = LinearTrainer._arrays
-
-    def _batch(self, batch_or_replay, idx):
-        a, n, N = self._arrays(batch_or_replay)
-        if idx is not None:
-            assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()
-            B = idx.numel()
-        else:
-            B = n
-        assert B >= 1
-        ws = C.c_size_t()
-        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, C.byref(ws), None), "exptrain_sizes")
-        if self._work is None or self._work.numel() < ws.value:
-            self._work = torch.empty((ws.value,), dtype=torch.uint8, device=self.device)
-        return a, N, B
-
-    def launches(self, B: int) -> int:
-        """Kernel launches of one step on B rows: 2 (antsrl_exptrain_sizes)."""
-        n = C.c_int32()
-        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, None, C.byref(n)), "exptrain_sizes")
-        return n.value
+    def _sizes(self, B, workspace_bytes, launches):
+        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, workspace_bytes, launches), "exptrain_sizes")
 
     def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The loss (0-d device tensor) and the gradients of all P floats into self.grads; nothing is updated.  Rows: as
         MemoryTrainer.grad."""
         (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        if loss is None:
-            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        loss = self._loss(loss)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_exptrain_grad(self.n_features, _p(self.model), _p(self.target), _p(st), _p(ast),
                                                       _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N, _p(idx), B,
@@ -569,8 +507,7 @@ class ExploreTrainer:
 
     def apply(self, grads: Optional[torch.Tensor] = None) -> None:
         """One Adam step on all P floats from the flat gradient (self.grads by default)."""
-        g = self.grads if grads is None else grads
-        assert g.device == self.device and g.dtype == torch.float32 and g.numel() == self.trained_floats and g.is_contiguous()
+        g = self._grads(grads)
         self.step_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_exptrain_apply(self.n_features, _p(self.model), _p(self._adam[0]), _p(self._adam[1]),
@@ -582,8 +519,7 @@ class ExploreTrainer:
         """One training step on the minibatch, gradient and Adam in the same two launches (antsrl_exptrain_step): returns
         the loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
         (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        if loss is None:
-            loss = torch.empty((), dtype=torch.float32, device=self.device)
+        loss = self._loss(loss)
         self.step_count += 1
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_exptrain_step(self.n_features, _p(self.model), _p(self.target), _p(self._adam[0]),
@@ -593,14 +529,3 @@ class ExploreTrainer:
                                                       _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
                                                       _lib.stream(self.device)), "exptrain_step")
         return loss
-
-    def train(self, replay, done: bool, minibatch: int = 256, min_replay: int = 1000,
-              generator: Optional[torch.Generator] = None):
-        """ExploreAgentPytorch.train (:90-133): 0 below min_replay, else a step on `minibatch` rows drawn on the device
-        (with replacement), then the target counter (host side: `done` is a host bool) and the sync."""
-        if len(replay) < min_replay:
-            return 0
-        idx = torch.randint(0, len(replay), (minibatch,), device=self.device, generator=generator)
-        return self.train_on(replay, idx, done)
-
-    train_on = LinearTrainer.train_on
