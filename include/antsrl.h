@@ -560,7 +560,12 @@ int antsrl_policy_memory_tiles(const AntsMemNetShape *s, int precision, const vo
  * Workspace for B rows (Bp = r32(B)), in fp32 blocks each rounded up to 64 floats: 3 Bp r32(out) per trained layer
  * (target and model outputs, model output gradients), nchunk x sum over trained layers of r32(out) (r32(in) + 1)
  * (row-chunk gradient partials; nchunk = min(64, ceil(Bp / 256)) chunks of r32(ceil(Bp / nchunk)) rows, recounted as
- * ceil(Bp / chunk)), and ceil(Bp / 256) loss partials.  1 <= B <= 2^24.  Outputs may be NULL. */
+ * ceil(Bp / chunk)), and ceil(Bp / 256) loss partials.  The blocks lie in this order, each [Bp][r32(out)] row-major:
+ * the target net's nine layer outputs (state_dict order: layer1-4, rotation_layer1-3, pheromone_layer1-2), the model's
+ * nine, the model's nine output gradients dh1 dh2 dh3 dg dr1 dr2 dqr dp1 dqp (dL/d of those outputs, the same order),
+ * then the partials [nchunk][per layer: weight [r32(out)][r32(in)], then bias [r32(out)]], then the loss partials.
+ * Padded columns of every block and padded rows of the output gradients and partials are written as 0; padded rows of
+ * the layer outputs hold the net's output for x = 0.  1 <= B <= 2^24.  Outputs may be NULL. */
 int antsrl_memtrain_sizes(const AntsMemNetShape *s, int64_t B, size_t *params_floats, size_t *trained_floats,
                           size_t *state_bytes, size_t *workspace_bytes);
 

@@ -123,8 +123,8 @@ def test_step_is_inside_the_fp32_sum_bound(case):
 
 @pytest.mark.parametrize("betas", [(0.9, 0.999), (0.5, 0.9)])
 def test_adam_over_30_steps_against_torch(betas):
-    """apply() on supplied gradients, 30 steps, against torch.optim.Adam (foreach=False) on the CPU: lt_adam's host scalars
-    step_size and bc2_sqrt at every step > 1.
+    """apply() on supplied gradients, 30 steps, against torch.optim.Adam (foreach=False) on the CPU: the host scalars
+    step_size and bc2_sqrt of antsrl_adam_args (antsrl_adam.h) at every step > 1.
 
     The moments are bit-equal to the restatement of antsrl_adam.h (memory_train_ref.adam_step: every product rounded
     before it is added), as test_adam_stage_matches_torch holds them for the memory agent.  They are NOT bit-equal to

@@ -2,7 +2,13 @@
 of tests/memory_train_ref.py: `bf16_train_grads` (the kernels' precision contract, up to fp32 summation order),
 `fp32_train_step` (the reference's arithmetic, pinned to the reference's own train() by
 tests/test_memory_train_fixture.py) and `adam_step` / torch.optim.Adam.  The measured errors are printed (run with -s)
-and recorded in DESIGN §7.7."""
+and recorded in DESIGN §7.7.
+
+GRAD_TOL and LOSS_TOL here are measured, relative to each tensor's largest element, and against a comparator that runs
+on the GPU itself: they hold the step to the reference's arithmetic end to end and no closer.  The sharp checks of the
+kernels are in tests/test_gpu_memory_train_stages.py: inputs on which the step is exact in fp32 and must equal float64
+bit for bit (gradients, loss, m, v, both bf16 packs), and every launch held element by element inside an a-priori bound
+of float64 on its own inputs, at every width, seam and guard."""
 import numpy as np
 import pytest
 
