@@ -14,13 +14,19 @@ contract from the order of fp32 sums alone: linear_train_ref.py's method carried
 `state`: sd (the four tensors under ExploreModel's names), target (the same four), m / v (Adam's moments by name), step.
 `batch` = (states [B, F], agent_states [B, 2], actions [B, 2], rewards [B], new_states, new_agent_states, dones [B]),
 already gathered.  Both steps return (loss, grads by name)."""
+from functools import partial
+
 import numpy as np
 import torch
 
-from linear_train_ref import U_BF16, U_FP32, _t, bf16, gamma  # noqa: F401
+import dqn_ref as D
+from dqn_ref import U_BF16, U_FP32, bf16, gamma, gather  # noqa: F401
+from dqn_ref import as_batch as _t
 
 NAMES = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias")
 W1, B1, W2, B2 = NAMES
+adam = partial(D.adam, NAMES)                      # (state, grads, lr, betas, eps): Adam over all four tensors
+worst_share = partial(D.worst_share, keys=NAMES)   # (got, want, bound, keys=NAMES)
 
 
 def new_state(sd, target=None):
@@ -33,22 +39,6 @@ def new_state(sd, target=None):
 
 def sync_target(state):
     state["target"] = {k: v.clone() for k, v in state["sd"].items()}
-
-
-def adam(state, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
-    """torch.optim.Adam, single tensor, fp32 per element; the bias corrections in double (linear_train_ref.adam over the
-    four tensors)."""
-    state["step"] += 1
-    t = state["step"]
-    bc1, bc2 = 1.0 - betas[0] ** t, 1.0 - betas[1] ** t
-    step_size, bc2_sqrt = np.float32(lr / bc1), np.float32(bc2 ** 0.5)
-    for k in NAMES:
-        g = grads[k].to(torch.float32)
-        m, v = state["m"][k], state["v"][k]
-        m.lerp_(g, float(np.float32(1.0 - betas[0])))
-        v.mul_(float(np.float32(betas[1]))).addcmul_(g, g, value=float(np.float32(1.0 - betas[1])))
-        denom = (v.sqrt() / float(bc2_sqrt)).add_(float(np.float32(eps)))
-        state["sd"][k].addcdiv_(m, denom, value=-float(step_size))
 
 
 def fp32_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
@@ -110,34 +100,20 @@ def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999),
 def _bounds(state, batch, discount, h, hn, eh, ehn, xe, exe, own, elem, rowsum, loss_elem):
     """A forward error bound carried to the loss and to every gradient.  h, hn: the hidden values of the rows (under the
     model) and of their successors (under the target), eh, ehn what they may be off by; xe [B, F + 2] the layer1
-    gradient's right operand and exe what IT may be off by (float64).
-        e_q  = e_h |w2|^T + own ((|h| + e_h) |w2|^T + |b2|)                 own: layer2's own sum (0: exact)
-        e_y  = discount max_o e_q' ;  e_d = e_q[a] + e_y + elem (|q| + |reward| + discount |max q'| + e_q + e_y)
-        loss:  sum_b (2 |d| e_d + e_d^2) / (3 B)  +  (rowsum + loss_elem) sum_b (|d| + e_d)^2 / (3 B)
-        g_w2:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  +  rowsum sum_b 2 / (3 B) (|d| + e_d) (|h| + e_h)
+    gradient's right operand and exe what IT may be off by (float64).  Layer2 is dqn_ref.propagate_head's head (e_q, e_y,
+    e_d, the loss, g_w2, g_b2); from its d and e_d, layer1:
         dh:    e_dh[b][j] = 2 / (3 B) (e_d + elem (|d| + e_d)) |w2[a][j]|    d's error through w2[a]; elem: the scaling and
                                                                               the product dq * w2 round once each
         g_w1:  sum_b (e_dh (|xe| + e_xe) + |dh| e_xe)  +  rowsum sum_b (|dh| + e_dh) (|xe| + e_xe)
         g_b1:  the same with xe := 1, e_xe := 0."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd, tg = state["sd"], state["target"]
-    W, b, tw, tb = sd[W2].double(), sd[B2].double(), tg[W2].double(), tg[B2].double()
-    B = len(rw)
-    rows = torch.arange(B)
     a = act[:, 0].clamp(0, 2)
-    live = (~dn).double()
-    q = (h @ W.T + b)[rows, a]
-    qn = (hn @ tw.T + tb).max(dim=1).values
-    d = q - (rw.double() + discount * qn * live)
-    eq = (eh @ W.abs().T + own * ((h.abs() + eh) @ W.abs().T + b.abs()))[rows, a]
-    ey = discount * (ehn @ tw.abs().T + own * ((hn.abs() + ehn) @ tw.abs().T + tb.abs())).max(dim=1).values * live
-    ed = eq + ey + elem * (q.abs() + rw.double().abs() + discount * qn.abs() * live + eq + ey)
-    c = 2.0 / (3 * B)
-    out = {"loss": float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum() + (rowsum + loss_elem) * ((d.abs() + ed) ** 2 / (3 * B)).sum())}
-    per = c * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh + rowsum * (d.abs() + ed)[:, None] * (h.abs() + eh))
-    out[W2] = torch.zeros((3, 32), dtype=torch.float64).index_add_(0, a, per)
-    out[B2] = torch.zeros((3,), dtype=torch.float64).index_add_(0, a, c * (ed + rowsum * (d.abs() + ed)))
-    wa = W[a].abs()                                                      # [B, 32]
+    out = {}
+    out["loss"], out[W2], out[B2], d, ed = D.propagate_head(sd[W2], sd[B2], tg[W2], tg[B2], a, rw, (~dn).double(), discount,
+                                                            h, hn, eh, ehn, own, elem, rowsum, loss_elem)
+    c = 2.0 / (3 * len(rw))
+    wa = sd[W2].double()[a].abs()                                        # [B, 32]
     dh = c * d.abs()[:, None] * wa
     edh = c * (ed + elem * (d.abs() + ed))[:, None] * wa
     out[W1] = edh.T @ (xe.abs() + exe) + dh.T @ exe + rowsum * ((dh + edh).T @ (xe.abs() + exe))
@@ -183,17 +159,6 @@ def fp32_sum_bounds(state, batch, discount=0.5):
                    gamma(4))
 
 
-def worst_share(got, want, bound, keys=NAMES):
-    """max over the elements of |got - want| / bound (an element with a zero bound must be equal: inf otherwise)."""
-    worst = 0.0
-    for k in keys:
-        err = (got[k].double() - want[k].double()).abs()
-        bd = torch.as_tensor(bound[k], dtype=torch.float64)
-        share = torch.where(err == 0, torch.zeros_like(err), err / bd)
-        worst = max(worst, float(share.max()))
-    return worst
-
-
 # ---- the cases both test files share -----------------------------------------------------------------------------------
 def make_case(F, B, seed, N=None, dones="some", spread=True):
     """A net (model and a target that differs from it), a replay of N rows and B indices into it, on the CPU.
@@ -218,10 +183,6 @@ def make_case(F, B, seed, N=None, dones="some", spread=True):
           "none": torch.zeros((N,), dtype=torch.bool)}[dones]
     idx = torch.randint(0, N, (B,), generator=g)
     return state, (st, ast, act, rw, nst, nast, dn), idx
-
-
-def gather(arrays, idx):
-    return tuple(a[idx].numpy() for a in arrays)
 
 
 #: (F, B): the smallest shapes at which each seam of antsrl_exptrain.hip exists — one row, a partial and a full 32-row

@@ -12,13 +12,20 @@ from the order of fp32 sums alone (the bound of the shapes beyond F = 294: linea
 Both restatements take and update a `state` dict: sd (the six tensors under CollectModel's names), target_w3 / target_b3, m / v (Adam's
 moments of the four trained tensors, by name), step.  `batch` = (states [B, F], agent_states [B, 2], actions [B, 2],
 rewards [B], new_states, new_agent_states, dones [B]), already gathered.  Both return (loss, grads by name)."""
+from functools import partial
+
 import numpy as np
 import torch
+
+import dqn_ref as D
+from dqn_ref import U_BF16, U_FP32, bf16, gamma  # noqa: F401
+from dqn_ref import as_batch as _t
 
 NAMES = ("explore_model.layer1.weight", "explore_model.layer1.bias", "explore_model.layer2.weight",
          "explore_model.layer2.bias", "layer3.weight", "layer3.bias")
 TRAINED = NAMES[2:]
-U_BF16 = 2.0 ** -9  # bfloat16's unit roundoff (8 significand bits, round to nearest even)
+adam = partial(D.adam, TRAINED)                      # (state, grads, lr, betas, eps): Adam over the four trained tensors
+worst_share = partial(D.worst_share, keys=TRAINED)   # (got, want, bound)
 
 
 def new_state(sd):
@@ -29,29 +36,6 @@ def new_state(sd):
 
 def sync_target(state):
     state["target_w3"], state["target_b3"] = state["sd"]["layer3.weight"].clone(), state["sd"]["layer3.bias"].clone()
-
-
-def _t(batch):
-    st, ast, act, rw, nst, nast, dn = batch
-    f = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32)  # noqa: E731
-    B = len(rw)
-    return (f(st).reshape(B, -1), f(ast).reshape(B, 2), torch.as_tensor(np.asarray(act), dtype=torch.int64), f(rw),
-            f(nst).reshape(B, -1), f(nast).reshape(B, 2), torch.as_tensor(np.asarray(dn), dtype=torch.bool))
-
-
-def adam(state, grads, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
-    """torch.optim.Adam, single tensor, fp32 per element; the bias corrections in double."""
-    state["step"] += 1
-    t = state["step"]
-    bc1, bc2 = 1.0 - betas[0] ** t, 1.0 - betas[1] ** t
-    step_size, bc2_sqrt = np.float32(lr / bc1), np.float32(bc2 ** 0.5)
-    for k in TRAINED:
-        g = grads[k].to(torch.float32)
-        m, v = state["m"][k], state["v"][k]
-        m.lerp_(g, float(np.float32(1.0 - betas[0])))
-        v.mul_(float(np.float32(betas[1]))).addcmul_(g, g, value=float(np.float32(1.0 - betas[1])))
-        denom = (v.sqrt() / float(bc2_sqrt)).add_(float(np.float32(eps)))
-        state["sd"][k].addcdiv_(m, denom, value=-float(step_size))
 
 
 def fp32_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
@@ -76,10 +60,6 @@ def fp32_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps
     if update:
         adam(state, grads, lr, betas, eps)
     return float(loss.detach()), grads
-
-
-def bf16(x):
-    return torch.as_tensor(x, dtype=torch.float32).to(torch.bfloat16).to(torch.float32)
 
 
 def contract_hidden(sd, x, a):
@@ -124,47 +104,18 @@ def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999),
     return loss, grads
 
 
-def _propagate(head, act, rw, live, discount, h, hn, eh, ehn, own=0.0, elem=0.0, rowsum=0.0, loss_elem=0.0):
-    """One head's share of a forward error bound, carried to the loss and the gradient sums (bf16_bounds and
-    fp32_sum_bounds share it).  head = (W, b, next W, next b, column of act); h, hn the hidden values of the rows and of
-    their successors and eh, ehn what they may be off by (float64, [B, 32]).
-        e_q  = e_h |W|^T + own ((|h| + e_h) |W|^T + |b|)        own: the head's own sum (0: exact)
-        e_y  = discount max_o e_q' (max is 1-Lipschitz);  e_d = e_q[action] + e_y + elem (|q| + |reward| + discount |max q'| + e_q + e_y)
-        loss:  sum_b (2 |d| e_d + e_d^2) / (3 B)  +  (rowsum + loss_elem) sum_b (|d| + e_d)^2 / (3 B)
-        grad:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  +  rowsum sum_b 2 / (3 B) (|d| + e_d) (|h| + e_h)
-    (weights; h := 1, e_h := 0 for the biases).  Returns (loss bound, weight bound [3, 32], bias bound [3])."""
-    W, b, tw, tb, col = head
-    W, b, tw, tb = W.double(), b.double(), tw.double(), tb.double()
-    B = len(rw)
-    rows = torch.arange(B)
-    a = act[:, col]
-    q = (h @ W.T + b)[rows, a]
-    qn = (hn @ tw.T + tb).max(dim=1).values
-    d = q - (rw.double() + discount * qn * live)
-    eq = (eh @ W.abs().T + own * ((h.abs() + eh) @ W.abs().T + b.abs()))[rows, a]
-    ey = discount * (ehn @ tw.abs().T + own * ((hn.abs() + ehn) @ tw.abs().T + tb.abs())).max(dim=1).values * live
-    ed = eq + ey + elem * (q.abs() + rw.double().abs() + discount * qn.abs() * live + eq + ey)
-    loss = float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum() + (rowsum + loss_elem) * ((d.abs() + ed) ** 2 / (3 * B)).sum())
-    per = (2.0 / (3 * B)) * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh
-                             + rowsum * (d.abs() + ed)[:, None] * (h.abs() + eh))   # [B, 32]
-    gw = torch.zeros((3, 32), dtype=torch.float64)
-    gb = torch.zeros((3,), dtype=torch.float64)
-    gw.index_add_(0, a, per)
-    gb.index_add_(0, a, (2.0 / (3 * B)) * (ed + rowsum * (d.abs() + ed)))
-    return loss, gw, gb
-
-
-def _heads(state):
+def _heads(state, act):
+    """Per head what D.propagate_head takes first: (W, b, the target's W, b, the action taken)."""
     sd = state["sd"]
-    return ((sd[NAMES[2]], sd[NAMES[3]], sd[NAMES[2]], sd[NAMES[3]], 0),          # rotation: the target net shares layer2
-            (sd[NAMES[4]], sd[NAMES[5]], state["target_w3"], state["target_b3"], 1))
+    return ((sd[NAMES[2]], sd[NAMES[3]], sd[NAMES[2]], sd[NAMES[3]], act[:, 0]),  # rotation: the target net shares layer2
+            (sd[NAMES[4]], sd[NAMES[5]], state["target_w3"], state["target_b3"], act[:, 1]))
 
 
 def bf16_bounds(state, batch, discount=0.5):
     """How far the contract may stand from fp32, from bfloat16's unit roundoff u = 2^-9 alone.  x and w1 are each
     rounded once, so a product is off by at most (2 u + u^2) |x w|:
         e_h  = (2 u + u^2) (|x| |w1|^T)                         per hidden value           [B, 32]
-    carried through the heads, the TD target, the loss and the gradient sums by _propagate, with d, h taken from the
+    carried through the heads, the TD target, the loss and the gradient sums by dqn_ref.propagate_head, with d, h taken from the
     fp32 forward.  fp32 summation adds a slack of the order 2^-24 * (terms) on top, far below (fp32_sum_bounds)."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd = state["sd"]
@@ -176,18 +127,10 @@ def bf16_bounds(state, batch, discount=0.5):
     h, hn = hfun(st, ast), hfun(nst, nast)
     live = (~dn).double()
     out = {}
-    for i, head in enumerate(_heads(state)):
-        out[("loss", i)], out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = _propagate(head, act, rw, live, discount, h, hn, eh, ehn)
+    for i, head in enumerate(_heads(state, act)):
+        out[("loss", i)], out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = D.propagate_head(*head, rw, live, discount, h, hn, eh, ehn)[:3]
     out["h"] = eh
     return out
-
-
-U_FP32 = 2.0 ** -24  # fp32's unit roundoff
-
-
-def gamma(n, u=U_FP32):
-    """Higham's gamma_n = n u / (1 - n u): n roundings of relative size u compound to at most this."""
-    return n * u / (1.0 - n * u)
 
 
 def fp32_sum_bounds(state, batch, discount=0.5):
@@ -201,7 +144,7 @@ def fp32_sum_bounds(state, batch, discount=0.5):
         y, d     a rounding each for discount * max, + reward, q - y, and the restatement's own: 4 u on the operands
         rows     gamma(B + 2) sum_b |term|: B - 1 additions, the product, the 2 / (3 B) scaling and the restatement's rounding
         loss     gamma(4) more per term: d * d, * 1 / (3 B), twice, and the sum of the two heads
-    carried to d, the loss and the gradients by _propagate, as bf16_bounds carries 2 u + u^2."""
+    carried to d, the loss and the gradients by dqn_ref.propagate_head, as bf16_bounds carries 2 u + u^2."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd = state["sd"]
     B, F = st.shape
@@ -213,9 +156,9 @@ def fp32_sum_bounds(state, batch, discount=0.5):
     (h, eh), (hn, ehn) = hidden(st, ast), hidden(nst, nast)
     live = (~dn).double()
     out = {"loss": 0.0}
-    for i, head in enumerate(_heads(state)):
-        loss, out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = _propagate(
-            head, act, rw, live, discount, h, hn, eh, ehn, own=gamma(34), elem=4 * U_FP32, rowsum=gamma(B + 2), loss_elem=gamma(4))
+    for i, head in enumerate(_heads(state, act)):
+        loss, out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = D.propagate_head(
+            *head, rw, live, discount, h, hn, eh, ehn, own=gamma(34), elem=4 * U_FP32, rowsum=gamma(B + 2), loss_elem=gamma(4))[:3]
         out["loss"] += loss
     return out
 

@@ -17,6 +17,7 @@ import os
 import numpy as np
 import torch
 
+from dqn_ref import RING, U_FP32, gamma  # noqa: F401
 from memory_policy_ref import LAYERS, rebuild_seeded
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contract", "memory_train_ref.npz")
@@ -39,8 +40,7 @@ def fixture_batch(rec, c):
     """The minibatch of call c: (states, agent_states, actions, rewards, new_states, new_agent_states, dones) tensors."""
     pos = {int(r): i for i, r in enumerate(rec["rows/index"])}
     sel = np.array([pos[int(i)] for i in rec["c%d/idx" % c]])
-    names = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
-    return tuple(torch.from_numpy(np.ascontiguousarray(rec["rows/" + k][sel])) for k in names)
+    return tuple(torch.from_numpy(np.ascontiguousarray(rec["rows/" + k][sel])) for k in RING)
 
 
 def _x(st, ast):
@@ -172,12 +172,7 @@ FWD_LAUNCH = ((0,), (1,), (2,), (3,), (4, 7), (5, 8), (6,))   # the layers of th
 BWD_LAUNCH = ((6, 8), (5,), (4,), (3,), (2,), (1,))           # dOut of these layers -> dOut of their input layer
 DOUT_ORDER = (0, 1, 2, 3, 4, 5, 6, 7, 8)                      # dh1 dh2 dh3 dg dr1 dr2 dqr dp1 dqp = dOut of layer 0..8
 STAGES = tuple("fwd%d" % i for i in range(7)) + ("td",) + tuple("bwd%d" % i for i in range(6)) + ("wgrad", "finalize")
-U_FP32 = 2.0 ** -24
 TINY = 2.0 ** -126  # the smallest normal float: an MFMA may flush a subnormal product or sum
-
-
-def gamma(n, u=U_FP32):
-    return n * u / (1.0 - n * u)
 
 
 def _r(v, a):

@@ -1,7 +1,6 @@
 """The explore agent on the device: ExploreTrainer against the device-contract restatement and the
 reference's arithmetic (tests/explore_train_ref.py), ExploreAgent's acting and fused loop, standalone and in-loop, and the
 hand-over of its layer1 to CollectAgent."""
-import ctypes as C
 import os
 import sys
 
@@ -9,20 +8,16 @@ import numpy as np
 import pytest
 
 import explore_train_ref as X
+from agent_harness import drive_loop, inloop_runs
+from agent_harness import make_env as _env
+from agent_harness import param_tolerance as _param_tolerance
+from agent_harness import ptr as _p
+from agent_harness import same_rings as _same_rings
+from agent_harness import stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 SENTINEL = 12345.0
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _trainer(state, F, discount=0.5, lr=1e-4):
@@ -54,13 +49,6 @@ def _make(name):
     batch = X.gather_clamped(arrays, idx, B)
     dev = tuple(a.cuda().contiguous() for a in arrays)
     return state, dev, (None if idx is None else idx.cuda()), discount, B, F, batch
-
-
-def _param_tolerance(ref_after, before):
-    """Device and torch evaluate the same fp32 expression p + -step_size * (m / denom) from bit-equal m and v; they may
-    round the update term differently by an ulp or two of the UPDATE, and the sum then lands on a neighbouring float:
-    one ulp of the parameter, 2^-23 |p|, plus 4 ulps of the update itself for parameters smaller than their update."""
-    return 2.0 ** -23 * (ref_after.abs() + 4 * (ref_after - before).abs())
 
 
 # ---- 1. the step against the contract, and equal bits
@@ -144,18 +132,6 @@ def test_twenty_steps_against_the_references_arithmetic():
 
 
 # ---- 3. acting
-def _env(E=4, N=64, max_time=2000, seed=5, dtype=None, meta=False):
-    import torch
-    from antsrl_amd import config as cm
-    from antsrl_amd.batched import BatchedAntsEnv
-    from antsrl_amd.synth import synth_init
-    kw = dict(act_path=cm.ACT_CELL_META) if meta else {}
-    cfg = cm.make_cfg(E, N, 64, 64, deposit_strength=256.0, max_time=max_time, **kw)
-    env = BatchedAntsEnv(cfg, obs_dtype=dtype or torch.float32)
-    env.reset(synth_init(cfg, seed=seed, n_food_discs=6, food_rmin=3, food_rmax=6))
-    return env
-
-
 def _agent(**kw):
     from antsrl_amd.agent import ExploreAgent
     return ExploreAgent(epsilon=0.5, learning_rate=1e-3, min_replay=500, replay_size=3000, seed=7, **kw)
@@ -191,104 +167,49 @@ def test_get_action_acts_with_the_target_net():
 
 
 # ---- 4. the loop
-def _same_rings(a, b):
-    import torch
-    for n in RING:
-        assert torch.equal(getattr(a, n), getattr(b, n)), n
-    assert (a.head, a.fill) == (b.head, b.fill)
-
-
 def test_the_loop_equals_the_loop_driven_entry_by_entry():
     import torch
     from antsrl_amd import _lib
     from antsrl_amd import config as cm
-    from antsrl_amd.replay import DeviceReplayMemory
     from antsrl_amd.train import ExploreTrainer
-    lib = _lib.load()
-    steps, E, N, max_time = 30, 4, 64, 12
-    env_a, env_b = _env(E, N, max_time), _env(E, N, max_time)
+    steps, E, N = 30, 4, 64
     ag = _agent()
-    ag.setup(env_a)
-    ag.initialize(env_a)
-    env_a.observe()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")  # the fused loop reads nothing back
-    losses, acts_a = [], []
-    try:
-        for t in range(steps):
-            losses.append(ag.rollout_step(env_a))
-            acts_a.append(ag._rot.clone())
-    finally:
-        torch.cuda.set_sync_debug_mode(0)
-    M, F = E * N, 294
-    tr = ExploreTrainer(F, env_b.device, lr=1e-3, seed=7)
-    rm = DeviceReplayMemory(3000, (7, 7, 6), [2], [2], device=env_b.device)
-    gen = torch.Generator(device=env_b.device)
-    gen.manual_seed(7)
-    act0 = torch.full((E, N, 2), 10.0, device=env_b.device)
-    env_b.set_activation(act0)
-    obs, ast, _ = env_b.observe()
-    scratch = torch.zeros((M,), dtype=torch.int8, device="cuda")
-    mine, acts, synced_after_done = [], [], []
-    for t in range(steps):
-        rot, _ = tr.policy.act(obs, ast)
-        rot = rot.reshape(-1).clone()
-        _lib.check(lib.antsrl_agent_select_actions(7, t, 0, E, N, 0.5, 3, 3, _p(rot), _p(scratch), None, _stream()))
-        acts.append(rot)
-        rm.record_pre(obs, ast, None, rot, None, n_envs=E, n_ants=N, seed=7, step=t)
-        done = env_b.query(cm.Q_TIMESTEP) == max_time
-        env_b.step_update(rot.view(E, N), None)
-        rm.record_post(env_b.obs, env_b.agent_state, None, env_b.reward.view(-1), env_b.done)
-        mine.append(tr.train(rm, done, minibatch=256, min_replay=500, generator=gen))
-        if done and tr.step_count:
-            synced_after_done.append(torch.equal(tr.target, tr.model))
-    assert len(rm) == min(3000, steps * M) and tr.step_count == steps - 1  # 256 rows after step 0: below min_replay
-    assert synced_after_done and all(synced_after_done) and tr.syncs >= 1  # the run crosses one done
-    for t, (x, y) in enumerate(zip(losses, mine)):
+    r = drive_loop(ag, ExploreTrainer, 256, False, lambda tr: torch.equal(tr.target, tr.model), steps, E, N, max_time=12)
+    tr, rm = r.trainer, r.ring
+    assert len(rm) == min(3000, steps * E * N) and tr.step_count == steps - 1  # 256 rows after step 0: below min_replay
+    assert r.synced_after_done and all(r.synced_after_done) and tr.syncs >= 1  # the run crosses one done
+    for t, (x, y) in enumerate(zip(r.losses, r.host_losses)):
         assert (x == 0 and y == 0) or float(x) == float(y), "step %d" % t
-    for t, (r0, r1) in enumerate(zip(acts_a, acts)):
+    for t, ((r0,), (r1,)) in enumerate(zip(r.acts, r.host_acts)):
         assert torch.equal(r0, r1), "actions, step %d" % t
     _same_rings(ag.replay_memory, rm)
     assert bool((rm.actions[:len(rm), 1] == 1).all())  # a NULL pheromone is stored as 1
     assert set(rm.actions[:len(rm), 0].unique().tolist()) <= {0, 1, 2}
     assert torch.equal(ag.trainer.model, tr.model) and torch.equal(ag.trainer._adam, tr._adam) and torch.equal(ag.trainer.target, tr.target)
-    assert torch.equal(env_a.obs, env_b.obs)
+    assert torch.equal(r.env_a.obs, r.env_b.obs)
     # no pheromone action ever reached the environment: the activation is what initialize set
     got = torch.empty((E, N, 2), dtype=torch.float32, device="cuda")
-    _lib.check(lib.antsrl_read_state(env_a._h, cm.S_ACTIVATION, _p(got), _stream()))
-    assert torch.equal(got, act0)
+    _lib.check(_lib.load().antsrl_read_state(r.env_a._h, cm.S_ACTIVATION, _p(got), _stream()))
+    assert torch.equal(got, r.activation)
 
 
 def test_inloop_equals_standalone():
     import torch
-    steps, E, N, max_time = 30, 4, 64, 12
-    runs = []
-    for inloop in (False, True):
-        env = _env(E, N, max_time, dtype=torch.bfloat16, meta=True)
-        ag = _agent(inloop=inloop, record_per_step=50)  # 50 rows per step: steps 0..8 stay below min_replay and do not train
-        ag.setup(env)
-        ag.initialize(env)
-        env.observe()
-        acts, losses, after_sync = [], [], 0
-        for t in range(steps):
-            v = ag.trainer.version
-            losses.append(ag.rollout_step(env))
-            acts.append(ag._rot.clone())
-            after_sync += int(t + 1 < steps and ag.trainer.version != v)  # the next step is the first after a sync
-        runs.append((ag, env, acts, losses, after_sync))
-    (a, ea, aa, la, _), (b, eb, ab, lb, after_sync) = runs
+    steps = 30
+    ra, rb = inloop_runs(_agent, False, steps, E=4, N=64, max_time=12)  # steps 0..8 stay below min_replay and do not train
+    a, b, after_sync = ra.agent, rb.agent, rb.after_sync
     # every step is an in-loop hit except the very first (its observation was produced before the loop) and the first
     # after each sync, training or not
     assert a.inloop_hits == 0 and after_sync >= 1 and b.inloop_hits == steps - 1 - after_sync
-    for r0, r1 in zip(aa, ab):
+    for (r0,), (r1,) in zip(ra.acts, rb.acts):
         assert torch.equal(r0, r1)
-    for x, y in zip(la, lb):
+    for x, y in zip(ra.losses, rb.losses):
         assert (x == 0 and y == 0) or float(x) == float(y)
     _same_rings(a.replay_memory, b.replay_memory)
     ta, tb = a.trainer, b.trainer
     assert torch.equal(ta.model, tb.model) and torch.equal(ta.target, tb.target) and torch.equal(ta._adam, tb._adam)
     assert (ta.step_count, ta.syncs) == (tb.step_count, tb.syncs) and ta.step_count > 0 and ta.syncs >= 1
-    assert torch.equal(ea.obs, eb.obs)
+    assert torch.equal(ra.env.obs, rb.env.obs)
     assert bool((a.replay_memory.actions[:len(a.replay_memory), 1] == 1).all())
 
 

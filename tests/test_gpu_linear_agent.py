@@ -2,7 +2,6 @@
 LinearTrainer against the device-contract restatement and the reference's recorded run (tests/linear_train_ref.py,
 golden/contract/linear_train_ref.npz), CollectAgent's acting against the recorded actions, and its fused loop against the
 same loop driven entry by entry, standalone and in-loop."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -10,11 +9,16 @@ import pytest
 
 import linear_train_ref as L
 import memory_agent_ref as R
+from agent_harness import drive_loop, inloop_runs
+from agent_harness import make_env as _env
+from agent_harness import ptr as _p
+from agent_harness import same_rings as _same_rings
+from agent_harness import stream as _stream
+from dqn_ref import RING
 
 pytestmark = pytest.mark.gpu
 
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contract", "linear_train_ref.npz")
-RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 
 # Bounds of test_step_equals_the_contract: about 4 x the worst figure the sweep prints (-s) on an MI355X, per batch size
 # (DESIGN §7.11 and profiles/linear_agent_c5.json list the measured values).  What they cover is the order of fp32 sums: the
@@ -24,15 +28,6 @@ BOUND_GRAD = {False: 8e-7, True: 2.8e-6}    # 1.99e-7        6.89e-7     max |g 
 BOUND_LOSS = {False: 5e-7, True: 2e-6}      # 1.21e-7        5.01e-7     |loss - loss_ref| / loss_ref
 BOUND_HEADS = 1e-4   # |p - p_ref| in units of one step of lr, from equal gradients: test_gpu_memory_train.py's bound
 #                      (measured worst 3.73e-5: one ulp of a head weight near 0.1 against a step of 1e-4)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ---- 1. select
@@ -60,13 +55,6 @@ def test_select_actions_equals_select_and_the_restatement(E, N, eps, step, base)
 
 
 # ---- 2. record
-def _same_rings(a, b, names=RING):
-    import torch
-    for n in names:
-        assert torch.equal(getattr(a, n), getattr(b, n)), n
-    assert (a.head, a.fill) == (b.head, b.fill)
-
-
 @pytest.mark.parametrize("P,bf16,pitch", [((7, 7, 6), False, 0), ((7, 7, 6), True, 0), ((7, 7, 7), False, 352),
                                           ((7, 7, 7), True, 384), ((3, 3, 1), False, 0)])
 def test_record_plain_equals_record(P, bf16, pitch):
@@ -258,18 +246,6 @@ def test_get_action_against_the_recorded_actions():
 
 
 # ---- 7. the loop
-def _env(E=4, N=64, max_time=2000, seed=5, dtype=None, meta=False):
-    import torch
-    from antsrl_amd import config as cm
-    from antsrl_amd.batched import BatchedAntsEnv
-    from antsrl_amd.synth import synth_init
-    kw = dict(act_path=cm.ACT_CELL_META) if meta else {}
-    cfg = cm.make_cfg(E, N, 64, 64, deposit_strength=256.0, max_time=max_time, **kw)
-    env = BatchedAntsEnv(cfg, obs_dtype=dtype or torch.float32)
-    env.reset(synth_init(cfg, seed=seed, n_food_discs=6, food_rmin=3, food_rmax=6))
-    return env
-
-
 def _agent(**kw):
     from antsrl_amd.agent import CollectAgent
     return CollectAgent(epsilon=0.5, learning_rate=1e-3, min_replay=500, replay_size=3000, seed=7, **kw)
@@ -285,82 +261,32 @@ def _same_agents(a, b):
 
 def test_the_loop_equals_the_loop_driven_entry_by_entry():
     import torch
-    from antsrl_amd import _lib
-    from antsrl_amd import config as cm
-    from antsrl_amd.replay import DeviceReplayMemory
     from antsrl_amd.train import LinearTrainer
-    lib = _lib.load()
-    steps, E, N, max_time = 36, 4, 64, 12
-    env_a, env_b = _env(E, N, max_time), _env(E, N, max_time)
+    steps, E, N = 36, 4, 64
     ag = _agent()
-    ag.setup(env_a)
-    ag.initialize(env_a)
-    env_a.observe()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")  # the fused loop reads nothing back
-    losses, acts_a = [], []
-    try:
-        for t in range(steps):
-            losses.append(ag.rollout_step(env_a))
-            acts_a.append((ag._rot.clone(), ag._ph.clone()))  # what the step acted with (device copies: no read-back)
-    finally:
-        torch.cuda.set_sync_debug_mode(0)
-    # ---- the same loop, host-driven, one entry at a time
-    M, F = E * N, 294
-    tr = LinearTrainer(F, env_b.device, lr=1e-3, seed=7)
-    rm = DeviceReplayMemory(3000, (7, 7, 6), [2], [2], device=env_b.device)
-    gen = torch.Generator(device=env_b.device)
-    gen.manual_seed(7)
-    env_b.set_activation(torch.full((E, N, 2), 10.0, device=env_b.device))
-    obs, ast, _ = env_b.observe()
-    mine, acts, synced_after_done = [], [], []
-    for t in range(steps):
-        rot, ph = tr.policy.act(obs, ast)
-        rot, ph = rot.reshape(-1).clone(), ph.reshape(-1).clone()
-        _lib.check(lib.antsrl_agent_select_actions(7, t, 0, E, N, 0.5, 3, 3, _p(rot), _p(ph), None, _stream()))
-        acts.append((rot, ph))
-        rm.record_pre(obs, ast, None, rot, ph, n_envs=E, n_ants=N, seed=7, step=t)
-        done = env_b.query(cm.Q_TIMESTEP) == max_time
-        env_b.step_update(rot.view(E, N), ph.view(E, N))
-        rm.record_post(env_b.obs, env_b.agent_state, None, env_b.reward.view(-1), env_b.done)
-        loss = tr.train(rm, done, minibatch=264, min_replay=500, generator=gen)
-        mine.append(loss)
-        if done and tr.step_count:
-            synced_after_done.append(torch.equal(tr.target_l3, tr.heads[99:198]))
-    assert len(rm) == min(3000, steps * M) and tr.step_count == steps - 1  # 256 rows after step 0: below min_replay
-    assert synced_after_done and all(synced_after_done)
-    for t, (x, y) in enumerate(zip(losses, mine)):
+    r = drive_loop(ag, LinearTrainer, 264, True, lambda tr: torch.equal(tr.target_l3, tr.heads[99:198]), steps, E, N, max_time=12)
+    tr, rm = r.trainer, r.ring
+    assert len(rm) == min(3000, steps * E * N) and tr.step_count == steps - 1  # 256 rows after step 0: below min_replay
+    assert r.synced_after_done and all(r.synced_after_done)
+    for t, (x, y) in enumerate(zip(r.losses, r.host_losses)):
         assert (x == 0 and y == 0) or float(x) == float(y), "step %d" % t
-    for t, ((r0, p0), (r1, p1)) in enumerate(zip(acts_a, acts)):
+    for t, ((r0, p0), (r1, p1)) in enumerate(zip(r.acts, r.host_acts)):
         assert torch.equal(r0, r1) and torch.equal(p0, p1), "actions, step %d" % t
     _same_rings(ag.replay_memory, rm)
     assert torch.equal(ag.trainer.heads, tr.heads) and torch.equal(ag.trainer._adam, tr._adam) and torch.equal(ag.trainer.target_l3, tr.target_l3)
-    assert torch.equal(env_a.obs, env_b.obs)
+    assert torch.equal(r.env_a.obs, r.env_b.obs)
 
 
 def test_inloop_equals_standalone():
     import torch
-    steps, E, N, max_time = 36, 4, 64, 12
-    runs = []
-    for inloop in (False, True):
-        env = _env(E, N, max_time, dtype=torch.bfloat16, meta=True)
-        ag = _agent(inloop=inloop, record_per_step=50)  # 50 rows per step: steps 0..9 stay below min_replay and do not train
-        ag.setup(env)
-        ag.initialize(env)
-        env.observe()
-        acts, losses = [], []
-        for t in range(steps):
-            losses.append(ag.rollout_step(env))
-            acts.append((ag._rot.clone(), ag._ph.clone()))
-        runs.append((ag, env, acts, losses))
-    (a, ea, aa, la), (b, eb, ab, lb) = runs
-    assert b.inloop_hits >= 8 and a.inloop_hits == 0  # the steps below min_replay took the observation kernel's actions
-    for (r0, p0), (r1, p1) in zip(aa, ab):
+    a, b = inloop_runs(_agent, True, steps=36, E=4, N=64, max_time=12)  # steps 0..9 stay below min_replay and do not train
+    assert b.agent.inloop_hits >= 8 and a.agent.inloop_hits == 0  # the steps below min_replay took the observation kernel's actions
+    for (r0, p0), (r1, p1) in zip(a.acts, b.acts):
         assert torch.equal(r0, r1) and torch.equal(p0, p1)
-    for x, y in zip(la, lb):
+    for x, y in zip(a.losses, b.losses):
         assert (x == 0 and y == 0) or float(x) == float(y)
-    _same_agents(a, b)
-    assert torch.equal(ea.obs, eb.obs) and a.trainer.step_count > 0
+    _same_agents(a.agent, b.agent)
+    assert torch.equal(a.env.obs, b.env.obs) and a.agent.trainer.step_count > 0
 
 
 # ---- 8. learning happens

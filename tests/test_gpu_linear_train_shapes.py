@@ -90,7 +90,7 @@ def test_step_is_inside_the_fp32_sum_bound(case):
     gd = {k: v.cpu() for k, v in tr.grad_dict().items()}
     err = {k: (gd[k].double() - g_ref[k].double()).abs() for k in L.TRAINED}
     gmax = max(float(g_ref[k].abs().max()) for k in L.TRAINED)
-    ratio = max(float(torch.where(err[k] == 0, torch.zeros_like(err[k]), err[k] / bound[k]).max()) for k in L.TRAINED)
+    ratio = L.worst_share(gd, g_ref, bound)
     L.adam(host, gd, tr.lr, tr.betas, tr.eps)
     st, after = tr.adam_state(), tr.state_dict()
     worst_p = max(float((after[k].cpu() - host["sd"][k]).abs().max()) for k in L.TRAINED) / tr.lr

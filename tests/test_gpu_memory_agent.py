@@ -9,15 +9,13 @@ import numpy as np
 import pytest
 
 import memory_agent_ref as R
+from agent_harness import make_env as _env
+from agent_harness import ptr as _p
+from agent_harness import same_rings as _same_rings
 
 pytestmark = pytest.mark.gpu
 
 CONTRACT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "contract")
-RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _select(seed, step, base, E, N, eps, rot, ph, old, new, explored=None, n_rot=3, n_ph=3):
@@ -90,13 +88,6 @@ def test_recording_the_references_own_run():
     assert np.array_equal(rm.dones[:160].cpu().numpy(), np.repeat(z["done"], n))
 
 
-def _same_rings(a, b):
-    import torch
-    assert (a.head, a.fill) == (b.head, b.fill), ((a.head, a.fill), (b.head, b.fill))
-    for k in RING:
-        assert torch.equal(getattr(a, k), getattr(b, k)), k
-
-
 @pytest.mark.parametrize("P,bf16,pitch", [((7, 7, 6), False, 0), ((7, 7, 7), False, 0), ((7, 7, 6), True, 0),
                                           ((7, 7, 7), True, 0), ((7, 7, 6), False, 320), ((7, 7, 7), False, 352),
                                           ((7, 7, 7), True, 384), ((3, 3, 1), False, 0), ((1, 1, 2), True, 0)])
@@ -138,17 +129,6 @@ def test_record_equals_extend(P, bf16, pitch):
     c.record_post(buf1, ast1, m1, rew, done.bool())
     d.extend(obs0.float(), torch.cat([ast0, m0], 1), (rot.long() + 1, None), rew, obs1.float(), torch.cat([ast1, m1], 1), done)
     _same_rings(c, d)
-
-
-def _env(E=4, N=64, max_time=2000, seed=5, dtype=None):
-    import torch
-    from antsrl_amd import config as cm
-    from antsrl_amd.batched import BatchedAntsEnv
-    from antsrl_amd.synth import synth_init
-    cfg = cm.make_cfg(E, N, 64, 64, deposit_strength=256.0, max_time=max_time)
-    env = BatchedAntsEnv(cfg, obs_dtype=dtype or torch.float32)
-    env.reset(synth_init(cfg, seed=seed, n_food_discs=6, food_rmin=3, food_rmax=6))
-    return env
 
 
 def _agent(state_memory="reference", **kw):

@@ -9,19 +9,12 @@ import numpy as np
 import pytest
 
 import memory_agent_plan_ref as P
+from agent_harness import make_env as _env
+from agent_harness import ptr as _p
+from agent_harness import same_rings as _same_rings
+from agent_harness import stream as _stream
 
 pytestmark = pytest.mark.gpu
-
-RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _plan(seed, step, base, E, N, eps):
@@ -145,17 +138,6 @@ def test_tile_list_forward_equals_the_full_forward(precision, bf16_obs, power, m
 
 
 # ---- the loop
-def _env(E=4, N=64, max_time=2000, seed=5, dtype=None):
-    import torch
-    from antsrl_amd import config as cm
-    from antsrl_amd.batched import BatchedAntsEnv
-    from antsrl_amd.synth import synth_init
-    cfg = cm.make_cfg(E, N, 64, 64, deposit_strength=256.0, max_time=max_time)
-    env = BatchedAntsEnv(cfg, obs_dtype=dtype or torch.float32)
-    env.reset(synth_init(cfg, seed=seed, n_food_discs=6, food_rmin=3, food_rmax=6))
-    return env
-
-
 def _agent(eps, state_memory="reference", **kw):
     from antsrl_amd.agent import MemoryAgent
     return MemoryAgent(epsilon=eps, discount=0.99, learning_rate=1e-3, min_replay=500, replay_size=3000, seed=7,
@@ -164,10 +146,7 @@ def _agent(eps, state_memory="reference", **kw):
 
 def _same_end_state(a, b):
     import torch
-    ra, rb = a.replay_memory, b.replay_memory
-    assert (ra.head, ra.fill) == (rb.head, rb.fill)
-    for k in RING:
-        assert torch.equal(getattr(ra, k), getattr(rb, k)), k
+    _same_rings(a.replay_memory, b.replay_memory)
     # masters of every parameter, Adam's moments and the packs live in these two state buffers
     assert torch.equal(a.trainer._model, b.trainer._model) and torch.equal(a.trainer._target, b.trainer._target)
     assert (a.trainer.step_count, a.trainer.syncs) == (b.trainer.step_count, b.trainer.syncs)

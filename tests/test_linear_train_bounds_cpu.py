@@ -117,11 +117,8 @@ def _state(inp):
 
 def _worst(loss, grads, loss_ref, g_ref, bound):
     """The largest |error| / bound over the loss and every gradient element (0 / 0 = 0; error over a zero bound = inf)."""
-    def ratio(err, b):
-        err, b = torch.as_tensor(err, dtype=torch.float64), torch.as_tensor(b, dtype=torch.float64)
-        return float(torch.where(err == 0, torch.zeros_like(err), err / b).max())
-    return max([ratio(abs(loss - loss_ref), bound["loss"])] +
-               [ratio((grads[k].double() - g_ref[k].double()).abs(), bound[k]) for k in L.TRAINED])
+    f64 = lambda v: torch.as_tensor(v, dtype=torch.float64)  # noqa: E731
+    return L.worst_share({**grads, "loss": f64(loss)}, {**g_ref, "loss": f64(loss_ref)}, bound, keys=L.TRAINED + ("loss",))
 
 
 def test_the_lds_crossing_has_a_width_on_each_side():
