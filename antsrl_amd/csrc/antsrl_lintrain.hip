@@ -38,8 +38,12 @@ __device__ __forceinline__ void lt_epilogue(const LinTrainArgs &a, const int t, 
         dqn_store_adam(a.heads, a.batch.grads, a.adam, t, total);
 }
 
+// One wave per SIMD (amdgpu_waves_per_eu(1, 1)): with two workgroups resident on a CU, about 1 launch in 17 at F = 294 and
+// 512 workgroups left ONE workgroup's 199 partials different from every other launch's, always one of the first 256
+// workgroups (the first on its CU), finite; with one wave per SIMD, 0 of 400 (profiles/dqn_launch_repeat.py; DESIGN §7.13: the mechanism is not known, the
+// condition is).  Up to 256 workgroups there was one wave per SIMD anyway.
 template <int NW> // waves per workgroup
-__global__ void __launch_bounds__(64 * NW) k_lintrain(const LinTrainArgs a)
+__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) k_lintrain(const LinTrainArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const DqnBatch &mb = a.batch;

@@ -62,8 +62,19 @@ def propagate_head(W, b, tw, tb, a, rw, live, discount, h, hn, eh, ehn, own=0.0,
         grad:  sum_b 2 / (3 B) (e_d (|h| + e_h) + |d| e_h)  +  rowsum sum_b 2 / (3 B) (|d| + e_d) (|h| + e_h)
     (weights; h := 1, e_h := 0 for the biases).  Returns (loss bound, weight bound [3, 32], bias bound [3], d [B], e_d [B]):
     d and e_d are what a layer in front of the head carries on."""
+    loss, gw, gb, d, ed = propagate_head_grouped(W, b, tw, tb, a, rw, live, discount, h, hn, eh, ehn,
+                                                 torch.zeros((len(rw),), dtype=torch.int64),
+                                                 torch.tensor([rowsum], dtype=torch.float64), own, elem, loss_elem)
+    return float(loss[0]), gw[0], gb[0], d, ed
+
+
+def propagate_head_grouped(W, b, tw, tb, a, rw, live, discount, h, hn, eh, ehn, group, rowsum, own=0.0, elem=0.0,
+                           loss_elem=0.0):
+    """propagate_head with the rows summed group by group: group [B] int64 names the sum a row goes into (a workgroup's
+    partial, say) and rowsum [G] float64 is the row-sum factor of each.  B in 2 / (3 B) and 1 / (3 B) stays the batch's.
+    Returns (loss bound [G], weight bound [G, 3, 32], bias bound [G, 3], d [B], e_d [B])."""
     W, b, tw, tb = W.double(), b.double(), tw.double(), tb.double()
-    B = len(rw)
+    B, G = len(rw), len(rowsum)
     rows = torch.arange(B)
     q = (h @ W.T + b)[rows, a]
     qn = (hn @ tw.T + tb).max(dim=1).values
@@ -71,13 +82,15 @@ def propagate_head(W, b, tw, tb, a, rw, live, discount, h, hn, eh, ehn, own=0.0,
     eq = (eh @ W.abs().T + own * ((h.abs() + eh) @ W.abs().T + b.abs()))[rows, a]
     ey = discount * (ehn @ tw.abs().T + own * ((hn.abs() + ehn) @ tw.abs().T + tb.abs())).max(dim=1).values * live
     ed = eq + ey + elem * (q.abs() + rw.double().abs() + discount * qn.abs() * live + eq + ey)
-    loss = float(((2 * d.abs() * ed + ed * ed) / (3 * B)).sum() + (rowsum + loss_elem) * ((d.abs() + ed) ** 2 / (3 * B)).sum())
-    per = (2.0 / (3 * B)) * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh
-                             + rowsum * (d.abs() + ed)[:, None] * (h.abs() + eh))   # [B, 32]
-    gw = torch.zeros((3, 32), dtype=torch.float64)
-    gb = torch.zeros((3,), dtype=torch.float64)
-    gw.index_add_(0, a, per)
-    gb.index_add_(0, a, (2.0 / (3 * B)) * (ed + rowsum * (d.abs() + ed)))
+
+    def sums(per, index, n):  # per [B, ...] -> [n, ...]: the rows of each index added up
+        return torch.zeros((n,) + per.shape[1:], dtype=torch.float64).index_add_(0, index, per)
+    loss = sums((2 * d.abs() * ed + ed * ed) / (3 * B), group, G) + (rowsum + loss_elem) * sums((d.abs() + ed) ** 2 / (3 * B), group, G)
+    c, slot = 2.0 / (3 * B), group * 3 + a  # a gradient row per group and action
+    fwd = sums(c * (ed[:, None] * (h.abs() + eh) + d.abs()[:, None] * eh), slot, 3 * G).view(G, 3, 32)
+    mag = sums(c * (d.abs() + ed)[:, None] * (h.abs() + eh), slot, 3 * G).view(G, 3, 32)
+    gw = fwd + rowsum[:, None, None] * mag
+    gb = sums(c * ed, slot, 3 * G).view(G, 3) + rowsum[:, None] * sums(c * (d.abs() + ed), slot, 3 * G).view(G, 3)
     return loss, gw, gb, d, ed
 
 

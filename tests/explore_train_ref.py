@@ -80,16 +80,25 @@ def contract_forward(state, batch, discount=0.5):
     return dict(h=h, hn=hn, q=q, qn=qn, a=a, d=q[torch.arange(len(rw)), a] - y, xe=bf16(torch.cat([st, ast], 1)))
 
 
-def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
-    f = contract_forward(state, batch, discount)
-    d, a, h = f["d"], f["a"], f["h"]
+def contract_backward(state, f):
+    """From contract_forward's f, in fp32: dq [B, 4] (dL/dq at the taken action, then the row's loss term) and
+    dh [B, 32] = dq w2[a], one product per element."""
+    d, a = f["d"], f["a"]
     B = len(d)
     scale, inv = float(np.float32(2.0 / (3.0 * B))), float(np.float32(1.0 / (3.0 * B)))
-    g = d * scale                                   # fp32
-    dq = torch.zeros((B, 3), dtype=torch.float32)
+    g = d * scale
+    dq = torch.zeros((B, 4), dtype=torch.float32)
     dq[torch.arange(B), a] = g
-    loss = float((d * d * inv).double().sum())
-    dh = g[:, None] * state["sd"][W2][a]            # fp32: one product per element
+    dq[:, 3] = d * d * inv
+    return dq, g[:, None] * state["sd"][W2][a]
+
+
+def contract_train_step(state, batch, discount=0.5, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, update=True):
+    f = contract_forward(state, batch, discount)
+    h = f["h"]
+    dq, dh = contract_backward(state, f)
+    loss = float(dq[:, 3].double().sum())
+    dq = dq[:, :3]
     grads = {W1: (dh.double().T @ f["xe"].double()).to(torch.float32), B1: dh.double().sum(0).to(torch.float32),
              W2: (dq.double().T @ h.double()).to(torch.float32), B2: dq.double().sum(0).to(torch.float32)}
     if update:
@@ -105,7 +114,8 @@ def _bounds(state, batch, discount, h, hn, eh, ehn, xe, exe, own, elem, rowsum, 
         dh:    e_dh[b][j] = 2 / (3 B) (e_d + elem (|d| + e_d)) |w2[a][j]|    d's error through w2[a]; elem: the scaling and
                                                                               the product dq * w2 round once each
         g_w1:  sum_b (e_dh (|xe| + e_xe) + |dh| e_xe)  +  rowsum sum_b (|dh| + e_dh) (|xe| + e_xe)
-        g_b1:  the same with xe := 1, e_xe := 0."""
+        g_b1:  the same with xe := 1, e_xe := 0.
+    Key "dh" holds e_dh."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd, tg = state["sd"], state["target"]
     a = act[:, 0].clamp(0, 2)
@@ -118,6 +128,7 @@ def _bounds(state, batch, discount, h, hn, eh, ehn, xe, exe, own, elem, rowsum, 
     edh = c * (ed + elem * (d.abs() + ed))[:, None] * wa
     out[W1] = edh.T @ (xe.abs() + exe) + dh.T @ exe + rowsum * ((dh + edh).T @ (xe.abs() + exe))
     out[B1] = edh.sum(0) + rowsum * (dh + edh).sum(0)
+    out["dh"] = edh  # [B, 32]: what dh itself may be off by
     return out
 
 
@@ -146,17 +157,110 @@ def fp32_sum_bounds(state, batch, discount=0.5):
         rows     gamma(B + 2) sum_b |term| for g_w2, g_b2, g_w1, g_b1 alike: B - 1 additions, the product, the
                  restatement's rounding (bf16 x is exact on both sides: e_xe = 0)
         loss     gamma(4) more per term."""
+    h, hn, eh, ehn, xe = _sum_bound_hidden(state, batch)
+    return _bounds(state, batch, discount, h, hn, eh, ehn, xe, torch.zeros_like(xe), gamma(34), 4 * U_FP32,
+                   gamma(len(batch[3]) + 2), gamma(4))
+
+
+def _sum_bound_hidden(state, batch):
+    """Layer1 under fp32_sum_bounds: h, h', what they may be off by, and xe (float64)."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
-    sd, tg = state["sd"], state["target"]
-    B, F = st.shape
+    F = st.shape[1]
 
     def hidden(w, x, a):
         xa = bf16(torch.cat([x, a], 1)).double()
         w1, b1 = bf16(w[W1]).double(), w[B1].double()
         return xa, xa @ w1.T + b1, gamma(F + 3) * (xa.abs() @ w1.abs().T + b1.abs())
-    (xe, h, eh), (_, hn, ehn) = hidden(sd, st, ast), hidden(tg, nst, nast)
-    return _bounds(state, batch, discount, h, hn, eh, ehn, xe, torch.zeros_like(xe), gamma(34), 4 * U_FP32, gamma(B + 2),
-                   gamma(4))
+    (xe, h, eh), (_, hn, ehn) = hidden(state["sd"], st, ast), hidden(state["target"], nst, nast)
+    return h, hn, eh, ehn, xe
+
+
+# ---- the workspace (antsrl_exptrain.hip): the forward stage's partials, then dh ---------------------------------------------
+OUT = 100   # what a workgroup of the forward stage sums over its rows: layer2's 99 gradients (w2 [3][32], b2 [3]), the loss
+PART = 104  # floats per workgroup in the workspace: OUT and four of padding
+
+
+def blocks(B):
+    """Workgroups of the forward stage (antsrl_exptrain_blocks): four tiles of 32 rows each, one per wave, no looping."""
+    return ((B + 31) // 32 + 3) // 4
+
+
+def work_layout(B):
+    """The workspace of a step on B rows: partials [blocks][PART] fp32 from byte 0, dh [B][32] fp32 at the next multiple
+    of 256 bytes, nothing behind row B - 1."""
+    dh = (blocks(B) * PART * 4 + 255) // 256 * 256
+    return dict(blocks=blocks(B), dh_offset=dh, bytes=dh + B * 32 * 4)
+
+
+def row_workgroup(B):
+    """[B] int64: tile t = b // 32 belongs to workgroup t // 4 (wave t % 4)."""
+    return torch.arange(B) // 128
+
+
+def row_terms(dq, h):
+    """dq [B, 4] (contract_backward's) and h [B, 32] -> [B, OUT]: what each row adds to the forward stage's outputs."""
+    B = len(dq)
+    h1 = torch.cat([h, torch.ones((B, 1), dtype=h.dtype)], 1)
+    return torch.cat([(dq[:, :3, None] * h1[:, None, :32]).reshape(B, 96), dq], 1)
+
+
+def device_order_sum(terms, B):
+    """terms [B, n] fp32 -> ([n], [blocks, n]): the row sums in the order of k_exptrain_fwd and the last workgroup of
+    k_exptrain_l1, and the workgroups' partials on the way (a wave's one tile row by row from zero, the workgroup's
+    four waves, then the workgroups)."""
+    nb = blocks(B)
+    pad = torch.zeros((nb * 128, terms.shape[1]), dtype=torch.float32)
+    pad[:B] = terms
+    pad = pad.view(nb, 4, 32, -1)
+    out = torch.zeros((nb, 4, terms.shape[1]), dtype=torch.float32)
+    for r in range(32):
+        out = out + pad[:, :, r]
+    part = torch.zeros((nb, terms.shape[1]), dtype=torch.float32)
+    for w in range(4):
+        part = part + out[:, w]
+    return ordered_sum(part), part
+
+
+def ordered_sum(part):
+    """[blocks, n] fp32 -> [n]: a sequential fp32 sum from 0.0 in workgroup order."""
+    s = torch.zeros((part.shape[1],), dtype=torch.float32)
+    for b in range(part.shape[0]):
+        s = s + part[b]
+    return s
+
+
+def expected_partials(state, batch, discount=0.5):
+    """[blocks, OUT] float64: every workgroup's partial from contract_forward's h and d, the products and the sums over
+    the workgroup's rows in float64."""
+    f = contract_forward(state, batch, discount)
+    B = len(f["d"])
+    dq, _ = contract_backward(state, f)
+    return torch.zeros((blocks(B), OUT), dtype=torch.float64).index_add_(0, row_workgroup(B), row_terms(dq.double(), f["h"].double()))
+
+
+def partial_bounds(state, batch, discount=0.5):
+    """fp32_sum_bounds' layer2 and loss for one workgroup's partial at a time, [blocks, OUT] float64: the terms summed over
+    that workgroup's rows only, with the batch's B in 2 / (3 B) and 1 / (3 B), and gamma(rows + 4 + 2) for the row sums,
+    rows being the workgroup's (the rows, the wave adds, the product and the restatement's rounding)."""
+    st, ast, act, rw, nst, nast, dn = _t(batch)
+    sd, tg = state["sd"], state["target"]
+    B = len(rw)
+    h, hn, eh, ehn, _ = _sum_bound_hidden(state, batch)
+    group = row_workgroup(B)
+    rowsum = gamma(torch.bincount(group, minlength=blocks(B)).double() + 6)
+    loss, gw, gb = D.propagate_head_grouped(sd[W2], sd[B2], tg[W2], tg[B2], act[:, 0].clamp(0, 2), rw, (~dn).double(), discount,
+                                            h, hn, eh, ehn, group, rowsum, own=gamma(34), elem=4 * U_FP32, loss_elem=gamma(4))[:3]
+    return torch.cat([gw.reshape(-1, 96), gb, loss[:, None]], 1)
+
+
+#: (F, B) at which the workspace is read back (test_gpu_dqn_train_workspace.py): two tiles in one workgroup, five
+#: workgroups narrow and at F = 294, the cap of 512 workgroups narrow and at F = 294, the widest rows
+WORKSPACE_SHAPES = ((17, 33), (17, 513), (294, 513), (17, 65536), (294, 65536), (1022, 33))
+
+
+def workspace_case(F, B):
+    """make_case at a WORKSPACE_SHAPES shape (a ring of 3000 rows under the large batches)."""
+    return make_case(F, B, 100 * F + B, N=3000 if B > 4096 else None)
 
 
 # ---- the cases both test files share -----------------------------------------------------------------------------------

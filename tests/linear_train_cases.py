@@ -59,6 +59,16 @@ CASES.append(_case("dones-all", 17, 264, 300, dones="all"))
 CASES.append(_case("dones-none", 17, 264, 300, dones="none"))
 IDS = [c["name"] for c in CASES]
 
+# The shapes at which the workspace is read back (test_gpu_dqn_train_workspace.py), the smallest at which each grid regime
+# of the gradient stage exists: 5 workgroups, the last with one tile on wave 0 and three idle waves; 17 tiles; 512
+# workgroups of one tile per wave, narrow and at F = 294 without and with dones; 1024 workgroups whose waves loop.
+WORKSPACE = [c for c in CASES if c["name"] in ("seam-F17-B513", "seam-F17-B544")]
+WORKSPACE.append(_case("full-F17-B65536", 17, 65536, 3000))
+WORKSPACE.append(_case("full-F294-B65536-dones-none", 294, 65536, 3000, dones="none", **_wide(294)))
+WORKSPACE.append(_case("full-F294-B65536", 294, 65536, 3000, **_wide(294)))
+WORKSPACE += [c for c in CASES if c["name"] == "gridcap-F17-B131233"]
+WORKSPACE_IDS = [c["name"] for c in WORKSPACE]
+
 
 def lds_bytes(F, nw=4):
     """Dynamic LDS of the gradient stage at width F (lt_lds, antsrl_lintrain.hip): W1 as bf16 [32][16 ksteps + 8], three

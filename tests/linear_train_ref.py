@@ -145,21 +145,116 @@ def fp32_sum_bounds(state, batch, discount=0.5):
         rows     gamma(B + 2) sum_b |term|: B - 1 additions, the product, the 2 / (3 B) scaling and the restatement's rounding
         loss     gamma(4) more per term: d * d, * 1 / (3 B), twice, and the sum of the two heads
     carried to d, the loss and the gradients by dqn_ref.propagate_head, as bf16_bounds carries 2 u + u^2."""
+    B = len(batch[3])
+    out = {"loss": 0.0}
+    for i, head in enumerate(_sum_bound_heads(state, batch, discount)):
+        loss, out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = D.propagate_head(
+            *head, own=gamma(34), elem=4 * U_FP32, rowsum=gamma(B + 2), loss_elem=gamma(4))[:3]
+        out["loss"] += loss
+    return out
+
+
+def _sum_bound_heads(state, batch, discount):
+    """Per head, propagate_head's arguments up to e_h' under fp32_sum_bounds: layer1 and what it may be off by."""
     st, ast, act, rw, nst, nast, dn = _t(batch)
     sd = state["sd"]
-    B, F = st.shape
+    F = st.shape[1]
     w1, b1 = bf16(sd[NAMES[0]]).double(), sd[NAMES[1]].double()
 
     def hidden(x, a):
         xa = bf16(torch.cat([x, a], 1)).double()
         return xa @ w1.T + b1, gamma(F + 3) * (xa.abs() @ w1.abs().T + b1.abs())
     (h, eh), (hn, ehn) = hidden(st, ast), hidden(nst, nast)
-    live = (~dn).double()
-    out = {"loss": 0.0}
-    for i, head in enumerate(_heads(state, act)):
-        loss, out[NAMES[2 + 2 * i]], out[NAMES[3 + 2 * i]] = D.propagate_head(
-            *head, rw, live, discount, h, hn, eh, ehn, own=gamma(34), elem=4 * U_FP32, rowsum=gamma(B + 2), loss_elem=gamma(4))[:3]
-        out["loss"] += loss
+    return [head + (rw, (~dn).double(), discount, h, hn, eh, ehn) for head in _heads(state, act)]
+
+
+# ---- the workspace of the gradient stage (antsrl_lintrain.hip): one row of partial sums per workgroup ----------------------
+OUT = 199   # what a workgroup sums over its rows: the 198 gradients in the flat block's order (w2 [3][32] at 0, b2 at 96,
+#             w3 [3][32] at 99, b3 at 195), then the loss term
+PART = 200  # floats per workgroup in the workspace: OUT and one of padding
+
+
+def blocks(B):
+    """Workgroups of the gradient stage (antsrl_lintrain_blocks): one up to 16 tiles of 32 rows, which then finishes the
+    step itself and leaves the workspace alone; else one per 4 tiles, at most 1024 (whose waves then loop)."""
+    ntiles = (B + 31) // 32
+    return 1 if ntiles <= 16 else min((ntiles + 3) // 4, 1024)
+
+
+def work_layout(B):
+    """The workspace of a step on B rows: partials [blocks][PART] fp32 from byte 0, nothing behind them."""
+    return dict(blocks=blocks(B), bytes=blocks(B) * PART * 4)
+
+
+def row_workgroup(B):
+    """[B] int64: the workgroup whose partial row b goes into.  Tile t = b // 32 belongs to wave t % (4 blocks) of the
+    grid, which is wave (t % (4 blocks)) % 4 of workgroup (t % (4 blocks)) // 4."""
+    return (torch.arange(B) // 32) % (4 * blocks(B)) // 4
+
+
+def device_order_sum(terms, B):
+    """terms [B, n] fp32 -> ([n], [blocks, n]): the row sums in the order of k_lintrain and k_lintrain_finish, and the
+    workgroups' partials on the way (a wave's tiles row by row, the workgroup's four waves, then the workgroups)."""
+    ntiles, nb = (B + 31) // 32, blocks(B)
+    waves = nb * 4
+    rounds = (ntiles + waves - 1) // waves
+    pad = torch.zeros((rounds * waves * 32, terms.shape[1]), dtype=torch.float32)
+    pad[:B] = terms
+    pad = pad.view(rounds, waves, 32, -1)  # tile t = round * waves + (block * 4 + wave in block)
+    out = torch.zeros((waves, terms.shape[1]), dtype=torch.float32)
+    for rd in range(rounds):
+        for r in range(32):
+            out = out + pad[rd, :, r]
+    out = out.view(nb, 4, -1)
+    part = torch.zeros((nb, terms.shape[1]), dtype=torch.float32)
+    for w in range(4):
+        part = part + out[:, w]
+    return ordered_sum(part), part
+
+
+def ordered_sum(part):
+    """[blocks, n] fp32 -> [n]: the finish, a sequential fp32 sum from 0.0 in workgroup order."""
+    s = torch.zeros((part.shape[1],), dtype=torch.float32)
+    for b in range(part.shape[0]):
+        s = s + part[b]
+    return s
+
+
+def row_terms(dq, h):
+    """dq [B, 7] (the six dL/dq and the row's loss term) and h [B, 32] -> [B, OUT]: what each row adds to the outputs."""
+    B = len(dq)
+    h1 = torch.cat([h, torch.ones((B, 1), dtype=h.dtype)], 1)
+    return torch.cat([(dq[:, :3, None] * h1[:, None, :32]).reshape(B, 96), dq[:, :3],
+                      (dq[:, 3:6, None] * h1[:, None, :32]).reshape(B, 96), dq[:, 3:7]], 1)
+
+
+def expected_partials(state, batch, discount=0.5):
+    """[blocks, OUT] float64: every workgroup's partial from contract_forward's h and d, the products and the sums over
+    the workgroup's rows in float64."""
+    f = contract_forward(state, batch, discount)
+    B = len(f["dr"])
+    scale, inv = float(np.float32(2.0 / (3.0 * B))), float(np.float32(1.0 / (3.0 * B)))
+    rows = torch.arange(B)
+    dq = torch.zeros((B, 7), dtype=torch.float32)
+    dq[rows, f["act"][:, 0]] = f["dr"] * scale
+    dq[rows, 3 + f["act"][:, 1]] = f["dp"] * scale
+    dq[:, 6] = f["dr"] * f["dr"] * inv + f["dp"] * f["dp"] * inv
+    return torch.zeros((blocks(B), OUT), dtype=torch.float64).index_add_(0, row_workgroup(B), row_terms(dq.double(), f["h"].double()))
+
+
+def partial_bounds(state, batch, discount=0.5):
+    """fp32_sum_bounds for one workgroup's partial at a time, [blocks, OUT] float64: its terms summed over that
+    workgroup's rows only, with the batch's B in 2 / (3 B) and 1 / (3 B), and gamma(rows + 4 + 2) for the row sums, rows
+    being the workgroup's: a term passes through at most that many roundings on its way into the partial (the rows of
+    its wave, the wave adds, the product) and the restatement adds its own."""
+    B = len(batch[3])
+    group = row_workgroup(B)
+    rowsum = gamma(torch.bincount(group, minlength=blocks(B)).double() + 6)
+    out = torch.zeros((blocks(B), OUT), dtype=torch.float64)
+    for i, head in enumerate(_sum_bound_heads(state, batch, discount)):
+        loss, gw, gb = D.propagate_head_grouped(*head, group, rowsum, own=gamma(34), elem=4 * U_FP32, loss_elem=gamma(4))[:3]
+        out[:, 99 * i: 99 * i + 96], out[:, 99 * i + 96: 99 * i + 99] = gw.reshape(-1, 96), gb
+        out[:, 198] += loss
     return out
 
 

@@ -1,7 +1,9 @@
 """The bounds the GPU tests of antsrl_exptrain_step rest on (tests/explore_train_ref.py), checked without a GPU:
 contract_train_step stays within bf16_bounds of the torch autograd step, two fp32 restatements of the contract in
 different row orders stay inside fp32_sum_bounds, and each of six defects a device could have leaves that bound at every
-case where it can bite.  -s prints the worst share of each bound."""
+case where it can bite; the same per workgroup of the forward stage (explore_train_ref.partial_bounds of
+expected_partials, at WORKSPACE_SHAPES, with the defect tile_to_wrong_workgroup on top).  -s prints the worst share of
+each bound."""
 import numpy as np
 import pytest
 import torch
@@ -9,6 +11,8 @@ import torch
 import explore_train_ref as X
 
 DEFECTS = ("target_h_from_model", "agent_columns_dropped", "no_g_b1", "dh_from_row_0", "dones_ignored", "scale_2_over_B")
+#: the defects that reach the forward stage's partials (layer2's gradients and the loss), and one that reaches nothing else
+PARTIAL_DEFECTS = ("target_h_from_model", "dones_ignored", "scale_2_over_B", "tile_to_wrong_workgroup")
 
 
 def _rowsum(terms, order):
@@ -62,8 +66,17 @@ def restate_fp32(state, batch, discount, order, defect=None):
         grads[X.W1][:, F:] = 0.0
     if defect == "no_g_b1":
         grads[X.B1] = torch.zeros((32,))
-    loss = float(_rowsum(d * d * float(np.float32(1.0 / (3.0 * B))), order))
-    return loss, grads, dict(a=a, dn=dn, d=d)
+    lterm = d * d * float(np.float32(1.0 / (3.0 * B)))
+    loss = float(_rowsum(lterm, order))
+    # the forward stage's partials: a workgroup's 128 rows in torch's order, or tile by tile in the device's
+    terms = X.row_terms(torch.cat([dq, lterm[:, None]], 1), h)
+    if defect == "tile_to_wrong_workgroup":  # tiles 0 and 4 change places: the first tiles of workgroups 0 and 1
+        terms = torch.cat([terms[128:160], terms[32:128], terms[0:32], terms[160:]])
+    if order == "torch":
+        part = torch.stack([terms[g:g + 128].sum(0) for g in range(0, B, 128)])
+    else:
+        part = X.device_order_sum(terms, B)[1]
+    return loss, grads, dict(a=a, dn=dn, d=d, part=part)
 
 
 def _cases():
@@ -116,3 +129,52 @@ def test_two_fp32_orders_stay_inside_the_sum_bound_and_every_defect_leaves_it(na
         assert share > 1.0, (defect, share)
     print("\n%-16s fp32 sum bound: clean restatements use %.3g of it, the mildest defect %.3g x" % (name, worst, least))
     assert worst <= 0.5  # the clean restatements use a small share: the bound is not so loose that it hides a defect
+
+
+# ---- the forward stage's partials: what test_gpu_dqn_train_workspace.py reads back from the workspace ------------------
+def _partial_share(part, want, bound):
+    """The largest |partial - expected| / bound over [workgroup][output] (0 / 0 = 0; an error over a zero bound = inf)."""
+    err = (part.double() - want).abs()
+    return float(torch.where(err == 0, torch.zeros_like(err), err / bound).max())
+
+
+@pytest.mark.parametrize("F,B", X.WORKSPACE_SHAPES)
+def test_the_workspace_layout_is_the_librarys(F, B):
+    import ctypes as C
+    from antsrl_amd import _lib
+    from antsrl_amd import build as buildmod
+    buildmod.build_hip()
+    ws = C.c_size_t()
+    assert _lib.load().antsrl_exptrain_sizes(F, B, None, C.byref(ws), None) == 0
+    W = X.work_layout(B)
+    assert ws.value == W["bytes"] == W["dh_offset"] + 128 * B
+    assert W["dh_offset"] % 256 == 0 and 0 <= W["dh_offset"] - W["blocks"] * X.PART * 4 < 256
+    assert W["blocks"] == -(-(-(-B // 32)) // 4) == int(X.row_workgroup(B).max()) + 1
+
+
+@pytest.mark.parametrize("F,B", X.WORKSPACE_SHAPES)
+def test_fp32_partials_stay_inside_the_per_partial_bound_and_every_defect_leaves_it(F, B):
+    state, arrays, idx = X.workspace_case(F, B)
+    batch = X.gather(arrays, idx)
+    want, bound = X.expected_partials(state, batch), X.partial_bounds(state, batch)
+    loss_c, g_c = X.contract_train_step(state, batch, update=False)
+    flat = torch.cat([g_c[X.W2].reshape(-1).double(), g_c[X.B2].double(), torch.tensor([loss_c], dtype=torch.float64)])
+    assert bool(((want.sum(0) - flat).abs() <= 2.0 ** -22 * want.abs().sum(0)).all())  # the contract's sums, cut by workgroup
+    worst = 0.0
+    for order in ("torch", "device"):
+        part = restate_fp32(state, batch, 0.5, order)[2]["part"]
+        assert part.shape == want.shape == bound.shape == (X.blocks(B), X.OUT)
+        worst = max(worst, _partial_share(part, want, bound))
+    assert worst <= 1.0, worst
+    least = float("inf")
+    for defect in PARTIAL_DEFECTS:
+        if defect == "tile_to_wrong_workgroup" and B <= 128:
+            continue  # one workgroup: there is no wrong one
+        part = restate_fp32(state, batch, 0.5, "device", defect)[2]["part"]
+        share = _partial_share(part, want, bound)
+        least = min(least, share)
+        assert share > 1.0, (defect, share)
+        if defect == "tile_to_wrong_workgroup":
+            out = ((part.double() - want).abs() > bound).any(dim=1).nonzero().view(-1).tolist()
+            assert out == [0, 1], out
+    print("\nF%d_B%d per-partial bound: clean restatements use %.3g of it, the mildest defect %.3g x" % (F, B, worst, least))

@@ -9,7 +9,8 @@ import pytest
 
 import linear_train_ref as L
 import memory_agent_ref as R
-from agent_harness import drive_loop, inloop_runs
+from agent_harness import drive_loop, inloop_runs, linear_snapshot, twin_report
+from agent_harness import random_linear_replay as _random_replay
 from agent_harness import make_env as _env
 from agent_harness import ptr as _p
 from agent_harness import same_rings as _same_rings
@@ -100,18 +101,6 @@ def test_record_plain_equals_record(P, bf16, pitch):
 
 
 # ---- 3. the training step against the contract
-def _random_replay(N, F, seed, with_done):
-    import torch
-    g = torch.Generator(device="cuda").manual_seed(seed)
-    st, nst = (torch.rand((N, F), device="cuda", generator=g) for _ in range(2))
-    st[torch.rand((N, F), device="cuda", generator=g) < 0.5] = 0.0  # observations are sparse
-    ast, nast = (torch.rand((N, 2), device="cuda", generator=g) * 4 - 2 for _ in range(2))
-    act = torch.randint(0, 3, (N, 2), device="cuda", generator=g)
-    rw = torch.randn((N,), device="cuda", generator=g)
-    dn = (torch.rand((N,), device="cuda", generator=g) < 0.3) if with_done else torch.zeros((N,), dtype=torch.bool, device="cuda")
-    return (st, ast, act, rw, nst, nast, dn), g
-
-
 def _host_state(tr):
     s = L.new_state({k: v.cpu() for k, v in tr.state_dict().items()})
     t = tr.target_state_dict()
@@ -154,7 +143,15 @@ def test_step_equals_the_contract(B, with_done):
     tw.target_l3.mul_(0.5)
     l2 = tw.grad(arrays, idx)
     tw.apply()
-    assert float(l2) == loss and torch.equal(tw.heads, tr.heads) and torch.equal(tw._adam, tr._adam) and torch.equal(tw.grads, tr.grads)
+
+    def why():  # (built on a failure only) above 512 rows the workspace tells which workgroups and outputs differ
+        if B <= 512:
+            return "grad() %.10g against step() %.10g" % (float(l2), loss)
+        return twin_report(linear_snapshot(tr, torch.tensor(loss), B), linear_snapshot(tw, l2, B))
+    assert float(l2) == loss, why()
+    assert torch.equal(tw.heads, tr.heads), why()
+    assert torch.equal(tw._adam, tr._adam), why()
+    assert torch.equal(tw.grads, tr.grads), why()
 
 
 # ---- 4. against the fixture, in fp32

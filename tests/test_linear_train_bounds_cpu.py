@@ -3,7 +3,7 @@
 Safe: two fp32 restatements of the contract, which differ from contract_train_step only in where sums round, lie inside
 the bound.  Layer1 is summed input by input in fp32 in one and in 16-input chunks (an exact chunk sum, one rounding: the
 MFMA's k-step) in the other; both sum the rows in fp32 in the device's order: a wave's tiles row by row, the workgroup's
-four waves, then the workgroups.
+four waves, then the workgroups (linear_train_ref.device_order_sum).
 
 Sharp: seven defective restatements, each one wrong thing a kernel could do, leave the bound on at least one gradient
 element or on the loss.  The condition, which holds for every case and is not relaxed for any: a defect that changes
@@ -15,7 +15,12 @@ alone, whatever the inputs: 2 / (3 * 32 * ntiles) for 2 / (3 B) scales every sum
 that IS the same number, and the test asserts equal bits.  Where 1 - B / (32 ntiles) < gamma(B + 2) (B = 131 233: 2.4e-4
 against 7.8e-3) the change is at most that share of sum |term| and so below the bound's row-sum part on every element; the
 test asserts that it moves the result and records that the bound cannot see it: at that size equal bits between
-grad + apply and step, and the device's own measured error, are what guard the scale.  No shape is skipped."""
+grad + apply and step, and the device's own measured error, are what guard the scale.  No shape is skipped.
+
+The same two halves hold per workgroup (linear_train_cases.WORKSPACE, the shapes at which test_gpu_dqn_train_workspace.py
+reads the workspace back): the restatements' partials lie inside linear_train_ref.partial_bounds of expected_partials, and
+every defect, tile_to_wrong_workgroup among them, leaves it on at least one partial.  There the tile-count scale is within
+reach at B = 131 233 too: a workgroup sums 256 rows at most, and gamma(262) is 1.6e-5."""
 import numpy as np
 import pytest
 import torch
@@ -44,31 +49,8 @@ def _layer1(xb, wb, chunked):
     return acc
 
 
-def _device_order_sum(terms, B):
-    """terms [B, n] fp32 -> [n]: the row sums in the order of k_lintrain and k_lintrain_finish."""
-    ntiles = (B + 31) // 32
-    blocks = 1 if ntiles <= 16 else min((ntiles + 3) // 4, 1024)
-    waves = blocks * 4
-    rounds = (ntiles + waves - 1) // waves
-    pad = torch.zeros((rounds * waves * 32, terms.shape[1]), dtype=torch.float32)
-    pad[:B] = terms
-    pad = pad.view(rounds, waves, 32, -1)  # tile t = round * waves + (block * 4 + wave in block)
-    out = torch.zeros((waves, terms.shape[1]), dtype=torch.float32)
-    for rd in range(rounds):
-        for r in range(32):
-            out = out + pad[rd, :, r]
-    out = out.view(blocks, 4, -1)
-    part = torch.zeros((blocks, terms.shape[1]), dtype=torch.float32)
-    for w in range(4):
-        part = part + out[:, w]
-    s = torch.zeros((terms.shape[1],), dtype=torch.float32)
-    for b in range(blocks):
-        s = s + part[b]
-    return s
-
-
 def restated(state, batch, discount, chunked=False, defect=None):
-    """The contract in fp32 throughout (loss float, grads by name), with one defect or none."""
+    """The contract in fp32 throughout (loss float, grads by name, the workgroups' partials), with one defect or none."""
     st, ast, act, rw, nst, nast, dn = L._t(batch)
     sd = state["sd"]
     B, F = st.shape
@@ -101,12 +83,12 @@ def restated(state, batch, discount, chunked=False, defect=None):
     dq[:, 6] = dr * dr * inv + dp * dp * inv
     if defect == "last_row_left_out":
         dq[B - 1] = 0.0
-    h1 = torch.cat([h, torch.ones((B, 1))], 1)
-    terms = torch.cat([(dq[:, :3, None] * h1[:, None, :32]).reshape(B, 96), dq[:, :3],
-                       (dq[:, 3:6, None] * h1[:, None, :32]).reshape(B, 96), dq[:, 3:7]], 1)  # the 198 gradients, the loss
-    s = _device_order_sum(terms, B)
+    terms = L.row_terms(dq, h)  # the 198 gradients, the loss
+    if defect == "tile_to_wrong_workgroup":  # tiles 0 and 4 change places: the first tiles of workgroups 0 and 1
+        terms = torch.cat([terms[128:160], terms[32:128], terms[0:32], terms[160:]])
+    s, part = L.device_order_sum(terms, B)
     grads = {L.NAMES[2]: s[0:96].view(3, 32), L.NAMES[3]: s[96:99], L.NAMES[4]: s[99:195].view(3, 32), L.NAMES[5]: s[195:198]}
-    return float(s[198]), grads
+    return float(s[198]), grads, part
 
 
 def _state(inp):
@@ -133,7 +115,7 @@ def test_fp32_restatements_are_inside_the_bound(case):
     loss_ref, g_ref = L.contract_train_step(state, batch, case["discount"], update=False)
     bound = L.fp32_sum_bounds(state, batch, case["discount"])
     for chunked in (False, True):
-        loss, grads = restated(state, batch, case["discount"], chunked)
+        loss, grads, _ = restated(state, batch, case["discount"], chunked)
         w = _worst(loss, grads, loss_ref, g_ref, bound)
         print("%s, layer1 %s: worst error / bound %.3g" % (case["name"], "in 16-input chunks" if chunked else "sequential", w))
         assert w <= 1.0
@@ -151,9 +133,9 @@ def test_every_defect_leaves_the_bound(case):
         state, batch = _state(inp), K.gathered(inp, B)
         loss_ref, g_ref = L.contract_train_step(state, batch, discount, update=False)
         bound = L.fp32_sum_bounds(state, batch, discount)
-        loss, grads = restated(state, batch, discount, defect=defect)
+        loss, grads, _ = restated(state, batch, discount, defect=defect)
         if defect == "scale_by_tiles" and B % 32 == 0:  # the same number: 32 * ntiles == B
-            good_loss, good = restated(state, batch, discount)
+            good_loss, good, _ = restated(state, batch, discount)
             assert loss == good_loss and all(torch.equal(grads[k], good[k]) for k in L.TRAINED)
             continue
         w = _worst(loss, grads, loss_ref, g_ref, bound)
@@ -162,3 +144,63 @@ def test_every_defect_leaves_the_bound(case):
             assert w > 0.0  # a change, but one no summation-order bound can tell from a permitted order
             continue
         assert w > 1.0, (case["name"], defect, w)
+
+
+# ---- the workgroups' partials: what test_gpu_dqn_train_workspace.py reads back from the workspace ----------------------
+def _partial_share(part, want, bound):
+    """The largest |partial - expected| / bound over [workgroup][output] (0 / 0 = 0; an error over a zero bound = inf)."""
+    err = (part.double() - want).abs()
+    return float(torch.where(err == 0, torch.zeros_like(err), err / bound).max())
+
+
+@pytest.mark.parametrize("case", K.WORKSPACE, ids=K.WORKSPACE_IDS)
+def test_the_workspace_layout_is_the_librarys(case):
+    import ctypes as C
+    from antsrl_amd import _lib
+    from antsrl_amd import build as buildmod
+    buildmod.build_hip()
+    ws, launches = C.c_size_t(), C.c_int32()
+    assert _lib.load().antsrl_lintrain_sizes(case["F"], case["B"], None, C.byref(ws), C.byref(launches)) == 0
+    W = L.work_layout(case["B"])
+    assert ws.value == W["bytes"] == W["blocks"] * L.PART * 4 and launches.value == 2 and W["blocks"] > 1
+    group = L.row_workgroup(case["B"])
+    assert int(group.max()) == min(W["blocks"], (case["B"] + 127) // 128) - 1 and int(torch.bincount(group).max()) <= 128 * -(-case["B"] // (128 * W["blocks"]))
+
+
+@pytest.mark.parametrize("case", K.WORKSPACE, ids=K.WORKSPACE_IDS)
+def test_fp32_partials_are_inside_the_per_partial_bound(case):
+    inp = K.inputs(case)
+    state, batch = _state(inp), K.gathered(inp, case["B"])
+    want, bound = L.expected_partials(state, batch, case["discount"]), L.partial_bounds(state, batch, case["discount"])
+    loss_ref, g_ref = L.contract_train_step(state, batch, case["discount"], update=False)
+    total = want.sum(0)  # the partials are the contract's sums, cut by workgroup
+    flat = torch.cat([g_ref[k].reshape(-1).double() for k in L.TRAINED] + [torch.tensor([loss_ref], dtype=torch.float64)])
+    assert bool(((total - flat).abs() <= 2.0 ** -22 * want.abs().sum(0)).all())
+    for chunked in (False, True):
+        part = restated(state, batch, case["discount"], chunked)[2]
+        assert part.shape == want.shape == bound.shape == (L.blocks(case["B"]), L.OUT)
+        w = _partial_share(part, want, bound)
+        print("%s, layer1 %s: worst partial error / bound %.3g" % (case["name"], "in 16-input chunks" if chunked else "sequential", w))
+        assert w <= 1.0
+
+
+@pytest.mark.parametrize("case", [c for c in K.WORKSPACE if c["dones"] == "mixed"], ids=lambda c: c["name"])
+def test_every_defect_leaves_the_per_partial_bound(case):
+    """The condition of test_every_defect_leaves_the_bound, on the partials: a defect that changes a partial leaves that
+    partial's bound.  tile_to_wrong_workgroup changes no total beyond its rounding, and two partials entirely."""
+    B = case["B"]
+    inp = K.inputs(case, dones="mixed", discount=0.5)
+    state, batch = _state(inp), K.gathered(inp, B)
+    want, bound = L.expected_partials(state, batch, 0.5), L.partial_bounds(state, batch, 0.5)
+    good = restated(state, batch, 0.5, chunked=True)[2]
+    for defect in DEFECTS + ("tile_to_wrong_workgroup",):
+        part = restated(state, batch, 0.5, chunked=True, defect=defect)[2]
+        if defect == "scale_by_tiles" and B % 32 == 0:  # the same number: 32 * ntiles == B
+            assert torch.equal(part, good)
+            continue
+        w = _partial_share(part, want, bound)
+        print("%s, %s: worst partial error / bound %.3g" % (case["name"], defect, w))
+        assert w > 1.0, (case["name"], defect, w)
+        if defect == "tile_to_wrong_workgroup":
+            out = ((part.double() - want).abs() > bound).any(dim=1).nonzero().view(-1).tolist()
+            assert out == [0, 1], out
