@@ -23,7 +23,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_policy_memory_tiles", "antsrl_agent_plan", "antsrl_agent_select_actions",
            "antsrl_replay_record_pre_plain", "antsrl_replay_record_post_plain", "antsrl_lintrain_sizes",
            "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step", "antsrl_exptrain_sizes",
-           "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step")
+           "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step", "antsrl_rework_collapsed_bytes",
+           "antsrl_rework_collapse", "antsrl_policy_rework")
 
 _lib = None
 
@@ -31,6 +32,11 @@ _lib = None
 class AntsMemNetShape(C.Structure):
     """include/antsrl.h AntsMemNetShape."""
     _fields_ = [(n, C.c_int32) for n in ("n_features", "agent_dim", "mem_size", "h1", "h2", "h3", "n_rot", "n_ph")]
+
+
+class AntsReworkShape(C.Structure):
+    """include/antsrl.h AntsReworkShape."""
+    _fields_ = [(n, C.c_int32) for n in ("n_features", "agent_dim", "g1", "g2", "g3", "r1", "r2", "r3", "p1", "n_rot", "n_ph")]
 
 
 class AntsRecordSpec(C.Structure):
@@ -123,6 +129,9 @@ def load() -> C.CDLL:
     lib.antsrl_exptrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.antsrl_exptrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
                                                              C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.antsrl_rework_collapsed_bytes.argtypes = [C.POINTER(AntsReworkShape), sz]
+    lib.antsrl_rework_collapse.argtypes = [C.POINTER(AntsReworkShape), C.POINTER(vp), vp, vp]
+    lib.antsrl_policy_rework.argtypes = [C.POINTER(AntsReworkShape), vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

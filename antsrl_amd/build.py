@@ -19,13 +19,14 @@ LIB_PATH = os.path.join(LIB_DIR, "libantsrl_hip.so")
 SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl_sweep.hip", "antsrl_state.hip",
            "antsrl_capi.hip", "antsrl_policy.hip", "antsrl_mem.hip",
            "antsrl_memnet.hip", "antsrl_memnet_f32.hip", "antsrl_memtrain.hip", "antsrl_memagent.hip",
-           "antsrl_memapi.hip", "antsrl_lintrain.hip", "antsrl_exptrain.hip", "antsrl_linapi.hip"]
+           "antsrl_memapi.hip", "antsrl_lintrain.hip", "antsrl_exptrain.hip", "antsrl_linapi.hip",
+           "antsrl_rework.hip", "antsrl_reworkapi.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
                                            "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
-                                           "antsrl_exptrain.h")] + [
+                                           "antsrl_exptrain.h", "antsrl_rework.h")] + [
     os.path.join(HERE, "..", "include", "antsrl.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
@@ -39,7 +40,8 @@ def hipcc() -> str:
 
 
 #: host-only translation units (no kernel in them): a change there moves no byte on the device
-HOST_ONLY_SOURCES = ("antsrl_capi.hip", "antsrl_mem.hip", "antsrl_memapi.hip", "antsrl_linapi.hip")
+HOST_ONLY_SOURCES = ("antsrl_capi.hip", "antsrl_mem.hip", "antsrl_memapi.hip", "antsrl_linapi.hip",
+                     "antsrl_reworkapi.hip")
 
 
 def source_hash() -> str:

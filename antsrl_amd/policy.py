@@ -269,3 +269,120 @@ class MemoryPolicy:
                                                          fmt, _p(agent_state), _p(memory), m, _p(dst), _p(self._rot), _p(self._ph),
                                                          _p(q), _lib.stream(self.device)), "policy_memory_ex")
         return self._rot.view(lead), self._ph.view(lead), dst
+
+
+#: CollectModelRework's layers in its state_dict order (agents/collect_agent_rework.py:36-47): the order
+#: antsrl_rework_collapse takes them in
+REWORK_LAYERS = ("layer1", "layer2", "layer3", "layer4", "rotation_layer1", "rotation_layer2", "rotation_layer3",
+                 "rotation_layer4", "pheromone_layer1", "pheromone_layer2")
+
+
+def rework_shape_from_state_dict(sd) -> dict:
+    """AntsReworkShape's fields of a CollectModelRework state_dict, from its shapes alone (layer1: g1 x D with
+    D = n_features + 2), after checking that every layer's input is the width of the layer it is fed from."""
+    shp = {k: tuple(torch.as_tensor(v).shape) for k, v in sd.items()}
+    out = {l: shp[l + ".weight"][0] for l in REWORK_LAYERS}
+    D = shp["layer1.weight"][1]
+    s = dict(n_features=D - 2, agent_dim=2, g1=out["layer1"], g2=out["layer2"], g3=out["layer3"], r1=out["rotation_layer1"],
+             r2=out["rotation_layer2"], r3=out["rotation_layer3"], p1=out["pheromone_layer1"], n_rot=out["rotation_layer4"],
+             n_ph=out["pheromone_layer2"])
+    for name, want in rework_param_shapes(**{k: v for k, v in s.items() if k != "agent_dim"}).items():
+        assert shp[name + ".weight"] == want and shp[name + ".bias"] == want[:1], \
+            "%s: %s / %s, not %s" % (name, shp[name + ".weight"], shp[name + ".bias"], want)
+    return s
+
+
+def rework_param_shapes(n_features: int, n_rot: int = 3, n_ph: int = 3, g1: int = 64, g2: int = 128, g3: int = 32,
+                        r1: int = 64, r2: int = 128, r3: int = 32, p1: int = 32) -> dict:
+    """name -> (out, in) of every Linear of CollectModelRework (collect_agent_rework.py:36-47; its widths by default)."""
+    D = n_features + 2
+    return dict(layer1=(g1, D), layer2=(g2, g1), layer3=(g3, g2), layer4=(D, g3), rotation_layer1=(r1, D),
+                rotation_layer2=(r2, r1), rotation_layer3=(r3, r2), rotation_layer4=(n_rot, r3), pheromone_layer1=(p1, D),
+                pheromone_layer2=(n_ph, p1))
+
+
+class ReworkPolicy:
+    """The reference's `CollectModelRework` (agents/collect_agent_rework.py:24-63, the net main.py's CollectAgentRework
+    trains) evaluated on the device.  The net has no activation, so its ten layers are multiplied out once per weight
+    change (`antsrl_rework_collapse`, float64, rounded once to fp32: `collapsed_weight` [NQ, D], `collapsed_bias` [NQ],
+    NQ = n_rot + n_ph) and `act` is NQ fp32 dot products per ant (`antsrl_policy_rework`).
+
+    Weights are nn.Linear-initialised (seeded) or loaded with load_state_dict from the reference's own state_dict (its
+    parameter names, e.g. target_model.state_dict(); the widths come from its shapes)."""
+
+    def __init__(self, n_features: int, device, n_rot: int = 3, n_ph: int = 3, seed: int = 0):
+        g = torch.Generator(device="cpu")
+        g.manual_seed(seed)
+        self.n_features = n_features
+        self.device = torch.device(device)
+        sd = {}
+        for name, (out_f, in_f) in rework_param_shapes(n_features, n_rot, n_ph).items():
+            b = 1.0 / math.sqrt(in_f)  # nn.Linear's default init
+            sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
+            sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
+        self._lib = _lib.load()
+        self._rot = self._ph = None
+        self._set(sd)
+
+    def _set(self, sd):
+        shp = rework_shape_from_state_dict(sd)
+        assert shp["n_features"] == self.n_features, "state_dict is for %d features, not %d" % (shp["n_features"], self.n_features)
+        self.n_rot, self.n_ph = shp["n_rot"], shp["n_ph"]
+        self.params = {"%s.%s" % (l, w): torch.as_tensor(sd["%s.%s" % (l, w)]).to(self.device, torch.float32).contiguous()
+                       for l in REWORK_LAYERS for w in ("weight", "bias")}
+        self.shape = _lib.AntsReworkShape(*[shp[n] for n, _ in _lib.AntsReworkShape._fields_])
+        n = C.c_size_t()
+        _lib.check(self._lib.antsrl_rework_collapsed_bytes(C.byref(self.shape), C.byref(n)), "rework_collapsed_bytes")
+        self.collapsed = None
+        if self.device.type != "cuda":  # weights only (no kernel can run on them)
+            return
+        self.collapsed = torch.empty((n.value // 4,), dtype=torch.float32, device=self.device)
+        ptrs = (C.c_void_p * 20)(*[t.data_ptr() for t in self.params.values()])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_rework_collapse(C.byref(self.shape), ptrs, _p(self.collapsed),
+                                                        _lib.stream(self.device)), "rework_collapse")
+
+    def state_dict(self) -> dict:
+        return dict(self.params)
+
+    def load_state_dict(self, sd) -> None:
+        """A CollectModelRework state_dict (the reference's parameter names); the shapes are checked by name, then the
+        layers are collapsed again."""
+        self._set(sd)
+
+    @property
+    def collapsed_weight(self) -> torch.Tensor:
+        nq, D = self.n_rot + self.n_ph, self.n_features + 2
+        return self.collapsed[: nq * D].view(nq, D)
+
+    @property
+    def collapsed_bias(self) -> torch.Tensor:
+        nq, D = self.n_rot + self.n_ph, self.n_features + 2
+        return self.collapsed[nq * D: nq * D + nq]
+
+    def act(self, obs: torch.Tensor, agent_state: torch.Tensor, logits: Optional[torch.Tensor] = None, env=None):
+        """CollectAgentRework.get_action's network branch (:167-174): obs [..., P, P, K] float32 (or bfloat16 from a
+        BatchedAntsEnv(obs_dtype=torch.bfloat16)) and agent_state float32 [..., 2] on the device ->
+        (rotation int8 [...], pheromone int8 [...]), ready to pass to step().  `logits` (float32 [M, n_rot + n_ph])
+        receives both heads' q.  The returned tensors are reused buffers."""
+        assert self.collapsed is not None, "ReworkPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
+        lead = obs.shape[:-3]
+        m = 1
+        for d in lead:
+            m *= d
+        assert obs.is_contiguous() and agent_state.is_contiguous()
+        assert obs.dtype in (torch.float32, torch.bfloat16) and agent_state.dtype == torch.float32
+        if env is not None:
+            assert env.obs.dtype == obs.dtype, "obs and env.obs differ in dtype"
+        assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
+        if logits is not None:
+            assert logits.shape == (m, self.n_rot + self.n_ph) and logits.dtype == torch.float32 and logits.is_contiguous()
+        if self._rot is None or self._rot.numel() != m:
+            self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
+            self._ph = torch.empty((m,), dtype=torch.int8, device=self.device)
+        fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_policy_rework(C.byref(self.shape), _p(self.collapsed), _p(obs), fmt, _p(agent_state),
+                                                      m, _p(self._rot), _p(self._ph), _p(logits), _lib.stream(self.device)),
+                       "policy_rework")
+        return self._rot.view(lead), self._ph.view(lead)

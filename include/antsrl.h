@@ -822,6 +822,65 @@ int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, 
                          const int64_t *idx, int64_t B, float discount, int64_t step, double lr, double beta1, double beta2,
                          double eps, float *grads, float *loss, void *workspace, void *stream);
 
+/* The rework agent's net (no kernel counterpart in the reference; replaces the network branch of
+ * CollectAgentRework.get_action, agents/collect_agent_rework.py:165-174, which evaluates target_model's
+ * CollectModelRework.forward, :49-63, on the host).  Per ant, x = cat[obs.view(F), agent_state(2)], D = F + 2:
+ *     general = layer4(layer3(layer2(layer1(x))))                        D -> g1 -> g2 -> g3 -> D
+ *     q_rot   = rotation_layer4(rotation_layer3(rotation_layer2(rotation_layer1(general))))   D -> r1 -> r2 -> r3 -> n_rot
+ *     q_ph    = pheromone_layer2(pheromone_layer1(general))              D -> p1 -> n_ph
+ *     rotation = argmax(q_rot) - n_rot / 2,  pheromone = argmax(q_ph)    (first maximum on ties)
+ * The reference's class has g1, g2, g3 = r1, r2, r3 = 64, 128, 32 and p1 = 32.  There is no activation anywhere, so both
+ * heads are one affine map q = Wc x + bc, Wc [NQ][D], bc [NQ], NQ = n_rot + n_ph, the rotation rows first.  The layers are
+ * multiplied out once per weight change (antsrl_rework_collapse: float64, rounded once to float32) and every step is NQ
+ * fp32 dot products of length D per ant (antsrl_policy_rework).  There is one forward path: no layered mode, no precision
+ * switch.  Against the float64 layered forward the collapsed form is no further off than torch's own fp32 layered forward.
+ * Supported: n_features >= 1, agent_dim = 2, D <= 1024, every hidden width 1 .. 256, 1 <= n_rot, n_ph <= 8;
+ * ANTSRL_E_UNSUPPORTED for positive values outside that, ANTSRL_E_INVALID for values < 1, missing or misaligned pointers,
+ * an unknown obs_format and n_ants < 0.  Every check runs before any HIP call.  Each entry is one launch on `stream`: no
+ * host synchronisation, no allocation. */
+typedef struct AntsReworkShape {
+    int32_t n_features, agent_dim,
+            g1, g2, g3,      /* layer1..3 outputs: 64, 128, 32 in the reference's class */
+            r1, r2, r3,      /* rotation_layer1..3 outputs: 64, 128, 32 */
+            p1,              /* pheromone_layer1 output: 32 */
+            n_rot, n_ph;
+} AntsReworkShape;
+
+/* Size of the collapsed buffer (host only; no HIP call): 4 * (NQ * D + NQ) bytes, Wc float [NQ][D] then bc float [NQ].
+ * 7 128 bytes at F = 294, n_rot = n_ph = 3. */
+int antsrl_rework_collapsed_bytes(const AntsReworkShape *s, size_t *bytes);
+
+/* Multiplies the ten layers out (one small kernel, one workgroup per row of Wc).  params: host array of the 20 device
+ * pointers of CollectModelRework.state_dict() in its order (float32, nn.Linear layouts [out][in], 4-byte aligned):
+ * layer1..4, rotation_layer1..4, pheromone_layer1..2, each .weight then .bias.  collapsed: device buffer of
+ * antsrl_rework_collapsed_bytes bytes, 4-byte aligned.
+ * Row o of Wc starts as row o of its head's last layer (rotation_layer4 for o < n_rot, else pheromone_layer2 row
+ * o - n_rot), v, with bc = that layer's bias; v is pushed down through rotation_layer3, 2, 1 (pheromone_layer1), then
+ * layer4, 3, 2, 1.  A push through layer l (W_l [out][in], b_l [out]) is, in float64 with every product rounded before it
+ * is added and the contracted index i ascending,
+ *     bc <- ((bc + v[0] b_l[0]) + v[1] b_l[1]) + ...        v'[c] = ((0 + v[0] W_l[0][c]) + v[1] W_l[1][c]) + ...
+ * and Wc[o][c] = (float)v[c], bc[o] = (float)bc after the last: one rounding each.  No atomics: equal weights give equal
+ * bits in every launch.  Call it again whenever the weights change (the target net's: once per episode under the
+ * reference's UPDATE_TARGET_EVERY = 1). */
+int antsrl_rework_collapse(const AntsReworkShape *s, const float *const *params, void *collapsed, void *stream);
+
+/* The forward pass and both argmaxes for n_ants ants (get_action's target_model call and torch.max, :170-174).
+ * collapsed: what antsrl_rework_collapse wrote; obs: [n_ants][F], float32 (ANTSRL_OBS_F32) or bfloat16 (ANTSRL_OBS_BF16,
+ * widened exactly), dense, 4-byte aligned; agent_state float [n_ants][2]; rotation int8 [n_ants] = argmax - n_rot / 2 and
+ * pheromone int8 [n_ants], both required, directly usable as antsrl_step's actions; q_out float [n_ants][NQ] (rotation head
+ * then pheromone head) or NULL.  n_ants == 0 succeeds and launches nothing; n_ants < 2^31.
+ * Arithmetic is fp32 throughout.  Sixteen lanes share a row; with l the lane's place among them,
+ *     a_l = 0;  for k = 4 l .. 4 l + 3, then 64 + 4 l .. , ... ascending:  a_l = fmaf(x[k], Wc[o][k], a_l)
+ *     a = the a_l added pairwise: l with l ^ 1, then with l ^ 2, then with 7 - l inside its eight, then with 15 - l
+ *     q[o] = a + bc[o]
+ * so an ant's q and actions depend only on its own inputs and the collapsed buffer: not on n_ants, its place in the
+ * batch, its neighbours or the grid, nor on the observation format when the values are equal; a launch repeated gives
+ * the same bits.  No load touches a byte outside obs, agent_state and the collapsed buffer; nothing but rotation,
+ * pheromone and q_out is written. */
+int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
+                         const float *agent_state, int64_t n_ants, int8_t *rotation, int8_t *pheromone, float *q_out,
+                         void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
