@@ -3,7 +3,8 @@ reference's RLApi surface).  See DESIGN.md."""
 from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
-__all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer"]
+__all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
+           "ReworkTrainer"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -19,4 +20,7 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "ExploreTrainer":
         from .train import ExploreTrainer
         return ExploreTrainer
+    if name == "ReworkTrainer":
+        from .train import ReworkTrainer
+        return ReworkTrainer
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -23,6 +23,26 @@ struct ReworkParams {
     const float *p[2 * RW_LAYERS]; // the 20 tensors of CollectModelRework.state_dict(), in its order (weight, bias per layer)
 };
 
+struct __attribute__((packed, aligned(4))) RwF4 { float v[4]; }; // 4-byte aligned 16-byte load
+
+// a + (a of the lane that CTRL names), by a DPP move inside the row of 16 lanes
+template <int CTRL>
+__device__ __forceinline__ float rw_add_dpp(float a)
+{
+    const int other = __builtin_amdgcn_update_dpp(0, __float_as_int(a), CTRL, 0xf, 0xf, false);
+    return a + __int_as_float(other);
+}
+
+// the sum over a group of 16 lanes, in every lane of it: l ^ 1, l ^ 2, 7 - l within eight, 15 - l
+__device__ __forceinline__ float rw_group_sum(float a)
+{
+    a = rw_add_dpp<0xB1>(a);  // quad_perm [1, 0, 3, 2]
+    a = rw_add_dpp<0x4E>(a);  // quad_perm [2, 3, 0, 1]
+    a = rw_add_dpp<0x141>(a); // row_half_mirror
+    a = rw_add_dpp<0x140>(a); // row_mirror
+    return a;
+}
+
 // one launch each
 ANTSRL_INTERNAL hipError_t antsrl_launch_rework_collapse(const ReworkParams &P, const ReworkDims &d, float *collapsed,
                                                          hipStream_t st);

@@ -41,7 +41,6 @@
 #define RW_G 4              // chunks of a row whose loads are issued together
 #define RW_MAX_BLOCKS 1024  // 4 workgroups per CU, what 120 VGPRs admit; rows beyond are looped
 
-struct __attribute__((packed, aligned(4))) RwF4 { float v[4]; }; // 4-byte aligned 16-byte load
 typedef float rw_f32x2 __attribute__((ext_vector_type(2)));
 
 // inputs of layer l in the state_dict's order (its outputs are the inputs of the layer above it)
@@ -101,24 +100,6 @@ hipError_t antsrl_launch_rework_collapse(const ReworkParams &P, const ReworkDims
 {
     hipLaunchKernelGGL(k_rework_collapse, dim3(d.n_rot + d.n_ph), dim3(RW_TPB), 0, st, P, d, collapsed);
     return hipGetLastError();
-}
-
-// a + (a of the lane that CTRL names), by a DPP move inside the row of 16 lanes
-template <int CTRL>
-__device__ __forceinline__ float rw_add_dpp(float a)
-{
-    const int other = __builtin_amdgcn_update_dpp(0, __float_as_int(a), CTRL, 0xf, 0xf, false);
-    return a + __int_as_float(other);
-}
-
-// the sum over a group of 16 lanes, in every lane of it: l ^ 1, l ^ 2, 7 - l within eight, 15 - l
-__device__ __forceinline__ float rw_group_sum(float a)
-{
-    a = rw_add_dpp<0xB1>(a);  // quad_perm [1, 0, 3, 2]
-    a = rw_add_dpp<0x4E>(a);  // quad_perm [2, 3, 0, 1]
-    a = rw_add_dpp<0x141>(a); // row_half_mirror
-    a = rw_add_dpp<0x140>(a); // row_mirror
-    return a;
 }
 
 template <bool OBS16, int NQP>

@@ -1,15 +1,18 @@
 // antsrl_reworkapi.hip — the rework agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h, "The rework agent's
 // net"): antsrl_rework_collapsed_bytes, antsrl_rework_collapse and antsrl_policy_rework in front of antsrl_rework.hip's
-// two kernels.
+// two kernels, and behind them its training step ("The rework agent's training step"): antsrl_reworktrain_sizes / _grad /
+// _apply / _step in front of antsrl_reworktrain.hip's four, with the argument rules of the linear and explore agents'
+// (antsrl_linapi.hip).
 //
-// Host-side only: validates every argument before any HIP call and enqueues one kernel on the caller's stream.  No
-// handle, no allocation, no synchronisation, no exceptions across the ABI.
+// Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
+// allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
 #include "antsrl_rework.h"
+#include "antsrl_reworktrain.h"
 
 static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
 
@@ -80,4 +83,130 @@ extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collap
     return enqueued(antsrl_launch_rework_act((const float *)collapsed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
                                              (int)n_ants, rotation, pheromone, q_out, (hipStream_t)stream),
                     who);
+}
+
+// ---- the training step (antsrl_reworktrain.hip) ----------------------------------------------------------------------------
+
+#define RT_REQUIRE(p, align)                                                                                             \
+    do {                                                                                                                 \
+        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                                          \
+        if ((uintptr_t)(p) & ((align) - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
+    } while (0)
+
+static int rt_B(const char *who, int64_t B)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > RT_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, RT_MAX_B);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_reworktrain_sizes(const AntsReworkShape *s, int64_t B, size_t *params_floats, size_t *workspace_bytes,
+                                        int32_t *launches)
+{
+    const char *who = "reworktrain_sizes";
+    ReworkDims d;
+    int rc = rework_check(s, &d, who);
+    if (rc == ANTSRL_OK) rc = rt_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    ReworkTrainLayout L;
+    antsrl_reworktrain_layout(d, (int)B, &L);
+    if (params_floats) *params_floats = L.off[2 * RW_LAYERS];
+    if (workspace_bytes) *workspace_bytes = L.bytes;
+    if (launches) *launches = 4;
+    return ANTSRL_OK;
+}
+
+// the shape, the nets, the minibatch and the workspace of the gradient stage and the fused step
+static int rt_args(const char *who, const AntsReworkShape *s, float *model, const float *target_collapsed,
+                   const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                   const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                   const int64_t *idx, int64_t B, float discount, float *grads, bool grads_required, float *loss,
+                   void *workspace, ReworkTrainArgs *a)
+{
+    int rc = rework_check(s, &a->d, who);
+    if (rc == ANTSRL_OK) rc = rt_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    RT_REQUIRE(model, 4);
+    RT_REQUIRE(target_collapsed, 4);
+    RT_REQUIRE(workspace, 256);
+    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
+    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
+    RT_REQUIRE(states, 4);
+    RT_REQUIRE(agent_states, 4);
+    RT_REQUIRE(actions, 8);
+    RT_REQUIRE(rewards, 4);
+    RT_REQUIRE(new_states, 4);
+    RT_REQUIRE(new_agent_states, 4);
+    RT_REQUIRE(dones, 1);
+    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
+    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
+    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
+    RT_REQUIRE(loss, 4);
+    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
+    antsrl_reworktrain_layout(a->d, (int)B, &a->L);
+    a->states = states; a->agent_states = agent_states; a->rewards = rewards; a->new_states = new_states;
+    a->new_agent_states = new_agent_states; a->actions = actions; a->idx = idx; a->dones = dones;
+    a->grads = grads; a->loss = loss; a->work = (unsigned char *)workspace;
+    a->n_rows = n_rows;
+    a->B = (int)B;
+    a->discount = discount;
+    a->dq_rot = (float)(2.0 / ((double)a->d.n_rot * (double)B));
+    a->dq_ph = (float)(2.0 / ((double)a->d.n_ph * (double)B));
+    a->loss_rot = (float)(1.0 / ((double)a->d.n_rot * (double)B));
+    a->loss_ph = (float)(1.0 / ((double)a->d.n_ph * (double)B));
+    a->model = model; a->target = target_collapsed;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_reworktrain_grad(const AntsReworkShape *s, const float *model, const float *target_collapsed,
+                                       const float *states, const float *agent_states, const int64_t *actions,
+                                       const float *rewards, const float *new_states, const float *new_agent_states,
+                                       const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount,
+                                       float *grads, float *loss, void *workspace, void *stream)
+{
+    const char *who = "reworktrain_grad";
+    ReworkTrainArgs a = {};
+    const int rc = rt_args(who, s, const_cast<float *>(model), target_collapsed, states, agent_states, actions, rewards,
+                           new_states, new_agent_states, dones, n_rows, idx, B, discount, grads, true, loss, workspace, &a);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_reworktrain(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
+}
+
+extern "C" int antsrl_reworktrain_apply(const AntsReworkShape *s, float *model, float *adam_m, float *adam_v,
+                                        const float *grads, int64_t step, double lr, double beta1, double beta2, double eps,
+                                        void *stream)
+{
+    const char *who = "reworktrain_apply";
+    ReworkDims d;
+    int rc = rework_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    RT_REQUIRE(model, 4);
+    RT_REQUIRE(adam_m, 4);
+    RT_REQUIRE(adam_v, 4);
+    RT_REQUIRE(grads, 4);
+    AdamArgs o = {};
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o)) != ANTSRL_OK) return rc;
+    o.m = adam_m; o.v = adam_v;
+    ReworkTrainLayout L;
+    antsrl_reworktrain_layout(d, 1, &L);
+    return enqueued(antsrl_launch_adam(model, o, grads, (int)L.off[2 * RW_LAYERS], (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, const float *target_collapsed, float *adam_m,
+                                       float *adam_v, const float *states, const float *agent_states, const int64_t *actions,
+                                       const float *rewards, const float *new_states, const float *new_agent_states,
+                                       const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount,
+                                       int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
+                                       float *loss, void *workspace, void *stream)
+{
+    const char *who = "reworktrain_step";
+    ReworkTrainArgs a = {};
+    int rc = rt_args(who, s, model, target_collapsed, states, agent_states, actions, rewards, new_states, new_agent_states,
+                     dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
+    if (rc != ANTSRL_OK) return rc;
+    RT_REQUIRE(adam_m, 4);
+    RT_REQUIRE(adam_v, 4);
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    return enqueued(antsrl_launch_reworktrain(a, (hipStream_t)stream), who);
 }

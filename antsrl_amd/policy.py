@@ -310,18 +310,27 @@ class ReworkPolicy:
     Weights are nn.Linear-initialised (seeded) or loaded with load_state_dict from the reference's own state_dict (its
     parameter names, e.g. target_model.state_dict(); the widths come from its shapes)."""
 
-    def __init__(self, n_features: int, device, n_rot: int = 3, n_ph: int = 3, seed: int = 0):
+    def __init__(self, n_features: int, device, n_rot: int = 3, n_ph: int = 3, seed: int = 0, params=None):
+        """params: the 20 tensors (fp32, contiguous, on `device`, the reference's names) to ADOPT as they are instead of
+        initialising: the policy reads them where they lie (ReworkTrainer's target block) and `recollapse()` follows
+        their changes."""
         g = torch.Generator(device="cpu")
         g.manual_seed(seed)
         self.n_features = n_features
         self.device = torch.device(device)
+        self._lib = _lib.load()
+        self._rot = self._ph = None
+        if params is not None:
+            for t in params.values():
+                assert t.device.type == self.device.type and t.dtype == torch.float32 and t.is_contiguous()
+            self._set(params)
+            assert all(self.params[k] is params[k] for k in self.params), "adopted tensors are not copied"
+            return
         sd = {}
         for name, (out_f, in_f) in rework_param_shapes(n_features, n_rot, n_ph).items():
             b = 1.0 / math.sqrt(in_f)  # nn.Linear's default init
             sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
             sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
-        self._lib = _lib.load()
-        self._rot = self._ph = None
         self._set(sd)
 
     def _set(self, sd):
@@ -337,6 +346,11 @@ class ReworkPolicy:
         if self.device.type != "cuda":  # weights only (no kernel can run on them)
             return
         self.collapsed = torch.empty((n.value // 4,), dtype=torch.float32, device=self.device)
+        self.recollapse()
+
+    def recollapse(self) -> None:
+        """Multiplies the layers out again, into the same collapsed buffer: after the tensors of `params` changed in
+        place."""
         ptrs = (C.c_void_p * 20)(*[t.data_ptr() for t in self.params.values()])
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_rework_collapse(C.byref(self.shape), ptrs, _p(self.collapsed),

@@ -80,7 +80,7 @@ class _DqnTrainer:
 
     def launches(self, B: int) -> int:
         """Kernel launches of one step on B rows (antsrl_lintrain_sizes: 1 up to 512 rows, else 2; antsrl_exptrain_sizes:
-        2)."""
+        2; antsrl_reworktrain_sizes: 4)."""
         n = C.c_int32()
         self._sizes(B, None, C.byref(n))
         return n.value
@@ -528,4 +528,129 @@ class ExploreTrainer(_DqnTrainer):
                                                       self.lr, self.betas[0], self.betas[1], self.eps,
                                                       _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
                                                       _lib.stream(self.device)), "exptrain_step")
+        return loss
+
+
+class ReworkTrainer(_DqnTrainer):
+    """CollectAgentRework's model, target model and optimizer on the device (agents/collect_agent_rework.py:66-152;
+    defaults: the reference class's, discount 0.5, Adam lr 1e-4, minibatch 264), trained by `antsrl_reworktrain_step`
+    (antsrl_reworktrain.hip).
+
+    All ten layers are trained: one flat fp32 block of P floats per net (include/antsrl.h), the 20 state_dict tensors in
+    their order; the target net is a second block.  `policy` is the acting ReworkPolicy (get_action acts with the target
+    net, :170): its tensors are views of the TARGET block and its collapsed buffer is the one the training step takes
+    its TD targets from.  sync_target and load_state_dict copy the block and collapse once; a training step changes
+    neither the policy's collapsed buffer nor `version`, which counts the changes of the acting weights.
+
+    The surface is ExploreTrainer's: grad / apply / step, train(replay, done), train_on, launches, state_dict /
+    load_state_dict under CollectModelRework's twenty names (the hidden widths come from a state_dict's shapes),
+    target_state_dict, sync_target, adam_state, grad_dict."""
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, n_rot: int = 3, n_ph: int = 3, seed: int = 0,
+                 state_dict=None):
+        from .policy import ReworkPolicy, rework_param_shapes, rework_shape_from_state_dict
+        super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
+        self.version = 0
+        if state_dict is None:
+            state_dict = ReworkPolicy(n_features, "cpu", n_rot=n_rot, n_ph=n_ph, seed=seed).state_dict()
+        shp = rework_shape_from_state_dict(state_dict)
+        assert shp["n_features"] == n_features, "state_dict is for %d features, not %d" % (shp["n_features"], n_features)
+        self.n_rot, self.n_ph = shp["n_rot"], shp["n_ph"]
+        self.shape = _lib.AntsReworkShape(*[shp[n] for n, _ in _lib.AntsReworkShape._fields_])
+        self._offs, off = {}, 0
+        for name, (o, i) in rework_param_shapes(**{k: v for k, v in shp.items() if k != "agent_dim"}).items():
+            self._offs[name + ".weight"] = (off, (o, i))
+            self._offs[name + ".bias"] = (off + o * i, (o,))
+            off += o * i + o
+        pf = C.c_size_t()
+        _lib.check(self._lib.antsrl_reworktrain_sizes(C.byref(self.shape), 1, C.byref(pf), None, None), "reworktrain_sizes")
+        self.trained_floats = pf.value
+        assert self.trained_floats == off
+        self.model = torch.cat([torch.as_tensor(state_dict[k]).to(torch.float32).reshape(-1) for k in self._offs]).to(self.device)
+        self.target = self.model.clone()
+        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
+        self.policy = ReworkPolicy(n_features, self.device, params=self._views(self.target))  # acts on the target block
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def _views(self, flat) -> dict:
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self) -> dict:
+        """The model's 20 tensors (copies) under CollectModelRework's names, in its order."""
+        return {k: v.clone() for k, v in self._views(self.model).items()}
+
+    def target_state_dict(self) -> dict:
+        return {k: v.clone() for k, v in self._views(self.target).items()}
+
+    def load_state_dict(self, sd) -> None:
+        """CollectAgentRework.load_model (:186-188): sets the model AND the target net, and collapses the target once.
+        Adam's state is kept, as the reference's optimizer keeps it."""
+        for k, dst in self._views(self.model).items():
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+            dst.copy_(src)
+        self.target.copy_(self.model)
+        self.policy.recollapse()
+        self.version += 1
+
+    def adam_state(self) -> dict:
+        """torch.optim.Adam's state for the 20 tensors: step, exp_avg, exp_avg_sq (copies)."""
+        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
+                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
+
+    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
+        """The flat gradient (self.grads by default) as views named like the 20 tensors."""
+        return self._views(self.grads if grads is None else grads)
+
+    def sync_target(self) -> None:
+        """target := model (:147-150): one device copy of the block and one collapse; the acting policy's tensors are
+        views of the block."""
+        self.target.copy_(self.model)
+        self.policy.recollapse()
+        self.syncs += 1
+        self.version += 1
+
+    # ---- the stages ---------------------------------------------------------------------------------------------
+    def _sizes(self, B, workspace_bytes, launches):
+        _lib.check(self._lib.antsrl_reworktrain_sizes(C.byref(self.shape), B, None, workspace_bytes, launches),
+                   "reworktrain_sizes")
+
+    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The loss (0-d device tensor) and the gradients of all P floats into self.grads; nothing is updated.  Rows: as
+        MemoryTrainer.grad."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        loss = self._loss(loss)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_reworktrain_grad(C.byref(self.shape), _p(self.model), _p(self.policy.collapsed),
+                                                         _p(st), _p(ast), _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N,
+                                                         _p(idx), B, self.discount, _p(self.grads), _p(loss),
+                                                         _p(self._work), _lib.stream(self.device)), "reworktrain_grad")
+        return loss
+
+    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
+        """One Adam step on all P floats from the flat gradient (self.grads by default)."""
+        g = self._grads(grads)
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_reworktrain_apply(C.byref(self.shape), _p(self.model), _p(self._adam[0]),
+                                                          _p(self._adam[1]), _p(g), self.step_count, self.lr, self.betas[0],
+                                                          self.betas[1], self.eps, _lib.stream(self.device)),
+                       "reworktrain_apply")
+
+    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+             keep_grads: bool = True) -> torch.Tensor:
+        """One training step on the minibatch, gradient and Adam in the same four launches (antsrl_reworktrain_step):
+        returns the loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
+        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
+        loss = self._loss(loss)
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_reworktrain_step(C.byref(self.shape), _p(self.model), _p(self.policy.collapsed),
+                                                         _p(self._adam[0]), _p(self._adam[1]), _p(st), _p(ast), _p(act),
+                                                         _p(rw), _p(nst), _p(nast), _p(dn), N, _p(idx), B, self.discount,
+                                                         self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
+                                                         _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
+                                                         _lib.stream(self.device)), "reworktrain_step")
         return loss

@@ -881,6 +881,58 @@ int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const 
                          const float *agent_state, int64_t n_ants, int8_t *rotation, int8_t *pheromone, float *q_out,
                          void *stream);
 
+/* The rework agent's training step: CollectAgentRework.train (agents/collect_agent_rework.py:110-152) for the net above,
+ * all 20 tensors trained.  A net is ONE flat fp32 block of P floats (params_floats): the 20 tensors of the state_dict in its
+ * order (layer1..4, rotation_layer1..4, pheromone_layer1..2, each .weight [out][in] then .bias), dense.  `model` is such a
+ * block; adam_m, adam_v and grads are float [P], laid out the same way.  The TARGET net enters as its collapsed buffer
+ * (target_collapsed: what antsrl_rework_collapse wrote for it, the acting policy's), which is only read.
+ * Per minibatch row b (replay row i = idx[b], or b when idx is NULL; i is clamped to [0, n_rows); a_rot = actions[i][0]
+ * clamped to [0, n_rot), a_ph = actions[i][1] to [0, n_ph)), x = states[i] ++ agent_states[i], x' the successor's:
+ *     q  = Wc x + bc          the MODEL's collapsed form (float64 chain, rounded once: antsrl_rework_collapse's bits),
+ *     q' = Wc' x' + bc'       the target's; both in fp32 in antsrl_policy_rework's order of sums
+ *     per head (n outputs):   y = rewards[i] + discount * max(q'_head) * !dones[i],   d = q[a] - y,   g = d * (2 / (n B))
+ *     loss = sum_b d_rot^2 / (n_rot B) + sum_b d_ph^2 / (n_ph B)        MSELoss of both heads; each scale applied once
+ *     G [NQ][D] = sum_b (g_rot x at row a_rot, g_ph x at row n_rot + a_ph),   s [NQ] likewise without x       fp32
+ * The net has no activation, so with M_l [NQ][out_l] the head rows pushed down to layer l's output (antsrl_rework_collapse's
+ * v on its way; the unit rows at a head's last layer; zero in the other head's layers) and A_l [NQ][out_l] the pseudo-rows
+ * pushed up, A_l = A_in(l) W_l^T + s (x) b_l with A of x being G (in(l): layer4 for rotation_layer1 and pheromone_layer1),
+ *     dW_l = sum_k M_l[k] (x) A_in(l)[k],   db_l = sum_k M_l[k] s[k]
+ * k over all NQ pseudo-rows for layer1..4, over the head's own for its layers.  Both chains and these sums are float64, every
+ * product rounded before it is added, the contracted index (k here) ascending from zero, the bias term s[k] b_l[j] added
+ * last; each gradient is rounded once to fp32.  No B x width activation is stored.
+ * Order of the fp32 sums over rows (no atomics; equal inputs give equal bits whatever ran before): a workgroup of the batch
+ * pass takes the rows 16 (w + i parts) .. + 15, i = 0, 1, ..., and adds them in ascending order from zero, the product g x
+ * rounded first; the workgroups' partials are added in workgroup order from zero.
+ * Launches: four (down chain, batch pass, up chain, gradient with Adam).  workspace (256-byte aligned, workspace_bytes) is
+ * always needed; with NQ = n_rot + n_ph, out_l the outputs of layer l and every part rounded up to 256 bytes, in this order:
+ *     collapsed  float  [NQ D + NQ]                 the model's Wc, bc
+ *     M_l        double [NQ][out_l], l = 0..9
+ *     partials   float  [parts][stride]             parts = min(ceil(B / 16), 256), stride = NQ D + NQ + 2 rounded up to 64:
+ *                                                   G at 0, s at NQ D, sum d_rot^2 and sum d_ph^2 behind it
+ *     G, s       float  [NQ D + NQ]
+ *     A_l        double [NQ][out_l], l = 0..6 and 8
+ * Adam is antsrl_lintrain_*'s (antsrl_adam.h) on all P floats.  _grad followed by _apply gives the bits of _step.  The target
+ * sync is the caller's: a device copy of the block and one antsrl_rework_collapse.  Shapes: the net's supported range above;
+ * 1 <= B <= 65536 (above: ANTSRL_E_UNSUPPORTED).  Arrays as for antsrl_lintrain_*.  Every argument is checked before
+ * anything is launched; antsrl_reworktrain_sizes makes no HIP call; no host synchronisation.
+ *   _grad:  loss and grads; model is not written.
+ *   _apply: Adam on model from grads; step >= 1 is Adam's step count.
+ *   _step:  both in the same four launches (grads may be NULL). */
+int antsrl_reworktrain_sizes(const AntsReworkShape *s, int64_t B, size_t *params_floats, size_t *workspace_bytes,
+                             int32_t *launches);
+int antsrl_reworktrain_grad(const AntsReworkShape *s, const float *model, const float *target_collapsed, const float *states,
+                            const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                            const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx,
+                            int64_t B, float discount, float *grads, float *loss, void *workspace, void *stream);
+int antsrl_reworktrain_apply(const AntsReworkShape *s, float *model, float *adam_m, float *adam_v, const float *grads,
+                             int64_t step, double lr, double beta1, double beta2, double eps, void *stream);
+int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, const float *target_collapsed, float *adam_m,
+                            float *adam_v, const float *states, const float *agent_states, const int64_t *actions,
+                            const float *rewards, const float *new_states, const float *new_agent_states,
+                            const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount,
+                            int64_t step, double lr, double beta1, double beta2, double eps, float *grads, float *loss,
+                            void *workspace, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
