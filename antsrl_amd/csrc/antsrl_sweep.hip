@@ -566,6 +566,7 @@ k_sweep_sep2(const KP p, const float *__restrict__ in, float *__restrict__ out, 
 }
 
 // host-side launchers (called from antsrl_capi.hip)
+// (tests/sweep_ref.py: sweep_plan restates this geometry — kernel, strip width, segment rows — change both together)
 template <int C>
 static hipError_t launch_sweep_c(const KP &p, int cur, hipStream_t st)
 {

@@ -392,13 +392,7 @@ def test_config4_shape_radius3_vs_oracle(torch_mod):
     _compare_with_oracle(torch_mod, cfg, synth_init(cfg, seed=11), steps=6, seed=8, jitter_mode="builtin")
 
 
-def _stencil_filter(radius, separable, seed):
-    rng = np.random.default_rng(seed)
-    if separable:
-        f = np.outer(0.2 + rng.random(2 * radius + 1), 0.2 + rng.random(2 * radius + 1))  # asymmetric rank-1
-    else:
-        f = 0.1 + rng.random((2 * radius + 1, 2 * radius + 1))
-    return f / f.sum() * 0.97
+from sweep_ref import stencil_filter as _stencil_filter  # noqa: E402  (shared with the dense-field sweep tests)
 
 
 @pytest.mark.parametrize("radius,separable", [(1, False), (1, True), (2, True), (2, False), (3, True), (3, False)])
