@@ -4,7 +4,7 @@ from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
-           "ReworkTrainer"]
+           "ReworkTrainer", "ReworkAgent"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -23,4 +23,7 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "ReworkTrainer":
         from .train import ReworkTrainer
         return ReworkTrainer
+    if name == "ReworkAgent":
+        from .agent import ReworkAgent
+        return ReworkAgent
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

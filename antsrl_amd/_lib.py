@@ -25,7 +25,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step", "antsrl_exptrain_sizes",
            "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step", "antsrl_rework_collapsed_bytes",
            "antsrl_rework_collapse", "antsrl_policy_rework", "antsrl_reworktrain_sizes", "antsrl_reworktrain_grad",
-           "antsrl_reworktrain_apply", "antsrl_reworktrain_step")
+           "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select")
 
 _lib = None
 
@@ -134,6 +134,8 @@ def load() -> C.CDLL:
     lib.antsrl_rework_collapse.argtypes = [C.POINTER(AntsReworkShape), C.POINTER(vp), vp, vp]
     lib.antsrl_policy_rework.argtypes = [C.POINTER(AntsReworkShape), vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp]
     rs = C.POINTER(AntsReworkShape)
+    lib.antsrl_policy_rework_select.argtypes = [rs, vp, vp, i32, vp, C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, vp, vp,
+                                                vp, vp, vp]
     lib.antsrl_reworktrain_sizes.argtypes = [rs, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
     lib.antsrl_reworktrain_grad.argtypes = [rs] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
     lib.antsrl_reworktrain_apply.argtypes = [rs, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]

@@ -23,10 +23,11 @@ overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed
 `skip_explored` (off by default: skip the net for tiles whose ants all explore this step; results are unchanged).
 Exploration is drawn once per environment and step (an environment is one reference colony).
 
-`_DeviceAgent` holds what the three agents share (the hyper-parameters, the front of setup, the reference's surface
+`_DeviceAgent` holds what the agents share (the hyper-parameters, the front of setup, the reference's surface
 around get_action, and the fused loop); `_InLoopAgent` adds what the two memory-less agents share on top of it: their
 acting step and the bookkeeping of the in-loop policy's handle.  An agent writes its trainer, its get_action and what
-it keeps between steps.
+it keeps between steps.  `ReworkAgent` (CollectAgentRework, the agent main.py imports first) sits on `_DeviceAgent`
+directly: its net is ReworkPolicy's, and its acting step under exploration is one launch.
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ from . import _lib
 from ._lib import ptr as _p
 from . import config as cm
 from .replay import DeviceReplayMemory
-from .train import ExploreTrainer, LinearTrainer, MemoryTrainer
+from .train import ExploreTrainer, LinearTrainer, MemoryTrainer, ReworkTrainer
 
 
 def _backend(api_or_env):
@@ -424,3 +425,70 @@ class ExploreAgent(_InLoopAgent):
     def _refresh_due(self, training: bool) -> bool:
         """Always: the observation this step produces is acted on with these weights."""
         return True
+
+
+class ReworkAgent(_DeviceAgent):
+    """The rework agent on the device: CollectAgentRework (agents/collect_agent_rework.py:66-188, the agent main.py imports
+    first) with its net (ReworkPolicy: the ten layers collapsed once per weight change), its replay memory,
+    its epsilon-greedy step and its training step (ReworkTrainer, §7.15) resident on the GPU.
+
+    The reference class's surface (setup, initialize, get_action, update_replay_memory, train, save_model, load_model, a
+    settable epsilon) and _DeviceAgent's fused loop with no host synchronisation; the acting net is the target net
+    (:170), so the acting weights change at a sync or a load only.  `rotations` and `pheromones` are the heads' widths,
+    1 ... 8 each.
+
+    `fused_select` (on by default): a training step acts and selects in ONE launch (ReworkPolicy.act_select,
+    antsrl_policy_rework_select), which does not evaluate the net for the colonies that explore; off, it is the net on
+    the whole batch and antsrl_agent_select_actions behind it.  Both give the same actions, rings, weights and losses
+    bit for bit (§7.16).
+
+    Reference lines (collect_agent_rework.py): setup :87-103, initialize :105-107, train :110-152, update_replay_memory
+    :154-163, get_action :165-181, save_model :183-184 (the 20-tensor state_dict under CollectModelRework's names: the
+    reference's load_model loads it), load_model :186-188."""
+
+    def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
+                 learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
+                 fused_select: bool = True):
+        assert 1 <= rotations <= 8 and 1 <= pheromones <= 8, \
+            "the net's heads are 1 to 8 wide (antsrl_policy_rework), not %r and %r" % (rotations, pheromones)
+        super().__init__("collect_agent_rework", epsilon, discount, rotations, pheromones, learning_rate, record_per_step,
+                         replay_size, minibatch, min_replay, update_target_every, seed)
+        self.fused_select = fused_select
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """CollectAgentRework.setup (:87-103) for every ant of the batch."""
+        self._setup(api_or_env, [2])
+        self.trainer = ReworkTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+                                     update_target_every=self.update_target_every, n_rot=self.rotations,
+                                     n_ph=self.pheromones, seed=self.seed)
+        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    def get_action(self, obs, agent_state, training: bool, env=None):
+        """:165-180 -> (rotation int8, pheromone int8), views of the agent's own buffers.  The target net acts; with
+        `training` the colonies that explore this step (probability epsilon each, one draw per colony) take uniform
+        actions instead, the draws of the draw specification: in the same launch (`fused_select`), or by
+        antsrl_agent_select_actions behind the net."""
+        obs = self._obs(obs).contiguous()
+        ast = self._dev(agent_state, torch.float32).contiguous()
+        step = self.step_counter
+        lead = obs.shape[:-3]
+        out = (self._rot, self._ph)
+        if training and self.fused_select and self.epsilon > 0:
+            self.policy.act_select(obs, ast, seed=self.seed, step=step, env_id_base=self.env_id_base, n_envs=self.n_envs,
+                                   n_ants=self.n_ants_per_env, epsilon=self.epsilon, out=out, explored=self._explored, env=env)
+        else:
+            self.policy.act(obs, ast, env=env, out=out)
+            if training and self.epsilon > 0:
+                with torch.cuda.device(self.device):
+                    _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
+                                                                     self.n_ants_per_env, float(self.epsilon), self.rotations,
+                                                                     self.pheromones, _p(self._rot), _p(self._ph),
+                                                                     _p(self._explored), _lib.stream(self.device)),
+                               "agent_select_actions")
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), self._ph.view(lead)

@@ -24,7 +24,7 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
-                                           "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h",
+                                           "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_draw.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
                                            "antsrl_exptrain.h", "antsrl_rework.h", "antsrl_reworktrain.h")] + [
     os.path.join(HERE, "..", "include", "antsrl.h")]

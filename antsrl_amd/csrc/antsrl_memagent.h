@@ -39,3 +39,6 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_agent_select(const SelArgs &a, bool vec
 // the plan reads seed, step, epsilon, env_base, n_ants and M of `a` (select's own arguments: one env_explores for both)
 ANTSRL_INTERNAL hipError_t antsrl_launch_agent_plan(const SelArgs &a, int32_t *tiles, int32_t *n_live, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_replay_record(const RecArgs &a, bool obs_bf16, bool post, hipStream_t st);
+
+// host: n_envs, n_ants >= 1, n_envs * n_ants < 2^31, env_id_base >= 0, env_id_base + n_envs < 2^31 (antsrl_memapi.hip)
+ANTSRL_INTERNAL int antsrl_check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants);

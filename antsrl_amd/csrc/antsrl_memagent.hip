@@ -3,7 +3,7 @@
 // antsrl_agent_plan (the tiles of the batch that hold an ant of a non-exploring environment, for antsrl_policy_memory_tiles) and
 // antsrl_replay_record_pre / _post (update_replay_memory + ReplayMemory.extend, :178-187, replay_memory.py:83-114, as two
 // gathers of whole rows around the environment step).  The draw specification is written out in include/antsrl.h; the
-// device functions below are that text.
+// device functions of antsrl_draw.h are that text.
 //
 // k_replay_record: one wave per replay entry.  The entry's ant and ring row are wave-uniform (scalar registers); the
 // observation row is copied as 16-byte stores from the first 16-byte boundary of the DESTINATION row on, fed by 16-, 8-
@@ -16,19 +16,9 @@
 // re-reads them before a training step samples them).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_draw.h" // the draw specification (include/antsrl.h)
 #include "antsrl_memagent.h"
 #include "antsrl_util.h"
-
-// ------------------------------------------------------------------ the draw specification (include/antsrl.h)
-__device__ __forceinline__ uint64_t agent_draw(uint64_t seed, uint64_t tag, uint64_t env, uint64_t step, uint64_t item)
-{
-    uint64_t k = mix64(seed + 0x9E3779B97F4A7C15ULL * (env + 1));
-    k = mix64(k ^ (0xD1B54A32D192ED03ULL * (step + 1)));
-    k = mix64(k + 0x9E3779B97F4A7C15ULL * (item + 1));
-    return mix64(k ^ tag);
-}
-__device__ __forceinline__ double draw_u01(uint64_t k) { return (double)(k >> 11) * (1.0 / 9007199254740992.0); }
-__device__ __forceinline__ uint32_t draw_below(uint64_t k, uint32_t n) { return (uint32_t)(((k >> 32) * (uint64_t)n) >> 32); }
 
 // ------------------------------------------------------------------ antsrl_agent_select
 __device__ __forceinline__ bool env_explores(const SelArgs &a, uint32_t e)

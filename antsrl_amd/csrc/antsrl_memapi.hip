@@ -325,7 +325,8 @@ extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, cons
 }
 
 // ---- the loop (antsrl_memagent.hip)
-static int check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants)
+// (also the rule of antsrl_policy_rework_select, antsrl_reworkapi.hip: declared in antsrl_memagent.h)
+int antsrl_check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants)
 {
     if (n_envs < 1 || n_ants < 1) return fail(ANTSRL_E_INVALID, "%s: n_envs and n_ants must be >= 1 (%d, %d)", who, n_envs, n_ants);
     if ((long long)n_envs * n_ants > 0x7fffffffLL)
@@ -354,7 +355,7 @@ extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_
                                    int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored, void *stream)
 {
     const char *who = "agent_select";
-    int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
     if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
     if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
     if (rc == ANTSRL_OK) rc = check_width(who, "mem_size", mem_size);
@@ -388,7 +389,7 @@ extern "C" int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_ba
                                  double epsilon, int32_t *tiles, int32_t *n_live, void *stream)
 {
     const char *who = "agent_plan";
-    const int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    const int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
     if (rc != ANTSRL_OK) return rc;
     if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
     REQUIRE(tiles, 4);
@@ -404,7 +405,7 @@ extern "C" int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_ba
 static int check_spec(const char *who, const AntsRecordSpec *r, bool plain = false)
 {
     if (!r) return fail(ANTSRL_E_INVALID, "%s: NULL spec", who);
-    int rc = check_batch(who, r->env_id_base, r->n_envs, r->n_ants);
+    int rc = antsrl_check_batch(who, r->env_id_base, r->n_envs, r->n_ants);
     if (rc != ANTSRL_OK) return rc;
     if (r->n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, r->n_features);
     if ((rc = check_width(who, "agent_dim", r->agent_dim)) != ANTSRL_OK) return rc;
@@ -495,7 +496,7 @@ extern "C" int antsrl_agent_select_actions(uint64_t seed, uint64_t step, int32_t
                                            uint8_t *explored, void *stream)
 {
     const char *who = "agent_select_actions";
-    int rc = check_batch(who, env_id_base, n_envs, n_ants);
+    int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
     if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
     if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
     if (rc != ANTSRL_OK) return rc;

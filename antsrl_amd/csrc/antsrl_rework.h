@@ -4,7 +4,7 @@
 //     q = Wc x + bc,   Wc [NQ][D], bc [NQ],   NQ = n_rot + n_ph, the rotation rows first.
 //
 // COLLAPSED is the flat fp32 buffer  Wc [NQ][D] at 0,  bc [NQ] at NQ * D  (floats): what k_rework_collapse writes and
-// k_rework_act reads.
+// k_rework_act reads (with or without the epsilon-greedy select inside: ReworkSelect).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,9 +43,22 @@ __device__ __forceinline__ float rw_group_sum(float a)
     return a;
 }
 
+// epsilon-greedy behind the forward pass (antsrl_policy_rework_select): antsrl_agent_select_actions' arguments
+struct ReworkSelect {
+    uint64_t seed, step;
+    double epsilon;
+    uint8_t *explored; // [n_envs] or NULL
+    uint32_t env_base, n_ants;
+};
+
 // one launch each
 ANTSRL_INTERNAL hipError_t antsrl_launch_rework_collapse(const ReworkParams &P, const ReworkDims &d, float *collapsed,
                                                          hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_rework_act(const float *collapsed, const ReworkDims &d, const void *obs,
                                                     bool obs_bf16, const float *agent_state, int M, int8_t *rot, int8_t *ph,
                                                     float *q_out, hipStream_t st);
+// M = n_envs * sel.n_ants rows
+ANTSRL_INTERNAL hipError_t antsrl_launch_rework_act_select(const float *collapsed, const ReworkDims &d, const void *obs,
+                                                           bool obs_bf16, const float *agent_state, int M,
+                                                           const ReworkSelect &sel, int8_t *rot, int8_t *ph, float *q_out,
+                                                           hipStream_t st);

@@ -1,6 +1,6 @@
 // antsrl_reworkapi.hip — the rework agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h, "The rework agent's
 // net"): antsrl_rework_collapsed_bytes, antsrl_rework_collapse and antsrl_policy_rework in front of antsrl_rework.hip's
-// two kernels, and behind them its training step ("The rework agent's training step"): antsrl_reworktrain_sizes / _grad /
+// kernels (antsrl_policy_rework_select: the forward pass and the epsilon-greedy select in one), and behind them its training step ("The rework agent's training step"): antsrl_reworktrain_sizes / _grad /
 // _apply / _step in front of antsrl_reworktrain.hip's four, with the argument rules of the linear and explore agents'
 // (antsrl_linapi.hip).
 //
@@ -11,6 +11,7 @@
 
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
+#include "antsrl_memagent.h" // antsrl_check_batch
 #include "antsrl_rework.h"
 #include "antsrl_reworktrain.h"
 
@@ -82,6 +83,31 @@ extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collap
     if (n_ants == 0) return ANTSRL_OK; // nothing to do, nothing launched
     return enqueued(antsrl_launch_rework_act((const float *)collapsed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
                                              (int)n_ants, rotation, pheromone, q_out, (hipStream_t)stream),
+                    who);
+}
+
+extern "C" int antsrl_policy_rework_select(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
+                                           const float *agent_state, uint64_t seed, uint64_t step, int32_t env_id_base,
+                                           int32_t n_envs, int32_t n_ants, double epsilon, int8_t *rotation,
+                                           int8_t *pheromone, uint8_t *explored, float *q_out, void *stream)
+{
+    const char *who = "policy_rework_select";
+    ReworkDims d;
+    int rc = rework_check(s, &d, who);
+    if (rc != ANTSRL_OK) return rc;
+    if (!collapsed || !obs || !agent_state || !rotation || !pheromone)
+        return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state, rotation, pheromone are required", who);
+    if (((uintptr_t)collapsed | (uintptr_t)obs | (uintptr_t)agent_state | (uintptr_t)q_out) & 3)
+        return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state and q_out must be 4-byte aligned", who);
+    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
+        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
+    if ((rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants)) != ANTSRL_OK) return rc;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
+    ReworkSelect sel = {};
+    sel.seed = seed; sel.step = step; sel.epsilon = epsilon; sel.explored = explored;
+    sel.env_base = (uint32_t)env_id_base; sel.n_ants = (uint32_t)n_ants;
+    return enqueued(antsrl_launch_rework_act_select((const float *)collapsed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
+                                                    n_envs * n_ants, sel, rotation, pheromone, q_out, (hipStream_t)stream),
                     who);
 }
 

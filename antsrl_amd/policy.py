@@ -374,11 +374,9 @@ class ReworkPolicy:
         nq, D = self.n_rot + self.n_ph, self.n_features + 2
         return self.collapsed[nq * D: nq * D + nq]
 
-    def act(self, obs: torch.Tensor, agent_state: torch.Tensor, logits: Optional[torch.Tensor] = None, env=None):
-        """CollectAgentRework.get_action's network branch (:167-174): obs [..., P, P, K] float32 (or bfloat16 from a
-        BatchedAntsEnv(obs_dtype=torch.bfloat16)) and agent_state float32 [..., 2] on the device ->
-        (rotation int8 [...], pheromone int8 [...]), ready to pass to step().  `logits` (float32 [M, n_rot + n_ph])
-        receives both heads' q.  The returned tensors are reused buffers."""
+    def _rows(self, obs, agent_state, logits, env, out):
+        """The checks act and act_select share -> (lead shape, rows, obs_format, rotation, pheromone): `out` = (rot, ph),
+        int8 tensors of one element per row that receive the actions, else the policy's own reused buffers."""
         assert self.collapsed is not None, "ReworkPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
         lead = obs.shape[:-3]
         m = 1
@@ -391,12 +389,46 @@ class ReworkPolicy:
         assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
         if logits is not None:
             assert logits.shape == (m, self.n_rot + self.n_ph) and logits.dtype == torch.float32 and logits.is_contiguous()
-        if self._rot is None or self._rot.numel() != m:
-            self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
-            self._ph = torch.empty((m,), dtype=torch.int8, device=self.device)
+        if out is not None:
+            rot, ph = out
+            for t in (rot, ph):
+                assert t.dtype == torch.int8 and t.numel() == m and t.is_contiguous() and t.device == obs.device
+        else:
+            if self._rot is None or self._rot.numel() != m:
+                self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
+                self._ph = torch.empty((m,), dtype=torch.int8, device=self.device)
+            rot, ph = self._rot, self._ph
         fmt = 1 if obs.dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
+        return lead, m, fmt, rot, ph
+
+    def act(self, obs: torch.Tensor, agent_state: torch.Tensor, logits: Optional[torch.Tensor] = None, env=None, out=None):
+        """CollectAgentRework.get_action's network branch (:167-174): obs [..., P, P, K] float32 (or bfloat16 from a
+        BatchedAntsEnv(obs_dtype=torch.bfloat16)) and agent_state float32 [..., 2] on the device ->
+        (rotation int8 [...], pheromone int8 [...]), ready to pass to step().  `logits` (float32 [M, n_rot + n_ph])
+        receives both heads' q.  The returned tensors are reused buffers, or views of `out` = (rot, ph) when the caller
+        owns them."""
+        lead, m, fmt, rot, ph = self._rows(obs, agent_state, logits, env, out)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_policy_rework(C.byref(self.shape), _p(self.collapsed), _p(obs), fmt, _p(agent_state),
-                                                      m, _p(self._rot), _p(self._ph), _p(logits), _lib.stream(self.device)),
+                                                      m, _p(rot), _p(ph), _p(logits), _lib.stream(self.device)),
                        "policy_rework")
-        return self._rot.view(lead), self._ph.view(lead)
+        return rot.view(lead), ph.view(lead)
+
+    def act_select(self, obs: torch.Tensor, agent_state: torch.Tensor, *, seed: int, step: int, env_id_base: int, n_envs: int,
+                   n_ants: int, epsilon: float, out=None, explored: Optional[torch.Tensor] = None,
+                   logits: Optional[torch.Tensor] = None, env=None):
+        """get_action with its epsilon branch (:165-174) in one launch (antsrl_policy_rework_select): act() on n_envs
+        colonies of n_ants ants each, with the colonies that explore at (seed, step) taking the draw specification's
+        uniform actions instead: the bits of act() followed by antsrl_agent_select_actions, without the forward pass of
+        the rows that would be overwritten.  `explored` (uint8 [n_envs]) receives 1 for an exploring colony; `logits`
+        is written for the rows of the other colonies only."""
+        lead, m, fmt, rot, ph = self._rows(obs, agent_state, logits, env, out)
+        assert m == n_envs * n_ants, "%d rows are not %d colonies of %d ants" % (m, n_envs, n_ants)
+        if explored is not None:
+            assert explored.dtype == torch.uint8 and explored.numel() == n_envs and explored.is_contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_policy_rework_select(C.byref(self.shape), _p(self.collapsed), _p(obs), fmt,
+                                                             _p(agent_state), seed, step, env_id_base, n_envs, n_ants,
+                                                             float(epsilon), _p(rot), _p(ph), _p(explored), _p(logits),
+                                                             _lib.stream(self.device)), "policy_rework_select")
+        return rot.view(lead), ph.view(lead)

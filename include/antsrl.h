@@ -881,6 +881,30 @@ int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const 
                          const float *agent_state, int64_t n_ants, int8_t *rotation, int8_t *pheromone, float *q_out,
                          void *stream);
 
+/* antsrl_policy_rework and the epsilon-greedy select behind it (get_action's two branches, :165-174) in ONE launch, for
+ * n_envs colonies of n_ants ants (rows in the batch's own order: ant a of colony e is row e * n_ants + a).  For equal
+ * arguments it writes, bit for bit, the rotation, pheromone and explored bytes that
+ *     antsrl_policy_rework(s, collapsed, obs, obs_format, agent_state, n_envs * n_ants, rotation, pheromone, ..)
+ *     antsrl_agent_select_actions(seed, step, env_id_base, n_envs, n_ants, epsilon, s->n_rot, s->n_ph, rotation,
+ *                                 pheromone, explored, ..)
+ * write one after the other, under THE DRAW SPECIFICATION above and its stream tags as they are: colony e explores iff
+ * u01(draw(seed, ANTSRL_DRAW_EXPLORE, env_id_base + e, step, 0)) < epsilon (the same double comparison), and its ant a
+ * then takes below(draw(.., ANTSRL_DRAW_ROTATION, .., a), n_rot) - n_rot / 2 and below(draw(.., ANTSRL_DRAW_PHEROMONE,
+ * .., a), n_ph).  What it saves is the forward pass of the exploring colonies: a run of eight consecutive rows that all
+ * explore is neither loaded nor multiplied, so the observation and agent_state rows of an exploring colony need not hold
+ * meaningful values (a run that mixes exploring and other rows is evaluated whole; what it computes for an exploring row
+ * goes nowhere).  Rows of the other colonies get antsrl_policy_rework's arithmetic and bits.
+ * explored: uint8 [n_envs] (1 = explored) or NULL; q_out: float [n_envs * n_ants][NQ] or NULL: the rows of the colonies that
+ * do not explore get antsrl_policy_rework's q, the rows of the exploring ones are NOT written.
+ * Rules: antsrl_policy_rework's (shape, pointers, alignment, obs_format) and antsrl_agent_select's (n_envs, n_ants >= 1,
+ * n_envs * n_ants < 2^31, env_id_base >= 0 with env_id_base + n_envs < 2^31, 0 <= epsilon <= 1), all checked before any
+ * HIP call.  One launch, no atomics, no host synchronisation, no allocation; each output byte has one writer and a
+ * repeated launch gives the same bits.  No load touches a byte outside obs, agent_state and the collapsed buffer. */
+int antsrl_policy_rework_select(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
+                                const float *agent_state, uint64_t seed, uint64_t step, int32_t env_id_base,
+                                int32_t n_envs, int32_t n_ants, double epsilon, int8_t *rotation, int8_t *pheromone,
+                                uint8_t *explored, float *q_out, void *stream);
+
 /* The rework agent's training step: CollectAgentRework.train (agents/collect_agent_rework.py:110-152) for the net above,
  * all 20 tensors trained.  A net is ONE flat fp32 block of P floats (params_floats): the 20 tensors of the state_dict in its
  * order (layer1..4, rotation_layer1..4, pheromone_layer1..2, each .weight [out][in] then .bias), dense.  `model` is such a
