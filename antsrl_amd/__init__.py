@@ -4,7 +4,7 @@ from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
-           "ReworkTrainer", "ReworkAgent"]
+           "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -26,4 +26,10 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "ReworkAgent":
         from .agent import ReworkAgent
         return ReworkAgent
+    if name == "EpisodeMonitor":
+        from .monitor import EpisodeMonitor
+        return EpisodeMonitor
+    if name in ("train_episodes", "epsilon_schedule"):
+        from . import driver
+        return getattr(driver, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -25,7 +25,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step", "antsrl_exptrain_sizes",
            "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step", "antsrl_rework_collapsed_bytes",
            "antsrl_rework_collapse", "antsrl_policy_rework", "antsrl_reworktrain_sizes", "antsrl_reworktrain_grad",
-           "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select")
+           "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select", "antsrl_monitor_sizes",
+           "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode")
 
 _lib = None
 
@@ -141,6 +142,10 @@ def load() -> C.CDLL:
     lib.antsrl_reworktrain_apply.argtypes = [rs, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.antsrl_reworktrain_step.argtypes = [rs] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
                                                                C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.antsrl_monitor_sizes.argtypes = [i32, i32, i32, i32, sz]
+    lib.antsrl_monitor_init.argtypes = [vp, i32, i32, i32, i32, vp]
+    lib.antsrl_monitor_step.argtypes = [vp, i32, i32, i32, i32, vp, vp, C.c_double, i32, i32, vp]
+    lib.antsrl_monitor_end_episode.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

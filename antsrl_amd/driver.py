@@ -1,0 +1,78 @@
+"""main.py's episode loop (:66-157) around the device agents' fused step.
+
+    log = train_episodes(agent, env, gen, episodes=100, steps=2000)
+
+runs what the reference's driver runs, on one BatchedAntsEnv handle and without a host read of device data: a fresh map
+per episode (antsrl_generate on the same handle), agent.setup once, agent.initialize and the first observation per
+episode, `steps` rollout_steps each followed by EpisodeMonitor.step(env.reward, loss), EpisodeMonitor.end_episode, and
+the epsilon schedule (:149).  The statistics are the monitor's (antsrl_amd/monitor.py); the one synchronisation is its
+log() at the end (and the snapshots, where asked for: a snapshot is a read-back).
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+
+from . import config as cm
+from .monitor import EpisodeMonitor
+from .snapshot import snapshot_batched
+
+
+def epsilon_schedule(episode: int, min_epsilon: float = 0.01, max_epsilon: float = 1.0) -> float:
+    """main.py:149: the epsilon set after episode `episode` (counted from 0)."""
+    return max(min_epsilon, min(max_epsilon, 1.0 - math.log10((episode + 1) / 2)))
+
+
+def episode_seed(cfg, gen, seed: int, episode: int) -> int:
+    """The seed of episode `episode` under the rule include/antsrl.h documents for auto-reset: + 1 per episode for
+    ANTSRL_RNG_COUNTER, + AntsCfg.n_envs_total (0 = env_id_base + n_envs) for ANTSRL_RNG_REFERENCE, so episode k of
+    the driver draws the map the k-th auto-reset would have drawn."""
+    if gen.rng_kind == cm.RNG_REFERENCE:
+        return seed + episode * (cfg.n_envs_total or cfg.env_id_base + cfg.n_envs)
+    return seed + episode
+
+
+def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,
+                   min_epsilon: float = 0.01, max_epsilon: float = 1.0, monitor: Optional[EpisodeMonitor] = None,
+                   snapshot_every: Optional[int] = None, save_as: Optional[str] = None) -> dict:
+    """main.py's loop for `agent` (a device agent: MemoryAgent, CollectAgent, ExploreAgent, ReworkAgent) on `env` (a
+    BatchedAntsEnv).  gen: the AntsGen handed to env.generate for every episode (config.make_gen).  An agent that has
+    not been set up is set up on `env` at the first episode (once, :82-84).  monitor: an EpisodeMonitor to continue or
+    one with another report_every; by default one sized to this run that reports every 50 steps (:115).
+    snapshot_every: keep snapshot_batched(env) after every step of episode 0 and of every snapshot_every-th episode
+    (:67, :137-138, main.py's visualize_every); those episodes synchronise at every step.  save_as: agent.save_model at
+    the end, when training (:154-157).
+
+    Returns the monitor's log() (reports, report_episode, report_step, all_reward, all_loss, grand_total, n_losses)
+    with `epsilons` (the epsilon each episode ran with), `monitor`, and `states` (the snapshots, in order) when
+    snapshot_every is given.  Not training, all_loss is main.py:111's 0."""
+    env = getattr(env, "_backend", env)
+    mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=50, max_reports=max(1, episodes * (steps // 50)),
+                                                             max_episodes=max(1, episodes))
+    states, epsilons = [], []
+    for episode in range(episodes):
+        visualize = snapshot_every is not None and ((episode + 1) % snapshot_every == 0 or episode == 0 or not training)
+        env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
+        if agent.trainer is None:
+            agent.setup(env)
+        agent.initialize(env)
+        env.observe()
+        epsilons.append(float(agent.epsilon))
+        for s in range(steps):
+            loss = agent.rollout_step(env, training)
+            mon.step(env.reward, loss if training else None)
+            if visualize:
+                states.extend(snapshot_batched(env))
+        mon.end_episode()
+        agent.epsilon = epsilon_schedule(episode, min_epsilon, max_epsilon)
+    if save_as is not None and training:
+        agent.save_model(save_as)
+    log = mon.log()
+    if not training:
+        log["all_loss"] = np.zeros_like(log["all_loss"])
+    log.update(epsilons=np.array(epsilons), monitor=mon)
+    if snapshot_every is not None:
+        log["states"] = states
+    return log

@@ -957,6 +957,50 @@ int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, const float 
                             int64_t step, double lr, double beta1, double beta2, double eps, float *grads, float *loss,
                             void *workspace, void *stream);
 
+/* The training monitor: what the reference's driver keeps around its step (main.py:66-152), resident on the device, so
+ * that a training curve costs one launch per step and no host synchronisation.  Its state is ONE caller-allocated device
+ * block (8-byte aligned, antsrl_monitor_sizes bytes) of float64 / int64 words, dense, in this order, for E = n_envs
+ * environments of N = n_ants ants:
+ *     episode_reward  double [E][N]                   main.py:89, one array per environment
+ *     avg_loss        double                          main.py:59, :106-109: the running loss
+ *     n_losses        int64                           losses seen so far; 0 is main.py's `avg_loss is None`
+ *     last_loss       double                          the last loss seen
+ *     reports         double [max_reports][E][3]      {total, min, max} of episode_reward[e][:] (main.py:115-120)
+ *     episodes        double [max_episodes][3]        {grand_total, avg_loss, n_losses} (main.py:151-152), a row per episode
+ * so bytes = 8 * (E N + 3 + 3 E max_reports + 3 max_episodes).  The means (main.py:116) are the caller's division: the
+ * device divides nothing.
+ *   _init:  zeroes the block (+0.0 and 0).
+ *   _step:  ONE launch.  episode_reward[e][n] += (double)reward[e][n] (main.py:100; what numpy does for float64 +=
+ *           float32).  With has_loss, the loss is *loss_dev when loss_dev is not NULL (the 0-d tensor a training step
+ *           returns, read on the device) and loss_host otherwise (the host's 0 below min_replay, which the reference feeds
+ *           into the average too): the first loss becomes avg_loss, a later one gives 0.99 * avg_loss + 0.01 * (double)loss
+ *           with each product rounded before the add; n_losses += 1, last_loss = (double)loss.  With report_slot >= 0 the
+ *           launch also writes reports[report_slot][e] from the updated episode_reward; report_slot = -1: no report, and
+ *           then nothing is reduced.
+ *   _end_episode:  ONE launch.  episodes[episode_slot] = {grand_total, avg_loss, (double)n_losses}, where grand_total is
+ *           the sum over the environments of `total` in reports[last_report_slot], or 0 for last_report_slot = -1 (an
+ *           episode without a report: main.py:90's mean_reward = 0, which goes stale between reports); then
+ *           episode_reward = +0.0.  avg_loss, n_losses and last_loss carry over (main.py sets avg_loss before the episode
+ *           loop).
+ * THE ORDER OF THE SUMS (float64 adds, round to nearest even; no atomics: equal inputs give equal bits whatever ran
+ * before).  One workgroup of 256 threads per environment: slot t starts at +0.0 and adds the ants t, t + 256, t + 512, ...
+ * in ascending order; the 256 slots are folded with x[i] += x[i + s] for i < s, s = 128, 64, ..., 1; total = x[0].
+ * grand_total folds the environments' totals by the same rule in one workgroup (slot t takes the environments t, t + 256,
+ * ...).  min and max are order-free (a slot starts from its first ant, no infinity enters); a NaN reward is not ordered
+ * and leaves them undefined.
+ * Rules, all checked before any HIP call (ANTSRL_E_INVALID): state not NULL and 8-byte aligned; n_envs, n_ants >= 1 with
+ * n_envs * n_ants < 2^31 - 256; max_reports, max_episodes >= 1; reward not NULL, reward and loss_dev 4-byte aligned;
+ * report_slot and last_report_slot in [-1, max_reports), episode_slot in [0, max_episodes): a slot is never wrapped or
+ * overwritten silently.  antsrl_monitor_sizes makes no HIP call; no entry allocates or synchronises the host. */
+int antsrl_monitor_sizes(int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes, size_t *bytes);
+int antsrl_monitor_init(void *state, int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes,
+                        void *stream);
+int antsrl_monitor_step(void *state, int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes,
+                        const float *reward, const float *loss_dev, double loss_host, int has_loss, int report_slot,
+                        void *stream);
+int antsrl_monitor_end_episode(void *state, int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes,
+                               int episode_slot, int last_report_slot, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
