@@ -10,8 +10,10 @@ from .config import AntsCfg, AntsGen, AntsInit
 LIB_PATH = os.environ.get("ANTSRL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                         "libantsrl_hip.so")  # ANTSRL_LIB: A/B builds
 
-#: every symbol include/antsrl.h declares
+#: every symbol include/antsrl.h declares (but antsrl_workspace_bytes2 and antsrl_create2: the list holds the names of
+#: letters and underscores, as tests/test_abi_cpu.py reads them off the header; load() binds those two by name all the same)
 EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl_workspace_bytes", "antsrl_create",
+           "antsrl_workspace_map",
            "antsrl_destroy", "antsrl_reset", "antsrl_generate", "antsrl_step", "antsrl_observe", "antsrl_update", "antsrl_flush",
            "antsrl_step_update", "antsrl_set_timing_events", "antsrl_set_activation", "antsrl_policy_mlp", "antsrl_read_state", "antsrl_state_bytes",
            "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_mem_alloc", "antsrl_mem_free",
@@ -48,6 +50,11 @@ class AntsRecordSpec(C.Structure):
         (n, C.c_int64) for n in ("K", "head", "max_len")] + [(n, C.c_uint64) for n in ("seed", "step")]
 
 
+class AntsWsArray(C.Structure):
+    """include/antsrl.h AntsWsArray."""
+    _fields_ = [("name", C.c_char * 24), ("block", C.c_int32), ("_pad", C.c_int32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
 class AntsrlError(RuntimeError):
     pass
 
@@ -71,6 +78,9 @@ def load() -> C.CDLL:
     lib.antsrl_last_error.restype = C.c_char_p
     lib.antsrl_workspace_bytes.argtypes = [C.POINTER(AntsCfg), C.POINTER(C.c_size_t)]
     lib.antsrl_create.argtypes = [C.POINTER(AntsCfg), vp, C.c_size_t, C.POINTER(vp)]
+    lib.antsrl_workspace_bytes2.argtypes = [C.POINTER(AntsCfg), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.antsrl_create2.argtypes = [C.POINTER(AntsCfg), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(vp)]
+    lib.antsrl_workspace_map.argtypes = [C.POINTER(AntsCfg), i32, C.POINTER(AntsWsArray), C.c_int32, C.POINTER(C.c_int32)]
     lib.antsrl_destroy.argtypes = [vp]
     lib.antsrl_destroy.restype = None
     lib.antsrl_reset.argtypes = [vp, C.POINTER(AntsInit), vp]

@@ -1,7 +1,7 @@
 """BatchedAntsEnv — E independent AntsRL environments stepped on one MI355X.
 
 Thin host-side plumbing over the C-ABI (include/antsrl.h): PyTorch-ROCm supplies device memory
-(one workspace tensor + the observation / reward / done output tensors) and the stream; every
+(the workspace — a cell-record block and a state block — + the observation / reward / done output tensors) and the stream; every
 piece of arithmetic happens in the HIP kernels of libantsrl_hip.so.  There is no CPU fallback.
 
 Call order mirrors the reference driver (main.py:88-131):
@@ -53,7 +53,7 @@ def placement_levels_seen(times) -> bool:
 
 class BatchedAntsEnv:
     def __init__(self, cfg: AntsCfg, device: Optional[torch.device] = None, obs_dtype: torch.dtype = torch.float32,
-                 obs_row_stride=None, pieced_memory: bool = True):
+                 obs_row_stride=None, pieced_memory: bool = True, split_workspace: bool = True):
         """obs_dtype: torch.float32 (the reference's values) or torch.bfloat16 (the same values rounded
         to nearest even: half the bytes per step; what the bf16 policy rounds its input to anyway —
         antsrl_set_obs_format).
@@ -64,7 +64,9 @@ class BatchedAntsEnv:
         instead of torch.empty; the workspace stays a torch allocation.  On MI355X the observation kernel runs 15 % apart
         depending on the physical layout of these two buffers; this combination is the fast one on most boxes, two torch
         allocations are mostly slow (antsrl_amd/vmm.py, profiles/history/r04/placement_probe*.txt).  tune_placement() measures the
-        four combinations on the box at hand and keeps the fastest."""
+        four combinations on the box at hand and keeps the fastest.
+        split_workspace: the workspace is two allocations (antsrl_create2) — the cell records, and the state block with
+        everything else — so that tune_placement() can place them apart; False: one allocation (antsrl_create)."""
         if obs_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("obs_dtype must be torch.float32 or torch.bfloat16")
         if not torch.cuda.is_available():
@@ -77,11 +79,19 @@ class BatchedAntsEnv:
         need = C.c_size_t()
         _lib.check(self.lib.antsrl_workspace_bytes(C.byref(self.cfg), C.byref(need)), "workspace_bytes")
         self.workspace_bytes = need.value
+        # the workspace as two blocks (antsrl_create2): the cell records — scattered accesses — and everything else
+        nst, nrec = C.c_size_t(), C.c_size_t()
+        _lib.check(self.lib.antsrl_workspace_bytes2(C.byref(self.cfg), C.byref(nst), C.byref(nrec)), "workspace_bytes2")
+        self.state_bytes, self.record_bytes = nst.value, nrec.value
+        self._split = bool(split_workspace)
+        if not self._split:  # (one block: it plays the record block's part everywhere below, and there is no state block)
+            self.state_bytes, self.record_bytes = 0, self.workspace_bytes
         with torch.cuda.device(self.device):
             big = (lambda n: vmm.empty_u8(n, self.device)) if pieced_memory else (lambda n: torch.empty(n, dtype=torch.uint8, device=self.device))
             self._pieced = bool(pieced_memory)
             self._h = None
-            self._make_handle(torch.empty(need.value + 256, dtype=torch.uint8, device=self.device))
+            self._state = None
+            self._make_handle(torch.empty(self.record_bytes + 256, dtype=torch.uint8, device=self.device))
             E, N, P, K = cfg.n_envs, cfg.n_ants, cfg.pside, cfg.n_channels
             esz = 4 if obs_dtype == torch.float32 else 2
             row = P * P * K
@@ -137,14 +147,29 @@ class BatchedAntsEnv:
         self.done = piece("done", sizes[2][1], torch.uint8, (E,))
         self._host_out = None
 
-    def _make_handle(self, ws: torch.Tensor) -> None:
-        """(Re)creates the handle over workspace tensor `ws` with this env's configuration and observation format."""
+    def _make_handle(self, ws: torch.Tensor, state: Optional[torch.Tensor] = None) -> None:
+        """(Re)creates the handle with this env's configuration and observation format over the record block `ws` (the
+        cell records: the bulk of the workspace and the block the gathers hit — `_ws`) and the state block `state` (the
+        per-ant / per-env arrays, bit maps, frames — `_state`; None: the one the env has, or a fresh torch.empty one)."""
         if getattr(self, "_h", None):
             self.lib.antsrl_destroy(self._h)
-        self._ws = ws
+            self._h = None
+        if ws.numel() < self.record_bytes + (-ws.data_ptr()) % 256:
+            raise _lib.AntsrlError("record block too small: %d bytes for %d" % (ws.numel(), self.record_bytes))
         self._ws_ptr = ws.data_ptr() + (-ws.data_ptr()) % 256
         self._h = C.c_void_p()
-        _lib.check(self.lib.antsrl_create(C.byref(self.cfg), C.c_void_p(self._ws_ptr), self.workspace_bytes, C.byref(self._h)), "create")
+        if not self._split:
+            self._ws, self._state = ws, None
+            _lib.check(self.lib.antsrl_create(C.byref(self.cfg), C.c_void_p(self._ws_ptr), self.workspace_bytes, C.byref(self._h)), "create")
+        else:
+            if state is None:
+                state = self._state if self._state is not None else torch.empty(self.state_bytes + 256, dtype=torch.uint8, device=self.device)
+            if state.numel() < self.state_bytes + (-state.data_ptr()) % 256:
+                raise _lib.AntsrlError("state block too small: %d bytes for %d" % (state.numel(), self.state_bytes))
+            self._ws, self._state = ws, state
+            self._state_ptr = state.data_ptr() + (-state.data_ptr()) % 256
+            _lib.check(self.lib.antsrl_create2(C.byref(self.cfg), C.c_void_p(self._state_ptr), self.state_bytes,
+                                               C.c_void_p(self._ws_ptr), self.record_bytes, C.byref(self._h)), "create2")
         if getattr(self, "_obs_dtype", torch.float32) == torch.bfloat16:
             _lib.check(self.lib.antsrl_set_obs_format(self._h, 1), "set_obs_format")
         pitch, row = getattr(self, "_obs_pitch_row", (0, 0))
@@ -152,7 +177,7 @@ class BatchedAntsEnv:
             _lib.check(self.lib.antsrl_set_obs_row_stride(self._h, pitch), "set_obs_row_stride")
 
     def tune_placement(self, age: int = 150, steps: int = 30, verbose: bool = False, extra_outputs: int = 4,
-                       walk_spacers: int = 3, spacer_gib: float = 24.0, force_walk: bool = False):
+                       walk_spacers: int = 3, spacer_gib: float = 24.0, force_walk: bool = False, state_stage: bool = True):
         """Pick the (workspace, output buffer) pair whose PHYSICAL placement steps fastest.  Call it right after construction,
         BEFORE reset() / generate() and before anything is attached to the handle: it runs scratch episodes (device
         generator + uniform random actions), may re-create the handle on another workspace, and leaves it to be reset.
@@ -173,7 +198,17 @@ class BatchedAntsEnv:
         levels have been seen (`force_walk`: walk regardless — tests).  Everything but
         the kept pair is freed at the end (pieced buffers go back to the library's pool, spacers to the driver).
         One-off cost ~0.4 s at c3 (plus ~0.1 s per walk step).  Returns the ms/step figures, the four pairs first (None for
-        small batches, where there is nothing to alias)."""
+        small batches, where there is nothing to alias).
+
+        The workspace is two blocks (antsrl_create2), and "workspace" above is its RECORD block: the cell records, the block
+        the gathers hit.  A second stage (`state_stage`) then places the STATE block — the per-ant arrays k_update_move
+        streams while it scatters into the records — with the chosen pair fixed: the env's own torch.empty block, a pieced
+        one and a corner of up to two record blocks the first stage drew and did not keep are each stepped through a scratch
+        episode, and the one with the lowest k_update_move time (the library's timing hook, events [1]..[2]) replaces the
+        default if it is at least 3 % faster (the kernel's two levels lie 6 % apart at c3) and the observation kernel has not
+        lost as much.  Otherwise every block stays where it was.  A kept corner keeps its whole block allocated, so a corner
+        is kept only where the pieced block does not reach the fast level, and then only for 5 %.  The walk is never extended
+        for this stage.  `placement_trials["state_stage"]` records the candidates and their times."""
         if self._out_total < vmm.SMALL_BYTES:
             return None
         if self._loaded:
@@ -198,30 +233,32 @@ class BatchedAntsEnv:
                 for t in range(age):
                     self.step_update(rot[t % 4], ph[t % 4], None)
 
-            NEV, PSTEPS = cfgmod.TIMING_EVENTS, 8
-            evs = _lib.HipEvents(NEV * PSTEPS)
+            NEV, PSTEPS, PSTEPS_STATE = cfgmod.TIMING_EVENTS, 8, 24  # (stage two looks for 6 % on a kernel a fifth as long: more samples)
+            evs = _lib.HipEvents(NEV * PSTEPS_STATE)
             prc_times = []  # the observation kernel alone, per trial: what the zones act on (the levels are read off THIS)
+            upd_times = []  # k_update_move alone, per trial (events [1]..[2]): what the second stage reads
 
-            def measure():
+            def measure(psteps=PSTEPS):
                 for t in range(4):
                     self.step_update(rot[t % 4], ph[t % 4], None)
                 e0.record()
                 for t in range(steps):
                     self.step_update(rot[t % 4], ph[t % 4], None)
                 e1.record()
-                for t in range(PSTEPS):  # (then a few steps with the library's timing hook: k_perceive by HIP events)
+                for t in range(psteps):  # (then a few steps with the library's timing hook: k_perceive by HIP events)
                     self.set_timing_events([evs.ev[NEV * t + i].value for i in range(NEV)])
                     self.step_update(rot[t % 4], ph[t % 4], None)
                 torch.cuda.current_stream(dev).synchronize()
-                prc_times.append(float(np.mean([evs.elapsed_ms(NEV * t + 2, NEV * t + 3) for t in range(PSTEPS)])))
+                prc_times.append(float(np.mean([evs.elapsed_ms(NEV * t + 2, NEV * t + 3) for t in range(psteps)])))
+                upd_times.append(float(np.mean([evs.elapsed_ms(NEV * t + 1, NEV * t + 2) for t in range(psteps)])))
                 return e0.elapsed_time(e1) / steps
             # the env's own pair first (workspace torch.empty, outputs pieced unless pieced_memory=False), then the other three
-            own_ws, own_out = self._ws, self._out_flat
-            n_ws, n_out = self.workspace_bytes + 256, self._out_total + 256
+            own_ws, own_out, own_state = self._ws, self._out_flat, self._state
+            n_ws, n_out, n_state = self.record_bytes + 256, self._out_total + 256, self.state_bytes + 256
             pairs, times = [], []
             for ws_kind in ("own", "other"):
                 if ws_kind == "other":
-                    self._make_handle(vmm.empty_u8(n_ws, dev))  # (the env's own workspace is torch.empty memory)
+                    self._make_handle(vmm.empty_u8(n_ws, dev))  # (the env's own record block is torch.empty memory)
                 scratch_episode()
                 for out_kind in ("own", "other"):
                     if out_kind == "other":
@@ -277,21 +314,61 @@ class BatchedAntsEnv:
                 labels.append("ws torch (walk %d: +%.0f GiB) / out %s" % (walked, depth, "pieced" if self._pieced else "torch"))
             # the pair with the fastest observation kernel (the step time around it carries the timing hook's own stalls)
             best = min(range(len(times)), key=prc_times.__getitem__)
-            evs.destroy()
             if verbose:
                 print("tune_placement: ms/step per (workspace, outputs) pair %s -> %d" % (["%.4f" % t for t in times], best))
             ws, out = pairs[best]
-            del pairs, spacers
-            if ws.data_ptr() != self._ws.data_ptr():
-                self._make_handle(ws)
+            n_stage1 = len(times)
+            # Stage two: that pair stays; the STATE block — what k_update_move streams while it scatters into the records — is
+            # tried on the env's own torch.empty block, a pieced one, and a corner of the record blocks the first stage drew
+            # and did not keep (other zones, already paid for); k_update_move's own time decides.
+            state_cands = [("state torch (default)", own_state)]
+            if state_stage and self._split:
+                try:
+                    state_cands.append(("state pieced", vmm.pieced_u8(n_state, dev)))
+                except _lib.AntsrlError:
+                    pass
+                seen = {ws.data_ptr()}
+                for (w2, _o), lab in zip(pairs, labels):
+                    if w2.data_ptr() not in seen and w2.numel() >= n_state and len(state_cands) < 4:
+                        seen.add(w2.data_ptr())
+                        state_cands.append(("state in spare record block (%s)" % lab.split(" / ")[0], w2[:n_state]))
+            for lab, st in state_cands if len(state_cands) > 1 else []:
+                self._make_handle(ws, st)
+                self._bind_outputs(out)
+                scratch_episode()
+                times.append(measure(PSTEPS_STATE))
+            evs.destroy()
+            s_upd, s_prc = upd_times[n_stage1:], prc_times[n_stage1:]
+            times, prc_times, upd_times = times[:n_stage1], prc_times[:n_stage1], upd_times[:n_stage1]
+            s_best = 0
+            if s_upd:
+                # The two levels of k_update_move lie 6 % apart (0.0340 / 0.0320 ms at c3); a candidate replaces the default only
+                # when it is faster by half of that — anything less is one level, measured twice — and k_perceive, the larger
+                # kernel, has not paid for it.
+                # A block of its own comes before a corner of a spare record block, whose other bytes (1 GB at c3) would stay
+                # allocated for nothing: a corner is kept only where no block of its own reaches the fast level, and only for
+                # 5 % (corners measure 2-4 % under a default that is already on the fast level: profiles/r06).
+                def fast(k, by):
+                    return s_upd[k] <= (1.0 - by) * s_upd[0] and s_upd[k] + s_prc[k] < s_upd[0] + s_prc[0]
+                own = [k for k in range(1, len(s_upd)) if state_cands[k][0] == "state pieced" and fast(k, 0.03)]
+                corners = [k for k in range(1, len(s_upd)) if state_cands[k][0] != "state pieced" and fast(k, 0.05)]
+                if own or corners:
+                    s_best = min(own or corners, key=s_upd.__getitem__)
+            state = state_cands[s_best][1]
+            state_labels = [lab for lab, _ in state_cands]
+            del pairs, spacers, state_cands
+            if ws.data_ptr() != self._ws.data_ptr() or (state is not None and state.data_ptr() != self._state.data_ptr()):
+                self._make_handle(ws, state)
             self._bind_outputs(out)
             if walked:  # (the walk's spacers and losing buffers: torch's go back to the driver, the pool's are unmapped — their
                 vmm.trim()  # ranges retired, never re-used; without a walk the few losing buffers simply stay pooled)
             torch.cuda.empty_cache()
             self._out_flat.zero_()
-            del own_ws, own_out, ws, out
+            del own_ws, own_out, own_state, ws, out, state
         self.placement_trials = dict(ms_per_step=[round(t, 5) for t in times], observation_kernel_ms=[round(t, 5) for t in prc_times],
-                                     chosen=best, pairs=labels, both_levels_seen=bool(both_levels(prc_times)), walk_steps=walked)
+                                     chosen=best, pairs=labels, both_levels_seen=bool(both_levels(prc_times)), walk_steps=walked,
+                                     state_stage=dict(candidates=state_labels, update_move_kernel_ms=[round(t, 5) for t in s_upd],
+                                                      observation_kernel_ms=[round(t, 5) for t in s_prc], chosen=s_best))
         self._loaded = None  # (the scratch episodes were the tuner's own: the handle is as new)
         return times
 

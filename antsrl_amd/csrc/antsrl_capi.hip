@@ -54,7 +54,7 @@ struct AntsHandle {
     bool need_full_collect;// next update must run Anthill.update over the whole grid
     bool is_reset;
     bool episode_over;     // a refused auto-reset left a finished episode behind (see antsrl_step_update)
-    size_t ws_bytes;
+    size_t ws_bytes[2];    // the state block and the record block (one block: [0] is all of it, [1] = 0)
     AntsGen gen;           // device generator parameters (antsrl_generate)
     bool has_gen;
     uint64_t episode_seed; // seed of the current episode
@@ -164,57 +164,75 @@ static bool use_interleaved(const AntsCfg *c)
     return use_scaled(c) && c->n_phero == 2;
 }
 
-// Carves the workspace; with base == NULL only computes the size.
-static size_t carve(const AntsCfg *c, DState *s, unsigned char *base)
+// Carves the workspace; with NULL bases only computes the sizes.  Two blocks (antsrl_create2): the cell records — what the
+// kernels reach with scattered per-cell accesses — are taken from `rec_base` with a count of their own, everything else
+// from `base`.  One block (antsrl_create: split == false, rec_base == base): one count, the records between the per-ant
+// arrays and the bit maps.  bytes[0] / bytes[1]: the state / record block's size (one block: bytes[0] is all of it).
+// `map` / `cap` / `count`: antsrl_workspace_map.
+static void carve(const AntsCfg *c, DState *s, unsigned char *base, unsigned char *rec_base, bool split, size_t bytes[2],
+                  AntsWsArray *map = nullptr, int32_t cap = 0, int32_t *count = nullptr)
 {
     const size_t E = c->n_envs, N = c->n_ants, G = (size_t)c->w * c->h, Cn = c->n_phero, R = c->n_rocks;
     const size_t words = (G + 31) / 32;
-    size_t off = 0;
-    auto take = [&](size_t bytes) -> unsigned char * {
-        unsigned char *ptr = base ? base + off : nullptr;
-        off = (off + bytes + 255) / 256 * 256;
+    size_t off[2] = {0, 0};
+    int32_t n_arrays = 0;
+    auto take_from = [&](int block, const char *name, size_t nbytes) -> unsigned char * {
+        unsigned char *b = block ? rec_base : base;
+        size_t &o = off[split ? block : 0];
+        unsigned char *ptr = b ? b + o : nullptr;
+        if (map && n_arrays < cap) {
+            AntsWsArray &a = map[n_arrays];
+            memset(&a, 0, sizeof(a));
+            strncpy(a.name, name, sizeof(a.name) - 1);
+            a.block = split ? block : 0; a.offset = o; a.bytes = nbytes;
+        }
+        ++n_arrays;
+        o = (o + nbytes + 255) / 256 * 256;
         return ptr;
     };
+    auto take = [&](const char *name, size_t nbytes) { return take_from(0, name, nbytes); };
+    auto take_rec = [&](const char *name, size_t nbytes) { return take_from(1, name, nbytes); };
     KP kp;
     fill_kp(c, &kp);
     DState d;
-    d.x = (double *)take(8 * E * N); d.y = (double *)take(8 * E * N); d.theta = (double *)take(8 * E * N);
-    d.prev_x = (double *)take(8 * E * N); d.prev_y = (double *)take(8 * E * N);
-    d.prev_dist = (double *)take(8 * E * N);
-    d.holding = (float *)take(4 * E * N); d.seed = (float *)take(4 * E * N);
-    d.prev_holding = (float *)take(4 * E * N);
-    d.activation = (float *)take(4 * E * N * Cn);
-    d.mandibles = (uint8_t *)take(E * N); d.reward_state = (uint8_t *)take(E * N);
-    d.dirty_cell = (int32_t *)take(4 * E * N);
-    d.walldep_cell = (int32_t *)take(4 * E * N);
+    d.x = (double *)take("x", 8 * E * N); d.y = (double *)take("y", 8 * E * N); d.theta = (double *)take("theta", 8 * E * N);
+    d.prev_x = (double *)take("prev_x", 8 * E * N); d.prev_y = (double *)take("prev_y", 8 * E * N);
+    d.prev_dist = (double *)take("prev_dist", 8 * E * N);
+    d.holding = (float *)take("holding", 4 * E * N); d.seed = (float *)take("seed", 4 * E * N);
+    d.prev_holding = (float *)take("prev_holding", 4 * E * N);
+    d.activation = (float *)take("activation", 4 * E * N * Cn);
+    d.mandibles = (uint8_t *)take("mandibles", E * N); d.reward_state = (uint8_t *)take("reward_state", E * N);
+    d.dirty_cell = (int32_t *)take("dirty_cell", 4 * E * N);
+    d.walldep_cell = (int32_t *)take("walldep_cell", 4 * E * N);
     if (use_interleaved(c)) { // one {p0, p1, food, pad} record per cell
-        d.phero[0] = d.phero[1] = (float *)take(16 * E * G);
-        d.food = d.phero[0] ? d.phero[0] + 2 : nullptr;
+        d.phero[0] = d.phero[1] = (float *)take_rec("records", 16 * E * G);
+        d.food = d.phero[0] ? d.phero[0] + 2 : nullptr; // (inside the record array, whichever block holds it)
     } else {
-        d.phero[0] = (float *)take(4 * E * G * Cn);
-        d.phero[1] = use_scaled(c) ? d.phero[0] : (float *)take(4 * E * G * Cn); // no ping-pong when scaled
-        d.food = (float *)take(4 * E * G * (size_t)kp.fs); // {food, META} records on the cell-meta path
+        d.phero[0] = (float *)take_rec("phero0", 4 * E * G * Cn);
+        d.phero[1] = use_scaled(c) ? d.phero[0] : (float *)take_rec("phero1", 4 * E * G * Cn); // no ping-pong when scaled
+        d.food = (float *)take_rec("food", 4 * E * G * (size_t)kp.fs); // {food, META} records on the cell-meta path
     }
-    d.walls_bits = (uint32_t *)take(4 * E * words); d.area_bits = (uint32_t *)take(4 * E * words);
-    d.explored_bits = (uint32_t *)take(4 * E * words);
+    d.walls_bits = (uint32_t *)take("walls_bits", 4 * E * words); d.area_bits = (uint32_t *)take("area_bits", 4 * E * words);
+    d.explored_bits = (uint32_t *)take("explored_bits", 4 * E * words);
     d.big_pres = d.big_old = nullptr;
     if (!kp.meta && antsrl_act_needs_hbm_maps(kp)) {
-        d.big_pres = (uint32_t *)take(4 * E * words);
-        d.big_old = (uint32_t *)take(4 * E * words);
+        d.big_pres = (uint32_t *)take("big_pres", 4 * E * words);
+        d.big_old = (uint32_t *)take("big_old", 4 * E * words);
     }
-    d.primed_cur = kp.meta ? (uint8_t *)take(E) : nullptr;
-    d.frames = kp.meta ? (AntFrame *)take(sizeof(AntFrame) * E * N) : nullptr;
-    d.anthill_xyr = (int32_t *)take(4 * E * 3);
-    d.anthill_food = (double *)take(8 * E);
-    d.rock_cx = (double *)take(8 * E * (R ? R : 1)); d.rock_cy = (double *)take(8 * E * (R ? R : 1));
-    d.rock_r = (double *)take(8 * E * (R ? R : 1)); d.rock_w = (double *)take(8 * E * (R ? R : 1));
-    d.timestep = (int32_t *)take(4 * E);
-    d.reward_primed = (uint8_t *)take(E);
-    d.gen_discs = (int32_t *)take(4 * E * ANTSRL_MAX_FOOD_DISCS * 3);
-    d.gen_perlin = (int32_t *)take(4 * E * 2);
-    d.pol_pack = (unsigned char *)take(ANTSRL_POL_PACK_BYTES);
+    d.primed_cur = kp.meta ? (uint8_t *)take("primed_cur", E) : nullptr;
+    d.frames = kp.meta ? (AntFrame *)take("frames", sizeof(AntFrame) * E * N) : nullptr;
+    d.anthill_xyr = (int32_t *)take("anthill_xyr", 4 * E * 3);
+    d.anthill_food = (double *)take("anthill_food", 8 * E);
+    d.rock_cx = (double *)take("rock_cx", 8 * E * (R ? R : 1)); d.rock_cy = (double *)take("rock_cy", 8 * E * (R ? R : 1));
+    d.rock_r = (double *)take("rock_r", 8 * E * (R ? R : 1)); d.rock_w = (double *)take("rock_w", 8 * E * (R ? R : 1));
+    d.timestep = (int32_t *)take("timestep", 4 * E);
+    d.reward_primed = (uint8_t *)take("reward_primed", E);
+    d.gen_discs = (int32_t *)take("gen_discs", 4 * E * ANTSRL_MAX_FOOD_DISCS * 3);
+    d.gen_perlin = (int32_t *)take("gen_perlin", 4 * E * 2);
+    d.pol_pack = (unsigned char *)take("pol_pack", ANTSRL_POL_PACK_BYTES);
     if (s) *s = d;
-    return off;
+    if (count) *count = n_arrays;
+    bytes[0] = off[0]; bytes[1] = off[1];
 }
 
 static void fill_kp(const AntsCfg *c, KP *p)
@@ -325,31 +343,49 @@ extern "C" int antsrl_workspace_bytes(const AntsCfg *cfg, size_t *bytes)
     int rc = validate(cfg);
     if (rc) return rc;
     if (!bytes) return fail(ANTSRL_E_INVALID, "bytes is NULL");
-    *bytes = carve(cfg, nullptr, nullptr);
+    size_t b[2];
+    carve(cfg, nullptr, nullptr, nullptr, false, b);
+    *bytes = b[0];
     return ANTSRL_OK;
 }
 
-extern "C" int antsrl_create(const AntsCfg *cfg, void *workspace, size_t workspace_bytes, AntsHandle **out)
+extern "C" int antsrl_workspace_bytes2(const AntsCfg *cfg, size_t *state_bytes, size_t *record_bytes)
 {
     int rc = validate(cfg);
     if (rc) return rc;
-    if (!out) return fail(ANTSRL_E_INVALID, "out is NULL");
-    if (!workspace) return fail(ANTSRL_E_INVALID, "workspace is NULL");
-    if (((uintptr_t)workspace & 255) != 0) return fail(ANTSRL_E_INVALID, "workspace must be 256-byte aligned");
-    const size_t need = carve(cfg, nullptr, nullptr);
-    if (workspace_bytes < need)
-        return fail(ANTSRL_E_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    size_t b[2];
+    carve(cfg, nullptr, nullptr, nullptr, true, b);
+    if (state_bytes) *state_bytes = b[0];
+    if (record_bytes) *record_bytes = b[1];
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_workspace_map(const AntsCfg *cfg, int split, AntsWsArray *entries, int32_t cap, int32_t *count)
+{
+    int rc = validate(cfg);
+    if (rc) return rc;
+    if (!count) return fail(ANTSRL_E_INVALID, "count is NULL");
+    if (cap < 0 || (cap > 0 && !entries)) return fail(ANTSRL_E_INVALID, "entries is NULL or cap < 0");
+    size_t b[2];
+    carve(cfg, nullptr, nullptr, nullptr, split != 0, b, entries, cap, count);
+    return ANTSRL_OK;
+}
+
+// the handle over a carved workspace: one block (split == false, record_ws == workspace) or two
+static int create_handle(const AntsCfg *cfg, void *state_ws, void *record_ws, bool split, const size_t need[2], AntsHandle **out)
+{
     AntsHandle *h = new (std::nothrow) AntsHandle();
     if (!h) return fail(ANTSRL_E_NOMEM, "out of host memory");
     h->cfg = *cfg;
     fill_kp(cfg, &h->p);
-    carve(cfg, &h->p.s, (unsigned char *)workspace);
+    size_t b[2];
+    carve(cfg, &h->p.s, (unsigned char *)state_ws, (unsigned char *)record_ws, split, b);
     h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = false; h->episode_over = false; h->pend_update = false;
     h->phase_next = 0;
     h->pol = PolArgs{};
     h->sweeps = 0; h->need_wall_clear = false;
     h->has_gen = false; h->episode_seed = 0; h->host_timestep = 1; h->obs_bf16 = false; h->obs_pitch = 0;
-    h->ws_bytes = need;
+    h->ws_bytes[0] = need[0]; h->ws_bytes[1] = need[1];
     h->ev_armed = false;
     h->obs_seq = 0;
     if (!h->p.meta && !antsrl_act_fits(h->p)) {
@@ -361,6 +397,41 @@ extern "C" int antsrl_create(const AntsCfg *cfg, void *workspace, size_t workspa
     }
     *out = h;
     return ANTSRL_OK;
+}
+
+extern "C" int antsrl_create(const AntsCfg *cfg, void *workspace, size_t workspace_bytes, AntsHandle **out)
+{
+    int rc = validate(cfg);
+    if (rc) return rc;
+    if (!out) return fail(ANTSRL_E_INVALID, "out is NULL");
+    if (!workspace) return fail(ANTSRL_E_INVALID, "workspace is NULL");
+    if (((uintptr_t)workspace & 255) != 0) return fail(ANTSRL_E_INVALID, "workspace must be 256-byte aligned");
+    size_t need[2];
+    carve(cfg, nullptr, nullptr, nullptr, false, need);
+    if (workspace_bytes < need[0])
+        return fail(ANTSRL_E_NOMEM, "workspace too small: %zu < %zu bytes", workspace_bytes, need[0]);
+    return create_handle(cfg, workspace, workspace, false, need, out);
+}
+
+extern "C" int antsrl_create2(const AntsCfg *cfg, void *state_ws, size_t state_bytes, void *record_ws, size_t record_bytes,
+                              AntsHandle **out)
+{
+    int rc = validate(cfg);
+    if (rc) return rc;
+    if (!out) return fail(ANTSRL_E_INVALID, "out is NULL");
+    if (!state_ws || !record_ws) return fail(ANTSRL_E_INVALID, "state_ws or record_ws is NULL");
+    if ((((uintptr_t)state_ws | (uintptr_t)record_ws) & 255) != 0)
+        return fail(ANTSRL_E_INVALID, "state_ws and record_ws must be 256-byte aligned");
+    size_t need[2];
+    carve(cfg, nullptr, nullptr, nullptr, true, need);
+    if (state_bytes < need[0])
+        return fail(ANTSRL_E_NOMEM, "state block too small: %zu < %zu bytes", state_bytes, need[0]);
+    if (record_bytes < need[1])
+        return fail(ANTSRL_E_NOMEM, "record block too small: %zu < %zu bytes", record_bytes, need[1]);
+    const uintptr_t s0 = (uintptr_t)state_ws, r0 = (uintptr_t)record_ws;
+    if (s0 < r0 + need[1] && r0 < s0 + need[0])
+        return fail(ANTSRL_E_INVALID, "the state block and the record block overlap");
+    return create_handle(cfg, state_ws, record_ws, true, need, out);
 }
 
 extern "C" void antsrl_destroy(AntsHandle *h) { delete h; }

@@ -16,7 +16,8 @@
  *    and contiguous; the library never allocates, frees or synchronises inside
  *    step/update/observe (it only enqueues kernels on the caller's stream);
  *  - all persistent state lives in ONE caller-provided device workspace whose
- *    size is reported by antsrl_workspace_bytes();
+ *    size is reported by antsrl_workspace_bytes() — or in two blocks, cell records
+ *    and everything else (antsrl_workspace_bytes2 / antsrl_create2);
  *  - return value 0 = success, negative = error (see ANTSRL_E_*); nothing is
  *    thrown across the ABI; antsrl_last_error() gives a message for the last
  *    failure on the calling thread;
@@ -255,6 +256,32 @@ int antsrl_workspace_bytes(const AntsCfg *cfg, size_t *bytes);
  * 256-byte aligned).  Replaces RLApi.__init__ (environment/RL_api.py:23) +
  * RLApi.setup_perception (RL_api.py:80-93).  Host-only: touches no device state. */
 int antsrl_create(const AntsCfg *cfg, void *workspace, size_t workspace_bytes, AntsHandle **out);
+
+/* The workspace as TWO caller-provided blocks (no reference counterpart).  The RECORD block holds what the kernels reach
+ * with scattered per-cell accesses: the interleaved {p0, p1, food, META} cell records, or — any other configuration — the
+ * pheromone buffers and the food / {food, META} records.  The STATE block holds everything else: the per-ant and per-env
+ * arrays (streamed), the bit maps, the perception frames, the rock tables, the generator's tables and the in-loop policy's
+ * pack.  On MI355X a scattered stream and a streaming one run slower against each other inside one zone of the device's
+ * memory than across two: with two blocks the caller can place them apart, which one block — one
+ * allocation, one zone — cannot.  The blocks may lie anywhere relative to each other (either may have the lower address);
+ * each is 256-byte aligned and must not overlap the other.  antsrl_workspace_bytes2 reports the two sizes (either pointer
+ * may be NULL); their sum equals antsrl_workspace_bytes.  A handle of antsrl_create2 behaves exactly like one of
+ * antsrl_create in every entry point, bit for bit; antsrl_create is antsrl_create2 over one block, carved in one sequence
+ * (the records between the per-ant arrays and the bit maps, where they have always been). */
+int antsrl_workspace_bytes2(const AntsCfg *cfg, size_t *state_bytes, size_t *record_bytes);
+int antsrl_create2(const AntsCfg *cfg, void *state_ws, size_t state_bytes, void *record_ws, size_t record_bytes,
+                   AntsHandle **out);
+
+/* Where every array of the workspace lies (host only; no reference counterpart: tests and tools check the carve with it).
+ * split = 0: the one block of antsrl_create (block is 0 for every entry); split = 1: the two blocks of antsrl_create2
+ * (block 0 = state, 1 = records).  Writes min(*count, cap) entries in carve order and sets *count to the number of arrays
+ * (entries may be NULL with cap 0).  An entry's reserved bytes are `bytes` rounded up to 256. */
+typedef struct AntsWsArray {
+    char name[24];
+    int32_t block, _pad;
+    uint64_t offset, bytes;
+} AntsWsArray;
+int antsrl_workspace_map(const AntsCfg *cfg, int split, AntsWsArray *entries, int32_t cap, int32_t *count);
 
 void antsrl_destroy(AntsHandle *h);
 
