@@ -28,7 +28,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_exptrain_grad", "antsrl_exptrain_apply", "antsrl_exptrain_step", "antsrl_rework_collapsed_bytes",
            "antsrl_rework_collapse", "antsrl_policy_rework", "antsrl_reworktrain_sizes", "antsrl_reworktrain_grad",
            "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select", "antsrl_monitor_sizes",
-           "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode")
+           "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
+           "antsrl_recorder_begin", "antsrl_recorder_frame")
 
 _lib = None
 
@@ -156,6 +157,9 @@ def load() -> C.CDLL:
     lib.antsrl_monitor_init.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.antsrl_monitor_step.argtypes = [vp, i32, i32, i32, i32, vp, vp, C.c_double, i32, i32, vp]
     lib.antsrl_monitor_end_episode.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp]
+    lib.antsrl_recorder_sizes.argtypes = [vp, i32, i32, i32, sz, sz, sz]
+    lib.antsrl_recorder_begin.argtypes = [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, vp]
+    lib.antsrl_recorder_frame.argtypes = [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

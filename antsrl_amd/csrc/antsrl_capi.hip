@@ -1,5 +1,6 @@
 // antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), and the library's error
-// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip.
+// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip; the episode recorder's are here (they need
+// the handle and its deferred update), its kernels in antsrl_recorder.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the
@@ -14,6 +15,7 @@
 
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
+#include "antsrl_recorder.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
@@ -976,6 +978,86 @@ extern "C" int antsrl_perceptive_field(AntsHandle *h, uint8_t *dst, void *stream
     //  reference, where RLApi.observation computes it; behind an update that has run it is the moved ants')
     hipError_t e = antsrl_launch_perceptive_field(h->p, dst, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "perceptive_field");
+    return ANTSRL_OK;
+}
+
+// ---- the episode recorder (include/antsrl.h, "The episode recorder"; kernels in antsrl_recorder.hip) ------------------
+static int recorder_layout(const char *who, const AntsHandle *h, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
+                           RecorderLayout *L)
+{
+    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
+    if (n_sel < 1 || n_sel > ANTSRL_RECORDER_MAX_ENVS)
+        return fail(ANTSRL_E_INVALID, "%s: n_sel %d is not in 1..%d", who, n_sel, ANTSRL_RECORDER_MAX_ENVS);
+    if (max_frames < 1) return fail(ANTSRL_E_INVALID, "%s: max_frames must be >= 1 (%d)", who, max_frames);
+    const bool keeps_map = h->cfg.reward_kind == ANTSRL_REWARD_EXPLORATION || h->cfg.reward_kind == ANTSRL_REWARD_ALL;
+    *L = antsrl_recorder_layout(n_sel, h->p.N, h->p.R, h->p.C, (size_t)h->p.W * h->p.H, with_heatmap && keeps_map ? 1 : 0);
+    return ANTSRL_OK;
+}
+
+// every argument of _begin / _frame (has_frame), before any HIP call
+static int recorder_check(const char *who, const AntsHandle *h, const void *block, const int32_t *env_indices, int32_t n_sel,
+                          int32_t max_frames, int32_t with_heatmap, bool has_frame, int32_t frame, RecorderLayout *L, RecorderSel *sel)
+{
+    int rc = recorder_layout(who, h, n_sel, max_frames, with_heatmap, L);
+    if (rc) return rc;
+    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
+    if ((uintptr_t)block & 15) return fail(ANTSRL_E_INVALID, "%s: block must be 16-byte aligned", who);
+    if (!env_indices) return fail(ANTSRL_E_INVALID, "%s: NULL env_indices", who);
+    memset(sel, 0, sizeof(*sel));
+    for (int s = 0; s < n_sel; ++s) {
+        const int32_t e = env_indices[s];
+        if (e < 0 || e >= h->p.E)
+            return fail(ANTSRL_E_INVALID, "%s: env_indices[%d] = %d is not in [0, n_envs = %d)", who, s, e, h->p.E);
+        for (int t = 0; t < s; ++t)
+            if (sel->env[t] == e) return fail(ANTSRL_E_INVALID, "%s: env_indices[%d] repeats environment %d", who, s, e);
+        sel->env[s] = e;
+    }
+    if (has_frame && (frame < 0 || frame >= max_frames))
+        return fail(ANTSRL_E_INVALID, "%s: frame %d is not in [0, max_frames = %d)", who, frame, max_frames);
+    if (!h->is_reset) return not_reset(h);
+    if (h->phase_next) return mid_update(h);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_recorder_sizes(const AntsHandle *h, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
+                                     size_t *static_bytes, size_t *frame_bytes, size_t *bytes)
+{
+    RecorderLayout L;
+    int rc = recorder_layout("recorder_sizes", h, n_sel, max_frames, with_heatmap, &L);
+    if (rc) return rc;
+    if (static_bytes) *static_bytes = L.static_bytes;
+    if (frame_bytes) *frame_bytes = L.frame_bytes;
+    if (bytes) *bytes = L.static_bytes + (size_t)max_frames * L.frame_bytes;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_recorder_begin(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
+                                     int32_t max_frames, int32_t with_heatmap, void *stream)
+{
+    RecorderLayout L;
+    RecorderSel sel;
+    int rc = recorder_check("recorder_begin", h, block, env_indices, n_sel, max_frames, with_heatmap, false, 0, &L, &sel);
+    if (rc) return rc;
+    rc = flush_pending(h, (hipStream_t)stream); // (as antsrl_read_state: the log holds the state after the update)
+    if (rc) return rc;
+    hipError_t e = antsrl_launch_record_static(h->p, L, sel, (unsigned char *)block, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "recorder_begin");
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
+                                     int32_t max_frames, int32_t with_heatmap, int32_t frame, void *stream)
+{
+    RecorderLayout L;
+    RecorderSel sel;
+    int rc = recorder_check("recorder_frame", h, block, env_indices, n_sel, max_frames, with_heatmap, true, frame, &L, &sel);
+    if (rc) return rc;
+    rc = flush_pending(h, (hipStream_t)stream); // a frame is the state AFTER Environment.update (main.py:138)
+    if (rc) return rc;
+    hipError_t e = antsrl_launch_record_frame(h->p, h->cur, L, sel,
+                                              (unsigned char *)block + L.static_bytes + (size_t)frame * L.frame_bytes,
+                                              (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "recorder_frame");
     return ANTSRL_OK;
 }
 

@@ -1,6 +1,7 @@
 // antsrl_state.hip — reset, device-side episode generator, activation, state read-out (not on the hot
 // path), launchers.
 #include "antsrl_util.h"
+#include "antsrl_cellread.h"
 
 // ===================================================================================
 // reset / state I/O (not on the hot path)
@@ -434,48 +435,36 @@ __global__ void k_read_state(const KP p, const int which, const int cur, void *_
     case ANTSRL_S_PHERO: // interleaved [E][G][C] -> canonical [E][C][G]
         for (size_t i = t0; i < EG * p.C; i += stride) {
             const size_t e = i / (G * p.C), rem = i - e * G * p.C, c = rem / G, g = rem - c * G;
-            float v = p.s.phero[cur][(e * G + prec_cell(p, (uint32_t)g)) * p.ps + c];
-            if (p.scaled) {
-                v *= (float)p.g_now;
-                if (v < (float)p.threshold) v = 0.0f;
-            }
-            ((float *)dstv)[i] = v;
+            ((float *)dstv)[i] = cell_phero(p, cur, e, G, (uint32_t)g, (int)c);
         }
         break;
     case ANTSRL_S_PHERO_C0: case ANTSRL_S_PHERO_C1: case ANTSRL_S_PHERO_C2: case ANTSRL_S_PHERO_C3: {
         const int c = which - ANTSRL_S_PHERO_C0; // one channel [E][W][H]
         for (size_t i = t0; i < EG; i += stride) {
             const size_t e = i / G;
-            float v = p.s.phero[cur][(e * G + prec_cell(p, (uint32_t)(i - e * G))) * p.ps + c];
-            if (p.scaled) {
-                v *= (float)p.g_now;
-                if (v < (float)p.threshold) v = 0.0f;
-            }
-            ((float *)dstv)[i] = v;
+            ((float *)dstv)[i] = cell_phero(p, cur, e, G, (uint32_t)(i - e * G), c);
         }
     } break;
     case ANTSRL_S_FOOD:
         for (size_t i = t0; i < EG; i += stride) {
             const size_t e = i / G;
-            ((float *)dstv)[i] = p.s.food[(e * G + frec_cell(p, (uint32_t)(i - e * G))) * p.fs];
+            ((float *)dstv)[i] = cell_food(p, e, G, (uint32_t)(i - e * G));
         }
         break;
     case ANTSRL_S_EXPLORED:
     case ANTSRL_S_WALLS:
     case ANTSRL_S_ANTHILL_AREA: {
-        const uint32_t *bits = which == ANTSRL_S_EXPLORED ? p.s.explored_bits
-                               : which == ANTSRL_S_WALLS  ? p.s.walls_bits : p.s.area_bits;
-        if (which == ANTSRL_S_EXPLORED && p.meta) { // cell-meta layout: explored <=> the cell carries a stamp
-            const uint32_t *m = reinterpret_cast<const uint32_t *>(p.s.food) + 1;
+        const uint32_t *bits = which == ANTSRL_S_WALLS ? p.s.walls_bits : p.s.area_bits;
+        if (which == ANTSRL_S_EXPLORED) { // (the stamps of the cell-meta layout, or k_act's bit map: cell_explored)
             for (size_t i = t0; i < EG; i += stride) {
                 const size_t e = i / G;
-                ((uint8_t *)dstv)[i] = (uint8_t)((m[(e * G + frec_cell(p, (uint32_t)(i - e * G))) * p.fs] >> META_STAMP_SHIFT) != META_NEVER);
+                ((uint8_t *)dstv)[i] = cell_explored(p, e, G, (uint32_t)(i - e * G));
             }
             break;
         }
         for (size_t i = t0; i < EG; i += stride) {
             const size_t e = i / G, g = i - e * G;
-            ((uint8_t *)dstv)[i] = (uint8_t)test_bit(bits + e * p.words, (uint32_t)g);
+            ((uint8_t *)dstv)[i] = cell_bit(p, bits, e, (uint32_t)g);
         }
     } break;
     case ANTSRL_S_ANTHILL_FOOD: for (size_t i = t0; i < (size_t)p.E; i += stride) ((double *)dstv)[i] = p.s.anthill_food[i]; break;

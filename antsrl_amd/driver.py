@@ -6,7 +6,8 @@ runs what the reference's driver runs, on one BatchedAntsEnv handle and without 
 per episode (antsrl_generate on the same handle), agent.setup once, agent.initialize and the first observation per
 episode, `steps` rollout_steps each followed by EpisodeMonitor.step(env.reward, loss), EpisodeMonitor.end_episode, and
 the epsilon schedule (:149).  The statistics are the monitor's (antsrl_amd/monitor.py); the one synchronisation is its
-log() at the end (and the snapshots, where asked for: a snapshot is a read-back).
+log() at the end (and the snapshots, where asked for: a snapshot is a read-back — unless snapshot_on_device keeps the
+visualised episodes' frames on the device, antsrl_amd/recorder.py, and reads them once per such episode).
 """
 from __future__ import annotations
 
@@ -17,6 +18,7 @@ import numpy as np
 
 from . import config as cm
 from .monitor import EpisodeMonitor
+from .recorder import EpisodeRecorder
 from .snapshot import snapshot_batched
 
 
@@ -36,14 +38,17 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
 
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,
                    min_epsilon: float = 0.01, max_epsilon: float = 1.0, monitor: Optional[EpisodeMonitor] = None,
-                   snapshot_every: Optional[int] = None, save_as: Optional[str] = None) -> dict:
+                   snapshot_every: Optional[int] = None, save_as: Optional[str] = None, snapshot_on_device: bool = False,
+                   snapshot_envs=(0,)) -> dict:
     """main.py's loop for `agent` (a device agent: MemoryAgent, CollectAgent, ExploreAgent, ReworkAgent) on `env` (a
     BatchedAntsEnv).  gen: the AntsGen handed to env.generate for every episode (config.make_gen).  An agent that has
     not been set up is set up on `env` at the first episode (once, :82-84).  monitor: an EpisodeMonitor to continue or
     one with another report_every; by default one sized to this run that reports every 50 steps (:115).
     snapshot_every: keep snapshot_batched(env) after every step of episode 0 and of every snapshot_every-th episode
-    (:67, :137-138, main.py's visualize_every); those episodes synchronise at every step.  save_as: agent.save_model at
-    the end, when training (:154-157).
+    (:67, :137-138, main.py's visualize_every); those episodes synchronise at every step.  snapshot_on_device: those
+    episodes record into an EpisodeRecorder instead (environments snapshot_envs, a block of `steps` frames reused by
+    every visualised episode): one launch per step, and one read-back at the episode's end for the same snapshots.
+    save_as: agent.save_model at the end, when training (:154-157).
 
     Returns the monitor's log() (reports, report_episode, report_step, all_reward, all_loss, grand_total, n_losses)
     with `epsilons` (the epsilon each episode ran with), `monitor`, and `states` (the snapshots, in order) when
@@ -52,6 +57,7 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
     mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=50, max_reports=max(1, episodes * (steps // 50)),
                                                              max_episodes=max(1, episodes))
     states, epsilons = [], []
+    recorder = None
     for episode in range(episodes):
         visualize = snapshot_every is not None and ((episode + 1) % snapshot_every == 0 or episode == 0 or not training)
         env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
@@ -59,12 +65,21 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
             agent.setup(env)
         agent.initialize(env)
         env.observe()
+        on_device = visualize and snapshot_on_device
+        if on_device:
+            if recorder is None:
+                recorder = EpisodeRecorder(env, env_indices=snapshot_envs, max_frames=max(1, steps))
+            recorder.begin()
         epsilons.append(float(agent.epsilon))
         for s in range(steps):
             loss = agent.rollout_step(env, training)
             mon.step(env.reward, loss if training else None)
-            if visualize:
+            if on_device:
+                recorder.record()
+            elif visualize:
                 states.extend(snapshot_batched(env))
+        if on_device:
+            states.extend(recorder.snapshots())
         mon.end_episode()
         agent.epsilon = epsilon_schedule(episode, min_epsilon, max_epsilon)
     if save_as is not None and training:

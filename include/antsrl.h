@@ -1028,6 +1028,61 @@ int antsrl_monitor_step(void *state, int32_t n_envs, int32_t n_ants, int32_t max
 int antsrl_monitor_end_episode(void *state, int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes,
                                int episode_slot, int last_report_slot, void *stream);
 
+/* The episode recorder: the replay viewer's snapshots (Environment.save_state, environment.py:36-40: the visualisation
+ * copies main.py:138 keeps after every step of a visualised episode) of up to ANTSRL_RECORDER_MAX_ENVS chosen
+ * environments, packed into a device-resident frame log with ONE launch per step and nothing read back.  The log is ONE
+ * caller-allocated device block (16-byte aligned, `bytes` of antsrl_recorder_sizes); the caller copies it to the host at
+ * the episode's end and decodes it (antsrl_amd/recorder.py).
+ *
+ * The block, for S = n_sel environments of N ants, R rocks, C pheromone channels and G = W * H cells.  Every section
+ * starts 16-byte aligned: a section of n bytes takes a16(n) = n rounded up to 16, and the kernels write its padding as
+ * zeros.  First the static part, static_bytes = S * (16 + 16 R + a16(G)); per selected environment, in the order of
+ * env_indices:
+ *     anthill_xyr   int32 [3], 4 bytes of zeros       Anthill.x, .y, .radius
+ *     rock_rw       double [R][2]                      {radius, weight} per rock
+ *     walls         uint8 [W][H]                       Walls.map (0 / 1)
+ * then max_frames frames of frame_bytes each, frame f at static_bytes + f * frame_bytes; a frame holds the S
+ * environments in the order of env_indices, frame_bytes = S * (32 + 16 R + a16(24 N) + a16(4 N) + 2 a16(N) +
+ * (C + 1 + X) a16(G)) with X = 1 when the explored section is present; per environment:
+ *     timestep      int32, 12 bytes of zeros           Environment.timestep
+ *     anthill_food  double, 8 bytes of zeros           Anthill.food
+ *     rock_centers  double [R][2]
+ *     ants_xyt      double [N][3]                      Ants.ants
+ *     holding       float  [N]
+ *     mandibles     uint8  [N]
+ *     reward_state  uint8  [N]
+ *     phero         uint8  [C] planes of [W][H], each plane a16(G) bytes     pheromone.py:17
+ *     food          uint8  [W][H]                      food.py:10
+ *     explored      uint8  [W][H] (0 / 1)              the reward's explored_map: present only with with_heatmap != 0 on a
+ *                                                      handle whose reward kind keeps one (ANTSRL_REWARD_EXPLORATION,
+ *                                                      ANTSRL_REWARD_ALL); otherwise the section is absent, not zero
+ * The values are what antsrl_read_state gives for ANTSRL_S_PHERO, _FOOD, _EXPLORED, _WALLS and the per-ant / per-env
+ * selectors at the same moment, on every layout the handle can be in; phero and food are then cast to uint8.
+ * THE CAST: (uint8_t)(int32_t)v, truncation toward zero, for 0 <= v < 256, which is numpy's astype(np.uint8) there; a
+ * value of 256 or more SATURATES to 255 (a pheromone without max_val, a food pile above 255: numpy's result for those
+ * is platform-defined).
+ *   _sizes:  the three sizes (any of the pointers may be NULL); no HIP call.
+ *   _begin:  ONE launch: the static part.  Call it after antsrl_reset / antsrl_generate and before the episode's first
+ *            _frame; with AntsGen.auto_reset the walls, the anthill and the rocks change at the reset, so the caller
+ *            calls _begin again at an episode boundary.
+ *   _frame:  ONE launch: frame `frame` of the block, from the state as it stands.  A frame is the state AFTER
+ *            Environment.update (where main.py:138 takes it): like antsrl_read_state, _begin and _frame first enqueue a
+ *            deferred update on their stream argument (see antsrl_update), which therefore does not fuse with the next
+ *            step's move.
+ * env_indices is a HOST array of n_sel distinct indices in [0, n_envs); they travel to the kernel by value.  The same
+ * n_sel, max_frames and with_heatmap go to every call on one block (they fix its layout).
+ * Rules, all checked before any HIP call (ANTSRL_E_INVALID, the block untouched): block not NULL and 16-byte aligned;
+ * 1 <= n_sel <= ANTSRL_RECORDER_MAX_ENVS; env_indices not NULL, every index in [0, n_envs), none repeated;
+ * max_frames >= 1; frame in [0, max_frames): a frame is never wrapped; a handle that has been reset; no
+ * Environment.update in progress (antsrl_update_phase).  No entry allocates or synchronises the host. */
+#define ANTSRL_RECORDER_MAX_ENVS 8
+int antsrl_recorder_sizes(const AntsHandle *h, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
+                          size_t *static_bytes, size_t *frame_bytes, size_t *bytes);
+int antsrl_recorder_begin(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
+                          int32_t max_frames, int32_t with_heatmap, void *stream);
+int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
+                          int32_t max_frames, int32_t with_heatmap, int32_t frame, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
