@@ -29,7 +29,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_rework_collapse", "antsrl_policy_rework", "antsrl_reworktrain_sizes", "antsrl_reworktrain_grad",
            "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select", "antsrl_monitor_sizes",
            "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
-           "antsrl_recorder_begin", "antsrl_recorder_frame")
+           "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames")
 
 _lib = None
 
@@ -49,6 +49,12 @@ class AntsRecordSpec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_envs", "n_ants", "env_id_base", "n_features", "agent_dim", "mem_size", "n_rot",
                                          "obs_format", "obs_pitch", "reserved")] + [
         (n, C.c_int64) for n in ("K", "head", "max_len")] + [(n, C.c_uint64) for n in ("seed", "step")]
+
+
+class AntsRenderOpts(C.Structure):
+    """include/antsrl.h AntsRenderOpts."""
+    _fields_ = [(n, C.c_int32) for n in ("zoom", "view_mask", "ant_radius", "layer_only")] + [
+        ("phero_max_val", C.c_double), ("phero_colors", (C.c_uint8 * 3) * 4)]
 
 
 class AntsWsArray(C.Structure):
@@ -160,6 +166,8 @@ def load() -> C.CDLL:
     lib.antsrl_recorder_sizes.argtypes = [vp, i32, i32, i32, sz, sz, sz]
     lib.antsrl_recorder_begin.argtypes = [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, vp]
     lib.antsrl_recorder_frame.argtypes = [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]
+    lib.antsrl_render_sizes.argtypes = [vp, i32, C.POINTER(AntsRenderOpts), sz, sz]
+    lib.antsrl_render_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(AntsRenderOpts), vp, vp, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -1,6 +1,7 @@
 // antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), and the library's error
 // reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip; the episode recorder's are here (they need
-// the handle and its deferred update), its kernels in antsrl_recorder.hip.
+// the handle and its deferred update), its kernels in antsrl_recorder.hip; the episode renderer's stand beside them (they
+// take the recorder's block and its layout), its kernels in antsrl_render.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the
@@ -16,6 +17,7 @@
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
 #include "antsrl_recorder.h"
+#include "antsrl_render.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
 hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
@@ -1058,6 +1060,68 @@ extern "C" int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *
                                               (unsigned char *)block + L.static_bytes + (size_t)frame * L.frame_bytes,
                                               (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "recorder_frame");
+    return ANTSRL_OK;
+}
+
+// ---- the episode renderer (include/antsrl.h, "The episode renderer"; kernels in antsrl_render.hip) --------------------
+static int render_opts(const char *who, const AntsHandle *h, int32_t n_sel, const AntsRenderOpts *o)
+{
+    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
+    if (!o) return fail(ANTSRL_E_INVALID, "%s: NULL opts", who);
+    if (n_sel < 1 || n_sel > ANTSRL_RECORDER_MAX_ENVS)
+        return fail(ANTSRL_E_INVALID, "%s: n_sel %d is not in 1..%d", who, n_sel, ANTSRL_RECORDER_MAX_ENVS);
+    if (o->zoom < 1 || o->zoom > ANTSRL_RENDER_MAX_ZOOM)
+        return fail(ANTSRL_E_INVALID, "%s: zoom %d is not in 1..%d", who, o->zoom, ANTSRL_RENDER_MAX_ZOOM);
+    if (o->ant_radius < 0 || o->ant_radius > ANTSRL_RENDER_MAX_ANT_RADIUS)
+        return fail(ANTSRL_E_INVALID, "%s: ant_radius %d is not in 0..%d", who, o->ant_radius, ANTSRL_RENDER_MAX_ANT_RADIUS);
+    if (!(o->phero_max_val > 0.0)) return fail(ANTSRL_E_INVALID, "%s: phero_max_val must be > 0 (%g)", who, o->phero_max_val);
+    if (o->view_mask & ~ANTSRL_RENDER_VIEW_ALL)
+        return fail(ANTSRL_E_INVALID, "%s: view_mask 0x%x has bits outside 0x%x", who, (unsigned)o->view_mask, ANTSRL_RENDER_VIEW_ALL);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_render_sizes(const AntsHandle *h, int32_t n_sel, const AntsRenderOpts *o, size_t *frame_env_bytes,
+                                   size_t *scratch_bytes_per_frame)
+{
+    int rc = render_opts("render_sizes", h, n_sel, o);
+    if (rc) return rc;
+    const size_t W = (size_t)h->p.W, H = (size_t)h->p.H, Z = (size_t)o->zoom;
+    if (frame_env_bytes) *frame_env_bytes = o->layer_only ? 4 * W * H : 3 * (W * Z) * (H * Z);
+    if (scratch_bytes_per_frame) *scratch_bytes_per_frame = 4 * (size_t)n_sel;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_render_frames(AntsHandle *h, const void *block, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
+                                    int32_t first, int32_t count, const AntsRenderOpts *o, void *out, void *scratch, void *stream)
+{
+    const char *who = "render_frames";
+    int rc = render_opts(who, h, n_sel, o);
+    if (rc) return rc;
+    RenderArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = recorder_layout(who, h, n_sel, max_frames, with_heatmap, &a.L);
+    if (rc) return rc;
+    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
+    if (!out) return fail(ANTSRL_E_INVALID, "%s: NULL out", who);
+    if (!scratch) return fail(ANTSRL_E_INVALID, "%s: NULL scratch", who);
+    if ((uintptr_t)block & 15) return fail(ANTSRL_E_INVALID, "%s: block must be 16-byte aligned", who);
+    if ((uintptr_t)out & 15) return fail(ANTSRL_E_INVALID, "%s: out must be 16-byte aligned", who);
+    if ((uintptr_t)scratch & 15) return fail(ANTSRL_E_INVALID, "%s: scratch must be 16-byte aligned", who);
+    if (first < 0 || count < 1 || (long long)first + count > max_frames)
+        return fail(ANTSRL_E_INVALID, "%s: frames %d .. %d + %d are not inside [0, max_frames = %d)", who, first, first, count, max_frames);
+    const size_t groups = o->layer_only ? render_layer_groups(a.L.G) : render_tiles(h->p.W, h->p.H, o->zoom);
+    if (count > 65535 || groups * (size_t)n_sel * (size_t)count >= ANTSRL_RENDER_MAX_GROUPS)
+        return fail(ANTSRL_E_INVALID, "%s: count %d is past the launch limits (65535 frames, %zu workgroups per frame of 2^24): split the call",
+                    who, count, groups * (size_t)n_sel);
+    if (!h->is_reset) return not_reset(h); // (the block was recorded from this handle)
+    a.block = (const unsigned char *)block;
+    a.out = (unsigned char *)out;
+    a.fmax = (int32_t *)scratch;
+    a.W = h->p.W; a.H = h->p.H; a.Z = o->zoom; a.TY = render_ty(o->zoom); a.view = o->view_mask; a.ra = o->ant_radius; a.first = first; a.count = count;
+    a.phero_den = o->phero_max_val + 0.0001;
+    memcpy(a.col, o->phero_colors, sizeof(a.col));
+    hipError_t e = antsrl_launch_render(a, o->layer_only != 0, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, who);
     return ANTSRL_OK;
 }
 

@@ -7,11 +7,13 @@ per episode (antsrl_generate on the same handle), agent.setup once, agent.initia
 episode, `steps` rollout_steps each followed by EpisodeMonitor.step(env.reward, loss), EpisodeMonitor.end_episode, and
 the epsilon schedule (:149).  The statistics are the monitor's (antsrl_amd/monitor.py); the one synchronisation is its
 log() at the end (and the snapshots, where asked for: a snapshot is a read-back — unless snapshot_on_device keeps the
-visualised episodes' frames on the device, antsrl_amd/recorder.py, and reads them once per such episode).
+visualised episodes' frames on the device, antsrl_amd/recorder.py, and reads them once per such episode).  With render_dir
+those episodes are also drawn on the device (antsrl_amd/render.py) and written as PNG files.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import numpy as np
@@ -19,6 +21,7 @@ import numpy as np
 from . import config as cm
 from .monitor import EpisodeMonitor
 from .recorder import EpisodeRecorder
+from .render import EpisodeRenderer
 from .snapshot import snapshot_batched
 
 
@@ -39,7 +42,7 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,
                    min_epsilon: float = 0.01, max_epsilon: float = 1.0, monitor: Optional[EpisodeMonitor] = None,
                    snapshot_every: Optional[int] = None, save_as: Optional[str] = None, snapshot_on_device: bool = False,
-                   snapshot_envs=(0,)) -> dict:
+                   snapshot_envs=(0,), render_dir: Optional[str] = None, render_every: int = 1) -> dict:
     """main.py's loop for `agent` (a device agent: MemoryAgent, CollectAgent, ExploreAgent, ReworkAgent) on `env` (a
     BatchedAntsEnv).  gen: the AntsGen handed to env.generate for every episode (config.make_gen).  An agent that has
     not been set up is set up on `env` at the first episode (once, :82-84).  monitor: an EpisodeMonitor to continue or
@@ -48,6 +51,9 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
     (:67, :137-138, main.py's visualize_every); those episodes synchronise at every step.  snapshot_on_device: those
     episodes record into an EpisodeRecorder instead (environments snapshot_envs, a block of `steps` frames reused by
     every visualised episode): one launch per step, and one read-back at the episode's end for the same snapshots.
+    render_dir (needs snapshot_on_device): after the last step of a visualised episode — the moment main.py pickles —
+    every render_every-th recorded frame of the first of snapshot_envs is drawn by an EpisodeRenderer with its defaults
+    (a pheromone without max_val is divided by 255, where the recorder's cast saturates) and written to render_dir/episode_%04d/frame_%05d.png.
     save_as: agent.save_model at the end, when training (:154-157).
 
     Returns the monitor's log() (reports, report_episode, report_step, all_reward, all_loss, grand_total, n_losses)
@@ -56,8 +62,10 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
     env = getattr(env, "_backend", env)
     mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=50, max_reports=max(1, episodes * (steps // 50)),
                                                              max_episodes=max(1, episodes))
+    if render_dir is not None and not snapshot_on_device:
+        raise ValueError("train_episodes: render_dir draws the recorder's frames: it needs snapshot_on_device=True")
     states, epsilons = [], []
-    recorder = None
+    recorder = renderer = None
     for episode in range(episodes):
         visualize = snapshot_every is not None and ((episode + 1) % snapshot_every == 0 or episode == 0 or not training)
         env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
@@ -80,6 +88,10 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
                 states.extend(snapshot_batched(env))
         if on_device:
             states.extend(recorder.snapshots())
+            if render_dir is not None and recorder.n_frames:
+                if renderer is None:
+                    renderer = EpisodeRenderer(recorder, phero_max_val=None if env.cfg.has_max_val else 255.0)
+                renderer.save(os.path.join(render_dir, "episode_%04d" % episode), every=render_every)
         mon.end_episode()
         agent.epsilon = epsilon_schedule(episode, min_epsilon, max_epsilon)
     if save_as is not None and training:

@@ -79,6 +79,16 @@ class EpisodeRecorder:
         self.n_frames = 0
         self._begun = False
 
+    @property
+    def static_fields(self):
+        """The sections of one environment's piece of the static part, in order: (name, dtype, shape, bytes)."""
+        return list(self._static_fields)
+
+    @property
+    def frame_fields(self):
+        """The sections of one environment's piece of a frame, in order (pheromone plane k is "phero%d" % k)."""
+        return list(self._frame_fields)
+
     def _args(self):
         return (self.env._h, _p(self.block), self._idx, len(self.env_indices), self.max_frames, int(self.with_heatmap))
 

@@ -1083,6 +1083,71 @@ int antsrl_recorder_begin(AntsHandle *h, void *block, const int32_t *env_indices
 int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
                           int32_t max_frames, int32_t with_heatmap, int32_t frame, void *stream);
 
+/* The episode renderer: RGB frames of a recorded episode, computed on the device from the episode recorder's block and
+ * from nothing else (the live state is not read, so no deferred update is enqueued and a running episode is not
+ * disturbed; the block is read-only here).  It stands in for the reference's replay viewer (gui/visualize.py), of which
+ * it reproduces ONE part bit for bit — the colour layer, the chain of mix_alpha calls (visualize.py:23-26, :220-244) —
+ * and replaces the rest (pygame sprites and textures) with a composition of its own, in integers.  One call renders
+ * `count` frames, frames first .. first + count - 1 of the block, for all S = n_sel recorded environments.
+ *
+ * view_mask: bit i is the viewer's view[i]: 0 background (dirt, anthill, walls), 1 ants, 2 explored map, 3 pheromones,
+ * 4 food, 5 rocks.  ANTSRL_RENDER_VIEW_ALL sets them all; any other bit is refused.
+ *
+ * THE COLOUR LAYER, per cell, in float64 with every product, sum and quotient rounded on its own (no fused
+ * multiply-add) and one IEEE division per channel.  It starts from rgb = (255, 255, 255), A = 0.0 and applies, in the
+ * order a snapshot lists its objects (food, the pheromones 0 .. C - 1, the explored map):
+ *     food         colour (64, 255, 64)       a = food / (max + 0.0001) * 0.3        view bit 4
+ *                  (max: the maximum of THIS frame's food plane of this environment)
+ *     pheromone k  colour phero_colors[k]     a = (phero / (phero_max_val + 0.0001)) * 0.6      view bit 3
+ *     explored     colour (255, 255, 0)       a = explored / 1.0 * 0.3               view bit 2, only where the block has
+ *                                                                                    the explored section
+ * each as   m = A + a * (1 - A);   per channel  v = (rgb * A + (colour * a) * (1 - A)) / (m + 0.001),  rgb = (uint8) v
+ * (truncated);   A = m.   After the chain alpha8 = (uint8)(A * 255).  A layer whose view bit is clear is skipped
+ * entirely.  These are the reference's bytes (tests/golden/contract/render_layer_ref.npz holds its own mix_alpha's) but
+ * for two cases: an explored map that is all false is 0 / 0 in the reference (it cannot occur after a recorded step);
+ * here its alpha is 0 in every cell, as in any unexplored cell.  A pheromone without max_val makes the reference's
+ * viewer raise; here the caller passes phero_max_val > 0 (255, where the recorder's cast saturates, is the natural one).
+ *
+ * THE COMPOSITION, in integers.  Image row py is y and column px is x (what pygame's surfarray shows); the cell of a
+ * pixel is (px / zoom, py / zoom) — nearest-neighbour upscaling.  blend(src, a, dst) = (src * a + dst * (255 - a) +
+ * 127) / 255 per channel.  Per cell, in this order: the background, dirt (134, 96, 67) under view bit 0, else black;
+ * the anthill (0, 0, 255) blended at alpha 128 where (ax - x)^2 + (ay - y)^2 <= r^2, under view bit 0; the colour
+ * layer blended at alpha8; a wall cell, opaque rock (96, 96, 96), under view bit 0.  Then per pixel: the rocks under
+ * view bit 5, flat (150, 150, 150) where dx * dx + dy * dy <= rad * rad with dx = (px + 0.5) / zoom - cx and dy
+ * likewise (float64, every operation rounded); the ants under view bit 1: ant i has its centre at ((int)(x * zoom),
+ * (int)(y * zoom)) and covers the pixels with integer dx^2 + dy^2 <= ant_radius^2, in the colour ((uint8)(255 * rs /
+ * 255.0), the same, (uint8)(128 * rs / 255.0)) for rs = reward_state[i] (REWARD_ANTS_COLOR * reward_state / 255), but
+ * where holding[i] > 0 the pixels with dx^2 + dy^2 <= (ant_radius / 2)^2 (integer division) are (64, 255, 64).  Where
+ * ants overlap the HIGHEST index wins (the reference blits in index order); ants are clipped at the image's edge.
+ * There is no heading mark, no sprite, no texture and no text.
+ *
+ * out: uint8 [count][S][H * zoom][W * zoom][3]; with layer_only != 0 instead uint8 [count][S][W][H][4], the colour
+ * layer's R, G, B and alpha8 per cell.  scratch: count * scratch_bytes_per_frame bytes (the food maxima).
+ *   _sizes:   frame_env_bytes = one environment's picture of one frame (3 * W * zoom * H * zoom, or 4 * W * H with
+ *             layer_only); scratch_bytes_per_frame = 4 * n_sel.  Either pointer may be NULL.  No HIP call.
+ *   _frames:  two launches (the food maxima, then the frames) on `stream`.  block, n_sel, max_frames and with_heatmap are
+ *             what the block was recorded with.
+ * Rules, all checked before any HIP call (ANTSRL_E_INVALID, out and scratch untouched): handle, opts, block, out and
+ * scratch not NULL; block, out and scratch 16-byte aligned; 1 <= n_sel <= ANTSRL_RECORDER_MAX_ENVS; max_frames >= 1;
+ * 1 <= zoom <= ANTSRL_RENDER_MAX_ZOOM; 0 <= ant_radius <= ANTSRL_RENDER_MAX_ANT_RADIUS; phero_max_val > 0 (and not
+ * NaN); view_mask within ANTSRL_RENDER_VIEW_ALL; first >= 0, count >= 1, first + count <= max_frames; and the launch
+ * limits: count <= 65535 and groups * n_sel * count < 2^24, where groups = ceil(W / 32) * ceil(H / ty) with ty = 32
+ * for zoom 1 and 2, 16 for zoom 3, 8 for zoom 4 and 5 and 4 above (a workgroup's tile of cells), or ceil(W * H /
+ * 256) with layer_only — a caller with more frames splits them over several calls; and a handle that has been reset
+ * (the block was recorded from it).  The entries do not allocate and do not synchronise the host. */
+#define ANTSRL_RENDER_MAX_ZOOM 8
+#define ANTSRL_RENDER_MAX_ANT_RADIUS 1024
+#define ANTSRL_RENDER_VIEW_ALL 63
+typedef struct {
+    int32_t zoom, view_mask, ant_radius, layer_only;
+    double phero_max_val;
+    uint8_t phero_colors[4][3];
+} AntsRenderOpts;
+int antsrl_render_sizes(const AntsHandle *h, int32_t n_sel, const AntsRenderOpts *o,
+                        size_t *frame_env_bytes, size_t *scratch_bytes_per_frame);
+int antsrl_render_frames(AntsHandle *h, const void *block, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
+                         int32_t first, int32_t count, const AntsRenderOpts *o, void *out, void *scratch, void *stream);
+
 /* Copies one piece of state into a caller device buffer in the canonical
  * reference-shaped layout (ANTSRL_S_*).  Replaces attribute reads such as
  * api.ants.ants, pheromone.phero, food.qte, anthill.food. */
