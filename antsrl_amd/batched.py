@@ -589,6 +589,11 @@ class BatchedAntsEnv:
         _lib.check(self.lib.antsrl_query(self._h, int(what), C.byref(v)), "query")
         return int(v.value)
 
+    def set_perceive_path(self, path: int) -> None:
+        """antsrl_set_perceive_path: config.PERCEIVE_GENERIC pins k_perceive's generic kernel, config.PERCEIVE_AUTO gives the
+        choice back to the library (config.Q_PERCEIVE_FAST tells which one runs)."""
+        _lib.check(self.lib.antsrl_set_perceive_path(self._h, int(path)), "set_perceive_path")
+
     def set_activation(self, act, new_deposit_strength: float = 0.0) -> None:
         """Ants.activate_all_pheromones (ants.py:86-87)."""
         c = self.cfg

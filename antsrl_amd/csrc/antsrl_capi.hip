@@ -39,7 +39,8 @@ bool antsrl_meta_supported(const KP &p);
 hipError_t antsrl_launch_move(const KP &p, const int8_t *rot, const int8_t *ph, uint8_t *done, int do_step, uint32_t seq,
                               hipStream_t st);
 hipError_t antsrl_launch_perceive(const KP &p, int cur, float *obs, float *agent_state, float *reward, int flags,
-                                  uint32_t seq, hipStream_t st, const PolArgs *pol, uint32_t obs_pitch);
+                                  uint32_t seq, hipStream_t st, const PolArgs *pol, uint32_t obs_pitch, bool generic);
+bool antsrl_perceive_fast(const KP &p);
 bool antsrl_inloop_policy_supported(const KP &p);
 hipError_t antsrl_launch_policy_pack(unsigned char *pack, const float *w1, const float *b1, const float *w2, const float *b2,
                                      const float *w3, const float *b3, int F, hipStream_t st);
@@ -66,6 +67,7 @@ struct AntsHandle {
     long long sweeps;      // scaled mode: updates since the units were last re-based
     bool obs_bf16;         // observation buffers are bfloat16 (antsrl_set_obs_format)
     uint32_t obs_pitch;    // elements between two ants' observation rows (antsrl_set_obs_row_stride), 0 = dense
+    bool prc_generic;      // k_perceive's generic kernel is pinned (antsrl_set_perceive_path)
     bool need_wall_clear;  // scaled mode: initial grid may hold pheromone on wall cells
     hipEvent_t ev[ANTSRL_TIMING_EVENTS]; // measurement hook (antsrl_set_timing_events)
     bool ev_armed;
@@ -389,6 +391,7 @@ static int create_handle(const AntsCfg *cfg, void *state_ws, void *record_ws, bo
     h->pol = PolArgs{};
     h->sweeps = 0; h->need_wall_clear = false;
     h->has_gen = false; h->episode_seed = 0; h->host_timestep = 1; h->obs_bf16 = false; h->obs_pitch = 0;
+    h->prc_generic = false;
     h->ws_bytes[0] = need[0]; h->ws_bytes[1] = need[1];
     h->ev_armed = false;
     h->obs_seq = 0;
@@ -557,6 +560,14 @@ extern "C" int antsrl_set_obs_row_stride(AntsHandle *h, int32_t stride_elems)
     return ANTSRL_OK;
 }
 
+extern "C" int antsrl_set_perceive_path(AntsHandle *h, int path)
+{
+    if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
+    if (path != ANTSRL_PERCEIVE_AUTO && path != ANTSRL_PERCEIVE_GENERIC) return fail(ANTSRL_E_INVALID, "bad perceive path %d", path);
+    h->prc_generic = path == ANTSRL_PERCEIVE_GENERIC;
+    return ANTSRL_OK;
+}
+
 // Enqueues a deferred update on its own (k_update_one), e.g. ahead of a state read.
 static int flush_pending(AntsHandle *h, hipStream_t st)
 {
@@ -612,7 +623,7 @@ static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, floa
     e = antsrl_launch_perceive(h->p, h->cur, obs, agent_state, reward,
                                (stepping ? ACT_STEP : 0) | (obs ? ACT_HAS_OBS : 0) | (frames ? ACT_FRAMES : 0) |
                                    ((obs || h->pol.pack) && h->obs_bf16 ? ACT_OBS_BF16 : 0), // (act-only: rows in LDS, bf16)
-                               h->obs_seq, st, &h->pol, h->obs_pitch);
+                               h->obs_seq, st, &h->pol, h->obs_pitch, h->prc_generic);
     if (e == hipErrorNotSupported)
         return fail(ANTSRL_E_UNSUPPORTED, "a padded observation row stride and the in-loop policy exclude each other (the net reads a dense tile image)");
     if (e != hipSuccess) return hip_fail(e, "perceive");
@@ -853,6 +864,7 @@ extern "C" int antsrl_query(const AntsHandle *h, int what, long long *value)
     case ANTSRL_Q_PERCEIVE_RUN: *value = h->p.meta ? antsrl_perceive_run(h->p) : 0; break;
     case ANTSRL_Q_TIMESTEP: *value = h->host_timestep; break;
     case ANTSRL_Q_DEFERRED_UPDATE: *value = antsrl_update_move_supported(h->p); break;
+    case ANTSRL_Q_PERCEIVE_FAST: *value = h->p.meta && !h->prc_generic && antsrl_perceive_fast(h->p); break;
     default: return fail(ANTSRL_E_INVALID, "bad query selector %d", what);
     }
     return ANTSRL_OK;

@@ -18,6 +18,7 @@
 #include "antsrl_util.h"
 #include "antsrl_flush.h"
 #include "antsrl_update_one.h"
+#include <type_traits>
 
 #define PRC_UNROLL 2 // ants per group (their gathers are issued together, their rows leave together)
 // The gathers of TWO groups are in flight ahead of the group being consumed (same-box A/B of one / two / all four groups
@@ -270,13 +271,14 @@ k_update_move(const KP p, const int out_buf, const double g_dep, const double in
 // ---------------------------------------------------------------------------------------------------
 // LDS: rock table of the workgroup's environment [R][4] doubles, then per wave: frames [run] (written by the workgroup's
 // prologue wave), rockmask [run] (by the wave's own lanes, one ant per lane), staging (two rows back to back + alignment
-// slack).
+// slack).  (k_perceive's FAST form keeps the rock masks in a register: `rock_reg`, no rockmask array.)
 struct PrcOff {
     uint32_t rock, wave0, frame, rm, stage, per_wave, stride;
     size_t total;
 };
 
-__host__ __device__ __forceinline__ PrcOff prc_offsets(int run, int PP, int K, int R, int nwaves, bool no_stage = false, uint32_t pitch = 0)
+__host__ __device__ __forceinline__ PrcOff prc_offsets(int run, int PP, int K, int R, int nwaves, bool no_stage = false, uint32_t pitch = 0,
+                                                       bool rock_reg = false)
 {
     PrcOff o;
     o.rock = 0;
@@ -285,7 +287,7 @@ __host__ __device__ __forceinline__ PrcOff prc_offsets(int run, int PP, int K, i
     o.rm = (uint32_t)(sizeof(AntFrame) * (size_t)run);
     // (no rocks: no rock masks — 128 bytes per workgroup that decide the in-loop policy launch's residency: its tile image
     //  brings a workgroup to 23 488 bytes with them, 23 360 without, and the CU's 160 KB admit SEVEN workgroups up to 23 408)
-    o.stage = (uint32_t)align_up(o.rm + (R > 0 ? 4 * (size_t)run : 0), 16);
+    o.stage = (uint32_t)align_up(o.rm + ((R > 0 && !rock_reg) ? 4 * (size_t)run : 0), 16);
     const size_t rowf = (size_t)PP * K;
     o.stride = (uint32_t)((2 * rowf + 32 + 3) / 4 * 4); // floats: misalignment / carry (< one 128-byte line) + two rows
     if (2 * pitch > o.stride) o.stride = 2 * pitch;     // padded rows (PAD): two rows at the observation's row pitch
@@ -412,7 +414,14 @@ __device__ __forceinline__ void policy_tile(const PolArgs &pol, const uint16_t *
 #define PRC_MIN_WAVES 7
 #endif
 #define PRC_SGPR_ATTR __attribute__((amdgpu_num_sgpr(PRC_SGPR_CAP)))
-template <int LAYOUT, bool OBS16, bool ILV, bool HAS_OBS, bool POLICY = false, bool PAD = false>
+// FAST (the launcher's choice, antsrl_perceive_fast below): power-of-two grid, interleaved records in 2 x 4-cell blocks, a
+// perception mask — the configurations the product is measured on.  The per-ant path then holds no wrap or layout decision:
+// `& (W - 1)` and tiled_slot unconditionally, no flag and no modulo reciprocal live across the loop; the lane permute in
+// front of the gather address and the rock test are decided once per wave (PRC_CHUNKS below), the wave's rock masks live in
+// a register.  FAST = false is the kernel for every other grid and record layout, as it was.  Same bits either way
+// (tests/test_gpu_perceive_fastpath.py); c5 -6.2 %, c2 -3.8 %, c3 -1.4 % per step (profiles/r07/perceive_fastpath_ab.txt,
+// the code in numbers: perceive_fastpath_isa.txt).
+template <int LAYOUT, bool OBS16, bool ILV, bool HAS_OBS, bool POLICY = false, bool PAD = false, bool FAST = false>
 __global__ void __launch_bounds__(PRC_TPB, PRC_MIN_WAVES) PRC_SGPR_ATTR
 k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs, float *__restrict__ agent_state,
            float *__restrict__ reward, const int flags, const uint32_t seq, const int run, const int nseg, const PolArgs pol,
@@ -420,6 +429,7 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
 {
     static_assert(!POLICY || OBS16, "the in-loop policy reads bfloat16 rows");
     static_assert(!PAD || (HAS_OBS && !POLICY), "padded rows: an observation tensor, no in-loop policy image");
+    static_assert(!FAST || ILV, "the fast path reads interleaved records");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int C = 2;
     const int tid = threadIdx.x;
@@ -443,11 +453,12 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
         }
         e = env_of_block(e, p.E, seq); // (odd observations from the other end: antsrl_util.h)
     }
-    const PrcOff lo = prc_offsets(run, PP, K, R, nwaves, POLICY, PAD ? pitch_arg : 0u);
+    const PrcOff lo = prc_offsets(run, PP, K, R, nwaves, POLICY, PAD ? pitch_arg : 0u, FAST);
     double *rock = (double *)(smem + lo.rock);
     unsigned char *wbase = smem + lo.wave0 + (size_t)wave * lo.per_wave;
     AntFrame *frames = (AntFrame *)(wbase + lo.frame);
-    uint32_t *rmask = (uint32_t *)(wbase + lo.rm);
+    uint32_t *rmask = (uint32_t *)(wbase + lo.rm); // (FAST: not there)
+    (void)rmask;
     float *stage = (float *)(wbase + lo.stage);
     // POLICY: [tile rows][row] bf16, contiguous like the rows in memory (+ a zeroed pad the last k-step reads into), then
     // {holding, seed} of the tile's ants
@@ -506,6 +517,7 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     const size_t a_pre = eN + (size_t)min(PRC_ANT(min(lane, max(n_run, 1) - 1)), N - 1);
     const float pre_hold = p.s.holding[a_pre];
     const float pre_seed = (agent_state || POLICY) ? p.s.seed[a_pre] : 0.0f;
+    uint32_t rm_lane = 0u; // lane j: the rocks within reach of the patch of the wave's j-th ant (bit q <-> rock q)
     {
         // the two waves rotate with the workgroup index (wave 0 has the net at the end of a POLICY launch)
         const uint32_t wsel = (blockIdx.x >> 3) + (blockIdx.x >> 8);
@@ -557,7 +569,8 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
         }
         if (!have_frames || R > 0) __syncthreads(); // (the rock table and every wave's frames are complete)
         else wave_lds_sync();                       // (this wave's own frames)
-        // the rocks whose disc can reach the patch (conservative; the exact test runs per cell below)
+        // the rocks whose disc can reach the patch (conservative; the exact test runs per cell below).  FAST: lane j keeps
+        // the mask of the wave's j-th ant in a register — process() takes it by a lane read, not from LDS
         if (lane < n_run) {
             uint32_t rm = 0u;
             if (R > 0) {
@@ -570,9 +583,13 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
                     if (border || dx * dx + dy * dy < rr * rr) rm |= 1u << q;
                 }
             }
-            if (R > 0) rmask[lane] = rm;
+            if constexpr (FAST) rm_lane = rm;
+            else if (R > 0) rmask[lane] = rm;
         }
     }
+    // FAST, wave-uniform: some ant of this wave has a rock in reach (most waves have none: their loop tests nothing per ant)
+    const bool wave_rocks = FAST && LAYOUT == PLAYOUT_DEFAULT_ROCKS && __ballot(rm_lane != 0u) != 0ull;
+    (void)wave_rocks;
     wave_lds_sync();
     if (n_run <= 0) { // (no barrier below: waves run independently from here on — but for the policy's hand-over)
         if constexpr (POLICY) __syncthreads();
@@ -590,9 +607,9 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     const float g_now = (float)p.g_now;                       // scaled mode: v = u * f0^S ...
     const float cut = p.scaled ? (float)p.threshold : 0.0f;   // ... and 0 below the 0.01 cut
     const uint32_t row = (uint32_t)PP * (uint32_t)K;            // elements per ant
-    const bool wrap_fast = W > 4 * (p.r + 4) && H > 4 * (p.r + 4) && p.fwd_delta < W / 4 && p.fwd_delta < H / 4 &&
+    const bool wrap_fast = !FAST && W > 4 * (p.r + 4) && H > 4 * (p.r + 4) && p.fwd_delta < W / 4 && p.fwd_delta < H / 4 &&
                            p.fwd_delta > -W / 4 && p.fwd_delta > -H / 4 && p.delta < 2.0;
-    const bool wrap_pow2 = (W & (W - 1)) == 0 && (H & (H - 1)) == 0;
+    const bool wrap_pow2 = FAST || ((W & (W - 1)) == 0 && (H & (H - 1)) == 0);
 
     // ---- perception: one LANE per perceived cell (49 of 64 lanes at the reference's 7x7): the cell's
     // offsets, mask bit and output slot are per-lane constants, the ant's frame is wave-uniform (LDS
@@ -615,10 +632,10 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     // food / META record index of cell (ix, iy) (frec_xy in antsrl_util.h): blocks of 2 x 4 cells per 128-byte line of the
     // interleaved 16-byte records (KP::tiled: the one gather), blocks of 4 x 4 cells of the 8-byte {food, META} records beside
     // row-major pheromone buffers (KP::ftile: the second gather; the first one, `pc_`, is row-major), else row-major
-    const bool tiled = p.tiled != 0, ftile = p.ftile != 0;
+    const bool tiled = FAST || p.tiled != 0, ftile = !FAST && p.ftile != 0;
 #define PRC_SLOT(ix, iy) (tiled ? tiled_slot((ix), (iy), H) : ftile ? tiled44_slot((ix), (iy), H) : (uint32_t)((ix) * H + (iy)))
 #define PRC_LOAD4(ptr) (*reinterpret_cast<const stream_f4 *>(ptr)) // (cached: as nt loads the gathers lose their L1 hits, +5 %)
-#define PRC_FETCH(G0, GRP)                                                                               \
+#define PRC_FETCH(G0, GRP, PERM)                                                                            \
     {                                                                                                    \
         _Pragma("unroll") for (int u = 0; u < PRC_UNROLL; ++u)                                           \
         {                                                                                                \
@@ -641,12 +658,12 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
         }                                                                                                \
         _Pragma("unroll") for (int u = 0; u < PRC_UNROLL; ++u)                                           \
         {                                                                                                \
-            const uint32_t gc_ = (uint32_t)__shfl((int)GRP.cell[u], src_lane);                       \
+            const uint32_t gc_ = (PERM) ? (uint32_t)__shfl((int)GRP.cell[u], src_lane) : GRP.cell[u]; \
             if (ILV) { /* one {p0, p1, food, META} record per cell: a single 16-byte gather */     \
                 const stream_f4 t = PRC_LOAD4(ph + (size_t)gc_ * 4);                                     \
                 GRP.pv[u][0] = t.x; GRP.pv[u][1] = t.y; GRP.fd[u] = t.z; GRP.mt[u] = __float_as_uint(t.w); \
             } else {                                                                                     \
-                const uint32_t pc_ = (uint32_t)__shfl((int)GRP.pc[u], src_lane);                       \
+                const uint32_t pc_ = (PERM) ? (uint32_t)__shfl((int)GRP.pc[u], src_lane) : GRP.pc[u];  \
                 const float2 t = *reinterpret_cast<const float2 *>(ph + (size_t)pc_ * 2);                \
                 const float2 f = *reinterpret_cast<const float2 *>(fm + (size_t)gc_ * 2);                \
                 GRP.pv[u][0] = t.x; GRP.pv[u][1] = t.y; GRP.fd[u] = f.x; GRP.mt[u] = __float_as_uint(f.y); \
@@ -682,7 +699,10 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
         }
     }
     // ---- what happens to one group once its gathers are back: counts / marks, channel values, LDS staging, copy-out
-    auto process = [&](const PrcGrp &g, const int j0) __attribute__((always_inline)) {
+    // (`rk`: this wave has a rock in reach — a compile-time tag, so that a wave without one carries no rock test at all)
+    auto process = [&](const PrcGrp &g, const int j0, auto rk) __attribute__((always_inline)) {
+        constexpr bool WAVE_ROCKS = decltype(rk)::value;
+        (void)WAVE_ROCKS;
 #pragma unroll
         for (int u = 0; u < PRC_UNROLL; ++u) {
             const int j = min(j0 + u, n_run - 1);
@@ -713,7 +733,10 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
                 const float v_wall = (mt & META_WALL) ? 1.0f : 0.0f;  // :128-129
                 float v_rock = 0.0f;                                  // :132-135
                 if (LAYOUT == PLAYOUT_DEFAULT_ROCKS) {
-                    uint32_t rm = mask_q ? rmask[j] : 0u;
+                    uint32_t rm = 0u;
+                    if constexpr (!FAST) rm = mask_q ? rmask[j] : 0u; // (an LDS read and its wait per ant)
+                    else if constexpr (WAVE_ROCKS) // (j is wave-uniform: one lane read, no LDS round trip in the ant's chain)
+                        rm = mask_q ? (uint32_t)__builtin_amdgcn_readlane((int)rm_lane, j) : 0u;
                     bool any = false;
                     if (rm) { // (rare: a rock within reach of this ant's patch)
                         const AntFrame fr = frames[j];
@@ -818,23 +841,47 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     // consumed the gathers of g + 1 and g + 2 are in flight: the wait for g + 1's gathers — issued before the stores of
     // g - 1 — no longer waits for stores one iteration old but for those of g - 2.  (Groups past the run's end are
     // clamped onto its last ant: harmless re-reads; every chunk starts with no load pending.)
-    for (int c0 = 0; c0 < n_run; c0 += 4 * PRC_UNROLL) {
-        PRC_FETCH(min(c0, n_run - 1), gA)
-        PRC_FETCH(min(c0 + PRC_UNROLL, n_run - 1), gB)
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt / lgkmcnt untouched
-        PRC_FETCH(min(c0 + 2 * PRC_UNROLL, n_run - 1), gC)
-        process(gA, c0);
-        if (c0 + PRC_UNROLL < n_run) {
-            PRC_FETCH(min(c0 + 3 * PRC_UNROLL, n_run - 1), gA)
-            process(gB, c0 + PRC_UNROLL);
-            if (c0 + 2 * PRC_UNROLL < n_run) {
-                process(gC, c0 + 2 * PRC_UNROLL);
-                if (c0 + 3 * PRC_UNROLL < n_run) {
-                    process(gA, c0 + 3 * PRC_UNROLL);
-                }
-            }
-        }
+    // FAST: two decisions are taken ONCE per wave, outside the chunks (a run-time condition inside a chunk would cost the
+    // compiler its count of the operations in flight — see HAS_OBS above): the chunk exists in up to four straight-line copies.
+    // (The generic kernel keeps ONE chunk, permute and LDS mask read included: its in-loop policy forms sit at the 72-VGPR
+    // bound and spill vector registers with more copies — profiles/r07/perceive_fastpath_isa.txt.)
+    //   PERM  some lane borrows another lane's gather address (src_lane != lane).  When every lane owns its gather — any reward
+    //         that counts explored cells, or no mask — the two lane permutes in front of each gather address are the identity:
+    //         an LDS-crossbar round trip in every ant's dependent chain for nothing.
+    //   RK    the wave has a rock in reach of one of its patches (wave_rocks).
+#define PRC_CHUNKS(PERM, RK)                                                                  \
+    for (int c0 = 0; c0 < n_run; c0 += 4 * PRC_UNROLL) {                                      \
+        constexpr std::integral_constant<bool, (RK)> rk_{};                                   \
+        PRC_FETCH(min(c0, n_run - 1), gA, PERM)                                               \
+        PRC_FETCH(min(c0 + PRC_UNROLL, n_run - 1), gB, PERM)                                  \
+        __builtin_amdgcn_s_waitcnt(0x0F70); /* vmcnt(0), expcnt / lgkmcnt untouched */        \
+        PRC_FETCH(min(c0 + 2 * PRC_UNROLL, n_run - 1), gC, PERM)                              \
+        process(gA, c0, rk_);                                                                 \
+        if (c0 + PRC_UNROLL < n_run) {                                                        \
+            PRC_FETCH(min(c0 + 3 * PRC_UNROLL, n_run - 1), gA, PERM)                          \
+            process(gB, c0 + PRC_UNROLL, rk_);                                                \
+            if (c0 + 2 * PRC_UNROLL < n_run) {                                                \
+                process(gC, c0 + 2 * PRC_UNROLL, rk_);                                        \
+                if (c0 + 3 * PRC_UNROLL < n_run) {                                            \
+                    process(gA, c0 + 3 * PRC_UNROLL, rk_);                                    \
+                }                                                                             \
+            }                                                                                 \
+        }                                                                                     \
     }
+#define PRC_CHUNKS_RK(PERM)                                                                   \
+    if (LAYOUT == PLAYOUT_DEFAULT_ROCKS && wave_rocks) PRC_CHUNKS(PERM, true)                 \
+    else PRC_CHUNKS(PERM, false)
+    if constexpr (FAST) {
+        if (need_mask == ~0ull) { // (lanes past the perception are clamped onto its last cell: they own when it does)
+            PRC_CHUNKS_RK(false)
+        } else {
+            PRC_CHUNKS_RK(true)
+        }
+    } else {
+        PRC_CHUNKS(true, false)
+    }
+#undef PRC_CHUNKS_RK
+#undef PRC_CHUNKS
 #undef PRC_FETCH
 
     // ---- agent_state (RL_api.py:160-162), reward.observation hooks, give_reward: lane j <-> the wave's j-th ant
@@ -1000,17 +1047,17 @@ hipError_t antsrl_launch_update_move(const KP &p, int out_buf, double g_dep, dou
     return hipGetLastError();
 }
 
-template <int LAYOUT, bool OBS16, bool ILV, bool HAS_OBS, bool POLICY = false, bool PAD = false>
+template <int LAYOUT, bool OBS16, bool ILV, bool HAS_OBS, bool POLICY = false, bool PAD = false, bool FAST = false>
 static hipError_t launch_perceive_t(const KP &p, const float *cells, float *obs, float *agent_state, float *reward,
                                     int flags, uint32_t seq, hipStream_t st, const PolArgs &pol = PolArgs{}, uint32_t pitch = 0)
 {
     const int run = pick_run(p), nwaves = PRC_TPB / 64;
     if (POLICY && run * nwaves > 32) return hipErrorInvalidValue; // one MFMA tile of 32 ants per workgroup
     const int nseg = (p.N + run * nwaves - 1) / (run * nwaves);
-    const PrcOff lo = prc_offsets(run, p.PP, p.K, p.R, nwaves, POLICY, PAD ? pitch : 0u);
+    const PrcOff lo = prc_offsets(run, p.PP, p.K, p.R, nwaves, POLICY, PAD ? pitch : 0u, FAST);
     const size_t lds = POLICY ? align_up(lo.total, 16) + 2 * (size_t)prc_policy_img_elems(p.PP * p.K) + 4 * 64 : lo.total;
     if (lds > 64 * 1024) return hipErrorInvalidValue; // (never with the shapes antsrl_meta_supported admits)
-    hipLaunchKernelGGL((k_perceive<LAYOUT, OBS16, ILV, HAS_OBS, POLICY, PAD>), dim3((unsigned)((size_t)p.E * nseg)), dim3(PRC_TPB), lds, st, p,
+    hipLaunchKernelGGL((k_perceive<LAYOUT, OBS16, ILV, HAS_OBS, POLICY, PAD, FAST>), dim3((unsigned)((size_t)p.E * nseg)), dim3(PRC_TPB), lds, st, p,
                        cells, obs, agent_state, reward, flags, seq, run, nseg, pol, pitch);
     return hipGetLastError();
 }
@@ -1018,27 +1065,43 @@ static hipError_t launch_perceive_t(const KP &p, const float *cells, float *obs,
 // the in-loop policy needs one tile of at most 32 ants per k_perceive workgroup
 bool antsrl_inloop_policy_supported(const KP &p) { return p.meta && pick_run(p) * (PRC_TPB / 64) <= 32; }
 
+// k_perceive's fast path (its FAST parameter): power-of-two grid, interleaved 16-byte records in 2 x 4-cell blocks
+// (KP::tiled; never together with KP::ftile), the reference's perception mask.  Everything else runs the generic kernel.
+bool antsrl_perceive_fast(const KP &p)
+{
+    return (p.W & (p.W - 1)) == 0 && (p.H & (p.H - 1)) == 0 && p.tiled != 0 && p.ftile == 0 && p.ps == 4 && p.fs == 4 &&
+           p.has_mask != 0;
+}
+
 // obs_pitch: elements between two ants' observation rows (antsrl_set_obs_row_stride), 0 = dense
+// generic: run the generic kernel where the fast path would be taken (antsrl_set_perceive_path: tests compare the two)
 hipError_t antsrl_launch_perceive(const KP &p, int cur, float *obs, float *agent_state, float *reward, int flags,
-                                  uint32_t seq, hipStream_t st, const PolArgs *pol, uint32_t obs_pitch)
+                                  uint32_t seq, hipStream_t st, const PolArgs *pol, uint32_t obs_pitch, bool generic)
 {
     const int layout = prc_layout(p);
     const bool o16 = (flags & ACT_OBS_BF16) != 0, ilv = p.ps == 4 && p.fs == 4;
+    const bool fast = !generic && antsrl_perceive_fast(p);
     const float *cells = p.s.phero[cur];
     const bool with_pol = pol && pol->pack && o16; // (the in-loop policy reads bf16 rows: antsrl_set_inloop_policy)
     const bool padded = obs && obs_pitch != 0 && obs_pitch != (uint32_t)(p.PP * p.K);
     if (padded && with_pol) return hipErrorNotSupported; // (the tile image the net reads is dense)
 #define PRC_GO(LY)                                                                                             \
     {                                                                                                          \
-        if (padded && o16) return launch_perceive_t<LY, true, ILVV, true, false, true>(p, cells, obs, agent_state, reward, flags, seq, st, PolArgs{}, obs_pitch); \
-        if (padded) return launch_perceive_t<LY, false, ILVV, true, false, true>(p, cells, obs, agent_state, reward, flags, seq, st, PolArgs{}, obs_pitch); \
-        if (with_pol && !obs) return launch_perceive_t<LY, true, ILVV, false, true>(p, cells, obs, agent_state, reward, flags, seq, st, *pol); \
-        if (!obs) return launch_perceive_t<LY, false, ILVV, false>(p, cells, obs, agent_state, reward, flags, seq, st); \
-        if (with_pol) return launch_perceive_t<LY, true, ILVV, true, true>(p, cells, obs, agent_state, reward, flags, seq, st, *pol); \
-        if (o16) return launch_perceive_t<LY, true, ILVV, true>(p, cells, obs, agent_state, reward, flags, seq, st);    \
-        return launch_perceive_t<LY, false, ILVV, true>(p, cells, obs, agent_state, reward, flags, seq, st);            \
+        if (padded && o16) return launch_perceive_t<LY, true, ILVV, true, false, true, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st, PolArgs{}, obs_pitch); \
+        if (padded) return launch_perceive_t<LY, false, ILVV, true, false, true, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st, PolArgs{}, obs_pitch); \
+        if (with_pol && !obs) return launch_perceive_t<LY, true, ILVV, false, true, false, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st, *pol); \
+        if (!obs) return launch_perceive_t<LY, false, ILVV, false, false, false, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st); \
+        if (with_pol) return launch_perceive_t<LY, true, ILVV, true, true, false, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st, *pol); \
+        if (o16) return launch_perceive_t<LY, true, ILVV, true, false, false, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st);    \
+        return launch_perceive_t<LY, false, ILVV, true, false, false, FASTV>(p, cells, obs, agent_state, reward, flags, seq, st);            \
     }
-#define PRC_GO2(LY) { if (ilv) { constexpr bool ILVV = true; PRC_GO(LY) } else { constexpr bool ILVV = false; PRC_GO(LY) } }
+    // (FAST is instantiated for interleaved records only: it cannot hold otherwise)
+#define PRC_GO2(LY)                                                                           \
+    {                                                                                         \
+        if (ilv && fast) { constexpr bool ILVV = true, FASTV = true; PRC_GO(LY) }             \
+        else if (ilv) { constexpr bool ILVV = true, FASTV = false; PRC_GO(LY) }               \
+        else { constexpr bool ILVV = false, FASTV = false; PRC_GO(LY) }                       \
+    }
     if (layout == PLAYOUT_DEFAULT) PRC_GO2(PLAYOUT_DEFAULT)
     if (layout == PLAYOUT_DEFAULT_ROCKS) PRC_GO2(PLAYOUT_DEFAULT_ROCKS)
 #undef PRC_GO2

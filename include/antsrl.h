@@ -395,6 +395,8 @@ enum {
     ANTSRL_Q_TIMESTEP = 5,         /* Environment.timestep (environment.py:27,45) as the host mirrors it: every env of a
                                       handle steps in lockstep, so no device read is needed                */
     ANTSRL_Q_DEFERRED_UPDATE = 6,  /* 1: antsrl_update(NULL jitter) is deferred into the next step (k_update_move) */
+    ANTSRL_Q_PERCEIVE_FAST = 7,    /* 1: k_perceive runs its fast path (power-of-two grid, interleaved records in 2 x 4-cell
+                                      blocks, a perception mask) and antsrl_set_perceive_path has not pinned the generic one */
     ANTSRL_Q_COUNT_
 };
 int antsrl_query(const AntsHandle *h, int what, long long *value);
@@ -447,6 +449,14 @@ int antsrl_set_obs_format(AntsHandle *h, int format);
  * buf.view(E, N, stride)[..., :P*P*K].view(E, N, P, P, K).  0 (or P*P*K) = dense.  Cell-meta path only
  * (ANTSRL_Q_CELL_META); not together with antsrl_set_inloop_policy; antsrl_set_obs_format resets it. */
 int antsrl_set_obs_row_stride(AntsHandle *h, int32_t stride_elems);
+
+/* Which k_perceive the handle launches (no reference counterpart; for tests and A/B runs).  The kernel has a fast path that
+ * the library selects by itself where the configuration allows it (ANTSRL_Q_PERCEIVE_FAST) and a generic one for every
+ * other grid and record layout; both compute the same bits.  ANTSRL_PERCEIVE_GENERIC pins the generic kernel,
+ * ANTSRL_PERCEIVE_AUTO (the default) gives the choice back. */
+#define ANTSRL_PERCEIVE_AUTO 0
+#define ANTSRL_PERCEIVE_GENERIC 1
+int antsrl_set_perceive_path(AntsHandle *h, int path);
 
 /* Ants.activate_all_pheromones (environment/ants.py:86-87).  act: float [E][N][C].
  * new_deposit_strength > 0 also changes AntsCfg.deposit_strength (the dtype switch
