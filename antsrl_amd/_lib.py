@@ -16,7 +16,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_workspace_map",
            "antsrl_destroy", "antsrl_reset", "antsrl_generate", "antsrl_step", "antsrl_observe", "antsrl_update", "antsrl_flush",
            "antsrl_step_update", "antsrl_set_timing_events", "antsrl_set_activation", "antsrl_policy_mlp", "antsrl_read_state", "antsrl_state_bytes",
-           "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_set_perceive_path", "antsrl_mem_alloc", "antsrl_mem_free",
+           "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_set_perceive_path", "antsrl_refresh_explored_summary", "antsrl_mem_alloc", "antsrl_mem_free",
            "antsrl_mem_trim", "antsrl_mem_stats", "antsrl_update_phase",
            "antsrl_perceptive_field", "antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory",
            "antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
@@ -109,6 +109,7 @@ def load() -> C.CDLL:
     lib.antsrl_bench_copy.argtypes = [vp, vp, C.c_size_t, vp]
     lib.antsrl_set_obs_row_stride.argtypes = [vp, i32]
     lib.antsrl_set_perceive_path.argtypes = [vp, i32]
+    lib.antsrl_refresh_explored_summary.argtypes = [vp, vp]
     lib.antsrl_mem_alloc.argtypes = [C.c_size_t, i32, C.POINTER(vp)]
     lib.antsrl_mem_free.argtypes = [vp]
     lib.antsrl_mem_trim.argtypes = []

@@ -591,8 +591,14 @@ class BatchedAntsEnv:
 
     def set_perceive_path(self, path: int) -> None:
         """antsrl_set_perceive_path: config.PERCEIVE_GENERIC pins k_perceive's generic kernel, config.PERCEIVE_AUTO gives the
-        choice back to the library (config.Q_PERCEIVE_FAST tells which one runs)."""
+        choice back to the library (config.Q_PERCEIVE_FAST tells which one runs), config.PERCEIVE_FAST_NOSKIP runs the fast
+        kernel without the explored summary (config.Q_EXPLORED_SUMMARY)."""
         _lib.check(self.lib.antsrl_set_perceive_path(self._h, int(path)), "set_perceive_path")
+
+    def refresh_explored_summary(self) -> None:
+        """antsrl_refresh_explored_summary: enqueue a refresh of the explored summary now (nothing where the handle keeps none)."""
+        with self._on_device():
+            _lib.check(self.lib.antsrl_refresh_explored_summary(self._h, self._stream()), "refresh_explored_summary")
 
     def set_activation(self, act, new_deposit_strength: float = 0.0) -> None:
         """Ants.activate_all_pheromones (ants.py:86-87)."""

@@ -31,8 +31,8 @@ REWARD_NONE, REWARD_EXPLORATION, REWARD_FOOD, REWARD_ALL = range(4)
 PHERO_AUTO, PHERO_EXPLICIT_SWEEP = 0, 1
 ACT_AUTO, ACT_CELL_META, ACT_SINGLE_KERNEL = 0, 1, 2
 TIMING_EVENTS = 5  # antsrl_set_timing_events
-Q_CELL_META, Q_SCALED_UNITS, Q_INTERLEAVED, Q_FILTER_SEPARABLE, Q_PERCEIVE_RUN, Q_TIMESTEP, Q_DEFERRED_UPDATE, Q_PERCEIVE_FAST = range(8)  # antsrl_query
-PERCEIVE_AUTO, PERCEIVE_GENERIC = 0, 1  # antsrl_set_perceive_path
+Q_CELL_META, Q_SCALED_UNITS, Q_INTERLEAVED, Q_FILTER_SEPARABLE, Q_PERCEIVE_RUN, Q_TIMESTEP, Q_DEFERRED_UPDATE, Q_PERCEIVE_FAST, Q_EXPLORED_SUMMARY = range(9)  # antsrl_query
+PERCEIVE_AUTO, PERCEIVE_GENERIC, PERCEIVE_FAST_NOSKIP = 0, 1, 2  # antsrl_set_perceive_path
 
 (S_ANTS_XYT, S_PREV_XY, S_HOLDING, S_MANDIBLES, S_ACTIVATION, S_PHERO, S_FOOD, S_EXPLORED,
  S_ANTHILL_FOOD, S_ROCK_CENTERS, S_TIMESTEP, S_REWARD_STATE, S_WALLS, S_ANTHILL_AREA,

@@ -45,6 +45,8 @@ bool antsrl_inloop_policy_supported(const KP &p);
 hipError_t antsrl_launch_policy_pack(unsigned char *pack, const float *w1, const float *b1, const float *w2, const float *b2,
                                      const float *w3, const float *b3, int F, hipStream_t st);
 hipError_t antsrl_launch_meta_rebase(const KP &p, hipStream_t st);
+bool antsrl_explored_summary_supported(const KP &p, bool with_policy);
+hipError_t antsrl_launch_explored_summary(const KP &p, hipStream_t st);
 bool antsrl_update_move_supported(const KP &p);
 hipError_t antsrl_launch_update_move(const KP &p, int out_buf, double g_dep, double inv_g_dep, const int8_t *rot,
                                      const int8_t *ph, uint8_t *done, uint32_t seq, hipStream_t st, bool with_frames);
@@ -68,6 +70,10 @@ struct AntsHandle {
     bool obs_bf16;         // observation buffers are bfloat16 (antsrl_set_obs_format)
     uint32_t obs_pitch;    // elements between two ants' observation rows (antsrl_set_obs_row_stride), 0 = dense
     bool prc_generic;      // k_perceive's generic kernel is pinned (antsrl_set_perceive_path)
+    bool prc_noskip;       // the fast kernel ignores the explored summary, none is kept (ANTSRL_PERCEIVE_FAST_NOSKIP)
+    uint32_t sum_obs;      // observations since the last reset: the explored summary's refresh cadence (summary_cadence)
+    bool sum_due;          // a refresh of the summary is due behind the observation just enqueued (summary_refresh_due)
+    bool sum_live;         // a refresh has been enqueued since the last reset: k_perceive consumes the summary (ACT_SUMMARY)
     bool need_wall_clear;  // scaled mode: initial grid may hold pheromone on wall cells
     hipEvent_t ev[ANTSRL_TIMING_EVENTS]; // measurement hook (antsrl_set_timing_events)
     bool ev_armed;
@@ -391,7 +397,7 @@ static int create_handle(const AntsCfg *cfg, void *state_ws, void *record_ws, bo
     h->pol = PolArgs{};
     h->sweeps = 0; h->need_wall_clear = false;
     h->has_gen = false; h->episode_seed = 0; h->host_timestep = 1; h->obs_bf16 = false; h->obs_pitch = 0;
-    h->prc_generic = false;
+    h->prc_generic = false; h->prc_noskip = false; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
     h->ws_bytes[0] = need[0]; h->ws_bytes[1] = need[1];
     h->ev_armed = false;
     h->obs_seq = 0;
@@ -456,7 +462,7 @@ extern "C" int antsrl_reset(AntsHandle *h, const AntsInit *init, void *stream)
     h->p.deposit_strength = h->cfg.deposit_strength;
     h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = true; h->episode_over = false;
     h->sweeps = 0; h->need_wall_clear = h->p.scaled && init->phero != nullptr;
-    h->host_timestep = 1; h->obs_seq = 0;
+    h->host_timestep = 1; h->obs_seq = 0; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
     set_decay(h);
     return ANTSRL_OK;
 }
@@ -483,7 +489,7 @@ static int do_generate(AntsHandle *h, uint64_t seed, hipStream_t st)
     if (e != hipSuccess) return hip_fail(e, "generate");
     h->p.deposit_strength = h->cfg.deposit_strength;
     h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = true; h->episode_over = false;
-    h->sweeps = 0; h->need_wall_clear = false; h->host_timestep = 1; h->obs_seq = 0;
+    h->sweeps = 0; h->need_wall_clear = false; h->host_timestep = 1; h->obs_seq = 0; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
     h->episode_seed = seed;
     set_decay(h);
     return ANTSRL_OK;
@@ -563,9 +569,33 @@ extern "C" int antsrl_set_obs_row_stride(AntsHandle *h, int32_t stride_elems)
 extern "C" int antsrl_set_perceive_path(AntsHandle *h, int path)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (path != ANTSRL_PERCEIVE_AUTO && path != ANTSRL_PERCEIVE_GENERIC) return fail(ANTSRL_E_INVALID, "bad perceive path %d", path);
+    if (path != ANTSRL_PERCEIVE_AUTO && path != ANTSRL_PERCEIVE_GENERIC && path != ANTSRL_PERCEIVE_FAST_NOSKIP)
+        return fail(ANTSRL_E_INVALID, "bad perceive path %d", path);
     h->prc_generic = path == ANTSRL_PERCEIVE_GENERIC;
+    h->prc_noskip = path == ANTSRL_PERCEIVE_FAST_NOSKIP;
     return ANTSRL_OK;
+}
+
+// The explored summary (antsrl_explored.h) is kept and consumed by this handle as it is set up now.  (Bits set while it
+// was stay true whatever the path is switched to in between: they are only ever cleared by a reset.)
+static bool summary_on(const AntsHandle *h)
+{
+    return !h->prc_generic && !h->prc_noskip && antsrl_explored_summary_supported(h->p, h->pol.pack != nullptr && h->obs_bf16);
+}
+// The refresh cadence, in observations since the last reset: behind observation 256, 512 and 1024, then behind every
+// 1024th.  Until an episode's first refresh k_perceive is not told of the summary at all (sum_live): no bit can be set, the
+// launch is spared the summary's loads.  (From 128 on, the first 400 steps of a c3 episode still ran 0.5 % slower than the
+// parent's, the parent's spread being 0.4 %: early in an episode the ants stand close together, their patches share lines
+// anyway, and the skip buys less than its prologue costs.)  One refresh reads the tiles still open — a line each, whole where the sample is explored: 0.09 ms at c3 behind
+// observation 63, 0.06 ms behind 399 — and early in an episode the frontier's tiles are read again at every one.  Behind every
+// 64th observation from 64 on the first 400 steps of a c3 episode ran 1.9 % SLOWER than the parent's; exploration slows
+// down as it completes (0.87 of the map at age 200, 0.97 at 300, 0.999 at 600), so the intervals may double
+// (profiles/r08/ROUND_NOTES.md).
+#define SUMMARY_FIRST 256u
+#define SUMMARY_STEADY 1024u
+static bool summary_cadence(uint32_t n)
+{
+    return n >= SUMMARY_FIRST && (n <= SUMMARY_STEADY ? (n & (n - 1u)) == 0u : n % SUMMARY_STEADY == 0u);
 }
 
 // Enqueues a deferred update on its own (k_update_one), e.g. ahead of a state read.
@@ -622,11 +652,26 @@ static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, floa
     if (timed) (void)hipEventRecord(h->ev[2], st);
     e = antsrl_launch_perceive(h->p, h->cur, obs, agent_state, reward,
                                (stepping ? ACT_STEP : 0) | (obs ? ACT_HAS_OBS : 0) | (frames ? ACT_FRAMES : 0) |
-                                   ((obs || h->pol.pack) && h->obs_bf16 ? ACT_OBS_BF16 : 0), // (act-only: rows in LDS, bf16)
+                                   ((obs || h->pol.pack) && h->obs_bf16 ? ACT_OBS_BF16 : 0) | // (act-only: rows in LDS, bf16)
+                                   (h->sum_live && summary_on(h) ? ACT_SUMMARY : 0),
                                h->obs_seq, st, &h->pol, h->obs_pitch, h->prc_generic);
     if (e == hipErrorNotSupported)
         return fail(ANTSRL_E_UNSUPPORTED, "a padded observation row stride and the in-loop policy exclude each other (the net reads a dense tile image)");
     if (e != hipSuccess) return hip_fail(e, "perceive");
+    if (summary_cadence(++h->sum_obs) && summary_on(h)) h->sum_due = true; // (enqueued by the caller: summary_refresh_due)
+    return ANTSRL_OK;
+}
+
+// The summary's refresh when the cadence asks for one: BEHIND the observation whose marks it may count (bits are set
+// between observations only), and — in antsrl_step_update — behind the timing event that closes k_perceive's bracket: its
+// time is the step's, not the k_update_move bracket's or the k_perceive bracket's.
+static int summary_refresh_due(AntsHandle *h, hipStream_t st)
+{
+    if (!h->sum_due) return ANTSRL_OK;
+    h->sum_due = false;
+    h->sum_live = true;
+    hipError_t e = antsrl_launch_explored_summary(h->p, st);
+    if (e != hipSuccess) return hip_fail(e, "explored summary");
     return ANTSRL_OK;
 }
 
@@ -706,7 +751,8 @@ extern "C" int antsrl_step(AntsHandle *h, const int8_t *rotation, const int8_t *
     if (!h->is_reset) return not_reset(h);
     if (h->phase_next) return mid_update(h);
     if (!agent_state || !reward || !done) return fail(ANTSRL_E_INVALID, "agent_state, reward, done are required");
-    return do_step(h, rotation, phero, obs, agent_state, reward, done, (hipStream_t)stream);
+    int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, (hipStream_t)stream);
+    return rc ? rc : summary_refresh_due(h, (hipStream_t)stream);
 }
 
 extern "C" int antsrl_observe(AntsHandle *h, float *obs, float *agent_state, float *reward, void *stream)
@@ -714,8 +760,10 @@ extern "C" int antsrl_observe(AntsHandle *h, float *obs, float *agent_state, flo
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
     if (!h->is_reset) return not_reset(h);
     if (h->phase_next) return mid_update(h);
-    if (h->p.meta)
-        return meta_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false);
+    if (h->p.meta) {
+        int rc = meta_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false);
+        return rc ? rc : summary_refresh_due(h, (hipStream_t)stream);
+    }
     if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
     hipError_t e = antsrl_launch_act(h->p, nullptr, nullptr, h->cur, obs, agent_state, reward, nullptr,
                                      obs ? ACT_HAS_OBS | (h->obs_bf16 ? ACT_OBS_BF16 : 0) : 0, (hipStream_t)stream);
@@ -798,6 +846,20 @@ extern "C" int antsrl_update_phase(AntsHandle *h, int phase, const double *wall_
     return ANTSRL_OK;
 }
 
+extern "C" int antsrl_refresh_explored_summary(AntsHandle *h, void *stream)
+{
+    if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
+    if (!h->is_reset) return not_reset(h);
+    if (h->phase_next) return mid_update(h);
+    if (!summary_on(h)) return ANTSRL_OK;
+    int frc = flush_pending(h, (hipStream_t)stream); // (as antsrl_read_state: behind a deferred update)
+    if (frc) return frc;
+    h->sum_live = true;
+    hipError_t e = antsrl_launch_explored_summary(h->p, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "explored summary");
+    return ANTSRL_OK;
+}
+
 extern "C" int antsrl_flush(AntsHandle *h, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
@@ -829,6 +891,8 @@ extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const i
     int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, st, timed);
     if (rc) return rc;
     if (timed) (void)hipEventRecord(h->ev[3], st);
+    rc = summary_refresh_due(h, st);
+    if (rc) return rc;
     if (sweep_late) {
         hipError_t e = antsrl_launch_sweep(h->p, h->cur, st);
         if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
@@ -865,6 +929,7 @@ extern "C" int antsrl_query(const AntsHandle *h, int what, long long *value)
     case ANTSRL_Q_TIMESTEP: *value = h->host_timestep; break;
     case ANTSRL_Q_DEFERRED_UPDATE: *value = antsrl_update_move_supported(h->p); break;
     case ANTSRL_Q_PERCEIVE_FAST: *value = h->p.meta && !h->prc_generic && antsrl_perceive_fast(h->p); break;
+    case ANTSRL_Q_EXPLORED_SUMMARY: *value = summary_on(h); break;
     default: return fail(ANTSRL_E_INVALID, "bad query selector %d", what);
     }
     return ANTSRL_OK;

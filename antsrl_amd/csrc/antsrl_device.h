@@ -167,4 +167,5 @@ struct KP {
 #define ACT_STEP 1        // run RLApi.step's action phases before observing
 #define ACT_HAS_OBS 2     // obs pointer valid
 #define ACT_OBS_BF16 8     // `obs` is a bfloat16 tensor (antsrl_set_obs_format): same values, rounded to nearest even
+#define ACT_SUMMARY 32     // k_perceive's fast path: DState::explored_bits holds the explored summary (antsrl_explored.h) — consume it
 #define ACT_FRAMES 16      // k_perceive: DState::frames holds this observation's frames (written by the k_update_move in front of it)

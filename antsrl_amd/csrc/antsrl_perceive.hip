@@ -18,6 +18,7 @@
 #include "antsrl_util.h"
 #include "antsrl_flush.h"
 #include "antsrl_update_one.h"
+#include "antsrl_explored.h"
 #include <type_traits>
 
 #define PRC_UNROLL 2 // ants per group (their gathers are issued together, their rows leave together)
@@ -430,6 +431,14 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     static_assert(!POLICY || OBS16, "the in-loop policy reads bfloat16 rows");
     static_assert(!PAD || (HAS_OBS && !POLICY), "padded rows: an observation tensor, no in-loop policy image");
     static_assert(!FAST || ILV, "the fast path reads interleaved records");
+    // SKIP: this instantiation consumes the explored summary (ACT_SUMMARY) — the FAST ones with the rock channel and without
+    // the in-loop policy, i.e. c3's.  The summary's words are one more memory round trip between the prologue's barrier and
+    // a wave's first gather.  c3's launch is nine residency rounds of a kernel bound by its memory side and does not see it
+    // (the lines saved take 2.25 % off the step); c2's launch (no rocks) is ONE round, every wave's latency is the kernel's:
+    // +2.4 % per step with the skip compiled in.  The in-loop policy's launches are latency-bound in the same way, and the
+    // one without rocks, at the 72-VGPR bound already, spills two vector registers with the select.  Those instantiations
+    // are the parent's code, instruction for instruction (profiles/r08/ROUND_NOTES.md, isa_counts.txt).
+    constexpr bool SKIP = FAST && LAYOUT == PLAYOUT_DEFAULT_ROCKS && !POLICY;
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int C = 2;
     const int tid = threadIdx.x;
@@ -518,6 +527,7 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     const float pre_hold = p.s.holding[a_pre];
     const float pre_seed = (agent_state || POLICY) ? p.s.seed[a_pre] : 0.0f;
     uint32_t rm_lane = 0u; // lane j: the rocks within reach of the patch of the wave's j-th ant (bit q <-> rock q)
+    bool skip_lane = false; // lane j: the patch of the wave's j-th ant lies in fully explored tiles (FAST with ACT_SUMMARY)
     {
         // the two waves rotate with the workgroup index (wave 0 has the net at the end of a POLICY launch)
         const uint32_t wsel = (blockIdx.x >> 3) + (blockIdx.x >> 8);
@@ -583,10 +593,22 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
                     if (border || dx * dx + dy * dy < rr * rr) rm |= 1u << q;
                 }
             }
-            if constexpr (FAST) rm_lane = rm;
-            else if (R > 0) rmask[lane] = rm;
+            if constexpr (FAST) {
+                rm_lane = rm;
+                // the explored summary (antsrl_explored.h): every tile this ant's patch can touch has its bit — none of its
+                // cells can be unexplored, the records of its masked cells are not needed.  Up to three words of the
+                // environment's one L2-resident summary line, once per ant, in front of the loop: ONE memory round trip
+                // (the small-box form issues every load in front of every use).
+                if (SKIP && (flags & ACT_SUMMARY)) { // (launch-uniform)
+                    const uint32_t *sum = p.s.explored_bits + (size_t)e * p.words;
+                    const ExplBox bx = explored_box(frames[lane].cx, frames[lane].cy, explored_box_margin(p.r, p.delta), W, H);
+                    skip_lane = explored_box_small(bx) ? explored_box_full_small(sum, bx, W, H) : explored_box_full(sum, bx, W, H);
+                }
+            } else if (R > 0) rmask[lane] = rm;
         }
     }
+    // FAST, wave-uniform: bit j <-> the wave's j-th ant skips the gathers of its masked cells (0 without ACT_SUMMARY)
+    const unsigned long long skip_ants = SKIP ? __ballot(skip_lane) : 0ull;
     // FAST, wave-uniform: some ant of this wave has a rock in reach (most waves have none: their loop tests nothing per ant)
     const bool wave_rocks = FAST && LAYOUT == PLAYOUT_DEFAULT_ROCKS && __ballot(rm_lane != 0u) != 0ull;
     (void)wave_rocks;
@@ -628,6 +650,11 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
     const bool own = mask_q || explore;
     const unsigned long long need_mask = __ballot(own);
     const int src_lane = own ? lane : (need_mask ? __builtin_ctzll(need_mask) : 0);
+    // FAST: the lane whose record index the masked lanes of a skipping ant borrow (skip_ants) — a needed lane of the same
+    // ant, the centre cell with the reference's mask: its line is fetched anyway
+    const unsigned long long unmasked = __ballot(mask_q);
+    const int donor = __builtin_amdgcn_readfirstlane(unmasked ? __builtin_ctzll(unmasked) : 0);
+    (void)donor;
 
     // food / META record index of cell (ix, iy) (frec_xy in antsrl_util.h): blocks of 2 x 4 cells per 128-byte line of the
     // interleaved 16-byte records (KP::tiled: the one gather), blocks of 4 x 4 cells of the 8-byte {food, META} records beside
@@ -658,7 +685,12 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
         }                                                                                                \
         _Pragma("unroll") for (int u = 0; u < PRC_UNROLL; ++u)                                           \
         {                                                                                                \
-            const uint32_t gc_ = (PERM) ? (uint32_t)__shfl((int)GRP.cell[u], src_lane) : GRP.cell[u]; \
+            uint32_t gc_ = (PERM) ? (uint32_t)__shfl((int)GRP.cell[u], src_lane) : GRP.cell[u];       \
+            if (SKIP && !(PERM)) { /* a skipping ant: a lane read into a scalar and a select, no branch */ \
+                const int j_ = min((G0) + u, n_run - 1);                                                 \
+                const uint32_t dc_ = (uint32_t)__builtin_amdgcn_readlane((int)GRP.cell[u], donor);       \
+                gc_ = (((skip_ants >> j_) & 1ull) && !mask_q) ? dc_ : gc_;                               \
+            }                                                                                            \
             if (ILV) { /* one {p0, p1, food, META} record per cell: a single 16-byte gather */     \
                 const stream_f4 t = PRC_LOAD4(ph + (size_t)gc_ * 4);                                     \
                 GRP.pv[u][0] = t.x; GRP.pv[u][1] = t.y; GRP.fd[u] = t.z; GRP.mt[u] = __float_as_uint(t.w); \
@@ -709,7 +741,9 @@ k_perceive(const KP p, const float *__restrict__ cells, float *__restrict__ obs,
             const bool real = (j0 + u < n_run) && lane < PP; // clamped duplicates must not count twice
             const uint32_t mt = g.mt[u];
             // reward_custom.py:19,22 (mask ignored): unexplored before THIS observation <=> stamp >= seq
-            const bool unexp = real && explore && (mt >> META_STAMP_SHIFT) >= seq;
+            // (a skipping lane holds a borrowed record: it counts nothing and marks nothing, whatever that record says)
+            const bool skipping = SKIP && !mask_q && ((skip_ants >> j) & 1ull) != 0ull;
+            const bool unexp = real && explore && !skipping && (mt >> META_STAMP_SHIFT) >= seq;
             const uint32_t n_un = (uint32_t)__popcll(__ballot(unexp));
             cntv = (lane == j0 + u) ? n_un : cntv; // (a clamped duplicate lands on a lane past the run: never read)
             // mark: the stamp half-word of the META word := seq.  A plain 2-byte store, no atomic: every writer of
@@ -950,6 +984,60 @@ __global__ void k_meta_rebase(const KP p)
     }
 }
 
+// The explored summary's refresh (antsrl_explored.h): one wave per summary word = 32 tiles of one environment.  Tiles whose
+// bit is set are not read, so the cost falls with the unexplored remainder.  Of the others the wave first reads ONE cell
+// each (one line per tile, one instruction for all 32): a tile whose sample has never been explored — nearly every open
+// tile early in an episode — is dropped there, at an eighth of its bytes.  The rest are read whole, 64 META words = 8
+// lines per tile, four tiles in flight, and get their bit if none carries META_NEVER.  The word belongs to this wave alone
+// and no observation runs beside the kernel (stream order): a plain store.
+// The stamp re-base above keeps explored cells explored (stamp 0, below the restarted counter) and never-explored ones
+// META_NEVER: every set bit stays true across it, the summary needs no re-base of its own.
+__global__ void __launch_bounds__(256) k_explored_summary(const KP p)
+{
+    const int lane = threadIdx.x & 63;
+    const int th = p.H >> EXPL_TILE_SHIFT, th_sh = __builtin_ctz((unsigned)th);
+    const uint32_t nt = explored_tile_count(p.W, p.H), nw = (nt + 31u) >> 5;
+    const size_t gw = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    if (gw >= (size_t)p.E * nw) return; // (wave-uniform)
+    const uint32_t e = (uint32_t)(gw / nw), w = (uint32_t)(gw % nw);
+    uint32_t *sum = p.s.explored_bits + (size_t)e * p.words + w;
+    const uint32_t have = *sum;
+    const uint32_t left = nt - 32u * w, valid = left >= 32u ? ~0u : (1u << left) - 1u;
+    uint32_t todo = valid & ~have;
+    if (!todo) return;
+    const uint32_t *meta = reinterpret_cast<const uint32_t *>(p.s.food) + (size_t)e * p.W * p.H * p.fs + 1;
+    const size_t FS = (size_t)p.fs;
+    { // the sample: lane b reads cell (3, 3) of tile 32 w + b
+        uint32_t m = META_NEVER << META_STAMP_SHIFT;
+        if (lane < 32 && ((todo >> lane) & 1u)) {
+            const uint32_t t = 32u * w + (uint32_t)lane;
+            const int x = (int)(t >> th_sh) * 8 + 3, y = (int)(t & (uint32_t)(th - 1)) * 8 + 3;
+            m = meta[(size_t)frec_xy(p, x, y) * FS];
+        }
+        todo &= (uint32_t)__ballot((m >> META_STAMP_SHIFT) != META_NEVER);
+    }
+    uint32_t add = 0u;
+    while (todo) { // (wave-uniform)
+        uint32_t b[4], m[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { // the next four open tiles (the last one repeated when fewer are left)
+            b[k] = (uint32_t)__builtin_ctz(todo);
+            const uint32_t rest = todo & (todo - 1u);
+            todo = (rest || k == 3) ? rest : todo;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { // lane <-> cell (lane / 8, lane % 8) of the tile
+            const uint32_t t = 32u * w + b[k];
+            const int x = (int)(t >> th_sh) * 8 + (lane >> 3), y = (int)(t & (uint32_t)(th - 1)) * 8 + (lane & 7);
+            m[k] = meta[(size_t)frec_xy(p, x, y) * FS];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (__ballot((m[k] >> META_STAMP_SHIFT) == META_NEVER) == 0ull) add |= 1u << b[k];
+    }
+    if (add && lane == 0) *sum = have | add;
+}
+
 // ===================================================================================
 // host-side launchers (called from antsrl_capi.hip)
 // ===================================================================================
@@ -1107,6 +1195,25 @@ hipError_t antsrl_launch_perceive(const KP &p, int cur, float *obs, float *agent
 #undef PRC_GO2
 #undef PRC_GO
     return hipErrorInvalidValue;
+}
+
+// Where the explored summary is kept and consumed: the fast kernel with the rock channel and no in-loop policy (k_perceive's
+// SKIP), a reward that counts explored cells (without one the masked lanes borrow an address already), a mask that masks
+// something, a grid with tiles.
+bool antsrl_explored_summary_supported(const KP &p, bool with_policy)
+{
+    if (with_policy || prc_layout(p) != PLAYOUT_DEFAULT_ROCKS) return false; // (k_perceive's SKIP: the instantiations that consume it)
+    if (!p.meta || !antsrl_perceive_fast(p) || !p.explore_on || !explored_tiles_ok(p.W, p.H)) return false;
+    for (int q = 0; q < p.PP; ++q)
+        if (!p.mask[q]) return true;
+    return false;
+}
+
+hipError_t antsrl_launch_explored_summary(const KP &p, hipStream_t st)
+{
+    const size_t waves = (size_t)p.E * ((explored_tile_count(p.W, p.H) + 31u) >> 5);
+    hipLaunchKernelGGL(k_explored_summary, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, p);
+    return hipGetLastError();
 }
 
 hipError_t antsrl_launch_meta_rebase(const KP &p, hipStream_t st)

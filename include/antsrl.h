@@ -397,6 +397,10 @@ enum {
     ANTSRL_Q_DEFERRED_UPDATE = 6,  /* 1: antsrl_update(NULL jitter) is deferred into the next step (k_update_move) */
     ANTSRL_Q_PERCEIVE_FAST = 7,    /* 1: k_perceive runs its fast path (power-of-two grid, interleaved records in 2 x 4-cell
                                       blocks, a perception mask) and antsrl_set_perceive_path has not pinned the generic one */
+    ANTSRL_Q_EXPLORED_SUMMARY = 8, /* 1: the handle, as it is set up now, keeps the explored summary and its k_perceive consumes
+                                      it (see antsrl_set_perceive_path): the fast path with the rock channel perceived and no
+                                      in-loop policy, a mask with masked cells, a reward that counts explored cells, a grid
+                                      of at least 8 x 8 cells                                                    */
     ANTSRL_Q_COUNT_
 };
 int antsrl_query(const AntsHandle *h, int what, long long *value);
@@ -453,10 +457,26 @@ int antsrl_set_obs_row_stride(AntsHandle *h, int32_t stride_elems);
 /* Which k_perceive the handle launches (no reference counterpart; for tests and A/B runs).  The kernel has a fast path that
  * the library selects by itself where the configuration allows it (ANTSRL_Q_PERCEIVE_FAST) and a generic one for every
  * other grid and record layout; both compute the same bits.  ANTSRL_PERCEIVE_GENERIC pins the generic kernel,
- * ANTSRL_PERCEIVE_AUTO (the default) gives the choice back. */
+ * ANTSRL_PERCEIVE_AUTO (the default) gives the choice back.
+ * THE EXPLORED SUMMARY.  Where a reward counts explored cells, the records of the MASKED cells of a patch are gathered for
+ * that count alone.  The fast path therefore keeps — where the rock channel is perceived and no in-loop policy is set: the
+ * configurations in which it was measured to pay; everywhere else nothing is kept and nothing changes — one bit per tile of 8 x 8 cells, "every cell of this tile has been
+ * explored", in the handle's workspace (the "explored_bits" array of antsrl_workspace_map, which nothing else uses on the
+ * cell-meta path; bit (x / 8) * (H / 8) + y / 8, 32 bits per word) and skips those gathers for every ant whose patch lies
+ * in tiles that have their bit: same results, fewer lines fetched.  The bits are cleared by antsrl_reset / antsrl_generate
+ * (an auto-reset included) and set by a refresh the library enqueues behind the 256th, 512th and every 1024th observation
+ * since; the kernel consults them from an episode's first refresh on (the library's own or antsrl_refresh_explored_summary).
+ * ANTSRL_PERCEIVE_FAST_NOSKIP runs the fast kernel with the summary ignored and no refresh enqueued (A/B runs, tests);
+ * ANTSRL_Q_EXPLORED_SUMMARY tells whether a handle keeps and consumes it. */
 #define ANTSRL_PERCEIVE_AUTO 0
 #define ANTSRL_PERCEIVE_GENERIC 1
+#define ANTSRL_PERCEIVE_FAST_NOSKIP 2
 int antsrl_set_perceive_path(AntsHandle *h, int path);
+
+/* Enqueues a refresh of the explored summary now (antsrl_set_perceive_path), behind a pending deferred update as
+ * antsrl_read_state does: every tile whose cells are all explored at that point gets its bit.  Returns ANTSRL_OK and does
+ * nothing where the handle keeps no summary (ANTSRL_Q_EXPLORED_SUMMARY == 0). */
+int antsrl_refresh_explored_summary(AntsHandle *h, void *stream);
 
 /* Ants.activate_all_pheromones (environment/ants.py:86-87).  act: float [E][N][C].
  * new_deposit_strength > 0 also changes AntsCfg.deposit_strength (the dtype switch
