@@ -88,6 +88,20 @@ class _DeviceAgent:
         self._action_step = 0
         return env
 
+    def _action_buffers(self) -> None:
+        """`_rot` / `_ph`: the step's actions of every ant, for an agent whose get_action returns views of its own."""
+        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+
+    def _select_actions(self, step: int, n_ph: int) -> None:
+        """antsrl_agent_select_actions on `_rot` / `_ph`: the colonies that explore at (seed, step) take uniform actions,
+        a pheromone among n_ph."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
+                                                             self.n_ants_per_env, float(self.epsilon), self.rotations,
+                                                             n_ph, _p(self._rot), _p(self._ph), _p(self._explored),
+                                                             _lib.stream(self.device)), "agent_select_actions")
+
     # ---- the reference's surface ----------------------------------------------------------------------------------
     def initialize(self, api_or_env) -> None:
         """Every pheromone activation x 10."""
@@ -263,10 +277,9 @@ class _InLoopAgent(_DeviceAgent):
 
     def _setup(self, api_or_env, agent_states_space):
         env = super()._setup(api_or_env, agent_states_space)
-        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        # (without a pheromone head only antsrl_agent_select_actions writes here, the pheromone it draws for every
-        # exploring ant, and nothing reads it)
-        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        # (without a pheromone head only antsrl_agent_select_actions writes _ph, the pheromone it draws for every exploring
+        # ant, and nothing reads it)
+        self._action_buffers()
         self._env = None            # the environment the in-loop policy is attached to
         self._handle_version = -1   # trainer.version of the weights in its handle
         self._next_version = -1     # ... of the weights its next_rotation / next_pheromone were produced under
@@ -316,11 +329,7 @@ class _InLoopAgent(_DeviceAgent):
         if ph is not None:
             self._ph.copy_(ph.reshape(-1))
         if training:
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
-                                                                 self.n_ants_per_env, float(self.epsilon), self.rotations,
-                                                                 3, _p(self._rot), _p(self._ph), _p(self._explored),
-                                                                 _lib.stream(self.device)), "agent_select_actions")
+            self._select_actions(step, 3)
         self._action_step = step
         self.step_counter += 1
         return self._rot.view(lead), (None if ph is None else self._ph.view(lead))
@@ -462,8 +471,7 @@ class ReworkAgent(_DeviceAgent):
         self.trainer = ReworkTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
                                      update_target_every=self.update_target_every, n_rot=self.rotations,
                                      n_ph=self.pheromones, seed=self.seed)
-        self._rot = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
-        self._ph = torch.zeros((self.n_ants,), dtype=torch.int8, device=self.device)
+        self._action_buffers()
         if trained_model is not None:
             self.load_model(trained_model)
 
@@ -483,12 +491,7 @@ class ReworkAgent(_DeviceAgent):
         else:
             self.policy.act(obs, ast, env=env, out=out)
             if training and self.epsilon > 0:
-                with torch.cuda.device(self.device):
-                    _lib.check(self._lib.antsrl_agent_select_actions(self.seed, step, self.env_id_base, self.n_envs,
-                                                                     self.n_ants_per_env, float(self.epsilon), self.rotations,
-                                                                     self.pheromones, _p(self._rot), _p(self._ph),
-                                                                     _p(self._explored), _lib.stream(self.device)),
-                               "agent_select_actions")
+                self._select_actions(step, self.pheromones)
         self._action_step = step
         self.step_counter += 1
         return self._rot.view(lead), self._ph.view(lead)

@@ -1,7 +1,8 @@
 // antsrl_adam.h — torch.optim.Adam's single-tensor step in fp32, for the memory agent's apply stage (antsrl_memtrain.hip),
-// the linear agent's training step (antsrl_lintrain.hip) and the explore agent's (antsrl_exptrain.hip): the host side
-// (antsrl_adam_args: the checks of an entry's Adam arguments and the scalars), one element on the device (adam_element,
-// adam_at) and the flat kernel behind antsrl_lintrain_apply / antsrl_exptrain_apply (antsrl_launch_adam).  The host
+// the linear agent's training step (antsrl_lintrain.hip), the explore agent's (antsrl_exptrain.hip) and the rework
+// agent's (antsrl_reworktrain.hip): the host side (antsrl_adam_args: the checks of an entry's Adam arguments and the
+// scalars; antsrl_adam_apply: antsrl_lintrain_apply / antsrl_exptrain_apply / antsrl_reworktrain_apply behind the net's
+// own check), one element on the device (adam_element, adam_at) and the flat kernel (antsrl_launch_adam).  The host
 // computes step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) in double and rounds every scalar to
 // float once (w1m = 1 - beta1, w2m = 1 - beta2), as the op does.
 #pragma once
@@ -40,6 +41,20 @@ static inline int antsrl_adam_args(const char *who, int64_t step, double lr, dou
 
 // Adam on params[0 .. P) from grads (o.m, o.v and the scalars are read): one flat kernel, antsrl_lintrain.hip holds it
 ANTSRL_INTERNAL hipError_t antsrl_launch_adam(float *params, const AdamArgs &o, const float *grads, int P, hipStream_t st);
+
+// the rest of an _apply entry over a flat block of P floats, behind the entry's check of `params`
+static inline int antsrl_adam_apply(const char *who, float *params, float *adam_m, float *adam_v, const float *grads,
+                                    int64_t step, double lr, double beta1, double beta2, double eps, int P, void *stream)
+{
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    REQUIRE(grads, 4);
+    AdamArgs o = {};
+    const int rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o);
+    if (rc != ANTSRL_OK) return rc;
+    o.m = adam_m; o.v = adam_v;
+    return enqueued(antsrl_launch_adam(params, o, grads, P, (hipStream_t)stream), who);
+}
 
 // returns the new parameter; mm and vv are Adam's moments of the element, updated in place
 __device__ __forceinline__ float adam_element(float p, const float g, float &mm, float &vv, const float step_size,

@@ -1,8 +1,8 @@
 // antsrl_dqn_dev.h — the device code the linear agent's training step (antsrl_lintrain.hip) and the explore agent's
 // (antsrl_exptrain.hip) share, once: the acting kernel's layer-1 sequence (k_policy_flat, antsrl_policy.hip) as the
-// training forward restates it, the clamp that keeps idx inside the ring, the 3-output head and the tail of the
-// epilogues.  Every helper is force-inlined and the build has -ffp-contract=off: a caller computes the bits it computed
-// with the helper's body written out.
+// training forward restates it, the 3-output head and the tail of the epilogues (the clamp that keeps idx inside the
+// ring, dqn_row, is antsrl_dqn.h's: the rework agent's step takes it too).  Every helper is force-inlined and the build
+// has -ffp-contract=off: a caller computes the bits it computed with the helper's body written out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "antsrl_adam.h"
@@ -17,13 +17,6 @@ __device__ __forceinline__ void dqn_wave_sync()
     // LDS hand-off inside one wave: its LDS instructions execute in order, only the compiler must not reorder
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-}
-
-// the replay row of minibatch row b (b < B), never outside the replay arrays
-__device__ __forceinline__ long long dqn_row(const DqnBatch &q, const int b)
-{
-    const long long ri = q.idx ? q.idx[b] : (long long)b;
-    return ri < 0 ? 0 : (ri >= q.n_rows ? q.n_rows - 1 : ri);
 }
 
 // the observation columns of a W1 [32][F + 2] as the bf16 A operand w1s [32][KP] (zero for k >= F), by wave wib of nw

@@ -1,9 +1,10 @@
 // antsrl_linapi.hip — the linear agent's training step in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The linear
 // agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels, and
 // behind them the explore agent's ("The explore agent's training step"): antsrl_exptrain_sizes / _grad / _apply / _step
-// in front of antsrl_exptrain.hip's, with the same argument rules.  dqn_batch checks and fills what both steps take from
-// the replay arrays (DqnBatch, antsrl_dqn.h), antsrl_adam_args (antsrl_adam.h) Adam's part; an entry checks its own
-// net's pointers, its limit on B and its workspace rule.
+// in front of antsrl_exptrain.hip's, with the same argument rules.  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
+// what every step takes from the replay arrays, the rework agent's (antsrl_reworkapi.hip) included; dqn_batch adds what
+// the 32-wide nets keep in DqnBatch, antsrl_adam_args (antsrl_adam.h) Adam's part; an entry checks its own net's
+// pointers, its limit on B and its workspace rule.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -39,45 +40,22 @@ static int et_B(const char *who, int64_t B)
     return ANTSRL_OK;
 }
 
-#define LT_REQUIRE(p, align)                                                                                             \
-    do {                                                                                                                 \
-        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                                          \
-        if ((uintptr_t)(p) & ((align) - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
-    } while (0)
-
-// the minibatch of a gradient stage or a fused step, for n_features and B its entry has checked; workspace (checked by
-// the entry's own rule) becomes the partials
+// the minibatch of a gradient stage or a fused step, for n_features and B its entry has checked: antsrl_dqn_minibatch's
+// part, then what the 32-wide nets add; workspace (checked by the entry's own rule) becomes the partials
 static int dqn_batch(const char *who, int32_t n_features, const float *states, const float *agent_states,
                      const int64_t *actions, const float *rewards, const float *new_states, const float *new_agent_states,
                      const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads,
                      bool grads_required, float *loss, void *workspace, DqnBatch *q)
 {
-    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
-    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
-    LT_REQUIRE(states, 4);
-    LT_REQUIRE(agent_states, 4);
-    LT_REQUIRE(actions, 8);
-    LT_REQUIRE(rewards, 4);
-    LT_REQUIRE(new_states, 4);
-    LT_REQUIRE(new_agent_states, 4);
-    LT_REQUIRE(dones, 1);
-    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
-    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
-    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
-    LT_REQUIRE(loss, 4);
-    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
-    q->states = states; q->agent_states = agent_states; q->rewards = rewards; q->new_states = new_states;
-    q->new_agent_states = new_agent_states; q->actions = actions; q->idx = idx; q->dones = dones;
-    q->grads = grads; q->loss = loss; q->partials = (float *)workspace;
-    q->n_rows = n_rows;
-    q->B = (int)B; q->F = n_features; q->ksteps = (n_features + 15) / 16; q->ntiles = ((int)B + 31) / 32;
-    q->discount = discount;
+    const int rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones,
+                                        n_rows, idx, B, discount, grads, grads_required, loss, q);
+    if (rc != ANTSRL_OK) return rc;
+    q->partials = (float *)workspace;
+    q->F = n_features; q->ksteps = (n_features + 15) / 16; q->ntiles = ((int)B + 31) / 32;
     q->dq_scale = (float)(2.0 / (3.0 * (double)B));
     q->loss_scale = (float)(1.0 / (3.0 * (double)B));
     return ANTSRL_OK;
 }
-
-static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
 
 // ---- the linear agent's training step (antsrl_lintrain.hip) ---------------------------------------------------------------
 
@@ -102,11 +80,11 @@ static int lt_net(const char *who, int32_t n_features, int64_t B, const float *w
     int rc = lt_features(who, n_features);
     if (rc == ANTSRL_OK) rc = lt_B(who, B);
     if (rc != ANTSRL_OK) return rc;
-    LT_REQUIRE(w1, 4);
-    LT_REQUIRE(b1, 4);
-    LT_REQUIRE(heads, 4);
-    LT_REQUIRE(target_l3, 4);
-    if (antsrl_lintrain_blocks((int)B, n_features) > 1) LT_REQUIRE(workspace, 256);
+    REQUIRE(w1, 4);
+    REQUIRE(b1, 4);
+    REQUIRE(heads, 4);
+    REQUIRE(target_l3, 4);
+    if (antsrl_lintrain_blocks((int)B, n_features) > 1) REQUIRE(workspace, 256);
     a->w1 = w1; a->b1 = b1; a->heads = heads; a->target_l3 = target_l3;
     return ANTSRL_OK;
 }
@@ -131,15 +109,8 @@ extern "C" int antsrl_lintrain_apply(float *heads, float *adam_m, float *adam_v,
                                      double beta1, double beta2, double eps, void *stream)
 {
     const char *who = "lintrain_apply";
-    LT_REQUIRE(heads, 4);
-    LT_REQUIRE(adam_m, 4);
-    LT_REQUIRE(adam_v, 4);
-    LT_REQUIRE(grads, 4);
-    AdamArgs o = {};
-    const int rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o);
-    if (rc != ANTSRL_OK) return rc;
-    o.m = adam_m; o.v = adam_v;
-    return enqueued(antsrl_launch_adam(heads, o, grads, LT_HEADS, (hipStream_t)stream), who);
+    REQUIRE(heads, 4);
+    return antsrl_adam_apply(who, heads, adam_m, adam_v, grads, step, lr, beta1, beta2, eps, LT_HEADS, stream);
 }
 
 extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const float *b1, float *heads,
@@ -157,8 +128,8 @@ extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const f
         rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
                        idx, B, discount, grads, false, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
-    LT_REQUIRE(adam_m, 4);
-    LT_REQUIRE(adam_v, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
     if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
     a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_lintrain(a, (hipStream_t)stream), who);
@@ -186,9 +157,9 @@ static int et_net(const char *who, int32_t n_features, int64_t B, float *model, 
     int rc = lt_features(who, n_features);
     if (rc == ANTSRL_OK) rc = et_B(who, B);
     if (rc != ANTSRL_OK) return rc;
-    LT_REQUIRE(model, 4);
-    LT_REQUIRE(target, 4);
-    LT_REQUIRE(workspace, 256);
+    REQUIRE(model, 4);
+    REQUIRE(target, 4);
+    REQUIRE(workspace, 256);
     a->model = model; a->target = target;
     a->dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
     a->blocks = antsrl_exptrain_blocks((int)B);
@@ -215,16 +186,11 @@ extern "C" int antsrl_exptrain_apply(int32_t n_features, float *model, float *ad
                                      int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
 {
     const char *who = "exptrain_apply";
-    int rc = lt_features(who, n_features);
+    const int rc = lt_features(who, n_features);
     if (rc != ANTSRL_OK) return rc;
-    LT_REQUIRE(model, 4);
-    LT_REQUIRE(adam_m, 4);
-    LT_REQUIRE(adam_v, 4);
-    LT_REQUIRE(grads, 4);
-    AdamArgs o = {};
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o)) != ANTSRL_OK) return rc;
-    o.m = adam_m; o.v = adam_v;
-    return enqueued(antsrl_launch_adam(model, o, grads, (int)antsrl_exptrain_floats(n_features), (hipStream_t)stream), who);
+    REQUIRE(model, 4);
+    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps,
+                             (int)antsrl_exptrain_floats(n_features), stream);
 }
 
 extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
@@ -241,8 +207,8 @@ extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const floa
         rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
                        idx, B, discount, grads, false, loss, workspace, &a.batch);
     if (rc != ANTSRL_OK) return rc;
-    LT_REQUIRE(adam_m, 4);
-    LT_REQUIRE(adam_v, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
     if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
     a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who);

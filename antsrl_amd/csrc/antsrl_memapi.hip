@@ -29,8 +29,6 @@ static int check_D(const char *who, int32_t n_features, int32_t agent_dim, int32
     return ANTSRL_OK;
 }
 
-static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
-
 // the 26 tensors of CollectModelMemory.state_dict(): none NULL
 static int check_params(const char *who, const float *const *params)
 {
@@ -343,12 +341,6 @@ static int check_width(const char *who, const char *name, int32_t v)
 }
 
 #define MISALIGNED(p, n) (((uintptr_t)(p) & ((n) - 1)) != 0)
-
-#define REQUIRE(p, align)                                                                                    \
-    do {                                                                                                     \
-        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                              \
-        if (MISALIGNED(p, align)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
-    } while (0)
 
 extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
                                    double epsilon, int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation,

@@ -137,8 +137,6 @@ hipError_t antsrl_launch_monitor_end_episode(double *state, const MonitorLayout 
 
 // ---- the C-ABI ---------------------------------------------------------------------------------------------------------
 
-static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
-
 static int monitor_check(const char *who, int32_t n_envs, int32_t n_ants, int32_t max_reports, int32_t max_episodes,
                          MonitorLayout *L)
 {

@@ -2,7 +2,7 @@
 // net"): antsrl_rework_collapsed_bytes, antsrl_rework_collapse and antsrl_policy_rework in front of antsrl_rework.hip's
 // kernels (antsrl_policy_rework_select: the forward pass and the epsilon-greedy select in one), and behind them its training step ("The rework agent's training step"): antsrl_reworktrain_sizes / _grad /
 // _apply / _step in front of antsrl_reworktrain.hip's four, with the argument rules of the linear and explore agents'
-// (antsrl_linapi.hip).
+// (antsrl_linapi.hip): the minibatch's are antsrl_dqn_minibatch's (antsrl_dqn.h) for all three.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -10,12 +10,11 @@
 #include <stdint.h>
 
 #include "antsrl_device.h"
+#include "antsrl_dqn.h" // antsrl_dqn_minibatch
 #include "antsrl_fail.h"
 #include "antsrl_memagent.h" // antsrl_check_batch
 #include "antsrl_rework.h"
 #include "antsrl_reworktrain.h"
-
-static int enqueued(hipError_t e, const char *who) { return e != hipSuccess ? hip_fail(e, who) : ANTSRL_OK; }
 
 static int rework_check(const AntsReworkShape *s, ReworkDims *d, const char *who)
 {
@@ -65,13 +64,12 @@ extern "C" int antsrl_rework_collapse(const AntsReworkShape *s, const float *con
     return enqueued(antsrl_launch_rework_collapse(P, d, (float *)collapsed, (hipStream_t)stream), who);
 }
 
-extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
-                                    const float *agent_state, int64_t n_ants, int8_t *rotation, int8_t *pheromone,
-                                    float *q_out, void *stream)
+// the shape and the operands of a forward pass, with or without the select behind it
+static int rework_act_check(const char *who, const AntsReworkShape *s, ReworkDims *d, const void *collapsed, const void *obs,
+                            int obs_format, const float *agent_state, const int8_t *rotation, const int8_t *pheromone,
+                            const float *q_out)
 {
-    const char *who = "policy_rework";
-    ReworkDims d;
-    const int rc = rework_check(s, &d, who);
+    const int rc = rework_check(s, d, who);
     if (rc != ANTSRL_OK) return rc;
     if (!collapsed || !obs || !agent_state || !rotation || !pheromone)
         return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state, rotation, pheromone are required", who);
@@ -79,6 +77,17 @@ extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collap
         return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state and q_out must be 4-byte aligned", who);
     if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
         return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
+                                    const float *agent_state, int64_t n_ants, int8_t *rotation, int8_t *pheromone,
+                                    float *q_out, void *stream)
+{
+    const char *who = "policy_rework";
+    ReworkDims d;
+    const int rc = rework_act_check(who, s, &d, collapsed, obs, obs_format, agent_state, rotation, pheromone, q_out);
+    if (rc != ANTSRL_OK) return rc;
     if (n_ants < 0 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [0, 2^31)", who);
     if (n_ants == 0) return ANTSRL_OK; // nothing to do, nothing launched
     return enqueued(antsrl_launch_rework_act((const float *)collapsed, d, obs, obs_format == ANTSRL_OBS_BF16, agent_state,
@@ -93,14 +102,8 @@ extern "C" int antsrl_policy_rework_select(const AntsReworkShape *s, const void 
 {
     const char *who = "policy_rework_select";
     ReworkDims d;
-    int rc = rework_check(s, &d, who);
+    int rc = rework_act_check(who, s, &d, collapsed, obs, obs_format, agent_state, rotation, pheromone, q_out);
     if (rc != ANTSRL_OK) return rc;
-    if (!collapsed || !obs || !agent_state || !rotation || !pheromone)
-        return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state, rotation, pheromone are required", who);
-    if (((uintptr_t)collapsed | (uintptr_t)obs | (uintptr_t)agent_state | (uintptr_t)q_out) & 3)
-        return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state and q_out must be 4-byte aligned", who);
-    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
     if ((rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants)) != ANTSRL_OK) return rc;
     if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
     ReworkSelect sel = {};
@@ -112,12 +115,6 @@ extern "C" int antsrl_policy_rework_select(const AntsReworkShape *s, const void 
 }
 
 // ---- the training step (antsrl_reworktrain.hip) ----------------------------------------------------------------------------
-
-#define RT_REQUIRE(p, align)                                                                                             \
-    do {                                                                                                                 \
-        if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                                          \
-        if ((uintptr_t)(p) & ((align) - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
-    } while (0)
 
 static int rt_B(const char *who, int64_t B)
 {
@@ -142,7 +139,7 @@ extern "C" int antsrl_reworktrain_sizes(const AntsReworkShape *s, int64_t B, siz
     return ANTSRL_OK;
 }
 
-// the shape, the nets, the minibatch and the workspace of the gradient stage and the fused step
+// the shape, the nets, the workspace and (antsrl_dqn_minibatch) the minibatch of the gradient stage and the fused step
 static int rt_args(const char *who, const AntsReworkShape *s, float *model, const float *target_collapsed,
                    const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
                    const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
@@ -152,30 +149,14 @@ static int rt_args(const char *who, const AntsReworkShape *s, float *model, cons
     int rc = rework_check(s, &a->d, who);
     if (rc == ANTSRL_OK) rc = rt_B(who, B);
     if (rc != ANTSRL_OK) return rc;
-    RT_REQUIRE(model, 4);
-    RT_REQUIRE(target_collapsed, 4);
-    RT_REQUIRE(workspace, 256);
-    if (n_rows < 1 || n_rows > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: n_rows must be in [1, 2^40] (%lld)", who, (long long)n_rows);
-    if (!idx && B > n_rows) return fail(ANTSRL_E_INVALID, "%s: without idx, B = %lld rows need n_rows >= B (%lld)", who, (long long)B, (long long)n_rows);
-    RT_REQUIRE(states, 4);
-    RT_REQUIRE(agent_states, 4);
-    RT_REQUIRE(actions, 8);
-    RT_REQUIRE(rewards, 4);
-    RT_REQUIRE(new_states, 4);
-    RT_REQUIRE(new_agent_states, 4);
-    RT_REQUIRE(dones, 1);
-    if ((uintptr_t)idx & 7) return fail(ANTSRL_E_INVALID, "%s: idx must be 8-byte aligned", who);
-    if (grads_required && !grads) return fail(ANTSRL_E_INVALID, "%s: grads is required", who);
-    if ((uintptr_t)grads & 3) return fail(ANTSRL_E_INVALID, "%s: grads must be 4-byte aligned", who);
-    RT_REQUIRE(loss, 4);
-    if (!(discount == discount)) return fail(ANTSRL_E_INVALID, "%s: discount is NaN", who);
+    REQUIRE(model, 4);
+    REQUIRE(target_collapsed, 4);
+    REQUIRE(workspace, 256);
+    if ((rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                                   idx, B, discount, grads, grads_required, loss, a)) != ANTSRL_OK)
+        return rc;
     antsrl_reworktrain_layout(a->d, (int)B, &a->L);
-    a->states = states; a->agent_states = agent_states; a->rewards = rewards; a->new_states = new_states;
-    a->new_agent_states = new_agent_states; a->actions = actions; a->idx = idx; a->dones = dones;
-    a->grads = grads; a->loss = loss; a->work = (unsigned char *)workspace;
-    a->n_rows = n_rows;
-    a->B = (int)B;
-    a->discount = discount;
+    a->work = (unsigned char *)workspace;
     a->dq_rot = (float)(2.0 / ((double)a->d.n_rot * (double)B));
     a->dq_ph = (float)(2.0 / ((double)a->d.n_ph * (double)B));
     a->loss_rot = (float)(1.0 / ((double)a->d.n_rot * (double)B));
@@ -204,18 +185,12 @@ extern "C" int antsrl_reworktrain_apply(const AntsReworkShape *s, float *model, 
 {
     const char *who = "reworktrain_apply";
     ReworkDims d;
-    int rc = rework_check(s, &d, who);
+    const int rc = rework_check(s, &d, who);
     if (rc != ANTSRL_OK) return rc;
-    RT_REQUIRE(model, 4);
-    RT_REQUIRE(adam_m, 4);
-    RT_REQUIRE(adam_v, 4);
-    RT_REQUIRE(grads, 4);
-    AdamArgs o = {};
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &o)) != ANTSRL_OK) return rc;
-    o.m = adam_m; o.v = adam_v;
+    REQUIRE(model, 4);
     ReworkTrainLayout L;
     antsrl_reworktrain_layout(d, 1, &L);
-    return enqueued(antsrl_launch_adam(model, o, grads, (int)L.off[2 * RW_LAYERS], (hipStream_t)stream), who);
+    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps, (int)L.off[2 * RW_LAYERS], stream);
 }
 
 extern "C" int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, const float *target_collapsed, float *adam_m,
@@ -230,8 +205,8 @@ extern "C" int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, c
     int rc = rt_args(who, s, model, target_collapsed, states, agent_states, actions, rewards, new_states, new_agent_states,
                      dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
     if (rc != ANTSRL_OK) return rc;
-    RT_REQUIRE(adam_m, 4);
-    RT_REQUIRE(adam_v, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
     if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
     a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_reworktrain(a, (hipStream_t)stream), who);

@@ -3,12 +3,14 @@
 // activation, so the loss's gradient has rank NQ = n_rot + n_ph in every weight (include/antsrl.h, "The rework agent's
 // training step").  A net is ONE flat fp32 block: the 20 tensors of the state_dict in its order, dense.
 //
-// The minibatch has its own struct beside DqnBatch (antsrl_dqn.h): that one's ksteps, ntiles and the fixed 3 in dq_scale
-// are the 32-wide nets'; the argument rules are the same.
+// The minibatch's fields lie in ReworkTrainArgs under DqnBatch's names (antsrl_dqn.h), so antsrl_dqn_minibatch checks
+// and fills them and dqn_row clamps idx for this step as for the 32-wide nets'; that struct's ksteps, ntiles and the fixed
+// 3 in dq_scale are theirs alone.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "antsrl_adam.h"
+#include "antsrl_dqn.h"
 #include "antsrl_fail.h"
 #include "antsrl_rework.h"
 

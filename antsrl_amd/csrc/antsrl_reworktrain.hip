@@ -165,8 +165,7 @@ __global__ void __launch_bounds__(RT_TPB) k_reworktrain_batch(const ReworkTrainA
             const int b = pass * RT_ROWS + r;
             const bool valid = b < B;
             const int bb = valid ? b : B - 1;
-            long long ri = a.idx ? a.idx[bb] : (long long)bb;
-            ri = ri < 0 ? 0 : (ri >= a.n_rows ? a.n_rows - 1 : ri);
+            const long long ri = dqn_row(a, bb);
             const float *__restrict__ xs = a.states + (size_t)ri * F, *__restrict__ xn = a.new_states + (size_t)ri * F;
             const float as0 = a.agent_states[(size_t)ri * 2], as1 = a.agent_states[(size_t)ri * 2 + 1];
             const float an0 = a.new_agent_states[(size_t)ri * 2], an1 = a.new_agent_states[(size_t)ri * 2 + 1];

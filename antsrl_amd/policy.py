@@ -23,22 +23,44 @@ from . import _lib
 from ._lib import ptr as _p
 
 
+def linear_init(shapes: dict, seed: int) -> dict:
+    """nn.Linear's default initialisation (kaiming_uniform(a=sqrt(5)) == U(-1/sqrt(in), 1/sqrt(in)), the bias from the
+    same interval) of the layers name -> (out, in), as a state_dict on the CPU: one generator seeded once, the layers in
+    the dict's order, a layer's weight drawn before its bias."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    sd = {}
+    for name, (out_f, in_f) in shapes.items():
+        b = 1.0 / math.sqrt(in_f)
+        sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
+        sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
+    return sd
+
+
+def check_rows(n_features: int, obs: torch.Tensor, agent_state: torch.Tensor, env) -> tuple:
+    """What every act path checks of its rows: obs [..., P, P, K] (float32, or bfloat16 as `env` produced it) and
+    agent_state float32 [..., 2], dense -> (the leading shape, the rows)."""
+    lead = obs.shape[:-3]
+    m = math.prod(lead)
+    assert obs.is_contiguous() and agent_state.is_contiguous()
+    assert obs.dtype in (torch.float32, torch.bfloat16) and agent_state.dtype == torch.float32
+    if env is not None:
+        assert env.obs.dtype == obs.dtype, "obs and env.obs differ in dtype"
+    assert obs.numel() == m * n_features and agent_state.numel() == m * 2
+    return lead, m
+
+
 class LinearPolicy:
     def __init__(self, n_features: int, device, with_pheromone_head: bool = True, seed: int = 0):
-        g = torch.Generator(device="cpu")
-        g.manual_seed(seed)
-
-        def linear(out_f, in_f):  # nn.Linear's default init (kaiming_uniform(a=sqrt(5)) == U(-1/sqrt(in), 1/sqrt(in)))
-            b = 1.0 / math.sqrt(in_f)
-            w = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
-            bias = (torch.rand((out_f,), generator=g) * 2 - 1) * b
-            return w.to(device).contiguous(), bias.to(device).contiguous()
-
+        shapes = dict(layer1=(32, n_features + 2), layer2=(3, 32))
+        if with_pheromone_head:
+            shapes["layer3"] = (3, 32)
+        sd = {k: v.to(device).contiguous() for k, v in linear_init(shapes, seed).items()}
         self.n_features = n_features
         self.device = torch.device(device)
-        self.w1, self.b1 = linear(32, n_features + 2)
-        self.w2, self.b2 = linear(3, 32)
-        self.w3, self.b3 = linear(3, 32) if with_pheromone_head else (None, None)
+        self.w1, self.b1 = sd["layer1.weight"], sd["layer1.bias"]
+        self.w2, self.b2 = sd["layer2.weight"], sd["layer2.bias"]
+        self.w3, self.b3 = sd.get("layer3.weight"), sd.get("layer3.bias")
         self._lib = _lib.load()
         self._rot = self._ph = None
 
@@ -59,17 +81,9 @@ class LinearPolicy:
         """obs [..., P, P, K] (float32, or bfloat16 from a BatchedAntsEnv(obs_dtype=torch.bfloat16) passed as
         `env`) and agent_state float32 [..., 2] on the GPU -> (rotation int8 [...], pheromone int8 [...] or
         None), ready to pass to step()."""
-        lead = obs.shape[:-3]
-        m = 1
-        for d in lead:
-            m *= d
-        assert obs.is_contiguous() and agent_state.is_contiguous()
-        if obs.dtype == torch.bfloat16:
-            assert env is not None and env.obs.dtype == torch.bfloat16, "bfloat16 observations: pass the env that produced them"
-        else:
-            assert obs.dtype == torch.float32 and (env is None or env.obs.dtype == torch.float32)
-        handle = env._h if (env is not None and obs.dtype == torch.bfloat16) else None
-        assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
+        lead, m = check_rows(self.n_features, obs, agent_state, env)
+        assert obs.dtype != torch.bfloat16 or env is not None, "bfloat16 observations: pass the env that produced them"
+        handle = env._h if obs.dtype == torch.bfloat16 else None
         if self._rot is None or self._rot.numel() != m:
             self._rot = torch.empty((m,), dtype=torch.int8, device=self.device)
             self._ph = torch.empty((m,), dtype=torch.int8, device=self.device) if self.w3 is not None else None
@@ -155,15 +169,9 @@ class MemoryPolicy:
                  seed: int = 0, precision: str = "bf16"):
         assert precision in MEMNET_PRECISIONS, "precision must be one of %s, not %r" % (tuple(MEMNET_PRECISIONS), precision)
         self.precision = precision
-        g = torch.Generator(device="cpu")
-        g.manual_seed(seed)
         self.n_features = n_features
         self.device = torch.device(device)
-        sd = {}
-        for name, (out_f, in_f) in memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph).items():
-            b = 1.0 / math.sqrt(in_f)  # nn.Linear's default init
-            sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
-            sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
+        sd = linear_init(memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph), seed)
         self._lib = _lib.load()
         self.memory = None
         self._rot = self._ph = None
@@ -230,15 +238,7 @@ class MemoryPolicy:
         other ants' rotation, pheromone, memory and q are NOT written (the returned action tensors are reused buffers:
         the caller owns every element it did not list).  In place, the listed tiles must be distinct."""
         assert self.packed is not None, "MemoryPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
-        lead = obs.shape[:-3]
-        m = 1
-        for d in lead:
-            m *= d
-        assert obs.is_contiguous() and agent_state.is_contiguous()
-        assert obs.dtype in (torch.float32, torch.bfloat16) and agent_state.dtype == torch.float32
-        if env is not None:
-            assert env.obs.dtype == obs.dtype, "obs and env.obs differ in dtype"
-        assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
+        lead, m = check_rows(self.n_features, obs, agent_state, env)
         if memory is None:
             if self.memory is None or self.memory.shape[0] != m:
                 assert self.memory is None, "self.memory holds %d ants, not %d: reset_memory(n_ants)" % (self.memory.shape[0], m)
@@ -314,8 +314,6 @@ class ReworkPolicy:
         """params: the 20 tensors (fp32, contiguous, on `device`, the reference's names) to ADOPT as they are instead of
         initialising: the policy reads them where they lie (ReworkTrainer's target block) and `recollapse()` follows
         their changes."""
-        g = torch.Generator(device="cpu")
-        g.manual_seed(seed)
         self.n_features = n_features
         self.device = torch.device(device)
         self._lib = _lib.load()
@@ -326,12 +324,7 @@ class ReworkPolicy:
             self._set(params)
             assert all(self.params[k] is params[k] for k in self.params), "adopted tensors are not copied"
             return
-        sd = {}
-        for name, (out_f, in_f) in rework_param_shapes(n_features, n_rot, n_ph).items():
-            b = 1.0 / math.sqrt(in_f)  # nn.Linear's default init
-            sd[name + ".weight"] = (torch.rand((out_f, in_f), generator=g) * 2 - 1) * b
-            sd[name + ".bias"] = (torch.rand((out_f,), generator=g) * 2 - 1) * b
-        self._set(sd)
+        self._set(linear_init(rework_param_shapes(n_features, n_rot, n_ph), seed))
 
     def _set(self, sd):
         shp = rework_shape_from_state_dict(sd)
@@ -378,15 +371,7 @@ class ReworkPolicy:
         """The checks act and act_select share -> (lead shape, rows, obs_format, rotation, pheromone): `out` = (rot, ph),
         int8 tensors of one element per row that receive the actions, else the policy's own reused buffers."""
         assert self.collapsed is not None, "ReworkPolicy on %s holds weights only: the kernel needs a GPU device" % self.device
-        lead = obs.shape[:-3]
-        m = 1
-        for d in lead:
-            m *= d
-        assert obs.is_contiguous() and agent_state.is_contiguous()
-        assert obs.dtype in (torch.float32, torch.bfloat16) and agent_state.dtype == torch.float32
-        if env is not None:
-            assert env.obs.dtype == obs.dtype, "obs and env.obs differ in dtype"
-        assert obs.numel() == m * self.n_features and agent_state.numel() == m * 2
+        lead, m = check_rows(self.n_features, obs, agent_state, env)
         if logits is not None:
             assert logits.shape == (m, self.n_rot + self.n_ph) and logits.dtype == torch.float32 and logits.is_contiguous()
         if out is not None:

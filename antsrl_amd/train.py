@@ -25,9 +25,10 @@ TRAINED_LAYERS = MEMNET_LAYERS[:9]
 
 
 class _DqnTrainer:
-    """What the three trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
-    workspace, and train() around step().  A subclass holds its nets, writes grad / apply / step over its own entries,
-    sync_target, and `_sizes(B, workspace_bytes, launches)`, its antsrl_*train_sizes call."""
+    """What the four trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
+    workspace, and train() around step().  A subclass holds its nets, writes grad / apply / step over its own entries
+    (_FlatTrainer does, for the three whose ABIs share one argument order), sync_target, and
+    `_sizes(B, workspace_bytes, launches)`, its antsrl_*train_sizes call."""
 
     minibatch = 264  # train()'s default: the reference class's
 
@@ -264,6 +265,85 @@ class MemoryTrainer(_DqnTrainer):
         return loss
 
 
+class _FlatTrainer(_DqnTrainer):
+    """What the linear, the explore and the rework trainer share on top of _DqnTrainer: their entries antsrl_<entry>_sizes
+    / _grad / _apply / _step take one argument order behind the net's own leading arguments (include/antsrl.h), so the
+    three stages are written once.  A subclass names its `entry`, writes `_sizes`, gives `_net()` (what _grad and _step
+    take in front of the arrays) and `_apply_net()` (what _apply takes in front of Adam's m), keeps Adam's moments in
+    `_adam` [2][P] and overrides `_weights_changed` when a training step moves its acting weights.
+
+    The views are those of a net that is ONE flat block described by `_offs` (name -> (offset, shape)), `model` and
+    `target`: the explore and the rework trainer's.  The linear trainer's net has two parts and it writes its own."""
+
+    entry = None  # "lintrain", "exptrain", "reworktrain"
+
+    def _net(self) -> tuple:
+        raise NotImplementedError
+
+    def _apply_net(self) -> tuple:
+        raise NotImplementedError
+
+    def _weights_changed(self) -> None:
+        """A call that changed the model's weights has been enqueued."""
+
+    def _call(self, stage: str, *args):
+        name = "%s_%s" % (self.entry, stage)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._lib, "antsrl_" + name)(*args, _lib.stream(self.device)), name)
+
+    def _adam_args(self) -> tuple:
+        return self.step_count, self.lr, self.betas[0], self.betas[1], self.eps
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def _views(self, flat) -> dict:
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self) -> dict:
+        """The model's tensors (copies) under the reference's names, in its order."""
+        return {k: v.clone() for k, v in self._views(self.model).items()}
+
+    def target_state_dict(self) -> dict:
+        return {k: v.clone() for k, v in self._views(self.target).items()}
+
+    def adam_state(self) -> dict:
+        """torch.optim.Adam's state for the trained tensors: step, exp_avg, exp_avg_sq (copies)."""
+        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
+                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
+
+    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
+        """The flat gradient (self.grads by default) as views named like the trained tensors."""
+        return self._views(self.grads if grads is None else grads)
+
+    # ---- the stages ---------------------------------------------------------------------------------------------
+    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The loss (0-d device tensor) and the gradients of the trained floats into self.grads; nothing is updated.
+        Rows: as MemoryTrainer.grad."""
+        arrays, N, B = self._batch(batch_or_replay, idx)
+        loss = self._loss(loss)
+        self._call("grad", *self._net(), *map(_p, arrays), N, _p(idx), B, self.discount, _p(self.grads), _p(loss),
+                   _p(self._work))
+        return loss
+
+    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
+        """One Adam step on the trained floats from the flat gradient (self.grads by default)."""
+        g = self._grads(grads)
+        self.step_count += 1
+        self._call("apply", *self._apply_net(), _p(self._adam[0]), _p(self._adam[1]), _p(g), *self._adam_args())
+        self._weights_changed()
+
+    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
+             keep_grads: bool = True) -> torch.Tensor:
+        """One training step on the minibatch, gradient and Adam in the same launches (antsrl_<entry>_step): returns the
+        loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
+        arrays, N, B = self._batch(batch_or_replay, idx)
+        loss = self._loss(loss)
+        self.step_count += 1
+        self._call("step", *self._net(), _p(self._adam[0]), _p(self._adam[1]), *map(_p, arrays), N, _p(idx), B, self.discount,
+                   *self._adam_args(), _p(self.grads) if keep_grads else None, _p(loss), _p(self._work))
+        self._weights_changed()
+        return loss
+
+
 #: CollectModel.state_dict()'s names and order (agents/collect_agent.py:24-51 over explore_agent_pytorch.py:24-45)
 LINEAR_NAMES = ("explore_model.layer1.weight", "explore_model.layer1.bias", "explore_model.layer2.weight",
                 "explore_model.layer2.bias", "layer3.weight", "layer3.bias")
@@ -276,7 +356,7 @@ LINEAR_TRAINED = {"explore_model.layer2.weight": (0, (3, 32)), "explore_model.la
 EXPLORE_NAMES = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias")
 
 
-class LinearTrainer(_DqnTrainer):
+class LinearTrainer(_FlatTrainer):
     """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
     reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
 
@@ -289,6 +369,8 @@ class LinearTrainer(_DqnTrainer):
     The surface is MemoryTrainer's: grad / apply / step, train(replay, done), state_dict / load_state_dict under the
     reference's six names, target_state_dict, sync_target, adam_state, grad_dict.  train() is CollectAgent.train
     (:105-148)."""
+
+    entry = "lintrain"
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
@@ -370,49 +452,18 @@ class LinearTrainer(_DqnTrainer):
     def _sizes(self, B, workspace_bytes, launches):
         _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, workspace_bytes, launches), "lintrain_sizes")
 
-    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The loss (0-d device tensor) and the gradients of the four trained tensors into self.grads; nothing is
-        updated.  Rows: as MemoryTrainer.grad."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
+    def _net(self) -> tuple:
         p = self.policy
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_lintrain_grad(self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3),
-                                                      _p(st), _p(ast), _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N,
-                                                      _p(idx), B, self.discount, _p(self.grads), _p(loss), _p(self._work),
-                                                      _lib.stream(self.device)), "lintrain_grad")
-        return loss
+        return self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3)
 
-    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
-        """One Adam step on the 198 trained floats from the flat gradient (self.grads by default)."""
-        g = self._grads(grads)
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_lintrain_apply(_p(self.heads), _p(self._adam[0]), _p(self._adam[1]), _p(g),
-                                                       self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                       _lib.stream(self.device)), "lintrain_apply")
-        self.version += 1
+    def _apply_net(self) -> tuple:
+        return (_p(self.heads),)
 
-    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
-             keep_grads: bool = True) -> torch.Tensor:
-        """One training step on the minibatch, gradient and Adam in the same launches (antsrl_lintrain_step): returns the
-        loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
-        p = self.policy
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_lintrain_step(self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3),
-                                                      _p(self._adam[0]), _p(self._adam[1]), _p(st), _p(ast), _p(act), _p(rw),
-                                                      _p(nst), _p(nast), _p(dn), N, _p(idx), B, self.discount,
-                                                      self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                      _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
-                                                      _lib.stream(self.device)), "lintrain_step")
-        self.version += 1
-        return loss
+    def _weights_changed(self) -> None:
+        self.version += 1  # every step moves the live layer2
 
 
-class ExploreTrainer(_DqnTrainer):
+class ExploreTrainer(_FlatTrainer):
     """ExploreAgentPytorch's model, target model and optimizer on the device (agents/explore_agent_pytorch.py:48-133 as it
     was meant: ExploreModel with the concat of CollectModel.forward, collect_agent.py:47-49; defaults: the reference
     class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_exptrain_step` (antsrl_exptrain.hip).
@@ -427,6 +478,7 @@ class ExploreTrainer(_DqnTrainer):
     ExploreAgentPytorch.train (:90-133)."""
 
     minibatch = 256
+    entry = "exptrain"
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
@@ -452,16 +504,6 @@ class ExploreTrainer(_DqnTrainer):
             self.load_state_dict(state_dict)
 
     # ---- weights ------------------------------------------------------------------------------------------------
-    def _views(self, flat) -> dict:
-        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
-
-    def state_dict(self) -> dict:
-        """The model's four tensors (copies) under ExploreModel's names, in its order."""
-        return {k: v.clone() for k, v in self._views(self.model).items()}
-
-    def target_state_dict(self) -> dict:
-        return {k: v.clone() for k, v in self._views(self.target).items()}
-
     def load_state_dict(self, sd) -> None:
         """ExploreAgentPytorch.load_model (:157-159): sets the model AND the target net.  ExploreModel's names, bare or
         behind CollectModel's `explore_model.` prefix (other entries, such as layer3, are ignored).  Adam's state is
@@ -474,15 +516,6 @@ class ExploreTrainer(_DqnTrainer):
         self.target.copy_(self.model)
         self.version += 1
 
-    def adam_state(self) -> dict:
-        """torch.optim.Adam's state for the four tensors: step, exp_avg, exp_avg_sq (copies)."""
-        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
-                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
-
-    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
-        """The flat gradient (self.grads by default) as views named like the four tensors."""
-        return self._views(self.grads if grads is None else grads)
-
     def sync_target(self) -> None:
         """target := model (:127-131): one device copy of the block; the acting policy's tensors are views of it."""
         self.target.copy_(self.model)
@@ -493,45 +526,14 @@ class ExploreTrainer(_DqnTrainer):
     def _sizes(self, B, workspace_bytes, launches):
         _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, workspace_bytes, launches), "exptrain_sizes")
 
-    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The loss (0-d device tensor) and the gradients of all P floats into self.grads; nothing is updated.  Rows: as
-        MemoryTrainer.grad."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_exptrain_grad(self.n_features, _p(self.model), _p(self.target), _p(st), _p(ast),
-                                                      _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N, _p(idx), B,
-                                                      self.discount, _p(self.grads), _p(loss), _p(self._work),
-                                                      _lib.stream(self.device)), "exptrain_grad")
-        return loss
+    def _net(self) -> tuple:
+        return self.n_features, _p(self.model), _p(self.target)
 
-    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
-        """One Adam step on all P floats from the flat gradient (self.grads by default)."""
-        g = self._grads(grads)
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_exptrain_apply(self.n_features, _p(self.model), _p(self._adam[0]), _p(self._adam[1]),
-                                                       _p(g), self.step_count, self.lr, self.betas[0], self.betas[1],
-                                                       self.eps, _lib.stream(self.device)), "exptrain_apply")
-
-    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
-             keep_grads: bool = True) -> torch.Tensor:
-        """One training step on the minibatch, gradient and Adam in the same two launches (antsrl_exptrain_step): returns
-        the loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_exptrain_step(self.n_features, _p(self.model), _p(self.target), _p(self._adam[0]),
-                                                      _p(self._adam[1]), _p(st), _p(ast), _p(act), _p(rw), _p(nst),
-                                                      _p(nast), _p(dn), N, _p(idx), B, self.discount, self.step_count,
-                                                      self.lr, self.betas[0], self.betas[1], self.eps,
-                                                      _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
-                                                      _lib.stream(self.device)), "exptrain_step")
-        return loss
+    def _apply_net(self) -> tuple:
+        return self.n_features, _p(self.model)
 
 
-class ReworkTrainer(_DqnTrainer):
+class ReworkTrainer(_FlatTrainer):
     """CollectAgentRework's model, target model and optimizer on the device (agents/collect_agent_rework.py:66-152;
     defaults: the reference class's, discount 0.5, Adam lr 1e-4, minibatch 264), trained by `antsrl_reworktrain_step`
     (antsrl_reworktrain.hip).
@@ -545,6 +547,8 @@ class ReworkTrainer(_DqnTrainer):
     The surface is ExploreTrainer's: grad / apply / step, train(replay, done), train_on, launches, state_dict /
     load_state_dict under CollectModelRework's twenty names (the hidden widths come from a state_dict's shapes),
     target_state_dict, sync_target, adam_state, grad_dict."""
+
+    entry = "reworktrain"
 
     def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
                  eps: float = 1e-8, update_target_every: int = 1, n_rot: int = 3, n_ph: int = 3, seed: int = 0,
@@ -574,16 +578,6 @@ class ReworkTrainer(_DqnTrainer):
         self.policy = ReworkPolicy(n_features, self.device, params=self._views(self.target))  # acts on the target block
 
     # ---- weights ------------------------------------------------------------------------------------------------
-    def _views(self, flat) -> dict:
-        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
-
-    def state_dict(self) -> dict:
-        """The model's 20 tensors (copies) under CollectModelRework's names, in its order."""
-        return {k: v.clone() for k, v in self._views(self.model).items()}
-
-    def target_state_dict(self) -> dict:
-        return {k: v.clone() for k, v in self._views(self.target).items()}
-
     def load_state_dict(self, sd) -> None:
         """CollectAgentRework.load_model (:186-188): sets the model AND the target net, and collapses the target once.
         Adam's state is kept, as the reference's optimizer keeps it."""
@@ -594,15 +588,6 @@ class ReworkTrainer(_DqnTrainer):
         self.target.copy_(self.model)
         self.policy.recollapse()
         self.version += 1
-
-    def adam_state(self) -> dict:
-        """torch.optim.Adam's state for the 20 tensors: step, exp_avg, exp_avg_sq (copies)."""
-        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
-                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
-
-    def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
-        """The flat gradient (self.grads by default) as views named like the 20 tensors."""
-        return self._views(self.grads if grads is None else grads)
 
     def sync_target(self) -> None:
         """target := model (:147-150): one device copy of the block and one collapse; the acting policy's tensors are
@@ -617,40 +602,8 @@ class ReworkTrainer(_DqnTrainer):
         _lib.check(self._lib.antsrl_reworktrain_sizes(C.byref(self.shape), B, None, workspace_bytes, launches),
                    "reworktrain_sizes")
 
-    def grad(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The loss (0-d device tensor) and the gradients of all P floats into self.grads; nothing is updated.  Rows: as
-        MemoryTrainer.grad."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_reworktrain_grad(C.byref(self.shape), _p(self.model), _p(self.policy.collapsed),
-                                                         _p(st), _p(ast), _p(act), _p(rw), _p(nst), _p(nast), _p(dn), N,
-                                                         _p(idx), B, self.discount, _p(self.grads), _p(loss),
-                                                         _p(self._work), _lib.stream(self.device)), "reworktrain_grad")
-        return loss
+    def _net(self) -> tuple:
+        return C.byref(self.shape), _p(self.model), _p(self.policy.collapsed)
 
-    def apply(self, grads: Optional[torch.Tensor] = None) -> None:
-        """One Adam step on all P floats from the flat gradient (self.grads by default)."""
-        g = self._grads(grads)
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_reworktrain_apply(C.byref(self.shape), _p(self.model), _p(self._adam[0]),
-                                                          _p(self._adam[1]), _p(g), self.step_count, self.lr, self.betas[0],
-                                                          self.betas[1], self.eps, _lib.stream(self.device)),
-                       "reworktrain_apply")
-
-    def step(self, batch_or_replay, idx: Optional[torch.Tensor] = None, loss: Optional[torch.Tensor] = None,
-             keep_grads: bool = True) -> torch.Tensor:
-        """One training step on the minibatch, gradient and Adam in the same four launches (antsrl_reworktrain_step):
-        returns the loss as a 0-d device tensor.  The same bits as grad() followed by apply()."""
-        (st, ast, act, rw, nst, nast, dn), N, B = self._batch(batch_or_replay, idx)
-        loss = self._loss(loss)
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_reworktrain_step(C.byref(self.shape), _p(self.model), _p(self.policy.collapsed),
-                                                         _p(self._adam[0]), _p(self._adam[1]), _p(st), _p(ast), _p(act),
-                                                         _p(rw), _p(nst), _p(nast), _p(dn), N, _p(idx), B, self.discount,
-                                                         self.step_count, self.lr, self.betas[0], self.betas[1], self.eps,
-                                                         _p(self.grads) if keep_grads else None, _p(loss), _p(self._work),
-                                                         _lib.stream(self.device)), "reworktrain_step")
-        return loss
+    def _apply_net(self) -> tuple:
+        return C.byref(self.shape), _p(self.model)
