@@ -4,7 +4,7 @@ from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
-           "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule"]
+           "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -29,6 +29,9 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "EpisodeMonitor":
         from .monitor import EpisodeMonitor
         return EpisodeMonitor
+    if name == "EpisodeStats":
+        from .stats import EpisodeStats
+        return EpisodeStats
     if name in ("train_episodes", "epsilon_schedule"):
         from . import driver
         return getattr(driver, name)

@@ -29,7 +29,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_rework_collapse", "antsrl_policy_rework", "antsrl_reworktrain_sizes", "antsrl_reworktrain_grad",
            "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select", "antsrl_monitor_sizes",
            "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
-           "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames")
+           "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames",
+           "antsrl_stats_sizes", "antsrl_stats_row")
 
 _lib = None
 
@@ -170,6 +171,8 @@ def load() -> C.CDLL:
     lib.antsrl_recorder_frame.argtypes = [vp, vp, C.POINTER(C.c_int32), i32, i32, i32, i32, vp]
     lib.antsrl_render_sizes.argtypes = [vp, i32, C.POINTER(AntsRenderOpts), sz, sz]
     lib.antsrl_render_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(AntsRenderOpts), vp, vp, vp]
+    lib.antsrl_stats_sizes.argtypes = [vp, i32, sz, sz, sz]
+    lib.antsrl_stats_row.argtypes = [vp, vp, i32, i32, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

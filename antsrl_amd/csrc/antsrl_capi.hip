@@ -1,7 +1,8 @@
 // antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), and the library's error
-// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip; the episode recorder's are here (they need
-// the handle and its deferred update), its kernels in antsrl_recorder.hip; the episode renderer's stand beside them (they
-// take the recorder's block and its layout), its kernels in antsrl_render.hip.
+// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip; the episode recorder's and the colony
+// statistics' are here (they need the handle and its deferred update), their kernels in antsrl_recorder.hip /
+// antsrl_stats.hip; the episode renderer's stand beside them (they take the recorder's block and its layout), its kernels
+// in antsrl_render.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the
@@ -17,6 +18,7 @@
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
 #include "antsrl_recorder.h"
+#include "antsrl_stats.h"
 #include "antsrl_render.h"
 
 // launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
@@ -1137,6 +1139,47 @@ extern "C" int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *
                                               (unsigned char *)block + L.static_bytes + (size_t)frame * L.frame_bytes,
                                               (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "recorder_frame");
+    return ANTSRL_OK;
+}
+
+// ---- the colony statistics (include/antsrl.h, "The colony statistics"; kernels in antsrl_stats.hip) -------------------
+static int stats_layout(const char *who, const AntsHandle *h, int32_t max_rows, StatsLayout *L)
+{
+    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
+    if (max_rows < 1) return fail(ANTSRL_E_INVALID, "%s: max_rows must be >= 1 (%d)", who, max_rows);
+    const bool keeps_map = h->cfg.reward_kind == ANTSRL_REWARD_EXPLORATION || h->cfg.reward_kind == ANTSRL_REWARD_ALL;
+    *L = antsrl_stats_layout(h->p.E, h->p.C, (size_t)h->p.W * h->p.H, keeps_map ? 1 : 0);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_stats_sizes(const AntsHandle *h, int32_t max_rows, size_t *row_bytes, size_t *scratch_bytes, size_t *bytes)
+{
+    StatsLayout L;
+    int rc = stats_layout("stats_sizes", h, max_rows, &L);
+    if (rc) return rc;
+    if (row_bytes) *row_bytes = 8 * L.row_words;
+    if (scratch_bytes) *scratch_bytes = 8 * L.scratch_words;
+    if (bytes) *bytes = 8 * ((size_t)max_rows * L.row_words + L.scratch_words);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_stats_row(AntsHandle *h, void *block, int32_t max_rows, int32_t row, void *stream)
+{
+    const char *who = "stats_row";
+    StatsLayout L;
+    int rc = stats_layout(who, h, max_rows, &L);
+    if (rc) return rc;
+    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
+    if ((uintptr_t)block & 7) return fail(ANTSRL_E_INVALID, "%s: block must be 8-byte aligned", who);
+    if (row < 0 || row >= max_rows) return fail(ANTSRL_E_INVALID, "%s: row %d is not in [0, max_rows = %d)", who, row, max_rows);
+    if (!h->is_reset) return not_reset(h);
+    if (h->phase_next) return mid_update(h);
+    rc = flush_pending(h, (hipStream_t)stream); // a row is the state AFTER Environment.update, as a recorded frame is
+    if (rc) return rc;
+    double *words = (double *)block;
+    hipError_t e = antsrl_launch_stats_row(h->p, h->cur, L, words + (size_t)row * L.row_words,
+                                           words + (size_t)max_rows * L.row_words, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, who);
     return ANTSRL_OK;
 }
 

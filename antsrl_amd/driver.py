@@ -8,7 +8,9 @@ episode, `steps` rollout_steps each followed by EpisodeMonitor.step(env.reward, 
 the epsilon schedule (:149).  The statistics are the monitor's (antsrl_amd/monitor.py); the one synchronisation is its
 log() at the end (and the snapshots, where asked for: a snapshot is a read-back — unless snapshot_on_device keeps the
 visualised episodes' frames on the device, antsrl_amd/recorder.py, and reads them once per such episode).  With render_dir
-those episodes are also drawn on the device (antsrl_amd/render.py) and written as PNG files.
+those episodes are also drawn on the device (antsrl_amd/render.py) and written as PNG files.  With stats_every the colony's
+own numbers (food at the anthill, on the map and carried, explored cells, pheromone: antsrl_amd/stats.py) are reduced on
+the device every so many steps and read back once, with the monitor's log.
 """
 from __future__ import annotations
 
@@ -42,7 +44,8 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,
                    min_epsilon: float = 0.01, max_epsilon: float = 1.0, monitor: Optional[EpisodeMonitor] = None,
                    snapshot_every: Optional[int] = None, save_as: Optional[str] = None, snapshot_on_device: bool = False,
-                   snapshot_envs=(0,), render_dir: Optional[str] = None, render_every: int = 1) -> dict:
+                   snapshot_envs=(0,), render_dir: Optional[str] = None, render_every: int = 1,
+                   stats_every: Optional[int] = None) -> dict:
     """main.py's loop for `agent` (a device agent: MemoryAgent, CollectAgent, ExploreAgent, ReworkAgent) on `env` (a
     BatchedAntsEnv).  gen: the AntsGen handed to env.generate for every episode (config.make_gen).  An agent that has
     not been set up is set up on `env` at the first episode (once, :82-84).  monitor: an EpisodeMonitor to continue or
@@ -55,17 +58,28 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
     every render_every-th recorded frame of the first of snapshot_envs is drawn by an EpisodeRenderer with its defaults
     (a pheromone without max_val is divided by 255, where the recorder's cast saturates) and written to render_dir/episode_%04d/frame_%05d.png.
     save_as: agent.save_model at the end, when training (:154-157).
+    stats_every: a row of colony statistics (antsrl_amd/stats.py: food at the anthill, on the map and carried, explored
+    cells, pheromone) after step s of an episode when (s + 1) % stats_every == 0, and after an episode's last step if
+    that step did not already give one; two launches per row, read back once at the end.  None: nothing is constructed
+    and nothing is launched.
 
     Returns the monitor's log() (reports, report_episode, report_step, all_reward, all_loss, grand_total, n_losses)
-    with `epsilons` (the epsilon each episode ran with), `monitor`, and `states` (the snapshots, in order) when
-    snapshot_every is given.  Not training, all_loss is main.py:111's 0."""
+    with `epsilons` (the epsilon each episode ran with), `monitor`, `states` (the snapshots, in order) when
+    snapshot_every is given, and `stats` when stats_every is: EpisodeStats.rows() plus the host arrays `episode` and
+    `step` (counted from 1, as report_step is) of every row.  Not training, all_loss is main.py:111's 0."""
     env = getattr(env, "_backend", env)
     mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=50, max_reports=max(1, episodes * (steps // 50)),
                                                              max_episodes=max(1, episodes))
     if render_dir is not None and not snapshot_on_device:
         raise ValueError("train_episodes: render_dir draws the recorder's frames: it needs snapshot_on_device=True")
+    if stats_every is not None and stats_every < 1:
+        raise ValueError("train_episodes: stats_every must be >= 1 (%d)" % stats_every)
     states, epsilons = [], []
-    recorder = renderer = None
+    recorder = renderer = stats = None
+    stats_at = []  # (episode, step) per row; step counts from 1, as the monitor's report_step does
+    if stats_every is not None:
+        from .stats import EpisodeStats
+        stats = EpisodeStats(env, max_rows=max(1, episodes * (steps // stats_every + (1 if steps % stats_every else 0))))
     for episode in range(episodes):
         visualize = snapshot_every is not None and ((episode + 1) % snapshot_every == 0 or episode == 0 or not training)
         env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
@@ -86,6 +100,9 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
                 recorder.record()
             elif visualize:
                 states.extend(snapshot_batched(env))
+            if stats is not None and ((s + 1) % stats_every == 0 or s == steps - 1):
+                stats.record()
+                stats_at.append((episode, s + 1))
         if on_device:
             states.extend(recorder.snapshots())
             if render_dir is not None and recorder.n_frames:
@@ -102,4 +119,7 @@ def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0,
     log.update(epsilons=np.array(epsilons), monitor=mon)
     if snapshot_every is not None:
         log["states"] = states
+    if stats is not None:
+        at = np.array(stats_at, dtype=np.int64).reshape(-1, 2)
+        log["stats"] = dict(stats.rows(), episode=at[:, 0], step=at[:, 1])
     return log

@@ -1113,6 +1113,45 @@ int antsrl_recorder_begin(AntsHandle *h, void *block, const int32_t *env_indices
 int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
                           int32_t max_frames, int32_t with_heatmap, int32_t frame, void *stream);
 
+/* The colony statistics: what a training run reports of the task itself — the food a colony brought home (the number
+ * the reference's viewer prints, FOOD IN ANTHILL, gui/visualize.py:247), the food left on the map and in the mandibles,
+ * the explored cells, the pheromone on the map — as ONE row per call, reduced on the device in two launches, nothing
+ * read back.  The block is caller-allocated device memory (8-byte aligned, `bytes` of antsrl_stats_sizes): max_rows rows
+ * and then the scratch for the segments' partials.  A row is E = n_envs records of Q = 7 + 2 C dense 8-byte words, C =
+ * n_phero; row r lies at r * row_bytes, environment e's record at word e * Q of it:
+ *     word 0       int64    timestep[e]        ANTSRL_S_TIMESTEP
+ *          1       double   anthill_food[e]    ANTSRL_S_ANTHILL_FOOD, copied, not summed
+ *          2       double   food_left          the sum of (double)food[e][g] over the grid (ANTSRL_S_FOOD)
+ *          3       int64    food_cells         cells with food > 0
+ *          4       double   food_carried       the sum of (double)holding[e][n] (ANTSRL_S_HOLDING)
+ *          5       int64    n_carrying         ants with holding > 0
+ *          6       int64    explored_cells     cells with ANTSRL_S_EXPLORED != 0; -1 where the reward kind keeps no
+ *                                              explored map (only ANTSRL_REWARD_EXPLORATION and ANTSRL_REWARD_ALL keep one)
+ *          7 + 2c  double   phero_mass[c]      the sum of the materialised (double)phero[e][c][g] (ANTSRL_S_PHERO_C<c>:
+ *                                              scaled units times g_now, zero below the threshold)
+ *          8 + 2c  int64    phero_cells[c]     cells whose materialised value is > 0
+ * Every value is what antsrl_read_state gives at the same moment, on every layout the handle can be in.
+ * row_bytes = 8 E Q;  scratch_bytes = 8 E nseg (3 + 2 C) with nseg = ceil(G / 4096), G = W * H;  bytes = max_rows *
+ * row_bytes + scratch_bytes.  The scratch is rewritten by every row and means nothing to the caller.
+ * THE ORDER OF THE SUMS (float64 adds, round to nearest even; no atomics: equal state gives equal bits).  Cells: the
+ * canonical cell ids g = x * H + y of an environment are cut into segments of 4096; one workgroup of 256 threads per
+ * (segment, environment): slot t starts at +0.0 / 0 and takes the cells seg * 4096 + t + 256 k, k = 0, 1, ..., in
+ * ascending order, skipping g >= G; the 256 slots are folded with x[i] += x[i + s] for i < s, s = 128, 64, ..., 1; x[0]
+ * is the segment's partial, written to the scratch.  Second stage: one workgroup per environment: slot t takes the
+ * partials of the segments t, t + 256, ... in ascending order, with the same fold; the same workgroup sums holding as
+ * the training monitor sums rewards (slot t takes the ants t, t + 256, ..., the same fold) and copies timestep and
+ * anthill_food.  The counts are int64 and exact; they take the same path.
+ *   _sizes:  the three sizes (any of the pointers may be NULL); no HIP call.
+ *   _row:    TWO launches: row `row` of the block, from the state as it stands.  Like antsrl_read_state and
+ *            antsrl_recorder_frame it first enqueues a deferred update on its stream argument (see antsrl_update): a row
+ *            is the state AFTER Environment.update, and the step behind a row does not fuse its update with the move.
+ * The same max_rows goes to every call on one block (it fixes where the scratch lies).
+ * Rules, all checked before any HIP call (ANTSRL_E_INVALID, the block untouched): handle not NULL; max_rows >= 1; block
+ * not NULL and 8-byte aligned; row in [0, max_rows): a row is never wrapped; a handle that has been reset; no
+ * Environment.update in progress (antsrl_update_phase).  No entry allocates or synchronises the host. */
+int antsrl_stats_sizes(const AntsHandle *h, int32_t max_rows, size_t *row_bytes, size_t *scratch_bytes, size_t *bytes);
+int antsrl_stats_row(AntsHandle *h, void *block, int32_t max_rows, int32_t row, void *stream);
+
 /* The episode renderer: RGB frames of a recorded episode, computed on the device from the episode recorder's block and
  * from nothing else (the live state is not read, so no deferred update is enqueued and a running episode is not
  * disturbed; the block is read-only here).  It stands in for the reference's replay viewer (gui/visualize.py), of which
