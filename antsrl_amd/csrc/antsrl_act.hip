@@ -2,6 +2,7 @@
 // one workgroup per environment: mandibles + food exchange, activation, rotate, move, perception
 // gather, reward.  Host launchers at the end.  No MFMA: nothing on this path is a dense contraction.
 #include "antsrl_util.h"
+#include "antsrl_launch.h"
 #include "antsrl_update_env.h"
 #include "antsrl_flush.h"
 

@@ -1,12 +1,10 @@
-// antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), and the library's error
-// reporting (antsrl_fail.h).  The memory agent's entries are in antsrl_memapi.hip; the episode recorder's and the colony
-// statistics' are here (they need the handle and its deferred update), their kernels in antsrl_recorder.hip /
-// antsrl_stats.hip; the episode renderer's stand beside them (they take the recorder's block and its layout), its kernels
-// in antsrl_render.hip.
+// antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), the library's error
+// reporting (antsrl_fail.h) and the handle's helpers (antsrl_handle.h).  The memory agent's entries are in
+// antsrl_memapi.hip; the episode recorder's, the colony statistics' and the episode renderer's in antsrl_logapi.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the
-// caller's stream.  No allocation, no synchronisation, no exceptions across the ABI.
+// caller's stream (antsrl_launch.h).  No allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -15,80 +13,8 @@
 #include <string.h>
 #include <new>
 
-#include "antsrl_device.h"
-#include "antsrl_fail.h"
-#include "antsrl_recorder.h"
-#include "antsrl_stats.h"
-#include "antsrl_render.h"
-
-// launchers (antsrl_act.hip, antsrl_update.hip, antsrl_sweep.hip, antsrl_state.hip)
-hipError_t antsrl_launch_act(const KP &p, const int8_t *rot, const int8_t *ph, int cur, float *obs,
-                             float *agent_state, float *reward, uint8_t *done, int flags, hipStream_t st);
-bool antsrl_act_fits(const KP &p);
-bool antsrl_act_needs_hbm_maps(const KP &p);
-hipError_t antsrl_launch_sweep(const KP &p, int cur, hipStream_t st);
-hipError_t antsrl_launch_update(const KP &p, const double *jitter, int out_buf, hipStream_t st, int phases = 15);
-hipError_t antsrl_launch_collect_full(const KP &p, hipStream_t st);
-hipError_t antsrl_launch_reset(const KP &p, const AntsInit *in, hipStream_t st);
-hipError_t antsrl_launch_set_activation(const KP &p, const float *act, hipStream_t st);
-hipError_t antsrl_launch_read_state(const KP &p, int which, int cur, void *dst, hipStream_t st);
-hipError_t antsrl_launch_perceptive_field(const KP &p, uint8_t *dst, hipStream_t st);
-hipError_t antsrl_launch_generate(const KP &p, const AntsGen &g, uint64_t seed, hipStream_t st);
-hipError_t antsrl_launch_phero_wall_clear(const KP &p, hipStream_t st, int buf = 0);
-hipError_t antsrl_launch_phero_renorm(const KP &p, hipStream_t st);
-// cell-meta path (antsrl_perceive.hip)
-bool antsrl_meta_supported(const KP &p);
-hipError_t antsrl_launch_move(const KP &p, const int8_t *rot, const int8_t *ph, uint8_t *done, int do_step, uint32_t seq,
-                              hipStream_t st);
-hipError_t antsrl_launch_perceive(const KP &p, int cur, float *obs, float *agent_state, float *reward, int flags,
-                                  uint32_t seq, hipStream_t st, const PolArgs *pol, uint32_t obs_pitch, bool generic);
-bool antsrl_perceive_fast(const KP &p);
-bool antsrl_inloop_policy_supported(const KP &p);
-hipError_t antsrl_launch_policy_pack(unsigned char *pack, const float *w1, const float *b1, const float *w2, const float *b2,
-                                     const float *w3, const float *b3, int F, hipStream_t st);
-hipError_t antsrl_launch_meta_rebase(const KP &p, hipStream_t st);
-bool antsrl_explored_summary_supported(const KP &p, bool with_policy);
-hipError_t antsrl_launch_explored_summary(const KP &p, hipStream_t st);
-bool antsrl_update_move_supported(const KP &p);
-hipError_t antsrl_launch_update_move(const KP &p, int out_buf, double g_dep, double inv_g_dep, const int8_t *rot,
-                                     const int8_t *ph, uint8_t *done, uint32_t seq, hipStream_t st, bool with_frames);
-int antsrl_perceive_run(const KP &p);
-hipError_t antsrl_launch_copy16(void *dst, const void *src, size_t bytes, hipStream_t st);
-
-struct AntsHandle {
-    AntsCfg cfg;
-    KP p;
-    int cur;               // pheromone buffer holding the current grid
-    int steps_since_update;// RLApi.step calls since the last Environment.update
-    bool need_full_collect;// next update must run Anthill.update over the whole grid
-    bool is_reset;
-    bool episode_over;     // a refused auto-reset left a finished episode behind (see antsrl_step_update)
-    size_t ws_bytes[2];    // the state block and the record block (one block: [0] is all of it, [1] = 0)
-    AntsGen gen;           // device generator parameters (antsrl_generate)
-    bool has_gen;
-    uint64_t episode_seed; // seed of the current episode
-    int host_timestep;     // mirrors Environment.timestep (all envs step in lockstep)
-    long long sweeps;      // scaled mode: updates since the units were last re-based
-    bool obs_bf16;         // observation buffers are bfloat16 (antsrl_set_obs_format)
-    uint32_t obs_pitch;    // elements between two ants' observation rows (antsrl_set_obs_row_stride), 0 = dense
-    bool prc_generic;      // k_perceive's generic kernel is pinned (antsrl_set_perceive_path)
-    bool prc_noskip;       // the fast kernel ignores the explored summary, none is kept (ANTSRL_PERCEIVE_FAST_NOSKIP)
-    uint32_t sum_obs;      // observations since the last reset: the explored summary's refresh cadence (summary_cadence)
-    bool sum_due;          // a refresh of the summary is due behind the observation just enqueued (summary_refresh_due)
-    bool sum_live;         // a refresh has been enqueued since the last reset: k_perceive consumes the summary (ACT_SUMMARY)
-    bool need_wall_clear;  // scaled mode: initial grid may hold pheromone on wall cells
-    hipEvent_t ev[ANTSRL_TIMING_EVENTS]; // measurement hook (antsrl_set_timing_events)
-    bool ev_armed;
-    uint32_t obs_seq;      // cell-meta path: observations since the explored stamps were last re-based
-    PolArgs pol;           // in-loop policy (antsrl_set_inloop_policy); pol.pack == NULL: none
-    // Deferred update (include/antsrl.h): Environment.update was requested, its host-side bookkeeping is done, its
-    // kernel has NOT been enqueued yet — the next antsrl_step runs it fused with the move (k_update_move); every other
-    // entry point that touches the state enqueues it first (flush_pending).
-    bool pend_update;
-    KP pend_p;             // kernel parameters as they stood at the update's call (g_dep / inv_g_dep differ afterwards)
-    int pend_out_buf;
-    int phase_next;        // antsrl_update_phase: the next phase of an Environment.update in progress (0: none in progress)
-};
+#include "antsrl_handle.h"
+#include "antsrl_launch.h"
 
 static thread_local char g_err[512] = "";
 
@@ -394,15 +320,7 @@ static int create_handle(const AntsCfg *cfg, void *state_ws, void *record_ws, bo
     fill_kp(cfg, &h->p);
     size_t b[2];
     carve(cfg, &h->p.s, (unsigned char *)state_ws, (unsigned char *)record_ws, split, b);
-    h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = false; h->episode_over = false; h->pend_update = false;
-    h->phase_next = 0;
-    h->pol = PolArgs{};
-    h->sweeps = 0; h->need_wall_clear = false;
-    h->has_gen = false; h->episode_seed = 0; h->host_timestep = 1; h->obs_bf16 = false; h->obs_pitch = 0;
-    h->prc_generic = false; h->prc_noskip = false; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
     h->ws_bytes[0] = need[0]; h->ws_bytes[1] = need[1];
-    h->ev_armed = false;
-    h->obs_seq = 0;
     if (!h->p.meta && !antsrl_act_fits(h->p)) {
         delete h;
         return fail(ANTSRL_E_UNSUPPORTED,
@@ -451,6 +369,18 @@ extern "C" int antsrl_create2(const AntsCfg *cfg, void *state_ws, size_t state_b
 
 extern "C" void antsrl_destroy(AntsHandle *h) { delete h; }
 
+// The start of an episode, once the launch that writes its state has succeeded (ahead of it the caller has dropped
+// `pend_update` and `phase_next` of the state being replaced).
+static void begin_episode(AntsHandle *h, bool need_wall_clear, uint64_t episode_seed)
+{
+    h->p.deposit_strength = h->cfg.deposit_strength;
+    h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = true; h->episode_over = false;
+    h->sweeps = 0; h->need_wall_clear = need_wall_clear; h->host_timestep = 1;
+    h->obs_seq = 0; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
+    h->episode_seed = episode_seed;
+    set_decay(h);
+}
+
 extern "C" int antsrl_reset(AntsHandle *h, const AntsInit *init, void *stream)
 {
     if (!h || !init) return fail(ANTSRL_E_INVALID, "NULL handle or init");
@@ -459,13 +389,8 @@ extern "C" int antsrl_reset(AntsHandle *h, const AntsInit *init, void *stream)
     if (h->p.R > 0 && !init->rocks) return fail(ANTSRL_E_INVALID, "AntsInit.rocks is NULL but n_rocks > 0");
     h->pend_update = false; // (a deferred update of the state being replaced)
     h->phase_next = 0;
-    hipError_t e = antsrl_launch_reset(h->p, init, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "reset");
-    h->p.deposit_strength = h->cfg.deposit_strength;
-    h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = true; h->episode_over = false;
-    h->sweeps = 0; h->need_wall_clear = h->p.scaled && init->phero != nullptr;
-    h->host_timestep = 1; h->obs_seq = 0; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
-    set_decay(h);
+    if (int rc = enqueued(antsrl_launch_reset(h->p, init, (hipStream_t)stream), "reset")) return rc;
+    begin_episode(h, h->p.scaled && init->phero != nullptr, h->episode_seed); // (the seed is the generator's: it stays)
     return ANTSRL_OK;
 }
 
@@ -487,13 +412,8 @@ static int do_generate(AntsHandle *h, uint64_t seed, hipStream_t st)
     if (rc) return rc;
     h->pend_update = false; // (a deferred update of the state being replaced)
     h->phase_next = 0;
-    hipError_t e = antsrl_launch_generate(h->p, h->gen, seed, st);
-    if (e != hipSuccess) return hip_fail(e, "generate");
-    h->p.deposit_strength = h->cfg.deposit_strength;
-    h->cur = 0; h->steps_since_update = 0; h->need_full_collect = true; h->is_reset = true; h->episode_over = false;
-    h->sweeps = 0; h->need_wall_clear = false; h->host_timestep = 1; h->obs_seq = 0; h->sum_obs = 0; h->sum_due = false; h->sum_live = false;
-    h->episode_seed = seed;
-    set_decay(h);
+    if (int rc = enqueued(antsrl_launch_generate(h->p, h->gen, seed, st), "generate")) return rc;
+    begin_episode(h, false, seed);
     return ANTSRL_OK;
 }
 
@@ -600,39 +520,32 @@ static bool summary_cadence(uint32_t n)
     return n >= SUMMARY_FIRST && (n <= SUMMARY_STEADY ? (n & (n - 1u)) == 0u : n % SUMMARY_STEADY == 0u);
 }
 
-// Enqueues a deferred update on its own (k_update_one), e.g. ahead of a state read.
-static int flush_pending(AntsHandle *h, hipStream_t st)
+int flush_pending(AntsHandle *h, hipStream_t st) // antsrl_handle.h
 {
     if (!h->pend_update) return ANTSRL_OK;
     h->pend_update = false;
-    hipError_t e = antsrl_launch_update(h->pend_p, nullptr, h->pend_out_buf, st);
-    if (e != hipSuccess) return hip_fail(e, "deferred update");
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_update(h->pend_p, nullptr, h->pend_out_buf, st), "deferred update");
 }
 
-static int not_reset(const AntsHandle *h)
+int handle_ready(const AntsHandle *h, MidUpdate mid) // antsrl_handle.h
 {
-    if (h->episode_over)
+    if (!h->is_reset && h->episode_over)
         return fail(ANTSRL_E_INVALID, "the episode is over and its auto-reset was refused (episode seed past np.random.seed's 32 bits): "
                                       "call antsrl_reset or antsrl_generate");
-    return fail(ANTSRL_E_INVALID, "antsrl_reset has not been called on this handle");
-}
-
-static int mid_update(const AntsHandle *h)
-{
-    return fail(ANTSRL_E_INVALID, "an Environment.update is in progress (antsrl_update_phase %d of 4 is next): finish it first", h->phase_next);
+    if (!h->is_reset) return fail(ANTSRL_E_INVALID, "antsrl_reset has not been called on this handle");
+    if (h->phase_next && mid == MID_UPDATE_REFUSED)
+        return fail(ANTSRL_E_INVALID, "an Environment.update is in progress (antsrl_update_phase %d of 4 is next): finish it first", h->phase_next);
+    return ANTSRL_OK;
 }
 
 // One observation on the cell-meta path: k_move (with the action phases when `stepping`) then k_perceive.
 static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *obs, float *agent_state,
                         float *reward, uint8_t *done, bool stepping, hipStream_t st, bool timed)
 {
-    hipError_t e;
     if (obs && h->obs_pitch != 0 && h->obs_pitch != (uint32_t)(h->p.PP * h->p.K) && h->pol.pack && h->obs_bf16) // (both setters refuse the
         return fail(ANTSRL_E_UNSUPPORTED, "a padded observation row stride and the in-loop policy exclude each other"); // pair; before any launch)
     if (h->obs_seq >= META_NEVER - 2) { // explored stamps: re-base long before the counter can reach "never"
-        e = antsrl_launch_meta_rebase(h->p, st);
-        if (e != hipSuccess) return hip_fail(e, "explored-stamp rebase");
+        if (int rc = enqueued(antsrl_launch_meta_rebase(h->p, st), "explored-stamp rebase")) return rc;
         h->obs_seq = 0;
     }
     h->obs_seq++;
@@ -643,25 +556,37 @@ static int meta_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, floa
         // bfloat16 or stay in LDS: c5 -2.5 %, k_perceive -5 % — and cost 1-2 us of a second sincos where it is bound by its
         // float32 store stream, which hides the prologue anyway (c3 / c2 / c4: +1 %; profiles/r04/frames_ab.txt).
         frames = h->pol.pack != nullptr;
-        e = antsrl_launch_update_move(h->p, h->pend_out_buf, h->pend_p.g_dep, h->pend_p.inv_g_dep, rot, ph, done, h->obs_seq, st, frames);
-        if (e != hipSuccess) return hip_fail(e, "update + move");
+        if (int rc = enqueued(antsrl_launch_update_move(h->p, h->pend_out_buf, h->pend_p.g_dep, h->pend_p.inv_g_dep, rot, ph, done,
+                                                        h->obs_seq, st, frames),
+                              "update + move"))
+            return rc;
     } else {
-        int rc = flush_pending(h, st);
-        if (rc) return rc;
-        e = antsrl_launch_move(h->p, rot, ph, done, stepping ? 1 : 0, h->obs_seq, st);
-        if (e != hipSuccess) return hip_fail(e, "move");
+        if (int rc = flush_pending(h, st)) return rc;
+        if (int rc = enqueued(antsrl_launch_move(h->p, rot, ph, done, stepping ? 1 : 0, h->obs_seq, st), "move")) return rc;
     }
     if (timed) (void)hipEventRecord(h->ev[2], st);
-    e = antsrl_launch_perceive(h->p, h->cur, obs, agent_state, reward,
-                               (stepping ? ACT_STEP : 0) | (obs ? ACT_HAS_OBS : 0) | (frames ? ACT_FRAMES : 0) |
-                                   ((obs || h->pol.pack) && h->obs_bf16 ? ACT_OBS_BF16 : 0) | // (act-only: rows in LDS, bf16)
-                                   (h->sum_live && summary_on(h) ? ACT_SUMMARY : 0),
-                               h->obs_seq, st, &h->pol, h->obs_pitch, h->prc_generic);
+    hipError_t e = antsrl_launch_perceive(h->p, h->cur, obs, agent_state, reward,
+                                          (stepping ? ACT_STEP : 0) | (obs ? ACT_HAS_OBS : 0) | (frames ? ACT_FRAMES : 0) |
+                                              ((obs || h->pol.pack) && h->obs_bf16 ? ACT_OBS_BF16 : 0) | // (act-only: rows in LDS, bf16)
+                                              (h->sum_live && summary_on(h) ? ACT_SUMMARY : 0),
+                                          h->obs_seq, st, &h->pol, h->obs_pitch, h->prc_generic);
     if (e == hipErrorNotSupported)
         return fail(ANTSRL_E_UNSUPPORTED, "a padded observation row stride and the in-loop policy exclude each other (the net reads a dense tile image)");
-    if (e != hipSuccess) return hip_fail(e, "perceive");
+    if (int rc = enqueued(e, "perceive")) return rc;
     if (summary_cadence(++h->sum_obs) && summary_on(h)) h->sum_due = true; // (enqueued by the caller: summary_refresh_due)
     return ANTSRL_OK;
+}
+
+// One observation on the single-kernel path (k_act), meta_observe's counterpart; `what`: the caller's word for hip_fail.
+static int act_observe(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *obs, float *agent_state, float *reward,
+                       uint8_t *done, bool stepping, hipStream_t st, bool timed, const char *what)
+{
+    if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
+    if (timed) (void)hipEventRecord(h->ev[2], st);
+    hipError_t e = antsrl_launch_act(h->p, rot, ph, h->cur, obs, agent_state, reward, done,
+                                     (stepping ? ACT_STEP : 0) | (obs ? ACT_HAS_OBS : 0) | (obs && h->obs_bf16 ? ACT_OBS_BF16 : 0), st);
+    if (e == hipErrorNotSupported) return bf16_unsupported();
+    return enqueued(e, what);
 }
 
 // The summary's refresh when the cadence asks for one: BEHIND the observation whose marks it may count (bits are set
@@ -672,9 +597,7 @@ static int summary_refresh_due(AntsHandle *h, hipStream_t st)
     if (!h->sum_due) return ANTSRL_OK;
     h->sum_due = false;
     h->sum_live = true;
-    hipError_t e = antsrl_launch_explored_summary(h->p, st);
-    if (e != hipSuccess) return hip_fail(e, "explored summary");
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_explored_summary(h->p, st), "explored summary");
 }
 
 static int do_step(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *obs, float *agent_state,
@@ -683,43 +606,51 @@ static int do_step(AntsHandle *h, const int8_t *rot, const int8_t *ph, float *ob
     if (ph && h->p.C != 2) // Ants.activate_pheromone hard-codes two channels, ants.py:89-96
         return fail(ANTSRL_E_INVALID, "pheromone actions need exactly 2 pheromone channels (ants.py:89-96)");
     if (h->steps_since_update > 0) h->need_full_collect = true; // dirty-cell list would be overwritten
-    if (h->p.meta) {
-        int rc = meta_observe(h, rot, ph, obs, agent_state, reward, done, true, st, timed);
-        if (rc) return rc;
-        h->steps_since_update++;
-        return ANTSRL_OK;
-    }
-    if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
-    if (timed) (void)hipEventRecord(h->ev[2], st);
-    hipError_t e = antsrl_launch_act(h->p, rot, ph, h->cur, obs, agent_state, reward, done,
-                                     ACT_STEP | (obs ? ACT_HAS_OBS : 0) | (obs && h->obs_bf16 ? ACT_OBS_BF16 : 0), st);
-    if (e == hipErrorNotSupported) return bf16_unsupported();
-    if (e != hipSuccess) return hip_fail(e, "step");
+    int rc = h->p.meta ? meta_observe(h, rot, ph, obs, agent_state, reward, done, true, st, timed)
+                       : act_observe(h, rot, ph, obs, agent_state, reward, done, true, st, timed, "step");
+    if (rc) return rc;
     h->steps_since_update++;
+    return ANTSRL_OK;
+}
+
+// The two ends of an Environment.update that antsrl_update and antsrl_update_phase share (they must stay bit-identical).
+// Scaled units, ahead of the update's first kernel: re-base the units long before u = v / f0^S can overflow fp32
+// (value-preserving), then the Walls pass of this update (walls.py:30) on the initial grid, before its deposits land.
+static int update_prepare_scaled(AntsHandle *h, hipStream_t st)
+{
+    if (h->p.g_dep < 1e-20) {
+        if (int rc = enqueued(antsrl_launch_phero_renorm(h->p, st), "pheromone renorm")) return rc;
+        h->sweeps = 0;
+        set_decay(h);
+    }
+    if (h->need_wall_clear) {
+        if (int rc = enqueued(antsrl_launch_phero_wall_clear(h->p, st), "pheromone wall clear")) return rc;
+        h->need_wall_clear = false;
+    }
+    return ANTSRL_OK;
+}
+
+// Behind the update's last kernel: Anthill.update over the whole grid when due, then the environment's timestep advances.
+// `flip`: the swept grid becomes the current one here (antsrl_update_phase has flipped in its ROCKS_PHEROMONE phase).
+static int update_close(AntsHandle *h, hipStream_t st, bool flip)
+{
+    if (h->need_full_collect) {
+        if (int rc = enqueued(antsrl_launch_collect_full(h->p, st), "anthill collect")) return rc;
+        h->need_full_collect = false;
+    }
+    if (flip) h->cur ^= 1;
+    h->steps_since_update = 0;
+    h->host_timestep++;
     return ANTSRL_OK;
 }
 
 static int do_update(AntsHandle *h, const double *jitter, hipStream_t st, bool sweep_done, bool may_defer)
 {
-    hipError_t e;
-    int frc = flush_pending(h, st); // (two updates in a row)
-    if (frc) return frc;
+    if (int rc = flush_pending(h, st)) return rc; // (two updates in a row)
     if (h->p.scaled) {
-        if (h->p.g_dep < 1e-20) { // re-base the units long before u = v / f0^S can overflow fp32
-            e = antsrl_launch_phero_renorm(h->p, st);
-            if (e != hipSuccess) return hip_fail(e, "pheromone renorm");
-            h->sweeps = 0;
-            set_decay(h);
-        }
-        if (h->need_wall_clear) { // Walls pass of this update (walls.py:30) on the initial grid,
-                                  // before this update's deposits land
-            e = antsrl_launch_phero_wall_clear(h->p, st);
-            if (e != hipSuccess) return hip_fail(e, "pheromone wall clear");
-            h->need_wall_clear = false;
-        }
+        if (int rc = update_prepare_scaled(h, st)) return rc;
     } else if (!sweep_done) {
-        e = antsrl_launch_sweep(h->p, h->cur, st);
-        if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
+        if (int rc = enqueued(antsrl_launch_sweep(h->p, h->cur, st), "pheromone sweep")) return rc;
     }
     // Deferred: with the library's own wall jitter (no caller buffer to outlive the call) and nothing that has to
     // run after the update kernel in this call, the kernel is left for the next step's k_update_move.
@@ -728,30 +659,20 @@ static int do_update(AntsHandle *h, const double *jitter, hipStream_t st, bool s
         h->pend_p = h->p;
         h->pend_out_buf = h->p.scaled ? 0 : h->cur ^ 1;
     } else {
-        e = antsrl_launch_update(h->p, jitter, h->p.scaled ? 0 : h->cur ^ 1, st);
-        if (e != hipSuccess) return hip_fail(e, "update");
+        if (int rc = enqueued(antsrl_launch_update(h->p, jitter, h->p.scaled ? 0 : h->cur ^ 1, st), "update")) return rc;
     }
     if (h->p.scaled) {
         h->sweeps++;
         set_decay(h);
     }
-    if (h->need_full_collect) {
-        e = antsrl_launch_collect_full(h->p, st);
-        if (e != hipSuccess) return hip_fail(e, "anthill collect");
-        h->need_full_collect = false;
-    }
-    if (!h->p.scaled) h->cur ^= 1;
-    h->steps_since_update = 0;
-    h->host_timestep++;
-    return ANTSRL_OK;
+    return update_close(h, st, !h->p.scaled);
 }
 
 extern "C" int antsrl_step(AntsHandle *h, const int8_t *rotation, const int8_t *phero, float *obs,
                            float *agent_state, float *reward, uint8_t *done, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
     if (!agent_state || !reward || !done) return fail(ANTSRL_E_INVALID, "agent_state, reward, done are required");
     int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, (hipStream_t)stream);
     return rc ? rc : summary_refresh_due(h, (hipStream_t)stream);
@@ -760,25 +681,17 @@ extern "C" int antsrl_step(AntsHandle *h, const int8_t *rotation, const int8_t *
 extern "C" int antsrl_observe(AntsHandle *h, float *obs, float *agent_state, float *reward, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
-    if (h->p.meta) {
-        int rc = meta_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false);
-        return rc ? rc : summary_refresh_due(h, (hipStream_t)stream);
-    }
-    if (obs && h->obs_pitch) return fail(ANTSRL_E_UNSUPPORTED, "antsrl_set_obs_row_stride needs the cell-meta path (ANTSRL_Q_CELL_META)");
-    hipError_t e = antsrl_launch_act(h->p, nullptr, nullptr, h->cur, obs, agent_state, reward, nullptr,
-                                     obs ? ACT_HAS_OBS | (h->obs_bf16 ? ACT_OBS_BF16 : 0) : 0, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return bf16_unsupported();
-    if (e != hipSuccess) return hip_fail(e, "observe");
-    return ANTSRL_OK;
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if (!h->p.meta)
+        return act_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false, "observe");
+    int rc = meta_observe(h, nullptr, nullptr, obs, agent_state, reward, nullptr, false, (hipStream_t)stream, false);
+    return rc ? rc : summary_refresh_due(h, (hipStream_t)stream);
 }
 
 extern "C" int antsrl_update(AntsHandle *h, const double *wall_jitter, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
     return do_update(h, wall_jitter, (hipStream_t)stream, false, true);
 }
 
@@ -787,42 +700,27 @@ extern "C" int antsrl_update(AntsHandle *h, const double *wall_jitter, void *str
 extern "C" int antsrl_update_phase(AntsHandle *h, int phase, const double *wall_jitter, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
+    if (int rc = handle_ready(h, MID_UPDATE_ALLOWED)) return rc; // (the phase in progress is checked below)
     if (phase < ANTSRL_PHASE_WALLS || phase > ANTSRL_PHASE_ANTHILL) return fail(ANTSRL_E_INVALID, "bad phase %d", phase);
     if (phase != h->phase_next)
         return fail(ANTSRL_E_INVALID, "antsrl_update_phase: phase %d is next, got %d (WALLS, ROCKS_PHEROMONE, ANTS, ANTHILL in order)", h->phase_next, phase);
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
+    const int out_buf = h->p.scaled ? 0 : h->cur; // (as it stands when the phase's update kernel is enqueued)
     if (phase == ANTSRL_PHASE_WALLS) { // walls.py:22-30 (update_step -1)
-        int frc = flush_pending(h, st);
-        if (frc) return frc;
+        if (int rc = flush_pending(h, st)) return rc;
         if (h->p.scaled) {
-            if (h->p.g_dep < 1e-20) { // re-base the units long before u = v / f0^S can overflow fp32 (value-preserving)
-                e = antsrl_launch_phero_renorm(h->p, st);
-                if (e != hipSuccess) return hip_fail(e, "pheromone renorm");
-                h->sweeps = 0;
-                set_decay(h);
-            }
-            if (h->need_wall_clear) {
-                e = antsrl_launch_phero_wall_clear(h->p, st);
-                if (e != hipSuccess) return hip_fail(e, "pheromone wall clear");
-                h->need_wall_clear = false;
-            }
+            if (int rc = update_prepare_scaled(h, st)) return rc;
         } else { // `phero[map] = 0` as a step of its own (the sweep of the next phase does it again, to the same effect)
-            e = antsrl_launch_phero_wall_clear(h->p, st, h->cur);
-            if (e != hipSuccess) return hip_fail(e, "pheromone wall clear");
+            if (int rc = enqueued(antsrl_launch_phero_wall_clear(h->p, st, h->cur), "pheromone wall clear")) return rc;
         }
-        e = antsrl_launch_update(h->p, wall_jitter, h->p.scaled ? 0 : h->cur, st, 1 /* UPD_WALLS */);
-        if (e != hipSuccess) return hip_fail(e, "update: walls");
+        if (int rc = enqueued(antsrl_launch_update(h->p, wall_jitter, out_buf, st, UPD_WALLS), "update: walls")) return rc;
     } else if (phase == ANTSRL_PHASE_ROCKS_PHEROMONE) { // circle_obstacles.py:32-58, pheromone.py:43-45 (update_step 0)
-        e = antsrl_launch_update(h->p, nullptr, h->p.scaled ? 0 : h->cur, st, 2 /* UPD_ROCKS */);
-        if (e != hipSuccess) return hip_fail(e, "update: rocks");
+        if (int rc = enqueued(antsrl_launch_update(h->p, nullptr, out_buf, st, UPD_ROCKS), "update: rocks")) return rc;
         if (h->p.scaled) { // the conceptual sweep: readers materialise one more decay from here on; the deposit of the
             h->sweeps++;   // ANTS phase lands "after the sweep of this update" = at the new g_now
             set_decay(h);
         } else {
-            e = antsrl_launch_sweep(h->p, h->cur, st);
-            if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
+            if (int rc = enqueued(antsrl_launch_sweep(h->p, h->cur, st), "pheromone sweep")) return rc;
             h->cur ^= 1; // readers (and the deposit) see the swept grid from here on
         }
     } else if (phase == ANTSRL_PHASE_ANTS) { // ants.py:123-130 (update_step 999)
@@ -831,18 +729,10 @@ extern "C" int antsrl_update_phase(AntsHandle *h, int phase, const double *wall_
             kp.g_dep = kp.g_now;
             kp.inv_g_dep = 1.0 / kp.g_dep;
         }
-        e = antsrl_launch_update(kp, nullptr, kp.scaled ? 0 : h->cur, st, 4 /* UPD_ANTS */);
-        if (e != hipSuccess) return hip_fail(e, "update: ants");
+        if (int rc = enqueued(antsrl_launch_update(kp, nullptr, out_buf, st, UPD_ANTS), "update: ants")) return rc;
     } else { // anthill.py:41-46 (update_step 1000); the environment's timestep advances here
-        e = antsrl_launch_update(h->p, nullptr, h->p.scaled ? 0 : h->cur, st, 8 /* UPD_ANTHILL */);
-        if (e != hipSuccess) return hip_fail(e, "update: anthill");
-        if (h->need_full_collect) {
-            e = antsrl_launch_collect_full(h->p, st);
-            if (e != hipSuccess) return hip_fail(e, "anthill collect");
-            h->need_full_collect = false;
-        }
-        h->steps_since_update = 0;
-        h->host_timestep++;
+        if (int rc = enqueued(antsrl_launch_update(h->p, nullptr, out_buf, st, UPD_ANTHILL), "update: anthill")) return rc;
+        if (int rc = update_close(h, st, false)) return rc;
     }
     h->phase_next = (phase + 1) % 4;
     return ANTSRL_OK;
@@ -851,15 +741,11 @@ extern "C" int antsrl_update_phase(AntsHandle *h, int phase, const double *wall_
 extern "C" int antsrl_refresh_explored_summary(AntsHandle *h, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
     if (!summary_on(h)) return ANTSRL_OK;
-    int frc = flush_pending(h, (hipStream_t)stream); // (as antsrl_read_state: behind a deferred update)
-    if (frc) return frc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc; // (as antsrl_read_state: behind a deferred update)
     h->sum_live = true;
-    hipError_t e = antsrl_launch_explored_summary(h->p, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "explored summary");
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_explored_summary(h->p, (hipStream_t)stream), "explored summary");
 }
 
 extern "C" int antsrl_flush(AntsHandle *h, void *stream)
@@ -873,8 +759,7 @@ extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const i
                                   uint8_t *done, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
     if (!agent_state || !reward || !done) return fail(ANTSRL_E_INVALID, "agent_state, reward, done are required");
     hipStream_t st = (hipStream_t)stream;
     const bool timed = h->ev_armed;
@@ -885,20 +770,16 @@ extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const i
     // in phero[cur] — this sweep's input — with k_update_move, so the sweep follows the step's kernels (the perception
     // reads phero[cur], too, and nothing of the step reads the sweep's output).
     const bool sweep_late = !h->p.scaled && h->pend_update;
-    if (!h->p.scaled && !sweep_late) {
-        hipError_t e = antsrl_launch_sweep(h->p, h->cur, st);
-        if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
-    }
+    if (!h->p.scaled && !sweep_late)
+        if (int rc = enqueued(antsrl_launch_sweep(h->p, h->cur, st), "pheromone sweep")) return rc;
     if (timed) (void)hipEventRecord(h->ev[1], st);
     int rc = do_step(h, rotation, phero, obs, agent_state, reward, done, st, timed);
     if (rc) return rc;
     if (timed) (void)hipEventRecord(h->ev[3], st);
     rc = summary_refresh_due(h, st);
     if (rc) return rc;
-    if (sweep_late) {
-        hipError_t e = antsrl_launch_sweep(h->p, h->cur, st);
-        if (e != hipSuccess) return hip_fail(e, "pheromone sweep");
-    }
+    if (sweep_late) rc = enqueued(antsrl_launch_sweep(h->p, h->cur, st), "pheromone sweep");
+    if (rc) return rc;
     const bool was_done = h->host_timestep == h->cfg.max_time; // RL_api.py:200, same for every env
     const bool regen = was_done && h->has_gen && h->gen.auto_reset;
     rc = do_update(h, wall_jitter, st, true, !regen);
@@ -941,9 +822,7 @@ extern "C" int antsrl_bench_copy(void *dst, const void *src, size_t bytes, void 
 {
     if (!dst || !src || (bytes & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15))
         return fail(ANTSRL_E_INVALID, "bench_copy: 16-byte aligned pointers and a multiple of 16 bytes");
-    hipError_t e = antsrl_launch_copy16(dst, src, bytes, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "bench_copy");
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_copy16(dst, src, bytes, (hipStream_t)stream), "bench_copy");
 }
 
 extern "C" int antsrl_set_timing_events(AntsHandle *h, void *const *events)
@@ -958,19 +837,12 @@ extern "C" int antsrl_set_timing_events(AntsHandle *h, void *const *events)
 extern "C" int antsrl_set_activation(AntsHandle *h, const float *act, double new_deposit_strength, void *stream)
 {
     if (!h || !act) return fail(ANTSRL_E_INVALID, "NULL handle or act");
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
-    int frc = flush_pending(h, (hipStream_t)stream); // (the deferred update deposits with the activation as it was)
-    if (frc) return frc;
-    hipError_t e = antsrl_launch_set_activation(h->p, act, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "set_activation");
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc; // (the deferred update deposits with the activation as it was)
+    if (int rc = enqueued(antsrl_launch_set_activation(h->p, act, (hipStream_t)stream), "set_activation")) return rc;
     if (new_deposit_strength > 0) h->p.deposit_strength = new_deposit_strength;
     return ANTSRL_OK;
 }
-
-hipError_t antsrl_launch_policy(const float *obs, const float *agent_state, const float *w1, const float *b1,
-                                const float *w2, const float *b2, const float *w3, const float *b3, int8_t *rot,
-                                int8_t *ph, float *logits, int M, int F, hipStream_t st, bool obs_bf16);
 
 extern "C" int antsrl_policy_mlp(AntsHandle *h, const float *obs, const float *agent_state, int64_t n_ants,
                                  int32_t n_features, const float *w1, const float *b1, const float *w2,
@@ -984,10 +856,9 @@ extern "C" int antsrl_policy_mlp(AntsHandle *h, const float *obs, const float *a
         return fail(ANTSRL_E_INVALID, "policy_mlp: w3/b3 go together and are needed for a pheromone output");
     if (n_ants < 1 || n_ants > 0x7fffffff || n_features < 1 || n_features + 2 > 1024)
         return fail(ANTSRL_E_INVALID, "policy_mlp: n_ants >= 1 and 1 <= n_features <= 1022");
-    hipError_t e = antsrl_launch_policy(obs, agent_state, w1, b1, w2, b2, w3, b3, rotation, pheromone, logits,
-                                        (int)n_ants, n_features, (hipStream_t)stream, h && h->obs_bf16);
-    if (e != hipSuccess) return hip_fail(e, "policy_mlp");
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_policy(obs, agent_state, w1, b1, w2, b2, w3, b3, rotation, pheromone, logits, (int)n_ants,
+                                         n_features, (hipStream_t)stream, h && h->obs_bf16),
+                    "policy_mlp");
 }
 
 extern "C" int antsrl_set_inloop_policy(AntsHandle *h, int32_t n_features, const float *w1, const float *b1, const float *w2,
@@ -1011,8 +882,9 @@ extern "C" int antsrl_set_inloop_policy(AntsHandle *h, int32_t n_features, const
     if (h->obs_pitch != 0 && h->obs_pitch != (uint32_t)(h->p.PP * h->p.K))
         return fail(ANTSRL_E_UNSUPPORTED, "the in-loop policy and a padded observation row stride exclude each other (the net reads a "
                                           "dense tile image): antsrl_set_obs_row_stride(h, 0) first");
-    hipError_t e = antsrl_launch_policy_pack(h->p.s.pol_pack, w1, b1, w2, b2, w3, b3, n_features, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "inloop_policy pack");
+    if (int rc = enqueued(antsrl_launch_policy_pack(h->p.s.pol_pack, w1, b1, w2, b2, w3, b3, n_features, (hipStream_t)stream),
+                          "inloop_policy pack"))
+        return rc;
     h->pol.pack = h->p.s.pol_pack;
     h->pol.rot = rotation_next;
     h->pol.ph = pheromone_next;
@@ -1054,206 +926,18 @@ extern "C" int antsrl_state_bytes(const AntsHandle *h, int which, size_t *bytes)
 extern "C" int antsrl_perceptive_field(AntsHandle *h, uint8_t *dst, void *stream)
 {
     if (!h || !dst) return fail(ANTSRL_E_INVALID, "NULL handle or dst");
-    if (!h->is_reset) return not_reset(h);
+    if (int rc = handle_ready(h, MID_UPDATE_ALLOWED)) return rc;
     // (no flush: a DEFERRED update has not touched the positions yet — the field is the last observation's, as in the
     //  reference, where RLApi.observation computes it; behind an update that has run it is the moved ants')
-    hipError_t e = antsrl_launch_perceptive_field(h->p, dst, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "perceptive_field");
-    return ANTSRL_OK;
-}
-
-// ---- the episode recorder (include/antsrl.h, "The episode recorder"; kernels in antsrl_recorder.hip) ------------------
-static int recorder_layout(const char *who, const AntsHandle *h, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
-                           RecorderLayout *L)
-{
-    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
-    if (n_sel < 1 || n_sel > ANTSRL_RECORDER_MAX_ENVS)
-        return fail(ANTSRL_E_INVALID, "%s: n_sel %d is not in 1..%d", who, n_sel, ANTSRL_RECORDER_MAX_ENVS);
-    if (max_frames < 1) return fail(ANTSRL_E_INVALID, "%s: max_frames must be >= 1 (%d)", who, max_frames);
-    const bool keeps_map = h->cfg.reward_kind == ANTSRL_REWARD_EXPLORATION || h->cfg.reward_kind == ANTSRL_REWARD_ALL;
-    *L = antsrl_recorder_layout(n_sel, h->p.N, h->p.R, h->p.C, (size_t)h->p.W * h->p.H, with_heatmap && keeps_map ? 1 : 0);
-    return ANTSRL_OK;
-}
-
-// every argument of _begin / _frame (has_frame), before any HIP call
-static int recorder_check(const char *who, const AntsHandle *h, const void *block, const int32_t *env_indices, int32_t n_sel,
-                          int32_t max_frames, int32_t with_heatmap, bool has_frame, int32_t frame, RecorderLayout *L, RecorderSel *sel)
-{
-    int rc = recorder_layout(who, h, n_sel, max_frames, with_heatmap, L);
-    if (rc) return rc;
-    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
-    if ((uintptr_t)block & 15) return fail(ANTSRL_E_INVALID, "%s: block must be 16-byte aligned", who);
-    if (!env_indices) return fail(ANTSRL_E_INVALID, "%s: NULL env_indices", who);
-    memset(sel, 0, sizeof(*sel));
-    for (int s = 0; s < n_sel; ++s) {
-        const int32_t e = env_indices[s];
-        if (e < 0 || e >= h->p.E)
-            return fail(ANTSRL_E_INVALID, "%s: env_indices[%d] = %d is not in [0, n_envs = %d)", who, s, e, h->p.E);
-        for (int t = 0; t < s; ++t)
-            if (sel->env[t] == e) return fail(ANTSRL_E_INVALID, "%s: env_indices[%d] repeats environment %d", who, s, e);
-        sel->env[s] = e;
-    }
-    if (has_frame && (frame < 0 || frame >= max_frames))
-        return fail(ANTSRL_E_INVALID, "%s: frame %d is not in [0, max_frames = %d)", who, frame, max_frames);
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_recorder_sizes(const AntsHandle *h, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
-                                     size_t *static_bytes, size_t *frame_bytes, size_t *bytes)
-{
-    RecorderLayout L;
-    int rc = recorder_layout("recorder_sizes", h, n_sel, max_frames, with_heatmap, &L);
-    if (rc) return rc;
-    if (static_bytes) *static_bytes = L.static_bytes;
-    if (frame_bytes) *frame_bytes = L.frame_bytes;
-    if (bytes) *bytes = L.static_bytes + (size_t)max_frames * L.frame_bytes;
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_recorder_begin(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
-                                     int32_t max_frames, int32_t with_heatmap, void *stream)
-{
-    RecorderLayout L;
-    RecorderSel sel;
-    int rc = recorder_check("recorder_begin", h, block, env_indices, n_sel, max_frames, with_heatmap, false, 0, &L, &sel);
-    if (rc) return rc;
-    rc = flush_pending(h, (hipStream_t)stream); // (as antsrl_read_state: the log holds the state after the update)
-    if (rc) return rc;
-    hipError_t e = antsrl_launch_record_static(h->p, L, sel, (unsigned char *)block, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "recorder_begin");
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_recorder_frame(AntsHandle *h, void *block, const int32_t *env_indices, int32_t n_sel,
-                                     int32_t max_frames, int32_t with_heatmap, int32_t frame, void *stream)
-{
-    RecorderLayout L;
-    RecorderSel sel;
-    int rc = recorder_check("recorder_frame", h, block, env_indices, n_sel, max_frames, with_heatmap, true, frame, &L, &sel);
-    if (rc) return rc;
-    rc = flush_pending(h, (hipStream_t)stream); // a frame is the state AFTER Environment.update (main.py:138)
-    if (rc) return rc;
-    hipError_t e = antsrl_launch_record_frame(h->p, h->cur, L, sel,
-                                              (unsigned char *)block + L.static_bytes + (size_t)frame * L.frame_bytes,
-                                              (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "recorder_frame");
-    return ANTSRL_OK;
-}
-
-// ---- the colony statistics (include/antsrl.h, "The colony statistics"; kernels in antsrl_stats.hip) -------------------
-static int stats_layout(const char *who, const AntsHandle *h, int32_t max_rows, StatsLayout *L)
-{
-    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
-    if (max_rows < 1) return fail(ANTSRL_E_INVALID, "%s: max_rows must be >= 1 (%d)", who, max_rows);
-    const bool keeps_map = h->cfg.reward_kind == ANTSRL_REWARD_EXPLORATION || h->cfg.reward_kind == ANTSRL_REWARD_ALL;
-    *L = antsrl_stats_layout(h->p.E, h->p.C, (size_t)h->p.W * h->p.H, keeps_map ? 1 : 0);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_stats_sizes(const AntsHandle *h, int32_t max_rows, size_t *row_bytes, size_t *scratch_bytes, size_t *bytes)
-{
-    StatsLayout L;
-    int rc = stats_layout("stats_sizes", h, max_rows, &L);
-    if (rc) return rc;
-    if (row_bytes) *row_bytes = 8 * L.row_words;
-    if (scratch_bytes) *scratch_bytes = 8 * L.scratch_words;
-    if (bytes) *bytes = 8 * ((size_t)max_rows * L.row_words + L.scratch_words);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_stats_row(AntsHandle *h, void *block, int32_t max_rows, int32_t row, void *stream)
-{
-    const char *who = "stats_row";
-    StatsLayout L;
-    int rc = stats_layout(who, h, max_rows, &L);
-    if (rc) return rc;
-    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
-    if ((uintptr_t)block & 7) return fail(ANTSRL_E_INVALID, "%s: block must be 8-byte aligned", who);
-    if (row < 0 || row >= max_rows) return fail(ANTSRL_E_INVALID, "%s: row %d is not in [0, max_rows = %d)", who, row, max_rows);
-    if (!h->is_reset) return not_reset(h);
-    if (h->phase_next) return mid_update(h);
-    rc = flush_pending(h, (hipStream_t)stream); // a row is the state AFTER Environment.update, as a recorded frame is
-    if (rc) return rc;
-    double *words = (double *)block;
-    hipError_t e = antsrl_launch_stats_row(h->p, h->cur, L, words + (size_t)row * L.row_words,
-                                           words + (size_t)max_rows * L.row_words, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, who);
-    return ANTSRL_OK;
-}
-
-// ---- the episode renderer (include/antsrl.h, "The episode renderer"; kernels in antsrl_render.hip) --------------------
-static int render_opts(const char *who, const AntsHandle *h, int32_t n_sel, const AntsRenderOpts *o)
-{
-    if (!h) return fail(ANTSRL_E_INVALID, "%s: NULL handle", who);
-    if (!o) return fail(ANTSRL_E_INVALID, "%s: NULL opts", who);
-    if (n_sel < 1 || n_sel > ANTSRL_RECORDER_MAX_ENVS)
-        return fail(ANTSRL_E_INVALID, "%s: n_sel %d is not in 1..%d", who, n_sel, ANTSRL_RECORDER_MAX_ENVS);
-    if (o->zoom < 1 || o->zoom > ANTSRL_RENDER_MAX_ZOOM)
-        return fail(ANTSRL_E_INVALID, "%s: zoom %d is not in 1..%d", who, o->zoom, ANTSRL_RENDER_MAX_ZOOM);
-    if (o->ant_radius < 0 || o->ant_radius > ANTSRL_RENDER_MAX_ANT_RADIUS)
-        return fail(ANTSRL_E_INVALID, "%s: ant_radius %d is not in 0..%d", who, o->ant_radius, ANTSRL_RENDER_MAX_ANT_RADIUS);
-    if (!(o->phero_max_val > 0.0)) return fail(ANTSRL_E_INVALID, "%s: phero_max_val must be > 0 (%g)", who, o->phero_max_val);
-    if (o->view_mask & ~ANTSRL_RENDER_VIEW_ALL)
-        return fail(ANTSRL_E_INVALID, "%s: view_mask 0x%x has bits outside 0x%x", who, (unsigned)o->view_mask, ANTSRL_RENDER_VIEW_ALL);
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_render_sizes(const AntsHandle *h, int32_t n_sel, const AntsRenderOpts *o, size_t *frame_env_bytes,
-                                   size_t *scratch_bytes_per_frame)
-{
-    int rc = render_opts("render_sizes", h, n_sel, o);
-    if (rc) return rc;
-    const size_t W = (size_t)h->p.W, H = (size_t)h->p.H, Z = (size_t)o->zoom;
-    if (frame_env_bytes) *frame_env_bytes = o->layer_only ? 4 * W * H : 3 * (W * Z) * (H * Z);
-    if (scratch_bytes_per_frame) *scratch_bytes_per_frame = 4 * (size_t)n_sel;
-    return ANTSRL_OK;
-}
-
-extern "C" int antsrl_render_frames(AntsHandle *h, const void *block, int32_t n_sel, int32_t max_frames, int32_t with_heatmap,
-                                    int32_t first, int32_t count, const AntsRenderOpts *o, void *out, void *scratch, void *stream)
-{
-    const char *who = "render_frames";
-    int rc = render_opts(who, h, n_sel, o);
-    if (rc) return rc;
-    RenderArgs a;
-    memset(&a, 0, sizeof(a));
-    rc = recorder_layout(who, h, n_sel, max_frames, with_heatmap, &a.L);
-    if (rc) return rc;
-    if (!block) return fail(ANTSRL_E_INVALID, "%s: NULL block", who);
-    if (!out) return fail(ANTSRL_E_INVALID, "%s: NULL out", who);
-    if (!scratch) return fail(ANTSRL_E_INVALID, "%s: NULL scratch", who);
-    if ((uintptr_t)block & 15) return fail(ANTSRL_E_INVALID, "%s: block must be 16-byte aligned", who);
-    if ((uintptr_t)out & 15) return fail(ANTSRL_E_INVALID, "%s: out must be 16-byte aligned", who);
-    if ((uintptr_t)scratch & 15) return fail(ANTSRL_E_INVALID, "%s: scratch must be 16-byte aligned", who);
-    if (first < 0 || count < 1 || (long long)first + count > max_frames)
-        return fail(ANTSRL_E_INVALID, "%s: frames %d .. %d + %d are not inside [0, max_frames = %d)", who, first, first, count, max_frames);
-    const size_t groups = o->layer_only ? render_layer_groups(a.L.G) : render_tiles(h->p.W, h->p.H, o->zoom);
-    if (count > 65535 || groups * (size_t)n_sel * (size_t)count >= ANTSRL_RENDER_MAX_GROUPS)
-        return fail(ANTSRL_E_INVALID, "%s: count %d is past the launch limits (65535 frames, %zu workgroups per frame of 2^24): split the call",
-                    who, count, groups * (size_t)n_sel);
-    if (!h->is_reset) return not_reset(h); // (the block was recorded from this handle)
-    a.block = (const unsigned char *)block;
-    a.out = (unsigned char *)out;
-    a.fmax = (int32_t *)scratch;
-    a.W = h->p.W; a.H = h->p.H; a.Z = o->zoom; a.TY = render_ty(o->zoom); a.view = o->view_mask; a.ra = o->ant_radius; a.first = first; a.count = count;
-    a.phero_den = o->phero_max_val + 0.0001;
-    memcpy(a.col, o->phero_colors, sizeof(a.col));
-    hipError_t e = antsrl_launch_render(a, o->layer_only != 0, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, who);
-    return ANTSRL_OK;
+    return enqueued(antsrl_launch_perceptive_field(h->p, dst, (hipStream_t)stream), "perceptive_field");
 }
 
 extern "C" int antsrl_read_state(AntsHandle *h, int which, void *dst, void *stream)
 {
     if (!h || !dst) return fail(ANTSRL_E_INVALID, "NULL handle or dst");
-    if (!h->is_reset) return not_reset(h);
+    if (int rc = handle_ready(h, MID_UPDATE_ALLOWED)) return rc;
     if (which < 0 || which >= ANTSRL_S_COUNT_) return fail(ANTSRL_E_INVALID, "bad state selector %d", which);
     if (state_bytes(h, which) == 0) return ANTSRL_OK;
-    int frc = flush_pending(h, (hipStream_t)stream);
-    if (frc) return frc;
-    hipError_t e = antsrl_launch_read_state(h->p, which, h->cur, dst, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "read_state");
-    return ANTSRL_OK;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc;
+    return enqueued(antsrl_launch_read_state(h->p, which, h->cur, dst, (hipStream_t)stream), "read_state");
 }

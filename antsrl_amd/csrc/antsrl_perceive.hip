@@ -16,6 +16,7 @@
 //
 // No MFMA: nothing on this path is a dense contraction.  Host launchers at the end.
 #include "antsrl_util.h"
+#include "antsrl_launch.h"
 #include "antsrl_flush.h"
 #include "antsrl_update_one.h"
 #include "antsrl_explored.h"

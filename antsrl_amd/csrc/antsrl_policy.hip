@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "antsrl_device.h"
 #include "antsrl_lds_optin.h"
+#include "antsrl_launch.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

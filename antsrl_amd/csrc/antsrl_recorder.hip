@@ -1,7 +1,7 @@
 // antsrl_recorder.hip — the episode recorder's kernels (include/antsrl.h, "The episode recorder"; antsrl_recorder.h holds
 // the block's layout).  What the replay viewer needs of the chosen environments — Environment.save_state's visualisation
 // copies (environment.py:36-40): uint8 grids and the ants — goes into a device-resident frame log, one launch per step,
-// nothing read back.  The C-ABI entries are in antsrl_capi.hip (they need the handle and its deferred update).
+// nothing read back.  The C-ABI entries are in antsrl_logapi.hip.
 //
 //   k_record_static   once per recorded episode: anthill_xyr, the rocks' radius and weight, the walls
 //   k_record_frame    once per recorded step: timestep, anthill_food, rock centres, the ants, and the pheromone / food /

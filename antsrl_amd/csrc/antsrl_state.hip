@@ -1,6 +1,7 @@
 // antsrl_state.hip — reset, device-side episode generator, activation, state read-out (not on the hot
 // path), launchers.
 #include "antsrl_util.h"
+#include "antsrl_launch.h"
 #include "antsrl_cellread.h"
 
 // ===================================================================================

@@ -1,8 +1,7 @@
 // antsrl_stats.hip — the colony statistics' kernels (include/antsrl.h, "The colony statistics"; antsrl_stats.h holds the
 // block's layout and the order of the sums).  What a training run reports of the task itself — food at the anthill, on the
 // map and in the mandibles, explored cells, pheromone on the map — as one row of 7 + 2 C words per environment, reduced
-// on the device in two launches, nothing read back.  The C-ABI entries are in antsrl_capi.hip (they need the handle and its
-// deferred update).
+// on the device in two launches, nothing read back.  The C-ABI entries are in antsrl_logapi.hip.
 //
 //   k_stats_cells   one workgroup of 256 per (segment of 4096 canonical cells, environment): every cell's values once
 //                   (antsrl_cellread.h: one 16-byte load per cell on the interleaved records), the segment's partials

@@ -1,6 +1,7 @@
 // antsrl_sweep.hip — pheromone sweeps: k_sweep0 (radius 0, streaming), k_sweep_march (radius 1..3,
 // register-marching stencil, separable form for rank-1 filters), the wall clear / re-basing passes of the scaled representation, launchers.
 #include "antsrl_util.h"
+#include "antsrl_launch.h"
 
 // ===================================================================================
 // Pheromone sweep — Walls zeroing (walls.py:30) + Pheromone.update (pheromone.py:43-45)

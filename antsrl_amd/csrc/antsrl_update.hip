@@ -1,6 +1,7 @@
 // antsrl_update.hip — Environment.update minus the pheromone sweep (environment.py:42-47): k_update
 // (per-phase loops, any N), k_update_one (one ant per thread, N <= 1024), k_collect_full, launchers.
 #include "antsrl_util.h"
+#include "antsrl_launch.h"
 #include "antsrl_update_env.h"
 #include "antsrl_update_one.h"
 

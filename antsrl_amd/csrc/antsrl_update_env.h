@@ -2,6 +2,7 @@
 // (antsrl_update.hip); k_act sizes its LDS union with update_scratch_bytes() (antsrl_act.hip).
 #pragma once
 #include "antsrl_util.h"
+#include "antsrl_launch.h" // UPD_*
 
 // ===================================================================================
 // k_update — Environment.update minus the pheromone sweep (environment.py:42-47):
@@ -35,11 +36,6 @@ __device__ __forceinline__ uint32_t block_excl_scan_flag(bool flag, uint32_t *wa
 // update_step() order (environment.py:43-47); the pheromone's own step-0 update is the host's sweep launch / scaled-unit
 // bookkeeping.  The environment's timestep advances with the LAST phase (the jitter of the first one is keyed on
 // timestep + 1 either way).
-#define UPD_WALLS 1
-#define UPD_ROCKS 2
-#define UPD_ANTS 4
-#define UPD_ANTHILL 8
-#define UPD_ALL 15
 template <int C>
 __device__ __forceinline__ void update_env(const KP &p, const int e, const double *__restrict__ wall_jitter,
                                            const int out_buf, unsigned char *smem, const int phases = UPD_ALL)

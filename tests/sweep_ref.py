@@ -86,7 +86,7 @@ def apriori_rtol(plan):
 
 # ------------------------------------------------------------------------------------------------ the plan
 def filter_is_rank1(filt):
-    """antsrl_capi.hip:266-293: F == u v^T around the largest tap, to 1e-15 of it."""
+    """fill_kp (antsrl_capi.hip), the rank-1 test: F == u v^T around the largest tap, to 1e-15 of it."""
     F = np.asarray(filt, dtype=np.float64)
     S = F.shape[0]
     if S == 1:
@@ -188,7 +188,7 @@ def exposed(defect, plan):
 
 
 def wall_words(walls):
-    """uint8 [E, W, H] -> the device's bitmap: (G + 31) / 32 words per environment (antsrl_capi.hip:225), cell g in bit
+    """uint8 [E, W, H] -> the device's bitmap: (G + 31) / 32 words per environment (fill_kp in antsrl_capi.hip), cell g in bit
     g & 31 of word g >> 5 (test_bit), environment e's words at e * words."""
     E = walls.shape[0]
     G = walls[0].size

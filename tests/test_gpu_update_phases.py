@@ -70,6 +70,57 @@ def test_four_phases_are_one_update(mode, inject):
     assert int(a.query(cm.Q_TIMESTEP)) == int(b.query(cm.Q_TIMESTEP)) == 10
 
 
+@pytest.mark.parametrize("mode", ["scaled", "diffuse3x3"])
+def test_between_two_phases_state_changes_are_refused_and_reads_are_served(mode):
+    """The complete table at the smallest shape: behind PHASE_WALLS every entry that changes the state is refused with "in
+    progress", every read succeeds; behind the three remaining phases every entry works again and the state is that of a
+    twin that called update."""
+    import torch
+    from antsrl_amd import _lib, config as cm
+    from antsrl_amd.batched import BatchedAntsEnv
+    from antsrl_amd.synth import random_actions, synth_init
+    kw = dict(deposit_strength=256.0)
+    if _filters()[mode] is not None:
+        kw["filt"] = _filters()[mode]
+    cfg = cm.make_cfg(3, 8, 16, 12, **kw)
+    init = synth_init(cfg, seed=5, n_food_discs=2, food_rmin=1, food_rmax=2)
+    a, b = BatchedAntsEnv(cfg), BatchedAntsEnv(cfg)
+    assert bool(b.query(cm.Q_SCALED_UNITS)) == (mode == "scaled")
+    rot, ph = random_actions(cfg, 3, seed=6)
+    act = torch.ones((cfg.n_envs, cfg.n_ants, cfg.n_phero), dtype=torch.float32, device=b.device)
+    changes = {"step": lambda e: e.step(rot[1], ph[1]), "observe": lambda e: e.observe(), "update": lambda e: e.update(None),
+               "step_update": lambda e: e.step_update(rot[1], ph[1]), "set_activation": lambda e: e.set_activation(act),
+               "refresh_explored_summary": lambda e: e.refresh_explored_summary()}
+    reads = {"read_state": lambda e: e.read_state(cm.S_PHERO), "perceptive_field": lambda e: e.perceptive_field(),
+             "flush": lambda e: e.flush(), "query": lambda e: e.query(cm.Q_TIMESTEP)}
+    for e in (a, b):
+        e.reset(init)
+        e.step(rot[0], ph[0])
+    a.update(None)
+    b.update_phase(cm.PHASE_WALLS)
+    for name, call in changes.items():
+        with pytest.raises(_lib.AntsrlError, match="in progress"):
+            call(b)
+    for name, call in reads.items():
+        call(b)
+    assert int(b.query(cm.Q_TIMESTEP)) == int(a.query(cm.Q_TIMESTEP)) - 1
+    for phase in (cm.PHASE_ROCKS_PHEROMONE, cm.PHASE_ANTS, cm.PHASE_ANTHILL):
+        b.update_phase(phase)
+    for name in STATE:
+        assert torch.equal(a.read_state(getattr(cm, name)), b.read_state(getattr(cm, name))), "%s (%s)" % (name, mode)
+    for name, call in list(changes.items()) + list(reads.items()):  # every entry works again, on both alike
+        for x, y in zip(_tensors(call(a)), _tensors(call(b))):
+            assert torch.equal(x, y), "%s (%s)" % (name, mode)
+    for name in STATE:
+        assert torch.equal(a.read_state(getattr(cm, name)), b.read_state(getattr(cm, name))), "%s at the end (%s)" % (name, mode)
+    assert int(a.query(cm.Q_TIMESTEP)) == int(b.query(cm.Q_TIMESTEP)) == 4
+
+
+def _tensors(out):
+    import torch
+    return [t for t in (out if isinstance(out, tuple) else (out,)) if isinstance(t, torch.Tensor)]
+
+
 @pytest.mark.parametrize("tag", ["scaled", "diffuse"])
 def test_host_objects_between_the_worlds_objects_see_what_the_references_saw(tag):
     from antsrl_amd.generator import EnvironmentGenerator
