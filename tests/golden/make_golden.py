@@ -21,6 +21,15 @@ Fixture layout (np.savez_compressed):
     ants[T,N,3] prev[T,N,2] holding[T,N] mandibles[T,N] activation[T,N,C] reward_state[T,N]
     food[T,W,H] phero[T,C,W,H] explored[T,W,H] anthill_food[T] rock_centers[T,R,2] timestep[T]
   after step / observe ops:  obs[T,N,P,P,K] agent_state[T,N,2] reward[T,N] done[T]
+
+Long runs (``grid_every``) thin the four big arrays: ``grids[T]`` marks the ops at which food, phero,
+explored and obs were kept, and those arrays then hold one row per marked op, in op order (G rows
+instead of T).  Everything else stays per op.  A file without ``grids`` keeps them at every op.
+
+``place_ants`` / ``place_rocks`` set data on the reference's own objects after ``generate``: ant
+positions anywhere on the grid (borders, corners, wall cells), rocks of any centre, radius and weight.
+``init_*`` is recorded after them; such a file also carries wall_density / rich_food / placed_* in its
+meta, so that a reader can tell which part of the initial state the generator's streams still explain.
 """
 import json
 import os
@@ -96,7 +105,7 @@ def make_reward(kind, weights):
 def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wall_density=0.0,
                  n_rocks=0, reward="exploration", weights=None, float_activation=False,
                  filt=None, max_time=2000, script=None, food_extra=True, none_actions=False,
-                 store_every=1, rich_food=False):
+                 store_every=1, rich_food=False, place_ants=None, place_rocks=None, grid_every=None):
     rng = np.random.default_rng(1000 + seed)
     weights = weights or {}
     old_filter = ref_pheromone.DIFFUSE_FILTER
@@ -117,7 +126,23 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
         env = gen.generate(api)
         ants = api.ants
         rocks = None
-        if n_rocks > 0:
+        if place_ants is not None:
+            # hook: positions anywhere on the grid.  Ants.__init__ (ants.py:27-30) and All_Rewards.setup
+            # (reward_custom.py:77) have run on the generator's positions: redo what they derived from them.
+            xyt = np.asarray(place_ants(rng, w, h, env), dtype=float)
+            assert xyt.shape == (n_ants, 3)
+            ants.ants[:] = xyt
+            ants.warp_xy()
+            ants.prev_ants = ants.ants.copy()
+            if hasattr(api.reward, "previous_dist"):
+                api.reward.previous_dist = api.reward.compute_distance(ants.x, ants.y)
+        if n_rocks > 0 and place_rocks is not None:
+            # hook: centres, radii and weights of the caller's choosing, float64 [n_rocks, 4]
+            rk = np.asarray(place_rocks(rng, w, h, env), dtype=float)
+            assert rk.shape == (n_rocks, 4)
+            rocks = CircleObstacles(env, centers=rk[:, :2].copy(), radiuses=rk[:, 2].copy(), weights=rk[:, 3].copy())
+            api.perceived_objects.append(rocks)
+        elif n_rocks > 0:
             # generator's rock branch raises NameError (environment_generator.py:83-84):
             # build the object directly, near the anthill so ants collide with it.
             centers = np.stack([ax + rng.uniform(-12, 12, n_rocks), ay + rng.uniform(-12, 12, n_rocks)], 1)
@@ -143,6 +168,9 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
                     carry=api.carry_speed_reduction, backward=api.backward_speed_reduction,
                     max_hold=float(ants.max_hold), max_val=float(pheros[0].max_val),
                     reward_threshold=api.reward_threshold, seed=seed)
+        if place_ants is not None or place_rocks is not None or grid_every is not None:
+            meta.update(wall_density=wall_density, rich_food=bool(rich_food), food_extra=bool(food_extra),
+                        placed_ants=place_ants is not None, placed_rocks=place_rocks is not None)
         rec = dict(
             init_ants_xyt=ants.ants.copy(), init_seed=ants.seed.copy(), init_walls=walls.map.copy(),
             init_food=food.qte.copy(), init_anthill_xyr=np.array([anthill.x, anthill.y, anthill.radius]),
@@ -156,6 +184,11 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
             for _ in range(steps):
                 script += [OP_STEP, OP_UPDATE]
         T = len(script)
+        # ops at which the grids and the observation are kept: both ops of every grid_every-th step and of the last
+        grids = np.ones(T, bool) if grid_every is None else np.array(
+            [(t % (2 * grid_every) in (0, 1)) or t >= T - 2 for t in range(T)])
+        row = np.cumsum(grids) - 1  # op -> row of the thinned arrays
+        G = int(grids.sum())
         P = api.perception_coords.shape[0]
         K = len(api.perceived_objects)
         R = n_rocks
@@ -165,13 +198,16 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
                  ants=np.zeros((T, n_ants, 3)), prev=np.zeros((T, n_ants, 2)), holding=np.zeros((T, n_ants)),
                  mandibles=np.zeros((T, n_ants), np.uint8), activation=np.zeros((T, n_ants, n_phero)),
                  reward_state=np.zeros((T, n_ants), np.uint8),
-                 food=np.zeros((T, w, h), np.float32), phero=np.zeros((T, n_phero, w, h)),
-                 explored=np.zeros((T, w, h), np.uint8), anthill_food=np.zeros(T),
+                 food=np.zeros((G, w, h), np.float32), phero=np.zeros((G, n_phero, w, h)),
+                 explored=np.zeros((G, w, h), np.uint8), anthill_food=np.zeros(T),
                  rock_centers=np.zeros((T, R, 2)), timestep=np.zeros(T, np.int32),
-                 obs=np.zeros((T, n_ants, P, P, K)), agent_state=np.zeros((T, n_ants, 2)),
+                 obs=np.zeros((G, n_ants, P, P, K)), agent_state=np.zeros((T, n_ants, 2)),
                  reward=np.zeros((T, n_ants)), done=np.zeros(T, np.uint8), stored=np.zeros(T, np.uint8))
+        if grid_every is not None:
+            S["grids"] = grids.astype(np.uint8)
         real_random = np.random.random
         for t, op in enumerate(script):
+            g = row[t] if grids[t] else None
             if op == OP_STEP:
                 rot = rng.integers(-1, 2, n_ants)
                 ph = rng.integers(0, 3, n_ants)
@@ -181,10 +217,14 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
                 S["rot"][t], S["ph"][t] = rot, ph
                 S["has_rot"][t], S["has_ph"][t] = use_rot, use_ph
                 o, a, r, d = api.step(rot if use_rot else None, ph if use_ph else None)
-                S["obs"][t], S["agent_state"][t], S["reward"][t], S["done"][t] = o, a, r, d
+                S["agent_state"][t], S["reward"][t], S["done"][t] = a, r, d
+                if g is not None:
+                    S["obs"][g] = o
             elif op == OP_OBSERVE:
                 o, a, _ = api.observation()
-                S["obs"][t], S["agent_state"][t] = o, a
+                S["agent_state"][t] = a
+                if g is not None:
+                    S["obs"][g] = o
                 S["reward"][t] = api.reward.rewards
             else:
                 draws = []
@@ -208,22 +248,24 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
             S["mandibles"][t] = np.asarray(ants.mandibles).astype(np.uint8)
             S["activation"][t] = ants.phero_activation.astype(float)
             S["reward_state"][t] = np.asarray(ants.reward_state).astype(np.uint8)
-            S["food"][t] = food.qte
-            assert np.array_equal(S["food"][t].astype(np.float64), food.qte)
-            store = (t % (2 * store_every) in (0, 1)) or t >= T - 2
+            assert np.array_equal(food.qte.astype(np.float32).astype(np.float64), food.qte)
+            if g is not None:
+                S["food"][g] = food.qte
+            store = ((t % (2 * store_every) in (0, 1)) or t >= T - 2) and g is not None
             S["stored"][t] = store
             if store:
                 for c, p in enumerate(pheros):
-                    S["phero"][t, c] = p.phero
+                    S["phero"][g, c] = p.phero
             em = getattr(api.reward, "explored_map", None)
-            if em is not None:
-                S["explored"][t] = em
+            if em is not None and g is not None:
+                S["explored"][g] = em
             S["anthill_food"][t] = anthill.food
             if rocks is not None:
                 S["rock_centers"][t] = rocks.centers
             S["timestep"][t] = env.timestep
         S["explored"] = np.packbits(S["explored"], axis=-1)
         path = os.path.join(OUT, name + ".npz")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
         np.savez_compressed(path, meta_json=np.array(json.dumps(meta)), **rec, **S)
         print("%-28s T=%3d  pickups(max holding)=%g  hits=%d  anthill_food=%g  %.0f KiB" % (
             name, T, S["holding"].max(), S["hits"].sum(), S["anthill_food"][-1], os.path.getsize(path) / 1024))
@@ -245,7 +287,74 @@ def radius3_filter(e=0.001):
     return g / g.sum() * (1 - e)
 
 
+def ants_on_borders(rng, w, h, env):
+    """A quarter of the ants in the four corner cells' neighbourhood, the rest within 1.5 cells of an edge, heading anywhere."""
+    n = [o for o in env.objects if type(o).__name__ == "Ants"][0].n_ants
+    xyt = np.zeros((n, 3))
+    for i in range(n):
+        d = rng.uniform(0.05, 1.5)
+        if i % 4 == 0:  # a corner
+            xyt[i, 0] = (0 if rng.integers(2) else w) + rng.uniform(-1.5, 1.5)
+            xyt[i, 1] = (0 if rng.integers(2) else h) + rng.uniform(-1.5, 1.5)
+        elif i % 2:     # left / right edge
+            xyt[i, 0] = d if rng.integers(2) else w - d
+            xyt[i, 1] = rng.uniform(0, h)
+        else:           # bottom / top edge
+            xyt[i, 0] = rng.uniform(0, w)
+            xyt[i, 1] = d if rng.integers(2) else h - d
+    xyt[:, 2] = rng.uniform(0, 2 * np.pi, n)
+    return xyt  # (Ants.warp_xy folds the corner ants' negative coordinates)
+
+
+def ants_spread(rng, w, h, env):
+    """Uniform over the whole grid, wall cells included."""
+    n = [o for o in env.objects if type(o).__name__ == "Ants"][0].n_ants
+    return np.stack([rng.uniform(0, w, n), rng.uniform(0, h, n), rng.uniform(0, 2 * np.pi, n)], 1)
+
+
+def rocks_at(rows):
+    """place_rocks hook from literal rows (cx, cy, radius, weight); cx / cy may be given as fractions of w / h."""
+    def place(rng, w, h, env):
+        rk = np.array(rows, dtype=float)
+        rk[:, 0] *= w
+        rk[:, 1] *= h
+        return rk + np.concatenate([rng.uniform(-0.5, 0.5, (len(rk), 2)), np.zeros((len(rk), 2))], 1)
+    return place
+
+
 MAIN_WEIGHTS = dict(fct_explore=1, fct_food=2, fct_anthill=10, fct_explore_holding=1, fct_headinganthill=3)  # main.py:42
+
+def crowd_scenarios():
+    """Ants where the first 13 runs never put them: on the borders, on wall cells, under several rocks at once, many to a
+    cell; rocks light enough to be pushed out of the grid.  tests/crowd_events.py counts what each run contains."""
+    # c01: ants on the borders and in the corners, light rocks straddling the border
+    run_scenario("c01_border_rocks", n_ants=48, steps=80, seed=21, wall_density=0.05, n_rocks=4,
+                 place_ants=ants_on_borders, grid_every=8,
+                 place_rocks=rocks_at([(0.0, 0.3, 6, 2.0), (0.98, 0.7, 5, 1.0), (0.5, 0.0, 7, 4.0), (0.02, 0.98, 4, 0.6)]))
+    # c02: spread ants, dense walls, overlapping light rocks, float activation, All_Rewards
+    run_scenario("c02_dense_walls_rocks", n_ants=64, steps=120, seed=22, wall_density=0.3, n_rocks=4, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, place_ants=ants_spread, grid_every=15,
+                 place_rocks=rocks_at([(0.3, 0.3, 8, 3.0), (0.4, 0.35, 7, 2.0), (0.7, 0.6, 9, 1.5), (0.6, 0.7, 6, 0.8)]))
+    # c03: rocks under the 3 x 3 diffusion filter, on a grid that is no power of two
+    run_scenario("c03_rocks_diffuse3x3", w=48, h=40, n_ants=40, steps=40, seed=23, wall_density=0.1, n_rocks=3,
+                 filt=diffuse3(0.05), float_activation=True, place_ants=ants_spread, grid_every=5,
+                 place_rocks=rocks_at([(0.3, 0.5, 6, 2.0), (0.45, 0.55, 5, 1.0), (0.8, 0.2, 5, 3.0)]))
+    # c04: 64 ants on 16 x 12 cells (H no multiple of 8), two small light rocks
+    run_scenario("c04_tiny_16x12", w=16, h=12, n_ants=64, steps=80, seed=34, wall_density=0.08, n_rocks=2, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, food_extra=False, place_ants=ants_spread, grid_every=4,
+                 place_rocks=rocks_at([(0.3, 0.4, 2.0, 0.5), (0.7, 0.6, 1.5, 0.2)]))
+    # c05: rich food with rocks on top of it
+    run_scenario("c05_rich_food_rocks", n_ants=48, steps=60, seed=25, wall_density=0.05, n_rocks=3, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, rich_food=True, place_ants=ants_spread, grid_every=6,
+                 place_rocks=rocks_at([(0.4, 0.4, 7, 2.0), (0.55, 0.5, 6, 1.0), (0.5, 0.65, 5, 0.6)]))
+    # c06: 600 steps without rocks: scaled units and coordinates over a long horizon against the reference itself
+    run_scenario("c06_long_600", n_ants=12, steps=600, seed=26, wall_density=0.1, reward="all", weights=MAIN_WEIGHTS,
+                 float_activation=True, place_ants=ants_spread, grid_every=100)
+    # oracle only (the device's drift over hundreds of rock pushes is DESIGN.md section 4's subject): 400 steps with rocks
+    run_scenario("oracle_only/o01_rocks_400", n_ants=16, steps=400, seed=27, wall_density=0.1, n_rocks=3, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, place_ants=ants_spread, grid_every=80,
+                 place_rocks=rocks_at([(0.3, 0.3, 8, 3.0), (0.6, 0.6, 7, 1.0), (0.1, 0.8, 6, 0.5)]))
+
 
 if __name__ == "__main__":
     run_scenario("s01_plain", steps=60, seed=3)
@@ -269,3 +378,4 @@ if __name__ == "__main__":
                  float_activation=True, rich_food=True)
     run_scenario("s12_256_n256", w=256, h=256, n_ants=256, steps=20, seed=14, wall_density=0.05,
                  n_rocks=4, store_every=5)
+    crowd_scenarios()

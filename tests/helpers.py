@@ -20,8 +20,22 @@ def fixture_names():
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
 
 
+def oracle_only_fixture_names():
+    """Recordings only the oracle replays (hundreds of steps WITH rocks: the device's coordinate drift over that many rock
+    pushes is DESIGN.md section 4's subject), as names load_fixture takes."""
+    return sorted("oracle_only/" + os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "oracle_only", "*.npz")))
+
+
+def crowd_fixture_names():
+    """The recordings with placed ants / rocks (make_golden.crowd_scenarios) the GPU replays."""
+    return [n for n in fixture_names() if n.startswith("c")]
+
+
 def load_fixture(name, n_envs=1):
-    """-> (cfg, init dict of numpy arrays with leading env axis, F = npz dict, meta)."""
+    """-> (cfg, init dict of numpy arrays with leading env axis, F = npz dict, meta).
+
+    F["grids"][t] says whether food / phero / explored / obs were kept at op t and F["grid_row"][t] is the row of those four
+    arrays that holds op t (a file without the mask keeps them at every op: row t)."""
     F = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     meta = json.loads(str(F["meta_json"]))
     channels, pi = [], 0
@@ -49,7 +63,12 @@ def load_fixture(name, n_envs=1):
                 walls=rep(F["init_walls"].astype(np.uint8)), food=rep(F["init_food"].astype(np.float32)),
                 anthill_xyr=rep(F["init_anthill_xyr"].astype(np.int32)),
                 rocks=rep(F["init_rocks"]) if meta["n_rocks"] else None)
-    F["explored"] = np.unpackbits(F["explored"], axis=-1)
+    F["explored"] = np.unpackbits(F["explored"], axis=-1)[..., :meta["h"]]  # packbits pads H to a multiple of 8
+    T = len(F["ops"])
+    F["grids"] = F["grids"].astype(bool) if "grids" in F else np.ones(T, bool)
+    F["grid_row"] = np.where(F["grids"], np.cumsum(F["grids"]) - 1, -1)
+    for k in ("food", "phero", "explored", "obs"):
+        assert len(F[k]) == int(F["grids"].sum()), (name, k)
     return cfg, init, F, meta
 
 

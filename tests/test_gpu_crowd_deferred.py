@@ -1,0 +1,75 @@
+"""The deferred update (k_update_move) on the crowd fixtures' states.
+
+test_hip_matches_reference_golden reads the state after every op and injects the recorded jitter, so every update of a
+recording runs in k_update_one.  Here the device is driven the way bench.py drives it — step_update(rot, ph, None) every
+step and no state read in between, so every update rides inside the next step's k_update_move — from the initial state and
+with the actions of each crowd recording (ants on the borders, on wall cells, under overlapping rocks, 64 to 192 cells).
+Three environments with a non-zero env_id_base draw different wall jitter and diverge; the oracle draws the same jitter
+from the same generator.  tests/test_crowd_fixtures_cpu.py certifies what these very runs contain."""
+import numpy as np
+import pytest
+
+import crowd_events as ce
+from helpers import assert_xy_close, crowd_fixture_names, load_fixture, phero_close
+from test_crowd_fixtures_cpu import ENV_ID_BASE, N_ENVS
+from test_gpu_parity import XY_ATOL, _cpu, check_obs
+
+pytestmark = pytest.mark.gpu
+
+
+def test_both_perceive_paths_are_among_the_cases():
+    shapes = [(m["w"], m["h"]) for m in (load_fixture(n)[3] for n in crowd_fixture_names())]
+    assert (64, 64) in shapes and any(w & (w - 1) or h & (h - 1) for w, h in shapes)
+
+
+@pytest.mark.parametrize("name", crowd_fixture_names())
+def test_deferred_path_follows_the_oracle_on_crowd_states(name):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    from antsrl_amd import config as cm
+    from antsrl_amd.batched import BatchedAntsEnv
+    cfg, init, F, meta = load_fixture(name, N_ENVS)
+    cfg.env_id_base = ENV_ID_BASE
+    cfg.act_path = cm.ACT_CELL_META
+    E, N = N_ENVS, cfg.n_ants
+    env = BatchedAntsEnv(cfg)
+    assert env.query(cm.Q_CELL_META) == 1 and env.query(cm.Q_DEFERRED_UPDATE) == 1
+    pow2 = not (cfg.w & (cfg.w - 1) or cfg.h & (cfg.h - 1))
+    assert env.query(cm.Q_PERCEIVE_FAST) == int(pow2), "fast k_perceive on power-of-two grids with the default mask, else generic"
+    env.reset(init)
+    if meta["deposit_strength"] != 1.0:
+        env.set_activation(np.broadcast_to(F["init_activation"], (E,) + F["init_activation"].shape).copy(),
+                           meta["deposit_strength"])
+    # the device first (nothing but step_update touches the handle), its outputs kept on the device; then the oracle
+    got = []
+    for t in np.nonzero(F["ops"] == ce.OP_STEP)[0]:
+        rot = np.broadcast_to(F["rot"][t], (E, N))
+        ph = np.broadcast_to(F["ph"][t], (E, N))
+        got.append([x.clone() for x in env.step_update(rot, ph, None)])
+    trs, want, orc = ce.oracle_deferred_run(cfg, init, F, meta, ENV_ID_BASE, n_threads=N_ENVS)
+    assert len(got) == len(want)
+    for s, ((obs, ast, rew, done), (o_obs, o_ast, o_rew, o_done)) in enumerate(zip(got, want)):
+        ctx = "%s step %d" % (name, s)
+        np.testing.assert_array_equal(_cpu(rew), o_rew.astype(np.float32), err_msg=ctx + " reward")
+        np.testing.assert_array_equal(_cpu(done), o_done, err_msg=ctx + " done")
+        np.testing.assert_array_equal(_cpu(ast), o_ast.astype(np.float32), err_msg=ctx + " agent_state")
+        go = _cpu(obs)
+        for e in range(E):
+            check_obs(cfg, go[e], o_obs[e], ctx + " env %d" % e)
+    # the complete state after the last step (this read enqueues the last deferred update)
+    ctx = name + " final"
+    xyt = _cpu(env.read_state(cm.S_ANTS_XYT))
+    assert_xy_close(xyt, orc.ants_xyt, XY_ATOL, ctx)
+    np.testing.assert_array_equal(np.floor(xyt[..., :2]), np.floor(orc.ants_xyt[..., :2]), err_msg=ctx + " cells")
+    assert_xy_close(_cpu(env.read_state(cm.S_PREV_XY)), np.stack([orc.prev_x, orc.prev_y], -1), XY_ATOL, ctx + " prev")
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_HOLDING)), orc.holding, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_MANDIBLES)), orc.mandibles, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_FOOD)), orc.food, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_EXPLORED)), orc.explored, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_ANTHILL_FOOD)), orc.anthill_food, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_TIMESTEP)), orc.timestep, err_msg=ctx)
+    np.testing.assert_array_equal(_cpu(env.read_state(cm.S_REWARD_STATE)), orc.reward_state, err_msg=ctx)
+    ok = phero_close(_cpu(env.read_state(cm.S_PHERO)), orc.phero, threshold=cfg.phero_threshold)
+    assert ok.all(), "%s pheromone: %d cells off" % (ctx, (~ok).sum())
+    if cfg.n_rocks:
+        assert_xy_close(_cpu(env.read_state(cm.S_ROCK_CENTERS)), orc.rock_centers, XY_ATOL, ctx + " rocks")

@@ -272,6 +272,8 @@ def test_generate_with_the_reference_streams_draws_the_golden_initial_states():
         env.generate(cm.make_gen(0.0, 6, 3, 6, rng="reference"), int(meta["seed"]))
         np.testing.assert_array_equal(env.read_state(cm.S_ANTHILL_XYR).cpu().numpy()[0], F["init_anthill_xyr"], err_msg=name)
         np.testing.assert_array_equal(env.read_state(cm.S_SEED).cpu().numpy()[0], F["init_seed"].astype(np.float32), err_msg=name)
+        if meta.get("placed_ants", False):
+            continue  # the recorder put these ants where the generator never does; seeds and anthill are still its draws
         xyt = env.read_state(cm.S_ANTS_XYT).cpu().numpy()[0]
         np.testing.assert_array_equal(xyt[:, 2], F["init_ants_xyt"][:, 2], err_msg=name)
         np.testing.assert_allclose(xyt[:, :2], F["init_ants_xyt"][:, :2], rtol=0, atol=1e-11, err_msg=name)

@@ -55,6 +55,8 @@ def check_obs(cfg, got, want, ctx):
 
 def check_state(env, cfg, F, t, meta, ctx, envs, with_phero):
     from antsrl_amd import config as cm
+    g = F["grid_row"][t] if F["grids"][t] else None  # the row of food / phero / explored for op t, where the file kept them
+    with_phero = with_phero and g is not None
     xyt = _cpu(env.read_state(cm.S_ANTS_XYT))
     prev = _cpu(env.read_state(cm.S_PREV_XY))
     hold = _cpu(env.read_state(cm.S_HOLDING))
@@ -75,17 +77,18 @@ def check_state(env, cfg, F, t, meta, ctx, envs, with_phero):
         np.testing.assert_array_equal(mand[e], F["mandibles"][t], err_msg=ctx + " mandibles")
         np.testing.assert_array_equal(act[e], F["activation"][t], err_msg=ctx + " activation")
         np.testing.assert_array_equal(rs[e], F["reward_state"][t], err_msg=ctx + " reward_state")
-        np.testing.assert_array_equal(food[e], F["food"][t], err_msg=ctx + " food")
+        if g is not None:
+            np.testing.assert_array_equal(food[e], F["food"][g], err_msg=ctx + " food")
         assert ts[e] == F["timestep"][t], ctx
         assert af[e] == F["anthill_food"][t], ctx + " anthill_food"
-        if meta["reward"] in ("exploration", "all"):
-            np.testing.assert_array_equal(expl[e], F["explored"][t], err_msg=ctx + " explored")
+        if meta["reward"] in ("exploration", "all") and g is not None:
+            np.testing.assert_array_equal(expl[e], F["explored"][g], err_msg=ctx + " explored")
         if cfg.n_rocks:
             assert_xy_close(rc[e], F["rock_centers"][t], XY_ATOL, ctx)
         if with_phero:
-            ok = phero_close(ph[e], F["phero"][t], threshold=cfg.phero_threshold)
+            ok = phero_close(ph[e], F["phero"][g], threshold=cfg.phero_threshold)
             assert ok.all(), "%s pheromone: %d cells off, max |d|=%g" % (
-                ctx, (~ok).sum(), np.abs(ph[e] - F["phero"][t])[~ok].max())
+                ctx, (~ok).sum(), np.abs(ph[e] - F["phero"][g])[~ok].max())
 
 
 def _modes():
@@ -136,7 +139,8 @@ def test_hip_matches_reference_golden(torch_mod, name, mode, act):
         if op != OP_UPDATE:
             o, a, r = _cpu(obs), _cpu(ast), _cpu(rew)
             for e in envs:
-                check_obs(cfg, o[e], F["obs"][t], ctx)
+                if F["grids"][t]:
+                    check_obs(cfg, o[e], F["obs"][F["grid_row"][t]], ctx)
                 np.testing.assert_array_equal(a[e], F["agent_state"][t].astype(np.float32), err_msg=ctx)
                 np.testing.assert_array_equal(r[e], F["reward"][t].astype(np.float32), err_msg=ctx + " reward")
         check_state(env, cfg, F, t, meta, ctx, envs, bool(F["stored"][t]))
