@@ -67,14 +67,15 @@ class Oracle:
         self.n_threads = n_threads
         E, N, W, H, Cn, R = cfg.n_envs, cfg.n_ants, cfg.w, cfg.h, cfg.n_phero, cfg.n_rocks
         xyt = np.asarray(init["ants_xyt"], dtype=np.float64).reshape(E, N, 3)
-        self.x = np.ascontiguousarray(xyt[..., 0])
-        self.y = np.ascontiguousarray(xyt[..., 1])
-        self.theta = np.ascontiguousarray(xyt[..., 2])
+        # (copies: with one env and one ant a column of xyt is already contiguous, and a view would step the caller's init)
+        self.x = np.array(xyt[..., 0], order="C")
+        self.y = np.array(xyt[..., 1], order="C")
+        self.theta = np.array(xyt[..., 2], order="C")
         self.prev_x = np.zeros((E, N))
         self.prev_y = np.zeros((E, N))
         self.holding = np.zeros((E, N))
         self.mandibles = np.zeros((E, N), np.uint8)
-        self.seed = np.ascontiguousarray(np.asarray(init["seed"], dtype=np.float64).reshape(E, N))
+        self.seed = np.array(init["seed"], dtype=np.float64).reshape(E, N)
         self.reward_state = np.zeros((E, N), np.uint8)
         self.activation = np.zeros((E, N, Cn))
         ph = init.get("phero")

@@ -132,7 +132,7 @@ def oracle_deferred_run(cfg, init, F, meta, env_id_base, nudge=False, n_threads=
 
     for t in steps:
         rot = np.broadcast_to(F["rot"][t], (E, cfg.n_ants))
-        ph = np.broadcast_to(F["ph"][t], (E, cfg.n_ants))
+        ph = np.broadcast_to(F["ph"][t], (E, cfg.n_ants)) if F["has_ph"][t] else None  # (rotation-only recordings)
         outs.append(o.step(rot, ph))
         keep(OP_STEP)
         o.update(None)

@@ -30,6 +30,13 @@ instead of T).  Everything else stays per op.  A file without ``grids`` keeps th
 positions anywhere on the grid (borders, corners, wall cells), rocks of any centre, radius and weight.
 ``init_*`` is recorded after them; such a file also carries wall_density / rich_food / placed_* in its
 meta, so that a reader can tell which part of the initial state the generator's streams still explain.
+
+The variant hooks (``variant_scenarios``) move the configuration off the values every earlier file shares: ``api_kw`` (the
+five RLApi arguments), ``perception`` = (mask or None, shift[, radius]), ``delta`` (RL_api.DELTA, patched around the calls
+that read it), ``reorder`` (the perceived list: objects dropped, repeated, in another order), ``max_hold``, ``max_val``
+(None allowed), ``no_ph`` (rotation-only: activate_pheromone needs exactly two channels) and ``activation`` (the value
+activate_all_pheromones sets).  Such a file's meta also holds delta, radius, perceived_arg (per perceived object: the
+pheromone's index in ants.pheromones, else 0) and max_val = null for None; a mask of None is stored as an empty array.
 """
 import json
 import os
@@ -46,6 +53,7 @@ if not hasattr(np, "bool"):
 sys.path.insert(0, "/root/reference")
 
 import environment.pheromone as ref_pheromone  # noqa: E402
+import environment.RL_api as ref_rl_api  # noqa: E402
 from environment.RL_api import RLApi  # noqa: E402
 from environment.circle_obstacles import CircleObstacles  # noqa: E402
 from environment.rewards.reward import Reward  # noqa: E402
@@ -105,16 +113,22 @@ def make_reward(kind, weights):
 def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wall_density=0.0,
                  n_rocks=0, reward="exploration", weights=None, float_activation=False,
                  filt=None, max_time=2000, script=None, food_extra=True, none_actions=False,
-                 store_every=1, rich_food=False, place_ants=None, place_rocks=None, grid_every=None):
+                 store_every=1, rich_food=False, place_ants=None, place_rocks=None, grid_every=None,
+                 api_kw=None, perception=None, delta=None, reorder=None, max_hold=None, max_val=255, no_ph=False,
+                 activation=10):
     rng = np.random.default_rng(1000 + seed)
     weights = weights or {}
+    variant = (api_kw is not None or perception is not None or delta is not None or reorder is not None
+               or max_hold is not None or max_val != 255 or no_ph or activation != 10)
     old_filter = ref_pheromone.DIFFUSE_FILTER
+    old_delta = ref_rl_api.DELTA
     if filt is not None:
         ref_pheromone.DIFFUSE_FILTER = np.asarray(filt, dtype=float)  # read at call time, pheromone.py:44
     try:
-        api = RLApi(make_reward(reward, weights), reward_threshold=1, max_speed=1,
-                    max_rot_speed=40 / 180 * np.pi, carry_speed_reduction=0.05,
-                    backward_speed_reduction=0.5)
+        kw = dict(reward_threshold=1, max_speed=1, max_rot_speed=40 / 180 * np.pi, carry_speed_reduction=0.05,
+                  backward_speed_reduction=0.5)
+        kw.update(api_kw or {})
+        api = RLApi(make_reward(reward, weights), **kw)
         # the generator draws the anthill from `random` first; peek so food can be put near it
         random.seed(seed)
         ax = int(random.random() * w * 0.5 + w * 0.25)
@@ -123,8 +137,20 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
         gen = EnvironmentGenerator(w, h, n_ants, n_phero, 0,
                                    FoodNearAnthill(6, 3, 6, extra, rng if rich_food else None),
                                    BernoulliWalls(wall_density, rng), max_time, seed=seed)
+        if perception is not None and perception[0] is not None:
+            gen.setup_perception(np.asarray(perception[0], dtype=bool), perception[1])
+        if delta is not None:
+            ref_rl_api.DELTA = delta  # read by RLApi.setup_perception at call time, RL_api.py:93
         env = gen.generate(api)
+        if perception is not None and perception[0] is None:
+            # generate() takes the radius from the mask's shape (environment_generator.py:102): no mask goes in afterwards
+            api.setup_perception(perception[2], api.perceived_objects, None, perception[1])
+        ref_rl_api.DELTA = old_delta
         ants = api.ants
+        if max_hold is not None:
+            ants.max_hold = max_hold
+        for p in ants.pheromones:
+            p.max_val = max_val
         rocks = None
         if place_ants is not None:
             # hook: positions anywhere on the grid.  Ants.__init__ (ants.py:27-30) and All_Rewards.setup
@@ -149,8 +175,10 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
             rocks = CircleObstacles(env, centers=centers.copy(), radiuses=rng.random(n_rocks) * 5 + 5,
                                     weights=rng.random(n_rocks) * 50 + 50)
             api.perceived_objects.append(rocks)
+        if reorder is not None:
+            api.perceived_objects = list(reorder(list(api.perceived_objects)))
         if float_activation:
-            ants.activate_all_pheromones(np.ones((n_ants, n_phero)) * 10)  # collect_agent_memory.py:129-131
+            ants.activate_all_pheromones(np.ones((n_ants, n_phero)) * activation)  # collect_agent_memory.py:129-131
 
         objs = {type(o).__name__: o for o in env.objects}
         pheros = [o for o in env.objects if isinstance(o, Pheromone)]
@@ -166,18 +194,23 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
                     perceived=kinds, fwd_delta=float(api.perception_fwd_delta),
                     max_speed=api.max_speed, max_rot_speed=api.max_rot_speed,
                     carry=api.carry_speed_reduction, backward=api.backward_speed_reduction,
-                    max_hold=float(ants.max_hold), max_val=float(pheros[0].max_val),
+                    max_hold=float(ants.max_hold), max_val=None if max_val is None else float(pheros[0].max_val),
                     reward_threshold=api.reward_threshold, seed=seed)
-        if place_ants is not None or place_rocks is not None or grid_every is not None:
+        if place_ants is not None or place_rocks is not None or grid_every is not None or variant:
             meta.update(wall_density=wall_density, rich_food=bool(rich_food), food_extra=bool(food_extra),
                         placed_ants=place_ants is not None, placed_rocks=place_rocks is not None)
+        if variant:
+            meta.update(delta=float(delta if delta is not None else old_delta), radius=int(api.perception_radius),
+                        perceived_arg=[ants.pheromones.index(o) if isinstance(o, Pheromone) else 0
+                                       for o in api.perceived_objects])
         rec = dict(
             init_ants_xyt=ants.ants.copy(), init_seed=ants.seed.copy(), init_walls=walls.map.copy(),
             init_food=food.qte.copy(), init_anthill_xyr=np.array([anthill.x, anthill.y, anthill.radius]),
             init_rocks=(np.concatenate([rocks.centers, rocks.radiuses[:, None], rocks.weights[:, None]], 1)
                         if rocks is not None else np.zeros((0, 4))),
             init_activation=ants.phero_activation.astype(float).copy(),
-            init_anthill_area=anthill.area.copy(), mask=api.perception_mask.copy())
+            init_anthill_area=anthill.area.copy(),
+            mask=api.perception_mask.copy() if api.perception_mask is not None else np.zeros((0, 0), bool))
 
         if script is None:
             script = []
@@ -214,6 +247,8 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
                 use_rot, use_ph = True, True
                 if none_actions:
                     use_rot, use_ph = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+                if no_ph:
+                    use_ph = False
                 S["rot"][t], S["ph"][t] = rot, ph
                 S["has_rot"][t], S["has_ph"][t] = use_rot, use_ph
                 o, a, r, d = api.step(rot if use_rot else None, ph if use_ph else None)
@@ -271,6 +306,7 @@ def run_scenario(name, *, w=64, h=64, n_ants=32, n_phero=2, steps=60, seed=3, wa
             name, T, S["holding"].max(), S["hits"].sum(), S["anthill_food"][-1], os.path.getsize(path) / 1024))
     finally:
         ref_pheromone.DIFFUSE_FILTER = old_filter
+        ref_rl_api.DELTA = old_delta
 
 
 def diffuse3(d, e=0.001):
@@ -356,6 +392,88 @@ def crowd_scenarios():
                  place_rocks=rocks_at([(0.3, 0.3, 8, 3.0), (0.6, 0.6, 7, 1.0), (0.1, 0.8, 6, 0.5)]))
 
 
+#: the generator's other mask (commented out at environment_generator.py:30-34): radius 2
+MASK_5X5 = np.array([[0, 1, 1, 1, 0],
+                     [1, 1, 1, 1, 1],
+                     [1, 1, 1, 1, 1],
+                     [0, 1, 1, 1, 0],
+                     [0, 0, 1, 0, 0]], dtype=bool)
+#: a 7 x 7 mask that is neither the default nor symmetric under any flip or transposition
+MASK_7X7_OTHER = np.array([[0, 0, 0, 0, 0, 0, 1],
+                           [0, 1, 1, 1, 1, 0, 0],
+                           [1, 1, 1, 1, 1, 1, 0],
+                           [1, 1, 1, 0, 1, 1, 1],
+                           [0, 1, 1, 1, 1, 1, 1],
+                           [0, 1, 1, 1, 1, 1, 0],
+                           [1, 0, 1, 1, 0, 0, 0]], dtype=bool)
+OTHER_WEIGHTS = dict(fct_explore=0.3, fct_food=7, fct_anthill=3, fct_explore_holding=0.7, fct_headinganthill=1.5)
+NO_EXPLORE_WEIGHTS = dict(fct_explore=0, fct_food=2, fct_anthill=10, fct_explore_holding=0, fct_headinganthill=3)
+DEG = np.pi / 180
+
+
+def by_kind(order):
+    """reorder hook: the perceived list rebuilt from kind names; "Pheromone0" / "Pheromone1" / ... name ants.pheromones[i]."""
+    def pick(objs):
+        pheros = [o for o in objs if isinstance(o, Pheromone)]
+        named = {type(o).__name__: o for o in objs if not isinstance(o, Pheromone)}
+        named.update({"Pheromone%d" % i: p for i, p in enumerate(pheros)})
+        return [named[k] for k in order]
+    return pick
+
+
+def variant_scenarios():
+    """Configurations no earlier recording has: every RLApi argument, both perception sizes and no mask, DELTA, the
+    channel list, max_hold, max_val, 1 and 3 pheromones, other reward weights.  tests/test_variant_fixtures_cpu.py counts
+    what each run contains."""
+    # v01: carry 0.3 on rich food: an ant that holds 4 or 5 walks backwards, at half speed; another 7 x 7 mask on the
+    # power-of-two grid (cell-meta path, fast k_perceive), shift 3, rocks
+    run_scenario("v01_carry_backward", n_ants=32, steps=60, seed=41, wall_density=0.03, n_rocks=2, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, rich_food=True, grid_every=5,
+                 api_kw=dict(carry_speed_reduction=0.3), perception=(MASK_7X7_OTHER, 3))
+    # v02: carry 0.5, backward 0.25, 25 degrees a step, rocks; a threshold (6) above the most an ant earns without a pickup
+    # or a delivery: every one of the 49 sample points counts, masked or not (reward_custom.py:89), so a fresh window gives
+    # 4.9, and heading for the anthill adds 0.3; a pickup of 3 or more (2 x taken) or a delivery (10) still passes it
+    run_scenario("v02_backward_quarter", n_ants=32, steps=60, seed=42, wall_density=0.03, n_rocks=2, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, rich_food=True, grid_every=5,
+                 api_kw=dict(carry_speed_reduction=0.5, backward_speed_reduction=0.25, max_rot_speed=25 * DEG,
+                             reward_threshold=6))
+    # v03: 2.5 cells a step, 65 degrees, threshold 0.35, weights that are neither main.py's nor dyadic; rocks and walls
+    run_scenario("v03_speed_threshold", n_ants=40, steps=50, seed=43, wall_density=0.05, n_rocks=3, reward="all",
+                 weights=OTHER_WEIGHTS, float_activation=True, grid_every=5,
+                 api_kw=dict(max_speed=2.5, max_rot_speed=65 * DEG, reward_threshold=0.35, carry_speed_reduction=0.12))
+    # v04: All_Rewards that never counts explored cells (reward_custom.py:87), threshold 0.05
+    run_scenario("v04_no_explore", n_ants=32, steps=60, seed=44, wall_density=0.03, reward="all",
+                 weights=NO_EXPLORE_WEIGHTS, float_activation=True, grid_every=5, api_kw=dict(reward_threshold=0.05))
+    # v05: the generator's 5 x 5 mask, no forward shift, rocks
+    run_scenario("v05_mask5_shift0", n_ants=32, steps=50, seed=45, wall_density=0.05, n_rocks=2, grid_every=4,
+                 perception=(MASK_5X5, 0))
+    # v06: radius 5, no mask, shift 2.5, DELTA 1.37
+    run_scenario("v06_radius5_delta", n_ants=24, steps=40, seed=47, wall_density=0.05, grid_every=8,
+                 perception=(None, 2.5, 5), delta=1.37)
+    # v07: Food before Anthill, both twice (RL_api.py:180-184 walks set, clear, set, clear: an ant over food on the anthill
+    # area ends with open mandibles, where the generator's order closes them), pheromone 1 before pheromone 0, rocks;
+    # max_hold 2 on rich food.  Every op keeps its grids: the test reads the food under every pickup.
+    run_scenario("v07_reordered_hold2", n_ants=32, steps=60, seed=48, wall_density=0.03, n_rocks=2, reward="all",
+                 weights=MAIN_WEIGHTS, float_activation=True, rich_food=True, max_hold=2,
+                 reorder=by_kind(["Food", "Anthill", "Pheromone1", "Ants", "Food", "Pheromone0", "Walls", "CircleObstacles",
+                                  "Anthill"]))
+    # v08: neither Food nor a pheromone perceived (no ant can pick anything up), Pheromone(max_val=None): deposits unclipped
+    run_scenario("v08_no_food_no_phero", n_ants=32, steps=50, seed=49, wall_density=0.05, float_activation=True,
+                 grid_every=5, max_val=None, reorder=by_kind(["Ants", "Anthill", "Walls"]))
+    # v09: Food but no Anthill (mandibles close and never open), ExplorationReward with other motion parameters
+    run_scenario("v09_food_no_anthill", n_ants=32, steps=50, seed=50, wall_density=0.03, rich_food=True, grid_every=5,
+                 api_kw=dict(max_speed=1.75, max_rot_speed=90 * DEG, carry_speed_reduction=0.12, backward_speed_reduction=0.75),
+                 reorder=by_kind(["Ants", "Pheromone0", "Pheromone1", "Walls", "Food"]))
+    # v10: one pheromone with max_val 100, deposits of 60 (two ants to a cell reach the cap); Food_Reward, other motion
+    run_scenario("v10_one_phero_max100", n_ants=48, n_phero=1, steps=60, seed=51, wall_density=0.03, reward="food",
+                 float_activation=True, activation=60, no_ph=True, max_val=100, grid_every=5,
+                 api_kw=dict(max_speed=1.5, max_rot_speed=55 * DEG, carry_speed_reduction=0.1))
+    # v11: three pheromones under a random 11 x 11 mask
+    run_scenario("v11_three_phero_mask11", n_ants=24, n_phero=3, steps=40, seed=52, wall_density=0.05,
+                 float_activation=True, no_ph=True, grid_every=10, store_every=2,
+                 perception=(np.random.default_rng(52).random((11, 11)) < 0.7, 4))
+
+
 if __name__ == "__main__":
     run_scenario("s01_plain", steps=60, seed=3)
     run_scenario("s02_walls", steps=60, seed=4, wall_density=0.05)
@@ -379,3 +497,4 @@ if __name__ == "__main__":
     run_scenario("s12_256_n256", w=256, h=256, n_ants=256, steps=20, seed=14, wall_density=0.05,
                  n_rocks=4, store_every=5)
     crowd_scenarios()
+    variant_scenarios()

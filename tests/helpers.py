@@ -31,6 +31,11 @@ def crowd_fixture_names():
     return [n for n in fixture_names() if n.startswith("c")]
 
 
+def variant_fixture_names():
+    """The recordings of configurations off the reference's defaults (make_golden.variant_scenarios)."""
+    return [n for n in fixture_names() if n.startswith("v")]
+
+
 def load_fixture(name, n_envs=1):
     """-> (cfg, init dict of numpy arrays with leading env axis, F = npz dict, meta).
 
@@ -38,18 +43,23 @@ def load_fixture(name, n_envs=1):
     arrays that holds op t (a file without the mask keeps them at every op: row t)."""
     F = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     meta = json.loads(str(F["meta_json"]))
+    # a pheromone channel's argument: recorded (perceived_arg) where the file has it; the earlier files perceive the
+    # pheromones once each and in order, so counting them gives the same
     channels, pi = [], 0
-    for k in meta["perceived"]:
+    for i, k in enumerate(meta["perceived"]):
         kind = _KIND[k]
         if kind == cfgmod.CH_PHERO:
-            channels.append((kind, pi))
+            channels.append((kind, meta["perceived_arg"][i] if "perceived_arg" in meta else pi))
             pi += 1
         else:
             channels.append((kind, 0))
     wts = meta["weights"] or {}
+    # (a perception without a mask is stored as an empty array, its radius in the meta)
+    mask = F["mask"].astype(np.uint8) if F["mask"].size else None
     cfg = cfgmod.make_cfg(
         n_envs, meta["n_ants"], meta["w"], meta["h"], n_phero=meta["n_phero"], n_rocks=meta["n_rocks"],
-        max_time=meta["max_time"], mask=F["mask"].astype(np.uint8), fwd_delta=meta["fwd_delta"],
+        max_time=meta["max_time"], mask=mask, perception_radius=meta.get("radius"), fwd_delta=meta["fwd_delta"],
+        delta=meta.get("delta", 1.1),
         channels=channels, max_speed=meta["max_speed"], max_rot_speed=meta["max_rot_speed"],
         carry_speed_reduction=meta["carry"], backward_speed_reduction=meta["backward"],
         max_hold=meta["max_hold"], phero_max_val=meta["max_val"], deposit_strength=meta["deposit_strength"],

@@ -5,13 +5,21 @@ recording runs in k_update_one.  Here the device is driven the way bench.py driv
 step and no state read in between, so every update rides inside the next step's k_update_move — from the initial state and
 with the actions of each crowd recording (ants on the borders, on wall cells, under overlapping rocks, 64 to 192 cells).
 Three environments with a non-zero env_id_base draw different wall jitter and diverge; the oracle draws the same jitter
-from the same generator.  tests/test_crowd_fixtures_cpu.py certifies what these very runs contain."""
+from the same generator.  tests/test_crowd_fixtures_cpu.py certifies what these very runs contain.
+
+The variant recordings (tests/golden/v*.npz: carry, backward, speed, rotation, threshold and weights off their defaults,
+other masks) are driven the same way wherever the handle defers the update (Q_DEFERRED_UPDATE): k_update_move carries its
+own copy of the move (`fwd < 0 -> fwd * backward`), which nothing else reaches.  A shape the cell-meta path refuses would take
+ACT_AUTO, which never defers: those recordings (v06-v11) are no cases here, the golden replay runs them; a rotation-only
+recording would pass no pheromone actions.  tests/test_variant_fixtures_cpu.py certifies that the
+oracle's runs here contain the backward move and rewards between each threshold and 1."""
 import numpy as np
 import pytest
 
 import crowd_events as ce
-from helpers import assert_xy_close, crowd_fixture_names, load_fixture, phero_close
+from helpers import assert_xy_close, crowd_fixture_names, load_fixture, phero_close, variant_fixture_names
 from test_crowd_fixtures_cpu import ENV_ID_BASE, N_ENVS
+from test_variant_fixtures_cpu import is_backward_file
 from test_gpu_parity import XY_ATOL, _cpu, check_obs
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +30,55 @@ def test_both_perceive_paths_are_among_the_cases():
     assert (64, 64) in shapes and any(w & (w - 1) or h & (h - 1) for w, h in shapes)
 
 
-@pytest.mark.parametrize("name", crowd_fixture_names())
+def _variant_handle(cfg):
+    """A variant recording's handle: the cell-meta path where it takes the shape, else the library's own choice."""
+    from antsrl_amd import _lib, config as cm
+    from antsrl_amd.batched import BatchedAntsEnv
+    cfg.act_path = cm.ACT_CELL_META
+    try:
+        return BatchedAntsEnv(cfg)
+    except _lib.AntsrlError as e:
+        if "ANTSRL_ACT_CELL_META" not in str(e):
+            raise
+    cfg.act_path = cm.ACT_AUTO
+    return BatchedAntsEnv(cfg)
+
+
+def _defers(meta, mask):
+    """The library's conditions for k_update_move (antsrl_update_move_supported: the cell-meta layout, two pheromones, at
+    most 1024 ants), restated on a recording's meta so that the cases below can be chosen at collection: the generator's
+    channel order, 128..368 observation values per ant over at most 64 cells.  The test right below holds it to the library."""
+    order = ["Ants", "Pheromone", "Pheromone", "Anthill", "Walls", "Food"] + (["CircleObstacles"] if meta["n_rocks"] else [])
+    cells = (2 * meta.get("radius", mask.shape[0] // 2) + 1) ** 2
+    return (meta["n_phero"] == 2 and meta["perceived"] == order and meta.get("perceived_arg", [0, 0, 1])[1:3] == [0, 1]
+            and cells <= 64 and 128 <= cells * len(order) <= 368 and meta["n_ants"] <= 1024)
+
+
+def deferring_variant_names():
+    out = []
+    for name in variant_fixture_names():
+        cfg, init, F, meta = load_fixture(name)
+        if _defers(meta, F["mask"]):
+            out.append(name)
+    return out
+
+
+def test_the_backward_move_and_the_threshold_run_deferred():
+    """The variant recordings driven below are exactly those whose handle defers the update (a shape the cell-meta path
+    refuses takes ACT_AUTO, which never defers); at least one backward-motion recording and the threshold / weights
+    recording are among them."""
+    from antsrl_amd import config as cm
+    deferred = []
+    for name in variant_fixture_names():
+        cfg, init, F, meta = load_fixture(name, N_ENVS)
+        if _variant_handle(cfg).query(cm.Q_DEFERRED_UPDATE) == 1:
+            deferred.append(meta)
+    assert [m["name"] for m in deferred] == deferring_variant_names()
+    assert any(is_backward_file(m) for m in deferred)
+    assert any(m["reward_threshold"] < 1 and m["max_speed"] == 2.5 and m["reward"] == "all" for m in deferred)
+
+
+@pytest.mark.parametrize("name", crowd_fixture_names() + deferring_variant_names())
 def test_deferred_path_follows_the_oracle_on_crowd_states(name):
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
@@ -30,12 +86,16 @@ def test_deferred_path_follows_the_oracle_on_crowd_states(name):
     from antsrl_amd.batched import BatchedAntsEnv
     cfg, init, F, meta = load_fixture(name, N_ENVS)
     cfg.env_id_base = ENV_ID_BASE
-    cfg.act_path = cm.ACT_CELL_META
     E, N = N_ENVS, cfg.n_ants
-    env = BatchedAntsEnv(cfg)
-    assert env.query(cm.Q_CELL_META) == 1 and env.query(cm.Q_DEFERRED_UPDATE) == 1
-    pow2 = not (cfg.w & (cfg.w - 1) or cfg.h & (cfg.h - 1))
-    assert env.query(cm.Q_PERCEIVE_FAST) == int(pow2), "fast k_perceive on power-of-two grids with the default mask, else generic"
+    if name in variant_fixture_names():
+        env = _variant_handle(cfg)
+        assert env.query(cm.Q_CELL_META) == 1 and env.query(cm.Q_DEFERRED_UPDATE) == 1
+    else:
+        cfg.act_path = cm.ACT_CELL_META
+        env = BatchedAntsEnv(cfg)
+        assert env.query(cm.Q_CELL_META) == 1 and env.query(cm.Q_DEFERRED_UPDATE) == 1
+        pow2 = not (cfg.w & (cfg.w - 1) or cfg.h & (cfg.h - 1))
+        assert env.query(cm.Q_PERCEIVE_FAST) == int(pow2), "fast k_perceive on power-of-two grids with the default mask, else generic"
     env.reset(init)
     if meta["deposit_strength"] != 1.0:
         env.set_activation(np.broadcast_to(F["init_activation"], (E,) + F["init_activation"].shape).copy(),
@@ -44,7 +104,7 @@ def test_deferred_path_follows_the_oracle_on_crowd_states(name):
     got = []
     for t in np.nonzero(F["ops"] == ce.OP_STEP)[0]:
         rot = np.broadcast_to(F["rot"][t], (E, N))
-        ph = np.broadcast_to(F["ph"][t], (E, N))
+        ph = np.broadcast_to(F["ph"][t], (E, N)) if F["has_ph"][t] else None
         got.append([x.clone() for x in env.step_update(rot, ph, None)])
     trs, want, orc = ce.oracle_deferred_run(cfg, init, F, meta, ENV_ID_BASE, n_threads=N_ENVS)
     assert len(got) == len(want)

@@ -6,6 +6,19 @@ anthill.food, explored map, integer perception channels, reward and done BIT-EXA
 coordinates within 1e-9 (device sin/cos may differ from glibc in the last ulp); pheromone grid
 and pheromone perception channels within 1e-5 (fp32 grid vs float64 reference, comparator
 `helpers.phero_close`).
+
+What is held to the REFERENCE (test_hip_matches_reference_golden on tests/golden/*.npz), beyond
+the settings the first 20 recordings share: carry_speed_reduction 0.1 / 0.12 / 0.3 / 0.5 and
+backward_speed_reduction 0.25 / 0.75 (the backward move), max_speed 1.5 / 1.75 / 2.5, max_rot_speed
+25 / 55 / 65 / 90 degrees, reward_threshold 0.05 / 0.35 / 6, All_Rewards with two other weight sets
+(one without exploration), the 5 x 5 mask without a shift, another 7 x 7 mask, an 11 x 11 mask,
+radius 5 without a mask, shifts 0 / 2.5 / 3, DELTA 1.37, channel lists in another order, with
+repeats and with objects left out, max_hold 2, max_val 100 and None, 1 and 3 pheromones (the v*.npz
+files; tests/test_variant_fixtures_cpu.py says what each contains).  Held to the ORACLE only: every
+other value of those parameters that tests/test_gpu_fuzz.py draws (perception radius 1, 4, 6 and 7,
+four pheromones, backward 0 and 1, threshold 0 and 2.5, max_rot_speed 0), the diffusion filters of
+radius 1 to 3 other than the two recorded ones, phero_threshold (the reference hard-codes 0.01) and
+Perlin walls.
 """
 import numpy as np
 import pytest
@@ -646,6 +659,105 @@ def test_known_answers(torch_mod):
     mask = cm.mask_array(cfg)
     assert (o[:, ~mask, :] == -1).all()
     assert set(np.unique(o[:, mask, 0])) <= {0.0, 1.0}
+
+
+def test_known_answers_backward_move_and_threshold(torch_mod):
+    """Hand-derived, no oracle: RL_api.py:194-196 and ants.py:119-121 with parameters off their defaults.
+
+    One ant at (5.5, 5.5), theta 0, on a cell with 5 food, speed 1, no rotation.  The step closes its mandibles, it takes
+    5, and fwd = 1 - 5 * carry: carry 0.3 gives -0.5, times backward (0.5 -> x = 5.25, 0.25 -> x = 5.375); carry 0.2
+    gives 0, which is not negative (x stays 5.5 whatever backward is).  On both act paths through step + update, and
+    through two step_update calls: the second move, holding 5 from its start, rides in k_update_move.
+
+    An exploration reward of 0.5: one ant at (5.2, 5.2), theta pi/4, radius 1 without a mask or shift, speed sqrt(2).  The
+    3 x 3 sample points, DELTA = 1.1 apart and turned by theta + pi/2, are the ant, four at (+-0.778, +-0.778) and four at
+    (+-1.556, 0) / (0, +-1.556) from it: nine distinct cells, which a first observation explores (0.9; every sample point
+    counts, masked or not, reward_custom.py:19).  The step moves the ant by (1, 1); of the nine cells of the shifted
+    pattern (6,6) (5,5) (5,7) (7,5) are explored and (7,7) (5,6) (8,6) (6,5) (6,8) are new: 5 / 10.  reward_state is 255
+    under threshold 0.35, 0 under threshold 1, and 229 = int(255 * 0.9) after the update (ants.py:130)."""
+    from antsrl_amd import config as cm
+    from antsrl_amd.batched import BatchedAntsEnv
+    W = H = 16
+    walls = np.zeros((1, W, H), np.uint8)
+    food = np.zeros((1, W, H), np.float32)
+    food[0, 5, 5] = 5.0
+    init = dict(ants_xyt=np.array([[[5.5, 5.5, 0.0]]]), seed=np.full((1, 1), 0.25), walls=walls, food=food,
+                anthill_xyr=np.array([[12, 12, 1]], np.int32))
+    stay, none = np.zeros((1, 1), np.int8), np.zeros((1, 1), np.int8)
+
+    def x_and_holding(env):
+        xyt = _cpu(env.read_state(cm.S_ANTS_XYT))[0, 0]
+        assert abs(xyt[1] - 5.5) <= XY_ATOL and xyt[2] == 0.0
+        return xyt[0], _cpu(env.read_state(cm.S_HOLDING))[0, 0]
+
+    for act in (cm.ACT_CELL_META, cm.ACT_SINGLE_KERNEL):
+        for carry, backward, dx in [(0.3, 0.5, -0.25), (0.3, 0.25, -0.125), (0.2, 0.5, 0.0), (0.2, 0.25, 0.0)]:
+            ctx = "act path %d carry %g backward %g" % (act, carry, backward)
+            cfg = cm.make_cfg(1, 1, W, H, deposit_strength=256.0, act_path=act, carry_speed_reduction=carry,
+                              backward_speed_reduction=backward, max_speed=1.0)
+            env = BatchedAntsEnv(cfg)
+            env.reset(init)
+            _, ast, _, _ = env.step(stay, none)
+            assert _cpu(ast)[0, 0, 0] == 5.0, ctx
+            x, hold = x_and_holding(env)
+            assert hold == 5.0 and abs(x - (5.5 + dx)) <= XY_ATOL, (ctx, x)
+            if dx == 0.0:
+                assert x == 5.5, (ctx, x)  # fwd is exactly 0: nothing is added
+            env.update(None)
+            x, hold = x_and_holding(env)
+            assert hold == 5.0 and abs(x - (5.5 + dx)) <= XY_ATOL, (ctx, x)
+            assert _cpu(env.read_state(cm.S_FOOD))[0, 5, 5] == 0.0, ctx
+            if act != cm.ACT_CELL_META:
+                continue
+            # the same, one call per step and no read in between: the second move is k_update_move's
+            env = BatchedAntsEnv(cfg)
+            assert env.query(cm.Q_DEFERRED_UPDATE) == 1
+            env.reset(init)
+            env.step_update(stay, none, None)
+            _, ast, _, _ = env.step_update(stay, none, None)
+            assert _cpu(ast)[0, 0, 0] == 5.0, ctx
+            x, hold = x_and_holding(env)
+            assert hold == 5.0 and abs(x - (5.5 + 2 * dx)) <= XY_ATOL, (ctx, x)
+
+    init["food"] = np.zeros((1, W, H), np.float32)
+    init["ants_xyt"] = np.array([[[5.2, 5.2, np.pi / 4]]])
+    for threshold, lit in [(0.35, 255), (1.0, 0)]:
+        cfg = cm.make_cfg(1, 1, W, H, mask=None, perception_radius=1, fwd_delta=0.0, max_speed=float(np.sqrt(2)),
+                          reward_kind=cm.REWARD_EXPLORATION, reward_threshold=threshold)
+        env = BatchedAntsEnv(cfg)
+        env.reset(init)
+        _, _, rew = env.observe()
+        assert _cpu(rew)[0, 0] == np.float32(0.9), threshold
+        assert _cpu(env.read_state(cm.S_REWARD_STATE))[0, 0] == 0, threshold  # (an observation gives no reward, RL_api.py:96-165)
+        _, _, rew, _ = env.step(stay, none)
+        assert _cpu(rew)[0, 0] == np.float32(0.5), threshold
+        assert _cpu(env.read_state(cm.S_REWARD_STATE))[0, 0] == lit, threshold
+        env.update(None)
+        assert _cpu(env.read_state(cm.S_REWARD_STATE))[0, 0] == int(lit * 0.9), threshold
+    assert int(255 * 0.9) == 229
+
+
+def test_variant_recordings_reach_every_path(torch_mod):
+    """Which kernels the variant recordings (tests/golden/v*.npz) run on in test_hip_matches_reference_golden: at least four
+    on the cell-meta path (k_move + k_perceive), at least one of those on the fast k_perceive, and every one on k_act."""
+    from antsrl_amd import _lib, config as cm
+    from antsrl_amd.batched import BatchedAntsEnv
+    cell_meta, fast = [], []
+    for name in helpers.variant_fixture_names():
+        cfg, init, F, meta = load_fixture(name, 3)
+        cfg.act_path = cm.ACT_SINGLE_KERNEL
+        assert BatchedAntsEnv(cfg).query(cm.Q_CELL_META) == 0, name
+        cfg.act_path = cm.ACT_CELL_META
+        try:
+            env = BatchedAntsEnv(cfg)
+        except _lib.AntsrlError as e:
+            assert "ANTSRL_ACT_CELL_META" in str(e), name
+            continue
+        cell_meta.append(name)
+        if env.query(cm.Q_PERCEIVE_FAST) == 1:
+            fast.append(name)
+    print("cell-meta:", cell_meta, "fast k_perceive:", fast)
+    assert len(cell_meta) >= 4 and len(fast) >= 1
 
 
 def test_large_grids_and_many_envs(torch_mod):
