@@ -10,6 +10,7 @@ Call order mirrors the reference driver (main.py:88-131):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional
 
@@ -20,35 +21,25 @@ from . import _lib
 from . import config as cfgmod
 from . import vmm
 from .config import AntsCfg, AntsInit
+from .placement import Tuner, placement_levels_seen  # noqa: F401  (the rule's old home: tests and recorded probes import it from here)
 
-_STATE_DTYPES = {
-    cfgmod.S_ANTS_XYT: torch.float64, cfgmod.S_PREV_XY: torch.float64, cfgmod.S_HOLDING: torch.float32,
-    cfgmod.S_MANDIBLES: torch.uint8, cfgmod.S_ACTIVATION: torch.float32, cfgmod.S_PHERO: torch.float32,
-    cfgmod.S_FOOD: torch.float32, cfgmod.S_EXPLORED: torch.uint8, cfgmod.S_ANTHILL_FOOD: torch.float64,
-    cfgmod.S_ROCK_CENTERS: torch.float64, cfgmod.S_TIMESTEP: torch.int32, cfgmod.S_REWARD_STATE: torch.uint8,
-    cfgmod.S_WALLS: torch.uint8, cfgmod.S_ANTHILL_AREA: torch.uint8, cfgmod.S_SEED: torch.float32,
-    cfgmod.S_ANTHILL_XYR: torch.int32, cfgmod.S_ROCK_RW: torch.float64,
-    cfgmod.S_PHERO_C0: torch.float32, cfgmod.S_PHERO_C1: torch.float32, cfgmod.S_PHERO_C2: torch.float32,
-    cfgmod.S_PHERO_C3: torch.float32,
+# what read_state returns, array by array: dtype and shape (E envs, N ants, W x H cells, C pheromone channels, R rocks)
+_ANTS, _GRID = ("E", "N"), ("E", "W", "H")
+_STATE_ARRAYS = {
+    cfgmod.S_ANTS_XYT: (torch.float64, ("E", "N", 3)), cfgmod.S_PREV_XY: (torch.float64, ("E", "N", 2)),
+    cfgmod.S_HOLDING: (torch.float32, _ANTS), cfgmod.S_MANDIBLES: (torch.uint8, _ANTS), cfgmod.S_SEED: (torch.float32, _ANTS),
+    cfgmod.S_ACTIVATION: (torch.float32, ("E", "N", "C")), cfgmod.S_REWARD_STATE: (torch.uint8, _ANTS),
+    cfgmod.S_PHERO: (torch.float32, ("E", "C", "W", "H")), cfgmod.S_FOOD: (torch.float32, _GRID),
+    cfgmod.S_EXPLORED: (torch.uint8, _GRID), cfgmod.S_WALLS: (torch.uint8, _GRID), cfgmod.S_ANTHILL_AREA: (torch.uint8, _GRID),
+    cfgmod.S_ANTHILL_FOOD: (torch.float64, ("E",)), cfgmod.S_TIMESTEP: (torch.int32, ("E",)),
+    cfgmod.S_ANTHILL_XYR: (torch.int32, ("E", 3)),
+    cfgmod.S_ROCK_CENTERS: (torch.float64, ("E", "R", 2)), cfgmod.S_ROCK_RW: (torch.float64, ("E", "R", 2)),
+    cfgmod.S_PHERO_C0: (torch.float32, _GRID), cfgmod.S_PHERO_C1: (torch.float32, _GRID),
+    cfgmod.S_PHERO_C2: (torch.float32, _GRID), cfgmod.S_PHERO_C3: (torch.float32, _GRID),
 }
-
-
-import contextlib
 
 _NULL_CTX = contextlib.nullcontext()
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def placement_levels_seen(times) -> bool:
-    """tune_placement's stopping rule: have the trials — the observation kernel's times — shown BOTH placement levels (15 %
-    apart at c3)?  A spread of 6 % or more among the trials — not counting a trial far above everything else, which is not a level (a
-    first touch, a profiler's hiccup: 0.32 ms among 0.233s on a device whose every buffer sat on the slow level)."""
-    ok = [t for t in times if t < 1.25 * min(times)]
-    return max(ok) >= 1.06 * min(ok)  # (k_perceive: 15-18 % apart at c3 / c4 / c5, 3-4 % at c2-sized batches — which then walk)
 
 
 class BatchedAntsEnv:
@@ -64,7 +55,7 @@ class BatchedAntsEnv:
         instead of torch.empty; the workspace stays a torch allocation.  On MI355X the observation kernel runs 15 % apart
         depending on the physical layout of these two buffers; this combination is the fast one on most boxes, two torch
         allocations are mostly slow (antsrl_amd/vmm.py, profiles/history/r04/placement_probe*.txt).  tune_placement() measures the
-        four combinations on the box at hand and keeps the fastest.
+        four combinations on the box at hand and keeps the fastest (the tuner: antsrl_amd/placement.py).
         split_workspace: the workspace is two allocations (antsrl_create2) — the cell records, and the state block with
         everything else — so that tune_placement() can place them apart; False: one allocation (antsrl_create)."""
         if obs_dtype not in (torch.float32, torch.bfloat16):
@@ -91,24 +82,20 @@ class BatchedAntsEnv:
             self._pieced = bool(pieced_memory)
             self._h = None
             self._state = None
-            self._make_handle(torch.empty(self.record_bytes + 256, dtype=torch.uint8, device=self.device))
             E, N, P, K = cfg.n_envs, cfg.n_ants, cfg.pside, cfg.n_channels
             esz = 4 if obs_dtype == torch.float32 else 2
             row = P * P * K
             if obs_row_stride not in (None, "line"):
                 raise ValueError("obs_row_stride must be None or 'line'")
             pitch = row if obs_row_stride is None else (row * esz + 127) // 128 * 128 // esz
+            self._obs_dtype, self._obs_pitch_row = obs_dtype, (pitch, row)  # (what _make_handle sets the handle's format from)
+            self._make_handle(torch.empty(self.record_bytes + 256, dtype=torch.uint8, device=self.device))
             sizes = [("agent_state", E * N * 2 * 4), ("reward", E * N * 4), ("done", E), ("obs", E * N * pitch * esz)]
             offs, total = {}, 0
             for name, nbytes in sizes:
                 offs[name] = total
                 total += (nbytes + 255) // 256 * 256
             self._out_sizes, self._out_offs, self._out_total, self._small_bytes = sizes, offs, total, offs["obs"]
-            self._obs_dtype, self._obs_pitch_row = obs_dtype, (pitch, row)
-            if obs_dtype == torch.bfloat16:
-                _lib.check(self.lib.antsrl_set_obs_format(self._h, 1), "set_obs_format")
-            if pitch != row:
-                _lib.check(self.lib.antsrl_set_obs_row_stride(self._h, pitch), "set_obs_row_stride")
             self.obs_row_pitch = pitch
             self._bind_outputs(big(total + 256).zero_())
         self._keep = None
@@ -170,9 +157,9 @@ class BatchedAntsEnv:
             self._state_ptr = state.data_ptr() + (-state.data_ptr()) % 256
             _lib.check(self.lib.antsrl_create2(C.byref(self.cfg), C.c_void_p(self._state_ptr), self.state_bytes,
                                                C.c_void_p(self._ws_ptr), self.record_bytes, C.byref(self._h)), "create2")
-        if getattr(self, "_obs_dtype", torch.float32) == torch.bfloat16:
+        if self._obs_dtype == torch.bfloat16:
             _lib.check(self.lib.antsrl_set_obs_format(self._h, 1), "set_obs_format")
-        pitch, row = getattr(self, "_obs_pitch_row", (0, 0))
+        pitch, row = self._obs_pitch_row
         if pitch != row:
             _lib.check(self.lib.antsrl_set_obs_row_stride(self._h, pitch), "set_obs_row_stride")
 
@@ -215,162 +202,7 @@ class BatchedAntsEnv:
             # (it re-creates the handle: an episode, an activation matrix, an attached policy or timing events would be
             #  dropped silently, and a scratch episode would be left in their place — ADVICE r4)
             raise _lib.AntsrlError("tune_placement() must run right after construction: this handle has already been %s" % self._loaded)
-        c = self.cfg
-        E, N = c.n_envs, c.n_ants
-        dev = self.device
-
-        def torch_u8(n):
-            return torch.empty(n, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            g = torch.Generator(device=dev)
-            g.manual_seed(7)
-            rot = torch.randint(-1, 2, (4, E, N), generator=g, device=dev, dtype=torch.int8)
-            ph = torch.randint(0, 3, (4, E, N), generator=g, device=dev, dtype=torch.int8) if c.n_phero == 2 else [None] * 4
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-            def scratch_episode():
-                self.generate(cfgmod.make_gen(), episode_seed=0x7A11)
-                for t in range(age):
-                    self.step_update(rot[t % 4], ph[t % 4], None)
-
-            NEV, PSTEPS, PSTEPS_STATE = cfgmod.TIMING_EVENTS, 8, 24  # (stage two looks for 6 % on a kernel a fifth as long: more samples)
-            evs = _lib.HipEvents(NEV * PSTEPS_STATE)
-            prc_times = []  # the observation kernel alone, per trial: what the zones act on (the levels are read off THIS)
-            upd_times = []  # k_update_move alone, per trial (events [1]..[2]): what the second stage reads
-
-            def measure(psteps=PSTEPS):
-                for t in range(4):
-                    self.step_update(rot[t % 4], ph[t % 4], None)
-                e0.record()
-                for t in range(steps):
-                    self.step_update(rot[t % 4], ph[t % 4], None)
-                e1.record()
-                for t in range(psteps):  # (then a few steps with the library's timing hook: k_perceive by HIP events)
-                    self.set_timing_events([evs.ev[NEV * t + i].value for i in range(NEV)])
-                    self.step_update(rot[t % 4], ph[t % 4], None)
-                torch.cuda.current_stream(dev).synchronize()
-                prc_times.append(float(np.mean([evs.elapsed_ms(NEV * t + 2, NEV * t + 3) for t in range(psteps)])))
-                upd_times.append(float(np.mean([evs.elapsed_ms(NEV * t + 1, NEV * t + 2) for t in range(psteps)])))
-                return e0.elapsed_time(e1) / steps
-            # the env's own pair first (workspace torch.empty, outputs pieced unless pieced_memory=False), then the other three
-            own_ws, own_out, own_state = self._ws, self._out_flat, self._state
-            n_ws, n_out, n_state = self.record_bytes + 256, self._out_total + 256, self.state_bytes + 256
-            pairs, times = [], []
-            for ws_kind in ("own", "other"):
-                if ws_kind == "other":
-                    self._make_handle(vmm.empty_u8(n_ws, dev))  # (the env's own record block is torch.empty memory)
-                scratch_episode()
-                for out_kind in ("own", "other"):
-                    if out_kind == "other":
-                        self._bind_outputs((torch_u8(n_out) if self._pieced else vmm.empty_u8(n_out, dev)).zero_())
-                    elif ws_kind == "other":
-                        self._bind_outputs(own_out)
-                    pairs.append((self._ws, self._out_flat))
-                    times.append(measure())
-            labels = ["ws torch / out %s" % ("pieced" if self._pieced else "torch"),
-                      "ws torch / out %s" % ("torch" if self._pieced else "pieced"),
-                      "ws pieced / out %s" % ("pieced" if self._pieced else "torch"),
-                      "ws pieced / out %s" % ("torch" if self._pieced else "pieced")]
-            if extra_outputs > 0 and self._pieced:
-                self._make_handle(own_ws)
-                scratch_episode()
-                for k in range(int(extra_outputs)):
-                    self._bind_outputs(vmm.empty_u8(n_out, dev).zero_())
-                    pairs.append((self._ws, self._out_flat))
-                    times.append(measure())
-                    labels.append("ws torch / out pieced (draw %d)" % (k + 2))
-            # Both levels seen?  If not, walk further into the device's memory until a buffer of another zone turns up.
-            spacers = []
-            walked = 0
-            both_levels = placement_levels_seen
-            while self._pieced and walked < int(walk_spacers) and (force_walk or not both_levels(prc_times)):
-                # one step of the walk: a spacer from EACH allocator (hipMalloc and the virtual-memory one draw from
-                # different ends of the device's memory: profiles/r05/two_colour.txt), then one more output buffer of each
-                # kind against the env's own workspace, and the env's own output buffer against one more torch workspace
-                free_b = torch.cuda.mem_get_info(dev)[0]
-                want = int(min(spacer_gib * 2 ** 30, free_b / 5))
-                if want < (4 << 30):
-                    break
-                try:
-                    spacers.append(torch_u8(want))
-                    spacers.append(vmm.empty_u8(want, dev))
-                except (RuntimeError, _lib.AntsrlError):
-                    break
-                walked += 1
-                depth = sum(x.numel() for x in spacers) / 2 ** 30
-                if self._ws.data_ptr() != own_ws.data_ptr():
-                    self._make_handle(own_ws)
-                scratch_episode()
-                for kind, mk in (("pieced", lambda: vmm.empty_u8(n_out, dev)), ("torch", lambda: torch_u8(n_out))):
-                    self._bind_outputs(mk().zero_())
-                    pairs.append((self._ws, self._out_flat))
-                    times.append(measure())
-                    labels.append("ws torch / out %s (walk %d: +%.0f GiB)" % (kind, walked, depth))
-                self._make_handle(torch_u8(n_ws))
-                scratch_episode()
-                self._bind_outputs(own_out)
-                pairs.append((self._ws, self._out_flat))
-                times.append(measure())
-                labels.append("ws torch (walk %d: +%.0f GiB) / out %s" % (walked, depth, "pieced" if self._pieced else "torch"))
-            # the pair with the fastest observation kernel (the step time around it carries the timing hook's own stalls)
-            best = min(range(len(times)), key=prc_times.__getitem__)
-            if verbose:
-                print("tune_placement: ms/step per (workspace, outputs) pair %s -> %d" % (["%.4f" % t for t in times], best))
-            ws, out = pairs[best]
-            n_stage1 = len(times)
-            # Stage two: that pair stays; the STATE block — what k_update_move streams while it scatters into the records — is
-            # tried on the env's own torch.empty block, a pieced one, and a corner of the record blocks the first stage drew
-            # and did not keep (other zones, already paid for); k_update_move's own time decides.
-            state_cands = [("state torch (default)", own_state)]
-            if state_stage and self._split:
-                try:
-                    state_cands.append(("state pieced", vmm.pieced_u8(n_state, dev)))
-                except _lib.AntsrlError:
-                    pass
-                seen = {ws.data_ptr()}
-                for (w2, _o), lab in zip(pairs, labels):
-                    if w2.data_ptr() not in seen and w2.numel() >= n_state and len(state_cands) < 4:
-                        seen.add(w2.data_ptr())
-                        state_cands.append(("state in spare record block (%s)" % lab.split(" / ")[0], w2[:n_state]))
-            for lab, st in state_cands if len(state_cands) > 1 else []:
-                self._make_handle(ws, st)
-                self._bind_outputs(out)
-                scratch_episode()
-                times.append(measure(PSTEPS_STATE))
-            evs.destroy()
-            s_upd, s_prc = upd_times[n_stage1:], prc_times[n_stage1:]
-            times, prc_times, upd_times = times[:n_stage1], prc_times[:n_stage1], upd_times[:n_stage1]
-            s_best = 0
-            if s_upd:
-                # The two levels of k_update_move lie 6 % apart (0.0340 / 0.0320 ms at c3); a candidate replaces the default only
-                # when it is faster by half of that — anything less is one level, measured twice — and k_perceive, the larger
-                # kernel, has not paid for it.
-                # A block of its own comes before a corner of a spare record block, whose other bytes (1 GB at c3) would stay
-                # allocated for nothing: a corner is kept only where no block of its own reaches the fast level, and only for
-                # 5 % (corners measure 2-4 % under a default that is already on the fast level: profiles/r06).
-                def fast(k, by):
-                    return s_upd[k] <= (1.0 - by) * s_upd[0] and s_upd[k] + s_prc[k] < s_upd[0] + s_prc[0]
-                own = [k for k in range(1, len(s_upd)) if state_cands[k][0] == "state pieced" and fast(k, 0.03)]
-                corners = [k for k in range(1, len(s_upd)) if state_cands[k][0] != "state pieced" and fast(k, 0.05)]
-                if own or corners:
-                    s_best = min(own or corners, key=s_upd.__getitem__)
-            state = state_cands[s_best][1]
-            state_labels = [lab for lab, _ in state_cands]
-            del pairs, spacers, state_cands
-            if ws.data_ptr() != self._ws.data_ptr() or (state is not None and state.data_ptr() != self._state.data_ptr()):
-                self._make_handle(ws, state)
-            self._bind_outputs(out)
-            if walked:  # (the walk's spacers and losing buffers: torch's go back to the driver, the pool's are unmapped — their
-                vmm.trim()  # ranges retired, never re-used; without a walk the few losing buffers simply stay pooled)
-            torch.cuda.empty_cache()
-            self._out_flat.zero_()
-            del own_ws, own_out, own_state, ws, out, state
-        self.placement_trials = dict(ms_per_step=[round(t, 5) for t in times], observation_kernel_ms=[round(t, 5) for t in prc_times],
-                                     chosen=best, pairs=labels, both_levels_seen=bool(both_levels(prc_times)), walk_steps=walked,
-                                     state_stage=dict(candidates=state_labels, update_move_kernel_ms=[round(t, 5) for t in s_upd],
-                                                      observation_kernel_ms=[round(t, 5) for t in s_prc], chosen=s_best))
-        self._loaded = None  # (the scratch episodes were the tuner's own: the handle is as new)
-        return times
+        return Tuner(self, age, steps, verbose, extra_outputs, walk_spacers, spacer_gib, force_walk, state_stage).run()
 
     @property
     def _obs_buf(self):
@@ -524,16 +356,16 @@ class BatchedAntsEnv:
         """RLApi.step (RL_api.py:168-204) for all envs -> (obs, agent_state, reward, done)."""
         rot, ph = self._actions(rotation, phero)
         with self._on_device():
-            _lib.check(self.lib.antsrl_step(self._h, _ptr(rot), _ptr(ph), _ptr(self._obs_buf if want_obs else None),
-                                            _ptr(self.agent_state), _ptr(self.reward), _ptr(self.done),
+            _lib.check(self.lib.antsrl_step(self._h, _lib.ptr(rot), _lib.ptr(ph), _lib.ptr(self._obs_buf if want_obs else None),
+                                            _lib.ptr(self.agent_state), _lib.ptr(self.reward), _lib.ptr(self.done),
                                             self._stream()), "step")
         return self.obs, self.agent_state, self.reward, self.done
 
     def observe(self, want_obs: bool = True):
         """RLApi.observation (RL_api.py:96-165) -> (obs, agent_state, reward)."""
         with self._on_device():
-            _lib.check(self.lib.antsrl_observe(self._h, _ptr(self._obs_buf if want_obs else None),
-                                               _ptr(self.agent_state), _ptr(self.reward), self._stream()),
+            _lib.check(self.lib.antsrl_observe(self._h, _lib.ptr(self._obs_buf if want_obs else None),
+                                               _lib.ptr(self.agent_state), _lib.ptr(self.reward), self._stream()),
                        "observe")
         return self.obs, self.agent_state, self.reward
 
@@ -542,7 +374,7 @@ class BatchedAntsEnv:
         c = self.cfg
         j = self._dev(wall_jitter, torch.float64, (c.n_envs, c.n_ants))
         with self._on_device():
-            _lib.check(self.lib.antsrl_update(self._h, _ptr(j), self._stream()), "update")
+            _lib.check(self.lib.antsrl_update(self._h, _lib.ptr(j), self._stream()), "update")
 
     def update_phase(self, phase: int, wall_jitter=None) -> None:
         """antsrl_update_phase: one of the four reference steps of Environment.update (config.PHASE_WALLS,
@@ -551,7 +383,7 @@ class BatchedAntsEnv:
         c = self.cfg
         j = self._dev(wall_jitter, torch.float64, (c.n_envs, c.n_ants)) if phase == cfgmod.PHASE_WALLS else None
         with self._on_device():
-            _lib.check(self.lib.antsrl_update_phase(self._h, int(phase), _ptr(j), self._stream()), "update_phase")
+            _lib.check(self.lib.antsrl_update_phase(self._h, int(phase), _lib.ptr(j), self._stream()), "update_phase")
 
     def flush(self) -> None:
         """antsrl_flush: enqueue a deferred Environment.update now (before copying / checkpointing the workspace, or
@@ -566,9 +398,9 @@ class BatchedAntsEnv:
         rot, ph = self._actions(rotation, phero)
         j = self._dev(wall_jitter, torch.float64, (c.n_envs, c.n_ants))
         with self._on_device():
-            _lib.check(self.lib.antsrl_step_update(self._h, _ptr(rot), _ptr(ph), _ptr(j),
-                                                   _ptr(self._obs_buf if want_obs else None), _ptr(self.agent_state),
-                                                   _ptr(self.reward), _ptr(self.done), self._stream()),
+            _lib.check(self.lib.antsrl_step_update(self._h, _lib.ptr(rot), _lib.ptr(ph), _lib.ptr(j),
+                                                   _lib.ptr(self._obs_buf if want_obs else None), _lib.ptr(self.agent_state),
+                                                   _lib.ptr(self.reward), _lib.ptr(self.done), self._stream()),
                        "step_update")
         return self.obs, self.agent_state, self.reward, self.done
 
@@ -605,7 +437,7 @@ class BatchedAntsEnv:
         c = self.cfg
         a = self._dev(act, torch.float32, (c.n_envs, c.n_ants, c.n_phero))
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.antsrl_set_activation(self._h, _ptr(a), float(new_deposit_strength),
+            _lib.check(self.lib.antsrl_set_activation(self._h, _lib.ptr(a), float(new_deposit_strength),
                                                       self._stream()), "set_activation")
         self._loaded = "given an activation matrix"
 
@@ -615,26 +447,17 @@ class BatchedAntsEnv:
         c = self.cfg
         out = torch.empty((c.n_envs, c.w, c.h), dtype=torch.uint8, device=self.device)
         with self._on_device():
-            _lib.check(self.lib.antsrl_perceptive_field(self._h, _ptr(out), self._stream()), "perceptive_field")
+            _lib.check(self.lib.antsrl_perceptive_field(self._h, _lib.ptr(out), self._stream()), "perceptive_field")
         return out.to(torch.bool)
 
     def read_state(self, which: int) -> torch.Tensor:
         c = self.cfg
-        E, N, W, H, Cn, R = c.n_envs, c.n_ants, c.w, c.h, c.n_phero, c.n_rocks
-        shapes = {
-            cfgmod.S_ANTS_XYT: (E, N, 3), cfgmod.S_PREV_XY: (E, N, 2), cfgmod.S_HOLDING: (E, N),
-            cfgmod.S_MANDIBLES: (E, N), cfgmod.S_ACTIVATION: (E, N, Cn), cfgmod.S_PHERO: (E, Cn, W, H),
-            cfgmod.S_FOOD: (E, W, H), cfgmod.S_EXPLORED: (E, W, H), cfgmod.S_ANTHILL_FOOD: (E,),
-            cfgmod.S_ROCK_CENTERS: (E, R, 2), cfgmod.S_TIMESTEP: (E,), cfgmod.S_REWARD_STATE: (E, N),
-            cfgmod.S_WALLS: (E, W, H), cfgmod.S_ANTHILL_AREA: (E, W, H), cfgmod.S_SEED: (E, N),
-            cfgmod.S_ANTHILL_XYR: (E, 3), cfgmod.S_ROCK_RW: (E, R, 2),
-            cfgmod.S_PHERO_C0: (E, W, H), cfgmod.S_PHERO_C1: (E, W, H), cfgmod.S_PHERO_C2: (E, W, H),
-            cfgmod.S_PHERO_C3: (E, W, H),
-        }
-        if cfgmod.S_PHERO_C0 <= which <= cfgmod.S_PHERO_C3 and which - cfgmod.S_PHERO_C0 >= Cn:
-            raise _lib.AntsrlError("pheromone channel %d of %d" % (which - cfgmod.S_PHERO_C0, Cn))
-        out = torch.empty(shapes[which], dtype=_STATE_DTYPES[which], device=self.device)
+        dims = dict(E=c.n_envs, N=c.n_ants, W=c.w, H=c.h, C=c.n_phero, R=c.n_rocks)
+        if cfgmod.S_PHERO_C0 <= which <= cfgmod.S_PHERO_C3 and which - cfgmod.S_PHERO_C0 >= c.n_phero:
+            raise _lib.AntsrlError("pheromone channel %d of %d" % (which - cfgmod.S_PHERO_C0, c.n_phero))
+        dtype, shape = _STATE_ARRAYS[which]
+        out = torch.empty([dims.get(d, d) for d in shape], dtype=dtype, device=self.device)
         if out.numel():
             with torch.cuda.device(self.device):
-                _lib.check(self.lib.antsrl_read_state(self._h, which, _ptr(out), self._stream()), "read_state")
+                _lib.check(self.lib.antsrl_read_state(self._h, which, _lib.ptr(out), self._stream()), "read_state")
         return out

@@ -4,7 +4,8 @@ On MI355X the observation kernel runs 15 % slower when the observation tensor (a
 records (scattered gathers) lie in the same ZONE of the device's memory (profiles/r05/two_colour.txt).  In a
 fresh process hipMalloc (what torch.empty ends in) and the HIP virtual-memory allocator draw from different zones: the
 observation tensor on antsrl_mem_alloc pieces + the workspace on torch.empty is a fast pair (k_perceive 0.167 against 0.197 ms
-at c3), two torch.empty buffers the slow one; BatchedAntsEnv.tune_placement measures the device at hand.
+at c3), two torch.empty buffers the slow one; BatchedAntsEnv.tune_placement (antsrl_amd/placement.py) measures the
+device at hand.
 `pieced_u8(nbytes, device)` is a uint8 tensor over such memory.  PyTorch stays plumbing: the tensor wraps the pointer through
 `__cuda_array_interface__`."""
 from __future__ import annotations
