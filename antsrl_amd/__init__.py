@@ -4,7 +4,7 @@ from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
-           "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats"]
+           "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -20,6 +20,9 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "ExploreTrainer":
         from .train import ExploreTrainer
         return ExploreTrainer
+    if name == "JointTrainer":
+        from .train import JointTrainer
+        return JointTrainer
     if name == "ReworkTrainer":
         from .train import ReworkTrainer
         return ReworkTrainer

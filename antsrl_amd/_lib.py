@@ -30,7 +30,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_reworktrain_apply", "antsrl_reworktrain_step", "antsrl_policy_rework_select", "antsrl_monitor_sizes",
            "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
            "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames",
-           "antsrl_stats_sizes", "antsrl_stats_row")
+           "antsrl_stats_sizes", "antsrl_stats_row", "antsrl_jointtrain_sizes", "antsrl_jointtrain_grad",
+           "antsrl_jointtrain_apply", "antsrl_jointtrain_step")
 
 _lib = None
 
@@ -151,6 +152,11 @@ def load() -> C.CDLL:
     lib.antsrl_exptrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
     lib.antsrl_exptrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
                                                              C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.antsrl_jointtrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
+    lib.antsrl_jointtrain_grad.argtypes = [i32] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
+    lib.antsrl_jointtrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    lib.antsrl_jointtrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
+                                                               C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.antsrl_rework_collapsed_bytes.argtypes = [C.POINTER(AntsReworkShape), sz]
     lib.antsrl_rework_collapse.argtypes = [C.POINTER(AntsReworkShape), C.POINTER(vp), vp, vp]
     lib.antsrl_policy_rework.argtypes = [C.POINTER(AntsReworkShape), vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp]

@@ -40,7 +40,7 @@ from . import _lib
 from ._lib import ptr as _p
 from . import config as cm
 from .replay import DeviceReplayMemory
-from .train import ExploreTrainer, LinearTrainer, MemoryTrainer, ReworkTrainer
+from .train import ExploreTrainer, JointTrainer, LinearTrainer, MemoryTrainer, ReworkTrainer
 
 
 def _backend(api_or_env):
@@ -349,6 +349,10 @@ class CollectAgent(_InLoopAgent):
     agent_states rows, and the memory-less entries antsrl_agent_select_actions / antsrl_replay_record_*_plain (the
     memory agent's kernels, draw specification and stream tags).
 
+    `train_layer1=True` lifts the reference's freeze of layer1 and changes nothing else (the curriculum's third stage,
+    DESIGN §7.21): setup builds a `JointTrainer`, whose step trains all six tensors; layer1 and layer2 stay shared with the
+    target net, so every training step moves the acting weights, as it does with the freeze in place.
+
     `inloop=True` (_InLoopAgent): a training step changes layer2, so while the agent trains at every step the in-loop
     actions of the step before are one update old and are not used: in-loop acting pays off for the steps that do not
     train (below min_replay, training=False), and the handle is refreshed at the first step that will not train after
@@ -362,17 +366,20 @@ class CollectAgent(_InLoopAgent):
     def __init__(self, epsilon: float = 0.1, discount: float = 0.5, rotations: int = 3, pheromones: int = 3,
                  learning_rate: float = 1e-4, *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0,
-                 inloop: bool = False):
+                 inloop: bool = False, train_layer1: bool = False):
         assert rotations == 3 and pheromones == 3, "the linear net's heads are 3 wide (antsrl_policy_mlp)"
         super().__init__("collect_agent", epsilon, discount, rotations, pheromones, learning_rate, record_per_step,
                          replay_size, minibatch, min_replay, update_target_every, seed, inloop=inloop)
+        self.train_layer1 = bool(train_layer1)
 
     def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None) -> None:
         """CollectAgent.setup (:75-98) for every ant of the batch.  `explore_model`: a four-tensor ExploreModel state_dict
         file (ExploreAgent.save_model) whose layer1 and layer2 go under the collect heads (:84, the curriculum's second
-        stage: layer1 stays frozen from here on); applied behind `trained_model`, layer3 stays as it is."""
+        stage: layer1 stays frozen from here on, unless `train_layer1`); applied behind `trained_model`, layer3 stays as
+        it is."""
         env = self._setup(api_or_env, [2])
-        self.trainer = LinearTrainer(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
+        trainer_cls = JointTrainer if self.train_layer1 else LinearTrainer
+        self.trainer = trainer_cls(self.n_features, self.device, discount=self.discount, lr=self.learning_rate,
                                      update_target_every=self.update_target_every, seed=self.seed)
         if trained_model is not None:
             self.load_model(trained_model)

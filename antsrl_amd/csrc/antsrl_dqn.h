@@ -1,6 +1,6 @@
 // antsrl_dqn.h — what every on-device DQN training step takes from the replay arrays, whichever net it trains.  The
 // minibatch's fields carry one set of names in DqnBatch (below: the 32-wide nets', in front of the net's own pointers in
-// LinTrainArgs, antsrl_lintrain.h, and ExpTrainArgs, antsrl_exptrain.h) and in ReworkTrainArgs (antsrl_reworktrain.h),
+// LinTrainArgs, antsrl_lintrain.h, ExpTrainArgs, antsrl_exptrain.h, and JointTrainArgs, antsrl_jointtrain.h) and in ReworkTrainArgs (antsrl_reworktrain.h),
 // so one host function checks and fills them for every entry (antsrl_dqn_minibatch) and one device function clamps idx
 // into the ring (dqn_row).  Adam's part is AdamArgs (antsrl_adam.h); antsrl_dqn_dev.h holds the device code the two
 // 32-wide steps share.
@@ -9,6 +9,9 @@
 #include "antsrl_fail.h"
 
 #define DQN_HIDDEN 32 // layer1's outputs
+// the layer1 stage the steps that train layer1 share (dqn_l1_stage, antsrl_dqn_dev.h)
+#define DQN_L1_WAVES 16 // waves per workgroup: wave w walks rows w, w + 16, ...
+#define DQN_L1_SLAB 8   // columns of the [32][F + 3] product one workgroup owns
 
 struct DqnBatch {
     const float *states, *agent_states, *rewards, *new_states, *new_agent_states;

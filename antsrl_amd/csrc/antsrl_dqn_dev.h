@@ -1,7 +1,8 @@
-// antsrl_dqn_dev.h — the device code the linear agent's training step (antsrl_lintrain.hip) and the explore agent's
-// (antsrl_exptrain.hip) share, once: the acting kernel's layer-1 sequence (k_policy_flat, antsrl_policy.hip) as the
-// training forward restates it, the 3-output head and the tail of the epilogues (the clamp that keeps idx inside the
-// ring, dqn_row, is antsrl_dqn.h's: the rework agent's step takes it too).  Every helper is force-inlined and the build
+// antsrl_dqn_dev.h — the device code the linear agent's training step (antsrl_lintrain.hip), the explore agent's
+// (antsrl_exptrain.hip) and the joint step (antsrl_jointtrain.hip) share, once: the acting kernel's layer-1 sequence
+// (k_policy_flat, antsrl_policy.hip) as the training forward restates it, the 3-output head, the tail of the epilogues
+// and the layer1 stage of the two steps that train layer1 (the clamp that keeps idx inside the ring, dqn_row, is
+// antsrl_dqn.h's: the rework agent's step takes it too).  Every helper is force-inlined and the build
 // has -ffp-contract=off: a caller computes the bits it computed with the helper's body written out.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -84,4 +85,88 @@ __device__ __forceinline__ void dqn_store_adam(float *params, float *grads, cons
 {
     if (grads) grads[i] = total;
     if (o.on) adam_at(params, o, i, total);
+}
+
+// ---- the layer1 stage of a step that trains layer1 (k_exptrain_l1, antsrl_exptrain.hip; k_jointtrain_l1,
+// antsrl_jointtrain.hip): one body, the net's flat block described by DqnL1Layout ------------------------------------------
+#define DQN_L1_UNROLL 8 // rows per wave in flight
+
+// where a flat block [w1 [32][F + 2] at 0 | ...] keeps what the stage writes, and what the forward stage left it
+struct DqnL1Layout {
+    size_t b1;    // offset of b1 [32]
+    size_t heads; // offset of the floats behind layer1 whose gradients the forward stage's partials hold
+    int nout;     // partial sums per workgroup of the forward stage: the heads' gradients in the block's order, then the loss
+    int pitch;    // floats per row of the partials
+};
+
+__device__ __forceinline__ float dqn_bf16(const float x) { return (float)(__bf16)x; }
+
+// columns k0 .. k0 + 3 of xe[b] = bf16(states[ri]) ++ bf16(agent_states[ri]) ++ 1 (zero beyond)
+__device__ __forceinline__ void dqn_xe_cols(const DqnBatch &a, const long long ri, const int k0, float (&x)[4])
+{
+    const int F = a.F;
+    if (k0 + 3 < F) {
+        const DqnF4 v = *reinterpret_cast<const DqnF4 *>(a.states + (size_t)ri * F + k0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = dqn_bf16(v.v[i]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int k = k0 + i;
+            if (k < F) x[i] = dqn_bf16(a.states[(size_t)ri * F + k]);
+            else if (k < F + 2) x[i] = dqn_bf16(a.agent_states[(size_t)ri * 2 + (k - F)]);
+            else x[i] = k == F + 2 ? 1.0f : 0.0f;
+        }
+    }
+}
+
+// The body of a layer1 stage's kernel: 64 * DQN_L1_WAVES threads, nslabs + 1 workgroups, red [DQN_L1_WAVES * 32 *
+// DQN_L1_SLAB] floats of LDS.  Workgroup s < nslabs owns columns 8 s .. 8 s + 7 of
+//     g[j][k] = sum_b dh[b][j] * xe[b][k]       (columns 0 .. F + 1 are g_w1, column F + 2 is g_b1):
+// lane (j, c) = (lane & 31, lane >> 5) of wave w keeps the four columns 8 s + 4 c .. + 3 of hidden unit j and walks rows
+// w, w + 16, ... in ascending order, one fmaf per row and column from zero, DQN_L1_UNROLL rows' loads in flight; the 16
+// waves' sums are added in wave order from wave 0's; the workgroup writes the gradient and runs Adam on its own columns.
+// Workgroup nslabs adds the forward stage's partials in workgroup order, writes the heads' gradients and the loss and
+// runs Adam on the heads.
+__device__ __forceinline__ void dqn_l1_stage(const DqnBatch &mb, float *params, const AdamArgs &adam, const float *dh,
+                                             const int blocks, const int nslabs, const DqnL1Layout lay, float *red)
+{
+    const int IN = mb.F + 2;
+    if ((int)blockIdx.x == nslabs) { // the heads and the loss: the forward stage's partials in workgroup order
+        if ((int)threadIdx.x >= lay.nout) return;
+        float s = 0.0f;
+        for (int b = 0; b < blocks; ++b) s += mb.partials[(size_t)b * lay.pitch + threadIdx.x];
+        if ((int)threadIdx.x == lay.nout - 1) *mb.loss = s;
+        else dqn_store_adam(params, mb.grads, adam, lay.heads + threadIdx.x, s);
+        return;
+    }
+    const int lane = threadIdx.x & 63, j = lane & 31, c = lane >> 5, wib = threadIdx.x >> 6;
+    const int k0 = blockIdx.x * DQN_L1_SLAB + 4 * c;
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll 1
+    for (int b0 = wib; b0 < mb.B; b0 += DQN_L1_WAVES * DQN_L1_UNROLL) {
+        float d[DQN_L1_UNROLL], x[DQN_L1_UNROLL][4];
+#pragma unroll
+        for (int u = 0; u < DQN_L1_UNROLL; ++u) { // the loads of DQN_L1_UNROLL rows first: they do not depend on one another
+            const int b = min(b0 + DQN_L1_WAVES * u, mb.B - 1);
+            d[u] = dh[(size_t)b * DQN_HIDDEN + j];
+            dqn_xe_cols(mb, dqn_row(mb, b), k0, x[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < DQN_L1_UNROLL; ++u)
+            if (b0 + DQN_L1_WAVES * u < mb.B) { // (uniform in the wave)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) acc[i] = fmaf(d[u], x[u][i], acc[i]);
+            }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[(wib * DQN_HIDDEN + j) * DQN_L1_SLAB + 4 * c + i] = acc[i];
+    __syncthreads();
+    if (threadIdx.x >= DQN_HIDDEN * DQN_L1_SLAB) return;
+    const int jj = threadIdx.x >> 3, col = threadIdx.x & 7, k = blockIdx.x * DQN_L1_SLAB + col;
+    float s = red[jj * DQN_L1_SLAB + col];
+#pragma unroll
+    for (int w = 1; w < DQN_L1_WAVES; ++w) s += red[(w * DQN_HIDDEN + jj) * DQN_L1_SLAB + col];
+    if (k < IN) dqn_store_adam(params, mb.grads, adam, (size_t)jj * IN + k, s);
+    else if (k == IN) dqn_store_adam(params, mb.grads, adam, lay.b1 + jj, s);
 }

@@ -23,9 +23,9 @@
 #define ET_OUT 100          // what the forward stage sums over rows: layer2's 99 gradients and the loss
 #define ET_PART 104         // floats per workgroup in the partials (ET_OUT rounded up to 16 bytes)
 #define ET_WAVES 4          // waves per workgroup of the forward stage: it takes 4 tiles of 32 rows
-#define ET_L1_WAVES 16      // waves per workgroup of the layer1 stage: wave w walks rows w, w + 16, ...
+#define ET_L1_WAVES DQN_L1_WAVES // waves per workgroup of the layer1 stage: wave w walks rows w, w + 16, ...
 #define ET_MAX_B 65536      // rows of a minibatch
-#define ET_SLAB 8           // columns of layer1 one workgroup of the layer1 stage owns
+#define ET_SLAB DQN_L1_SLAB // columns of layer1 one workgroup of the layer1 stage owns
 
 struct ExpTrainArgs {
     DqnBatch batch;           // grads: P floats; partials: [workgroups of the forward stage][ET_PART]

@@ -13,7 +13,7 @@
 // The wave leaves h (with a column of ones for b2) and dq (with the row's loss term) in its LDS tile, and lane l sums
 // outputs l and l + 64 of the 100 (layer2's 99 gradients, the loss) over the tile's 32 rows in row order from zero; the
 // workgroup adds its four waves' sums in wave order and writes them to its row of the partials.
-// Stage 2 (k_exptrain_l1).  Workgroup s < S = ceil((F + 3) / 8) owns columns 8 s .. 8 s + 7 of the [32][F + 3] product
+// Stage 2 (k_exptrain_l1: dqn_l1_stage, antsrl_dqn_dev.h, shared with the joint step).  Workgroup s < S = ceil((F + 3) / 8) owns columns 8 s .. 8 s + 7 of the [32][F + 3] product
 //     g[j][k] = sum_b dh[b][j] * xe[b][k],      xe[b] = bf16(states[i_b]) ++ bf16(agent_states[i_b]) ++ 1
 // (columns 0 .. F + 1 are g_w1, column F + 2 is g_b1).  Lane (j, c) = (lane & 31, lane >> 5) of wave w keeps the four
 // columns 8 s + 4 c .. + 3 of hidden unit j and walks rows w, w + 16, w + 32, ... (16 waves) in ascending order, one fmaf per
@@ -33,7 +33,6 @@
 #define ET_DSTRIDE 4  // floats per row of its dq tile: 3 dq, the loss term
 #define ET_SLOT 100   // floats per layer2 in LDS: [3][32] + [3], padded to 16 bytes
 #define ET_TILE (32 * ET_HSTRIDE + 32 * ET_DSTRIDE)
-#define ET_UNROLL 8   // rows per wave in flight in stage 2
 
 __device__ __forceinline__ float et_bf16(const float x) { return (float)(__bf16)x; }
 
@@ -167,67 +166,12 @@ __global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainAr
     }
 }
 
-// columns k0 .. k0 + 3 of xe[b] = bf16(states[ri]) ++ bf16(agent_states[ri]) ++ 1 (zero beyond)
-__device__ __forceinline__ void et_cols(const DqnBatch &a, const long long ri, const int k0, float (&x)[4])
-{
-    const int F = a.F;
-    if (k0 + 3 < F) {
-        const DqnF4 v = *reinterpret_cast<const DqnF4 *>(a.states + (size_t)ri * F + k0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) x[i] = et_bf16(v.v[i]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int k = k0 + i;
-            if (k < F) x[i] = et_bf16(a.states[(size_t)ri * F + k]);
-            else if (k < F + 2) x[i] = et_bf16(a.agent_states[(size_t)ri * 2 + (k - F)]);
-            else x[i] = k == F + 2 ? 1.0f : 0.0f;
-        }
-    }
-}
-
+// the layer1 stage: dqn_l1_stage (antsrl_dqn_dev.h) on ExploreModel's block, b1 behind w1 and layer2 behind b1
 __global__ void __launch_bounds__(64 * ET_L1_WAVES) k_exptrain_l1(const ExpTrainArgs a, const int nslabs)
 {
     __shared__ float red[ET_L1_WAVES * ET_HIDDEN * ET_SLAB];
-    const DqnBatch &mb = a.batch;
-    const int F = mb.F, IN = F + 2;
-    if ((int)blockIdx.x == nslabs) { // layer2 and the loss: stage 1's partials in workgroup order
-        if (threadIdx.x >= ET_OUT) return;
-        float s = 0.0f;
-        for (int b = 0; b < a.blocks; ++b) s += mb.partials[(size_t)b * ET_PART + threadIdx.x];
-        if (threadIdx.x == ET_L2) *mb.loss = s;
-        else dqn_store_adam(a.model, mb.grads, a.adam, (size_t)ET_HIDDEN * IN + ET_HIDDEN + threadIdx.x, s);
-        return;
-    }
-    const int lane = threadIdx.x & 63, j = lane & 31, c = lane >> 5, wib = threadIdx.x >> 6;
-    const int k0 = blockIdx.x * ET_SLAB + 4 * c;
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll 1
-    for (int b0 = wib; b0 < mb.B; b0 += ET_L1_WAVES * ET_UNROLL) {
-        float d[ET_UNROLL], x[ET_UNROLL][4];
-#pragma unroll
-        for (int u = 0; u < ET_UNROLL; ++u) { // the loads of ET_UNROLL rows first: they do not depend on one another
-            const int b = min(b0 + ET_L1_WAVES * u, mb.B - 1);
-            d[u] = a.dh[(size_t)b * ET_HIDDEN + j];
-            et_cols(mb, dqn_row(mb, b), k0, x[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < ET_UNROLL; ++u)
-            if (b0 + ET_L1_WAVES * u < mb.B) { // (uniform in the wave)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = fmaf(d[u], x[u][i], acc[i]);
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[(wib * ET_HIDDEN + j) * ET_SLAB + 4 * c + i] = acc[i];
-    __syncthreads();
-    if (threadIdx.x >= ET_HIDDEN * ET_SLAB) return;
-    const int jj = threadIdx.x >> 3, col = threadIdx.x & 7, k = blockIdx.x * ET_SLAB + col;
-    float s = red[jj * ET_SLAB + col];
-#pragma unroll
-    for (int w = 1; w < ET_L1_WAVES; ++w) s += red[(w * ET_HIDDEN + jj) * ET_SLAB + col];
-    if (k < IN) dqn_store_adam(a.model, mb.grads, a.adam, (size_t)jj * IN + k, s);
-    else if (k == IN) dqn_store_adam(a.model, mb.grads, a.adam, (size_t)ET_HIDDEN * IN + jj, s);
+    const size_t ob1 = (size_t)ET_HIDDEN * (a.batch.F + 2);
+    dqn_l1_stage(a.batch, a.model, a.adam, a.dh, a.blocks, nslabs, DqnL1Layout{ob1, ob1 + ET_HIDDEN, ET_OUT, ET_PART}, red);
 }
 
 static size_t et_lds(int ksteps)

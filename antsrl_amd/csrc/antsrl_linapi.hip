@@ -1,7 +1,8 @@
 // antsrl_linapi.hip — the linear agent's training step in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The linear
 // agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels, and
 // behind them the explore agent's ("The explore agent's training step"): antsrl_exptrain_sizes / _grad / _apply / _step
-// in front of antsrl_exptrain.hip's, with the same argument rules.  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
+// in front of antsrl_exptrain.hip's, and the joint step's ("The joint training step"): antsrl_jointtrain_sizes / _grad /
+// _apply / _step in front of antsrl_jointtrain.hip's, all with the same argument rules.  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
 // what every step takes from the replay arrays, the rework agent's (antsrl_reworkapi.hip) included; dqn_batch adds what
 // the 32-wide nets keep in DqnBatch, antsrl_adam_args (antsrl_adam.h) Adam's part; an entry checks its own net's
 // pointers, its limit on B and its workspace rule.
@@ -16,6 +17,7 @@
 #include "antsrl_dqn.h"
 #include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
+#include "antsrl_jointtrain.h"
 #include "antsrl_lintrain.h"
 
 #define LT_MAX_B (1 << 24)
@@ -212,4 +214,90 @@ extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const floa
     if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
     a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who);
+}
+
+// ---- the joint training step: layer1 under the collect heads (antsrl_jointtrain.hip) ---------------------------------------
+
+static int jt_B(const char *who, int64_t B)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > JT_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, JT_MAX_B);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_jointtrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
+                                       int32_t *launches)
+{
+    const char *who = "jointtrain_sizes";
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = jt_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    if (trained_floats) *trained_floats = antsrl_jointtrain_floats(n_features);
+    if (workspace_bytes) *workspace_bytes = antsrl_jointtrain_dh_offset((int)B) + (size_t)B * JT_HIDDEN * sizeof(float);
+    if (launches) *launches = 2;
+    return ANTSRL_OK;
+}
+
+// the net and the workspace of the gradient stage and the fused step
+static int jt_net(const char *who, int32_t n_features, int64_t B, float *model, const float *target_l3, void *workspace,
+                  JointTrainArgs *a)
+{
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = jt_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    REQUIRE(target_l3, 4);
+    REQUIRE(workspace, 256);
+    a->model = model; a->target_l3 = target_l3;
+    a->dh = (float *)((unsigned char *)workspace + antsrl_jointtrain_dh_offset((int)B));
+    a->blocks = antsrl_jointtrain_blocks((int)B);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_jointtrain_grad(int32_t n_features, const float *model, const float *target_l3, const float *states,
+                                      const float *agent_states, const int64_t *actions, const float *rewards,
+                                      const float *new_states, const float *new_agent_states, const uint8_t *dones,
+                                      int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, float *loss,
+                                      void *workspace, void *stream)
+{
+    const char *who = "jointtrain_grad";
+    JointTrainArgs a = {};
+    int rc = jt_net(who, n_features, B, const_cast<float *>(model), target_l3, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, true, loss, workspace, &a.batch);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_jointtrain(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
+}
+
+extern "C" int antsrl_jointtrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
+                                       int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
+{
+    const char *who = "jointtrain_apply";
+    const int rc = lt_features(who, n_features);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps,
+                             (int)antsrl_jointtrain_floats(n_features), stream);
+}
+
+extern "C" int antsrl_jointtrain_step(int32_t n_features, float *model, const float *target_l3, float *adam_m, float *adam_v,
+                                      const float *states, const float *agent_states, const int64_t *actions,
+                                      const float *rewards, const float *new_states, const float *new_agent_states,
+                                      const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount,
+                                      int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
+                                      float *loss, void *workspace, void *stream)
+{
+    const char *who = "jointtrain_step";
+    JointTrainArgs a = {};
+    int rc = jt_net(who, n_features, B, model, target_l3, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, false, loss, workspace, &a.batch);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    return enqueued(antsrl_launch_jointtrain(a, (hipStream_t)stream), who);
 }

@@ -25,9 +25,9 @@ TRAINED_LAYERS = MEMNET_LAYERS[:9]
 
 
 class _DqnTrainer:
-    """What the four trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
+    """What the five trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
     workspace, and train() around step().  A subclass holds its nets, writes grad / apply / step over its own entries
-    (_FlatTrainer does, for the three whose ABIs share one argument order), sync_target, and
+    (_FlatTrainer does, for the four whose ABIs share one argument order), sync_target, and
     `_sizes(B, workspace_bytes, launches)`, its antsrl_*train_sizes call."""
 
     minibatch = 264  # train()'s default: the reference class's
@@ -80,8 +80,8 @@ class _DqnTrainer:
         return a, N, B
 
     def launches(self, B: int) -> int:
-        """Kernel launches of one step on B rows (antsrl_lintrain_sizes: 1 up to 512 rows, else 2; antsrl_exptrain_sizes:
-        2; antsrl_reworktrain_sizes: 4)."""
+        """Kernel launches of one step on B rows (antsrl_lintrain_sizes: 1 up to 512 rows, else 2; antsrl_exptrain_sizes
+        and antsrl_jointtrain_sizes: 2; antsrl_reworktrain_sizes: 4)."""
         n = C.c_int32()
         self._sizes(B, None, C.byref(n))
         return n.value
@@ -266,16 +266,17 @@ class MemoryTrainer(_DqnTrainer):
 
 
 class _FlatTrainer(_DqnTrainer):
-    """What the linear, the explore and the rework trainer share on top of _DqnTrainer: their entries antsrl_<entry>_sizes
+    """What the linear, the explore, the joint and the rework trainer share on top of _DqnTrainer: their entries antsrl_<entry>_sizes
     / _grad / _apply / _step take one argument order behind the net's own leading arguments (include/antsrl.h), so the
     three stages are written once.  A subclass names its `entry`, writes `_sizes`, gives `_net()` (what _grad and _step
     take in front of the arrays) and `_apply_net()` (what _apply takes in front of Adam's m), keeps Adam's moments in
     `_adam` [2][P] and overrides `_weights_changed` when a training step moves its acting weights.
 
     The views are those of a net that is ONE flat block described by `_offs` (name -> (offset, shape)), `model` and
-    `target`: the explore and the rework trainer's.  The linear trainer's net has two parts and it writes its own."""
+    `target`: the explore and the rework trainer's (the joint trainer's `model`; its target is layer3 alone).  The linear
+    trainer's net has two parts and it writes its own."""
 
-    entry = None  # "lintrain", "exptrain", "reworktrain"
+    entry = None  # "lintrain", "exptrain", "jointtrain", "reworktrain"
 
     def _net(self) -> tuple:
         raise NotImplementedError
@@ -531,6 +532,102 @@ class ExploreTrainer(_FlatTrainer):
 
     def _apply_net(self) -> tuple:
         return self.n_features, _p(self.model)
+
+
+class JointTrainer(_FlatTrainer):
+    """CollectAgent's model, target model and optimizer on the device with the freeze of layer1 lifted and nothing else
+    changed: the third stage of the linear agent's curriculum, trained by `antsrl_jointtrain_step`
+    (antsrl_jointtrain.hip).  It is the reference's own train() (agents/collect_agent.py:105-148) once
+    requires_grad is set again on explore_model.layer1: the reference's Adam already holds all six tensors.
+
+    All six tensors are trained: ONE flat fp32 block `model` of P = 32 (F + 2) + 32 + 198 floats in
+    CollectModel.state_dict()'s order (include/antsrl.h).  Model and target net share one ExploreModel, so layer1 and
+    layer2 are live in both nets and only layer3 has a target copy, `target_l3` (99 floats).  `policy` is the acting
+    LinearPolicy (get_action acts with the target net, :166): its w1, b1, w2, b2 are views of `model` and its w3, b3 views
+    of `target_l3`, so it needs no copy after a step.  `version` counts the changes of the acting weights: every step
+    moves layer1 and layer2.
+
+    The surface is LinearTrainer's: grad / apply / step, train(replay, done), train_on, launches, state_dict /
+    load_state_dict under the reference's six names, load_explore_state_dict, target_state_dict, sync_target,
+    adam_state, grad_dict."""
+
+    entry = "jointtrain"
+
+    def __init__(self, n_features: int, device, discount: float = 0.5, lr: float = 1e-4, betas=(0.9, 0.999),
+                 eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
+        from .policy import LinearPolicy
+        super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
+        self.version = 0
+        IN = n_features + 2
+        shapes = ((32, IN), (32,), (3, 32), (3,), (3, 32), (3,))
+        self._offs, off = {}, 0
+        for k, shp in zip(LINEAR_NAMES, shapes):
+            self._offs[k] = (off, shp)
+            off += math.prod(shp)
+        tf = C.c_size_t()
+        _lib.check(self._lib.antsrl_jointtrain_sizes(n_features, 1, C.byref(tf), None, None), "jointtrain_sizes")
+        self.trained_floats = tf.value
+        assert self.trained_floats == off == 32 * IN + 230
+        p = LinearPolicy(n_features, self.device, seed=seed)
+        self.model = torch.cat([t.reshape(-1) for t in (p.w1, p.b1, p.w2, p.b2, p.w3, p.b3)]).contiguous()
+        self._l3 = slice(self._offs["layer3.weight"][0], off)  # layer3 in the block: the 99 floats the target copies
+        self.target_l3 = self.model[self._l3].clone()
+        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
+        mv = self._views(self.model)
+        p.w1, p.b1, p.w2, p.b2 = (mv[k] for k in LINEAR_NAMES[:4])                # the live layer1 and layer2
+        p.w3, p.b3 = self.target_l3[0:96].view(3, 32), self.target_l3[96:99]      # the target layer3
+        self.policy = p
+        if state_dict is not None:
+            self.load_state_dict(state_dict)
+
+    # ---- weights ------------------------------------------------------------------------------------------------
+    def target_state_dict(self) -> dict:
+        """The target net's: the shared layer1 and layer2, its own layer3."""
+        d = self.state_dict()
+        d["layer3.weight"], d["layer3.bias"] = self.target_l3[0:96].view(3, 32).clone(), self.target_l3[96:99].clone()
+        return d
+
+    def _load(self, sd, names) -> None:
+        views = self._views(self.model)
+        for k in names:
+            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+            assert tuple(src.shape) == tuple(views[k].shape), (k, tuple(src.shape), tuple(views[k].shape))
+            views[k].copy_(src)
+        self.version += 1
+
+    def load_state_dict(self, sd) -> None:
+        """CollectAgent.load_model (:182-184): sets the model AND the target net.  What LinearTrainer.load_state_dict
+        accepts: CollectModel's names, or ExploreModel's bare layer1 / layer2 (with layer3).  Adam's state is kept."""
+        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v
+              for k, v in sd.items()}
+        self._load(sd, LINEAR_NAMES)
+        self.target_l3.copy_(self.model[self._l3])
+
+    def load_explore_state_dict(self, sd) -> None:
+        """layer1 and layer2 from a four-tensor ExploreModel state_dict (LinearTrainer.load_explore_state_dict): layer3,
+        its target copy and Adam's state stay as they are."""
+        sd = {(k if k.startswith("explore_model.") else "explore_model." + k): v for k, v in sd.items()}
+        self._load(sd, LINEAR_NAMES[:4])
+
+    def sync_target(self) -> None:
+        """target := model (:143-146): layer3 is all the two nets do not share."""
+        self.target_l3.copy_(self.model[self._l3])
+        self.syncs += 1
+        self.version += 1
+
+    # ---- the stages ---------------------------------------------------------------------------------------------
+    def _sizes(self, B, workspace_bytes, launches):
+        _lib.check(self._lib.antsrl_jointtrain_sizes(self.n_features, B, None, workspace_bytes, launches), "jointtrain_sizes")
+
+    def _net(self) -> tuple:
+        return self.n_features, _p(self.model), _p(self.target_l3)
+
+    def _apply_net(self) -> tuple:
+        return self.n_features, _p(self.model)
+
+    def _weights_changed(self) -> None:
+        self.version += 1  # every step moves the live layer1 and layer2
 
 
 class ReworkTrainer(_FlatTrainer):

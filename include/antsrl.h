@@ -879,6 +879,65 @@ int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, 
                          const int64_t *idx, int64_t B, float discount, int64_t step, double lr, double beta1, double beta2,
                          double eps, float *grads, float *loss, void *workspace, void *stream);
 
+/* The joint training step: CollectAgent.train (agents/collect_agent.py:105-148) with the freeze of layer1 lifted and
+ * nothing else changed — the third stage of the linear agent's curriculum.  The reference's CollectModel clears
+ * requires_grad on explore_model.layer1 but its Adam is built over all of model.parameters(): with requires_grad set
+ * again, its own train() moves all six tensors, and that is what this is.  Model and target net share one ExploreModel,
+ * so layer1 and layer2 are live in both nets and only layer3 has a target copy (a target copy of layer1 would be another
+ * algorithm).  A net is ONE flat fp32 block of P = 32 (F + 2) + 32 + 198 floats in CollectModel.state_dict()'s order:
+ *   w1 [32][F + 2] at 0,  b1 [32] at 32 (F + 2),  w2 [3][32] at 32 (F + 2) + 32,  b2 [3] at 32 (F + 2) + 128,
+ *   w3 [3][32] at 32 (F + 2) + 131,  b3 [3] at 32 (F + 2) + 227
+ * (the last four are antsrl_lintrain_*'s `heads` block); target_l3 is float [99] (w3 [3][32], b3 [3]) and only read;
+ * adam_m, adam_v and grads are float [P], laid out as the net is, under ONE Adam step count.  Per minibatch row b (replay
+ * row i = idx[b], or b when idx is NULL; i is clamped to [0, n_rows); a_rot, a_ph = actions[i][0], actions[i][1], each
+ * clamped to 0..2), with x = states[i] ++ agent_states[i] and x' = new_states[i] ++ new_agent_states[i]:
+ *     h = layer1(x), h' = layer1(x')                      BOTH through the same live w1 (one bfloat16 image of it, not
+ *                                                         two), the acting kernel's sequence as for antsrl_lintrain_*: x
+ *                                                         and w1 rounded to bfloat16 (RNE), the F observation inputs
+ *                                                         through v_mfma_f32_32x32x16_bf16 in ascending 16-input steps
+ *                                                         from a zero accumulator, then
+ *                                                         acc + (x[F] w1[.][F] + x[F + 1] w1[.][F + 1]) + b1 in fp32
+ *     q_rot = layer2(h), q_ph = layer3(h)                 everything from here on is fp32 on the fp32 masters
+ *     y_rot = rewards[i] + discount * max(layer2(h')) * !dones[i]           the live layer2
+ *     y_ph  = rewards[i] + discount * max(target_layer3(h')) * !dones[i]    (the TD targets carry no gradient)
+ *     d_rot = q_rot[a_rot] - y_rot,  d_ph = q_ph[a_ph] - y_ph
+ *     loss  = sum_b (d_rot^2 / (3 B) + d_ph^2 / (3 B))    MSELoss over [B, 3] per head, the two added
+ *     dq_rot = d_rot * (2 / (3 B)) at a_rot, dq_ph = d_ph * (2 / (3 B)) at a_ph, 0 elsewhere
+ *     g_w2 = dq_rot^T h, g_b2 = sum_b dq_rot, g_w3 = dq_ph^T h, g_b3 = sum_b dq_ph
+ *     dh[b][j]   = dq_rot[b] * w2[a_rot][j] + dq_ph[b] * w3[a_ph][j]      two fp32 products and one add, each rounded
+ *                                                                          on its own, in that order
+ *     g_w1[j][k] = sum_b dh[b][j] * bf16(x[b][k])         all F + 2 columns, agent_state's two included
+ *     g_b1[j]    = sum_b dh[b][j]
+ * The gradient reaches layer1 only through the model's forward on x, from both heads; it is the straight-through gradient
+ * of antsrl_exptrain_* (bfloat16 x against the fp32 master w1).
+ * Order of the sums over rows (no atomics; equal inputs give equal bits):
+ *   the 198 head gradients, loss: the 32 rows of a tile in row order from zero (product rounded, then added); a workgroup
+ *       of the forward stage adds its four tiles' sums in tile order; the workgroups' sums are added in workgroup order.
+ *   g_w1, g_b1: antsrl_exptrain_*'s, by the same device code: rows w, w + 16, w + 32, ... in ascending order by one fmaf
+ *       per row from zero, for w = 0..15; then (((s0 + s1) + s2) + ...) + s15.
+ * Adam is antsrl_lintrain_*'s (antsrl_adam.h) on all P floats.  _grad followed by _apply gives the bits of _step.  The
+ * target sync is one device copy of layer3's 99 floats, the caller's.
+ * Launches: two at every B (the forward stage, one wave per 32 rows, four waves per workgroup; the layer1 stage, one
+ * workgroup per 8 columns of the [32][F + 3] product, and one more for the heads and the loss).  workspace (256-byte
+ * aligned, workspace_bytes: the forward stage's partial sums, [workgroups][200] floats rounded up to 256 bytes, then
+ * dh [B][32]; nothing follows row B - 1) is always needed.  Arrays as for antsrl_lintrain_*.  1 <= B <= 65536 (above:
+ * ANTSRL_E_UNSUPPORTED).  Every argument is checked before anything is launched; no host synchronisation.
+ *   _grad:  loss and grads; model is not written.
+ *   _apply: Adam on model from grads; step >= 1 is Adam's step count.
+ *   _step:  both in the same two launches (grads may be NULL). */
+int antsrl_jointtrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes, int32_t *launches);
+int antsrl_jointtrain_grad(int32_t n_features, const float *model, const float *target_l3, const float *states,
+                           const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                           const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                           float discount, float *grads, float *loss, void *workspace, void *stream);
+int antsrl_jointtrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads, int64_t step,
+                            double lr, double beta1, double beta2, double eps, void *stream);
+int antsrl_jointtrain_step(int32_t n_features, float *model, const float *target_l3, float *adam_m, float *adam_v,
+                           const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                           const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                           const int64_t *idx, int64_t B, float discount, int64_t step, double lr, double beta1, double beta2,
+                           double eps, float *grads, float *loss, void *workspace, void *stream);
+
 /* The rework agent's net (no kernel counterpart in the reference; replaces the network branch of
  * CollectAgentRework.get_action, agents/collect_agent_rework.py:165-174, which evaluates target_model's
  * CollectModelRework.forward, :49-63, on the host).  Per ant, x = cat[obs.view(F), agent_state(2)], D = F + 2:
