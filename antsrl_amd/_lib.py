@@ -31,7 +31,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
            "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames",
            "antsrl_stats_sizes", "antsrl_stats_row", "antsrl_jointtrain_sizes", "antsrl_jointtrain_grad",
-           "antsrl_jointtrain_apply", "antsrl_jointtrain_step")
+           "antsrl_jointtrain_apply", "antsrl_jointtrain_step", "antsrl_obs_coords", "antsrl_give_reward")
 
 _lib = None
 
@@ -100,6 +100,8 @@ def load() -> C.CDLL:
     lib.antsrl_flush.argtypes = [vp, vp]
     lib.antsrl_update_phase.argtypes = [vp, i32, vp, vp]
     lib.antsrl_perceptive_field.argtypes = [vp, vp, vp]
+    lib.antsrl_obs_coords.argtypes = [vp, vp, vp]
+    lib.antsrl_give_reward.argtypes = [vp, vp, C.c_double, vp, vp]
     lib.antsrl_step_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.antsrl_set_timing_events.argtypes = [vp, C.POINTER(vp)]
     lib.antsrl_set_activation.argtypes = [vp, vp, C.c_double, vp]

@@ -99,6 +99,8 @@ class BatchedAntsEnv:
             self.obs_row_pitch = pitch
             self._bind_outputs(big(total + 256).zero_())
         self._keep = None
+        self._reward_hook = None  # (fn, threshold, coords) of set_reward_hook
+        self._auto_reset = False  # the handle's generator regenerates inside antsrl_step_update (generate)
         self._loaded = None     # what has been done to the handle since construction (tune_placement refuses to run then)
         self._host_out = None   # pinned mirror of _out_flat (outputs_to_host)
         self._host_act = None   # pinned staging of numpy actions + the event of its last upload
@@ -256,6 +258,9 @@ class BatchedAntsEnv:
         gen.auto_reset, step_update() regenerates all envs after the step that reported done.
         walls (uint8 / bool [E, W, H], for gen.wall_kind == WALLS_INPUT): the bitmaps a walls_generator returned."""
         g = gen if gen is not None else cfgmod.make_gen()
+        if g.auto_reset and self._reward_hook is not None:
+            raise _lib.AntsrlError("a reward hook and a generator with auto_reset exclude each other (the auto-reset lives "
+                                   "inside antsrl_step_update)")
         if walls is not None:
             c = self.cfg
             self._gen_walls = self._dev(np.asarray(walls).astype(np.uint8) if not torch.is_tensor(walls) else walls,
@@ -264,6 +269,7 @@ class BatchedAntsEnv:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.antsrl_generate(self._h, C.byref(g), int(episode_seed), self._stream()), "generate")
         self._loaded = "given an episode (generate)"
+        self._auto_reset = bool(g.auto_reset)
 
     def _actions(self, rotation, phero):
         c = self.cfg
@@ -353,21 +359,86 @@ class BatchedAntsEnv:
                 piece("reward", self.reward), piece("done", self.done))
 
     def step(self, rotation, phero, want_obs: bool = True):
-        """RLApi.step (RL_api.py:168-204) for all envs -> (obs, agent_state, reward, done)."""
+        """RLApi.step (RL_api.py:168-204) for all envs -> (obs, agent_state, reward, done).  With a reward hook
+        (set_reward_hook) the hook's reward is given before the call returns."""
         rot, ph = self._actions(rotation, phero)
         with self._on_device():
             _lib.check(self.lib.antsrl_step(self._h, _lib.ptr(rot), _lib.ptr(ph), _lib.ptr(self._obs_buf if want_obs else None),
                                             _lib.ptr(self.agent_state), _lib.ptr(self.reward), _lib.ptr(self.done),
                                             self._stream()), "step")
+        if self._reward_hook is not None:
+            self.give_reward(self._hook_reward(True), self._reward_hook[1])
         return self.obs, self.agent_state, self.reward, self.done
 
     def observe(self, want_obs: bool = True):
-        """RLApi.observation (RL_api.py:96-165) -> (obs, agent_state, reward)."""
+        """RLApi.observation (RL_api.py:96-165) -> (obs, agent_state, reward).  With a reward hook the hook's reward
+        replaces `reward`; nothing is GIVEN (the reference flashes the ants in RLApi.step only, RL_api.py:203)."""
         with self._on_device():
             _lib.check(self.lib.antsrl_observe(self._h, _lib.ptr(self._obs_buf if want_obs else None),
                                                _lib.ptr(self.agent_state), _lib.ptr(self.reward), self._stream()),
                        "observe")
+        if self._reward_hook is not None:
+            with self._on_device():
+                self.reward.copy_(self._reward64(self._hook_reward(False)))
         return self.obs, self.agent_state, self.reward
+
+    # ------------------------------------------------------------------ a caller's reward
+    def obs_coords(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """antsrl_obs_coords: int32 [E, N, P, P, 2] on the device, the cell (x, y) every offset of every ant's perception
+        grid lands on — `abs_coords` of RL_api.py:100-119, what the reference hands to Reward.observation; masked offsets
+        included.  From the ants as they stand: ask right behind step() / observe(), before update()."""
+        c = self.cfg
+        shape = (c.n_envs, c.n_ants, c.pside, c.pside, 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("obs_coords: out must be a contiguous int32 tensor of shape %s on %s" % (shape, self.device))
+        with self._on_device():
+            _lib.check(self.lib.antsrl_obs_coords(self._h, _lib.ptr(out), self._stream()), "obs_coords")
+        return out
+
+    def _reward64(self, reward) -> torch.Tensor:
+        c = self.cfg
+        return self._dev(reward, torch.float64, (c.n_envs, c.n_ants))
+
+    def give_reward(self, reward, threshold: float) -> None:
+        """antsrl_give_reward: Ants.give_reward(reward - threshold) (RL_api.py:203, ants.py:119-121) for a reward the caller
+        computed — any float tensor or array of [E, N], taken as float64: reward_state flashes to 255 where reward -
+        threshold > 0, and `self.reward` takes the reward in place, so the packed output buffer, outputs_to_host() and
+        whoever reads env.reward afterwards see it.  Between step() and update()."""
+        r = self._reward64(reward)
+        with self._on_device():
+            _lib.check(self.lib.antsrl_give_reward(self._h, _lib.ptr(r), float(threshold), _lib.ptr(self.reward),
+                                                   self._stream()), "give_reward")
+
+    def set_reward_hook(self, fn, threshold: float = 0.0, coords: bool = True) -> None:
+        """A reward computed by the caller at every step: `fn(env, obs_coords_or_None, stepped)` returns the reward of
+        [E, N] (any float tensor or array); `obs_coords` is obs_coords() (None with coords=False: no launch), `stepped`
+        tells a step from a bare observation; the step's own outputs (env.obs, env.agent_state, env.reward — the
+        kernels' reward, zeros under REWARD_NONE) are there to read.  step() then is antsrl_step, fn, give_reward(fn's
+        reward, threshold); observe() runs fn and writes env.reward only; step_update() is antsrl_step, fn,
+        give_reward, antsrl_update — the update still defers into the next step's launch wherever it does without a
+        hook, and but for the reward and reward_state every tensor is the un-hooked step_update's.
+        The env must have been created with reward_threshold = +inf (config.make_cfg; reward_kind REWARD_NONE, or a
+        built-in kind whose reward fn builds on), so that the kernels' own flash never fires: the caller's threshold lives
+        here.  Out of scope: a generator with auto_reset — the auto-reset lives inside antsrl_step_update, which a hooked
+        step_update does not call; the pair raises.  set_reward_hook(None) restores the un-hooked path exactly."""
+        if fn is None:
+            self._reward_hook = None
+            return
+        if not callable(fn):
+            raise TypeError("set_reward_hook: fn must be callable (or None)")
+        if not (self.cfg.reward_threshold == float("inf")):
+            raise ValueError("set_reward_hook: create the env with reward_threshold=float('inf') (the kernels' own "
+                             "give_reward must never fire; the hook's threshold decides), got %r" % (self.cfg.reward_threshold,))
+        if self._auto_reset:
+            raise _lib.AntsrlError("a reward hook and a generator with auto_reset exclude each other (the auto-reset lives "
+                                   "inside antsrl_step_update)")
+        self._reward_hook = (fn, float(threshold), bool(coords))
+
+    def _hook_reward(self, stepped: bool):
+        fn, _, coords = self._reward_hook
+        return fn(self, self.obs_coords() if coords else None, stepped)
 
     def update(self, wall_jitter=None) -> None:
         """Environment.update (environment.py:42-47)."""
@@ -395,6 +466,10 @@ class BatchedAntsEnv:
         """main.py:98 + main.py:131 in one call.  want_obs=False: no observation tensor is written (rewards,
         agent_state, done and — with LinearPolicy.attach — the next actions still are: the act-only rollout)."""
         c = self.cfg
+        if self._reward_hook is not None:  # step, the hook's reward, give_reward — then the update (set_reward_hook)
+            out = self.step(rotation, phero, want_obs)
+            self.update(wall_jitter)
+            return out
         rot, ph = self._actions(rotation, phero)
         j = self._dev(wall_jitter, torch.float64, (c.n_envs, c.n_ants))
         with self._on_device():

@@ -932,6 +932,26 @@ extern "C" int antsrl_perceptive_field(AntsHandle *h, uint8_t *dst, void *stream
     return enqueued(antsrl_launch_perceptive_field(h->p, dst, (hipStream_t)stream), "perceptive_field");
 }
 
+// A caller's Reward (include/antsrl.h): obs_coords for its observation(), give_reward for what its step() returned.  Both
+// sit between the step and the update; behind a DEFERRED update they enqueue it first — give_reward's 255 must land on
+// the decayed reward_state, and the coordinates are those of the ants where the update left them.
+extern "C" int antsrl_obs_coords(AntsHandle *h, int32_t *dst, void *stream)
+{
+    if (!h || !dst) return fail(ANTSRL_E_INVALID, "NULL handle or dst");
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if ((uintptr_t)dst & 7) return fail(ANTSRL_E_INVALID, "obs_coords: dst must be 8-byte aligned (one int32 pair per store)");
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc;
+    return enqueued(antsrl_launch_obs_coords(h->p, dst, (hipStream_t)stream), "obs_coords");
+}
+
+extern "C" int antsrl_give_reward(AntsHandle *h, const double *reward, double threshold, float *reward_out, void *stream)
+{
+    if (!h || !reward) return fail(ANTSRL_E_INVALID, "NULL handle or reward");
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc;
+    return enqueued(antsrl_launch_give_reward(h->p, reward, threshold, reward_out, (hipStream_t)stream), "give_reward");
+}
+
 extern "C" int antsrl_read_state(AntsHandle *h, int which, void *dst, void *stream)
 {
     if (!h || !dst) return fail(ANTSRL_E_INVALID, "NULL handle or dst");

@@ -32,6 +32,9 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_generate(const KP &p, const AntsGen &g,
 ANTSRL_INTERNAL hipError_t antsrl_launch_set_activation(const KP &p, const float *act, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_read_state(const KP &p, int which, int cur, void *dst, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_perceptive_field(const KP &p, uint8_t *dst, hipStream_t st);
+ANTSRL_INTERNAL hipError_t antsrl_launch_obs_coords(const KP &p, int32_t *dst, hipStream_t st);
+ANTSRL_INTERNAL hipError_t antsrl_launch_give_reward(const KP &p, const double *reward, double threshold, float *reward_out,
+                                                     hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_copy16(void *dst, const void *src, size_t bytes, hipStream_t st);
 // antsrl_perceive.hip: the cell-meta path
 ANTSRL_INTERNAL bool antsrl_meta_supported(const KP &p);

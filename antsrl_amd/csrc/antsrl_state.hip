@@ -544,10 +544,42 @@ hipError_t antsrl_launch_set_activation(const KP &p, const float *act, hipStream
     return hipGetLastError();
 }
 
+// k_perceive's observation geometry (centre shifted by fwd_delta along the heading, offsets rotated by theta + pi / 2,
+// half-to-even rounding, toroidal wrap: RL_api.py:100-119), its one statement outside k_perceive, in two pieces: an ant's
+// perception frame (the rotation by theta + pi / 2 and the shifted centre — the only sincos calls), and the cell that
+// offset q of the P x P grid lands on (perception_coords' order: column q % P, row q / P).  k_perceptive_field and
+// k_obs_coords both go through them.
+struct PerceptionFrame {
+    double sn2, cs2, cx, cy;
+};
+
+__device__ __forceinline__ PerceptionFrame perception_frame(const KP &p, size_t a)
+{
+    PerceptionFrame f;
+    const double th = p.s.theta[a];
+    double sn, cs;
+    sincos(th + PI_D * 0.5, &f.sn2, &f.cs2);
+    f.cx = p.s.x[a];
+    f.cy = p.s.y[a];
+    if (p.fwd_delta != 0.0) {
+        sincos(th, &sn, &cs);
+        f.cx += cs * p.fwd_delta;
+        f.cy += sn * p.fwd_delta;
+    }
+    return f;
+}
+
+__device__ __forceinline__ int2 perceived_cell(const KP &p, const PerceptionFrame &f, int q)
+{
+    const double ox = (double)(q % p.P - p.r) * p.delta, oy = (double)(q / p.P - p.r) * p.delta;
+    const int ix = wrap_index((int)rint((f.cs2 * ox - f.sn2 * oy) + f.cx), p.W);
+    const int iy = wrap_index((int)rint((f.sn2 * ox + f.cs2 * oy) + f.cy), p.H);
+    return make_int2(ix, iy);
+}
+
 // RLApi.perceptive_field (RL_api.py:144-153, save_perceptive_field — the viewer's overlay): dst[e][x][y] = 1 where some ant's
 // perception reaches (masked cells not counted), from the ants' positions as they stand — the caller asks right behind the
-// observation.  One thread per (ant, perceived cell); the geometry is k_perceive's (centre shifted by fwd_delta along the
-// heading, offsets rotated by theta + pi / 2, half-to-even rounding, toroidal wrap: RL_api.py:100-119).  Not on the hot path.
+// observation.  One thread per (ant, perceived cell); the geometry is k_perceive's (perceived_cell).  Not on the hot path.
 __global__ void __launch_bounds__(256) k_perceptive_field(const KP p, uint8_t *__restrict__ dst)
 {
     const size_t n = (size_t)p.E * p.N * p.PP;
@@ -557,19 +589,8 @@ __global__ void __launch_bounds__(256) k_perceptive_field(const KP p, uint8_t *_
         const int q = (int)(i - a * p.PP);
         if (p.has_mask && !p.mask[q]) continue;
         const size_t e = a / p.N;
-        const double th = p.s.theta[a];
-        double sn, cs, sn2, cs2;
-        sincos(th + PI_D * 0.5, &sn2, &cs2);
-        double cx = p.s.x[a], cy = p.s.y[a];
-        if (p.fwd_delta != 0.0) {
-            sincos(th, &sn, &cs);
-            cx += cs * p.fwd_delta;
-            cy += sn * p.fwd_delta;
-        }
-        const double ox = (double)(q % p.P - p.r) * p.delta, oy = (double)(q / p.P - p.r) * p.delta;
-        const int ix = wrap_index((int)rint((cs2 * ox - sn2 * oy) + cx), p.W);
-        const int iy = wrap_index((int)rint((sn2 * ox + cs2 * oy) + cy), p.H);
-        dst[e * G + (size_t)ix * p.H + iy] = 1;
+        const int2 c = perceived_cell(p, perception_frame(p, a), q);
+        dst[e * G + (size_t)c.x * p.H + c.y] = 1;
     }
 }
 
@@ -578,6 +599,65 @@ hipError_t antsrl_launch_perceptive_field(const KP &p, uint8_t *dst, hipStream_t
     hipError_t e = hipMemsetAsync(dst, 0, (size_t)p.E * p.W * p.H, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_perceptive_field, dim3(grid_for((size_t)p.E * p.N * p.PP)), dim3(256), 0, st, p, dst);
+    return hipGetLastError();
+}
+
+// obs_coords of RLApi.observation (RL_api.py:100-119, what it hands to Reward.observation at :164): dst int32
+// [E][N][P][P][2], the cell every offset of every ant's perception grid lands on, masked offsets included (the reference
+// passes them too).  A wave takes 64 consecutive ants: lane l computes the frame of ant l — so the sincos pair runs once
+// per ANT, not once per cell — and the wave then walks the 64 * PP pairs of its ants, which are contiguous in dst, 64 at
+// a time: lane l takes pair k + l, fetches the frame of the ant that pair belongs to from that ant's lane (a cross-lane
+// read, no LDS) and stores its 8 bytes, 512 contiguous bytes per wave and store.
+__global__ void __launch_bounds__(256) k_obs_coords(const KP p, int2 *__restrict__ dst)
+{
+    const size_t EN = (size_t)p.E * p.N;
+    const size_t n_waves = (EN + 63) / 64;
+    const int lane = threadIdx.x & 63;
+    const size_t wave0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, wave_stride = ((size_t)gridDim.x * blockDim.x) >> 6;
+    for (size_t w = wave0; w < n_waves; w += wave_stride) { // (wave-uniform: every lane of a wave makes the same trips)
+        const size_t a0 = w * 64;
+        const int n_ants = (int)min((size_t)64, EN - a0);
+        PerceptionFrame f = {0.0, 0.0, 0.0, 0.0};
+        if (lane < n_ants) f = perception_frame(p, a0 + lane);
+        const int n_pairs = n_ants * p.PP;
+        for (int k0 = 0; k0 < n_pairs; k0 += 64) {
+            const int k = k0 + lane;
+            const bool live = k < n_pairs;
+            const int j = live ? k / p.PP : 0; // the lane that holds this pair's ant
+            PerceptionFrame g;
+            g.sn2 = __shfl(f.sn2, j);
+            g.cs2 = __shfl(f.cs2, j);
+            g.cx = __shfl(f.cx, j);
+            g.cy = __shfl(f.cy, j);
+            if (live) dst[a0 * p.PP + k] = perceived_cell(p, g, k - j * p.PP);
+        }
+    }
+}
+
+hipError_t antsrl_launch_obs_coords(const KP &p, int32_t *dst, hipStream_t st)
+{
+    const size_t n_waves = ((size_t)p.E * p.N + 63) / 64;
+    hipLaunchKernelGGL(k_obs_coords, dim3(grid_for(n_waves * 64)), dim3(256), 0, st, p, (int2 *)dst);
+    return hipGetLastError();
+}
+
+// Ants.give_reward(reward - threshold) (ants.py:119-121) for a reward the CALLER computed: reward_state = min(reward_state
+// + 255, 255) = 255 where reward - threshold > 0, in float64 like the reference; reward_out (may be NULL) takes the reward
+// as the float32 the step's own reward output holds.  One lane per ant.
+__global__ void __launch_bounds__(256) k_give_reward(const KP p, const double *__restrict__ reward, double threshold,
+                                                     float *__restrict__ reward_out)
+{
+    const size_t EN = (size_t)p.E * p.N;
+    for (size_t a = (size_t)blockIdx.x * blockDim.x + threadIdx.x; a < EN; a += (size_t)gridDim.x * blockDim.x) {
+        const double rw = reward[a];
+        if (rw - threshold > 0) p.s.reward_state[a] = 255;
+        if (reward_out) reward_out[a] = (float)rw;
+    }
+}
+
+hipError_t antsrl_launch_give_reward(const KP &p, const double *reward, double threshold, float *reward_out, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_give_reward, dim3(grid_for((size_t)p.E * p.N)), dim3(256), 0, st, p, reward, threshold, reward_out);
     return hipGetLastError();
 }
 

@@ -349,8 +349,26 @@ class Reward:  # environment/rewards/reward.py:6-45
     def weights(self):
         return {}
 
+    def observation(self, obs_coords, perception, agent_state):
+        """reward.py:21-27: called by RLApi behind every observation with the integer cells each ant perceives
+        ([n, P, P, 2], masked offsets included), the perception and agent_state it returns.  A caller's subclass
+        overrides it; `self.rewards` already holds the device's reward (zeros for this base class, the built-in's
+        for a subclass of one), so super().observation(...) has nothing left to do."""
+        pass
+
+    def step(self, done, turn_index, open_close_mandibles, on_off_pheromones):
+        """reward.py:29-38 -> the per-ant reward of this step, [n]."""
+        return self.rewards
+
     def visualization(self):
         return None
+
+
+def _callers_reward(reward) -> bool:
+    """A reward whose class overrides observation() or step() is the caller's own: RLApi calls both, like the reference
+    (RL_api.py:164, :202-203), and gives what step() returns.  The built-ins used as they are stay on the device."""
+    cls = type(reward)
+    return cls.observation is not Reward.observation or cls.step is not Reward.step
 
 
 class _ExploredMixin:
@@ -412,6 +430,8 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         self.as_numpy = as_numpy
         self._pending = None  # (base cfg kwargs, init arrays) from the generator
         self._backend = None
+        self._custom = False     # the reward's class overrides observation() / step() (_callers_reward): set by _materialize
+        self._setup_due = False  # its setup() waits for the device batch (register_ants)
 
     # -- wiring ----------------------------------------------------------------
     def register_ants(self, new_ants: Ants):  # RL_api.py:57-66
@@ -421,7 +441,11 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         self.environment = new_ants.environment
         self.environment.add_object(self)
         self.perceived_objects = []
-        self.reward.setup(self.ants)
+        # (RL_api.py:66.  A caller's reward may read the world through the views in its setup(), which takes the device
+        #  batch: where there is none yet, its setup() runs right behind _materialize instead)
+        self._setup_due = _callers_reward(self.reward) and self._backend is None
+        if not self._setup_due:
+            self.reward.setup(self.ants)
 
     def setup_perception(self, radius: int, objects: List[EnvObject], mask=None, forward_delta=0):
         """RL_api.py:80-93.  (Re)creates the device batch for this perception set-up and loads the
@@ -448,12 +472,18 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
     def _materialize(self):
         from .batched import BatchedAntsEnv
         kw, init = self._pending
+        # A caller's reward (_callers_reward): the kernels' own give_reward must never fire — 0 - inf > 0 is false —
+        # and RLApi.step gives what reward.step() returned, against self.reward_threshold.  The kind stays the class's:
+        # REWARD_NONE for a subclass of Reward, the built-in's (with its weights) for a subclass of a built-in, whose
+        # device reward the subclass then finds in self.rewards.
+        self._custom = _callers_reward(self.reward)
+        threshold = float("inf") if self._custom else float(self.reward_threshold)
         cfg = cm.make_cfg(mask=self.perception_mask, perception_radius=self.perception_radius,
                           fwd_delta=float(self.perception_fwd_delta), delta=DELTA, channels=self._channels(),
                           max_speed=float(self.max_speed), max_rot_speed=float(self.max_rot_speed),
                           carry_speed_reduction=float(self.carry_speed_reduction),
                           backward_speed_reduction=float(self.backward_speed_reduction),
-                          reward_kind=self.reward.kind, reward_threshold=float(self.reward_threshold),
+                          reward_kind=self.reward.kind, reward_threshold=threshold,
                           **self.reward.weights(), **kw)
         self._backend = BatchedAntsEnv(cfg)
         if isinstance(init, tuple):  # ("device", AntsGen, episode_seed[, walls bitmaps]): generated on the GPU
@@ -461,6 +491,17 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         else:
             self._backend.reset(init)
         self.environment._backend = self._backend
+        if self._setup_due:
+            self._setup_due = False
+            self.reward.setup(self.ants)
+
+    # -- a caller's reward -------------------------------------------------------
+    def _coords(self):
+        """obs_coords as the reference hands them to Reward.observation (RL_api.py:164): [n, P, P, 2], int64 numpy with
+        as_numpy, else the device's int32 tensor."""
+        c = self._backend.obs_coords()
+        c = c.reshape((c.shape[0] * c.shape[1],) + tuple(c.shape[2:]))
+        return c.cpu().numpy().astype(np.int64) if self.as_numpy else c
 
     # -- outputs ---------------------------------------------------------------
     def _out(self, t, fold=True):
@@ -483,7 +524,10 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         self._field()
         self.reward.rewards = self._out(rew)
         state = self._state()
-        return self._out(obs), self._out(ast), state
+        o, a = self._out(obs), self._out(ast)
+        if self._custom:
+            self.reward.observation(self._coords(), o, a)  # RL_api.py:164
+        return o, a, state
 
     def _field(self):  # RL_api.py:144-153
         if self.save_perceptive_field:
@@ -504,6 +548,8 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         b = self._backend
         obs, ast, rew, done = b.step(self._acts(rotation), self._acts(on_off_pheromones))
         self._field()
+        if self._custom:
+            return self._step_callers_reward(rotation, on_off_pheromones)
         if self.as_numpy:  # the four outputs in one device-to-host copy
             obs, ast, rew, done = b.outputs_to_host()
             fold = lambda t: t.reshape((t.shape[0] * t.shape[1],) + t.shape[2:])
@@ -517,6 +563,28 @@ class RLApi(EnvObject):  # environment/RL_api.py:22-204
         else:
             d = done.cpu().numpy().astype(bool) if self.as_numpy else done
         return self._out(obs), self._out(ast), r, d
+
+    def _step_callers_reward(self, rotation, on_off_pheromones):
+        """The rest of RLApi.step for a caller's reward (RL_api.py:198-204), behind the device's step: reward.observation
+        with the cells perceived, reward.step with the raw action arguments and the mandibles as the step left them,
+        then Ants.give_reward(reward - reward_threshold) on the device.  Returns the caller's array as it is."""
+        b = self._backend
+        if self.as_numpy:  # the four outputs in one device-to-host copy, as in step()
+            fold = lambda t: t.reshape((t.shape[0] * t.shape[1],) + t.shape[2:])
+            o, a, r, done = b.outputs_to_host()
+            o, a, r = fold(o), fold(a), fold(r)
+        else:
+            o, a, r, done = self._out(b.obs), self._out(b.agent_state), self._out(b.reward), b.done
+        self.reward.rewards = r  # the device's reward: zeros, or the built-in's under a subclass of one
+        if b.cfg.n_envs == 1:
+            d = bool(np.asarray(done.cpu() if hasattr(done, "cpu") else done)[0])
+        else:
+            d = done.astype(bool) if self.as_numpy else done
+        self.reward.observation(self._coords(), o, a)
+        mandibles = self._out(b.read_state(cm.S_MANDIBLES) != 0)
+        reward = self.reward.step(d, rotation, mandibles, on_off_pheromones)
+        b.give_reward(self._acts(reward), self.reward_threshold)
+        return o, a, reward, d
 
     def visualize_copy(self, newenv):
         from .snapshot import RLVisualization

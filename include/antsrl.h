@@ -1288,6 +1288,32 @@ int antsrl_read_state(AntsHandle *h, int which, void *dst, void *stream);
  * flushed by this call. */
 int antsrl_perceptive_field(AntsHandle *h, uint8_t *dst, void *stream);
 
+/* A CALLER'S Reward.  The reference's extension point is the Reward base class (environment/rewards/reward.py): RLApi
+ * hands Reward.observation the integer cells every ant perceives (RL_api.py:164), takes the reward from Reward.step
+ * (RL_api.py:202) and flashes the ants it rewards, Ants.give_reward(reward - reward_threshold) (RL_api.py:203,
+ * ants.py:119-121).  A handle created with reward_kind = ANTSRL_REWARD_NONE and reward_threshold = +infinity writes a
+ * reward of 0 and never flashes on its own (0 - inf > 0 is false; a built-in kind with an infinite threshold still
+ * writes its reward and never flashes); these two entries then are the caller's half of RLApi.step.  They belong
+ * BETWEEN the step and the update:
+ *     antsrl_step;  antsrl_obs_coords;  <the caller's reward>;  antsrl_give_reward;  antsrl_update
+ * — the reference gives the reward before Environment.update decays reward_state (ants.py:130).  Towards the handle
+ * both behave alike: a handle that was never reset is refused, so is one between two phases of antsrl_update_phase
+ * (they are no mere reads of a half-updated world), and a DEFERRED update is enqueued first (the coordinates are then
+ * those of the ants where that update left them, and the 255 lands on the decayed reward_state).  Neither allocates
+ * nor synchronises the host.
+ *
+ * antsrl_obs_coords: dst int32 [E][N][P][P][2] (8-byte aligned) = abs_coords of RL_api.py:100-119 for the ants as they
+ * stand: the centre shifted by fwd_delta along the heading, the grid's offsets times delta rotated by theta + pi / 2,
+ * rounded half to even, wrapped onto the torus; pair (x, y) of row i, column j belongs to the offset perception_coords
+ * [i][j] = ((j - r) * delta, (i - r) * delta), the order of the observation's cells.  MASKED offsets are included, as in
+ * the reference: the caller applies the mask.
+ *
+ * antsrl_give_reward: reward float64 [E][N].  reward_state[a] = 255 where reward[a] - threshold > 0, evaluated in
+ * float64; reward_out (float32 [E][N], may be NULL) takes (float)reward[a] — pass the step's reward buffer and whoever
+ * reads it afterwards sees the caller's reward. */
+int antsrl_obs_coords(AntsHandle *h, int32_t *dst, void *stream);
+int antsrl_give_reward(AntsHandle *h, const double *reward, double threshold, float *reward_out, void *stream);
+
 /* Size in bytes of what antsrl_read_state(which) writes. */
 int antsrl_state_bytes(const AntsHandle *h, int which, size_t *bytes);
 
