@@ -4,7 +4,8 @@ from . import config  # noqa: F401
 from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
-           "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats"]
+           "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats",
+           "EnvCheckpoint"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -35,6 +36,9 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "EpisodeStats":
         from .stats import EpisodeStats
         return EpisodeStats
+    if name == "EnvCheckpoint":
+        from .checkpoint import EnvCheckpoint
+        return EnvCheckpoint
     if name in ("train_episodes", "epsilon_schedule"):
         from . import driver
         return getattr(driver, name)

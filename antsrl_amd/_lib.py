@@ -31,7 +31,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode", "antsrl_recorder_sizes",
            "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames",
            "antsrl_stats_sizes", "antsrl_stats_row", "antsrl_jointtrain_sizes", "antsrl_jointtrain_grad",
-           "antsrl_jointtrain_apply", "antsrl_jointtrain_step", "antsrl_obs_coords", "antsrl_give_reward")
+           "antsrl_jointtrain_apply", "antsrl_jointtrain_step", "antsrl_obs_coords", "antsrl_give_reward",
+           "antsrl_checkpoint_map", "antsrl_checkpoint_save", "antsrl_checkpoint_load", "antsrl_fork_envs")
 
 _lib = None
 
@@ -62,6 +63,11 @@ class AntsRenderOpts(C.Structure):
 class AntsWsArray(C.Structure):
     """include/antsrl.h AntsWsArray."""
     _fields_ = [("name", C.c_char * 24), ("block", C.c_int32), ("_pad", C.c_int32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class AntsCkptArray(C.Structure):
+    """include/antsrl.h AntsCkptArray."""
+    _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes_per_env", C.c_uint64)]
 
 
 class AntsrlError(RuntimeError):
@@ -98,6 +104,11 @@ def load() -> C.CDLL:
     lib.antsrl_observe.argtypes = [vp, vp, vp, vp, vp]
     lib.antsrl_update.argtypes = [vp, vp, vp]
     lib.antsrl_flush.argtypes = [vp, vp]
+    lib.antsrl_checkpoint_map.argtypes = [C.POINTER(AntsCfg), C.POINTER(AntsCkptArray), C.c_int32, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.antsrl_checkpoint_save.argtypes = [vp, vp, vp, vp]
+    lib.antsrl_checkpoint_load.argtypes = [vp, vp, vp, vp]
+    lib.antsrl_fork_envs.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, vp]
     lib.antsrl_update_phase.argtypes = [vp, i32, vp, vp]
     lib.antsrl_perceptive_field.argtypes = [vp, vp, vp]
     lib.antsrl_obs_coords.argtypes = [vp, vp, vp]

@@ -162,6 +162,86 @@ class _DeviceAgent:
         """Model and target net (and the acting policy) from a state_dict file of the reference's."""
         self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"))
 
+    # ---- the training state: out of the agent and back ------------------------------------------------------------
+    #: the trainers' device buffers, whichever a trainer has: the nets (MemoryTrainer's `_model` / `_target` hold Adam's
+    #: moments and the operand packs as well), Adam's moments of the flat trainers, LinearTrainer's frozen layer1
+    _TRAINER_BUFFERS = ("_model", "_target", "model", "target", "heads", "target_l3", "_adam", "policy.w1", "policy.b1")
+    _TRAINER_COUNTERS = ("step_count", "target_update_counter", "syncs")
+    _REPLAY_TENSORS = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
+
+    def _trainer_buffers(self) -> dict:
+        out = {}
+        for path in self._TRAINER_BUFFERS:
+            obj = self.trainer
+            for part in path.split("."):
+                obj = getattr(obj, part, None)
+            if torch.is_tensor(obj):
+                out[path] = obj
+        return out
+
+    def training_state(self) -> dict:
+        """Everything rollout_step reads or changes besides the environment, as a dict of tensors (copies, on the
+        agent's device), ints, floats and bytes that torch.save takes: the trainer's nets and Adam's moments, its
+        counters, the replay memory's seven tensors with head and fill, the torch generator's state, step_counter and
+        `_action_step`, epsilon, `_explored`, and MemoryAgent's carried memory.  With BatchedAntsEnv.checkpoint() it is
+        what a run needs to continue bit for bit (load_training_state)."""
+        rm = self.replay_memory
+        assert rm._pending is None, "training_state between record_pre and record_post"
+        d = dict(agent=type(self).__name__, trainer={k: v.clone() for k, v in self._trainer_buffers().items()},
+                 counters={k: int(getattr(self.trainer, k)) for k in self._TRAINER_COUNTERS},
+                 replay={k: getattr(rm, k).clone() for k in self._REPLAY_TENSORS}, head=int(rm.head), fill=int(rm.fill),
+                 generator=self.generator.get_state().clone(), step_counter=int(self.step_counter),
+                 action_step=int(self._action_step), epsilon=float(self.epsilon), explored=self._explored.clone())
+        if hasattr(self, "_mem"):  # MemoryAgent: both halves of the carried memory and which one is previous_memory
+            d["memory"] = [m.clone() for m in self._mem]
+            d["memory_cur"] = int(self._cur)
+        return d
+
+    def load_training_state(self, d: dict) -> None:
+        """training_state()'s dict into an agent that has been set up on an env of the same shape (with the same
+        hyper-parameters): every tensor is copied into the agent's own, then the acting weights are installed again (the
+        trainer's acting policy, and the in-loop policy's handle where one is attached)."""
+        if d["agent"] != type(self).__name__:
+            raise ValueError("a %s's training state cannot go into a %s" % (d["agent"], type(self).__name__))
+        tr, rm = self.trainer, self.replay_memory
+        mine = self._trainer_buffers()
+        pairs = [(mine.get(k), v, "trainer." + k) for k, v in d["trainer"].items()]
+        pairs += [(getattr(rm, k), d["replay"][k], "replay." + k) for k in self._REPLAY_TENSORS]
+        pairs.append((self._explored, d["explored"], "explored"))
+        if hasattr(self, "_mem"):
+            pairs += [(m, v, "memory") for m, v in zip(self._mem, d["memory"])]
+        if set(mine) != set(d["trainer"]):
+            raise ValueError("the trainer's buffers are %s, the state's %s" % (sorted(mine), sorted(d["trainer"])))
+        for dst, src, what in pairs:
+            if tuple(dst.shape) != tuple(src.shape) or dst.dtype != src.dtype:
+                raise ValueError("%s: %s %s in the state, %s %s in this agent" % (what, src.dtype, tuple(src.shape), dst.dtype,
+                                                                                 tuple(dst.shape)))
+        with torch.cuda.device(self.device):
+            for dst, src, _ in pairs:
+                dst.copy_(src)
+            self.generator.set_state(d["generator"].cpu())
+        for k in self._TRAINER_COUNTERS:
+            setattr(tr, k, int(d["counters"][k]))
+        rm.head, rm.fill, rm._pending = int(d["head"]), int(d["fill"]), None
+        self.step_counter, self._action_step, self.epsilon = int(d["step_counter"]), int(d["action_step"]), float(d["epsilon"])
+        if hasattr(self, "_mem"):
+            self._cur = int(d["memory_cur"])
+            self._memory_before = self._mem[1 - self._cur]
+        # the acting weights again: a flat trainer's acting net is views of the buffers just written (its version moves),
+        # MemoryTrainer repacks its policy from the target net, ReworkTrainer collapses the target block
+        if hasattr(tr, "_weights_changed"):
+            tr._weights_changed()
+        if hasattr(tr, "version"):
+            tr.version += 1
+        if hasattr(tr, "_repack_policy"):
+            tr._repack_policy()
+        if hasattr(tr.policy, "recollapse"):
+            tr.policy.recollapse()
+        self._acting_weights_loaded()
+
+    def _acting_weights_loaded(self) -> None:
+        """load_training_state has replaced the acting weights."""
+
     # ---- the fused loop -------------------------------------------------------------------------------------------
     def rollout_step(self, env, training: bool = True):
         """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
@@ -303,6 +383,13 @@ class _InLoopAgent(_DeviceAgent):
     def _refresh_due(self, training: bool) -> bool:
         """Whether a handle with stale weights gets the acting weights at the step that starts now."""
         raise NotImplementedError
+
+    def _acting_weights_loaded(self) -> None:
+        """The in-loop policy on the handle again (a restored env does not carry the pack), and whatever actions the
+        observation kernel left are not these weights'."""
+        self._next_version = -1
+        if self._env is not None:
+            self.refresh_inloop()
 
     def _stepped(self, env) -> None:
         if env is self._env:

@@ -101,6 +101,7 @@ class BatchedAntsEnv:
         self._keep = None
         self._reward_hook = None  # (fn, threshold, coords) of set_reward_hook
         self._auto_reset = False  # the handle's generator regenerates inside antsrl_step_update (generate)
+        self._gen_walls_input = False  # ... from the caller's bitmaps (WALLS_INPUT): a checkpoint does not carry it
         self._loaded = None     # what has been done to the handle since construction (tune_placement refuses to run then)
         self._host_out = None   # pinned mirror of _out_flat (outputs_to_host)
         self._host_act = None   # pinned staging of numpy actions + the event of its last upload
@@ -270,6 +271,7 @@ class BatchedAntsEnv:
             _lib.check(self.lib.antsrl_generate(self._h, C.byref(g), int(episode_seed), self._stream()), "generate")
         self._loaded = "given an episode (generate)"
         self._auto_reset = bool(g.auto_reset)
+        self._gen_walls_input = g.wall_kind == cfgmod.WALLS_INPUT
 
     def _actions(self, rotation, phero):
         c = self.cfg
@@ -461,6 +463,60 @@ class BatchedAntsEnv:
         to time the update on its own); a no-op when nothing is pending."""
         with self._on_device():
             _lib.check(self.lib.antsrl_flush(self._h, self._stream()), "flush")
+
+    # ------------------------------------------------------------------ checkpoint, restore, fork
+    def checkpoint(self):
+        """The batch's whole state as an EnvCheckpoint (antsrl_amd/checkpoint.py): antsrl_checkpoint_save's device block
+        and host blob, and clones of the outputs of the last step.  A deferred update is enqueued first.  Not in it: the
+        in-loop policy's pack (the agent installs it again), a generator's WALLS_INPUT bitmaps, and a reward hook's own
+        state — a caller's Reward object is the caller's to carry; restore() and fork() do not touch it."""
+        from .checkpoint import EnvCheckpoint, checkpoint_map
+        _, dev, host = checkpoint_map(self.cfg)
+        blob = C.create_string_buffer(host)
+        with self._on_device():
+            block = torch.empty((dev,), dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.antsrl_checkpoint_save(self._h, _lib.ptr(block), blob, self._stream()), "checkpoint_save")
+            outs = [t.clone() for t in (self._obs_buf, self.agent_state, self.reward, self.done)]
+        return EnvCheckpoint(self.cfg, block, blob.raw, *outs, auto_reset=self._auto_reset and not self._gen_walls_input)
+
+    def restore(self, ck) -> None:
+        """antsrl_checkpoint_load and the outputs: from here on the env continues bit for bit as the one `ck` was taken
+        from did.  The env holds an episode already (reset() / generate(): whatever it holds is replaced) and has `ck`'s
+        AntsCfg (any workspace layout: one block or two, placed anywhere); ValueError when the output shapes or the
+        observation dtype differ."""
+        mine = dict(obs=self._obs_buf, agent_state=self.agent_state, reward=self.reward, done=self.done)
+        for k, t in mine.items():
+            s = getattr(ck, k)
+            if tuple(s.shape) != tuple(t.shape) or s.dtype != t.dtype:
+                raise ValueError("restore: the checkpoint's %s is %s %s, this env's %s %s" % (
+                    k, s.dtype, tuple(s.shape), t.dtype, tuple(t.shape)))
+        if ck.auto_reset and self._reward_hook is not None:
+            raise _lib.AntsrlError("a reward hook and a generator with auto_reset exclude each other (the auto-reset lives "
+                                   "inside antsrl_step_update)")
+        with self._on_device():
+            block = ck.block.to(self.device)
+            _lib.check(self.lib.antsrl_checkpoint_load(self._h, _lib.ptr(block), ck.blob, self._stream()), "checkpoint_load")
+            for k, t in mine.items():
+                t.copy_(getattr(ck, k))
+        self._loaded = "restored from a checkpoint"
+        self._auto_reset = bool(ck.auto_reset)
+
+    def fork(self, src, dst) -> None:
+        """antsrl_fork_envs: environment src[i] is copied over environment dst[i], state and output rows (dst entries
+        distinct, none of them a src; a src may repeat).  A destination keeps its own global environment id: under the
+        library's own wall jitter it diverges from its source from then on (include/antsrl.h)."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64).reshape(-1), dtype=np.int32)
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64).reshape(-1), dtype=np.int32)
+        if s.size != d.size:
+            raise ValueError("fork: %d src for %d dst" % (s.size, d.size))
+        i32p = C.POINTER(C.c_int32)
+        with self._on_device():
+            _lib.check(self.lib.antsrl_fork_envs(self._h, s.ctypes.data_as(i32p), d.ctypes.data_as(i32p), int(s.size),
+                                                 self._stream()), "fork_envs")
+            si = torch.as_tensor(s, dtype=torch.int64, device=self.device)
+            di = torch.as_tensor(d, dtype=torch.int64, device=self.device)
+            for t in (self._obs_buf, self.agent_state, self.reward, self.done):
+                t[di] = t[si]
 
     def step_update(self, rotation, phero, wall_jitter=None, want_obs: bool = True):
         """main.py:98 + main.py:131 in one call.  want_obs=False: no observation tensor is written (rewards,

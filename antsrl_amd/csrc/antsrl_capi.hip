@@ -13,6 +13,9 @@
 #include <string.h>
 #include <new>
 
+#include <stddef.h>
+
+#include "antsrl_checkpoint.h"
 #include "antsrl_handle.h"
 #include "antsrl_launch.h"
 
@@ -308,6 +311,49 @@ extern "C" int antsrl_workspace_map(const AntsCfg *cfg, int split, AntsWsArray *
     if (cap < 0 || (cap > 0 && !entries)) return fail(ANTSRL_E_INVALID, "entries is NULL or cap < 0");
     size_t b[2];
     carve(cfg, nullptr, nullptr, nullptr, split != 0, b, entries, cap, count);
+    return ANTSRL_OK;
+}
+
+// The checkpoint's device block (include/antsrl.h, "CHECKPOINT"): every array of the carve but pol_pack, in carve order,
+// each stored whole and rounded up to 256 bytes — the carve's own sequence with the two blocks' counts merged into one, so
+// it does not depend on `split`.  Fills `ws` (the arrays where they lie in a workspace carved with `split` over `base` /
+// `rec_base`; may be NULL with NULL bases) and `ck` side by side, ENV_COPY_MAX_ARRAYS entries each; returns their number.
+static int32_t ckpt_arrays(const AntsCfg *c, bool split, unsigned char *base, unsigned char *rec_base, unsigned char **ptrs,
+                           AntsCkptArray *ck, size_t *device_bytes)
+{
+    AntsWsArray all[ENV_COPY_MAX_ARRAYS + 1];
+    int32_t count = 0, n = 0;
+    size_t b[2], off = 0;
+    carve(c, nullptr, nullptr, nullptr, split, b, all, ENV_COPY_MAX_ARRAYS + 1, &count);
+    if (count > ENV_COPY_MAX_ARRAYS + 1) return -1;
+    for (int32_t i = 0; i < count; ++i) {
+        if (strcmp(all[i].name, "pol_pack") == 0) continue; // the caller's policy, not state: the agent installs it again
+        if (ptrs) ptrs[n] = (all[i].block ? rec_base : base) + all[i].offset;
+        memset(&ck[n], 0, sizeof(ck[n]));
+        memcpy(ck[n].name, all[i].name, sizeof(ck[n].name));
+        ck[n].offset = off;
+        ck[n].bytes_per_env = all[i].bytes / (uint64_t)c->n_envs; // (every array of the carve is environment-major)
+        off = (off + all[i].bytes + 255) / 256 * 256;
+        ++n;
+    }
+    *device_bytes = off;
+    return n;
+}
+
+extern "C" int antsrl_checkpoint_map(const AntsCfg *cfg, AntsCkptArray *entries, int32_t cap, int32_t *count,
+                                     size_t *device_bytes, size_t *host_bytes)
+{
+    int rc = validate(cfg);
+    if (rc) return rc;
+    if (cap < 0 || (cap > 0 && !entries)) return fail(ANTSRL_E_INVALID, "checkpoint_map: entries is NULL or cap < 0");
+    AntsCkptArray ck[ENV_COPY_MAX_ARRAYS];
+    size_t dev = 0;
+    const int32_t n = ckpt_arrays(cfg, false, nullptr, nullptr, nullptr, ck, &dev);
+    if (n < 0) return fail(ANTSRL_E_UNSUPPORTED, "checkpoint_map: more than %d arrays in the carve", ENV_COPY_MAX_ARRAYS);
+    for (int32_t i = 0; i < n && i < cap; ++i) entries[i] = ck[i];
+    if (count) *count = n;
+    if (device_bytes) *device_bytes = dev;
+    if (host_bytes) *host_bytes = sizeof(AntsCkptBlob);
     return ANTSRL_OK;
 }
 
@@ -752,6 +798,149 @@ extern "C" int antsrl_flush(AntsHandle *h, void *stream)
 {
     if (!h) return fail(ANTSRL_E_INVALID, "NULL handle");
     return flush_pending(h, (hipStream_t)stream);
+}
+
+// ---- checkpoint, restore, fork (include/antsrl.h, "CHECKPOINT") ---------------------------------------------------------
+// The arrays of this handle's workspace beside their places in a checkpoint block, as k_env_copy's table; `blk` NULL: the
+// fork's table (rows inside the workspace, bytes per environment).  The workspace's bases are the first array of each block.
+static int ckpt_table(const AntsHandle *h, EnvCopyTable *t, unsigned char *blk, bool to_block, const char *who)
+{
+    const bool split = h->ws_bytes[1] != 0;
+    unsigned char *base = (unsigned char *)h->p.s.x, *rec_base = split ? (unsigned char *)h->p.s.phero[0] : base;
+    unsigned char *ptrs[ENV_COPY_MAX_ARRAYS];
+    AntsCkptArray ck[ENV_COPY_MAX_ARRAYS];
+    size_t dev = 0;
+    const int32_t n = ckpt_arrays(&h->cfg, split, base, rec_base, ptrs, ck, &dev);
+    if (n < 0) return fail(ANTSRL_E_UNSUPPORTED, "%s: more than %d arrays in the carve", who, ENV_COPY_MAX_ARRAYS);
+    if (blk) { // (both directions write one range and read the other: neither may reach into the workspace)
+        const uintptr_t b0 = (uintptr_t)blk, s0 = (uintptr_t)base, r0 = (uintptr_t)rec_base;
+        if ((b0 < s0 + h->ws_bytes[0] && s0 < b0 + dev) || (split && b0 < r0 + h->ws_bytes[1] && r0 < b0 + dev))
+            return fail(ANTSRL_E_INVALID, "%s: device_block overlaps the handle's workspace", who);
+    }
+    memset(t, 0, sizeof(*t));
+    uint64_t chunks = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        EnvCopyArray &a = t->a[i];
+        a.bytes = blk ? ck[i].bytes_per_env * (uint64_t)h->p.E : ck[i].bytes_per_env;
+        unsigned char *in_blk = blk ? blk + ck[i].offset : ptrs[i];
+        a.src = to_block ? ptrs[i] : in_blk;
+        a.dst = to_block ? in_blk : ptrs[i];
+        a.first_chunk = (uint32_t)chunks;
+        chunks += env_copy_chunks(a.bytes);
+    }
+    if (chunks > 0x7fffffffull) return fail(ANTSRL_E_UNSUPPORTED, "%s: the workspace is too large for one copy", who);
+    t->n_arrays = n;
+    t->chunks_per_row = (uint32_t)chunks;
+    return ANTSRL_OK;
+}
+
+// the name of the AntsCfg field that holds byte `off`
+static const char *cfg_field_at(size_t off)
+{
+#define CFG_FIELD(f) \
+    if (off >= offsetof(AntsCfg, f) && off < offsetof(AntsCfg, f) + sizeof(((AntsCfg *)0)->f)) return #f;
+    CFG_FIELD(abi_version) CFG_FIELD(n_envs) CFG_FIELD(n_ants) CFG_FIELD(w) CFG_FIELD(h) CFG_FIELD(n_phero) CFG_FIELD(n_rocks)
+    CFG_FIELD(max_time) CFG_FIELD(perception_radius) CFG_FIELD(n_channels) CFG_FIELD(channel_kind) CFG_FIELD(channel_arg)
+    CFG_FIELD(has_mask) CFG_FIELD(mask) CFG_FIELD(delta) CFG_FIELD(fwd_delta) CFG_FIELD(max_speed) CFG_FIELD(max_rot_speed)
+    CFG_FIELD(carry_speed_reduction) CFG_FIELD(backward_speed_reduction) CFG_FIELD(max_hold) CFG_FIELD(has_max_val)
+    CFG_FIELD(filter_radius) CFG_FIELD(phero_max_val) CFG_FIELD(deposit_strength) CFG_FIELD(phero_threshold) CFG_FIELD(filter)
+    CFG_FIELD(reward_kind) CFG_FIELD(phero_mode) CFG_FIELD(reward_threshold) CFG_FIELD(fct_explore) CFG_FIELD(fct_food)
+    CFG_FIELD(fct_anthill) CFG_FIELD(fct_explore_holding) CFG_FIELD(fct_headinganthill) CFG_FIELD(rng_seed) CFG_FIELD(act_path)
+    CFG_FIELD(env_id_base) CFG_FIELD(n_envs_total)
+#undef CFG_FIELD
+    return "padding";
+}
+
+extern "C" int antsrl_checkpoint_save(AntsHandle *h, void *device_block, void *host_blob, void *stream)
+{
+    if (!h || !device_block || !host_blob) return fail(ANTSRL_E_INVALID, "checkpoint_save: NULL handle, device_block or host_blob");
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if ((uintptr_t)device_block & 15) return fail(ANTSRL_E_INVALID, "checkpoint_save: device_block must be 16-byte aligned");
+    EnvCopyTable t;
+    if (int rc = ckpt_table(h, &t, (unsigned char *)device_block, true, "checkpoint_save")) return rc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc; // (the block holds the state BEHIND a deferred update)
+    if (int rc = enqueued(antsrl_launch_env_copy(t, (hipStream_t)stream), "checkpoint_save")) return rc;
+    AntsCkptBlob b;
+    memset(&b, 0, sizeof(b));
+    b.magic = ANTSRL_CKPT_MAGIC; b.version = ANTSRL_CKPT_VERSION; b.size = sizeof(b);
+    b.cfg = h->cfg;
+    b.cur = h->cur; b.steps_since_update = h->steps_since_update; b.host_timestep = h->host_timestep;
+    b.obs_seq = h->obs_seq; b.sum_obs = h->sum_obs;
+    b.need_full_collect = h->need_full_collect; b.is_reset = h->is_reset; b.episode_over = h->episode_over;
+    b.has_gen = h->has_gen && h->gen.wall_kind != ANTSRL_WALLS_INPUT; // (its bitmaps are the caller's: not carried)
+    b.sum_due = h->sum_due; b.sum_live = h->sum_live; b.need_wall_clear = h->need_wall_clear;
+    b.sweeps = h->sweeps; b.episode_seed = h->episode_seed; b.deposit_strength = h->p.deposit_strength;
+    if (b.has_gen) {
+        b.gen = h->gen;
+        b.gen.walls_input = nullptr;
+    }
+    memcpy(host_blob, &b, sizeof(b));
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_checkpoint_load(AntsHandle *h, const void *device_block, const void *host_blob, void *stream)
+{
+    if (!h || !device_block || !host_blob) return fail(ANTSRL_E_INVALID, "checkpoint_load: NULL handle, device_block or host_blob");
+    AntsCkptBlob b;
+    memcpy(&b, host_blob, 16); // magic, version, size: the rest only once these say what it is
+    if (b.magic != ANTSRL_CKPT_MAGIC) return fail(ANTSRL_E_INVALID, "checkpoint_load: host_blob has magic 0x%08x, not 0x%08x", b.magic, ANTSRL_CKPT_MAGIC);
+    if (b.version != ANTSRL_CKPT_VERSION)
+        return fail(ANTSRL_E_INVALID, "checkpoint_load: host_blob has format version %u, this library reads %u", b.version, ANTSRL_CKPT_VERSION);
+    if (b.size != sizeof(b)) return fail(ANTSRL_E_INVALID, "checkpoint_load: host_blob says size %llu, the format's is %zu", (unsigned long long)b.size, sizeof(b));
+    memcpy(&b, host_blob, sizeof(b));
+    const unsigned char *theirs = (const unsigned char *)&b.cfg, *ours = (const unsigned char *)&h->cfg;
+    for (size_t i = 0; i < sizeof(AntsCfg); ++i)
+        if (theirs[i] != ours[i])
+            return fail(ANTSRL_E_INVALID, "checkpoint_load: the checkpoint's AntsCfg differs from this handle's in %s (byte %zu)", cfg_field_at(i), i);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    if ((uintptr_t)device_block & 15) return fail(ANTSRL_E_INVALID, "checkpoint_load: device_block must be 16-byte aligned");
+    EnvCopyTable t;
+    if (int rc = ckpt_table(h, &t, (unsigned char *)device_block, false, "checkpoint_load")) return rc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc; // (ahead of the copy that replaces what it writes)
+    if (int rc = enqueued(antsrl_launch_env_copy(t, (hipStream_t)stream), "checkpoint_load")) return rc;
+    h->cur = b.cur; h->steps_since_update = b.steps_since_update; h->host_timestep = b.host_timestep;
+    h->obs_seq = b.obs_seq; h->sum_obs = b.sum_obs;
+    h->need_full_collect = b.need_full_collect; h->is_reset = b.is_reset; h->episode_over = b.episode_over;
+    h->sum_due = b.sum_due; h->need_wall_clear = b.need_wall_clear;
+    h->sweeps = b.sweeps; h->episode_seed = b.episode_seed; h->p.deposit_strength = b.deposit_strength;
+    h->has_gen = b.has_gen;
+    if (b.has_gen) h->gen = b.gen;
+    set_decay(h); // g_now / g_dep / inv_g_dep follow from sweeps
+    // The summary's bits came over with explored_bits.  A set bit is a fact about the explored stamps, which came over with
+    // the records (antsrl_explored.h): it stays true in any handle, so one that keeps a summary goes on consuming it.
+    h->sum_live = b.sum_live && summary_on(h);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_fork_envs(AntsHandle *h, const int32_t *src, const int32_t *dst, int32_t n, void *stream)
+{
+    if (!h || !src || !dst) return fail(ANTSRL_E_INVALID, "fork_envs: NULL handle, src or dst");
+    if (n < 1) return fail(ANTSRL_E_INVALID, "fork_envs: n must be >= 1, got %d", n);
+    const int32_t E = h->p.E;
+    uint32_t is_dst[(65535 + 31) / 32 + 1];
+    memset(is_dst, 0, sizeof(is_dst));
+    for (int32_t i = 0; i < n; ++i) { // (stops at the first repeated dst: at most E + 1 entries are read)
+        if (src[i] < 0 || src[i] >= E) return fail(ANTSRL_E_INVALID, "fork_envs: src[%d] = %d is not in [0, %d)", i, src[i], E);
+        if (dst[i] < 0 || dst[i] >= E) return fail(ANTSRL_E_INVALID, "fork_envs: dst[%d] = %d is not in [0, %d)", i, dst[i], E);
+        if (is_dst[dst[i] >> 5] >> (dst[i] & 31) & 1u) return fail(ANTSRL_E_INVALID, "fork_envs: dst %d appears twice (dst[%d])", dst[i], i);
+        is_dst[dst[i] >> 5] |= 1u << (dst[i] & 31);
+    }
+    for (int32_t i = 0; i < n; ++i)
+        if (is_dst[src[i] >> 5] >> (src[i] & 31) & 1u)
+            return fail(ANTSRL_E_INVALID, "fork_envs: environment %d is a src (src[%d]) and a dst", src[i], i);
+    if (int rc = handle_ready(h, MID_UPDATE_REFUSED)) return rc;
+    EnvCopyTable t;
+    if (int rc = ckpt_table(h, &t, nullptr, false, "fork_envs")) return rc;
+    if (int rc = flush_pending(h, (hipStream_t)stream)) return rc;
+    for (int32_t i0 = 0; i0 < n; i0 += ENV_COPY_MAX_PAIRS) { // (the pairs are kernel arguments: one launch per 640 of them)
+        t.rows = n - i0 < ENV_COPY_MAX_PAIRS ? n - i0 : ENV_COPY_MAX_PAIRS;
+        for (int32_t i = 0; i < t.rows; ++i) {
+            t.pair_src[i] = (uint16_t)src[i0 + i];
+            t.pair_dst[i] = (uint16_t)dst[i0 + i];
+        }
+        if (int rc = enqueued(antsrl_launch_env_copy(t, (hipStream_t)stream), "fork_envs")) return rc;
+    }
+    return ANTSRL_OK;
 }
 
 extern "C" int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const int8_t *phero,

@@ -53,6 +53,9 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_perceive(const KP &p, int cur, float *o
 ANTSRL_INTERNAL bool antsrl_explored_summary_supported(const KP &p, bool with_policy);
 ANTSRL_INTERNAL hipError_t antsrl_launch_explored_summary(const KP &p, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_meta_rebase(const KP &p, hipStream_t st);
+// antsrl_checkpoint.hip: k_env_copy over the table of antsrl_checkpoint.h (save, load, fork)
+struct EnvCopyTable;
+ANTSRL_INTERNAL hipError_t antsrl_launch_env_copy(const EnvCopyTable &t, hipStream_t st);
 // antsrl_policy.hip
 ANTSRL_INTERNAL hipError_t antsrl_launch_policy_pack(unsigned char *pack, const float *w1, const float *b1, const float *w2,
                                                      const float *b2, const float *w3, const float *b3, int F, hipStream_t st);

@@ -368,6 +368,59 @@ int antsrl_update_phase(AntsHandle *h, int phase, const double *wall_jitter, voi
  * update with the handle: the workspace is the caller's, flush first if its content is still wanted. */
 int antsrl_flush(AntsHandle *h, void *stream);
 
+/* CHECKPOINT, RESTORE, FORK (no reference counterpart: the reference's state is a handful of numpy arrays that
+ * copy.deepcopy handles).  A batch's state lies in two places: the workspace, whose carve depends on how the handle was
+ * made (one block or two, placed anywhere), and the handle's host fields.  A checkpoint is a DEVICE BLOCK and a HOST BLOB.
+ *
+ * The device block holds every array of antsrl_workspace_map except pol_pack, in carve order, each stored whole
+ * ([E][bytes_per_env]: every array of the carve is environment-major) and rounded up to 256 bytes.  It does not depend on
+ * `split` or on where the workspace lies: a block saved from an antsrl_create handle loads into an antsrl_create2 handle of
+ * the same AntsCfg and the other way round.  pol_pack is the caller's policy (antsrl_set_inloop_policy), not state: the
+ * caller installs it again.  antsrl_checkpoint_map (host only, no handle) reports the block's arrays as
+ * antsrl_workspace_map does the workspace's (min(*count, cap) entries written, any output pointer may be NULL) and the two
+ * sizes: device_bytes, the block's (the end of its last array), and host_bytes, the blob's.
+ *
+ * The host blob is a versioned plain struct of host_bytes bytes, opaque to the caller: a magic, a format version, its own
+ * size, the saving handle's whole AntsCfg, and every field of the handle that an entry point changes after antsrl_create
+ * and that belongs to the episode — the current pheromone buffer, the steps since the last update, whether the next update
+ * collects over the whole grid, the episode's seed and the kept generator (antsrl_generate), Environment.timestep's host
+ * mirror, the scaled units' sweep count (the decay factors are recomputed from it), the explored summary's cadence and
+ * whether it is consumed, the explored stamps' sequence number, a pending wall clear, the deposit strength
+ * (antsrl_set_activation).  AntsGen.walls_input is a caller's pointer and is stored as NULL: a generator of kind
+ * ANTSRL_WALLS_INPUT is NOT carried — the loading handle comes back without a kept generator (no auto-reset) until
+ * antsrl_generate gives it one.  What belongs to the loading handle is not in the blob and stays as the handle has it: the
+ * observation format and row stride, the perceive path, the in-loop policy, the timing events.  The explored summary is
+ * consumed after a load when the checkpoint's was and the loading handle keeps one (ANTSRL_Q_EXPLORED_SUMMARY).
+ *
+ * antsrl_checkpoint_save: enqueues a deferred update first (the block holds the state behind it), then ONE copy kernel on
+ * `stream`; the blob is written before the call returns, the block is complete once `stream` has drained.  device_block:
+ * device memory of device_bytes bytes, 16-byte aligned, outside the workspace.
+ * antsrl_checkpoint_load: the reverse, into a handle that holds an episode (antsrl_reset / antsrl_generate has been called;
+ * whatever it held is replaced).  Refused with ANTSRL_E_INVALID, before anything is enqueued, when the blob's magic, version
+ * or size is not this library's or its AntsCfg differs from the handle's in any byte (the message names the first field
+ * that differs).  From a load on, every entry point continues bit for bit as the saving handle did from the save on.
+ * The caller-owned outputs (obs, agent_state, reward, done) are the caller's to keep beside the checkpoint.
+ *
+ * antsrl_fork_envs: environment src[i] is copied over environment dst[i], i = 0 .. n - 1, inside the workspace (`src` and
+ * `dst` are HOST arrays).  n >= 1, every index in [0, n_envs), the dst entries distinct, no dst entry among the src entries;
+ * a src entry may repeat (one source fans out).  The pairs travel as kernel arguments: one launch per 640 pairs.  The
+ * handle's host fields are shared by all its environments (they step in lockstep) and do not change.  A destination keeps
+ * its own GLOBAL ENVIRONMENT ID (AntsCfg.env_id_base + index): with the library's own wall jitter (antsrl_update with
+ * wall_jitter == NULL) its jitter stream is its own from the fork on, so a branch diverges from its source as soon as one
+ * of its ants runs into a wall, even under equal actions; with explicit wall_jitter rows equal to the source's — or on a
+ * map without walls — it repeats the source exactly.
+ *
+ * All three refuse a handle without an episode and one between two phases of antsrl_update_phase. */
+typedef struct AntsCkptArray {
+    char name[24];
+    uint64_t offset, bytes_per_env;
+} AntsCkptArray;
+int antsrl_checkpoint_map(const AntsCfg *cfg, AntsCkptArray *entries, int32_t cap, int32_t *count, size_t *device_bytes,
+                          size_t *host_bytes);
+int antsrl_checkpoint_save(AntsHandle *h, void *device_block, void *host_blob, void *stream);
+int antsrl_checkpoint_load(AntsHandle *h, const void *device_block, const void *host_blob, void *stream);
+int antsrl_fork_envs(AntsHandle *h, const int32_t *src, const int32_t *dst, int32_t n, void *stream);
+
 /* main.py:98 followed by main.py:131 — one full simulation step. */
 int antsrl_step_update(AntsHandle *h, const int8_t *rotation, const int8_t *phero,
                        const double *wall_jitter, float *obs, float *agent_state, float *reward,
