@@ -5,7 +5,7 @@ from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
            "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats",
-           "EnvCheckpoint"]
+           "EnvCheckpoint", "PopulationAgent", "train_population"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -39,7 +39,10 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "EnvCheckpoint":
         from .checkpoint import EnvCheckpoint
         return EnvCheckpoint
-    if name in ("train_episodes", "epsilon_schedule"):
+    if name == "PopulationAgent":
+        from .population import PopulationAgent
+        return PopulationAgent
+    if name in ("train_episodes", "train_population", "epsilon_schedule"):
         from . import driver
         return getattr(driver, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

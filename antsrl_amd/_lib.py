@@ -32,7 +32,9 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_recorder_begin", "antsrl_recorder_frame", "antsrl_render_sizes", "antsrl_render_frames",
            "antsrl_stats_sizes", "antsrl_stats_row", "antsrl_jointtrain_sizes", "antsrl_jointtrain_grad",
            "antsrl_jointtrain_apply", "antsrl_jointtrain_step", "antsrl_obs_coords", "antsrl_give_reward",
-           "antsrl_checkpoint_map", "antsrl_checkpoint_save", "antsrl_checkpoint_load", "antsrl_fork_envs")
+           "antsrl_checkpoint_map", "antsrl_checkpoint_save", "antsrl_checkpoint_load", "antsrl_fork_envs",
+           "antsrl_pop_policy", "antsrl_pop_select", "antsrl_pop_record_pre", "antsrl_pop_record_post",
+           "antsrl_pop_lintrain_step")
 
 _lib = None
 
@@ -68,6 +70,21 @@ class AntsWsArray(C.Structure):
 class AntsCkptArray(C.Structure):
     """include/antsrl.h AntsCkptArray."""
     _fields_ = [("name", C.c_char * 24), ("offset", C.c_uint64), ("bytes_per_env", C.c_uint64)]
+
+
+POP_MAX = 64  # include/antsrl.h ANTSRL_POP_MAX
+
+
+class AntsPopMember(C.Structure):
+    """include/antsrl.h AntsPopMember."""
+    _fields_ = [("seed", C.c_uint64), ("epsilon", C.c_double), ("learning_rate", C.c_double), ("discount", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class AntsPopSpec(C.Structure):
+    """include/antsrl.h AntsPopSpec."""
+    _fields_ = [(n, C.c_int32) for n in ("n_members", "n_envs", "n_ants", "env_id_base", "n_features", "obs_format",
+                                         "obs_pitch", "reserved")] + [("members", AntsPopMember * POP_MAX)]
 
 
 class AntsrlError(RuntimeError):
@@ -192,6 +209,13 @@ def load() -> C.CDLL:
     lib.antsrl_render_frames.argtypes = [vp, vp, i32, i32, i32, i32, i32, C.POINTER(AntsRenderOpts), vp, vp, vp]
     lib.antsrl_stats_sizes.argtypes = [vp, i32, sz, sz, sz]
     lib.antsrl_stats_row.argtypes = [vp, vp, i32, i32, vp]
+    ps = C.POINTER(AntsPopSpec)
+    lib.antsrl_pop_policy.argtypes = [ps] + [vp] * 9
+    lib.antsrl_pop_select.argtypes = [ps, C.c_uint64, vp, vp, vp, vp]
+    lib.antsrl_pop_record_pre.argtypes = [ps, C.c_uint64, C.c_int64, C.c_int64, C.c_int64] + [vp] * 8
+    lib.antsrl_pop_record_post.argtypes = [ps, C.c_uint64, C.c_int64, C.c_int64, C.c_int64] + [vp] * 9
+    lib.antsrl_pop_lintrain_step.argtypes = [ps] + [vp] * 12 + [C.c_int64, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
+                                                                C.c_double, vp, vp, vp, i32, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

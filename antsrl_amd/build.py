@@ -22,7 +22,8 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
            "antsrl_memapi.hip", "antsrl_lintrain.hip", "antsrl_exptrain.hip", "antsrl_jointtrain.hip",
            "antsrl_linapi.hip",
            "antsrl_rework.hip", "antsrl_reworktrain.hip", "antsrl_reworkapi.hip", "antsrl_monitor.hip", "antsrl_recorder.hip",
-           "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip"]
+           "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip",
+           "antsrl_population.hip", "antsrl_popapi.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
@@ -30,7 +31,11 @@ HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
                                            "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",
                                            "antsrl_cellread.h", "antsrl_recorder.h", "antsrl_render.h", "antsrl_stats.h",
-                                           "antsrl_launch.h", "antsrl_handle.h", "antsrl_checkpoint.h")] + [
+                                           "antsrl_launch.h", "antsrl_handle.h", "antsrl_checkpoint.h",
+                                           "antsrl_policy_flat.h", "antsrl_memagent_dev.h", "antsrl_lintrain_dev.h",
+                                           "antsrl_population.h", "antsrl_policy_flat_body.inc",
+                                           "antsrl_agent_select_actions.inc", "antsrl_replay_record_body.inc",
+                                           "antsrl_lintrain_body.inc")] + [
     os.path.join(HERE, "..", "include", "antsrl.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]
@@ -45,7 +50,7 @@ def hipcc() -> str:
 
 #: host-only translation units (no kernel in them): a change there moves no byte on the device
 HOST_ONLY_SOURCES = ("antsrl_capi.hip", "antsrl_mem.hip", "antsrl_memapi.hip", "antsrl_linapi.hip",
-                     "antsrl_reworkapi.hip", "antsrl_logapi.hip")
+                     "antsrl_reworkapi.hip", "antsrl_logapi.hip", "antsrl_popapi.hip")
 
 
 def source_hash() -> str:

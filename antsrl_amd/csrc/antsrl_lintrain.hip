@@ -20,23 +20,8 @@
 // 198 floats.  No atomics anywhere: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_dqn_dev.h"
 #include "antsrl_lds_optin.h"
-#include "antsrl_lintrain.h"
-
-#define LT_HSTRIDE 33 // floats per row of a wave's h tile: 32 hidden values and the 1.0 of the biases
-#define LT_DSTRIDE 8  // floats per row of its dq tile: 6 dq, the loss term, pad
-#define LT_SLOT 100   // floats per head in LDS: [3][32] + [3], padded to 16 bytes
-#define LT_HW 304     // the three slots, padded
-
-// what thread t < LT_OUT does with total t of the step: gradient t (and Adam on trained float t), or the loss
-__device__ __forceinline__ void lt_epilogue(const LinTrainArgs &a, const int t, const float total)
-{
-    if (t == LT_HEADS)
-        *a.batch.loss = total;
-    else
-        dqn_store_adam(a.heads, a.batch.grads, a.adam, t, total);
-}
+#include "antsrl_lintrain_dev.h" // lt_epilogue, lt_lds, the LDS layout: shared with antsrl_population.hip
 
 // One wave per SIMD (amdgpu_waves_per_eu(1, 1)): with two workgroups resident on a CU, about 1 launch in 17 at F = 294 and
 // 512 workgroups left ONE workgroup's 199 partials different from every other launch's, always one of the first 256
@@ -45,131 +30,7 @@ __device__ __forceinline__ void lt_epilogue(const LinTrainArgs &a, const int t, 
 template <int NW> // waves per workgroup
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) k_lintrain(const LinTrainArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    const DqnBatch &mb = a.batch;
-    const int F = mb.F, IN = F + 2, ksteps = mb.ksteps, KP = 16 * ksteps + 8; // 8 = bank skew
-    __bf16 *w1s = reinterpret_cast<__bf16 *>(smem);                                        // [32][KP]
-    float *hw = reinterpret_cast<float *>(smem + (size_t)LT_HIDDEN * KP * 2); // 3 slots of LT_SLOT: layer2, layer3, the target's layer3
-    float *l1x = hw + LT_HW;                                                  // [3][32]: b1 and the bf16-rounded W1 columns F, F + 1
-    float *wpart = l1x + 3 * LT_HIDDEN;                                       // [NW][LT_PART]
-    float *tiles = wpart + NW * LT_PART;                                                   // per wave: h [32][33], dq [32][8]
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5, wib = threadIdx.x >> 6;
-    float *ht = tiles + (size_t)wib * (32 * LT_HSTRIDE + 32 * LT_DSTRIDE), *dqs = ht + 32 * LT_HSTRIDE;
-
-    dqn_stage_w1(a.w1, w1s, F, ksteps, KP, wib, NW, lane);
-    for (int i = threadIdx.x; i < LT_HEADS + LT_L3; i += 64 * NW)
-        hw[(i / LT_L3) * LT_SLOT + i % LT_L3] = i < LT_HEADS ? a.heads[i] : a.target_l3[i - LT_HEADS];
-    if (threadIdx.x < LT_HIDDEN) {
-        const int hid = threadIdx.x;
-        l1x[hid] = a.b1[hid];
-        l1x[LT_HIDDEN + hid] = (float)(__bf16)a.w1[(size_t)hid * IN + F];
-        l1x[2 * LT_HIDDEN + hid] = (float)(__bf16)a.w1[(size_t)hid * IN + F + 1];
-    }
-    ht[r * LT_HSTRIDE + 32] = 1.0f; // (both half-waves write the same value)
-    __syncthreads();
-
-    float out[4] = {0.0f, 0.0f, 0.0f, 0.0f}; // outputs lane, lane + 64, lane + 128, lane + 192
-    // output o as a column of dq times a column of h: w2 [o / 32][o % 32], b2, w3, b3, the loss
-    int dcol[4], hcol[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int o = lane + 64 * j;
-        if (o < 96) { dcol[j] = o >> 5; hcol[j] = o & 31; }
-        else if (o < 99) { dcol[j] = o - 96; hcol[j] = 32; }
-        else if (o < 195) { dcol[j] = 3 + ((o - 99) >> 5); hcol[j] = (o - 99) & 31; }
-        else if (o < 198) { dcol[j] = 3 + (o - 195); hcol[j] = 32; }
-        else { dcol[j] = 6; hcol[j] = 32; } // o == 198: the loss (o > 198 is never stored)
-    }
-
-    const __bf16 *wrow = w1s + r * KP + 8 * h;
-    const int nwhole = F / 16; // k-steps whose 16 inputs all lie inside the row
-    for (int t = blockIdx.x * NW + wib; t < mb.ntiles; t += gridDim.x * NW) {
-        const int brow = t * 32 + r;
-        const bool valid = brow < mb.B;
-        const long long ri = dqn_row(mb, min(brow, mb.B - 1));
-        const float *xs = mb.states + (size_t)ri * F, *xn = mb.new_states + (size_t)ri * F;
-        f32x16 acc, accn;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = accn[g] = 0.0f;
-        int s = 0;
-#pragma unroll 1
-        for (; s < nwhole; ++s) {
-            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, true), bn = dqn_frag(xn, 16 * s + 8 * h, F, true);
-            const bf16x8 af = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bs, acc, 0, 0, 0);
-            accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bn, accn, 0, 0, 0);
-        }
-#pragma unroll 1
-        for (; s < ksteps; ++s) {
-            const bf16x8 bs = dqn_frag(xs, 16 * s + 8 * h, F, false), bn = dqn_frag(xn, 16 * s + 8 * h, F, false);
-            const bf16x8 af = *reinterpret_cast<const bf16x8 *>(wrow + 16 * s);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bs, acc, 0, 0, 0);
-            accn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bn, accn, 0, 0, 0);
-        }
-        const float as0 = (float)(__bf16)mb.agent_states[(size_t)ri * 2], as1 = (float)(__bf16)mb.agent_states[(size_t)ri * 2 + 1];
-        const float an0 = (float)(__bf16)mb.new_agent_states[(size_t)ri * 2], an1 = (float)(__bf16)mb.new_agent_states[(size_t)ri * 2 + 1];
-        float hv[16], hn[16];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) { // accumulator register g = 4 g4 + j of half-wave h is hidden value 8 g4 + 4 h + j
-            const float4 bb = *reinterpret_cast<const float4 *>(l1x + 8 * g4 + 4 * h);
-            const float4 c0 = *reinterpret_cast<const float4 *>(l1x + LT_HIDDEN + 8 * g4 + 4 * h);
-            const float4 c1 = *reinterpret_cast<const float4 *>(l1x + 2 * LT_HIDDEN + 8 * g4 + 4 * h);
-            const float bias1[4] = {bb.x, bb.y, bb.z, bb.w}, was0[4] = {c0.x, c0.y, c0.z, c0.w}, was1[4] = {c1.x, c1.y, c1.z, c1.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                hv[4 * g4 + j] = dqn_hidden(acc[4 * g4 + j], as0, was0[j], as1, was1[j], bias1[j]);
-                hn[4 * g4 + j] = dqn_hidden(accn[4 * g4 + j], an0, was0[j], an1, was1[j], bias1[j]);
-            }
-        }
-        float qr[3], qp[3], nr[3], np[3];
-        // (scheduling fences: the 48 weight vectors of the four heads are not all hoisted in front of the first product)
-        __builtin_amdgcn_sched_barrier(0);
-        dqn_head(hw, hv, h, qr);                  // model: layer2
-        __builtin_amdgcn_sched_barrier(0);
-        dqn_head(hw + LT_SLOT, hv, h, qp);        //        layer3
-        __builtin_amdgcn_sched_barrier(0);
-        dqn_head(hw, hn, h, nr);                  // target: the shared, live layer2
-        __builtin_amdgcn_sched_barrier(0);
-        dqn_head(hw + 2 * LT_SLOT, hn, h, np);    //         its own layer3
-        __builtin_amdgcn_sched_barrier(0);
-        const long long ar64 = mb.actions[(size_t)ri * 2], ap64 = mb.actions[(size_t)ri * 2 + 1];
-        const int ar = ar64 < 0 ? 0 : (ar64 > 2 ? 2 : (int)ar64), ap = ap64 < 0 ? 0 : (ap64 > 2 ? 2 : (int)ap64);
-        const float rew = mb.rewards[ri], live = mb.dones[ri] ? 0.0f : 1.0f;
-        const float yr = rew + mb.discount * fmaxf(fmaxf(nr[0], nr[1]), nr[2]) * live;
-        const float yp = rew + mb.discount * fmaxf(fmaxf(np[0], np[1]), np[2]) * live;
-        const float dr = (ar == 0 ? qr[0] : ar == 1 ? qr[1] : qr[2]) - yr, dp = (ap == 0 ? qp[0] : ap == 1 ? qp[1] : qp[2]) - yp;
-        dqn_wave_sync(); // the previous tile's sums are done with the tile
-#pragma unroll
-        for (int g = 0; g < 16; ++g) ht[r * LT_HSTRIDE + (g & 3) + 8 * (g >> 2) + 4 * h] = hv[g];
-        if (h == 0) {
-            const float gr = valid ? dr * mb.dq_scale : 0.0f, gp = valid ? dp * mb.dq_scale : 0.0f;
-#pragma unroll
-            for (int o = 0; o < 3; ++o) {
-                dqs[r * LT_DSTRIDE + o] = ar == o ? gr : 0.0f;
-                dqs[r * LT_DSTRIDE + 3 + o] = ap == o ? gp : 0.0f;
-            }
-            dqs[r * LT_DSTRIDE + 6] = valid ? dr * dr * mb.loss_scale + dp * dp * mb.loss_scale : 0.0f;
-        }
-        dqn_wave_sync();
-#pragma unroll 4
-        for (int rr = 0; rr < 32; ++rr) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) out[j] += dqs[rr * LT_DSTRIDE + dcol[j]] * ht[rr * LT_HSTRIDE + hcol[j]];
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (lane + 64 * j < LT_OUT) wpart[wib * LT_PART + lane + 64 * j] = out[j];
-    __syncthreads();
-    if (threadIdx.x < LT_OUT) {
-        float s = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) s += wpart[w * LT_PART + threadIdx.x];
-        if (gridDim.x == 1)
-            lt_epilogue(a, threadIdx.x, s); // (every wave has read the heads into LDS long before: behind two barriers)
-        else
-            mb.partials[(size_t)blockIdx.x * LT_PART + threadIdx.x] = s;
-    }
+#include "antsrl_lintrain_body.inc"
 }
 
 __global__ void __launch_bounds__(256) k_lintrain_finish(const LinTrainArgs a, const int nblocks)
@@ -185,12 +46,6 @@ __global__ void __launch_bounds__(256) k_adam_flat(float *params, const AdamArgs
 {
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p < P) adam_at(params, o, p, grads[p]);
-}
-
-static size_t lt_lds(int ksteps, int nw)
-{
-    return (size_t)LT_HIDDEN * (16 * ksteps + 8) * 2 +
-           (LT_HW + 3 * LT_HIDDEN + (size_t)nw * LT_PART + (size_t)nw * (32 * LT_HSTRIDE + 32 * LT_DSTRIDE)) * 4;
 }
 
 int antsrl_lintrain_blocks(int B, int F)

@@ -16,31 +16,15 @@
 // re-reads them before a training step samples them).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_draw.h" // the draw specification (include/antsrl.h)
-#include "antsrl_memagent.h"
-#include "antsrl_util.h"
+#include "antsrl_memagent_dev.h" // env_explores, load4, load1: what the bodies a population shares (the .inc texts) call
 
 // ------------------------------------------------------------------ antsrl_agent_select
-__device__ __forceinline__ bool env_explores(const SelArgs &a, uint32_t e)
-{
-    return draw_u01(agent_draw(a.seed, ANTSRL_DRAW_EXPLORE, (uint64_t)a.env_base + e, a.step, 0)) < a.epsilon;
-}
-
-// Part 1: one thread per ant (the actions).  Part 2: one thread per memory element (V floats), coalesced.
+// Part 1: one thread per ant (the actions: antsrl_agent_select_actions.inc).  Part 2: one thread per memory element (V floats), coalesced.
 template <int V>
 __global__ __launch_bounds__(256) void k_agent_select(const SelArgs a)
 {
     const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x, nthr = (uint64_t)gridDim.x * 256;
-    for (uint64_t i = tid; i < a.M; i += nthr) {
-        const uint32_t e = (uint32_t)i / a.n_ants, ai = (uint32_t)i - e * a.n_ants;
-        const bool ex = env_explores(a, e);
-        if (ex) {
-            const uint64_t env = (uint64_t)a.env_base + e;
-            a.rot[i] = (int8_t)((int)draw_below(agent_draw(a.seed, ANTSRL_DRAW_ROTATION, env, a.step, ai), a.n_rot) - (int)(a.n_rot / 2));
-            a.ph[i] = (int8_t)draw_below(agent_draw(a.seed, ANTSRL_DRAW_PHEROMONE, env, a.step, ai), a.n_ph);
-        }
-        if (ai == 0 && a.explored) a.explored[e] = ex ? 1 : 0;
-    }
+#include "antsrl_agent_select_actions.inc"
     if (a.mem_old == a.mem_next) return;
     for (uint64_t f = tid; f < a.mem_elems; f += nthr) {
         const uint32_t e = (uint32_t)(f / a.env_elems);
@@ -92,100 +76,10 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_agent_plan(const SelArgs a, co
 }
 
 // ------------------------------------------------------------------ antsrl_replay_record_pre / _post
-// 4 consecutive elements at p as floats.  mode 0: one load of the 4 (16 bytes float32, 8 bytes bfloat16), 1: two loads,
-// 2: four.  The caller picks the mode from p's alignment.
-template <bool BF16>
-__device__ __forceinline__ float4 load4(const void *p, int mode)
-{
-    if (BF16) {
-        uint32_t lo, hi;
-        if (mode == 0) {
-            const uint2 v = *reinterpret_cast<const uint2 *>(p);
-            lo = v.x; hi = v.y;
-        } else if (mode == 1) {
-            lo = reinterpret_cast<const uint32_t *>(p)[0];
-            hi = reinterpret_cast<const uint32_t *>(p)[1];
-        } else {
-            const uint16_t *q = reinterpret_cast<const uint16_t *>(p);
-            lo = (uint32_t)q[0] | ((uint32_t)q[1] << 16);
-            hi = (uint32_t)q[2] | ((uint32_t)q[3] << 16);
-        }
-        return make_float4(__uint_as_float(lo << 16), __uint_as_float(lo & 0xFFFF0000u), __uint_as_float(hi << 16),
-                           __uint_as_float(hi & 0xFFFF0000u));
-    }
-    if (mode == 0) return *reinterpret_cast<const float4 *>(p);
-    if (mode == 1) {
-        const float2 l = reinterpret_cast<const float2 *>(p)[0], h = reinterpret_cast<const float2 *>(p)[1];
-        return make_float4(l.x, l.y, h.x, h.y);
-    }
-    const float *q = reinterpret_cast<const float *>(p);
-    return make_float4(q[0], q[1], q[2], q[3]);
-}
-
-template <bool BF16>
-__device__ __forceinline__ float load1(const void *base, int i)
-{
-    if (BF16) return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t *>(base)[i] << 16);
-    return reinterpret_cast<const float *>(base)[i];
-}
-
 template <bool BF16, bool POST>
 __global__ __launch_bounds__(256) void k_replay_record(const RecArgs a)
 {
-    const int lane = threadIdx.x & 63;
-    const long long w = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (w >= a.n_write) return;
-    const long long j = a.j0 + w;
-    long long row = a.row0 + w;
-    if (row >= a.max_len) row -= a.max_len;
-    long long ant = j; // K == M: the identity
-    if (a.K != a.M) {
-        const long long lo = j * a.M / a.K, hi = (j + 1) * a.M / a.K, n = hi - lo;
-        long long off = 0;
-        if (n > 1) {
-            const double u = draw_u01(agent_draw(a.seed, ANTSRL_DRAW_SAMPLE, a.env_base, a.step, (uint64_t)j));
-            off = (long long)floor(u * (double)n);
-            if (off > n - 1) off = n - 1;
-        }
-        ant = lo + off;
-    }
-
-    // ---- the observation row
-    const int F = a.F;
-    const size_t esz = BF16 ? 2 : 4;
-    const unsigned char *src = reinterpret_cast<const unsigned char *>(a.obs) + (size_t)ant * (size_t)a.pitch * esz;
-    float *dst = a.states + (size_t)row * F;
-    int h = (int)(((16 - ((uintptr_t)dst & 15)) & 15) >> 2); // elements in front of dst's first 16-byte boundary
-    if (h > F) h = F;
-    const int nvec = (F - h) >> 2, t0 = h + 4 * nvec;
-    if (lane < h)
-        dst[lane] = load1<BF16>(src, lane);
-    else if (t0 + (lane - h) < F)
-        dst[t0 + (lane - h)] = load1<BF16>(src, t0 + (lane - h));
-    const unsigned char *sb = src + (size_t)h * esz;
-    const uintptr_t sa = (uintptr_t)sb;
-    const int mode = BF16 ? ((sa & 7) == 0 ? 0 : (sa & 3) == 0 ? 1 : 2) : ((sa & 15) == 0 ? 0 : (sa & 7) == 0 ? 1 : 2);
-    float4 *dv = reinterpret_cast<float4 *>(dst + h);
-    for (int v = lane; v < nvec; v += 128) { // two rounds of loads in flight before the stores
-        const bool two = v + 64 < nvec;
-        const float4 x0 = load4<BF16>(sb + (size_t)v * 4 * esz, mode);
-        float4 x1 = x0;
-        if (two) x1 = load4<BF16>(sb + (size_t)(v + 64) * 4 * esz, mode);
-        store_stream(&dv[v], x0);
-        if (two) store_stream(&dv[v + 64], x1);
-    }
-
-    // ---- the small fields, on the highest lanes
-    const int c = 63 - lane, AM = a.A + a.mem;
-    if (c < AM)
-        a.agent_states[(size_t)row * AM + c] = c < a.A ? a.agent_state[(size_t)ant * a.A + c] : a.memory[(size_t)ant * a.mem + (c - a.A)];
-    if (POST) {
-        if (c == 0) a.rewards[row] = a.reward[ant];
-        if (c == 1) a.dones[row] = a.done[(uint32_t)ant / (uint32_t)a.n_ants] ? 1 : 0;
-    } else {
-        if (c == 0) a.actions[2 * row] = (int64_t)a.rot[ant] + a.half_rot;
-        if (c == 1) a.actions[2 * row + 1] = a.ph ? (int64_t)a.ph[ant] : 1;
-    }
+#include "antsrl_replay_record_body.inc"
 }
 
 // ------------------------------------------------------------------ launchers (antsrl_memagent.h)

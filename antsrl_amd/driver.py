@@ -11,6 +11,9 @@ visualised episodes' frames on the device, antsrl_amd/recorder.py, and reads the
 those episodes are also drawn on the device (antsrl_amd/render.py) and written as PNG files.  With stats_every the colony's
 own numbers (food at the anthill, on the map and carried, explored cells, pheromone: antsrl_amd/stats.py) are reduced on
 the device every so many steps and read back once, with the monitor's log.
+
+`train_population` is the same loop for a PopulationAgent (antsrl_amd/population.py): P linear agents with their own
+seed, epsilon, discount and learning rate on one handle, per-member rewards, running losses and epsilon schedules.
 """
 from __future__ import annotations
 
@@ -39,6 +42,62 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
     if gen.rng_kind == cm.RNG_REFERENCE:
         return seed + episode * (cfg.n_envs_total or cfg.env_id_base + cfg.n_envs)
     return seed + episode
+
+
+def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True, min_epsilon=0.01,
+                     max_epsilon=1.0, monitor: Optional[EpisodeMonitor] = None, report_every: int = 50,
+                     save_as: Optional[str] = None) -> dict:
+    """train_episodes' loop for a PopulationAgent (antsrl_amd/population.py) on `env`, whose n_envs are the members' equal
+    shares: a fresh map per episode, pop.setup once, pop.initialize and the first observation per episode, `steps`
+    rollout_steps, and after every episode member p's epsilon from epsilon_schedule with its own bounds (min_epsilon,
+    max_epsilon: numbers, or arrays [P]).  No host read of device data before the end.
+
+    The statistics per member: its episode reward comes from an EpisodeMonitor's per-environment totals (fed loss=None;
+    `monitor` to continue one or by default one that reports every `report_every` steps), summed over the member's
+    environments on the host at the end; its running loss is PopulationLinearTrainer.running_loss (main.py:106-109 from
+    the member's first training step on, kept by the training launch), copied into a [episodes, P] device log at each
+    episode's end.  save_as: a format with one %d, pop.save_model(p, save_as % p) for every member at the end, when training.
+
+    Returns the monitor's log() with `member_total` and `member_reward` (float64 [episodes, P]: the sum and the mean per
+    ant of the member's environments at the episode's last report, 0 without one), `member_loss` (float64 [episodes, P],
+    nan while the population has not trained), `epsilons` ([episodes, P]: what each episode ran with) and `monitor`."""
+    import torch
+    env = getattr(env, "_backend", env)
+    P = pop.n_members
+    lo = np.broadcast_to(np.asarray(min_epsilon, dtype=np.float64), (P,))
+    hi = np.broadcast_to(np.asarray(max_epsilon, dtype=np.float64), (P,))
+    mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=report_every,
+                                                             max_reports=max(1, episodes * (steps // report_every)),
+                                                             max_episodes=max(1, episodes))
+    loss_log = torch.full((max(1, episodes), P), float("nan"), dtype=torch.float64, device=env.device)
+    epsilons, first_episode = [], mon.episode  # (a continued monitor counts its earlier episodes)
+    for episode in range(episodes):
+        env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
+        if pop.trainer is None:
+            pop.setup(env)
+        pop.initialize(env)
+        env.observe()
+        epsilons.append(pop.epsilon.copy())
+        for s in range(steps):
+            pop.rollout_step(env, training)
+            mon.step(env.reward, None)
+        if training and pop.trainer.step_count > 0:
+            loss_log[episode].copy_(pop.trainer.running_loss)
+        mon.end_episode()
+        pop.epsilon = [epsilon_schedule(episode, float(lo[p]), float(hi[p])) for p in range(P)]
+    if save_as is not None and training:
+        for p in range(P):
+            pop.save_model(p, save_as % p)
+    log = mon.log()
+    E, N = env.cfg.n_envs, env.cfg.n_ants
+    total = np.zeros((episodes, P))
+    for episode in range(episodes):
+        at = np.nonzero(log["report_episode"] == first_episode + episode)[0]
+        if len(at):  # the episode's last report: {total, min, max} per environment
+            total[episode] = log["reports"][at[-1], :, 0].reshape(P, E // P).sum(axis=1)
+    log.update(member_total=total, member_reward=total / float(E // P * N), member_loss=loss_log[:episodes].cpu().numpy(),
+               epsilons=np.array(epsilons).reshape(episodes, P), monitor=mon)
+    return log
 
 
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,

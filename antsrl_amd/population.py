@@ -1,0 +1,386 @@
+"""A population of P CollectAgents trained in lockstep on one BatchedAntsEnv, one launch per stage of the loop whatever
+P is (include/antsrl.h, "The population of linear agents"; antsrl_population.hip).
+
+    pop = PopulationAgent([dict(epsilon=0.5, discount=0.99, learning_rate=1e-4, seed=s) for s in range(16)],
+                          record_per_step=4096, min_replay=1000)
+    pop.setup(env)                      # env.cfg.n_envs = 16 * Em: member p owns environments [p Em, (p + 1) Em)
+    loss = pop.rollout_step(env)        # float32 [P] on the device (0 below min_replay): five launches and the env's step
+
+Member p is, bit for bit, a CollectAgent run alone on a handle of its Em environments created with env_id_base =
+cfg.env_id_base + p Em and the member's own seed, epsilon, discount and learning rate (tests/test_gpu_population.py): the
+kernels are the single agent's stages with the member taken from the grid, and every draw of the agents' loop is keyed
+on (seed, global environment id, step).
+
+The pieces mirror the single agent's: `PopulationLinearTrainer` (LinearTrainer's tensors with a leading [P]),
+`PopulationReplayMemory` (DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
+record the same number of rows at every step) and `PopulationAgent` (CollectAgent's surface, per member where the
+reference's has one model).  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
+changed epsilon costs no device copy.  Out of scope: the other agents' nets, in-loop acting (a handle holds one policy
+pack), B > 512, members of unequal size, training_state.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ptr as _p
+from . import config as cm
+from .agent import _backend
+from .policy import linear_init
+from .train import EXPLORE_NAMES, LINEAR_TRAINED
+
+RING_NAMES = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
+MEMBER_DEFAULTS = dict(epsilon=0.1, discount=0.5, learning_rate=1e-4, seed=0)  # CollectAgent's
+
+
+def _members(members: Sequence[dict]) -> list:
+    assert 1 <= len(members) <= _lib.POP_MAX, "a population has 1 .. %d members (%d)" % (_lib.POP_MAX, len(members))
+    out = []
+    for m in members:
+        extra = set(m) - set(MEMBER_DEFAULTS)
+        assert not extra, "a member is dict(epsilon=, discount=, learning_rate=, seed=), not %s" % sorted(extra)
+        out.append(dict(MEMBER_DEFAULTS, **m))
+    return out
+
+
+class _Geometry:
+    """What every entry's AntsPopSpec says of the handle: the batch, the observation rows and the members' host values."""
+
+    def __init__(self, n_members: int, n_envs: int, n_ants: int, env_id_base: int, n_features: int, obs_dtype):
+        if n_envs % n_members:
+            raise ValueError("n_envs = %d is not a multiple of the population's %d members" % (n_envs, n_members))
+        self.P, self.n_envs, self.n_ants, self.env_id_base, self.n_features = n_members, n_envs, n_ants, env_id_base, n_features
+        self.Em = n_envs // n_members
+        self.Mm = self.Em * n_ants
+        self.obs_format = 1 if obs_dtype == torch.bfloat16 else 0  # ANTSRL_OBS_BF16 / ANTSRL_OBS_F32
+
+    def spec(self, seed, epsilon, learning_rate, discount) -> _lib.AntsPopSpec:
+        """The AntsPopSpec of these host values.  The last one built is kept and handed out again while the values stay
+        the same: a step builds none, an episode's new epsilons build one."""
+        key = (tuple(int(v) for v in seed), tuple(float(v) for v in epsilon), tuple(float(v) for v in learning_rate),
+               tuple(float(v) for v in discount))
+        if getattr(self, "_spec_key", None) != key:
+            s = _lib.AntsPopSpec(self.P, self.n_envs, self.n_ants, self.env_id_base, self.n_features, self.obs_format, 0, 0)
+            for p in range(self.P):
+                s.members[p] = _lib.AntsPopMember(key[0][p], key[1][p], key[2][p], key[3][p], 0)
+            self._spec_key, self._spec = key, s
+        return self._spec
+
+
+class _MemberRing:
+    """Member p's slab of a PopulationReplayMemory under DeviceReplayMemory's names (views, not copies)."""
+
+    def __init__(self, ring, p: int):
+        for n in RING_NAMES:
+            setattr(self, n, getattr(ring, n)[p])
+        self.head, self.fill, self.max_len = ring.head, ring.fill, ring.max_len
+
+    def __len__(self):
+        return self.fill
+
+
+class PopulationReplayMemory:
+    """DeviceReplayMemory's seven arrays with a leading [P]: states [P, max_len, 7, 7, K] and so on.  `head` and `fill`
+    are shared.  record_pre / record_post are antsrl_pop_record_pre / _post: K rows per member and step into the same
+    rows of every member's slab, each member sampling its own ants with its own seed."""
+
+    def __init__(self, n_members: int, max_len: int, observation_space: Sequence[int], device="cuda"):
+        self.n_members, self.max_len, self.observation_space = n_members, max_len, tuple(observation_space)
+        self.device = torch.device(device)
+        z = lambda shape, dt: torch.zeros([n_members, max_len] + list(shape), dtype=dt, device=self.device)  # noqa: E731
+        self.states, self.new_states = z(observation_space, torch.float32), z(observation_space, torch.float32)
+        self.agent_states, self.new_agent_states = z([2], torch.float32), z([2], torch.float32)
+        self.actions = z([2], torch.int64)
+        self.rewards = z([], torch.float32)
+        self.dones = z([], torch.bool)
+        self.head = self.fill = 0
+        self._pending = None  # (spec, step, K) of a record_pre whose record_post has not come yet
+
+    def __len__(self):
+        return self.fill
+
+    def member(self, p: int) -> _MemberRing:
+        """Member p's slab under DeviceReplayMemory's seven names, with head and fill (views: same_rings works on it)."""
+        return _MemberRing(self, p)
+
+    def record_pre(self, spec, step: int, k: int, obs, agent_state, rotation, pheromone) -> None:
+        """Before the environment step: states, agent_states and actions of k of every member's transitions."""
+        assert self._pending is None, "record_pre twice without record_post"
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().antsrl_pop_record_pre(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
+                                                         _p(rotation), _p(pheromone), _p(self.states), _p(self.agent_states),
+                                                         _p(self.actions), _lib.stream(self.device)), "pop_record_pre")
+        self._pending = (spec, step, k)
+
+    def record_post(self, obs, agent_state, reward, done) -> None:
+        """After it: rewards, new_states, new_agent_states and dones of the same transitions; then head and fill advance
+        as DeviceReplayMemory's do for k rows."""
+        assert self._pending is not None, "record_post without record_pre"
+        spec, step, k = self._pending
+        if done.dtype == torch.bool:
+            done = done.view(torch.uint8)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().antsrl_pop_record_post(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
+                                                          _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
+                                                          _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
+                                                          _lib.stream(self.device)), "pop_record_post")
+        self._pending = None
+        n = k
+        if n > self.max_len:  # as extend: only the newest max_len entries survived
+            self.head = (self.head + n - self.max_len) % self.max_len
+            n = self.max_len
+        self.fill = min(self.max_len, max(self.fill, self.head + n))
+        self.head = (self.head + n) % self.max_len
+
+
+class PopulationLinearTrainer:
+    """LinearTrainer's tensors with a leading [P], trained by antsrl_pop_lintrain_step: one launch, one workgroup per
+    member.  w1 [P, 32, F + 2], b1 [P, 32] (frozen), heads [P, 198], target_l3 [P, 99], `_adam` [P, 2, 198], grads
+    [P, 198]; member p's weights are initialised as LinearTrainer(seed=seed_p)'s.  Per member: discount and learning rate.
+    Common: Adam's betas, eps and step count, update_target_every and the target counter.  `running_loss` (float64 [P])
+    is main.py:106-109's running loss per member, kept by the training launch itself from the first training step on."""
+
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+                 update_target_every: int = 1):
+        self.g, self.device = geometry, torch.device(device)
+        P, F = geometry.P, geometry.n_features
+        self.n_members, self.n_features = P, F
+        self.seeds = [int(s) for s in seeds]
+        self.discount, self.lr = np.asarray(discount, dtype=np.float64).copy(), np.asarray(lr, dtype=np.float64).copy()
+        self.betas, self.eps, self.update_target_every = tuple(float(b) for b in betas), float(eps), int(update_target_every)
+        self.target_update_counter = self.syncs = self.step_count = 0
+        sds = [linear_init(dict(layer1=(32, F + 2), layer2=(3, 32), layer3=(3, 32)), s) for s in self.seeds]
+        stack = lambda f: torch.stack([f(sd) for sd in sds]).to(self.device).contiguous()  # noqa: E731
+        self.w1, self.b1 = stack(lambda sd: sd["layer1.weight"]), stack(lambda sd: sd["layer1.bias"])
+        self.heads = stack(lambda sd: torch.cat([sd["layer2.weight"].reshape(-1), sd["layer2.bias"],
+                                                 sd["layer3.weight"].reshape(-1), sd["layer3.bias"]]))
+        self.target_l3 = self.heads[:, 99:198].clone()
+        self._adam = torch.zeros((P, 2, 198), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((P, 198), dtype=torch.float32, device=self.device)
+        self.running_loss = torch.zeros((P,), dtype=torch.float64, device=self.device)
+        self.last_idx = None  # the [P, B] indices of the last step
+        self._lib = _lib.load()
+
+    def _spec(self):
+        """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
+        return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    def _model_views(self, p: int) -> dict:
+        d = {"explore_model.layer1.weight": self.w1[p], "explore_model.layer1.bias": self.b1[p]}
+        for k, (o, shp) in LINEAR_TRAINED.items():
+            d[k] = self.heads[p, o: o + math.prod(shp)].view(shp)
+        return d
+
+    def state_dict(self, p: int) -> dict:
+        """Member p's six tensors (copies) under CollectModel's names, in its order: what the reference loads."""
+        return {k: v.clone() for k, v in self._model_views(p).items()}
+
+    def target_state_dict(self, p: int) -> dict:
+        d = self.state_dict(p)
+        d["layer3.weight"], d["layer3.bias"] = self.target_l3[p, 0:96].view(3, 32).clone(), self.target_l3[p, 96:99].clone()
+        return d
+
+    def _targets(self, p):
+        return range(self.n_members) if p is None else (p,)
+
+    def load_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """LinearTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
+        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v for k, v in sd.items()}
+        for q in self._targets(p):
+            for k, dst in self._model_views(q).items():
+                src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+                assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+                dst.copy_(src)
+            self.target_l3[q].copy_(self.heads[q, 99:198])
+
+    def load_explore_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """LinearTrainer.load_explore_state_dict for member p (None: every member): layer1 and layer2 from a four-tensor
+        ExploreModel state_dict; layer3, its target copy and Adam's state stay."""
+        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
+        for q in self._targets(p):
+            views = self._model_views(q)
+            for k in EXPLORE_NAMES:
+                dst = views["explore_model." + k]
+                src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
+                assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+                dst.copy_(src)
+
+    def adam_state(self, p: int) -> dict:
+        def views(row):
+            return {k: self._adam[p, row, o: o + math.prod(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
+        return dict(step=self.step_count, exp_avg=views(0), exp_avg_sq=views(1))
+
+    def sync_target(self) -> None:
+        """target := model for every member: one copy of [P, 99]."""
+        self.target_l3.copy_(self.heads[:, 99:198])
+        self.syncs += 1
+
+    # ---- the step -----------------------------------------------------------------------------------------------------
+    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
+        """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
+        slab: gradient, loss and Adam in one launch.  Returns the losses, float32 [P] on the device.  spec: the agent's
+        AntsPopSpec of this step (its seeds, learning rates and discounts are this trainer's), else one is built."""
+        P = self.n_members
+        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
+        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        first = self.step_count == 0
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_pop_lintrain_step(
+                C.byref(self._spec() if spec is None else spec), _p(self.w1), _p(self.b1), _p(self.heads), _p(self.target_l3), _p(self._adam),
+                _p(ring.states), _p(ring.agent_states), _p(ring.actions), _p(ring.rewards), _p(ring.new_states),
+                _p(ring.new_agent_states), _p(ring.dones), ring.max_len, _p(idx), idx.shape[1], self.step_count, self.betas[0],
+                self.betas[1], self.eps, _p(self.grads), _p(loss), _p(self.running_loss), int(first), _lib.stream(self.device)),
+                "pop_lintrain_step")
+        self.last_idx = idx
+        return loss
+
+    def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 264,
+              min_replay: int = 1000, spec=None):
+        """The reference's train for every member at once: 0 below min_replay, else a step on `minibatch` rows per member
+        drawn on the device (one torch.randint of [P, B]), then the target counter (host side) and the sync."""
+        if len(ring) < min_replay:
+            return 0
+        idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
+        loss = self.step(ring, idx, spec)
+        if done:
+            self.target_update_counter += 1
+        if self.target_update_counter >= self.update_target_every:
+            self.sync_target()
+            self.target_update_counter = 0
+        return loss
+
+
+class PopulationAgent:
+    """P CollectAgents in lockstep (the module docstring).  members: one dict(epsilon=, discount=, learning_rate=, seed=)
+    per member (CollectAgent's defaults where a key is missing).  Common to all members: record_per_step (K rows per
+    member and step; None: all Em * n_ants), replay_size, minibatch (B <= 512), min_replay, update_target_every; `seed`
+    seeds the generator of the minibatch indices.  The acting kernel is always the standalone one."""
+
+    name = "collect_agent_population"
+    rotations = pheromones = 3
+
+    def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
+        self.members = _members(members)
+        self.n_members = len(self.members)
+        self._epsilon = np.array([m["epsilon"] for m in self.members], dtype=np.float64)
+        self.record_per_step, self.replay_size, self.minibatch, self.min_replay = record_per_step, replay_size, minibatch, min_replay
+        self.update_target_every, self.seed = update_target_every, seed
+        self.trainer = self.replay_memory = self.generator = None
+        self.step_counter = 0
+        self._lib = _lib.load()
+
+    @property
+    def epsilon(self) -> np.ndarray:
+        """float64 [P]; settable with an array or one number for every member."""
+        return self._epsilon
+
+    @epsilon.setter
+    def epsilon(self, v) -> None:
+        self._epsilon = np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n_members,)).copy()
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None) -> None:
+        """CollectAgent.setup for every member; trained_model / explore_model go to every member."""
+        env = _backend(api_or_env)
+        cfg = env.cfg
+        self.device = env.device
+        self.observation_space = tuple(env.obs.shape[-3:])
+        self.n_features = int(np.prod(self.observation_space))
+        self.g = _Geometry(self.n_members, cfg.n_envs, cfg.n_ants, cfg.env_id_base, self.n_features, env.obs.dtype)
+        if self.record_per_step is not None and not 1 <= self.record_per_step <= self.g.Mm:
+            raise ValueError("record_per_step = %d is not in [1, %d], a member's ants" % (self.record_per_step, self.g.Mm))
+        self.seeds = [m["seed"] for m in self.members]
+        self.trainer = PopulationLinearTrainer(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
+                                               [m["learning_rate"] for m in self.members],
+                                               update_target_every=self.update_target_every)
+        self.replay_memory = PopulationReplayMemory(self.n_members, self.replay_size, self.observation_space, device=self.device)
+        M = cfg.n_envs * cfg.n_ants
+        self._rot = torch.zeros((M,), dtype=torch.int8, device=self.device)
+        self._ph = torch.zeros((M,), dtype=torch.int8, device=self.device)
+        self._explored = torch.zeros((cfg.n_envs,), dtype=torch.uint8, device=self.device)
+        self.generator = torch.Generator(device=self.device)
+        self.generator.manual_seed(self.seed)
+        self.step_counter = self._action_step = 0
+        if trained_model is not None:
+            self.load_model(trained_model)
+        if explore_model is not None:
+            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
+
+    def initialize(self, api_or_env) -> None:
+        """Every pheromone activation x 10."""
+        env = _backend(api_or_env)
+        c = env.cfg
+        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
+
+    def _spec(self):
+        """This step's AntsPopSpec: the kept one while no epsilon (or learning rate, or discount) has changed."""
+        tr = self.trainer
+        return self.g.spec(self.seeds, self._epsilon, tr.lr, tr.discount)
+
+    def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
+        """-> (rotation int8, pheromone int8), device tensors shaped like the batch: every member's acting net on its own
+        rows (antsrl_pop_policy); with `training`, antsrl_pop_select then replaces the actions of the environments that
+        explore this step, each member with its own seed and epsilon."""
+        assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
+            "a population reads the dense observation rows of its whole batch"
+        assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
+        tr, step, spec = self.trainer, self.step_counter, (self._spec() if spec is None else spec)  # (rollout_step's own)
+        lead = obs.shape[:-3]
+        with torch.cuda.device(self.device):
+            st = _lib.stream(self.device)
+            _lib.check(self._lib.antsrl_pop_policy(C.byref(spec), _p(obs), _p(agent_state), _p(tr.w1), _p(tr.b1), _p(tr.heads),
+                                                   _p(tr.target_l3), _p(self._rot), _p(self._ph), st), "pop_policy")
+            if training:
+                _lib.check(self._lib.antsrl_pop_select(C.byref(spec), step, _p(self._rot), _p(self._ph), _p(self._explored), st),
+                           "pop_select")
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), self._ph.view(lead)
+
+    def train(self, done: bool, step: int = 0, spec=None):
+        """0 below min_replay, else the losses of one step of every member, float32 [P] on the device."""
+        return self.trainer.train(self.replay_memory, bool(done), generator=self.generator, minibatch=self.minibatch,
+                                  min_replay=self.min_replay, spec=self._spec() if spec is None else spec)
+
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop for every member: act, select, record_pre, env.step_update, record_post, train.
+        Returns the losses (float32 [P] on the device; 0 below min_replay or when not training).  No host
+        synchronisation."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        rm, spec = self.replay_memory, self._spec()  # one spec for the step's five entries
+        rot, ph = self.get_action(obs, ast, training, env=env, spec=spec)
+        k = self.g.Mm if self.record_per_step is None else self.record_per_step
+        rm.record_pre(spec, self._action_step, k, obs, ast, self._rot, self._ph)
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        shape = (env.cfg.n_envs, env.cfg.n_ants)
+        env.step_update(rot.view(shape), ph.view(shape))
+        rm.record_post(env.obs, env.agent_state, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step, spec) if training else 0
+
+    # ---- models -------------------------------------------------------------------------------------------------------
+    def save_model(self, p: int, file_name: str) -> None:
+        """torch.save of member p's six-tensor state_dict under the reference's names (on the CPU)."""
+        torch.save({k: v.cpu() for k, v in self.trainer.state_dict(p).items()}, file_name)
+
+    def load_model(self, file_name: str, p: Optional[int] = None) -> None:
+        """Model and target net of member p (None: of every member) from a state_dict file of the reference's."""
+        self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"), p)
+
+    def copy_member(self, src: int, dst: int, ring: bool = True) -> None:
+        """Member src's weights (the frozen layer1 included), target, Adam moments and, with `ring`, ring slab over member
+        dst's: with env.fork the exploit step of population-based training.  The hyper-parameters stay dst's own."""
+        P = self.n_members
+        assert 0 <= src < P and 0 <= dst < P, (src, dst)
+        if src == dst:
+            return
+        tr, rm = self.trainer, self.replay_memory
+        for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam) + (tuple(getattr(rm, n) for n in RING_NAMES) if ring else ()):
+            t[dst].copy_(t[src])

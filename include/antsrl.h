@@ -1370,6 +1370,113 @@ int antsrl_give_reward(AntsHandle *h, const double *reward, double threshold, fl
 /* Size in bytes of what antsrl_read_state(which) writes. */
 int antsrl_state_bytes(const AntsHandle *h, int which, size_t *bytes);
 
+/* The population of linear agents: P CollectAgents (the net of "The linear agent's training step": layer1 frozen, layer2
+ * and layer3 trained, 198 floats) trained in lockstep on ONE handle, with one launch per stage of the agent's loop
+ * whatever P is.  Member p owns environments [p Em, (p + 1) Em) of the handle's n_envs = P Em, that is ants
+ * [p Mm, (p + 1) Mm) of the batch's flat order, Mm = Em n_ants.
+ *
+ * THE DEFINING PROPERTY.  Member p is, bit for bit, the single agent's entries (antsrl_policy_mlp,
+ * antsrl_agent_select_actions, antsrl_replay_record_pre_plain / _post_plain, antsrl_lintrain_step) run on a handle of
+ * those Em environments created with env_id_base = env_id_base + p Em, with the member's own seed, epsilon, discount
+ * and learning rate: actions, explored flags, ring rows, heads, Adam's moments, gradients and loss.  Each kernel here is
+ * the single agent's stage with the member taken from the grid, and runs the same body text as the single agent's kernel
+ * (one .inc file per body, included in both: antsrl_population.hip); every draw of the draw specification is keyed on the GLOBAL environment id.
+ *
+ * Layout: member-major device tensors, a member's block laid out exactly as the single agent's:
+ *   w1 float [P][32][F + 2], b1 float [P][32]       the frozen layer1 (a member may have its own)
+ *   heads float [P][198], target_l3 float [P][99]   as antsrl_lintrain_*'s heads and target_l3
+ *   adam float [P][2][198]                          a member's m, then its v
+ *   grads float [P][198], loss float [P]
+ *   the ring: the seven arrays of antsrl_replay_record_* with a leading [P] (states float [P][max_len][F], ...); head
+ *   and fill are ONE pair of host numbers, because every member records the same K rows at every step
+ *   obs [P][Mm][F] (= the handle's [n_envs][n_ants][F]), agent_state float [P][Mm][2], rotation / pheromone int8 [P][Mm],
+ *   reward float [P][Mm], done / explored uint8 [P][Em]: the handle's own buffers
+ *
+ * The table: the per-member hyper-parameters (seed, epsilon, discount, learning_rate) are HOST values in
+ * AntsPopSpec.members; an entry hands them to its kernel by value in the kernel's arguments, so changing an epsilon
+ * between steps costs no device allocation and no copy.  At most ANTSRL_POP_MAX = 64 members (about 1.5 KB of
+ * arguments).  Common to all members: Adam's betas, eps and step count, B, K, the ring's max_len.
+ *
+ * THE ALIGNMENT RULE (antsrl_pop_policy only).  The acting kernel streams each 32-ant tile of a member's rows as 16-byte
+ * pieces from the tile's first byte; tile t of member p starts (p Mm + 32 t) F elements behind obs.  Tiles within a member
+ * are 64 F (bfloat16) or 128 F (float32) bytes apart, always multiples of 16, so what is needed is that every MEMBER's
+ * slice starts 16-byte aligned: obs 16-byte aligned and
+ *     Em * n_ants * n_features * sizeof(element)  a multiple of 16.
+ * (The single agent's rows start at obs, so it never meets the rule.)  antsrl_pop_select reads no observation, and the
+ * record entries copy rows at whatever alignment they have, as antsrl_replay_record_* do.
+ * Only the flat form of the acting kernel is offered: an n_features whose W1 and two 32-row images do not fit 160 KiB
+ * of LDS (antsrl_policy_mlp's fallback case) is ANTSRL_E_UNSUPPORTED.  Observation rows are dense: obs_pitch is 0 or
+ * n_features.
+ *
+ * Refusals, each in words and before anything is launched (ANTSRL_E_INVALID unless stated):
+ *   a NULL spec; n_members outside [1, ANTSRL_POP_MAX]; n_envs, n_ants, env_id_base outside the rules of
+ *   antsrl_agent_select; n_envs not a multiple of n_members; n_features < 1, or n_features + 2 > 1024 (UNSUPPORTED); an
+ *   obs_format that is neither ANTSRL_OBS_F32 nor ANTSRL_OBS_BF16; an obs_pitch other than 0 or n_features
+ *   (UNSUPPORTED); a member's epsilon outside [0, 1] or NaN discount;
+ *   antsrl_pop_policy: the flat form does not take n_features (UNSUPPORTED); the alignment rule (UNSUPPORTED); obs not
+ *     16-byte aligned; any NULL or misaligned pointer (pheromone included: the net has both heads);
+ *   antsrl_pop_select: NULL rotation or pheromone (explored may be NULL);
+ *   antsrl_pop_record_*: K outside [1, Em n_ants]; max_len outside [1, 2^40]; head outside [0, max_len); any NULL or
+ *     misaligned pointer (pheromone may be NULL, as for antsrl_replay_record_pre);
+ *   antsrl_pop_lintrain_step: B < 1; B > 512 (UNSUPPORTED: a member's step is one workgroup, antsrl_lintrain_step's
+ *     one-launch form); n_rows outside [1, 2^40]; any NULL or misaligned pointer (idx is required, grads and
+ *     running_loss may be NULL); Adam's arguments as antsrl_lintrain_step's, for every member's learning_rate.
+ * No entry allocates or synchronises the host; there are no atomics: equal inputs give equal bits.  One launch each.
+ *
+ *   antsrl_pop_policy     the acting net of every member on its own rows: rotation = argmax(layer2(h)) - 1 with the
+ *                         member's live layer2 (heads [p][0 .. 99)), pheromone = argmax(layer3(h)) with its TARGET layer3
+ *                         (target_l3 [p]): the net CollectAgent.get_action acts with.  Grid (blocks, P): a workgroup
+ *                         stages one member's W1 and loops over that member's tiles only.
+ *   antsrl_pop_select     antsrl_agent_select_actions per member, n_rot = n_ph = 3: environment e of member p explores
+ *                         iff u01(draw(seed_p, ANTSRL_DRAW_EXPLORE, env_id_base + p Em + e, step, 0)) < epsilon_p.
+ *   antsrl_pop_record_*   antsrl_replay_record_*_plain per member (agent_dim 2, n_rot 3): K of the member's Mm
+ *                         transitions, sampled with draw(seed_p, ANTSRL_DRAW_SAMPLE, env_id_base + p Em, step, j), into
+ *                         rows (head + j) mod max_len of the member's slab.  Grid (ceil(K / 4), P).
+ *   antsrl_pop_lintrain_step   antsrl_lintrain_step per member, one workgroup each, grid (1, P): idx int64 [P][B], row p
+ *                         indexing member p's slab (clamped to [0, n_rows); n_rows is also the slab's stride in rows:
+ *                         pass max_len); discount_p; Adam with lr_p at the common step count.  running_loss (double [P],
+ *                         or NULL): the same launch then also keeps main.py:106-109's recurrence per member in float64,
+ *                         running_loss[p] = loss[p] when first_loss != 0 (the host knows its first training step), else
+ *                         0.99 * running_loss[p] + 0.01 * loss[p], each product rounded before the add
+ *                         (antsrl_monitor_step's arithmetic).
+ * The target sync is one device copy of [P][99] (heads [.][99 .. 198) into target_l3), the caller's. */
+#define ANTSRL_POP_MAX 64
+
+typedef struct AntsPopMember {
+    uint64_t seed;
+    double epsilon;
+    double learning_rate;
+    float discount;
+    int32_t reserved; /* 0 */
+} AntsPopMember;
+
+typedef struct AntsPopSpec {
+    int32_t n_members;                  /* P */
+    int32_t n_envs, n_ants, env_id_base; /* the whole handle's: Em = n_envs / n_members */
+    int32_t n_features;
+    int32_t obs_format;                 /* ANTSRL_OBS_F32 / ANTSRL_OBS_BF16 */
+    int32_t obs_pitch;                  /* 0 or n_features */
+    int32_t reserved;                   /* 0 */
+    AntsPopMember members[ANTSRL_POP_MAX];
+} AntsPopSpec;
+
+int antsrl_pop_policy(const AntsPopSpec *s, const void *obs, const float *agent_state, const float *w1, const float *b1,
+                      const float *heads, const float *target_l3, int8_t *rotation, int8_t *pheromone, void *stream);
+int antsrl_pop_select(const AntsPopSpec *s, uint64_t step, int8_t *rotation, int8_t *pheromone, uint8_t *explored,
+                      void *stream);
+int antsrl_pop_record_pre(const AntsPopSpec *s, uint64_t step, int64_t K, int64_t head, int64_t max_len, const void *obs,
+                          const float *agent_state, const int8_t *rotation, const int8_t *pheromone, float *states,
+                          float *agent_states, int64_t *actions, void *stream);
+int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64_t K, int64_t head, int64_t max_len, const void *obs,
+                           const float *agent_state, const float *reward, const uint8_t *done, float *rewards,
+                           float *new_states, float *new_agent_states, uint8_t *dones, void *stream);
+int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, const float *b1, float *heads, const float *target_l3,
+                             float *adam, const float *states, const float *agent_states, const int64_t *actions,
+                             const float *rewards, const float *new_states, const float *new_agent_states,
+                             const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, int64_t step, double beta1,
+                             double beta2, double eps, float *grads, float *loss, double *running_loss, int first_loss,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
