@@ -23,8 +23,9 @@ overwritten ten times per step), `replay_size`, `minibatch`, `min_replay`, `seed
 `skip_explored` (off by default: skip the net for tiles whose ants all explore this step; results are unchanged).
 Exploration is drawn once per environment and step (an environment is one reference colony).
 
-`_DeviceAgent` holds what the agents share (the hyper-parameters, the front of setup, the reference's surface
-around get_action, and the fused loop); `_InLoopAgent` adds what the two memory-less agents share on top of it: their
+`_LoopAgent` holds the fused loop and `initialize`, which a population of agents (population.py) runs as well;
+`_DeviceAgent` adds what the single-model agents share (the hyper-parameters, the front of setup, the reference's surface
+around get_action, the training state); `_InLoopAgent` adds what the two memory-less agents share on top of it: their
 acting step and the bookkeeping of the in-loop policy's handle.  An agent writes its trainer, its get_action and what
 it keeps between steps.  `ReworkAgent` (CollectAgentRework, the agent main.py imports first) sits on `_DeviceAgent`
 directly: its net is ReworkPolicy's, and its acting step under exploration is one launch.
@@ -39,7 +40,7 @@ import torch
 from . import _lib
 from ._lib import ptr as _p
 from . import config as cm
-from .replay import DeviceReplayMemory
+from .replay import RING_NAMES, DeviceReplayMemory
 from .train import ExploreTrainer, JointTrainer, LinearTrainer, MemoryTrainer, ReworkTrainer
 
 
@@ -50,11 +51,54 @@ def _backend(api_or_env):
     return b
 
 
-class _DeviceAgent:
-    """What every device agent is around its get_action: the hyper-parameters, the front of setup, the reference's
-    surface and the fused loop.  A subclass builds its trainer in setup, writes get_action (which returns (rotation,
-    pheromone or None) and, for an agent with a memory, the new memory behind them) and overrides `_state_memory` when it
-    has a memory to store and `_stepped` when it watches the environment's steps."""
+class _LoopAgent:
+    """The fused loop and `initialize`, for whatever acts on a BatchedAntsEnv and records into a ring: one model
+    (_DeviceAgent) or a population's P (population.PopulationAgent).  A subclass has `replay_memory`, `_action_step`,
+    get_action(obs, agent_state, training, env=) -> (rotation, pheromone or None[, the new memory]), train(done, step)
+    and `_record_kw`, what its ring's record_pre takes by name."""
+
+    def initialize(self, api_or_env) -> None:
+        """Every pheromone activation x 10."""
+        env = _backend(api_or_env)
+        c = env.cfg
+        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
+
+    def _state_memory(self):
+        """The memory that goes into agent_states: none."""
+        return None
+
+    def _stepped(self, env) -> None:
+        """`env` has just been stepped with this step's actions."""
+
+    def rollout_step(self, env, training: bool = True):
+        """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
+        observe() or a step): act, select, record_pre, env.step_update (without a pheromone action when get_action gives
+        none), record_post, train.  Returns the loss (0 while the replay memory is below min_replay or when not training,
+        else a device tensor).  No host synchronisation: `done` for the target counter is the host's own step count
+        against max_time."""
+        env = _backend(env)
+        obs, ast = env.obs, env.agent_state
+        assert obs.is_contiguous(), "%s reads dense observation rows (obs_row_stride=None)" % type(self).__name__
+        rot, ph, mem = (*self.get_action(obs, ast, training, env=env), None)[:3]
+        rm = self.replay_memory
+        rm.record_pre(obs, ast, self._state_memory(), rot.view(-1), None if ph is None else ph.view(-1), **self._record_kw())
+        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
+        shape = (env.cfg.n_envs, env.cfg.n_ants)
+        env.step_update(rot.view(shape), None if ph is None else ph.view(shape))
+        self._stepped(env)
+        rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
+        return self.train(done, self._action_step) if training else 0
+
+    def run(self, env, steps: int, training: bool = True) -> list:
+        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
+        return [self.rollout_step(env, training) for _ in range(steps)]
+
+
+class _DeviceAgent(_LoopAgent):
+    """What every single-model device agent is around its get_action: the hyper-parameters, the front of setup and the
+    reference's surface, on _LoopAgent's fused loop.  A subclass builds its trainer in setup, writes get_action (which
+    returns (rotation, pheromone or None) and, for an agent with a memory, the new memory behind them) and overrides
+    `_state_memory` when it has a memory to store and `_stepped` when it watches the environment's steps."""
 
     def __init__(self, name: str, epsilon: float, discount: float, rotations: int, pheromones: int, learning_rate: float,
                  record_per_step: Optional[int], replay_size: int, minibatch: int, min_replay: int,
@@ -103,12 +147,6 @@ class _DeviceAgent:
                                                              _lib.stream(self.device)), "agent_select_actions")
 
     # ---- the reference's surface ----------------------------------------------------------------------------------
-    def initialize(self, api_or_env) -> None:
-        """Every pheromone activation x 10."""
-        env = _backend(api_or_env)
-        c = env.cfg
-        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
-
     @property
     def policy(self):
         return self.trainer.policy
@@ -120,13 +158,6 @@ class _DeviceAgent:
     def _obs(self, a):
         """An observation as the kernels take it: a bfloat16 tensor as it is, anything else as float32 on the device."""
         return a if (torch.is_tensor(a) and a.dtype == torch.bfloat16) else self._dev(a, torch.float32)
-
-    def _state_memory(self):
-        """The memory that goes into agent_states: none."""
-        return None
-
-    def _stepped(self, env) -> None:
-        """`env` has just been stepped with this step's actions."""
 
     def _record_kw(self):
         return dict(n_envs=self.n_envs, n_ants=self.n_ants_per_env, k=self.record_per_step, seed=self.seed,
@@ -167,7 +198,6 @@ class _DeviceAgent:
     #: moments and the operand packs as well), Adam's moments of the flat trainers, LinearTrainer's frozen layer1
     _TRAINER_BUFFERS = ("_model", "_target", "model", "target", "heads", "target_l3", "_adam", "policy.w1", "policy.b1")
     _TRAINER_COUNTERS = ("step_count", "target_update_counter", "syncs")
-    _REPLAY_TENSORS = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 
     def _trainer_buffers(self) -> dict:
         out = {}
@@ -189,7 +219,7 @@ class _DeviceAgent:
         assert rm._pending is None, "training_state between record_pre and record_post"
         d = dict(agent=type(self).__name__, trainer={k: v.clone() for k, v in self._trainer_buffers().items()},
                  counters={k: int(getattr(self.trainer, k)) for k in self._TRAINER_COUNTERS},
-                 replay={k: getattr(rm, k).clone() for k in self._REPLAY_TENSORS}, head=int(rm.head), fill=int(rm.fill),
+                 replay={k: getattr(rm, k).clone() for k in RING_NAMES}, head=int(rm.head), fill=int(rm.fill),
                  generator=self.generator.get_state().clone(), step_counter=int(self.step_counter),
                  action_step=int(self._action_step), epsilon=float(self.epsilon), explored=self._explored.clone())
         if hasattr(self, "_mem"):  # MemoryAgent: both halves of the carried memory and which one is previous_memory
@@ -206,7 +236,7 @@ class _DeviceAgent:
         tr, rm = self.trainer, self.replay_memory
         mine = self._trainer_buffers()
         pairs = [(mine.get(k), v, "trainer." + k) for k, v in d["trainer"].items()]
-        pairs += [(getattr(rm, k), d["replay"][k], "replay." + k) for k in self._REPLAY_TENSORS]
+        pairs += [(getattr(rm, k), d["replay"][k], "replay." + k) for k in RING_NAMES]
         pairs.append((self._explored, d["explored"], "explored"))
         if hasattr(self, "_mem"):
             pairs += [(m, v, "memory") for m, v in zip(self._mem, d["memory"])]
@@ -241,30 +271,6 @@ class _DeviceAgent:
 
     def _acting_weights_loaded(self) -> None:
         """load_training_state has replaced the acting weights."""
-
-    # ---- the fused loop -------------------------------------------------------------------------------------------
-    def rollout_step(self, env, training: bool = True):
-        """One step of main.py's loop (:95-131) on `env` (a BatchedAntsEnv holding a current observation: after
-        observe() or a step): act, select, record_pre, env.step_update (without a pheromone action when get_action gives
-        none), record_post, train.  Returns the loss (0 while the replay memory is below min_replay or when not training,
-        else a 0-d device tensor).  No host synchronisation: `done` for the target counter is the host's own step count
-        against max_time."""
-        env = _backend(env)
-        obs, ast = env.obs, env.agent_state
-        assert obs.is_contiguous(), "%s reads dense observation rows (obs_row_stride=None)" % type(self.policy).__name__
-        rot, ph, mem = (*self.get_action(obs, ast, training, env=env), None)[:3]
-        rm = self.replay_memory
-        rm.record_pre(obs, ast, self._state_memory(), rot.view(-1), None if ph is None else ph.view(-1), **self._record_kw())
-        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
-        shape = (env.cfg.n_envs, env.cfg.n_ants)
-        env.step_update(rot.view(shape), None if ph is None else ph.view(shape))
-        self._stepped(env)
-        rm.record_post(env.obs, env.agent_state, mem, env.reward.view(-1), env.done)
-        return self.train(done, self._action_step) if training else 0
-
-    def run(self, env, steps: int, training: bool = True) -> list:
-        """`steps` rollout_steps; the losses (device tensors, or 0) in order."""
-        return [self.rollout_step(env, training) for _ in range(steps)]
 
 
 class MemoryAgent(_DeviceAgent):

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libantsrl_hip.so")
 SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl_sweep.hip", "antsrl_state.hip",
            "antsrl_capi.hip", "antsrl_policy.hip", "antsrl_mem.hip",
            "antsrl_memnet.hip", "antsrl_memnet_f32.hip", "antsrl_memtrain.hip", "antsrl_memagent.hip",
-           "antsrl_memapi.hip", "antsrl_lintrain.hip", "antsrl_exptrain.hip", "antsrl_jointtrain.hip",
+           "antsrl_memapi.hip", "antsrl_loopapi.hip", "antsrl_lintrain.hip", "antsrl_exptrain.hip", "antsrl_jointtrain.hip",
            "antsrl_linapi.hip",
            "antsrl_rework.hip", "antsrl_reworktrain.hip", "antsrl_reworkapi.hip", "antsrl_monitor.hip", "antsrl_recorder.hip",
            "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip",
@@ -27,7 +27,8 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
-                                           "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_draw.h",
+                                           "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_loopapi.h",
+                                           "antsrl_draw.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
                                            "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",
                                            "antsrl_cellread.h", "antsrl_recorder.h", "antsrl_render.h", "antsrl_stats.h",
@@ -49,7 +50,7 @@ def hipcc() -> str:
 
 
 #: host-only translation units (no kernel in them): a change there moves no byte on the device
-HOST_ONLY_SOURCES = ("antsrl_capi.hip", "antsrl_mem.hip", "antsrl_memapi.hip", "antsrl_linapi.hip",
+HOST_ONLY_SOURCES = ("antsrl_capi.hip", "antsrl_mem.hip", "antsrl_memapi.hip", "antsrl_loopapi.hip", "antsrl_linapi.hip",
                      "antsrl_reworkapi.hip", "antsrl_logapi.hip", "antsrl_popapi.hip")
 
 

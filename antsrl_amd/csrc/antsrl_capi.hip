@@ -1,6 +1,7 @@
 // antsrl_capi.hip — the environment's part of the C-ABI of libantsrl_hip.so (include/antsrl.h), the library's error
-// reporting (antsrl_fail.h) and the handle's helpers (antsrl_handle.h).  The memory agent's entries are in
-// antsrl_memapi.hip; the episode recorder's, the colony statistics' and the episode renderer's in antsrl_logapi.hip.
+// reporting (antsrl_fail.h) and the handle's helpers (antsrl_handle.h).  The memory agent's net has its entries in
+// antsrl_memapi.hip, the agents' loop in antsrl_loopapi.hip; the episode recorder's, the colony statistics' and the
+// episode renderer's are in antsrl_logapi.hip.
 //
 // Host-side only: validates the configuration, carves the caller's device workspace into the
 // state arrays of antsrl_device.h, and enqueues the kernels of antsrl_act / _update / _sweep / _state.hip on the

@@ -58,6 +58,16 @@ static inline int antsrl_dqn_minibatch(const char *who, const float *states, con
     return ANTSRL_OK;
 }
 
+// The 32-wide nets' rules, for the single agents' entries and the population's (antsrl_linapi.hip): 1 <= n_features,
+// n_features + 2 <= 1024; and antsrl_dqn_minibatch's part of *q followed by F, ksteps, ntiles, the two scales and the
+// partials (= workspace, NULL where a step is one workgroup per net), for n_features and B the entry has checked
+ANTSRL_INTERNAL int lt_features(const char *who, int32_t n_features);
+ANTSRL_INTERNAL int dqn_batch(const char *who, int32_t n_features, const float *states, const float *agent_states,
+                              const int64_t *actions, const float *rewards, const float *new_states,
+                              const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx,
+                              int64_t B, float discount, float *grads, bool grads_required, float *loss, void *workspace,
+                              DqnBatch *q);
+
 // the replay row of minibatch row b (b < B), never outside the replay arrays
 template <class Q>
 __device__ __forceinline__ long long dqn_row(const Q &q, const int b)

@@ -22,7 +22,7 @@
 
 #define LT_MAX_B (1 << 24)
 
-static int lt_features(const char *who, int32_t n_features)
+int lt_features(const char *who, int32_t n_features)
 {
     if (n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, n_features);
     if (n_features + 2 > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_features + 2 = %d > 1024", who, n_features + 2);
@@ -43,11 +43,12 @@ static int et_B(const char *who, int64_t B)
 }
 
 // the minibatch of a gradient stage or a fused step, for n_features and B its entry has checked: antsrl_dqn_minibatch's
-// part, then what the 32-wide nets add; workspace (checked by the entry's own rule) becomes the partials
-static int dqn_batch(const char *who, int32_t n_features, const float *states, const float *agent_states,
-                     const int64_t *actions, const float *rewards, const float *new_states, const float *new_agent_states,
-                     const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads,
-                     bool grads_required, float *loss, void *workspace, DqnBatch *q)
+// part, then what the 32-wide nets add; workspace (checked by the entry's own rule; NULL for a step of one workgroup
+// per net, the population's) becomes the partials.  Declared in antsrl_dqn.h.
+int dqn_batch(const char *who, int32_t n_features, const float *states, const float *agent_states, const int64_t *actions,
+              const float *rewards, const float *new_states, const float *new_agent_states, const uint8_t *dones,
+              int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, bool grads_required, float *loss,
+              void *workspace, DqnBatch *q)
 {
     const int rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones,
                                         n_rows, idx, B, discount, grads, grads_required, loss, q);

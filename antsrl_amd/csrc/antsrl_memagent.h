@@ -1,5 +1,5 @@
-// antsrl_memagent.h — arguments and launchers of the memory agent loop's kernels (antsrl_memagent.hip), shared with
-// their C-ABI entries (antsrl_memapi.hip).
+// antsrl_memagent.h — arguments and launchers of the agents' loop's kernels (antsrl_memagent.hip), shared with their
+// C-ABI entries (antsrl_loopapi.hip; the entries' argument rules: antsrl_loopapi.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +39,3 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_agent_select(const SelArgs &a, bool vec
 // the plan reads seed, step, epsilon, env_base, n_ants and M of `a` (select's own arguments: one env_explores for both)
 ANTSRL_INTERNAL hipError_t antsrl_launch_agent_plan(const SelArgs &a, int32_t *tiles, int32_t *n_live, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_replay_record(const RecArgs &a, bool obs_bf16, bool post, hipStream_t st);
-
-// host: n_envs, n_ants >= 1, n_envs * n_ants < 2^31, env_id_base >= 0, env_id_base + n_envs < 2^31 (antsrl_memapi.hip)
-ANTSRL_INTERNAL int antsrl_check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants);

@@ -1,33 +1,18 @@
-// antsrl_memapi.hip — the memory agent's part of the C-ABI of libantsrl_hip.so (include/antsrl.h): the net's inference
-// (antsrl_memnet_*, antsrl_policy_memory*), its training step (antsrl_memtrain_*) and the loop around them
-// (antsrl_agent_select, antsrl_agent_plan, antsrl_replay_record_*), with the loop's memory-less forms for the linear agent
-// (antsrl_agent_select_actions, antsrl_replay_record_*_plain: the same kernels without a memory operand).
+// antsrl_memapi.hip — the memory agent's net in the C-ABI of libantsrl_hip.so (include/antsrl.h): its inference
+// (antsrl_memnet_*, antsrl_policy_memory*) and its training step (antsrl_memtrain_*).  The loop around them is
+// antsrl_loopapi.hip's.
 //
-// Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip, antsrl_memtrain.hip
-// and antsrl_memagent.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
+// Host-side only: validates the arguments and enqueues the kernels of antsrl_memnet.hip / _memnet_f32.hip and
+// antsrl_memtrain.hip on the caller's stream.  No handle, no allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "antsrl_adam.h"
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
-#include "antsrl_memagent.h"
+#include "antsrl_loopapi.h" // the shape limits, the obs_format rule
 #include "antsrl_memnet.h"
 #include "antsrl_memtrain.h"
-
-// ---- the shape limits of the net's kernels, shared by the net's, the trainer's and the loop's entries
-static int check_max32(const char *who, const char *name, int32_t v)
-{
-    if (v > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: %s %d > 32", who, name, v);
-    return ANTSRL_OK;
-}
-
-static int check_D(const char *who, int32_t n_features, int32_t agent_dim, int32_t mem_size)
-{
-    const long long D = (long long)n_features + agent_dim + mem_size;
-    if (D > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: D = n_features + agent_dim + mem_size = %lld > 1024", who, D);
-    return ANTSRL_OK;
-}
 
 // the 26 tensors of CollectModelMemory.state_dict(): none NULL
 static int check_params(const char *who, const float *const *params)
@@ -44,16 +29,16 @@ static int memnet_check(const AntsMemNetShape *s, MemNetDims *d, const char *who
     if (s->n_features < 1 || s->agent_dim < 1 || s->mem_size < 1 || s->h1 < 1 || s->h2 < 1 || s->h3 < 1 || s->n_rot < 1 ||
         s->n_ph < 1)
         return fail(ANTSRL_E_INVALID, "%s: n_features, agent_dim, mem_size, h1, h2, h3, n_rot, n_ph must be >= 1", who);
-    int rc = check_D(who, s->n_features, s->agent_dim, s->mem_size);
-    if (rc == ANTSRL_OK) rc = check_max32(who, "agent_dim", s->agent_dim);
-    if (rc == ANTSRL_OK) rc = check_max32(who, "mem_size", s->mem_size);
+    int rc = antsrl_check_D(who, s->n_features, s->agent_dim, s->mem_size);
+    if (rc == ANTSRL_OK) rc = antsrl_check_max32(who, "agent_dim", s->agent_dim);
+    if (rc == ANTSRL_OK) rc = antsrl_check_max32(who, "mem_size", s->mem_size);
     if (rc != ANTSRL_OK) return rc;
     if (s->h1 % 32 || s->h2 % 32 || s->h3 % 32 || s->h1 > 256 || s->h2 > 256 || s->h3 > 256)
         return fail(ANTSRL_E_UNSUPPORTED, "%s: h1, h2, h3 (%d, %d, %d) must be multiples of 32 and <= 256", who, s->h1, s->h2,
                     s->h3);
-    // (n_rot, n_ph <= 32 has its own, combined text here and check_max32's in the loop's entries: both are tested)
+    // (n_rot, n_ph <= 32 has its own, combined text here and antsrl_check_max32's in the loop's entries: both are tested)
     if (s->n_rot > 32 || s->n_ph > 32) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_rot, n_ph (%d, %d) must be <= 32", who, s->n_rot, s->n_ph);
-    const int D = s->n_features + s->agent_dim + s->mem_size; // <= 1024 (check_D)
+    const int D = s->n_features + s->agent_dim + s->mem_size; // <= 1024 (antsrl_check_D)
     *d = MemNetDims{s->n_features, s->agent_dim, s->mem_size, D, s->h1, s->h2, s->h3, s->n_rot, s->n_ph};
     return ANTSRL_OK;
 }
@@ -105,7 +90,7 @@ static int policy_memory(const AntsMemNetShape *s, int precision, const void *pa
                          const int32_t *tiles = nullptr, const int32_t *n_live = nullptr)
 {
     MemNetDims d;
-    const int rc = memnet_check(s, &d, who);
+    int rc = memnet_check(s, &d, who);
     if (rc != ANTSRL_OK) return rc;
     if (!packed || !obs || !agent_state || !mem_in || !mem_out || !rotation)
         return fail(ANTSRL_E_INVALID, "%s: packed, obs, agent_state, mem_in, mem_out, rotation are required", who);
@@ -113,8 +98,7 @@ static int policy_memory(const AntsMemNetShape *s, int precision, const void *pa
     if (listed && (((uintptr_t)tiles | (uintptr_t)n_live) & 3))
         return fail(ANTSRL_E_INVALID, "%s: tiles and n_live must be 4-byte aligned", who);
     if ((uintptr_t)packed & 255) return fail(ANTSRL_E_INVALID, "%s: packed must be 256-byte aligned", who);
-    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
+    if ((rc = antsrl_check_obs_format(who, obs_format)) != ANTSRL_OK) return rc;
     if (n_ants < 1 || n_ants > 0x7fffffff) return fail(ANTSRL_E_INVALID, "%s: n_ants must be in [1, 2^31)", who);
     if (listed)
         return enqueued((precision == ANTSRL_MEMNET_FP32 ? antsrl_launch_memnet_f32_tiles : antsrl_launch_memnet_tiles)(
@@ -320,227 +304,4 @@ extern "C" int antsrl_memtrain_apply(const AntsMemNetShape *s, void *state, cons
     hipError_t e = antsrl_launch_memtrain_apply(d, (unsigned char *)state, grads, o.step_size, o.bc2_sqrt, o.w1m, o.beta2,
                                                 o.w2m, o.eps, (hipStream_t)stream);
     return enqueued(e, "memtrain_apply");
-}
-
-// ---- the loop (antsrl_memagent.hip)
-// (also the rule of antsrl_policy_rework_select, antsrl_reworkapi.hip: declared in antsrl_memagent.h)
-int antsrl_check_batch(const char *who, int32_t env_id_base, int32_t n_envs, int32_t n_ants)
-{
-    if (n_envs < 1 || n_ants < 1) return fail(ANTSRL_E_INVALID, "%s: n_envs and n_ants must be >= 1 (%d, %d)", who, n_envs, n_ants);
-    if ((long long)n_envs * n_ants > 0x7fffffffLL)
-        return fail(ANTSRL_E_INVALID, "%s: n_envs * n_ants = %lld must stay below 2^31", who, (long long)n_envs * n_ants);
-    if (env_id_base < 0 || (long long)env_id_base + n_envs > 0x7fffffffLL)
-        return fail(ANTSRL_E_INVALID, "%s: env_id_base must be >= 0 and env_id_base + n_envs must fit 31 bits", who);
-    return ANTSRL_OK;
-}
-
-static int check_width(const char *who, const char *name, int32_t v)
-{
-    if (v < 1) return fail(ANTSRL_E_INVALID, "%s: %s must be >= 1 (%d)", who, name, v);
-    return check_max32(who, name, v);
-}
-
-#define MISALIGNED(p, n) (((uintptr_t)(p) & ((n) - 1)) != 0)
-
-extern "C" int antsrl_agent_select(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
-                                   double epsilon, int32_t n_rot, int32_t n_ph, int32_t mem_size, int8_t *rotation,
-                                   int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored, void *stream)
-{
-    const char *who = "agent_select";
-    int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
-    if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
-    if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
-    if (rc == ANTSRL_OK) rc = check_width(who, "mem_size", mem_size);
-    if (rc != ANTSRL_OK) return rc;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
-    if (!rotation) return fail(ANTSRL_E_INVALID, "%s: rotation is required", who);
-    if (!pheromone) return fail(ANTSRL_E_INVALID, "%s: pheromone is required", who);
-    if (!mem_old) return fail(ANTSRL_E_INVALID, "%s: mem_old is required", who);
-    if (!mem_next) return fail(ANTSRL_E_INVALID, "%s: mem_next is required", who);
-    if (MISALIGNED(mem_old, 4) || MISALIGNED(mem_next, 4)) return fail(ANTSRL_E_INVALID, "%s: mem_old and mem_next must be 4-byte aligned", who);
-    if (mem_old != mem_next) { // the same buffer, or two that do not touch
-        const uintptr_t o = (uintptr_t)mem_old, n = (uintptr_t)mem_next;
-        const uintptr_t bytes = (uintptr_t)n_envs * (uintptr_t)n_ants * (uintptr_t)mem_size * 4;
-        if (o < n + bytes && n < o + bytes) return fail(ANTSRL_E_INVALID, "%s: mem_old and mem_next overlap without being equal", who);
-    }
-    SelArgs a;
-    a.seed = seed; a.step = step; a.epsilon = epsilon;
-    a.rot = rotation; a.ph = pheromone; a.mem_old = mem_old; a.mem_next = mem_next; a.explored = explored;
-    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants; a.n_rot = (uint32_t)n_rot; a.n_ph = (uint32_t)n_ph;
-    a.M = (uint32_t)((long long)n_envs * n_ants);
-    const uint64_t env_floats = (uint64_t)n_ants * (uint64_t)mem_size;
-    const bool vec = env_floats % 4 == 0 && !MISALIGNED(mem_old, 16) && !MISALIGNED(mem_next, 16);
-    const uint64_t env_elems = vec ? env_floats / 4 : env_floats;
-    if (env_elems > 0xffffffffULL) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_ants * mem_size = %llu is too large", who, (unsigned long long)env_floats);
-    a.env_elems = (uint32_t)env_elems;
-    a.mem_elems = env_elems * (uint64_t)n_envs;
-    return enqueued(antsrl_launch_agent_select(a, vec, (hipStream_t)stream), who);
-}
-
-extern "C" int antsrl_agent_plan(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
-                                 double epsilon, int32_t *tiles, int32_t *n_live, void *stream)
-{
-    const char *who = "agent_plan";
-    const int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
-    if (rc != ANTSRL_OK) return rc;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
-    REQUIRE(tiles, 4);
-    REQUIRE(n_live, 4);
-    SelArgs a = {};
-    a.seed = seed; a.step = step; a.epsilon = epsilon;
-    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants;
-    a.M = (uint32_t)((long long)n_envs * n_ants);
-    return enqueued(antsrl_launch_agent_plan(a, tiles, n_live, (hipStream_t)stream), who);
-}
-
-// plain: the memory-less entries, whose spec has mem_size == 0 (the entries with a memory go on refusing that)
-static int check_spec(const char *who, const AntsRecordSpec *r, bool plain = false)
-{
-    if (!r) return fail(ANTSRL_E_INVALID, "%s: NULL spec", who);
-    int rc = antsrl_check_batch(who, r->env_id_base, r->n_envs, r->n_ants);
-    if (rc != ANTSRL_OK) return rc;
-    if (r->n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, r->n_features);
-    if ((rc = check_width(who, "agent_dim", r->agent_dim)) != ANTSRL_OK) return rc;
-    if (plain && r->mem_size != 0) return fail(ANTSRL_E_INVALID, "%s: mem_size must be 0 (%d): this entry records no memory", who, r->mem_size);
-    if (!plain && (rc = check_width(who, "mem_size", r->mem_size)) != ANTSRL_OK) return rc;
-    if ((rc = check_width(who, "n_rot", r->n_rot)) != ANTSRL_OK) return rc;
-    if ((rc = check_D(who, r->n_features, r->agent_dim, r->mem_size)) != ANTSRL_OK) return rc;
-    if (r->obs_format != ANTSRL_OBS_F32 && r->obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16 (%d)", who, r->obs_format);
-    if (r->obs_pitch != 0 && (r->obs_pitch < r->n_features || r->obs_pitch >= (1 << 24)))
-        return fail(ANTSRL_E_INVALID, "%s: obs_pitch %d: 0 (dense) or at least the row's %d elements (and below 2^24)", who,
-                    r->obs_pitch, r->n_features);
-    const long long M = (long long)r->n_envs * r->n_ants;
-    if (r->K < 1 || r->K > M) return fail(ANTSRL_E_INVALID, "%s: K must be in [1, n_envs * n_ants = %lld] (%lld)", who, M, (long long)r->K);
-    if (r->max_len < 1) return fail(ANTSRL_E_INVALID, "%s: max_len must be >= 1 (%lld)", who, (long long)r->max_len);
-    if (r->max_len > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: max_len must be <= 2^40", who);
-    if (r->head < 0 || r->head >= r->max_len)
-        return fail(ANTSRL_E_INVALID, "%s: head must be in [0, max_len = %lld) (%lld)", who, (long long)r->max_len, (long long)r->head);
-    return ANTSRL_OK;
-}
-
-static void fill_rec(const AntsRecordSpec *r, RecArgs *a)
-{
-    a->seed = r->seed; a->step = r->step; a->env_base = (uint64_t)r->env_id_base;
-    a->M = (long long)r->n_envs * r->n_ants; a->K = r->K;
-    a->n_write = r->K < r->max_len ? r->K : r->max_len; // only the newest max_len entries can survive
-    a->j0 = r->K - a->n_write;
-    a->row0 = (r->head + a->j0) % r->max_len;
-    a->max_len = r->max_len;
-    a->pitch = r->obs_pitch ? r->obs_pitch : r->n_features;
-    a->n_ants = r->n_ants; a->F = r->n_features; a->A = r->agent_dim; a->mem = r->mem_size; a->half_rot = r->n_rot / 2;
-}
-
-static int launch_rec(const char *who, const AntsRecordSpec *r, const RecArgs &a, bool post, void *stream)
-{
-    return enqueued(antsrl_launch_replay_record(a, r->obs_format == ANTSRL_OBS_BF16, post, (hipStream_t)stream), who);
-}
-
-extern "C" int antsrl_replay_record_pre(const AntsRecordSpec *r, const void *obs, const float *agent_state,
-                                        const float *memory, const int8_t *rotation, const int8_t *pheromone, float *states,
-                                        float *agent_states, int64_t *actions, void *stream)
-{
-    const char *who = "replay_record_pre";
-    const int rc = check_spec(who, r);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(memory, 4);
-    REQUIRE(rotation, 1);
-    REQUIRE(states, 4);
-    REQUIRE(agent_states, 4);
-    REQUIRE(actions, 8);
-    RecArgs a = {};
-    fill_rec(r, &a);
-    a.obs = obs; a.agent_state = agent_state; a.memory = memory; a.rot = rotation; a.ph = pheromone;
-    a.states = states; a.agent_states = agent_states; a.actions = actions;
-    return launch_rec(who, r, a, false, stream);
-}
-
-extern "C" int antsrl_replay_record_post(const AntsRecordSpec *r, const void *obs, const float *agent_state,
-                                         const float *memory, const float *reward, const uint8_t *done, float *rewards,
-                                         float *new_states, float *new_agent_states, uint8_t *dones, void *stream)
-{
-    const char *who = "replay_record_post";
-    const int rc = check_spec(who, r);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(memory, 4);
-    REQUIRE(reward, 4);
-    REQUIRE(done, 1);
-    REQUIRE(rewards, 4);
-    REQUIRE(new_states, 4);
-    REQUIRE(new_agent_states, 4);
-    REQUIRE(dones, 1);
-    RecArgs a = {};
-    fill_rec(r, &a);
-    a.obs = obs; a.agent_state = agent_state; a.memory = memory; a.reward = reward; a.done = done;
-    a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
-    return launch_rec(who, r, a, true, stream);
-}
-
-// ---- the loop without a memory (the linear agent: agents/collect_agent.py:150-177).  The kernels are the ones above: the
-// select kernel copies no memory when mem_old == mem_next (both NULL here), the record kernel's small fields are
-// agent_dim + mem_size wide (mem_size 0 here), so neither ever touches a memory pointer.
-extern "C" int antsrl_agent_select_actions(uint64_t seed, uint64_t step, int32_t env_id_base, int32_t n_envs, int32_t n_ants,
-                                           double epsilon, int32_t n_rot, int32_t n_ph, int8_t *rotation, int8_t *pheromone,
-                                           uint8_t *explored, void *stream)
-{
-    const char *who = "agent_select_actions";
-    int rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants);
-    if (rc == ANTSRL_OK) rc = check_width(who, "n_rot", n_rot);
-    if (rc == ANTSRL_OK) rc = check_width(who, "n_ph", n_ph);
-    if (rc != ANTSRL_OK) return rc;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
-    if (!rotation) return fail(ANTSRL_E_INVALID, "%s: rotation is required", who);
-    if (!pheromone) return fail(ANTSRL_E_INVALID, "%s: pheromone is required", who);
-    SelArgs a = {};
-    a.seed = seed; a.step = step; a.epsilon = epsilon;
-    a.rot = rotation; a.ph = pheromone; a.explored = explored; // mem_old == mem_next == NULL: no memory part
-    a.env_base = (uint32_t)env_id_base; a.n_ants = (uint32_t)n_ants; a.n_rot = (uint32_t)n_rot; a.n_ph = (uint32_t)n_ph;
-    a.M = (uint32_t)((long long)n_envs * n_ants);
-    return enqueued(antsrl_launch_agent_select(a, false, (hipStream_t)stream), who);
-}
-
-extern "C" int antsrl_replay_record_pre_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state,
-                                              const int8_t *rotation, const int8_t *pheromone, float *states,
-                                              float *agent_states, int64_t *actions, void *stream)
-{
-    const char *who = "replay_record_pre_plain";
-    const int rc = check_spec(who, r, true);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(rotation, 1);
-    REQUIRE(states, 4);
-    REQUIRE(agent_states, 4);
-    REQUIRE(actions, 8);
-    RecArgs a = {};
-    fill_rec(r, &a);
-    a.obs = obs; a.agent_state = agent_state; a.rot = rotation; a.ph = pheromone;
-    a.states = states; a.agent_states = agent_states; a.actions = actions;
-    return launch_rec(who, r, a, false, stream);
-}
-
-extern "C" int antsrl_replay_record_post_plain(const AntsRecordSpec *r, const void *obs, const float *agent_state,
-                                               const float *reward, const uint8_t *done, float *rewards, float *new_states,
-                                               float *new_agent_states, uint8_t *dones, void *stream)
-{
-    const char *who = "replay_record_post_plain";
-    const int rc = check_spec(who, r, true);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, r->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(reward, 4);
-    REQUIRE(done, 1);
-    REQUIRE(rewards, 4);
-    REQUIRE(new_states, 4);
-    REQUIRE(new_agent_states, 4);
-    REQUIRE(dones, 1);
-    RecArgs a = {};
-    fill_rec(r, &a);
-    a.obs = obs; a.agent_state = agent_state; a.reward = reward; a.done = done;
-    a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
-    return launch_rec(who, r, a, true, stream);
 }

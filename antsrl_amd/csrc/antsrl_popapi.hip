@@ -11,6 +11,7 @@
 #include "antsrl_device.h"
 #include "antsrl_dqn.h"
 #include "antsrl_fail.h"
+#include "antsrl_loopapi.h"
 #include "antsrl_policy_flat.h"
 #include "antsrl_population.h"
 
@@ -29,17 +30,14 @@ static int pop_spec(const char *who, const AntsPopSpec *s, PopTable *t, int *Em)
     if (s->n_envs % s->n_members)
         return fail(ANTSRL_E_INVALID, "%s: n_envs = %d is not a multiple of n_members = %d (members own equal shares)", who,
                     s->n_envs, s->n_members);
-    if (s->n_features < 1) return fail(ANTSRL_E_INVALID, "%s: n_features must be >= 1 (%d)", who, s->n_features);
-    if (s->n_features + 2 > 1024) return fail(ANTSRL_E_UNSUPPORTED, "%s: n_features + 2 = %d > 1024", who, s->n_features + 2);
-    if (s->obs_format != ANTSRL_OBS_F32 && s->obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16 (%d)", who, s->obs_format);
+    if ((rc = lt_features(who, s->n_features)) != ANTSRL_OK) return rc;
+    if ((rc = antsrl_check_obs_format(who, s->obs_format)) != ANTSRL_OK) return rc;
     if (s->obs_pitch != 0 && s->obs_pitch != s->n_features)
         return fail(ANTSRL_E_UNSUPPORTED, "%s: a population reads dense observation rows: obs_pitch %d must be 0 or n_features = %d",
                     who, s->obs_pitch, s->n_features);
     for (int p = 0; p < s->n_members; ++p) {
         const AntsPopMember &m = s->members[p];
-        if (!(m.epsilon >= 0.0 && m.epsilon <= 1.0))
-            return fail(ANTSRL_E_INVALID, "%s: member %d: epsilon must be in [0, 1] (%g)", who, p, m.epsilon);
+        if ((rc = antsrl_check_epsilon(who, p, m.epsilon)) != ANTSRL_OK) return rc;
         if (!(m.discount == m.discount)) return fail(ANTSRL_E_INVALID, "%s: member %d: discount is NaN", who, p);
         t->m[p].seed = m.seed;
         t->m[p].epsilon = m.epsilon;
@@ -99,30 +97,20 @@ extern "C" int antsrl_pop_select(const AntsPopSpec *s, uint64_t step, int8_t *ro
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(rotation, 1);
     REQUIRE(pheromone, 1);
-    SelArgs a = {};
-    a.step = step;
-    a.rot = rotation; a.ph = pheromone; a.explored = explored; // mem_old == mem_next == NULL: no memory part
-    a.env_base = (uint32_t)s->env_id_base; a.n_ants = (uint32_t)s->n_ants; a.n_rot = POP_N_ROT; a.n_ph = POP_N_PH;
-    a.M = (uint32_t)(Em * s->n_ants);
+    SelArgs a; // member 0's Em environments; seed and epsilon come from the table
+    antsrl_sel_args(0, step, s->env_id_base, Em, s->n_ants, 0.0, POP_N_ROT, POP_N_PH, &a);
+    a.rot = rotation; a.ph = pheromone; a.explored = explored;
     return enqueued(antsrl_launch_pop_select(a, t, s->n_members, Em, (hipStream_t)stream), who);
 }
 
-// the ring's part of a record entry: K rows per member into the rows behind `head` of every member's slab
+// a record entry's RecArgs for member 0: K rows per member into the rows behind `head` of every member's slab
 static int pop_rec(const char *who, const AntsPopSpec *s, int Em, uint64_t step, int64_t K, int64_t head, int64_t max_len,
                    RecArgs *a)
 {
-    const long long Mm = (long long)Em * s->n_ants;
-    if (K < 1 || K > Mm)
-        return fail(ANTSRL_E_INVALID, "%s: K must be in [1, n_envs / n_members * n_ants = %lld] (%lld)", who, Mm, (long long)K);
-    if (max_len < 1 || max_len > (1LL << 40)) return fail(ANTSRL_E_INVALID, "%s: max_len must be in [1, 2^40] (%lld)", who, (long long)max_len);
-    if (head < 0 || head >= max_len)
-        return fail(ANTSRL_E_INVALID, "%s: head must be in [0, max_len = %lld) (%lld)", who, (long long)max_len, (long long)head);
+    a->M = (long long)Em * s->n_ants;
+    const int rc = antsrl_ring_rows(who, "n_envs / n_members * n_ants", a->M, K, head, max_len, a);
+    if (rc != ANTSRL_OK) return rc;
     a->step = step; a->env_base = (uint64_t)s->env_id_base;
-    a->M = Mm; a->K = K;
-    a->n_write = K < max_len ? K : max_len; // only the newest max_len entries can survive
-    a->j0 = K - a->n_write;
-    a->row0 = (head + a->j0) % max_len;
-    a->max_len = max_len;
     a->pitch = s->n_features;
     a->n_ants = s->n_ants; a->F = s->n_features; a->A = POP_AGENT_DIM; a->mem = 0; a->half_rot = POP_N_ROT / 2;
     return ANTSRL_OK;
@@ -140,15 +128,10 @@ extern "C" int antsrl_pop_record_pre(const AntsPopSpec *s, uint64_t step, int64_
     int rc = pop_spec(who, s, &t, &Em);
     if (rc == ANTSRL_OK) rc = pop_rec(who, s, Em, step, K, head, max_len, &a);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, s->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(rotation, 1);
-    REQUIRE(states, 4);
-    REQUIRE(agent_states, 4);
-    REQUIRE(actions, 8);
-    a.obs = obs; a.agent_state = agent_state; a.rot = rotation; a.ph = pheromone;
-    a.states = states; a.agent_states = agent_states; a.actions = actions;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, s->obs_format == ANTSRL_OBS_BF16, false, (hipStream_t)stream), who);
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_pre(who, &a, bf16, obs, agent_state, nullptr, rotation, pheromone, states, agent_states, actions);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, false, (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64_t K, int64_t head, int64_t max_len,
@@ -163,17 +146,10 @@ extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64
     int rc = pop_spec(who, s, &t, &Em);
     if (rc == ANTSRL_OK) rc = pop_rec(who, s, Em, step, K, head, max_len, &a);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, s->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
-    REQUIRE(agent_state, 4);
-    REQUIRE(reward, 4);
-    REQUIRE(done, 1);
-    REQUIRE(rewards, 4);
-    REQUIRE(new_states, 4);
-    REQUIRE(new_agent_states, 4);
-    REQUIRE(dones, 1);
-    a.obs = obs; a.agent_state = agent_state; a.reward = reward; a.done = done;
-    a.rewards = rewards; a.states = new_states; a.agent_states = new_agent_states; a.dones = dones;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, s->obs_format == ANTSRL_OBS_BF16, true, (hipStream_t)stream), who);
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_post(who, &a, bf16, obs, agent_state, nullptr, reward, done, rewards, new_states, new_agent_states, dones);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, const float *b1, float *heads,
@@ -198,19 +174,15 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
     REQUIRE(adam, 4);
     REQUIRE(idx, 8);
     LinTrainArgs a = {};
-    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table)
-    rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx, B,
-                              0.0f, grads, false, loss, &a.batch);
+    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table), no workspace
+    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
+                   B, 0.0f, grads, false, loss, nullptr, &a.batch);
     if (rc != ANTSRL_OK) return rc;
     if ((uintptr_t)running_loss & 7) return fail(ANTSRL_E_INVALID, "%s: running_loss must be 8-byte aligned", who);
     for (int p = 0; p < s->n_members; ++p) { // Adam's scalars per member: the step size is the learning rate's
         if ((rc = antsrl_adam_args(who, step, s->members[p].learning_rate, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
         t.m[p].step_size = a.adam.step_size;
     }
-    const int F = s->n_features;
-    a.batch.F = F; a.batch.ksteps = (F + 15) / 16; a.batch.ntiles = ((int)B + 31) / 32;
-    a.batch.dq_scale = (float)(2.0 / (3.0 * (double)B));
-    a.batch.loss_scale = (float)(1.0 / (3.0 * (double)B));
     a.w1 = w1; a.b1 = b1; a.heads = heads; a.target_l3 = target_l3;
     a.adam.m = adam; a.adam.v = adam + LT_HEADS;
     const PopRunningLoss rl = {running_loss, first_loss != 0};

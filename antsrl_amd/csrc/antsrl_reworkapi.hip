@@ -12,7 +12,7 @@
 #include "antsrl_device.h"
 #include "antsrl_dqn.h" // antsrl_dqn_minibatch
 #include "antsrl_fail.h"
-#include "antsrl_memagent.h" // antsrl_check_batch
+#include "antsrl_loopapi.h" // antsrl_check_batch, antsrl_check_epsilon, antsrl_check_obs_format
 #include "antsrl_rework.h"
 #include "antsrl_reworktrain.h"
 
@@ -75,9 +75,7 @@ static int rework_act_check(const char *who, const AntsReworkShape *s, ReworkDim
         return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state, rotation, pheromone are required", who);
     if (((uintptr_t)collapsed | (uintptr_t)obs | (uintptr_t)agent_state | (uintptr_t)q_out) & 3)
         return fail(ANTSRL_E_INVALID, "%s: collapsed, obs, agent_state and q_out must be 4-byte aligned", who);
-    if (obs_format != ANTSRL_OBS_F32 && obs_format != ANTSRL_OBS_BF16)
-        return fail(ANTSRL_E_INVALID, "%s: obs_format must be ANTSRL_OBS_F32 or ANTSRL_OBS_BF16", who);
-    return ANTSRL_OK;
+    return antsrl_check_obs_format(who, obs_format);
 }
 
 extern "C" int antsrl_policy_rework(const AntsReworkShape *s, const void *collapsed, const void *obs, int obs_format,
@@ -105,7 +103,7 @@ extern "C" int antsrl_policy_rework_select(const AntsReworkShape *s, const void 
     int rc = rework_act_check(who, s, &d, collapsed, obs, obs_format, agent_state, rotation, pheromone, q_out);
     if (rc != ANTSRL_OK) return rc;
     if ((rc = antsrl_check_batch(who, env_id_base, n_envs, n_ants)) != ANTSRL_OK) return rc;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(ANTSRL_E_INVALID, "%s: epsilon must be in [0, 1] (%g)", who, epsilon);
+    if ((rc = antsrl_check_epsilon(who, -1, epsilon)) != ANTSRL_OK) return rc;
     ReworkSelect sel = {};
     sel.seed = seed; sel.step = step; sel.epsilon = epsilon; sel.explored = explored;
     sel.env_base = (uint32_t)env_id_base; sel.n_ants = (uint32_t)n_ants;

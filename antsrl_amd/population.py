@@ -21,7 +21,6 @@ pack), B > 512, members of unequal size, training_state.
 from __future__ import annotations
 
 import ctypes as C
-import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -29,12 +28,12 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _p
-from . import config as cm
-from .agent import _backend
+from .agent import _LoopAgent, _backend
 from .policy import linear_init
-from .train import EXPLORE_NAMES, LINEAR_TRAINED
+from .replay import RING_NAMES, _Ring, ring_arrays
+from .train import (LINEAR_NAMES, _TargetCounter, _clones, collect_names, copy_named, linear_adam_state, linear_model_views,
+                    linear_target_state_dict)
 
-RING_NAMES = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 MEMBER_DEFAULTS = dict(epsilon=0.1, discount=0.5, learning_rate=1e-4, seed=0)  # CollectAgent's
 
 
@@ -84,43 +83,36 @@ class _MemberRing:
         return self.fill
 
 
-class PopulationReplayMemory:
+class PopulationReplayMemory(_Ring):
     """DeviceReplayMemory's seven arrays with a leading [P]: states [P, max_len, 7, 7, K] and so on.  `head` and `fill`
     are shared.  record_pre / record_post are antsrl_pop_record_pre / _post: K rows per member and step into the same
-    rows of every member's slab, each member sampling its own ants with its own seed."""
+    rows of every member's slab, each member sampling its own ants with its own seed.  They take their tensors in the
+    order DeviceReplayMemory's do (memory: None, a population's agents have none) and the step's AntsPopSpec, step and k
+    by name."""
 
     def __init__(self, n_members: int, max_len: int, observation_space: Sequence[int], device="cuda"):
-        self.n_members, self.max_len, self.observation_space = n_members, max_len, tuple(observation_space)
-        self.device = torch.device(device)
-        z = lambda shape, dt: torch.zeros([n_members, max_len] + list(shape), dtype=dt, device=self.device)  # noqa: E731
-        self.states, self.new_states = z(observation_space, torch.float32), z(observation_space, torch.float32)
-        self.agent_states, self.new_agent_states = z([2], torch.float32), z([2], torch.float32)
-        self.actions = z([2], torch.int64)
-        self.rewards = z([], torch.float32)
-        self.dones = z([], torch.bool)
-        self.head = self.fill = 0
-        self._pending = None  # (spec, step, K) of a record_pre whose record_post has not come yet
-
-    def __len__(self):
-        return self.fill
+        self.n_members, self.observation_space = n_members, tuple(observation_space)
+        self._alloc(max_len, observation_space, [2], [2], device, lead=(n_members,))
 
     def member(self, p: int) -> _MemberRing:
         """Member p's slab under DeviceReplayMemory's seven names, with head and fill (views: same_rings works on it)."""
         return _MemberRing(self, p)
 
-    def record_pre(self, spec, step: int, k: int, obs, agent_state, rotation, pheromone) -> None:
+    def record_pre(self, obs, agent_state, memory, rotation, pheromone, *, spec, step: int, k: int) -> None:
         """Before the environment step: states, agent_states and actions of k of every member's transitions."""
         assert self._pending is None, "record_pre twice without record_post"
+        assert memory is None, "a population's agents have no memory"
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().antsrl_pop_record_pre(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
                                                          _p(rotation), _p(pheromone), _p(self.states), _p(self.agent_states),
                                                          _p(self.actions), _lib.stream(self.device)), "pop_record_pre")
         self._pending = (spec, step, k)
 
-    def record_post(self, obs, agent_state, reward, done) -> None:
+    def record_post(self, obs, agent_state, memory, reward, done) -> None:
         """After it: rewards, new_states, new_agent_states and dones of the same transitions; then head and fill advance
         as DeviceReplayMemory's do for k rows."""
         assert self._pending is not None, "record_post without record_pre"
+        assert memory is None, "a population's agents have no memory"
         spec, step, k = self._pending
         if done.dtype == torch.bool:
             done = done.view(torch.uint8)
@@ -130,15 +122,10 @@ class PopulationReplayMemory:
                                                           _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
                                                           _lib.stream(self.device)), "pop_record_post")
         self._pending = None
-        n = k
-        if n > self.max_len:  # as extend: only the newest max_len entries survived
-            self.head = (self.head + n - self.max_len) % self.max_len
-            n = self.max_len
-        self.fill = min(self.max_len, max(self.fill, self.head + n))
-        self.head = (self.head + n) % self.max_len
+        self._advance(k)
 
 
-class PopulationLinearTrainer:
+class PopulationLinearTrainer(_TargetCounter):
     """LinearTrainer's tensors with a leading [P], trained by antsrl_pop_lintrain_step: one launch, one workgroup per
     member.  w1 [P, 32, F + 2], b1 [P, 32] (frozen), heads [P, 198], target_l3 [P, 99], `_adam` [P, 2, 198], grads
     [P, 198]; member p's weights are initialised as LinearTrainer(seed=seed_p)'s.  Per member: discount and learning rate.
@@ -172,49 +159,33 @@ class PopulationLinearTrainer:
 
     # ---- weights ------------------------------------------------------------------------------------------------------
     def _model_views(self, p: int) -> dict:
-        d = {"explore_model.layer1.weight": self.w1[p], "explore_model.layer1.bias": self.b1[p]}
-        for k, (o, shp) in LINEAR_TRAINED.items():
-            d[k] = self.heads[p, o: o + math.prod(shp)].view(shp)
-        return d
+        return linear_model_views(self.w1[p], self.b1[p], self.heads[p])
 
     def state_dict(self, p: int) -> dict:
         """Member p's six tensors (copies) under CollectModel's names, in its order: what the reference loads."""
-        return {k: v.clone() for k, v in self._model_views(p).items()}
+        return _clones(self._model_views(p))
 
     def target_state_dict(self, p: int) -> dict:
-        d = self.state_dict(p)
-        d["layer3.weight"], d["layer3.bias"] = self.target_l3[p, 0:96].view(3, 32).clone(), self.target_l3[p, 96:99].clone()
-        return d
+        return linear_target_state_dict(self.state_dict(p), self.target_l3[p])
 
-    def _targets(self, p):
-        return range(self.n_members) if p is None else (p,)
+    def _load(self, sd, p: Optional[int], names) -> None:
+        sd = collect_names(sd)
+        for q in (range(self.n_members) if p is None else (p,)):
+            copy_named(sd, self._model_views(q), names)
 
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
         """LinearTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
-        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v for k, v in sd.items()}
-        for q in self._targets(p):
-            for k, dst in self._model_views(q).items():
-                src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-                assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-                dst.copy_(src)
-            self.target_l3[q].copy_(self.heads[q, 99:198])
+        self._load(sd, p, LINEAR_NAMES)
+        rows = slice(None) if p is None else p
+        self.target_l3[rows].copy_(self.heads[rows, 99:198])
 
     def load_explore_state_dict(self, sd, p: Optional[int] = None) -> None:
         """LinearTrainer.load_explore_state_dict for member p (None: every member): layer1 and layer2 from a four-tensor
         ExploreModel state_dict; layer3, its target copy and Adam's state stay."""
-        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
-        for q in self._targets(p):
-            views = self._model_views(q)
-            for k in EXPLORE_NAMES:
-                dst = views["explore_model." + k]
-                src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-                assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-                dst.copy_(src)
+        self._load(sd, p, LINEAR_NAMES[:4])
 
     def adam_state(self, p: int) -> dict:
-        def views(row):
-            return {k: self._adam[p, row, o: o + math.prod(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
-        return dict(step=self.step_count, exp_avg=views(0), exp_avg_sq=views(1))
+        return linear_adam_state(self.step_count, self._adam[p])
 
     def sync_target(self) -> None:
         """target := model for every member: one copy of [P, 99]."""
@@ -249,15 +220,11 @@ class PopulationLinearTrainer:
             return 0
         idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
         loss = self.step(ring, idx, spec)
-        if done:
-            self.target_update_counter += 1
-        if self.target_update_counter >= self.update_target_every:
-            self.sync_target()
-            self.target_update_counter = 0
+        self._count_target(done)
         return loss
 
 
-class PopulationAgent:
+class PopulationAgent(_LoopAgent):
     """P CollectAgents in lockstep (the module docstring).  members: one dict(epsilon=, discount=, learning_rate=, seed=)
     per member (CollectAgent's defaults where a key is missing).  Common to all members: record_per_step (K rows per
     member and step; None: all Em * n_ants), replay_size, minibatch (B <= 512), min_replay, update_target_every; `seed`
@@ -275,6 +242,7 @@ class PopulationAgent:
         self.update_target_every, self.seed = update_target_every, seed
         self.trainer = self.replay_memory = self.generator = None
         self.step_counter = 0
+        self._step_spec = None  # rollout_step's: one AntsPopSpec for the step's five entries
         self._lib = _lib.load()
 
     @property
@@ -313,16 +281,13 @@ class PopulationAgent:
         if explore_model is not None:
             self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
 
-    def initialize(self, api_or_env) -> None:
-        """Every pheromone activation x 10."""
-        env = _backend(api_or_env)
-        c = env.cfg
-        env.set_activation(torch.full((c.n_envs, c.n_ants, c.n_phero), 10.0, dtype=torch.float32, device=env.device))
-
-    def _spec(self):
-        """This step's AntsPopSpec: the kept one while no epsilon (or learning rate, or discount) has changed."""
+    def _spec(self, spec=None):
+        """This step's AntsPopSpec: the caller's, else rollout_step's, else the one of the values as they are now (the
+        kept one while no epsilon, learning rate or discount has changed: the lookup walks 4 P host values)."""
+        if spec is None:
+            spec = self._step_spec
         tr = self.trainer
-        return self.g.spec(self.seeds, self._epsilon, tr.lr, tr.discount)
+        return self.g.spec(self.seeds, self._epsilon, tr.lr, tr.discount) if spec is None else spec
 
     def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
         """-> (rotation int8, pheromone int8), device tensors shaped like the batch: every member's acting net on its own
@@ -331,7 +296,7 @@ class PopulationAgent:
         assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
             "a population reads the dense observation rows of its whole batch"
         assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
-        tr, step, spec = self.trainer, self.step_counter, (self._spec() if spec is None else spec)  # (rollout_step's own)
+        tr, step, spec = self.trainer, self.step_counter, self._spec(spec)
         lead = obs.shape[:-3]
         with torch.cuda.device(self.device):
             st = _lib.stream(self.device)
@@ -347,23 +312,21 @@ class PopulationAgent:
     def train(self, done: bool, step: int = 0, spec=None):
         """0 below min_replay, else the losses of one step of every member, float32 [P] on the device."""
         return self.trainer.train(self.replay_memory, bool(done), generator=self.generator, minibatch=self.minibatch,
-                                  min_replay=self.min_replay, spec=self._spec() if spec is None else spec)
+                                  min_replay=self.min_replay, spec=self._spec(spec))
+
+    def _record_kw(self) -> dict:
+        k = self.g.Mm if self.record_per_step is None else self.record_per_step
+        return dict(spec=self._spec(), step=self._action_step, k=k)
 
     def rollout_step(self, env, training: bool = True):
-        """One step of main.py's loop for every member: act, select, record_pre, env.step_update, record_post, train.
-        Returns the losses (float32 [P] on the device; 0 below min_replay or when not training).  No host
-        synchronisation."""
-        env = _backend(env)
-        obs, ast = env.obs, env.agent_state
-        rm, spec = self.replay_memory, self._spec()  # one spec for the step's five entries
-        rot, ph = self.get_action(obs, ast, training, env=env, spec=spec)
-        k = self.g.Mm if self.record_per_step is None else self.record_per_step
-        rm.record_pre(spec, self._action_step, k, obs, ast, self._rot, self._ph)
-        done = env.query(cm.Q_TIMESTEP) == env.cfg.max_time  # RL_api.py:200, known on the host
-        shape = (env.cfg.n_envs, env.cfg.n_ants)
-        env.step_update(rot.view(shape), ph.view(shape))
-        rm.record_post(env.obs, env.agent_state, env.reward.view(-1), env.done)
-        return self.train(done, self._action_step, spec) if training else 0
+        """_LoopAgent's step for every member: act, select, record_pre, env.step_update, record_post, train, on ONE lookup
+        of the AntsPopSpec.  Returns the losses (float32 [P] on the device; 0 below min_replay or when not training).  No
+        host synchronisation."""
+        self._step_spec = self._spec()
+        try:
+            return super().rollout_step(env, training)
+        finally:
+            self._step_spec = None
 
     # ---- models -------------------------------------------------------------------------------------------------------
     def save_model(self, p: int, file_name: str) -> None:
@@ -382,5 +345,5 @@ class PopulationAgent:
         if src == dst:
             return
         tr, rm = self.trainer, self.replay_memory
-        for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam) + (tuple(getattr(rm, n) for n in RING_NAMES) if ring else ()):
+        for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam) + (ring_arrays(rm) if ring else ()):
             t[dst].copy_(t[src])

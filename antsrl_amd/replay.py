@@ -15,6 +15,7 @@ Same constructor, `extend`, `random_access`, `__len__`, `__getitem__` as the ref
 from __future__ import annotations
 
 import ctypes as C
+from operator import attrgetter
 from typing import Optional, Sequence
 
 import numpy as np
@@ -24,26 +25,43 @@ from . import _lib
 from ._lib import ptr as _p
 
 
-class DeviceReplayMemory:
-    def __init__(self, max_len: int, observation_space: Sequence[int], agent_space: Sequence[int],
-                 action_space: Sequence[int], device="cuda"):
-        self.max_len = max_len
-        self.observation_space, self.agent_space, self.action_space = observation_space, agent_space, action_space
-        self.device = torch.device(device)
-        z = lambda shape, dt: torch.zeros([max_len] + list(shape), dtype=dt, device=self.device)  # noqa: E731
-        self.states = z(observation_space, torch.float32)          # replay_memory.py:18-24
-        self.agent_states = z(agent_space, torch.float32)
+#: a ring's seven arrays, in the order every entry and every trainer takes them
+RING_NAMES = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
+ring_arrays = attrgetter(*RING_NAMES)  # ring -> the seven, as a tuple
+
+
+class _Ring:
+    """What the single agent's ring and the population's share: the seven arrays, `head`, `fill` and how they advance."""
+
+    def _alloc(self, max_len: int, observation_space, agent_space, action_space, device, lead=()) -> None:
+        """The seven arrays (replay_memory.py:18-24), zeroed, [*lead, max_len, ...]; head (:36) and fill (:39) at 0."""
+        self.max_len, self.device = max_len, torch.device(device)
+        z = lambda shape, dt: torch.zeros(list(lead) + [max_len] + list(shape), dtype=dt, device=self.device)  # noqa: E731
+        self.states, self.new_states = z(observation_space, torch.float32), z(observation_space, torch.float32)
+        self.agent_states, self.new_agent_states = z(agent_space, torch.float32), z(agent_space, torch.float32)
         self.actions = z(action_space, torch.int64)
         self.rewards = z([], torch.float32)
-        self.new_states = z(observation_space, torch.float32)
-        self.new_agent_states = z(agent_space, torch.float32)
         self.dones = z([], torch.bool)
-        self.head = 0   # :36
-        self.fill = 0   # :39
-        self._pending = None  # the AntsRecordSpec of a record_pre whose record_post has not come yet
+        self.head = self.fill = 0
+        self._pending = None  # what a record_pre keeps for its record_post
 
     def __len__(self):
         return self.fill
+
+    def _advance(self, n: int) -> None:
+        """head and fill behind n new entries written from `head` on (replay_memory.py:109-112)."""
+        if n > self.max_len:  # only the newest max_len entries survived: they start n - max_len rows on
+            self.head = (self.head + n - self.max_len) % self.max_len
+            n = self.max_len
+        self.fill = min(self.max_len, max(self.fill, self.head + n))
+        self.head = (self.head + n) % self.max_len
+
+
+class DeviceReplayMemory(_Ring):
+    def __init__(self, max_len: int, observation_space: Sequence[int], agent_space: Sequence[int],
+                 action_space: Sequence[int], device="cuda"):
+        self.observation_space, self.agent_space, self.action_space = observation_space, agent_space, action_space
+        self._alloc(max_len, observation_space, agent_space, action_space, device)
 
     def _t(self, a, dtype):
         if a is None:
@@ -83,19 +101,15 @@ class DeviceReplayMemory:
                 dn = dn.repeat_interleave(n // dn.numel())
         else:
             dn = torch.full((n,), bool(done), dtype=torch.bool, device=self.device)
-        if n > self.max_len:  # only the newest max_len entries can survive
-            cut = n - self.max_len
-            st, ast, act, rw, nst, nast, dn = (x[cut:] for x in (st, ast, act, rw, nst, nast, dn))
-            self.head = (self.head + cut) % self.max_len
-            n = self.max_len
-        first = min(self.max_len - self.head, n)  # :97
-        for dst, src in ((self.states, st), (self.agent_states, ast), (self.actions, act), (self.rewards, rw),
-                         (self.new_states, nst), (self.new_agent_states, nast), (self.dones, dn)):
-            dst[self.head:self.head + first] = src[:first]
-            if first < n:  # wrap to the beginning (documented intent of :113-114)
-                dst[: n - first] = src[first:]
-        self.fill = min(self.max_len, max(self.fill, self.head + n))  # :109
-        self.head = (self.head + n) % self.max_len                       # :112
+        cut = max(0, n - self.max_len)  # only the newest max_len entries can survive
+        row0, kept = (self.head + cut) % self.max_len, n - cut
+        first = min(self.max_len - row0, kept)  # :97
+        for dst, src in zip(ring_arrays(self), (st, ast, act, rw, nst, nast, dn)):
+            src = src[cut:]
+            dst[row0:row0 + first] = src[:first]
+            if first < kept:  # wrap to the beginning (documented intent of :113-114)
+                dst[: kept - first] = src[first:]
+        self._advance(n)
 
     # ---- one step's transitions recorded around the environment step (antsrl_replay_record_pre / _post) ----------------
     def record_pre(self, obs, agent_state, memory, rotation, pheromone, n_envs: int, n_ants: int, k: Optional[int] = None,
@@ -122,19 +136,16 @@ class DeviceReplayMemory:
         self._check(rotation, torch.int8, M)
         if pheromone is not None:
             self._check(pheromone, torch.int8, M)
-        with torch.cuda.device(self.states.device):
-            if memory is None:
-                _lib.check(_lib.load().antsrl_replay_record_pre_plain(C.byref(spec), _p(obs), _p(agent_state), _p(rotation),
-                                                                      _p(pheromone), _p(self.states), _p(self.agent_states),
-                                                                      _p(self.actions), _lib.stream(self.states.device)),
-                           "replay_record_pre_plain")
-                self._pending = spec
-                return
-            _lib.check(_lib.load().antsrl_replay_record_pre(C.byref(spec), _p(obs), _p(agent_state), _p(memory), _p(rotation),
-                                                            _p(pheromone), _p(self.states), _p(self.agent_states),
-                                                            _p(self.actions), _lib.stream(self.states.device)),
-                       "replay_record_pre")
+        self._record("replay_record_pre", spec, obs, agent_state, memory, rotation, pheromone, self.states, self.agent_states,
+                     self.actions)
         self._pending = spec
+
+    def _record(self, entry: str, spec, obs, agent_state, memory, *tensors) -> None:
+        """antsrl_<entry>, or antsrl_<entry>_plain (which takes no memory) when `memory` is None."""
+        entry, mem = (entry + "_plain", ()) if memory is None else (entry, (_p(memory),))
+        with torch.cuda.device(self.states.device):
+            _lib.check(getattr(_lib.load(), "antsrl_" + entry)(C.byref(spec), _p(obs), _p(agent_state), *mem, *map(_p, tensors),
+                                                               _lib.stream(self.states.device)), entry)
 
     def record_post(self, obs, agent_state, memory, reward, done) -> None:
         """The second half, AFTER the step: rewards, new_states, new_agent_states (= agent_state ++ memory) and dones of the
@@ -155,26 +166,10 @@ class DeviceReplayMemory:
             self._check(memory, torch.float32, M * spec.mem_size)
         self._check(reward, torch.float32, M)
         self._check(done, torch.uint8, spec.n_envs)
-        with torch.cuda.device(self.states.device):
-            if memory is None:
-                _lib.check(_lib.load().antsrl_replay_record_post_plain(C.byref(spec), _p(obs), _p(agent_state), _p(reward),
-                                                                       _p(done), _p(self.rewards), _p(self.new_states),
-                                                                       _p(self.new_agent_states),
-                                                                       _p(self.dones.view(torch.uint8)),
-                                                                       _lib.stream(self.states.device)),
-                           "replay_record_post_plain")
-            else:
-                _lib.check(_lib.load().antsrl_replay_record_post(C.byref(spec), _p(obs), _p(agent_state), _p(memory),
-                                                                 _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
-                                                                 _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
-                                                                 _lib.stream(self.states.device)), "replay_record_post")
+        self._record("replay_record_post", spec, obs, agent_state, memory, reward, done, self.rewards, self.new_states,
+                     self.new_agent_states, self.dones.view(torch.uint8))
         self._pending = None
-        n = int(spec.K)
-        if n > self.max_len:  # as extend: only the newest max_len entries survived
-            self.head = (self.head + n - self.max_len) % self.max_len
-            n = self.max_len
-        self.fill = min(self.max_len, max(self.fill, self.head + n))
-        self.head = (self.head + n) % self.max_len
+        self._advance(int(spec.K))
 
     def _obs_format(self, obs) -> int:
         assert obs.dtype in (torch.float32, torch.bfloat16), obs.dtype

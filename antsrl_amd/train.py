@@ -18,13 +18,40 @@ import torch
 
 from . import _lib
 from ._lib import ptr as _p
+from .replay import ring_arrays
 from .policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_ptrs, memnet_param_shapes, memnet_shape_from_state_dict
 
 #: the 9 layers the loss reaches (the first 18 tensors of the state_dict)
 TRAINED_LAYERS = MEMNET_LAYERS[:9]
 
 
-class _DqnTrainer:
+class _TargetCounter:
+    """The tail of the reference's train behind a training step, for a trainer with `target_update_counter`,
+    `update_target_every` and `sync_target`: the counter moves at an episode's end (`done`, a host bool) and the target
+    net follows the model when it reaches update_target_every (collect_agent.py:141-146)."""
+
+    def _count_target(self, done: bool) -> None:
+        if done:
+            self.target_update_counter += 1
+        if self.target_update_counter >= self.update_target_every:
+            self.sync_target()
+            self.target_update_counter = 0
+
+
+def copy_named(sd, views: dict, names=None) -> None:
+    """sd[k] into views[k] for k in names (None: every view), as float32 on the view's device; the shapes must agree."""
+    for k in (views if names is None else names):
+        dst = views[k]
+        src = torch.as_tensor(sd[k]).to(dst.device, torch.float32)
+        assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
+        dst.copy_(src)
+
+
+def _clones(views: dict) -> dict:
+    return {k: v.clone() for k, v in views.items()}
+
+
+class _DqnTrainer(_TargetCounter):
     """What the five trainers share: the hyper-parameters and counters, the checks of a minibatch's arrays and its
     workspace, and train() around step().  A subclass holds its nets, writes grad / apply / step over its own entries
     (_FlatTrainer does, for the four whose ABIs share one argument order), sync_target, and
@@ -49,8 +76,7 @@ class _DqnTrainer:
 
     def _arrays(self, batch_or_replay):
         r = batch_or_replay
-        a = (r.states, r.agent_states, r.actions, r.rewards, r.new_states, r.new_agent_states, r.dones) \
-            if hasattr(r, "states") else tuple(r)
+        a = ring_arrays(r) if hasattr(r, "states") else tuple(r)
         n = len(r) if hasattr(r, "states") else a[0].shape[0]
         assert len(a) == 7
         st, ast, act, rw, nst, nast, dn = a
@@ -107,11 +133,7 @@ class _DqnTrainer:
     def train_on(self, batch_or_replay, idx: Optional[torch.Tensor], done: bool):
         """train() on rows the caller picked: the step, then the target counter and the sync."""
         loss = self.step(batch_or_replay, idx)
-        if done:
-            self.target_update_counter += 1
-        if self.target_update_counter >= self.update_target_every:
-            self.sync_target()
-            self.target_update_counter = 0
+        self._count_target(done)
         return loss
 
 
@@ -177,10 +199,10 @@ class MemoryTrainer(_DqnTrainer):
     # ---- weights ------------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
         """The model net's 26 tensors (copies), the reference's names and order."""
-        return {k: v.clone() for k, v in self._views(self._model).items()}
+        return _clones(self._views(self._model))
 
     def target_state_dict(self) -> dict:
-        return {k: v.clone() for k, v in self._views(self._target).items()}
+        return _clones(self._views(self._target))
 
     def load_state_dict(self, sd, _reset_adam: bool = False) -> None:
         """CollectAgentMemory.load_model (:213-215): sets the model AND the target net (and the acting policy).  Adam's
@@ -204,8 +226,8 @@ class MemoryTrainer(_DqnTrainer):
 
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the 18 trained tensors: step, exp_avg, exp_avg_sq (copies)."""
-        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._model, "m").items()},
-                    exp_avg_sq={k: v.clone() for k, v in self._views(self._model, "v").items()})
+        return dict(step=self.step_count, exp_avg=_clones(self._views(self._model, "m")),
+                    exp_avg_sq=_clones(self._views(self._model, "v")))
 
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the 18 trained state_dict tensors."""
@@ -301,15 +323,15 @@ class _FlatTrainer(_DqnTrainer):
 
     def state_dict(self) -> dict:
         """The model's tensors (copies) under the reference's names, in its order."""
-        return {k: v.clone() for k, v in self._views(self.model).items()}
+        return _clones(self._views(self.model))
 
     def target_state_dict(self) -> dict:
-        return {k: v.clone() for k, v in self._views(self.target).items()}
+        return _clones(self._views(self.target))
 
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the trained tensors: step, exp_avg, exp_avg_sq (copies)."""
-        return dict(step=self.step_count, exp_avg={k: v.clone() for k, v in self._views(self._adam[0]).items()},
-                    exp_avg_sq={k: v.clone() for k, v in self._views(self._adam[1]).items()})
+        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0])),
+                    exp_avg_sq=_clones(self._views(self._adam[1])))
 
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the trained tensors."""
@@ -357,6 +379,41 @@ LINEAR_TRAINED = {"explore_model.layer2.weight": (0, (3, 32)), "explore_model.la
 EXPLORE_NAMES = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias")
 
 
+def collect_names(sd) -> dict:
+    """sd under CollectModel's names: ExploreModel's bare layer1 / layer2 go behind the `explore_model.` prefix."""
+    return {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v for k, v in sd.items()}
+
+
+def explore_names(sd) -> dict:
+    """sd under ExploreModel's bare names: CollectModel's `explore_model.` prefix goes."""
+    return {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
+
+
+def linear_trained_views(flat) -> dict:
+    """The four trained tensors as views of a flat 198-float block: the heads, a row of Adam's moments, a gradient."""
+    return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in LINEAR_TRAINED.items()}
+
+
+def linear_model_views(w1, b1, heads) -> dict:
+    """The linear net's six tensors under CollectModel's names, in its order: views of layer1 and of the heads' block."""
+    return {"explore_model.layer1.weight": w1, "explore_model.layer1.bias": b1, **linear_trained_views(heads)}
+
+
+def linear_l3_views(target_l3) -> dict:
+    """layer3 as views of the target net's only own tensor, its 99-float copy."""
+    return {"layer3.weight": target_l3[0:96].view(3, 32), "layer3.bias": target_l3[96:99]}
+
+
+def linear_target_state_dict(state_dict: dict, target_l3) -> dict:
+    """The target net's state_dict from the model's: the shared layer1 and layer2, its own layer3 (a copy)."""
+    return {**state_dict, **_clones(linear_l3_views(target_l3))}
+
+
+def linear_adam_state(step: int, adam) -> dict:
+    """torch.optim.Adam's state for the four trained tensors from the moments [2][198]: step, exp_avg, exp_avg_sq (copies)."""
+    return dict(step=step, exp_avg=_clones(linear_trained_views(adam[0])), exp_avg_sq=_clones(linear_trained_views(adam[1])))
+
+
 class LinearTrainer(_FlatTrainer):
     """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
     reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
@@ -384,7 +441,7 @@ class LinearTrainer(_FlatTrainer):
         self._adam = torch.zeros((2, 198), dtype=torch.float32, device=self.device)
         self.grads = torch.zeros((198,), dtype=torch.float32, device=self.device)
         p.w2, p.b2 = self.heads[0:96].view(3, 32), self.heads[96:99]              # the live layer2
-        p.w3, p.b3 = self.target_l3[0:96].view(3, 32), self.target_l3[96:99]      # the target layer3
+        p.w3, p.b3 = linear_l3_views(self.target_l3).values()                     # the target layer3
         self.policy = p
         self.trained_floats = 198
         if state_dict is not None:
@@ -392,30 +449,20 @@ class LinearTrainer(_FlatTrainer):
 
     # ---- weights ------------------------------------------------------------------------------------------------
     def _model_views(self) -> dict:
-        d = {"explore_model.layer1.weight": self.policy.w1, "explore_model.layer1.bias": self.policy.b1}
-        for k, (o, shp) in LINEAR_TRAINED.items():
-            d[k] = self.heads[o: o + math.prod(shp)].view(shp)
-        return d
+        return linear_model_views(self.policy.w1, self.policy.b1, self.heads)
 
     def state_dict(self) -> dict:
         """The model's six tensors (copies) under CollectModel's names, in its order."""
-        return {k: v.clone() for k, v in self._model_views().items()}
+        return _clones(self._model_views())
 
     def target_state_dict(self) -> dict:
         """The target net's: the shared layer1 and layer2, its own layer3."""
-        d = self.state_dict()
-        d["layer3.weight"], d["layer3.bias"] = self.target_l3[0:96].view(3, 32).clone(), self.target_l3[96:99].clone()
-        return d
+        return linear_target_state_dict(self.state_dict(), self.target_l3)
 
     def load_state_dict(self, sd) -> None:
         """CollectAgent.load_model (:182-184): sets the model AND the target net.  CollectModel's names, or ExploreModel's
         bare layer1 / layer2 (with layer3).  Adam's state is kept, as the reference's optimizer keeps it."""
-        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v
-              for k, v in sd.items()}
-        for k, dst in self._model_views().items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-            dst.copy_(src)
+        copy_named(collect_names(sd), self._model_views())
         self.target_l3.copy_(self.heads[99:198])
         self.version += 1
 
@@ -423,25 +470,16 @@ class LinearTrainer(_FlatTrainer):
         """The hand-over from stage 1 of the curriculum (the line agents/collect_agent.py:84 has commented out): layer1
         and layer2 from a four-tensor ExploreModel state_dict (an ExploreAgent's save_model; bare names or behind the
         `explore_model.` prefix).  layer3, its target copy and Adam's state stay as they are."""
-        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
-        views = self._model_views()
-        for k in EXPLORE_NAMES:
-            dst = views["explore_model." + k]
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-            dst.copy_(src)
+        copy_named(collect_names(sd), self._model_views(), LINEAR_NAMES[:4])
         self.version += 1
 
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the four trained tensors: step, exp_avg, exp_avg_sq (copies)."""
-        def views(row):
-            return {k: self._adam[row, o: o + math.prod(shp)].view(shp).clone() for k, (o, shp) in LINEAR_TRAINED.items()}
-        return dict(step=self.step_count, exp_avg=views(0), exp_avg_sq=views(1))
+        return linear_adam_state(self.step_count, self._adam)
 
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the four trained tensors."""
-        g = self.grads if grads is None else grads
-        return {k: g[o: o + math.prod(shp)].view(shp) for k, (o, shp) in LINEAR_TRAINED.items()}
+        return linear_trained_views(self.grads if grads is None else grads)
 
     def sync_target(self) -> None:
         """target := model (:143-146): layer3 is all the two nets do not share."""
@@ -509,11 +547,7 @@ class ExploreTrainer(_FlatTrainer):
         """ExploreAgentPytorch.load_model (:157-159): sets the model AND the target net.  ExploreModel's names, bare or
         behind CollectModel's `explore_model.` prefix (other entries, such as layer3, are ignored).  Adam's state is
         kept, as the reference's optimizer keeps it."""
-        sd = {(k[len("explore_model."):] if k.startswith("explore_model.") else k): v for k, v in sd.items()}
-        for k, dst in self._views(self.model).items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-            dst.copy_(src)
+        copy_named(explore_names(sd), self._views(self.model))
         self.target.copy_(self.model)
         self.version += 1
 
@@ -576,7 +610,7 @@ class JointTrainer(_FlatTrainer):
         self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
         mv = self._views(self.model)
         p.w1, p.b1, p.w2, p.b2 = (mv[k] for k in LINEAR_NAMES[:4])                # the live layer1 and layer2
-        p.w3, p.b3 = self.target_l3[0:96].view(3, 32), self.target_l3[96:99]      # the target layer3
+        p.w3, p.b3 = linear_l3_views(self.target_l3).values()                     # the target layer3
         self.policy = p
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -584,31 +618,20 @@ class JointTrainer(_FlatTrainer):
     # ---- weights ------------------------------------------------------------------------------------------------
     def target_state_dict(self) -> dict:
         """The target net's: the shared layer1 and layer2, its own layer3."""
-        d = self.state_dict()
-        d["layer3.weight"], d["layer3.bias"] = self.target_l3[0:96].view(3, 32).clone(), self.target_l3[96:99].clone()
-        return d
-
-    def _load(self, sd, names) -> None:
-        views = self._views(self.model)
-        for k in names:
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            assert tuple(src.shape) == tuple(views[k].shape), (k, tuple(src.shape), tuple(views[k].shape))
-            views[k].copy_(src)
-        self.version += 1
+        return linear_target_state_dict(self.state_dict(), self.target_l3)
 
     def load_state_dict(self, sd) -> None:
         """CollectAgent.load_model (:182-184): sets the model AND the target net.  What LinearTrainer.load_state_dict
         accepts: CollectModel's names, or ExploreModel's bare layer1 / layer2 (with layer3).  Adam's state is kept."""
-        sd = {(k if (k.startswith("explore_model.") or k.startswith("layer3.")) else "explore_model." + k): v
-              for k, v in sd.items()}
-        self._load(sd, LINEAR_NAMES)
+        copy_named(collect_names(sd), self._views(self.model))
         self.target_l3.copy_(self.model[self._l3])
+        self.version += 1
 
     def load_explore_state_dict(self, sd) -> None:
         """layer1 and layer2 from a four-tensor ExploreModel state_dict (LinearTrainer.load_explore_state_dict): layer3,
         its target copy and Adam's state stay as they are."""
-        sd = {(k if k.startswith("explore_model.") else "explore_model." + k): v for k, v in sd.items()}
-        self._load(sd, LINEAR_NAMES[:4])
+        copy_named(collect_names(sd), self._views(self.model), LINEAR_NAMES[:4])
+        self.version += 1
 
     def sync_target(self) -> None:
         """target := model (:143-146): layer3 is all the two nets do not share."""
@@ -678,10 +701,7 @@ class ReworkTrainer(_FlatTrainer):
     def load_state_dict(self, sd) -> None:
         """CollectAgentRework.load_model (:186-188): sets the model AND the target net, and collapses the target once.
         Adam's state is kept, as the reference's optimizer keeps it."""
-        for k, dst in self._views(self.model).items():
-            src = torch.as_tensor(sd[k]).to(self.device, torch.float32)
-            assert tuple(src.shape) == tuple(dst.shape), (k, tuple(src.shape), tuple(dst.shape))
-            dst.copy_(src)
+        copy_named(sd, self._views(self.model))
         self.target.copy_(self.model)
         self.policy.recollapse()
         self.version += 1

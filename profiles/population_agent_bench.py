@@ -96,8 +96,8 @@ def bench_population(env, P, iters):
     idx = torch.randint(0, len(rm), (P, B), device="cuda")
 
     def rec():
-        rm.record_pre(spec, 0, K, env.obs, env.agent_state, pop._rot, pop._ph)
-        rm.record_post(env.obs, env.agent_state, env.reward.view(-1), env.done)
+        rm.record_pre(env.obs, env.agent_state, None, pop._rot, pop._ph, spec=spec, step=0, k=K)
+        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
     lib, st = _lib.load(), _lib.stream(env.device)
 
     def select():
