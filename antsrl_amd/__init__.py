@@ -5,7 +5,7 @@ from .config import AntsCfg, make_cfg  # noqa: F401
 
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
            "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats",
-           "EnvCheckpoint", "PopulationAgent", "train_population"]
+           "EnvCheckpoint", "PopulationAgent", "train_population", "PopulationExploreAgent", "train_population_curriculum"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -39,10 +39,10 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "EnvCheckpoint":
         from .checkpoint import EnvCheckpoint
         return EnvCheckpoint
-    if name == "PopulationAgent":
-        from .population import PopulationAgent
-        return PopulationAgent
-    if name in ("train_episodes", "train_population", "epsilon_schedule"):
+    if name in ("PopulationAgent", "PopulationExploreAgent"):
+        from . import population
+        return getattr(population, name)
+    if name in ("train_episodes", "train_population", "train_population_curriculum", "epsilon_schedule"):
         from . import driver
         return getattr(driver, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -36,7 +36,7 @@ struct ExpTrainArgs {
     AdamArgs adam;            // m, v: P floats each
 };
 
-static inline size_t antsrl_exptrain_floats(int F) { return (size_t)ET_HIDDEN * (F + 2) + ET_HIDDEN + ET_L2; }
+__host__ __device__ static inline size_t antsrl_exptrain_floats(int F) { return (size_t)ET_HIDDEN * (F + 2) + ET_HIDDEN + ET_L2; }
 static inline int antsrl_exptrain_blocks(int B) { return ((B + 31) / 32 + ET_WAVES - 1) / ET_WAVES; }
 // bytes of the partials in front of dh in the workspace (256-byte aligned)
 static inline size_t antsrl_exptrain_dh_offset(int B) { return ((size_t)antsrl_exptrain_blocks(B) * ET_PART * 4 + 255) / 256 * 256; }

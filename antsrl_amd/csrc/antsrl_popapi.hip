@@ -1,6 +1,8 @@
 // antsrl_popapi.hip — the population of linear agents in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The population
 // of linear agents"): antsrl_pop_policy / _select / _record_pre / _record_post / _lintrain_step in front of
-// antsrl_population.hip's kernels.
+// antsrl_population.hip's kernels; and behind them the population of explore agents ("The population of explore
+// agents"): antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes / _step in front of antsrl_popexplore.hip's, on the same
+// spec rules (select and record are the entries above: that population's net has no pheromone head and its ring none).
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -18,6 +20,7 @@
 #define POP_N_ROT 3 // the linear net's heads are 3 wide
 #define POP_N_PH 3
 #define POP_AGENT_DIM 2
+#define POP_ET_MAX_B (32 * ET_WAVES * 4) // an explore member's minibatch: four forward workgroups, the linear members' 512 rows
 
 // what every entry checks of its spec; fills the table's seeds and epsilons and *Em, the environments per member
 static int pop_spec(const char *who, const AntsPopSpec *s, PopTable *t, int *Em)
@@ -187,4 +190,90 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
     a.adam.m = adam; a.adam.v = adam + LT_HEADS;
     const PopRunningLoss rl = {running_loss, first_loss != 0};
     return enqueued(antsrl_launch_pop_lintrain(a, t, s->n_members, rl, (hipStream_t)stream), who);
+}
+
+// ---- the population of explore agents (antsrl_popexplore.hip) -------------------------------------------------------------
+
+// a member's minibatch: 1 <= B <= 512 rows, at most four workgroups of the forward stage
+static int pop_et_B(const char *who, int64_t B)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > POP_ET_MAX_B)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows: a member's step is at most four forward workgroups", who,
+                    (long long)B, POP_ET_MAX_B);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, const float *agent_state,
+                                         const float *target_blocks, int8_t *rotation, void *stream)
+{
+    const char *who = "pop_explore_policy";
+    PopTable t;
+    int Em = 0;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, Em);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, 16);
+    REQUIRE(agent_state, 4);
+    REQUIRE(target_blocks, 4);
+    REQUIRE(rotation, 1);
+    PopExplorePolicyArgs a;
+    a.obs = obs; a.agent_state = agent_state; a.target = target_blocks; a.rot = rotation;
+    a.Mm = Em * s->n_ants; a.F = s->n_features; a.P = s->n_members;
+    return enqueued(antsrl_launch_pop_explore_policy(a, s->obs_format == ANTSRL_OBS_BF16, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
+                                         size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
+{
+    const char *who = "pop_exptrain_sizes";
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = pop_et_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    if (n_members < 1 || n_members > ANTSRL_POP_MAX)
+        return fail(ANTSRL_E_INVALID, "%s: n_members must be in [1, ANTSRL_POP_MAX = %d] (%d)", who, ANTSRL_POP_MAX, n_members);
+    const size_t stride = antsrl_pop_exptrain_stride((int)B);
+    if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
+    if (workspace_stride) *workspace_stride = stride;
+    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
+    if (launches) *launches = 2;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, const float *target, float *adam_m, float *adam_v,
+                                        const float *states, const float *agent_states, const int64_t *actions,
+                                        const float *rewards, const float *new_states, const float *new_agent_states,
+                                        const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, int64_t step,
+                                        double beta1, double beta2, double eps, float *grads, float *loss,
+                                        double *running_loss, int first_loss, void *workspace, void *stream)
+{
+    const char *who = "pop_exptrain_step";
+    PopTable t;
+    int Em = 0;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = pop_et_B(who, B);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    REQUIRE(target, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    REQUIRE(idx, 8);
+    REQUIRE(workspace, 256);
+    ExpTrainArgs a = {};
+    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table); its partials are the
+    // front of the workspace, its dh behind them
+    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
+                   B, 0.0f, grads, false, loss, workspace, &a.batch);
+    if (rc != ANTSRL_OK) return rc;
+    if ((uintptr_t)running_loss & 7) return fail(ANTSRL_E_INVALID, "%s: running_loss must be 8-byte aligned", who);
+    for (int p = 0; p < s->n_members; ++p) { // Adam's scalars per member: the step size is the learning rate's
+        if ((rc = antsrl_adam_args(who, step, s->members[p].learning_rate, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
+        t.m[p].step_size = a.adam.step_size;
+    }
+    a.model = model; a.target = target;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    a.dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
+    a.blocks = antsrl_exptrain_blocks((int)B);
+    const PopRunningLoss rl = {running_loss, first_loss != 0};
+    return enqueued(antsrl_launch_pop_exptrain(a, t, s->n_members, antsrl_pop_exptrain_stride((int)B), rl, (hipStream_t)stream), who);
 }

@@ -11,9 +11,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
 #include "antsrl_lintrain.h"
 #include "antsrl_memagent.h"
+#include "antsrl_policy_flat.h"
 
 // The members' hyper-parameters: host values that travel BY VALUE in the kernel arguments (as EnvCopyTable does,
 // antsrl_checkpoint.h), so a changed epsilon costs no device allocation and no copy.  24 bytes x 64 = 1.5 KB.
@@ -42,6 +44,47 @@ struct PopRunningLoss {
     int first;            // this is the first training step: running_loss[p] = loss[p]
 };
 
+// ---- the population of explore agents (antsrl_popexplore.hip; include/antsrl.h, "The population of explore agents") ----
+// A member's net is ExploreTrainer's flat block of antsrl_exptrain_floats(F) floats (antsrl_exptrain.h): model, target,
+// Adam's m and v and grads are [P][floats].  The count is odd for an even F (9603 at F = 294), so a member's block starts
+// 4-byte aligned and no more: every kernel reads and writes the blocks float by float.
+
+// the acting net of every member, which is its TARGET block, on its Mm rows: grid (blocks, P); rotation only
+struct PopExplorePolicyArgs {
+    const void *obs;          // [P][Mm][F], float32 or bfloat16, dense
+    const float *agent_state; // [P][Mm][2]
+    const float *target;      // [P][antsrl_exptrain_floats(F)]
+    int8_t *rot;              // [P][Mm]
+    int Mm, F, P;
+};
+
+// The acting kernels' grid rule per member (k_policy_flat's: a workgroup's two waves take a tile each), one round of
+// resident workgroups shared among the members; *lds is the kernel's dynamic LDS
+static inline int pop_policy_blocks(int Mm, int F, int P, size_t *lds)
+{
+    *lds = pol_flat_lds(F);
+    int per_cu = (int)((160 * 1024) / *lds);
+    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
+    const int ntiles = (Mm + 31) / 32;
+    int blocks = (ntiles + 1) / 2;
+    const int cap = (256 * per_cu + P - 1) / P;
+    return blocks > cap ? cap : blocks;
+}
+
+// bytes of a member's part of the explore step's workspace: the single step's (partials, then dh [B][32]) rounded up to
+// 256, so that every member's partials and dh start as aligned as the single step's (B * 128 is no multiple of 256 for odd B)
+static inline size_t antsrl_pop_exptrain_stride(int B)
+{
+    return (antsrl_exptrain_dh_offset(B) + (size_t)B * ET_HIDDEN * sizeof(float) + 255) / 256 * 256;
+}
+
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_explore_policy(const PopExplorePolicyArgs &a, bool obs_bf16, hipStream_t st);
+// a: the single agent's ExpTrainArgs for member 0 (B <= 512: at most four forward workgroups per member; idx [P][B];
+// partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_exptrain(const ExpTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
+                                                      const PopRunningLoss &rl, hipStream_t st);
+
+// ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_select(const SelArgs &a, const PopTable &t, int P, int Em, hipStream_t st);

@@ -154,14 +154,8 @@ hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipSt
 {
     if (a.Mm < 1 || a.P < 1 || !pol_flat_fits(a.F)) return hipErrorInvalidValue;
     const int ks = (a.F + 15) / 16, tile_elems = pol_flat_tile_elems(a.F);
-    const size_t lds = pol_flat_lds(a.F);
-    // k_policy_flat's grid rule per member: a workgroup's two waves take a tile each, one round of resident workgroups
-    // shared among the members
-    int per_cu = (int)((160 * 1024) / lds);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    const int ntiles = (a.Mm + 31) / 32;
-    int blocks = (ntiles + 1) / 2, cap = (256 * per_cu + a.P - 1) / a.P;
-    if (blocks > cap) blocks = cap;
+    size_t lds = 0;
+    const int blocks = pop_policy_blocks(a.Mm, a.F, a.P, &lds); // (antsrl_population.h: the explore population's rule too)
     const hipError_t e = obs_bf16 ? antsrl_lds_optin<k_pop_policy<true>>(lds) : antsrl_lds_optin<k_pop_policy<false>>(lds);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)blocks, (unsigned)a.P);

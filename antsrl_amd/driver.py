@@ -13,7 +13,9 @@ own numbers (food at the anthill, on the map and carried, explored cells, pherom
 the device every so many steps and read back once, with the monitor's log.
 
 `train_population` is the same loop for a PopulationAgent (antsrl_amd/population.py): P linear agents with their own
-seed, epsilon, discount and learning rate on one handle, per-member rewards, running losses and epsilon schedules.
+seed, epsilon, discount and learning rate on one handle, per-member rewards, running losses and epsilon schedules.  It
+drives a PopulationExploreAgent unchanged, and `train_population_curriculum` runs the curriculum's two stages for every
+member on one handle: the explore population, the hand-over of layer1 on the device, the collect population.
 """
 from __future__ import annotations
 
@@ -47,14 +49,14 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
 def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True, min_epsilon=0.01,
                      max_epsilon=1.0, monitor: Optional[EpisodeMonitor] = None, report_every: int = 50,
                      save_as: Optional[str] = None) -> dict:
-    """train_episodes' loop for a PopulationAgent (antsrl_amd/population.py) on `env`, whose n_envs are the members' equal
-    shares: a fresh map per episode, pop.setup once, pop.initialize and the first observation per episode, `steps`
+    """train_episodes' loop for a PopulationAgent or a PopulationExploreAgent (antsrl_amd/population.py) on `env`, whose
+    n_envs are the members' equal shares: a fresh map per episode, pop.setup once, pop.initialize and the first observation per episode, `steps`
     rollout_steps, and after every episode member p's epsilon from epsilon_schedule with its own bounds (min_epsilon,
     max_epsilon: numbers, or arrays [P]).  No host read of device data before the end.
 
     The statistics per member: its episode reward comes from an EpisodeMonitor's per-environment totals (fed loss=None;
     `monitor` to continue one or by default one that reports every `report_every` steps), summed over the member's
-    environments on the host at the end; its running loss is PopulationLinearTrainer.running_loss (main.py:106-109 from
+    environments on the host at the end; its running loss is the trainer's `running_loss` (main.py:106-109 from
     the member's first training step on, kept by the training launch), copied into a [episodes, P] device log at each
     episode's end.  save_as: a format with one %d, pop.save_model(p, save_as % p) for every member at the end, when training.
 
@@ -98,6 +100,38 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
     log.update(member_total=total, member_reward=total / float(E // P * N), member_loss=loss_log[:episodes].cpu().numpy(),
                epsilons=np.array(epsilons).reshape(episodes, P), monitor=mon)
     return log
+
+
+def train_population_curriculum(explore_pop, collect_pop, env, gen, episodes, steps: int, *, seed: int = 0,
+                                monitor: Optional[EpisodeMonitor] = None, report_every: int = 50, **kw) -> tuple:
+    """The linear agent's curriculum for every member of a sweep in one process, on one handle and one monitor:
+    train_population on `explore_pop` (a PopulationExploreAgent) for episodes[0] episodes, the hand-over on the device
+    (collect_pop.setup(env, explore_population=explore_pop): member p's layer1 and layer2 under member p's collect heads),
+    then train_population on `collect_pop` (a PopulationAgent of as many members, not set up yet) for episodes[1].
+    Stage 2's episode seeds start from seed + episodes[0]; **kw (training, min_epsilon,
+    max_epsilon, save_as — a format with one %s for the stage, "explore" or "collect", before the member's %d) goes to
+    both stages.  No file round trip, no per-member launch and no host read of device data inside an episode.
+
+    Returns (stage 1's log, stage 2's log), each train_population's; the monitor's rows are shared, so each log holds the
+    reports of the episodes up to its end, and `member_*` and `epsilons` are the stage's own."""
+    e1, e2 = episodes
+    env = getattr(env, "_backend", env)
+    assert collect_pop.trainer is None, "the collect population is set up by the hand-over"
+    if explore_pop.n_members != collect_pop.n_members:
+        raise ValueError("the explore population has %d members, the collect population %d" %
+                         (explore_pop.n_members, collect_pop.n_members))
+    mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=report_every,
+                                                             max_reports=max(1, (e1 + e2) * (steps // report_every)),
+                                                             max_episodes=max(1, e1 + e2))
+    save_as = kw.pop("save_as", None)
+    stage = lambda name: None if save_as is None else save_as % (name, "%d")  # noqa: E731
+    if explore_pop.trainer is None:  # (train_population would, at its first episode: e1 = 0 still hands something over)
+        env.generate(gen, episode_seed(env.cfg, gen, seed, 0))
+        explore_pop.setup(env)
+    log1 = train_population(explore_pop, env, gen, e1, steps, seed=seed, monitor=mon, save_as=stage("explore"), **kw)
+    collect_pop.setup(env, explore_population=explore_pop)
+    log2 = train_population(collect_pop, env, gen, e2, steps, seed=seed + e1, monitor=mon, save_as=stage("collect"), **kw)
+    return log1, log2
 
 
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,

@@ -11,16 +11,22 @@ cfg.env_id_base + p Em and the member's own seed, epsilon, discount and learning
 kernels are the single agent's stages with the member taken from the grid, and every draw of the agents' loop is keyed
 on (seed, global environment id, step).
 
+`PopulationExploreAgent` is the same for P ExploreAgents, the curriculum's first stage (antsrl_popexplore.hip; DESIGN
+§7.25): `PopulationExploreTrainer` holds ExploreTrainer's flat blocks with a leading [P], a step is two launches whatever P
+is, and `PopulationAgent.setup(env, explore_population=pop_e)` puts member p's layer1 and layer2 under member p's collect
+heads, device to device (driver.train_population_curriculum runs both stages on one handle).
+
 The pieces mirror the single agent's: `PopulationLinearTrainer` (LinearTrainer's tensors with a leading [P]),
 `PopulationReplayMemory` (DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
 record the same number of rows at every step) and `PopulationAgent` (CollectAgent's surface, per member where the
 reference's has one model).  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
-changed epsilon costs no device copy.  Out of scope: the other agents' nets, in-loop acting (a handle holds one policy
-pack), B > 512, members of unequal size, training_state.
+changed epsilon costs no device copy.  Out of scope: the joint, memory and rework agents' nets, in-loop acting (a handle
+holds one policy pack), B > 512, members of unequal size, training_state.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -31,8 +37,8 @@ from ._lib import ptr as _p
 from .agent import _LoopAgent, _backend
 from .policy import linear_init
 from .replay import RING_NAMES, _Ring, ring_arrays
-from .train import (LINEAR_NAMES, _TargetCounter, _clones, collect_names, copy_named, linear_adam_state, linear_model_views,
-                    linear_target_state_dict)
+from .train import (EXPLORE_NAMES, LINEAR_NAMES, _TargetCounter, _clones, collect_names, copy_named, explore_names,
+                    linear_adam_state, linear_model_views, linear_target_state_dict)
 
 MEMBER_DEFAULTS = dict(epsilon=0.1, discount=0.5, learning_rate=1e-4, seed=0)  # CollectAgent's
 
@@ -184,6 +190,21 @@ class PopulationLinearTrainer(_TargetCounter):
         ExploreModel state_dict; layer3, its target copy and Adam's state stay."""
         self._load(sd, p, LINEAR_NAMES[:4])
 
+    def load_explore_population(self, explore_trainer) -> None:
+        """The hand-over from stage 1 of the curriculum for every member at once: member p's layer1 and layer2 from
+        member p's MODEL block of a PopulationExploreTrainer (w1 | b1 | w2 | b2 in one flat block; heads[:99] is w2 | b2),
+        three device copies of [P, ...].  layer3, its target copy and Adam's state stay, as load_explore_state_dict
+        leaves them."""
+        P, n1 = self.n_members, 32 * (self.n_features + 2)
+        if explore_trainer.n_members != P:
+            raise ValueError("the explore population has %d members, this one %d" % (explore_trainer.n_members, P))
+        if explore_trainer.n_features != self.n_features:
+            raise ValueError("the explore population's rows have %d features, these %d" % (explore_trainer.n_features, self.n_features))
+        m = explore_trainer.model.to(self.device)
+        self.w1.view(P, n1).copy_(m[:, :n1])
+        self.b1.copy_(m[:, n1:n1 + 32])
+        self.heads[:, :99].copy_(m[:, n1 + 32:n1 + 131])
+
     def adam_state(self, p: int) -> dict:
         return linear_adam_state(self.step_count, self._adam[p])
 
@@ -224,17 +245,127 @@ class PopulationLinearTrainer(_TargetCounter):
         return loss
 
 
-class PopulationAgent(_LoopAgent):
-    """P CollectAgents in lockstep (the module docstring).  members: one dict(epsilon=, discount=, learning_rate=, seed=)
-    per member (CollectAgent's defaults where a key is missing).  Common to all members: record_per_step (K rows per
-    member and step; None: all Em * n_ants), replay_size, minibatch (B <= 512), min_replay, update_target_every; `seed`
-    seeds the generator of the minibatch indices.  The acting kernel is always the standalone one."""
+class PopulationExploreTrainer(_TargetCounter):
+    """ExploreTrainer's tensors with a leading [P], trained by antsrl_pop_exptrain_step: two launches whatever P is.
+    model, target, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat block is ExploreTrainer's:
+    layer1.weight, layer1.bias, layer2.weight, layer2.bias); member p's weights are initialised as
+    ExploreTrainer(seed=seed_p)'s, its target a copy.  The acting net of a member is its TARGET block.  Per member:
+    discount and learning rate.  Common: Adam's betas, eps and step count, update_target_every and the target counter.
+    `running_loss` (float64 [P]) is kept by the step's second launch from the first training step on."""
 
-    name = "collect_agent_population"
-    rotations = pheromones = 3
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+                 update_target_every: int = 1):
+        self.g, self.device = geometry, torch.device(device)
+        P, F = geometry.P, geometry.n_features
+        self.n_members, self.n_features = P, F
+        self.seeds = [int(s) for s in seeds]
+        self.discount, self.lr = np.asarray(discount, dtype=np.float64).copy(), np.asarray(lr, dtype=np.float64).copy()
+        self.betas, self.eps, self.update_target_every = tuple(float(b) for b in betas), float(eps), int(update_target_every)
+        self.target_update_counter = self.syncs = self.step_count = 0
+        self._lib = _lib.load()
+        IN = F + 2
+        self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
+                      "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
+        self.trained_floats = self._sizes(1)[0]
+        assert self.trained_floats == 32 * IN + 131
+        sds = [linear_init(dict(layer1=(32, IN), layer2=(3, 32)), s) for s in self.seeds]
+        self.model = torch.stack([torch.cat([sd[k].reshape(-1) for k in EXPLORE_NAMES]) for sd in sds]).to(self.device).contiguous()
+        self.target = self.model.clone()
+        self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.running_loss = torch.zeros((P,), dtype=torch.float64, device=self.device)
+        self.last_idx = None  # the [P, B] indices of the last step
+        self._work, self._work_B = None, 0
 
-    def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
-                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
+    def _sizes(self, B: int) -> tuple:
+        """antsrl_pop_exptrain_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches)."""
+        tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+        _lib.check(self._lib.antsrl_pop_exptrain_sizes(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
+                                                       C.byref(ws), C.byref(n)), "pop_exptrain_sizes")
+        return tf.value, stride.value, ws.value, n.value
+
+    def _spec(self):
+        """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
+        return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    def _views(self, flat) -> dict:
+        """The four tensors of one member's flat block (views) under ExploreModel's names, in its order."""
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self, p: int) -> dict:
+        """Member p's four tensors (copies) under ExploreModel's names: what ExploreAgent.save_model writes."""
+        return _clones(self._views(self.model[p]))
+
+    def target_state_dict(self, p: int) -> dict:
+        return _clones(self._views(self.target[p]))
+
+    def load_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """ExploreTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
+        sd = explore_names(sd)
+        for q in (range(self.n_members) if p is None else (p,)):
+            copy_named(sd, self._views(self.model[q]))
+        rows = slice(None) if p is None else p
+        self.target[rows].copy_(self.model[rows])
+
+    def adam_state(self, p: int) -> dict:
+        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0, p])),
+                    exp_avg_sq=_clones(self._views(self._adam[1, p])))
+
+    def sync_target(self) -> None:
+        """target := model for every member: one copy of [P, trained_floats]."""
+        self.target.copy_(self.model)
+        self.syncs += 1
+
+    # ---- the step -----------------------------------------------------------------------------------------------------
+    def workspace(self, B: int) -> torch.Tensor:
+        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
+        if self._work is None or self._work_B != B:
+            self._work = torch.empty((self._sizes(B)[2],), dtype=torch.uint8, device=self.device)
+            self._work_B = B
+        return self._work
+
+    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
+        """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
+        slab: gradient, loss and Adam of both layers in two launches.  Returns the losses, float32 [P] on the device."""
+        P = self.n_members
+        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
+        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        work = self.workspace(idx.shape[1])
+        first = self.step_count == 0
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_pop_exptrain_step(
+                C.byref(self._spec() if spec is None else spec), _p(self.model), _p(self.target), _p(self._adam[0]), _p(self._adam[1]),
+                _p(ring.states), _p(ring.agent_states), _p(ring.actions), _p(ring.rewards), _p(ring.new_states),
+                _p(ring.new_agent_states), _p(ring.dones), ring.max_len, _p(idx), idx.shape[1], self.step_count, self.betas[0],
+                self.betas[1], self.eps, _p(self.grads), _p(loss), _p(self.running_loss), int(first), _p(work),
+                _lib.stream(self.device)), "pop_exptrain_step")
+        self.last_idx = idx
+        return loss
+
+    def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 256,
+              min_replay: int = 1000, spec=None):
+        """The reference's train for every member at once: 0 below min_replay, else a step on `minibatch` rows per member
+        drawn on the device (one torch.randint of [P, B]), then the target counter (host side) and the sync."""
+        if len(ring) < min_replay:
+            return 0
+        idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
+        loss = self.step(ring, idx, spec)
+        self._count_target(done)
+        return loss
+
+
+class _Population(_LoopAgent):
+    """What the two populations share around their nets: the members' host values, the front of setup, the step's one
+    AntsPopSpec, select, the ring, train, the fused loop and the per-member files.  A subclass names its `minibatch`
+    default in its __init__, builds its trainer (`_make_trainer`), launches its acting net (`_policy`), says whether the
+    net has a pheromone head (`pheromones`) and lists the per-member tensors of its trainer (`_member_tensors`)."""
+
+    rotations = 3
+
+    def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int], replay_size: int, minibatch: int,
+                 min_replay: int, update_target_every: int, seed: int):
         self.members = _members(members)
         self.n_members = len(self.members)
         self._epsilon = np.array([m["epsilon"] for m in self.members], dtype=np.float64)
@@ -242,7 +373,7 @@ class PopulationAgent(_LoopAgent):
         self.update_target_every, self.seed = update_target_every, seed
         self.trainer = self.replay_memory = self.generator = None
         self.step_counter = 0
-        self._step_spec = None  # rollout_step's: one AntsPopSpec for the step's five entries
+        self._step_spec = None  # rollout_step's: one AntsPopSpec for the step's entries
         self._lib = _lib.load()
 
     @property
@@ -254,8 +385,8 @@ class PopulationAgent(_LoopAgent):
     def epsilon(self, v) -> None:
         self._epsilon = np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n_members,)).copy()
 
-    def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None) -> None:
-        """CollectAgent.setup for every member; trained_model / explore_model go to every member."""
+    def _setup(self, api_or_env, trainer_cls):
+        """The front of setup: the geometry, the trainer, the ring, the action buffers, the generator and the counters."""
         env = _backend(api_or_env)
         cfg = env.cfg
         self.device = env.device
@@ -265,9 +396,8 @@ class PopulationAgent(_LoopAgent):
         if self.record_per_step is not None and not 1 <= self.record_per_step <= self.g.Mm:
             raise ValueError("record_per_step = %d is not in [1, %d], a member's ants" % (self.record_per_step, self.g.Mm))
         self.seeds = [m["seed"] for m in self.members]
-        self.trainer = PopulationLinearTrainer(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
-                                               [m["learning_rate"] for m in self.members],
-                                               update_target_every=self.update_target_every)
+        self.trainer = trainer_cls(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
+                                   [m["learning_rate"] for m in self.members], update_target_every=self.update_target_every)
         self.replay_memory = PopulationReplayMemory(self.n_members, self.replay_size, self.observation_space, device=self.device)
         M = cfg.n_envs * cfg.n_ants
         self._rot = torch.zeros((M,), dtype=torch.int8, device=self.device)
@@ -276,10 +406,7 @@ class PopulationAgent(_LoopAgent):
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(self.seed)
         self.step_counter = self._action_step = 0
-        if trained_model is not None:
-            self.load_model(trained_model)
-        if explore_model is not None:
-            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
+        return env
 
     def _spec(self, spec=None):
         """This step's AntsPopSpec: the caller's, else rollout_step's, else the one of the values as they are now (the
@@ -289,25 +416,28 @@ class PopulationAgent(_LoopAgent):
         tr = self.trainer
         return self.g.spec(self.seeds, self._epsilon, tr.lr, tr.discount) if spec is None else spec
 
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        """The acting net of every member into `_rot` (and `_ph`, with a pheromone head)."""
+        raise NotImplementedError
+
     def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
-        """-> (rotation int8, pheromone int8), device tensors shaped like the batch: every member's acting net on its own
-        rows (antsrl_pop_policy); with `training`, antsrl_pop_select then replaces the actions of the environments that
-        explore this step, each member with its own seed and epsilon."""
+        """-> (rotation int8, pheromone int8 or None for a net without that head), device tensors shaped like the batch:
+        every member's acting net on its own rows; with `training`, antsrl_pop_select then replaces the actions of the
+        environments that explore this step, each member with its own seed and epsilon."""
         assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
             "a population reads the dense observation rows of its whole batch"
         assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
-        tr, step, spec = self.trainer, self.step_counter, self._spec(spec)
+        step, spec = self.step_counter, self._spec(spec)
         lead = obs.shape[:-3]
         with torch.cuda.device(self.device):
             st = _lib.stream(self.device)
-            _lib.check(self._lib.antsrl_pop_policy(C.byref(spec), _p(obs), _p(agent_state), _p(tr.w1), _p(tr.b1), _p(tr.heads),
-                                                   _p(tr.target_l3), _p(self._rot), _p(self._ph), st), "pop_policy")
+            self._policy(spec, obs, agent_state, st)
             if training:
                 _lib.check(self._lib.antsrl_pop_select(C.byref(spec), step, _p(self._rot), _p(self._ph), _p(self._explored), st),
                            "pop_select")
         self._action_step = step
         self.step_counter += 1
-        return self._rot.view(lead), self._ph.view(lead)
+        return self._rot.view(lead), (self._ph.view(lead) if self.pheromones else None)
 
     def train(self, done: bool, step: int = 0, spec=None):
         """0 below min_replay, else the losses of one step of every member, float32 [P] on the device."""
@@ -330,20 +460,91 @@ class PopulationAgent(_LoopAgent):
 
     # ---- models -------------------------------------------------------------------------------------------------------
     def save_model(self, p: int, file_name: str) -> None:
-        """torch.save of member p's six-tensor state_dict under the reference's names (on the CPU)."""
+        """torch.save of member p's state_dict under the reference's names (on the CPU)."""
         torch.save({k: v.cpu() for k, v in self.trainer.state_dict(p).items()}, file_name)
 
     def load_model(self, file_name: str, p: Optional[int] = None) -> None:
         """Model and target net of member p (None: of every member) from a state_dict file of the reference's."""
         self.trainer.load_state_dict(torch.load(file_name, map_location="cpu"), p)
 
+    def _member_tensors(self) -> tuple:
+        """(tensor, the dimension that counts the members) for every per-member tensor of the trainer."""
+        raise NotImplementedError
+
     def copy_member(self, src: int, dst: int, ring: bool = True) -> None:
-        """Member src's weights (the frozen layer1 included), target, Adam moments and, with `ring`, ring slab over member
-        dst's: with env.fork the exploit step of population-based training.  The hyper-parameters stay dst's own."""
+        """Member src's weights, target, Adam moments and, with `ring`, ring slab over member dst's: with env.fork the
+        exploit step of population-based training.  The hyper-parameters stay dst's own."""
         P = self.n_members
         assert 0 <= src < P and 0 <= dst < P, (src, dst)
         if src == dst:
             return
-        tr, rm = self.trainer, self.replay_memory
-        for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam) + (ring_arrays(rm) if ring else ()):
-            t[dst].copy_(t[src])
+        for t, dim in self._member_tensors() + (tuple((a, 0) for a in ring_arrays(self.replay_memory)) if ring else ()):
+            t.select(dim, dst).copy_(t.select(dim, src))
+
+
+class PopulationAgent(_Population):
+    """P CollectAgents in lockstep (the module docstring).  members: one dict(epsilon=, discount=, learning_rate=, seed=)
+    per member (CollectAgent's defaults where a key is missing).  Common to all members: record_per_step (K rows per
+    member and step; None: all Em * n_ants), replay_size, minibatch (B <= 512), min_replay, update_target_every; `seed`
+    seeds the generator of the minibatch indices.  The acting kernel is always the standalone one."""
+
+    name = "collect_agent_population"
+    pheromones = 3
+
+    def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
+        super().__init__(members, record_per_step=record_per_step, replay_size=replay_size, minibatch=minibatch,
+                         min_replay=min_replay, update_target_every=update_target_every, seed=seed)
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None,
+              explore_population=None) -> None:
+        """CollectAgent.setup for every member; trained_model / explore_model go to every member.  explore_population: a
+        PopulationExploreAgent of as many members, the curriculum's first stage: member p's layer1 and layer2 come from
+        its member p's model, device to device (PopulationLinearTrainer.load_explore_population); applied last."""
+        self._setup(api_or_env, PopulationLinearTrainer)
+        if trained_model is not None:
+            self.load_model(trained_model)
+        if explore_model is not None:
+            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
+        if explore_population is not None:
+            self.trainer.load_explore_population(explore_population.trainer)
+
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        tr = self.trainer
+        _lib.check(self._lib.antsrl_pop_policy(C.byref(spec), _p(obs), _p(agent_state), _p(tr.w1), _p(tr.b1), _p(tr.heads),
+                                               _p(tr.target_l3), _p(self._rot), _p(self._ph), st), "pop_policy")
+
+    def _member_tensors(self) -> tuple:
+        """The frozen layer1 included."""
+        tr = self.trainer
+        return tuple((t, 0) for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam))
+
+
+class PopulationExploreAgent(_Population):
+    """P ExploreAgents in lockstep: the first stage of the curriculum for every member of a sweep (the module
+    docstring).  Rotation only: get_action returns (rotation, None), the environment is stepped without a pheromone
+    action and the ring stores (rotation + 1, 1).  members and the common arguments are PopulationAgent's (ExploreAgent's
+    minibatch of 256; B <= 512).  The acting net of a member is its TARGET block, which changes at a sync or a load only.
+    Hand its members' layer1 and layer2 to a PopulationAgent with PopulationAgent.setup(env, explore_population=this)."""
+
+    name = "explore_agent_population"
+    pheromones = 0  # no pheromone head (antsrl_pop_select still draws a pheromone for every exploring ant: nothing reads it)
+
+    def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
+                 minibatch: int = 256, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
+        super().__init__(members, record_per_step=record_per_step, replay_size=replay_size, minibatch=minibatch,
+                         min_replay=min_replay, update_target_every=update_target_every, seed=seed)
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """ExploreAgent.setup for every member; trained_model goes to every member."""
+        self._setup(api_or_env, PopulationExploreTrainer)
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        _lib.check(self._lib.antsrl_pop_explore_policy(C.byref(spec), _p(obs), _p(agent_state), _p(self.trainer.target),
+                                                       _p(self._rot), st), "pop_explore_policy")
+
+    def _member_tensors(self) -> tuple:
+        tr = self.trainer
+        return ((tr.model, 0), (tr.target, 0), (tr._adam, 1))

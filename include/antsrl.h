@@ -1477,6 +1477,54 @@ int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, const float 
                              double beta2, double eps, float *grads, float *loss, double *running_loss, int first_loss,
                              void *stream);
 
+/* The population of explore agents: P ExploreAgents (the net of "The explore agent's training step": layer1 and layer2
+ * both trained, the target net a full copy) in lockstep on one handle — the first stage of the curriculum whose second
+ * stage is the population above.  The spec, the members' shares of the handle, the table and the alignment rule are that
+ * population's; so are select and record: antsrl_pop_select draws a pheromone that nothing reads, and
+ * antsrl_pop_record_pre with pheromone = NULL stores (rotation + 1, 1).
+ *
+ * THE DEFINING PROPERTY is the same: member p is, bit for bit, antsrl_policy_mlp without a pheromone head (w3 = NULL) on
+ * its TARGET block, antsrl_agent_select_actions, antsrl_replay_record_*_plain and antsrl_exptrain_step run on a handle of
+ * its Em environments, with its own seed, epsilon, discount and learning rate.
+ *
+ * Layout: model, target, adam_m, adam_v, grads float [P][T], T = 32 (F + 2) + 131 (antsrl_exptrain_sizes'
+ * trained_floats), a member's block laid out as antsrl_exptrain_step's; loss float [P]; idx int64 [P][B]; the ring as
+ * above.  T is odd for an even F, so a member's block is 4-byte aligned and no more: the kernels read and write the
+ * blocks one float at a time.  The workspace is member-major: member p's part starts p * workspace_stride bytes behind
+ * `workspace` and is laid out as antsrl_exptrain_step's (partials, then dh [B][32]); workspace_stride is that entry's
+ * workspace_bytes rounded up to 256.
+ *
+ * Refusals (ANTSRL_E_INVALID unless stated), before anything is launched: the spec's, as above;
+ *   antsrl_pop_explore_policy: the flat form does not take n_features (UNSUPPORTED); the alignment rule (UNSUPPORTED);
+ *     obs not 16-byte aligned; any NULL or misaligned pointer;
+ *   antsrl_pop_exptrain_sizes: n_features as above; B < 1; B > 512 (UNSUPPORTED); n_members outside [1, ANTSRL_POP_MAX];
+ *   antsrl_pop_exptrain_step: B < 1; B > 512 (UNSUPPORTED: at most four workgroups of the forward stage per member and
+ *     256 in all); n_rows outside [1, 2^40]; any NULL or misaligned pointer (idx is required and 8-byte aligned; the
+ *     workspace 256-byte aligned; grads and running_loss may be NULL, running_loss 8-byte aligned); Adam's arguments for
+ *     every member's learning_rate.
+ * No entry allocates or synchronises the host; no atomics: equal inputs give equal bits.
+ *
+ *   antsrl_pop_explore_policy  rotation = argmax(layer2(h)) - 1 of every member's TARGET block (target_blocks [P][T]) on
+ *                         its own rows.  One launch, grid (blocks, P), antsrl_pop_policy's launch rule.
+ *   antsrl_pop_exptrain_sizes  trained_floats = T, workspace_stride, workspace_bytes = n_members * workspace_stride and
+ *                         launches = 2 (any of the four may be NULL).
+ *   antsrl_pop_exptrain_step   antsrl_exptrain_step per member in TWO launches: the forward stage on grid
+ *                         (ceil(B / 128), P), the layer1 stage on grid (ceil((F + 3) / 8) + 1, P).  idx, n_rows, step,
+ *                         running_loss and first_loss as antsrl_pop_lintrain_step's; the second launch keeps the
+ *                         running loss.
+ * The target sync is one device copy of [P][T] (model into target), the caller's; the hand-over to the population of
+ * linear agents is a device copy per member of the model block's layer1 and layer2 into w1, b1 and heads [p][0 .. 99). */
+int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, const float *agent_state, const float *target_blocks,
+                              int8_t *rotation, void *stream);
+int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
+                              size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches);
+int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, const float *target, float *adam_m, float *adam_v,
+                             const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                             const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                             const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps,
+                             float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,174 @@
+"""CPU-side checks of the explore population's C-ABI entries (antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes /
+antsrl_pop_exptrain_step; include/antsrl.h, "The population of explore agents"): exported, the sizes, and every invalid
+argument refused in its own words before any HIP call.  No kernel is launched here: every call of an enqueueing entry
+fails validation, and the pointers are fakes that are never dereferenced (tests/test_population_abi_cpu.py's way)."""
+import ctypes as C
+
+import pytest
+
+from antsrl_amd import _lib
+from antsrl_amd import build as buildmod
+
+NEW = ("antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes", "antsrl_pop_exptrain_step")
+FAKE = C.c_void_p(1 << 20)  # 256-byte aligned
+ODD = C.c_void_p((1 << 20) + 2)
+ODD4 = C.c_void_p((1 << 20) + 4)
+ODD8 = C.c_void_p((1 << 20) + 8)
+ODD128 = C.c_void_p((1 << 20) + 128)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    buildmod.build_hip()
+    return _lib.load()
+
+
+def test_new_symbols_are_exported(lib):
+    for n in NEW:
+        assert hasattr(lib, n) and n in _lib.EXPORTS
+    assert lib.antsrl_abi_version() == 5  # the entries are additive
+
+
+def spec(**kw):
+    a = dict(P=3, E=6, N=20, base=0, F=294, fmt=1, pitch=0, reserved=0, eps=0.5, lr=1e-3, discount=0.5, seed=7)
+    a.update(kw)
+    s = _lib.AntsPopSpec(a["P"], a["E"], a["N"], a["base"], a["F"], a["fmt"], a["pitch"], a["reserved"])
+    for p in range(max(0, min(a["P"], _lib.POP_MAX))):
+        s.members[p] = _lib.AntsPopMember(a["seed"], a["eps"], a["lr"], a["discount"], 0)
+    return s
+
+
+POLICY_PTRS = ("obs", "agent_state", "target_blocks", "rotation")
+TRAIN_PTRS = ("model", "target", "adam_m", "adam_v", "states", "agent_states", "actions", "rewards", "new_states",
+              "new_agent_states", "dones")
+
+
+def policy(lib, s, **kw):
+    a = {n: FAKE for n in POLICY_PTRS}
+    a.update(kw)
+    return lib.antsrl_pop_explore_policy(C.byref(s) if s is not None else None, *[a[n] for n in POLICY_PTRS], None)
+
+
+def train(lib, s, **kw):
+    a = {n: FAKE for n in TRAIN_PTRS}
+    a.update(n_rows=200, idx=FAKE, B=48, step=1, beta1=0.9, beta2=0.999, eps=1e-8, grads=FAKE, loss=FAKE, running_loss=FAKE,
+             first=1, workspace=FAKE)
+    a.update(kw)
+    return lib.antsrl_pop_exptrain_step(C.byref(s) if s is not None else None, *[a[n] for n in TRAIN_PTRS], a["n_rows"], a["idx"],
+                                        a["B"], a["step"], a["beta1"], a["beta2"], a["eps"], a["grads"], a["loss"],
+                                        a["running_loss"], a["first"], a["workspace"], None)
+
+
+def sizes(lib, F, B, P):
+    tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+    rc = lib.antsrl_pop_exptrain_sizes(F, B, P, C.byref(tf), C.byref(stride), C.byref(ws), C.byref(n))
+    return rc, tf.value, stride.value, ws.value, n.value
+
+
+ENTRIES = ((policy, b"pop_explore_policy"), (train, b"pop_exptrain_step"))
+
+
+# ---- the spec: both enqueueing entries refuse it in the linear population's words, under their own names
+@pytest.mark.parametrize("kw,code,msg", [
+    (dict(P=0), -1, b"n_members must be in [1, ANTSRL_POP_MAX = 64] (0)"),
+    (dict(P=65, E=65), -1, b"n_members must be in [1, ANTSRL_POP_MAX = 64] (65)"),
+    (dict(P=3, E=7), -1, b"n_envs = 7 is not a multiple of n_members = 3"),
+    (dict(F=0), -1, b"n_features must be >= 1"), (dict(F=1023), -4, b"n_features + 2 = 1025 > 1024"),
+    (dict(pitch=320), -4, b"dense observation rows"), (dict(fmt=2), -1, b"obs_format"),
+    (dict(eps=1.5), -1, b"member 0: epsilon must be in [0, 1]"), (dict(discount=float("nan")), -1, b"member 0: discount is NaN"),
+])
+def test_spec_validation(lib, kw, code, msg):
+    for fn, who in ENTRIES:
+        assert fn(lib, spec(**kw)) == code, (who, kw)
+        err = lib.antsrl_last_error()
+        assert msg in err and who in err, (kw, err)
+
+
+def test_null_spec(lib):
+    for fn, who in ENTRIES:
+        assert fn(lib, None) == -1
+        assert b"NULL spec" in lib.antsrl_last_error() and who in lib.antsrl_last_error()
+
+
+# ---- the acting entry
+def test_policy_alignment_rule(lib):
+    """Em = 1, n_ants = 33, F = 294, bfloat16: a member's slice is 19 404 bytes = 16 * 1212 + 12."""
+    assert policy(lib, spec(P=2, E=2, N=33, fmt=1)) == -4
+    err = lib.antsrl_last_error()
+    assert b"pop_explore_policy" in err and b"19404 bytes" in err and b"multiple of 16" in err, err
+    # the acceptance test's two shapes pass the rule: what is refused next is a pointer
+    for s in (spec(P=3, E=6, N=20, fmt=1), spec(P=2, E=2, N=32, fmt=0)):
+        assert policy(lib, s, obs=None) == -1 and b"obs is required" in lib.antsrl_last_error()
+
+
+def test_policy_flat_form_only(lib):
+    assert policy(lib, spec(F=1000)) == -4
+    assert b"flat form only" in lib.antsrl_last_error() and b"pop_explore_policy" in lib.antsrl_last_error()
+
+
+@pytest.mark.parametrize("kw,msg", [({n: None}, n.encode() + b" is required") for n in POLICY_PTRS] + [
+    (dict(obs=ODD8), b"obs must be 16-byte"), (dict(agent_state=ODD), b"agent_state must be 4-byte"),
+    (dict(target_blocks=ODD), b"target_blocks must be 4-byte")])
+def test_policy_pointers(lib, kw, msg):
+    assert policy(lib, spec(), **kw) == -1
+    assert msg in lib.antsrl_last_error() and b"pop_explore_policy" in lib.antsrl_last_error(), lib.antsrl_last_error()
+
+
+# ---- the sizes
+def test_sizes(lib):
+    """F = 294, three members, B = 136 (two forward workgroups) and others: the stride is the single entry's bytes rounded
+    up to 256 (an odd B's dh [B][32] is no multiple of 256 bytes), the workspace three strides."""
+    single, one_launches = C.c_size_t(), C.c_int32()
+    for B in (136, 33, 1, 512):
+        assert lib.antsrl_exptrain_sizes(294, B, None, C.byref(single), C.byref(one_launches)) == 0
+        rc, tf, stride, ws, n = sizes(lib, 294, B, 3)
+        assert rc == 0 and tf == 32 * 296 + 131 and tf % 2 == 1  # an odd count: blocks are 4-byte aligned and no more
+        assert stride % 256 == 0 and single.value <= stride < single.value + 256, (B, stride, single.value)
+        assert ws == 3 * stride and n == 2 == one_launches.value
+    assert sizes(lib, 294, 33, 3)[2] > lib_single(lib, 294, 33)  # B = 33: 33 * 128 is no multiple of 256, the stride is rounded
+    # any output may be NULL
+    assert lib.antsrl_pop_exptrain_sizes(294, 136, 3, None, None, None, None) == 0
+
+
+def lib_single(lib, F, B):
+    single = C.c_size_t()
+    assert lib.antsrl_exptrain_sizes(F, B, None, C.byref(single), None) == 0
+    return single.value
+
+
+@pytest.mark.parametrize("args,code,msg", [
+    ((294, 0, 3), -1, b"B must be >= 1 (0)"), ((294, 513, 3), -4, b"B = 513 > 512 rows"),
+    ((294, 48, 0), -1, b"n_members must be in [1, ANTSRL_POP_MAX = 64] (0)"),
+    ((294, 48, 65), -1, b"n_members must be in [1, ANTSRL_POP_MAX = 64] (65)"),
+    ((0, 48, 3), -1, b"n_features must be >= 1"), ((1023, 48, 3), -4, b"n_features + 2 = 1025 > 1024")])
+def test_sizes_validation(lib, args, code, msg):
+    assert sizes(lib, *args)[0] == code
+    assert msg in lib.antsrl_last_error() and b"pop_exptrain_sizes" in lib.antsrl_last_error(), lib.antsrl_last_error()
+
+
+# ---- the training step
+def test_train_B(lib):
+    assert train(lib, spec(), B=513) == -4
+    err = lib.antsrl_last_error()
+    assert b"B = 513 > 512 rows" in err and b"pop_exptrain_step" in err, err
+    assert train(lib, spec(), B=0) == -1 and b"B must be >= 1" in lib.antsrl_last_error()
+    # 512 rows pass: the next refusal is a pointer's
+    assert train(lib, spec(), B=512, model=None) == -1 and b"model is required" in lib.antsrl_last_error()
+
+
+@pytest.mark.parametrize("kw,msg", [({n: None}, n.encode() + b" is required") for n in TRAIN_PTRS] + [
+    ({n: ODD}, n.encode() + b" must be") for n in TRAIN_PTRS if n != "dones"] + [
+    (dict(idx=None), b"idx is required"), (dict(idx=ODD4), b"idx must be 8-byte"), (dict(loss=None), b"loss is required"),
+    (dict(loss=ODD), b"loss must be 4-byte"), (dict(grads=ODD), b"grads must be 4-byte"),
+    (dict(running_loss=ODD4), b"running_loss must be 8-byte"), (dict(workspace=None), b"workspace is required"),
+    (dict(workspace=ODD128), b"workspace must be 256-byte"), (dict(n_rows=0), b"n_rows"),
+    (dict(step=0), b"step must be >= 1"), (dict(beta1=1.0), b"beta1, beta2"), (dict(eps=0.0), b"eps must be")])
+def test_train_validation(lib, kw, msg):
+    assert train(lib, spec(), **kw) == -1, kw
+    assert msg in lib.antsrl_last_error() and b"pop_exptrain_step" in lib.antsrl_last_error(), (kw, lib.antsrl_last_error())
+
+
+def test_train_member_learning_rate(lib):
+    s = spec()
+    s.members[2].learning_rate = -1.0
+    assert train(lib, s) == -1 and b"lr must be" in lib.antsrl_last_error()
