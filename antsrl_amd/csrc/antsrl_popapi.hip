@@ -21,14 +21,20 @@
 #define POP_N_PH 3
 #define POP_AGENT_DIM 2
 #define POP_ET_MAX_B (32 * ET_WAVES * 4) // an explore member's minibatch: four forward workgroups, the linear members' 512 rows
+#define POP_ET_LIMIT "at most four forward workgroups"
+
+static int pop_n_members(const char *who, int n_members)
+{
+    if (n_members >= 1 && n_members <= ANTSRL_POP_MAX) return ANTSRL_OK;
+    return fail(ANTSRL_E_INVALID, "%s: n_members must be in [1, ANTSRL_POP_MAX = %d] (%d)", who, ANTSRL_POP_MAX, n_members);
+}
 
 // what every entry checks of its spec; fills the table's seeds and epsilons and *Em, the environments per member
 static int pop_spec(const char *who, const AntsPopSpec *s, PopTable *t, int *Em)
 {
     if (!s) return fail(ANTSRL_E_INVALID, "%s: NULL spec", who);
-    if (s->n_members < 1 || s->n_members > ANTSRL_POP_MAX)
-        return fail(ANTSRL_E_INVALID, "%s: n_members must be in [1, ANTSRL_POP_MAX = %d] (%d)", who, ANTSRL_POP_MAX, s->n_members);
-    int rc = antsrl_check_batch(who, s->env_id_base, s->n_envs, s->n_ants);
+    int rc = pop_n_members(who, s->n_members);
+    if (rc == ANTSRL_OK) rc = antsrl_check_batch(who, s->env_id_base, s->n_envs, s->n_ants);
     if (rc != ANTSRL_OK) return rc;
     if (s->n_envs % s->n_members)
         return fail(ANTSRL_E_INVALID, "%s: n_envs = %d is not a multiple of n_members = %d (members own equal shares)", who,
@@ -155,6 +161,28 @@ extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64
     return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
 }
 
+// The training entries refuse in the order spec, B, their pointers, dqn_batch's arguments, running_loss, Adam's.
+// A member's minibatch: 1 <= B <= max_B rows; `limit` says what of the entry's step max_B rows are.
+static int pop_train_B(const char *who, int64_t B, int max_B, const char *limit)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > max_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows: a member's step is %s", who, (long long)B, max_B, limit);
+    return ANTSRL_OK;
+}
+
+// running_loss's alignment, then Adam's scalars per member: the step size is the learning rate's and goes into the table
+static int pop_train_tail(const char *who, const AntsPopSpec *s, int64_t step, double beta1, double beta2, double eps,
+                          const double *running_loss, AdamArgs *adam, PopTable *t)
+{
+    if ((uintptr_t)running_loss & 7) return fail(ANTSRL_E_INVALID, "%s: running_loss must be 8-byte aligned", who);
+    for (int p = 0; p < s->n_members; ++p) {
+        const int rc = antsrl_adam_args(who, step, s->members[p].learning_rate, beta1, beta2, eps, adam);
+        if (rc != ANTSRL_OK) return rc;
+        t->m[p].step_size = adam->step_size;
+    }
+    return ANTSRL_OK;
+}
+
 extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, const float *b1, float *heads,
                                         const float *target_l3, float *adam, const float *states, const float *agent_states,
                                         const int64_t *actions, const float *rewards, const float *new_states,
@@ -166,10 +194,8 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
     PopTable t;
     int Em = 0;
     int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, 32 * LT_FUSED_TILES, "one workgroup");
     if (rc != ANTSRL_OK) return rc;
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > 32 * LT_FUSED_TILES)
-        return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows: a member's step is one workgroup", who, (long long)B, 32 * LT_FUSED_TILES);
     REQUIRE(w1, 4);
     REQUIRE(b1, 4);
     REQUIRE(heads, 4);
@@ -180,12 +206,8 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
     // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table), no workspace
     rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
                    B, 0.0f, grads, false, loss, nullptr, &a.batch);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
     if (rc != ANTSRL_OK) return rc;
-    if ((uintptr_t)running_loss & 7) return fail(ANTSRL_E_INVALID, "%s: running_loss must be 8-byte aligned", who);
-    for (int p = 0; p < s->n_members; ++p) { // Adam's scalars per member: the step size is the learning rate's
-        if ((rc = antsrl_adam_args(who, step, s->members[p].learning_rate, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-        t.m[p].step_size = a.adam.step_size;
-    }
     a.w1 = w1; a.b1 = b1; a.heads = heads; a.target_l3 = target_l3;
     a.adam.m = adam; a.adam.v = adam + LT_HEADS;
     const PopRunningLoss rl = {running_loss, first_loss != 0};
@@ -193,16 +215,6 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
 }
 
 // ---- the population of explore agents (antsrl_popexplore.hip) -------------------------------------------------------------
-
-// a member's minibatch: 1 <= B <= 512 rows, at most four workgroups of the forward stage
-static int pop_et_B(const char *who, int64_t B)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > POP_ET_MAX_B)
-        return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows: a member's step is at most four forward workgroups", who,
-                    (long long)B, POP_ET_MAX_B);
-    return ANTSRL_OK;
-}
 
 extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, const float *agent_state,
                                          const float *target_blocks, int8_t *rotation, void *stream)
@@ -228,10 +240,9 @@ extern "C" int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t 
 {
     const char *who = "pop_exptrain_sizes";
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = pop_et_B(who, B);
+    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
     if (rc != ANTSRL_OK) return rc;
-    if (n_members < 1 || n_members > ANTSRL_POP_MAX)
-        return fail(ANTSRL_E_INVALID, "%s: n_members must be in [1, ANTSRL_POP_MAX = %d] (%d)", who, ANTSRL_POP_MAX, n_members);
     const size_t stride = antsrl_pop_exptrain_stride((int)B);
     if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
     if (workspace_stride) *workspace_stride = stride;
@@ -251,7 +262,7 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
     PopTable t;
     int Em = 0;
     int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_et_B(who, B);
+    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
     REQUIRE(target, 4);
@@ -264,12 +275,8 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
     // front of the workspace, its dh behind them
     rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
                    B, 0.0f, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
     if (rc != ANTSRL_OK) return rc;
-    if ((uintptr_t)running_loss & 7) return fail(ANTSRL_E_INVALID, "%s: running_loss must be 8-byte aligned", who);
-    for (int p = 0; p < s->n_members; ++p) { // Adam's scalars per member: the step size is the learning rate's
-        if ((rc = antsrl_adam_args(who, step, s->members[p].learning_rate, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-        t.m[p].step_size = a.adam.step_size;
-    }
     a.model = model; a.target = target;
     a.adam.m = adam_m; a.adam.v = adam_v;
     a.dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));

@@ -19,7 +19,9 @@ heads, device to device (driver.train_population_curriculum runs both stages on 
 The pieces mirror the single agent's: `PopulationLinearTrainer` (LinearTrainer's tensors with a leading [P]),
 `PopulationReplayMemory` (DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
 record the same number of rows at every step) and `PopulationAgent` (CollectAgent's surface, per member where the
-reference's has one model).  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
+reference's has one model).  The two trainers are one `_PopulationTrainer` (the members' host values, Adam's scalars, the
+counters, `running_loss`, `train` and `step`, whose call hands both entries the same nineteen arguments behind the net's
+pointers) under each net's tensors, dicts and entry, as the two agents are one `_Population`.  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
 changed epsilon costs no device copy.  Out of scope: the joint, memory and rework agents' nets, in-loop acting (a handle
 holds one policy pack), B > 512, members of unequal size, training_state.
 """
@@ -131,7 +133,64 @@ class PopulationReplayMemory(_Ring):
         self._advance(k)
 
 
-class PopulationLinearTrainer(_TargetCounter):
+class _PopulationTrainer(_TargetCounter):
+    """What the two population trainers share.  Per member: seed, discount and learning rate.  Common: Adam's betas, eps
+    and step count, update_target_every and the target counter.  `running_loss` (float64 [P]) is main.py:106-109's
+    running loss per member, kept by the training step's last launch from the first training step on.  `_spec`, `train`
+    and `step` are here; a subclass allocates its tensors (`grads` among them), holds the dict and load methods of its
+    net and names its entry (`_entry`)."""
+
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas, eps: float, update_target_every: int):
+        self.g, self.device = geometry, torch.device(device)
+        self.n_members, self.n_features = geometry.P, geometry.n_features
+        self.seeds = [int(s) for s in seeds]
+        self.discount, self.lr = np.asarray(discount, dtype=np.float64).copy(), np.asarray(lr, dtype=np.float64).copy()
+        self.betas, self.eps, self.update_target_every = tuple(float(b) for b in betas), float(eps), int(update_target_every)
+        self.target_update_counter = self.syncs = self.step_count = 0
+        self.running_loss = torch.zeros((self.n_members,), dtype=torch.float64, device=self.device)
+        self.last_idx = None  # the [P, B] indices of the last step
+        self._lib = _lib.load()
+
+    def _spec(self):
+        """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
+        return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
+
+    def _entry(self, B: int) -> tuple:
+        """(the training entry, its name in an error, the net's pointers that lead its arguments, what follows
+        first_loss) for a step on B rows per member."""
+        raise NotImplementedError
+
+    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
+        """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
+        slab: gradient, loss and Adam in the entry's launches, whatever P is.  Returns the losses, float32 [P] on the
+        device.  spec: the agent's AntsPopSpec of this step (its seeds, learning rates and discounts are this trainer's),
+        else one is built."""
+        P = self.n_members
+        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
+        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        entry, who, net, tail = self._entry(idx.shape[1])
+        first = self.step_count == 0
+        self.step_count += 1
+        with torch.cuda.device(self.device):
+            _lib.check(entry(C.byref(self._spec() if spec is None else spec), *net, *map(_p, ring_arrays(ring)), ring.max_len,
+                             _p(idx), idx.shape[1], self.step_count, self.betas[0], self.betas[1], self.eps, _p(self.grads),
+                             _p(loss), _p(self.running_loss), int(first), *tail, _lib.stream(self.device)), who)
+        self.last_idx = idx
+        return loss
+
+    def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 264,
+              min_replay: int = 1000, spec=None):
+        """The reference's train for every member at once: 0 below min_replay, else a step on `minibatch` rows per member
+        drawn on the device (one torch.randint of [P, B]), then the target counter (host side) and the sync."""
+        if len(ring) < min_replay:
+            return 0
+        idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
+        loss = self.step(ring, idx, spec)
+        self._count_target(done)
+        return loss
+
+
+class PopulationLinearTrainer(_PopulationTrainer):
     """LinearTrainer's tensors with a leading [P], trained by antsrl_pop_lintrain_step: one launch, one workgroup per
     member.  w1 [P, 32, F + 2], b1 [P, 32] (frozen), heads [P, 198], target_l3 [P, 99], `_adam` [P, 2, 198], grads
     [P, 198]; member p's weights are initialised as LinearTrainer(seed=seed_p)'s.  Per member: discount and learning rate.
@@ -140,13 +199,8 @@ class PopulationLinearTrainer(_TargetCounter):
 
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
                  update_target_every: int = 1):
-        self.g, self.device = geometry, torch.device(device)
-        P, F = geometry.P, geometry.n_features
-        self.n_members, self.n_features = P, F
-        self.seeds = [int(s) for s in seeds]
-        self.discount, self.lr = np.asarray(discount, dtype=np.float64).copy(), np.asarray(lr, dtype=np.float64).copy()
-        self.betas, self.eps, self.update_target_every = tuple(float(b) for b in betas), float(eps), int(update_target_every)
-        self.target_update_counter = self.syncs = self.step_count = 0
+        super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
+        P, F = self.n_members, self.n_features
         sds = [linear_init(dict(layer1=(32, F + 2), layer2=(3, 32), layer3=(3, 32)), s) for s in self.seeds]
         stack = lambda f: torch.stack([f(sd) for sd in sds]).to(self.device).contiguous()  # noqa: E731
         self.w1, self.b1 = stack(lambda sd: sd["layer1.weight"]), stack(lambda sd: sd["layer1.bias"])
@@ -155,13 +209,6 @@ class PopulationLinearTrainer(_TargetCounter):
         self.target_l3 = self.heads[:, 99:198].clone()
         self._adam = torch.zeros((P, 2, 198), dtype=torch.float32, device=self.device)
         self.grads = torch.zeros((P, 198), dtype=torch.float32, device=self.device)
-        self.running_loss = torch.zeros((P,), dtype=torch.float64, device=self.device)
-        self.last_idx = None  # the [P, B] indices of the last step
-        self._lib = _lib.load()
-
-    def _spec(self):
-        """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
-        return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
 
     # ---- weights ------------------------------------------------------------------------------------------------------
     def _model_views(self, p: int) -> dict:
@@ -213,39 +260,13 @@ class PopulationLinearTrainer(_TargetCounter):
         self.target_l3.copy_(self.heads[:, 99:198])
         self.syncs += 1
 
-    # ---- the step -----------------------------------------------------------------------------------------------------
-    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
-        """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
-        slab: gradient, loss and Adam in one launch.  Returns the losses, float32 [P] on the device.  spec: the agent's
-        AntsPopSpec of this step (its seeds, learning rates and discounts are this trainer's), else one is built."""
-        P = self.n_members
-        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
-        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
-        first = self.step_count == 0
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_pop_lintrain_step(
-                C.byref(self._spec() if spec is None else spec), _p(self.w1), _p(self.b1), _p(self.heads), _p(self.target_l3), _p(self._adam),
-                _p(ring.states), _p(ring.agent_states), _p(ring.actions), _p(ring.rewards), _p(ring.new_states),
-                _p(ring.new_agent_states), _p(ring.dones), ring.max_len, _p(idx), idx.shape[1], self.step_count, self.betas[0],
-                self.betas[1], self.eps, _p(self.grads), _p(loss), _p(self.running_loss), int(first), _lib.stream(self.device)),
-                "pop_lintrain_step")
-        self.last_idx = idx
-        return loss
-
-    def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 264,
-              min_replay: int = 1000, spec=None):
-        """The reference's train for every member at once: 0 below min_replay, else a step on `minibatch` rows per member
-        drawn on the device (one torch.randint of [P, B]), then the target counter (host side) and the sync."""
-        if len(ring) < min_replay:
-            return 0
-        idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
-        loss = self.step(ring, idx, spec)
-        self._count_target(done)
-        return loss
+    def _entry(self, B: int) -> tuple:
+        """One launch; no workspace."""
+        return (self._lib.antsrl_pop_lintrain_step, "pop_lintrain_step",
+                (_p(self.w1), _p(self.b1), _p(self.heads), _p(self.target_l3), _p(self._adam)), ())
 
 
-class PopulationExploreTrainer(_TargetCounter):
+class PopulationExploreTrainer(_PopulationTrainer):
     """ExploreTrainer's tensors with a leading [P], trained by antsrl_pop_exptrain_step: two launches whatever P is.
     model, target, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat block is ExploreTrainer's:
     layer1.weight, layer1.bias, layer2.weight, layer2.bias); member p's weights are initialised as
@@ -255,15 +276,8 @@ class PopulationExploreTrainer(_TargetCounter):
 
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
                  update_target_every: int = 1):
-        self.g, self.device = geometry, torch.device(device)
-        P, F = geometry.P, geometry.n_features
-        self.n_members, self.n_features = P, F
-        self.seeds = [int(s) for s in seeds]
-        self.discount, self.lr = np.asarray(discount, dtype=np.float64).copy(), np.asarray(lr, dtype=np.float64).copy()
-        self.betas, self.eps, self.update_target_every = tuple(float(b) for b in betas), float(eps), int(update_target_every)
-        self.target_update_counter = self.syncs = self.step_count = 0
-        self._lib = _lib.load()
-        IN = F + 2
+        super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
+        P, IN = self.n_members, self.n_features + 2
         self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
                       "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
         self.trained_floats = self._sizes(1)[0]
@@ -273,8 +287,6 @@ class PopulationExploreTrainer(_TargetCounter):
         self.target = self.model.clone()
         self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
         self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.running_loss = torch.zeros((P,), dtype=torch.float64, device=self.device)
-        self.last_idx = None  # the [P, B] indices of the last step
         self._work, self._work_B = None, 0
 
     def _sizes(self, B: int) -> tuple:
@@ -283,10 +295,6 @@ class PopulationExploreTrainer(_TargetCounter):
         _lib.check(self._lib.antsrl_pop_exptrain_sizes(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
                                                        C.byref(ws), C.byref(n)), "pop_exptrain_sizes")
         return tf.value, stride.value, ws.value, n.value
-
-    def _spec(self):
-        """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
-        return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
 
     # ---- weights ------------------------------------------------------------------------------------------------------
     def _views(self, flat) -> dict:
@@ -325,35 +333,15 @@ class PopulationExploreTrainer(_TargetCounter):
             self._work_B = B
         return self._work
 
-    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
-        """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
-        slab: gradient, loss and Adam of both layers in two launches.  Returns the losses, float32 [P] on the device."""
-        P = self.n_members
-        assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
-        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
-        work = self.workspace(idx.shape[1])
-        first = self.step_count == 0
-        self.step_count += 1
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.antsrl_pop_exptrain_step(
-                C.byref(self._spec() if spec is None else spec), _p(self.model), _p(self.target), _p(self._adam[0]), _p(self._adam[1]),
-                _p(ring.states), _p(ring.agent_states), _p(ring.actions), _p(ring.rewards), _p(ring.new_states),
-                _p(ring.new_agent_states), _p(ring.dones), ring.max_len, _p(idx), idx.shape[1], self.step_count, self.betas[0],
-                self.betas[1], self.eps, _p(self.grads), _p(loss), _p(self.running_loss), int(first), _p(work),
-                _lib.stream(self.device)), "pop_exptrain_step")
-        self.last_idx = idx
-        return loss
+    def _entry(self, B: int) -> tuple:
+        """Two launches; behind first_loss goes the workspace for B rows per member."""
+        return (self._lib.antsrl_pop_exptrain_step, "pop_exptrain_step",
+                (_p(self.model), _p(self.target), _p(self._adam[0]), _p(self._adam[1])), (_p(self.workspace(B)),))
 
     def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 256,
               min_replay: int = 1000, spec=None):
-        """The reference's train for every member at once: 0 below min_replay, else a step on `minibatch` rows per member
-        drawn on the device (one torch.randint of [P, B]), then the target counter (host side) and the sync."""
-        if len(ring) < min_replay:
-            return 0
-        idx = torch.randint(0, len(ring), (self.n_members, minibatch), device=self.device, generator=generator)
-        loss = self.step(ring, idx, spec)
-        self._count_target(done)
-        return loss
+        """_PopulationTrainer.train with ExploreAgent's minibatch of 256 as the default."""
+        return super().train(ring, done, generator, minibatch, min_replay, spec)
 
 
 class _Population(_LoopAgent):

@@ -1,0 +1,47 @@
+"""What the CPU-side checks of the two populations' C-ABI entries share (test_population_abi_cpu.py,
+test_population_explore_abi_cpu.py): the fake pointers, the library, an AntsPopSpec from keywords, the call of an entry
+from a dict of defaults, and the arguments the two training entries have in common."""
+import ctypes as C
+
+import pytest
+
+from antsrl_amd import _lib
+from antsrl_amd import build as buildmod
+
+FAKE = C.c_void_p(1 << 20)  # 256-byte aligned; never dereferenced
+ODD = C.c_void_p((1 << 20) + 2)
+ODD4 = C.c_void_p((1 << 20) + 4)
+ODD8 = C.c_void_p((1 << 20) + 8)
+ODD128 = C.c_void_p((1 << 20) + 128)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    buildmod.build_hip()
+    return _lib.load()
+
+
+def spec(**kw):
+    a = dict(P=3, E=6, N=20, base=0, F=294, fmt=1, pitch=0, reserved=0, eps=0.5, lr=1e-3, discount=0.5, seed=7)
+    a.update(kw)
+    s = _lib.AntsPopSpec(a["P"], a["E"], a["N"], a["base"], a["F"], a["fmt"], a["pitch"], a["reserved"])
+    for p in range(max(0, min(a["P"], _lib.POP_MAX))):
+        s.members[p] = _lib.AntsPopMember(a["seed"], a["eps"], a["lr"], a["discount"], 0)
+    return s
+
+
+def call(entry, s, order, defaults, kw):
+    """entry(the spec or NULL, `defaults` updated by `kw` in `order`, a NULL stream)."""
+    a = dict(defaults, **kw)
+    return entry(C.byref(s) if s is not None else None, *[a[n] for n in order], None)
+
+
+#: what follows the net's pointers and the ring's arrays in both training entries, and a valid value of each
+TRAIN_TAIL = dict(n_rows=200, idx=FAKE, B=48, step=1, beta1=0.9, beta2=0.999, eps=1e-8, grads=FAKE, loss=FAKE, running_loss=FAKE,
+                  first=1)
+
+
+def call_train(entry, s, ptrs, kw, **extra):
+    """A training entry: its pointers `ptrs` (all FAKE), TRAIN_TAIL, then `extra` (the explore step's workspace)."""
+    defaults = dict({n: FAKE for n in ptrs}, **TRAIN_TAIL, **extra)
+    return call(entry, s, ptrs + tuple(TRAIN_TAIL) + tuple(extra), defaults, kw)

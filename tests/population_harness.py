@@ -1,6 +1,8 @@
-"""What the device tests of the population share (test_gpu_population.py): the two shapes of the acceptance test, the
-environment a population acts in with the shard handles of its members, and the comparison itself — a PopulationAgent's
-fused loop against every member run ALONE on a shard handle of its own environments, driven entry by entry as
+"""What the device tests of the two populations share (test_gpu_population.py, test_gpu_population_explore.py): the
+environment a population acts in with the shard handles of its members, a description of each kind (COLLECT:
+PopulationAgent against LinearTrainer; EXPLORE: PopulationExploreAgent against ExploreTrainer and its LinearPolicy without
+a pheromone head) with the two shapes of its acceptance test, and the comparison itself — a population's fused loop
+against every member run ALONE on a shard handle of its own environments, driven entry by entry as
 agent_harness.drive_loop drives an agent.  torch is imported inside the functions, as in the GPU test files."""
 from types import SimpleNamespace
 
@@ -9,17 +11,19 @@ import numpy as np
 from agent_harness import ptr, same_rings, stream
 
 F = 294  # 7 x 7 x 6 observations
+RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 
-#: the acceptance test's two shapes.  (a): 40 ants per member, so its second tile has 8 rows; members 0 and 2 share a seed
-#: and must still differ through their environment ids; B = 48 is one whole tile and half of one; 40 rows per step wrap
-#: the 200-row ring in step 5.  (b): B = 264 is the reference's nine tiles; K = 24 is the stratified sample, and 24 rows
-#: per step wrap the 300-row ring at step 13.  max_time 8 gives an episode end and a target sync inside either run.
-SHAPES = dict(
-    a=dict(P=3, Em=2, N=20, bf16=True, epsilon=(0.0, 0.5, 1.0), lr=(1e-3, 1e-4, 3e-3), discount=(0.5, 0.99, 0.9),
-           seed=(7, 8, 7), K=None, ring=200, min_replay=80, B=48, max_time=8, steps=14, slice_bytes=23520),
-    b=dict(P=2, Em=1, N=32, bf16=False, epsilon=(0.5, 0.5), lr=(1e-3, 1e-3), discount=(0.5, 0.99), seed=(7, 9), K=24,
-           ring=300, min_replay=48, B=264, max_time=8, steps=18, slice_bytes=37632),
-)
+#: the acceptance tests' two shapes.  (a): 40 ants per member, so its second tile has 8 rows, bfloat16 on the cell-meta
+#: path; members 0 and 2 share a seed and must still differ through their environment ids; B = 48 is one whole tile and
+#: half of one (ONE forward workgroup of the explore step); 40 rows per step wrap the 200-row ring in step 5.  (b):
+#: float32; K = 24 is the stratified sample, and 24 rows per step wrap the 300-row ring at step 13.  Its B is the kind's:
+#: 264 is the reference's nine tiles; 136 is five tiles, so an explore member has TWO forward workgroups, the second with
+#: one tile of 8 valid rows, and the layer1 stage adds their partials in workgroup order.  max_time 8 gives an episode end
+#: and a target sync inside either run.  slice_bytes (collect): a member's observation slice, asserted in run_population.
+_A = dict(P=3, Em=2, N=20, bf16=True, epsilon=(0.0, 0.5, 1.0), lr=(1e-3, 1e-4, 3e-3), discount=(0.5, 0.99, 0.9),
+          seed=(7, 8, 7), K=None, ring=200, min_replay=80, B=48, max_time=8, steps=14)
+_B = dict(P=2, Em=1, N=32, bf16=False, epsilon=(0.5, 0.5), lr=(1e-3, 1e-3), discount=(0.5, 0.99), seed=(7, 9), K=24,
+          ring=300, min_replay=48, max_time=8, steps=18)
 
 
 def members_of(s):
@@ -52,108 +56,163 @@ def make_envs(P, Em, N, max_time, bf16, init_seed=5):
     return whole, shards
 
 
-def run_population(s):
-    """s: one of SHAPES.  The population's `steps` rollout_steps under a sync debug mode that makes any read-back an
-    error; returns the agent, its environment and per step (device copies) rot, ph, explored, reward, the loss (a [P]
-    tensor, or 0) and the [P, B] minibatch indices (None while it does not train)."""
-    import torch
-    from antsrl_amd.population import PopulationAgent
-    whole, shards = make_envs(s["P"], s["Em"], s["N"], s["max_time"], s["bf16"])
-    assert s["Em"] * s["N"] * F * (2 if s["bf16"] else 4) == s["slice_bytes"] and s["slice_bytes"] % 16 == 0
-    pop = PopulationAgent(members_of(s), record_per_step=s["K"], replay_size=s["ring"], minibatch=s["B"],
-                          min_replay=s["min_replay"], update_target_every=1, seed=3)
-    pop.setup(whole)
-    pop.initialize(whole)
-    whole.observe()
-    torch.cuda.synchronize()
-    torch.cuda.set_sync_debug_mode("error")  # the fused loop reads nothing back
-    log = []
-    try:
-        for t in range(s["steps"]):
-            before = pop.trainer.step_count
-            loss = pop.rollout_step(whole)
-            trained = pop.trainer.step_count != before
-            log.append(SimpleNamespace(rot=pop._rot.clone(), ph=pop._ph.clone(), explored=pop._explored.clone(),
-                                       reward=whole.reward.clone(), loss=loss, idx=pop.trainer.last_idx if trained else None))
-    finally:
-        torch.cuda.set_sync_debug_mode(0)
-    return SimpleNamespace(pop=pop, env=whole, shards=shards, log=log)
+class Kind:
+    """One kind of population.  population / single: the names of its agent class (antsrl_amd.population) and of the
+    single agent's trainer (antsrl_amd.train); pheromone: whether the net has that head; final: the trainer tensor a
+    run's `final` keeps a copy of; tensors(t, p, tr) -> the (name, member p's tensor of the population trainer t, the lone
+    trainer tr's) that same_trainers compares."""
+
+    make_envs, members_of = staticmethod(make_envs), staticmethod(members_of)
+
+    def __init__(self, population, single, pheromone, final, SHAPES, tensors):
+        self.population, self.single, self.pheromone, self.final, self.SHAPES, self.tensors = population, single, pheromone, final, SHAPES, tensors
+        self._runs = {}
+
+    def run_population(self, s):
+        """s: one of SHAPES.  The population's `steps` rollout_steps under a sync debug mode that makes any read-back an
+        error; returns the agent, its environment and per step (device copies) rot, ph, explored, reward, the loss (a
+        [P] tensor, or 0) and the [P, B] minibatch indices (None while it does not train)."""
+        import torch
+        from antsrl_amd import population
+        whole, shards = make_envs(s["P"], s["Em"], s["N"], s["max_time"], s["bf16"])
+        if "slice_bytes" in s:
+            assert s["Em"] * s["N"] * F * (2 if s["bf16"] else 4) == s["slice_bytes"] and s["slice_bytes"] % 16 == 0
+        assert (s["Em"] * s["N"] * F * (2 if s["bf16"] else 4)) % 16 == 0  # the acting kernel's alignment rule
+        pop = getattr(population, self.population)(members_of(s), record_per_step=s["K"], replay_size=s["ring"], minibatch=s["B"],
+                                                   min_replay=s["min_replay"], update_target_every=1, seed=3)
+        pop.setup(whole)
+        pop.initialize(whole)
+        whole.observe()
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("error")  # the fused loop reads nothing back
+        log = []
+        try:
+            for t in range(s["steps"]):
+                before = pop.trainer.step_count
+                loss = pop.rollout_step(whole)
+                trained = pop.trainer.step_count != before
+                log.append(SimpleNamespace(rot=pop._rot.clone(), ph=pop._ph.clone(), explored=pop._explored.clone(),
+                                           reward=whole.reward.clone(), loss=loss, idx=pop.trainer.last_idx if trained else None))
+        finally:
+            torch.cuda.set_sync_debug_mode(0)
+        return SimpleNamespace(pop=pop, env=whole, shards=shards, log=log)
+
+    def run_member_alone(self, s, p, run):
+        """Member p alone on its shard handle, entry by entry: the single trainer (seed, lr, discount of the member) and
+        its acting policy, antsrl_agent_select_actions, record_pre, step_update, record_post (the last three without a
+        pheromone for a net that has none), then train_on the population's own indices once fill >= min_replay.  After
+        every step rot, ph (with that head) and explored of the member's slice, env.reward of its rows and loss[p] are
+        equal; returns the member's trainer and ring."""
+        import torch
+        from antsrl_amd import _lib, train
+        from antsrl_amd import config as cm
+        from antsrl_amd.replay import DeviceReplayMemory
+        lib = _lib.load()
+        Em, N = s["Em"], s["N"]
+        Mm, env = Em * N, run.shards[p]
+        seed, eps = s["seed"][p], s["epsilon"][p]
+        tr = getattr(train, self.single)(F, env.device, discount=s["discount"][p], lr=s["lr"][p], update_target_every=1, seed=seed)
+        rm = DeviceReplayMemory(s["ring"], (7, 7, 6), [2], [2], device=env.device)
+        env.set_activation(torch.full((Em, N, env.cfg.n_phero), 10.0, device=env.device))
+        env.observe()
+        explored = torch.zeros((Em,), dtype=torch.uint8, device=env.device)
+        unread = torch.zeros((Mm,), dtype=torch.int8, device=env.device)  # without the head, select draws a pheromone that nothing reads
+        rows, envs = slice(p * Mm, (p + 1) * Mm), slice(p * Em, (p + 1) * Em)
+        for t, want in enumerate(run.log):
+            obs, ast = env.obs, env.agent_state
+            rot, ph = tr.policy.act(obs, ast, env=env)
+            rot = rot.reshape(-1).clone()
+            if self.pheromone:
+                ph = ph.reshape(-1).clone()
+            else:
+                none = ph
+                assert none is None
+            drawn = ph if self.pheromone else unread
+            _lib.check(lib.antsrl_agent_select_actions(seed, t, p * Em, Em, N, eps, 3, 3, ptr(rot), ptr(drawn), ptr(explored), stream()))
+            assert torch.equal(rot, want.rot[rows]), ("rot", p, t)
+            if self.pheromone:
+                assert torch.equal(ph, want.ph[rows]), ("ph", p, t)
+            assert torch.equal(explored, want.explored[envs]), ("explored", p, t)
+            rm.record_pre(obs, ast, None, rot, ph, n_envs=Em, n_ants=N, k=s["K"], seed=seed, step=t, env_id_base=p * Em)
+            done = env.query(cm.Q_TIMESTEP) == s["max_time"]
+            env.step_update(rot.view(Em, N), ph.view(Em, N) if self.pheromone else None)
+            rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
+            assert torch.equal(env.reward.view(-1), want.reward.view(-1)[rows]), ("reward", p, t)
+            if rm.fill >= s["min_replay"]:
+                assert want.idx is not None, ("the population did not train at step", t)
+                loss = tr.train_on(rm, want.idx[p], done)
+                assert torch.equal(loss, want.loss[p]), ("loss", p, t, float(loss), float(want.loss[p]))
+            else:
+                assert want.idx is None and not torch.is_tensor(want.loss) and want.loss == 0, ("the population trained at step", t)
+        return tr, rm
+
+    def same_trainers(self, t, p, tr):
+        """Member p's weights, target, Adam's moments and gradients in the population trainer `t` are the lone trainer
+        `tr`'s, and so are the dicts made of them."""
+        import torch
+        for name, mine, alone in self.tensors(t, p, tr):
+            assert torch.equal(mine, alone), (name, p)
+        sd, alone_sd = t.state_dict(p), tr.state_dict()
+        assert list(sd) == list(alone_sd) and all(torch.equal(sd[k], alone_sd[k]) for k in sd)
+        td, alone_td = t.target_state_dict(p), tr.target_state_dict()
+        assert list(td) == list(alone_td) and all(torch.equal(td[k], alone_td[k]) for k in td)
+        ad, alone_ad = t.adam_state(p), tr.adam_state()
+        assert ad["step"] == alone_ad["step"] and all(torch.equal(ad[m][k], alone_ad[m][k]) for m in ("exp_avg", "exp_avg_sq") for k in ad[m])
+
+    def same_member(self, pop, p, tr, rm):
+        """At the end: all seven ring tensors with head and fill, the weights, the target, Adam's moments, the gradients
+        and the counters of member p are its lone run's."""
+        same_rings(pop.replay_memory.member(p), rm)
+        t = pop.trainer
+        self.same_trainers(t, p, tr)
+        assert (t.step_count, t.syncs) == (tr.step_count, tr.syncs), ((t.step_count, t.syncs), (tr.step_count, tr.syncs))
+
+    def checked_run(self, name):
+        """The run of SHAPES[name] with every member checked against its lone run, once per session and kind (the
+        hand-over test reads the explore shape (b)'s population, test_copy_member goes on with shape (a)'s)."""
+        if name not in self._runs:
+            s = self.SHAPES[name]
+            run = self.run_population(s)
+            for p in range(s["P"]):
+                tr, rm = self.run_member_alone(s, p, run)
+                self.same_member(run.pop, p, tr, rm)
+            t, ring = run.pop.trainer, run.pop.replay_memory  # as the run left them (test_copy_member goes on with the agent)
+            run.final = SimpleNamespace(step_count=t.step_count, syncs=t.syncs, fill=ring.fill, head=ring.head,
+                                        **{self.final: getattr(t, self.final).clone()})
+            self._runs[name] = run
+        return self._runs[name]
+
+    def check_copy_member(self, weights, theirs):
+        """copy_member on shape (a)'s population after its comparison.  weights(p) -> copies of member p's weights, target
+        and Adam's moments; theirs: the test's words for "these are member 0's"."""
+        import torch
+        run = self.checked_run("a")
+        pop = run.pop
+        rm = pop.replay_memory
+        slab = lambda p: [getattr(rm, n)[p].clone() for n in RING]  # noqa: E731
+        before_w, before_s = [weights(p) for p in range(3)], [slab(p) for p in range(3)]
+        assert not all(torch.equal(a, b) for a, b in zip(before_s[0], before_s[2]))
+        pop.copy_member(0, 2, ring=False)
+        assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0])), theirs
+        assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[2])), "with ring=False the slab stays"
+        pop.copy_member(0, 2)
+        assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0]))
+        assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[0])), "the ring slab is member 0's"
+        for p in (0, 1):
+            assert all(torch.equal(a, b) for a, b in zip(weights(p), before_w[p])), "member %d changed" % p
+            assert all(torch.equal(a, b) for a, b in zip(slab(p), before_s[p])), "member %d's slab changed" % p
+        assert list(pop.epsilon) == [0.0, 0.5, 1.0]  # the hyper-parameters stay the member's own
+        # the population still steps: member 2 now trains member 0's weights on member 0's rows, under its own hyper-parameters
+        loss = pop.rollout_step(run.env)
+        assert loss.shape == (3,) and bool(torch.isfinite(loss).all())
 
 
-def run_member_alone(s, p, run):
-    """Member p alone on its shard handle, entry by entry: LinearTrainer(seed, lr, discount of the member),
-    antsrl_agent_select_actions, record_pre, step_update, record_post, then train_on the population's own indices once
-    fill >= min_replay.  After every step rot, ph and explored of the member's slice, env.reward of its rows and loss[p]
-    are equal; returns the member's trainer and ring."""
-    import torch
-    from antsrl_amd import _lib
-    from antsrl_amd import config as cm
-    from antsrl_amd.replay import DeviceReplayMemory
-    from antsrl_amd.train import LinearTrainer
-    lib = _lib.load()
-    Em, N = s["Em"], s["N"]
-    Mm, env = Em * N, run.shards[p]
-    seed, eps = s["seed"][p], s["epsilon"][p]
-    tr = LinearTrainer(F, env.device, discount=s["discount"][p], lr=s["lr"][p], update_target_every=1, seed=seed)
-    rm = DeviceReplayMemory(s["ring"], (7, 7, 6), [2], [2], device=env.device)
-    env.set_activation(torch.full((Em, N, env.cfg.n_phero), 10.0, device=env.device))
-    env.observe()
-    explored = torch.zeros((Em,), dtype=torch.uint8, device=env.device)
-    rows, envs = slice(p * Mm, (p + 1) * Mm), slice(p * Em, (p + 1) * Em)
-    for t, want in enumerate(run.log):
-        obs, ast = env.obs, env.agent_state
-        rot, ph = tr.policy.act(obs, ast, env=env)
-        rot, ph = rot.reshape(-1).clone(), ph.reshape(-1).clone()
-        _lib.check(lib.antsrl_agent_select_actions(seed, t, p * Em, Em, N, eps, 3, 3, ptr(rot), ptr(ph), ptr(explored), stream()))
-        assert torch.equal(rot, want.rot[rows]), ("rot", p, t)
-        assert torch.equal(ph, want.ph[rows]), ("ph", p, t)
-        assert torch.equal(explored, want.explored[envs]), ("explored", p, t)
-        rm.record_pre(obs, ast, None, rot, ph, n_envs=Em, n_ants=N, k=s["K"], seed=seed, step=t, env_id_base=p * Em)
-        done = env.query(cm.Q_TIMESTEP) == s["max_time"]
-        env.step_update(rot.view(Em, N), ph.view(Em, N))
-        rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
-        assert torch.equal(env.reward.view(-1), want.reward.view(-1)[rows]), ("reward", p, t)
-        if rm.fill >= s["min_replay"]:
-            assert want.idx is not None, ("the population did not train at step", t)
-            loss = tr.train_on(rm, want.idx[p], done)
-            assert torch.equal(loss, want.loss[p]), ("loss", p, t, float(loss), float(want.loss[p]))
-        else:
-            assert want.idx is None and not torch.is_tensor(want.loss) and want.loss == 0, ("the population trained at step", t)
-    return tr, rm
-
-
-def same_member(pop, p, tr, rm):
-    """At the end: all seven ring tensors with head and fill, heads, target_l3, Adam's moments, the gradients and the step
-    count of member p are its lone run's."""
-    import torch
-    same_rings(pop.replay_memory.member(p), rm)
-    t = pop.trainer
-    for name, mine, alone in (("w1", t.w1[p], tr.policy.w1), ("b1", t.b1[p], tr.policy.b1), ("heads", t.heads[p], tr.heads),
-                              ("target_l3", t.target_l3[p], tr.target_l3), ("adam", t._adam[p], tr._adam),
-                              ("grads", t.grads[p], tr.grads)):
-        assert torch.equal(mine, alone), (name, p)
-    assert (t.step_count, t.syncs) == (tr.step_count, tr.syncs), ((t.step_count, t.syncs), (tr.step_count, tr.syncs))
-    sd, alone_sd = t.state_dict(p), tr.state_dict()
-    assert list(sd) == list(alone_sd) and all(torch.equal(sd[k], alone_sd[k]) for k in sd)
-    td, alone_td = t.target_state_dict(p), tr.target_state_dict()
-    assert all(torch.equal(td[k], alone_td[k]) for k in td)
-    ad, alone_ad = t.adam_state(p), tr.adam_state()
-    assert ad["step"] == alone_ad["step"] and all(torch.equal(ad[m][k], alone_ad[m][k]) for m in ("exp_avg", "exp_avg_sq") for k in ad[m])
-
-
-_RUNS = {}
-
-
-def checked_run(name):
-    """The run of SHAPES[name] with every member checked against its lone run, once per session (test_copy_member works on
-    shape (a)'s population after the comparison has been made)."""
-    if name not in _RUNS:
-        s = SHAPES[name]
-        run = run_population(s)
-        for p in range(s["P"]):
-            tr, rm = run_member_alone(s, p, run)
-            same_member(run.pop, p, tr, rm)
-        t, ring = run.pop.trainer, run.pop.replay_memory  # as the run left them (test_copy_member goes on with the agent)
-        run.final = SimpleNamespace(heads=t.heads.clone(), step_count=t.step_count, syncs=t.syncs, fill=ring.fill, head=ring.head)
-        _RUNS[name] = run
-    return _RUNS[name]
+COLLECT = Kind("PopulationAgent", "LinearTrainer", True, "heads",
+               dict(a=dict(_A, slice_bytes=23520), b=dict(_B, B=264, slice_bytes=37632)),
+               lambda t, p, tr: (("w1", t.w1[p], tr.policy.w1), ("b1", t.b1[p], tr.policy.b1), ("heads", t.heads[p], tr.heads),
+                                 ("target_l3", t.target_l3[p], tr.target_l3), ("adam", t._adam[p], tr._adam),
+                                 ("grads", t.grads[p], tr.grads)))
+EXPLORE = Kind("PopulationExploreAgent", "ExploreTrainer", False, "model", dict(a=_A, b=dict(_B, B=136)),
+               lambda t, p, tr: (("model", t.model[p], tr.model), ("target", t.target[p], tr.target),
+                                 ("adam m", t._adam[0, p], tr._adam[0]), ("adam v", t._adam[1, p], tr._adam[1]),
+                                 ("grads", t.grads[p], tr.grads)))

@@ -9,7 +9,7 @@
 import numpy as np
 import pytest
 
-import population_harness as H
+from population_harness import COLLECT as H
 
 pytestmark = pytest.mark.gpu
 
@@ -40,29 +40,9 @@ def test_the_population_equals_its_members(name):
 
 
 def test_copy_member():
-    import torch
-    pop = H.checked_run("a").pop
-    tr, rm = pop.trainer, pop.replay_memory
+    tr = H.checked_run("a").pop.trainer
     weights = lambda p: [t[p].clone() for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam)]  # noqa: E731
-    slab = lambda p: [getattr(rm, n)[p].clone() for n in H_RING]  # noqa: E731
-    before_w, before_s = [weights(p) for p in range(3)], [slab(p) for p in range(3)]
-    assert not all(torch.equal(a, b) for a, b in zip(before_s[0], before_s[2]))
-    pop.copy_member(0, 2, ring=False)
-    assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0])), "weights, target and Adam are member 0's"
-    assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[2])), "with ring=False the slab stays"
-    pop.copy_member(0, 2)
-    assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0]))
-    assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[0])), "the ring slab is member 0's"
-    for p in (0, 1):
-        assert all(torch.equal(a, b) for a, b in zip(weights(p), before_w[p])), "member %d changed" % p
-        assert all(torch.equal(a, b) for a, b in zip(slab(p), before_s[p])), "member %d's slab changed" % p
-    assert list(pop.epsilon) == [0.0, 0.5, 1.0]  # the hyper-parameters stay the member's own
-    # the population still steps: member 2 now trains member 0's weights on member 0's rows, under its own hyper-parameters
-    loss = pop.rollout_step(H.checked_run("a").env)
-    assert loss.shape == (3,) and bool(torch.isfinite(loss).all())
-
-
-H_RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
+    H.check_copy_member(weights, "weights, target and Adam are member 0's")  # the assertions are the harness's
 
 
 def test_train_population(monkeypatch):

@@ -4,7 +4,7 @@ of explore agents") on the device.
 1. The population equals its members: member p is, bit for bit, an ExploreAgent's entries run alone on a shard handle of
    its Em environments with the member's own seed, epsilon, discount and learning rate — actions, explored flags,
    rewards and loss after every step; the ring, the model and target blocks, Adam's moments, gradients and counters at the
-   end (population_explore_harness.py holds the two shapes and the comparison).
+   end (population_harness.py holds the two shapes and the comparison).
 2. The step alone: PopulationExploreTrainer.step against P ExploreTrainer.steps on the same synthetic rows, over the
    widths and minibatches at which the kernels take another path; the running loss; equal bits for equal inputs; the
    members' parts of the workspace.
@@ -15,11 +15,10 @@ of explore agents") on the device.
 import numpy as np
 import pytest
 
-import population_explore_harness as H
+from population_harness import EXPLORE as H
+from population_harness import RING
 
 pytestmark = pytest.mark.gpu
-
-RING = ("states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
 
 
 @pytest.mark.parametrize("name", ["a", "b"])
@@ -227,27 +226,11 @@ def test_hand_over(tmp_path):
 # ---- 5. copy_member
 def test_copy_member():
     import torch
-    run = H.checked_run("a")
-    pop = run.pop
-    tr, rm = pop.trainer, pop.replay_memory
+    tr = H.checked_run("a").pop.trainer
     weights = lambda p: [t.clone() for t in (tr.model[p], tr.target[p], tr._adam[:, p])]  # noqa: E731
-    slab = lambda p: [getattr(rm, n)[p].clone() for n in RING]  # noqa: E731
-    before_w, before_s = [weights(p) for p in range(3)], [slab(p) for p in range(3)]
-    assert not all(torch.equal(a, b) for a, b in zip(before_s[0], before_s[2]))
+    before_w = [weights(p) for p in range(3)]
     assert not torch.equal(before_w[0][0], before_w[2][0])
-    pop.copy_member(0, 2, ring=False)
-    assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0])), "model, target and Adam are member 0's"
-    assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[2])), "with ring=False the slab stays"
-    pop.copy_member(0, 2)
-    assert all(torch.equal(a, b) for a, b in zip(weights(2), before_w[0]))
-    assert all(torch.equal(a, b) for a, b in zip(slab(2), before_s[0])), "the ring slab is member 0's"
-    for p in (0, 1):
-        assert all(torch.equal(a, b) for a, b in zip(weights(p), before_w[p])), "member %d changed" % p
-        assert all(torch.equal(a, b) for a, b in zip(slab(p), before_s[p])), "member %d's slab changed" % p
-    assert list(pop.epsilon) == [0.0, 0.5, 1.0]  # the hyper-parameters stay the member's own
-    # the population still steps: member 2 now trains member 0's weights on member 0's rows, under its own hyper-parameters
-    loss = pop.rollout_step(run.env)
-    assert loss.shape == (3,) and bool(torch.isfinite(loss).all())
+    H.check_copy_member(weights, "model, target and Adam are member 0's")  # the other assertions are the harness's
 
 
 # ---- 6. the curriculum

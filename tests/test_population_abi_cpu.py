@@ -7,19 +7,9 @@ import ctypes as C
 import pytest
 
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
+from population_abi import FAKE, ODD, ODD4, ODD8, call, call_train, lib, spec  # noqa: F401 (lib is a fixture)
 
 NEW = ("antsrl_pop_policy", "antsrl_pop_select", "antsrl_pop_record_pre", "antsrl_pop_record_post", "antsrl_pop_lintrain_step")
-FAKE = C.c_void_p(1 << 20)
-ODD = C.c_void_p((1 << 20) + 2)
-ODD4 = C.c_void_p((1 << 20) + 4)
-ODD8 = C.c_void_p((1 << 20) + 8)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported(lib):
@@ -32,57 +22,35 @@ def test_new_symbols_are_exported(lib):
     assert C.sizeof(_lib.AntsPopMember) == 32 and C.sizeof(_lib.AntsPopSpec) == 32 + 64 * 32
 
 
-def spec(**kw):
-    a = dict(P=3, E=6, N=20, base=0, F=294, fmt=1, pitch=0, reserved=0, eps=0.5, lr=1e-3, discount=0.5, seed=7)
-    a.update(kw)
-    s = _lib.AntsPopSpec(a["P"], a["E"], a["N"], a["base"], a["F"], a["fmt"], a["pitch"], a["reserved"])
-    for p in range(max(0, min(a["P"], _lib.POP_MAX))):
-        s.members[p] = _lib.AntsPopMember(a["seed"], a["eps"], a["lr"], a["discount"], 0)
-    return s
-
-
-def policy(lib, s, **kw):
-    a = dict(obs=FAKE, agent_state=FAKE, w1=FAKE, b1=FAKE, heads=FAKE, target_l3=FAKE, rotation=FAKE, pheromone=FAKE)
-    a.update(kw)
-    return lib.antsrl_pop_policy(C.byref(s) if s is not None else None, *[a[n] for n in POLICY_PTRS], None)
-
-
-def select(lib, s, **kw):
-    a = dict(step=0, rotation=FAKE, pheromone=FAKE, explored=None)
-    a.update(kw)
-    return lib.antsrl_pop_select(C.byref(s) if s is not None else None, a["step"], a["rotation"], a["pheromone"], a["explored"], None)
-
-
-def pre(lib, s, **kw):
-    a = dict(step=0, K=40, head=0, max_len=200, obs=FAKE, agent_state=FAKE, rotation=FAKE, pheromone=FAKE, states=FAKE,
-             agent_states=FAKE, actions=FAKE)
-    a.update(kw)
-    return lib.antsrl_pop_record_pre(C.byref(s) if s is not None else None, a["step"], a["K"], a["head"], a["max_len"],
-                                     *[a[n] for n in PRE_PTRS], None)
-
-
-def post(lib, s, **kw):
-    a = dict(step=0, K=40, head=0, max_len=200, obs=FAKE, agent_state=FAKE, reward=FAKE, done=FAKE, rewards=FAKE,
-             new_states=FAKE, new_agent_states=FAKE, dones=FAKE)
-    a.update(kw)
-    return lib.antsrl_pop_record_post(C.byref(s) if s is not None else None, a["step"], a["K"], a["head"], a["max_len"],
-                                      *[a[n] for n in POST_PTRS], None)
-
-
-def train(lib, s, **kw):
-    a = {n: FAKE for n in TRAIN_PTRS}
-    a.update(n_rows=200, idx=FAKE, B=48, step=1, beta1=0.9, beta2=0.999, eps=1e-8, grads=FAKE, loss=FAKE, running_loss=FAKE, first=1)
-    a.update(kw)
-    return lib.antsrl_pop_lintrain_step(C.byref(s) if s is not None else None, *[a[n] for n in TRAIN_PTRS], a["n_rows"], a["idx"],
-                                        a["B"], a["step"], a["beta1"], a["beta2"], a["eps"], a["grads"], a["loss"],
-                                        a["running_loss"], a["first"], None)
-
-
 POLICY_PTRS = ("obs", "agent_state", "w1", "b1", "heads", "target_l3", "rotation", "pheromone")
 PRE_PTRS = ("obs", "agent_state", "rotation", "pheromone", "states", "agent_states", "actions")
 POST_PTRS = ("obs", "agent_state", "reward", "done", "rewards", "new_states", "new_agent_states", "dones")
 TRAIN_PTRS = ("w1", "b1", "heads", "target_l3", "adam", "states", "agent_states", "actions", "rewards", "new_states",
               "new_agent_states", "dones")
+RING_ROWS = dict(step=0, K=40, head=0, max_len=200)  # what leads a record entry's arguments
+
+
+def policy(lib, s, **kw):
+    return call(lib.antsrl_pop_policy, s, POLICY_PTRS, {n: FAKE for n in POLICY_PTRS}, kw)
+
+
+def select(lib, s, **kw):
+    return call(lib.antsrl_pop_select, s, ("step", "rotation", "pheromone", "explored"),
+                dict(step=0, rotation=FAKE, pheromone=FAKE, explored=None), kw)
+
+
+def pre(lib, s, **kw):
+    return call(lib.antsrl_pop_record_pre, s, tuple(RING_ROWS) + PRE_PTRS, dict(RING_ROWS, **{n: FAKE for n in PRE_PTRS}), kw)
+
+
+def post(lib, s, **kw):
+    return call(lib.antsrl_pop_record_post, s, tuple(RING_ROWS) + POST_PTRS, dict(RING_ROWS, **{n: FAKE for n in POST_PTRS}), kw)
+
+
+def train(lib, s, **kw):
+    return call_train(lib.antsrl_pop_lintrain_step, s, TRAIN_PTRS, kw)
+
+
 ENTRIES = ((policy, b"pop_policy"), (select, b"pop_select"), (pre, b"pop_record_pre"), (post, b"pop_record_post"),
            (train, b"pop_lintrain_step"))
 

@@ -7,20 +7,9 @@ import ctypes as C
 import pytest
 
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
+from population_abi import FAKE, ODD, ODD4, ODD8, ODD128, call, call_train, lib, spec  # noqa: F401 (lib is a fixture)
 
 NEW = ("antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes", "antsrl_pop_exptrain_step")
-FAKE = C.c_void_p(1 << 20)  # 256-byte aligned
-ODD = C.c_void_p((1 << 20) + 2)
-ODD4 = C.c_void_p((1 << 20) + 4)
-ODD8 = C.c_void_p((1 << 20) + 8)
-ODD128 = C.c_void_p((1 << 20) + 128)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported(lib):
@@ -29,34 +18,17 @@ def test_new_symbols_are_exported(lib):
     assert lib.antsrl_abi_version() == 5  # the entries are additive
 
 
-def spec(**kw):
-    a = dict(P=3, E=6, N=20, base=0, F=294, fmt=1, pitch=0, reserved=0, eps=0.5, lr=1e-3, discount=0.5, seed=7)
-    a.update(kw)
-    s = _lib.AntsPopSpec(a["P"], a["E"], a["N"], a["base"], a["F"], a["fmt"], a["pitch"], a["reserved"])
-    for p in range(max(0, min(a["P"], _lib.POP_MAX))):
-        s.members[p] = _lib.AntsPopMember(a["seed"], a["eps"], a["lr"], a["discount"], 0)
-    return s
-
-
 POLICY_PTRS = ("obs", "agent_state", "target_blocks", "rotation")
 TRAIN_PTRS = ("model", "target", "adam_m", "adam_v", "states", "agent_states", "actions", "rewards", "new_states",
               "new_agent_states", "dones")
 
 
 def policy(lib, s, **kw):
-    a = {n: FAKE for n in POLICY_PTRS}
-    a.update(kw)
-    return lib.antsrl_pop_explore_policy(C.byref(s) if s is not None else None, *[a[n] for n in POLICY_PTRS], None)
+    return call(lib.antsrl_pop_explore_policy, s, POLICY_PTRS, {n: FAKE for n in POLICY_PTRS}, kw)
 
 
 def train(lib, s, **kw):
-    a = {n: FAKE for n in TRAIN_PTRS}
-    a.update(n_rows=200, idx=FAKE, B=48, step=1, beta1=0.9, beta2=0.999, eps=1e-8, grads=FAKE, loss=FAKE, running_loss=FAKE,
-             first=1, workspace=FAKE)
-    a.update(kw)
-    return lib.antsrl_pop_exptrain_step(C.byref(s) if s is not None else None, *[a[n] for n in TRAIN_PTRS], a["n_rows"], a["idx"],
-                                        a["B"], a["step"], a["beta1"], a["beta2"], a["eps"], a["grads"], a["loss"],
-                                        a["running_loss"], a["first"], a["workspace"], None)
+    return call_train(lib.antsrl_pop_exptrain_step, s, TRAIN_PTRS, kw, workspace=FAKE)
 
 
 def sizes(lib, F, B, P):
