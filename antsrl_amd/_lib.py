@@ -10,10 +10,9 @@ from .config import AntsCfg, AntsGen, AntsInit
 LIB_PATH = os.environ.get("ANTSRL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                         "libantsrl_hip.so")  # ANTSRL_LIB: A/B builds
 
-#: every symbol include/antsrl.h declares (but antsrl_workspace_bytes2 and antsrl_create2: the list holds the names of
-#: letters and underscores, as tests/test_abi_cpu.py reads them off the header; load() binds those two by name all the same)
+#: every symbol include/antsrl.h declares
 EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl_workspace_bytes", "antsrl_create",
-           "antsrl_workspace_map",
+           "antsrl_workspace_bytes2", "antsrl_create2", "antsrl_workspace_map",
            "antsrl_destroy", "antsrl_reset", "antsrl_generate", "antsrl_step", "antsrl_observe", "antsrl_update", "antsrl_flush",
            "antsrl_step_update", "antsrl_set_timing_events", "antsrl_set_activation", "antsrl_policy_mlp", "antsrl_read_state", "antsrl_state_bytes",
            "antsrl_set_obs_format", "antsrl_query", "antsrl_bench_copy", "antsrl_set_inloop_policy", "antsrl_set_obs_row_stride", "antsrl_set_perceive_path", "antsrl_refresh_explored_summary", "antsrl_mem_alloc", "antsrl_mem_free",
@@ -137,6 +136,7 @@ def load() -> C.CDLL:
     lib.antsrl_policy_mlp.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.antsrl_read_state.argtypes = [vp, i32, vp, vp]
     lib.antsrl_state_bytes.argtypes = [vp, i32, C.POINTER(C.c_size_t)]
+    lib.antsrl_set_obs_format.argtypes = [vp, i32]
     lib.antsrl_query.argtypes = [vp, i32, C.POINTER(C.c_longlong)]
     lib.antsrl_set_inloop_policy.argtypes = [vp, i32] + [vp] * 9
     lib.antsrl_bench_copy.argtypes = [vp, vp, C.c_size_t, vp]
@@ -173,32 +173,23 @@ def load() -> C.CDLL:
     lib.antsrl_agent_select_actions.argtypes = [C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp]
     lib.antsrl_replay_record_pre_plain.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 8
     lib.antsrl_replay_record_post_plain.argtypes = [C.POINTER(AntsRecordSpec)] + [vp] * 9
-    lib.antsrl_lintrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
-    lib.antsrl_lintrain_grad.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
-    lib.antsrl_lintrain_apply.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.antsrl_lintrain_step.argtypes = [i32] + [vp] * 13 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
-                                                             C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    lib.antsrl_exptrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
-    lib.antsrl_exptrain_grad.argtypes = [i32] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
-    lib.antsrl_exptrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.antsrl_exptrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
-                                                             C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
-    lib.antsrl_jointtrain_sizes.argtypes = [i32, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
-    lib.antsrl_jointtrain_grad.argtypes = [i32] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
-    lib.antsrl_jointtrain_apply.argtypes = [i32, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.antsrl_jointtrain_step.argtypes = [i32] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
-                                                               C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
     lib.antsrl_rework_collapsed_bytes.argtypes = [C.POINTER(AntsReworkShape), sz]
     lib.antsrl_rework_collapse.argtypes = [C.POINTER(AntsReworkShape), C.POINTER(vp), vp, vp]
     lib.antsrl_policy_rework.argtypes = [C.POINTER(AntsReworkShape), vp, vp, i32, vp, C.c_int64, vp, vp, vp, vp]
     rs = C.POINTER(AntsReworkShape)
     lib.antsrl_policy_rework_select.argtypes = [rs, vp, vp, i32, vp, C.c_uint64, C.c_uint64, i32, i32, i32, C.c_double, vp, vp,
                                                 vp, vp, vp]
-    lib.antsrl_reworktrain_sizes.argtypes = [rs, C.c_int64, sz, sz, C.POINTER(C.c_int32)]
-    lib.antsrl_reworktrain_grad.argtypes = [rs] + [vp] * 9 + [C.c_int64, vp, C.c_int64, C.c_float, vp, vp, vp, vp]
-    lib.antsrl_reworktrain_apply.argtypes = [rs, vp, vp, vp, vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, vp]
-    lib.antsrl_reworktrain_step.argtypes = [rs] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_float, C.c_int64, C.c_double,
-                                                               C.c_double, C.c_double, C.c_double, vp, vp, vp, vp]
+    # the four flat trainers (antsrl_<entry>_sizes / _grad / _apply / _step): one argument order behind the net's own
+    # leading arguments.  entry: (what _grad and _step take in front of the arrays, what _apply takes in front of Adam's m)
+    adam = [C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double]            # step, lr, beta1, beta2, eps
+    arrays = [vp] * 7 + [C.c_int64, vp, C.c_int64, C.c_float]                     # the seven arrays, n_rows, idx, B, discount
+    for entry, (net, apply_net) in {"lintrain": ([i32] + [vp] * 4, [vp]), "exptrain": ([i32, vp, vp], [i32, vp]),
+                                    "jointtrain": ([i32, vp, vp], [i32, vp]), "reworktrain": ([rs, vp, vp], [rs, vp])}.items():
+        for stage, argtypes in (("sizes", [net[0], C.c_int64, sz, sz, C.POINTER(C.c_int32)]),
+                                ("grad", net + arrays + [vp, vp, vp, vp]),                  # grads, loss, workspace, stream
+                                ("apply", apply_net + [vp, vp, vp] + adam + [vp]),          # adam_m, adam_v, grads; stream
+                                ("step", net + [vp, vp] + arrays + adam + [vp, vp, vp, vp])):  # adam_m, adam_v behind the net
+            getattr(lib, "antsrl_%s_%s" % (entry, stage)).argtypes = argtypes
     lib.antsrl_monitor_sizes.argtypes = [i32, i32, i32, i32, sz]
     lib.antsrl_monitor_init.argtypes = [vp, i32, i32, i32, i32, vp]
     lib.antsrl_monitor_step.argtypes = [vp, i32, i32, i32, i32, vp, vp, C.c_double, i32, i32, vp]

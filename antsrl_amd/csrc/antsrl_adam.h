@@ -1,8 +1,8 @@
 // antsrl_adam.h — torch.optim.Adam's single-tensor step in fp32, for the memory agent's apply stage (antsrl_memtrain.hip),
 // the linear agent's training step (antsrl_lintrain.hip), the explore agent's (antsrl_exptrain.hip) and the rework
 // agent's (antsrl_reworktrain.hip): the host side (antsrl_adam_args: the checks of an entry's Adam arguments and the
-// scalars; antsrl_adam_apply: antsrl_lintrain_apply / antsrl_exptrain_apply / antsrl_reworktrain_apply behind the net's
-// own check), one element on the device (adam_element, adam_at) and the flat kernel (antsrl_launch_adam).  The host
+// scalars; antsrl_adam_step: a fused _step entry's moments and scalars; antsrl_adam_apply: antsrl_lintrain_apply /
+// antsrl_exptrain_apply / antsrl_reworktrain_apply behind the net's own check), one element on the device (adam_element, adam_at) and the flat kernel (antsrl_launch_adam).  The host
 // computes step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) in double and rounds every scalar to
 // float once (w1m = 1 - beta1, w2m = 1 - beta2), as the op does.
 #pragma once
@@ -37,6 +37,16 @@ static inline int antsrl_adam_args(const char *who, int64_t step, double lr, dou
     o->w2m = (float)(1.0 - beta2);
     o->eps = (float)eps;
     return ANTSRL_OK;
+}
+
+// Adam's part of a fused _step entry, behind its minibatch: the two moments, then antsrl_adam_args, into *o
+static inline int antsrl_adam_step(const char *who, float *adam_m, float *adam_v, int64_t step, double lr, double beta1,
+                                   double beta2, double eps, AdamArgs *o)
+{
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    o->m = adam_m; o->v = adam_v;
+    return antsrl_adam_args(who, step, lr, beta1, beta2, eps, o);
 }
 
 // Adam on params[0 .. P) from grads (o.m, o.v and the scalars are read): one flat kernel, antsrl_lintrain.hip holds it

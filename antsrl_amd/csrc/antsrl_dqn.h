@@ -25,6 +25,18 @@ struct DqnBatch {
     float discount, dq_scale /* 2 / (3 B) */, loss_scale /* 1 / (3 B) */;
 };
 
+// a minibatch's rows against its entry's limit, for the explore, the joint and the rework step and the population's
+// members (the linear step's limit is an INVALID one with its own words, lt_B): 1 <= B <= max_B; `limit`, where the
+// entry gives one, says behind the second refusal what of a member's step max_B rows are
+static inline int antsrl_dqn_B(const char *who, int64_t B, int max_B, const char *limit = nullptr)
+{
+    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
+    if (B > max_B)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows%s%s", who, (long long)B, max_B,
+                    limit ? ": a member's step is " : "", limit ? limit : "");
+    return ANTSRL_OK;
+}
+
 // the minibatch of a gradient stage or a fused step, for a B its entry has checked: the replay arrays, idx, grads, loss
 // and the discount into the fields of *q that carry their names (Q: DqnBatch or ReworkTrainArgs), or the refusal.  The
 // net, the workspace and the scales stay with the entry.

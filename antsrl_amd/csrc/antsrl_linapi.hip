@@ -4,7 +4,7 @@
 // in front of antsrl_exptrain.hip's, and the joint step's ("The joint training step"): antsrl_jointtrain_sizes / _grad /
 // _apply / _step in front of antsrl_jointtrain.hip's, all with the same argument rules.  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
 // what every step takes from the replay arrays, the rework agent's (antsrl_reworkapi.hip) included; dqn_batch adds what
-// the 32-wide nets keep in DqnBatch, antsrl_adam_args (antsrl_adam.h) Adam's part; an entry checks its own net's
+// the 32-wide nets keep in DqnBatch, antsrl_adam_step (antsrl_adam.h) Adam's part; an entry checks its own net's
 // pointers, its limit on B and its workspace rule.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
@@ -32,13 +32,6 @@ int lt_features(const char *who, int32_t n_features)
 static int lt_B(const char *who, int64_t B)
 {
     if (B < 1 || B > LT_MAX_B) return fail(ANTSRL_E_INVALID, "%s: B must be in [1, 2^24] (%lld)", who, (long long)B);
-    return ANTSRL_OK;
-}
-
-static int et_B(const char *who, int64_t B)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > ET_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, ET_MAX_B);
     return ANTSRL_OK;
 }
 
@@ -130,11 +123,8 @@ extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const f
     if (rc == ANTSRL_OK)
         rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
                        idx, B, discount, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-    a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_lintrain(a, (hipStream_t)stream), who);
 }
 
@@ -145,7 +135,7 @@ extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trai
 {
     const char *who = "exptrain_sizes";
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = et_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, ET_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
     if (workspace_bytes) *workspace_bytes = antsrl_exptrain_dh_offset((int)B) + (size_t)B * ET_HIDDEN * sizeof(float);
@@ -158,7 +148,7 @@ static int et_net(const char *who, int32_t n_features, int64_t B, float *model, 
                   ExpTrainArgs *a)
 {
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = et_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, ET_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
     REQUIRE(target, 4);
@@ -209,29 +199,19 @@ extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const floa
     if (rc == ANTSRL_OK)
         rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
                        idx, B, discount, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-    a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who);
 }
 
 // ---- the joint training step: layer1 under the collect heads (antsrl_jointtrain.hip) ---------------------------------------
-
-static int jt_B(const char *who, int64_t B)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > JT_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, JT_MAX_B);
-    return ANTSRL_OK;
-}
 
 extern "C" int antsrl_jointtrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
                                        int32_t *launches)
 {
     const char *who = "jointtrain_sizes";
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = jt_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, JT_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     if (trained_floats) *trained_floats = antsrl_jointtrain_floats(n_features);
     if (workspace_bytes) *workspace_bytes = antsrl_jointtrain_dh_offset((int)B) + (size_t)B * JT_HIDDEN * sizeof(float);
@@ -244,7 +224,7 @@ static int jt_net(const char *who, int32_t n_features, int64_t B, float *model, 
                   JointTrainArgs *a)
 {
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = jt_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, JT_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
     REQUIRE(target_l3, 4);
@@ -295,10 +275,7 @@ extern "C" int antsrl_jointtrain_step(int32_t n_features, float *model, const fl
     if (rc == ANTSRL_OK)
         rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
                        idx, B, discount, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-    a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_jointtrain(a, (hipStream_t)stream), who);
 }

@@ -161,14 +161,8 @@ extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64
     return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
 }
 
-// The training entries refuse in the order spec, B, their pointers, dqn_batch's arguments, running_loss, Adam's.
-// A member's minibatch: 1 <= B <= max_B rows; `limit` says what of the entry's step max_B rows are.
-static int pop_train_B(const char *who, int64_t B, int max_B, const char *limit)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > max_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows: a member's step is %s", who, (long long)B, max_B, limit);
-    return ANTSRL_OK;
-}
+// The training entries refuse in the order spec, B (antsrl_dqn_B, antsrl_dqn.h, told what of the entry's step its limit
+// is), their pointers, dqn_batch's arguments, running_loss, Adam's.
 
 // running_loss's alignment, then Adam's scalars per member: the step size is the learning rate's and goes into the table
 static int pop_train_tail(const char *who, const AntsPopSpec *s, int64_t step, double beta1, double beta2, double eps,
@@ -194,7 +188,7 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
     PopTable t;
     int Em = 0;
     int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, 32 * LT_FUSED_TILES, "one workgroup");
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, 32 * LT_FUSED_TILES, "one workgroup");
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(w1, 4);
     REQUIRE(b1, 4);
@@ -240,7 +234,7 @@ extern "C" int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t 
 {
     const char *who = "pop_exptrain_sizes";
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
     if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
     if (rc != ANTSRL_OK) return rc;
     const size_t stride = antsrl_pop_exptrain_stride((int)B);
@@ -262,7 +256,7 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
     PopTable t;
     int Em = 0;
     int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_train_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
     REQUIRE(target, 4);

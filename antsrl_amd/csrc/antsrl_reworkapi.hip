@@ -10,7 +10,7 @@
 #include <stdint.h>
 
 #include "antsrl_device.h"
-#include "antsrl_dqn.h" // antsrl_dqn_minibatch
+#include "antsrl_dqn.h" // antsrl_dqn_B, antsrl_dqn_minibatch
 #include "antsrl_fail.h"
 #include "antsrl_loopapi.h" // antsrl_check_batch, antsrl_check_epsilon, antsrl_check_obs_format
 #include "antsrl_rework.h"
@@ -114,20 +114,13 @@ extern "C" int antsrl_policy_rework_select(const AntsReworkShape *s, const void 
 
 // ---- the training step (antsrl_reworktrain.hip) ----------------------------------------------------------------------------
 
-static int rt_B(const char *who, int64_t B)
-{
-    if (B < 1) return fail(ANTSRL_E_INVALID, "%s: B must be >= 1 (%lld)", who, (long long)B);
-    if (B > RT_MAX_B) return fail(ANTSRL_E_UNSUPPORTED, "%s: B = %lld > %d rows", who, (long long)B, RT_MAX_B);
-    return ANTSRL_OK;
-}
-
 extern "C" int antsrl_reworktrain_sizes(const AntsReworkShape *s, int64_t B, size_t *params_floats, size_t *workspace_bytes,
                                         int32_t *launches)
 {
     const char *who = "reworktrain_sizes";
     ReworkDims d;
     int rc = rework_check(s, &d, who);
-    if (rc == ANTSRL_OK) rc = rt_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, RT_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     ReworkTrainLayout L;
     antsrl_reworktrain_layout(d, (int)B, &L);
@@ -145,7 +138,7 @@ static int rt_args(const char *who, const AntsReworkShape *s, float *model, cons
                    void *workspace, ReworkTrainArgs *a)
 {
     int rc = rework_check(s, &a->d, who);
-    if (rc == ANTSRL_OK) rc = rt_B(who, B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, RT_MAX_B);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
     REQUIRE(target_collapsed, 4);
@@ -202,10 +195,7 @@ extern "C" int antsrl_reworktrain_step(const AntsReworkShape *s, float *model, c
     ReworkTrainArgs a = {};
     int rc = rt_args(who, s, model, target_collapsed, states, agent_states, actions, rewards, new_states, new_agent_states,
                      dones, n_rows, idx, B, discount, grads, false, loss, workspace, &a);
+    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    if ((rc = antsrl_adam_args(who, step, lr, beta1, beta2, eps, &a.adam)) != ANTSRL_OK) return rc;
-    a.adam.m = adam_m; a.adam.v = adam_v;
     return enqueued(antsrl_launch_reworktrain(a, (hipStream_t)stream), who);
 }

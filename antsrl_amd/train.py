@@ -292,7 +292,11 @@ class _FlatTrainer(_DqnTrainer):
     / _grad / _apply / _step take one argument order behind the net's own leading arguments (include/antsrl.h), so the
     three stages are written once.  A subclass names its `entry`, writes `_sizes`, gives `_net()` (what _grad and _step
     take in front of the arrays) and `_apply_net()` (what _apply takes in front of Adam's m), keeps Adam's moments in
-    `_adam` [2][P] and overrides `_weights_changed` when a training step moves its acting weights.
+    `_adam` [2][P] (`_alloc_trained`) and overrides `_weights_changed` when a training step moves its acting weights.
+
+    sync_target and load_state_dict are written once too: a subclass gives `_copy_target()`, what its target net owns
+    following the model, and `_rename(sd)`, a state_dict under the names of its views.  `version` counts the changes of
+    the acting weights: it moves behind the copy.
 
     The views are those of a net that is ONE flat block described by `_offs` (name -> (offset, shape)), `model` and
     `target`: the explore and the rework trainer's (the joint trainer's `model`; its target is layer3 alone).  The linear
@@ -305,6 +309,20 @@ class _FlatTrainer(_DqnTrainer):
 
     def _apply_net(self) -> tuple:
         raise NotImplementedError
+
+    def _copy_target(self) -> None:
+        raise NotImplementedError
+
+    @staticmethod
+    def _rename(sd):
+        return sd
+
+    def _alloc_trained(self, trained_floats: int) -> None:
+        """Adam's moments and the gradient of the trained floats, zeroed, and `version` at 0."""
+        self.trained_floats = trained_floats
+        self.version = 0
+        self._adam = torch.zeros((2, trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((trained_floats,), dtype=torch.float32, device=self.device)
 
     def _weights_changed(self) -> None:
         """A call that changed the model's weights has been enqueued."""
@@ -321,12 +339,28 @@ class _FlatTrainer(_DqnTrainer):
     def _views(self, flat) -> dict:
         return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
 
+    def _model_views(self) -> dict:
+        return self._views(self.model)
+
     def state_dict(self) -> dict:
         """The model's tensors (copies) under the reference's names, in its order."""
-        return _clones(self._views(self.model))
+        return _clones(self._model_views())
 
     def target_state_dict(self) -> dict:
         return _clones(self._views(self.target))
+
+    def load_state_dict(self, sd) -> None:
+        """The reference's load_model: sets the model AND the target net (the subclass says under which names, and what
+        else follows).  Adam's state is kept, as the reference's optimizer keeps it."""
+        copy_named(self._rename(sd), self._model_views())
+        self._copy_target()
+        self.version += 1
+
+    def sync_target(self) -> None:
+        """target := model, as the subclass's _copy_target has it.  Adam's state is not copied."""
+        self._copy_target()
+        self.syncs += 1
+        self.version += 1
 
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the trained tensors: step, exp_avg, exp_avg_sq (copies)."""
@@ -414,7 +448,27 @@ def linear_adam_state(step: int, adam) -> dict:
     return dict(step=step, exp_avg=_clones(linear_trained_views(adam[0])), exp_avg_sq=_clones(linear_trained_views(adam[1])))
 
 
-class LinearTrainer(_FlatTrainer):
+class _CollectTrainer(_FlatTrainer):
+    """What the linear and the joint trainer share: CollectModel's two nets share one ExploreModel, so layer1 and layer2
+    are live in both and the target net owns layer3 alone, `target_l3` (99 floats).  load_state_dict is
+    CollectAgent.load_model (agents/collect_agent.py:182-184) and takes CollectModel's names, or ExploreModel's bare
+    layer1 / layer2 (with layer3)."""
+
+    _rename = staticmethod(collect_names)
+
+    def target_state_dict(self) -> dict:
+        """The target net's: the shared layer1 and layer2, its own layer3."""
+        return linear_target_state_dict(self.state_dict(), self.target_l3)
+
+    def load_explore_state_dict(self, sd) -> None:
+        """The hand-over from stage 1 of the curriculum (the line agents/collect_agent.py:84 has commented out): layer1
+        and layer2 from a four-tensor ExploreModel state_dict (an ExploreAgent's save_model; bare names or behind the
+        `explore_model.` prefix).  layer3, its target copy and Adam's state stay as they are."""
+        copy_named(collect_names(sd), self._model_views(), LINEAR_NAMES[:4])
+        self.version += 1
+
+
+class LinearTrainer(_CollectTrainer):
     """CollectAgent's model, target model and optimizer on the device (agents/collect_agent.py:54-148; defaults: the
     reference class's, discount 0.5, Adam lr 1e-4), trained by `antsrl_lintrain_step` (antsrl_lintrain.hip).
 
@@ -434,16 +488,13 @@ class LinearTrainer(_FlatTrainer):
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
         from .policy import LinearPolicy
         super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
-        self.version = 0
+        self._alloc_trained(198)
         p = LinearPolicy(n_features, self.device, seed=seed)
         self.heads = torch.cat([p.w2.reshape(-1), p.b2, p.w3.reshape(-1), p.b3]).contiguous()
         self.target_l3 = self.heads[99:198].clone()
-        self._adam = torch.zeros((2, 198), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((198,), dtype=torch.float32, device=self.device)
         p.w2, p.b2 = self.heads[0:96].view(3, 32), self.heads[96:99]              # the live layer2
         p.w3, p.b3 = linear_l3_views(self.target_l3).values()                     # the target layer3
         self.policy = p
-        self.trained_floats = 198
         if state_dict is not None:
             self.load_state_dict(state_dict)
 
@@ -451,27 +502,9 @@ class LinearTrainer(_FlatTrainer):
     def _model_views(self) -> dict:
         return linear_model_views(self.policy.w1, self.policy.b1, self.heads)
 
-    def state_dict(self) -> dict:
-        """The model's six tensors (copies) under CollectModel's names, in its order."""
-        return _clones(self._model_views())
-
-    def target_state_dict(self) -> dict:
-        """The target net's: the shared layer1 and layer2, its own layer3."""
-        return linear_target_state_dict(self.state_dict(), self.target_l3)
-
-    def load_state_dict(self, sd) -> None:
-        """CollectAgent.load_model (:182-184): sets the model AND the target net.  CollectModel's names, or ExploreModel's
-        bare layer1 / layer2 (with layer3).  Adam's state is kept, as the reference's optimizer keeps it."""
-        copy_named(collect_names(sd), self._model_views())
+    def _copy_target(self) -> None:
+        """target := model (:143-146): layer3 is all the two nets do not share."""
         self.target_l3.copy_(self.heads[99:198])
-        self.version += 1
-
-    def load_explore_state_dict(self, sd) -> None:
-        """The hand-over from stage 1 of the curriculum (the line agents/collect_agent.py:84 has commented out): layer1
-        and layer2 from a four-tensor ExploreModel state_dict (an ExploreAgent's save_model; bare names or behind the
-        `explore_model.` prefix).  layer3, its target copy and Adam's state stay as they are."""
-        copy_named(collect_names(sd), self._model_views(), LINEAR_NAMES[:4])
-        self.version += 1
 
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the four trained tensors: step, exp_avg, exp_avg_sq (copies)."""
@@ -480,12 +513,6 @@ class LinearTrainer(_FlatTrainer):
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the four trained tensors."""
         return linear_trained_views(self.grads if grads is None else grads)
-
-    def sync_target(self) -> None:
-        """target := model (:143-146): layer3 is all the two nets do not share."""
-        self.target_l3.copy_(self.heads[99:198])
-        self.syncs += 1
-        self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
     def _sizes(self, B, workspace_bytes, launches):
@@ -523,19 +550,16 @@ class ExploreTrainer(_FlatTrainer):
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
         from .policy import LinearPolicy
         super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
-        self.version = 0
         IN = n_features + 2
         self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
                       "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
         tf = C.c_size_t()
         _lib.check(self._lib.antsrl_exptrain_sizes(n_features, 1, C.byref(tf), None, None), "exptrain_sizes")
-        self.trained_floats = tf.value
-        assert self.trained_floats == 32 * IN + 131
+        assert tf.value == 32 * IN + 131
+        self._alloc_trained(tf.value)
         p = LinearPolicy(n_features, self.device, with_pheromone_head=False, seed=seed)
         self.model = torch.cat([p.w1.reshape(-1), p.b1, p.w2.reshape(-1), p.b2]).contiguous()
         self.target = self.model.clone()
-        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
         tv = self._views(self.target)
         p.w1, p.b1, p.w2, p.b2 = (tv[k] for k in EXPLORE_NAMES)  # the acting net IS the target block
         self.policy = p
@@ -543,19 +567,13 @@ class ExploreTrainer(_FlatTrainer):
             self.load_state_dict(state_dict)
 
     # ---- weights ------------------------------------------------------------------------------------------------
-    def load_state_dict(self, sd) -> None:
-        """ExploreAgentPytorch.load_model (:157-159): sets the model AND the target net.  ExploreModel's names, bare or
-        behind CollectModel's `explore_model.` prefix (other entries, such as layer3, are ignored).  Adam's state is
-        kept, as the reference's optimizer keeps it."""
-        copy_named(explore_names(sd), self._views(self.model))
-        self.target.copy_(self.model)
-        self.version += 1
+    #: load_state_dict is ExploreAgentPytorch.load_model (:157-159) and takes ExploreModel's names, bare or behind
+    #: CollectModel's `explore_model.` prefix (other entries, such as layer3, are ignored)
+    _rename = staticmethod(explore_names)
 
-    def sync_target(self) -> None:
+    def _copy_target(self) -> None:
         """target := model (:127-131): one device copy of the block; the acting policy's tensors are views of it."""
         self.target.copy_(self.model)
-        self.syncs += 1
-        self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
     def _sizes(self, B, workspace_bytes, launches):
@@ -568,7 +586,7 @@ class ExploreTrainer(_FlatTrainer):
         return self.n_features, _p(self.model)
 
 
-class JointTrainer(_FlatTrainer):
+class JointTrainer(_CollectTrainer):
     """CollectAgent's model, target model and optimizer on the device with the freeze of layer1 lifted and nothing else
     changed: the third stage of the linear agent's curriculum, trained by `antsrl_jointtrain_step`
     (antsrl_jointtrain.hip).  It is the reference's own train() (agents/collect_agent.py:105-148) once
@@ -591,7 +609,6 @@ class JointTrainer(_FlatTrainer):
                  eps: float = 1e-8, update_target_every: int = 1, seed: int = 0, state_dict=None):
         from .policy import LinearPolicy
         super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
-        self.version = 0
         IN = n_features + 2
         shapes = ((32, IN), (32,), (3, 32), (3,), (3, 32), (3,))
         self._offs, off = {}, 0
@@ -600,14 +617,12 @@ class JointTrainer(_FlatTrainer):
             off += math.prod(shp)
         tf = C.c_size_t()
         _lib.check(self._lib.antsrl_jointtrain_sizes(n_features, 1, C.byref(tf), None, None), "jointtrain_sizes")
-        self.trained_floats = tf.value
-        assert self.trained_floats == off == 32 * IN + 230
+        assert tf.value == off == 32 * IN + 230
+        self._alloc_trained(tf.value)
         p = LinearPolicy(n_features, self.device, seed=seed)
         self.model = torch.cat([t.reshape(-1) for t in (p.w1, p.b1, p.w2, p.b2, p.w3, p.b3)]).contiguous()
         self._l3 = slice(self._offs["layer3.weight"][0], off)  # layer3 in the block: the 99 floats the target copies
         self.target_l3 = self.model[self._l3].clone()
-        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
         mv = self._views(self.model)
         p.w1, p.b1, p.w2, p.b2 = (mv[k] for k in LINEAR_NAMES[:4])                # the live layer1 and layer2
         p.w3, p.b3 = linear_l3_views(self.target_l3).values()                     # the target layer3
@@ -616,28 +631,9 @@ class JointTrainer(_FlatTrainer):
             self.load_state_dict(state_dict)
 
     # ---- weights ------------------------------------------------------------------------------------------------
-    def target_state_dict(self) -> dict:
-        """The target net's: the shared layer1 and layer2, its own layer3."""
-        return linear_target_state_dict(self.state_dict(), self.target_l3)
-
-    def load_state_dict(self, sd) -> None:
-        """CollectAgent.load_model (:182-184): sets the model AND the target net.  What LinearTrainer.load_state_dict
-        accepts: CollectModel's names, or ExploreModel's bare layer1 / layer2 (with layer3).  Adam's state is kept."""
-        copy_named(collect_names(sd), self._views(self.model))
-        self.target_l3.copy_(self.model[self._l3])
-        self.version += 1
-
-    def load_explore_state_dict(self, sd) -> None:
-        """layer1 and layer2 from a four-tensor ExploreModel state_dict (LinearTrainer.load_explore_state_dict): layer3,
-        its target copy and Adam's state stay as they are."""
-        copy_named(collect_names(sd), self._views(self.model), LINEAR_NAMES[:4])
-        self.version += 1
-
-    def sync_target(self) -> None:
+    def _copy_target(self) -> None:
         """target := model (:143-146): layer3 is all the two nets do not share."""
         self.target_l3.copy_(self.model[self._l3])
-        self.syncs += 1
-        self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
     def _sizes(self, B, workspace_bytes, launches):
@@ -675,7 +671,6 @@ class ReworkTrainer(_FlatTrainer):
                  state_dict=None):
         from .policy import ReworkPolicy, rework_param_shapes, rework_shape_from_state_dict
         super().__init__(n_features, device, 2, discount, lr, betas, eps, update_target_every)
-        self.version = 0
         if state_dict is None:
             state_dict = ReworkPolicy(n_features, "cpu", n_rot=n_rot, n_ph=n_ph, seed=seed).state_dict()
         shp = rework_shape_from_state_dict(state_dict)
@@ -689,30 +684,18 @@ class ReworkTrainer(_FlatTrainer):
             off += o * i + o
         pf = C.c_size_t()
         _lib.check(self._lib.antsrl_reworktrain_sizes(C.byref(self.shape), 1, C.byref(pf), None, None), "reworktrain_sizes")
-        self.trained_floats = pf.value
-        assert self.trained_floats == off
+        assert pf.value == off
+        self._alloc_trained(pf.value)
         self.model = torch.cat([torch.as_tensor(state_dict[k]).to(torch.float32).reshape(-1) for k in self._offs]).to(self.device)
         self.target = self.model.clone()
-        self._adam = torch.zeros((2, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
         self.policy = ReworkPolicy(n_features, self.device, params=self._views(self.target))  # acts on the target block
 
     # ---- weights ------------------------------------------------------------------------------------------------
-    def load_state_dict(self, sd) -> None:
-        """CollectAgentRework.load_model (:186-188): sets the model AND the target net, and collapses the target once.
-        Adam's state is kept, as the reference's optimizer keeps it."""
-        copy_named(sd, self._views(self.model))
+    def _copy_target(self) -> None:
+        """target := model (:147-150, and in CollectAgentRework.load_model, :186-188, which load_state_dict is): one
+        device copy of the block, then one collapse of it; the acting policy's tensors are views of the block."""
         self.target.copy_(self.model)
         self.policy.recollapse()
-        self.version += 1
-
-    def sync_target(self) -> None:
-        """target := model (:147-150): one device copy of the block and one collapse; the acting policy's tensors are
-        views of the block."""
-        self.target.copy_(self.model)
-        self.policy.recollapse()
-        self.syncs += 1
-        self.version += 1
 
     # ---- the stages ---------------------------------------------------------------------------------------------
     def _sizes(self, B, workspace_bytes, launches):

@@ -1,24 +1,10 @@
 """What the CPU-side checks of the two populations' C-ABI entries share (test_population_abi_cpu.py,
-test_population_explore_abi_cpu.py): the fake pointers, the library, an AntsPopSpec from keywords, the call of an entry
+test_population_explore_abi_cpu.py) on top of abi_fakes.py: an AntsPopSpec from keywords, the call of an entry
 from a dict of defaults, and the arguments the two training entries have in common."""
 import ctypes as C
 
-import pytest
-
+from abi_fakes import FAKE
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
-
-FAKE = C.c_void_p(1 << 20)  # 256-byte aligned; never dereferenced
-ODD = C.c_void_p((1 << 20) + 2)
-ODD4 = C.c_void_p((1 << 20) + 4)
-ODD8 = C.c_void_p((1 << 20) + 8)
-ODD128 = C.c_void_p((1 << 20) + 128)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def spec(**kw):

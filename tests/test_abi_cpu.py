@@ -20,10 +20,15 @@ def lib():
     return _lib.load()
 
 
-def declared_symbols():
+def header_code():
+    """include/antsrl.h without its comments and preprocessor lines."""
     text = open(os.path.join(ROOT, "include", "antsrl.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(antsrl_[a-z_]+)\s*\(", text)))
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", "", text, flags=re.S)
+    return "\n".join(line for line in text.split("\n") if not line.lstrip().startswith("#"))
+
+
+def declared_symbols():
+    return sorted(set(re.findall(r"\b(antsrl_[a-z0-9_]+)\s*\(", header_code())))
 
 
 def test_header_symbols_are_exported(lib):
@@ -32,6 +37,60 @@ def test_header_symbols_are_exported(lib):
     for n in names:
         assert hasattr(lib, n), "libantsrl_hip.so does not export %s" % n
     assert sorted(_lib.EXPORTS) == names
+
+
+#: the header's scalar types: bytes, and "i" signed integer, "u" unsigned integer, "f" floating point
+SCALARS = {"int": (4, "i"), "int8_t": (1, "i"), "int32_t": (4, "i"), "int64_t": (8, "i"), "long long": (8, "i"),
+           "uint8_t": (1, "u"), "uint64_t": (8, "u"), "size_t": (C.sizeof(C.c_void_p), "u"), "float": (4, "f"),
+           "double": (8, "f")}
+
+
+def scalar_kind(T):
+    """A ctypes scalar type as SCALARS describes the header's."""
+    if T in (C.c_float, C.c_double):
+        return C.sizeof(T), "f"
+    return C.sizeof(T), "i" if T(-1).value < 0 else "u"
+
+
+def header_prototypes():
+    """name -> [(base type, number of *)] of every antsrl_* prototype (`const` dropped; [] for a `(void)` one)."""
+    out = {}
+    for name, params in re.findall(r"\b(antsrl_\w+)\s*\(([^()]*)\)\s*;", header_code()):
+        assert name not in out, name
+        out[name] = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            words = re.sub(r"\bconst\b|\*", " ", p).split()
+            assert len(words) >= 2, "%s: parameter %r has no name" % (name, p)
+            out[name].append((" ".join(words[:-1]), p.count("*")))
+    return out
+
+
+def test_binding_agrees_with_the_header(lib):
+    """_lib.load()'s hand-written argtypes against include/antsrl.h, prototype by prototype: the parameter count, a
+    scalar's width and kind, a pointer bound as c_void_p or as a POINTER to what the header points to."""
+    protos = header_prototypes()
+    assert len(protos) == len(_lib.EXPORTS) == len(set(_lib.EXPORTS)), sorted(set(protos) ^ set(_lib.EXPORTS))
+    for name, params in protos.items():
+        bound = getattr(lib, name).argtypes
+        if not params:
+            assert not bound, name
+            continue
+        assert bound is not None, "%s has no argtypes" % name
+        assert len(bound) == len(params), "%s: %d argtypes, %d parameters" % (name, len(bound), len(params))
+        for i, ((base, stars), T) in enumerate(zip(params, bound)):
+            what = "%s, parameter %d (%s%s)" % (name, i, base, " *" * stars)
+            if stars == 0:
+                assert base in SCALARS, what
+                assert issubclass(T, C._SimpleCData) and T is not C.c_void_p and scalar_kind(T) == SCALARS[base], (what, T)
+            elif T is not C.c_void_p:
+                assert issubclass(T, C._Pointer), (what, T)
+                pointee = T._type_
+                if stars > 1:
+                    assert pointee is C.c_void_p or issubclass(pointee, C._Pointer), (what, pointee)
+                elif issubclass(pointee, C.Structure):
+                    assert pointee.__name__ == base, (what, pointee)
+                else:
+                    assert base in SCALARS and scalar_kind(pointee) == SCALARS[base], (what, pointee)
 
 
 def test_layout_and_version(lib):

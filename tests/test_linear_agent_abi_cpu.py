@@ -6,20 +6,12 @@ import ctypes as C
 
 import pytest
 
+import train_abi as TA
+from abi_fakes import FAKE, ODD, ODD4, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_agent_select_actions", "antsrl_replay_record_pre_plain", "antsrl_replay_record_post_plain",
        "antsrl_lintrain_sizes", "antsrl_lintrain_grad", "antsrl_lintrain_apply", "antsrl_lintrain_step")
-FAKE = C.c_void_p(1 << 20)
-ODD = C.c_void_p((1 << 20) + 2)
-ODD4 = C.c_void_p((1 << 20) + 4)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported(lib):
@@ -135,27 +127,10 @@ def test_lintrain_sizes(lib):
         assert msg in lib.antsrl_last_error()
 
 
-GRAD_PTRS = ("w1", "b1", "heads", "target_l3", "states", "agent_states", "actions", "rewards", "new_states",
-             "new_agent_states", "dones")
-
-
-def grad(lib, **kw):
-    a = {n: FAKE for n in GRAD_PTRS}
-    a.update(F=294, n_rows=1000, idx=FAKE, B=264, discount=0.5, grads=FAKE, loss=FAKE, work=C.c_void_p(1 << 21))
-    a.update(kw)
-    return lib.antsrl_lintrain_grad(a["F"], *[a[n] for n in GRAD_PTRS], a["n_rows"], a["idx"], a["B"], a["discount"],
-                                    a["grads"], a["loss"], a["work"], None)
-
-
-def step(lib, **kw):
-    a = {n: FAKE for n in GRAD_PTRS}
-    a.update(F=294, m=FAKE, v=FAKE, n_rows=1000, idx=FAKE, B=264, discount=0.5, step=1, lr=1e-4, beta1=0.9, beta2=0.999,
-             eps=1e-8, grads=None, loss=FAKE, work=C.c_void_p(1 << 21))
-    a.update(kw)
-    p = [a[n] for n in GRAD_PTRS]
-    return lib.antsrl_lintrain_step(a["F"], *p[:4], a["m"], a["v"], *p[4:], a["n_rows"], a["idx"], a["B"], a["discount"],
-                                    a["step"], a["lr"], a["beta1"], a["beta2"], a["eps"], a["grads"], a["loss"], a["work"], None)
-
+# the step's entries through train_abi.Kind; the cases are this file's own: B's limit is an INVALID one, the workspace is
+# needed beyond one workgroup only, and the step's default has no grads
+KIND = TA.Kind("lintrain", ("w1", "b1", "heads", "target_l3"), lambda a: a["F"], ("heads",),
+               dict(F=294, B=264, work=C.c_void_p(1 << 21)), step_defaults=dict(grads=None))
 
 BATCH_CASES = [(dict(F=0), -1, b"n_features"), (dict(F=1023), -4, b"1024"), (dict(B=0), -1, b"B must be"),
                (dict(B=(1 << 24) + 1), -1, b"B must be"), (dict(n_rows=0), -1, b"n_rows"),
@@ -164,21 +139,16 @@ BATCH_CASES = [(dict(F=0), -1, b"n_features"), (dict(F=1023), -4, b"1024"), (dic
                (dict(loss=ODD), -1, b"loss must be 4-byte"), (dict(discount=float("nan")), -1, b"discount is NaN"),
                (dict(B=4096, work=None), -1, b"workspace is required"),
                (dict(B=4096, work=C.c_void_p((1 << 21) + 16)), -1, b"workspace must be 256-byte"),
-               (dict(grads=ODD), -1, b"grads must be 4-byte")] + \
-    [({n: None}, -1, n.encode() + b" is required") for n in GRAD_PTRS] + \
-    [({n: ODD}, -1, n.encode() + b" must be") for n in GRAD_PTRS if n != "dones"]
+               (dict(grads=ODD), -1, b"grads must be 4-byte")] + TA.pointer_cases(KIND.ptrs)
 
 
 @pytest.mark.parametrize("kw,code,msg", BATCH_CASES)
 def test_lintrain_grad_and_step_validation(lib, kw, code, msg):
-    for fn, who in ((grad, b"lintrain_grad"), (step, b"lintrain_step")):
-        assert fn(lib, **kw) == code, kw
-        err = lib.antsrl_last_error()
-        assert msg in err and who in err, (kw, err)
+    KIND.check(("grad", "step"), lib, kw, code, msg)
 
 
 def test_lintrain_grad_needs_grads(lib):
-    assert grad(lib, grads=None) == -1 and b"grads is required" in lib.antsrl_last_error()
+    KIND.check_grad_needs_grads(lib)
 
 
 ADAM_CASES = [(dict(step=0), b"step must be >= 1"), (dict(lr=-1.0), b"lr must be"), (dict(lr=float("inf")), b"lr must be"),
@@ -188,20 +158,11 @@ ADAM_CASES = [(dict(step=0), b"step must be >= 1"), (dict(lr=-1.0), b"lr must be
 
 @pytest.mark.parametrize("kw,msg", ADAM_CASES + [(dict(m=None), b"adam_m is required"), (dict(v=ODD), b"adam_v must be 4-byte")])
 def test_lintrain_step_adam_validation(lib, kw, msg):
-    assert step(lib, **kw) == -1
-    assert msg in lib.antsrl_last_error(), lib.antsrl_last_error()
-
-
-def apply(lib, **kw):
-    a = dict(heads=FAKE, m=FAKE, v=FAKE, grads=FAKE, step=1, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
-    a.update(kw)
-    return lib.antsrl_lintrain_apply(a["heads"], a["m"], a["v"], a["grads"], a["step"], a["lr"], a["beta1"], a["beta2"],
-                                     a["eps"], None)
+    KIND.check(("step",), lib, kw, -1, msg)
 
 
 @pytest.mark.parametrize("kw,msg", ADAM_CASES + [(dict(heads=None), b"heads is required"), (dict(m=None), b"adam_m is required"),
                                                  (dict(v=None), b"adam_v is required"), (dict(grads=None), b"grads is required"),
                                                  (dict(heads=ODD), b"heads must be 4-byte")])
 def test_lintrain_apply_validation(lib, kw, msg):
-    assert apply(lib, **kw) == -1
-    assert msg in lib.antsrl_last_error() and b"lintrain_apply" in lib.antsrl_last_error(), lib.antsrl_last_error()
+    KIND.check(("apply",), lib, kw, -1, msg)

@@ -6,18 +6,11 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_agent_select", "antsrl_replay_record_pre", "antsrl_replay_record_post")
-FAKE = C.c_void_p(1 << 20)
 FAKE2 = C.c_void_p(1 << 30)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported(lib):

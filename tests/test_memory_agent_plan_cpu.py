@@ -8,18 +8,10 @@ import pytest
 
 import memory_agent_plan_ref as P
 import memory_agent_ref as R
+from abi_fakes import FAKE, ODD, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_agent_plan", "antsrl_policy_memory_tiles")
-FAKE = C.c_void_p(1 << 20)
-ODD = C.c_void_p((1 << 20) + 2)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def test_new_symbols_are_exported(lib):

@@ -6,16 +6,10 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_memnet_packed_bytes", "antsrl_memnet_pack", "antsrl_policy_memory")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(F=294, power=5, mem=20, n_rot=3, n_ph=3, agent_dim=2):
@@ -47,9 +41,7 @@ def test_packed_bytes_is_the_documented_size(lib, power, mem, want):
     assert 0.9 * want < n.value <= want
 
 
-FAKE = C.c_void_p(1 << 20)  # 256-byte aligned, never dereferenced: every call below fails validation first
-
-
+# (FAKE is never dereferenced: every call below fails validation first)
 def policy(lib, s, packed=FAKE, obs=FAKE, rot=FAKE, n_ants=64, fmt=0):
     return lib.antsrl_policy_memory(C.byref(s) if s is not None else None, packed, obs, fmt, FAKE, FAKE, n_ants, FAKE, rot,
                                     None, None, None)

@@ -6,17 +6,11 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_memnet_packed_bytes_ex", "antsrl_memnet_pack_ex", "antsrl_policy_memory_ex")
 BF16, FP32 = 0, 1
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(F=294, power=5, mem=20, n_rot=3, n_ph=3, agent_dim=2):
@@ -60,9 +54,7 @@ def test_sizes_across_shapes(lib, F, power, mem):
     assert old.value < n32.value <= 2 * old.value  # 4 bytes per weight instead of 2, the same biases
 
 
-FAKE = C.c_void_p(1 << 20)  # 256-byte aligned, never dereferenced: every call below fails validation first
-
-
+# (FAKE is never dereferenced: every call below fails validation first)
 def policy(lib, s, precision=FP32, packed=FAKE, obs=FAKE, rot=FAKE, n_ants=64, fmt=0):
     return lib.antsrl_policy_memory_ex(C.byref(s) if s is not None else None, precision, packed, obs, fmt, FAKE, FAKE,
                                        n_ants, FAKE, rot, None, None, None)

@@ -5,18 +5,11 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_memtrain_sizes", "antsrl_memtrain_init", "antsrl_memtrain_unpack", "antsrl_memtrain_copy",
        "antsrl_memtrain_grad", "antsrl_memtrain_apply")
-FAKE = C.c_void_p(1 << 20)  # 256-byte aligned, never dereferenced
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(F=294, power=5, mem=20, n_rot=3, n_ph=3, agent_dim=2):

@@ -9,15 +9,12 @@ import numpy as np
 import pytest
 
 import monitor_ref as R
+from abi_fakes import FAKE, INVALID, ODD, ODD4, lib  # noqa: F401 (lib is a fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "antsrl.h")
 CONTRACT = os.path.join(HERE, "golden", "contract")
 NAMES = ("antsrl_monitor_sizes", "antsrl_monitor_init", "antsrl_monitor_step", "antsrl_monitor_end_episode")
-INVALID = -1
-FAKE = C.c_void_p(1 << 20)
-ODD = C.c_void_p((1 << 20) + 4)   # 4-byte aligned only
-ODD2 = C.c_void_p((1 << 20) + 2)
 
 
 # ---- the restatement -----------------------------------------------------------------------------------------------------
@@ -125,14 +122,6 @@ def test_episode_seeds_follow_the_auto_reset_rule():
 
 
 # ---- the C-ABI -------------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def lib():
-    from antsrl_amd import _lib
-    from antsrl_amd import build as buildmod
-    buildmod.build_hip()
-    return _lib.load()
-
-
 def test_the_entries_are_exported_and_declared(lib):
     from antsrl_amd import _lib
     text = open(HEADER).read()
@@ -183,10 +172,10 @@ def test_bad_pointers_and_slots_are_refused_without_a_launch(lib):
     end = lambda state=FAKE, ep=0, last=-1: lib.antsrl_monitor_end_episode(state, *d, ep, last, None)  # noqa: E731
     for rc, msg in ((lambda: lib.antsrl_monitor_sizes(*d, None), b"NULL bytes"),
                     (lambda: lib.antsrl_monitor_init(None, *d, None), b"NULL state"),
-                    (lambda: lib.antsrl_monitor_init(ODD, *d, None), b"8-byte"),
-                    (lambda: step(state=None), b"NULL state"), (lambda: step(state=ODD), b"8-byte"),
-                    (lambda: step(reward=None), b"NULL reward"), (lambda: step(reward=ODD2), b"4-byte"),
-                    (lambda: step(loss=ODD2), b"4-byte"),
+                    (lambda: lib.antsrl_monitor_init(ODD4, *d, None), b"8-byte"),  # 4-byte aligned only
+                    (lambda: step(state=None), b"NULL state"), (lambda: step(state=ODD4), b"8-byte"),
+                    (lambda: step(reward=None), b"NULL reward"), (lambda: step(reward=ODD), b"4-byte"),
+                    (lambda: step(loss=ODD), b"4-byte"),
                     (lambda: step(slot=2), b"report_slot"), (lambda: step(slot=-2), b"report_slot"),
                     (lambda: step(slot=1 << 30), b"report_slot"),
                     (lambda: end(state=None), b"NULL state"), (lambda: end(ep=3), b"episode_slot"),

@@ -6,8 +6,9 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, ODD, ODD4, ODD8, ODD128, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from population_abi import FAKE, ODD, ODD4, ODD8, ODD128, call, call_train, lib, spec  # noqa: F401 (lib is a fixture)
+from population_abi import call, call_train, spec
 
 NEW = ("antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes", "antsrl_pop_exptrain_step")
 

@@ -7,29 +7,18 @@ import os
 
 import pytest
 
+from abi_fakes import FAKE, INVALID, ODD, UNSUPPORTED, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NAME = "antsrl_policy_rework_select"
 FIELDS = ("n_features", "agent_dim", "g1", "g2", "g3", "r1", "r2", "r3", "p1", "n_rot", "n_ph")
-INVALID, UNSUPPORTED = -1, -4
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "antsrl.h")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(**kw):
     v = dict(n_features=294, agent_dim=2, g1=64, g2=128, g3=32, r1=64, r2=128, r3=32, p1=32, n_rot=3, n_ph=3)
     v.update(kw)
     return _lib.AntsReworkShape(*[v[n] for n in FIELDS])
-
-
-FAKE = C.c_void_p(1 << 20)  # aligned, never dereferenced
-ODD = C.c_void_p((1 << 20) + 2)
 
 
 def select(lib, s, collapsed=FAKE, obs=FAKE, fmt=0, ast=FAKE, seed=1, step=2, base=0, n_envs=4, n_ants=64, epsilon=0.5,

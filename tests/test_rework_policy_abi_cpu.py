@@ -6,27 +6,17 @@ import ctypes as C
 
 import pytest
 
+from abi_fakes import FAKE, INVALID, UNSUPPORTED, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_rework_collapsed_bytes", "antsrl_rework_collapse", "antsrl_policy_rework")
 FIELDS = ("n_features", "agent_dim", "g1", "g2", "g3", "r1", "r2", "r3", "p1", "n_rot", "n_ph")
-INVALID, UNSUPPORTED = -1, -4
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(**kw):
     v = dict(n_features=294, agent_dim=2, g1=64, g2=128, g3=32, r1=64, r2=128, r3=32, p1=32, n_rot=3, n_ph=3)
     v.update(kw)
     return _lib.AntsReworkShape(*[v[n] for n in FIELDS])
-
-
-FAKE = C.c_void_p(1 << 20)  # aligned, never dereferenced
 
 
 def fake_params(n_null=None, misaligned=None):

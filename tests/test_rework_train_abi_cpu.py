@@ -8,21 +8,12 @@ import pytest
 import torch
 
 import rework_train_ref as T
+import train_abi as TA
+from abi_fakes import INVALID, UNSUPPORTED, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from antsrl_amd import build as buildmod
 
 NEW = ("antsrl_reworktrain_sizes", "antsrl_reworktrain_grad", "antsrl_reworktrain_apply", "antsrl_reworktrain_step")
-FAKE = C.c_void_p(1 << 20)   # 256-byte aligned
-ODD = C.c_void_p((1 << 20) + 2)
-ODD4 = C.c_void_p((1 << 20) + 4)
-INVALID, UNSUPPORTED = -1, -4
 FIELDS = [n for n, _ in _lib.AntsReworkShape._fields_]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    buildmod.build_hip()
-    return _lib.load()
 
 
 def shape(**kw):
@@ -80,78 +71,26 @@ def test_sizes_B_refusals(lib, B, code, msg):
     assert lib.antsrl_reworktrain_sizes(None, 264, None, None, None) == INVALID and b"NULL shape" in lib.antsrl_last_error()
 
 
-PTRS = ("model", "target_collapsed", "states", "agent_states", "actions", "rewards", "new_states", "new_agent_states", "dones")
+#: the keyword `shape` holds what differs from shape()'s defaults, or None for a NULL shape
+KIND = TA.Kind("reworktrain", ("model", "target_collapsed"),
+               lambda a: C.byref(shape(**a["shape"])) if a["shape"] is not None else None, ("lead", "model"), dict(shape={}, B=264))
+NET_CASES = [(dict(shape=kw), code, msg) for kw, code, msg in SHAPE_CASES]
 
 
-def _args(**kw):
-    a = dict(shape={}, n_rows=1000, idx=FAKE, B=264, discount=0.5, grads=FAKE, loss=FAKE, work=FAKE, m=FAKE, v=FAKE, step=1,
-             lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8)
-    a.update({n: FAKE for n in PTRS})
-    a.update(kw)
-    a["shape"] = C.byref(shape(**a["shape"])) if a["shape"] is not None else None
-    return a
-
-
-def grad(lib, **kw):
-    a = _args(**kw)
-    return lib.antsrl_reworktrain_grad(a["shape"], *[a[n] for n in PTRS], a["n_rows"], a["idx"], a["B"], a["discount"],
-                                       a["grads"], a["loss"], a["work"], None)
-
-
-def step(lib, **kw):
-    a = _args(**kw)
-    p = [a[n] for n in PTRS]
-    return lib.antsrl_reworktrain_step(a["shape"], *p[:2], a["m"], a["v"], *p[2:], a["n_rows"], a["idx"], a["B"], a["discount"],
-                                       a["step"], a["lr"], a["beta1"], a["beta2"], a["eps"], a["grads"], a["loss"], a["work"], None)
-
-
-def apply(lib, **kw):
-    a = _args(**kw)
-    return lib.antsrl_reworktrain_apply(a["shape"], a["model"], a["m"], a["v"], a["grads"], a["step"], a["lr"], a["beta1"],
-                                        a["beta2"], a["eps"], None)
-
-
-BATCH_CASES = [(dict(shape=kw), code, msg) for kw, code, msg in SHAPE_CASES]
-BATCH_CASES += [(dict(shape=None), INVALID, b"NULL shape"), (dict(B=0), INVALID, b"B must be"), (dict(B=65537), UNSUPPORTED, b"65536"),
-                (dict(n_rows=0), INVALID, b"n_rows"), (dict(idx=None, B=264, n_rows=263), INVALID, b"without idx"),
-                (dict(idx=ODD4), INVALID, b"idx must be 8-byte"), (dict(grads=ODD), INVALID, b"grads must be 4-byte"),
-                (dict(loss=None), INVALID, b"loss is required"), (dict(loss=ODD), INVALID, b"loss must be 4-byte"),
-                (dict(work=None), INVALID, b"workspace is required"), (dict(work=ODD4), INVALID, b"workspace must be 256-byte"),
-                (dict(discount=float("nan")), INVALID, b"discount is NaN"), (dict(actions=ODD4), INVALID, b"actions must be 8-byte")]
-BATCH_CASES += [(dict([(n, None)]), INVALID, n.encode() + b" is required") for n in PTRS]
-BATCH_CASES += [(dict([(n, ODD)]), INVALID, n.encode() + b" must be") for n in PTRS if n not in ("dones",)]
-
-
-@pytest.mark.parametrize("kw,code,msg", BATCH_CASES)
+@pytest.mark.parametrize("kw,code,msg", TA.batch_cases(NET_CASES + [(dict(shape=None), INVALID, b"NULL shape")], KIND))
 def test_grad_and_step_refusals(lib, kw, code, msg):
-    for fn, who in ((grad, b"reworktrain_grad"), (step, b"reworktrain_step")):
-        assert fn(lib, **kw) == code, kw
-        err = lib.antsrl_last_error()
-        assert msg in err and who in err, (kw, err)
+    KIND.check(("grad", "step"), lib, kw, code, msg)
 
 
 def test_grad_needs_grads_and_step_does_not_say_so(lib):
-    assert grad(lib, grads=None) == INVALID and b"grads is required" in lib.antsrl_last_error()
-    # (step with grads NULL is valid: checked on the GPU, where it may launch)
+    KIND.check_grad_needs_grads(lib)
 
 
-ADAM_CASES = [(dict(step=0), b"step must be >= 1"), (dict(lr=-1.0), b"lr"), (dict(lr=float("nan")), b"lr"),
-              (dict(beta1=1.0), b"beta1"), (dict(beta2=-0.1), b"beta1, beta2"), (dict(eps=0.0), b"eps"),
-              (dict(m=None), b"adam_m is required"), (dict(v=ODD), b"adam_v must be 4-byte")]
-
-
-@pytest.mark.parametrize("kw,msg", ADAM_CASES)
+@pytest.mark.parametrize("kw,msg", TA.ADAM_CASES)
 def test_step_adam_refusals(lib, kw, msg):
-    assert step(lib, **kw) == INVALID
-    err = lib.antsrl_last_error()
-    assert msg in err and b"reworktrain_step" in err, err
+    KIND.check(("step",), lib, kw, INVALID, msg)
 
 
-@pytest.mark.parametrize("kw,code,msg", [(dict(shape=kw), code, msg) for kw, code, msg in SHAPE_CASES]
-                         + [(dict(model=None), INVALID, b"model is required"), (dict(grads=None), INVALID, b"grads is required"),
-                            (dict(m=ODD), INVALID, b"adam_m must be"), (dict(v=None), INVALID, b"adam_v is required")]
-                         + [(kw, INVALID, msg) for kw, msg in ADAM_CASES[:6]])
+@pytest.mark.parametrize("kw,code,msg", TA.apply_cases(NET_CASES))
 def test_apply_refusals(lib, kw, code, msg):
-    assert apply(lib, **kw) == code
-    err = lib.antsrl_last_error()
-    assert msg in err and b"reworktrain_apply" in err, err
+    KIND.check(("apply",), lib, kw, code, msg)
