@@ -43,7 +43,9 @@
 struct __align__(16) AntFrame { double cx, cy, ct, st; }; // perception centre, cos/sin(theta + pi/2)
 // k_update_move: what the update hands to the move of the same ant in registers — x, y after the update (= the new `prev`)
 // and theta; the food value and META word of the cell the ant stands on (the deposit cell's record IS the record of the
-// move's mandible decision: one 16-byte load instead of a pheromone read, a dependent food read and an area-bit read);
+// move's mandible decision: one 16-byte load instead of a pheromone read, a dependent food read and an area-bit read; with
+// separate pheromone buffers the cell's 8-byte {food, META} record beside the pheromone read — in both layouts the move
+// itself reads no food, which is what lets it run without a barrier between its food reads and its food writes);
 // and the move's own per-ant inputs, fetched in front of the update so that their round trip rides with the update's.
 // Round 4 (profiles/history/r04/um_trace.txt: the workgroup's life is a chain of exposed latencies, not bytes): the move's rotation and
 // its float64 sincos — ~400 VALU instructions that need theta and the action only — are evaluated by the UPDATE while its
@@ -56,7 +58,7 @@ struct UmFwd {
     float food, hold;
     uint32_t meta;
     int m, rot, pa;
-    int rec;      // 1: food / meta are valid (interleaved records)
+    int rec;      // 1: food / meta are valid (k_update_move sets it under both record layouts)
     int pre;      // 1: th_new / sn / cs are valid
     int has_rot;  // the step rotates (a rotation tensor was passed)
     int ts;       // the env's timestep after the update

@@ -71,11 +71,14 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
             h_x = fw->x; h_y = fw->y; h_th = fw->th;
             h_hold = fw->hold; h_m = fw->m & 1; h_rot = fw->rot; h_pa = fw->pa;
             h_cprev = frec_xy(p, (int)fw->x, (int)fw->y);
-            // The record was loaded by the update before its anthill collect ran.  Food on the anthill area is all zero once
-            // the collect is done (anthill.py:41-46; the handle only defers an update that needs no full-grid collect), and
-            // nothing else in the update writes food: an area cell reads 0, any other cell what the load returned.
+            // The record was loaded by the update before its anthill collect ran — the whole 16-byte record of the interleaved
+            // layout or the 8-byte {food, META} record beside separate pheromone buffers, update_one_body.  Food on the anthill
+            // area is all zero once the collect is done (anthill.py:41-46; the handle only defers an update that needs no
+            // full-grid collect), and nothing else in the update writes food: an area cell reads 0, any other cell what the
+            // load returned.  NO food read is issued on this side of the barrier between update and move: phase 1b of another
+            // wave writes food with no barrier in front of it (below).
             if (fw->rec) h_q = (fw->meta & META_AREA) ? 0.0f : fw->food;
-            else h_q = food[h_cprev];
+            else h_q = food[h_cprev]; // (no caller: a move that loaded food HERE would need k_move's barrier ahead of phase 1b)
         } else {
             h_x = p.s.x[a1]; h_y = p.s.y[a1]; h_th = p.s.theta[a1];
             h_hold = p.s.holding[a1];
@@ -90,8 +93,11 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
         }
     }
     // (k_update_move: the update of the same launch has resolved last-writer-wins over exactly these cells — prev := cur, so
-    //  the food cell of the exchange is the deposit cell — and hands every ant its verdict, UmFwd::win: no table, no
-    //  inserts, and none of the move's barriers, which exist for the table alone; profiles/r04/um_trace_final.txt slots 10-12)
+    //  the food cell of the exchange is the deposit cell — and hands every ant its verdict, UMFWD_WIN, and its cell's food
+    //  word, UmFwd::food: no table, no inserts, no food read, and none of the move's barriers.  In k_move the barriers order the
+    //  table's inserts ahead of its look-ups AND every food read (the loads above, consumed in phase 1a) ahead of phase 1b's
+    //  food writes; k_update_move, BOTH instantiations, may drop them only because neither a table nor a food read is left on
+    //  this side of its own barrier between update and move; profiles/r04/um_trace_final.txt slots 10-12)
     if (do_step && !fw)
         for (int h = tid; h < p.HT; h += T) {
             hkeys[h] = HASH_EMPTY;
@@ -114,7 +120,8 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
 
     if (do_step) {
         // ---- phase 1a: mandible target (RL_api.py:178-185) + Ants.update_mandibles reads
-        //      (ants.py:102-114).  All food reads happen before any food write.
+        //      (ants.py:102-114).  All food reads happen before any food write: k_move's barrier below stands between them;
+        //      k_update_move's reads were issued by the update, ahead of the barrier between update and move.
         for (int i = tid; i < N; i += T) {
             double x, y;
             uint32_t cprev;
@@ -152,7 +159,7 @@ __device__ __forceinline__ void move_body(const KP &p, const int e, const int8_t
             if (fw) break; // (one ant per thread: a single pass, known at compile time; its slots of the scratch arrays are its own)
             lww_insert(hkeys, hvals, (uint32_t)p.HT - 1, cprev, (uint32_t)i);
         }
-        if (!fw) __syncthreads();
+        if (!fw) __syncthreads(); // (the table is complete, and every food read of phase 1a has returned)
         else __builtin_amdgcn_sched_barrier(0);
         // ---- phase 1b: ants.py:116 `qte[cell] += dropped - taken`, last ant on a cell wins
         for (int i = tid; i < N; i += T) {
@@ -260,7 +267,9 @@ k_update_move(const KP p, const int out_buf, const double g_dep, const double in
         fw.has_rot = rotation != nullptr;
         fw.primed = p.s.reward_primed[e]; // (every thread, one address: a branch around a load would carry its own wait)
     }
-    fw.rec = (ILV && C == 2) ? 1 : 0; // (interleaved records: the update forwards the cell's food / META words)
+    // (ILV: interleaved 16-byte records, else 8-byte {food, META} records — either way the update loads the record of the
+    //  ant's cell and forwards its food / META words: the move reads no food, see move_body)
+    fw.rec = (C == 2) ? 1 : 0;
     // (with_frames: the host's choice per launch — antsrl_capi.hip, meta_observe; 0 = no frame is built, nothing is parked)
     fw.frm_off = with_frames ? (uint32_t)align_up(max(update_one_lds_bytes(p.HT, p.R, (int)(blockDim.x >> 6), p.N), move_lds_bytes(p.HT, p.N)), 16) : 0u;
     update_one_body<C, ILV>(p, e, nullptr, out_buf, smem, g_dep, inv_g_dep, &fw);

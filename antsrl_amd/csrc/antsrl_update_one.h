@@ -23,7 +23,11 @@ __host__ __device__ inline size_t update_one_lds_bytes(int HT, int R, int nwaves
 // `e`: the environment of this workgroup (blockIdx.x, or counted from the other end: env_of_block in antsrl_util.h).
 // FWD_REC (k_update_move on interleaved records, p.ps == 4): the deposit cell's whole 16-byte record is loaded at once and
 // its food / META words are handed to the move — a template parameter so that no run-time branch joins two load forms
-// (the join's register copies would wait for the load on the spot).
+// (the join's register copies would wait for the load on the spot).  Without FWD_REC k_update_move keeps 8-byte {food, META}
+// records beside separate pheromone buffers (KP::fs == 2): the deposit cell's record is loaded beside `pold` and handed over
+// all the same.  EVERY food read of the move is therefore issued here, ahead of the update's barriers and of the
+// __syncthreads() that k_update_move puts between update and move: no wave can read a cell for its mandible decision after
+// another wave of the workgroup has written it in the move's phase 1b, and the move needs no barrier of its own for that.
 template <int C, bool FWD_REC = false>
 __device__ __forceinline__ void update_one_body(const KP &p, const int e, const double *__restrict__ wall_jitter, const int out_buf,
                                                 unsigned char *smem, const double g_dep, const double inv_g_dep, UmFwd *fw = nullptr)
@@ -185,6 +189,16 @@ __device__ __forceinline__ void update_one_body(const KP &p, const int e, const 
     } else {
 #pragma unroll
         for (int c = 0; c < C; ++c) pold[c] = out[(size_t)cell * PS + c];
+        if (fw) {
+            // {food, META} records (k_update_move only runs on the cell-meta layout: fs == 2 here): prev := cur, so this cell is
+            // the food cell of the move's exchange.  Loaded HERE, not by the move: the move's phase 1b writes food, and a load
+            // issued behind the barrier between update and move could return what another wave's winner has already written.
+            // The update's only food writes are the anthill clear on area cells (below), which the move's rule for a
+            // forwarded word covers: an area cell reads 0.
+            const float2 fr = *reinterpret_cast<const float2 *>(&food[frec_xy(p, (int)x, (int)y)]);
+            fw->food = fr.x;
+            fw->meta = __float_as_uint(fr.y);
+        }
     }
     if (fw) {
         // The move's rotation and sincos (RL_api.py:190-196, ants.py:62-67), HERE: they need theta and the action only, and
@@ -233,6 +247,8 @@ __device__ __forceinline__ void update_one_body(const KP &p, const int e, const 
         // The record's first use is HERE (and its food / META words in the move): without this the compiler extracts the area
         // bit right behind the load and waits for it there — the whole round trip in front of the hash inserts and two barriers.
         asm volatile("" : "+v"(pold[0]), "+v"(pold[C - 1]), "+v"(fw->food), "+v"(fw->meta));
+    } else if (fw) {
+        asm volatile("" : "+v"(fw->food), "+v"(fw->meta)); // (the same for the 8-byte record)
     }
     double gain = 0.0;
     if (on) {

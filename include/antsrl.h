@@ -344,6 +344,10 @@ int antsrl_observe(AntsHandle *h, float *obs, float *agent_state, float *reward,
  * antsrl_update, antsrl_reset / antsrl_generate) enqueues or drops it first, on ITS stream argument: results are
  * the same as with an immediate launch, bit for bit; only the moment the kernel is enqueued moves.  Callers that
  * alternate streams between calls must order them as they already have to for the state itself.
+ * In k_update_move the update hands the food word of each ant's cell to the move in a register under BOTH record layouts —
+ * the interleaved 16-byte {p0, p1, food, META} records (ANTSRL_Q_INTERLEAVED) and the 8-byte {food, META} records, tiled or
+ * row-major, beside separate pheromone buffers (explicit sweep, a filter with a radius) — so the move reads no food itself
+ * and every food read of a step precedes every food write, as in the reference (ants.py:102-117).
  * WORKSPACE CONSISTENCY: while an update is deferred, the workspace still holds the pre-update state.  A caller that
  * copies or checkpoints the workspace bytes, records an event "after the update" or times the update on its own calls
  * antsrl_flush first. */

@@ -6,6 +6,9 @@ step and no state read in between, so every update rides inside the next step's 
 with the actions of each crowd recording (ants on the borders, on wall cells, under overlapping rocks, 64 to 192 cells).
 Three environments with a non-zero env_id_base draw different wall jitter and diverge; the oracle draws the same jitter
 from the same generator.  tests/test_crowd_fixtures_cpu.py certifies what these very runs contain.
+Every recording runs twice: as recorded (scaled units and interleaved records everywhere but c03, whose filter has a radius:
+k_update_move<2, true>) and with AntsCfg.phero_mode = PHERO_EXPLICIT_SWEEP ({food, META} records beside separate pheromone
+buffers: k_update_move<2, false>) — the reference's semantics do not depend on the mode, so the oracle's run is the same.
 
 The variant recordings (tests/golden/v*.npz: carry, backward, speed, rotation, threshold and weights off their defaults,
 other masks) are driven the same way wherever the handle defers the update (Q_DEFERRED_UPDATE): k_update_move carries its
@@ -78,14 +81,27 @@ def test_the_backward_move_and_the_threshold_run_deferred():
     assert any(m["reward_threshold"] < 1 and m["max_speed"] == 2.5 and m["reward"] == "all" for m in deferred)
 
 
-@pytest.mark.parametrize("name", crowd_fixture_names() + deferring_variant_names())
-def test_deferred_path_follows_the_oracle_on_crowd_states(name):
+def _cases():
+    """(name, phero_mode): every recording as recorded, under its name as the case's id, and once more under the explicit sweep."""
+    names = crowd_fixture_names() + deferring_variant_names()
+    return ([pytest.param(n, "as_recorded", id=n) for n in names] +
+            [pytest.param(n, "explicit_sweep", id=n + "-explicit_sweep") for n in names])
+
+
+@pytest.mark.parametrize("name,phero_mode", _cases())
+def test_deferred_path_follows_the_oracle_on_crowd_states(name, phero_mode):
+    """explicit_sweep: the same recording with AntsCfg.phero_mode = PHERO_EXPLICIT_SWEEP — the reference's semantics do not
+    depend on it, so the oracle's run is the same; the device keeps 8-byte {food, META} records beside separate pheromone
+    buffers and every deferred update runs in k_update_move<2, false> (as recorded only c03's filter has a radius)."""
     import torch
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     from antsrl_amd import config as cm
     from antsrl_amd.batched import BatchedAntsEnv
     cfg, init, F, meta = load_fixture(name, N_ENVS)
     cfg.env_id_base = ENV_ID_BASE
+    explicit = phero_mode == "explicit_sweep"
+    if explicit:
+        cfg.phero_mode = cm.PHERO_EXPLICIT_SWEEP
     E, N = N_ENVS, cfg.n_ants
     if name in variant_fixture_names():
         env = _variant_handle(cfg)
@@ -95,7 +111,12 @@ def test_deferred_path_follows_the_oracle_on_crowd_states(name):
         env = BatchedAntsEnv(cfg)
         assert env.query(cm.Q_CELL_META) == 1 and env.query(cm.Q_DEFERRED_UPDATE) == 1
         pow2 = not (cfg.w & (cfg.w - 1) or cfg.h & (cfg.h - 1))
-        assert env.query(cm.Q_PERCEIVE_FAST) == int(pow2), "fast k_perceive on power-of-two grids with the default mask, else generic"
+        if explicit:  # (include/antsrl.h, ANTSRL_Q_PERCEIVE_FAST: the fast path reads interleaved records, which a sweep does not keep)
+            assert env.query(cm.Q_PERCEIVE_FAST) == 0, "generic k_perceive on the explicit-sweep layout"
+        else:
+            assert env.query(cm.Q_PERCEIVE_FAST) == int(pow2), "fast k_perceive on power-of-two grids with the default mask, else generic"
+    if explicit:
+        assert env.query(cm.Q_SCALED_UNITS) == 0 and env.query(cm.Q_INTERLEAVED) == 0
     env.reset(init)
     if meta["deposit_strength"] != 1.0:
         env.set_activation(np.broadcast_to(F["init_activation"], (E,) + F["init_activation"].shape).copy(),
