@@ -160,14 +160,16 @@ class _PopulationTrainer(_TargetCounter):
         first_loss) for a step on B rows per member."""
         raise NotImplementedError
 
-    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None) -> torch.Tensor:
+    def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
         slab: gradient, loss and Adam in the entry's launches, whatever P is.  Returns the losses, float32 [P] on the
         device.  spec: the agent's AntsPopSpec of this step (its seeds, learning rates and discounts are this trainer's),
-        else one is built."""
+        else one is built.  loss: where the losses go (as the single trainers' step takes it), else a new tensor."""
         P = self.n_members
         assert idx.device == self.device and idx.dtype == torch.int64 and idx.dim() == 2 and idx.shape[0] == P and idx.is_contiguous()
-        loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        if loss is None:
+            loss = torch.empty((P,), dtype=torch.float32, device=self.device)
+        assert loss.device == self.device and loss.dtype == torch.float32 and loss.shape == (P,) and loss.is_contiguous()
         entry, who, net, tail = self._entry(idx.shape[1])
         first = self.step_count == 0
         self.step_count += 1

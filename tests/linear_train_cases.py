@@ -93,11 +93,18 @@ def _observations(g, N, F, big):
     return x.float()
 
 
-def inputs(case, dones=None, discount=None):
-    """`dones` overrides the case's mode ("mixed", "all", "none") and `discount` its discount."""
+def input_seed(case, member=0):
+    """The seed of inputs(case, member=member): the case's own for member 0, as it always was."""
+    return 1000 * case["F"] + case["B"] + 7 * case["N"] + 1000003 * member
+
+
+def inputs(case, dones=None, discount=None, member=0):
+    """`dones` overrides the case's mode ("mixed", "all", "none") and `discount` its discount.  `member` (a population's:
+    population_stage_cases.py) is folded into the seed, so that every member's net, ring and indices differ in every
+    tensor; member 0 is the case as it stands."""
     F, B, N = case["F"], case["B"], case["N"]
     discount = case["discount"] if discount is None else discount
-    g = torch.Generator().manual_seed(1000 * F + B + 7 * N)
+    g = torch.Generator().manual_seed(input_seed(case, member))
 
     def linear(out_f, in_f):
         b = in_f ** -0.5

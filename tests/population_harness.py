@@ -3,7 +3,8 @@ environment a population acts in with the shard handles of its members, a descri
 PopulationAgent against LinearTrainer; EXPLORE: PopulationExploreAgent against ExploreTrainer and its LinearPolicy without
 a pheromone head) with the two shapes of its acceptance test, and the comparison itself — a population's fused loop
 against every member run ALONE on a shard handle of its own environments, driven entry by entry as
-agent_harness.drive_loop drives an agent.  torch is imported inside the functions, as in the GPU test files."""
+agent_harness.drive_loop drives an agent; and what the tests of a training step alone share (a synthetic ring, a trainer
+without an agent).  torch is imported inside the functions, as in the GPU test files."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -54,6 +55,36 @@ def make_envs(P, Em, N, max_time, bf16, init_seed=5):
         env.reset({k: np.ascontiguousarray(v[p * Em:(p + 1) * Em]) for k, v in init.items()})
         shards.append(env)
     return whole, shards
+
+
+# ---- a training step alone: test_gpu_population_explore.py's and test_gpu_population_stages.py's
+def synthetic_ring(P, L, space, device, seed):
+    """A PopulationReplayMemory of L full rows per member: random observations, agent states, actions in {0, 1, 2},
+    rewards and a fifth of the rows done."""
+    import torch
+    from antsrl_amd.population import PopulationReplayMemory
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    ring = PopulationReplayMemory(P, L, space, device=device)
+    r = lambda *shape: torch.rand(shape, generator=g)  # noqa: E731
+    ring.states.copy_(r(P, L, *space) * 2 - 1)
+    ring.new_states.copy_(r(P, L, *space) * 2 - 1)
+    ring.agent_states.copy_(r(P, L, 2))
+    ring.new_agent_states.copy_(r(P, L, 2))
+    ring.actions.copy_(torch.randint(0, 3, (P, L, 2), generator=g))
+    ring.rewards.copy_(r(P, L) * 4 - 2)
+    ring.dones.copy_(r(P, L) < 0.2)
+    ring.fill = L
+    return ring
+
+
+def population_trainer(cls, P, space, device, seeds, discount, lr):
+    """A population trainer without an agent.  cls: "PopulationLinearTrainer" or "PopulationExploreTrainer"."""
+    import torch
+    from antsrl_amd import population
+    F = int(np.prod(space))
+    g = population._Geometry(P, P, 8, 0, F, torch.float32)  # the training entry reads the spec's members and n_features only
+    return getattr(population, cls)(g, device, seeds, discount, lr, update_target_every=1000)
 
 
 class Kind:

@@ -12,11 +12,16 @@ of explore agents") on the device.
 4. The hand-over: layer1 and layer2 of every member into a PopulationAgent, device to device.
 5. copy_member.
 6. driver.train_population_curriculum: both stages on one handle and monitor, no host read inside an episode."""
+from functools import partial
+
 import numpy as np
 import pytest
 
 from population_harness import EXPLORE as H
-from population_harness import RING
+from population_harness import RING, synthetic_ring
+from population_harness import population_trainer as _population_trainer
+
+population_trainer = partial(_population_trainer, "PopulationExploreTrainer")  # (P, space, device, seeds, discount, lr)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,34 +52,6 @@ def test_the_population_equals_its_members(name):
 
 
 # ---- 2. the step alone
-def synthetic_ring(P, L, space, device, seed):
-    """A PopulationReplayMemory of L full rows per member: random observations, agent states, actions in {0, 1, 2},
-    rewards and a fifth of the rows done."""
-    import torch
-    from antsrl_amd.population import PopulationReplayMemory
-    g = torch.Generator(device="cpu")
-    g.manual_seed(seed)
-    ring = PopulationReplayMemory(P, L, space, device=device)
-    r = lambda *shape: torch.rand(shape, generator=g)  # noqa: E731
-    ring.states.copy_(r(P, L, *space) * 2 - 1)
-    ring.new_states.copy_(r(P, L, *space) * 2 - 1)
-    ring.agent_states.copy_(r(P, L, 2))
-    ring.new_agent_states.copy_(r(P, L, 2))
-    ring.actions.copy_(torch.randint(0, 3, (P, L, 2), generator=g))
-    ring.rewards.copy_(r(P, L) * 4 - 2)
-    ring.dones.copy_(r(P, L) < 0.2)
-    ring.fill = L
-    return ring
-
-
-def population_trainer(P, space, device, seeds, discount, lr):
-    import torch
-    from antsrl_amd.population import PopulationExploreTrainer, _Geometry
-    F = int(np.prod(space))
-    g = _Geometry(P, P, 8, 0, F, torch.float32)  # the training entry reads the spec's members and n_features only
-    return PopulationExploreTrainer(g, device, seeds, discount, lr, update_target_every=1000)
-
-
 @pytest.mark.parametrize("space", [(7, 7, 6), (5, 5, 2)], ids=["F294", "F50"])
 @pytest.mark.parametrize("B", [1, 33, 136, 512])
 def test_the_step_alone(space, B):
