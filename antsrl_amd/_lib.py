@@ -34,7 +34,8 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_checkpoint_map", "antsrl_checkpoint_save", "antsrl_checkpoint_load", "antsrl_fork_envs",
            "antsrl_pop_policy", "antsrl_pop_select", "antsrl_pop_record_pre", "antsrl_pop_record_post",
            "antsrl_pop_lintrain_step", "antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes",
-           "antsrl_pop_exptrain_step")
+           "antsrl_pop_exptrain_step", "antsrl_pop_joint_policy", "antsrl_pop_jointtrain_sizes",
+           "antsrl_pop_jointtrain_step")
 
 _lib = None
 
@@ -212,6 +213,9 @@ def load() -> C.CDLL:
     lib.antsrl_pop_exptrain_sizes.argtypes = [i32, C.c_int64, i32, sz, sz, sz, C.POINTER(C.c_int32)]
     lib.antsrl_pop_exptrain_step.argtypes = [ps] + [vp] * 11 + [C.c_int64, vp, C.c_int64, C.c_int64, C.c_double, C.c_double,
                                                                 C.c_double, vp, vp, vp, i32, vp, vp]
+    lib.antsrl_pop_joint_policy.argtypes = [ps] + [vp] * 7
+    lib.antsrl_pop_jointtrain_sizes.argtypes = lib.antsrl_pop_exptrain_sizes.argtypes
+    lib.antsrl_pop_jointtrain_step.argtypes = lib.antsrl_pop_exptrain_step.argtypes
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -34,7 +34,7 @@ struct JointTrainArgs {
     AdamArgs adam;            // m, v: P floats each
 };
 
-static inline size_t antsrl_jointtrain_floats(int F) { return (size_t)JT_HIDDEN * (F + 2) + JT_HIDDEN + JT_HEADS; }
+__host__ __device__ static inline size_t antsrl_jointtrain_floats(int F) { return (size_t)JT_HIDDEN * (F + 2) + JT_HIDDEN + JT_HEADS; }
 static inline int antsrl_jointtrain_blocks(int B) { return ((B + 31) / 32 + JT_WAVES - 1) / JT_WAVES; }
 // bytes of the partials in front of dh in the workspace (256-byte aligned)
 static inline size_t antsrl_jointtrain_dh_offset(int B) { return ((size_t)antsrl_jointtrain_blocks(B) * JT_PART * 4 + 255) / 256 * 256; }

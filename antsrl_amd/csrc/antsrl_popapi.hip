@@ -2,7 +2,9 @@
 // of linear agents"): antsrl_pop_policy / _select / _record_pre / _record_post / _lintrain_step in front of
 // antsrl_population.hip's kernels; and behind them the population of explore agents ("The population of explore
 // agents"): antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes / _step in front of antsrl_popexplore.hip's, on the same
-// spec rules (select and record are the entries above: that population's net has no pheromone head and its ring none).
+// spec rules (select and record are the entries above: that population's net has no pheromone head and its ring none);
+// and the population of joint agents ("The population of joint agents"): antsrl_pop_joint_policy /
+// antsrl_pop_jointtrain_sizes / _step in front of antsrl_popjoint.hip's, the explore entries with the joint net.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -22,6 +24,7 @@
 #define POP_AGENT_DIM 2
 #define POP_ET_MAX_B (32 * ET_WAVES * 4) // an explore member's minibatch: four forward workgroups, the linear members' 512 rows
 #define POP_ET_LIMIT "at most four forward workgroups"
+#define POP_JT_MAX_B (32 * JT_WAVES * 4) // a joint member's: the same four forward workgroups
 
 static int pop_n_members(const char *who, int n_members)
 {
@@ -277,4 +280,79 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
     a.blocks = antsrl_exptrain_blocks((int)B);
     const PopRunningLoss rl = {running_loss, first_loss != 0};
     return enqueued(antsrl_launch_pop_exptrain(a, t, s->n_members, antsrl_pop_exptrain_stride((int)B), rl, (hipStream_t)stream), who);
+}
+
+// ---- the population of joint agents (antsrl_popjoint.hip) ------------------------------------------------------------------
+
+extern "C" int antsrl_pop_joint_policy(const AntsPopSpec *s, const void *obs, const float *agent_state,
+                                       const float *model_blocks, const float *target_l3, int8_t *rotation,
+                                       int8_t *pheromone, void *stream)
+{
+    const char *who = "pop_joint_policy";
+    PopTable t;
+    int Em = 0;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, Em);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, 16);
+    REQUIRE(agent_state, 4);
+    REQUIRE(model_blocks, 4);
+    REQUIRE(target_l3, 4);
+    REQUIRE(rotation, 1);
+    REQUIRE(pheromone, 1);
+    PopJointPolicyArgs a;
+    a.obs = obs; a.agent_state = agent_state; a.model = model_blocks; a.target_l3 = target_l3;
+    a.rot = rotation; a.ph = pheromone;
+    a.Mm = Em * s->n_ants; a.F = s->n_features; a.P = s->n_members;
+    return enqueued(antsrl_launch_pop_joint_policy(a, s->obs_format == ANTSRL_OBS_BF16, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_jointtrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
+                                           size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
+{
+    const char *who = "pop_jointtrain_sizes";
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_JT_MAX_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    const size_t stride = antsrl_pop_jointtrain_stride((int)B);
+    if (trained_floats) *trained_floats = antsrl_jointtrain_floats(n_features);
+    if (workspace_stride) *workspace_stride = stride;
+    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
+    if (launches) *launches = 2;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *target_l3, float *adam_m,
+                                          float *adam_v, const float *states, const float *agent_states, const int64_t *actions,
+                                          const float *rewards, const float *new_states, const float *new_agent_states,
+                                          const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B, int64_t step,
+                                          double beta1, double beta2, double eps, float *grads, float *loss,
+                                          double *running_loss, int first_loss, void *workspace, void *stream)
+{
+    const char *who = "pop_jointtrain_step";
+    PopTable t;
+    int Em = 0;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_JT_MAX_B, POP_ET_LIMIT);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    REQUIRE(target_l3, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    REQUIRE(idx, 8);
+    REQUIRE(workspace, 256);
+    JointTrainArgs a = {};
+    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table); its partials are the
+    // front of the workspace, its dh behind them
+    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
+                   B, 0.0f, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
+    if (rc != ANTSRL_OK) return rc;
+    a.model = model; a.target_l3 = target_l3;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    a.dh = (float *)((unsigned char *)workspace + antsrl_jointtrain_dh_offset((int)B));
+    a.blocks = antsrl_jointtrain_blocks((int)B);
+    const PopRunningLoss rl = {running_loss, first_loss != 0};
+    return enqueued(antsrl_launch_pop_jointtrain(a, t, s->n_members, antsrl_pop_jointtrain_stride((int)B), rl, (hipStream_t)stream), who);
 }

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
+#include "antsrl_jointtrain.h"
 #include "antsrl_lintrain.h"
 #include "antsrl_memagent.h"
 #include "antsrl_policy_flat.h"
@@ -83,6 +84,35 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_explore_policy(const PopExplorePoli
 // partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_exptrain(const ExpTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
                                                       const PopRunningLoss &rl, hipStream_t st);
+
+// ---- the population of joint agents (antsrl_popjoint.hip; include/antsrl.h, "The population of joint agents") ----
+// A member's net is JointTrainer's flat block of antsrl_jointtrain_floats(F) floats (antsrl_jointtrain.h: w1 | b1 | w2 |
+// b2 | w3 | b3): model, Adam's m and v and grads are [P][floats], the target's layer3 [P][99].  Blocks are 4-byte aligned
+// and no more: every kernel reads and writes them float by float.
+
+// the acting net of every member on its Mm rows: grid (blocks, P); layer1 and layer2 of the LIVE model block, layer3 of
+// the target
+struct PopJointPolicyArgs {
+    const void *obs;          // [P][Mm][F], float32 or bfloat16, dense
+    const float *agent_state; // [P][Mm][2]
+    const float *model;       // [P][antsrl_jointtrain_floats(F)]
+    const float *target_l3;   // [P][99]
+    int8_t *rot, *ph;         // [P][Mm]
+    int Mm, F, P;
+};
+
+// bytes of a member's part of the joint step's workspace: the single step's (partials, then dh [B][32]) rounded up to
+// 256, as antsrl_pop_exptrain_stride
+static inline size_t antsrl_pop_jointtrain_stride(int B)
+{
+    return (antsrl_jointtrain_dh_offset(B) + (size_t)B * JT_HIDDEN * sizeof(float) + 255) / 256 * 256;
+}
+
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_joint_policy(const PopJointPolicyArgs &a, bool obs_bf16, hipStream_t st);
+// a: the single agent's JointTrainArgs for member 0 (B <= 512: at most four forward workgroups per member; idx [P][B];
+// partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_jointtrain(const JointTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
+                                                        const PopRunningLoss &rl, hipStream_t st);
 
 // ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.

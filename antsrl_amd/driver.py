@@ -103,7 +103,8 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
 
 
 def train_population_curriculum(explore_pop, collect_pop, env, gen, episodes, steps: int, *, seed: int = 0,
-                                monitor: Optional[EpisodeMonitor] = None, report_every: int = 50, **kw) -> tuple:
+                                monitor: Optional[EpisodeMonitor] = None, report_every: int = 50, joint_pop=None,
+                                **kw) -> tuple:
     """The linear agent's curriculum for every member of a sweep in one process, on one handle and one monitor:
     train_population on `explore_pop` (a PopulationExploreAgent) for episodes[0] episodes, the hand-over on the device
     (collect_pop.setup(env, explore_population=explore_pop): member p's layer1 and layer2 under member p's collect heads),
@@ -112,17 +113,31 @@ def train_population_curriculum(explore_pop, collect_pop, env, gen, episodes, st
     max_epsilon, save_as — a format with one %s for the stage, "explore" or "collect", before the member's %d) goes to
     both stages.  No file round trip, no per-member launch and no host read of device data inside an episode.
 
-    Returns (stage 1's log, stage 2's log), each train_population's; the monitor's rows are shared, so each log holds the
-    reports of the episodes up to its end, and `member_*` and `epsilons` are the stage's own."""
-    e1, e2 = episodes
+    joint_pop (a PopulationJointAgent of as many members, not set up yet): the curriculum's third stage follows, layer1
+    trained under the collect heads.  `episodes` then has three entries; the hand-over is
+    joint_pop.setup(env, collect_population=collect_pop) (member p's six tensors from member p of stage 2), the episode
+    seeds go on from seed + episodes[0] + episodes[1] and save_as's stage name is "joint".
+
+    Returns (stage 1's log, stage 2's log) and, with joint_pop, stage 3's behind them, each train_population's; the
+    monitor's rows are shared, so each log holds the reports of the episodes up to its end, and `member_*` and
+    `epsilons` are the stage's own."""
+    if joint_pop is None:
+        e1, e2 = episodes
+        e3 = 0
+    else:
+        e1, e2, e3 = episodes
+        assert joint_pop.trainer is None, "the joint population is set up by the hand-over"
+        if joint_pop.n_members != collect_pop.n_members:
+            raise ValueError("the collect population has %d members, the joint population %d" %
+                             (collect_pop.n_members, joint_pop.n_members))
     env = getattr(env, "_backend", env)
     assert collect_pop.trainer is None, "the collect population is set up by the hand-over"
     if explore_pop.n_members != collect_pop.n_members:
         raise ValueError("the explore population has %d members, the collect population %d" %
                          (explore_pop.n_members, collect_pop.n_members))
     mon = monitor if monitor is not None else EpisodeMonitor(env, report_every=report_every,
-                                                             max_reports=max(1, (e1 + e2) * (steps // report_every)),
-                                                             max_episodes=max(1, e1 + e2))
+                                                             max_reports=max(1, (e1 + e2 + e3) * (steps // report_every)),
+                                                             max_episodes=max(1, e1 + e2 + e3))
     save_as = kw.pop("save_as", None)
     stage = lambda name: None if save_as is None else save_as % (name, "%d")  # noqa: E731
     if explore_pop.trainer is None:  # (train_population would, at its first episode: e1 = 0 still hands something over)
@@ -131,7 +146,11 @@ def train_population_curriculum(explore_pop, collect_pop, env, gen, episodes, st
     log1 = train_population(explore_pop, env, gen, e1, steps, seed=seed, monitor=mon, save_as=stage("explore"), **kw)
     collect_pop.setup(env, explore_population=explore_pop)
     log2 = train_population(collect_pop, env, gen, e2, steps, seed=seed + e1, monitor=mon, save_as=stage("collect"), **kw)
-    return log1, log2
+    if joint_pop is None:
+        return log1, log2
+    joint_pop.setup(env, collect_population=collect_pop)
+    log3 = train_population(joint_pop, env, gen, e3, steps, seed=seed + e1 + e2, monitor=mon, save_as=stage("joint"), **kw)
+    return log1, log2, log3
 
 
 def train_episodes(agent, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True,

@@ -16,13 +16,19 @@ on (seed, global environment id, step).
 is, and `PopulationAgent.setup(env, explore_population=pop_e)` puts member p's layer1 and layer2 under member p's collect
 heads, device to device (driver.train_population_curriculum runs both stages on one handle).
 
+`PopulationJointAgent` is the same for P CollectAgent(train_layer1=True)s, the curriculum's third stage
+(antsrl_popjoint.hip): `PopulationJointTrainer` holds JointTrainer's flat blocks with a leading [P] and a
+target layer3 [P, 99], a step is two launches whatever P is, and `PopulationJointAgent.setup(env, collect_population=pop_c)`
+takes member p's six tensors from member p of the second stage, device to device (driver.train_population_curriculum
+runs all three stages on one handle when it is given a `joint_pop`).
+
 The pieces mirror the single agent's: `PopulationLinearTrainer` (LinearTrainer's tensors with a leading [P]),
 `PopulationReplayMemory` (DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
 record the same number of rows at every step) and `PopulationAgent` (CollectAgent's surface, per member where the
 reference's has one model).  The two trainers are one `_PopulationTrainer` (the members' host values, Adam's scalars, the
 counters, `running_loss`, `train` and `step`, whose call hands both entries the same nineteen arguments behind the net's
 pointers) under each net's tensors, dicts and entry, as the two agents are one `_Population`.  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
-changed epsilon costs no device copy.  Out of scope: the joint, memory and rework agents' nets, in-loop acting (a handle
+changed epsilon costs no device copy.  Out of scope: the memory and rework agents' nets, in-loop acting (a handle
 holds one policy pack), B > 512, members of unequal size, training_state.
 """
 from __future__ import annotations
@@ -134,7 +140,7 @@ class PopulationReplayMemory(_Ring):
 
 
 class _PopulationTrainer(_TargetCounter):
-    """What the two population trainers share.  Per member: seed, discount and learning rate.  Common: Adam's betas, eps
+    """What the population trainers share.  Per member: seed, discount and learning rate.  Common: Adam's betas, eps
     and step count, update_target_every and the target counter.  `running_loss` (float64 [P]) is main.py:106-109's
     running loss per member, kept by the training step's last launch from the first training step on.  `_spec`, `train`
     and `step` are here; a subclass allocates its tensors (`grads` among them), holds the dict and load methods of its
@@ -346,6 +352,119 @@ class PopulationExploreTrainer(_PopulationTrainer):
         return super().train(ring, done, generator, minibatch, min_replay, spec)
 
 
+class PopulationJointTrainer(_PopulationTrainer):
+    """JointTrainer's tensors with a leading [P], trained by antsrl_pop_jointtrain_step: two launches whatever P is.
+    model, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat block is JointTrainer's: the six
+    tensors in CollectModel.state_dict()'s order), target_l3 is [P, 99]; member p's weights are initialised as
+    JointTrainer(seed=seed_p)'s, its target layer3 a copy.  The acting net of a member is layer1 and layer2 of its LIVE
+    block and its target layer3.  Per member: discount and learning rate.  Common: Adam's betas, eps and step count,
+    update_target_every and the target counter.  `running_loss` (float64 [P]) is kept by the step's second launch from
+    the first training step on."""
+
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+                 update_target_every: int = 1):
+        super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
+        P, IN = self.n_members, self.n_features + 2
+        self._offs, off = {}, 0
+        for k, shp in zip(LINEAR_NAMES, ((32, IN), (32,), (3, 32), (3,), (3, 32), (3,))):
+            self._offs[k] = (off, shp)
+            off += math.prod(shp)
+        self.trained_floats = self._sizes(1)[0]
+        assert self.trained_floats == off == 32 * IN + 230
+        self._l3 = slice(off - 99, off)  # layer3 in a block: the 99 floats the target copies
+        sds = [linear_init(dict(layer1=(32, IN), layer2=(3, 32), layer3=(3, 32)), s) for s in self.seeds]
+        names = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias", "layer3.weight", "layer3.bias")
+        self.model = torch.stack([torch.cat([sd[k].reshape(-1) for k in names]) for sd in sds]).to(self.device).contiguous()
+        self.target_l3 = self.model[:, self._l3].clone()
+        self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self._work, self._work_B = None, 0
+
+    def _sizes(self, B: int) -> tuple:
+        """antsrl_pop_jointtrain_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches)."""
+        tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+        _lib.check(self._lib.antsrl_pop_jointtrain_sizes(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
+                                                         C.byref(ws), C.byref(n)), "pop_jointtrain_sizes")
+        return tf.value, stride.value, ws.value, n.value
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    def _views(self, flat) -> dict:
+        """The six tensors of one member's flat block (views) under CollectModel's names, in its order."""
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self, p: int) -> dict:
+        """Member p's six tensors (copies) under CollectModel's names, in its order: what the reference loads."""
+        return _clones(self._views(self.model[p]))
+
+    def target_state_dict(self, p: int) -> dict:
+        return linear_target_state_dict(self.state_dict(p), self.target_l3[p])
+
+    def _load(self, sd, p: Optional[int], names) -> None:
+        sd = collect_names(sd)
+        for q in (range(self.n_members) if p is None else (p,)):
+            copy_named(sd, self._views(self.model[q]), names)
+
+    def load_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """JointTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
+        self._load(sd, p, LINEAR_NAMES)
+        rows = slice(None) if p is None else p
+        self.target_l3[rows].copy_(self.model[rows, self._l3])
+
+    def load_explore_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """JointTrainer.load_explore_state_dict for member p (None: every member): layer1 and layer2 from a four-tensor
+        ExploreModel state_dict; layer3, its target copy and Adam's state stay."""
+        self._load(sd, p, LINEAR_NAMES[:4])
+
+    def load_explore_population(self, explore_trainer) -> None:
+        """PopulationLinearTrainer.load_explore_population for this net: a member's explore block (w1 | b1 | w2 | b2) is
+        the front of its joint block, one device copy of [P, 32 (F + 2) + 131]."""
+        _same_population(self, explore_trainer, "explore")
+        n = explore_trainer.trained_floats
+        self.model[:, :n].copy_(explore_trainer.model.to(self.device))
+
+    def load_collect_population(self, linear_trainer) -> None:
+        """The hand-over from stage 2 of the curriculum for every member at once: member p's w1, b1 and heads from a
+        PopulationLinearTrainer into its block (w1 | b1 | heads), three device copies of [P, ...]; target_l3 becomes the
+        block's layer3; Adam's state stays zero as it is.  For every p it is load_state_dict(linear_trainer.state_dict(p), p)."""
+        P, n1 = self.n_members, 32 * (self.n_features + 2)
+        _same_population(self, linear_trainer, "collect")
+        self.model[:, :n1].copy_(linear_trainer.w1.to(self.device).view(P, n1))
+        self.model[:, n1:n1 + 32].copy_(linear_trainer.b1.to(self.device))
+        self.model[:, n1 + 32:].copy_(linear_trainer.heads.to(self.device))
+        self.target_l3.copy_(self.model[:, self._l3])
+
+    def adam_state(self, p: int) -> dict:
+        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0, p])),
+                    exp_avg_sq=_clones(self._views(self._adam[1, p])))
+
+    def sync_target(self) -> None:
+        """target := model for every member: one copy of [P, 99]."""
+        self.target_l3.copy_(self.model[:, self._l3])
+        self.syncs += 1
+
+    # ---- the step -----------------------------------------------------------------------------------------------------
+    def workspace(self, B: int) -> torch.Tensor:
+        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
+        if self._work is None or self._work_B != B:
+            self._work = torch.empty((self._sizes(B)[2],), dtype=torch.uint8, device=self.device)
+            self._work_B = B
+        return self._work
+
+    def _entry(self, B: int) -> tuple:
+        """Two launches; behind first_loss goes the workspace for B rows per member."""
+        return (self._lib.antsrl_pop_jointtrain_step, "pop_jointtrain_step",
+                (_p(self.model), _p(self.target_l3), _p(self._adam[0]), _p(self._adam[1])), (_p(self.workspace(B)),))
+
+
+def _same_population(trainer, other, kind: str) -> None:
+    """A hand-over between two population trainers needs as many members and as wide rows: load_explore_population's
+    words, with the handing population's kind."""
+    if other.n_members != trainer.n_members:
+        raise ValueError("the %s population has %d members, this one %d" % (kind, other.n_members, trainer.n_members))
+    if other.n_features != trainer.n_features:
+        raise ValueError("the %s population's rows have %d features, these %d" % (kind, other.n_features, trainer.n_features))
+
+
 class _Population(_LoopAgent):
     """What the two populations share around their nets: the members' host values, the front of setup, the step's one
     AntsPopSpec, select, the ring, train, the fused loop and the per-member files.  A subclass names its `minibatch`
@@ -508,6 +627,40 @@ class PopulationAgent(_Population):
         """The frozen layer1 included."""
         tr = self.trainer
         return tuple((t, 0) for t in (tr.w1, tr.b1, tr.heads, tr.target_l3, tr._adam))
+
+
+class PopulationJointAgent(PopulationAgent):
+    """P CollectAgents with the freeze of layer1 lifted (CollectAgent(train_layer1=True)) in lockstep: the third stage
+    of the curriculum for every member of a sweep (the module docstring).  members and the common arguments are
+    PopulationAgent's (minibatch 264; B <= 512).  The acting net of a member is layer1 and layer2 of its LIVE block and
+    its target layer3: every training step moves it.  Take its members' nets from a PopulationAgent with
+    setup(env, collect_population=that)."""
+
+    name = "joint_agent_population"
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None,
+              explore_population=None, collect_population=None) -> None:
+        """PopulationAgent.setup with all six tensors trained.  collect_population: a PopulationAgent of as many members,
+        the curriculum's second stage: member p's six tensors come from its member p, device to device
+        (PopulationJointTrainer.load_collect_population); applied last."""
+        self._setup(api_or_env, PopulationJointTrainer)
+        if trained_model is not None:
+            self.load_model(trained_model)
+        if explore_model is not None:
+            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
+        if explore_population is not None:
+            self.trainer.load_explore_population(explore_population.trainer)
+        if collect_population is not None:
+            self.trainer.load_collect_population(collect_population.trainer)
+
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        tr = self.trainer
+        _lib.check(self._lib.antsrl_pop_joint_policy(C.byref(spec), _p(obs), _p(agent_state), _p(tr.model), _p(tr.target_l3),
+                                                     _p(self._rot), _p(self._ph), st), "pop_joint_policy")
+
+    def _member_tensors(self) -> tuple:
+        tr = self.trainer
+        return ((tr.model, 0), (tr.target_l3, 0), (tr._adam, 1))
 
 
 class PopulationExploreAgent(_Population):

@@ -1529,6 +1529,56 @@ int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, const float *ta
                              float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
                              void *stream);
 
+/* The population of joint agents: P CollectAgents with the freeze of layer1 lifted (the net of "The joint training
+ * step": all six tensors trained, layer1 and layer2 live in model and target net, layer3 with a target copy) in lockstep
+ * on one handle — the third stage of the curriculum whose first two stages are the populations above.  The spec, the
+ * members' shares of the handle, the table and the alignment rule are the population of linear agents'; so are select
+ * and record, unchanged: the net has both heads and the ring stores both actions.
+ *
+ * THE DEFINING PROPERTY is the same: member p is, bit for bit, antsrl_policy_mlp on layer1 and layer2 of its LIVE model
+ * block and its TARGET layer3, antsrl_agent_select_actions, antsrl_replay_record_*_plain and antsrl_jointtrain_step run
+ * on a handle of its Em environments, with its own seed, epsilon, discount and learning rate.
+ *
+ * Layout: model, adam_m, adam_v, grads float [P][T], T = 32 (F + 2) + 230 (antsrl_jointtrain_sizes' trained_floats), a
+ * member's block laid out as antsrl_jointtrain_step's (w1 | b1 | w2 | b2 | w3 | b3); target_l3 float [P][99]; loss float
+ * [P]; idx int64 [P][B]; the ring as above.  A member's block and its target layer3 (99 floats) are 4-byte aligned and
+ * no more: the kernels read and write the blocks one float at a time.  The workspace is member-major: member p's part
+ * starts p * workspace_stride bytes behind `workspace` and is laid out as antsrl_jointtrain_step's (partials, then dh
+ * [B][32]); workspace_stride is that entry's workspace_bytes rounded up to 256.
+ *
+ * Refusals (ANTSRL_E_INVALID unless stated), before anything is launched: the spec's, as above;
+ *   antsrl_pop_joint_policy: the flat form does not take n_features (UNSUPPORTED); the alignment rule (UNSUPPORTED);
+ *     obs not 16-byte aligned; any NULL or misaligned pointer (pheromone included: the net has both heads);
+ *   antsrl_pop_jointtrain_sizes: n_features as above; B < 1; B > 512 (UNSUPPORTED); n_members outside [1, ANTSRL_POP_MAX];
+ *   antsrl_pop_jointtrain_step: B < 1; B > 512 (UNSUPPORTED: at most four workgroups of the forward stage per member and
+ *     256 in all); n_rows outside [1, 2^40]; any NULL or misaligned pointer (idx is required and 8-byte aligned; the
+ *     workspace 256-byte aligned; grads and running_loss may be NULL, running_loss 8-byte aligned); Adam's arguments for
+ *     every member's learning_rate.
+ * No entry allocates or synchronises the host; no atomics: equal inputs give equal bits.
+ *
+ *   antsrl_pop_joint_policy    rotation = argmax(layer2(h)) - 1 and pheromone = argmax(layer3(h)) of every member on its
+ *                         own rows: w1, b1, w2, b2 of its LIVE block (model_blocks [P][T]), w3, b3 of its target_l3 [p].
+ *                         One launch, grid (blocks, P), antsrl_pop_policy's launch rule.
+ *   antsrl_pop_jointtrain_sizes  trained_floats = T, workspace_stride, workspace_bytes = n_members * workspace_stride and
+ *                         launches = 2 (any of the four may be NULL).
+ *   antsrl_pop_jointtrain_step   antsrl_jointtrain_step per member in TWO launches: the forward stage on grid
+ *                         (ceil(B / 128), P), the layer1 stage on grid (ceil((F + 3) / 8) + 1, P).  idx, n_rows, step,
+ *                         running_loss and first_loss as antsrl_pop_lintrain_step's; the second launch keeps the
+ *                         running loss.
+ * The target sync is one device copy of [P][99] (model [.][T - 99 .. T) into target_l3), the caller's; the hand-over
+ * from the population of linear agents is a device copy per tensor of w1, b1 and heads into the model block (w1 at 0,
+ * b1 at 32 (F + 2), heads behind it) and of heads [.][99 .. 198) into target_l3. */
+int antsrl_pop_joint_policy(const AntsPopSpec *s, const void *obs, const float *agent_state, const float *model_blocks,
+                            const float *target_l3, int8_t *rotation, int8_t *pheromone, void *stream);
+int antsrl_pop_jointtrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
+                                size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches);
+int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *target_l3, float *adam_m, float *adam_v,
+                               const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                               const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                               const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps,
+                               float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""Times a population of linear agents (--agent collect: antsrl_amd.population.PopulationAgent) or of
-explore agents (--agent explore: PopulationExploreAgent) at config 5's batch: 512 environments x 512 ants
+"""Times a population of linear agents (--agent collect: antsrl_amd.population.PopulationAgent), of
+explore agents (--agent explore: PopulationExploreAgent) or of joint agents (--agent joint:
+PopulationJointAgent against CollectAgent(train_layer1=True)) at config 5's batch: 512 environments x 512 ants
 on 256 x 256 cells, bfloat16 observations, K = 4096 rows recorded per member and step, the agent's minibatch (264 / 256).
 One environment, stepped by every configuration in turn:
 
-  single        CollectAgent / ExploreAgent alone on the whole batch
+  single        CollectAgent / ExploreAgent / CollectAgent(train_layer1=True) alone on the whole batch
   population    the population at P = 1, 4, 16 and 64 (--members; member p owns 512 / P environments)
   sequential    at P = 4 and 16 (--sequential), the same members run one after another on their slices of the batch with
                 the single agent's entries (policy, select, record, train: P launches per stage, 2 P for the explore
-                training step): the only way there was before, and the yardstick
+                and the joint training step): the only way there was before, and the yardstick
 
 For each: rollout_step, and the stages alone, each as the bare call of its entry through the Python object that owns it:
 policy (LinearPolicy.act / the population's acting entry), select (antsrl_agent_select_actions / antsrl_pop_select on the
@@ -19,8 +20,8 @@ median of the repeats with their spread (max - min).  The bar: a
 its train stage each lie below the sequential run's by more than three times the sequential run's own spread.  Prints one
 line per configuration and a JSON summary.
 
-    python profiles/population_bench.py --agent collect|explore [--iters 40] [--repeats 3] [--members 1,4,16,64]
-                                        [--sequential 4,16] [--json profiles/population_<agent|explore>_c5.json]
+    python profiles/population_bench.py --agent collect|explore|joint [--iters 40] [--repeats 3] [--members 1,4,16,64]
+                                        [--sequential 4,16] [--json profiles/population_<agent|explore|joint>_c5.json]
 """
 import argparse
 import ctypes
@@ -39,19 +40,22 @@ from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import CollectAgent, ExploreAgent  # noqa: E402
 from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
-from antsrl_amd.population import PopulationAgent, PopulationExploreAgent  # noqa: E402
+from antsrl_amd.population import PopulationAgent, PopulationExploreAgent, PopulationJointAgent  # noqa: E402
 from antsrl_amd.replay import DeviceReplayMemory  # noqa: E402
 from antsrl_amd.synth import synth_init  # noqa: E402
-from antsrl_amd.train import ExploreTrainer, LinearTrainer  # noqa: E402
+from antsrl_amd.train import ExploreTrainer, JointTrainer, LinearTrainer  # noqa: E402
 
 E, N, F, K, RING, MIN_REPLAY = 512, 512, 294, 4096, 20000, 1000
 NAMES = ("rollout_step", "policy", "select", "record", "train")
 #: per kind: the single agent, the population, the single trainer, whether the net has a pheromone head (without one the
-#: environment is stepped and the ring written with None), the minibatch and the default JSON file
+#: environment is stepped and the ring written with None), the minibatch and the default JSON file; single_kw: what the
+#: single agent's constructor takes on top
 KINDS = dict(collect=dict(single=CollectAgent, population=PopulationAgent, trainer=LinearTrainer, pheromone=True, B=264,
                           json="population_agent_c5.json"),
              explore=dict(single=ExploreAgent, population=PopulationExploreAgent, trainer=ExploreTrainer, pheromone=False, B=256,
-                          json="population_explore_c5.json"))
+                          json="population_explore_c5.json"),
+             joint=dict(single=CollectAgent, single_kw=dict(train_layer1=True), population=PopulationJointAgent, trainer=JointTrainer,
+                        pheromone=True, B=264, json="population_joint_c5.json"))
 
 
 def timed(fn, iters, warmup=5):
@@ -77,7 +81,8 @@ def figures(fns, iters, repeats):
 
 
 def bench_single(kind, env, iters, repeats):
-    ag = kind["single"](epsilon=0.1, record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1)
+    ag = kind["single"](epsilon=0.1, record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1,
+                        **kind.get("single_kw", {}))
     ag.setup(env)
     ag.initialize(env)
     env.observe()
@@ -212,7 +217,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--members", default="1,4,16,64", help="the population sizes to time")
     ap.add_argument("--sequential", default="4,16", help="of those, the sizes to time one member after another as well")
-    ap.add_argument("--json", default=None, help="default: profiles/population_agent_c5.json / population_explore_c5.json")
+    ap.add_argument("--json", default=None, help="default: profiles/population_agent_c5.json / population_explore_c5.json / population_joint_c5.json")
     args = ap.parse_args()
     kind = KINDS[args.agent]
     sizes, seq_sizes = ([int(x) for x in v.split(",") if x] for v in (args.members, args.sequential))
