@@ -35,7 +35,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_pop_policy", "antsrl_pop_select", "antsrl_pop_record_pre", "antsrl_pop_record_post",
            "antsrl_pop_lintrain_step", "antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes",
            "antsrl_pop_exptrain_step", "antsrl_pop_joint_policy", "antsrl_pop_jointtrain_sizes",
-           "antsrl_pop_jointtrain_step")
+           "antsrl_pop_jointtrain_step", "antsrl_pop_memtrain_sizes", "antsrl_pop_memtrain_step")
 
 _lib = None
 
@@ -216,6 +216,8 @@ def load() -> C.CDLL:
     lib.antsrl_pop_joint_policy.argtypes = [ps] + [vp] * 7
     lib.antsrl_pop_jointtrain_sizes.argtypes = lib.antsrl_pop_exptrain_sizes.argtypes
     lib.antsrl_pop_jointtrain_step.argtypes = lib.antsrl_pop_exptrain_step.argtypes
+    lib.antsrl_pop_memtrain_sizes.argtypes = [C.POINTER(AntsMemNetShape), C.c_int64, i32, sz, sz, sz, sz, C.POINTER(C.c_int32)]
+    lib.antsrl_pop_memtrain_step.argtypes = [ps, C.POINTER(AntsMemNetShape)] + lib.antsrl_pop_exptrain_step.argtypes[3:]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -163,8 +163,9 @@ extern "C" int antsrl_policy_memory_tiles(const AntsMemNetShape *s, int precisio
                                            rotation, pheromone, q_out, stream, "policy_memory_tiles", true, tiles, n_live);
 }
 
+int antsrl_memnet_dims(const char *who, const AntsMemNetShape *s, MemNetDims *d) { return memnet_check(s, d, who); }
+
 // ---- the training step (antsrl_memtrain.hip)
-#define MT_MAX_B (1 << 24)
 
 // tensor i of the state_dict (weight, bias per layer) in the state's flat fp32 parameter block, in floats
 struct ParamSpan {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "antsrl_fail.h"
 #include "antsrl_memnet.h"
 
 #define MT_NT 9   // trained layers: L1 L2 L3 L4 R1 R2 R3 P1 P2 (state_dict order)
@@ -49,6 +50,41 @@ struct MemTrainBatch {
     const int64_t *actions, *idx; // actions [N][2] (rotation index, pheromone index); idx [B] or NULL (rows 0..B-1)
     const uint8_t *dones;         // bool [N]
 };
+
+#define MT_MAX_B (1 << 24) // rows of a minibatch
+
+// The grad stage's launch list (7 forward, TD, 6 backward data, weight gradient, finalize: 16 launches) is written once,
+// antsrl_memtrain_grad_list, and run by both forms of the step through a MemTrainRun: the single step's puts k_mt_* on
+// its stream, the population's (antsrl_popmemtrain.hip) k_pop_mt_* on a grid (blocks, P).  The kernels' argument structs
+// are antsrl_memtrain_dev.h's.
+struct MtGemm;
+struct MtTd;
+struct MtWgrad;
+struct MtLayers;
+struct MtFinalize { // k_mt_finalize's arguments behind the layers
+    const float *part;
+    size_t part_chunk;
+    int nchunk;
+    float *grads;
+    const float *lossp;
+    int nloss;
+    float *loss;
+};
+struct MemTrainRun { // blocks: the grid's x dimension
+    virtual hipError_t gemm(const MtGemm &G, unsigned blocks) const = 0;
+    virtual hipError_t td(const MtTd &T, unsigned blocks) const = 0;
+    virtual hipError_t wgrad(const MtWgrad &G, unsigned blocks) const = 0;
+    virtual hipError_t finalize(const MtLayers &T, const MtFinalize &Z, unsigned blocks) const = 0;
+
+protected:
+    ~MemTrainRun() = default;
+};
+hipError_t antsrl_memtrain_grad_list(const MemNetDims &d, const unsigned char *state, const unsigned char *target,
+                                     const MemTrainBatch &b, int B, float discount, float *grads, float *loss,
+                                     unsigned char *work, const MemTrainRun &run);
+
+// the shape's rules of every entry of the net (antsrl_memapi.hip), for an entry elsewhere: *d, or the refusal under `who`
+ANTSRL_INTERNAL int antsrl_memnet_dims(const char *who, const AntsMemNetShape *s, MemNetDims *d);
 
 hipError_t antsrl_launch_memtrain_repack(const MemNetDims &d, unsigned char *state, hipStream_t st);
 hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char *state, const unsigned char *target,

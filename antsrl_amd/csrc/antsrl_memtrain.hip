@@ -35,14 +35,7 @@
 #include <stdint.h>
 #include "antsrl_adam.h"
 #include "antsrl_memtrain.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define MT_WAVES 4    // waves (independent output tiles) per workgroup
-#define MT_MAXP 4     // problems per grouped GEMM launch
-#define MT_MAXCHUNK 64
-#define MT_TD_BLOCK 256
+#include "antsrl_memtrain_dev.h"
 
 static inline size_t mt_al(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int mt_r32(int v) { return (v + 31) / 32 * 32; }
@@ -105,291 +98,48 @@ void antsrl_memtrain_work_layout(const MemNetDims &d, int B, MemTrainWork *W)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// operands
+// kernels: the structs and the device code under them are antsrl_memtrain_dev.h's, the bodies textual includes that
+// the population's kernels run too (antsrl_popmemtrain.hip)
 // ------------------------------------------------------------------------------------------------------------------
-struct MtX { // x = cat[obs.view(F), agent_state(A)] of B minibatch rows, read through idx straight from the replay arrays
-    const float *obs, *ag;
-    const int64_t *idx;
-    int B, F, A;
-};
-
-__device__ __forceinline__ float mt_x(const MtX &X, int b, int k)
-{
-    if (b >= X.B || k >= X.F + X.A) return 0.0f;
-    const size_t row = X.idx ? (size_t)X.idx[b] : (size_t)b;
-    return k < X.F ? X.obs[row * X.F + k] : X.ag[row * X.A + (k - X.F)];
-}
-
-__device__ __forceinline__ bf16x8 mt_row8(const float *p) // 8 consecutive fp32 (32-byte aligned) as bf16
-{
-    const float4 u = reinterpret_cast<const float4 *>(p)[0], v = reinterpret_cast<const float4 *>(p)[1];
-    bf16x8 r;
-    r[0] = (__bf16)u.x; r[1] = (__bf16)u.y; r[2] = (__bf16)u.z; r[3] = (__bf16)u.w;
-    r[4] = (__bf16)v.x; r[5] = (__bf16)v.y; r[6] = (__bf16)v.z; r[7] = (__bf16)v.w;
-    return r;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// grouped GEMM: forward and backward data
-// ------------------------------------------------------------------------------------------------------------------
-struct MtProb {
-    const float *a; int lda;              // A rows [Bp][lda] fp32, or NULL: the gathered x of net `xnet`
-    const __bf16 *w; int ldw; int K;      // B(k, j) = w[j * ldw + k]; K a multiple of 32
-    const float *a2; int lda2;            // optional second segment, summed into the same accumulator (a2 NULL: none)
-    const __bf16 *w2; int ldw2; int K2;
-    const float *bias; int nb;            // fp32 bias of the nb real columns, or NULL
-    const float *mask; int ldm;           // output *= (mask > 0), or NULL
-    float *c; int ldc; int N;             // output [Bp][ldc], N columns (a multiple of 32)
-    int relu, resid, xnet;                // relu; add the fp32 x of net xnet (the residual); which x feeds A
-    int tiles, tile0;
-};
-struct MtGemm {
-    MtProb p[MT_MAXP];
-    MtX x[2]; // 0: target rows (new_states, new_agent_states), 1: model rows (states, agent_states)
-    int np;
-};
-
-__device__ __forceinline__ f32x16 mt_segment(f32x16 acc, const float *a, int lda, const MtX *X, const __bf16 *w, int ldw,
-                                             int K, int arow, int bcol, int h)
-{
-    const __bf16 *wp = w + (size_t)bcol * ldw + 8 * h;
-    if (a) {
-        const float *ap = a + (size_t)arow * lda + 8 * h;
-        for (int k0 = 0; k0 < K; k0 += 16)
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(mt_row8(ap + k0), *reinterpret_cast<const bf16x8 *>(wp + k0), acc, 0, 0, 0);
-    } else {
-        for (int k0 = 0; k0 < K; k0 += 16) {
-            bf16x8 av;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) av[j] = (__bf16)mt_x(*X, arow, k0 + 8 * h + j);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, *reinterpret_cast<const bf16x8 *>(wp + k0), acc, 0, 0, 0);
-        }
-    }
-    return acc;
-}
-
+// grouped GEMM, forward and backward data
 __global__ void __launch_bounds__(64 * MT_WAVES) k_mt_gemm(MtGemm G)
 {
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int wave = blockIdx.x * MT_WAVES + (threadIdx.x >> 6);
-    int pi = -1;
-#pragma unroll
-    for (int i = 0; i < MT_MAXP; ++i)
-        if (i < G.np && wave >= G.p[i].tile0 && wave < G.p[i].tile0 + G.p[i].tiles) pi = i;
-    if (pi < 0) return;
-    const MtProb &P = G.p[pi];
-    const int t = wave - P.tile0, ntn = P.N / 32;
-    const int m0 = (t / ntn) * 32, n0 = (t % ntn) * 32;
-    f32x16 acc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
-    acc = mt_segment(acc, P.a, P.lda, &G.x[P.xnet], P.w, P.ldw, P.K, m0 + r, n0 + r, h);
-    if (P.a2) acc = mt_segment(acc, P.a2, P.lda2, &G.x[P.xnet], P.w2, P.ldw2, P.K2, m0 + r, n0 + r, h);
-    const int j = n0 + r;
-    const float bj = (P.bias && j < P.nb) ? P.bias[j] : 0.0f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int i = m0 + 8 * (g >> 2) + 4 * h + (g & 3);
-        float v = acc[g] + bj;
-        if (P.resid) v = v + mt_x(G.x[P.xnet], i, j);
-        if (P.relu) v = fmaxf(v, 0.0f);
-        if (P.mask) v = P.mask[(size_t)i * P.ldm + j] > 0.0f ? v : 0.0f;
-        P.c[(size_t)i * P.ldc + j] = v;
-    }
+    const MtAsFilled at{};
+#include "antsrl_memtrain_gemm_body.inc"
 }
 
-// ------------------------------------------------------------------------------------------------------------------
 // TD targets, dL/dq and the loss partials: one thread per row
-// ------------------------------------------------------------------------------------------------------------------
-struct MtTd {
-    const float *tqr, *tqp, *qr, *qp; // target / model head outputs [Bp][32]
-    float *dqr, *dqp;                 // [Bp][32]
-    const float *rewards;
-    const int64_t *actions, *idx;
-    const uint8_t *dones;
-    float *lossp;
-    int B, n_rot, n_ph;
-    float discount, norm_r, norm_p, inv_r, inv_p; // norm = 2 / (B n_head), inv = 1 / (B n_head)
-};
-
-__device__ __forceinline__ float mt_max(const float *q, int n)
-{
-    float m = q[0];
-    for (int k = 1; k < n; ++k) m = q[k] > m ? q[k] : m;
-    return m;
-}
-
 __global__ void __launch_bounds__(MT_TD_BLOCK) k_mt_td(MtTd T)
 {
-    __shared__ float red[MT_TD_BLOCK];
-    const int b = blockIdx.x * MT_TD_BLOCK + threadIdx.x;
-    const int Bp = (T.B + 31) / 32 * 32;
-    float contrib = 0.0f;
-    if (b < Bp) {
-        float dr = 0.0f, dp = 0.0f;
-        int ar = -1, ap = -1;
-        if (b < T.B) {
-            const size_t row = T.idx ? (size_t)T.idx[b] : (size_t)b;
-            const int64_t a0 = T.actions[2 * row], a1 = T.actions[2 * row + 1];
-            const float rew = T.rewards[row], nd = T.dones[row] ? 0.0f : 1.0f;
-            const size_t o = (size_t)b * 32;
-            if (a0 >= 0 && a0 < T.n_rot) {
-                ar = (int)a0;
-                const float y = rew + (T.discount * mt_max(T.tqr + o, T.n_rot)) * nd;
-                dr = T.qr[o + ar] - y;
-            }
-            if (a1 >= 0 && a1 < T.n_ph) {
-                ap = (int)a1;
-                const float y = rew + (T.discount * mt_max(T.tqp + o, T.n_ph)) * nd;
-                dp = T.qp[o + ap] - y;
-            }
-            contrib = dr * dr * T.inv_r + dp * dp * T.inv_p;
-        }
-        float4 *gr = reinterpret_cast<float4 *>(T.dqr + (size_t)b * 32), *gp = reinterpret_cast<float4 *>(T.dqp + (size_t)b * 32);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            float4 u, v;
-            u.x = 4 * c == ar ? dr * T.norm_r : 0.0f; u.y = 4 * c + 1 == ar ? dr * T.norm_r : 0.0f;
-            u.z = 4 * c + 2 == ar ? dr * T.norm_r : 0.0f; u.w = 4 * c + 3 == ar ? dr * T.norm_r : 0.0f;
-            v.x = 4 * c == ap ? dp * T.norm_p : 0.0f; v.y = 4 * c + 1 == ap ? dp * T.norm_p : 0.0f;
-            v.z = 4 * c + 2 == ap ? dp * T.norm_p : 0.0f; v.w = 4 * c + 3 == ap ? dp * T.norm_p : 0.0f;
-            gr[c] = u;
-            gp[c] = v;
-        }
-    }
-    red[threadIdx.x] = contrib; // fixed-order tree: deterministic
-    __syncthreads();
-    for (int s = MT_TD_BLOCK / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) T.lossp[blockIdx.x] = red[0];
+#include "antsrl_memtrain_td_body.inc"
 }
 
-// ------------------------------------------------------------------------------------------------------------------
 // weight gradients: one wave per (row chunk, 32 x 32 tile of dW); the in-tile-0 waves also sum db over their chunk
-// ------------------------------------------------------------------------------------------------------------------
-struct MtWg {
-    const float *dy; int lddy;  // dOut [Bp][lddy]
-    const float *x; int ldx;    // In [Bp][ldx], or NULL: the gathered model x
-    int Np, Kp;
-    size_t off;                 // this layer's block in a chunk's partials
-    int tiles, tile0;           // (Np / 32) (Kp / 32) nchunk
-};
-struct MtWgrad {
-    MtWg p[MT_NT];
-    MtX x;
-    float *part;
-    size_t part_chunk;
-    int chunk, Bp, np;
-};
-
 __global__ void __launch_bounds__(64 * MT_WAVES) k_mt_wgrad(MtWgrad G)
 {
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int wave = blockIdx.x * MT_WAVES + (threadIdx.x >> 6);
-    int pi = -1;
-    for (int i = 0; i < G.np; ++i)
-        if (wave >= G.p[i].tile0 && wave < G.p[i].tile0 + G.p[i].tiles) pi = i;
-    if (pi < 0) return;
-    const MtWg &P = G.p[pi];
-    const int tpc = (P.Np / 32) * (P.Kp / 32), t = wave - P.tile0;
-    const int c = t / tpc, o0 = ((t % tpc) / (P.Kp / 32)) * 32, i0 = ((t % tpc) % (P.Kp / 32)) * 32;
-    const int b0 = c * G.chunk, b1 = min(b0 + G.chunk, G.Bp);
-    f32x16 acc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[g] = 0.0f;
-    for (int k0 = b0; k0 < b1; k0 += 16) {
-        bf16x8 av, bv;
-        const size_t kb = (size_t)(k0 + 8 * h);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) av[j] = (__bf16)P.dy[(kb + j) * P.lddy + o0 + r];
-        if (P.x) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bv[j] = (__bf16)P.x[(kb + j) * P.ldx + i0 + r];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) bv[j] = (__bf16)mt_x(G.x, (int)kb + j, i0 + r);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, bv, acc, 0, 0, 0);
-    }
-    float *out = G.part + (size_t)c * G.part_chunk + P.off;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) out[(size_t)(o0 + 8 * (g >> 2) + 4 * h + (g & 3)) * P.Kp + i0 + r] = acc[g];
-    if (i0 == 0 && h == 0) { // db over the chunk, fp32, rows in order
-        float s = 0.0f;
-        for (int b = b0; b < b1; ++b) s += P.dy[(size_t)b * P.lddy + o0 + r];
-        out[(size_t)P.Np * P.Kp + o0 + r] = s;
-    }
+    const MtAsFilled at{};
+#include "antsrl_memtrain_wgrad_body.inc"
 }
 
-// ------------------------------------------------------------------------------------------------------------------
 // finalize: sum the chunk partials in ascending order into the flat gradient; the last thread sums the loss partials
-// ------------------------------------------------------------------------------------------------------------------
-struct MtLayers { // the trained layers' place in the flat buffer and in the partials / packs
-    size_t poff[MT_NT], woff[MT_NT], wtoff[MT_NT], part[MT_NT];
-    int out[MT_NT], in[MT_NT], Np[MT_NT], Kp[MT_NT];
-    size_t trained;
-};
-
-__device__ __forceinline__ int mt_layer_of(const MtLayers &T, size_t e)
-{
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < MT_NT; ++i) l = e >= T.poff[i] ? i : l;
-    return l;
-}
-
 __global__ void __launch_bounds__(256) k_mt_finalize(MtLayers T, const float *part, size_t part_chunk, int nchunk,
                                                      float *grads, const float *lossp, int nloss, float *loss)
 {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < T.trained) {
-        const int l = mt_layer_of(T, e);
-        const size_t k = e - T.poff[l], nw = (size_t)T.out[l] * T.in[l];
-        const size_t src = T.part[l] + (k < nw ? (k / T.in[l]) * T.Kp[l] + k % T.in[l] : (size_t)T.Np[l] * T.Kp[l] + (k - nw));
-        float s = 0.0f;
-        for (int c = 0; c < nchunk; ++c) s += part[(size_t)c * part_chunk + src];
-        grads[e] = s;
-    } else if (e == T.trained) {
-        float s = 0.0f;
-        for (int i = 0; i < nloss; ++i) s += lossp[i];
-        *loss = s;
-    }
+#include "antsrl_memtrain_finalize_body.inc"
 }
 
-// ------------------------------------------------------------------------------------------------------------------
 // apply: Adam + repack (update = 0: repack only)
-// ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_mt_adam(MtLayers T, float *params, float *m, float *v, __bf16 *pack,
                                                  const float *grads, int update, float step_size, float bc2_sqrt,
                                                  float w1, float beta2, float w2, float eps)
 {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= T.trained) return;
-    float p = params[e];
-    if (update) {
-        const float g = grads[e];
-        float mm = m[e], vv = v[e];
-        p = adam_element(p, g, mm, vv, step_size, bc2_sqrt, w1, beta2, w2, eps); // antsrl_adam.h
-        m[e] = mm;
-        v[e] = vv;
-        params[e] = p;
-    }
-    const int l = mt_layer_of(T, e);
-    const size_t k = e - T.poff[l];
-    if (k < (size_t)T.out[l] * T.in[l]) {
-        const int o = (int)(k / T.in[l]), i = (int)(k % T.in[l]);
-        const __bf16 pb = (__bf16)p;
-        pack[T.woff[l] + (size_t)o * T.Kp[l] + i] = pb;
-        pack[T.wtoff[l] + (size_t)i * T.Np[l] + o] = pb;
-    }
+#include "antsrl_memtrain_adam_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------------------------
-static MtLayers mt_layers(const MemTrainLayout &L, const MemTrainWork *W)
+MtLayers antsrl_memtrain_layers(const MemTrainLayout &L, const MemTrainWork *W)
 {
     MtLayers T;
     for (int l = 0; l < MT_NT; ++l) {
@@ -411,7 +161,7 @@ hipError_t antsrl_launch_memtrain_apply(const MemNetDims &d, unsigned char *stat
 {
     MemTrainLayout L;
     antsrl_memtrain_state_layout(d, &L);
-    const MtLayers T = mt_layers(L, nullptr);
+    const MtLayers T = antsrl_memtrain_layers(L, nullptr);
     const unsigned blocks = (unsigned)((L.trained_floats + 255) / 256);
     hipLaunchKernelGGL(k_mt_adam, dim3(blocks), dim3(256), 0, st, T, reinterpret_cast<float *>(state),
                        reinterpret_cast<float *>(state + L.m_off), reinterpret_cast<float *>(state + L.v_off),
@@ -438,15 +188,17 @@ static void mt_add(MtLaunch &Lc, MtProb p, int Bp)
     Lc.G.p[Lc.G.np++] = p;
 }
 
-static hipError_t mt_run(MtLaunch &Lc, hipStream_t st)
+static hipError_t mt_run(MtLaunch &Lc, const MemTrainRun &run)
 {
-    hipLaunchKernelGGL(k_mt_gemm, dim3((Lc.tiles + MT_WAVES - 1) / MT_WAVES), dim3(64 * MT_WAVES), 0, st, Lc.G);
-    return hipGetLastError();
+    return run.gemm(Lc.G, (unsigned)((Lc.tiles + MT_WAVES - 1) / MT_WAVES));
 }
 
-hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char *state, const unsigned char *target,
-                                       const MemTrainBatch &bt, int B, float discount, float *grads, float *loss,
-                                       unsigned char *work, hipStream_t st)
+// The step's launch list, written once: which problems go into which launch, and in what order.  `run` puts each
+// kernel on its stream: the single step's k_mt_* (below), or the population's k_pop_mt_* on a grid (x, P) with every
+// argument as it is filled here, for member 0.
+hipError_t antsrl_memtrain_grad_list(const MemNetDims &d, const unsigned char *state, const unsigned char *target,
+                                     const MemTrainBatch &bt, int B, float discount, float *grads, float *loss,
+                                     unsigned char *work, const MemTrainRun &run)
 {
     MemTrainLayout L;
     antsrl_memtrain_state_layout(d, &L);
@@ -491,7 +243,7 @@ hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char 
                 mt_add(Lc, p, Bp);
             }
         }
-        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+        if ((e = mt_run(Lc, run)) != hipSuccess) return e;
     }
 
     // TD targets and dL/dq
@@ -507,8 +259,7 @@ hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char 
         T.norm_p = (float)(2.0 / ((double)B * d.n_ph));
         T.inv_r = (float)(1.0 / ((double)B * d.n_rot));
         T.inv_p = (float)(1.0 / ((double)B * d.n_ph));
-        hipLaunchKernelGGL(k_mt_td, dim3(W.nloss), dim3(MT_TD_BLOCK), 0, st, T);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = run.td(T, (unsigned)W.nloss)) != hipSuccess) return e;
     }
 
     // backward data (model): dIn = dOut . W (pack W^T), masked by the ReLU of the layer that produced In
@@ -527,12 +278,12 @@ hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char 
         MtLaunch Lc{};
         mt_add(Lc, bwd(6), Bp); // R3 -> dr2
         mt_add(Lc, bwd(8), Bp); // P2 -> dp1
-        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+        if ((e = mt_run(Lc, run)) != hipSuccess) return e;
     }
     {
         MtLaunch Lc{};
         mt_add(Lc, bwd(5), Bp); // R2 -> dr1
-        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+        if ((e = mt_run(Lc, run)) != hipSuccess) return e;
     }
     {
         MtLaunch Lc{};
@@ -540,12 +291,12 @@ hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char 
         p.a2 = dout[7]; p.lda2 = L.Np[7];
         p.w2 = WTp(1, 7); p.ldw2 = L.Np[7]; p.K2 = L.Np[7];
         mt_add(Lc, p, Bp);
-        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+        if ((e = mt_run(Lc, run)) != hipSuccess) return e;
     }
     for (int l = 3; l >= 1; --l) { // L4 -> dh3, L3 -> dh2, L2 -> dh1
         MtLaunch Lc{};
         mt_add(Lc, bwd(l), Bp);
-        if ((e = mt_run(Lc, st)) != hipSuccess) return e;
+        if ((e = mt_run(Lc, run)) != hipSuccess) return e;
     }
 
     // weight gradients: row-chunk partials
@@ -568,15 +319,47 @@ hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char 
             p.tile0 = tiles;
             tiles += p.tiles;
         }
-        hipLaunchKernelGGL(k_mt_wgrad, dim3((tiles + MT_WAVES - 1) / MT_WAVES), dim3(64 * MT_WAVES), 0, st, G);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = run.wgrad(G, (unsigned)((tiles + MT_WAVES - 1) / MT_WAVES))) != hipSuccess) return e;
     }
     {
-        const MtLayers T = mt_layers(L, &W);
+        const MtLayers T = antsrl_memtrain_layers(L, &W);
         const unsigned blocks = (unsigned)((L.trained_floats + 1 + 255) / 256);
-        hipLaunchKernelGGL(k_mt_finalize, dim3(blocks), dim3(256), 0, st, T, (const float *)(wk + W.part), W.part_chunk,
-                           W.nchunk, grads, (const float *)(wk + W.lossp), W.nloss, loss);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        const MtFinalize Z = {wk + W.part, W.part_chunk, W.nchunk, grads, wk + W.lossp, W.nloss, loss};
+        if ((e = run.finalize(T, Z, blocks)) != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// the single step: the list's kernels as they are, on one stream
+struct MtRunSingle final : MemTrainRun {
+    hipStream_t st;
+    explicit MtRunSingle(hipStream_t s) : st(s) {}
+    hipError_t gemm(const MtGemm &G, unsigned blocks) const override
+    {
+        hipLaunchKernelGGL(k_mt_gemm, dim3(blocks), dim3(64 * MT_WAVES), 0, st, G);
+        return hipGetLastError();
+    }
+    hipError_t td(const MtTd &T, unsigned blocks) const override
+    {
+        hipLaunchKernelGGL(k_mt_td, dim3(blocks), dim3(MT_TD_BLOCK), 0, st, T);
+        return hipGetLastError();
+    }
+    hipError_t wgrad(const MtWgrad &G, unsigned blocks) const override
+    {
+        hipLaunchKernelGGL(k_mt_wgrad, dim3(blocks), dim3(64 * MT_WAVES), 0, st, G);
+        return hipGetLastError();
+    }
+    hipError_t finalize(const MtLayers &T, const MtFinalize &Z, unsigned blocks) const override
+    {
+        hipLaunchKernelGGL(k_mt_finalize, dim3(blocks), dim3(256), 0, st, T, Z.part, Z.part_chunk, Z.nchunk, Z.grads, Z.lossp,
+                           Z.nloss, Z.loss);
+        return hipGetLastError();
+    }
+};
+
+hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char *state, const unsigned char *target,
+                                       const MemTrainBatch &bt, int B, float discount, float *grads, float *loss,
+                                       unsigned char *work, hipStream_t st)
+{
+    return antsrl_memtrain_grad_list(d, state, target, bt, B, discount, grads, loss, work, MtRunSingle(st));
 }

@@ -4,7 +4,9 @@
 // agents"): antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes / _step in front of antsrl_popexplore.hip's, on the same
 // spec rules (select and record are the entries above: that population's net has no pheromone head and its ring none);
 // and the population of joint agents ("The population of joint agents"): antsrl_pop_joint_policy /
-// antsrl_pop_jointtrain_sizes / _step in front of antsrl_popjoint.hip's, the explore entries with the joint net.
+// antsrl_pop_jointtrain_sizes / _step in front of antsrl_popjoint.hip's, the explore entries with the joint net; and the
+// training step of the population of memory nets ("The population of memory nets"): antsrl_pop_memtrain_sizes / _step in
+// front of antsrl_popmemtrain.hip's.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -355,4 +357,85 @@ extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, co
     a.blocks = antsrl_jointtrain_blocks((int)B);
     const PopRunningLoss rl = {running_loss, first_loss != 0};
     return enqueued(antsrl_launch_pop_jointtrain(a, t, s->n_members, antsrl_pop_jointtrain_stride((int)B), rl, (hipStream_t)stream), who);
+}
+
+// ---- the population of memory nets (antsrl_popmemtrain.hip) ----------------------------------------------------------------
+
+// the shape's rules under the entry's name, then the two strides: the single trainer's state and workspace bytes, which
+// must be multiples of 256 for every member's blocks to start as aligned as a single trainer's
+static int pop_mem_layout(const char *who, const AntsMemNetShape *shape, int64_t B, MemNetDims *d, MemTrainLayout *L,
+                          MemTrainWork *W)
+{
+    int rc = antsrl_memnet_dims(who, shape, d);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, MT_MAX_B);
+    if (rc != ANTSRL_OK) return rc;
+    antsrl_memtrain_state_layout(*d, L);
+    antsrl_memtrain_work_layout(*d, (int)B, W);
+    if (L->bytes % 256 || W->bytes % 256)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: a member's state of %zu bytes and workspace of %zu bytes must be multiples of 256",
+                    who, L->bytes, W->bytes);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_memtrain_sizes(const AntsMemNetShape *shape, int64_t B, int32_t n_members, size_t *state_stride,
+                                         size_t *trained_floats, size_t *work_stride, size_t *workspace_bytes,
+                                         int32_t *launches)
+{
+    const char *who = "pop_memtrain_sizes";
+    MemNetDims d;
+    MemTrainLayout L;
+    MemTrainWork W;
+    int rc = pop_mem_layout(who, shape, B, &d, &L, &W);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    if (state_stride) *state_stride = L.bytes;
+    if (trained_floats) *trained_floats = L.trained_floats;
+    if (work_stride) *work_stride = W.bytes;
+    if (workspace_bytes) *workspace_bytes = W.bytes * (size_t)n_members;
+    if (launches) *launches = 17;
+    return ANTSRL_OK;
+}
+
+// antsrl_dqn_minibatch's fields around the memory step's batch
+struct PopMemBatch : MemTrainBatch {
+    float *grads, *loss;
+    long long n_rows;
+    int B;
+    float discount;
+};
+
+extern "C" int antsrl_pop_memtrain_step(const AntsPopSpec *s, const AntsMemNetShape *shape, void *net_states,
+                                        const void *target_states, const float *states, const float *agent_states,
+                                        const int64_t *actions, const float *rewards, const float *new_states,
+                                        const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                                        const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps,
+                                        float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
+                                        void *stream)
+{
+    const char *who = "pop_memtrain_step";
+    PopTable t;
+    int Em = 0;
+    MemNetDims d;
+    MemTrainLayout L;
+    MemTrainWork W;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = pop_mem_layout(who, shape, B, &d, &L, &W);
+    if (rc != ANTSRL_OK) return rc;
+    if (s->n_features != shape->n_features)
+        return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
+    REQUIRE(net_states, 256);
+    REQUIRE(target_states, 256);
+    REQUIRE(idx, 8);
+    REQUIRE(workspace, 256);
+    PopMemBatch bt = {};
+    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table)
+    rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx, B,
+                              0.0f, grads, true, loss, &bt);
+    AdamArgs adam = {};
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &adam, &t);
+    if (rc != ANTSRL_OK) return rc;
+    const PopRunningLoss rl = {running_loss, first_loss != 0};
+    return enqueued(antsrl_launch_pop_memtrain(d, (unsigned char *)net_states, (const unsigned char *)target_states, bt, n_rows,
+                                               (int)B, t, s->n_members, adam, grads, loss, rl, (unsigned char *)workspace,
+                                               (hipStream_t)stream), who);
 }

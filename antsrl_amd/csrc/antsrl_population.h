@@ -11,11 +11,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "antsrl_adam.h"
 #include "antsrl_exptrain.h"
 #include "antsrl_fail.h"
 #include "antsrl_jointtrain.h"
 #include "antsrl_lintrain.h"
 #include "antsrl_memagent.h"
+#include "antsrl_memtrain.h"
 #include "antsrl_policy_flat.h"
 
 // The members' hyper-parameters: host values that travel BY VALUE in the kernel arguments (as EnvCopyTable does,
@@ -113,6 +115,17 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_joint_policy(const PopJointPolicyAr
 // partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_jointtrain(const JointTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
                                                         const PopRunningLoss &rl, hipStream_t st);
+
+// ---- the population of memory nets (antsrl_popmemtrain.hip; include/antsrl.h, "The population of memory nets") ----
+// A member's net is MemoryTrainer's state buffer (antsrl_memtrain.h: masters | m | v | packs): states and targets are
+// [P][MemTrainLayout::bytes], the workspace [P][MemTrainWork::bytes], both strides multiples of 256 bytes (refused
+// otherwise); grads [P][trained_floats], loss [P], idx [P][B] (required); the ring's arrays with a leading [P] of `rows`
+// rows each, agent_states rows 2 + mem floats wide.  bt holds member 0's arrays; the table gives discount and step
+// size, adam the common scalars.  17 launches: the single step's 16 of the grad stage and its apply, each on a grid (x, P).
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memtrain(const MemNetDims &d, unsigned char *states, const unsigned char *targets,
+                                                      const MemTrainBatch &bt, long long rows, int B, const PopTable &t, int P,
+                                                      const AdamArgs &adam, float *grads, float *loss, const PopRunningLoss &rl,
+                                                      unsigned char *work, hipStream_t st);
 
 // ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.

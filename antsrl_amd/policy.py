@@ -153,6 +153,11 @@ def memnet_param_shapes(n_features: int, power: int, mem_size: int, n_rot: int, 
                 memory_layer1=(h2, D), memory_layer2=(h2, h2), memory_layer3=(mem_size, h2), forget_layer=(mem_size, h2))
 
 
+def memnet_shape(n_features: int, power: int, mem_size: int, n_rot: int, n_ph: int) -> _lib.AntsMemNetShape:
+    """The ABI's shape of CollectModelMemory: agent_dim 2, the three hidden widths from `power`."""
+    return _lib.AntsMemNetShape(n_features, 2, mem_size, 2 ** (1 + power), 2 ** (2 + power), 2 ** (3 + power), n_rot, n_ph)
+
+
 class MemoryPolicy:
     """The reference's recurrent memory agent net `CollectModelMemory` (agents/collect_agent_memory.py:24-78, the net
     main.py's CollectAgentMemory trains) evaluated on the device by `antsrl_policy_memory_ex`.
@@ -180,8 +185,7 @@ class MemoryPolicy:
     def _set(self, sd, power, mem_size, n_rot, n_ph):
         self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
         self.params = {k: torch.as_tensor(v).to(self.device, torch.float32).contiguous() for k, v in sd.items()}
-        self.shape = _lib.AntsMemNetShape(self.n_features, 2, mem_size, 2 ** (1 + power), 2 ** (2 + power),
-                                          2 ** (3 + power), n_rot, n_ph)
+        self.shape = memnet_shape(self.n_features, power, mem_size, n_rot, n_ph)
         n = C.c_size_t()
         _lib.check(self._lib.antsrl_memnet_packed_bytes_ex(C.byref(self.shape), self._precision_id(), C.byref(n)),
                    "memnet_packed_bytes_ex")

@@ -28,8 +28,16 @@ record the same number of rows at every step) and `PopulationAgent` (CollectAgen
 reference's has one model).  The two trainers are one `_PopulationTrainer` (the members' host values, Adam's scalars, the
 counters, `running_loss`, `train` and `step`, whose call hands both entries the same nineteen arguments behind the net's
 pointers) under each net's tensors, dicts and entry, as the two agents are one `_Population`.  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
-changed epsilon costs no device copy.  Out of scope: the memory and rework agents' nets, in-loop acting (a handle
-holds one policy pack), B > 512, members of unequal size, training_state.
+changed epsilon costs no device copy.
+
+`PopulationMemoryTrainer` is the training step of P memory nets (MemoryTrainer's, the net main.py drives) in the 17
+launches of one (antsrl_popmemtrain.hip): a member's state buffer is MemoryTrainer's, member p bit for bit
+a MemoryTrainer stepped alone on its slab.  Its ring is a PopulationReplayMemory built with agent_states_space =
+(2 + mem_size,).
+
+Out of scope: the memory net's acting with per-member packs, its select and record with the carried memory and its
+agent (next, in that order); the rework agent's net; in-loop acting (a handle holds one policy pack), B > 512 for the
+linear nets, members of unequal size, training_state.
 """
 from __future__ import annotations
 
@@ -43,10 +51,10 @@ import torch
 from . import _lib
 from ._lib import ptr as _p
 from .agent import _LoopAgent, _backend
-from .policy import linear_init
+from .policy import linear_init, memnet_param_shapes, memnet_shape
 from .replay import RING_NAMES, _Ring, ring_arrays
-from .train import (EXPLORE_NAMES, LINEAR_NAMES, _TargetCounter, _clones, collect_names, copy_named, explore_names,
-                    linear_adam_state, linear_model_views, linear_target_state_dict)
+from .train import (EXPLORE_NAMES, LINEAR_NAMES, _MemoryBlocks, _TargetCounter, _clones, collect_names, copy_named,
+                    explore_names, linear_adam_state, linear_model_views, linear_target_state_dict)
 
 MEMBER_DEFAULTS = dict(epsilon=0.1, discount=0.5, learning_rate=1e-4, seed=0)  # CollectAgent's
 
@@ -102,11 +110,13 @@ class PopulationReplayMemory(_Ring):
     are shared.  record_pre / record_post are antsrl_pop_record_pre / _post: K rows per member and step into the same
     rows of every member's slab, each member sampling its own ants with its own seed.  They take their tensors in the
     order DeviceReplayMemory's do (memory: None, a population's agents have none) and the step's AntsPopSpec, step and k
-    by name."""
+    by name.  agent_states_space: a row of agent_states and new_agent_states, (2,) for the linear nets; the ring a
+    PopulationMemoryTrainer steps on has (2 + mem_size,), and nothing records into it yet."""
 
-    def __init__(self, n_members: int, max_len: int, observation_space: Sequence[int], device="cuda"):
+    def __init__(self, n_members: int, max_len: int, observation_space: Sequence[int], device="cuda",
+                 agent_states_space: Sequence[int] = (2,)):
         self.n_members, self.observation_space = n_members, tuple(observation_space)
-        self._alloc(max_len, observation_space, [2], [2], device, lead=(n_members,))
+        self._alloc(max_len, observation_space, list(agent_states_space), [2], device, lead=(n_members,))
 
     def member(self, p: int) -> _MemberRing:
         """Member p's slab under DeviceReplayMemory's seven names, with head and fill (views: same_rings works on it)."""
@@ -454,6 +464,78 @@ class PopulationJointTrainer(_PopulationTrainer):
         """Two launches; behind first_loss goes the workspace for B rows per member."""
         return (self._lib.antsrl_pop_jointtrain_step, "pop_jointtrain_step",
                 (_p(self.model), _p(self.target_l3), _p(self._adam[0]), _p(self._adam[1])), (_p(self.workspace(B)),))
+
+
+class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
+    """MemoryTrainer's state buffers with a leading [P], trained by antsrl_pop_memtrain_step: 17 launches whatever P is
+    (16 of the gradient stage, 1 of Adam and the repack).  `_model` and `_target` are uint8 [P, state_stride], a member's
+    block MemoryTrainer's buffer (masters, Adam's m and v, the bf16 packs); grads is [P, trained_floats].  Member p is
+    initialised as MemoryTrainer(seed=seed_p) is, its target a copy.  Per member: discount and learning rate.  Common:
+    the net's shape, Adam's betas, eps and step count, update_target_every and the target counter.  `running_loss`
+    (float64 [P]) is kept by the finalize launch from the first training step on.  The ring of a step is a
+    PopulationReplayMemory(..., agent_states_space=(2 + mem_size,))."""
+
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+                 update_target_every: int = 1, *, power: int = 5, mem_size: int = 20, n_rot: int = 3, n_ph: int = 3):
+        super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
+        P, F = self.n_members, self.n_features
+        self._init_blocks(memnet_shape(F, power, mem_size, n_rot, n_ph), F, power, mem_size, n_rot, n_ph)
+        self.state_stride, tf = self._sizes(1)[:2]
+        assert self.state_stride == self.state_bytes and tf == self.trained_floats and self.state_stride % 256 == 0
+        self._model = torch.empty((P, self.state_stride), dtype=torch.uint8, device=self.device)
+        self._target = torch.empty_like(self._model)
+        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self._work, self._work_B = None, 0
+        shapes = memnet_param_shapes(F, power, mem_size, n_rot, n_ph)
+        for p, seed in enumerate(self.seeds):
+            self._init_state(linear_init(shapes, seed), (self._model[p], self._target[p]))
+
+    def _sizes(self, B: int) -> tuple:
+        """antsrl_pop_memtrain_sizes -> (a member's state stride, trained_floats, a member's workspace stride, the
+        workspace's bytes, launches)."""
+        ss, tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+        _lib.check(self._lib.antsrl_pop_memtrain_sizes(C.byref(self.shape), B, self.n_members, C.byref(ss), C.byref(tf),
+                                                       C.byref(stride), C.byref(ws), C.byref(n)), "pop_memtrain_sizes")
+        return ss.value, tf.value, stride.value, ws.value, n.value
+
+    # ---- weights ------------------------------------------------------------------------------------------------------
+    def state_dict(self, p: int) -> dict:
+        """Member p's 26 tensors (copies) under CollectModelMemory's names, in its order: what the reference loads."""
+        return _clones(self._views(self._model[p]))
+
+    def target_state_dict(self, p: int) -> dict:
+        return _clones(self._views(self._target[p]))
+
+    def load_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """MemoryTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
+        for q in (range(self.n_members) if p is None else (p,)):
+            keep = self._model[q, self._adam_range()].clone()
+            self._init_state(sd, (self._model[q], self._target[q]))
+            self._model[q, self._adam_range()] = keep
+
+    def adam_state(self, p: int) -> dict:
+        return self._adam_dict(self._model[p], self.step_count)
+
+    def sync_target(self) -> None:
+        """target := model for every member (antsrl_memtrain_copy on its block: masters and packs, not Adam's moments)."""
+        with torch.cuda.device(self.device):
+            for p in range(self.n_members):
+                _lib.check(self._lib.antsrl_memtrain_copy(C.byref(self.shape), _p(self._model[p]), _p(self._target[p]),
+                                                          _lib.stream(self.device)), "memtrain_copy")
+        self.syncs += 1
+
+    # ---- the step -----------------------------------------------------------------------------------------------------
+    def workspace(self, B: int) -> torch.Tensor:
+        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
+        if self._work is None or self._work_B != B:
+            self._work = torch.empty((self._sizes(B)[3],), dtype=torch.uint8, device=self.device)
+            self._work_B = B
+        return self._work
+
+    def _entry(self, B: int) -> tuple:
+        """17 launches; the shape leads the net's pointers, behind first_loss goes the workspace for B rows per member."""
+        return (self._lib.antsrl_pop_memtrain_step, "pop_memtrain_step",
+                (C.byref(self.shape), _p(self._model), _p(self._target)), (_p(self.workspace(B)),))
 
 
 def _same_population(trainer, other, kind: str) -> None:

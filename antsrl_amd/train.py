@@ -137,7 +137,66 @@ class _DqnTrainer(_TargetCounter):
         return loss
 
 
-class MemoryTrainer(_DqnTrainer):
+class _MemoryBlocks:
+    """A memory net's state buffer (include/antsrl.h, antsrl_memtrain_sizes) seen from the host, for MemoryTrainer and
+    for every member of population.PopulationMemoryTrainer: the sizes, the tensors' offsets in the flat parameter block
+    and the views on a buffer's parameters and Adam moments.  Needs `_lib` and `device`."""
+
+    def _init_blocks(self, shape, n_features: int, power: int, mem_size: int, n_rot: int, n_ph: int) -> None:
+        self.shape = shape
+        self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
+        pf, tf, sb = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), 1, C.byref(pf), C.byref(tf), C.byref(sb), None),
+                   "memtrain_sizes")
+        self.params_floats, self.trained_floats, self.state_bytes = pf.value, tf.value, sb.value
+        # the flat layout (include/antsrl.h): state_dict order, dense, weight then bias per layer
+        self._offs = {}
+        off = 0
+        for name, (o, i) in memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph).items():
+            self._offs[name + ".weight"] = (off, (o, i))
+            off += o * i
+            self._offs[name + ".bias"] = (off, (o,))
+            off += o
+        assert off == self.params_floats
+
+    def _adam_offsets(self):
+        """Byte offsets of Adam's m and v in a state buffer (256-byte aligned blocks behind the parameters)."""
+        m_off = (self.params_floats * 4 + 255) // 256 * 256
+        return m_off, (m_off + self.trained_floats * 4 + 255) // 256 * 256
+
+    def _adam_range(self):
+        m_off, v_off = self._adam_offsets()
+        return slice(m_off, v_off + self.trained_floats * 4)
+
+    def _views(self, buf, region="params"):
+        f = buf.view(torch.float32)
+        if region == "params":
+            base, names = 0, list(self._offs)
+        else:
+            m_off, v_off = self._adam_offsets()
+            base = (m_off if region == "m" else v_off) // 4
+            names = [k for k in self._offs if k.split(".")[0] in TRAINED_LAYERS]
+        return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + math.prod(self._offs[k][1])].view(self._offs[k][1])
+                for k in names}
+
+    def _init_state(self, sd, states) -> None:
+        """antsrl_memtrain_init of every buffer in `states` from the 26 tensors of sd (shapes checked): masters and packs
+        from sd, Adam's moments zero."""
+        for k, (_, shp) in self._offs.items():
+            assert tuple(sd[k].shape) == shp, (k, tuple(sd[k].shape), shp)
+        src = {k: torch.as_tensor(sd[k]).to(self.device, torch.float32).contiguous() for k in self._offs}
+        ptrs = memnet_param_ptrs(src)
+        with torch.cuda.device(self.device):
+            for state in states:
+                _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(state), _lib.stream(self.device)),
+                           "memtrain_init")
+
+    def _adam_dict(self, buf, step: int) -> dict:
+        """torch.optim.Adam's state for the 18 trained tensors of a buffer: step, exp_avg, exp_avg_sq (copies)."""
+        return dict(step=step, exp_avg=_clones(self._views(buf, "m")), exp_avg_sq=_clones(self._views(buf, "v")))
+
+
+class MemoryTrainer(_MemoryBlocks, _DqnTrainer):
     """CollectAgentMemory's model, target model and optimizer on the device (defaults: the reference class's,
     discount 0.5, lr 1e-4; main.py passes 0.99 and 1e-5).
 
@@ -159,42 +218,11 @@ class MemoryTrainer(_DqnTrainer):
                                    seed=seed, precision=policy_precision)
         if state_dict is None:
             state_dict = {k: v.clone() for k, v in self.policy.state_dict().items()}
-        self.power, self.mem_size, self.n_rot, self.n_ph = power, mem_size, n_rot, n_ph
-        self.shape = self.policy.shape
-        pf, tf, sb = C.c_size_t(), C.c_size_t(), C.c_size_t()
-        _lib.check(self._lib.antsrl_memtrain_sizes(C.byref(self.shape), 1, C.byref(pf), C.byref(tf), C.byref(sb), None),
-                   "memtrain_sizes")
-        self.params_floats, self.trained_floats, self.state_bytes = pf.value, tf.value, sb.value
+        self._init_blocks(self.policy.shape, n_features, power, mem_size, n_rot, n_ph)
         self._model = torch.empty((self.state_bytes,), dtype=torch.uint8, device=self.device)  # 512-byte aligned blocks
         self._target = torch.empty_like(self._model)
         self.grads = torch.zeros((self.trained_floats,), dtype=torch.float32, device=self.device)
-        # the flat layout (include/antsrl.h): state_dict order, dense, weight then bias per layer
-        self._offs = {}
-        off = 0
-        for name, (o, i) in memnet_param_shapes(n_features, power, mem_size, n_rot, n_ph).items():
-            self._offs[name + ".weight"] = (off, (o, i))
-            off += o * i
-            self._offs[name + ".bias"] = (off, (o,))
-            off += o
-        assert off == self.params_floats
         self.load_state_dict(state_dict, _reset_adam=True)
-
-    # ---- layout views -------------------------------------------------------------------------------------------
-    def _adam_offsets(self):
-        """Byte offsets of Adam's m and v in a state buffer (256-byte aligned blocks behind the parameters)."""
-        m_off = (self.params_floats * 4 + 255) // 256 * 256
-        return m_off, (m_off + self.trained_floats * 4 + 255) // 256 * 256
-
-    def _views(self, buf, region="params"):
-        f = buf.view(torch.float32)
-        if region == "params":
-            base, names = 0, list(self._offs)
-        else:
-            m_off, v_off = self._adam_offsets()
-            base = (m_off if region == "m" else v_off) // 4
-            names = [k for k in self._offs if k.split(".")[0] in TRAINED_LAYERS]
-        return {k: f[base + self._offs[k][0]: base + self._offs[k][0] + math.prod(self._offs[k][1])].view(self._offs[k][1])
-                for k in names}
 
     # ---- weights ------------------------------------------------------------------------------------------------
     def state_dict(self) -> dict:
@@ -207,27 +235,15 @@ class MemoryTrainer(_DqnTrainer):
     def load_state_dict(self, sd, _reset_adam: bool = False) -> None:
         """CollectAgentMemory.load_model (:213-215): sets the model AND the target net (and the acting policy).  Adam's
         state is kept, as the reference's optimizer keeps it."""
-        for k, (_, shp) in self._offs.items():
-            assert tuple(sd[k].shape) == shp, (k, tuple(sd[k].shape), shp)
-        src = {k: torch.as_tensor(sd[k]).to(self.device, torch.float32).contiguous() for k in self._offs}
-        ptrs = memnet_param_ptrs(src)
         keep = None if _reset_adam else self._model[self._adam_range()].clone()
-        with torch.cuda.device(self.device):
-            for state in (self._model, self._target):
-                _lib.check(self._lib.antsrl_memtrain_init(C.byref(self.shape), ptrs, _p(state), _lib.stream(self.device)),
-                           "memtrain_init")
+        self._init_state(sd, (self._model, self._target))
         if keep is not None:
             self._model[self._adam_range()] = keep
         self._repack_policy()
 
-    def _adam_range(self):
-        m_off, v_off = self._adam_offsets()
-        return slice(m_off, v_off + self.trained_floats * 4)
-
     def adam_state(self) -> dict:
         """torch.optim.Adam's state for the 18 trained tensors: step, exp_avg, exp_avg_sq (copies)."""
-        return dict(step=self.step_count, exp_avg=_clones(self._views(self._model, "m")),
-                    exp_avg_sq=_clones(self._views(self._model, "v")))
+        return self._adam_dict(self._model, self.step_count)
 
     def grad_dict(self, grads: Optional[torch.Tensor] = None) -> dict:
         """The flat gradient (self.grads by default) as views named like the 18 trained state_dict tensors."""

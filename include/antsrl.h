@@ -1579,6 +1579,48 @@ int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *
                                float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
                                void *stream);
 
+/* The population of memory nets: the DQN training step of P memory agent nets (the net of antsrl_memtrain_*, the agent
+ * main.py drives) in the launches of ONE step: 16 + 1 = 17 whatever P is, each the single step's kernel on a grid
+ * (x, P) with the member in the grid's y dimension.  Only the training step: acting with per-member packs, select and
+ * record with the carried memory and the agent's loop are not here yet.  The spec is the population of linear agents'
+ * (the training entry reads its members' discount and learning_rate and its n_features, which must be the shape's).
+ *
+ * THE DEFINING PROPERTY: member p is, bit for bit, antsrl_memtrain_grad followed by antsrl_memtrain_apply on its own
+ * state blocks, ring slab and idx row, with its own discount and learning rate; its result does not depend on P or on
+ * the other members' data.
+ *
+ * Layout: net_states and target_states are [P][state_stride] bytes, a member's block laid out as antsrl_memtrain_*'s
+ * state (state_stride is antsrl_memtrain_sizes' state_bytes); antsrl_memtrain_init / _unpack / _copy work on a member
+ * at net_states + p * state_stride.  The workspace is [P][work_stride] bytes, a member's part laid out as
+ * antsrl_memtrain_grad's (work_stride is antsrl_memtrain_sizes' workspace_bytes).  Both strides are multiples of 256, so
+ * that every member's blocks start as aligned as a single net's.  The ring's seven arrays have a leading [P] of n_rows
+ * rows each (agent_states and new_agent_states [P][n_rows][agent_dim + mem_size]); idx int64 [P][B], required, every
+ * value in [0, n_rows); grads float [P][trained_floats]; loss float [P]; running_loss double [P] or NULL.
+ *
+ * Refusals (ANTSRL_E_INVALID unless stated), before anything is launched: the spec's, as above; the shape's, as
+ * antsrl_memtrain_sizes' (a NULL shape; D = n_features + agent_dim + mem_size > 1024 is UNSUPPORTED);
+ *   antsrl_pop_memtrain_sizes: B outside [1, 2^24]; n_members outside [1, ANTSRL_POP_MAX];
+ *   antsrl_pop_memtrain_step: the spec's n_features is not the shape's; B < 1; net_states, target_states or workspace
+ *     NULL or not 256-byte aligned; idx NULL or not 8-byte aligned; n_rows outside [1, 2^40]; any ring array, grads or
+ *     loss NULL or misaligned (floats 4 bytes, actions 8); running_loss not 8-byte aligned; step < 1 and Adam's other
+ *     arguments for every member's learning_rate.
+ * No entry allocates or synchronises the host; no atomics: equal inputs give equal bits.
+ *
+ *   antsrl_pop_memtrain_sizes  state_stride, trained_floats, work_stride, workspace_bytes = n_members * work_stride and
+ *                         launches = 17 (any of the five may be NULL).  Host only.
+ *   antsrl_pop_memtrain_step   the step of every member: gradient and loss (16 launches), then Adam with the member's
+ *                         step size and the repack (1 launch).  step, beta1, beta2, eps, running_loss and first_loss as
+ *                         antsrl_pop_lintrain_step's; the finalize launch keeps the running loss.
+ * The target sync is antsrl_memtrain_copy per member, the caller's. */
+int antsrl_pop_memtrain_sizes(const AntsMemNetShape *shape, int64_t B, int32_t n_members, size_t *state_stride,
+                              size_t *trained_floats, size_t *work_stride, size_t *workspace_bytes, int32_t *launches);
+int antsrl_pop_memtrain_step(const AntsPopSpec *s, const AntsMemNetShape *shape, void *net_states, const void *target_states,
+                             const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                             const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                             const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps,
+                             float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
