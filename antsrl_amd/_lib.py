@@ -35,7 +35,9 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_pop_policy", "antsrl_pop_select", "antsrl_pop_record_pre", "antsrl_pop_record_post",
            "antsrl_pop_lintrain_step", "antsrl_pop_explore_policy", "antsrl_pop_exptrain_sizes",
            "antsrl_pop_exptrain_step", "antsrl_pop_joint_policy", "antsrl_pop_jointtrain_sizes",
-           "antsrl_pop_jointtrain_step", "antsrl_pop_memtrain_sizes", "antsrl_pop_memtrain_step")
+           "antsrl_pop_jointtrain_step", "antsrl_pop_memtrain_sizes", "antsrl_pop_memtrain_step",
+           "antsrl_pop_memnet_sizes", "antsrl_pop_policy_memory", "antsrl_pop_memory_select",
+           "antsrl_pop_memory_record_pre", "antsrl_pop_memory_record_post")
 
 _lib = None
 
@@ -218,6 +220,13 @@ def load() -> C.CDLL:
     lib.antsrl_pop_jointtrain_step.argtypes = lib.antsrl_pop_exptrain_step.argtypes
     lib.antsrl_pop_memtrain_sizes.argtypes = [C.POINTER(AntsMemNetShape), C.c_int64, i32, sz, sz, sz, sz, C.POINTER(C.c_int32)]
     lib.antsrl_pop_memtrain_step.argtypes = [ps, C.POINTER(AntsMemNetShape)] + lib.antsrl_pop_exptrain_step.argtypes[3:]
+    ms = C.POINTER(AntsMemNetShape)
+    lib.antsrl_pop_memnet_sizes.argtypes = [ms, i32, i32, sz, sz]
+    lib.antsrl_pop_policy_memory.argtypes = [ps, ms, i32] + [vp] * 9
+    lib.antsrl_pop_memory_select.argtypes = [ps, ms, C.c_uint64] + [vp] * 6
+    # the record pair's arguments with the shape behind the spec and `memory` behind agent_state
+    lib.antsrl_pop_memory_record_pre.argtypes = [ps, ms] + lib.antsrl_pop_record_pre.argtypes[1:] + [vp]
+    lib.antsrl_pop_memory_record_post.argtypes = [ps, ms] + lib.antsrl_pop_record_post.argtypes[1:] + [vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -24,11 +24,12 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
            "antsrl_rework.hip", "antsrl_reworktrain.hip", "antsrl_reworkapi.hip", "antsrl_monitor.hip", "antsrl_recorder.hip",
            "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip",
            "antsrl_population.hip", "antsrl_popexplore.hip", "antsrl_popjoint.hip", "antsrl_popmemtrain.hip",
-           "antsrl_popapi.hip"]
+           "antsrl_popmemnet.hip", "antsrl_popapi.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
-                                           "antsrl_memnet_dev.h", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_loopapi.h",
+                                           "antsrl_memnet_dev.h", "antsrl_memnet_bf16_dev.h", "antsrl_memnet_body.inc",
+                                           "antsrl_agent_select_memory.inc", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_loopapi.h",
                                            "antsrl_draw.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
                                            "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",

@@ -19,21 +19,14 @@
 #include "antsrl_memagent_dev.h" // env_explores, load4, load1: what the bodies a population shares (the .inc texts) call
 
 // ------------------------------------------------------------------ antsrl_agent_select
-// Part 1: one thread per ant (the actions: antsrl_agent_select_actions.inc).  Part 2: one thread per memory element (V floats), coalesced.
+// Part 1: one thread per ant (the actions: antsrl_agent_select_actions.inc).  Part 2: one thread per memory element (V floats),
+// coalesced (antsrl_agent_select_memory.inc).  Both are texts a population's select runs too.
 template <int V>
 __global__ __launch_bounds__(256) void k_agent_select(const SelArgs a)
 {
     const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x, nthr = (uint64_t)gridDim.x * 256;
 #include "antsrl_agent_select_actions.inc"
-    if (a.mem_old == a.mem_next) return;
-    for (uint64_t f = tid; f < a.mem_elems; f += nthr) {
-        const uint32_t e = (uint32_t)(f / a.env_elems);
-        if (!env_explores(a, e)) continue; // (the draw is cheap next to the forward pass this follows: kept per element)
-        if (V == 4)
-            reinterpret_cast<float4 *>(a.mem_next)[f] = reinterpret_cast<const float4 *>(a.mem_old)[f];
-        else
-            a.mem_next[f] = a.mem_old[f];
-    }
+#include "antsrl_agent_select_memory.inc"
 }
 
 // ------------------------------------------------------------------ antsrl_agent_plan

@@ -164,6 +164,7 @@ extern "C" int antsrl_policy_memory_tiles(const AntsMemNetShape *s, int precisio
 }
 
 int antsrl_memnet_dims(const char *who, const AntsMemNetShape *s, MemNetDims *d) { return memnet_check(s, d, who); }
+int antsrl_memnet_precision(const char *who, int precision) { return memnet_precision(precision, who); }
 
 // ---- the training step (antsrl_memtrain.hip)
 

@@ -85,6 +85,8 @@ hipError_t antsrl_memtrain_grad_list(const MemNetDims &d, const unsigned char *s
 
 // the shape's rules of every entry of the net (antsrl_memapi.hip), for an entry elsewhere: *d, or the refusal under `who`
 ANTSRL_INTERNAL int antsrl_memnet_dims(const char *who, const AntsMemNetShape *s, MemNetDims *d);
+// ... and the precision's: ANTSRL_MEMNET_BF16 or ANTSRL_MEMNET_FP32, anything else refused as the _ex entries refuse it
+ANTSRL_INTERNAL int antsrl_memnet_precision(const char *who, int precision);
 
 hipError_t antsrl_launch_memtrain_repack(const MemNetDims &d, unsigned char *state, hipStream_t st);
 hipError_t antsrl_launch_memtrain_grad(const MemNetDims &d, const unsigned char *state, const unsigned char *target,

@@ -6,7 +6,9 @@
 // and the population of joint agents ("The population of joint agents"): antsrl_pop_joint_policy /
 // antsrl_pop_jointtrain_sizes / _step in front of antsrl_popjoint.hip's, the explore entries with the joint net; and the
 // training step of the population of memory nets ("The population of memory nets"): antsrl_pop_memtrain_sizes / _step in
-// front of antsrl_popmemtrain.hip's.
+// front of antsrl_popmemtrain.hip's; and the memory agents' loop around it: antsrl_pop_memnet_sizes /
+// antsrl_pop_policy_memory in front of antsrl_popmemnet.hip's forward, antsrl_pop_memory_select and
+// antsrl_pop_memory_record_pre / _post in front of antsrl_population.hip's select and record with the carried memory.
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -18,6 +20,7 @@
 #include "antsrl_dqn.h"
 #include "antsrl_fail.h"
 #include "antsrl_loopapi.h"
+#include "antsrl_memnet.h"
 #include "antsrl_policy_flat.h"
 #include "antsrl_population.h"
 
@@ -438,4 +441,170 @@ extern "C" int antsrl_pop_memtrain_step(const AntsPopSpec *s, const AntsMemNetSh
     return enqueued(antsrl_launch_pop_memtrain(d, (unsigned char *)net_states, (const unsigned char *)target_states, bt, n_rows,
                                                (int)B, t, s->n_members, adam, grads, loss, rl, (unsigned char *)workspace,
                                                (hipStream_t)stream), who);
+}
+
+// ---- the memory agents' loop for a population (antsrl_popmemnet.hip; antsrl_population.hip's select and record) -------------
+
+// the shape's rules under the entry's name, then a member's pack stride: the single net's packed bytes, which must be a
+// multiple of 256 for every member's pack to start as aligned as a single net's (mn_layout rounds every block up to
+// 256: checked here, not assumed)
+static int pop_memnet_layout(const char *who, const AntsMemNetShape *shape, MemNetDims *d, size_t *pack_stride)
+{
+    const int rc = antsrl_memnet_dims(who, shape, d);
+    if (rc != ANTSRL_OK) return rc;
+    MemNetLayout L;
+    antsrl_memnet_layout(*d, &L);
+    if (L.bytes % 256)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: a member's pack of %zu bytes must be a multiple of 256", who, L.bytes);
+    *pack_stride = L.bytes;
+    return ANTSRL_OK;
+}
+
+// a population acts with the bf16 forward only (an unknown precision has been refused before this)
+static int pop_memnet_bf16(const char *who, int precision)
+{
+    if (precision == ANTSRL_MEMNET_BF16) return ANTSRL_OK;
+    return fail(ANTSRL_E_UNSUPPORTED, "%s: a population acts with bf16 operands only: precision ANTSRL_MEMNET_FP32 is not built", who);
+}
+
+// what the loop's entries check of (spec, shape) together: both sets of rules, then that they speak of the same rows
+static int pop_mem_spec(const char *who, const AntsPopSpec *s, const AntsMemNetShape *shape, PopTable *t, int *Em, MemNetDims *d,
+                        size_t *pack_stride)
+{
+    int rc = pop_spec(who, s, t, Em);
+    if (rc == ANTSRL_OK) rc = pop_memnet_layout(who, shape, d, pack_stride);
+    if (rc != ANTSRL_OK) return rc;
+    if (s->n_features != shape->n_features)
+        return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_memnet_sizes(const AntsMemNetShape *shape, int precision, int32_t n_members, size_t *pack_stride,
+                                       size_t *packed_bytes)
+{
+    const char *who = "pop_memnet_sizes";
+    MemNetDims d;
+    size_t stride = 0;
+    int rc = antsrl_memnet_precision(who, precision);
+    if (rc == ANTSRL_OK) rc = pop_memnet_layout(who, shape, &d, &stride);
+    if (rc == ANTSRL_OK) rc = pop_memnet_bf16(who, precision);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    if (pack_stride) *pack_stride = stride;
+    if (packed_bytes) *packed_bytes = stride * (size_t)n_members;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_policy_memory(const AntsPopSpec *s, const AntsMemNetShape *shape, int precision, const void *packed,
+                                        const void *obs, const float *agent_state, const float *mem_in, float *mem_out,
+                                        int8_t *rotation, int8_t *pheromone, float *q_out, void *stream)
+{
+    const char *who = "pop_policy_memory";
+    PopTable t;
+    int Em = 0;
+    MemNetDims d;
+    size_t stride = 0;
+    int rc = antsrl_memnet_precision(who, precision);
+    if (rc == ANTSRL_OK) rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
+    if (rc == ANTSRL_OK) rc = pop_memnet_bf16(who, precision);
+    if (rc != ANTSRL_OK) return rc;
+    const long long Mm = (long long)Em * s->n_ants;
+    if (Mm > 0x7fffffffLL - 32 * 4) // (a workgroup has at most four waves of 32 ants: the launcher rounds Mm up to that)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: n_envs / n_members * n_ants = %lld: the tile count of a member's grid row must fit "
+                                          "an int (at most 2^31 - 1 - 128 ants per member)", who, Mm);
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    REQUIRE(packed, 256);
+    REQUIRE(obs, bf16 ? 2 : 4);
+    REQUIRE(agent_state, 4);
+    REQUIRE(mem_in, 4);
+    REQUIRE(mem_out, 4);
+    REQUIRE(rotation, 1);
+    if ((uintptr_t)q_out & 3) return fail(ANTSRL_E_INVALID, "%s: q_out must be 4-byte aligned", who);
+    return enqueued(antsrl_launch_pop_memnet((const unsigned char *)packed, stride, d, obs, bf16, agent_state, mem_in, (int)Mm,
+                                             s->n_members, mem_out, rotation, pheromone, q_out, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_memory_select(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int8_t *rotation,
+                                        int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored,
+                                        void *stream)
+{
+    const char *who = "pop_memory_select";
+    PopTable t;
+    int Em = 0;
+    MemNetDims d;
+    size_t stride = 0;
+    const int rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(rotation, 1);
+    REQUIRE(pheromone, 1);
+    REQUIRE(mem_old, 4);
+    REQUIRE(mem_next, 4);
+    if (mem_old != mem_next) { // the same buffer, or two that do not touch (antsrl_agent_select's rule, on the whole batch)
+        const uintptr_t o = (uintptr_t)mem_old, n = (uintptr_t)mem_next;
+        const uintptr_t bytes = (uintptr_t)s->n_envs * (uintptr_t)s->n_ants * (uintptr_t)d.mem * 4;
+        if (o < n + bytes && n < o + bytes) return fail(ANTSRL_E_INVALID, "%s: mem_old and mem_next overlap without being equal", who);
+    }
+    SelArgs a; // member 0's Em environments; seed and epsilon come from the table
+    antsrl_sel_args(0, step, s->env_id_base, Em, s->n_ants, 0.0, d.n_rot, d.n_ph, &a);
+    a.rot = rotation; a.ph = pheromone; a.mem_old = mem_old; a.mem_next = mem_next; a.explored = explored;
+    // antsrl_agent_select's rule for float4 elements, which then holds for every member's offset as well: a member's
+    // halves start Em * env_floats floats behind the previous member's, a multiple of 4 floats = 16 bytes
+    const uint64_t env_floats = (uint64_t)s->n_ants * (uint64_t)d.mem; // < 2^36
+    const bool vec = env_floats % 4 == 0 && (((uintptr_t)mem_old | (uintptr_t)mem_next) & 15) == 0;
+    const uint64_t env_elems = vec ? env_floats / 4 : env_floats;
+    if (env_elems > 0xffffffffULL)
+        return fail(ANTSRL_E_UNSUPPORTED, "%s: n_ants * mem_size = %llu is too large", who, (unsigned long long)env_floats);
+    a.env_elems = (uint32_t)env_elems;
+    a.mem_elems = env_elems * (uint64_t)Em; // member 0's
+    return enqueued(antsrl_launch_pop_memory_select(a, t, s->n_members, Em, vec, (hipStream_t)stream), who);
+}
+
+// pop_rec with the shape's widths: agent_states rows are agent_dim + mem_size wide
+static int pop_mem_rec(const char *who, const AntsPopSpec *s, const MemNetDims &d, int Em, uint64_t step, int64_t K, int64_t head,
+                       int64_t max_len, RecArgs *a)
+{
+    const int rc = pop_rec(who, s, Em, step, K, head, max_len, a);
+    if (rc != ANTSRL_OK) return rc;
+    a->A = d.A; a->mem = d.mem; a->half_rot = d.n_rot / 2;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_memory_record_pre(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K,
+                                            int64_t head, int64_t max_len, const void *obs, const float *agent_state,
+                                            const float *memory, const int8_t *rotation, const int8_t *pheromone,
+                                            float *states, float *agent_states, int64_t *actions, void *stream)
+{
+    const char *who = "pop_memory_record_pre";
+    PopTable t;
+    int Em = 0;
+    MemNetDims d;
+    size_t stride = 0;
+    RecArgs a = {};
+    int rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
+    if (rc == ANTSRL_OK) rc = pop_mem_rec(who, s, d, Em, step, K, head, max_len, &a);
+    if (rc != ANTSRL_OK) return rc;
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_pre(who, &a, bf16, obs, agent_state, memory, rotation, pheromone, states, agent_states, actions);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, false, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K,
+                                             int64_t head, int64_t max_len, const void *obs, const float *agent_state,
+                                             const float *memory, const float *reward, const uint8_t *done, float *rewards,
+                                             float *new_states, float *new_agent_states, uint8_t *dones, void *stream)
+{
+    const char *who = "pop_memory_record_post";
+    PopTable t;
+    int Em = 0;
+    MemNetDims d;
+    size_t stride = 0;
+    RecArgs a = {};
+    int rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
+    if (rc == ANTSRL_OK) rc = pop_mem_rec(who, s, d, Em, step, K, head, max_len, &a);
+    if (rc != ANTSRL_OK) return rc;
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_post(who, &a, bf16, obs, agent_state, memory, reward, done, rewards, new_states, new_agent_states, dones);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
 }

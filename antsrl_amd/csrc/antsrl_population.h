@@ -127,11 +127,24 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memtrain(const MemNetDims &d, unsig
                                                       const AdamArgs &adam, float *grads, float *loss, const PopRunningLoss &rl,
                                                       unsigned char *work, hipStream_t st);
 
+// The acting net of every member on its Mm rows (antsrl_popmemnet.hip): packs [P][pack_stride] bytes, a member's block
+// antsrl_memnet_pack's; obs [P][Mm][F]; agent_state, mem_in, mem_out, rot, ph and q_out (or NULL) [P][Mm][...].  One
+// launch on a grid (ceil(Mm / (32 nw)), P); member p's outputs are antsrl_launch_memnet's on its slice with its pack.
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memnet(const unsigned char *packs, size_t pack_stride, const MemNetDims &d,
+                                                    const void *obs, bool obs_bf16, const float *agent_state,
+                                                    const float *mem_in, int Mm, int P, float *mem_out, int8_t *rot,
+                                                    int8_t *ph, float *q_out, hipStream_t st);
+// a: the single agent's SelArgs for member 0 WITH its memory part (mem_old, mem_next, env_elems, and mem_elems = member
+// 0's elements; vec: they count float4).  The table gives seed and epsilon.  (antsrl_population.hip, beside k_pop_select)
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memory_select(const SelArgs &a, const PopTable &t, int P, int Em, bool vec,
+                                                           hipStream_t st);
+
 // ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipStream_t st);
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_select(const SelArgs &a, const PopTable &t, int P, int Em, hipStream_t st);
-// a: the single agent's RecArgs for member 0 (M = Mm, its K, the shared ring rows); the table gives the seed
+// a: the single agent's RecArgs for member 0 (M = Mm, its K, the shared ring rows; memory NULL, or member 0's [Mm][mem]
+// with mem > 0: the memory agents' ring); the table gives the seed
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_record(const RecArgs &a, const PopTable &t, int P, int Em, bool obs_bf16,
                                                     bool post, hipStream_t st);
 // a: the single agent's LinTrainArgs for member 0 (B <= 512: one workgroup; idx [P][B]; adam.m of member 0, adam.v is

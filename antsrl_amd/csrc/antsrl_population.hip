@@ -7,6 +7,7 @@
 // by-value table — and then runs the SAME body text the single agent's __global__ kernel runs, included inside both:
 //   k_pop_policy<OBS16>      antsrl_policy_flat_body.inc       (k_policy_flat)      grid (blocks, P)
 //   k_pop_select             antsrl_agent_select_actions.inc   (k_agent_select)     grid (blocks, P)
+//   k_pop_memory_select<V>   ... and antsrl_agent_select_memory.inc (k_agent_select)    grid (blocks, P)
 //   k_pop_record<BF16, POST> antsrl_replay_record_body.inc     (k_replay_record)    grid (ceil(K / 4), P)
 //   k_pop_lintrain           antsrl_lintrain_body.inc, NW = 4  (k_lintrain<4>)      grid (1, P)
 // A body reads the x dimension of the grid as its kernel always did; the member is the y dimension.  The bodies are
@@ -70,6 +71,20 @@ __global__ __launch_bounds__(256) void k_pop_select(const SelArgs a0, const PopT
 #include "antsrl_agent_select_actions.inc"
 }
 
+// The select of a population of memory agents: k_agent_select's two parts for its member.  a0.mem_elems counts MEMBER 0's
+// memory elements in V units (V = 4: float4), so the member's halves start member * mem_elems * V floats on; both texts
+// then see nothing but their member's ants and environments.
+template <int V>
+__global__ __launch_bounds__(256) void k_pop_memory_select(const SelArgs a0, const PopTable tab, const uint32_t Em)
+{
+    SelArgs a = pop_select_member(a0, tab, blockIdx.y, Em);
+    a.mem_old = a0.mem_old + (size_t)blockIdx.y * a0.mem_elems * V;
+    a.mem_next = a0.mem_next + (size_t)blockIdx.y * a0.mem_elems * V;
+    const uint64_t tid = (uint64_t)blockIdx.x * 256 + threadIdx.x, nthr = (uint64_t)gridDim.x * 256;
+#include "antsrl_agent_select_actions.inc"
+#include "antsrl_agent_select_memory.inc"
+}
+
 // ------------------------------------------------------------------ the ring
 template <bool BF16, bool POST>
 __device__ __forceinline__ RecArgs pop_record_member(const RecArgs &a0, const PopTable &tab, const size_t member, const uint32_t Em)
@@ -80,6 +95,7 @@ __device__ __forceinline__ RecArgs pop_record_member(const RecArgs &a0, const Po
     a.env_base = a0.env_base + member * Em;
     a.obs = reinterpret_cast<const unsigned char *>(a0.obs) + member * Mm * (size_t)a0.pitch * (BF16 ? 2 : 4);
     a.agent_state = a0.agent_state + member * Mm * (size_t)a0.A;
+    a.memory = a0.memory ? a0.memory + member * Mm * (size_t)a0.mem : nullptr; // (the memory agents' ring: mem > 0)
     a.states = a0.states + member * L * (size_t)a0.F;
     a.agent_states = a0.agent_states + member * L * (size_t)(a0.A + a0.mem);
     if (POST) {
@@ -169,6 +185,18 @@ hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipSt
 hipError_t antsrl_launch_pop_select(const SelArgs &a, const PopTable &t, int P, int Em, hipStream_t st)
 {
     hipLaunchKernelGGL(k_pop_select, dim3(grid_for((size_t)a.M), (unsigned)P), dim3(256), 0, st, a, t, (uint32_t)Em);
+    return hipGetLastError();
+}
+
+hipError_t antsrl_launch_pop_memory_select(const SelArgs &a, const PopTable &t, int P, int Em, bool vec, hipStream_t st)
+{
+    // antsrl_launch_agent_select's grid for one member, a row of it per member
+    const uint64_t work = a.mem_old == a.mem_next ? a.M : (a.mem_elems > a.M ? a.mem_elems : a.M);
+    const dim3 grid(grid_for((size_t)work), (unsigned)P);
+    if (vec)
+        hipLaunchKernelGGL(k_pop_memory_select<4>, grid, dim3(256), 0, st, a, t, (uint32_t)Em);
+    else
+        hipLaunchKernelGGL(k_pop_memory_select<1>, grid, dim3(256), 0, st, a, t, (uint32_t)Em);
     return hipGetLastError();
 }
 

@@ -194,7 +194,9 @@ class MemoryPolicy:
         self.packed = None
         if self.device.type != "cuda":  # weights only (no kernel can run on them)
             return
-        self.packed = torch.empty((n.value,), dtype=torch.uint8, device=self.device)  # torch blocks are 512-byte aligned
+        # (torch blocks are 512-byte aligned; zeros: the pack kernel writes no byte of the padding between two blocks, and
+        # two packs of equal weights are then equal byte for byte)
+        self.packed = torch.zeros((n.value,), dtype=torch.uint8, device=self.device)
         ptrs = memnet_param_ptrs(self.params)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), self._precision_id(), ptrs,

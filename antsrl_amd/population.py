@@ -35,8 +35,13 @@ launches of one (antsrl_popmemtrain.hip): a member's state buffer
 a MemoryTrainer stepped alone on its slab.  Its ring is a PopulationReplayMemory built with agent_states_space =
 (2 + mem_size,).
 
-Out of scope: the memory net's acting with per-member packs, its select and record with the carried memory and its
-agent (next, in that order); the rework agent's net; in-loop acting (a handle holds one policy pack), B > 512 for the
+`PopulationMemoryAgent` is the same for P MemoryAgents, the agent main.py trains (antsrl_popmemnet.hip):
+every member's target net acts from its own bf16 pack (`PopulationMemoryTrainer.packed`) in one launch, select gives the
+ants of a member's exploring environments their old memory back, and the ring's rows carry the memory behind the agent
+state.  Member p is, bit for bit, a MemoryAgent run alone on a handle of its environments.
+
+Out of scope: the memory agents' explore plan and tile-list forward (skip_explored) and their fp32 acting precision; the
+rework agent's net; in-loop acting (a handle holds one policy pack), B > 512 for the
 linear nets, members of unequal size, training_state.
 """
 from __future__ import annotations
@@ -51,7 +56,7 @@ import torch
 from . import _lib
 from ._lib import ptr as _p
 from .agent import _LoopAgent, _backend
-from .policy import linear_init, memnet_param_shapes, memnet_shape
+from .policy import MEMNET_PRECISIONS, linear_init, memnet_param_ptrs, memnet_param_shapes, memnet_shape
 from .replay import RING_NAMES, _Ring, ring_arrays
 from .train import (EXPLORE_NAMES, LINEAR_NAMES, _MemoryBlocks, _TargetCounter, _clones, collect_names, copy_named,
                     explore_names, linear_adam_state, linear_model_views, linear_target_state_dict)
@@ -109,42 +114,68 @@ class PopulationReplayMemory(_Ring):
     """DeviceReplayMemory's seven arrays with a leading [P]: states [P, max_len, 7, 7, K] and so on.  `head` and `fill`
     are shared.  record_pre / record_post are antsrl_pop_record_pre / _post: K rows per member and step into the same
     rows of every member's slab, each member sampling its own ants with its own seed.  They take their tensors in the
-    order DeviceReplayMemory's do (memory: None, a population's agents have none) and the step's AntsPopSpec, step and k
-    by name.  agent_states_space: a row of agent_states and new_agent_states, (2,) for the linear nets; the ring a
-    PopulationMemoryTrainer steps on has (2 + mem_size,), and nothing records into it yet."""
+    order DeviceReplayMemory's do and the step's AntsPopSpec, step and k by name.  agent_states_space: a row of
+    agent_states and new_agent_states, (2,) for the linear nets (memory: None, those agents have none); the ring a
+    PopulationMemoryTrainer steps on has (2 + mem_size,): its record halves take `memory` (float32 [M, mem_size], every
+    member's rows) and, by name, the net's `shape`, and are antsrl_pop_memory_record_pre / _post."""
 
     def __init__(self, n_members: int, max_len: int, observation_space: Sequence[int], device="cuda",
                  agent_states_space: Sequence[int] = (2,)):
         self.n_members, self.observation_space = n_members, tuple(observation_space)
         self._alloc(max_len, observation_space, list(agent_states_space), [2], device, lead=(n_members,))
+        self.mem_size = int(np.prod(agent_states_space)) - 2  # what a row carries behind the agent state
 
     def member(self, p: int) -> _MemberRing:
         """Member p's slab under DeviceReplayMemory's seven names, with head and fill (views: same_rings works on it)."""
         return _MemberRing(self, p)
 
-    def record_pre(self, obs, agent_state, memory, rotation, pheromone, *, spec, step: int, k: int) -> None:
+    def _memory(self, memory, shape) -> None:
+        """A memory (and the net's shape) exactly when the rows are wider than the agent state."""
+        if self.mem_size == 0:
+            assert memory is None, "a population's agents have no memory"
+            return
+        assert shape is not None and shape.mem_size == self.mem_size, "a ring with a memory records with the net's shape"
+        assert memory is not None and memory.dtype == torch.float32 and memory.is_contiguous() and \
+            memory.shape[-1] == self.mem_size, "memory: float32 [M, %d]" % self.mem_size
+
+    def record_pre(self, obs, agent_state, memory, rotation, pheromone, *, spec, step: int, k: int, shape=None) -> None:
         """Before the environment step: states, agent_states and actions of k of every member's transitions."""
         assert self._pending is None, "record_pre twice without record_post"
-        assert memory is None, "a population's agents have no memory"
+        self._memory(memory, shape)
+        lib = _lib.load()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().antsrl_pop_record_pre(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
-                                                         _p(rotation), _p(pheromone), _p(self.states), _p(self.agent_states),
-                                                         _p(self.actions), _lib.stream(self.device)), "pop_record_pre")
-        self._pending = (spec, step, k)
+            if self.mem_size:
+                _lib.check(lib.antsrl_pop_memory_record_pre(C.byref(spec), C.byref(shape), step, k, self.head, self.max_len,
+                                                            _p(obs), _p(agent_state), _p(memory), _p(rotation), _p(pheromone),
+                                                            _p(self.states), _p(self.agent_states), _p(self.actions),
+                                                            _lib.stream(self.device)), "pop_memory_record_pre")
+            else:
+                _lib.check(lib.antsrl_pop_record_pre(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
+                                                     _p(rotation), _p(pheromone), _p(self.states), _p(self.agent_states),
+                                                     _p(self.actions), _lib.stream(self.device)), "pop_record_pre")
+        self._pending = (spec, step, k, shape)
 
     def record_post(self, obs, agent_state, memory, reward, done) -> None:
         """After it: rewards, new_states, new_agent_states and dones of the same transitions; then head and fill advance
         as DeviceReplayMemory's do for k rows."""
         assert self._pending is not None, "record_post without record_pre"
-        assert memory is None, "a population's agents have no memory"
-        spec, step, k = self._pending
+        spec, step, k, shape = self._pending
+        self._memory(memory, shape)
         if done.dtype == torch.bool:
             done = done.view(torch.uint8)
+        lib = _lib.load()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().antsrl_pop_record_post(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
-                                                          _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
-                                                          _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
-                                                          _lib.stream(self.device)), "pop_record_post")
+            if self.mem_size:
+                _lib.check(lib.antsrl_pop_memory_record_post(C.byref(spec), C.byref(shape), step, k, self.head, self.max_len,
+                                                             _p(obs), _p(agent_state), _p(memory), _p(reward), _p(done),
+                                                             _p(self.rewards), _p(self.new_states), _p(self.new_agent_states),
+                                                             _p(self.dones.view(torch.uint8)), _lib.stream(self.device)),
+                           "pop_memory_record_post")
+            else:
+                _lib.check(lib.antsrl_pop_record_post(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
+                                                      _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
+                                                      _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
+                                                      _lib.stream(self.device)), "pop_record_post")
         self._pending = None
         self._advance(k)
 
@@ -473,7 +504,11 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
     initialised as MemoryTrainer(seed=seed_p) is, its target a copy.  Per member: discount and learning rate.  Common:
     the net's shape, Adam's betas, eps and step count, update_target_every and the target counter.  `running_loss`
     (float64 [P]) is kept by the finalize launch from the first training step on.  The ring of a step is a
-    PopulationReplayMemory(..., agent_states_space=(2 + mem_size,))."""
+    PopulationReplayMemory(..., agent_states_space=(2 + mem_size,)).
+
+    `packed` (uint8 [P, pack_stride]) holds every member's ACTING net, its TARGET net as antsrl_memnet_pack_ex packs it
+    in bf16 (MemoryTrainer's `policy.packed` per member): what antsrl_pop_policy_memory acts with.  `_repack_policy`
+    packs it again, P launches, at construction, sync_target and load_state_dict; the step does not touch it."""
 
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
                  update_target_every: int = 1, *, power: int = 5, mem_size: int = 20, n_rot: int = 3, n_ph: int = 3):
@@ -489,6 +524,22 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         shapes = memnet_param_shapes(F, power, mem_size, n_rot, n_ph)
         for p, seed in enumerate(self.seeds):
             self._init_state(linear_init(shapes, seed), (self._model[p], self._target[p]))
+        stride, total = C.c_size_t(), C.c_size_t()
+        _lib.check(self._lib.antsrl_pop_memnet_sizes(C.byref(self.shape), MEMNET_PRECISIONS["bf16"], P, C.byref(stride),
+                                                     C.byref(total)), "pop_memnet_sizes")
+        self.pack_stride = stride.value
+        assert total.value == P * self.pack_stride and self.pack_stride % 256 == 0
+        self.packed = torch.zeros((P, self.pack_stride), dtype=torch.uint8, device=self.device)  # (torch blocks are 512-byte aligned)
+        self._repack_policy()
+
+    def _repack_policy(self, p: Optional[int] = None) -> None:
+        """MemoryTrainer._repack_policy for member p (None: every member): its block of `packed` := its target net,
+        antsrl_memnet_pack_ex in bf16 straight from the target's masters."""
+        with torch.cuda.device(self.device):
+            for q in (range(self.n_members) if p is None else (p,)):
+                ptrs = memnet_param_ptrs(self._views(self._target[q]))
+                _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), MEMNET_PRECISIONS["bf16"], ptrs,
+                                                           _p(self.packed[q]), _lib.stream(self.device)), "memnet_pack_ex")
 
     def _sizes(self, B: int) -> tuple:
         """antsrl_pop_memtrain_sizes -> (a member's state stride, trained_floats, a member's workspace stride, the
@@ -507,21 +558,25 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         return _clones(self._views(self._target[p]))
 
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
-        """MemoryTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
+        """MemoryTrainer.load_state_dict for member p (None: every member): model AND target (and the acting pack);
+        Adam's state is kept."""
         for q in (range(self.n_members) if p is None else (p,)):
             keep = self._model[q, self._adam_range()].clone()
             self._init_state(sd, (self._model[q], self._target[q]))
             self._model[q, self._adam_range()] = keep
+        self._repack_policy(p)
 
     def adam_state(self, p: int) -> dict:
         return self._adam_dict(self._model[p], self.step_count)
 
     def sync_target(self) -> None:
-        """target := model for every member (antsrl_memtrain_copy on its block: masters and packs, not Adam's moments)."""
+        """target := model for every member (antsrl_memtrain_copy on its block: masters and packs, not Adam's moments),
+        and the acting packs with it."""
         with torch.cuda.device(self.device):
             for p in range(self.n_members):
                 _lib.check(self._lib.antsrl_memtrain_copy(C.byref(self.shape), _p(self._model[p]), _p(self._target[p]),
                                                           _lib.stream(self.device)), "memtrain_copy")
+        self._repack_policy()
         self.syncs += 1
 
     # ---- the step -----------------------------------------------------------------------------------------------------
@@ -576,8 +631,10 @@ class _Population(_LoopAgent):
     def epsilon(self, v) -> None:
         self._epsilon = np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n_members,)).copy()
 
-    def _setup(self, api_or_env, trainer_cls):
-        """The front of setup: the geometry, the trainer, the ring, the action buffers, the generator and the counters."""
+    def _setup(self, api_or_env, trainer_cls, trainer_kw: Optional[dict] = None, agent_states_space: Sequence[int] = (2,)):
+        """The front of setup: the geometry, the trainer (trainer_kw: what its net takes by name beyond the common
+        arguments), the ring (agent_states_space: the width of its agent_states rows), the action buffers, the generator
+        and the counters."""
         env = _backend(api_or_env)
         cfg = env.cfg
         self.device = env.device
@@ -588,8 +645,10 @@ class _Population(_LoopAgent):
             raise ValueError("record_per_step = %d is not in [1, %d], a member's ants" % (self.record_per_step, self.g.Mm))
         self.seeds = [m["seed"] for m in self.members]
         self.trainer = trainer_cls(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
-                                   [m["learning_rate"] for m in self.members], update_target_every=self.update_target_every)
-        self.replay_memory = PopulationReplayMemory(self.n_members, self.replay_size, self.observation_space, device=self.device)
+                                   [m["learning_rate"] for m in self.members], update_target_every=self.update_target_every,
+                                   **(trainer_kw or {}))
+        self.replay_memory = PopulationReplayMemory(self.n_members, self.replay_size, self.observation_space, device=self.device,
+                                                    agent_states_space=agent_states_space)
         M = cfg.n_envs * cfg.n_ants
         self._rot = torch.zeros((M,), dtype=torch.int8, device=self.device)
         self._ph = torch.zeros((M,), dtype=torch.int8, device=self.device)
@@ -773,3 +832,96 @@ class PopulationExploreAgent(_Population):
     def _member_tensors(self) -> tuple:
         tr = self.trainer
         return ((tr.model, 0), (tr.target, 0), (tr._adam, 1))
+
+
+class PopulationMemoryAgent(_Population):
+    """P MemoryAgents in lockstep: CollectAgentMemory, the agent main.py trains, for every member of a sweep (the module
+    docstring).  members: PopulationAgent's dicts (MemoryAgent's defaults where a key is missing).  Common
+    to all members: the net's shape (mem_size, power), `state_memory` ("reference": agent_states rows hold the
+    post-action memory, as the reference stores it; "carried": the pre-action memory; antsrl_amd/agent.py says why
+    there are two), record_per_step, replay_size, minibatch (the reference's 264), min_replay, update_target_every;
+    `seed` seeds the generator of the minibatch indices.
+
+    The acting net of a member is its TARGET net, packed in bf16 (PopulationMemoryTrainer.packed), so it changes at a
+    sync or a load only.  get_action returns (rotation, pheromone, the new memory [M, mem_size]): one launch of every
+    member's forward (antsrl_pop_policy_memory), with `training` one of antsrl_pop_memory_select (uniform actions and the
+    old memory back for the ants of a member's exploring environments), then the two memory halves swap, as
+    MemoryAgent's do.  rollout_step is _Population's: one AntsPopSpec per step and no host read.
+
+    Not here: skip_explored (the explore plan and the tile-list forward) and the fp32 acting precision."""
+
+    name = "collect_agent_memory_population"
+    pheromones = 3
+
+    def __init__(self, members: Sequence[dict], *, mem_size: int = 20, power: int = 5, state_memory: str = "reference",
+                 record_per_step: Optional[int] = None, replay_size: int = 50000, minibatch: int = 264,
+                 min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
+        assert state_memory in ("reference", "carried"), "state_memory must be 'reference' or 'carried', not %r" % (state_memory,)
+        super().__init__(members, record_per_step=record_per_step, replay_size=replay_size, minibatch=minibatch,
+                         min_replay=min_replay, update_target_every=update_target_every, seed=seed)
+        self.mem_size, self.power, self.state_memory = mem_size, power, state_memory
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """MemoryAgent.setup for every member; trained_model goes to every member."""
+        self._setup(api_or_env, PopulationMemoryTrainer,
+                    dict(power=self.power, mem_size=self.mem_size, n_rot=self.rotations, n_ph=self.pheromones),
+                    agent_states_space=(2 + self.mem_size,))
+        M = self._rot.numel()
+        self._mem = [torch.zeros((M, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
+        self._cur = 0  # self._mem[self._cur] is previous_memory (collect_agent_memory.py:111), every member's rows
+        self._memory_before = self._mem[1]
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    @property
+    def previous_memory(self) -> torch.Tensor:
+        return self._mem[self._cur]
+
+    def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
+        """-> (rotation int8, pheromone int8, memory float32 [M, mem_size]), device tensors: every member's target net on
+        its own rows, the new memory into the other half; with `training`, antsrl_pop_memory_select then replaces the
+        actions of the environments that explore this step, each member with its own seed and epsilon, and gives their
+        ants the old memory back."""
+        assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
+            "a population reads the dense observation rows of its whole batch"
+        assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
+        step, spec, tr = self.step_counter, self._spec(spec), self.trainer
+        old, new = self._mem[self._cur], self._mem[1 - self._cur]
+        lead = obs.shape[:-3]
+        with torch.cuda.device(self.device):
+            st = _lib.stream(self.device)
+            _lib.check(self._lib.antsrl_pop_policy_memory(C.byref(spec), C.byref(tr.shape), MEMNET_PRECISIONS["bf16"],
+                                                          _p(tr.packed), _p(obs), _p(agent_state), _p(old), _p(new),
+                                                          _p(self._rot), _p(self._ph), None, st), "pop_policy_memory")
+            if training:
+                _lib.check(self._lib.antsrl_pop_memory_select(C.byref(spec), C.byref(tr.shape), step, _p(self._rot),
+                                                              _p(self._ph), _p(old), _p(new), _p(self._explored), st),
+                           "pop_memory_select")
+        self._memory_before = old
+        self._cur = 1 - self._cur
+        self._action_step = step
+        self.step_counter += 1
+        return self._rot.view(lead), self._ph.view(lead), new
+
+    def _state_memory(self) -> torch.Tensor:
+        """The memory that goes into agent_states (MemoryAgent._state_memory)."""
+        return self.previous_memory if self.state_memory == "reference" else self._memory_before
+
+    def _record_kw(self) -> dict:
+        return dict(super()._record_kw(), shape=self.trainer.shape)
+
+    def _member_tensors(self) -> tuple:
+        tr = self.trainer
+        return ((tr._model, 0), (tr._target, 0), (tr.packed, 0))
+
+    def copy_member(self, src: int, dst: int, ring: bool = True) -> None:
+        """_Population.copy_member (a state block holds the weights AND Adam's moments; the acting pack goes with the
+        target), and member src's rows of BOTH memory halves over dst's.  env.fork copies src's ants into dst's
+        environments; a fork without their memory would hand dst's memory, which belongs to the ants that were there
+        before, to src's ants.  Call it with the fork, between two steps."""
+        super().copy_member(src, dst, ring)
+        if src == dst:
+            return
+        Mm = self.g.Mm
+        for m in self._mem:
+            m[dst * Mm:(dst + 1) * Mm].copy_(m[src * Mm:(src + 1) * Mm])

@@ -1581,9 +1581,10 @@ int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *
 
 /* The population of memory nets: the DQN training step of P memory agent nets (the net of antsrl_memtrain_*, the agent
  * main.py drives) in the launches of ONE step: 16 + 1 = 17 whatever P is, each the single step's kernel on a grid
- * (x, P) with the member in the grid's y dimension.  Only the training step: acting with per-member packs, select and
- * record with the carried memory and the agent's loop are not here yet.  The spec is the population of linear agents'
- * (the training entry reads its members' discount and learning_rate and its n_features, which must be the shape's).
+ * (x, P) with the member in the grid's y dimension; and behind it the rest of the memory agents' loop for a population
+ * (antsrl_pop_policy_memory, antsrl_pop_memory_select, antsrl_pop_memory_record_pre / _post, below).  The spec is the
+ * population of linear agents' (the training entry reads its members' discount and learning_rate and its n_features,
+ * which must be the shape's).
  *
  * THE DEFINING PROPERTY: member p is, bit for bit, antsrl_memtrain_grad followed by antsrl_memtrain_apply on its own
  * state blocks, ring slab and idx row, with its own discount and learning rate; its result does not depend on P or on
@@ -1620,6 +1621,59 @@ int antsrl_pop_memtrain_step(const AntsPopSpec *s, const AntsMemNetShape *shape,
                              const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps,
                              float *grads, float *loss, double *running_loss, int first_loss, void *workspace,
                              void *stream);
+
+/* The population of memory nets, the loop around the step: acting with one pack per member, the epsilon-greedy select
+ * that gives exploring ants their old memory back, and the ring's two record halves with the carried memory.  One
+ * launch per entry whatever P is.  Em = n_envs / n_members, Mm = Em * n_ants; member p owns environments
+ * [p Em, (p + 1) Em) and ants [p Mm, (p + 1) Mm) of every array, as in the populations above.
+ *
+ * THE DEFINING PROPERTY: member p computes, bit for bit, what antsrl_policy_memory, antsrl_agent_select and
+ * antsrl_replay_record_pre / _post compute on its own slice with its own pack, seed and epsilon and env_id_base + p Em;
+ * no output of a member depends on P or on another member's data.
+ *
+ * Layout: packed is [P][pack_stride] bytes, a member's block what antsrl_memnet_pack_ex(ANTSRL_MEMNET_BF16) writes at
+ * packed + p * pack_stride (the caller packs a member when its acting weights change: P calls, not on the hot path);
+ * pack_stride is antsrl_memnet_packed_bytes' value, a multiple of 256 (checked, not assumed).  obs [P][Mm][n_features]
+ * dense; agent_state [P][Mm][agent_dim]; mem_in, mem_out, mem_old, mem_next, memory [P][Mm][mem_size]; rotation,
+ * pheromone [P][Mm]; q_out [P][Mm][n_rot + n_ph] or NULL; explored [n_envs] or NULL; the ring's arrays with a leading
+ * [P] of max_len rows, agent_states and new_agent_states rows agent_dim + mem_size floats wide.
+ *
+ * Precision: bf16 operands only.  An unknown precision is ANTSRL_E_INVALID, before any other check;
+ * ANTSRL_MEMNET_FP32 is ANTSRL_E_UNSUPPORTED (a population acts with the bf16 forward).
+ *
+ * Refusals (ANTSRL_E_INVALID unless stated), each in words and before any HIP call: a NULL spec or shape; the spec's
+ * rules, as above; the shape's, as antsrl_memnet_packed_bytes'; the spec's n_features is not the shape's; n_members
+ * outside [1, ANTSRL_POP_MAX]; Mm above 2^31 - 1 - 128, beyond which the tile count of a member's grid row does not fit
+ * an int (UNSUPPORTED); a pack stride that is not a multiple of 256 (UNSUPPORTED); packed NULL or not 256-byte
+ * aligned; obs, agent_state, mem_in, mem_out, rotation NULL, a float array not 4-byte aligned (bfloat16 obs: 2),
+ * actions not 8-byte aligned; mem_old and mem_next overlapping without being equal; for the record pair the ring rules
+ * of antsrl_pop_record_pre (K in [1, Mm], max_len in [1, 2^40], head in [0, max_len)) and memory NULL.
+ *
+ *   antsrl_pop_memnet_sizes    pack_stride and packed_bytes = n_members * pack_stride (either may be NULL).  Host only.
+ *   antsrl_pop_policy_memory   every member's net on its rows: rotation (argmax - n_rot / 2), pheromone (may be NULL),
+ *                         the new memory into mem_out (mem_in == mem_out is allowed: in place, as the single entry)
+ *                         and, when q_out is not NULL, both heads' outputs.  Grid (ceil(Mm / 128), P) at D <= 320.
+ *   antsrl_pop_memory_select   antsrl_agent_select per member with the member's seed and epsilon: the ants of an
+ *                         exploring environment take uniform actions and, unless mem_old == mem_next, their rows of
+ *                         mem_next become mem_old's.  n_rot, n_ph and mem_size are the shape's.  explored may be NULL.
+ *   antsrl_pop_memory_record_pre / _post   antsrl_pop_record_pre / _post with agent_dim, mem_size and n_rot / 2 from the
+ *                         shape and `memory` behind agent_state in every ring row.  (The pair without a shape keeps
+ *                         writing agent_dim = 2 wide rows and takes no memory.) */
+int antsrl_pop_memnet_sizes(const AntsMemNetShape *shape, int precision, int32_t n_members, size_t *pack_stride,
+                            size_t *packed_bytes);
+int antsrl_pop_policy_memory(const AntsPopSpec *s, const AntsMemNetShape *shape, int precision, const void *packed,
+                             const void *obs, const float *agent_state, const float *mem_in, float *mem_out,
+                             int8_t *rotation, int8_t *pheromone, float *q_out, void *stream);
+int antsrl_pop_memory_select(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int8_t *rotation,
+                             int8_t *pheromone, const float *mem_old, float *mem_next, uint8_t *explored, void *stream);
+int antsrl_pop_memory_record_pre(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K, int64_t head,
+                                 int64_t max_len, const void *obs, const float *agent_state, const float *memory,
+                                 const int8_t *rotation, const int8_t *pheromone, float *states, float *agent_states,
+                                 int64_t *actions, void *stream);
+int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K, int64_t head,
+                                  int64_t max_len, const void *obs, const float *agent_state, const float *memory,
+                                  const float *reward, const uint8_t *done, float *rewards, float *new_states,
+                                  float *new_agent_states, uint8_t *dones, void *stream);
 
 #ifdef __cplusplus
 }
