@@ -1,14 +1,12 @@
-// antsrl_popapi.hip — the population of linear agents in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The population
-// of linear agents"): antsrl_pop_policy / _select / _record_pre / _record_post / _lintrain_step in front of
-// antsrl_population.hip's kernels; and behind them the population of explore agents ("The population of explore
-// agents"): antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes / _step in front of antsrl_popexplore.hip's, on the same
-// spec rules (select and record are the entries above: that population's net has no pheromone head and its ring none);
-// and the population of joint agents ("The population of joint agents"): antsrl_pop_joint_policy /
-// antsrl_pop_jointtrain_sizes / _step in front of antsrl_popjoint.hip's, the explore entries with the joint net; and the
-// training step of the population of memory nets ("The population of memory nets"): antsrl_pop_memtrain_sizes / _step in
-// front of antsrl_popmemtrain.hip's; and the memory agents' loop around it: antsrl_pop_memnet_sizes /
-// antsrl_pop_policy_memory in front of antsrl_popmemnet.hip's forward, antsrl_pop_memory_select and
-// antsrl_pop_memory_record_pre / _post in front of antsrl_population.hip's select and record with the carried memory.
+// antsrl_popapi.hip — the populations in the C-ABI of libantsrl_hip.so (include/antsrl.h, "The population of ..."), one
+// line per population: its entries, and the file of the kernels they stand in front of.
+//   linear agents   antsrl_pop_policy / _select / _record_pre / _record_post / _lintrain_step        antsrl_population.hip
+//   explore agents  antsrl_pop_explore_policy / antsrl_pop_exptrain_sizes / _step (select and        antsrl_popexplore.hip
+//                   record are the linear agents': no pheromone head, and the ring stores none)
+//   joint agents    antsrl_pop_joint_policy / antsrl_pop_jointtrain_sizes / _step (likewise)         antsrl_popjoint.hip
+//   memory nets     antsrl_pop_memtrain_sizes / _step                                                antsrl_popmemtrain.hip
+//   memory agents   antsrl_pop_memnet_sizes / antsrl_pop_policy_memory                               antsrl_popmemnet.hip
+//                   antsrl_pop_memory_select / _record_pre / _record_post (with the carried memory)  antsrl_population.hip
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -79,18 +77,26 @@ static int pop_flat_rule(const char *who, const AntsPopSpec *s, int Em)
     return ANTSRL_OK;
 }
 
+// the front of the three flat acting entries: the spec's rules, the acting kernel's, then the rows; fills *Em
+static int pop_flat_policy(const char *who, const AntsPopSpec *s, const void *obs, const float *agent_state, int *Em)
+{
+    PopTable t;
+    int rc = pop_spec(who, s, &t, Em);
+    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, *Em);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(obs, 16);
+    REQUIRE(agent_state, 4);
+    return ANTSRL_OK;
+}
+
 extern "C" int antsrl_pop_policy(const AntsPopSpec *s, const void *obs, const float *agent_state, const float *w1,
                                  const float *b1, const float *heads, const float *target_l3, int8_t *rotation,
                                  int8_t *pheromone, void *stream)
 {
     const char *who = "pop_policy";
-    PopTable t;
     int Em = 0;
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, Em);
+    const int rc = pop_flat_policy(who, s, obs, agent_state, &Em);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, 16);
-    REQUIRE(agent_state, 4);
     REQUIRE(w1, 4);
     REQUIRE(b1, 4);
     REQUIRE(heads, 4);
@@ -120,17 +126,61 @@ extern "C" int antsrl_pop_select(const AntsPopSpec *s, uint64_t step, int8_t *ro
     return enqueued(antsrl_launch_pop_select(a, t, s->n_members, Em, (hipStream_t)stream), who);
 }
 
-// a record entry's RecArgs for member 0: K rows per member into the rows behind `head` of every member's slab
-static int pop_rec(const char *who, const AntsPopSpec *s, int Em, uint64_t step, int64_t K, int64_t head, int64_t max_len,
-                   RecArgs *a)
+static int pop_mem_spec(const char *who, const AntsPopSpec *s, const AntsMemNetShape *shape, PopTable *t, int *Em, MemNetDims *d,
+                        size_t *pack_stride); // (with the memory agents' entries, below)
+
+// The front of a record entry: the spec's rules, and with with_memory the shape's (pop_mem_spec), then RecArgs for member
+// 0: K rows per member into the rows behind `head` of every member's slab.  With a memory, agent_states rows are
+// agent_dim + mem_size wide.
+static int pop_rec(const char *who, const AntsPopSpec *s, bool with_memory, const AntsMemNetShape *shape, uint64_t step, int64_t K,
+                   int64_t head, int64_t max_len, PopTable *t, int *Em, RecArgs *a)
 {
-    a->M = (long long)Em * s->n_ants;
-    const int rc = antsrl_ring_rows(who, "n_envs / n_members * n_ants", a->M, K, head, max_len, a);
+    MemNetDims d;
+    size_t stride = 0;
+    int rc = with_memory ? pop_mem_spec(who, s, shape, t, Em, &d, &stride) : pop_spec(who, s, t, Em);
+    if (rc != ANTSRL_OK) return rc;
+    a->M = (long long)*Em * s->n_ants;
+    rc = antsrl_ring_rows(who, "n_envs / n_members * n_ants", a->M, K, head, max_len, a);
     if (rc != ANTSRL_OK) return rc;
     a->step = step; a->env_base = (uint64_t)s->env_id_base;
     a->pitch = s->n_features;
     a->n_ants = s->n_ants; a->F = s->n_features; a->A = POP_AGENT_DIM; a->mem = 0; a->half_rot = POP_N_ROT / 2;
+    if (with_memory) { a->A = d.A; a->mem = d.mem; a->half_rot = d.n_rot / 2; }
     return ANTSRL_OK;
+}
+
+// antsrl_pop_record_pre and antsrl_pop_memory_record_pre (with_memory: shape and memory are theirs; else NULL)
+static int pop_record_pre(const char *who, const AntsPopSpec *s, bool with_memory, const AntsMemNetShape *shape, uint64_t step,
+                          int64_t K, int64_t head, int64_t max_len, const void *obs, const float *agent_state, const float *memory,
+                          const int8_t *rotation, const int8_t *pheromone, float *states, float *agent_states, int64_t *actions,
+                          void *stream)
+{
+    PopTable t;
+    int Em = 0;
+    RecArgs a = {};
+    int rc = pop_rec(who, s, with_memory, shape, step, K, head, max_len, &t, &Em, &a);
+    if (rc != ANTSRL_OK) return rc;
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_pre(who, &a, bf16, obs, agent_state, memory, rotation, pheromone, states, agent_states, actions);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, false, (hipStream_t)stream), who);
+}
+
+// antsrl_pop_record_post and antsrl_pop_memory_record_post, likewise
+static int pop_record_post(const char *who, const AntsPopSpec *s, bool with_memory, const AntsMemNetShape *shape, uint64_t step,
+                           int64_t K, int64_t head, int64_t max_len, const void *obs, const float *agent_state,
+                           const float *memory, const float *reward, const uint8_t *done, float *rewards, float *new_states,
+                           float *new_agent_states, uint8_t *dones, void *stream)
+{
+    PopTable t;
+    int Em = 0;
+    RecArgs a = {};
+    int rc = pop_rec(who, s, with_memory, shape, step, K, head, max_len, &t, &Em, &a);
+    if (rc != ANTSRL_OK) return rc;
+    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
+    rc = antsrl_rec_post(who, &a, bf16, obs, agent_state, memory, reward, done, rewards, new_states, new_agent_states, dones);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_pop_record_pre(const AntsPopSpec *s, uint64_t step, int64_t K, int64_t head, int64_t max_len,
@@ -138,17 +188,8 @@ extern "C" int antsrl_pop_record_pre(const AntsPopSpec *s, uint64_t step, int64_
                                      const int8_t *pheromone, float *states, float *agent_states, int64_t *actions,
                                      void *stream)
 {
-    const char *who = "pop_record_pre";
-    PopTable t;
-    int Em = 0;
-    RecArgs a = {};
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_rec(who, s, Em, step, K, head, max_len, &a);
-    if (rc != ANTSRL_OK) return rc;
-    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
-    rc = antsrl_rec_pre(who, &a, bf16, obs, agent_state, nullptr, rotation, pheromone, states, agent_states, actions);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, false, (hipStream_t)stream), who);
+    return pop_record_pre("pop_record_pre", s, false, nullptr, step, K, head, max_len, obs, agent_state, nullptr, rotation, pheromone,
+                          states, agent_states, actions, stream);
 }
 
 extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64_t K, int64_t head, int64_t max_len,
@@ -156,17 +197,8 @@ extern "C" int antsrl_pop_record_post(const AntsPopSpec *s, uint64_t step, int64
                                       float *rewards, float *new_states, float *new_agent_states, uint8_t *dones,
                                       void *stream)
 {
-    const char *who = "pop_record_post";
-    PopTable t;
-    int Em = 0;
-    RecArgs a = {};
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_rec(who, s, Em, step, K, head, max_len, &a);
-    if (rc != ANTSRL_OK) return rc;
-    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
-    rc = antsrl_rec_post(who, &a, bf16, obs, agent_state, nullptr, reward, done, rewards, new_states, new_agent_states, dones);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
+    return pop_record_post("pop_record_post", s, false, nullptr, step, K, head, max_len, obs, agent_state, nullptr, reward, done,
+                           rewards, new_states, new_agent_states, dones, stream);
 }
 
 // The training entries refuse in the order spec, B (antsrl_dqn_B, antsrl_dqn.h, told what of the entry's step its limit
@@ -218,17 +250,69 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
 
 // ---- the population of explore agents (antsrl_popexplore.hip) -------------------------------------------------------------
 
+// REQUIRE for a pointer that the entries of a shared front name differently
+static int pop_require(const char *who, const char *name, const void *p, int align)
+{
+    if (!p) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
+    if ((uintptr_t)p & (uintptr_t)(align - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, name, align);
+    return ANTSRL_OK;
+}
+
+// antsrl_pop_exptrain_sizes and antsrl_pop_jointtrain_sizes: a flat-block net's, given its largest minibatch, the floats of
+// a member's block and the bytes of a member's part of the workspace
+static int pop_flat_sizes(const char *who, int32_t n_features, int64_t B, int32_t n_members, int max_B, size_t (*floats)(int),
+                          size_t (*stride_of)(int), size_t *trained_floats, size_t *workspace_stride, size_t *workspace_bytes,
+                          int32_t *launches)
+{
+    int rc = lt_features(who, n_features);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, max_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    const size_t stride = stride_of((int)B);
+    if (trained_floats) *trained_floats = floats(n_features);
+    if (workspace_stride) *workspace_stride = stride;
+    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
+    if (launches) *launches = 2;
+    return ANTSRL_OK;
+}
+
+// The front of antsrl_pop_exptrain_step and antsrl_pop_jointtrain_step, whose Args differ in the target's field alone (the
+// entry sets it, and dh and blocks from its own net's layout): the refusals in the training entries' order, then member
+// 0's minibatch (the slab's arrays, idx, grads, loss; the discount comes from the table; its partials are the front of the
+// workspace, its dh behind them), the model and Adam's moments.
+template <class Args>
+static int pop_flat_step(const char *who, const AntsPopSpec *s, int max_B, float *model, const float *target,
+                         const char *target_name, float *adam_m, float *adam_v, const float *states,
+                         const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                         const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                         int64_t step, double beta1, double beta2, double eps, float *grads, float *loss, const double *running_loss, void *workspace, Args *a, PopTable *t)
+{
+    int Em = 0;
+    int rc = pop_spec(who, s, t, &Em);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, max_B, POP_ET_LIMIT);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    if ((rc = pop_require(who, target_name, target, 4)) != ANTSRL_OK) return rc;
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    REQUIRE(idx, 8);
+    REQUIRE(workspace, 256);
+    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
+                   B, 0.0f, grads, false, loss, workspace, &a->batch);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a->adam, t);
+    if (rc != ANTSRL_OK) return rc;
+    a->model = model;
+    a->adam.m = adam_m; a->adam.v = adam_v;
+    return ANTSRL_OK;
+}
+
 extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, const float *agent_state,
                                          const float *target_blocks, int8_t *rotation, void *stream)
 {
     const char *who = "pop_explore_policy";
-    PopTable t;
     int Em = 0;
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, Em);
+    const int rc = pop_flat_policy(who, s, obs, agent_state, &Em);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, 16);
-    REQUIRE(agent_state, 4);
     REQUIRE(target_blocks, 4);
     REQUIRE(rotation, 1);
     PopExplorePolicyArgs a;
@@ -240,17 +324,8 @@ extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, 
 extern "C" int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
                                          size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
 {
-    const char *who = "pop_exptrain_sizes";
-    int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
-    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
-    if (rc != ANTSRL_OK) return rc;
-    const size_t stride = antsrl_pop_exptrain_stride((int)B);
-    if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
-    if (workspace_stride) *workspace_stride = stride;
-    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
-    if (launches) *launches = 2;
-    return ANTSRL_OK;
+    return pop_flat_sizes("pop_exptrain_sizes", n_features, B, n_members, POP_ET_MAX_B, antsrl_exptrain_floats,
+                          antsrl_pop_exptrain_stride, trained_floats, workspace_stride, workspace_bytes, launches);
 }
 
 extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, const float *target, float *adam_m, float *adam_v,
@@ -262,25 +337,12 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
 {
     const char *who = "pop_exptrain_step";
     PopTable t;
-    int Em = 0;
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_ET_MAX_B, POP_ET_LIMIT);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(model, 4);
-    REQUIRE(target, 4);
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    REQUIRE(idx, 8);
-    REQUIRE(workspace, 256);
     ExpTrainArgs a = {};
-    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table); its partials are the
-    // front of the workspace, its dh behind them
-    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
-                   B, 0.0f, grads, false, loss, workspace, &a.batch);
-    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
+    const int rc = pop_flat_step(who, s, POP_ET_MAX_B, model, target, "target", adam_m, adam_v, states, agent_states, actions,
+                                 rewards, new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads, loss,
+                                 running_loss, workspace, &a, &t);
     if (rc != ANTSRL_OK) return rc;
-    a.model = model; a.target = target;
-    a.adam.m = adam_m; a.adam.v = adam_v;
+    a.target = target;
     a.dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
     a.blocks = antsrl_exptrain_blocks((int)B);
     const PopRunningLoss rl = {running_loss, first_loss != 0};
@@ -294,13 +356,9 @@ extern "C" int antsrl_pop_joint_policy(const AntsPopSpec *s, const void *obs, co
                                        int8_t *pheromone, void *stream)
 {
     const char *who = "pop_joint_policy";
-    PopTable t;
     int Em = 0;
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = pop_flat_rule(who, s, Em);
+    const int rc = pop_flat_policy(who, s, obs, agent_state, &Em);
     if (rc != ANTSRL_OK) return rc;
-    REQUIRE(obs, 16);
-    REQUIRE(agent_state, 4);
     REQUIRE(model_blocks, 4);
     REQUIRE(target_l3, 4);
     REQUIRE(rotation, 1);
@@ -315,17 +373,8 @@ extern "C" int antsrl_pop_joint_policy(const AntsPopSpec *s, const void *obs, co
 extern "C" int antsrl_pop_jointtrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
                                            size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
 {
-    const char *who = "pop_jointtrain_sizes";
-    int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_JT_MAX_B, POP_ET_LIMIT);
-    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
-    if (rc != ANTSRL_OK) return rc;
-    const size_t stride = antsrl_pop_jointtrain_stride((int)B);
-    if (trained_floats) *trained_floats = antsrl_jointtrain_floats(n_features);
-    if (workspace_stride) *workspace_stride = stride;
-    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
-    if (launches) *launches = 2;
-    return ANTSRL_OK;
+    return pop_flat_sizes("pop_jointtrain_sizes", n_features, B, n_members, POP_JT_MAX_B, antsrl_jointtrain_floats,
+                          antsrl_pop_jointtrain_stride, trained_floats, workspace_stride, workspace_bytes, launches);
 }
 
 extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *target_l3, float *adam_m,
@@ -337,25 +386,12 @@ extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, co
 {
     const char *who = "pop_jointtrain_step";
     PopTable t;
-    int Em = 0;
-    int rc = pop_spec(who, s, &t, &Em);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, POP_JT_MAX_B, POP_ET_LIMIT);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(model, 4);
-    REQUIRE(target_l3, 4);
-    REQUIRE(adam_m, 4);
-    REQUIRE(adam_v, 4);
-    REQUIRE(idx, 8);
-    REQUIRE(workspace, 256);
     JointTrainArgs a = {};
-    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table); its partials are the
-    // front of the workspace, its dh behind them
-    rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
-                   B, 0.0f, grads, false, loss, workspace, &a.batch);
-    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
+    const int rc = pop_flat_step(who, s, POP_JT_MAX_B, model, target_l3, "target_l3", adam_m, adam_v, states, agent_states, actions,
+                                 rewards, new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads, loss,
+                                 running_loss, workspace, &a, &t);
     if (rc != ANTSRL_OK) return rc;
-    a.model = model; a.target_l3 = target_l3;
-    a.adam.m = adam_m; a.adam.v = adam_v;
+    a.target_l3 = target_l3;
     a.dh = (float *)((unsigned char *)workspace + antsrl_jointtrain_dh_offset((int)B));
     a.blocks = antsrl_jointtrain_blocks((int)B);
     const PopRunningLoss rl = {running_loss, first_loss != 0};
@@ -363,6 +399,13 @@ extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, co
 }
 
 // ---- the population of memory nets (antsrl_popmemtrain.hip) ----------------------------------------------------------------
+
+// a spec and a shape that have passed their own rules speak of the same rows
+static int pop_same_features(const char *who, const AntsPopSpec *s, const AntsMemNetShape *shape)
+{
+    if (s->n_features == shape->n_features) return ANTSRL_OK;
+    return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
+}
 
 // the shape's rules under the entry's name, then the two strides: the single trainer's state and workspace bytes, which
 // must be multiples of 256 for every member's blocks to start as aligned as a single trainer's
@@ -424,8 +467,7 @@ extern "C" int antsrl_pop_memtrain_step(const AntsPopSpec *s, const AntsMemNetSh
     int rc = pop_spec(who, s, &t, &Em);
     if (rc == ANTSRL_OK) rc = pop_mem_layout(who, shape, B, &d, &L, &W);
     if (rc != ANTSRL_OK) return rc;
-    if (s->n_features != shape->n_features)
-        return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
+    if ((rc = pop_same_features(who, s, shape)) != ANTSRL_OK) return rc;
     REQUIRE(net_states, 256);
     REQUIRE(target_states, 256);
     REQUIRE(idx, 8);
@@ -474,9 +516,7 @@ static int pop_mem_spec(const char *who, const AntsPopSpec *s, const AntsMemNetS
     int rc = pop_spec(who, s, t, Em);
     if (rc == ANTSRL_OK) rc = pop_memnet_layout(who, shape, d, pack_stride);
     if (rc != ANTSRL_OK) return rc;
-    if (s->n_features != shape->n_features)
-        return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
-    return ANTSRL_OK;
+    return pop_same_features(who, s, shape);
 }
 
 extern "C" int antsrl_pop_memnet_sizes(const AntsMemNetShape *shape, int precision, int32_t n_members, size_t *pack_stride,
@@ -559,34 +599,13 @@ extern "C" int antsrl_pop_memory_select(const AntsPopSpec *s, const AntsMemNetSh
     return enqueued(antsrl_launch_pop_memory_select(a, t, s->n_members, Em, vec, (hipStream_t)stream), who);
 }
 
-// pop_rec with the shape's widths: agent_states rows are agent_dim + mem_size wide
-static int pop_mem_rec(const char *who, const AntsPopSpec *s, const MemNetDims &d, int Em, uint64_t step, int64_t K, int64_t head,
-                       int64_t max_len, RecArgs *a)
-{
-    const int rc = pop_rec(who, s, Em, step, K, head, max_len, a);
-    if (rc != ANTSRL_OK) return rc;
-    a->A = d.A; a->mem = d.mem; a->half_rot = d.n_rot / 2;
-    return ANTSRL_OK;
-}
-
 extern "C" int antsrl_pop_memory_record_pre(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K,
                                             int64_t head, int64_t max_len, const void *obs, const float *agent_state,
                                             const float *memory, const int8_t *rotation, const int8_t *pheromone,
                                             float *states, float *agent_states, int64_t *actions, void *stream)
 {
-    const char *who = "pop_memory_record_pre";
-    PopTable t;
-    int Em = 0;
-    MemNetDims d;
-    size_t stride = 0;
-    RecArgs a = {};
-    int rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
-    if (rc == ANTSRL_OK) rc = pop_mem_rec(who, s, d, Em, step, K, head, max_len, &a);
-    if (rc != ANTSRL_OK) return rc;
-    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
-    rc = antsrl_rec_pre(who, &a, bf16, obs, agent_state, memory, rotation, pheromone, states, agent_states, actions);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, false, (hipStream_t)stream), who);
+    return pop_record_pre("pop_memory_record_pre", s, true, shape, step, K, head, max_len, obs, agent_state, memory, rotation,
+                          pheromone, states, agent_states, actions, stream);
 }
 
 extern "C" int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMemNetShape *shape, uint64_t step, int64_t K,
@@ -594,17 +613,6 @@ extern "C" int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMem
                                              const float *memory, const float *reward, const uint8_t *done, float *rewards,
                                              float *new_states, float *new_agent_states, uint8_t *dones, void *stream)
 {
-    const char *who = "pop_memory_record_post";
-    PopTable t;
-    int Em = 0;
-    MemNetDims d;
-    size_t stride = 0;
-    RecArgs a = {};
-    int rc = pop_mem_spec(who, s, shape, &t, &Em, &d, &stride);
-    if (rc == ANTSRL_OK) rc = pop_mem_rec(who, s, d, Em, step, K, head, max_len, &a);
-    if (rc != ANTSRL_OK) return rc;
-    const bool bf16 = s->obs_format == ANTSRL_OBS_BF16;
-    rc = antsrl_rec_post(who, &a, bf16, obs, agent_state, memory, reward, done, rewards, new_states, new_agent_states, dones);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_pop_record(a, t, s->n_members, Em, bf16, true, (hipStream_t)stream), who);
+    return pop_record_post("pop_memory_record_post", s, true, shape, step, K, head, max_len, obs, agent_state, memory, reward, done,
+                           rewards, new_states, new_agent_states, dones, stream);
 }

@@ -1,44 +1,46 @@
-"""A population of P CollectAgents trained in lockstep on one BatchedAntsEnv, one launch per stage of the loop whatever
-P is (include/antsrl.h, "The population of linear agents"; antsrl_population.hip).
+"""Populations: P agents trained in lockstep on one BatchedAntsEnv, one launch per stage of the loop whatever P is
+(include/antsrl.h, "The population of linear agents" and the sections behind it).
 
     pop = PopulationAgent([dict(epsilon=0.5, discount=0.99, learning_rate=1e-4, seed=s) for s in range(16)],
                           record_per_step=4096, min_replay=1000)
     pop.setup(env)                      # env.cfg.n_envs = 16 * Em: member p owns environments [p Em, (p + 1) Em)
     loss = pop.rollout_step(env)        # float32 [P] on the device (0 below min_replay): five launches and the env's step
 
-Member p is, bit for bit, a CollectAgent run alone on a handle of its Em environments created with env_id_base =
-cfg.env_id_base + p Em and the member's own seed, epsilon, discount and learning rate (tests/test_gpu_population.py): the
+Member p is, bit for bit, the single agent run alone on a handle of its Em environments created with env_id_base =
+cfg.env_id_base + p Em and the member's own seed, epsilon, discount and learning rate (tests/population_harness.py): the
 kernels are the single agent's stages with the member taken from the grid, and every draw of the agents' loop is keyed
-on (seed, global environment id, step).
+on (seed, global environment id, step).  The per-member hyper-parameters are host values that travel in the kernels'
+arguments (`_Geometry.spec`): a changed epsilon costs no device copy.
 
-`PopulationExploreAgent` is the same for P ExploreAgents, the curriculum's first stage (antsrl_popexplore.hip; DESIGN
-§7.25): `PopulationExploreTrainer` holds ExploreTrainer's flat blocks with a leading [P], a step is two launches whatever P
-is, and `PopulationAgent.setup(env, explore_population=pop_e)` puts member p's layer1 and layer2 under member p's collect
-heads, device to device (driver.train_population_curriculum runs both stages on one handle).
+The four populations, each an agent over a trainer:
 
-`PopulationJointAgent` is the same for P CollectAgent(train_layer1=True)s, the curriculum's third stage
-(antsrl_popjoint.hip): `PopulationJointTrainer` holds JointTrainer's flat blocks with a leading [P] and a
-target layer3 [P, 99], a step is two launches whatever P is, and `PopulationJointAgent.setup(env, collect_population=pop_c)`
-takes member p's six tensors from member p of the second stage, device to device (driver.train_population_curriculum
-runs all three stages on one handle when it is given a `joint_pop`).
+    PopulationAgent         PopulationLinearTrainer    P CollectAgents, the curriculum's second stage; layer1 frozen
+                                                       (antsrl_population.hip; §7.24): one training launch
+    PopulationExploreAgent  PopulationExploreTrainer   P ExploreAgents, the first stage; rotation only, the acting net the
+                                                       TARGET block (antsrl_popexplore.hip; §7.25): two launches
+    PopulationJointAgent    PopulationJointTrainer     P CollectAgent(train_layer1=True)s, the third stage; the acting net
+                                                       the LIVE block and the target layer3 (antsrl_popjoint.hip; §7.28): two
+    PopulationMemoryAgent   PopulationMemoryTrainer    P MemoryAgents, the agent main.py trains; the acting net the target's
+                                                       bf16 pack, the memory carried in the ring's rows behind the agent
+                                                       state (antsrl_popmemtrain.hip, antsrl_popmemnet.hip; §7.29, §7.30): 17
 
-The pieces mirror the single agent's: `PopulationLinearTrainer` (LinearTrainer's tensors with a leading [P]),
-`PopulationReplayMemory` (DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
-record the same number of rows at every step) and `PopulationAgent` (CollectAgent's surface, per member where the
-reference's has one model).  The two trainers are one `_PopulationTrainer` (the members' host values, Adam's scalars, the
-counters, `running_loss`, `train` and `step`, whose call hands both entries the same nineteen arguments behind the net's
-pointers) under each net's tensors, dicts and entry, as the two agents are one `_Population`.  The per-member hyper-parameters are host values that travel in the kernels' arguments: a
-changed epsilon costs no device copy.
+The stages hand over device to device: `PopulationAgent.setup(env, explore_population=pop_e)`,
+`PopulationJointAgent.setup(env, collect_population=pop_c)` (driver.train_population_curriculum runs them on one handle).
 
-`PopulationMemoryTrainer` is the training step of P memory nets (MemoryTrainer's, the net main.py drives) in the 17
-launches of one (antsrl_popmemtrain.hip): a member's state buffer is MemoryTrainer's, member p bit for bit
-a MemoryTrainer stepped alone on its slab.  Its ring is a PopulationReplayMemory built with agent_states_space =
-(2 + mem_size,).
+What is stated once:
 
-`PopulationMemoryAgent` is the same for P MemoryAgents, the agent main.py trains (antsrl_popmemnet.hip):
-every member's target net acts from its own bf16 pack (`PopulationMemoryTrainer.packed`) in one launch, select gives the
-ants of a member's exploring environments their old memory back, and the ring's rows carry the memory behind the agent
-state.  Member p is, bit for bit, a MemoryAgent run alone on a handle of its environments.
+    PopulationReplayMemory  DeviceReplayMemory's seven arrays with a leading [P]; head and fill are shared, the members
+                            record the same number of rows at every step.  One call site per record half, with or without
+                            a memory.
+    _PopulationTrainer      the members' host values, Adam's scalars, the counters, `running_loss`, `train`, `step` (whose
+                            call hands every entry the same nineteen arguments behind the net's pointers) and `workspace`.
+                            A trainer holds its net's tensors, dicts and loads and names its entry (`_entry`).
+    _PopulationFlatTrainer  under the explore and the joint trainer, train._FlatTrainer's counterpart: a member's net is
+                            one flat block; the name table, `_sizes`, `_views`, `adam_state`, Adam's tensor, `grads`, `_entry`.
+    _Population             the members' host values, the front of setup, the step's one AntsPopSpec, `get_action`, the
+                            ring, train, the fused loop, the per-member files and `copy_member`.  An agent names its
+                            trainer class and launches its acting net (`_policy`); the memory agent also has its own
+                            select and hands its new memory out behind the actions.
 
 Out of scope: the memory agents' explore plan and tile-list forward (skip_explored) and their fp32 acting precision; the
 rework agent's net; in-loop acting (a handle holds one policy pack), B > 512 for the
@@ -72,6 +74,11 @@ def _members(members: Sequence[dict]) -> list:
         assert not extra, "a member is dict(epsilon=, discount=, learning_rate=, seed=), not %s" % sorted(extra)
         out.append(dict(MEMBER_DEFAULTS, **m))
     return out
+
+
+def _rows(p: Optional[int]) -> slice:
+    """Member p, or every member (None): the rows of a [P, ...] tensor, and range(P)[rows] the members themselves."""
+    return slice(None) if p is None else slice(p, p + 1 or None)
 
 
 class _Geometry:
@@ -138,44 +145,34 @@ class PopulationReplayMemory(_Ring):
         assert memory is not None and memory.dtype == torch.float32 and memory.is_contiguous() and \
             memory.shape[-1] == self.mem_size, "memory: float32 [M, %d]" % self.mem_size
 
+    def _record(self, half: str, pending: tuple, obs, agent_state, memory, rest: tuple) -> None:
+        """antsrl_pop_record_<half> on (spec, step, k, shape) = pending: the step's rows, then `rest` (the half's other
+        inputs and the ring's arrays it writes).  A ring with a memory puts the shape behind the spec and the memory
+        behind the agent state, and calls antsrl_pop_memory_record_<half>."""
+        spec, step, k, shape = pending
+        self._memory(memory, shape)
+        name = ("pop_memory_record_" if self.mem_size else "pop_record_") + half
+        lead, mem = ((C.byref(spec), C.byref(shape)), (_p(memory),)) if self.mem_size else ((C.byref(spec),), ())
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.load(), "antsrl_" + name)(*lead, step, k, self.head, self.max_len, _p(obs), _p(agent_state),
+                                                              *mem, *map(_p, rest), _lib.stream(self.device)), name)
+
     def record_pre(self, obs, agent_state, memory, rotation, pheromone, *, spec, step: int, k: int, shape=None) -> None:
         """Before the environment step: states, agent_states and actions of k of every member's transitions."""
         assert self._pending is None, "record_pre twice without record_post"
-        self._memory(memory, shape)
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            if self.mem_size:
-                _lib.check(lib.antsrl_pop_memory_record_pre(C.byref(spec), C.byref(shape), step, k, self.head, self.max_len,
-                                                            _p(obs), _p(agent_state), _p(memory), _p(rotation), _p(pheromone),
-                                                            _p(self.states), _p(self.agent_states), _p(self.actions),
-                                                            _lib.stream(self.device)), "pop_memory_record_pre")
-            else:
-                _lib.check(lib.antsrl_pop_record_pre(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
-                                                     _p(rotation), _p(pheromone), _p(self.states), _p(self.agent_states),
-                                                     _p(self.actions), _lib.stream(self.device)), "pop_record_pre")
+        self._record("pre", (spec, step, k, shape), obs, agent_state, memory,
+                     (rotation, pheromone, self.states, self.agent_states, self.actions))
         self._pending = (spec, step, k, shape)
 
     def record_post(self, obs, agent_state, memory, reward, done) -> None:
         """After it: rewards, new_states, new_agent_states and dones of the same transitions; then head and fill advance
         as DeviceReplayMemory's do for k rows."""
         assert self._pending is not None, "record_post without record_pre"
-        spec, step, k, shape = self._pending
-        self._memory(memory, shape)
         if done.dtype == torch.bool:
             done = done.view(torch.uint8)
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            if self.mem_size:
-                _lib.check(lib.antsrl_pop_memory_record_post(C.byref(spec), C.byref(shape), step, k, self.head, self.max_len,
-                                                             _p(obs), _p(agent_state), _p(memory), _p(reward), _p(done),
-                                                             _p(self.rewards), _p(self.new_states), _p(self.new_agent_states),
-                                                             _p(self.dones.view(torch.uint8)), _lib.stream(self.device)),
-                           "pop_memory_record_post")
-            else:
-                _lib.check(lib.antsrl_pop_record_post(C.byref(spec), step, k, self.head, self.max_len, _p(obs), _p(agent_state),
-                                                      _p(reward), _p(done), _p(self.rewards), _p(self.new_states),
-                                                      _p(self.new_agent_states), _p(self.dones.view(torch.uint8)),
-                                                      _lib.stream(self.device)), "pop_record_post")
+        self._record("post", self._pending, obs, agent_state, memory,
+                     (reward, done, self.rewards, self.new_states, self.new_agent_states, self.dones.view(torch.uint8)))
+        k = self._pending[2]
         self._pending = None
         self._advance(k)
 
@@ -183,9 +180,9 @@ class PopulationReplayMemory(_Ring):
 class _PopulationTrainer(_TargetCounter):
     """What the population trainers share.  Per member: seed, discount and learning rate.  Common: Adam's betas, eps
     and step count, update_target_every and the target counter.  `running_loss` (float64 [P]) is main.py:106-109's
-    running loss per member, kept by the training step's last launch from the first training step on.  `_spec`, `train`
-    and `step` are here; a subclass allocates its tensors (`grads` among them), holds the dict and load methods of its
-    net and names its entry (`_entry`)."""
+    running loss per member, kept by the training step's last launch from the first training step on.  `_spec`, `train`,
+    `step` and `workspace` are here; a subclass allocates its tensors (`grads` among them), holds the dict and load
+    methods of its net, names its entry (`_entry`) and says how large the step's workspace is (`_workspace_bytes`)."""
 
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas, eps: float, update_target_every: int):
         self.g, self.device = geometry, torch.device(device)
@@ -196,16 +193,29 @@ class _PopulationTrainer(_TargetCounter):
         self.target_update_counter = self.syncs = self.step_count = 0
         self.running_loss = torch.zeros((self.n_members,), dtype=torch.float64, device=self.device)
         self.last_idx = None  # the [P, B] indices of the last step
+        self._work, self._work_B = None, 0
         self._lib = _lib.load()
 
     def _spec(self):
         """The spec of a step driven without an agent (epsilon 0: the training entry reads none)."""
         return self.g.spec(self.seeds, np.zeros(self.n_members), self.lr, self.discount)
 
-    def _entry(self, B: int) -> tuple:
-        """(the training entry, its name in an error, the net's pointers that lead its arguments, what follows
-        first_loss) for a step on B rows per member."""
+    def _entry(self) -> tuple:
+        """(the training entry, its name in an error, the net's pointers that lead its arguments)."""
         raise NotImplementedError
+
+    def _workspace_bytes(self, B: int) -> Optional[int]:
+        """The bytes of the step's workspace for B rows per member (the entry's _sizes says); None: the step has none."""
+        raise NotImplementedError
+
+    def workspace(self, B: int) -> Optional[torch.Tensor]:
+        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in),
+        allocated when B changes and handed to the entry behind first_loss; None for a step without one."""
+        if self._work_B != B:
+            n = self._workspace_bytes(B)
+            self._work = None if n is None else torch.empty((n,), dtype=torch.uint8, device=self.device)
+            self._work_B = B
+        return self._work
 
     def step(self, ring: PopulationReplayMemory, idx: torch.Tensor, spec=None, loss: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One training step of every member on its rows idx[p] (int64 [P, B] on the device, values in [0, fill)) of its
@@ -217,7 +227,9 @@ class _PopulationTrainer(_TargetCounter):
         if loss is None:
             loss = torch.empty((P,), dtype=torch.float32, device=self.device)
         assert loss.device == self.device and loss.dtype == torch.float32 and loss.shape == (P,) and loss.is_contiguous()
-        entry, who, net, tail = self._entry(idx.shape[1])
+        entry, who, net = self._entry()
+        work = self.workspace(idx.shape[1])
+        tail = () if work is None else (_p(work),)
         first = self.step_count == 0
         self.step_count += 1
         with torch.cuda.device(self.device):
@@ -272,13 +284,13 @@ class PopulationLinearTrainer(_PopulationTrainer):
 
     def _load(self, sd, p: Optional[int], names) -> None:
         sd = collect_names(sd)
-        for q in (range(self.n_members) if p is None else (p,)):
+        for q in range(self.n_members)[_rows(p)]:
             copy_named(sd, self._model_views(q), names)
 
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
         """LinearTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
         self._load(sd, p, LINEAR_NAMES)
-        rows = slice(None) if p is None else p
+        rows = _rows(p)
         self.target_l3[rows].copy_(self.heads[rows, 99:198])
 
     def load_explore_state_dict(self, sd, p: Optional[int] = None) -> None:
@@ -292,10 +304,7 @@ class PopulationLinearTrainer(_PopulationTrainer):
         three device copies of [P, ...].  layer3, its target copy and Adam's state stay, as load_explore_state_dict
         leaves them."""
         P, n1 = self.n_members, 32 * (self.n_features + 2)
-        if explore_trainer.n_members != P:
-            raise ValueError("the explore population has %d members, this one %d" % (explore_trainer.n_members, P))
-        if explore_trainer.n_features != self.n_features:
-            raise ValueError("the explore population's rows have %d features, these %d" % (explore_trainer.n_features, self.n_features))
+        _same_population(self, explore_trainer, "explore")
         m = explore_trainer.model.to(self.device)
         self.w1.view(P, n1).copy_(m[:, :n1])
         self.b1.copy_(m[:, n1:n1 + 32])
@@ -309,13 +318,74 @@ class PopulationLinearTrainer(_PopulationTrainer):
         self.target_l3.copy_(self.heads[:, 99:198])
         self.syncs += 1
 
-    def _entry(self, B: int) -> tuple:
-        """One launch; no workspace."""
+    def _entry(self) -> tuple:
+        """One launch."""
         return (self._lib.antsrl_pop_lintrain_step, "pop_lintrain_step",
-                (_p(self.w1), _p(self.b1), _p(self.heads), _p(self.target_l3), _p(self._adam)), ())
+                (_p(self.w1), _p(self.b1), _p(self.heads), _p(self.target_l3), _p(self._adam)))
+
+    def _workspace_bytes(self, B: int) -> None:
+        """The one launch keeps a member's minibatch in its workgroup: no workspace."""
+        return None
 
 
-class PopulationExploreTrainer(_PopulationTrainer):
+class _PopulationFlatTrainer(_PopulationTrainer):
+    """What the explore and the joint population trainer share, train._FlatTrainer's counterpart for a population: a
+    member's net is ONE flat block described by `_offs` (name -> (offset, shape)); `model`, `_adam[0]`, `_adam[1]` and
+    grads are [P, trained_floats]; the entries are antsrl_pop_<entry>_sizes / _step and take (model, the target, Adam's m,
+    Adam's v) in front of the ring's arrays.  A subclass names its `entry` and the tensor that is its `target_name`, lists
+    its layers (`_alloc_flat`), allocates its target and writes sync_target and its loads."""
+
+    entry = None  # "exptrain", "jointtrain"
+    target_name = None  # the attribute the step entry takes behind `model`
+
+    def _alloc_flat(self, names: Sequence[str], layers: dict) -> None:
+        """The table of a block whose tensors are `names` in order, a weight and a bias per layer of `layers` (name ->
+        (out, in), a block's order); `model`, member p's drawn as the single trainer's by linear_init(layers, seed_p);
+        Adam's moments and the gradients, zeroed."""
+        P = self.n_members
+        self._offs, off = {}, 0
+        for k, shp in zip(names, (s for out_f, in_f in layers.values() for s in ((out_f, in_f), (out_f,)))):
+            self._offs[k] = (off, shp)
+            off += math.prod(shp)
+        self._step_name = "pop_%s_step" % self.entry
+        self._step = getattr(self._lib, "antsrl_" + self._step_name)
+        self.trained_floats = self._sizes(1)[0]
+        assert self.trained_floats == off
+        self.model = torch.stack([torch.cat([t.reshape(-1) for t in linear_init(layers, s).values()])
+                                  for s in self.seeds]).to(self.device).contiguous()
+        self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
+
+    def _sizes(self, B: int) -> tuple:
+        """antsrl_pop_<entry>_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches)."""
+        name = "pop_%s_sizes" % self.entry
+        tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+        _lib.check(getattr(self._lib, "antsrl_" + name)(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
+                                                        C.byref(ws), C.byref(n)), name)
+        return tf.value, stride.value, ws.value, n.value
+
+    def _workspace_bytes(self, B: int) -> int:
+        return self._sizes(B)[2]
+
+    def _views(self, flat) -> dict:
+        """The tensors of one member's flat block (views) under the reference's names, in its order."""
+        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
+
+    def state_dict(self, p: int) -> dict:
+        """Member p's tensors (copies) under the reference's names, in its order: what the single agent saves and loads."""
+        return _clones(self._views(self.model[p]))
+
+    def adam_state(self, p: int) -> dict:
+        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0, p])),
+                    exp_avg_sq=_clones(self._views(self._adam[1, p])))
+
+    def _entry(self) -> tuple:
+        """Two launches."""
+        return (self._step, self._step_name,
+                (_p(self.model), _p(getattr(self, self.target_name)), _p(self._adam[0]), _p(self._adam[1])))
+
+
+class PopulationExploreTrainer(_PopulationFlatTrainer):
     """ExploreTrainer's tensors with a leading [P], trained by antsrl_pop_exptrain_step: two launches whatever P is.
     model, target, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat block is ExploreTrainer's:
     layer1.weight, layer1.bias, layer2.weight, layer2.bias); member p's weights are initialised as
@@ -323,69 +393,30 @@ class PopulationExploreTrainer(_PopulationTrainer):
     discount and learning rate.  Common: Adam's betas, eps and step count, update_target_every and the target counter.
     `running_loss` (float64 [P]) is kept by the step's second launch from the first training step on."""
 
+    entry, target_name = "exptrain", "target"
+
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
                  update_target_every: int = 1):
         super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
-        P, IN = self.n_members, self.n_features + 2
-        self._offs = {"layer1.weight": (0, (32, IN)), "layer1.bias": (32 * IN, (32,)),
-                      "layer2.weight": (32 * IN + 32, (3, 32)), "layer2.bias": (32 * IN + 128, (3,))}
-        self.trained_floats = self._sizes(1)[0]
+        IN = self.n_features + 2
+        self._alloc_flat(EXPLORE_NAMES, dict(layer1=(32, IN), layer2=(3, 32)))
         assert self.trained_floats == 32 * IN + 131
-        sds = [linear_init(dict(layer1=(32, IN), layer2=(3, 32)), s) for s in self.seeds]
-        self.model = torch.stack([torch.cat([sd[k].reshape(-1) for k in EXPLORE_NAMES]) for sd in sds]).to(self.device).contiguous()
         self.target = self.model.clone()
-        self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self._work, self._work_B = None, 0
-
-    def _sizes(self, B: int) -> tuple:
-        """antsrl_pop_exptrain_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches)."""
-        tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
-        _lib.check(self._lib.antsrl_pop_exptrain_sizes(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
-                                                       C.byref(ws), C.byref(n)), "pop_exptrain_sizes")
-        return tf.value, stride.value, ws.value, n.value
-
-    # ---- weights ------------------------------------------------------------------------------------------------------
-    def _views(self, flat) -> dict:
-        """The four tensors of one member's flat block (views) under ExploreModel's names, in its order."""
-        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
-
-    def state_dict(self, p: int) -> dict:
-        """Member p's four tensors (copies) under ExploreModel's names: what ExploreAgent.save_model writes."""
-        return _clones(self._views(self.model[p]))
 
     def target_state_dict(self, p: int) -> dict:
         return _clones(self._views(self.target[p]))
 
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
         """ExploreTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
-        sd = explore_names(sd)
-        for q in (range(self.n_members) if p is None else (p,)):
+        sd, rows = explore_names(sd), _rows(p)
+        for q in range(self.n_members)[rows]:
             copy_named(sd, self._views(self.model[q]))
-        rows = slice(None) if p is None else p
         self.target[rows].copy_(self.model[rows])
-
-    def adam_state(self, p: int) -> dict:
-        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0, p])),
-                    exp_avg_sq=_clones(self._views(self._adam[1, p])))
 
     def sync_target(self) -> None:
         """target := model for every member: one copy of [P, trained_floats]."""
         self.target.copy_(self.model)
         self.syncs += 1
-
-    # ---- the step -----------------------------------------------------------------------------------------------------
-    def workspace(self, B: int) -> torch.Tensor:
-        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
-        if self._work is None or self._work_B != B:
-            self._work = torch.empty((self._sizes(B)[2],), dtype=torch.uint8, device=self.device)
-            self._work_B = B
-        return self._work
-
-    def _entry(self, B: int) -> tuple:
-        """Two launches; behind first_loss goes the workspace for B rows per member."""
-        return (self._lib.antsrl_pop_exptrain_step, "pop_exptrain_step",
-                (_p(self.model), _p(self.target), _p(self._adam[0]), _p(self._adam[1])), (_p(self.workspace(B)),))
 
     def train(self, ring: PopulationReplayMemory, done: bool, generator: Optional[torch.Generator] = None, minibatch: int = 256,
               min_replay: int = 1000, spec=None):
@@ -393,7 +424,7 @@ class PopulationExploreTrainer(_PopulationTrainer):
         return super().train(ring, done, generator, minibatch, min_replay, spec)
 
 
-class PopulationJointTrainer(_PopulationTrainer):
+class PopulationJointTrainer(_PopulationFlatTrainer):
     """JointTrainer's tensors with a leading [P], trained by antsrl_pop_jointtrain_step: two launches whatever P is.
     model, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat block is JointTrainer's: the six
     tensors in CollectModel.state_dict()'s order), target_l3 is [P, 99]; member p's weights are initialised as
@@ -402,53 +433,30 @@ class PopulationJointTrainer(_PopulationTrainer):
     update_target_every and the target counter.  `running_loss` (float64 [P]) is kept by the step's second launch from
     the first training step on."""
 
+    entry, target_name = "jointtrain", "target_l3"
+
     def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
                  update_target_every: int = 1):
         super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
-        P, IN = self.n_members, self.n_features + 2
-        self._offs, off = {}, 0
-        for k, shp in zip(LINEAR_NAMES, ((32, IN), (32,), (3, 32), (3,), (3, 32), (3,))):
-            self._offs[k] = (off, shp)
-            off += math.prod(shp)
-        self.trained_floats = self._sizes(1)[0]
-        assert self.trained_floats == off == 32 * IN + 230
+        IN = self.n_features + 2
+        self._alloc_flat(LINEAR_NAMES, dict(layer1=(32, IN), layer2=(3, 32), layer3=(3, 32)))
+        off = self.trained_floats
+        assert off == 32 * IN + 230
         self._l3 = slice(off - 99, off)  # layer3 in a block: the 99 floats the target copies
-        sds = [linear_init(dict(layer1=(32, IN), layer2=(3, 32), layer3=(3, 32)), s) for s in self.seeds]
-        names = ("layer1.weight", "layer1.bias", "layer2.weight", "layer2.bias", "layer3.weight", "layer3.bias")
-        self.model = torch.stack([torch.cat([sd[k].reshape(-1) for k in names]) for sd in sds]).to(self.device).contiguous()
         self.target_l3 = self.model[:, self._l3].clone()
-        self._adam = torch.zeros((2, P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self._work, self._work_B = None, 0
-
-    def _sizes(self, B: int) -> tuple:
-        """antsrl_pop_jointtrain_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches)."""
-        tf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
-        _lib.check(self._lib.antsrl_pop_jointtrain_sizes(self.n_features, B, self.n_members, C.byref(tf), C.byref(stride),
-                                                         C.byref(ws), C.byref(n)), "pop_jointtrain_sizes")
-        return tf.value, stride.value, ws.value, n.value
-
-    # ---- weights ------------------------------------------------------------------------------------------------------
-    def _views(self, flat) -> dict:
-        """The six tensors of one member's flat block (views) under CollectModel's names, in its order."""
-        return {k: flat[o: o + math.prod(shp)].view(shp) for k, (o, shp) in self._offs.items()}
-
-    def state_dict(self, p: int) -> dict:
-        """Member p's six tensors (copies) under CollectModel's names, in its order: what the reference loads."""
-        return _clones(self._views(self.model[p]))
 
     def target_state_dict(self, p: int) -> dict:
         return linear_target_state_dict(self.state_dict(p), self.target_l3[p])
 
     def _load(self, sd, p: Optional[int], names) -> None:
         sd = collect_names(sd)
-        for q in (range(self.n_members) if p is None else (p,)):
+        for q in range(self.n_members)[_rows(p)]:
             copy_named(sd, self._views(self.model[q]), names)
 
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
         """JointTrainer.load_state_dict for member p (None: every member): model AND target; Adam's state is kept."""
         self._load(sd, p, LINEAR_NAMES)
-        rows = slice(None) if p is None else p
+        rows = _rows(p)
         self.target_l3[rows].copy_(self.model[rows, self._l3])
 
     def load_explore_state_dict(self, sd, p: Optional[int] = None) -> None:
@@ -474,27 +482,10 @@ class PopulationJointTrainer(_PopulationTrainer):
         self.model[:, n1 + 32:].copy_(linear_trainer.heads.to(self.device))
         self.target_l3.copy_(self.model[:, self._l3])
 
-    def adam_state(self, p: int) -> dict:
-        return dict(step=self.step_count, exp_avg=_clones(self._views(self._adam[0, p])),
-                    exp_avg_sq=_clones(self._views(self._adam[1, p])))
-
     def sync_target(self) -> None:
         """target := model for every member: one copy of [P, 99]."""
         self.target_l3.copy_(self.model[:, self._l3])
         self.syncs += 1
-
-    # ---- the step -----------------------------------------------------------------------------------------------------
-    def workspace(self, B: int) -> torch.Tensor:
-        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
-        if self._work is None or self._work_B != B:
-            self._work = torch.empty((self._sizes(B)[2],), dtype=torch.uint8, device=self.device)
-            self._work_B = B
-        return self._work
-
-    def _entry(self, B: int) -> tuple:
-        """Two launches; behind first_loss goes the workspace for B rows per member."""
-        return (self._lib.antsrl_pop_jointtrain_step, "pop_jointtrain_step",
-                (_p(self.model), _p(self.target_l3), _p(self._adam[0]), _p(self._adam[1])), (_p(self.workspace(B)),))
 
 
 class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
@@ -520,7 +511,6 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         self._model = torch.empty((P, self.state_stride), dtype=torch.uint8, device=self.device)
         self._target = torch.empty_like(self._model)
         self.grads = torch.zeros((P, self.trained_floats), dtype=torch.float32, device=self.device)
-        self._work, self._work_B = None, 0
         shapes = memnet_param_shapes(F, power, mem_size, n_rot, n_ph)
         for p, seed in enumerate(self.seeds):
             self._init_state(linear_init(shapes, seed), (self._model[p], self._target[p]))
@@ -536,7 +526,7 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         """MemoryTrainer._repack_policy for member p (None: every member): its block of `packed` := its target net,
         antsrl_memnet_pack_ex in bf16 straight from the target's masters."""
         with torch.cuda.device(self.device):
-            for q in (range(self.n_members) if p is None else (p,)):
+            for q in range(self.n_members)[_rows(p)]:
                 ptrs = memnet_param_ptrs(self._views(self._target[q]))
                 _lib.check(self._lib.antsrl_memnet_pack_ex(C.byref(self.shape), MEMNET_PRECISIONS["bf16"], ptrs,
                                                            _p(self.packed[q]), _lib.stream(self.device)), "memnet_pack_ex")
@@ -560,7 +550,7 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
     def load_state_dict(self, sd, p: Optional[int] = None) -> None:
         """MemoryTrainer.load_state_dict for member p (None: every member): model AND target (and the acting pack);
         Adam's state is kept."""
-        for q in (range(self.n_members) if p is None else (p,)):
+        for q in range(self.n_members)[_rows(p)]:
             keep = self._model[q, self._adam_range()].clone()
             self._init_state(sd, (self._model[q], self._target[q]))
             self._model[q, self._adam_range()] = keep
@@ -580,17 +570,12 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         self.syncs += 1
 
     # ---- the step -----------------------------------------------------------------------------------------------------
-    def workspace(self, B: int) -> torch.Tensor:
-        """The step's workspace for B rows per member (uint8, 256-byte aligned; member p's part starts p strides in)."""
-        if self._work is None or self._work_B != B:
-            self._work = torch.empty((self._sizes(B)[3],), dtype=torch.uint8, device=self.device)
-            self._work_B = B
-        return self._work
+    def _workspace_bytes(self, B: int) -> int:
+        return self._sizes(B)[3]
 
-    def _entry(self, B: int) -> tuple:
-        """17 launches; the shape leads the net's pointers, behind first_loss goes the workspace for B rows per member."""
-        return (self._lib.antsrl_pop_memtrain_step, "pop_memtrain_step",
-                (C.byref(self.shape), _p(self._model), _p(self._target)), (_p(self.workspace(B)),))
+    def _entry(self) -> tuple:
+        """17 launches; the shape leads the net's pointers."""
+        return (self._lib.antsrl_pop_memtrain_step, "pop_memtrain_step", (C.byref(self.shape), _p(self._model), _p(self._target)))
 
 
 def _same_population(trainer, other, kind: str) -> None:
@@ -603,12 +588,15 @@ def _same_population(trainer, other, kind: str) -> None:
 
 
 class _Population(_LoopAgent):
-    """What the two populations share around their nets: the members' host values, the front of setup, the step's one
-    AntsPopSpec, select, the ring, train, the fused loop and the per-member files.  A subclass names its `minibatch`
-    default in its __init__, builds its trainer (`_make_trainer`), launches its acting net (`_policy`), says whether the
-    net has a pheromone head (`pheromones`) and lists the per-member tensors of its trainer (`_member_tensors`)."""
+    """What the populations share around their nets: the members' host values, the front of setup, the step's one
+    AntsPopSpec, get_action, the ring, train, the fused loop, the per-member files and copy_member.  A subclass names
+    its `minibatch` default in its __init__ and its trainer's class (`trainer_cls`), launches its acting net (`_policy`),
+    says whether the net has a pheromone head (`pheromones`) and lists the per-member tensors of its trainer
+    (`_member_tensors`); one whose net carries a memory has a select of its own (`_select`) and hands more than the
+    actions out of get_action (`_acted`)."""
 
     rotations = 3
+    trainer_cls = None
 
     def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int], replay_size: int, minibatch: int,
                  min_replay: int, update_target_every: int, seed: int):
@@ -631,8 +619,8 @@ class _Population(_LoopAgent):
     def epsilon(self, v) -> None:
         self._epsilon = np.broadcast_to(np.asarray(v, dtype=np.float64), (self.n_members,)).copy()
 
-    def _setup(self, api_or_env, trainer_cls, trainer_kw: Optional[dict] = None, agent_states_space: Sequence[int] = (2,)):
-        """The front of setup: the geometry, the trainer (trainer_kw: what its net takes by name beyond the common
+    def _setup(self, api_or_env, trainer_kw: Optional[dict] = None, agent_states_space: Sequence[int] = (2,)):
+        """The front of setup: the geometry, the trainer (a `trainer_cls`; trainer_kw: what its net takes by name beyond the common
         arguments), the ring (agent_states_space: the width of its agent_states rows), the action buffers, the generator
         and the counters."""
         env = _backend(api_or_env)
@@ -644,9 +632,9 @@ class _Population(_LoopAgent):
         if self.record_per_step is not None and not 1 <= self.record_per_step <= self.g.Mm:
             raise ValueError("record_per_step = %d is not in [1, %d], a member's ants" % (self.record_per_step, self.g.Mm))
         self.seeds = [m["seed"] for m in self.members]
-        self.trainer = trainer_cls(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
-                                   [m["learning_rate"] for m in self.members], update_target_every=self.update_target_every,
-                                   **(trainer_kw or {}))
+        self.trainer = self.trainer_cls(self.g, self.device, self.seeds, [m["discount"] for m in self.members],
+                                        [m["learning_rate"] for m in self.members], update_target_every=self.update_target_every,
+                                        **(trainer_kw or {}))
         self.replay_memory = PopulationReplayMemory(self.n_members, self.replay_size, self.observation_space, device=self.device,
                                                     agent_states_space=agent_states_space)
         M = cfg.n_envs * cfg.n_ants
@@ -670,10 +658,20 @@ class _Population(_LoopAgent):
         """The acting net of every member into `_rot` (and `_ph`, with a pheromone head)."""
         raise NotImplementedError
 
+    def _select(self, spec, step: int, st) -> None:
+        """antsrl_pop_select on `_rot` / `_ph`: the environments that explore at (a member's seed, step) take uniform
+        actions."""
+        _lib.check(self._lib.antsrl_pop_select(C.byref(spec), step, _p(self._rot), _p(self._ph), _p(self._explored), st), "pop_select")
+
+    def _acted(self, lead) -> tuple:
+        """What get_action returns once the step's launches are enqueued: the actions, shaped like the batch."""
+        return self._rot.view(lead), (self._ph.view(lead) if self.pheromones else None)
+
     def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
-        """-> (rotation int8, pheromone int8 or None for a net without that head), device tensors shaped like the batch:
-        every member's acting net on its own rows; with `training`, antsrl_pop_select then replaces the actions of the
-        environments that explore this step, each member with its own seed and epsilon."""
+        """-> (rotation int8, pheromone int8 or None for a net without that head[, the new memory of a net that carries
+        one]), device tensors shaped like the batch: every member's acting net on its own rows (`_policy`); with
+        `training`, `_select` then replaces the actions of the environments that explore this step, each member with its
+        own seed and epsilon."""
         assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
             "a population reads the dense observation rows of its whole batch"
         assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
@@ -683,11 +681,10 @@ class _Population(_LoopAgent):
             st = _lib.stream(self.device)
             self._policy(spec, obs, agent_state, st)
             if training:
-                _lib.check(self._lib.antsrl_pop_select(C.byref(spec), step, _p(self._rot), _p(self._ph), _p(self._explored), st),
-                           "pop_select")
+                self._select(spec, step, st)
         self._action_step = step
         self.step_counter += 1
-        return self._rot.view(lead), (self._ph.view(lead) if self.pheromones else None)
+        return self._acted(lead)
 
     def train(self, done: bool, step: int = 0, spec=None):
         """0 below min_replay, else the losses of one step of every member, float32 [P] on the device."""
@@ -740,6 +737,7 @@ class PopulationAgent(_Population):
 
     name = "collect_agent_population"
     pheromones = 3
+    trainer_cls = PopulationLinearTrainer
 
     def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 264, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
@@ -750,8 +748,8 @@ class PopulationAgent(_Population):
               explore_population=None) -> None:
         """CollectAgent.setup for every member; trained_model / explore_model go to every member.  explore_population: a
         PopulationExploreAgent of as many members, the curriculum's first stage: member p's layer1 and layer2 come from
-        its member p's model, device to device (PopulationLinearTrainer.load_explore_population); applied last."""
-        self._setup(api_or_env, PopulationLinearTrainer)
+        its member p's model, device to device (the trainer's load_explore_population); applied last."""
+        self._setup(api_or_env)
         if trained_model is not None:
             self.load_model(trained_model)
         if explore_model is not None:
@@ -778,19 +776,14 @@ class PopulationJointAgent(PopulationAgent):
     setup(env, collect_population=that)."""
 
     name = "joint_agent_population"
+    trainer_cls = PopulationJointTrainer
 
     def setup(self, api_or_env, trained_model: Optional[str] = None, explore_model: Optional[str] = None,
               explore_population=None, collect_population=None) -> None:
         """PopulationAgent.setup with all six tensors trained.  collect_population: a PopulationAgent of as many members,
         the curriculum's second stage: member p's six tensors come from its member p, device to device
         (PopulationJointTrainer.load_collect_population); applied last."""
-        self._setup(api_or_env, PopulationJointTrainer)
-        if trained_model is not None:
-            self.load_model(trained_model)
-        if explore_model is not None:
-            self.trainer.load_explore_state_dict(torch.load(explore_model, map_location="cpu"))
-        if explore_population is not None:
-            self.trainer.load_explore_population(explore_population.trainer)
+        super().setup(api_or_env, trained_model, explore_model, explore_population)
         if collect_population is not None:
             self.trainer.load_collect_population(collect_population.trainer)
 
@@ -813,6 +806,7 @@ class PopulationExploreAgent(_Population):
 
     name = "explore_agent_population"
     pheromones = 0  # no pheromone head (antsrl_pop_select still draws a pheromone for every exploring ant: nothing reads it)
+    trainer_cls = PopulationExploreTrainer
 
     def __init__(self, members: Sequence[dict], *, record_per_step: Optional[int] = None, replay_size: int = 50000,
                  minibatch: int = 256, min_replay: int = 1000, update_target_every: int = 1, seed: int = 0):
@@ -821,7 +815,7 @@ class PopulationExploreAgent(_Population):
 
     def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
         """ExploreAgent.setup for every member; trained_model goes to every member."""
-        self._setup(api_or_env, PopulationExploreTrainer)
+        self._setup(api_or_env)
         if trained_model is not None:
             self.load_model(trained_model)
 
@@ -852,6 +846,7 @@ class PopulationMemoryAgent(_Population):
 
     name = "collect_agent_memory_population"
     pheromones = 3
+    trainer_cls = PopulationMemoryTrainer
 
     def __init__(self, members: Sequence[dict], *, mem_size: int = 20, power: int = 5, state_memory: str = "reference",
                  record_per_step: Optional[int] = None, replay_size: int = 50000, minibatch: int = 264,
@@ -863,13 +858,13 @@ class PopulationMemoryAgent(_Population):
 
     def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
         """MemoryAgent.setup for every member; trained_model goes to every member."""
-        self._setup(api_or_env, PopulationMemoryTrainer,
-                    dict(power=self.power, mem_size=self.mem_size, n_rot=self.rotations, n_ph=self.pheromones),
+        self._setup(api_or_env, dict(power=self.power, mem_size=self.mem_size, n_rot=self.rotations, n_ph=self.pheromones),
                     agent_states_space=(2 + self.mem_size,))
         M = self._rot.numel()
         self._mem = [torch.zeros((M, self.mem_size), dtype=torch.float32, device=self.device) for _ in range(2)]
         self._cur = 0  # self._mem[self._cur] is previous_memory (collect_agent_memory.py:111), every member's rows
         self._memory_before = self._mem[1]
+        self._halves = None  # (old, new) of the step get_action is in
         if trained_model is not None:
             self.load_model(trained_model)
 
@@ -877,30 +872,25 @@ class PopulationMemoryAgent(_Population):
     def previous_memory(self) -> torch.Tensor:
         return self._mem[self._cur]
 
-    def get_action(self, obs, agent_state, training: bool, env=None, spec=None):
-        """-> (rotation int8, pheromone int8, memory float32 [M, mem_size]), device tensors: every member's target net on
-        its own rows, the new memory into the other half; with `training`, antsrl_pop_memory_select then replaces the
-        actions of the environments that explore this step, each member with its own seed and epsilon, and gives their
-        ants the old memory back."""
-        assert obs.is_contiguous() and agent_state.is_contiguous() and obs.numel() == self._rot.numel() * self.n_features, \
-            "a population reads the dense observation rows of its whole batch"
-        assert (obs.dtype == torch.bfloat16) == (self.g.obs_format == 1), "the observation's dtype changed since setup"
-        step, spec, tr = self.step_counter, self._spec(spec), self.trainer
-        old, new = self._mem[self._cur], self._mem[1 - self._cur]
-        lead = obs.shape[:-3]
-        with torch.cuda.device(self.device):
-            st = _lib.stream(self.device)
-            _lib.check(self._lib.antsrl_pop_policy_memory(C.byref(spec), C.byref(tr.shape), MEMNET_PRECISIONS["bf16"],
-                                                          _p(tr.packed), _p(obs), _p(agent_state), _p(old), _p(new),
-                                                          _p(self._rot), _p(self._ph), None, st), "pop_policy_memory")
-            if training:
-                _lib.check(self._lib.antsrl_pop_memory_select(C.byref(spec), C.byref(tr.shape), step, _p(self._rot),
-                                                              _p(self._ph), _p(old), _p(new), _p(self._explored), st),
-                           "pop_memory_select")
-        self._memory_before = old
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        """Every member's target net on its own rows, the new memory into the other half."""
+        tr = self.trainer
+        old, new = self._halves = self._mem[self._cur], self._mem[1 - self._cur]
+        _lib.check(self._lib.antsrl_pop_policy_memory(C.byref(spec), C.byref(tr.shape), MEMNET_PRECISIONS["bf16"], _p(tr.packed),
+                                                      _p(obs), _p(agent_state), _p(old), _p(new), _p(self._rot), _p(self._ph),
+                                                      None, st), "pop_policy_memory")
+
+    def _select(self, spec, step: int, st) -> None:
+        """antsrl_pop_memory_select: _Population._select, and the ants of the exploring environments get their old memory
+        back."""
+        old, new = self._halves
+        _lib.check(self._lib.antsrl_pop_memory_select(C.byref(spec), C.byref(self.trainer.shape), step, _p(self._rot),
+                                                      _p(self._ph), _p(old), _p(new), _p(self._explored), st), "pop_memory_select")
+
+    def _acted(self, lead) -> tuple:
+        """(rotation int8, pheromone int8, the new memory float32 [M, mem_size]); the two halves swap, as MemoryAgent's do."""
+        self._memory_before, new = self._halves
         self._cur = 1 - self._cur
-        self._action_step = step
-        self.step_counter += 1
         return self._rot.view(lead), self._ph.view(lead), new
 
     def _state_memory(self) -> torch.Tensor:

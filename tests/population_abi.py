@@ -1,6 +1,6 @@
-"""What the CPU-side checks of the two populations' C-ABI entries share (test_population_abi_cpu.py,
-test_population_explore_abi_cpu.py) on top of abi_fakes.py: an AntsPopSpec from keywords, the call of an entry
-from a dict of defaults, and the arguments the two training entries have in common."""
+"""What the CPU-side checks of the populations' C-ABI entries share (test_population_abi_cpu.py, _explore_, _joint_,
+_memory_ and _memory_agent_abi_cpu.py) on top of abi_fakes.py: an AntsPopSpec and the memory net's AntsMemNetShape from
+keywords, the call of an entry from a dict of defaults, and the arguments the training entries have in common."""
 import ctypes as C
 
 from abi_fakes import FAKE
@@ -14,6 +14,16 @@ def spec(**kw):
     for p in range(max(0, min(a["P"], _lib.POP_MAX))):
         s.members[p] = _lib.AntsPopMember(a["seed"], a["eps"], a["lr"], a["discount"], 0)
     return s
+
+
+BF16, FP32 = 0, 1  # include/antsrl.h ANTSRL_MEMNET_BF16 / ANTSRL_MEMNET_FP32
+
+
+def shape(F=294, power=5, mem=20, n_rot=3, n_ph=3, A=2, **kw):
+    """The memory net's shape: the widths follow from `power` unless h1, h2 or h3 is given."""
+    a = dict(h1=2 ** (1 + power), h2=2 ** (2 + power), h3=2 ** (3 + power))
+    a.update(kw)
+    return _lib.AntsMemNetShape(F, A, mem, a["h1"], a["h2"], a["h3"], n_rot, n_ph)
 
 
 def call(entry, s, order, defaults, kw):

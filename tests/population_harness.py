@@ -1,10 +1,12 @@
-"""What the device tests of the two populations share (test_gpu_population.py, test_gpu_population_explore.py): the
-environment a population acts in with the shard handles of its members, a description of each kind (COLLECT:
-PopulationAgent against LinearTrainer; EXPLORE: PopulationExploreAgent against ExploreTrainer and its LinearPolicy without
-a pheromone head) with the two shapes of its acceptance test, and the comparison itself — a population's fused loop
-against every member run ALONE on a shard handle of its own environments, driven entry by entry as
-agent_harness.drive_loop drives an agent; and what the tests of a training step alone share (a synthetic ring, a trainer
-without an agent).  torch is imported inside the functions, as in the GPU test files."""
+"""What the device tests of the four populations share (test_gpu_population.py, _explore.py, _joint.py,
+_memory_agent.py): the environment a population acts in with the shard handles of its members, a description of each
+kind (COLLECT: PopulationAgent against LinearTrainer; EXPLORE: PopulationExploreAgent against ExploreTrainer and its
+LinearPolicy without a pheromone head; MEMORY: PopulationMemoryAgent against MemoryTrainer with the carried memory; the
+joint kind is built in its test file) with the two shapes of its acceptance test, and the comparison itself — a
+population's fused loop against every member run ALONE on a shard handle of its own environments, driven entry by entry
+as agent_harness.drive_loop drives an agent: one loop of each, whatever the net carries; and what the tests of a training
+step alone share (a synthetic ring, a trainer without an agent).  torch is imported inside the functions, as in the GPU
+test files."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -91,18 +93,62 @@ class Kind:
     """One kind of population.  population / single: the names of its agent class (antsrl_amd.population) and of the
     single agent's trainer (antsrl_amd.train); pheromone: whether the net has that head; final: the trainer tensor a
     run's `final` keeps a copy of; tensors(t, p, tr) -> the (name, member p's tensor of the population trainer t, the lone
-    trainer tr's) that same_trainers compares."""
+    trainer tr's) that same_trainers compares.  A kind whose net carries more than the agent state (MemoryKind) overrides
+    the hooks below the constructor; `variant` is what checked_run runs when it is given none."""
 
     make_envs, members_of = staticmethod(make_envs), staticmethod(members_of)
+    variant = None
 
     def __init__(self, population, single, pheromone, final, SHAPES, tensors):
         self.population, self.single, self.pheromone, self.final, self.SHAPES, self.tensors = population, single, pheromone, final, SHAPES, tensors
         self._runs = {}
 
-    def run_population(self, s):
+    # ---- the hooks: a net that carries nothing behind the agent state
+    def population_kw(self, s, variant):
+        """What the population's constructor takes on top of the common arguments."""
+        return {}
+
+    def log_extra(self, pop):
+        """What a step's log entry holds on top of rot, ph, explored, reward, loss and idx (device copies)."""
+        return {}
+
+    def lone(self, s, p, env):
+        """Member p's lone trainer and ring, and the state its loop carries from step to step."""
+        import torch
+        from antsrl_amd import train
+        from antsrl_amd.replay import DeviceReplayMemory
+        tr = getattr(train, self.single)(F, env.device, discount=s["discount"][p], lr=s["lr"][p], update_target_every=1, seed=s["seed"][p])
+        unread = torch.zeros((s["Em"] * s["N"],), dtype=torch.int8, device=env.device)  # without the head, select draws a pheromone that nothing reads
+        return tr, DeviceReplayMemory(s["ring"], (7, 7, 6), [2], [2], device=env.device), SimpleNamespace(unread=unread)
+
+    def lone_act(self, s, p, t, tr, env, st, explored, variant):
+        """Member p's lone act and select at step t -> rot, ph (None without the head), the memory record_pre takes, the
+        one record_post takes, and name -> tensor of what the step's log entry must hold of the member's rows besides."""
+        from antsrl_amd import _lib
+        rot, ph = tr.policy.act(env.obs, env.agent_state, env=env)
+        rot = rot.reshape(-1).clone()
+        if self.pheromone:
+            ph = ph.reshape(-1).clone()
+        else:
+            none = ph
+            assert none is None
+        drawn = ph if self.pheromone else st.unread
+        _lib.check(_lib.load().antsrl_agent_select_actions(s["seed"][p], t, p * s["Em"], s["Em"], s["N"], s["epsilon"][p], 3, 3, ptr(rot),
+                                                           ptr(drawn), ptr(explored), stream()))
+        return rot, ph, None, None, {}
+
+    def same_extra(self, pop, p, tr, st):
+        """What same_member compares on top of the ring, the trainers and the counters."""
+
+    def final_of(self, pop):
+        """Copies of what the tests read of the run's end besides the counters and the ring's head and fill."""
+        return {self.final: getattr(pop.trainer, self.final).clone()}
+
+    # ---- the comparison
+    def run_population(self, s, variant=None):
         """s: one of SHAPES.  The population's `steps` rollout_steps under a sync debug mode that makes any read-back an
         error; returns the agent, its environment and per step (device copies) rot, ph, explored, reward, the loss (a
-        [P] tensor, or 0) and the [P, B] minibatch indices (None while it does not train)."""
+        [P] tensor, or 0), the [P, B] minibatch indices (None while it does not train) and the kind's log_extra."""
         import torch
         from antsrl_amd import population
         whole, shards = make_envs(s["P"], s["Em"], s["N"], s["max_time"], s["bf16"])
@@ -110,7 +156,8 @@ class Kind:
             assert s["Em"] * s["N"] * F * (2 if s["bf16"] else 4) == s["slice_bytes"] and s["slice_bytes"] % 16 == 0
         assert (s["Em"] * s["N"] * F * (2 if s["bf16"] else 4)) % 16 == 0  # the acting kernel's alignment rule
         pop = getattr(population, self.population)(members_of(s), record_per_step=s["K"], replay_size=s["ring"], minibatch=s["B"],
-                                                   min_replay=s["min_replay"], update_target_every=1, seed=3)
+                                                   min_replay=s["min_replay"], update_target_every=1, seed=3,
+                                                   **self.population_kw(s, variant))
         pop.setup(whole)
         pop.initialize(whole)
         whole.observe()
@@ -123,51 +170,41 @@ class Kind:
                 loss = pop.rollout_step(whole)
                 trained = pop.trainer.step_count != before
                 log.append(SimpleNamespace(rot=pop._rot.clone(), ph=pop._ph.clone(), explored=pop._explored.clone(),
-                                           reward=whole.reward.clone(), loss=loss, idx=pop.trainer.last_idx if trained else None))
+                                           reward=whole.reward.clone(), loss=loss, idx=pop.trainer.last_idx if trained else None,
+                                           **self.log_extra(pop)))
         finally:
             torch.cuda.set_sync_debug_mode(0)
-        return SimpleNamespace(pop=pop, env=whole, shards=shards, log=log)
+        return SimpleNamespace(pop=pop, env=whole, shards=shards, log=log, variant=variant)
 
     def run_member_alone(self, s, p, run):
         """Member p alone on its shard handle, entry by entry: the single trainer (seed, lr, discount of the member) and
-        its acting policy, antsrl_agent_select_actions, record_pre, step_update, record_post (the last three without a
-        pheromone for a net that has none), then train_on the population's own indices once fill >= min_replay.  After
-        every step rot, ph (with that head) and explored of the member's slice, env.reward of its rows and loss[p] are
-        equal; returns the member's trainer and ring."""
+        its acting policy, the single agent's select (lone_act), record_pre, step_update, record_post (the last three
+        without a pheromone for a net that has none, and with the memories lone_act names), then train_on the population's
+        own indices once fill >= min_replay.  After every step rot, ph (with that head) and explored of the member's slice,
+        what lone_act names besides, env.reward of its rows and loss[p] are equal; returns the member's trainer, ring and
+        carried state."""
         import torch
-        from antsrl_amd import _lib, train
         from antsrl_amd import config as cm
-        from antsrl_amd.replay import DeviceReplayMemory
-        lib = _lib.load()
         Em, N = s["Em"], s["N"]
         Mm, env = Em * N, run.shards[p]
-        seed, eps = s["seed"][p], s["epsilon"][p]
-        tr = getattr(train, self.single)(F, env.device, discount=s["discount"][p], lr=s["lr"][p], update_target_every=1, seed=seed)
-        rm = DeviceReplayMemory(s["ring"], (7, 7, 6), [2], [2], device=env.device)
+        tr, rm, st = self.lone(s, p, env)
         env.set_activation(torch.full((Em, N, env.cfg.n_phero), 10.0, device=env.device))
         env.observe()
         explored = torch.zeros((Em,), dtype=torch.uint8, device=env.device)
-        unread = torch.zeros((Mm,), dtype=torch.int8, device=env.device)  # without the head, select draws a pheromone that nothing reads
         rows, envs = slice(p * Mm, (p + 1) * Mm), slice(p * Em, (p + 1) * Em)
         for t, want in enumerate(run.log):
             obs, ast = env.obs, env.agent_state
-            rot, ph = tr.policy.act(obs, ast, env=env)
-            rot = rot.reshape(-1).clone()
-            if self.pheromone:
-                ph = ph.reshape(-1).clone()
-            else:
-                none = ph
-                assert none is None
-            drawn = ph if self.pheromone else unread
-            _lib.check(lib.antsrl_agent_select_actions(seed, t, p * Em, Em, N, eps, 3, 3, ptr(rot), ptr(drawn), ptr(explored), stream()))
+            rot, ph, mem_pre, mem_post, extra = self.lone_act(s, p, t, tr, env, st, explored, run.variant)
             assert torch.equal(rot, want.rot[rows]), ("rot", p, t)
             if self.pheromone:
                 assert torch.equal(ph, want.ph[rows]), ("ph", p, t)
             assert torch.equal(explored, want.explored[envs]), ("explored", p, t)
-            rm.record_pre(obs, ast, None, rot, ph, n_envs=Em, n_ants=N, k=s["K"], seed=seed, step=t, env_id_base=p * Em)
+            for name, mine in extra.items():
+                assert torch.equal(mine, getattr(want, name)[rows]), (name, p, t)
+            rm.record_pre(obs, ast, mem_pre, rot, ph, n_envs=Em, n_ants=N, k=s["K"], seed=s["seed"][p], step=t, env_id_base=p * Em)
             done = env.query(cm.Q_TIMESTEP) == s["max_time"]
             env.step_update(rot.view(Em, N), ph.view(Em, N) if self.pheromone else None)
-            rm.record_post(env.obs, env.agent_state, None, env.reward.view(-1), env.done)
+            rm.record_post(env.obs, env.agent_state, mem_post, env.reward.view(-1), env.done)
             assert torch.equal(env.reward.view(-1), want.reward.view(-1)[rows]), ("reward", p, t)
             if rm.fill >= s["min_replay"]:
                 assert want.idx is not None, ("the population did not train at step", t)
@@ -175,7 +212,7 @@ class Kind:
                 assert torch.equal(loss, want.loss[p]), ("loss", p, t, float(loss), float(want.loss[p]))
             else:
                 assert want.idx is None and not torch.is_tensor(want.loss) and want.loss == 0, ("the population trained at step", t)
-        return tr, rm
+        return tr, rm, st
 
     def same_trainers(self, t, p, tr):
         """Member p's weights, target, Adam's moments and gradients in the population trainer `t` are the lone trainer
@@ -190,32 +227,34 @@ class Kind:
         ad, alone_ad = t.adam_state(p), tr.adam_state()
         assert ad["step"] == alone_ad["step"] and all(torch.equal(ad[m][k], alone_ad[m][k]) for m in ("exp_avg", "exp_avg_sq") for k in ad[m])
 
-    def same_member(self, pop, p, tr, rm):
+    def same_member(self, pop, p, tr, rm, st):
         """At the end: all seven ring tensors with head and fill, the weights, the target, Adam's moments, the gradients
-        and the counters of member p are its lone run's."""
+        and the counters of member p are its lone run's, and what the kind's same_extra compares."""
         same_rings(pop.replay_memory.member(p), rm)
         t = pop.trainer
         self.same_trainers(t, p, tr)
         assert (t.step_count, t.syncs) == (tr.step_count, tr.syncs), ((t.step_count, t.syncs), (tr.step_count, tr.syncs))
+        self.same_extra(pop, p, tr, st)
 
-    def checked_run(self, name):
-        """The run of SHAPES[name] with every member checked against its lone run, once per session and kind (the
-        hand-over test reads the explore shape (b)'s population, test_copy_member goes on with shape (a)'s)."""
-        if name not in self._runs:
+    def checked_run(self, name, variant=None):
+        """The run of SHAPES[name] (in the kind's `variant` when none is given) with every member checked against its lone
+        run, once per session, kind, shape and variant (the hand-over test reads the explore shape (b)'s population,
+        test_copy_member goes on with shape (a)'s)."""
+        key = (name, variant or self.variant)
+        if key not in self._runs:
             s = self.SHAPES[name]
-            run = self.run_population(s)
+            run = self.run_population(s, key[1])
             for p in range(s["P"]):
-                tr, rm = self.run_member_alone(s, p, run)
-                self.same_member(run.pop, p, tr, rm)
+                self.same_member(run.pop, p, *self.run_member_alone(s, p, run))
             t, ring = run.pop.trainer, run.pop.replay_memory  # as the run left them (test_copy_member goes on with the agent)
-            run.final = SimpleNamespace(step_count=t.step_count, syncs=t.syncs, fill=ring.fill, head=ring.head,
-                                        **{self.final: getattr(t, self.final).clone()})
-            self._runs[name] = run
-        return self._runs[name]
+            run.final = SimpleNamespace(step_count=t.step_count, syncs=t.syncs, fill=ring.fill, head=ring.head, **self.final_of(run.pop))
+            self._runs[key] = run
+        return self._runs[key]
 
     def check_copy_member(self, weights, theirs):
         """copy_member on shape (a)'s population after its comparison.  weights(p) -> copies of member p's weights, target
-        and Adam's moments; theirs: the test's words for "these are member 0's"."""
+        and Adam's moments (and whatever else the copy takes along whether or not it takes the ring); theirs: the test's
+        words for "these are member 0's"."""
         import torch
         run = self.checked_run("a")
         pop = run.pop
@@ -238,6 +277,51 @@ class Kind:
         assert loss.shape == (3,) and bool(torch.isfinite(loss).all())
 
 
+class MemoryKind(Kind):
+    """A population whose net carries a memory: PopulationMemoryAgent against MemoryTrainer, its acting policy with the
+    carried memory and antsrl_agent_select.  A shape names the net (power, mem); the variant is the population's
+    state_memory.  A step's log entry holds the new memory (`mem`); the lone loop carries the two memory halves."""
+
+    variant = "reference"
+
+    def population_kw(self, s, variant):
+        return dict(mem_size=s["mem"], power=s["power"], state_memory=variant)
+
+    def log_extra(self, pop):
+        return dict(mem=pop.previous_memory.clone())
+
+    def lone(self, s, p, env):
+        import torch
+        from antsrl_amd.replay import DeviceReplayMemory
+        from antsrl_amd.train import MemoryTrainer
+        tr = MemoryTrainer(F, env.device, discount=s["discount"][p], lr=s["lr"][p], update_target_every=1, power=s["power"],
+                           mem_size=s["mem"], seed=s["seed"][p])
+        halves = [torch.zeros((s["Em"] * s["N"], s["mem"]), device=env.device) for _ in range(2)]
+        return tr, DeviceReplayMemory(s["ring"], (7, 7, 6), [2 + s["mem"]], [2], device=env.device), SimpleNamespace(halves=halves, cur=0)
+
+    def lone_act(self, s, p, t, tr, env, st, explored, variant):
+        from antsrl_amd import _lib
+        old, new = st.halves[st.cur], st.halves[1 - st.cur]
+        rot, ph, _ = tr.policy.act(env.obs, env.agent_state, memory=old, out=new, env=env)
+        rot, ph = rot.reshape(-1).clone(), ph.reshape(-1).clone()
+        _lib.check(_lib.load().antsrl_agent_select(s["seed"][p], t, p * s["Em"], s["Em"], s["N"], s["epsilon"][p], 3, 3, s["mem"], ptr(rot),
+                                                   ptr(ph), ptr(old), ptr(new), ptr(explored), stream()), "agent_select")
+        st.cur = 1 - st.cur
+        return rot, ph, new if variant == "reference" else old, new, dict(mem=new)
+
+    def same_extra(self, pop, p, tr, st):
+        """The dict has the reference's 26 tensors; both memory halves, the current one first."""
+        import torch
+        Mm = pop.g.Mm
+        rows = slice(p * Mm, (p + 1) * Mm)
+        assert len(pop.trainer.state_dict(p)) == 26
+        assert torch.equal(pop._mem[pop._cur][rows], st.halves[st.cur]) and torch.equal(pop._mem[1 - pop._cur][rows], st.halves[1 - st.cur])
+
+    def final_of(self, pop):
+        ring = pop.replay_memory
+        return dict(model=pop.trainer._model.clone(), agent_states=ring.agent_states.clone(), new_agent_states=ring.new_agent_states.clone())
+
+
 COLLECT = Kind("PopulationAgent", "LinearTrainer", True, "heads",
                dict(a=dict(_A, slice_bytes=23520), b=dict(_B, B=264, slice_bytes=37632)),
                lambda t, p, tr: (("w1", t.w1[p], tr.policy.w1), ("b1", t.b1[p], tr.policy.b1), ("heads", t.heads[p], tr.heads),
@@ -247,3 +331,9 @@ EXPLORE = Kind("PopulationExploreAgent", "ExploreTrainer", False, "model", dict(
                lambda t, p, tr: (("model", t.model[p], tr.model), ("target", t.target[p], tr.target),
                                  ("adam m", t._adam[0, p], tr._adam[0]), ("adam v", t._adam[1, p], tr._adam[1]),
                                  ("grads", t.grads[p], tr.grads)))
+#: (a) is _A with a small net; (b) is _B with the reference's B = 264, power 5 and mem 20.  The state blocks hold the
+#: masters, Adam's moments and the training packs: compared byte for byte, with the acting pack
+MEMORY = MemoryKind("PopulationMemoryAgent", "MemoryTrainer", True, "_model",
+                    dict(a=dict(_A, power=4, mem=3), b=dict(_B, B=264, power=5, mem=20)),
+                    lambda t, p, tr: (("the model's state block", t._model[p], tr._model), ("the target's state block", t._target[p], tr._target),
+                                      ("the acting pack", t.packed[p], tr.policy.packed), ("grads", t.grads[p], tr.grads)))

@@ -10,7 +10,7 @@ import pytest
 import memory_train_ref as R
 from abi_fakes import FAKE, ODD, ODD4, ODD128, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from population_abi import call_train, spec
+from population_abi import call_train, shape, spec
 
 NEW = ("antsrl_pop_memtrain_sizes", "antsrl_pop_memtrain_step")
 WHO = b"pop_memtrain_step"
@@ -20,10 +20,6 @@ def test_new_symbols_are_exported(lib):
     for n in NEW:
         assert hasattr(lib, n) and n in _lib.EXPORTS
     assert lib.antsrl_abi_version() == 5  # the entries are additive
-
-
-def shape(F=294, power=5, mem=20, n_rot=3, n_ph=3, agent_dim=2):
-    return _lib.AntsMemNetShape(F, agent_dim, mem, 2 ** (1 + power), 2 ** (2 + power), 2 ** (3 + power), n_rot, n_ph)
 
 
 NET_PTRS = ("net_states", "target_states")

@@ -10,23 +10,16 @@ import pytest
 
 from abi_fakes import FAKE, ODD, ODD4, ODD128, lib  # noqa: F401 (lib is a fixture)
 from antsrl_amd import _lib
-from population_abi import call, spec
+from population_abi import BF16, FP32, call, shape, spec
 
 NEW = ("antsrl_pop_memnet_sizes", "antsrl_pop_policy_memory", "antsrl_pop_memory_select", "antsrl_pop_memory_record_pre",
        "antsrl_pop_memory_record_post")
-BF16, FP32 = 0, 1  # include/antsrl.h ANTSRL_MEMNET_BF16 / ANTSRL_MEMNET_FP32
 
 
 def test_new_symbols_are_exported(lib):
     for n in NEW:
         assert hasattr(lib, n) and n in _lib.EXPORTS
     assert lib.antsrl_abi_version() == 5  # the entries are additive
-
-
-def shape(F=294, A=2, mem=20, power=5, n_rot=3, n_ph=3, **kw):
-    a = dict(h1=2 ** (1 + power), h2=2 ** (2 + power), h3=2 ** (3 + power))
-    a.update(kw)
-    return _lib.AntsMemNetShape(F, A, mem, a["h1"], a["h2"], a["h3"], n_rot, n_ph)
 
 
 POLICY_PTRS = ("packed", "obs", "agent_state", "mem_in", "mem_out", "rotation", "pheromone", "q_out")
