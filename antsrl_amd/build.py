@@ -32,11 +32,11 @@ HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "
                                            "antsrl_agent_select_memory.inc", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_loopapi.h",
                                            "antsrl_draw.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
-                                           "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",
+                                           "antsrl_l1train.h", "antsrl_l1train_dev.h", "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",
                                            "antsrl_cellread.h", "antsrl_recorder.h", "antsrl_render.h", "antsrl_stats.h",
                                            "antsrl_launch.h", "antsrl_handle.h", "antsrl_checkpoint.h",
                                            "antsrl_policy_flat.h", "antsrl_memagent_dev.h", "antsrl_lintrain_dev.h",
-                                           "antsrl_population.h", "antsrl_policy_flat_body.inc",
+                                           "antsrl_population.h", "antsrl_population_dev.h", "antsrl_policy_flat_body.inc",
                                            "antsrl_agent_select_actions.inc", "antsrl_replay_record_body.inc",
                                            "antsrl_lintrain_body.inc", "antsrl_exptrain_dev.h",
                                            "antsrl_exptrain_fwd_body.inc", "antsrl_jointtrain_dev.h",

@@ -1,6 +1,6 @@
 // antsrl_dqn.h — what every on-device DQN training step takes from the replay arrays, whichever net it trains.  The
 // minibatch's fields carry one set of names in DqnBatch (below: the 32-wide nets', in front of the net's own pointers in
-// LinTrainArgs, antsrl_lintrain.h, ExpTrainArgs, antsrl_exptrain.h, and JointTrainArgs, antsrl_jointtrain.h) and in ReworkTrainArgs (antsrl_reworktrain.h),
+// LinTrainArgs, antsrl_lintrain.h, and L1TrainArgs, antsrl_l1train.h) and in ReworkTrainArgs (antsrl_reworktrain.h),
 // so one host function checks and fills them for every entry (antsrl_dqn_minibatch) and one device function clamps idx
 // into the ring (dqn_row).  Adam's part is AdamArgs (antsrl_adam.h); antsrl_dqn_dev.h holds the device code the two
 // 32-wide steps share.

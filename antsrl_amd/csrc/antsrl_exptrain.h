@@ -14,32 +14,25 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_adam.h"
-#include "antsrl_dqn.h"
-#include "antsrl_fail.h"
+#include "antsrl_l1train.h"
 
 #define ET_HIDDEN DQN_HIDDEN
 #define ET_L2 99            // floats of layer2: w2 [3][32], b2 [3]
 #define ET_OUT 100          // what the forward stage sums over rows: layer2's 99 gradients and the loss
 #define ET_PART 104         // floats per workgroup in the partials (ET_OUT rounded up to 16 bytes)
-#define ET_WAVES 4          // waves per workgroup of the forward stage: it takes 4 tiles of 32 rows
-#define ET_L1_WAVES DQN_L1_WAVES // waves per workgroup of the layer1 stage: wave w walks rows w, w + 16, ...
-#define ET_MAX_B 65536      // rows of a minibatch
-#define ET_SLAB DQN_L1_SLAB // columns of layer1 one workgroup of the layer1 stage owns
+#define ET_WAVES L1T_WAVES  // waves per workgroup of the forward stage
 
-struct ExpTrainArgs {
-    DqnBatch batch;           // grads: P floats; partials: [workgroups of the forward stage][ET_PART]
-    float *model;             // P floats: read by the forward, written by Adam
-    const float *target;      // P floats, only read
-    float *dh;                // workspace: [B][32]
-    int blocks;               // workgroups of the forward stage
-    AdamArgs adam;            // m, v: P floats each
+// the step on antsrl_l1train.h's frame: L1TrainArgs with a target of floats(F) floats, the full copy
+struct ANTSRL_INTERNAL ExpNet {
+    static constexpr int OUT = ET_OUT, PART = ET_PART;
+    static constexpr int MAX_B = 65536, POP_MAX_B = 32 * ET_WAVES * 4; // a member's: four forward workgroups, the linear members' 512 rows
+    static constexpr const char *TARGET = "target";
+    __host__ __device__ static size_t floats(int F) { return l1t_floats(F, ET_L2); }
+    __host__ __device__ static size_t target_floats(int F) { return floats(F); }
+    static size_t lds(int ksteps);
+    static hipError_t launch(const L1TrainArgs &a, hipStream_t st);
+    // a: member 0's (B <= POP_MAX_B; idx [P][B]; partials and dh inside member 0's part of the workspace); the table
+    // gives discount and step size
+    static hipError_t launch_pop(const L1TrainArgs &a, const PopTable &t, int P, size_t ws_stride, const PopRunningLoss &rl,
+                                 hipStream_t st);
 };
-
-__host__ __device__ static inline size_t antsrl_exptrain_floats(int F) { return (size_t)ET_HIDDEN * (F + 2) + ET_HIDDEN + ET_L2; }
-static inline int antsrl_exptrain_blocks(int B) { return ((B + 31) / 32 + ET_WAVES - 1) / ET_WAVES; }
-// bytes of the partials in front of dh in the workspace (256-byte aligned)
-static inline size_t antsrl_exptrain_dh_offset(int B) { return ((size_t)antsrl_exptrain_blocks(B) * ET_PART * 4 + 255) / 256 * 256; }
-
-// the forward stage and the layer1 stage: two launches
-ANTSRL_INTERNAL hipError_t antsrl_launch_exptrain(const ExpTrainArgs &a, hipStream_t st);

@@ -25,34 +25,22 @@
 // No atomics anywhere and every order above is fixed: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_dqn_dev.h"
 #include "antsrl_exptrain.h"
 #include "antsrl_exptrain_dev.h"
-#include "antsrl_lds_optin.h"
+#include "antsrl_l1train_dev.h"
 
 // the forward stage: its body is one text (antsrl_exptrain_fwd_body.inc), run for every member of a population by
 // k_pop_exptrain_fwd (antsrl_popexplore.hip) too
-__global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const ExpTrainArgs a)
+__global__ void __launch_bounds__(64 * ET_WAVES) k_exptrain_fwd(const L1TrainArgs a)
 {
 #include "antsrl_exptrain_fwd_body.inc"
 }
 
 // the layer1 stage: dqn_l1_stage (antsrl_dqn_dev.h) on ExploreModel's block, b1 behind w1 and layer2 behind b1
-__global__ void __launch_bounds__(64 * ET_L1_WAVES) k_exptrain_l1(const ExpTrainArgs a, const int nslabs)
+__global__ void __launch_bounds__(64 * DQN_L1_WAVES) k_exptrain_l1(const L1TrainArgs a, const int nslabs)
 {
-    __shared__ float red[ET_L1_WAVES * ET_HIDDEN * ET_SLAB];
-    const size_t ob1 = (size_t)ET_HIDDEN * (a.batch.F + 2);
-    dqn_l1_stage(a.batch, a.model, a.adam, a.dh, a.blocks, nslabs, DqnL1Layout{ob1, ob1 + ET_HIDDEN, ET_OUT, ET_PART}, red);
+    l1t_l1_stage<ExpNet>(a, nslabs);
 }
 
-hipError_t antsrl_launch_exptrain(const ExpTrainArgs &a, hipStream_t st)
-{
-    const size_t lds = et_lds(a.batch.ksteps); // 61 KB at F = 294, 151 KB at the widest rows: above 64 KiB it is an opt-in per device
-    hipError_t e = antsrl_lds_optin<k_exptrain_fwd>(lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_exptrain_fwd, dim3(a.blocks), dim3(64 * ET_WAVES), lds, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const int nslabs = (a.batch.F + 3 + ET_SLAB - 1) / ET_SLAB;
-    hipLaunchKernelGGL(k_exptrain_l1, dim3(nslabs + 1), dim3(64 * ET_L1_WAVES), 0, st, a, nslabs);
-    return hipGetLastError();
-}
+// (the forward stage's LDS: 61 KB at F = 294, 151 KB at the widest rows)
+hipError_t ExpNet::launch(const L1TrainArgs &a, hipStream_t st) { return l1t_launch<ExpNet, k_exptrain_fwd, k_exptrain_l1>(a, st); }

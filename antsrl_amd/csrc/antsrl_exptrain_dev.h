@@ -15,7 +15,7 @@
 __device__ __forceinline__ float et_bf16(const float x) { return (float)(__bf16)x; }
 
 // the forward stage's dynamic LDS: 61 KB at F = 294, 151 KB at the widest rows: above 64 KiB it is an opt-in per device
-static inline size_t et_lds(int ksteps)
+inline size_t ExpNet::lds(int ksteps)
 {
     return (size_t)2 * ET_HIDDEN * (16 * ksteps + 8) * 2 +
            (2 * ET_SLOT + 6 * ET_HIDDEN + (size_t)ET_WAVES * ET_PART + (size_t)ET_WAVES * ET_TILE) * 4;

@@ -2,7 +2,7 @@
 // inside the braces of the two kernels that run it, k_exptrain_fwd (antsrl_exptrain.hip) and k_pop_exptrain_fwd
 // (antsrl_popexplore.hip).  A textual include and not a __device__ function, for the reason antsrl_policy_flat_body.inc
 // gives (DESIGN §7.24): included, k_exptrain_fwd's text is what it always was.  It reads one name of the including
-// kernel: `a`, the ExpTrainArgs of the net it trains, and the x dimension of the grid (the workgroups that share the
+// kernel: `a`, the L1TrainArgs of the net it trains, and the x dimension of the grid (the workgroups that share the
 // minibatch's tiles).  antsrl_exptrain.hip's header describes the stage; antsrl_exptrain_dev.h holds its LDS layout.
     extern __shared__ __align__(16) unsigned char smem[];
     const DqnBatch &mb = a.batch;

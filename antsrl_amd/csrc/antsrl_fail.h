@@ -19,3 +19,11 @@ static inline int enqueued(hipError_t e, const char *who) { return e != hipSucce
         if (!(p)) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, #p);                                          \
         if ((uintptr_t)(p) & ((align) - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, #p, (int)(align)); \
     } while (0)
+
+// REQUIRE for a pointer that the entries of a shared body name differently: `name` is the ABI's
+static inline int require_named(const char *who, const char *name, const void *p, int align)
+{
+    if (!p) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
+    if ((uintptr_t)p & (uintptr_t)(align - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, name, align);
+    return ANTSRL_OK;
+}

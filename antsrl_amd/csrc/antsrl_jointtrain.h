@@ -13,31 +13,25 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_adam.h"
-#include "antsrl_dqn.h"
-#include "antsrl_fail.h"
+#include "antsrl_l1train.h"
 #include "antsrl_lintrain.h"
 
 #define JT_HIDDEN DQN_HIDDEN
 #define JT_HEADS LT_HEADS   // floats behind layer1: w2, b2, w3, b3
 #define JT_OUT LT_OUT       // what the forward stage sums over rows: the 198 head gradients and the loss
 #define JT_PART LT_PART     // floats per workgroup in the partials: k_lintrain's [200] row
-#define JT_WAVES 4          // waves per workgroup of the forward stage: it takes 4 tiles of 32 rows
-#define JT_MAX_B 65536      // rows of a minibatch
+#define JT_WAVES L1T_WAVES  // waves per workgroup of the forward stage
 
-struct JointTrainArgs {
-    DqnBatch batch;           // grads: P floats; partials: [workgroups of the forward stage][JT_PART]
-    float *model;             // P floats: read by the forward, written by Adam
-    const float *target_l3;   // LT_L3 floats, only read
-    float *dh;                // workspace: [B][32]
-    int blocks;               // workgroups of the forward stage
-    AdamArgs adam;            // m, v: P floats each
+// the step on antsrl_l1train.h's frame: L1TrainArgs whose target is the target net's layer3, LT_L3 floats
+struct ANTSRL_INTERNAL JointNet {
+    static constexpr int OUT = JT_OUT, PART = JT_PART;
+    static constexpr int MAX_B = 65536, POP_MAX_B = 32 * JT_WAVES * 4; // a member's: the explore member's four forward workgroups
+    static constexpr const char *TARGET = "target_l3";
+    __host__ __device__ static size_t floats(int F) { return l1t_floats(F, JT_HEADS); }
+    __host__ __device__ static size_t target_floats(int) { return LT_L3; }
+    static size_t lds(int ksteps);
+    static hipError_t launch(const L1TrainArgs &a, hipStream_t st);
+    // a: member 0's, as ExpNet::launch_pop's (antsrl_exptrain.h)
+    static hipError_t launch_pop(const L1TrainArgs &a, const PopTable &t, int P, size_t ws_stride, const PopRunningLoss &rl,
+                                 hipStream_t st);
 };
-
-__host__ __device__ static inline size_t antsrl_jointtrain_floats(int F) { return (size_t)JT_HIDDEN * (F + 2) + JT_HIDDEN + JT_HEADS; }
-static inline int antsrl_jointtrain_blocks(int B) { return ((B + 31) / 32 + JT_WAVES - 1) / JT_WAVES; }
-// bytes of the partials in front of dh in the workspace (256-byte aligned)
-static inline size_t antsrl_jointtrain_dh_offset(int B) { return ((size_t)antsrl_jointtrain_blocks(B) * JT_PART * 4 + 255) / 256 * 256; }
-
-// the forward stage and the layer1 stage: two launches
-ANTSRL_INTERNAL hipError_t antsrl_launch_jointtrain(const JointTrainArgs &a, hipStream_t st);

@@ -19,36 +19,24 @@
 // No atomics anywhere and every order above is fixed: equal inputs give equal bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_dqn_dev.h"
 #include "antsrl_jointtrain.h"
 #include "antsrl_jointtrain_dev.h"
-#include "antsrl_lds_optin.h"
+#include "antsrl_l1train_dev.h"
 
 // One wave per SIMD, as k_lintrain (antsrl_lintrain.hip): this is that kernel's forward at up to 512
 // workgroups, and the condition under which it once returned a differing row of partials is a second wave on the SIMD.
 // The body is one text (antsrl_jointtrain_fwd_body.inc), run for every member of a population by k_pop_jointtrain_fwd
 // (antsrl_popjoint.hip) too.
-__global__ void __launch_bounds__(64 * JT_WAVES) __attribute__((amdgpu_waves_per_eu(1, 1))) k_jointtrain_fwd(const JointTrainArgs a)
+__global__ void __launch_bounds__(64 * JT_WAVES) __attribute__((amdgpu_waves_per_eu(1, 1))) k_jointtrain_fwd(const L1TrainArgs a)
 {
 #include "antsrl_jointtrain_fwd_body.inc"
 }
 
 // the layer1 stage: dqn_l1_stage (antsrl_dqn_dev.h) on CollectModel's block, b1 behind w1 and the 198 heads behind b1
-__global__ void __launch_bounds__(64 * DQN_L1_WAVES) k_jointtrain_l1(const JointTrainArgs a, const int nslabs)
+__global__ void __launch_bounds__(64 * DQN_L1_WAVES) k_jointtrain_l1(const L1TrainArgs a, const int nslabs)
 {
-    __shared__ float red[DQN_L1_WAVES * JT_HIDDEN * DQN_L1_SLAB];
-    const size_t ob1 = (size_t)JT_HIDDEN * (a.batch.F + 2);
-    dqn_l1_stage(a.batch, a.model, a.adam, a.dh, a.blocks, nslabs, DqnL1Layout{ob1, ob1 + JT_HIDDEN, JT_OUT, JT_PART}, red);
+    l1t_l1_stage<JointNet>(a, nslabs);
 }
 
-hipError_t antsrl_launch_jointtrain(const JointTrainArgs &a, hipStream_t st)
-{
-    const size_t lds = jt_lds(a.batch.ksteps); // 45 760 bytes at F = 294, 91 840 at the widest rows: above 64 KiB it is an opt-in per device
-    hipError_t e = antsrl_lds_optin<k_jointtrain_fwd>(lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_jointtrain_fwd, dim3(a.blocks), dim3(64 * JT_WAVES), lds, st, a);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const int nslabs = (a.batch.F + 3 + DQN_L1_SLAB - 1) / DQN_L1_SLAB;
-    hipLaunchKernelGGL(k_jointtrain_l1, dim3(nslabs + 1), dim3(64 * DQN_L1_WAVES), 0, st, a, nslabs);
-    return hipGetLastError();
-}
+// (the forward stage's LDS: 45 760 bytes at F = 294, 91 840 at the widest rows)
+hipError_t JointNet::launch(const L1TrainArgs &a, hipStream_t st) { return l1t_launch<JointNet, k_jointtrain_fwd, k_jointtrain_l1>(a, st); }

@@ -14,7 +14,7 @@
 #define JT_TILE (32 * JT_HSTRIDE + 32 * JT_DSTRIDE)
 
 // the forward stage's dynamic LDS: 45 760 bytes at F = 294, 91 840 at the widest rows: above 64 KiB it is an opt-in per device
-static inline size_t jt_lds(int ksteps)
+inline size_t JointNet::lds(int ksteps)
 {
     return (size_t)JT_HIDDEN * (16 * ksteps + 8) * 2 +
            (JT_HW + 3 * JT_HIDDEN + (size_t)JT_WAVES * JT_PART + (size_t)JT_WAVES * JT_TILE) * 4;

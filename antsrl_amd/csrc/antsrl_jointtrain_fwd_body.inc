@@ -2,7 +2,7 @@
 // the braces of the two kernels that run it, k_jointtrain_fwd (antsrl_jointtrain.hip) and k_pop_jointtrain_fwd
 // (antsrl_popjoint.hip).  A textual include and not a __device__ function, for the reason antsrl_policy_flat_body.inc
 // gives (DESIGN §7.24): included, k_jointtrain_fwd's text is what it always was.  It reads one name of the including
-// kernel: `a`, the JointTrainArgs of the net it trains, and the x dimension of the grid (the workgroups that share the
+// kernel: `a`, the L1TrainArgs of the net it trains (its target: layer3), and the x dimension of the grid (the workgroups that share the
 // minibatch's tiles).  antsrl_jointtrain.hip's header describes the stage; antsrl_jointtrain_dev.h holds its LDS layout.
     extern __shared__ __align__(16) unsigned char smem[];
     const DqnBatch &mb = a.batch;
@@ -18,7 +18,7 @@
 
     dqn_stage_w1(a.model, w1s, F, ksteps, KP, wib, JT_WAVES, lane);
     for (int i = threadIdx.x; i < JT_HEADS + LT_L3; i += 64 * JT_WAVES)
-        hw[(i / LT_L3) * JT_SLOT + i % LT_L3] = i < JT_HEADS ? heads[i] : a.target_l3[i - JT_HEADS];
+        hw[(i / LT_L3) * JT_SLOT + i % LT_L3] = i < JT_HEADS ? heads[i] : a.target[i - JT_HEADS];
     if (threadIdx.x < JT_HIDDEN) {
         const int hid = threadIdx.x;
         l1x[hid] = b1[hid];

@@ -2,7 +2,8 @@
 // agent's training step"): antsrl_lintrain_sizes / _grad / _apply / _step in front of antsrl_lintrain.hip's kernels, and
 // behind them the explore agent's ("The explore agent's training step"): antsrl_exptrain_sizes / _grad / _apply / _step
 // in front of antsrl_exptrain.hip's, and the joint step's ("The joint training step"): antsrl_jointtrain_sizes / _grad /
-// _apply / _step in front of antsrl_jointtrain.hip's, all with the same argument rules.  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
+// _apply / _step in front of antsrl_jointtrain.hip's, all with the same argument rules; the last two nets' entries are
+// calls of one body per stage over the net's descriptor (antsrl_l1train.h).  antsrl_dqn_minibatch (antsrl_dqn.h) checks and fills
 // what every step takes from the replay arrays, the rework agent's (antsrl_reworkapi.hip) included; dqn_batch adds what
 // the 32-wide nets keep in DqnBatch, antsrl_adam_step (antsrl_adam.h) Adam's part; an entry checks its own net's
 // pointers, its limit on B and its workspace rule.
@@ -128,35 +129,85 @@ extern "C" int antsrl_lintrain_step(int32_t n_features, const float *w1, const f
     return enqueued(antsrl_launch_lintrain(a, (hipStream_t)stream), who);
 }
 
-// ---- the explore agent's training step (antsrl_exptrain.hip) ------------------------------------------------------------
+// ---- the steps that train layer1 (antsrl_l1train.h's frame): one body per stage over the net's descriptor, ExpNet for
+// the explore agent's step (antsrl_exptrain.hip) and JointNet for the joint step (antsrl_jointtrain.hip) --------------------
 
-extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
-                                     int32_t *launches)
+template <class Net>
+static int l1t_sizes(const char *who, int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
+                     int32_t *launches)
 {
-    const char *who = "exptrain_sizes";
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, ET_MAX_B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, Net::MAX_B);
     if (rc != ANTSRL_OK) return rc;
-    if (trained_floats) *trained_floats = antsrl_exptrain_floats(n_features);
-    if (workspace_bytes) *workspace_bytes = antsrl_exptrain_dh_offset((int)B) + (size_t)B * ET_HIDDEN * sizeof(float);
+    if (trained_floats) *trained_floats = Net::floats(n_features);
+    if (workspace_bytes) *workspace_bytes = l1t_workspace_bytes<Net>((int)B);
     if (launches) *launches = 2;
     return ANTSRL_OK;
 }
 
 // the nets and the workspace of the gradient stage and the fused step
-static int et_net(const char *who, int32_t n_features, int64_t B, float *model, const float *target, void *workspace,
-                  ExpTrainArgs *a)
+template <class Net>
+static int l1t_net(const char *who, int32_t n_features, int64_t B, float *model, const float *target, void *workspace,
+                   L1TrainArgs *a)
 {
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, ET_MAX_B);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, Net::MAX_B);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
-    REQUIRE(target, 4);
+    if ((rc = require_named(who, Net::TARGET, target, 4)) != ANTSRL_OK) return rc;
     REQUIRE(workspace, 256);
     a->model = model; a->target = target;
-    a->dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
-    a->blocks = antsrl_exptrain_blocks((int)B);
+    a->dh = (float *)((unsigned char *)workspace + l1t_dh_offset<Net>((int)B));
+    a->blocks = l1t_blocks((int)B);
     return ANTSRL_OK;
+}
+
+template <class Net>
+static int l1t_grad(const char *who, int32_t n_features, const float *model, const float *target, const float *states,
+                    const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
+                    const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
+                    float discount, float *grads, float *loss, void *workspace, void *stream)
+{
+    L1TrainArgs a = {};
+    int rc = l1t_net<Net>(who, n_features, B, const_cast<float *>(model), target, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, true, loss, workspace, &a.batch);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(Net::launch(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
+}
+
+template <class Net>
+static int l1t_step(const char *who, int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
+                    const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                    const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                    const int64_t *idx, int64_t B, float discount, int64_t step, double lr, double beta1, double beta2,
+                    double eps, float *grads, float *loss, void *workspace, void *stream)
+{
+    L1TrainArgs a = {};
+    int rc = l1t_net<Net>(who, n_features, B, model, target, workspace, &a);
+    if (rc == ANTSRL_OK)
+        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
+                       idx, B, discount, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(Net::launch(a, (hipStream_t)stream), who);
+}
+
+template <class Net>
+static int l1t_apply(const char *who, int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
+                     int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
+{
+    const int rc = lt_features(who, n_features);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps, (int)Net::floats(n_features), stream);
+}
+
+extern "C" int antsrl_exptrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
+                                     int32_t *launches)
+{
+    return l1t_sizes<ExpNet>("exptrain_sizes", n_features, B, trained_floats, workspace_bytes, launches);
 }
 
 extern "C" int antsrl_exptrain_grad(int32_t n_features, const float *model, const float *target, const float *states,
@@ -165,25 +216,14 @@ extern "C" int antsrl_exptrain_grad(int32_t n_features, const float *model, cons
                                     int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, float *loss,
                                     void *workspace, void *stream)
 {
-    const char *who = "exptrain_grad";
-    ExpTrainArgs a = {};
-    int rc = et_net(who, n_features, B, const_cast<float *>(model), target, workspace, &a);
-    if (rc == ANTSRL_OK)
-        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
-                       idx, B, discount, grads, true, loss, workspace, &a.batch);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
+    return l1t_grad<ExpNet>("exptrain_grad", n_features, model, target, states, agent_states, actions, rewards, new_states,
+                            new_agent_states, dones, n_rows, idx, B, discount, grads, loss, workspace, stream);
 }
 
 extern "C" int antsrl_exptrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
                                      int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
 {
-    const char *who = "exptrain_apply";
-    const int rc = lt_features(who, n_features);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(model, 4);
-    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps,
-                             (int)antsrl_exptrain_floats(n_features), stream);
+    return l1t_apply<ExpNet>("exptrain_apply", n_features, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps, stream);
 }
 
 extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const float *target, float *adam_m, float *adam_v,
@@ -193,46 +233,15 @@ extern "C" int antsrl_exptrain_step(int32_t n_features, float *model, const floa
                                     int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
                                     float *loss, void *workspace, void *stream)
 {
-    const char *who = "exptrain_step";
-    ExpTrainArgs a = {};
-    int rc = et_net(who, n_features, B, model, target, workspace, &a);
-    if (rc == ANTSRL_OK)
-        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
-                       idx, B, discount, grads, false, loss, workspace, &a.batch);
-    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_exptrain(a, (hipStream_t)stream), who);
+    return l1t_step<ExpNet>("exptrain_step", n_features, model, target, adam_m, adam_v, states, agent_states, actions,
+                            rewards, new_states, new_agent_states, dones, n_rows, idx, B, discount, step, lr, beta1, beta2, eps,
+                            grads, loss, workspace, stream);
 }
-
-// ---- the joint training step: layer1 under the collect heads (antsrl_jointtrain.hip) ---------------------------------------
 
 extern "C" int antsrl_jointtrain_sizes(int32_t n_features, int64_t B, size_t *trained_floats, size_t *workspace_bytes,
                                        int32_t *launches)
 {
-    const char *who = "jointtrain_sizes";
-    int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, JT_MAX_B);
-    if (rc != ANTSRL_OK) return rc;
-    if (trained_floats) *trained_floats = antsrl_jointtrain_floats(n_features);
-    if (workspace_bytes) *workspace_bytes = antsrl_jointtrain_dh_offset((int)B) + (size_t)B * JT_HIDDEN * sizeof(float);
-    if (launches) *launches = 2;
-    return ANTSRL_OK;
-}
-
-// the net and the workspace of the gradient stage and the fused step
-static int jt_net(const char *who, int32_t n_features, int64_t B, float *model, const float *target_l3, void *workspace,
-                  JointTrainArgs *a)
-{
-    int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, JT_MAX_B);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(model, 4);
-    REQUIRE(target_l3, 4);
-    REQUIRE(workspace, 256);
-    a->model = model; a->target_l3 = target_l3;
-    a->dh = (float *)((unsigned char *)workspace + antsrl_jointtrain_dh_offset((int)B));
-    a->blocks = antsrl_jointtrain_blocks((int)B);
-    return ANTSRL_OK;
+    return l1t_sizes<JointNet>("jointtrain_sizes", n_features, B, trained_floats, workspace_bytes, launches);
 }
 
 extern "C" int antsrl_jointtrain_grad(int32_t n_features, const float *model, const float *target_l3, const float *states,
@@ -241,25 +250,14 @@ extern "C" int antsrl_jointtrain_grad(int32_t n_features, const float *model, co
                                       int64_t n_rows, const int64_t *idx, int64_t B, float discount, float *grads, float *loss,
                                       void *workspace, void *stream)
 {
-    const char *who = "jointtrain_grad";
-    JointTrainArgs a = {};
-    int rc = jt_net(who, n_features, B, const_cast<float *>(model), target_l3, workspace, &a);
-    if (rc == ANTSRL_OK)
-        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
-                       idx, B, discount, grads, true, loss, workspace, &a.batch);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_jointtrain(a, (hipStream_t)stream), who); // a.adam.on == 0: model is only read
+    return l1t_grad<JointNet>("jointtrain_grad", n_features, model, target_l3, states, agent_states, actions, rewards, new_states,
+                              new_agent_states, dones, n_rows, idx, B, discount, grads, loss, workspace, stream);
 }
 
 extern "C" int antsrl_jointtrain_apply(int32_t n_features, float *model, float *adam_m, float *adam_v, const float *grads,
                                        int64_t step, double lr, double beta1, double beta2, double eps, void *stream)
 {
-    const char *who = "jointtrain_apply";
-    const int rc = lt_features(who, n_features);
-    if (rc != ANTSRL_OK) return rc;
-    REQUIRE(model, 4);
-    return antsrl_adam_apply(who, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps,
-                             (int)antsrl_jointtrain_floats(n_features), stream);
+    return l1t_apply<JointNet>("jointtrain_apply", n_features, model, adam_m, adam_v, grads, step, lr, beta1, beta2, eps, stream);
 }
 
 extern "C" int antsrl_jointtrain_step(int32_t n_features, float *model, const float *target_l3, float *adam_m, float *adam_v,
@@ -269,13 +267,7 @@ extern "C" int antsrl_jointtrain_step(int32_t n_features, float *model, const fl
                                       int64_t step, double lr, double beta1, double beta2, double eps, float *grads,
                                       float *loss, void *workspace, void *stream)
 {
-    const char *who = "jointtrain_step";
-    JointTrainArgs a = {};
-    int rc = jt_net(who, n_features, B, model, target_l3, workspace, &a);
-    if (rc == ANTSRL_OK)
-        rc = dqn_batch(who, n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows,
-                       idx, B, discount, grads, false, loss, workspace, &a.batch);
-    if (rc == ANTSRL_OK) rc = antsrl_adam_step(who, adam_m, adam_v, step, lr, beta1, beta2, eps, &a.adam);
-    if (rc != ANTSRL_OK) return rc;
-    return enqueued(antsrl_launch_jointtrain(a, (hipStream_t)stream), who);
+    return l1t_step<JointNet>("jointtrain_step", n_features, model, target_l3, adam_m, adam_v, states, agent_states,
+                              actions, rewards, new_states, new_agent_states, dones, n_rows, idx, B, discount, step, lr, beta1,
+                              beta2, eps, grads, loss, workspace, stream);
 }

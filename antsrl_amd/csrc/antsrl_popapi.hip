@@ -25,9 +25,7 @@
 #define POP_N_ROT 3 // the linear net's heads are 3 wide
 #define POP_N_PH 3
 #define POP_AGENT_DIM 2
-#define POP_ET_MAX_B (32 * ET_WAVES * 4) // an explore member's minibatch: four forward workgroups, the linear members' 512 rows
-#define POP_ET_LIMIT "at most four forward workgroups"
-#define POP_JT_MAX_B (32 * JT_WAVES * 4) // a joint member's: the same four forward workgroups
+#define POP_L1T_LIMIT "at most four forward workgroups" // (what Net::POP_MAX_B rows are, antsrl_l1train.h)
 
 static int pop_n_members(const char *who, int n_members)
 {
@@ -250,60 +248,55 @@ extern "C" int antsrl_pop_lintrain_step(const AntsPopSpec *s, const float *w1, c
 
 // ---- the population of explore agents (antsrl_popexplore.hip) -------------------------------------------------------------
 
-// REQUIRE for a pointer that the entries of a shared front name differently
-static int pop_require(const char *who, const char *name, const void *p, int align)
-{
-    if (!p) return fail(ANTSRL_E_INVALID, "%s: %s is required", who, name);
-    if ((uintptr_t)p & (uintptr_t)(align - 1)) return fail(ANTSRL_E_INVALID, "%s: %s must be %d-byte aligned", who, name, align);
-    return ANTSRL_OK;
-}
-
-// antsrl_pop_exptrain_sizes and antsrl_pop_jointtrain_sizes: a flat-block net's, given its largest minibatch, the floats of
-// a member's block and the bytes of a member's part of the workspace
-static int pop_flat_sizes(const char *who, int32_t n_features, int64_t B, int32_t n_members, int max_B, size_t (*floats)(int),
-                          size_t (*stride_of)(int), size_t *trained_floats, size_t *workspace_stride, size_t *workspace_bytes,
-                          int32_t *launches)
+// antsrl_pop_exptrain_sizes and antsrl_pop_jointtrain_sizes: a layer1-trained net's (antsrl_l1train.h), by its descriptor
+template <class Net>
+static int pop_l1t_sizes(const char *who, int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
+                         size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
 {
     int rc = lt_features(who, n_features);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, max_B, POP_ET_LIMIT);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, Net::POP_MAX_B, POP_L1T_LIMIT);
     if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
     if (rc != ANTSRL_OK) return rc;
-    const size_t stride = stride_of((int)B);
-    if (trained_floats) *trained_floats = floats(n_features);
+    const size_t stride = l1t_pop_stride<Net>((int)B);
+    if (trained_floats) *trained_floats = Net::floats(n_features);
     if (workspace_stride) *workspace_stride = stride;
     if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
     if (launches) *launches = 2;
     return ANTSRL_OK;
 }
 
-// The front of antsrl_pop_exptrain_step and antsrl_pop_jointtrain_step, whose Args differ in the target's field alone (the
-// entry sets it, and dh and blocks from its own net's layout): the refusals in the training entries' order, then member
-// 0's minibatch (the slab's arrays, idx, grads, loss; the discount comes from the table; its partials are the front of the
-// workspace, its dh behind them), the model and Adam's moments.
-template <class Args>
-static int pop_flat_step(const char *who, const AntsPopSpec *s, int max_B, float *model, const float *target,
-                         const char *target_name, float *adam_m, float *adam_v, const float *states,
-                         const float *agent_states, const int64_t *actions, const float *rewards, const float *new_states,
-                         const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx, int64_t B,
-                         int64_t step, double beta1, double beta2, double eps, float *grads, float *loss, const double *running_loss, void *workspace, Args *a, PopTable *t)
+// antsrl_pop_exptrain_step and antsrl_pop_jointtrain_step: the refusals in the training entries' order, then member 0's
+// arguments (the slab's arrays, idx, grads, loss; the discount comes from the table; its partials are the front of the
+// workspace, its dh behind them; the model, the target under the name its entry gives it, Adam's moments) and the launches
+template <class Net>
+static int pop_l1t_step(const char *who, const AntsPopSpec *s, float *model, const float *target, float *adam_m, float *adam_v,
+                        const float *states, const float *agent_states, const int64_t *actions, const float *rewards,
+                        const float *new_states, const float *new_agent_states, const uint8_t *dones, int64_t n_rows,
+                        const int64_t *idx, int64_t B, int64_t step, double beta1, double beta2, double eps, float *grads,
+                        float *loss, double *running_loss, int first_loss, void *workspace, void *stream)
 {
+    PopTable t;
+    L1TrainArgs a = {};
     int Em = 0;
-    int rc = pop_spec(who, s, t, &Em);
-    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, max_B, POP_ET_LIMIT);
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, Net::POP_MAX_B, POP_L1T_LIMIT);
     if (rc != ANTSRL_OK) return rc;
     REQUIRE(model, 4);
-    if ((rc = pop_require(who, target_name, target, 4)) != ANTSRL_OK) return rc;
+    if ((rc = require_named(who, Net::TARGET, target, 4)) != ANTSRL_OK) return rc;
     REQUIRE(adam_m, 4);
     REQUIRE(adam_v, 4);
     REQUIRE(idx, 8);
     REQUIRE(workspace, 256);
     rc = dqn_batch(who, s->n_features, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx,
-                   B, 0.0f, grads, false, loss, workspace, &a->batch);
-    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a->adam, t);
+                   B, 0.0f, grads, false, loss, workspace, &a.batch);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
     if (rc != ANTSRL_OK) return rc;
-    a->model = model;
-    a->adam.m = adam_m; a->adam.v = adam_v;
-    return ANTSRL_OK;
+    a.model = model; a.target = target;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    a.dh = (float *)((unsigned char *)workspace + l1t_dh_offset<Net>((int)B));
+    a.blocks = l1t_blocks((int)B);
+    const PopRunningLoss rl = {running_loss, first_loss != 0};
+    return enqueued(Net::launch_pop(a, t, s->n_members, l1t_pop_stride<Net>((int)B), rl, (hipStream_t)stream), who);
 }
 
 extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, const float *agent_state,
@@ -324,8 +317,8 @@ extern "C" int antsrl_pop_explore_policy(const AntsPopSpec *s, const void *obs, 
 extern "C" int antsrl_pop_exptrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
                                          size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
 {
-    return pop_flat_sizes("pop_exptrain_sizes", n_features, B, n_members, POP_ET_MAX_B, antsrl_exptrain_floats,
-                          antsrl_pop_exptrain_stride, trained_floats, workspace_stride, workspace_bytes, launches);
+    return pop_l1t_sizes<ExpNet>("pop_exptrain_sizes", n_features, B, n_members, trained_floats, workspace_stride, workspace_bytes,
+                                 launches);
 }
 
 extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, const float *target, float *adam_m, float *adam_v,
@@ -335,18 +328,9 @@ extern "C" int antsrl_pop_exptrain_step(const AntsPopSpec *s, float *model, cons
                                         double beta1, double beta2, double eps, float *grads, float *loss,
                                         double *running_loss, int first_loss, void *workspace, void *stream)
 {
-    const char *who = "pop_exptrain_step";
-    PopTable t;
-    ExpTrainArgs a = {};
-    const int rc = pop_flat_step(who, s, POP_ET_MAX_B, model, target, "target", adam_m, adam_v, states, agent_states, actions,
-                                 rewards, new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads, loss,
-                                 running_loss, workspace, &a, &t);
-    if (rc != ANTSRL_OK) return rc;
-    a.target = target;
-    a.dh = (float *)((unsigned char *)workspace + antsrl_exptrain_dh_offset((int)B));
-    a.blocks = antsrl_exptrain_blocks((int)B);
-    const PopRunningLoss rl = {running_loss, first_loss != 0};
-    return enqueued(antsrl_launch_pop_exptrain(a, t, s->n_members, antsrl_pop_exptrain_stride((int)B), rl, (hipStream_t)stream), who);
+    return pop_l1t_step<ExpNet>("pop_exptrain_step", s, model, target, adam_m, adam_v, states, agent_states, actions, rewards,
+                                new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads, loss,
+                                running_loss, first_loss, workspace, stream);
 }
 
 // ---- the population of joint agents (antsrl_popjoint.hip) ------------------------------------------------------------------
@@ -373,8 +357,8 @@ extern "C" int antsrl_pop_joint_policy(const AntsPopSpec *s, const void *obs, co
 extern "C" int antsrl_pop_jointtrain_sizes(int32_t n_features, int64_t B, int32_t n_members, size_t *trained_floats,
                                            size_t *workspace_stride, size_t *workspace_bytes, int32_t *launches)
 {
-    return pop_flat_sizes("pop_jointtrain_sizes", n_features, B, n_members, POP_JT_MAX_B, antsrl_jointtrain_floats,
-                          antsrl_pop_jointtrain_stride, trained_floats, workspace_stride, workspace_bytes, launches);
+    return pop_l1t_sizes<JointNet>("pop_jointtrain_sizes", n_features, B, n_members, trained_floats, workspace_stride,
+                                   workspace_bytes, launches);
 }
 
 extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, const float *target_l3, float *adam_m,
@@ -384,18 +368,9 @@ extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, co
                                           double beta1, double beta2, double eps, float *grads, float *loss,
                                           double *running_loss, int first_loss, void *workspace, void *stream)
 {
-    const char *who = "pop_jointtrain_step";
-    PopTable t;
-    JointTrainArgs a = {};
-    const int rc = pop_flat_step(who, s, POP_JT_MAX_B, model, target_l3, "target_l3", adam_m, adam_v, states, agent_states, actions,
-                                 rewards, new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads, loss,
-                                 running_loss, workspace, &a, &t);
-    if (rc != ANTSRL_OK) return rc;
-    a.target_l3 = target_l3;
-    a.dh = (float *)((unsigned char *)workspace + antsrl_jointtrain_dh_offset((int)B));
-    a.blocks = antsrl_jointtrain_blocks((int)B);
-    const PopRunningLoss rl = {running_loss, first_loss != 0};
-    return enqueued(antsrl_launch_pop_jointtrain(a, t, s->n_members, antsrl_pop_jointtrain_stride((int)B), rl, (hipStream_t)stream), who);
+    return pop_l1t_step<JointNet>("pop_jointtrain_step", s, model, target_l3, adam_m, adam_v, states, agent_states, actions,
+                                  rewards, new_states, new_agent_states, dones, n_rows, idx, B, step, beta1, beta2, eps, grads,
+                                  loss, running_loss, first_loss, workspace, stream);
 }
 
 // ---- the population of memory nets (antsrl_popmemtrain.hip) ----------------------------------------------------------------

@@ -48,7 +48,7 @@ struct PopRunningLoss {
 };
 
 // ---- the population of explore agents (antsrl_popexplore.hip; include/antsrl.h, "The population of explore agents") ----
-// A member's net is ExploreTrainer's flat block of antsrl_exptrain_floats(F) floats (antsrl_exptrain.h): model, target,
+// A member's net is ExploreTrainer's flat block of ExpNet::floats(F) floats (antsrl_exptrain.h): model, target,
 // Adam's m and v and grads are [P][floats].  The count is odd for an even F (9603 at F = 294), so a member's block starts
 // 4-byte aligned and no more: every kernel reads and writes the blocks float by float.
 
@@ -56,7 +56,7 @@ struct PopRunningLoss {
 struct PopExplorePolicyArgs {
     const void *obs;          // [P][Mm][F], float32 or bfloat16, dense
     const float *agent_state; // [P][Mm][2]
-    const float *target;      // [P][antsrl_exptrain_floats(F)]
+    const float *target;      // [P][ExpNet::floats(F)]
     int8_t *rot;              // [P][Mm]
     int Mm, F, P;
 };
@@ -74,21 +74,11 @@ static inline int pop_policy_blocks(int Mm, int F, int P, size_t *lds)
     return blocks > cap ? cap : blocks;
 }
 
-// bytes of a member's part of the explore step's workspace: the single step's (partials, then dh [B][32]) rounded up to
-// 256, so that every member's partials and dh start as aligned as the single step's (B * 128 is no multiple of 256 for odd B)
-static inline size_t antsrl_pop_exptrain_stride(int B)
-{
-    return (antsrl_exptrain_dh_offset(B) + (size_t)B * ET_HIDDEN * sizeof(float) + 255) / 256 * 256;
-}
-
+// (the training step is ExpNet::launch_pop, antsrl_exptrain.h; a member's part of its workspace l1t_pop_stride<ExpNet>(B) bytes)
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_explore_policy(const PopExplorePolicyArgs &a, bool obs_bf16, hipStream_t st);
-// a: the single agent's ExpTrainArgs for member 0 (B <= 512: at most four forward workgroups per member; idx [P][B];
-// partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
-ANTSRL_INTERNAL hipError_t antsrl_launch_pop_exptrain(const ExpTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
-                                                      const PopRunningLoss &rl, hipStream_t st);
 
 // ---- the population of joint agents (antsrl_popjoint.hip; include/antsrl.h, "The population of joint agents") ----
-// A member's net is JointTrainer's flat block of antsrl_jointtrain_floats(F) floats (antsrl_jointtrain.h: w1 | b1 | w2 |
+// A member's net is JointTrainer's flat block of JointNet::floats(F) floats (antsrl_jointtrain.h: w1 | b1 | w2 |
 // b2 | w3 | b3): model, Adam's m and v and grads are [P][floats], the target's layer3 [P][99].  Blocks are 4-byte aligned
 // and no more: every kernel reads and writes them float by float.
 
@@ -97,24 +87,14 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_exptrain(const ExpTrainArgs &a, con
 struct PopJointPolicyArgs {
     const void *obs;          // [P][Mm][F], float32 or bfloat16, dense
     const float *agent_state; // [P][Mm][2]
-    const float *model;       // [P][antsrl_jointtrain_floats(F)]
+    const float *model;       // [P][JointNet::floats(F)]
     const float *target_l3;   // [P][99]
     int8_t *rot, *ph;         // [P][Mm]
     int Mm, F, P;
 };
 
-// bytes of a member's part of the joint step's workspace: the single step's (partials, then dh [B][32]) rounded up to
-// 256, as antsrl_pop_exptrain_stride
-static inline size_t antsrl_pop_jointtrain_stride(int B)
-{
-    return (antsrl_jointtrain_dh_offset(B) + (size_t)B * JT_HIDDEN * sizeof(float) + 255) / 256 * 256;
-}
-
+// (the training step is JointNet::launch_pop, antsrl_jointtrain.h; a member's part of its workspace l1t_pop_stride<JointNet>(B) bytes)
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_joint_policy(const PopJointPolicyArgs &a, bool obs_bf16, hipStream_t st);
-// a: the single agent's JointTrainArgs for member 0 (B <= 512: at most four forward workgroups per member; idx [P][B];
-// partials and dh inside member 0's part of the workspace); the table gives discount and step size; two launches
-ANTSRL_INTERNAL hipError_t antsrl_launch_pop_jointtrain(const JointTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
-                                                        const PopRunningLoss &rl, hipStream_t st);
 
 // ---- the population of memory nets (antsrl_popmemtrain.hip; include/antsrl.h, "The population of memory nets") ----
 // A member's net is MemoryTrainer's state buffer (antsrl_memtrain.h: masters | m | v | packs): states and targets are

@@ -18,11 +18,9 @@
 // environment id.  No atomics; no kernel reads what another member's workgroups write.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "antsrl_lds_optin.h"
 #include "antsrl_lintrain_dev.h"
 #include "antsrl_memagent_dev.h"
-#include "antsrl_policy_flat.h"
-#include "antsrl_population.h"
+#include "antsrl_population_dev.h"
 
 // the table is a kernel argument of three kernels, beside the single agent's argument struct
 static_assert(sizeof(PopTable) + sizeof(LinTrainArgs) + sizeof(PopRunningLoss) <= 4096, "k_pop_lintrain's arguments");
@@ -130,18 +128,10 @@ __device__ __forceinline__ LinTrainArgs pop_lintrain_member(const LinTrainArgs &
     a.adam.m = a0.adam.m + member * 2 * LT_HEADS;
     a.adam.v = a0.adam.v + member * 2 * LT_HEADS;
     a.adam.step_size = tab.m[member].step_size;
-    DqnBatch &mb = a.batch;
-    mb.states = a0.batch.states + member * L * F;
-    mb.new_states = a0.batch.new_states + member * L * F;
-    mb.agent_states = a0.batch.agent_states + member * L * 2;
-    mb.new_agent_states = a0.batch.new_agent_states + member * L * 2;
-    mb.actions = a0.batch.actions + member * L * 2;
-    mb.rewards = a0.batch.rewards + member * L;
-    mb.dones = a0.batch.dones + member * L;
-    mb.idx = a0.batch.idx + member * (size_t)a0.batch.B;
-    mb.grads = a0.batch.grads ? a0.batch.grads + member * LT_HEADS : nullptr;
-    mb.loss = a0.batch.loss + member;
-    mb.discount = tab.m[member].discount;
+    pop_ring_member(a.batch, a0.batch, member, L, F);
+    a.batch.grads = a0.batch.grads ? a0.batch.grads + member * LT_HEADS : nullptr;
+    a.batch.loss = a0.batch.loss + member;
+    a.batch.discount = tab.m[member].discount;
     return a;
 }
 
@@ -158,7 +148,8 @@ k_pop_lintrain(const LinTrainArgs a0, const PopTable tab, const PopRunningLoss r
     constexpr int NW = 4;
 #include "antsrl_lintrain_body.inc"
     // main.py:106-109 in float64, antsrl_monitor.hip's arithmetic (each product rounded before the add: the build's
-    // -ffp-contract=off), by the thread that has just written the member's loss
+    // -ffp-contract=off), by the thread that has just written the member's loss.  (pop_l1t_l1_stage has the same four
+    // lines: called from one helper, this kernel's code differs)
     if (rl.running_loss && threadIdx.x == LT_HEADS) {
         const double l = (double)*a.batch.loss;
         rl.running_loss[blockIdx.y] = rl.first ? l : 0.99 * rl.running_loss[blockIdx.y] + 0.01 * l;
@@ -168,18 +159,7 @@ k_pop_lintrain(const LinTrainArgs a0, const PopTable tab, const PopRunningLoss r
 // ------------------------------------------------------------------ launchers (antsrl_population.h)
 hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipStream_t st)
 {
-    if (a.Mm < 1 || a.P < 1 || !pol_flat_fits(a.F)) return hipErrorInvalidValue;
-    const int ks = (a.F + 15) / 16, tile_elems = pol_flat_tile_elems(a.F);
-    size_t lds = 0;
-    const int blocks = pop_policy_blocks(a.Mm, a.F, a.P, &lds); // (antsrl_population.h: the explore population's rule too)
-    const hipError_t e = obs_bf16 ? antsrl_lds_optin<k_pop_policy<true>>(lds) : antsrl_lds_optin<k_pop_policy<false>>(lds);
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)blocks, (unsigned)a.P);
-    if (obs_bf16)
-        hipLaunchKernelGGL(k_pop_policy<true>, grid, dim3(POL_FLAT_THREADS), lds, st, a, ks, tile_elems);
-    else
-        hipLaunchKernelGGL(k_pop_policy<false>, grid, dim3(POL_FLAT_THREADS), lds, st, a, ks, tile_elems);
-    return hipGetLastError();
+    return pop_policy_launch<k_pop_policy<true>, k_pop_policy<false>>(a, obs_bf16, st);
 }
 
 hipError_t antsrl_launch_pop_select(const SelArgs &a, const PopTable &t, int P, int Em, hipStream_t st)

@@ -306,9 +306,10 @@ class MemoryTrainer(_MemoryBlocks, _DqnTrainer):
 class _FlatTrainer(_DqnTrainer):
     """What the linear, the explore, the joint and the rework trainer share on top of _DqnTrainer: their entries antsrl_<entry>_sizes
     / _grad / _apply / _step take one argument order behind the net's own leading arguments (include/antsrl.h), so the
-    three stages are written once.  A subclass names its `entry`, writes `_sizes`, gives `_net()` (what _grad and _step
-    take in front of the arrays) and `_apply_net()` (what _apply takes in front of Adam's m), keeps Adam's moments in
-    `_adam` [2][P] (`_alloc_trained`) and overrides `_weights_changed` when a training step moves its acting weights.
+    three stages and `_sizes` are written once.  A subclass names its `entry`, gives `_net()` (what _grad and _step take
+    in front of the arrays), keeps Adam's moments in `_adam` [2][P] (`_alloc_trained`) and overrides `_weights_changed`
+    when a training step moves its acting weights, `_lead()` when its entries' leading argument is not n_features, and
+    `_apply_net()` (what _apply takes in front of Adam's m) when its net is not one block `model`.
 
     sync_target and load_state_dict are written once too: a subclass gives `_copy_target()`, what its target net owns
     following the model, and `_rename(sd)`, a state_dict under the names of its views.  `version` counts the changes of
@@ -323,8 +324,16 @@ class _FlatTrainer(_DqnTrainer):
     def _net(self) -> tuple:
         raise NotImplementedError
 
+    def _lead(self):
+        """The leading argument of every entry."""
+        return self.n_features
+
     def _apply_net(self) -> tuple:
-        raise NotImplementedError
+        return self._lead(), _p(self.model)
+
+    def _sizes(self, B, workspace_bytes, launches):
+        name = "%s_sizes" % self.entry
+        _lib.check(getattr(self._lib, "antsrl_" + name)(self._lead(), B, None, workspace_bytes, launches), name)
 
     def _copy_target(self) -> None:
         raise NotImplementedError
@@ -531,9 +540,6 @@ class LinearTrainer(_CollectTrainer):
         return linear_trained_views(self.grads if grads is None else grads)
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    def _sizes(self, B, workspace_bytes, launches):
-        _lib.check(self._lib.antsrl_lintrain_sizes(self.n_features, B, None, workspace_bytes, launches), "lintrain_sizes")
-
     def _net(self) -> tuple:
         p = self.policy
         return self.n_features, _p(p.w1), _p(p.b1), _p(self.heads), _p(self.target_l3)
@@ -592,14 +598,8 @@ class ExploreTrainer(_FlatTrainer):
         self.target.copy_(self.model)
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    def _sizes(self, B, workspace_bytes, launches):
-        _lib.check(self._lib.antsrl_exptrain_sizes(self.n_features, B, None, workspace_bytes, launches), "exptrain_sizes")
-
     def _net(self) -> tuple:
         return self.n_features, _p(self.model), _p(self.target)
-
-    def _apply_net(self) -> tuple:
-        return self.n_features, _p(self.model)
 
 
 class JointTrainer(_CollectTrainer):
@@ -652,14 +652,8 @@ class JointTrainer(_CollectTrainer):
         self.target_l3.copy_(self.model[self._l3])
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    def _sizes(self, B, workspace_bytes, launches):
-        _lib.check(self._lib.antsrl_jointtrain_sizes(self.n_features, B, None, workspace_bytes, launches), "jointtrain_sizes")
-
     def _net(self) -> tuple:
         return self.n_features, _p(self.model), _p(self.target_l3)
-
-    def _apply_net(self) -> tuple:
-        return self.n_features, _p(self.model)
 
     def _weights_changed(self) -> None:
         self.version += 1  # every step moves the live layer1 and layer2
@@ -714,12 +708,8 @@ class ReworkTrainer(_FlatTrainer):
         self.policy.recollapse()
 
     # ---- the stages ---------------------------------------------------------------------------------------------
-    def _sizes(self, B, workspace_bytes, launches):
-        _lib.check(self._lib.antsrl_reworktrain_sizes(C.byref(self.shape), B, None, workspace_bytes, launches),
-                   "reworktrain_sizes")
+    def _lead(self):
+        return C.byref(self.shape)
 
     def _net(self) -> tuple:
-        return C.byref(self.shape), _p(self.model), _p(self.policy.collapsed)
-
-    def _apply_net(self) -> tuple:
-        return C.byref(self.shape), _p(self.model)
+        return self._lead(), _p(self.model), _p(self.policy.collapsed)
