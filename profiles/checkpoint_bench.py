@@ -20,11 +20,12 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
@@ -32,20 +33,9 @@ from antsrl_amd.checkpoint import checkpoint_map  # noqa: E402
 from bench import CONFIGS, device_identity  # noqa: E402
 
 
-def timed(fns, iters, warmup=3):
-    """ms per call of each fn in `fns`, alternating them inside one timed loop (one event pair per call)."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for _ in fns]
-    for i in range(iters):
-        for k, fn in enumerate(fns):
-            ev[k][i][0].record()
-            fn()
-            ev[k][i][1].record()
-    torch.cuda.synchronize()
-    return [float(np.median([a.elapsed_time(b) for a, b in row])) for row in ev]
+def timed(fns, iters):
+    """Median ms per call of each fn in `fns`, alternating them inside one timed loop."""
+    return BL.median(BL.per_call(fns, iters, 3)).tolist()
 
 
 def run(name, iters):

@@ -18,19 +18,18 @@ own; five rounds; the median over the rounds and their spread, (max - min) / med
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
+from antsrl_amd.agent import MemoryAgent, ReworkAgent  # noqa: E402
 from antsrl_amd.monitor import EpisodeMonitor  # noqa: E402
 from antsrl_amd.stats import EpisodeStats  # noqa: E402
 
@@ -39,19 +38,10 @@ EVERY, ROUNDS = 50, 5
 
 def setup(config):
     if config == "c5":
-        from rework_agent_bench import agent_on, c5_env
-        env = c5_env("bfloat16")
-        return env, agent_on(env, True)
-    from antsrl_amd.agent import MemoryAgent
-    from memory_agent_bench import c3_env
-    env = c3_env()
-    ag = MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1)
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(20):  # fill the ring past min_replay: every timed step trains
-        ag.rollout_step(env)
-    return env, ag
+        env = BL.c5_env(torch.bfloat16)
+        return env, BL.warmed(ReworkAgent(epsilon=0.1, record_per_step=4096, min_replay=1000, seed=1, fused_select=True), env)
+    env = BL.c3_env()  # 20 steps fill the ring past min_replay: every timed step trains
+    return env, BL.warmed(MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1), env, steps=20)
 
 
 def host_path(env):
@@ -64,25 +54,9 @@ def host_path(env):
     return [t.cpu() for t in out]
 
 
-def blocks(fns, rounds=ROUNDS, warmup=1):
+def blocks(fns):
     """Per fn: (median over the rounds of the ms per call, spread); one event pair around one call, the fns alternate."""
-    for fn in fns:
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in fns] for _ in range(rounds)]
-    for r in range(rounds):
-        for k, fn in enumerate(fns):
-            ev[r][k][0].record()
-            fn()
-            ev[r][k][1].record()
-    torch.cuda.synchronize()
-    out = []
-    for k in range(len(fns)):
-        ms = [ev[r][k][0].elapsed_time(ev[r][k][1]) for r in range(rounds)]
-        med = float(np.median(ms))
-        out.append((med, (max(ms) - min(ms)) / med))
-    return out
+    return BL.median_spread(BL.per_block(fns, 1, rounds=ROUNDS, warmup=1))
 
 
 def bench_loop(config):
@@ -163,18 +137,12 @@ def main():
         env = BatchedAntsEnv(cfg)
         env.reset(synth_init(cfg, seed=3))
         out = dict(device=torch.cuda.get_device_name(0), shape=[E, W, H], row_alone=bench_alone(env, EpisodeStats(env, 1), args.iters))
-        if args.json:
-            with open(args.json, "w") as f:
-                json.dump(out, f, indent=1)
-        print(json.dumps(out))
-        return
+        return BL.write_json(out, args.json)
     loop, env, stats = bench_loop(args.config)
     alone = bench_alone(env, stats, args.iters)
     alone["row_over_step"] = alone["row_ms"] / loop["step_ms"]
     out = dict(device=torch.cuda.get_device_name(0), config=args.config, rounds=ROUNDS, loop=loop, row_alone=alone)
-    with open(args.json or os.path.join(ROOT, "profiles", "colony_stats_%s.json" % args.config), "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json or os.path.join(ROOT, "profiles", "colony_stats_%s.json" % args.config))
 
 
 if __name__ == "__main__":

@@ -18,31 +18,37 @@ a speed-up: the hook is extra work by construction, and the figures say what it 
     python profiles/custom_reward_bench.py [--iters 60] [--json profiles/custom_reward_c5.json]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
-from joint_agent_bench import timed  # noqa: E402
-from linear_agent_bench import E, M, N, agent_on, c5_env  # noqa: E402
+from antsrl_amd.agent import CollectAgent  # noqa: E402
+from benchlib import M  # noqa: E402
+
+
+def timed(fns, iters):
+    """Per fn in `fns`, [median, 10th percentile, 90th percentile] ms per call, alternating them inside one timed loop."""
+    return BL.p50_p10_p90(BL.per_call(fns, iters, 10)).tolist()
+
+
+def c5_env():
+    return BL.c5_env(torch.bfloat16, cm.ACT_CELL_META)
 
 
 def hook_env():
     """c5_env with the reward left to a hook: REWARD_NONE, and a threshold the kernels' own give_reward never passes."""
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0, act_path=cm.ACT_CELL_META, reward_kind=cm.REWARD_NONE,
-                      reward_threshold=float("inf"))
-    env = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)
-    env.reset(synth_init(cfg, seed=3))
-    return env
+    return BL.c5_env(torch.bfloat16, cm.ACT_CELL_META, reward_kind=cm.REWARD_NONE, reward_threshold=float("inf"))
+
+
+def agent_on(env, K):
+    return BL.warmed(CollectAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, inloop=False), env)
 
 
 class VisitsHook:
@@ -90,7 +96,7 @@ def bench_rollout(iters, K=4096):
     envs = [c5_env(), hook_env(), hook_env()]
     envs[1].set_reward_hook(VisitsHook(envs[1]), 0.3)
     envs[2].set_reward_hook(holding_hook, 0.0, coords=False)
-    agents = [agent_on(e, False, K) for e in envs]
+    agents = [agent_on(e, K) for e in envs]
     fns = [(lambda a=a, e=e: a.rollout_step(e)) for a, e in zip(agents, envs)]
     (t0, *s0), (t1, *s1), (t2, *s2) = timed(fns, iters)
     return dict(shape="512 x 512 ants, 256 x 256, bf16 observations", K=K, minibatch=264, unhooked_rollout_step_ms=t0,
@@ -115,9 +121,7 @@ def main():
         print("rollout_step un-hooked %.3f ms, hooked with coordinates %.3f ms (+ %.3f), hooked without %.3f ms (+ %.3f)"
               % (r["unhooked_rollout_step_ms"], r["hooked_coords_rollout_step_ms"], r["coords_hook_over_unhooked_ms"],
                  r["hooked_nocoords_rollout_step_ms"], r["nocoords_hook_over_unhooked_ms"]), flush=True)
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

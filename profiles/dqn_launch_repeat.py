@@ -13,8 +13,9 @@ import sys
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
 
+import benchlib as BL  # noqa: E402
 import linear_train_cases as K  # noqa: E402
 import linear_train_ref as L  # noqa: E402
 
@@ -41,13 +42,8 @@ def main():
     events = [(int(i), int(w)) for i, w in bad.nonzero().tolist()]
     print("library %s: %d of %d launches hold a workgroup whose partials differ from the mode; (launch, workgroup) %s%s"
           % (_lib.LIB_PATH, int(bad.any(1).sum()), n, events[:24], " ..." if len(events) > 24 else ""))
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(100)]
-    for a, b in ev:
-        a.record()
-        tr.grad(arrays, idx)
-        b.record()
-    torch.cuda.synchronize()
-    print("grad() at F = %d, B = %d: median %.4f ms over 100" % (case["F"], B, sorted(a.elapsed_time(b) for a, b in ev)[50]))
+    ms = BL.per_call([lambda: tr.grad(arrays, idx)], 100, 0)[0]  # (the launches above are the warm-up)
+    print("grad() at F = %d, B = %d: median %.4f ms over 100" % (case["F"], B, sorted(ms)[50]))
 
 
 if __name__ == "__main__":

@@ -16,32 +16,33 @@ method).  One process.
     python profiles/episode_recorder_bench.py [--iters 100] [--snapshot-iters 10] [--json profiles/episode_recorder_c5.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from antsrl_amd import config as cm  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
+import benchlib as BL  # noqa: E402
+from antsrl_amd.agent import ReworkAgent  # noqa: E402
 from antsrl_amd.monitor import EpisodeMonitor  # noqa: E402
 from antsrl_amd.recorder import EpisodeRecorder  # noqa: E402
 from antsrl_amd.snapshot import snapshot_batched  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
-from rework_agent_bench import E, M, N, ROUNDS, agent_on  # noqa: E402
+from benchlib import E, M, N  # noqa: E402
 
-EVERY, MAX_REPORTS, WARMUP = 50, 64, 5
+EVERY, MAX_REPORTS, WARMUP, ROUNDS = 50, 64, 5, 5
 
 
 def timed_rounds(cases, warmup=WARMUP):
     """cases: [(fn, iters, wall)].  Per case (median ms per call over ROUNDS, spread): device events around the calls, or,
-    for a case that synchronises by itself (wall), the host's clock between two device synchronisations."""
+    for a case that synchronises by itself (wall), the host's clock between two device synchronisations.
+
+    The one private timing loop left beside benchlib's two: it synchronises before every block, so that the host's clock
+    starts on an idle device, and reads that clock around the same block; benchlib.per_block does neither, and taking both
+    in would make it the longer and the less plain of the two."""
     for fn, _, _ in cases:
         for _ in range(warmup):
             fn()
@@ -59,7 +60,7 @@ def timed_rounds(cases, warmup=WARMUP):
             torch.cuda.synchronize()
             t1 = time.perf_counter()
             ms[k].append((t1 - t0) * 1e3 / iters if wall else e0.elapsed_time(e1) / iters)
-    return [(float(np.median(m)), (max(m) - min(m)) / float(np.median(m))) for m in ms]
+    return BL.median_spread(np.array(ms))
 
 
 def main():
@@ -68,15 +69,13 @@ def main():
     ap.add_argument("--snapshot-iters", type=int, default=10)
     ap.add_argument("--json", default=os.path.join(ROOT, "profiles", "episode_recorder_c5.json"))
     args = ap.parse_args()
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0)
-    init = synth_init(cfg, seed=3)
     envs, ags, mons = [], [], []
     for _ in range(4):
-        env = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)
-        env.reset(init)
+        env = BL.c5_env(torch.bfloat16)
         envs.append(env)
-        ags.append(agent_on(env, True))
+        ags.append(BL.warmed(ReworkAgent(epsilon=0.1, record_per_step=4096, min_replay=1000, seed=1, fused_select=True), env))
         mons.append(EpisodeMonitor(env, report_every=EVERY, max_reports=MAX_REPORTS, max_episodes=1))
+    cfg = envs[0].cfg
     assert (WARMUP + ROUNDS * args.iters) // EVERY <= MAX_REPORTS
     rec = EpisodeRecorder(envs[1], env_indices=(0,), max_frames=WARMUP + ROUNDS * args.iters)
     rec.begin()
@@ -117,9 +116,7 @@ def main():
                            step_snapshot_batched="host clock between device synchronisations"))
     print("  ".join("%s %.4f ms (spread %.1f %%)" % (n, t, 100 * s) for n, (t, s) in zip(names, ts)), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

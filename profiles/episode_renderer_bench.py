@@ -24,12 +24,12 @@ import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 import render_ref as RR  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
@@ -43,22 +43,9 @@ N, ZOOM, ROUNDS, WARMUP = 512, 3, 5, 2
 
 
 def timed(fns, iters):
-    """Median ms per call over ROUNDS and the spread, per function; the functions alternate inside a round."""
-    for fn in fns:
-        for _ in range(WARMUP):
-            fn()
-    torch.cuda.synchronize()
-    ms = [[] for _ in fns]
-    for _ in range(ROUNDS):
-        for k, fn in enumerate(fns):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(iters):
-                fn()
-            e1.record()
-            torch.cuda.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / iters)
-    return [(float(np.median(m)), float((max(m) - min(m)) / np.median(m))) for m in ms]
+    """Median ms per call over ROUNDS and the spread, per function; the functions alternate inside a round, a synchronise
+    after every block."""
+    return BL.median_spread(BL.per_block(fns, iters, rounds=ROUNDS, warmup=WARMUP, sync_blocks=True))
 
 
 def main():

@@ -14,19 +14,28 @@ The method is profiles/linear_agent_bench.py's: hipEvents around `--iters` warme
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/explore_agent_bench.py --probe 40   # launches per step
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
+from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import ExploreAgent  # noqa: E402
 from antsrl_amd.train import ExploreTrainer  # noqa: E402
-from linear_agent_bench import E, F, M, N, c5_env, timed  # noqa: E402
+from benchlib import E, F, M, N  # noqa: E402
+
+
+def timed(fns, iters):
+    """Median ms per call of each fn in `fns`, alternating them inside one timed loop."""
+    return BL.median(BL.per_call(fns, iters, 10)).tolist()
+
+
+def c5_env():
+    return BL.c5_env(torch.bfloat16, cm.ACT_CELL_META)
 
 
 class EagerRef(torch.nn.Module):
@@ -77,13 +86,7 @@ def bench_train(B, iters):
 
 
 def agent_on(env, inloop, K=4096):
-    ag = ExploreAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, inloop=inloop)
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(3):
-        ag.rollout_step(env)  # past min_replay: every further step trains
-    return ag
+    return BL.warmed(ExploreAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, inloop=inloop), env)
 
 
 def bench_rollout(iters, K=4096):
@@ -145,9 +148,7 @@ def main():
         print("rollout_step %.3f ms (inloop %.3f ms, %d hits in %d steps), sum of parts %.3f ms, gap %.3f ms; parts: %s"
               % (r["rollout_step_ms"], r["rollout_step_inloop_ms"], r["inloop_hits"], r["inloop_steps"], r["sum_of_parts_ms"],
                  r["gap_ms"], ", ".join("%s %.3f" % kv for kv in r["parts_ms"].items())), flush=True)
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

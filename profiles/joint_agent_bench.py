@@ -14,41 +14,29 @@ one process, medians; the spread of each (10th and 90th percentile) is reported 
     python profiles/joint_agent_bench.py [--iters 60] [--json profiles/joint_agent_c5.json]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
+from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import CollectAgent  # noqa: E402
 from antsrl_amd.train import JointTrainer, LinearTrainer  # noqa: E402
-from linear_agent_bench import EagerRef as FrozenEagerRef  # noqa: E402
-from linear_agent_bench import F, M, c5_env  # noqa: E402
+from benchlib import F, M  # noqa: E402
+from linear_agent_bench import EagerRef as FrozenEagerRef  # noqa: E402  (a model, not harness: the one import between benches)
 
 
-def timed(fns, iters, warmup=10):
-    """Per fn in `fns`, (median, 10th percentile, 90th percentile) ms per call, alternating them inside one timed loop."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for _ in fns]
-    for i in range(iters):
-        for k, fn in enumerate(fns):
-            ev[k][i][0].record()
-            fn()
-            ev[k][i][1].record()
-    torch.cuda.synchronize()
-    out = []
-    for row in ev:
-        t = [a.elapsed_time(b) for a, b in row]
-        out.append(tuple(float(np.percentile(t, q)) for q in (50, 10, 90)))
-    return out
+def timed(fns, iters):
+    """Per fn in `fns`, [median, 10th percentile, 90th percentile] ms per call, alternating them inside one timed loop."""
+    return BL.p50_p10_p90(BL.per_call(fns, iters, 10)).tolist()
+
+
+def c5_env():
+    return BL.c5_env(torch.bfloat16, cm.ACT_CELL_META)
 
 
 class EagerRef(FrozenEagerRef):
@@ -81,13 +69,7 @@ def bench_train(B, iters):
 
 
 def agent_on(env, train_layer1, K=4096):
-    ag = CollectAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, train_layer1=train_layer1)
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(3):
-        ag.rollout_step(env)  # past min_replay: every further step trains
-    return ag
+    return BL.warmed(CollectAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, train_layer1=train_layer1), env)
 
 
 def bench_rollout(iters, K=4096):
@@ -117,9 +99,7 @@ def main():
         out["rollout"] = r
         print("rollout_step %.3f ms, frozen %.3f ms (x %.3f)" % (r["rollout_step_ms"], r["frozen_rollout_step_ms"], r["ratio"]),
               flush=True)
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

@@ -15,23 +15,19 @@ hipEvents around `--iters` warmed iterations, medians.  Prints one line per case
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/linear_agent_bench.py --probe 40   # launches per step
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import CollectAgent  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
 from antsrl_amd.train import LinearTrainer  # noqa: E402
-
-E, N, F = 512, 512, 294
+from benchlib import E, F, M, N  # noqa: E402
 
 #: what `pytest -s tests/test_gpu_linear_agent.py` printed on an MI355X, and the bounds the tests hold (about 4 x): the
 #: kernel against the device-contract restatement (B <= 4096 / B = 65 536), and against the reference's recorded run
@@ -43,23 +39,11 @@ TEST_ERRORS = dict(
                       one_minus_cosine_gradient=dict(measured=2.0e-6, bound=8e-6),
                       one_minus_cosine_delta=dict(measured=4.0e-5, bound=1.6e-4)),
     acting=dict(decisions_left_out=5, decisions=512, cap=0.01))
-M = E * N
 
 
-def timed(fns, iters, warmup=10):
-    """ms per call of each fn in `fns`, alternating them inside one timed loop (one event pair per call)."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for _ in fns]
-    for i in range(iters):
-        for k, fn in enumerate(fns):
-            ev[k][i][0].record()
-            fn()
-            ev[k][i][1].record()
-    torch.cuda.synchronize()
-    return [float(np.median([a.elapsed_time(b) for a, b in row])) for row in ev]
+def timed(fns, iters):
+    """Median ms per call of each fn in `fns`, alternating them inside one timed loop."""
+    return BL.median(BL.per_call(fns, iters, 10)).tolist()
 
 
 class EagerRef(torch.nn.Module):
@@ -116,20 +100,11 @@ def bench_train(B, iters):
 
 
 def c5_env():
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0, act_path=cm.ACT_CELL_META)
-    env = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)
-    env.reset(synth_init(cfg, seed=3))
-    return env
+    return BL.c5_env(torch.bfloat16, cm.ACT_CELL_META)
 
 
 def agent_on(env, inloop, K=4096):
-    ag = CollectAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, inloop=inloop)
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(3):
-        ag.rollout_step(env)  # past min_replay: every further step trains
-    return ag
+    return BL.warmed(CollectAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, inloop=inloop), env)
 
 
 def bench_rollout(iters, K=4096):
@@ -195,9 +170,7 @@ def main():
         print("rollout_step %.3f ms (inloop %.3f ms), sum of parts %.3f ms, gap %.3f ms; parts: %s"
               % (r["rollout_step_ms"], r["rollout_step_inloop_ms"], r["sum_of_parts_ms"], r["gap_ms"],
                  ", ".join("%s %.3f" % kv for kv in r["parts_ms"].items())), flush=True)
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

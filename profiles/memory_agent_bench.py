@@ -25,43 +25,28 @@ hipEvents around `--iters` warmed iterations.  Prints one line per case and a JS
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
-from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import MemoryAgent  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
 from antsrl_amd.replay import DeviceReplayMemory  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
+from benchlib import C3_E as E, C3_N as N, F  # noqa: E402
 from memory_agent_ref import sample_indices  # noqa: E402
 
-E, N, P, MEM = 1024, 512, (7, 7, 6), 20
-M, F = E * N, 294
+P, MEM = (7, 7, 6), 20
+M = E * N
 
 
-def timed(fns, iters, warmup=10):
-    """ms per call of each fn in `fns`, alternating them inside one timed loop (one event pair per call)."""
-    for _ in range(warmup):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)] for _ in fns]
-    for i in range(iters):
-        for k, fn in enumerate(fns):
-            ev[k][i][0].record()
-            fn()
-            ev[k][i][1].record()
-    torch.cuda.synchronize()
-    return [float(np.median([a.elapsed_time(b) for a, b in row])) for row in ev]
+def timed(fns, iters):
+    """Median ms per call of each fn in `fns`, alternating them inside one timed loop."""
+    return BL.median(BL.per_call(fns, iters, 10)).tolist()
 
 
 def record_bytes(K):
@@ -112,13 +97,6 @@ def bench_record(K, ring, iters):
     t_copy = copy_ms(by // 2, iters)  # a copy of n bytes moves 2 n
     return dict(K=K, ring=ring, record_ms=t_new, clone_extend_ms=t_old, speedup=t_old / t_new, bytes=by,
                 gbytes_per_s=by / t_new * 1e-6, copy_ms_same_bytes=t_copy, fraction_of_copy_rate=t_copy / t_new)
-
-
-def c3_env():
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0)
-    env = BatchedAntsEnv(cfg)
-    env.reset(synth_init(cfg, seed=3))
-    return env
 
 
 def bench_skip(env, ag, epsilons, iters):
@@ -172,7 +150,7 @@ def main():
     ap.add_argument("--skip-explored", action="store_true", help="with --probe: the agent runs with skip_explored=True")
     ap.add_argument("--probe", type=int, default=0, help="run this many rollout_steps at K = 4096 and exit (for rocprofv3)")
     a = ap.parse_args()
-    env = c3_env()
+    env = BL.c3_env()
     ag = MemoryAgent(epsilon=0.1, discount=0.99, learning_rate=1e-5, record_per_step=4096, seed=1,
                      skip_explored=a.skip_explored)
     ag.setup(env)
@@ -186,10 +164,7 @@ def main():
     out = dict(device=torch.cuda.get_device_name(0), iters=a.iters, batch=[E, N], n_features=F)
     if a.epsilon is not None:
         out["skip_explored"] = bench_skip(env, ag, a.epsilon or [0.0, 0.1, 0.5, 0.9, 1.0], a.iters)
-        print(json.dumps(out))
-        with open(a.json or os.path.join(ROOT, "profiles", "memory_agent_skip_c3.json"), "w") as f:
-            json.dump(out, f, indent=1)
-        return
+        return BL.write_json(out, a.json or os.path.join(ROOT, "profiles", "memory_agent_skip_c3.json"))
     out["record"] = [bench_record(M, M, max(20, a.iters // 4)), bench_record(4096, 50000, a.iters)]
     for r in out["record"]:
         print("record K = %6d: pre + post %.4f ms | clone + extend %.4f ms (%.1fx) | %.0f MB at %.0f GB/s = %.2f of the "
@@ -229,10 +204,7 @@ def main():
                           parts_sum_ms=sum(t_parts.values()) + t_parts["record_pre"])
     print("rollout_step %.4f ms | parts %s (record_post ~ record_pre) sum %.4f ms" % (
         t_step, {k: round(v, 4) for k, v in t_parts.items()}, out["rollout"]["parts_sum_ms"]), flush=True)
-    print(json.dumps(out))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
+    BL.write_json(out, a.json)
 
 
 if __name__ == "__main__":

@@ -10,15 +10,16 @@ line per case and a JSON summary.
 FLOP count: 2 x (multiply-adds of the twelve layers at their real widths) per ant.  The MFMA peaks of the MI355X are
 2.5 PFLOP/s for bf16 operands and 157.3 TFLOP/s for fp32 operands (dense)."""
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 import torch.nn.functional as Fn  # noqa: E402
+
+import benchlib as BL  # noqa: E402
 
 from antsrl_amd.policy import MEMNET_LAYERS, MemoryPolicy, memnet_param_shapes  # noqa: E402
 
@@ -54,16 +55,8 @@ def eager_fp32(W, obs, ast, mem):
 
 
 def time_ms(fn, iters):
-    for _ in range(3):
-        fn()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
+    """ms per call of fn: one event pair around `iters` warmed calls."""
+    return float(BL.per_block([fn], iters, warmup=3)[0, 0])
 
 
 def main():
@@ -106,10 +99,7 @@ def main():
                       "torch %s %.3f ms (x%.2f)" % (prec, power, mem_size, name, ms, tf, 100 * tf / peak, prec, obs_gbs, prec,
                                                      me, me / ms), flush=True)
             del pol
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

@@ -17,21 +17,21 @@ weights in bf16 plus Adam's fp32 p, m, v, g traffic.  Peaks: 2.5 PFLOP/s bf16 MF
     rocprofv3 --kernel-trace --stats -d DIR -o run -- python profiles/memory_train_bench.py --probe hip     # launches
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 import torch.nn.functional as Fn  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd.policy import MEMNET_LAYERS, memnet_param_shapes  # noqa: E402
 from antsrl_amd.train import MemoryTrainer  # noqa: E402
+from benchlib import F  # noqa: E402
 
 PEAK_TFLOPS, PEAK_TBS = 2500.0, 8.0
-F = 294
 
 
 def batch(N, mem, seed=0):
@@ -87,17 +87,9 @@ class TorchTrain:
         return loss.detach()
 
 
-def timed(fn, iters, warmup=5):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
+def timed(fn, iters):
+    """ms per call of fn: one event pair around `iters` warmed calls."""
+    return float(BL.per_block([fn], iters, warmup=5)[0, 0])
 
 
 def shape_costs(power, mem, B):
@@ -151,10 +143,7 @@ def main():
                                                                row["hip_pct_peak_bytes"]), flush=True)
             del tr, b
     out = dict(device=torch.cuda.get_device_name(0), iters=a.iters, results=res)
-    print(json.dumps(out))
-    if a.json:
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
+    BL.write_json(out, a.json)
 
 
 if __name__ == "__main__":

@@ -25,27 +25,26 @@ line per configuration and a JSON summary.
 """
 import argparse
 import ctypes
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from bench import device_identity  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd.agent import CollectAgent, ExploreAgent  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
 from antsrl_amd.population import PopulationAgent, PopulationExploreAgent, PopulationJointAgent  # noqa: E402
 from antsrl_amd.replay import DeviceReplayMemory  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
 from antsrl_amd.train import ExploreTrainer, JointTrainer, LinearTrainer  # noqa: E402
+from benchlib import E, F, N  # noqa: E402
 
-E, N, F, K, RING, MIN_REPLAY = 512, 512, 294, 4096, 20000, 1000
+K, RING, MIN_REPLAY = 4096, 20000, 1000
 NAMES = ("rollout_step", "policy", "select", "record", "train")
 #: per kind: the single agent, the population, the single trainer, whether the net has a pheromone head (without one the
 #: environment is stepped and the ring written with None), the minibatch and the default JSON file; single_kw: what the
@@ -58,37 +57,21 @@ KINDS = dict(collect=dict(single=CollectAgent, population=PopulationAgent, train
                         pheromone=True, B=264, json="population_joint_c5.json"))
 
 
-def timed(fn, iters, warmup=5):
+def timed(fn, iters):
     """Median ms per call of fn (one event pair per call)."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
-    for a, b in ev:
-        a.record()
-        fn()
-        b.record()
-    torch.cuda.synchronize()
-    return float(np.median([a.elapsed_time(b) for a, b in ev]))
+    return float(BL.median(BL.per_call([fn], iters, 5)[0]))
 
 
 def figures(fns, iters, repeats):
     """fns: the five callables in NAMES' order -> dict(ms: name -> the median of the repeats' medians, spread_ms: name ->
     their max - min).  A repeat times all five before the next one starts."""
-    a = np.array([[timed(fn, iters) for fn in fns] for _ in range(repeats)])
-    return dict(ms=dict(zip(NAMES, (float(x) for x in np.median(a, axis=0)))),
-                spread_ms=dict(zip(NAMES, (float(x) for x in a.max(axis=0) - a.min(axis=0)))))
+    a = np.array([[timed(fn, iters) for fn in fns] for _ in range(repeats)]).T  # [fn, repeat]
+    return dict(ms=dict(zip(NAMES, BL.median(a).tolist())), spread_ms=dict(zip(NAMES, BL.abs_spread(a).tolist())))
 
 
 def bench_single(kind, env, iters, repeats):
-    ag = kind["single"](epsilon=0.1, record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1,
-                        **kind.get("single_kw", {}))
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(3):
-        ag.rollout_step(env)  # past min_replay: every further step trains
-    assert ag.trainer.step_count > 0
+    ag = BL.warmed(kind["single"](epsilon=0.1, record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1,
+                                  **kind.get("single_kw", {})), env)
     rot, ph = (None if t is None else t.clone().view(-1) for t in ag.get_action(env.obs, env.agent_state, False, env=env))
     rm, kw = ag.replay_memory, ag._record_kw()
     idx = torch.randint(0, len(rm), (kind["B"],), device="cuda")
@@ -101,17 +84,12 @@ def bench_single(kind, env, iters, repeats):
 
 
 def members(P):
-    return [dict(epsilon=0.1, discount=0.5 + 0.49 * p / max(1, P - 1), learning_rate=1e-4 * (1 + p % 4), seed=1 + p) for p in range(P)]
+    return BL.members(P, 1e-4)
 
 
 def bench_population(kind, env, P, iters, repeats):
-    pop = kind["population"](members(P), record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1)
-    pop.setup(env)
-    pop.initialize(env)
-    env.observe()
-    for _ in range(3):
-        pop.rollout_step(env)
-    assert pop.trainer.step_count > 0
+    pop = BL.warmed(kind["population"](members(P), record_per_step=K, replay_size=RING, min_replay=MIN_REPLAY, minibatch=kind["B"], seed=1),
+                    env)
     rm, spec = pop.replay_memory, pop._spec()
     idx = torch.randint(0, len(rm), (P, kind["B"]), device="cuda")
     ph = pop._ph if kind["pheromone"] else None
@@ -222,9 +200,7 @@ def main():
     kind = KINDS[args.agent]
     sizes, seq_sizes = ([int(x) for x in v.split(",") if x] for v in (args.members, args.sequential))
     assert set(seq_sizes) <= set(sizes), "--sequential names sizes that --members does not"
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0, act_path=cm.ACT_CELL_META)
-    env = BatchedAntsEnv(cfg, obs_dtype=torch.bfloat16)
-    env.reset(synth_init(cfg, seed=3))
+    env = BL.c5_env(torch.bfloat16, cm.ACT_CELL_META)
     out = dict(device=device_identity(torch, torch.cuda.current_device()), agent=args.agent, iters=args.iters, repeats=args.repeats,
                shape="512 x 512 ants, 256 x 256, bf16 observations, K = %d per member, B = %d, ring %d rows per member" % (K, kind["B"], RING),
                figures="ms: median over the repeats of the median of `iters` calls; spread_ms: max - min over the repeats")
@@ -252,9 +228,7 @@ def main():
         print("sequential P = %2d (population : sequential = %.3f, train %.3f; below by three spreads: %s): %s"
               % (P, r["population_to_sequential"]["rollout_step"], r["population_to_sequential"]["train"],
                  r["below_by_three_spreads"], line(r)), flush=True)
-    with open(args.json or os.path.join(ROOT, "profiles", kind["json"]), "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json or os.path.join(ROOT, "profiles", kind["json"]))
 
 
 if __name__ == "__main__":

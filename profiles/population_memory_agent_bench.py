@@ -22,33 +22,24 @@ JSON line.  Without a GPU it exits with an error.
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-E, N, W, F, POWER, MEM, K, B, RING, MIN_REPLAY = 1024, 512, 256, 294, 5, 20, 4096, 264, 20000, 1000
+import benchlib as BL  # noqa: E402
+from benchlib import C3_E as E, C3_N as N, CELLS as W, F  # noqa: E402
+
+POWER, MEM, K, B, RING, MIN_REPLAY = 5, 20, 4096, 264, 20000, 1000
 NAMES = ("rollout_step", "policy", "select", "record", "train")
 
 
 def members(P):
-    return [dict(epsilon=0.1, discount=0.5 + 0.49 * p / max(1, P - 1), learning_rate=1e-5 * (1 + p % 4), seed=1 + p) for p in range(P)]
-
-
-def per_call_us(fn, calls):
-    """µs per call of fn: two device events around `calls` consecutive calls."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(calls):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1000.0 / calls
+    return BL.members(P, 1e-5)
 
 
 def make_env(cm, BatchedAntsEnv, n_envs, init, base=0):
@@ -65,14 +56,9 @@ class Lone:
         from antsrl_amd import _lib
         from antsrl_amd.agent import MemoryAgent
         self.env, self.lib = env, lib
-        ag = self.ag = MemoryAgent(epsilon=m["epsilon"], discount=m["discount"], learning_rate=m["learning_rate"], record_per_step=K,
-                                   replay_size=RING, minibatch=B, min_replay=MIN_REPLAY, seed=m["seed"], mem_size=MEM, power=POWER)
-        ag.setup(env)
-        ag.initialize(env)
-        env.observe()
-        for _ in range(3):
-            ag.rollout_step(env)  # past min_replay: every further step trains
-        assert ag.trainer.step_count > 0
+        ag = self.ag = BL.warmed(MemoryAgent(epsilon=m["epsilon"], discount=m["discount"], learning_rate=m["learning_rate"],
+                                             record_per_step=K, replay_size=RING, minibatch=B, min_replay=MIN_REPLAY, seed=m["seed"],
+                                             mem_size=MEM, power=POWER), env)
         self.rot, self.ph, _ = (t.clone().view(-1) for t in ag.get_action(env.obs, env.agent_state, False, env=env))
         self.idx = torch.randint(0, len(ag.replay_memory), (B,), device=env.device)
         self._p, self._st, self._check = _lib.ptr, _lib.stream(env.device), _lib.check
@@ -120,14 +106,8 @@ class Pop:
         from antsrl_amd import _lib
         from antsrl_amd.population import PopulationMemoryAgent
         self.env, self.lib = env, lib
-        pop = self.pop = PopulationMemoryAgent(members(P), mem_size=MEM, power=POWER, record_per_step=K, replay_size=RING, minibatch=B,
-                                               min_replay=MIN_REPLAY, seed=1)
-        pop.setup(env)
-        pop.initialize(env)
-        env.observe()
-        for _ in range(3):
-            pop.rollout_step(env)
-        assert pop.trainer.step_count > 0
+        pop = self.pop = BL.warmed(PopulationMemoryAgent(members(P), mem_size=MEM, power=POWER, record_per_step=K, replay_size=RING,
+                                                         minibatch=B, min_replay=MIN_REPLAY, seed=1), env)
         self.spec = pop._spec()
         self.idx = torch.randint(0, len(pop.replay_memory), (P, B), device=env.device)
         self._p, self._st, self._check = _lib.ptr, _lib.stream(env.device), _lib.check
@@ -192,13 +172,12 @@ def main():
             for _ in range(3):
                 fn()
     torch.cuda.synchronize()
-    # [repeat][configuration][figure]; inside a repeat the configurations alternate figure by figure
-    times = np.zeros((args.repeats, len(configs), len(NAMES)))
-    for r in range(args.repeats):
-        for j in range(len(NAMES)):
-            for i, f in enumerate(fns):
-                times[r, i, j] = per_call_us(f[j], args.steps)
-    med, spread = np.median(times, axis=0), times.max(axis=0) - times.min(axis=0)
+    # inside a repeat the configurations alternate figure by figure; no warm-up here, so nothing between the one above and
+    # the first event: us [configuration][figure][repeat]
+    order = [f[j] for j in range(len(NAMES)) for f in fns]
+    times = BL.per_block(order, args.steps, rounds=args.repeats, sync_blocks=True) * 1000.0
+    times = times.reshape(len(NAMES), len(configs), args.repeats).transpose(1, 0, 2)
+    med, spread = BL.median(times), BL.abs_spread(times)
 
     out = dict(device=device_identity(torch, torch.cuda.current_device()), steps=args.steps, repeats=args.repeats,
                shape="%d x %d ants, %d x %d cells, bf16 observations, F = %d, power %d, mem %d, K = %d per member, B = %d, ring %d rows "
@@ -223,10 +202,7 @@ def main():
         claims["P%d_below_sequential_by_three_spreads" % P] = {n: bool(pop["us"][n] < seq["us"][n] - 3.0 * seq["spread_us"][n])
                                                                for n in NAMES}
     out["claims"] = claims
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

@@ -19,21 +19,22 @@ configuration and one JSON line.  Without a GPU it exits with an error.
                                                      [--json profiles/population_memory_train.json]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-F, POWER, MEM, B, ROWS = 294, 5, 20, 264, 4096
+import benchlib as BL  # noqa: E402
+from benchlib import F  # noqa: E402
+
+POWER, MEM, B, ROWS = 5, 20, 264, 4096
 
 
 def members(P):
-    return [dict(discount=0.5 + 0.49 * p / max(1, P - 1), learning_rate=1e-5 * (1 + p % 4), seed=1 + p) for p in range(P)]
+    return BL.members(P, 1e-5, epsilon=None)
 
 
 def synthetic_ring(P, seed):
@@ -51,17 +52,6 @@ def synthetic_ring(P, seed):
     ring.dones.copy_(r(ring.dones) < 0.2)
     ring.fill = ROWS
     return ring
-
-
-def per_step_us(fn, steps):
-    """µs per call of fn: two device events around `steps` consecutive calls."""
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1000.0 / steps
 
 
 def main():
@@ -122,12 +112,10 @@ def main():
                 t.step(slabs[p], idx[p])
         configs.append(("sequential", P, 17 * P, seq))
 
-    for _, _, _, fn in configs:  # warm-up of every shape: the workspaces, the code objects, the clocks
-        for _ in range(10):
-            fn()
-    torch.cuda.synchronize()
-    times = np.array([[per_step_us(fn, args.steps) for _, _, _, fn in configs] for _ in range(args.repeats)])
-    med, spread = np.median(times, axis=0), times.max(axis=0) - times.min(axis=0)
+    # the warm-up of every shape (the workspaces, the code objects, the clocks), then per repeat and configuration two
+    # device events around `steps` consecutive steps and a synchronise: us [configuration][repeat]
+    times = BL.per_block([fn for _, _, _, fn in configs], args.steps, rounds=args.repeats, warmup=10, sync_blocks=True) * 1000.0
+    med, spread = BL.median(times), BL.abs_spread(times)
 
     out = dict(device=device_identity(torch, torch.cuda.current_device()), steps=args.steps, repeats=args.repeats,
                shape="F = %d, power %d, mem %d, B = %d, ring %d rows per member" % (F, POWER, MEM, B, ROWS),
@@ -154,10 +142,7 @@ def main():
     if find("population", 1):
         claims["P1_minus_entries_us"] = find("population", 1)["us_per_step"] - find("entries", 1)["us_per_step"]
     out["claims"] = claims
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

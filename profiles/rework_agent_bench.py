@@ -16,52 +16,30 @@ writes a JSON summary.
     python profiles/rework_agent_bench.py [--iters 200] [--json profiles/rework_agent_c5.json]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
-import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
-from antsrl_amd import config as cm  # noqa: E402
 from antsrl_amd._lib import ptr as _p  # noqa: E402
 from antsrl_amd.agent import ReworkAgent  # noqa: E402
-from antsrl_amd.batched import BatchedAntsEnv  # noqa: E402
 from antsrl_amd.policy import ReworkPolicy  # noqa: E402
-from antsrl_amd.synth import synth_init  # noqa: E402
+from benchlib import E, F, M, N  # noqa: E402
 
-E, N, F = 512, 512, 294
-M = E * N
 EPSILONS = (0.0, 0.01, 0.1, 0.3, 0.6, 1.0)
 FORMATS = ("float32", "bfloat16")
 ROUNDS = 5
 
 
-def rounds(fns, iters, warmup=5):
+def rounds(fns, iters):
     """Per fn: (median over ROUNDS of the ms per call, spread of the rounds); the fns alternate inside every round, one
     event pair around `iters` calls of one fn."""
-    for fn in fns:
-        for _ in range(warmup):
-            fn()
-    torch.cuda.synchronize()
-    ev = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in fns] for _ in range(ROUNDS)]
-    for r in range(ROUNDS):
-        for k, fn in enumerate(fns):
-            ev[r][k][0].record()
-            for _ in range(iters):
-                fn()
-            ev[r][k][1].record()
-    torch.cuda.synchronize()
-    out = []
-    for k in range(len(fns)):
-        ms = [ev[r][k][0].elapsed_time(ev[r][k][1]) / iters for r in range(ROUNDS)]
-        med = float(np.median(ms))
-        out.append((med, (max(ms) - min(ms)) / med))
-    return out
+    return BL.median_spread(BL.per_block(fns, iters, rounds=ROUNDS, warmup=5))
 
 
 def bench_act(fmt, iters):
@@ -103,20 +81,11 @@ def bench_act(fmt, iters):
 
 
 def c5_env(fmt):
-    cfg = cm.make_cfg(E, N, 256, 256, deposit_strength=256.0)
-    env = BatchedAntsEnv(cfg, obs_dtype=getattr(torch, fmt))
-    env.reset(synth_init(cfg, seed=3))
-    return env
+    return BL.c5_env(getattr(torch, fmt))
 
 
 def agent_on(env, fused, K=4096):
-    ag = ReworkAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, fused_select=fused)
-    ag.setup(env)
-    ag.initialize(env)
-    env.observe()
-    for _ in range(3):
-        ag.rollout_step(env)  # past min_replay: every further step trains
-    return ag
+    return BL.warmed(ReworkAgent(epsilon=0.1, record_per_step=K, min_replay=1000, seed=1, fused_select=fused), env)
 
 
 def bench_rollout(fmt, iters, K=4096):
@@ -177,9 +146,7 @@ def main():
                act=[bench_act(fmt, args.iters) for fmt in FORMATS])
     if not args.skip_rollout:
         out["rollout"] = [bench_rollout(fmt, max(20, args.iters // 4)) for fmt in FORMATS]
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

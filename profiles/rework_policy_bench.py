@@ -14,16 +14,16 @@ over enough launches to fill a good fraction of a second.  Prints one line per c
 """
 import argparse
 import ctypes as C
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 import torch.nn.functional as Fn  # noqa: E402
+
+import benchlib as BL  # noqa: E402
 
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd.policy import LinearPolicy, ReworkPolicy  # noqa: E402
@@ -39,22 +39,9 @@ def eager_fp32(W, obs, ast):
     return torch.max(q_rot, dim=1).indices, torch.max(q_ph, dim=1).indices
 
 
-def mean_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def iters_for(fn, budget_ms):
     """Warms `fn` up and sizes a timed loop to about budget_ms."""
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    return max(5, min(8000, int(budget_ms / max(mean_ms(fn, 5), 1e-3))))
+    return max(5, min(8000, int(budget_ms / max(float(BL.per_block([fn], 5, warmup=3)[0, 0]), 1e-3))))
 
 
 def main():
@@ -92,11 +79,9 @@ def main():
         if obs.dtype == torch.float32:
             cases["linear_policy"] = lambda: lin.act(obs, ast)
         iters = {k: iters_for(fn, args.budget_ms) for k, fn in cases.items()}
-        ms = {k: [] for k in cases}
-        for _ in range(args.rounds):  # alternating: every round times every case once
-            for k, fn in cases.items():
-                ms[k].append(mean_ms(fn, iters[k]))
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        # alternating: every round times every case once, a synchronise after each
+        t = BL.per_block(list(cases.values()), list(iters.values()), rounds=args.rounds, sync_blocks=True)
+        ms, med = dict(zip(cases, t.tolist())), dict(zip(cases, BL.median(t).tolist()))
         copy_gbs = 2 * nbytes / med["copy"] / 1e6            # read + written bytes
         obs_at_copy_ms = nbytes / copy_gbs / 1e6             # (iii)
         row = dict(obs=name, M=M, F=F, act_ms=round(med["act"], 4), act_min_ms=round(min(ms["act"]), 4),
@@ -113,10 +98,7 @@ def main():
               % (name, med["act"], min(ms["act"]), max(ms["act"]), row["obs_read_gbs"], med["eager_fp32"],
                  row["speedup_vs_eager"], ("%.4f ms" % med["linear_policy"]) if "linear_policy" in med else "n/a (needs its env)",
                  copy_gbs, obs_at_copy_ms, 100 * row["share_of_copy_rate"], med["collapse"]), flush=True)
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

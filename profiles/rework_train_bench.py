@@ -13,16 +13,16 @@ The step's four launches are timed by the profiler in a run of its own, which th
     rocprofv3 --kernel-trace --stats -d <dir> -- python profiles/rework_train_bench.py --loop 2000 --B 264
 """
 import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 import torch.nn.functional as Fn  # noqa: E402
+
+import benchlib as BL  # noqa: E402
 
 from antsrl_amd.train import ReworkTrainer  # noqa: E402
 
@@ -60,21 +60,9 @@ class Eager:
         return loss
 
 
-def mean_ms(fn, iters):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(iters):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / iters
-
-
 def iters_for(fn, budget_ms):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    return max(5, min(8000, int(budget_ms / max(mean_ms(fn, 5), 1e-3))))
+    """Warms `fn` up and sizes a timed loop to about budget_ms."""
+    return max(5, min(8000, int(budget_ms / max(float(BL.per_block([fn], 5, warmup=3)[0, 0]), 1e-3))))
 
 
 def replay(N, F, dev, seed=3):
@@ -111,11 +99,9 @@ def main():
         cases = {"step": lambda: tr.step(arrays, idx, keep_grads=False), "grad": lambda: tr.grad(arrays, idx),
                  "eager_fp32": lambda: eager.step(arrays, idx)}
         iters = {k: iters_for(fn, args.budget_ms) for k, fn in cases.items()}
-        ms = {k: [] for k in cases}
-        for _ in range(args.rounds):  # alternating: every round times every case once
-            for k, fn in cases.items():
-                ms[k].append(mean_ms(fn, iters[k]))
-        med = {k: statistics.median(v) for k, v in ms.items()}
+        # alternating: every round times every case once, a synchronise after each
+        t = BL.per_block(list(cases.values()), list(iters.values()), rounds=args.rounds, sync_blocks=True)
+        ms, med = dict(zip(cases, t.tolist())), dict(zip(cases, BL.median(t).tolist()))
         row = dict(B=B, F=F, launches=tr.launches(B), rounds=args.rounds, iters=iters,
                    **{k + "_ms": round(v, 4) for k, v in med.items()},
                    **{k + "_range_ms": [round(min(ms[k]), 4), round(max(ms[k]), 4)] for k in ms},
@@ -124,10 +110,7 @@ def main():
         print("B %d: step %.4f ms [%.4f, %.4f] | grad %.4f ms | eager torch fp32 %.3f ms [%.3f, %.3f] (x%.1f)"
               % (B, med["step"], min(ms["step"]), max(ms["step"]), med["grad"], med["eager_fp32"], min(ms["eager_fp32"]),
                  max(ms["eager_fp32"]), row["eager_over_step"]), flush=True)
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":

@@ -14,22 +14,28 @@ median over the rounds and their spread, (max - min) / median (profiles/rework_a
     python profiles/train_driver_bench.py [--iters 100] [--json profiles/train_driver_c5.json]
 """
 import argparse
-import json
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "profiles"))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "profiles")]
 
 import torch  # noqa: E402
 
+import benchlib as BL  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd._lib import ptr as _p  # noqa: E402
+from antsrl_amd.agent import ReworkAgent  # noqa: E402
 from antsrl_amd.monitor import EpisodeMonitor  # noqa: E402
-from rework_agent_bench import E, M, N, ROUNDS, agent_on, c5_env, rounds  # noqa: E402
+from benchlib import E, M, N  # noqa: E402
 
-EVERY, MAX_REPORTS = 50, 64
+EVERY, MAX_REPORTS, ROUNDS = 50, 64, 5
+
+
+def rounds(fns, iters):
+    """Per fn: (median over ROUNDS of the ms per call, spread of the rounds); the fns alternate inside every round, one
+    event pair around `iters` calls of one fn."""
+    return BL.median_spread(BL.per_block(fns, iters, rounds=ROUNDS, warmup=5))
 
 
 class EagerBook:
@@ -57,8 +63,8 @@ class EagerBook:
 
 
 def bench_rollout(fmt, iters):
-    envs = [c5_env(fmt) for _ in range(3)]
-    ags = [agent_on(env, True) for env in envs]
+    envs = [BL.c5_env(getattr(torch, fmt)) for _ in range(3)]
+    ags = [BL.warmed(ReworkAgent(epsilon=0.1, record_per_step=4096, min_replay=1000, seed=1, fused_select=True), env) for env in envs]
     mon = EpisodeMonitor(envs[1], report_every=EVERY, max_reports=MAX_REPORTS, max_episodes=1)
     book = EagerBook(envs[2].device)
     assert (5 + ROUNDS * iters) // EVERY <= MAX_REPORTS
@@ -113,9 +119,7 @@ def main():
     args = ap.parse_args()
     out = dict(device=torch.cuda.get_device_name(0), iters=args.iters, rounds=ROUNDS, envs=E, ants=N,
                bookkeeping_alone=bench_alone(4 * args.iters), rollout=[bench_rollout("bfloat16", args.iters)])
-    with open(args.json, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(out))
+    BL.write_json(out, args.json)
 
 
 if __name__ == "__main__":
