@@ -6,7 +6,7 @@ from .config import AntsCfg, make_cfg  # noqa: F401
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
            "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats",
            "EnvCheckpoint", "PopulationAgent", "train_population", "PopulationExploreAgent", "train_population_curriculum",
-           "PopulationJointAgent", "PopulationMemoryAgent"]
+           "PopulationJointAgent", "PopulationMemoryAgent", "PopulationReworkAgent"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -40,7 +40,8 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
     if name == "EnvCheckpoint":
         from .checkpoint import EnvCheckpoint
         return EnvCheckpoint
-    if name in ("PopulationAgent", "PopulationExploreAgent", "PopulationJointAgent", "PopulationMemoryAgent"):
+    if name in ("PopulationAgent", "PopulationExploreAgent", "PopulationJointAgent", "PopulationMemoryAgent",
+                "PopulationReworkAgent"):
         from . import population
         return getattr(population, name)
     if name in ("train_episodes", "train_population", "train_population_curriculum", "epsilon_schedule"):

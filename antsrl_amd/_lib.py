@@ -37,7 +37,9 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_pop_exptrain_step", "antsrl_pop_joint_policy", "antsrl_pop_jointtrain_sizes",
            "antsrl_pop_jointtrain_step", "antsrl_pop_memtrain_sizes", "antsrl_pop_memtrain_step",
            "antsrl_pop_memnet_sizes", "antsrl_pop_policy_memory", "antsrl_pop_memory_select",
-           "antsrl_pop_memory_record_pre", "antsrl_pop_memory_record_post")
+           "antsrl_pop_memory_record_pre", "antsrl_pop_memory_record_post", "antsrl_pop_rework_collapse",
+           "antsrl_pop_policy_rework", "antsrl_pop_policy_rework_select", "antsrl_pop_reworktrain_sizes",
+           "antsrl_pop_reworktrain_step")
 
 _lib = None
 
@@ -227,6 +229,11 @@ def load() -> C.CDLL:
     # the record pair's arguments with the shape behind the spec and `memory` behind agent_state
     lib.antsrl_pop_memory_record_pre.argtypes = [ps, ms] + lib.antsrl_pop_record_pre.argtypes[1:] + [vp]
     lib.antsrl_pop_memory_record_post.argtypes = [ps, ms] + lib.antsrl_pop_record_post.argtypes[1:] + [vp]
+    lib.antsrl_pop_rework_collapse.argtypes = [rs, i32, vp, vp, vp]
+    lib.antsrl_pop_policy_rework.argtypes = [ps, rs] + [vp] * 7
+    lib.antsrl_pop_policy_rework_select.argtypes = [ps, rs, vp, vp, vp, C.c_uint64] + [vp] * 5
+    lib.antsrl_pop_reworktrain_sizes.argtypes = [rs, C.c_int64, i32, sz, sz, sz, sz, C.POINTER(C.c_int32)]
+    lib.antsrl_pop_reworktrain_step.argtypes = [ps, rs] + lib.antsrl_pop_exptrain_step.argtypes[1:]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -24,7 +24,7 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
            "antsrl_rework.hip", "antsrl_reworktrain.hip", "antsrl_reworkapi.hip", "antsrl_monitor.hip", "antsrl_recorder.hip",
            "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip",
            "antsrl_population.hip", "antsrl_popexplore.hip", "antsrl_popjoint.hip", "antsrl_popmemtrain.hip",
-           "antsrl_popmemnet.hip", "antsrl_popapi.hip"]
+           "antsrl_popmemnet.hip", "antsrl_poprework.hip", "antsrl_popapi.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
@@ -43,7 +43,10 @@ HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "
                                            "antsrl_jointtrain_fwd_body.inc", "antsrl_memtrain_dev.h",
                                            "antsrl_memtrain_gemm_body.inc", "antsrl_memtrain_td_body.inc",
                                            "antsrl_memtrain_wgrad_body.inc", "antsrl_memtrain_finalize_body.inc",
-                                           "antsrl_memtrain_adam_body.inc")] + [
+                                           "antsrl_memtrain_adam_body.inc", "antsrl_reworkapi.h",
+                                           "antsrl_rework_collapse_body.inc", "antsrl_rework_act_body.inc",
+                                           "antsrl_reworktrain_down_body.inc", "antsrl_reworktrain_batch_body.inc",
+                                           "antsrl_reworktrain_up_body.inc", "antsrl_reworktrain_grad_body.inc")] + [
     os.path.join(HERE, "..", "include", "antsrl.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17",
          "-Wall", "-Wno-unused-function"]

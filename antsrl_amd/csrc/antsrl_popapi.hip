@@ -7,6 +7,9 @@
 //   memory nets     antsrl_pop_memtrain_sizes / _step                                                antsrl_popmemtrain.hip
 //   memory agents   antsrl_pop_memnet_sizes / antsrl_pop_policy_memory                               antsrl_popmemnet.hip
 //                   antsrl_pop_memory_select / _record_pre / _record_post (with the carried memory)  antsrl_population.hip
+//   rework agents   antsrl_pop_rework_collapse / antsrl_pop_policy_rework / _select /                antsrl_poprework.hip
+//                   antsrl_pop_reworktrain_sizes / _step (select without the fusion and record
+//                   are the linear agents')
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
@@ -21,6 +24,7 @@
 #include "antsrl_memnet.h"
 #include "antsrl_policy_flat.h"
 #include "antsrl_population.h"
+#include "antsrl_reworkapi.h" // rework_check
 
 #define POP_N_ROT 3 // the linear net's heads are 3 wide
 #define POP_N_PH 3
@@ -63,11 +67,19 @@ static int pop_spec(const char *who, const AntsPopSpec *s, PopTable *t, int *Em)
 
 // The acting kernel's rule: its producer loads 16-byte pieces from the first byte of a member's rows, so every member's
 // slice must start 16-byte aligned: obs itself, and Em * n_ants * n_features * sizeof(element) a multiple of 16.
+static int pop_slice_rule(const char *who, const AntsPopSpec *s, int Em);
 static int pop_flat_rule(const char *who, const AntsPopSpec *s, int Em)
 {
     if (!pol_flat_fits(s->n_features))
         return fail(ANTSRL_E_UNSUPPORTED, "%s: n_features = %d: the net and two 32-row images do not fit the LDS, and a population "
                                           "acts with the flat form only", who, s->n_features);
+    return pop_slice_rule(who, s, Em);
+}
+
+// pop_flat_rule's alignment rule alone, for an acting kernel that is not the flat form (the rework net's, which reads
+// its rows by 16-byte and dword loads from a member's first byte)
+static int pop_slice_rule(const char *who, const AntsPopSpec *s, int Em)
+{
     const long long bytes = (long long)Em * s->n_ants * s->n_features * (s->obs_format == ANTSRL_OBS_BF16 ? 2 : 4);
     if (bytes % 16)
         return fail(ANTSRL_E_UNSUPPORTED, "%s: a member's observation slice of %lld bytes (n_envs / n_members * n_ants * n_features "
@@ -375,8 +387,9 @@ extern "C" int antsrl_pop_jointtrain_step(const AntsPopSpec *s, float *model, co
 
 // ---- the population of memory nets (antsrl_popmemtrain.hip) ----------------------------------------------------------------
 
-// a spec and a shape that have passed their own rules speak of the same rows
-static int pop_same_features(const char *who, const AntsPopSpec *s, const AntsMemNetShape *shape)
+// a spec and a shape (the memory net's or the rework net's) that have passed their own rules speak of the same rows
+template <class Shape>
+static int pop_same_features(const char *who, const AntsPopSpec *s, const Shape *shape)
 {
     if (s->n_features == shape->n_features) return ANTSRL_OK;
     return fail(ANTSRL_E_INVALID, "%s: the spec's n_features = %d is not the shape's %d", who, s->n_features, shape->n_features);
@@ -590,4 +603,138 @@ extern "C" int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMem
 {
     return pop_record_post("pop_memory_record_post", s, true, shape, step, K, head, max_len, obs, agent_state, memory, reward, done,
                            rewards, new_states, new_agent_states, dones, stream);
+}
+
+// ---- the population of rework agents (antsrl_poprework.hip) ----------------------------------------------------------------
+
+// the floats of a member's collapsed buffer
+static size_t pop_rw_collapsed_floats(const ReworkDims &d) { return (size_t)(d.n_rot + d.n_ph) * (size_t)(d.D + 1); }
+
+// what the two acting entries check: the spec's rules, the shape's (antsrl_reworkapi.hip's), that they speak of the same
+// rows, the slice rule, then the pointers; fills member 0's arguments
+static int pop_rw_policy(const char *who, const AntsPopSpec *s, const AntsReworkShape *shape, const void *collapsed, const void *obs,
+                         const float *agent_state, int8_t *rotation, int8_t *pheromone, float *q_out, PopTable *t,
+                         PopReworkActArgs *a)
+{
+    int Em = 0;
+    int rc = pop_spec(who, s, t, &Em);
+    if (rc == ANTSRL_OK) rc = rework_check(shape, &a->d, who);
+    if (rc == ANTSRL_OK) rc = pop_same_features(who, s, shape);
+    if (rc == ANTSRL_OK) rc = pop_slice_rule(who, s, Em);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(collapsed, 4);
+    REQUIRE(obs, 16);
+    REQUIRE(agent_state, 4);
+    REQUIRE(rotation, 1);
+    REQUIRE(pheromone, 1);
+    if ((uintptr_t)q_out & 3) return fail(ANTSRL_E_INVALID, "%s: q_out must be 4-byte aligned", who);
+    a->collapsed = (const float *)collapsed; a->obs = obs; a->agent_state = agent_state;
+    a->rot = rotation; a->ph = pheromone; a->q_out = q_out;
+    a->Mm = Em * s->n_ants; a->Em = Em; a->P = s->n_members;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_rework_collapse(const AntsReworkShape *shape, int32_t n_members, const float *target_blocks,
+                                          float *collapsed, void *stream)
+{
+    const char *who = "pop_rework_collapse";
+    PopReworkCollapseArgs a = {};
+    int rc = rework_check(shape, &a.d, who);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(target_blocks, 4);
+    REQUIRE(collapsed, 4);
+    ReworkTrainLayout L;
+    antsrl_reworktrain_layout(a.d, 1, &L);
+    for (int i = 0; i <= 2 * RW_LAYERS; ++i) a.off[i] = L.off[i];
+    a.blocks = target_blocks; a.collapsed = collapsed;
+    return enqueued(antsrl_launch_pop_rework_collapse(a, n_members, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_policy_rework(const AntsPopSpec *s, const AntsReworkShape *shape, const void *collapsed,
+                                        const void *obs, const float *agent_state, int8_t *rotation, int8_t *pheromone,
+                                        float *q_out, void *stream)
+{
+    const char *who = "pop_policy_rework";
+    PopTable t;
+    PopReworkActArgs a = {};
+    const int rc = pop_rw_policy(who, s, shape, collapsed, obs, agent_state, rotation, pheromone, q_out, &t, &a);
+    if (rc != ANTSRL_OK) return rc;
+    return enqueued(antsrl_launch_pop_rework_act(a, t, s->obs_format == ANTSRL_OBS_BF16, false, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_policy_rework_select(const AntsPopSpec *s, const AntsReworkShape *shape, const void *collapsed,
+                                               const void *obs, const float *agent_state, uint64_t step, int8_t *rotation,
+                                               int8_t *pheromone, uint8_t *explored, float *q_out, void *stream)
+{
+    const char *who = "pop_policy_rework_select";
+    PopTable t;
+    PopReworkActArgs a = {};
+    const int rc = pop_rw_policy(who, s, shape, collapsed, obs, agent_state, rotation, pheromone, q_out, &t, &a);
+    if (rc != ANTSRL_OK) return rc;
+    // member 0's select; seed and epsilon come from the table
+    a.sel.step = step; a.sel.explored = explored;
+    a.sel.env_base = (uint32_t)s->env_id_base; a.sel.n_ants = (uint32_t)s->n_ants;
+    return enqueued(antsrl_launch_pop_rework_act(a, t, s->obs_format == ANTSRL_OBS_BF16, true, (hipStream_t)stream), who);
+}
+
+extern "C" int antsrl_pop_reworktrain_sizes(const AntsReworkShape *shape, int64_t B, int32_t n_members, size_t *trained_floats,
+                                            size_t *collapsed_floats, size_t *workspace_stride, size_t *workspace_bytes,
+                                            int32_t *launches)
+{
+    const char *who = "pop_reworktrain_sizes";
+    ReworkDims d;
+    int rc = rework_check(shape, &d, who);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, RT_MAX_B);
+    if (rc == ANTSRL_OK) rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    ReworkTrainLayout L;
+    antsrl_reworktrain_layout(d, (int)B, &L);
+    const size_t stride = (L.bytes + 255) / 256 * 256; // (the layout rounds every part up to 256: the stride is L.bytes)
+    if (trained_floats) *trained_floats = L.off[2 * RW_LAYERS];
+    if (collapsed_floats) *collapsed_floats = pop_rw_collapsed_floats(d);
+    if (workspace_stride) *workspace_stride = stride;
+    if (workspace_bytes) *workspace_bytes = stride * (size_t)n_members;
+    if (launches) *launches = 4;
+    return ANTSRL_OK;
+}
+
+extern "C" int antsrl_pop_reworktrain_step(const AntsPopSpec *s, const AntsReworkShape *shape, float *model,
+                                           const float *target_collapsed, float *adam_m, float *adam_v, const float *states,
+                                           const float *agent_states, const int64_t *actions, const float *rewards,
+                                           const float *new_states, const float *new_agent_states, const uint8_t *dones,
+                                           int64_t n_rows, const int64_t *idx, int64_t B, int64_t step, double beta1,
+                                           double beta2, double eps, float *grads, float *loss, double *running_loss,
+                                           int first_loss, void *workspace, void *stream)
+{
+    const char *who = "pop_reworktrain_step";
+    PopTable t;
+    ReworkTrainArgs a = {};
+    int Em = 0;
+    int rc = pop_spec(who, s, &t, &Em);
+    if (rc == ANTSRL_OK) rc = rework_check(shape, &a.d, who);
+    if (rc == ANTSRL_OK) rc = antsrl_dqn_B(who, B, RT_MAX_B);
+    if (rc == ANTSRL_OK) rc = pop_same_features(who, s, shape);
+    if (rc != ANTSRL_OK) return rc;
+    REQUIRE(model, 4);
+    REQUIRE(target_collapsed, 4);
+    REQUIRE(adam_m, 4);
+    REQUIRE(adam_v, 4);
+    REQUIRE(idx, 8);
+    REQUIRE(workspace, 256);
+    // member 0's minibatch: the slab's arrays, idx, grads, loss (the discount comes from the table)
+    rc = antsrl_dqn_minibatch(who, states, agent_states, actions, rewards, new_states, new_agent_states, dones, n_rows, idx, B,
+                              0.0f, grads, false, loss, &a);
+    if (rc == ANTSRL_OK) rc = pop_train_tail(who, s, step, beta1, beta2, eps, running_loss, &a.adam, &t);
+    if (rc != ANTSRL_OK) return rc;
+    antsrl_reworktrain_layout(a.d, (int)B, &a.L); // the single step's for this B: `parts` with it
+    a.work = (unsigned char *)workspace;
+    a.dq_rot = (float)(2.0 / ((double)a.d.n_rot * (double)B));
+    a.dq_ph = (float)(2.0 / ((double)a.d.n_ph * (double)B));
+    a.loss_rot = (float)(1.0 / ((double)a.d.n_rot * (double)B));
+    a.loss_ph = (float)(1.0 / ((double)a.d.n_ph * (double)B));
+    a.model = model; a.target = target_collapsed;
+    a.adam.m = adam_m; a.adam.v = adam_v;
+    const PopRunningLoss rl = {running_loss, first_loss != 0};
+    return enqueued(antsrl_launch_pop_reworktrain(a, t, s->n_members, (a.L.bytes + 255) / 256 * 256, rl, (hipStream_t)stream), who);
 }

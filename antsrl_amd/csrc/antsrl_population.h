@@ -19,6 +19,7 @@
 #include "antsrl_memagent.h"
 #include "antsrl_memtrain.h"
 #include "antsrl_policy_flat.h"
+#include "antsrl_reworktrain.h"
 
 // The members' hyper-parameters: host values that travel BY VALUE in the kernel arguments (as EnvCopyTable does,
 // antsrl_checkpoint.h), so a changed epsilon costs no device allocation and no copy.  24 bytes x 64 = 1.5 KB.
@@ -118,6 +119,50 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memnet(const unsigned char *packs, 
 // 0's elements; vec: they count float4).  The table gives seed and epsilon.  (antsrl_population.hip, beside k_pop_select)
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_memory_select(const SelArgs &a, const PopTable &t, int P, int Em, bool vec,
                                                            hipStream_t st);
+
+// ---- the population of rework agents (antsrl_poprework.hip; include/antsrl.h, "The population of rework agents") ----
+// A member's net is ReworkTrainer's flat block of NF = ReworkTrainLayout::off[20] floats (antsrl_reworktrain.h): model,
+// target, Adam's m and v and grads are [P][NF]; a member's collapsed buffer (antsrl_rework.h) is CF = NQ D + NQ floats,
+// collapsed [P][CF].  Neither count is a multiple of 4 in general (D = 296: CF = 1782), so blocks and buffers start
+// 4-byte aligned and no more: every kernel reads and writes them one float at a time.
+
+// tensor t of a member's block, the state_dict's order: what ReworkParams::p[t] is for a single net
+struct PopReworkTensors {
+    const float *block; // the member's
+    const size_t *off;  // ReworkTrainLayout::off, where the kernel's arguments hold it
+    __device__ __forceinline__ const float *operator[](int t) const { return block + off[t]; }
+};
+
+// the members' blocks for k_pop_rework_collapse: grid (NQ, P)
+struct PopReworkCollapseArgs {
+    const float *blocks; // [P][NF]
+    float *collapsed;    // [P][CF]
+    size_t off[2 * RW_LAYERS + 1]; // off[20] = NF
+    ReworkDims d;
+};
+
+// the acting net of every member on its Mm rows: grid (blocks, P).  sel: member 0's (its seed and epsilon come from the
+// table, env_base and explored move by Em); read by the SEL instantiations only
+struct PopReworkActArgs {
+    const float *collapsed;   // [P][CF]
+    const void *obs;          // [P][Mm][F], float32 or bfloat16, dense; a member's slice a multiple of 16 bytes
+    const float *agent_state; // [P][Mm][2]
+    int8_t *rot, *ph;         // [P][Mm]
+    float *q_out;             // [P][Mm][NQ] or NULL
+    int Mm, Em, P;
+    ReworkDims d;
+    ReworkSelect sel;
+};
+
+// one launch each; `select`: act and epsilon-greedy in one (a.sel and the table's seeds and epsilons are read)
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_rework_collapse(const PopReworkCollapseArgs &a, int P, hipStream_t st);
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_rework_act(const PopReworkActArgs &a, const PopTable &t, bool obs_bf16, bool select,
+                                                        hipStream_t st);
+// a: the single step's ReworkTrainArgs for member 0 (a.L antsrl_reworktrain_layout's for a.B; idx [P][B]; a.target the
+// members' collapsed buffers); ws_stride: bytes between two members' parts of the workspace.  Four launches on grids
+// (x, P); the table gives discount and step size
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_reworktrain(const ReworkTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
+                                                         const PopRunningLoss &rl, hipStream_t st);
 
 // ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.

@@ -12,7 +12,9 @@
 // Member 0's minibatch b0 moved to `member` in mb (a copy of b0), as far as every step moves it alike: the ring's seven
 // arrays by the member's L rows of F features, idx by B.  grads, loss, partials and discount stay with the caller, behind
 // this in the order the kernels have always had them (k_pop_lintrain compiles to other code when a statement moves).
-__device__ __forceinline__ void pop_ring_member(DqnBatch &mb, const DqnBatch &b0, const size_t member, const size_t L, const size_t F)
+// Q, Q0: DqnBatch, or the rework step's arguments, which carry the minibatch under the same names (antsrl_dqn.h).
+template <class Q, class Q0>
+__device__ __forceinline__ void pop_ring_member(Q &mb, const Q0 &b0, const size_t member, const size_t L, const size_t F)
 {
     mb.states = b0.states + member * L * F;
     mb.new_states = b0.new_states + member * L * F;
@@ -43,6 +45,52 @@ __device__ __forceinline__ L1TrainArgs pop_l1t_member(const L1TrainArgs &a0, con
     a.batch.loss = a0.batch.loss + member;
     a.batch.partials = a0.batch.partials + member * ws_floats;
     a.batch.discount = tab.m[member].discount;
+    return a;
+}
+
+// The arguments of the rework net's step (antsrl_reworktrain.h) for `member`, from member 0's: the model block, Adam's
+// moments and the gradients by the block's floats, the target (the member's collapsed buffer) by a buffer's floats, the
+// ring and idx as every step moves them, loss by one float, the workspace by ws_stride bytes (a multiple of 256, at
+// least a0.L.bytes); discount and Adam's step size from the table.  The layout a.L is every member's: it is the single
+// step's for the same B.
+//
+// What comes back is PopReworkTrainArgs: ReworkTrainArgs under the names the bodies read, with `d` and `L` REFERENCES to
+// member 0's, where the kernel's arguments hold them.  The bodies index L's arrays by a layer they compute; a moved copy
+// of the whole struct is then an array in scratch (808 bytes a thread in the down, up and gradient kernels), a reference
+// leaves the tables in the argument segment as the single kernels have them.
+struct PopReworkTrainArgs {
+    const ReworkDims &d;
+    const ReworkTrainLayout &L;
+    const float *states, *agent_states, *rewards, *new_states, *new_agent_states;
+    const int64_t *actions, *idx;
+    const uint8_t *dones;
+    float *grads, *loss;
+    unsigned char *work;
+    long long n_rows;
+    int B;
+    float discount, dq_rot, dq_ph, loss_rot, loss_ph;
+    float *model;
+    const float *target;
+    AdamArgs adam;
+};
+
+__device__ __forceinline__ PopReworkTrainArgs pop_rt_member(const ReworkTrainArgs &a0, const PopTable &tab, const size_t member,
+                                                            const size_t ws_stride)
+{
+    const size_t L = (size_t)a0.n_rows, F = (size_t)a0.d.F, NF = a0.L.off[2 * RW_LAYERS];
+    const size_t CF = (size_t)(a0.d.n_rot + a0.d.n_ph) * (size_t)(a0.d.D + 1);
+    PopReworkTrainArgs a = {a0.d, a0.L, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, a0.n_rows, a0.B, 0.0f, a0.dq_rot, a0.dq_ph, a0.loss_rot, a0.loss_ph, nullptr, nullptr, a0.adam};
+    a.model = a0.model + member * NF;
+    a.target = a0.target + member * CF;
+    a.adam.m = a0.adam.m + member * NF;
+    a.adam.v = a0.adam.v + member * NF;
+    a.adam.step_size = tab.m[member].step_size;
+    pop_ring_member(a, a0, member, L, F);
+    a.grads = a0.grads ? a0.grads + member * NF : nullptr;
+    a.loss = a0.loss + member;
+    a.work = a0.work + member * ws_stride;
+    a.discount = tab.m[member].discount;
     return a;
 }
 

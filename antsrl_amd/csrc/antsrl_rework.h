@@ -25,6 +25,31 @@ struct ReworkParams {
 
 struct __attribute__((packed, aligned(4))) RwF4 { float v[4]; }; // 4-byte aligned 16-byte load
 
+// what the kernels' bodies (antsrl_rework_collapse_body.inc, antsrl_rework_act_body.inc) share with whoever includes them
+#define RW_TPB 256
+#define RW_U 2              // sets of four rows a wave has in flight
+#define RW_G 4              // chunks of a row whose loads are issued together
+#define RW_MAX_BLOCKS 1024  // 4 workgroups per CU, what 120 VGPRs admit; rows beyond are looped
+
+typedef float rw_f32x2 __attribute__((ext_vector_type(2)));
+
+// inputs of layer l in the state_dict's order (its outputs are the inputs of the layer above it)
+__device__ __forceinline__ int rw_in(const ReworkDims &d, int l)
+{
+    switch (l) {
+    case 0: return d.D;
+    case 1: return d.g1;
+    case 2: return d.g2;
+    case 3: return d.g3;
+    case 4: return d.D;
+    case 5: return d.r1;
+    case 6: return d.r2;
+    case 7: return d.r3;
+    case 8: return d.D;
+    default: return d.p1;
+    }
+}
+
 // a + (a of the lane that CTRL names), by a DPP move inside the row of 16 lanes
 template <int CTRL>
 __device__ __forceinline__ float rw_add_dpp(float a)

@@ -17,6 +17,8 @@
 #define RT_ROWS 16        // minibatch rows a workgroup of the batch pass takes at a time: four per wave
 #define RT_MAX_PARTS 256  // workgroups of the batch pass, one partial each (rows beyond are looped)
 #define RT_MAX_B 65536
+#define RT_TPB 256        // threads of every workgroup of the step
+#define RT_INFO 8 // floats of a row's hand-over in LDS: g_rot, g_ph, d_rot^2, d_ph^2, a_rot, n_rot + a_ph (int), the replay row (int64)
 
 // where everything lies: floats into a parameter block, bytes into the workspace (every part 256-byte aligned)
 struct ReworkTrainLayout {

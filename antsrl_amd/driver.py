@@ -50,7 +50,7 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
                      max_epsilon=1.0, monitor: Optional[EpisodeMonitor] = None, report_every: int = 50,
                      save_as: Optional[str] = None) -> dict:
     """train_episodes' loop for a population (antsrl_amd/population.py: PopulationAgent, PopulationExploreAgent,
-    PopulationJointAgent, and PopulationMemoryAgent, which it drives as it is: the loop reads a population's n_members,
+    PopulationJointAgent, and PopulationMemoryAgent and PopulationReworkAgent, which it drives as they are: the loop reads a population's n_members,
     trainer, epsilon, setup, initialize, rollout_step and save_model and nothing of its net) on `env`, whose
     n_envs are the members' equal shares: a fresh map per episode, pop.setup once, pop.initialize and the first observation per episode, `steps`
     rollout_steps, and after every episode member p's epsilon from epsilon_schedule with its own bounds (min_epsilon,

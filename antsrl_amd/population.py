@@ -1,5 +1,5 @@
 """Populations: P agents trained in lockstep on one BatchedAntsEnv, one launch per stage of the loop whatever P is
-(include/antsrl.h, "The population of linear agents" and the sections behind it; DESIGN §7.24 - §7.31).
+(include/antsrl.h, "The population of linear agents" and the sections behind it; DESIGN §7.24 - §7.31, §7.34).
 
     pop = PopulationAgent([dict(epsilon=0.5, discount=0.99, learning_rate=1e-4, seed=s) for s in range(16)],
                           record_per_step=4096, min_replay=1000)
@@ -12,7 +12,7 @@ kernels are the single agent's stages with the member taken from the grid, and e
 on (seed, global environment id, step).  The per-member hyper-parameters are host values that travel in the kernels'
 arguments (`_Geometry.spec`): a changed epsilon costs no device copy.
 
-The four populations, each an agent over a trainer:
+The five populations, each an agent over a trainer:
 
     PopulationAgent         PopulationLinearTrainer    P CollectAgents, the curriculum's second stage; layer1 frozen
                                                        (antsrl_population.hip; §7.24): one training launch
@@ -23,6 +23,9 @@ The four populations, each an agent over a trainer:
     PopulationMemoryAgent   PopulationMemoryTrainer    P MemoryAgents, the agent main.py trains; the acting net the target's
                                                        bf16 pack, the memory carried in the ring's rows behind the agent
                                                        state (antsrl_popmemtrain.hip, antsrl_popmemnet.hip; §7.29, §7.30): 17
+    PopulationReworkAgent   PopulationReworkTrainer    P ReworkAgents, the agent main.py imports first; the acting net the
+                                                       target block multiplied out, act and select one launch
+                                                       (antsrl_poprework.hip; §7.34): four
 
 The stages hand over device to device: `PopulationAgent.setup(env, explore_population=pop_e)`,
 `PopulationJointAgent.setup(env, collect_population=pop_c)` (driver.train_population_curriculum runs them on one handle).
@@ -35,15 +38,15 @@ What is stated once:
     _PopulationTrainer      the members' host values, Adam's scalars, the counters, `running_loss`, `train`, `step` (whose
                             call hands every entry the same nineteen arguments behind the net's pointers) and `workspace`.
                             A trainer holds its net's tensors, dicts and loads and names its entry (`_entry`).
-    _PopulationFlatTrainer  under the explore and the joint trainer, train._FlatTrainer's counterpart: a member's net is
+    _PopulationFlatTrainer  under the explore, the joint and the rework trainer, train._FlatTrainer's counterpart: a member's net is
                             one flat block; the name table, `_sizes`, `_views`, `adam_state`, Adam's tensor, `grads`, `_entry`.
     _Population             the members' host values, the front of setup, the step's one AntsPopSpec, `get_action`, the
                             ring, train, the fused loop, the per-member files and `copy_member`.  An agent names its
                             trainer class and launches its acting net (`_policy`); the memory agent also has its own
                             select and hands its new memory out behind the actions.
 
-Out of scope: the memory agents' explore plan and tile-list forward (skip_explored) and their fp32 acting precision; the
-rework agent's net; in-loop acting (a handle holds one policy pack), B > 512 for the
+Out of scope: the memory agents' explore plan and tile-list forward (skip_explored) and their fp32 acting precision;
+in-loop acting (a handle holds one policy pack), B > 512 for the
 linear nets, members of unequal size, training_state.
 """
 from __future__ import annotations
@@ -58,7 +61,8 @@ import torch
 from . import _lib
 from ._lib import ptr as _p
 from .agent import _LoopAgent, _backend
-from .policy import MEMNET_PRECISIONS, linear_init, memnet_param_ptrs, memnet_param_shapes, memnet_shape
+from .policy import (MEMNET_PRECISIONS, REWORK_LAYERS, linear_init, memnet_param_ptrs, memnet_param_shapes, memnet_shape,
+                     rework_param_shapes)
 from .replay import RING_NAMES, _Ring, ring_arrays
 from .train import (EXPLORE_NAMES, LINEAR_NAMES, _MemoryBlocks, _TargetCounter, _clones, collect_names, copy_named,
                     explore_names, linear_adam_state, linear_model_views, linear_target_state_dict)
@@ -329,13 +333,13 @@ class PopulationLinearTrainer(_PopulationTrainer):
 
 
 class _PopulationFlatTrainer(_PopulationTrainer):
-    """What the explore and the joint population trainer share, train._FlatTrainer's counterpart for a population: a
+    """What the explore, the joint and the rework population trainer share, train._FlatTrainer's counterpart for a population: a
     member's net is ONE flat block described by `_offs` (name -> (offset, shape)); `model`, `_adam[0]`, `_adam[1]` and
     grads are [P, trained_floats]; the entries are antsrl_pop_<entry>_sizes / _step and take (model, the target, Adam's m,
     Adam's v) in front of the ring's arrays.  A subclass names its `entry` and the tensor that is its `target_name`, lists
     its layers (`_alloc_flat`), allocates its target and writes sync_target and its loads."""
 
-    entry = None  # "exptrain", "jointtrain"
+    entry = None  # "exptrain", "jointtrain", "reworktrain" (whose entries take the net's shape in front: it overrides _sizes and _entry)
     target_name = None  # the attribute the step entry takes behind `model`
 
     def _alloc_flat(self, names: Sequence[str], layers: dict) -> None:
@@ -578,6 +582,78 @@ class PopulationMemoryTrainer(_MemoryBlocks, _PopulationTrainer):
         return (self._lib.antsrl_pop_memtrain_step, "pop_memtrain_step", (C.byref(self.shape), _p(self._model), _p(self._target)))
 
 
+class PopulationReworkTrainer(_PopulationFlatTrainer):
+    """ReworkTrainer's tensors with a leading [P], trained by antsrl_pop_reworktrain_step: the single step's four
+    launches whatever P is.  model, target, `_adam[0]`, `_adam[1]` and grads are [P, trained_floats] (a member's flat
+    block is ReworkTrainer's: CollectModelRework's twenty tensors in its state_dict's order), `collapsed` is
+    [P, NQ D + NQ]: member p's TARGET block multiplied out (ReworkPolicy's collapsed buffer), what the population acts
+    with and the step takes its TD targets from.  Member p's weights are initialised as ReworkPolicy(seed=seed_p)
+    initialises a lone net, its target a copy.  Per member: discount and learning rate.  Common: the net's shape (the
+    heads' widths; the reference's hidden widths), Adam's betas, eps and step count, update_target_every and the target
+    counter.  `running_loss` (float64 [P]) is kept by the step's third launch from the first training step on.
+
+    sync_target and load_state_dict copy blocks and collapse ONCE for all members (antsrl_pop_rework_collapse); a
+    training step changes neither `collapsed` nor `version`, which counts the changes of the acting weights as
+    ReworkTrainer's does."""
+
+    entry, target_name = "reworktrain", "collapsed"
+
+    def __init__(self, geometry: _Geometry, device, seeds, discount, lr, betas=(0.9, 0.999), eps: float = 1e-8,
+                 update_target_every: int = 1, *, n_rot: int = 3, n_ph: int = 3):
+        super().__init__(geometry, device, seeds, discount, lr, betas, eps, update_target_every)
+        layers = rework_param_shapes(self.n_features, n_rot, n_ph)
+        shp = dict(n_features=self.n_features, agent_dim=2, n_rot=n_rot, n_ph=n_ph,
+                   **{k: layers[l][0] for k, l in (("g1", "layer1"), ("g2", "layer2"), ("g3", "layer3"), ("r1", "rotation_layer1"),
+                                                   ("r2", "rotation_layer2"), ("r3", "rotation_layer3"), ("p1", "pheromone_layer1"))})
+        self.n_rot, self.n_ph = n_rot, n_ph
+        self.shape = _lib.AntsReworkShape(*[shp[n] for n, _ in _lib.AntsReworkShape._fields_])
+        self._alloc_flat(["%s.%s" % (l, w) for l in REWORK_LAYERS for w in ("weight", "bias")], layers)
+        self.collapsed_floats = self._sizes(1)[4]
+        assert self.collapsed_floats == (n_rot + n_ph) * (self.n_features + 3)
+        self.target = self.model.clone()
+        self.collapsed = torch.empty((self.n_members, self.collapsed_floats), dtype=torch.float32, device=self.device)
+        self.version = 0
+        self._collapse()
+
+    def _sizes(self, B: int) -> tuple:
+        """antsrl_pop_reworktrain_sizes -> (trained_floats, a member's workspace stride, the workspace's bytes, launches,
+        the floats of a member's collapsed buffer)."""
+        tf, cf, stride, ws, n = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_int32()
+        _lib.check(self._lib.antsrl_pop_reworktrain_sizes(C.byref(self.shape), B, self.n_members, C.byref(tf), C.byref(cf),
+                                                          C.byref(stride), C.byref(ws), C.byref(n)), "pop_reworktrain_sizes")
+        return tf.value, stride.value, ws.value, n.value, cf.value
+
+    def _collapse(self) -> None:
+        """`collapsed` := every member's target block multiplied out: one launch."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_pop_rework_collapse(C.byref(self.shape), self.n_members, _p(self.target), _p(self.collapsed),
+                                                            _lib.stream(self.device)), "pop_rework_collapse")
+
+    def target_state_dict(self, p: int) -> dict:
+        return _clones(self._views(self.target[p]))
+
+    def load_state_dict(self, sd, p: Optional[int] = None) -> None:
+        """ReworkTrainer.load_state_dict for member p (None: every member): model AND target, then the collapse; Adam's
+        state is kept.  The widths are the population's: a state_dict of another shape is refused."""
+        rows = _rows(p)
+        for q in range(self.n_members)[rows]:
+            copy_named(sd, self._views(self.model[q]))
+        self.target[rows].copy_(self.model[rows])
+        self._collapse()
+        self.version += 1
+
+    def sync_target(self) -> None:
+        """target := model for every member: one copy of [P, trained_floats] and one collapse launch."""
+        self.target.copy_(self.model)
+        self._collapse()
+        self.syncs += 1
+        self.version += 1
+
+    def _entry(self) -> tuple:
+        """Four launches; the shape leads the net's pointers."""
+        return (self._step, self._step_name, (C.byref(self.shape),) + super()._entry()[2])
+
+
 def _same_population(trainer, other, kind: str) -> None:
     """A hand-over between two population trainers needs as many members and as wide rows: load_explore_population's
     words, with the handing population's kind."""
@@ -663,6 +739,13 @@ class _Population(_LoopAgent):
         actions."""
         _lib.check(self._lib.antsrl_pop_select(C.byref(spec), step, _p(self._rot), _p(self._ph), _p(self._explored), st), "pop_select")
 
+    def _act(self, spec, obs, agent_state, training: bool, step: int, st) -> None:
+        """The step's acting launches: `_policy`, and with `training` `_select` behind it.  (The rework agent fuses the
+        two into one launch.)"""
+        self._policy(spec, obs, agent_state, st)
+        if training:
+            self._select(spec, step, st)
+
     def _acted(self, lead) -> tuple:
         """What get_action returns once the step's launches are enqueued: the actions, shaped like the batch."""
         return self._rot.view(lead), (self._ph.view(lead) if self.pheromones else None)
@@ -679,9 +762,7 @@ class _Population(_LoopAgent):
         lead = obs.shape[:-3]
         with torch.cuda.device(self.device):
             st = _lib.stream(self.device)
-            self._policy(spec, obs, agent_state, st)
-            if training:
-                self._select(spec, step, st)
+            self._act(spec, obs, agent_state, training, step, st)
         self._action_step = step
         self.step_counter += 1
         return self._acted(lead)
@@ -915,3 +996,63 @@ class PopulationMemoryAgent(_Population):
         Mm = self.g.Mm
         for m in self._mem:
             m[dst * Mm:(dst + 1) * Mm].copy_(m[src * Mm:(src + 1) * Mm])
+
+
+class PopulationReworkAgent(_Population):
+    """P ReworkAgents in lockstep: CollectAgentRework, the agent main.py imports first, for every member of a sweep (the
+    module docstring).  members: PopulationAgent's dicts (ReworkAgent's defaults where a key is missing).
+    Common to all members: the heads' widths (`rotations`, `pheromones`, 1 .. 8 each), `fused_select`, record_per_step,
+    replay_size, minibatch (the reference's 264; up to 65536), min_replay, update_target_every; `seed` seeds the
+    generator of the minibatch indices.
+
+    The acting net of a member is its TARGET block multiplied out (PopulationReworkTrainer.collapsed), so it changes at
+    a sync or a load only.  `fused_select` (on by default): with `training`, act and select are ONE launch for all
+    members whatever their epsilons (antsrl_pop_policy_rework_select): a member's pass whose rows all explore is not
+    evaluated, a member with epsilon 0 is evaluated on every row.  Off, it is the net on the whole batch
+    (antsrl_pop_policy_rework) and antsrl_pop_select behind it.  Both give the same actions, rings, weights and losses
+    bit for bit, as ReworkAgent's two forms do.
+
+    The ring and its record halves are the linear population's: they store rotation + 1, so `rotations` is 2 or 3 (a
+    wider rotation head acts and trains through the entries, but not through this loop); antsrl_pop_select draws among
+    three rotations and three pheromones, so fused_select=False needs both heads three wide."""
+
+    name = "collect_agent_rework_population"
+    pheromones = True
+    trainer_cls = PopulationReworkTrainer
+
+    def __init__(self, members: Sequence[dict], *, rotations: int = 3, pheromones: int = 3, fused_select: bool = True,
+                 record_per_step: Optional[int] = None, replay_size: int = 50000, minibatch: int = 264, min_replay: int = 1000,
+                 update_target_every: int = 1, seed: int = 0):
+        assert 1 <= rotations <= 8 and 1 <= pheromones <= 8, \
+            "the net's heads are 1 to 8 wide (antsrl_pop_policy_rework), not %r and %r" % (rotations, pheromones)
+        assert rotations // 2 == 1, "the population's ring stores rotation + 1: rotations must be 2 or 3, not %r" % (rotations,)
+        assert fused_select or (rotations, pheromones) == (3, 3), \
+            "antsrl_pop_select draws among three rotations and three pheromones: fused_select=False needs heads (3, 3)"
+        super().__init__(members, record_per_step=record_per_step, replay_size=replay_size, minibatch=minibatch,
+                         min_replay=min_replay, update_target_every=update_target_every, seed=seed)
+        self.rotations, self.pheromones, self.fused_select = rotations, pheromones, fused_select
+
+    def setup(self, api_or_env, trained_model: Optional[str] = None) -> None:
+        """ReworkAgent.setup for every member; trained_model goes to every member."""
+        self._setup(api_or_env, dict(n_rot=self.rotations, n_ph=self.pheromones))
+        if trained_model is not None:
+            self.load_model(trained_model)
+
+    def _policy(self, spec, obs, agent_state, st) -> None:
+        tr = self.trainer
+        _lib.check(self._lib.antsrl_pop_policy_rework(C.byref(spec), C.byref(tr.shape), _p(tr.collapsed), _p(obs), _p(agent_state),
+                                                      _p(self._rot), _p(self._ph), None, st), "pop_policy_rework")
+
+    def _act(self, spec, obs, agent_state, training: bool, step: int, st) -> None:
+        """With `training` and `fused_select`, act and select in one launch; else _Population's two."""
+        if not (training and self.fused_select):
+            return super()._act(spec, obs, agent_state, training, step, st)
+        tr = self.trainer
+        _lib.check(self._lib.antsrl_pop_policy_rework_select(C.byref(spec), C.byref(tr.shape), _p(tr.collapsed), _p(obs),
+                                                             _p(agent_state), step, _p(self._rot), _p(self._ph),
+                                                             _p(self._explored), None, st), "pop_policy_rework_select")
+
+    def _member_tensors(self) -> tuple:
+        """The collapsed buffer travels with the target block it was multiplied out of."""
+        tr = self.trainer
+        return ((tr.model, 0), (tr.target, 0), (tr.collapsed, 0), (tr._adam, 1))

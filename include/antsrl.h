@@ -1675,6 +1675,73 @@ int antsrl_pop_memory_record_post(const AntsPopSpec *s, const AntsMemNetShape *s
                                   const float *reward, const uint8_t *done, float *rewards, float *new_states,
                                   float *new_agent_states, uint8_t *dones, void *stream);
 
+/* The population of rework agents: P CollectAgentReworks (the net of "The rework agent's net" and "The rework agent's
+ * training step") in lockstep on one handle.  The collapse of every member's target net is ONE launch, the acting net
+ * with or without the epsilon-greedy select ONE launch and the training step the single step's FOUR launches, each on
+ * a grid (x, P) with the member in the grid's y dimension, whatever P is.  The spec is the population of linear
+ * agents'; Em = n_envs / n_members, Mm = Em * n_ants; member p owns environments [p Em, (p + 1) Em) and ants
+ * [p Mm, (p + 1) Mm).  Members share one AntsReworkShape (hidden widths, n_rot and n_ph, 1 .. 8 each).  The select
+ * without the fusion and the ring's two record halves are the population of linear agents' (antsrl_pop_select,
+ * antsrl_pop_record_pre / _post: three-wide heads, rotation + 1 stored).
+ *
+ * THE DEFINING PROPERTY: member p computes, bit for bit, what antsrl_rework_collapse, antsrl_policy_rework,
+ * antsrl_policy_rework_select (seed, epsilon of the member, env_id_base + p Em) and antsrl_reworktrain_step (discount and
+ * learning rate of the member) compute on its own block, collapsed buffer, rows, ring slab and idx row; no output of a
+ * member depends on P or on another member's data.  A member with epsilon 0 is evaluated on every row by the select
+ * entry and gets antsrl_policy_rework's bits.
+ *
+ * Layout: NF = antsrl_reworktrain_sizes' params_floats, CF = (n_rot + n_ph) * (n_features + 2) + n_rot + n_ph.  model,
+ * target_blocks, adam_m, adam_v and grads are float [P][NF], a member's block the single trainer's (the 20 tensors of
+ * the state_dict in its order); collapsed and target_collapsed float [P][CF], a member's buffer what
+ * antsrl_rework_collapse writes.  Blocks and buffers are 4-byte aligned and no more (neither count is a multiple of 4 in
+ * general).  obs [P][Mm][n_features] dense, a member's slice a multiple of 16 bytes; agent_state [P][Mm][2]; rotation,
+ * pheromone [P][Mm]; q_out [P][Mm][n_rot + n_ph] or NULL; explored [n_envs] or NULL.  The workspace is
+ * [P][workspace_stride] bytes, a member's part laid out as antsrl_reworktrain_step's for the same B; the stride is a
+ * multiple of 256 and at least antsrl_reworktrain_sizes' workspace_bytes.  The ring's seven arrays have a leading [P] of
+ * n_rows rows each; idx int64 [P][B], required, every value in [0, n_rows); loss float [P]; running_loss double [P] or
+ * NULL.
+ *
+ * Refusals (ANTSRL_E_INVALID unless stated), each in words and before any launch: a NULL spec or shape; the spec's
+ * rules, as above; the shape's, as antsrl_rework_collapse's (a head wider than 8, a hidden width above 256 and
+ * n_features + 2 > 1024 are UNSUPPORTED); the spec's n_features is not the shape's; n_members outside
+ * [1, ANTSRL_POP_MAX]; a member's observation slice that is no multiple of 16 bytes (UNSUPPORTED);
+ *   the acting entries: collapsed, agent_state or q_out not 4-byte aligned, obs not 16-byte aligned, any of them but
+ *     q_out NULL, rotation or pheromone NULL;
+ *   antsrl_pop_reworktrain_sizes / _step: B outside [1, 65536] (above: UNSUPPORTED); model, target_collapsed, adam_m or
+ *     adam_v NULL or not 4-byte aligned; idx NULL or not 8-byte aligned; workspace NULL or not 256-byte aligned; n_rows
+ *     outside [1, 2^40]; any ring array, grads or loss NULL or misaligned; running_loss not 8-byte aligned; step < 1 and
+ *     Adam's other arguments for every member's learning_rate.
+ * No entry allocates or synchronises the host; no atomics: equal inputs give equal bits.
+ *
+ *   antsrl_pop_rework_collapse       collapsed[p] = antsrl_rework_collapse of block p of target_blocks.  Grid (NQ, P).
+ *   antsrl_pop_policy_rework         every member's collapsed net on its rows: rotation (argmax - n_rot / 2), pheromone
+ *                         and, when q_out is not NULL, both heads' outputs.
+ *   antsrl_pop_policy_rework_select  the same and antsrl_pop_select's epsilon-greedy in one launch, among n_rot and n_ph
+ *                         actions, without the forward pass of the rows whose whole pass explores; q_out is written
+ *                         for the rows of the other colonies only.
+ *   antsrl_pop_reworktrain_sizes     trained_floats = NF, collapsed_floats = CF, workspace_stride, workspace_bytes =
+ *                         n_members * workspace_stride and launches = 4 (any of the five may be NULL).  Host only.
+ *   antsrl_pop_reworktrain_step      the step of every member: down chain, batch pass, up chain (which keeps the running
+ *                         loss), gradient and Adam with the member's step size.  step, beta1, beta2, eps, running_loss
+ *                         and first_loss as antsrl_pop_lintrain_step's.  target_collapsed is read, never written.
+ * The target sync is one copy of [P][NF] and one antsrl_pop_rework_collapse, the caller's. */
+int antsrl_pop_rework_collapse(const AntsReworkShape *shape, int32_t n_members, const float *target_blocks, float *collapsed,
+                               void *stream);
+int antsrl_pop_policy_rework(const AntsPopSpec *s, const AntsReworkShape *shape, const void *collapsed, const void *obs,
+                             const float *agent_state, int8_t *rotation, int8_t *pheromone, float *q_out, void *stream);
+int antsrl_pop_policy_rework_select(const AntsPopSpec *s, const AntsReworkShape *shape, const void *collapsed, const void *obs,
+                                    const float *agent_state, uint64_t step, int8_t *rotation, int8_t *pheromone,
+                                    uint8_t *explored, float *q_out, void *stream);
+int antsrl_pop_reworktrain_sizes(const AntsReworkShape *shape, int64_t B, int32_t n_members, size_t *trained_floats,
+                                 size_t *collapsed_floats, size_t *workspace_stride, size_t *workspace_bytes,
+                                 int32_t *launches);
+int antsrl_pop_reworktrain_step(const AntsPopSpec *s, const AntsReworkShape *shape, float *model, const float *target_collapsed,
+                                float *adam_m, float *adam_v, const float *states, const float *agent_states,
+                                const int64_t *actions, const float *rewards, const float *new_states,
+                                const float *new_agent_states, const uint8_t *dones, int64_t n_rows, const int64_t *idx,
+                                int64_t B, int64_t step, double beta1, double beta2, double eps, float *grads, float *loss,
+                                double *running_loss, int first_loss, void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Times a population of linear agents (--agent collect: antsrl_amd.population.PopulationAgent), of
-explore agents (--agent explore: PopulationExploreAgent) or of joint agents (--agent joint:
-PopulationJointAgent against CollectAgent(train_layer1=True)) at config 5's batch: 512 environments x 512 ants
+explore agents (--agent explore: PopulationExploreAgent), of joint agents (--agent joint:
+PopulationJointAgent against CollectAgent(train_layer1=True)) or of rework agents (--agent rework:
+PopulationReworkAgent against ReworkAgent; rollout_step acts and selects in one launch in both, the
+`policy` and `select` stages are the two entries of the form without the fusion) at config 5's batch: 512 environments x 512 ants
 on 256 x 256 cells, bfloat16 observations, K = 4096 rows recorded per member and step, the agent's minibatch (264 / 256).
 One environment, stepped by every configuration in turn:
 
-  single        CollectAgent / ExploreAgent / CollectAgent(train_layer1=True) alone on the whole batch
+  single        CollectAgent / ExploreAgent / CollectAgent(train_layer1=True) / ReworkAgent alone on the whole batch
   population    the population at P = 1, 4, 16 and 64 (--members; member p owns 512 / P environments)
   sequential    at P = 4 and 16 (--sequential), the same members run one after another on their slices of the batch with
                 the single agent's entries (policy, select, record, train: P launches per stage, 2 P for the explore
@@ -20,8 +22,8 @@ median of the repeats with their spread (max - min).  The bar: a
 its train stage each lie below the sequential run's by more than three times the sequential run's own spread.  Prints one
 line per configuration and a JSON summary.
 
-    python profiles/population_bench.py --agent collect|explore|joint [--iters 40] [--repeats 3] [--members 1,4,16,64]
-                                        [--sequential 4,16] [--json profiles/population_<agent|explore|joint>_c5.json]
+    python profiles/population_bench.py --agent collect|explore|joint|rework [--iters 40] [--repeats 3] [--members 1,4,16,64]
+                                        [--sequential 4,16] [--json profiles/population_<agent|explore|joint|rework>_c5.json]
 """
 import argparse
 import ctypes
@@ -38,10 +40,10 @@ import benchlib as BL  # noqa: E402
 from bench import device_identity  # noqa: E402
 from antsrl_amd import _lib  # noqa: E402
 from antsrl_amd import config as cm  # noqa: E402
-from antsrl_amd.agent import CollectAgent, ExploreAgent  # noqa: E402
-from antsrl_amd.population import PopulationAgent, PopulationExploreAgent, PopulationJointAgent  # noqa: E402
+from antsrl_amd.agent import CollectAgent, ExploreAgent, ReworkAgent  # noqa: E402
+from antsrl_amd.population import PopulationAgent, PopulationExploreAgent, PopulationJointAgent, PopulationReworkAgent  # noqa: E402
 from antsrl_amd.replay import DeviceReplayMemory  # noqa: E402
-from antsrl_amd.train import ExploreTrainer, JointTrainer, LinearTrainer  # noqa: E402
+from antsrl_amd.train import ExploreTrainer, JointTrainer, LinearTrainer, ReworkTrainer  # noqa: E402
 from benchlib import E, F, N  # noqa: E402
 
 K, RING, MIN_REPLAY = 4096, 20000, 1000
@@ -54,7 +56,9 @@ KINDS = dict(collect=dict(single=CollectAgent, population=PopulationAgent, train
              explore=dict(single=ExploreAgent, population=PopulationExploreAgent, trainer=ExploreTrainer, pheromone=False, B=256,
                           json="population_explore_c5.json"),
              joint=dict(single=CollectAgent, single_kw=dict(train_layer1=True), population=PopulationJointAgent, trainer=JointTrainer,
-                        pheromone=True, B=264, json="population_joint_c5.json"))
+                        pheromone=True, B=264, json="population_joint_c5.json"),
+             rework=dict(single=ReworkAgent, population=PopulationReworkAgent, trainer=ReworkTrainer, pheromone=True, B=264,
+                         json="population_rework_c5.json"))
 
 
 def timed(fn, iters):
@@ -101,7 +105,7 @@ def bench_population(kind, env, P, iters, repeats):
 
     def select():
         _lib.check(lib.antsrl_pop_select(ctypes.byref(spec), 0, _lib.ptr(pop._rot), _lib.ptr(pop._ph), _lib.ptr(pop._explored), st))
-    return dict(P=P, envs_per_member=E // P,
+    return dict(P=P, envs_per_member=E // P, train_ms_per_member_step=None,
                 **figures((lambda: pop.rollout_step(env), lambda: pop.get_action(env.obs, env.agent_state, False, env=env, spec=spec),
                            select, rec, lambda: pop.trainer.step(rm, idx, spec)), iters, repeats))
 
@@ -195,7 +199,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--members", default="1,4,16,64", help="the population sizes to time")
     ap.add_argument("--sequential", default="4,16", help="of those, the sizes to time one member after another as well")
-    ap.add_argument("--json", default=None, help="default: profiles/population_agent_c5.json / population_explore_c5.json / population_joint_c5.json")
+    ap.add_argument("--json", default=None, help="default: profiles/population_<agent|explore|joint|rework>_c5.json")
     args = ap.parse_args()
     kind = KINDS[args.agent]
     sizes, seq_sizes = ([int(x) for x in v.split(",") if x] for v in (args.members, args.sequential))
@@ -215,6 +219,7 @@ def main():
     for P in sizes:
         r = bench_population(kind, env, P, args.iters, args.repeats)
         r["ratio_to_single"] = r["ms"]["rollout_step"] / single
+        r["train_ms_per_member_step"] = r["ms"]["train"] / P  # against the single trainer's step, out["single"]["ms"]["train"]
         out["population"].append(r)
         print("population P = %2d (x %.3f of single): %s" % (P, r["ratio_to_single"], line(r)), flush=True)
     for P in seq_sizes:
