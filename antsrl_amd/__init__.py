@@ -6,7 +6,8 @@ from .config import AntsCfg, make_cfg  # noqa: F401
 __all__ = ["config", "AntsCfg", "make_cfg", "CollectAgent", "LinearTrainer", "ExploreAgent", "ExploreTrainer",
            "JointTrainer", "ReworkTrainer", "ReworkAgent", "EpisodeMonitor", "train_episodes", "epsilon_schedule", "EpisodeStats",
            "EnvCheckpoint", "PopulationAgent", "train_population", "PopulationExploreAgent", "train_population_curriculum",
-           "PopulationJointAgent", "PopulationMemoryAgent", "PopulationReworkAgent"]
+           "PopulationJointAgent", "PopulationMemoryAgent", "PopulationReworkAgent", "PopulationFitness", "PbtConfig",
+           "pbt_plan"]
 
 
 def __getattr__(name):  # the linear agent and its trainer import torch: resolved on first use
@@ -44,6 +45,9 @@ def __getattr__(name):  # the linear agent and its trainer import torch: resolve
                 "PopulationReworkAgent"):
         from . import population
         return getattr(population, name)
+    if name in ("PopulationFitness", "PbtConfig", "pbt_plan"):
+        from . import pbt
+        return getattr(pbt, name)
     if name in ("train_episodes", "train_population", "train_population_curriculum", "epsilon_schedule"):
         from . import driver
         return getattr(driver, name)

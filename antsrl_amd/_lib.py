@@ -39,7 +39,7 @@ EXPORTS = ("antsrl_abi_version", "antsrl_cfg_size", "antsrl_last_error", "antsrl
            "antsrl_pop_memnet_sizes", "antsrl_pop_policy_memory", "antsrl_pop_memory_select",
            "antsrl_pop_memory_record_pre", "antsrl_pop_memory_record_post", "antsrl_pop_rework_collapse",
            "antsrl_pop_policy_rework", "antsrl_pop_policy_rework_select", "antsrl_pop_reworktrain_sizes",
-           "antsrl_pop_reworktrain_step")
+           "antsrl_pop_reworktrain_step", "antsrl_pop_fitness", "antsrl_pop_exploit")
 
 _lib = None
 
@@ -234,6 +234,9 @@ def load() -> C.CDLL:
     lib.antsrl_pop_policy_rework_select.argtypes = [ps, rs, vp, vp, vp, C.c_uint64] + [vp] * 5
     lib.antsrl_pop_reworktrain_sizes.argtypes = [rs, C.c_int64, i32, sz, sz, sz, sz, C.POINTER(C.c_int32)]
     lib.antsrl_pop_reworktrain_step.argtypes = [ps, rs] + lib.antsrl_pop_exptrain_step.argtypes[1:]
+    lib.antsrl_pop_fitness.argtypes = [vp, i32, i32, i32, vp, vp]
+    lib.antsrl_pop_exploit.argtypes = [i32, C.POINTER(vp), C.POINTER(C.c_uint64), i32, i32, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the build lost a symbol
     lib.antsrl_cfg_size.restype = C.c_size_t

@@ -24,7 +24,7 @@ SOURCES = ["antsrl_act.hip", "antsrl_perceive.hip", "antsrl_update.hip", "antsrl
            "antsrl_rework.hip", "antsrl_reworktrain.hip", "antsrl_reworkapi.hip", "antsrl_monitor.hip", "antsrl_recorder.hip",
            "antsrl_render.hip", "antsrl_stats.hip", "antsrl_logapi.hip", "antsrl_checkpoint.hip",
            "antsrl_population.hip", "antsrl_popexplore.hip", "antsrl_popjoint.hip", "antsrl_popmemtrain.hip",
-           "antsrl_popmemnet.hip", "antsrl_poprework.hip", "antsrl_popapi.hip"]
+           "antsrl_popmemnet.hip", "antsrl_poprework.hip", "antsrl_popfitness.hip", "antsrl_popapi.hip"]
 HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "antsrl_update_env.h",
                                            "antsrl_update_one.h", "antsrl_flush.h", "antsrl_layout.h",
                                            "antsrl_lds_optin.h", "antsrl_fail.h", "antsrl_memnet.h",
@@ -32,7 +32,7 @@ HEADERS = [os.path.join(CSRC, h) for h in ("antsrl_device.h", "antsrl_util.h", "
                                            "antsrl_agent_select_memory.inc", "antsrl_memtrain.h", "antsrl_memagent.h", "antsrl_loopapi.h",
                                            "antsrl_draw.h",
                                            "antsrl_adam.h", "antsrl_dqn.h", "antsrl_dqn_dev.h", "antsrl_lintrain.h",
-                                           "antsrl_l1train.h", "antsrl_l1train_dev.h", "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h",
+                                           "antsrl_l1train.h", "antsrl_l1train_dev.h", "antsrl_exptrain.h", "antsrl_jointtrain.h", "antsrl_rework.h", "antsrl_reworktrain.h", "antsrl_monitor.h", "antsrl_monitor_dev.h",
                                            "antsrl_cellread.h", "antsrl_recorder.h", "antsrl_render.h", "antsrl_stats.h",
                                            "antsrl_launch.h", "antsrl_handle.h", "antsrl_checkpoint.h",
                                            "antsrl_policy_flat.h", "antsrl_memagent_dev.h", "antsrl_lintrain_dev.h",

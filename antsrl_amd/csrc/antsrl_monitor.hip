@@ -16,6 +16,7 @@
 #include "antsrl_device.h"
 #include "antsrl_fail.h"
 #include "antsrl_monitor.h"
+#include "antsrl_monitor_dev.h" // the slots and their folds, shared with antsrl_popfitness.hip
 
 struct MonitorStep {
     double *er;          // episode_reward [E][N]
@@ -46,16 +47,6 @@ __global__ void __launch_bounds__(MON_THREADS) k_monitor_accum(MonitorStep a)
     if (i == 0) monitor_loss(a.head, a.loss);
 }
 
-// x[i] += x[i + s] for i < s, s = 128, ..., 1, over the workgroup's 256 slots; the result in x[0]
-__device__ __forceinline__ void monitor_fold(double *x, int t)
-{
-    __syncthreads();
-    for (int s = MON_THREADS / 2; s >= 1; s >>= 1) {
-        if (t < s) x[t] = x[t] + x[t + s];
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(MON_THREADS) k_monitor_report(MonitorStep a)
 {
     __shared__ double xs[MON_THREADS], xmn[MON_THREADS], xmx[MON_THREADS];
@@ -66,22 +57,10 @@ __global__ void __launch_bounds__(MON_THREADS) k_monitor_report(MonitorStep a)
     for (int n = t; n < N; n += MON_THREADS) {
         const double v = er[n] + (double)rw[n];
         er[n] = v;
-        sum = sum + v;
-        mn = (n == t || v < mn) ? v : mn;
-        mx = (n == t || v > mx) ? v : mx;
+        monitor_slot_take(v, n == t, sum, mn, mx);
     }
     xs[t] = sum; xmn[t] = mn; xmx[t] = mx;
-    __syncthreads();
-    for (int s = MON_THREADS / 2; s >= 1; s >>= 1) {
-        if (t < s) {
-            xs[t] = xs[t] + xs[t + s];
-            if (t + s < N) { // slots t >= N hold no ant (the slots with one are a prefix, before and after every fold)
-                xmn[t] = xmn[t + s] < xmn[t] ? xmn[t + s] : xmn[t];
-                xmx[t] = xmx[t + s] > xmx[t] ? xmx[t + s] : xmx[t];
-            }
-        }
-        __syncthreads();
-    }
+    monitor_fold3(xs, xmn, xmx, t, N); // slots t >= N hold no ant
     if (t == 0) {
         double *r = a.report + (size_t)e * 3;
         r[0] = xs[0]; r[1] = xmn[0]; r[2] = xmx[0];

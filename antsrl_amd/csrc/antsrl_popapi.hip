@@ -10,16 +10,21 @@
 //   rework agents   antsrl_pop_rework_collapse / antsrl_pop_policy_rework / _select /                antsrl_poprework.hip
 //                   antsrl_pop_reworktrain_sizes / _step (select without the fusion and record
 //                   are the linear agents')
+//   every kind      antsrl_pop_fitness (a member's episode reward off the monitor's block)           antsrl_popfitness.hip
+//                   antsrl_pop_exploit (members' rows over other members', one launch)               antsrl_checkpoint.hip
 //
 // Host-side only: validates every argument before any HIP call and enqueues on the caller's stream.  No handle, no
 // allocation, no synchronisation, no exceptions across the ABI.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "antsrl_adam.h"
+#include "antsrl_checkpoint.h" // EnvCopyTable: the exploit is k_env_copy's
 #include "antsrl_device.h"
 #include "antsrl_dqn.h"
 #include "antsrl_fail.h"
+#include "antsrl_launch.h" // antsrl_launch_env_copy
 #include "antsrl_loopapi.h"
 #include "antsrl_memnet.h"
 #include "antsrl_policy_flat.h"
@@ -737,4 +742,73 @@ extern "C" int antsrl_pop_reworktrain_step(const AntsPopSpec *s, const AntsRewor
     a.adam.m = adam_m; a.adam.v = adam_v;
     const PopRunningLoss rl = {running_loss, first_loss != 0};
     return enqueued(antsrl_launch_pop_reworktrain(a, t, s->n_members, (a.L.bytes + 255) / 256 * 256, rl, (hipStream_t)stream), who);
+}
+
+// ---- population-based training (antsrl_popfitness.hip, antsrl_checkpoint.hip) -----------------------------------------------
+
+extern "C" int antsrl_pop_fitness(const double *episode_reward, int n_envs, int n_ants, int n_members, double *row, void *stream)
+{
+    const char *who = "pop_fitness";
+    REQUIRE(episode_reward, 8);
+    REQUIRE(row, 8);
+    int rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    if (n_envs < 1 || n_ants < 1) return fail(ANTSRL_E_INVALID, "%s: n_envs and n_ants must be >= 1 (%d, %d)", who, n_envs, n_ants);
+    if (n_envs % n_members)
+        return fail(ANTSRL_E_INVALID, "%s: n_envs = %d is not a multiple of n_members = %d (members own equal shares)", who, n_envs,
+                    n_members);
+    const uintptr_t e0 = (uintptr_t)episode_reward, e1 = e0 + (uintptr_t)n_envs * (uintptr_t)n_ants * 8;
+    const uintptr_t r0 = (uintptr_t)row, r1 = r0 + (uintptr_t)n_members * 24;
+    if (r0 < e1 && e0 < r1) return fail(ANTSRL_E_INVALID, "%s: row overlaps episode_reward", who);
+    return enqueued(antsrl_launch_pop_fitness(episode_reward, n_envs / n_members, n_ants, n_members, row, (hipStream_t)stream), who);
+}
+
+// Every pair and every per-member array in ONE launch of k_env_copy: the fork's table (antsrl_checkpoint.h) with the
+// members as its rows and src == dst == base[a].  The kernel takes 16 bytes per lane where a pair's two rows are
+// congruent modulo 16, 4 bytes where modulo 4 only (a block of 9603 floats), single bytes otherwise, and touches no byte
+// outside a row.
+extern "C" int antsrl_pop_exploit(int n_arrays, void *const *base, const uint64_t *row_bytes, int n_members, int n_pairs,
+                                  const int32_t *src, const int32_t *dst, void *stream)
+{
+    const char *who = "pop_exploit";
+    if (n_arrays < 1 || n_arrays > ENV_COPY_MAX_ARRAYS)
+        return fail(ANTSRL_E_INVALID, "%s: n_arrays must be in [1, ENV_COPY_MAX_ARRAYS = %d] (%d)", who, ENV_COPY_MAX_ARRAYS, n_arrays);
+    if (n_pairs < 0 || n_pairs > ENV_COPY_MAX_PAIRS)
+        return fail(ANTSRL_E_INVALID, "%s: n_pairs must be in [0, ENV_COPY_MAX_PAIRS = %d] (%d)", who, ENV_COPY_MAX_PAIRS, n_pairs);
+    int rc = pop_n_members(who, n_members);
+    if (rc != ANTSRL_OK) return rc;
+    if (!base || !row_bytes) return fail(ANTSRL_E_INVALID, "%s: NULL base or row_bytes", who);
+    EnvCopyTable t;
+    memset(&t, 0, sizeof(t));
+    uint64_t chunks = 0;
+    for (int a = 0; a < n_arrays; ++a) {
+        if (row_bytes[a] == 0) return fail(ANTSRL_E_INVALID, "%s: row_bytes[%d] is 0", who, a);
+        if (!base[a]) return fail(ANTSRL_E_INVALID, "%s: base[%d] is NULL", who, a);
+        EnvCopyArray &e = t.a[a];
+        e.src = e.dst = (unsigned char *)base[a];
+        e.bytes = row_bytes[a];
+        e.first_chunk = (uint32_t)chunks;
+        chunks += env_copy_chunks(e.bytes);
+        if (chunks > 0x7fffffffull) return fail(ANTSRL_E_UNSUPPORTED, "%s: the rows are too large for one copy", who);
+    }
+    if (n_pairs == 0) return ANTSRL_OK; // nothing to copy: no launch
+    if (!src || !dst) return fail(ANTSRL_E_INVALID, "%s: NULL src or dst", who);
+    static_assert(ANTSRL_POP_MAX <= 64, "a member set is one 64-bit word");
+    uint64_t is_dst = 0;
+    for (int i = 0; i < n_pairs; ++i) { // (stops at the first repeated dst: at most n_members + 1 entries are read)
+        if (src[i] < 0 || src[i] >= n_members) return fail(ANTSRL_E_INVALID, "%s: src[%d] = %d is not in [0, %d)", who, i, src[i], n_members);
+        if (dst[i] < 0 || dst[i] >= n_members) return fail(ANTSRL_E_INVALID, "%s: dst[%d] = %d is not in [0, %d)", who, i, dst[i], n_members);
+        if (is_dst >> dst[i] & 1u) return fail(ANTSRL_E_INVALID, "%s: dst %d appears twice (dst[%d])", who, dst[i], i);
+        is_dst |= 1ull << dst[i];
+    }
+    for (int i = 0; i < n_pairs; ++i)
+        if (is_dst >> src[i] & 1u) return fail(ANTSRL_E_INVALID, "%s: member %d is a src (src[%d]) and a dst", who, src[i], i);
+    t.n_arrays = n_arrays;
+    t.rows = n_pairs;
+    t.chunks_per_row = (uint32_t)chunks;
+    for (int i = 0; i < n_pairs; ++i) {
+        t.pair_src[i] = (uint16_t)src[i];
+        t.pair_dst[i] = (uint16_t)dst[i];
+    }
+    return enqueued(antsrl_launch_env_copy(t, (hipStream_t)stream), who);
 }

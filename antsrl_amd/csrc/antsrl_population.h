@@ -164,6 +164,18 @@ ANTSRL_INTERNAL hipError_t antsrl_launch_pop_rework_act(const PopReworkActArgs &
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_reworktrain(const ReworkTrainArgs &a, const PopTable &t, int P, size_t ws_stride,
                                                          const PopRunningLoss &rl, hipStream_t st);
 
+// ---- population-based training (antsrl_popfitness.hip; include/antsrl.h, "Population-based training") ----
+// row[p] = {total, min, max} of member p's environments [p Em, (p + 1) Em) of episode_reward (double [P Em][N], the
+// monitor block's, read only): grid P, one workgroup of MON_THREADS = 256 per member.  THE ORDER OF THE SUMS is the
+// monitor's (antsrl_monitor.h), every add a float64 add:
+//     an environment's total:  the total[e] rule: slot t starts at +0.0 and adds ants t, t + 256, ... ascending; the 256
+//                              slots are folded with x[i] += x[i + s] for i < s, s = 128, 64, ..., 1.
+//     the member's total:      the same rule over its Em environment totals: slot t takes environments t, t + 256, ... of
+//                              the member.
+//     min / max:               of the environments' totals; order-free.
+// (The exploit is antsrl_launch_env_copy's table, antsrl_checkpoint.h: no kernel of its own.)
+ANTSRL_INTERNAL hipError_t antsrl_launch_pop_fitness(const double *episode_reward, int Em, int N, int P, double *row, hipStream_t st);
+
 // ---- the population of linear agents ----
 // a: the single agent's SelArgs for member 0 (M = Mm); Em environments per member.  The table gives seed and epsilon.
 ANTSRL_INTERNAL hipError_t antsrl_launch_pop_policy(const PopPolicyArgs &a, bool obs_bf16, hipStream_t st);

@@ -16,6 +16,9 @@ the device every so many steps and read back once, with the monitor's log.
 seed, epsilon, discount and learning rate on one handle, per-member rewards, running losses and epsilon schedules.  It
 drives a PopulationExploreAgent unchanged, and `train_population_curriculum` runs the curriculum's two stages for every
 member on one handle: the explore population, the hand-over of layer1 on the device, the collect population.
+With `pbt=PbtConfig(...)` it is population-based training (antsrl_amd/pbt.py): after a generation's last episode the
+members are ranked on the device's fitness row, winners are copied over losers in one launch and the losers' learning
+rates and discounts are perturbed; one row read per generation is all the host reads.
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from typing import Optional
 import numpy as np
 
 from . import config as cm
+from . import pbt as _pbt
 from .monitor import EpisodeMonitor
 from .recorder import EpisodeRecorder
 from .render import EpisodeRenderer
@@ -48,7 +52,7 @@ def episode_seed(cfg, gen, seed: int, episode: int) -> int:
 
 def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0, training: bool = True, min_epsilon=0.01,
                      max_epsilon=1.0, monitor: Optional[EpisodeMonitor] = None, report_every: int = 50,
-                     save_as: Optional[str] = None) -> dict:
+                     save_as: Optional[str] = None, pbt: Optional["_pbt.PbtConfig"] = None) -> dict:
     """train_episodes' loop for a population (antsrl_amd/population.py: PopulationAgent, PopulationExploreAgent,
     PopulationJointAgent, and PopulationMemoryAgent and PopulationReworkAgent, which it drives as they are: the loop reads a population's n_members,
     trainer, epsilon, setup, initialize, rollout_step and save_model and nothing of its net) on `env`, whose
@@ -64,7 +68,18 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
 
     Returns the monitor's log() with `member_total` and `member_reward` (float64 [episodes, P]: the sum and the mean per
     ant of the member's environments at the episode's last report, 0 without one), `member_loss` (float64 [episodes, P],
-    nan while the population has not trained), `epsilons` ([episodes, P]: what each episode ran with) and `monitor`."""
+    nan while the population has not trained), `epsilons` ([episodes, P]: what each episode ran with) and `monitor`.
+
+    pbt: a PbtConfig (antsrl_amd/pbt.py) turns the fixed sweep into population-based training.  None: nothing of it is
+    constructed, launched or read.  With a config, after the last step of every generation_every-th episode and before
+    the monitor's end_episode (which zeroes episode_reward): a PopulationFitness row is recorded (antsrl_pop_fitness),
+    that ONE row is read back, pbt_plan ranks the members on their totals, pop.exploit copies every winner over its loser
+    in one launch (with the ring slab when pbt.ring), and the losers' perturbed learning rates and discounts are
+    assigned to pop.trainer.lr / .discount in place.  The read of the row is the one host synchronisation per
+    generation: the hyper-parameters travel by value from the host in every launch, so the host has to know who inherited
+    what.  The epsilon schedule, the target counter and Adam's step count are common to the members and not touched.
+    The log then has `pbt`: dict(fitness [G, P, 3], src_of [G, P], lr and discount [G + 1, P] (row 0: the start),
+    generation_episode [G])."""
     import torch
     env = getattr(env, "_backend", env)
     P = pop.n_members
@@ -75,10 +90,16 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
                                                              max_episodes=max(1, episodes))
     loss_log = torch.full((max(1, episodes), P), float("nan"), dtype=torch.float64, device=env.device)
     epsilons, first_episode = [], mon.episode  # (a continued monitor counts its earlier episodes)
+    fitness = rng = gens = None  # population-based training: made once the population is set up
     for episode in range(episodes):
         env.generate(gen, episode_seed(env.cfg, gen, seed, episode))
         if pop.trainer is None:
             pop.setup(env)
+        if pbt is not None and fitness is None:
+            fitness = _pbt.PopulationFitness(pop, max_rows=max(1, episodes // pbt.generation_every))
+            rng = np.random.default_rng(pbt.seed)
+            gens = dict(fitness=[], src_of=[], generation_episode=[],
+                        lr=[pop.trainer.lr.copy()], discount=[pop.trainer.discount.copy()])  # row 0: the start
         pop.initialize(env)
         env.observe()
         epsilons.append(pop.epsilon.copy())
@@ -87,6 +108,16 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
             mon.step(env.reward, None)
         if training and pop.trainer.step_count > 0:
             loss_log[episode].copy_(pop.trainer.running_loss)
+        if pbt is not None and (episode + 1) % pbt.generation_every == 0:
+            tr = pop.trainer
+            row = fitness.row(fitness.record(mon))  # the generation's one host synchronisation
+            src_of, lr, discount = _pbt.pbt_plan(row[:, 0], tr.lr, tr.discount, quantile=pbt.quantile, factors=pbt.factors,
+                                                 lr_bounds=pbt.lr_bounds, gap_bounds=pbt.gap_bounds, rng=rng)
+            dst = np.nonzero(src_of != np.arange(P))[0]
+            pop.exploit(src_of[dst], dst, pbt.ring)
+            tr.lr[:], tr.discount[:] = lr, discount
+            for k, v in dict(fitness=row, src_of=src_of, lr=lr, discount=discount, generation_episode=episode).items():
+                gens[k].append(v)
         mon.end_episode()
         pop.epsilon = [epsilon_schedule(episode, float(lo[p]), float(hi[p])) for p in range(P)]
     if save_as is not None and training:
@@ -101,6 +132,13 @@ def train_population(pop, env, gen, episodes: int, steps: int, *, seed: int = 0,
             total[episode] = log["reports"][at[-1], :, 0].reshape(P, E // P).sum(axis=1)
     log.update(member_total=total, member_reward=total / float(E // P * N), member_loss=loss_log[:episodes].cpu().numpy(),
                epsilons=np.array(epsilons).reshape(episodes, P), monitor=mon)
+    if pbt is not None:
+        gens = gens or dict(fitness=[], src_of=[], generation_episode=[], lr=[], discount=[])  # (a run of no episode)
+        log["pbt"] = dict(fitness=np.array(gens["fitness"], dtype=np.float64).reshape(-1, P, 3),
+                          src_of=np.array(gens["src_of"], dtype=np.int64).reshape(-1, P),
+                          lr=np.array(gens["lr"], dtype=np.float64).reshape(-1, P),
+                          discount=np.array(gens["discount"], dtype=np.float64).reshape(-1, P),
+                          generation_episode=np.array(gens["generation_episode"], dtype=np.int64))
     return log
 
 

@@ -41,7 +41,8 @@ What is stated once:
     _PopulationFlatTrainer  under the explore, the joint and the rework trainer, train._FlatTrainer's counterpart: a member's net is
                             one flat block; the name table, `_sizes`, `_views`, `adam_state`, Adam's tensor, `grads`, `_entry`.
     _Population             the members' host values, the front of setup, the step's one AntsPopSpec, `get_action`, the
-                            ring, train, the fused loop, the per-member files and `copy_member`.  An agent names its
+                            ring, train, the fused loop, the per-member files, `exploit` (every pair and per-member array
+                            in one launch, antsrl_pop_exploit; antsrl_amd/pbt.py) and `copy_member`.  An agent names its
                             trainer class and launches its acting net (`_policy`); the memory agent also has its own
                             select and hands its new memory out behind the actions.
 
@@ -799,15 +800,42 @@ class _Population(_LoopAgent):
         """(tensor, the dimension that counts the members) for every per-member tensor of the trainer."""
         raise NotImplementedError
 
+    def _member_arrays(self, ring: bool) -> list:
+        """[(address, bytes of a member's row)] of every per-member array, members outermost: what `_member_tensors`
+        lists (a tensor whose member dimension is 1, `_adam` [2][P][...], as one array per leading index) and, with
+        `ring`, the ring's seven arrays."""
+        out = []
+        for t, dim in self._member_tensors() + (tuple((a, 0) for a in ring_arrays(self.replay_memory)) if ring else ()):
+            assert t.is_contiguous() and dim in (0, 1) and t.shape[dim] == self.n_members, (tuple(t.shape), dim)
+            for part in ((t,) if dim == 0 else t.unbind(0)):
+                out.append((part.data_ptr(), part[0].numel() * part.element_size()))
+        return out
+
+    def exploit(self, src: Sequence[int], dst: Sequence[int], ring: bool = True) -> None:
+        """The exploit step of population-based training: for every pair i, member src[i]'s weights, target, Adam
+        moments, what else `_member_tensors` lists and, with `ring`, ring slab over member dst[i]'s, all pairs and all
+        arrays in ONE launch (antsrl_pop_exploit).  A src may repeat; a dst may neither repeat nor be a src.  The
+        hyper-parameters, seeds and epsilons stay where they are.  No host synchronisation."""
+        src, dst = [int(v) for v in src], [int(v) for v in dst]
+        assert len(src) == len(dst), "one dst per src (%d, %d)" % (len(src), len(dst))
+        if not src:
+            return
+        arrays = self._member_arrays(ring)
+        n = len(arrays)
+        base = (C.c_void_p * n)(*[a for a, _ in arrays])
+        row_bytes = (C.c_uint64 * n)(*[b for _, b in arrays])
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.antsrl_pop_exploit(n, base, row_bytes, self.n_members, len(src), (C.c_int32 * len(src))(*src),
+                                                    (C.c_int32 * len(dst))(*dst), _lib.stream(self.device)), "pop_exploit")
+
     def copy_member(self, src: int, dst: int, ring: bool = True) -> None:
-        """Member src's weights, target, Adam moments and, with `ring`, ring slab over member dst's: with env.fork the
-        exploit step of population-based training.  The hyper-parameters stay dst's own."""
+        """Member src's weights, target, Adam moments and, with `ring`, ring slab over member dst's: `exploit` of one
+        pair; with env.fork the exploit step of population-based training.  The hyper-parameters stay dst's own."""
         P = self.n_members
         assert 0 <= src < P and 0 <= dst < P, (src, dst)
         if src == dst:
             return
-        for t, dim in self._member_tensors() + (tuple((a, 0) for a in ring_arrays(self.replay_memory)) if ring else ()):
-            t.select(dim, dst).copy_(t.select(dim, src))
+        self.exploit([src], [dst], ring)
 
 
 class PopulationAgent(_Population):
@@ -982,20 +1010,13 @@ class PopulationMemoryAgent(_Population):
         return dict(super()._record_kw(), shape=self.trainer.shape)
 
     def _member_tensors(self) -> tuple:
+        """A state block holds the weights AND Adam's moments; the acting pack goes with the target; and a member's rows
+        of BOTH memory halves ([P Mm][mem], seen as [P][Mm][mem]).  env.fork copies src's ants into dst's environments; a
+        fork without their memory would hand dst's memory, which belongs to the ants that were there before, to src's
+        ants.  So copy_member and exploit go with the fork, between two steps."""
         tr = self.trainer
-        return ((tr._model, 0), (tr._target, 0), (tr.packed, 0))
-
-    def copy_member(self, src: int, dst: int, ring: bool = True) -> None:
-        """_Population.copy_member (a state block holds the weights AND Adam's moments; the acting pack goes with the
-        target), and member src's rows of BOTH memory halves over dst's.  env.fork copies src's ants into dst's
-        environments; a fork without their memory would hand dst's memory, which belongs to the ants that were there
-        before, to src's ants.  Call it with the fork, between two steps."""
-        super().copy_member(src, dst, ring)
-        if src == dst:
-            return
-        Mm = self.g.Mm
-        for m in self._mem:
-            m[dst * Mm:(dst + 1) * Mm].copy_(m[src * Mm:(src + 1) * Mm])
+        halves = tuple((m.view(self.n_members, self.g.Mm, self.mem_size), 0) for m in self._mem)
+        return ((tr._model, 0), (tr._target, 0), (tr.packed, 0)) + halves
 
 
 class PopulationReworkAgent(_Population):

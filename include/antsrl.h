@@ -1742,6 +1742,42 @@ int antsrl_pop_reworktrain_step(const AntsPopSpec *s, const AntsReworkShape *sha
                                 int64_t B, int64_t step, double beta1, double beta2, double eps, float *grads, float *loss,
                                 double *running_loss, int first_loss, void *workspace, void *stream);
 
+/* Population-based training: what a loop that ranks the members of any of the five populations, copies a winner over a
+ * loser and perturbs the loser's hyper-parameters needs of the device (antsrl_amd/pbt.py holds the loop's host side;
+ * DESIGN 7.35).  Both entries validate every argument on the host before any HIP call and enqueue ONE launch on the
+ * caller's stream; neither allocates or synchronises.
+ *
+ * antsrl_pop_fitness: row[p] = {total, min, max} of member p's episode reward, p = 0 .. n_members - 1 (double
+ * [n_members][3]).  episode_reward is the monitor block's double [n_envs][n_ants] ("The training monitor"); it is read,
+ * never written.  Member p owns environments [p Em, (p + 1) Em), Em = n_envs / n_members.  `total` is over the member's
+ * ants; min and max are over its environments' totals.  One workgroup of 256 per member, grid n_members.
+ * THE ORDER OF THE SUMS is the monitor's (antsrl_monitor.h), every add a float64 add, round to nearest even:
+ *     an environment's total:  the total[e] rule: slot t starts at +0.0 and adds episode_reward[e][n] for n = t, t + 256,
+ *                              t + 512, ... ascending; the 256 slots are folded with x[i] += x[i + s] for i < s,
+ *                              s = 128, 64, ..., 1; total = x[0].
+ *     the member's total:      the same rule over its Em environment totals: slot t takes environments t, t + 256, ...
+ *                              of the member.
+ *     min / max:               order-free.
+ * So a member's total is reproducible bit for bit, and it equals the grand_total rule applied to the member's
+ * environments of a monitor's report taken at the same step.  Nothing here is float32.
+ * ANTSRL_E_INVALID, each with its own message: a NULL or not 8-byte aligned episode_reward or row; n_members outside
+ * [1, ANTSRL_POP_MAX]; n_envs < 1 or n_ants < 1; n_envs no multiple of n_members; row overlapping episode_reward.
+ *
+ * antsrl_pop_exploit: array a (a = 0 .. n_arrays - 1) is [n_members] rows of row_bytes[a] bytes at base[a], members
+ * outermost; for every pair i, row src[i] of EVERY array is copied over row dst[i].  One launch of the table-driven copy
+ * behind antsrl_fork_envs whatever n_arrays and n_pairs are: 16 bytes per lane where a pair's two rows are congruent
+ * modulo 16, 4 bytes where they are congruent modulo 4 only (a member's block of 9603 floats), single bytes otherwise;
+ * no byte outside a destination row is written and none outside a source row is read.  base and row_bytes are host
+ * arrays; src and dst are host arrays too.  A src may repeat (one winner over several losers).  The arrays must not
+ * overlap each other (not checked).
+ * ANTSRL_E_INVALID, each with its own message: n_arrays outside [1, 40]; n_pairs outside [0, 640] (n_pairs == 0 returns
+ * ANTSRL_OK and launches nothing); n_members outside [1, ANTSRL_POP_MAX]; NULL base or row_bytes; a row_bytes of 0; a
+ * NULL base[a]; NULL src or dst; an index outside [0, n_members); a dst that repeats; a dst that is also a src (so no
+ * row is read and written in one launch). */
+int antsrl_pop_fitness(const double *episode_reward, int n_envs, int n_ants, int n_members, double *row, void *stream);
+int antsrl_pop_exploit(int n_arrays, void *const *base, const uint64_t *row_bytes, int n_members, int n_pairs,
+                       const int32_t *src, const int32_t *dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
